@@ -35,6 +35,12 @@ have gone by; protocol version 3 -- version 2 reported the LAST pass, which depe
 interleavings of the frames in flight the pass cap fell on); `converged` says whether the last two passes agreed within
 1 %, `pass_spread` is (max - min) / median over the same passes; every pass is listed in `passes`, the first one -- from
 the idle GPU -- also as `cold_start`.  `--single-pass` runs one pass and reports that.
+
+`--dump-outputs DIR` writes, on rank 0, the frames of the last timed step (of the last pass) as DIR/<name>.npy in
+float32 (uint8 frames converted exactly): this rank's views as `rgb` / `rgb8` [V,H,W,3] and, with more than one rank,
+`rgb8_gathered`, the frames every rank sent.  Scene, cameras and poses are seeded, so two builds given the same
+arguments can be compared file for file.  Outputs above 64 MB in all are cut to one seeded sample of pixel positions,
+the same for every array (listed in DIR/pixel_index.npy); each array is then [V,P,3].
 """
 from __future__ import annotations
 
@@ -116,6 +122,28 @@ def cpu_baseline(scene, cam, budget_s=20.0):
     return {"value": 1.0 / med, "unit": "frames/s", "cores": threads, "kind": "port",
             "sample": f"{len(times)} full frames of the same workload after 1 warm-up (median), C oracle with "
                       f"OpenMP on {threads} threads of {os.cpu_count()} host CPUs"}
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, outputs, budget=DUMP_BYTES):
+    """Write each [V,H,W,C] CPU tensor of ``outputs`` as path/<name>.npy in float32 (module docstring).  When they
+    would take more than ``budget`` bytes, every array keeps the same seeded sample of the H*W pixel positions."""
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    arrays = {k: v.numpy().astype(np.float32) for k, v in outputs.items()}
+    index = path / "pixel_index.npy"
+    index.unlink(missing_ok=True)   # (a sample of an earlier run must not describe full arrays)
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        H, W = next(iter(arrays.values())).shape[1:3]
+        per_pixel = sum(a.shape[0] * a.shape[3] * 4 for a in arrays.values()) + 8   # + the position, float64
+        n = (budget - 128 * (len(arrays) + 1)) // per_pixel                          # (128: an .npy header)
+        pix = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+        arrays = {k: a.reshape(a.shape[0], H * W, a.shape[3])[:, pix] for k, a in arrays.items()}
+        np.save(index, pix.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(path / f"{k}.npy", a)
 
 
 def workload(cfg, rank, world, views_per_step, n_gaussians, with_scene=True):
@@ -230,10 +258,15 @@ def main():
                     help="config 3: independent views each GPU renders per step; 2 = a view pair (one projection pass for both)")
     ap.add_argument("--single-pass", action="store_true", help="one W + K pass from the idle GPU (no second, clock-ramped pass)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: a stand-in renderer over gloo (launch / shard / gather path only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frames of the last timed step to DIR/<name>.npy (module docstring)")
     a = ap.parse_args()
 
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if a.dry_run and a.dump_outputs:
+        raise SystemExit("--dump-outputs writes the renderer's frames: it does not go with --dry-run")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # no launcher: start the ranks ourselves, BEFORE this process touches a GPU (a child process, not an exec)
         raise SystemExit(self_launch(a.gpus, sys.argv[1:], a.dry_run))
@@ -334,6 +367,13 @@ def main():
     post_ramp = [t for k, t in enumerate(pass_times) if sum(pass_times[:k]) >= 0.030] or [pass_times[-1]]
     elapsed = float(np.median(post_ramp))
     pass_spread = (max(post_ramp) - min(post_ramp)) / elapsed
+
+    if rank == 0 and a.dump_outputs:
+        # the last timed step's frames (the last pass ran; run() completed them), before the renders below reuse bufs[0]
+        outs = {k: v[:V].cpu() for k, v in pipe.buffer_of(a.steps - 1).items()}
+        if world > 1 and keep["frames"] is not None:
+            outs["rgb8_gathered"] = torch.cat([f.cpu() for f in keep["frames"]])
+        dump_outputs(a.dump_outputs, outs)
 
     gather_check = None
     if rank == 0 and world > 1 and keep["frames"] is not None:

@@ -221,3 +221,40 @@ def test_bench_gather_with_a_world_that_does_not_divide_the_views():
     rc, line, err = _bench(["--gpus", "3", "--dry-run", "--config", "4", "--steps", "3", "--warmup", "1"])
     assert rc == 0, err[-2000:]
     assert line["n_gpus"] == 3 and line["gather_ok"] and line["config"]["views_per_step"] == 8
+
+
+def test_bench_dump_outputs_full_arrays_and_one_seeded_sample_above_64mb(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files of a step's frames; two 1080p views of rgb + rgb8 (100 MB as float32) are cut
+    to one seeded sample of pixel positions, shared by every array, the same in every run and within 64 MB in all."""
+    import importlib.util
+    from pathlib import Path
+    spec = importlib.util.spec_from_file_location("bench", Path(__file__).resolve().parent.parent / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(1)
+
+    def frames(H, W):
+        return {"rgb": torch.from_numpy(rng.random((2, H, W, 3), dtype=np.float32)),
+                "rgb8": torch.from_numpy(rng.integers(0, 256, (2, H, W, 3), dtype=np.uint8))}
+
+    H, W = 1080, 1920
+    big = frames(H, W)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, big)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["pixel_index.npy", "rgb.npy", "rgb8.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64_000_000
+    pix = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert pix.dtype == np.float64 and np.array_equal(pix, np.load(tmp_path / "b" / "pixel_index.npy"))
+    pix = pix.astype(np.int64)
+    assert len(np.unique(pix)) == len(pix) > H * W // 2 and pix.min() >= 0 and pix.max() < H * W
+    for k, v in big.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == np.float32 and got.shape == (2, len(pix), 3)
+        assert np.array_equal(got, v.numpy().reshape(2, H * W, 3)[:, pix].astype(np.float32))
+        assert np.array_equal(got, np.load(tmp_path / "b" / f"{k}.npy"))
+    small = frames(4, 6)                                  # under the budget: whole arrays, and no stale sample beside them
+    bench.dump_outputs(tmp_path / "a", small)
+    assert not (tmp_path / "a" / "pixel_index.npy").exists()
+    for k, v in small.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.numpy().astype(np.float32))

@@ -52,3 +52,38 @@ def test_bench_line_schema_at_the_drivers_command_shape():
     # every output of Door A, pipelined (rgb + accumulation + depth with the fill): not slower than the blocking form
     assert d["door_a_async"]["value"] >= 0.95 * d["door_a_sync"]["value"] and d["door_a_async"]["frames"] >= 50
     assert "door_a_async" in d["config"]["workload"]                    # the line says what `value` does not write
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_frames_of_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` at the metric's config: the dumped sample of the last timed step's two views equals a blocking render of
+    the same seeded scene and cameras (bench.workload), bit for bit, float32 RGB and uint8 RGB."""
+    import importlib.util
+
+    import numpy as np
+    from sim_a_splat_amd.rasterizer import Rasterizer
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "SAS_DIST_BACKEND", "SAS_FORCE_DEVICE"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                        "--no-extras", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])["steps"] == 3
+    assert sorted(f.name for f in tmp_path.iterdir()) == ["pixel_index.npy", "rgb.npy", "rgb8.npy"]
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64_000_000
+    spec = importlib.util.spec_from_file_location("bench", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    scene, cams, want, _, _, _, _ = bench.workload(3, 0, 1, 2, 1_000_000)
+    pix = np.load(tmp_path / "pixel_index.npy").astype(np.int64)
+    r = Rasterizer(0)
+    try:
+        r.upload(scene.means, scene.opacities, scene.sh, quats=scene.quats, scales=scene.scales, sh_degree=3)
+        out = r.render_batch(np.stack([c.viewmat for c in cams]), np.stack([c.K for c in cams]), cams[0].width, cams[0].height,
+                             bench.BG, want=want)
+        for k in want:
+            got = np.load(tmp_path / f"{k}.npy")
+            ref = out[k].cpu().numpy().reshape(len(cams), -1, 3)[:, pix].astype(np.float32)
+            assert got.dtype == np.float32 and np.array_equal(got, ref), k
+    finally:
+        r.close()
