@@ -176,6 +176,30 @@ int sas_render_rgbd(sas_ctx *ctx, const float viewmat[16], const float K[9], int
                     float *depth, float *points, uint8_t *mask, void *stream);
 
 /*
+ * Per-Gaussian feature channels, composited through exactly the frame's own weights.  Serves Door A's
+ * get_outputs_for_camera(..., compute_semantics) (ns_utils/nerfstudio_utils.py:123, :166-172) for feature-splat models, whose
+ * per-Gaussian vectors (the point-cloud helpers' clip_embeds, :343-402) are alpha-blended as the colours are, and the per-link
+ * splat groups of the segmentation step (splat_handler.py:62-83) as masks: one-hot group features.
+ * sas_scene_features, after sas_scene_upload (a new upload forgets the features, as it forgets the link constants):
+ *   features  [n,channels] float32, host or device, the caller's Gaussian order, 1 <= channels <= 256; NaN becomes -FLT_MAX and
+ *             +-Inf +-FLT_MAX (the colours' finite mapping); NULL: one-hot of the scene's group ids, channels == n_groups
+ *   SAS_ERR_NO_SCENE without a scene; SAS_ERR_INVALID when n is not the scene's, channels is out of range, or one-hot is
+ *   asked of a scene without groups.  Returns when the store is in place (frames in flight are completed first).
+ * sas_render_features: sas_render's frame (rgb / alpha / depth bit-identical to it; SAS_FULL_SORT is implied: the channels are
+ *   composited from the complete tile lists) plus
+ *   features  [H,W,channels] f32 device, required:  F[p,k] = sum_i vis_i f[i,k] (front to back) + (1 - alpha_p) fbg[k]
+ *             with the weights vis_i of the frame's own compositing; NOT clamped.  For features in [0,1], clamp(F[..,3j:3j+3],
+ *             0, 1) is bit-identical to the rgb of the scene recoloured with those three channels (sh_degree < 0, fbg = bg)
+ *   feature_background [channels] host array, or NULL (zeros)
+ *   Flags as sas_render (SAS_ASYNC, SAS_FAST_EXP, SAS_DEPTH_FILL_MAX, SAS_TIMING).  SAS_ERR_INVALID when no features are set
+ *   for the current scene or `features` is NULL.
+ */
+int sas_scene_features(sas_ctx *ctx, int64_t n, int channels, const float *features);
+int sas_render_features(sas_ctx *ctx, const float *viewmat, const float *K, int width, int height, const float *background,
+                        const float *feature_background, unsigned flags, float *rgb, float *alpha, float *depth,
+                        float *features, void *stream);
+
+/*
  * Render n_views views of the same size in one call.  Serves the per-camera loops of
  * SplatHandler.render / SplatEnvWrapper.render (splat_handler.py:337-345, splat_env_wrapper.py:147-158).
  *   viewmats [n_views,16], Ks [n_views,9] host arrays; outputs are [n_views,H,W,...] device arrays

@@ -39,6 +39,9 @@ struct RenderArgs {
     bool order_caller = true;  // the frame writes device buffers of the caller: it runs behind what the caller's stream holds, and the
                                // caller's stream is ordered behind it (false: frames delivered to host memory, sas_render_batch_host)
     bool solo = false;         // a blocking call for this one view with nothing else in flight: the caller waits for the frame's chain
+    float *features = nullptr; // sas_render_features: [H,W,feat_c] (device), composited behind the frame's k_blend
+    int feat_c = 0;
+    float fbg[SAS_MAX_FEATURES];   // feature background, [feat_c]
     bool valid = false;
 };
 
@@ -106,6 +109,9 @@ struct sas_ctx {
     std::string err;
     // scene
     DevBuf g0, g1, g2, col, gid8, perm;
+    DevBuf feat;         // feature store (sas_scene_features): [chunks][n_pad][SAS_FEAT_K], slot order
+    int feat_c = 0;      // its channels; has_feat: set for the current scene (an upload forgets it)
+    bool has_feat = false;
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
     // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
     // the call returns: nothing is remembered across calls)
@@ -527,9 +533,22 @@ int enqueue_frame(sas_ctx *c, Slot &sl, int role = ROLE_SINGLE, Slot *partner = 
     if (timing) HIP_TRY(c, hipEventRecord(sl.ev[4], st));
     const bool fill = a.depth && (a.flags & SAS_DEPTH_FILL_MAX);
     const bool quad = sl.quad;   // (prepare_frame; never for SAS_FULL_SORT frames)
-    if (full) sas_launch_blend(st, c->scene, tiles, P, f, (a.flags & SAS_FAST_EXP) != 0, fill);
-    else sas_launch_tiles_lazy(st, c->scene, tiles, P, f, (a.flags & SAS_FAST_EXP) != 0, fill, quad,
-                               ttiles ? sl.ev[4] : nullptr, ttiles ? sl.ev[5] : nullptr);
+    if (full) {
+        sas_launch_blend(st, c->scene, tiles, P, f, (a.flags & SAS_FAST_EXP) != 0, fill);
+        if (a.features) {   // a feature frame (sas_render_features): the same lists and records once more, per chunk of channels
+            SasFeatures F{};
+            F.store = (const float *)c->feat.p;
+            F.out = a.features;
+            F.n_pad = c->scene.n_pad;
+            F.C = a.feat_c;
+            F.chunks = sas_feature_chunks(a.feat_c);
+            memcpy(F.bg, a.fbg, sizeof(float) * (size_t)a.feat_c);
+            sas_launch_blend_features(st, c->scene, tiles, P, f, F, (a.flags & SAS_FAST_EXP) != 0);
+        }
+    } else {
+        sas_launch_tiles_lazy(st, c->scene, tiles, P, f, (a.flags & SAS_FAST_EXP) != 0, fill, quad,
+                              ttiles ? sl.ev[4] : nullptr, ttiles ? sl.ev[5] : nullptr);
+    }
     if (timing) HIP_TRY(c, hipEventRecord(sl.ev[5], st));
     const bool pts = a.depth && (a.points || a.mask);
     if (fill || pts) sas_launch_depth_tail(st, tiles, P, f, fill, pts);
@@ -807,7 +826,7 @@ int sas_destroy(sas_ctx *c)
                           &sl.scr.wgvis, &sl.scr.wgbase, &sl.scr.tilemax})
             release(*b);
     }
-    for (DevBuf *b : {&c->g0, &c->g1, &c->g2, &c->col, &c->gid8, &c->perm, &c->host_stage}) release(*b);
+    for (DevBuf *b : {&c->g0, &c->g1, &c->g2, &c->col, &c->gid8, &c->perm, &c->host_stage, &c->feat}) release(*b);
     delete c;
     return SAS_OK;
 }
@@ -832,6 +851,7 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
         if (rcw) return rcw;
     }
     c->has_scene = false;
+    c->has_feat = false;
 
     const int deg = sh_degree < 0 ? -1 : sh_degree;
     const int coeff_floats = deg < 0 ? 3 : 3 * (deg + 1) * (deg + 1);
@@ -1129,6 +1149,9 @@ struct ViewCall {
     uint8_t *mask;
     uint8_t *rgb8_host = nullptr;
     const float *poses = nullptr;   // [n_groups,12] group poses of THIS view (a pose set), or nullptr: the context's current poses
+    float *features = nullptr;      // sas_render_features: [H,W,feat_c] device output, feature background fbg [feat_c] (nullptr: 0)
+    const float *fbg = nullptr;
+    int feat_c = 0;
 };
 
 static int check_view(sas_ctx *c, const ViewCall &v, int width, int height)
@@ -1147,7 +1170,7 @@ static void fill_args(RenderArgs &a, const ViewCall &v, int width, int height, c
 {
     a.solo = solo;
     // rgb8 beside rgb8_host is the context's own staging frame (sas_render_batch_host): nothing of the caller's on the device
-    a.order_caller = v.rgb || v.alpha || v.depth || v.points || v.mask || (v.rgb8 && !v.rgb8_host);
+    a.order_caller = v.rgb || v.alpha || v.depth || v.points || v.mask || v.features || (v.rgb8 && !v.rgb8_host);
     memcpy(a.viewmat, v.viewmat, sizeof(a.viewmat));
     memcpy(a.K, v.K, sizeof(a.K));
     for (int k = 0; k < 3; ++k) a.bg[k] = background ? background[k] : 0.0f;
@@ -1155,6 +1178,9 @@ static void fill_args(RenderArgs &a, const ViewCall &v, int width, int height, c
     a.rgb = v.rgb; a.alpha = v.alpha; a.depth = v.depth; a.rgb8 = v.rgb8;
     a.points = v.points; a.mask = v.mask;
     a.rgb8_host = v.rgb8_host;
+    a.features = v.features;
+    a.feat_c = v.features ? v.feat_c : 0;
+    for (int k = 0; k < a.feat_c; ++k) a.fbg[k] = v.fbg ? v.fbg[k] : 0.0f;
     a.use_max_depth = max_depth != nullptr;
     a.max_depth = max_depth ? *max_depth : 0.0f;
     a.stream = st;
@@ -1239,6 +1265,69 @@ int sas_render(sas_ctx *c, const float *viewmat, const float *K, int width, int 
 {
     return render_impl(c, viewmat, K, width, height, background, flags, rgb, alpha, depth, rgb8, nullptr, nullptr,
                        nullptr, stream);
+}
+
+int sas_scene_features(sas_ctx *c, int64_t n, int channels, const float *features)
+{
+    if (!c) return SAS_ERR_INVALID;
+    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_features before sas_scene_upload");
+    if (n != c->scene.n) return fail(c, SAS_ERR_INVALID, "features for %lld Gaussians, the scene has %lld", (long long)n, (long long)c->scene.n);
+    if (channels < 1 || channels > SAS_MAX_FEATURES) return fail(c, SAS_ERR_INVALID, "channels %d out of [1,%d]", channels, SAS_MAX_FEATURES);
+    if (!features && c->scene.n_groups <= 0) return fail(c, SAS_ERR_INVALID, "one-hot group features need a scene with splat groups");
+    if (!features && channels != c->scene.n_groups)
+        return fail(c, SAS_ERR_INVALID, "one-hot group features have n_groups=%d channels, got %d", c->scene.n_groups, channels);
+    HIP_TRY(c, hipSetDevice(c->device));
+    {
+        const int rcw = complete_all(c);   // frames in flight read the store
+        if (rcw) return rcw;
+    }
+    c->has_feat = false;
+    const int64_t n_pad = c->scene.n_pad;
+    const size_t np = (size_t)(n_pad > 0 ? n_pad : 64);
+    int rc;
+    if ((rc = ensure(c, c->feat, sizeof(float) * SAS_FEAT_K * (size_t)sas_feature_chunks(channels) * np))) return rc;
+    // the caller's array: read in place when it is device memory of this context's device, else staged (host memory)
+    const float *src = nullptr;
+    DevBuf s_src;
+    if (features && n > 0) {
+        hipPointerAttribute_t at{};
+        const bool on_device = hipPointerGetAttributes(&at, features) == hipSuccess && at.type == hipMemoryTypeDevice &&
+                               at.device == c->device;
+        (void)hipGetLastError();   // (a plain host pointer leaves an error behind on some runtimes)
+        if (on_device) {
+            src = features;
+        } else {
+            if ((rc = ensure(c, s_src, sizeof(float) * (size_t)n * (size_t)channels))) return rc;
+            const hipError_t e = hipMemcpy(s_src.p, features, sizeof(float) * (size_t)n * (size_t)channels, hipMemcpyDefault);
+            if (e != hipSuccess) { release(s_src); return fail(c, SAS_ERR_HIP, "feature copy: %s", hipGetErrorString(e)); }
+            src = (const float *)s_src.p;
+        }
+    }
+    // on the context's own (idle: complete_all above) stream, waited for alone -- not the whole device
+    hipStream_t st = c->slots[0].fs;
+    sas_launch_feature_store(st, n, n_pad, c->scene.perm, c->scene.gid8, src, channels, (float *)c->feat.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    release(s_src);
+    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "feature store: %s", hipGetErrorString(e));
+    c->feat_c = channels;
+    c->has_feat = true;
+    return SAS_OK;
+}
+
+int sas_render_features(sas_ctx *c, const float *viewmat, const float *K, int width, int height, const float *background,
+                        const float *feature_background, unsigned flags, float *rgb, float *alpha, float *depth, float *features,
+                        void *stream)
+{
+    if (!c) return SAS_ERR_INVALID;
+    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_render_features before sas_scene_upload");
+    if (!c->has_feat) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
+    if (!features) return fail(c, SAS_ERR_INVALID, "the features output is required");
+    ViewCall v = {viewmat, K, rgb, alpha, depth, nullptr, nullptr, nullptr};
+    v.features = features;
+    v.fbg = feature_background;
+    v.feat_c = c->feat_c;
+    return render_views(c, &v, 1, width, height, background, flags | SAS_FULL_SORT, nullptr, stream, false, !(flags & SAS_ASYNC));
 }
 
 int sas_render_rgbd(sas_ctx *c, const float *viewmat, const float *K, int width, int height, const float *background,

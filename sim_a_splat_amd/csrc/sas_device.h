@@ -12,6 +12,11 @@ constexpr float kNear = 0.01f, kFar = 1e10f, kEps2d = 0.3f;
 constexpr float kAlphaThr = 1.0f / 255.0f, kMaxAlpha = 0.999f, kTStop = 1e-4f;
 
 DEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// Contract T2 (round 5): a colour is FINITE when it leaves the projection: clamped to +-FLT_MAX (the identity on every finite value; a
+// NaN becomes -FLT_MAX).  The compositing loop adds every staged entry to every pixel of its block with weight +0 where the entry is
+// skipped -- exact for finite colours, but 0 * Inf = NaN would spread one bad SH coefficient over whole blocks.  The feature store
+// (sas_scene_features) maps its channels the same way.
+DEV float finite_colour(float v) { return fminf(fmaxf(v, -3.402823466e38f), 3.402823466e38f); }
 // set bits of m below this lane's position (v_mbcnt_lo/hi: two instructions; hipcc does not form them from
 // __popcll(m & lanes_below))
 DEV unsigned mbcnt64(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); }

@@ -179,6 +179,26 @@ struct SasHostCopy {
 };
 void sas_launch_host_copy(hipStream_t st, const SasHostCopy &h);
 
+// Per-Gaussian feature channels (sas_scene_features / sas_render_features; DESIGN.md 3, "Feature channels").
+// The store is [chunks][n_pad][SAS_FEAT_K] float32 in slot order, channels c >= C zero; k_blend_features composites one chunk
+// of SAS_FEAT_K channels per workgroup, from the complete lists a SAS_FULL_SORT frame keeps.
+#define SAS_FEAT_K 8
+#define SAS_MAX_FEATURES 256
+struct SasFeatures {
+    const float *store;   // [chunks][n_pad][SAS_FEAT_K]
+    float *out;           // [H,W,C] device
+    long long n_pad;
+    int C, chunks;
+    float bg[SAS_MAX_FEATURES];   // feature background, [C] (rest zero)
+};
+static inline int sas_feature_chunks(int C) { return (C + SAS_FEAT_K - 1) / SAS_FEAT_K; }
+// store <- features [n,C] of the caller's order (device; nullptr: one-hot of gid8 with C = n_groups), through perm, finite_colour
+void sas_launch_feature_store(hipStream_t st, int64_t n, int64_t n_pad, const int *perm, const uint8_t *gid8, const float *src,
+                              int C, float *store);
+// after sas_launch_blend, on the same frame: the features of every pixel, one workgroup per (tile, chunk)
+void sas_launch_blend_features(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
+                               const SasFeatures &F, bool fast_exp);
+
 // launchers (sas_kernels.hip)
 void sas_launch_relayout(hipStream_t st, int64_t n, int64_t n_pad, const int *perm, const float *means, const float *quats,
                          const float *scales, const float *cov6, const float *opac, const float *colors,

@@ -1159,7 +1159,7 @@ DEV void geom_role(const SasScene &s, const SasCam &c, const SasFrame &f, unsign
 // Contract T2 (round 5): a colour is FINITE when it leaves the projection: clamped to +-FLT_MAX (the identity on every finite value; a
 // NaN becomes -FLT_MAX).  The compositing loop adds every staged entry to every pixel of its block with weight +0 where the entry is
 // skipped -- exact for finite colours, but 0 * Inf = NaN would spread one bad SH coefficient over whole blocks.
-DEV float finite_colour(float v) { return fminf(fmaxf(v, -3.402823466e38f), 3.402823466e38f); }
+// (finite_colour: sas_device.h -- the feature store maps its inputs the same way)
 template <int DEG, int NV, typename RowFn>
 DEV void color_role(const SasScene &s, const ProjArgs &vs, unsigned wg, const float *poses, bool poses_inline, RowFn inline_row)
 {

@@ -617,6 +617,9 @@ DEV BlendLds blend_lds(unsigned char *raw)
 // their own queues in lockstep, front to back (a group that runs out reads the sentinel record,
 // which no pixel accepts).  Returns true when every pixel of the tile has terminated (uniform over
 // the workgroup).  `slot_at(i)` gives the storage slot of entry i.
+// KEEP IN STEP: k_blend_features (end of this file) restates this loop's per-pixel chain entry by entry -- which entries a
+// lane takes (block mask, a block whose pixels have all terminated at the start of a batch), alpha, the 1/255 skip, the stop
+// rule and the fma_ order of p.r -- so that feature channels get exactly these weights (tests/test_gpu_f_features.py).
 #ifndef SAS_TUNE_LATE_COLOUR
 #define SAS_TUNE_LATE_COLOUR 0
 #endif
@@ -1898,4 +1901,188 @@ void sas_launch_depth_tail(hipStream_t st, int tiles, const SasParams &P, const 
     if (fill && points) hipLaunchKernelGGL((k_depth_tail<true, true>), dim3(1024), dim3(256), 0, st, tm, tiles, P);
     else if (fill) hipLaunchKernelGGL((k_depth_tail<true, false>), dim3(1024), dim3(256), 0, st, tm, tiles, P);
     else if (points) hipLaunchKernelGGL((k_depth_tail<false, true>), dim3(1024), dim3(256), 0, st, tm, tiles, P);
+}
+
+// ================================================================================================
+// Feature channels ("Feature channels"): C per-Gaussian channels through the frame's own weights
+// ================================================================================================
+namespace {
+
+constexpr int kFeatQ = SAS_FEAT_K / 4;   // float4 per entry of a chunk
+
+// store[(q n_pad + j) K + k] = channel q K + k of the Gaussian in slot j (the caller's Gaussian perm[j]), through finite_colour;
+// one-hot mode (src == nullptr): (gid8[j] == q K + k).  Channels >= C and slots >= n are zero.  One thread per (chunk, slot).
+__global__ __launch_bounds__(256) void k_feature_store(long long n, long long n_pad, const int *perm, const uint8_t *gid8,
+                                                       const float *src, int C, int chunks, float *store)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long total = (long long)chunks * n_pad;
+    if (t >= total) return;
+    const int q = (int)(t / n_pad);
+    const long long j = t - (long long)q * n_pad;
+    float v[SAS_FEAT_K];
+    long long i = 0;
+    if (j < n && SAS_IN(j, n, 301)) i = perm[j];
+    const bool ok = j < n && SAS_IN(i, n, 302) && i >= 0 && i < n;
+#pragma unroll
+    for (int k = 0; k < SAS_FEAT_K; ++k) {
+        const int ch = q * SAS_FEAT_K + k;
+        v[k] = 0.0f;
+        if (ok && ch < C) {
+            if (src) {
+                const long long at = i * C + ch;
+                if (SAS_IN(at, n * C, 303)) v[k] = finite_colour(src[at]);
+            } else if (SAS_IN(j, n_pad, 304)) {
+                v[k] = gid8[j] == ch ? 1.0f : 0.0f;
+            }
+        }
+    }
+    float4 *dst = reinterpret_cast<float4 *>(store) + t * kFeatQ;
+    if (SAS_IN(t * kFeatQ + kFeatQ - 1, total * kFeatQ, 305)) {
+#pragma unroll
+        for (int r = 0; r < kFeatQ; ++r) dst[r] = make_float4(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
+    }
+}
+
+// One workgroup per (tile, chunk of SAS_FEAT_K channels), one lane per pixel (pixel_of), on the complete depth-ordered list the
+// full path's k_blend has just composited.  A lane takes the entries blend_range takes -- those whose block mask names its 4x4
+// block, none after its whole block had terminated at the start of a batch -- with blend_range's alpha, 1/255 skip, stop rule
+// and fma_ chain of p.r (composite_trip), entry by entry: a trip's pair of entries is the same chain.  A terminated pixel (x =
+// NaN) takes nothing more in either kernel: its alpha is opacity x exp(-86) < 1/255, or 0.999, which stops it again, for every
+// opacity up to 8.7e34 and for +-Inf and NaN.  The K channels are accumulated in registers; every chunk recomputes alpha and T.
+template <bool FAST_EXP>
+__global__ __launch_bounds__(256) void k_blend_features(SasParams P, SasFrame f, long long n_gauss, SasFeatures F)
+{
+    __shared__ float4 s_g[256];               // (u, v, A/2, B): blend_range's q0
+    __shared__ float2 s_h[256];               // (C/2, opacity): its q1's first half
+    __shared__ float4 s_f[kFeatQ][256];       // the chunk's features
+    __shared__ unsigned s_m[256];             // block masks (block_mask16)
+    __shared__ unsigned char s_q[4][256];     // per wave: the batch's entries that name one of its four blocks
+    const SasCam &c = P.cam;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int oi = (int)blockIdx.x, q = (int)blockIdx.y;
+    if (!SAS_IN(oi, f.n_tiles, 310)) return;
+    const int tile = f.tile_order[oi];
+    if (!SAS_IN(tile, f.n_tiles, 311)) return;   // (uniform)
+    const int tx = tile % c.tw, ty = tile / c.tw;
+    int ox, oy;
+    pixel_of(wv, lane, ox, oy);
+    const int ix = tx * SAS_TILE + ox, iy = ty * SAS_TILE + oy;
+    const bool inside = ix < c.W && iy < c.H;
+    PixState p = pix_init(inside, ox);
+    const PixConst pc = pix_const(ox, oy);
+    float acc[SAS_FEAT_K];
+#pragma unroll
+    for (int k = 0; k < SAS_FEAT_K; ++k) acc[k] = 0.0f;
+    const long long beg = f.tile_offset[tile];
+    long long end = f.tile_offset[tile + 1];
+    if (end > f.cap) end = f.cap;
+    const int count = end > beg ? (int)(end - beg) : 0;
+    const float X0 = (float)(tx * SAS_TILE) + kTileCentre, Y0 = (float)(ty * SAS_TILE) + kTileCentre;
+    const float sE5 = vgpr_const(0x3aafa464u);
+    const int grp = lane >> 4;
+    const int my_bit = ((wv & 1) * 2 + (grp & 1)) + 4 * ((wv >> 1) * 2 + (grp >> 1));
+    const unsigned wbits = 0x33u << (2 * (wv & 1) + 8 * (wv >> 1));   // the wave's four blocks
+    bool wdone = __all(pix_dead(p));
+    for (int at = 0; at < count; at += 256) {
+        // (also the barrier behind the previous batch's reads)
+        if (__syncthreads_and(wdone ? 1 : 0)) break;
+        const int e = at + tid;
+        unsigned m = 0u;
+        if (e < count) {
+            const long long pos = beg + e;
+            long long id = SAS_IN(pos, f.cap, 312) ? (long long)(unsigned)f.sorted_ids[pos] : n_gauss - 1;
+            if (!SAS_IN(id, n_gauss, 313) || id >= n_gauss) id = n_gauss - 1;   // never dereference a bad index
+            const float4 ra = f.rec[SAS_RS * id + 0], rb = f.rec[SAS_RS * id + 1];
+            m = block_mask16(tx, ty, ra.x, ra.y, ra.z, ra.w, rb.x, rb.z);
+            s_g[tid] = make_float4(ra.x - X0, ra.y - Y0, 0.5f * ra.z, ra.w);
+            s_h[tid] = make_float2(0.5f * rb.x, rb.y);
+            const long long fo = ((long long)q * F.n_pad + id) * kFeatQ;
+            const bool fin = SAS_IN(id, F.n_pad, 314) && id < F.n_pad;
+#pragma unroll
+            for (int r = 0; r < kFeatQ; ++r)
+                s_f[r][tid] = fin ? reinterpret_cast<const float4 *>(F.store)[fo + r] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        s_m[tid] = m;
+        __syncthreads();
+        if (wdone) continue;
+        // blend_range's queue rules: a block whose 16 pixels have all terminated takes nothing more in this batch
+        const unsigned long long dm = __ballot(pix_dead(p));
+        const bool blk_live = ((dm >> (16 * grp)) & 0xffffull) != 0xffffull;
+        int qn = 0;
+        const int cnt = (count - at) < 256 ? (count - at) : 256;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int ej = 64 * j + lane;
+            const bool has = ej < cnt && (s_m[ej] & wbits) != 0u;
+            const unsigned long long bm = __ballot(has);
+            if (has && SAS_IN(qn + (int)mbcnt64(bm), 256, 315)) s_q[wv][qn + (int)mbcnt64(bm)] = (unsigned char)ej;
+            qn += (int)__popcll(bm);
+        }
+        const int kend = __builtin_amdgcn_readfirstlane(qn);
+        for (int k = 0; k < kend; ++k) {
+            const int ent = s_q[wv][k];
+            const unsigned me = s_m[ent];
+            const float4 g = s_g[ent];
+            const float2 h = s_h[ent];
+            const float dx = g.x - p.x, dy = g.y - pc.y;
+            const float sg = fma_(dx, fma_(g.w, dy, g.z * dx), (h.x * dy) * dy);
+            const float E = FAST_EXP ? __expf(fmaxf(-sg, -86.0f)) : c_expf_neg(fmaxf(-sg, -86.0f), sE5);
+            const float al = fminf(kMaxAlpha, h.y * E);
+            const bool take = blk_live && ((me >> my_bit) & 1u);
+            const float w = (!take || al < kAlphaThr) ? 0.0f : al * p.T;
+            const float nT = p.T - w;
+            const bool stop = nT <= kTStop;
+            const float vis = stop ? 0.0f : w;
+            p.T = stop ? p.T : nT;
+            if (stop) p.x = __builtin_nanf("");
+#pragma unroll
+            for (int r = 0; r < kFeatQ; ++r) {
+                const float4 fv = s_f[r][ent];
+                acc[4 * r + 0] = fma_(fv.x, vis, acc[4 * r + 0]);
+                acc[4 * r + 1] = fma_(fv.y, vis, acc[4 * r + 1]);
+                acc[4 * r + 2] = fma_(fv.z, vis, acc[4 * r + 2]);
+                acc[4 * r + 3] = fma_(fv.w, vis, acc[4 * r + 3]);
+            }
+            if ((k & 7) == 7 && __all(pix_dead(p))) break;
+        }
+        wdone = __all(pix_dead(p));
+    }
+    // write_pixel's epilogue on the chunk's channels: a = 1 - T, w = 1 - a, v = acc + w bg (no clamp)
+    if (!inside) return;
+    const long long pix = (long long)iy * c.W + ix;
+    if (!SAS_IN(pix, P.out.n_pixels, 316)) return;
+    const float a = 1.0f - p.T;
+    const float wb = 1.0f - a;
+    const int c0 = q * SAS_FEAT_K;
+#pragma unroll
+    for (int k = 0; k < SAS_FEAT_K; ++k) {
+        const int ch = c0 + k;
+        if (ch < F.C && SAS_IN(ch, SAS_MAX_FEATURES, 317)) {
+            const long long o = pix * F.C + ch;
+            if (SAS_IN(o, P.out.n_pixels * F.C, 318)) F.out[o] = acc[k] + wb * F.bg[ch];
+        }
+    }
+}
+
+}  // namespace
+
+void sas_launch_feature_store(hipStream_t st, int64_t n, int64_t n_pad, const int *perm, const uint8_t *gid8, const float *src,
+                              int C, float *store)
+{
+    const int chunks = sas_feature_chunks(C);
+    const long long total = (long long)chunks * n_pad;
+    if (total <= 0) return;
+    hipLaunchKernelGGL(k_feature_store, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (long long)n, (long long)n_pad,
+                       perm, gid8, src, C, chunks, store);
+}
+
+void sas_launch_blend_features(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
+                               const SasFeatures &F, bool fast_exp)
+{
+    if (tiles <= 0 || F.chunks <= 0) return;
+    const long long n = s.n > 0 ? s.n : 1;
+    const dim3 grid((unsigned)tiles, (unsigned)F.chunks);
+    if (fast_exp) hipLaunchKernelGGL(k_blend_features<true>, grid, dim3(256), 0, st, P, f, n, F);
+    else hipLaunchKernelGGL(k_blend_features<false>, grid, dim3(256), 0, st, P, f, n, F);
 }

@@ -40,6 +40,42 @@ def cov3x3_to_cov6(cov: ArrayLike) -> ArrayLike:
     return np.stack([c[:, 0, 0], c[:, 0, 1], c[:, 0, 2], c[:, 1, 1], c[:, 1, 2], c[:, 2, 2]], axis=1)
 
 
+MAX_FEATURES = 256   # channels of a feature store (sas_scene_features)
+
+
+def feature_channels(shape: Sequence[int], n: int) -> int:
+    """Channels C of a feature array of ``shape`` for a scene of ``n`` Gaussians ([n,C], 1 <= C <= 256); ValueError otherwise."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 2 or shape[0] != n:
+        raise ValueError(f"features must be [N={n},C], got {list(shape)}")
+    if not 1 <= shape[1] <= MAX_FEATURES:
+        raise ValueError(f"features must have 1..{MAX_FEATURES} channels, got {shape[1]}")
+    return shape[1]
+
+
+def feature_background_array(fbg, C: int) -> Optional[np.ndarray]:
+    """The feature background as a float32 host array [C] (None: zeros, passed as NULL); ValueError on a wrong length."""
+    if fbg is None:
+        return None
+    if isinstance(fbg, torch.Tensor):
+        fbg = fbg.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(fbg, dtype=np.float32)).reshape(-1)
+    if a.shape[0] != C:
+        raise ValueError(f"feature_background must have {C} values, got {a.shape[0]}")
+    return a
+
+
+def group_labels(weights: torch.Tensor, alpha: torch.Tensor, min_alpha: float = 0.5) -> torch.Tensor:
+    """Per-pixel splat group of group weights [H,W,G] (render_group_masks): the argmax over groups, ties to the lowest
+    group id, and 255 where ``alpha [H,W,1] < min_alpha``.  uint8 [H,W] (with 256 groups, group 255 reads as none)."""
+    G = int(weights.shape[-1])
+    top = weights.max(dim=-1, keepdim=True).values
+    ids = torch.arange(G, dtype=torch.int32, device=weights.device)
+    lab = torch.where(weights == top, ids, torch.full_like(ids, G)).min(dim=-1).values.clamp_(max=255)
+    lab = torch.where(alpha[..., 0] < min_alpha, torch.full_like(lab, 255), lab)
+    return lab.to(torch.uint8)
+
+
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # (private, but what torch.cuda.current_stream itself calls)
 
 
@@ -74,6 +110,8 @@ class Rasterizer:
             raise SasError(f"sas_create(device={self.device.index}) failed with status {rc}")
         self.n = 0
         self.n_groups = 0
+        self.n_features = 0     # channels of the feature store (upload_features); 0: none for this scene
+        self._features_onehot = False
         self._keep = []  # outputs of in-flight async frames (the C ABI keeps up to four)
         self._argcache = {}  # id(argument) -> (argument, float32 array, address): _host_arg
 
@@ -132,6 +170,26 @@ class Rasterizer:
                     "sas_scene_upload")
         self.n = n
         self.n_groups = int(n_groups) if group_id is not None else 0
+        self.n_features = 0     # (the upload forgot them)
+        self._features_onehot = False
+
+    @_locked
+    def upload_features(self, features: Optional[ArrayLike] = None) -> None:
+        """Per-Gaussian feature channels for ``render_features``: ``[N,C]`` numpy or torch (host or device, the order of
+        ``upload``), 1 <= C <= 256; NaN and +-Inf are mapped to -+FLT_MAX as colours are.  ``None``: one-hot of the scene's
+        splat groups (C = n_groups), built on the device.  A new ``upload`` forgets them."""
+        if features is None:
+            if self.n_groups <= 0:
+                raise ValueError("one-hot group features need a scene uploaded with group_id")
+            self._check(self._L.sas_scene_features(self._ctx, self.n, self.n_groups, None), "sas_scene_features")
+            self.n_features, self._features_onehot = self.n_groups, True
+            return
+        C = feature_channels(features.shape, self.n)
+        f, pf = _as_f32(features, (self.n, C), "features")
+        if isinstance(f, torch.Tensor) and f.is_cuda:
+            torch.cuda.synchronize(f.device)   # device-resident inputs must be complete before the copy
+        self._check(self._L.sas_scene_features(self._ctx, self.n, C, pf), "sas_scene_features")
+        self.n_features, self._features_onehot = C, False
 
     @_locked
     def set_group_poses(self, Rt: ArrayLike) -> None:
@@ -287,6 +345,57 @@ class Rasterizer:
         self._keep = []
         res["mask"] = mask8.view(torch.bool)
         return res
+
+    @_locked
+    def render_features(self, viewmat: ArrayLike, K: ArrayLike, width: int, height: int,
+                        background: Sequence[float] = (0.0, 0.0, 0.0), *, feature_background=None,
+                        want: Iterable[str] = ("features",), fast_exp: bool = False, depth_fill_max: bool = False,
+                        block: bool = True, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """Render one view with the feature channels of ``upload_features``: ``features [H,W,C]`` float32, not clamped,
+        ``F = sum_i w_i f_i + (1 - alpha) feature_background`` with the frame's own weights w_i (``feature_background``:
+        [C], default zeros), plus any of ``rgb`` / ``alpha`` / ``depth`` listed in ``want`` (bit-identical to ``render``).
+        ``block=False`` enqueues as ``render`` does."""
+        C = self.n_features
+        if C <= 0:
+            raise SasError("render_features: no features uploaded for this scene (upload_features)")
+        fb = feature_background_array(feature_background, C)
+        V, pV = self._host_arg(viewmat, 16)
+        Kc, pK = self._host_arg(K, 9)
+        bg, pbg = self._host_arg(background, 3)
+        W, H = int(width), int(height)
+        shapes = dict(self._SHAPES, features=(C, torch.float32))
+        shapes.pop("rgb8")
+        want = tuple(want)
+        res: Dict[str, torch.Tensor] = {}
+        ptrs = {"rgb": None, "alpha": None, "depth": None, "features": None}
+        for k in set(want) | {"features"}:
+            ch, dt = shapes[k]   # KeyError: unknown output
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty((H, W, ch), dtype=dt, device=self.device)
+            elif t.shape != (H, W, ch) or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor {(H, W, ch)} on {self.device}")
+            res[k] = t
+            ptrs[k] = t.data_ptr()
+        flags = (_capi.SAS_DEPTH_FILL_MAX if depth_fill_max else 0) | (_capi.SAS_FAST_EXP if fast_exp else 0) | \
+                (0 if block else _capi.SAS_ASYNC)
+        rc = self._L.sas_render_features(self._ctx, pV, pK, W, H, pbg, fb.ctypes.data if fb is not None else None, flags,
+                                         ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["features"], self._stream())
+        if rc != 0:
+            self._check(rc, "sas_render_features")
+        self._keep = [] if block else (self._keep + [(dict(res), V, Kc, bg, fb)])[-4:]
+        return {k: res[k] for k in want}
+
+    @_locked
+    def render_group_masks(self, viewmat: ArrayLike, K: ArrayLike, width: int, height: int, *,
+                           min_alpha: float = 0.5) -> Dict[str, torch.Tensor]:
+        """Which splat group (robot link) each pixel shows: ``weights [H,W,G]`` (the one-hot group features composited, zero
+        background), ``labels [H,W]`` uint8 (``group_labels``: argmax, ties to the lowest id, 255 where alpha < min_alpha)
+        and ``alpha [H,W,1]``.  Selects the one-hot group store (replacing features uploaded before)."""
+        if not self._features_onehot:
+            self.upload_features(None)
+        o = self.render_features(viewmat, K, width, height, want=("features", "alpha"))
+        return {"weights": o["features"], "labels": group_labels(o["features"], o["alpha"], min_alpha), "alpha": o["alpha"]}
 
     def _pose_sets(self, pose_sets, pose_set, C: int):
         """(Rt [S,G,12] float32, index [C] int32) of per-view pose sets, validated."""
