@@ -4,9 +4,6 @@
 #include <stdint.h>
 
 #define SAS_TILE 16
-#ifndef SAS_TILE_GROUP
-#define SAS_TILE_GROUP 4   // tiles per unit of the tile order a single-pass projection's tail writes (A/B builds: 1)
-#endif
 // record / colour strides in float4: a 32-byte record and a colour array of its own.  (Measured against the colour inside a
 // 48-byte record as rounds 1-4 had it, the two roles of the projection each writing part of every line: projection +5 us, tile
 // kernel +1.5 us, pair bench -5 %: profiles/r05_ab_record_layout.txt.)
@@ -135,12 +132,8 @@ struct SasParams {
 
 // Up to SAS_MAX_GROUP same-sized views rendered by ONE set of launches: the cameras of a Gym step.  Passed to the
 // *_multi kernels by value.
-#ifndef SAS_MULTI_INLINE_ROWS
-#define SAS_MULTI_INLINE_ROWS 32   // pose rows (all views together) a launch group carries in its argument segment
-#endif
-#ifndef SAS_PROJ_INLINE_ROWS
-#define SAS_PROJ_INLINE_ROWS 16    // ... a single view / a view pair
-#endif
+constexpr int kMultiInlineRows = 32;   // pose rows (all views together) a launch group carries in its argument segment
+constexpr int kProjInlineRows = 16;    // ... a single view / a view pair
 struct SasMulti {
     SasFrame f[SAS_MAX_GROUP];
     SasParams P[SAS_MAX_GROUP];
@@ -148,12 +141,12 @@ struct SasMulti {
     int mix_k;                                  // geometry blocks per 8 leading blocks of the projection launch (set by the launcher)
     int pose_inline;                            // 1: view k's poses are pose_rows + pose_off[k] (set by the launcher)
     int pose_off[SAS_MAX_GROUP];
-    float pose_rows[12 * SAS_MULTI_INLINE_ROWS];
+    float pose_rows[12 * kMultiInlineRows];
 };
 // Will the projection launch carry the poses itself (no upload kernel, no dependent-kernel gap in front of it)?
 static inline bool sas_poses_inline(int n_groups, int n_views, bool multi)
 {
-    return n_groups > 0 && (multi ? n_groups * n_views <= SAS_MULTI_INLINE_ROWS : n_groups <= SAS_PROJ_INLINE_ROWS);
+    return n_groups > 0 && (multi ? n_groups * n_views <= kMultiInlineRows : n_groups <= kProjInlineRows);
 }
 
 // Group poses of the views of a launch: ONE small kernel copies each view's [rows, 12] block into that view's device

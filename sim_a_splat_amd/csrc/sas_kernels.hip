@@ -197,11 +197,6 @@ DEV void sh3_second(const float *b /* floats 24 .. 47: coefficient k of channel 
 // are broadcast while the wave is still convergent (a cross-lane read of an inactive lane
 // returns 0), then handed to emit(tile, v0, v1).  Must be reached by all 64 lanes.
 constexpr int kSmallRect = 8;
-// timing experiments only (-DSAS_TUNE_PABL=mask: 1 no count atomics, 2 no key stores, 4 no LDS atomics, 8 no record stores, 16 one tile per Gaussian,
-// 32 colour blocks leave at once, 64 geometry blocks leave at once, 128 no binning (geometry = T1 + records + ticket + tail)): wrong frames
-#ifndef SAS_TUNE_PABL
-#define SAS_TUNE_PABL 0
-#endif
 
 #ifdef SAS_TUNE_PTIME
 // A/B builds only (tools/proj_time.py): per geometry workgroup, EXCLUSIVE laps of thread 0's wall time (100 MHz ticks):
@@ -251,16 +246,8 @@ DEV void for_each_tile(bool active, int x0, int x1, int y0, int y1, int tw, unsi
 // histogram over that window and leave the CU as ONE global atomic per touched tile instead of
 // one per intersection (device-scope atomics execute at the memory side: ~10 G/s scattered).
 // Gaussians with a large rectangle stay out of the window and use the wave-cooperative walk.
-#ifndef SAS_TUNE_HIST
-#define SAS_TUNE_HIST SAS_WIN_BINS
-#endif
-static_assert(SAS_TUNE_HIST <= SAS_WIN_BINS, "wg_base holds SAS_WIN_BINS entries per workgroup");
-#ifndef SAS_TUNE_WINRECT
-#define SAS_TUNE_WINRECT 64
-#endif
-constexpr int kHistBins = SAS_TUNE_HIST;      // 8 KiB of LDS
-static_assert(SAS_TUNE_WINRECT <= 64, "count_tiles keeps one mask bit per tile of a window rectangle");
-constexpr int kWinRect = SAS_TUNE_WINRECT;    // largest rectangle (tiles) that takes part in the window
+constexpr int kHistBins = SAS_WIN_BINS;   // 8 KiB of LDS
+constexpr int kWinRect = 64;              // largest rectangle (tiles) that takes part in the window: one mask bit per tile in count_tiles
 
 struct Window {
     int X0, Y0, ww, area;   // origin, width, bin count (0: no participant)
@@ -493,8 +480,7 @@ DEV void count_tiles(const SasFrame &f, int tw, int tile_px, const ViewGeom &g, 
     const CullGeom cg = cull_geom(g);
     const float px = (float)tile_px;
     const unsigned long long key = ((unsigned long long)__float_as_uint(g.z) << 32) | (unsigned long long)slot;
-    const int x0 = g.x0, y0 = g.y0;
-    const int x1 = (SAS_TUNE_PABL & 16) ? min(g.x1, g.x0 + 1) : g.x1, y1 = (SAS_TUNE_PABL & 16) ? min(g.y1, g.y0 + 1) : g.y1;   // (16: one tile per Gaussian)
+    const int x0 = g.x0, x1 = g.x1, y0 = g.y0, y1 = g.y1;
     const int rect_area = vis ? (x1 - x0) * (y1 - y0) : 0;
     const bool in_win = rect_area > 0 && rect_area <= kWinRect;
     const Window w = wg_window_zeroed(in_win, x0, x1, y0, y1, s_win, s_hist);   // (the bins are zero behind its barrier)
@@ -509,7 +495,7 @@ DEV void count_tiles(const SasFrame &f, int tw, int tile_px, const ViewGeom &g, 
                     const int b = (ty - w.Y0) * w.ww + (tx - w.X0);
                     if (cull && !tile_reached(cg, r, tx, px)) continue;
                     reached |= 1ull << k;
-                    if (!(SAS_TUNE_PABL & 4) && SAS_IN(b, kHistBins, 101)) atomicAdd(&s_hist[b], 1);
+                    if (SAS_IN(b, kHistBins, 101)) atomicAdd(&s_hist[b], 1);
                 }
             }
         }
@@ -526,7 +512,7 @@ DEV void count_tiles(const SasFrame &f, int tw, int tile_px, const ViewGeom &g, 
             for (unsigned b = tid; b < (unsigned)w.area; b += 256u) {
                 const int cnt = s_hist[b];
                 const int tile = (w.Y0 + (int)row) * tw + w.X0 + (int)col;
-                const int base = (!(SAS_TUNE_PABL & 1) && cnt && SAS_IN(tile, f.n_tiles, 102)) ? atomicAdd(&f.tile_count[tile], cnt) : 0;
+                const int base = (cnt && SAS_IN(tile, f.n_tiles, 102)) ? atomicAdd(&f.tile_count[tile], cnt) : 0;
                 if (seg > 0) {   // where the workgroup's run starts inside the tile's segment stays in LDS; the bin becomes its rank counter
                     s_base[b] = base;
                     s_hist[b] = 0;
@@ -550,9 +536,9 @@ DEV void count_tiles(const SasFrame &f, int tw, int tile_px, const ViewGeom &g, 
                         const int b = (ty - w.Y0) * w.ww + (tx - w.X0);
                         if (!SAS_IN(b, kHistBins, 117)) continue;
                         if (!(reached & 1ull)) continue;   // (what the count pass found)
-                        const int pos = s_base[b] + ((SAS_TUNE_PABL & 4) ? (int)(threadIdx.x & 63) : atomicAdd(&s_hist[b], 1));
+                        const int pos = s_base[b] + atomicAdd(&s_hist[b], 1);
                         // pos >= seg: the tile has outgrown its segment (the tail reports it; the frame is rendered again)
-                        if (!(SAS_TUNE_PABL & 2) && pos < seg && SAS_IN((long long)(ty * tw + tx) * seg + pos, f.cap, 118)) f.keys[(long long)(ty * tw + tx) * seg + pos] = key;
+                        if (pos < seg && SAS_IN((long long)(ty * tw + tx) * seg + pos, f.cap, 118)) f.keys[(long long)(ty * tw + tx) * seg + pos] = key;
                     }
         }
     } else if (threadIdx.x == 0 && w.area > 0) {
@@ -645,11 +631,7 @@ DEV void scan_tail_single(const SasFrame *fp, int *lds, unsigned pl_wg_, unsigne
     int *s_bins = lds + 16;      // [16 classes (descending)][32 copies]
     int *s_off = s_bins + 512, *s_rank = s_off + 512, *s_ctot = s_rank + 512;
     unsigned char *s_clsb = reinterpret_cast<unsigned char *>(lds + kTailScratch);   // class of group w = tiles 4 w .. 4 w + 3
-#if SAS_TILE_GROUP == 1
-    constexpr int kClsGroups = 2 * kHistBins - kTailScratch;   // (a word of four class bytes per group)
-#else
     constexpr int kClsGroups = 4 * (2 * kHistBins - kTailScratch);
-#endif
     const int words = (tiles + 3) >> 2;       // groups of four tiles = 16-byte words of counts
     const bool in_lds = words <= kClsGroups;   // (uniform)
     const int4 *cnt4 = reinterpret_cast<const int4 *>(f.tile_count);   // (zero-padded past its end: sas_count_stride)
@@ -688,22 +670,9 @@ DEV void scan_tail_single(const SasFrame *fp, int *lds, unsigned pl_wg_, unsigne
             total += (c[j].x + c[j].y) + (c[j].z + c[j].w);
             const int gmax = max(max(c[j].x, c[j].y), max(c[j].z, c[j].w));
             maxlen = max(maxlen, gmax);
-#if SAS_TILE_GROUP == 1   // A/B build: the order's unit is a tile (four class bytes per word, four times the atomics and order stores)
-            const int cc[4] = {c[j].x, c[j].y, c[j].z, c[j].w};
-            unsigned packed = 0u;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (4 * w + q >= tiles) break;
-                const int cl = 15 - len_class(cc[q]);
-                packed |= (unsigned)cl << (8 * q);
-                atomicAdd(&s_bins[cl * 32 + (lane & 31)], 1);
-            }
-            if (in_lds) reinterpret_cast<unsigned *>(s_clsb)[w] = packed;
-#else
             const int cl = 15 - len_class(gmax);
             atomicAdd(&s_bins[cl * 32 + (lane & 31)], 1);
             if (in_lds) s_clsb[w] = (unsigned char)cl;
-#endif
         }
     }
     total = wave_sum_i32(total); maxlen = wave_max_i32(maxlen);   // (DPP steps: sas_device.h)
@@ -742,23 +711,6 @@ DEV void scan_tail_single(const SasFrame *fp, int *lds, unsigned pl_wg_, unsigne
     //      b renders tile 4 tile_order[b / 4] + b % 4)
 #pragma unroll 4
     for (int w = tid; w < words; w += 256) {
-#if SAS_TILE_GROUP == 1
-        unsigned packed;
-        if (in_lds) {
-            packed = reinterpret_cast<const unsigned *>(s_clsb)[w];
-        } else {
-            const int4 c = cnt4[w];
-            packed = (unsigned)(15 - len_class(c.x)) | ((unsigned)(15 - len_class(c.y)) << 8) | ((unsigned)(15 - len_class(c.z)) << 16) |
-                     ((unsigned)(15 - len_class(c.w)) << 24);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (4 * w + q >= tiles) break;
-            const int b = (int)((packed >> (8 * q)) & 255u) * 32 + (lane & 31);
-            const int pos = s_off[b] + atomicAdd(&s_rank[b], 1);
-            if (SAS_IN(pos, tiles, 105)) f.tile_order[pos] = 4 * w + q;
-        }
-#else
         int cl;
         if (in_lds) {
             cl = (int)s_clsb[w];
@@ -769,7 +721,6 @@ DEV void scan_tail_single(const SasFrame *fp, int *lds, unsigned pl_wg_, unsigne
         const int b = cl * 32 + (lane & 31);
         const int pos = s_off[b] + atomicAdd(&s_rank[b], 1);
         if (SAS_IN(pos, words, 105)) f.tile_order[pos] = w;
-#endif
     }
     if (tid == 0) {
         const int carry = s_w[0] + s_w[1] + s_w[2] + s_w[3];
@@ -1008,7 +959,7 @@ struct ProjArgs {
     SasFrame f[2];
     int mix_k;                                   // of 8 consecutive leading blocks, this many are geometry blocks
     int pose_inline;                             // 1: the group poses are pose_rows (small blocks: no upload kernel)
-    float pose_rows[12 * SAS_PROJ_INLINE_ROWS];
+    float pose_rows[12 * kProjInlineRows];
 };
 
 // GEOMETRY role: T1 of Gaussians [256 wg, 256 wg + 256) for ONE view, then that view's binning; reached by all 256 threads.
@@ -1095,20 +1046,18 @@ DEV void geom_role(const SasScene &s, const SasCam &c, const SasFrame &f, unsign
             project_view(c, cov, op, cx, cy, cz, g);
         }
         if (g.vis) {
-            if (!(SAS_TUNE_PABL & 8)) {
-                f.rec[SAS_RS * i + 0] = make_float4(g.mx, g.my, g.ca, g.cb);
-                f.rec[SAS_RS * i + 1] = make_float4(g.ccn, op, g.thr, g.z);
-                // radii (parity hook only): full 32 bits each (a camera inside the cloud produces radii beyond 65535
-                // pixels); saturated to INT_MAX
-                const int irx = (int)fminf(g.rx, 2147483520.0f), iry = (int)fminf(g.ry, 2147483520.0f);
-                if (f.keep_info) f.info[i] = make_uint4((unsigned)g.x0 | ((unsigned)g.x1 << 16), (unsigned)g.y0 | ((unsigned)g.y1 << 16), (unsigned)irx, (unsigned)iry);
-            }
+            f.rec[SAS_RS * i + 0] = make_float4(g.mx, g.my, g.ca, g.cb);
+            f.rec[SAS_RS * i + 1] = make_float4(g.ccn, op, g.thr, g.z);
+            // radii (parity hook only): full 32 bits each (a camera inside the cloud produces radii beyond 65535
+            // pixels); saturated to INT_MAX
+            const int irx = (int)fminf(g.rx, 2147483520.0f), iry = (int)fminf(g.ry, 2147483520.0f);
+            if (f.keep_info) f.info[i] = make_uint4((unsigned)g.x0 | ((unsigned)g.x1 << 16), (unsigned)g.y0 | ((unsigned)g.y1 << 16), (unsigned)irx, (unsigned)iry);
         } else if (f.keep_info) {
             f.info[i] = make_uint4(0u, 0u, 0u, 0u);
         }
     }
     PL_LAP(0);
-    if (!(SAS_TUNE_PABL & 128)) count_tiles(f, c.tw, c.tile_px, g, (unsigned)i, wg, s_win, s_hist, s_base, s_nvis, pl_t_);
+    count_tiles(f, c.tw, c.tile_px, g, (unsigned)i, wg, s_win, s_hist, s_base, s_nvis, pl_t_);
     // ---- the last geometry workgroup of the view to get here scans the counts of its frame.
     // Everything the tail reads from other workgroups was written by AGENT-scope atomics (the per-tile counts, the
     // window-miss counter, wg_vis), which are performed at the point all XCDs share; what remains is ordering:
@@ -1142,10 +1091,8 @@ DEV void geom_role(const SasScene &s, const SasCam &c, const SasFrame &f, unsign
 #endif
     if (!*s_last) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the tail's loads below are not served from a stale cache line
-#ifndef SAS_TUNE_NOTAIL
     if (f.seg > 0) scan_tail_single(&f, s_hist, pl_wg_, pl_t_);   // (uniform)
     else scan_tail_two_pass(&f, s_hist);
-#endif
     PL_LAP(9);
 #ifdef SAS_TUNE_PTIME
     if (threadIdx.x == 0 && wg < (unsigned)kDbgPMax) g_dbg_plap[16 * wg + 15] = wall_clock64();
@@ -1217,7 +1164,7 @@ DEV void color_role(const SasScene &s, const ProjArgs &vs, unsigned wg, const fl
         for (int v = 0; v < NV; ++v) {
             float rgb[3];
             sh3_second(b, S[v], rgb);
-            if (ok[v] && !(SAS_TUNE_PABL & 8)) vs.f[v].col[SAS_CS * i] = make_float4(finite_colour(rgb[0]), finite_colour(rgb[1]), finite_colour(rgb[2]), 0.0f);
+            if (ok[v]) vs.f[v].col[SAS_CS * i] = make_float4(finite_colour(rgb[0]), finite_colour(rgb[1]), finite_colour(rgb[2]), 0.0f);
         }
     } else {
         constexpr int KF = DEG >= 0 ? 3 * (DEG + 1) * (DEG + 1) : 4;
@@ -1239,7 +1186,7 @@ DEV void color_role(const SasScene &s, const ProjArgs &vs, unsigned wg, const fl
             } else {
                 rgb[0] = sh[0]; rgb[1] = sh[1]; rgb[2] = sh[2];
             }
-            if (!(SAS_TUNE_PABL & 8)) vs.f[v].col[SAS_CS * i] = make_float4(finite_colour(rgb[0]), finite_colour(rgb[1]), finite_colour(rgb[2]), 0.0f);
+            vs.f[v].col[SAS_CS * i] = make_float4(finite_colour(rgb[0]), finite_colour(rgb[1]), finite_colour(rgb[2]), 0.0f);
         }
     }
 #ifdef SAS_TUNE_PTIME
@@ -1274,15 +1221,10 @@ __host__ DEV Role block_role(unsigned b, unsigned n_geo, unsigned mix_k)
     return r;
 }
 
-#ifdef SAS_TUNE_POCC   // A/B builds: waves per SIMD forced for the projection
-#define SAS_PROJECT_ATTRS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAS_TUNE_POCC, SAS_TUNE_POCC)))
-#else
-#define SAS_PROJECT_ATTRS __launch_bounds__(256)
-#endif
 // grid.x = (NV + 1) * n_wg: NV * n_wg geometry blocks (view = index % NV: the views' blocks of one chunk of Gaussians are
 // neighbours in dispatch order and share its 48 bytes through the cache) and n_wg colour blocks
 template <int DEG, int NV>
-__global__ SAS_PROJECT_ATTRS void k_project(SasScene s, ProjArgs vs)
+__global__ __launch_bounds__(256) void k_project(SasScene s, ProjArgs vs)
 {
     __shared__ __attribute__((aligned(16))) int s_win[16];
     __shared__ __attribute__((aligned(16))) int s_bins2[2 * kHistBins];   // one block: the tail uses all 16 KiB of it
@@ -1294,10 +1236,9 @@ __global__ SAS_PROJECT_ATTRS void k_project(SasScene s, ProjArgs vs)
     const Role r = block_role(blockIdx.x, (unsigned)NV * kSpreadRows * spread_cols(n_wg), (unsigned)vs.mix_k);
     auto row = [&](unsigned g, int k) { return vs.pose_rows[12u * g + (unsigned)k]; };
     if (!r.geom) {
-        if (!(SAS_TUNE_PABL & 32) && r.idx < n_wg) color_role<DEG, NV>(s, vs, r.idx, vs.f[0].group_Rt, vs.pose_inline != 0, row);
+        if (r.idx < n_wg) color_role<DEG, NV>(s, vs, r.idx, vs.f[0].group_Rt, vs.pose_inline != 0, row);
         return;
     }
-    if (SAS_TUNE_PABL & 64) return;
     const unsigned wg = spread_chunk(NV == 1 ? r.idx : r.idx >> 1, n_wg);
     if (wg >= n_wg) return;
     // (two inlined copies for a pair, chosen by a uniform branch: the view's camera and frame are then read from the
@@ -1477,10 +1418,7 @@ DEV void scatter_body(const SasScene &s, int tw, const SasFrame &f)
 // VGPRs leave 32 per SIMD lane): a scatter wave that fits into the remainder runs BESIDE a full complement of tile waves
 // instead of displacing one (wave slots 5 + 1 of 8, LDS 5 x 27 + 18.5 of 160 KB).  Left to itself the compiler takes 46:
 // the kernel's LDS caps it at eight waves per SIMD, below which registers look free.
-#ifndef SAS_TUNE_SCATTER_VGPR
-#define SAS_TUNE_SCATTER_VGPR 32
-#endif
-#define SAS_SCATTER_ATTRS __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(SAS_TUNE_SCATTER_VGPR)))
+#define SAS_SCATTER_ATTRS __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32)))
 __global__ SAS_SCATTER_ATTRS void k_scatter(SasScene s, int tw, SasFrame f) { scatter_body(s, tw, f); }
 __global__ SAS_SCATTER_ATTRS void k_scatter_multi(SasScene s, int tw, SasMulti mf) { scatter_body(s, tw, mf.f[blockIdx.y]); }
 

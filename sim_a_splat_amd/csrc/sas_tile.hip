@@ -620,9 +620,6 @@ DEV BlendLds blend_lds(unsigned char *raw)
 // KEEP IN STEP: k_blend_features (end of this file) restates this loop's per-pixel chain entry by entry -- which entries a
 // lane takes (block mask, a block whose pixels have all terminated at the start of a batch), alpha, the 1/255 skip, the stop
 // rule and the fma_ order of p.r -- so that feature channels get exactly these weights (tests/test_gpu_f_features.py).
-#ifndef SAS_TUNE_LATE_COLOUR
-#define SAS_TUNE_LATE_COLOUR 0
-#endif
 template <bool FAST_EXP, typename SlotAt>
 DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const PixConst pc, int count, SlotAt slot_at,
                      const BlendLds &L, PixState &p, bool &wdone, unsigned long long &ph_lap_, unsigned &sync_phase)
@@ -659,9 +656,9 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
         L.q2[256] = make_float4(z0, z0, z0, z0);
     }
     const float X0 = (float)(tx * SAS_TILE) + kTileCentre, Y0 = (float)(ty * SAS_TILE) + kTileCentre;   // the polynomial's origin: the tile's centre
-    // this lane's block: bit in the entry masks, and its queue
-    const int grp = lane >> 4;
-    const int my_bit = ((wv & 1) * 2 + (grp & 1)) + 4 * ((wv >> 1) * 2 + (grp >> 1));
+    // this lane's block's queue; wx: the block column where the wave's quadrant starts (computed here, ahead of the staging:
+    // where it is computed decides the register assignment of the trip loop)
+    const int grp = lane >> 4, wx = (wv & 1) * 2;
     unsigned short *wq = L.queue + wv * 1024;        // this wave's four queues
     const unsigned short *myq = wq + grp * 256;
     const char *q0b = reinterpret_cast<const char *>(L.q0);
@@ -739,7 +736,7 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
             asm volatile("" : "+v"(lane16));
             // bit of the wave's block 0 in the entry masks, opaque per batch (hipcc otherwise keeps the four masks 1 << bit alive
             // across the tile's loops and spills them: sixteen scratch reloads per batch)
-            unsigned bit0 = (unsigned)((wv & 1) * 2 + 8 * (wv >> 1));
+            unsigned bit0 = (unsigned)(wx + 8 * (wv >> 1));
             asm volatile("" : "+v"(bit0));
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -774,11 +771,7 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
             // Two queue entries per trip: their record loads, sigmas and exponentials are independent
             // (one wave alone cannot hide the two dependent LDS round trips of an entry); only the
             // transmittance chain is sequential.  A queue of odd length ends on the sentinel.
-#if SAS_TUNE_LATE_COLOUR
-            struct Trip { float4 K0, K1; float2 H0, H1; unsigned o0, o1; };
-#else
             struct Trip { float4 K0, K1, C0, C1; float2 H0, H1; };
-#endif
             auto load_trip = [&](Trip &t, int k, unsigned pair) {   // pair = queue entries k, k + 1
                 unsigned off0 = pair & 0xffffu, off1 = pair >> 16;
 #ifdef SAS_TUNE_STATS
@@ -792,12 +785,10 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
                 t.H0 = *reinterpret_cast<const float2 *>(q1b + off0);
                 t.K1 = *reinterpret_cast<const float4 *>(q0b + off1);
                 t.H1 = *reinterpret_cast<const float2 *>(q1b + off1);
-#if SAS_TUNE_LATE_COLOUR
-                t.o0 = off0; t.o1 = off1;   // (experiment: colour and depth are fetched when the alphas are known -- 8 registers fewer at the trip's peak)
-#else
-                t.C0 = *reinterpret_cast<const float4 *>(q2b + off0);   // colour, depth
+                // colour, depth: read with the geometry (read once the alphas are known, they cost the tile kernel 2 %:
+                // docs/EXPERIMENTS.md R5.2)
+                t.C0 = *reinterpret_cast<const float4 *>(q2b + off0);
                 t.C1 = *reinterpret_cast<const float4 *>(q2b + off1);
-#endif
             };
             // returns true when every pixel of the wave has terminated
             auto composite_trip = [&](const Trip &t) -> bool {
@@ -836,19 +827,10 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
                 p.T = Tn;
                 // lanes that do not composite add with weight +0: fmaf(c, 0, x) == x for the finite
                 // colours and depths of the path
-#if SAS_TUNE_LATE_COLOUR
-                __builtin_amdgcn_sched_barrier(0);
-                const float4 lc0 = *reinterpret_cast<const float4 *>(q2b + t.o0), lc1 = *reinterpret_cast<const float4 *>(q2b + t.o1);
-                p.r = fma_(lc1.x, vis1, fma_(lc0.x, vis0, p.r));
-                p.g = fma_(lc1.y, vis1, fma_(lc0.y, vis0, p.g));
-                p.b = fma_(lc1.z, vis1, fma_(lc0.z, vis0, p.b));
-                p.d = fma_(lc1.w, vis1, fma_(lc0.w, vis0, p.d));
-#else
                 p.r = fma_(t.C1.x, vis1, fma_(t.C0.x, vis0, p.r));
                 p.g = fma_(t.C1.y, vis1, fma_(t.C0.y, vis0, p.g));
                 p.b = fma_(t.C1.z, vis1, fma_(t.C0.z, vis0, p.b));
                 p.d = fma_(t.C1.w, vis1, fma_(t.C0.w, vis0, p.d));
-#endif
 #ifdef SAS_TUNE_STATS
                 {
                     const unsigned long long m0 = __ballot(vis0 > 0.0f), m1 = __ballot(vis1 > 0.0f);
@@ -926,9 +908,6 @@ DEV bool blend_range_quad(const SasFrame &f, long long n_gauss, int tx, int ty, 
         have = idx < count;
         if (have) {
             long long id = slot_at(idx);
-#if defined(SAS_TUNE_ABLATE) && (SAS_TUNE_ABLATE & 8)
-            id &= 1023;   // timing experiment: the records come from 48 KiB that stay in the caches (wrong images)
-#endif
             if (!SAS_IN(id, n_gauss, 231) || id >= n_gauss) id = n_gauss - 1;
             ra = f.rec[SAS_RS * id + 0];
             rb = f.rec[SAS_RS * id + 1];
@@ -993,11 +972,7 @@ DEV bool blend_range_quad(const SasFrame &f, long long n_gauss, int tx, int ty, 
                 if (has && SAS_IN(qn + below, 256, 232)) wq[qn + below] = (unsigned short)(lane16 + 1024u * j);
                 qn += (int)__popcll(m);
             }
-#if defined(SAS_TUNE_ABLATE) && (SAS_TUNE_ABLATE & 4)
-            const int kend = 0;   // timing experiment: staging, masks and queues, but no trips (wrong images)
-#else
             const int kend = __builtin_amdgcn_readfirstlane(qn);
-#endif
             PH_ADD(3, 1);
             const unsigned long long t_t = PH_T();
             PH_ADD(7, t_t - t_b3);
@@ -1195,39 +1170,14 @@ __global__ __launch_bounds__(256) void k_blend(SasParams P, SasFrame f, long lon
 // ================================================================================================
 // Production path: lazy depth ordering fused with compositing
 // ================================================================================================
-// (the SAS_TUNE_* macros exist for A/B builds only: SAS_HIPCC_FLAGS="-DSAS_TUNE_CHUNK=2048" python -m sim_a_splat_amd.build)
-#ifndef SAS_TUNE_CHUNK
-#define SAS_TUNE_CHUNK 512
-#endif
-#ifndef SAS_TUNE_OCC
-#define SAS_TUNE_OCC 5
-#endif
-#ifndef SAS_TUNE_U
-#define SAS_TUNE_U 8
-#endif
-constexpr int kChunk = SAS_TUNE_CHUNK;   // entries ordered and composited per round
-#ifndef SAS_TUNE_QCHUNK
-#define SAS_TUNE_QCHUNK 1024
-#endif
-constexpr int kChunkQuad = SAS_TUNE_QCHUNK;   // ... in the quad layout
-#ifndef SAS_TUNE_QPART
-#define SAS_TUNE_QPART 1
-#endif
-#ifndef SAS_TUNE_RANKMAX
-#define SAS_TUNE_RANKMAX 32
-#endif
-constexpr int kRankMax = SAS_TUNE_RANKMAX;   // largest depth bucket a chunk is ordered by counting (else radix passes)
-#ifndef SAS_TUNE_PARTMIN
-#define SAS_TUNE_PARTMIN (8 * SAS_TUNE_CHUNK)
-#endif
+constexpr int kChunk = 512;       // entries ordered and composited per round
+constexpr int kChunkQuad = 1024;  // ... in the quad layout
+constexpr int kRankMax = 32;      // largest depth bucket a chunk is ordered by counting (else radix passes)
 // A list that still holds more than this many keys when its SECOND round starts is laid out by bucket once
 // (later rounds then read only their own chunk); shorter remainders are cheaper to re-scan (measured: the
 // layout pass + the per-chunk depth gathers cost 3 % at config 2, lists of ~4 000).
-constexpr int kPartitionMin = SAS_TUNE_PARTMIN;
+constexpr int kPartitionMin = 8 * kChunk;
 constexpr int kLazyThreads = 256;
-#ifndef SAS_EMPTY_GROUPS_OFF
-#define SAS_EMPTY_GROUPS_OFF 0   // A/B builds: 1 = every tile of an all-empty group takes a workgroup of its own (round 4)
-#endif
 
 // Lay the keys of buckets >= b_first out by bucket: slot ids into `ids` at the positions handed out by the
 // per-bucket cursors `cur` (LDS, preset to each bucket's start).  A real call, not inlined: it runs once for
@@ -1251,12 +1201,6 @@ __device__ __attribute__((noinline)) void partition_by_bucket(const unsigned lon
 template <bool FAST_EXP, bool WANT_MAX, bool QUAD>
 DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss, const int *perm, unsigned wg /* workgroup index within the view */)
 {
-    // timing experiments only (-DSAS_TUNE_ABLATE=1: no chunk sort, =2: no compositing): wrong images
-#ifdef SAS_TUNE_ABLATE
-    constexpr int ablate = SAS_TUNE_ABLATE;
-#else
-    constexpr int ablate = 0;
-#endif
     // LDS: the chunk of keys, then a region shared in time by the sort scratch and the blend staging
     // entries ordered and composited per round: in the quad layout (frames of a few hundred tiles: the chip is not
     // full, every round's passes and barriers sit on the chain of a wave that is alone on its SIMD) twice as many
@@ -1286,16 +1230,12 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
     // (the grid is the tile count rounded up to whole groups: the last group may be ragged; all of this is uniform)
     int tile;
     if (f.seg > 0) {
-#if SAS_TILE_GROUP == 1
-        if (wg >= (unsigned)f.n_tiles) return;
-        tile = f.tile_order[wg];
-#else
         // Groups whose four tiles are all empty are the last class of the order; class_cursor[15] says where it starts.  Such a
         // group costs ONE workgroup that paints its four tiles' background (the other three leave after a scalar load), instead
         // of four that each fetch their tile, its count and paint 256 pixels: the empty tiles were 6 % of the kernel's slot time
         // (3 880 of config 3's 8 160 tiles), which is what frames in flight compete for.  A blocking frame alone on the GPU keeps a
         // workgroup per tile (SasFrame::group_fill): there the kernel's END counts, and four tiles in a row lengthen it.
-        if (!QUAD && !SAS_EMPTY_GROUPS_OFF && f.group_fill && (int)(wg >> 2) >= f.class_cursor[15]) {
+        if (!QUAD && f.group_fill && (int)(wg >> 2) >= f.class_cursor[15]) {
             if (wg & 3u) return;
             const int g4 = 4 * f.tile_order[wg >> 2];
             const SasCam &cc = P.cam;
@@ -1321,7 +1261,6 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
         }
         tile = 4 * f.tile_order[wg >> 2] + (int)(wg & 3u);
         if (tile >= f.n_tiles) return;
-#endif
     } else {
         if (wg >= (unsigned)f.n_tiles) return;
         tile = f.tile_order[wg];
@@ -1401,18 +1340,9 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
         if (lane == 0) { atomicMin(&s_mn, mn); atomicMax(&s_mx, mx); }
         __syncthreads();
         const unsigned dmin = s_mn, span = s_mx - s_mn;
-#ifdef SAS_TUNE_SHORT_RADIX
-#pragma unroll
-        for (int u = 0; u < NK; ++u) {
-            const int i = u * kLazyThreads + tid;
-            if (i < n) ck[i] = kk[u] - ((unsigned long long)dmin << 32);
-        }
-        __syncthreads();
-        if (!(ablate & 1)) lds_radix_sort<4, NK>(ck, n, span, perm, cnt, dbase, s_wsum);
-#else
         // Ordered as a chunk of a long list is: 256 depth buckets over the list's range, keys placed grouped by
         // bucket, every key ranked inside its own bucket (a handful of compares) -- a third of the instructions
-        // of three radix passes.  A crowded bucket (coplanar splats) falls back to the radix passes.
+        // of three radix passes (docs/EXPERIMENTS.md s5.20).  A crowded bucket (coplanar splats) falls back to the radix passes.
         const int sbits = span ? 32 - __clz(span) : 0;
         const int shift = sbits > 8 ? sbits - 8 : 0;
 #pragma unroll
@@ -1438,19 +1368,16 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
                 }
             }
             __syncthreads();
-            if (!(ablate & 1)) {
-                const unsigned long long t_s = PH_T();
-                if (!big) lds_bucket_rank_sort<NK>(ck, n, 0, shift, s_hist, s_cur, perm);
-                else lds_radix_sort<4, NK>(ck, n, span, perm, cnt, dbase, s_wsum);
-                PH_ADD(0, PH_T() - t_s);
-            }
+            const unsigned long long t_s = PH_T();
+            if (!big) lds_bucket_rank_sort<NK>(ck, n, 0, shift, s_hist, s_cur, perm);
+            else lds_radix_sort<4, NK>(ck, n, span, perm, cnt, dbase, s_wsum);
+            PH_ADD(0, PH_T() - t_s);
         }
-#endif
         PH_LAP(13);
-        if (!(ablate & 2)) blend(n, [&](int i) { return (long long)lo32(ck[i]); });
+        blend(n, [&](int i) { return (long long)lo32(ck[i]); });
     } else if (n > CH) {
         // ---- long list: every pass over the keys keeps U independent loads per thread in flight
-        constexpr int U = SAS_TUNE_U;
+        constexpr int U = 8;
         const unsigned long long t_p = PH_T();
         if (tid == 0) { s_mn = ~0u; s_mx = 0u; }
         s_hist[tid] = 0u;
@@ -1568,7 +1495,7 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
             //      chunk instead of scanning the whole list again (n^2 / 512 key reads on a long translucent list;
             //      only worth it when many rounds are still to come: kPartitionMin).
             //      Bucket t of the remainder starts at the exclusive count of buckets b_next .. t - 1: the scan above.
-            if ((!QUAD || SAS_TUNE_QPART) && !partitioned && b_next > 0 && s_rem > (unsigned)kPartitionMin) {
+            if (!partitioned && b_next > 0 && s_rem > (unsigned)kPartitionMin) {
                 s_cur[tid] = my_incl - my_hv;
                 __syncthreads();
                 partition_by_bucket(g, n, dmin, shift, b_next, s_cur, ids);
@@ -1635,21 +1562,16 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
             const int m = (int)s_m;
             // ---- order the chunk, then composite it
             const unsigned long long t_s = PH_T();
-            if (!(ablate & 1)) {
-                if (!big) {
-                    lds_bucket_rank_sort<CH / kLazyThreads>(ck, m, b0, shift, s_hist, s_cur, perm);
-                } else {   // a crowded bucket (coplanar splats): radix passes cost the same whatever the distribution
-                    const unsigned long long hi_excl = ((unsigned long long)(b1 - b0 + 1) << shift);
-                    const unsigned rel_span = (unsigned)min((unsigned long long)(span - ((unsigned)b0 << shift)), hi_excl - 1ull);
-                    lds_radix_sort<4, CH / kLazyThreads>(ck, m, rel_span, perm, cnt, dbase, s_wsum);
-                }
+            if (!big) {
+                lds_bucket_rank_sort<CH / kLazyThreads>(ck, m, b0, shift, s_hist, s_cur, perm);
+            } else {   // a crowded bucket (coplanar splats): radix passes cost the same whatever the distribution
+                const unsigned long long hi_excl = ((unsigned long long)(b1 - b0 + 1) << shift);
+                const unsigned rel_span = (unsigned)min((unsigned long long)(span - ((unsigned)b0 << shift)), hi_excl - 1ull);
+                lds_radix_sort<4, CH / kLazyThreads>(ck, m, rel_span, perm, cnt, dbase, s_wsum);
             }
             PH_ADD(0, PH_T() - t_s);
             PH_LAP(6);
-            bool all_done = true;   // ablation build (SAS_TUNE_ABLATE): pretend the first chunk saturates
-            if (!(ablate & 2))
-                all_done = blend(m, [&](int i) { return (long long)lo32(ck[i]); });
-            if (all_done) break;
+            if (blend(m, [&](int i) { return (long long)lo32(ck[i]); })) break;
             if (partitioned) p_consumed += m;
             b_next = b1 + 1;
             if (b_next > 255) break;
@@ -1687,7 +1609,8 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
 #endif
 }
 
-#define SAS_LAZY_ATTRS __attribute__((amdgpu_flat_work_group_size(kLazyThreads, kLazyThreads), amdgpu_waves_per_eu(SAS_TUNE_OCC, SAS_TUNE_OCC)))
+// five waves per SIMD (96 VGPRs): a sixth does not pay, whatever its code (docs/EXPERIMENTS.md R5.2)
+#define SAS_LAZY_ATTRS __attribute__((amdgpu_flat_work_group_size(kLazyThreads, kLazyThreads), amdgpu_waves_per_eu(5, 5)))
 template <bool FAST_EXP, bool WANT_MAX, bool QUAD>
 __global__ SAS_LAZY_ATTRS void k_tile_lazy(SasParams P, SasFrame f, long long n_gauss, const int *perm)
 {
@@ -1832,22 +1755,15 @@ void sas_launch_blend(hipStream_t st, const SasScene &s, int tiles, const SasPar
 // Production path: lazy ordering + compositing of every tile in one launch.
 // quad: frames of a few hundred tiles, binned in 8-pixel tiles by their projection (`tiles` counts those): one
 // workgroup per 8x8 quadrant (pixel_of_quad); exact exponential only (SAS_FAST_EXP frames take the ordinary layout).
-// experiments: SAS_TILE_DYN_LDS = bytes of unused dynamic LDS per tile workgroup (the compiled kernel, fewer workgroups per CU:
-// 6656 -> four, 14000 -> three; profiles/r05_ab_tile_workgroups_per_cu.txt)
-static unsigned lazy_dyn_lds()
-{
-    static const unsigned v = [] { const char *e = getenv("SAS_TILE_DYN_LDS"); return e ? (unsigned)atoi(e) : 0u; }();
-    return v;
-}
 
 template <bool FAST, bool WMAX, bool QUAD>
 static void launch_lazy(hipStream_t st, unsigned grid, const SasParams &P, const SasFrame &f, long long n, const int *perm,
                         hipEvent_t e0, hipEvent_t e1)
 {
     if (e0 && e1)
-        hipExtLaunchKernelGGL((k_tile_lazy<FAST, WMAX, QUAD>), dim3(grid), dim3(kLazyThreads), lazy_dyn_lds(), st, e0, e1, 0, P, f, n, perm);
+        hipExtLaunchKernelGGL((k_tile_lazy<FAST, WMAX, QUAD>), dim3(grid), dim3(kLazyThreads), 0, st, e0, e1, 0, P, f, n, perm);
     else
-        hipLaunchKernelGGL((k_tile_lazy<FAST, WMAX, QUAD>), dim3(grid), dim3(kLazyThreads), lazy_dyn_lds(), st, P, f, n, perm);
+        hipLaunchKernelGGL((k_tile_lazy<FAST, WMAX, QUAD>), dim3(grid), dim3(kLazyThreads), 0, st, P, f, n, perm);
 }
 
 bool sas_tiles_lazy_quad_ok(bool fast_exp) { return !fast_exp; }
@@ -1873,9 +1789,9 @@ template <bool FAST, bool WMAX, bool QUAD>
 static void launch_lazy_multi(hipStream_t st, dim3 grid, const SasMulti &mf, long long n, const int *perm, hipEvent_t e0, hipEvent_t e1)
 {
     if (e0 && e1)
-        hipExtLaunchKernelGGL((k_tile_lazy_multi<FAST, WMAX, QUAD>), grid, dim3(kLazyThreads), lazy_dyn_lds(), st, e0, e1, 0, mf, n, perm);
+        hipExtLaunchKernelGGL((k_tile_lazy_multi<FAST, WMAX, QUAD>), grid, dim3(kLazyThreads), 0, st, e0, e1, 0, mf, n, perm);
     else
-        hipLaunchKernelGGL((k_tile_lazy_multi<FAST, WMAX, QUAD>), grid, dim3(kLazyThreads), lazy_dyn_lds(), st, mf, n, perm);
+        hipLaunchKernelGGL((k_tile_lazy_multi<FAST, WMAX, QUAD>), grid, dim3(kLazyThreads), 0, st, mf, n, perm);
 }
 
 void sas_launch_tiles_lazy_multi(hipStream_t st, const SasScene &s, int tiles, const SasMulti &mf, bool fast_exp, bool want_max,
