@@ -200,6 +200,28 @@ int sas_render_features(sas_ctx *ctx, const float *viewmat, const float *K, int 
                         float *features, void *stream);
 
 /*
+ * Triangle meshes composited into every frame ("Meshes"): the task object and the robot's URDF visuals that the
+ * reference's viser scene holds beside the splats (splat_handler.py:145-219) and poses at every draw message (:238-263,
+ * :296-314).  sas_scene_meshes, after sas_scene_upload (a new upload forgets the meshes):
+ *   vertices  [n_vertices,3] float32, mesh-local (the handle's scale applied); triangles [n_triangles,3] int32 vertex indices
+ *   colors    [n_triangles,3] float32, one colour per triangle
+ *   group     [n_triangles] uint8: the pose group ([n_groups,12] block of sas_set_group_poses / sas_set_link_poses / the pose
+ *             sets of the *_posed calls) that moves the triangle; a scene without splat groups takes group 0, unposed
+ *   ambient, diffuse: shading m = clamp(c (ambient + diffuse |n . v|), 0, 1), n the unit world-space face normal, v the unit
+ *             ray from the camera centre to the triangle's centroid (ambient 1, diffuse 0: flat colour)
+ *   All pointers host or device.  n_triangles == 0 clears the meshes.  SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID
+ *   for an index out of range, a group >= max(n_groups, 1), or a non-finite ambient / diffuse.
+ * Every render call then composites the meshes: per pixel the nearest triangle whose interior holds the pixel centre (depth
+ * interpolated linear in 1/z, ties to the smaller (depth bits, triangle index), shared edges by a top-left rule, triangles
+ * clipped at z = 0.01, non-finite or degenerate ones dropped) hides every splat at or behind its depth and takes the
+ * background's place: rgb = clamp(C + T m).  alpha, depth and the RGB-D points / mask describe the splats in front of it.
+ * Frames with meshes are SAS_FULL_SORT frames (batches take them one view at a time); sas_render_features refuses a context
+ * with meshes (SAS_ERR_INVALID).
+ */
+int sas_scene_meshes(sas_ctx *ctx, int64_t n_vertices, const float *vertices, int64_t n_triangles, const int32_t *triangles,
+                     const float *colors, const uint8_t *group, float ambient, float diffuse);
+
+/*
  * Render n_views views of the same size in one call.  Serves the per-camera loops of
  * SplatHandler.render / SplatEnvWrapper.render (splat_handler.py:337-345, splat_env_wrapper.py:147-158).
  *   viewmats [n_views,16], Ks [n_views,9] host arrays; outputs are [n_views,H,W,...] device arrays

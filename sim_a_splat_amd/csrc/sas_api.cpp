@@ -88,6 +88,10 @@ struct Slot {
     SasParams params{};
     bool busy = false, timed = false, timed_tiles = false;
     bool quad = false;   // the frame runs in the quad layout: projected, binned and composited in 8-pixel tiles (prepare_frame)
+    bool mesh = false;   // the frame composites the context's meshes (enqueue_frame): mesh_host tells whether its lists fit
+    DevBuf mrec, mrect, mtiles, mlist;   // its mesh scratch (SasMeshFrame): records, rectangles, [count | offset | cursor], lists
+    long long mcap = 0;                  // entries mlist holds (grown like the splat keys when a frame outgrows it)
+    unsigned *mesh_host = nullptr;       // pinned [2], written by k_mesh_scan
     bool direct = false; // single-pass binning (SasFrame::seg > 0): the projection emits the keys, no scatter launch (prepare_frame)
     bool host_direct = false;   // the tile kernel delivers the uint8 frame to pinned host memory itself
     bool info_kept = false;     // the frame's projection wrote info[] (SasFrame::keep_info): sas_read_projection need not project again
@@ -112,6 +116,9 @@ struct sas_ctx {
     DevBuf feat;         // feature store (sas_scene_features): [chunks][n_pad][SAS_FEAT_K], slot order
     int feat_c = 0;      // its channels; has_feat: set for the current scene (an upload forgets it)
     bool has_feat = false;
+    DevBuf mesh_vert, mesh_tri, mesh_col;   // meshes (sas_scene_meshes): float4 vertices, int4 (i0, i1, i2, group), float4 colours
+    SasMeshScene mesh{};
+    bool has_mesh = false;   // set for the current scene (an upload forgets the meshes)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
     // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
     // the call returns: nothing is remembered across calls)
@@ -484,6 +491,37 @@ int prepare_frame(sas_ctx *c, Slot &sl, hipStream_t init_st)
     return SAS_OK;
 }
 
+// Mesh scratch of the slot's frame: 2 records per triangle, the tile counts / offsets / cursors, the lists (first guess: four
+// tiles per record; a frame whose lists outgrow it is rendered again with the measured need, as for the splat keys).
+int prepare_mesh(sas_ctx *c, Slot &sl, int tiles)
+{
+    const size_t nrec = 2 * (size_t)c->mesh.nt;
+    int rc;
+    if (sl.mcap == 0) sl.mcap = std::max<long long>(1 << 16, 4 * (long long)nrec);
+    if ((rc = ensure(c, sl.mrec, sizeof(float4) * 4 * nrec))) return rc;
+    if ((rc = ensure(c, sl.mrect, sizeof(int4) * nrec))) return rc;
+    if ((rc = ensure(c, sl.mtiles, sizeof(int) * (3 * sas_tile_stride(tiles) + 16)))) return rc;
+    if ((rc = ensure(c, sl.mlist, sizeof(int) * (size_t)sl.mcap))) return rc;
+    return SAS_OK;
+}
+
+SasMeshFrame mesh_frame_of(sas_ctx *c, Slot &sl)
+{
+    const int tiles = sl.cam.tw * sl.cam.th;
+    const size_t ts = sas_tile_stride(tiles);
+    SasMeshFrame m{};
+    m.rec = (float4 *)sl.mrec.p;
+    m.rect = (int4 *)sl.mrect.p;
+    m.tile_count = (int *)sl.mtiles.p;
+    m.tile_offset = (int *)sl.mtiles.p + ts;
+    m.tile_cursor = (int *)sl.mtiles.p + 2 * ts;
+    m.list = (int *)sl.mlist.p;
+    m.cap = sl.mcap;
+    m.n_rec = 2 * c->mesh.nt;
+    m.status_host = sl.mesh_host;
+    return m;
+}
+
 // Enqueue the slot's frame on its internal stream (the slot must be idle on the GPU).  The two frames of a view
 // pair (role, partner; both prepared by the caller) share the leader's projection.
 int enqueue_frame(sas_ctx *c, Slot &sl, int role = ROLE_SINGLE, Slot *partner = nullptr)
@@ -514,6 +552,17 @@ int enqueue_frame(sas_ctx *c, Slot &sl, int role = ROLE_SINGLE, Slot *partner = 
         if ((rc = enqueue_poses(c, mem, 1, st, false))) return rc;   // a pair shares its poses: the leader's block serves both views
     }
     if (role == ROLE_FOLLOWER) HIP_TRY(c, hipStreamWaitEvent(st, partner->pair_ev, 0));
+    // a frame with meshes (always SAS_FULL_SORT, a view of its own): the triangle setup reads the slot's poses on the device
+    sl.mesh = full && c->has_mesh && c->mesh.nt > 0;
+    if (sl.mesh && (rc = prepare_mesh(c, sl, tiles))) return rc;
+    if (sl.mesh && sas_poses_inline(c->scene.n_groups, 1, false)) {
+        SasPoseUpload u{};
+        u.nv = 1;
+        u.dst[0] = (float *)sl.poses_dev.p;
+        u.src_host[0] = sl.poses_host;
+        u.floats[0] = 12 * c->scene.n_groups;
+        sas_launch_pose_upload(st, u);
+    }
     if (timing) HIP_TRY(c, hipEventRecord(sl.ev[0], st));
     if (role == ROLE_LEADER) {
         const int ptiles = partner->cam.tw * partner->cam.th;
@@ -533,7 +582,11 @@ int enqueue_frame(sas_ctx *c, Slot &sl, int role = ROLE_SINGLE, Slot *partner = 
     if (timing) HIP_TRY(c, hipEventRecord(sl.ev[4], st));
     const bool fill = a.depth && (a.flags & SAS_DEPTH_FILL_MAX);
     const bool quad = sl.quad;   // (prepare_frame; never for SAS_FULL_SORT frames)
-    if (full) {
+    if (sl.mesh) {
+        const SasMeshFrame mf = mesh_frame_of(c, sl);
+        sas_launch_mesh_bin(st, c->mesh, P, f, mf);
+        sas_launch_blend_mesh(st, c->scene, tiles, P, f, mf, (a.flags & SAS_FAST_EXP) != 0, fill);
+    } else if (full) {
         sas_launch_blend(st, c->scene, tiles, P, f, (a.flags & SAS_FAST_EXP) != 0, fill);
         if (a.features) {   // a feature frame (sas_render_features): the same lists and records once more, per chunk of channels
             SasFeatures F{};
@@ -680,6 +733,11 @@ int complete_oldest(sas_ctx *c)
             c->stats[SAS_S_QUAD_LAYOUT] = mem[k]->quad ? 1 : 0;
             c->stats[SAS_S_LAUNCH_VIEWS] = g;
             overflow = overflow || s[2] != 0;
+            if (mem[k]->mesh && mem[k]->mesh_host[1] != 0) {   // the triangle lists outgrew the slot's: grow to the need (+25 %)
+                const long long need = (long long)mem[k]->mesh_host[0];
+                mem[k]->mcap = std::max(mem[k]->mcap, need + need / 4 + 1024);
+                overflow = true;
+            }
         }
         if (sl.timed) {
             for (int k = 0; k < 6; ++k) (void)hipEventElapsedTime(&c->stage_ms[k], sl.ev[k], sl.ev[k + 1]);
@@ -784,6 +842,7 @@ int sas_create(int device, sas_ctx **out)
     for (Slot &sl : c->slots) {
         ok = ok && hipHostMalloc((void **)&sl.stats_host, 8 * sizeof(unsigned)) == hipSuccess;
         ok = ok && hipHostMalloc((void **)&sl.poses_host, sizeof(float) * 12 * 256) == hipSuccess;
+        ok = ok && hipHostMalloc((void **)&sl.mesh_host, 2 * sizeof(unsigned)) == hipSuccess;
         ok = ok && hipStreamCreateWithFlags(&sl.fs, hipStreamNonBlocking) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&sl.start, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess;
@@ -793,6 +852,7 @@ int sas_create(int device, sas_ctx **out)
         ok = ok && hipEventCreateWithFlags(&sl.sort_streams.fork, hipEventDisableTiming) == hipSuccess;
         for (auto &e : sl.sort_streams.join) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
         if (ok) memset(sl.stats_host, 0, 8 * sizeof(unsigned));
+        if (ok) memset(sl.mesh_host, 0, 2 * sizeof(unsigned));
     }
     if (!ok) {
         sas_destroy(c);
@@ -816,6 +876,7 @@ int sas_destroy(sas_ctx *c)
         if (sl.fs) (void)hipStreamDestroy(sl.fs);
         if (sl.stats_host) (void)hipHostFree(sl.stats_host);
         if (sl.poses_host) (void)hipHostFree(sl.poses_host);
+        if (sl.mesh_host) (void)hipHostFree(sl.mesh_host);
         release(sl.poses_dev);
         if (sl.start) (void)hipEventDestroy(sl.start);
         if (sl.done) (void)hipEventDestroy(sl.done);
@@ -823,10 +884,12 @@ int sas_destroy(sas_ctx *c)
         for (auto &e : sl.ev)
             if (e) (void)hipEventDestroy(e);
         for (DevBuf *b : {&sl.scr.rec, &sl.scr.col, &sl.scr.info, &sl.scr.tilebuf, &sl.scr.keys, &sl.scr.ids, &sl.scr.counters,
-                          &sl.scr.wgvis, &sl.scr.wgbase, &sl.scr.tilemax})
+                          &sl.scr.wgvis, &sl.scr.wgbase, &sl.scr.tilemax, &sl.mrec, &sl.mrect, &sl.mtiles, &sl.mlist})
             release(*b);
     }
-    for (DevBuf *b : {&c->g0, &c->g1, &c->g2, &c->col, &c->gid8, &c->perm, &c->host_stage, &c->feat}) release(*b);
+    for (DevBuf *b : {&c->g0, &c->g1, &c->g2, &c->col, &c->gid8, &c->perm, &c->host_stage, &c->feat, &c->mesh_vert, &c->mesh_tri,
+                      &c->mesh_col})
+        release(*b);
     delete c;
     return SAS_OK;
 }
@@ -852,6 +915,7 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
     }
     c->has_scene = false;
     c->has_feat = false;
+    c->has_mesh = false;
 
     const int deg = sh_degree < 0 ? -1 : sh_degree;
     const int coeff_floats = deg < 0 ? 3 : 3 * (deg + 1) * (deg + 1);
@@ -1200,6 +1264,7 @@ static int render_views(sas_ctx *c, const ViewCall *views, int n, int width, int
                         unsigned flags, const float *max_depth, void *stream, bool grouped = false, bool solo = false)
 {
     if (!c) return SAS_ERR_INVALID;
+    if (c->has_mesh) flags |= SAS_FULL_SORT;   // (sas_scene_meshes: the meshes are composited by the full path's k_blend_mesh)
     for (int k = 0; k < n; ++k) {
         const int rc = check_view(c, views[k], width, height);
         if (rc) return rc;
@@ -1322,12 +1387,75 @@ int sas_render_features(sas_ctx *c, const float *viewmat, const float *K, int wi
     if (!c) return SAS_ERR_INVALID;
     if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_render_features before sas_scene_upload");
     if (!c->has_feat) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
+    if (c->has_mesh) return fail(c, SAS_ERR_INVALID, "feature frames of a context with meshes are not supported (sas_scene_meshes)");
     if (!features) return fail(c, SAS_ERR_INVALID, "the features output is required");
     ViewCall v = {viewmat, K, rgb, alpha, depth, nullptr, nullptr, nullptr};
     v.features = features;
     v.fbg = feature_background;
     v.feat_c = c->feat_c;
     return render_views(c, &v, 1, width, height, background, flags | SAS_FULL_SORT, nullptr, stream, false, !(flags & SAS_ASYNC));
+}
+
+int sas_scene_meshes(sas_ctx *c, int64_t n_vertices, const float *vertices, int64_t n_triangles, const int32_t *triangles,
+                     const float *colors, const uint8_t *group, float ambient, float diffuse)
+{
+    if (!c) return SAS_ERR_INVALID;
+    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_meshes before sas_scene_upload");
+    if (n_triangles < 0 || n_vertices < 0 || n_triangles > (1 << 29) || n_vertices > 0x7fffffffll)
+        return fail(c, SAS_ERR_INVALID, "bad mesh sizes: %lld vertices, %lld triangles", (long long)n_vertices, (long long)n_triangles);
+    if (!std::isfinite(ambient) || !std::isfinite(diffuse)) return fail(c, SAS_ERR_INVALID, "ambient and diffuse must be finite");
+    if (n_triangles > 0 && (!vertices || !triangles || !colors || !group)) return fail(c, SAS_ERR_INVALID, "vertices, triangles, colors and group are required");
+    HIP_TRY(c, hipSetDevice(c->device));
+    {
+        const int rcw = complete_all(c);   // frames in flight read the meshes
+        if (rcw) return rcw;
+    }
+    if (n_triangles == 0) {
+        c->has_mesh = false;
+        return SAS_OK;
+    }
+    const size_t nv = (size_t)n_vertices, nt = (size_t)n_triangles;
+    std::vector<float> v(3 * nv), col(3 * nt);
+    std::vector<int32_t> tri(3 * nt);
+    std::vector<uint8_t> g(nt);
+    if (nv) HIP_TRY(c, hipMemcpy(v.data(), vertices, sizeof(float) * 3 * nv, hipMemcpyDefault));
+    HIP_TRY(c, hipMemcpy(tri.data(), triangles, sizeof(int32_t) * 3 * nt, hipMemcpyDefault));
+    HIP_TRY(c, hipMemcpy(col.data(), colors, sizeof(float) * 3 * nt, hipMemcpyDefault));
+    HIP_TRY(c, hipMemcpy(g.data(), group, nt, hipMemcpyDefault));
+    const int ng = std::max(1, c->scene.n_groups);
+    std::vector<float4> v4(nv), c4(nt);
+    std::vector<int4> t4(nt);
+    for (size_t i = 0; i < nv; ++i) v4[i] = make_float4(v[3 * i], v[3 * i + 1], v[3 * i + 2], 0.0f);
+    for (size_t t = 0; t < nt; ++t) {
+        for (int k = 0; k < 3; ++k)
+            if (tri[3 * t + k] < 0 || (int64_t)tri[3 * t + k] >= n_vertices)
+                return fail(c, SAS_ERR_INVALID, "triangles[%zu][%d]=%d out of [0,%lld)", t, k, tri[3 * t + k], (long long)n_vertices);
+        if (g[t] >= ng) return fail(c, SAS_ERR_INVALID, "group[%zu]=%d >= %d pose groups", t, (int)g[t], ng);
+        t4[t] = make_int4(tri[3 * t], tri[3 * t + 1], tri[3 * t + 2], (int)g[t]);
+        c4[t] = make_float4(col[3 * t], col[3 * t + 1], col[3 * t + 2], 0.0f);
+    }
+    // validated: only now are the previous meshes replaced (a rejected call leaves them in place; a failed device copy
+    // below leaves none)
+    c->has_mesh = false;
+    int rc;
+    if ((rc = ensure(c, c->mesh_vert, sizeof(float4) * std::max<size_t>(nv, 1)))) return rc;
+    if ((rc = ensure(c, c->mesh_tri, sizeof(int4) * nt))) return rc;
+    if ((rc = ensure(c, c->mesh_col, sizeof(float4) * nt))) return rc;
+    if (nv) HIP_TRY(c, hipMemcpy(c->mesh_vert.p, v4.data(), sizeof(float4) * nv, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->mesh_tri.p, t4.data(), sizeof(int4) * nt, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->mesh_col.p, c4.data(), sizeof(float4) * nt, hipMemcpyHostToDevice));
+    c->mesh = SasMeshScene{};
+    c->mesh.vert = (const float4 *)c->mesh_vert.p;
+    c->mesh.tri = (const int4 *)c->mesh_tri.p;
+    c->mesh.color = (const float4 *)c->mesh_col.p;
+    c->mesh.nv = (int)n_vertices;
+    c->mesh.nt = (int)n_triangles;
+    c->mesh.n_groups = c->scene.n_groups;
+    c->mesh.ka = ambient;
+    c->mesh.kd = diffuse;
+    for (Slot &sl : c->slots) sl.mcap = 0;   // re-derive the list capacity for the new meshes
+    c->has_mesh = true;
+    return SAS_OK;
 }
 
 int sas_render_rgbd(sas_ctx *c, const float *viewmat, const float *K, int width, int height, const float *background,
@@ -1351,6 +1479,7 @@ static int render_batch_impl(sas_ctx *c, int n_views, const float *viewmats, con
                              uint8_t *rgb8_host, void *stream, const PoseSets &ps = PoseSets())
 {
     if (!c) return SAS_ERR_INVALID;
+    if (c->has_mesh) flags |= SAS_FULL_SORT;   // one view per frame (sas_scene_meshes)
     if (n_views < 0 || (n_views > 0 && (!viewmats || !Ks))) return fail(c, SAS_ERR_INVALID, "bad view batch");
     if (ps.Rt) {
         if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
@@ -1419,6 +1548,7 @@ static int render_batch_host_impl(sas_ctx *c, int n_views, const float *viewmats
 {
     if (!c) return SAS_ERR_INVALID;
     if (!rgb8_host || (flags & SAS_ASYNC)) return fail(c, SAS_ERR_INVALID, "sas_render_batch_host: host buffer required, blocking only");
+    if (c->has_mesh) flags |= SAS_FULL_SORT;   // (sas_scene_meshes)
     if (n_views <= 0) return n_views == 0 ? SAS_OK : fail(c, SAS_ERR_INVALID, "bad view batch");
     if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "bad image size");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1491,14 +1621,17 @@ int sas_frames_completed(sas_ctx *c, int64_t *submitted, int64_t *completed)
 #ifdef SAS_DEBUG_BOUNDS
 extern "C" int sas_debug_bounds_kernels(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_tiles(unsigned long long *out, int reset);
+extern "C" int sas_debug_bounds_mesh(unsigned long long *out, int reset);
 /* Bounds-checked build only: out[0] = guarded accesses found out of range since the last reset (they were
  * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none). */
 int sas_debug_bounds(unsigned long long *out, int reset)
 {
-    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-    if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset)) return SAS_ERR_HIP;
-    const unsigned long long *first = a[0] ? a : b;
-    out[0] = a[0] + b[0];
+    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0};
+    if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset) ||
+        sas_debug_bounds_mesh(m, reset))
+        return SAS_ERR_HIP;
+    const unsigned long long *first = a[0] ? a : (b[0] ? b : m);
+    out[0] = a[0] + b[0] + m[0];
     out[1] = first[1]; out[2] = first[2]; out[3] = first[3];
     return SAS_OK;
 }

@@ -234,3 +234,36 @@ static inline size_t sas_count_stride(int tiles) { return (((size_t)tiles + 1 + 
 // [tickets][8 statistics words + 16 class cursors + 8 pad][tile_count][tile_big]
 static inline size_t sas_counter_ints(int tiles) { return SAS_TICKET_INTS + 32 + 2 * sas_count_stride(tiles); }
 static inline size_t sas_tile_stride(int tiles) { return ((size_t)tiles + 1 + 3) & ~(size_t)3; }
+
+// Triangle meshes (sas_scene_meshes; DESIGN.md 3, "Meshes").  A frame of a context that holds meshes is a SAS_FULL_SORT frame
+// plus three launches in front of its k_blend: k_mesh_setup (one thread per triangle: pose, view, near clip at kNear, shading,
+// screen-space records, per-tile counts), k_mesh_scan (offsets; overflow of the list capacity to the pinned status words) and
+// k_mesh_scatter (record indices into per-tile lists).  k_blend_mesh then resolves every pixel's nearest triangle in its tile
+// prologue and composites the splats in front of it.
+// A record (4 float4 per clipped triangle, 2 per triangle: a triangle crossing the near plane leaves at most two):
+//   [0] (a0, b0, c0, a1) [1] (b1, c1, a2, b2) [2] (c2, za, zb, zc) [3] (r, g, b, -)
+// edge i: E_i(x, y) = a_i x + b_i y + c_i > 0 inside (ties: a_i > 0, or a_i == 0 and b_i > 0; (a_i, b_i) a unit vector),
+// 1/z = za x + zb y + zc, at the pixel centre (x + 0.5, y + 0.5) taken relative to the image centre (W/2, H/2).  Its tile rectangle is kept beside it (x0, y0, x1, y1; x0 > x1: no record).
+struct SasMeshScene {
+    const float4 *vert;     // [nv] mesh-local vertices (x, y, z, 0), the handle's scale applied
+    const int4 *tri;        // [nt] (i0, i1, i2, pose group)
+    const float4 *color;    // [nt] (r, g, b, 0)
+    int nv, nt;
+    int n_groups;           // the scene's (0: no splat groups, every triangle unposed)
+    float ka, kd;
+};
+struct SasMeshFrame {
+    float4 *rec;            // [2 nt * 4]
+    int4 *rect;             // [2 nt]
+    int *tile_count;        // [tiles] zeroed in front of the setup
+    int *tile_offset;       // [tiles + 1]
+    int *tile_cursor;       // [tiles]
+    int *list;              // [cap]
+    long long cap;
+    int n_rec;              // 2 nt
+    unsigned *status_host;  // pinned [2]: [0] entries the lists needed, [1] 1 when that exceeds cap
+};
+void sas_launch_mesh_bin(hipStream_t st, const SasMeshScene &m, const SasParams &P, const SasFrame &f, const SasMeshFrame &mf);
+// sas_launch_blend for a frame with meshes
+void sas_launch_blend_mesh(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
+                           const SasMeshFrame &mf, bool fast_exp, bool want_max);

@@ -1,0 +1,199 @@
+// sas_mesh.hip -- triangle meshes of a frame (sas_scene_meshes; DESIGN.md 3, "Meshes"): setup, binning.
+// The per-pixel resolution and the occlusion of the splats are k_blend_mesh's (sas_tile.hip).
+#include "sas_device.h"
+
+namespace {
+
+constexpr int kMeshSetupThreads = 256;
+constexpr int kMeshScanThreads = 1024;
+
+struct Vc { double x, y, z; };   // a camera-frame vertex
+
+// Screen-space record of one clipped triangle (camera-frame vertices, z >= kNear).  false: degenerate or off screen.
+DEV bool mesh_record(const SasCam &c, const Vc *q, float4 *rec, int4 &rect)
+{
+    double u[3], v[3], w[3];
+    for (int k = 0; k < 3; ++k) {
+        w[k] = 1.0 / q[k].z;
+        u[k] = (double)c.fx * q[k].x * w[k] + (double)c.cx;
+        v[k] = (double)c.fy * q[k].y * w[k] + (double)c.cy;
+    }
+    double area = (u[1] - u[0]) * (v[2] - v[0]) - (u[2] - u[0]) * (v[1] - v[0]);
+    if (!(fabs(area) > 0.0) || !isfinite(area)) return false;
+    if (area < 0.0) {   // counter-clockwise in (u, v): inside is E > 0 on every edge
+        double t;
+        t = u[1]; u[1] = u[2]; u[2] = t;
+        t = v[1]; v[1] = v[2]; v[2] = t;
+        t = w[1]; w[1] = w[2]; w[2] = t;
+        area = -area;
+    }
+    double umin = fmin(u[0], fmin(u[1], u[2])), umax = fmax(u[0], fmax(u[1], u[2]));
+    double vmin = fmin(v[0], fmin(v[1], v[2])), vmax = fmax(v[0], fmax(v[1], v[2]));
+    // pixel centres x + 0.5 in [umin, umax]
+    if (umax < 0.5 || vmax < 0.5 || umin > (double)c.W - 0.5 || vmin > (double)c.H - 0.5) return false;
+    // Planes in the frame of the image centre (xo, yo), edges normalised: E is the signed distance in pixels, and c the distance
+    // of the centre from the edge's line -- small for every edge that passes the image, however far its ends project (a
+    // triangle clipped at the near plane of a wrist camera), so float32 keeps E's error far below 1e-3 px on screen.
+    const double xo = 0.5 * (double)c.W, yo = 0.5 * (double)c.H;
+    float e[9];
+    for (int i = 0; i < 3; ++i) {
+        const int j = (i + 1) % 3;
+        const double a0 = v[i] - v[j], b0 = u[j] - u[i];
+        const double len = sqrt(a0 * a0 + b0 * b0);
+        if (!(len > 0.0)) return false;
+        const double a = a0 / len, b = b0 / len;
+        // c from the edge's lexicographically smaller end: the same edge walked the other way (a neighbour) gets exactly -a, -b, -c,
+        // so E is exactly negated and the tie rule gives a shared edge's pixel centre to one of the two
+        const bool ifirst = u[i] < u[j] || (u[i] == u[j] && v[i] < v[j]);
+        const double ue = ifirst ? u[i] : u[j], ve = ifirst ? v[i] : v[j];
+        e[3 * i + 0] = (float)a;
+        e[3 * i + 1] = (float)b;
+        e[3 * i + 2] = (float)(-(a * (ue - xo) + b * (ve - yo)));
+    }
+    // 1/z = za (x - xo) + zb (y - yo) + zc through the three vertices (zc: 1/z at the image centre)
+    const double za = ((w[1] - w[0]) * (v[2] - v[0]) - (w[2] - w[0]) * (v[1] - v[0])) / area;
+    const double zb = ((u[1] - u[0]) * (w[2] - w[0]) - (u[2] - u[0]) * (w[1] - w[0])) / area;
+    const double zc = w[0] + za * (xo - u[0]) + zb * (yo - v[0]);
+    rec[0] = make_float4(e[0], e[1], e[2], e[3]);
+    rec[1] = make_float4(e[4], e[5], e[6], e[7]);
+    rec[2] = make_float4(e[8], (float)za, (float)zb, (float)zc);
+    // tiles whose pixel centres the rectangle can hold
+    const double lo_x = fmax(umin - 0.5, 0.0), hi_x = fmin(umax - 0.5, (double)c.W - 1.0);
+    const double lo_y = fmax(vmin - 0.5, 0.0), hi_y = fmin(vmax - 0.5, (double)c.H - 1.0);
+    rect = make_int4((int)floor(lo_x) / SAS_TILE, (int)floor(lo_y) / SAS_TILE, (int)ceil(hi_x) / SAS_TILE, (int)ceil(hi_y) / SAS_TILE);
+    rect.z = min(rect.z, c.tw - 1);
+    rect.w = min(rect.w, c.th - 1);
+    return rect.x <= rect.z && rect.y <= rect.w;
+}
+
+// One thread per triangle: group pose and view (float, as the projection moves the Gaussians), shading, near clip, records
+// 2 t and 2 t + 1, per-tile counts.
+__global__ __launch_bounds__(kMeshSetupThreads) void k_mesh_setup(SasMeshScene m, SasParams P, SasFrame f, SasMeshFrame mf)
+{
+    const int t = blockIdx.x * kMeshSetupThreads + threadIdx.x;
+    if (t >= m.nt) return;
+    const SasCam &c = P.cam;
+    int4 none = make_int4(1, 0, 0, 0);
+    mf.rect[2 * t] = none;
+    mf.rect[2 * t + 1] = none;
+    const int4 tr = m.tri[t];
+    const int g = tr.w;
+    const float *G = (f.group_Rt && g >= 0 && g < m.n_groups) ? f.group_Rt + 12 * g : nullptr;
+    float wv[3][3];
+    Vc q[3];
+    bool ok = true;
+    const int ids[3] = {tr.x, tr.y, tr.z};
+    for (int k = 0; k < 3; ++k) {
+        if (!SAS_IN(ids[k], m.nv, 301)) return;
+        const float4 p = m.vert[ids[k]];
+        float x = p.x, y = p.y, z = p.z;
+        if (G) {
+            const float x2 = affine3(G[0], G[1], G[2], G[3], x, y, z), y2 = affine3(G[4], G[5], G[6], G[7], x, y, z),
+                        z2 = affine3(G[8], G[9], G[10], G[11], x, y, z);
+            x = x2; y = y2; z = z2;
+        }
+        wv[k][0] = x; wv[k][1] = y; wv[k][2] = z;
+        q[k].x = affine3(c.R[0], c.R[1], c.R[2], c.t[0], x, y, z);
+        q[k].y = affine3(c.R[3], c.R[4], c.R[5], c.t[1], x, y, z);
+        q[k].z = affine3(c.R[6], c.R[7], c.R[8], c.t[2], x, y, z);
+        ok = ok && isfinite(q[k].x) && isfinite(q[k].y) && isfinite(q[k].z);
+    }
+    if (!ok) return;
+    // shading: |n . v|, n the unit world-space face normal (two-sided), v the unit ray from the camera centre to the centroid
+    const double e1[3] = {(double)wv[1][0] - wv[0][0], (double)wv[1][1] - wv[0][1], (double)wv[1][2] - wv[0][2]};
+    const double e2[3] = {(double)wv[2][0] - wv[0][0], (double)wv[2][1] - wv[0][1], (double)wv[2][2] - wv[0][2]};
+    double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+    const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (!(nn > 0.0) || !isfinite(nn)) return;   // degenerate
+    double d[3];
+    for (int i = 0; i < 3; ++i) d[i] = ((double)wv[0][i] + (double)wv[1][i] + (double)wv[2][i]) / 3.0 - (double)c.campos[i];
+    const double dn = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    const double ndv = dn > 0.0 ? fabs(n[0] * d[0] + n[1] * d[1] + n[2] * d[2]) / (nn * dn) : 1.0;
+    const double shade = (double)m.ka + (double)m.kd * ndv;
+    const float4 col = m.color[t];
+    const float cr = (float)fmin(fmax((double)col.x * shade, 0.0), 1.0), cg = (float)fmin(fmax((double)col.y * shade, 0.0), 1.0),
+                cb = (float)fmin(fmax((double)col.z * shade, 0.0), 1.0);
+    // near clip: the polygon's vertices in order, each edge that crosses z = kNear cut from its inside end
+    Vc poly[4];
+    int np = 0;
+    for (int k = 0; k < 3; ++k) {
+        const Vc &a = q[k], &b = q[(k + 1) % 3];
+        const bool ain = a.z >= (double)kNear, bin = b.z >= (double)kNear;
+        if (ain) poly[np++] = a;
+        if (ain != bin) {
+            const Vc &i = ain ? a : b, &o = ain ? b : a;
+            const double s = ((double)kNear - i.z) / (o.z - i.z);
+            poly[np++] = Vc{i.x + s * (o.x - i.x), i.y + s * (o.y - i.y), (double)kNear};
+        }
+    }
+    for (int k = 0; k + 2 < np; ++k) {   // fan: one triangle, or two
+        const Vc tri3[3] = {poly[0], poly[k + 1], poly[k + 2]};
+        const int r = 2 * t + k;
+        int4 rect;
+        if (!mesh_record(c, tri3, mf.rec + 4 * r, rect)) continue;
+        mf.rec[4 * r + 3] = make_float4(cr, cg, cb, 0.0f);
+        mf.rect[r] = rect;
+        for (int ty = rect.y; ty <= rect.w; ++ty)
+            for (int tx = rect.x; tx <= rect.z; ++tx) atomicAdd(&mf.tile_count[ty * c.tw + tx], 1);
+    }
+}
+
+// One workgroup: exclusive scan of the tile counts into offsets and cursors; the total and the overflow flag to the host.
+__global__ __launch_bounds__(kMeshScanThreads) void k_mesh_scan(SasMeshFrame mf, int tiles)
+{
+    __shared__ int s_w[kMeshScanThreads / 64];
+    __shared__ int s_base;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int at = 0; at < tiles; at += kMeshScanThreads) {
+        const int i = at + tid;
+        const int v = i < tiles ? mf.tile_count[i] : 0;
+        const int inc = (int)wave_inclusive_sum_u32((unsigned)v);
+        if (lane == 63) s_w[wv] = inc;
+        __syncthreads();
+        int before = s_base;
+        for (int k = 0; k < wv; ++k) before += s_w[k];
+        if (i < tiles) {
+            mf.tile_offset[i] = before + inc - v;
+            mf.tile_cursor[i] = before + inc - v;
+        }
+        __syncthreads();
+        if (tid == kMeshScanThreads - 1) s_base = before + inc;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        mf.tile_offset[tiles] = s_base;
+        mf.status_host[0] = (unsigned)s_base;
+        mf.status_host[1] = (long long)s_base > mf.cap ? 1u : 0u;
+    }
+}
+
+// One thread per record: its index into the list of every tile of its rectangle (the order inside a list is free: k_blend_mesh
+// keeps the minimum of (depth bits, triangle) whatever the order).
+__global__ __launch_bounds__(kMeshSetupThreads) void k_mesh_scatter(SasMeshFrame mf, int n_rec, int tw)
+{
+    const int r = blockIdx.x * kMeshSetupThreads + threadIdx.x;
+    if (r >= n_rec) return;
+    const int4 rect = mf.rect[r];
+    for (int ty = rect.y; ty <= rect.w; ++ty)
+        for (int tx = rect.x; tx <= rect.z; ++tx) {
+            const int pos = atomicAdd(&mf.tile_cursor[ty * tw + tx], 1);
+            if (pos < mf.cap && SAS_IN(pos, mf.cap, 302)) mf.list[pos] = r;
+        }
+}
+
+}  // namespace
+
+SAS_BOUNDS_ACCESSOR(sas_debug_bounds_mesh)
+
+void sas_launch_mesh_bin(hipStream_t st, const SasMeshScene &m, const SasParams &P, const SasFrame &f, const SasMeshFrame &mf)
+{
+    const int tiles = P.cam.tw * P.cam.th;
+    (void)hipMemsetAsync(mf.tile_count, 0, sizeof(int) * (size_t)tiles, st);
+    const unsigned g1 = (unsigned)((m.nt + kMeshSetupThreads - 1) / kMeshSetupThreads);
+    const unsigned g2 = (unsigned)((2 * m.nt + kMeshSetupThreads - 1) / kMeshSetupThreads);
+    hipLaunchKernelGGL(k_mesh_setup, dim3(g1), dim3(kMeshSetupThreads), 0, st, m, P, f, mf);
+    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kMeshScanThreads), 0, st, mf, tiles);
+    hipLaunchKernelGGL(k_mesh_scatter, dim3(g2), dim3(kMeshSetupThreads), 0, st, mf, 2 * m.nt, P.cam.tw);
+}

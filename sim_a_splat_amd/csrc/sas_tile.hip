@@ -620,9 +620,13 @@ DEV BlendLds blend_lds(unsigned char *raw)
 // KEEP IN STEP: k_blend_features (end of this file) restates this loop's per-pixel chain entry by entry -- which entries a
 // lane takes (block mask, a block whose pixels have all terminated at the start of a batch), alpha, the 1/255 skip, the stop
 // rule and the fma_ order of p.r -- so that feature channels get exactly these weights (tests/test_gpu_f_features.py).
-template <bool FAST_EXP, typename SlotAt>
+// MESH (k_blend_mesh): `zlim` is the depth of the pixel's nearest triangle (+Inf: none).  The first entry whose depth is
+// >= zlim ends the pixel as the transmittance stop does: it is not added, nor is anything after it.  k_blend_features
+// has no such rule: feature frames of a context with meshes are refused (sas_render_features).
+template <bool FAST_EXP, bool MESH = false, typename SlotAt>
 DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const PixConst pc, int count, SlotAt slot_at,
-                     const BlendLds &L, PixState &p, bool &wdone, unsigned long long &ph_lap_, unsigned &sync_phase)
+                     const BlendLds &L, PixState &p, bool &wdone, unsigned long long &ph_lap_, unsigned &sync_phase,
+                     float zlim = 0.0f)
 {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     float4 ra = make_float4(0, 0, 0, 0), rb = ra, rc = ra;
@@ -814,7 +818,18 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
                 const float nT1 = nT0 - w1;
                 float vis0 = w0, vis1 = w1, Tn = nT1;
                 bool all_dead = false;
-                if (__ballot(nT1 <= kTStop)) {   // 31 % of the trips at configs 2 and 3
+                if constexpr (MESH) {
+                    // an entry at or behind the pixel's triangle (depth >= zlim) stops the pixel as the transmittance test does
+                    const bool cut0 = t.C0.w >= zlim, cut1 = t.C1.w >= zlim;
+                    if (__ballot(nT1 <= kTStop || cut0 || cut1)) {
+                        const bool stop0 = nT0 <= kTStop || cut0, stopped = nT1 <= kTStop || cut0 || cut1;
+                        vis0 = stop0 ? 0.0f : w0;
+                        vis1 = stopped ? 0.0f : w1;
+                        Tn = stop0 ? p.T : (stopped ? nT0 : nT1);
+                        if (stopped) p.x = __builtin_nanf("");
+                        all_dead = __all(pix_dead(p));
+                    }
+                } else if (__ballot(nT1 <= kTStop)) {   // 31 % of the trips at configs 2 and 3
                     // the splat that ends a pixel is not added, and the pixel takes nothing after it
                     // (a live pixel has T > 1e-4, so a skipped splat never stops it)
                     const bool stop0 = nT0 <= kTStop, stopped = nT1 <= kTStop;
@@ -1164,6 +1179,73 @@ __global__ __launch_bounds__(256) void k_blend(SasParams P, SasFrame f, long lon
         if (o.rgb8_host) store_rows_to_host<16>(o.rgb8_host, c.W, tx * SAS_TILE, ty * SAS_TILE, ox, oy, true, packed, s_raw);
         if (WANT_MAX) store_tile_max(f, tile, ED, s_wmax);
         if (tid == 0) { f.tile_count[tile] = 0; f.tile_big[tile] = 0; }   // the frame's counters leave the frame zeroed (SasFrame invariant)
+    }
+}
+
+// k_blend for a frame with meshes (its lists, records and tiles as k_blend's; SAS_FULL_SORT frames deliver no rgb8 to the
+// host from the tile kernel).  In the tile prologue every thread resolves its own pixel over its tile's triangle list: the
+// minimum of (depth bits, record) among the records whose interior holds the pixel centre, whatever the list's order (no
+// z-buffer, no atomics).  The splats are then composited in front of that depth (blend_range<.., MESH>), and the triangle's
+// colour takes the background's place in write_pixel.
+template <bool FAST_EXP, bool WANT_MAX>
+__global__ __launch_bounds__(256) void k_blend_mesh(SasParams P, SasFrame f, long long n_gauss, const int *tl, const int *range,
+                                                    SasMeshFrame M)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kBlendLdsBytes];
+    __shared__ unsigned s_wmax[4];
+    const SasCam &c = P.cam;
+    const BlendLds L = blend_lds(s_raw);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    unsigned sync_phase = 0u;
+    for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x) {
+        const int tile = tl[oi];
+        const int tx = tile % c.tw, ty = tile / c.tw;
+        int ox, oy;
+        pixel_of(wv, lane, ox, oy);
+        const int ix = tx * SAS_TILE + ox, iy = ty * SAS_TILE + oy;
+        const bool inside = ix < c.W && iy < c.H;
+        // the pixel's triangle (records 2 t, 2 t + 1 belong to triangle t: the record index orders triangles as their index does)
+        // the pixel centre in the records' frame (the image centre; exact: halves of integers)
+        const float px = ((float)ix + 0.5f) - 0.5f * c.Wf, py = ((float)iy + 0.5f) - 0.5f * c.Hf;
+        unsigned long long best = ~0ull;
+        const long long mb = M.tile_offset[tile];
+        long long me = M.tile_offset[tile + 1];
+        if (me > M.cap) me = M.cap;
+        for (long long i = mb; i < me; ++i) {
+            const int r = M.list[i];
+            if (!SAS_IN(r, M.n_rec, 311)) continue;
+            const float4 r0 = M.rec[4 * r], r1 = M.rec[4 * r + 1], r2 = M.rec[4 * r + 2];
+            const float e0 = r0.x * px + r0.y * py + r0.z, e1 = r0.w * px + r1.x * py + r1.y, e2 = r1.z * px + r1.w * py + r2.x;
+            // top-left rule: an edge through the centre holds it when (a > 0) or (a == 0 and b > 0)
+            const bool in0 = e0 > 0.0f || (e0 == 0.0f && (r0.x > 0.0f || (r0.x == 0.0f && r0.y > 0.0f)));
+            const bool in1 = e1 > 0.0f || (e1 == 0.0f && (r0.w > 0.0f || (r0.w == 0.0f && r1.x > 0.0f)));
+            const bool in2 = e2 > 0.0f || (e2 == 0.0f && (r1.z > 0.0f || (r1.z == 0.0f && r1.w > 0.0f)));
+            const float iz = r2.y * px + r2.z * py + r2.w;
+            if (in0 && in1 && in2 && iz > 0.0f) {
+                const unsigned long long key = ((unsigned long long)__float_as_uint(1.0f / iz) << 32) | (unsigned)r;
+                best = key < best ? key : best;
+            }
+        }
+        float zlim = __builtin_inff();
+        SasOutputs o = P.out;
+        if (best != ~0ull) {
+            zlim = __uint_as_float((unsigned)(best >> 32));
+            const float4 m3 = M.rec[4 * (long long)(unsigned)(best & 0xffffffffu) + 3];
+            o.bg[0] = m3.x; o.bg[1] = m3.y; o.bg[2] = m3.z;
+        }
+        PixState p = pix_init(inside, ox);
+        bool wdone = __all(!inside);
+        const long long beg = f.tile_offset[tile];
+        long long end = f.tile_offset[tile + 1];
+        if (end > f.cap) end = f.cap;
+        const int *ids = f.sorted_ids + beg;
+        unsigned long long ph_lap_ = 0ull;
+        blend_range<FAST_EXP, true>(f, n_gauss, tx, ty, pix_const(ox, oy), (int)(end - beg),
+                                    [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, zlim);
+        unsigned packed;
+        const float ED = write_pixel(o, p, inside, ix, iy, c.W, packed);
+        if (WANT_MAX) store_tile_max(f, tile, ED, s_wmax);
+        if (tid == 0) { f.tile_count[tile] = 0; f.tile_big[tile] = 0; }   // (SasFrame invariant)
     }
 }
 
@@ -1750,6 +1832,21 @@ void sas_launch_blend(hipStream_t st, const SasScene &s, int tiles, const SasPar
 {
     const long long n = s.n > 0 ? s.n : 1;
     blend_list(st, (unsigned)tiles, P, f, n, f.tile_order, f.sort_class + 4, fast_exp, want_max);
+}
+
+void sas_launch_blend_mesh(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
+                           const SasMeshFrame &mf, bool fast_exp, bool want_max)
+{
+    const long long n = s.n > 0 ? s.n : 1;
+    const dim3 grid((unsigned)tiles), blk(256);
+    const int *tl = f.tile_order, *range = f.sort_class + 4;
+    if (fast_exp) {
+        if (want_max) hipLaunchKernelGGL((k_blend_mesh<true, true>), grid, blk, 0, st, P, f, n, tl, range, mf);
+        else hipLaunchKernelGGL((k_blend_mesh<true, false>), grid, blk, 0, st, P, f, n, tl, range, mf);
+    } else {
+        if (want_max) hipLaunchKernelGGL((k_blend_mesh<false, true>), grid, blk, 0, st, P, f, n, tl, range, mf);
+        else hipLaunchKernelGGL((k_blend_mesh<false, false>), grid, blk, 0, st, P, f, n, tl, range, mf);
+    }
 }
 
 // Production path: lazy ordering + compositing of every tile in one launch.

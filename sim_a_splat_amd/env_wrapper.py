@@ -36,11 +36,13 @@ from .handler import CameraRig, SplatHandler
 class SplatEnvWrapper:
     def __init__(self, env, splat_assets_path: Optional[str] = None, match_object_name: Optional[str] = None,
                  splat_config_name: Optional[str] = None, task_assets_path: Optional[str] = None,
-                 task_assets_name: Optional[str] = None, *, splat_handler: Optional[SplatHandler] = None, device=0):
+                 task_assets_name: Optional[str] = None, *, splat_handler: Optional[SplatHandler] = None, device=0,
+                 meshes=()):
         """``splat_handler`` (keyword-only, not in the reference): a handler built elsewhere -- from arrays, or
         shared between vectorised envs -- instead of loading the assets named by the path arguments."""
         self.env = env
         self._device = device
+        self._meshes = tuple(meshes)   # SplatHandler(meshes=...): task / robot meshes in the frames
         self.draw_msg = None
         self._rig: Optional[CameraRig] = None
         if splat_handler is not None:
@@ -83,7 +85,7 @@ class SplatEnvWrapper:
                                           u.package_name, u.urdf_name, task_assets_path=task_assets_path,
                                           task_assets_name=task_assets_name,
                                           sim_robot_weld_frame_transform=getattr(u, "weld_frame_transform", None),
-                                          device=self._device)
+                                          device=self._device, meshes=self._meshes)
         logging.info("splat scene ready: %d Gaussians in %d groups", self.splat_handler.means.shape[0],
                      len(self.splat_handler.splat_links_handler) + 1)
         return self.splat_handler.scene     # the renderer is in-process: no client to wait for (wait_steps unused)

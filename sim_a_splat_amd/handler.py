@@ -39,6 +39,28 @@ def _translation_of(x) -> np.ndarray:
     return np.asarray(x, dtype=np.float64).reshape(3)
 
 
+TASK_MESH_COLOR = (0.956, 0.396, 0.365)   # splat_handler.py:205
+
+
+def _mesh_arrays(meshes, task_assets_path=None, task_assets_name=None) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
+    """``meshes`` as names or arrays -> ``{"task": (vertices, faces)}`` (mesh-local, unscaled)."""
+    from . import mesh_io
+    out: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
+    items = meshes.items() if isinstance(meshes, dict) else ((m, None) for m in (meshes or ()))
+    for name, val in items:
+        if name == "robot":
+            raise NotImplementedError("robot meshes (the URDF visuals) are not drawn yet; meshes=('task',) is")
+        if name != "task":
+            raise ValueError(f"unknown mesh {name!r}: 'task'")
+        if val is None:
+            if not task_assets_name:
+                raise ValueError("meshes=('task',) needs task_assets_path and task_assets_name")
+            val = mesh_io.load_mesh(f"{task_assets_path}/{task_assets_name}")
+        v, f = val
+        out["task"] = (np.asarray(v, np.float64).reshape(-1, 3), np.asarray(f, np.int64).reshape(-1, 3))
+    return out
+
+
 class SplatHandler:
     """``SplatHandler(splat_assets_path, match_object_name, splat_config_name, package_path, package_name,
     urdf_name, task_assets_path=None, task_assets_name=None, sim_robot_weld_frame_transform=..., server=None)``
@@ -49,15 +71,18 @@ class SplatHandler:
     * URDF ``{package_path}/{package_name}urdf/{urdf_name}`` (the reference concatenates exactly so, :52,148)
       for the visual-mesh forward kinematics;
     * ``server``: where the reference takes a viser server, this takes the object that plays ``server.scene`` +
-      the client, a ``SplatScene`` (created on ``device`` when None).  Task / robot meshes are not displayed
-      (viewer-only, out of scope); ``task_assets_*`` are accepted and kept for the Drake namespaces.
+      the client, a ``SplatScene`` (created on ``device`` when None);
+    * ``meshes`` (not in the reference, default ``()``: splats only): ``"task"`` composites the task object
+      ``{task_assets_path}/{task_assets_name}`` into every frame, in the reference's colour (0.956, 0.396, 0.365), scaled by the
+      ICP scale and posed by ``draw_handler`` as at :296-314 (``_add_task_meshes``, :199-219).  The robot's URDF visual
+      meshes (``"robot"``, :145-197) are not drawn yet: asking for them raises.
 
     ``SplatHandler.from_arrays`` builds the same object from arrays already in memory."""
 
     def __init__(self, splat_assets_path: str, match_object_name: str, splat_config_name: str, package_path: str,
                  package_name: str, urdf_name: str, task_assets_path: Optional[str] = None,
                  task_assets_name: Optional[str] = None, sim_robot_weld_frame_transform=None, server: Optional[SplatScene] = None,
-                 *, device=0, bounds=None):
+                 *, device=0, bounds=None, meshes=()):
         from pathlib import Path
         from . import io, urdf_fk
         from .covariance import GSplatLoader
@@ -72,8 +97,9 @@ class SplatHandler:
         keep = aabb_mask(loader.means.cpu().numpy(), bounds)
         arr = lambda t: t.cpu().numpy()[keep]
         masks = {k: np.asarray(v, dtype=bool)[keep] for k, v in masks.items()}
+        meshes = _mesh_arrays(meshes, task_assets_path, task_assets_name)
         self._setup(arr(loader.means), arr(loader.covs), arr(loader.colors), arr(loader.opacities), masks, icp, fk,
-                    instance_uid=match_object_name, weld=sim_robot_weld_frame_transform, scene=server, device=device)
+                    instance_uid=match_object_name, weld=sim_robot_weld_frame_transform, scene=server, device=device, meshes=meshes)
         self.masks_dir = str(masks_dir)
         self.robot_description_dir = robot_description_dir
         self.rbt_drake_namespace = f"plant::{urdf_name.split('.')[0]}::"                       # :58-60
@@ -82,16 +108,20 @@ class SplatHandler:
     @classmethod
     def from_arrays(cls, means, covs, colors, opacities, link_masks: Dict[str, np.ndarray], icp_transformation: np.ndarray,
                     fk_transforms: Sequence[np.ndarray], instance_uid: str = "robot", robot_num: int = 3,
-                    weld_translation=(0.0, 0.0, 0.0), scene: Optional[SplatScene] = None, device=0) -> "SplatHandler":
+                    weld_translation=(0.0, 0.0, 0.0), scene: Optional[SplatScene] = None, device=0, meshes=(),
+                    task_assets_path: Optional[str] = None, task_assets_name: Optional[str] = None) -> "SplatHandler":
         """The same handler from arrays: Gaussians [N,...], the per-link boolean masks ``link0..``, the 4x4 ICP
-        similarity and one 4x4 forward-kinematics pose per visual mesh at the mask-time joint configuration."""
+        similarity and one 4x4 forward-kinematics pose per visual mesh at the mask-time joint configuration.
+        ``meshes``: names (``"task"``: read from ``task_assets_path/task_assets_name``) or arrays,
+        ``{"task": (vertices [V,3], faces [F,3])}``."""
         self = cls.__new__(cls)
         self._setup(means, covs, colors, opacities, link_masks, icp_transformation, fk_transforms, instance_uid=instance_uid,
-                    weld=weld_translation, scene=scene, device=device, robot_num=robot_num)
+                    weld=weld_translation, scene=scene, device=device, robot_num=robot_num,
+                    meshes=_mesh_arrays(meshes, task_assets_path, task_assets_name))
         return self
 
     def _setup(self, means, covs, colors, opacities, link_masks, icp_transformation, fk_transforms, *, instance_uid, weld,
-               scene, device, robot_num: int = 3) -> None:
+               scene, device, robot_num: int = 3, meshes=None) -> None:
         self.scene = scene if scene is not None else SplatScene(device)
         self.server = self.scene                               # the reference's name for it (close(), clients)
         self.instance_uid = instance_uid
@@ -115,6 +145,12 @@ class SplatHandler:
         rest = ~self.robot_splat_idxs                          # "/scene_ohne_robot" (:112-119)
         self.scene_handle = self.scene.add_gaussian_splats("/scene_ohne_robot", means[rest], covs[rest], colors[rest],
                                                            opacities[rest])
+        # task mesh (_add_task_meshes, :199-219): vertices scaled by the ICP scale, the reference's colour, a pose row of its own
+        self.task_mesh_frame_handle = None
+        if meshes and "task" in meshes:
+            v, f = meshes["task"]
+            self.task_mesh_frame_handle = self.scene.add_mesh_simple(f"{instance_uid}/mesh_task/task", v, f, TASK_MESH_COLOR,
+                                                                     scale=self.scale_factor)
         # the draw message's pose algebra runs inside the library when the scene offers it (sas_set_link_poses)
         self._k_fast = min(len(self.fk), 7, len(self.splat_links_handler))
         self._fast = hasattr(self.scene, "set_link_poses") and self._k_fast > 0
@@ -139,10 +175,45 @@ class SplatHandler:
         masks = {k: np.asarray(v, dtype=bool)[keep] for k, v in masks.items()}
         return cls.from_arrays(arr(loader.means), arr(loader.covs), arr(loader.colors), arr(loader.opacities), masks, icp, fk, **kw)
 
+    def mesh_pose_rows(self, msg) -> Tuple[np.ndarray, np.ndarray]:
+        """The pose rows ``draw_handler(msg)`` gives this handler's meshes, WITHOUT touching the scene: ``(rows [m], [m,12]
+        float32)``.  Task mesh: the last entry with ``robot_num == blk_idx``, ``icp o SE3(q/|q|, p s)`` in float64 (:296-314),
+        through the handle's quaternion as ``draw_handler`` assigns it."""
+        h = self.task_mesh_frame_handle
+        if h is None:
+            return np.zeros(0, np.int64), np.zeros((0, 12), np.float32)
+        hits = [i for i in range(msg.num_links) if msg.robot_num[i] == self.blk_idx]
+        if not hits:
+            return np.zeros(0, np.int64), np.zeros((0, 12), np.float32)
+        wxyz, t = self._task_pose(msg, hits[-1])
+        row = np.zeros((1, 3, 4), np.float32)
+        row[0, :, :3] = poses.quat_wxyz_to_matrix(wxyz)
+        row[0, :, 3] = t
+        return np.array([h.index], np.int64), row.reshape(1, 12)
+
+    def _task_pose(self, msg, idx):
+        q = np.asarray(msg.quaternion[idx], dtype=np.float64)
+        q = q / np.linalg.norm(q)
+        R = self.Ri @ poses.quat_wxyz_to_matrix(q)
+        t = self.Ri @ (np.asarray(msg.position[idx], dtype=np.float64) * self.scale_factor) + self.ti
+        return poses.matrix_to_quat_wxyz(R), t
+
+    def _draw_meshes(self, msg) -> None:
+        h = self.task_mesh_frame_handle
+        if h is None:
+            return
+        for idx in range(msg.num_links):
+            if msg.robot_num[idx] == self.blk_idx:
+                wxyz, t = self._task_pose(msg, idx)
+                h.wxyz = wxyz
+                h.position = t
+
     def draw_handler(self, msg) -> None:
         """``msg``: lcmt_viewer_draw-shaped (num_links, robot_num[], position[][3], quaternion[][4] wxyz).  The
         k-th link of the robot (``robot_num == rbt_idx``, message order) drives splat group k, as in the reference
         (:227-314); all links are posed in one batch of small matrix products."""
+        if getattr(self, "task_mesh_frame_handle", None) is not None:
+            self._draw_meshes(msg)
         rn, rbt = msg.robot_num, self.rbt_idx
         idxs = [idx for idx in range(msg.num_links) if rn[idx] == rbt]
         if len(idxs) > len(self.fk):

@@ -112,6 +112,7 @@ class Rasterizer:
         self.n_groups = 0
         self.n_features = 0     # channels of the feature store (upload_features); 0: none for this scene
         self._features_onehot = False
+        self.n_mesh_triangles = 0   # triangles of the meshes (upload_meshes); 0: none for this scene
         self._keep = []  # outputs of in-flight async frames (the C ABI keeps up to four)
         self._argcache = {}  # id(argument) -> (argument, float32 array, address): _host_arg
 
@@ -172,6 +173,7 @@ class Rasterizer:
         self.n_groups = int(n_groups) if group_id is not None else 0
         self.n_features = 0     # (the upload forgot them)
         self._features_onehot = False
+        self.n_mesh_triangles = 0
 
     @_locked
     def upload_features(self, features: Optional[ArrayLike] = None) -> None:
@@ -190,6 +192,35 @@ class Rasterizer:
             torch.cuda.synchronize(f.device)   # device-resident inputs must be complete before the copy
         self._check(self._L.sas_scene_features(self._ctx, self.n, C, pf), "sas_scene_features")
         self.n_features, self._features_onehot = C, False
+
+    @_locked
+    def upload_meshes(self, vertices: ArrayLike, triangles: ArrayLike, colors: ArrayLike, groups: Optional[ArrayLike] = None,
+                      ambient: float = 0.4, diffuse: float = 0.6) -> None:
+        """Triangle meshes composited into every frame (sas_scene_meshes; DESIGN.md 3, "Meshes"): ``vertices [V,3]`` (mesh-local,
+        scale applied), ``triangles [T,3]`` vertex indices, ``colors [T,3]`` (or one ``[3]`` for all), ``groups [T]`` the pose
+        group moving each triangle (``None``: group 0).  Shading ``clamp(c (ambient + diffuse |n . v|), 0, 1)``.  Frames then take
+        the full-sort path.  A new ``upload`` forgets the meshes; ``T == 0`` clears them."""
+        host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+        v = np.ascontiguousarray(np.asarray(host(vertices), dtype=np.float32).reshape(-1, 3))
+        t = np.ascontiguousarray(np.asarray(host(triangles), dtype=np.int64).reshape(-1, 3))
+        if t.size and (t.min() < 0 or t.max() >= v.shape[0]):
+            raise ValueError(f"triangle indices out of [0,{v.shape[0]})")
+        t = np.ascontiguousarray(t.astype(np.int32))
+        T = t.shape[0]
+        c = np.asarray(host(colors), dtype=np.float32)
+        c = np.ascontiguousarray(np.broadcast_to(c.reshape(-1, 3) if c.size != 3 else c.reshape(1, 3), (T, 3)))
+        g = np.zeros(T, np.uint8) if groups is None else np.asarray(host(groups))
+        if g.size and (g.min() < 0 or g.max() > 255):
+            raise ValueError("mesh groups must be in [0,255]")
+        g = np.ascontiguousarray(np.broadcast_to(g.astype(np.uint8).reshape(-1), (T,)))
+        self._check(self._L.sas_scene_meshes(self._ctx, v.shape[0], v.ctypes.data, T, t.ctypes.data, c.ctypes.data, g.ctypes.data,
+                                             float(ambient), float(diffuse)), "sas_scene_meshes")
+        self.n_mesh_triangles = T
+
+    @_locked
+    def clear_meshes(self) -> None:
+        self._check(self._L.sas_scene_meshes(self._ctx, 0, None, 0, None, None, None, 0.4, 0.6), "sas_scene_meshes")
+        self.n_mesh_triangles = 0
 
     @_locked
     def set_group_poses(self, Rt: ArrayLike) -> None:

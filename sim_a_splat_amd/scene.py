@@ -67,6 +67,11 @@ class GaussianSplatHandle:
             self._write_row()
 
 
+class MeshHandle(GaussianSplatHandle):
+    """What ``add_mesh_simple`` / ``add_mesh_trimesh`` return: a triangle mesh on a pose row of its own (DESIGN.md 3,
+    "Meshes"), with the ``.wxyz`` / ``.position`` setters of a splat group.  Meshes and splat groups share the 256 rows."""
+
+
 _NO_OWNER_APPLIED = object()   # SplatScene._link_owner_applied: the library's context holds nobody's link constants
 
 
@@ -90,6 +95,7 @@ class SplatScene:
         self.lock = threading.RLock()
         self._raster = Rasterizer(device)
         self._groups: List[Dict[str, np.ndarray]] = []
+        self._meshes: List[Dict[str, np.ndarray]] = []   # vertices (scaled), faces, per-face colours, pose row
         self._handles: List[GaussianSplatHandle] = []
         self._uploaded = False
         self._poses_dirty = True
@@ -101,6 +107,7 @@ class SplatScene:
         self._link_consts: Dict[object, tuple] = {}
         self._link_owner_applied = _NO_OWNER_APPLIED
         self.background = tuple(background)
+        self.mesh_ambient, self.mesh_diffuse = 0.4, 0.6   # mesh shading ("Meshes"); set before the first render
         self.camera = _Camera()
 
     def add_gaussian_splats(self, name: str, centers, covariances, rgbs, opacities, wxyz=(1.0, 0.0, 0.0, 0.0),
@@ -111,6 +118,7 @@ class SplatScene:
             if len(self._groups) >= 256:
                 raise RuntimeError("at most 256 splat groups")
             self._groups.append(dict(
+                row=len(self._handles),
                 centers=c,
                 covariances=np.asarray(covariances, dtype=np.float32).reshape(n, 3, 3),
                 rgbs=np.asarray(rgbs, dtype=np.float32).reshape(n, 3),
@@ -123,6 +131,45 @@ class SplatScene:
             self._uploaded = False
             self._poses_dirty = True
         return h
+
+    def add_mesh_simple(self, name: str, vertices, faces, color=(0.5, 0.5, 0.5), wxyz=(1.0, 0.0, 0.0, 0.0),
+                        position=(0.0, 0.0, 0.0), scale: float = 1.0) -> MeshHandle:
+        """viser's ``scene.add_mesh_simple``: ``vertices [V,3]`` (times ``scale``), ``faces [F,3]``, one colour (or ``[F,3]``)."""
+        v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3) * float(scale)
+        f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+        col = np.asarray(color, dtype=np.float64)
+        col = col / 255.0 if col.dtype.kind in "iu" or col.max(initial=0.0) > 1.0 else col
+        col = np.broadcast_to(col.reshape(-1, 3) if col.size != 3 else col.reshape(1, 3), (f.shape[0], 3))
+        if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+            raise ValueError(f"{name}: face index out of range")
+        with self.lock:
+            if len(self._handles) >= 256:
+                raise RuntimeError("at most 256 splat groups and meshes")
+            h = MeshHandle(self, name, len(self._handles), wxyz, position)
+            self._meshes.append(dict(row=h.index, vertices=v.astype(np.float32), faces=f.astype(np.int32),
+                                     colors=np.ascontiguousarray(col, dtype=np.float32)))
+            self._handles.append(h)
+            self._Rt = np.concatenate([self._Rt, np.zeros((1, 3, 4), np.float32)], axis=0)
+            h._write_row()
+            self._uploaded = False
+            self._poses_dirty = True
+        return h
+
+    def add_mesh_trimesh(self, name: str, mesh, scale: float = 1.0, wxyz=(1.0, 0.0, 0.0, 0.0),
+                         position=(0.0, 0.0, 0.0)) -> MeshHandle:
+        """viser's ``scene.add_mesh_trimesh``, duck-typed: ``mesh.vertices``, ``mesh.faces`` and, when present,
+        ``mesh.visual.vertex_colors`` (RGB(A), 0-255 or 0-1) averaged over each face's three vertices."""
+        v = np.asarray(mesh.vertices, dtype=np.float64).reshape(-1, 3)
+        f = np.asarray(mesh.faces, dtype=np.int64).reshape(-1, 3)
+        vc = getattr(getattr(mesh, "visual", None), "vertex_colors", None)
+        if vc is not None and len(vc) == len(v):
+            vc = np.asarray(vc, dtype=np.float64)[:, :3]
+            if vc.max(initial=0.0) > 1.0:
+                vc = vc / 255.0
+            color = vc[f].mean(axis=1)
+        else:
+            color = (0.5, 0.5, 0.5)
+        return self.add_mesh_simple(name, v, f, color, wxyz=wxyz, position=position, scale=scale)
 
     # -- the draw message's pose algebra inside the library (SplatHandler.draw_handler's fast path) ---------------
     def set_link_constants(self, scale: float, Ri, ti, Rfk, tfk, weld=None, groups=None, owner=None) -> None:
@@ -163,19 +210,30 @@ class SplatScene:
     # -- internals ---------------------------------------------------------------------------
     def _sync(self) -> None:
         if not self._uploaded:
-            if not self._groups:
+            if not self._handles:
                 z = np.zeros
                 self._raster.upload(z((0, 3), np.float32), z((0,), np.float32), z((0, 3), np.float32),
                                     covariances=z((0, 6), np.float32), sh_degree=-1)
             else:
-                cat = lambda k: np.concatenate([g[k] for g in self._groups], axis=0)
-                gid = np.concatenate([np.full(g["centers"].shape[0], i, dtype=np.uint8) for i, g in enumerate(self._groups)])
-                self._raster.upload(cat("centers"), cat("opacities"), cat("rgbs"), covariances=cat("covariances"),
-                                    sh_degree=-1, group_id=gid, n_groups=len(self._groups))
+                # one pose row per handle (splat groups and meshes in creation order); group ids even for a single group
+                # whenever meshes exist, so that a mesh's row is a group of the scene
+                z = np.zeros
+                cat = lambda k, shape: np.concatenate([g[k] for g in self._groups], axis=0) if self._groups else z(shape, np.float32)
+                gid = np.concatenate([np.full(g["centers"].shape[0], g["row"], dtype=np.uint8) for g in self._groups]) \
+                    if self._groups else np.zeros(0, np.uint8)
+                self._raster.upload(cat("centers", (0, 3)), cat("opacities", (0,)), cat("rgbs", (0, 3)),
+                                    covariances=cat("covariances", (0, 6)), sh_degree=-1, group_id=gid, n_groups=len(self._handles))
+            if self._meshes:
+                off = np.cumsum([0] + [m["vertices"].shape[0] for m in self._meshes])[:-1]
+                self._raster.upload_meshes(np.concatenate([m["vertices"] for m in self._meshes]),
+                                           np.concatenate([m["faces"] + o for m, o in zip(self._meshes, off)]),
+                                           np.concatenate([m["colors"] for m in self._meshes]),
+                                           groups=np.concatenate([np.full(m["faces"].shape[0], m["row"], np.uint8) for m in self._meshes]),
+                                           ambient=self.mesh_ambient, diffuse=self.mesh_diffuse)
             self._uploaded = True
             self._poses_dirty = True
             self._link_owner_applied = _NO_OWNER_APPLIED    # a fresh upload: the context holds nobody's link constants
-        if self._poses_dirty and self._groups:
+        if self._poses_dirty and self._handles:
             self._raster.set_group_poses(self._Rt.reshape(-1, 12))
         self._poses_dirty = False
 

@@ -139,6 +139,9 @@ class SplatVecEnv:
         rows = self.scene.group_pose_rows()
         idx, link_rows = self.handler.link_pose_rows(msg)
         rows[idx] = link_rows
+        if hasattr(self.handler, "mesh_pose_rows"):   # the env's own task mesh pose
+            midx, mesh_rows = self.handler.mesh_pose_rows(msg)
+            rows[midx] = mesh_rows
         return rows
 
     def _submit(self, i: int, buf: torch.Tensor) -> None:
