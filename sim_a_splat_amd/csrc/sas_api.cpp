@@ -24,25 +24,30 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// Where one view's images go: device buffers of the caller, except rgb8_host.  A view carries them from the C ABI to
+// its slot as a whole (ViewCall -> RenderArgs); only the kernels' argument segment has a layout of its own (SasOutputs).
+struct ViewOut {
+    float *rgb = nullptr, *alpha = nullptr, *depth = nullptr;
+    uint8_t *rgb8 = nullptr;
+    float *points = nullptr;   // RGB-D tail (sas_render_rgbd)
+    uint8_t *mask = nullptr;
+    uint8_t *rgb8_host = nullptr;   // sas_render_batch_host: host copy of rgb8, made on the frame's stream
+    float *features = nullptr;      // sas_render_features: [H,W,feat_c] (device), composited behind the frame's k_blend
+};
+
 struct RenderArgs {
     float viewmat[16], K[9], bg[3];
     int W = 0, H = 0;
     unsigned flags = 0;
-    float *rgb = nullptr, *alpha = nullptr, *depth = nullptr;
-    uint8_t *rgb8 = nullptr;
-    uint8_t *rgb8_host = nullptr;   // sas_render_batch_host: host copy of rgb8, made on the frame's stream
-    float *points = nullptr;   // RGB-D tail (sas_render_rgbd)
-    uint8_t *mask = nullptr;
+    ViewOut out;
     float max_depth = 0.0f;
     bool use_max_depth = false;
     hipStream_t stream = nullptr;
     bool order_caller = true;  // the frame writes device buffers of the caller: it runs behind what the caller's stream holds, and the
                                // caller's stream is ordered behind it (false: frames delivered to host memory, sas_render_batch_host)
     bool solo = false;         // a blocking call for this one view with nothing else in flight: the caller waits for the frame's chain
-    float *features = nullptr; // sas_render_features: [H,W,feat_c] (device), composited behind the frame's k_blend
-    int feat_c = 0;
+    int feat_c = 0;            // channels of out.features
     float fbg[SAS_MAX_FEATURES];   // feature background, [feat_c]
-    bool valid = false;
 };
 
 }  // namespace
@@ -69,8 +74,10 @@ struct Scratch {
 // A frame writes its output buffers only after everything the caller had enqueued on `stream` at the
 // time of sas_render (its projection and binning, which touch only the scene and the slot's scratch,
 // do not wait for the caller); the caller's stream is made to wait for frame i when it is complete.
+// Frames reach the GPU through enqueue_launch alone, as a single view, a view pair (two slots, two streams, one
+// two-view projection) or a launch group (up to SAS_MAX_GROUP slots, every launch shared, the leader's stream).
 // A frame is: [group poses: one small upload kernel] projection (+ key emit, scan and tile order in its tail) [-> scatter: two-pass binning only] -> tile kernel
-// [-> depth tail] [-> host copy].  Parameters travel in the kernels' argument segments, the counters are left
+// [-> depth tail] [-> host copy] (enqueue_chain).  Parameters travel in the kernels' argument segments, the counters are left
 // zeroed by the tile kernel, the statistics reach the host through pinned words the projection's tail writes:
 // no memset, no upload and no read-back copy around a frame.
 struct Slot {
@@ -88,14 +95,14 @@ struct Slot {
     SasParams params{};
     bool busy = false, timed = false, timed_tiles = false;
     bool quad = false;   // the frame runs in the quad layout: projected, binned and composited in 8-pixel tiles (prepare_frame)
-    bool mesh = false;   // the frame composites the context's meshes (enqueue_frame): mesh_host tells whether its lists fit
+    bool mesh = false;   // the frame composites the context's meshes (enqueue_chain): mesh_host tells whether its lists fit
     DevBuf mrec, mrect, mtiles, mlist;   // its mesh scratch (SasMeshFrame): records, rectangles, [count | offset | cursor], lists
     long long mcap = 0;                  // entries mlist holds (grown like the splat keys when a frame outgrows it)
     unsigned *mesh_host = nullptr;       // pinned [2], written by k_mesh_scan
-    bool direct = false; // single-pass binning (SasFrame::seg > 0): the projection emits the keys, no scatter launch (prepare_frame)
-    bool host_direct = false;   // the tile kernel delivers the uint8 frame to pinned host memory itself
+    bool direct = false; // single-pass binning (SasFrame::seg > 0): the projection emits the keys, no scatter launch (choose_binning)
+    bool host_direct = false;   // the tile kernel delivers the uint8 frame to pinned host memory itself (host_direct_ok)
     bool info_kept = false;     // the frame's projection wrote info[] (SasFrame::keep_info): sas_read_projection need not project again
-    int group = 1;   // slots of the launch group this slot LEADS (enqueue_group); 0: member of the group led by an earlier slot
+    int group = 1;   // slots of the launch group this slot LEADS (enqueue_chain); 0: member of the group led by an earlier slot
 };
 
 constexpr int kMaxSlots = 8;
@@ -290,9 +297,24 @@ void make_cam(const float *V, const float *K, int W, int H, int tile_px, SasCam 
 // (a multiple of four ints and four to spare: the projection's tail reads both arrays with 16-byte loads)
 static size_t f_wg_stride(const sas_ctx *c) { return (((size_t)((c->scene.n + 255) / 256) + 3) & ~(size_t)3) + 4; }
 
-SasFrame frame_of(sas_ctx *c, Slot &sl, int tiles, bool keep_info = false)
+// Tiles of the slot's frame, at the frame's own binning: 16-pixel tiles, or the 8-pixel ones of the quad layout.
+int tiles_of(const Slot &sl) { return sl.cam.tw * sl.cam.th; }
+
+// Keys the slot's frame may write: its tiles' segments (single-pass binning), else what the compact lists hold.
+long long frame_cap(const Slot &sl) { return sl.direct ? (long long)tiles_of(sl) * sl.scr.seg : sl.scr.cap; }
+
+// Entries of the slot's key and id buffers: never fewer than the compact lists need, so a launch group that goes
+// two-pass as a whole (enqueue_launch) finds room in the buffers of its single-pass members.
+size_t key_slots(const Slot &sl) { return (size_t)std::max(frame_cap(sl), sl.scr.cap); }
+
+// What a buffer that a frame outgrew is grown to: the measured need + 25 % (`slack`: so that a tiny need does not
+// regrow step by step).
+long long grown(long long need, long long slack) { return need + need / 4 + slack; }
+
+SasFrame frame_of(sas_ctx *c, Slot &sl, bool keep_info = false)
 {
     Scratch &q = sl.scr;
+    const int tiles = tiles_of(sl);
     SasFrame f{};
     f.rec = (float4 *)q.rec.p;
     f.col = (float4 *)q.col.p;
@@ -313,7 +335,7 @@ SasFrame frame_of(sas_ctx *c, Slot &sl, int tiles, bool keep_info = false)
     f.keys = (unsigned long long *)q.keys.p;
     f.sorted_ids = (int *)q.ids.p;
     f.seg = sl.direct ? (int)q.seg : 0;
-    f.cap = sl.direct ? (long long)tiles * q.seg : q.cap;
+    f.cap = frame_cap(sl);
     f.wg_vis = (int *)q.wgvis.p;
     f.cull = (sl.direct && c->cull_mode != 0) ? 1 : 0;
 #ifdef SAS_TUNE_STATS
@@ -331,9 +353,9 @@ SasFrame frame_of(sas_ctx *c, Slot &sl, int tiles, bool keep_info = false)
     return f;
 }
 
-// Roles of a slot in a view pair (sas_render_batch): the LEADER's stream runs one two-view projection (whose tail
-// scans both views' counts); the FOLLOWER's stream waits for it and continues with its own binning and tiles.
-enum { ROLE_SINGLE = 0, ROLE_LEADER = 1, ROLE_FOLLOWER = 2 };
+// A context that holds meshes renders SAS_FULL_SORT frames: the meshes are composited by the full path's k_blend_mesh
+// (sas_scene_meshes), one view per frame.
+unsigned frame_flags(const sas_ctx *c, unsigned flags) { return c->has_mesh ? flags | SAS_FULL_SORT : flags; }
 
 // quad layout for views of `launch_tiles` tiles each?  By the view's own size: counting the frames in
 // flight as well measured worse -- 32 Gym cameras per step in launch groups of two run 30 % faster in the quad
@@ -357,6 +379,15 @@ bool kernel_can_write_host(sas_ctx *c, const void *p)
     return ok;
 }
 
+// Does the tile kernel deliver this view's uint8 frame to `dst` itself?  Frame wanted in pinned host memory and every
+// tile complete: it stores its rows there (no device staging frame, no copy kernel); SAS_FULL_SORT frames keep the
+// staging path.  Asked per view; a batch needs its staging frames unless every view answers yes.
+bool host_direct_ok(sas_ctx *c, const uint8_t *dst, int W, int H, unsigned flags)
+{
+    return dst && W % SAS_TILE == 0 && H % SAS_TILE == 0 && ((size_t)dst & 15) == 0 && !(flags & SAS_FULL_SORT) &&
+           kernel_can_write_host(c, dst);
+}
+
 // Nothing pending on the caller's stream?
 static bool stream_idle(hipStream_t s)
 {
@@ -367,10 +398,12 @@ static bool stream_idle(hipStream_t s)
 
 // Group poses of the n frames (one launch): each slot's snapshot goes to its own device block, so frames in flight
 // may carry different poses (vectorised envs, a pose update per Gym step) and nothing drains between them.
-int enqueue_poses(sas_ctx *c, Slot *const *sl, int n, hipStream_t st, bool multi)
+// `device_reader`: something besides the projection reads the block on the device, so it is uploaded even when the
+// projection carries the poses itself.
+void enqueue_poses(sas_ctx *c, Slot *const *sl, int n, hipStream_t st, bool device_reader = false)
 {
-    if (c->scene.n_groups <= 0) return SAS_OK;
-    if (sas_poses_inline(c->scene.n_groups, n, multi)) return SAS_OK;   // small blocks ride in the projection's arguments
+    if (c->scene.n_groups <= 0) return;
+    if (!device_reader && sas_poses_inline(c->scene.n_groups, n, n > 1)) return;   // small blocks ride in the projection's arguments
     SasPoseUpload u{};
     u.nv = n;
     for (int k = 0; k < n; ++k) {
@@ -379,10 +412,92 @@ int enqueue_poses(sas_ctx *c, Slot *const *sl, int n, hipStream_t st, bool multi
         u.floats[k] = 12 * c->scene.n_groups;
     }
     sas_launch_pose_upload(st, u);
-    return SAS_OK;
 }
 
-// Camera constants, scratch sizes and the parameter block of the slot's frame.  `init_st`: the stream the frame's
+// Single-pass or two-pass binning for the slot's frame (sl.direct), and the length of a tile's segment (scr.seg).
+// Single-pass binning: every tile owns a segment of q.seg keys.  First guess: 16 x the mean list of a frame with five
+// intersections per Gaussian, a power of two (config 3: 16 384 keys = 1.6 GB of keys + ids per slot; its longest list
+// is ~6 k); a frame whose longest list outgrows it is rendered again with larger segments (complete_oldest).
+void choose_binning(sas_ctx *c, Slot &sl)
+{
+    Scratch &q = sl.scr;
+    const int tiles = tiles_of(sl);
+    const int64_t n = c->scene.n;
+    if (q.seg_tiles != tiles || q.seg_n != n) {
+        // another frame size or scene: remember what this one had learned, take up what the slot knows about the new one
+        // (else 0: guessed below -- a segment length learned on a 300-tile frame says nothing about a 1 200-tile one)
+        if (q.seg_tiles >= 0 && q.seg > 0) {
+            int k = 0;
+            while (k < 4 && !(q.seg_memo[k].tiles == q.seg_tiles && q.seg_memo[k].n == q.seg_n)) ++k;
+            if (k == 4) { k = q.seg_memo_next; q.seg_memo_next = (q.seg_memo_next + 1) % 4; }
+            q.seg_memo[k] = {q.seg_tiles, q.seg_n, q.seg};
+        }
+        q.seg = 0;
+        for (const auto &m : q.seg_memo)
+            if (m.tiles == tiles && m.n == n) q.seg = m.seg;
+        q.seg_too_big = false;
+        q.seg_tiles = tiles;
+        q.seg_n = n;
+    }
+    sl.direct = c->direct_mode != 0 && !(sl.args.flags & SAS_FULL_SORT) && !q.seg_too_big;
+    if (!sl.direct) return;
+    if (q.seg == 0) {
+        long long guess = c->seg_guess_factor * ((5 * n) / (tiles > 0 ? tiles : 1) + 1);
+        long long s2 = 1024;
+        while (s2 < guess) s2 <<= 1;
+        q.seg = s2;
+    }
+    const long long slot_budget = c->direct_budget / std::max(1, c->n_slots);   // the budget is the context's: its slots share it
+    if ((long long)tiles * q.seg * 12 > slot_budget || q.seg > (1ll << 30)) {
+        sl.direct = false;          // pathological concentration (or a huge frame): the two-pass path has no such limit
+        q.seg_too_big = true;
+    }
+}
+
+// Key and id buffers for the binning choose_binning settled on; segments that do not fit the GPU's free memory turn
+// the frame two-pass.
+int ensure_keys(sas_ctx *c, Slot &sl)
+{
+    Scratch &q = sl.scr;
+    // buffers sized for a much larger frame (or for segments the slot has since given up) go back to the allocator:
+    // several contexts share a card (vectorised ranks, torch), and ensure() by itself only ever grows
+    if (q.keys.bytes > 4 * sizeof(unsigned long long) * key_slots(sl) && q.keys.bytes > (256u << 20)) { release(q.keys); release(q.ids); }
+    auto alloc = [&]() {
+        const int rc = ensure(c, q.keys, sizeof(unsigned long long) * key_slots(sl));
+        return rc ? rc : ensure(c, q.ids, sizeof(int) * key_slots(sl));
+    };
+    if (sl.direct && alloc()) {
+        // the segments do not fit this GPU's free memory: not an error, the two-pass path needs 12 bytes per intersection only
+        // (whatever of the segment-sized pair was allocated is released: the compact lists take a fraction of it)
+        (void)hipGetLastError();
+        c->err.clear();
+        release(q.keys);
+        release(q.ids);
+        sl.direct = false;
+        q.seg_too_big = true;
+    }
+    return alloc();
+}
+
+// The parameter block of the slot's frame (it travels in the argument segment of every kernel of the frame), and
+// who delivers a frame wanted on the host.
+void fill_params(sas_ctx *c, Slot &sl)
+{
+    const RenderArgs &a = sl.args;
+    const ViewOut &o = a.out;
+    sl.host_direct = host_direct_ok(c, o.rgb8_host, a.W, a.H, a.flags);
+    SasParams &hp = sl.params;
+    hp.cam = sl.cam;
+    hp.out.rgb = o.rgb; hp.out.alpha = o.alpha; hp.out.depth = o.depth;
+    hp.out.rgb8 = sl.host_direct ? nullptr : o.rgb8;
+    hp.out.rgb8_host = sl.host_direct ? o.rgb8_host : nullptr;
+    hp.out.bg[0] = a.bg[0]; hp.out.bg[1] = a.bg[1]; hp.out.bg[2] = a.bg[2];
+    hp.out.points = o.points; hp.out.mask = o.mask;
+    hp.out.max_depth = a.max_depth; hp.out.use_max_depth = a.use_max_depth ? 1 : 0;
+    hp.out.n_pixels = (long long)a.W * a.H;
+}
+
+// Camera constants, scratch and the parameter block of the slot's frame.  `init_st`: the stream the frame's
 // projection will run on (the slot's own, or its pair / group leader's): a new counter block is cleared there.
 int prepare_frame(sas_ctx *c, Slot &sl, hipStream_t init_st)
 {
@@ -392,8 +507,7 @@ int prepare_frame(sas_ctx *c, Slot &sl, hipStream_t init_st)
     const int tiles16 = ((a.W + SAS_TILE - 1) / SAS_TILE) * ((a.H + SAS_TILE - 1) / SAS_TILE);
     sl.quad = use_quad(c, tiles16, a.flags, a.solo) && a.W <= 65535 * (SAS_TILE / 2) && a.H <= 65535 * (SAS_TILE / 2);   // (tile coordinates are 16 bits in info)
     make_cam(a.viewmat, a.K, a.W, a.H, sl.quad ? SAS_TILE / 2 : SAS_TILE, sl.cam);
-    const SasCam &cam = sl.cam;
-    const int tiles = cam.tw * cam.th;
+    const int tiles = tiles_of(sl);
     const int64_t n = c->scene.n;
     Scratch &q = sl.scr;
     int rc;
@@ -420,95 +534,29 @@ int prepare_frame(sas_ctx *c, Slot &sl, hipStream_t init_st)
     if ((rc = ensure(c, q.wgvis, sizeof(int) * 2 * f_wg_stride(c)))) return rc;   // visible counts | 16-pixel intersections (quad layout)
     if ((rc = ensure(c, q.wgbase, sizeof(int) * SAS_WIN_BINS * (size_t)((n + 255) / 256 + 1)))) return rc;
     if ((rc = ensure(c, q.tilemax, sizeof(unsigned) * (size_t)tiles))) return rc;
-    // Single-pass binning: every tile owns a segment of q.seg keys.  First guess: 16 x the mean list of a frame with five
-    // intersections per Gaussian, a power of two (config 3: 16 384 keys = 1.6 GB of keys + ids per slot; its longest list
-    // is ~6 k); a frame whose longest list outgrows it is rendered again with larger segments (complete_oldest).
-    const long long slot_budget = c->direct_budget / std::max(1, c->n_slots);   // the budget is the context's: its slots share it
-    if (q.seg_tiles != tiles || q.seg_n != n) {
-        // another frame size or scene: remember what this one had learned, take up what the slot knows about the new one
-        // (else 0: guessed below -- a segment length learned on a 300-tile frame says nothing about a 1 200-tile one)
-        if (q.seg_tiles >= 0 && q.seg > 0) {
-            int k = 0;
-            while (k < 4 && !(q.seg_memo[k].tiles == q.seg_tiles && q.seg_memo[k].n == q.seg_n)) ++k;
-            if (k == 4) { k = q.seg_memo_next; q.seg_memo_next = (q.seg_memo_next + 1) % 4; }
-            q.seg_memo[k] = {q.seg_tiles, q.seg_n, q.seg};
-        }
-        q.seg = 0;
-        for (const auto &m : q.seg_memo)
-            if (m.tiles == tiles && m.n == n) q.seg = m.seg;
-        q.seg_too_big = false;
-        q.seg_tiles = tiles;
-        q.seg_n = n;
-    }
-    sl.direct = c->direct_mode != 0 && !(a.flags & SAS_FULL_SORT) && !q.seg_too_big;
-    if (sl.direct) {
-        if (q.seg == 0) {
-            long long guess = c->seg_guess_factor * ((5 * n) / (tiles > 0 ? tiles : 1) + 1);
-            long long s2 = 1024;
-            while (s2 < guess) s2 <<= 1;
-            q.seg = s2;
-        }
-        if ((long long)tiles * q.seg * 12 > slot_budget || q.seg > (1ll << 30)) {
-            sl.direct = false;          // pathological concentration (or a huge frame): the two-pass path has no such limit
-            q.seg_too_big = true;
-        }
-    }
-    size_t n_keys = sl.direct ? (size_t)tiles * (size_t)q.seg : (size_t)q.cap;
-    {   // buffers sized for a much larger frame (or for segments the slot has since given up) go back to the allocator:
-        // several contexts share a card (vectorised ranks, torch), and ensure() by itself only ever grows
-        const size_t want_keys = sizeof(unsigned long long) * std::max(n_keys, (size_t)q.cap);
-        if (q.keys.bytes > 4 * want_keys && q.keys.bytes > (256u << 20)) { release(q.keys); release(q.ids); }
-    }
-    if (sl.direct && (ensure(c, q.keys, sizeof(unsigned long long) * std::max(n_keys, (size_t)q.cap)) ||
-                      ensure(c, q.ids, sizeof(int) * std::max(n_keys, (size_t)q.cap)))) {
-        // the segments do not fit this GPU's free memory: not an error, the two-pass path needs 12 bytes per intersection only
-        // (whatever of the segment-sized pair was allocated is released: the compact lists take a fraction of it)
-        (void)hipGetLastError();
-        c->err.clear();
-        release(q.keys);
-        release(q.ids);
-        sl.direct = false;
-        q.seg_too_big = true;
-        n_keys = (size_t)q.cap;
-    }
-    if ((rc = ensure(c, q.keys, sizeof(unsigned long long) * std::max(n_keys, (size_t)q.cap)))) return rc;
-    if ((rc = ensure(c, q.ids, sizeof(int) * std::max(n_keys, (size_t)q.cap)))) return rc;
+    choose_binning(c, sl);
+    if ((rc = ensure_keys(c, sl))) return rc;
     if (c->scene.n_groups > 0 && (rc = ensure(c, sl.poses_dev, sizeof(float) * 12 * 256))) return rc;
-
-    SasParams &hp = sl.params;
-    hp.cam = cam;
-    hp.out.rgb = a.rgb; hp.out.alpha = a.alpha; hp.out.depth = a.depth; hp.out.rgb8 = a.rgb8;
-    // frame wanted in pinned host memory and every tile complete: the tile kernel stores its rows there itself
-    // (no device staging frame, no copy kernel); SAS_FULL_SORT frames keep the staging path
-    sl.host_direct = a.rgb8_host && a.W % SAS_TILE == 0 && a.H % SAS_TILE == 0 && ((size_t)a.rgb8_host & 15) == 0 &&
-                     !(a.flags & SAS_FULL_SORT) && kernel_can_write_host(c, a.rgb8_host);
-    hp.out.rgb8_host = sl.host_direct ? a.rgb8_host : nullptr;
-    if (sl.host_direct) hp.out.rgb8 = nullptr;
-    hp.out.bg[0] = a.bg[0]; hp.out.bg[1] = a.bg[1]; hp.out.bg[2] = a.bg[2];
-    hp.out.points = a.points; hp.out.mask = a.mask;
-    hp.out.max_depth = a.max_depth; hp.out.use_max_depth = a.use_max_depth ? 1 : 0;
-    hp.out.n_pixels = (long long)a.W * a.H;
+    fill_params(c, sl);
     return SAS_OK;
 }
 
 // Mesh scratch of the slot's frame: 2 records per triangle, the tile counts / offsets / cursors, the lists (first guess: four
 // tiles per record; a frame whose lists outgrow it is rendered again with the measured need, as for the splat keys).
-int prepare_mesh(sas_ctx *c, Slot &sl, int tiles)
+int prepare_mesh(sas_ctx *c, Slot &sl)
 {
     const size_t nrec = 2 * (size_t)c->mesh.nt;
     int rc;
     if (sl.mcap == 0) sl.mcap = std::max<long long>(1 << 16, 4 * (long long)nrec);
     if ((rc = ensure(c, sl.mrec, sizeof(float4) * 4 * nrec))) return rc;
     if ((rc = ensure(c, sl.mrect, sizeof(int4) * nrec))) return rc;
-    if ((rc = ensure(c, sl.mtiles, sizeof(int) * (3 * sas_tile_stride(tiles) + 16)))) return rc;
-    if ((rc = ensure(c, sl.mlist, sizeof(int) * (size_t)sl.mcap))) return rc;
-    return SAS_OK;
+    if ((rc = ensure(c, sl.mtiles, sizeof(int) * (3 * sas_tile_stride(tiles_of(sl)) + 16)))) return rc;
+    return ensure(c, sl.mlist, sizeof(int) * (size_t)sl.mcap);
 }
 
 SasMeshFrame mesh_frame_of(sas_ctx *c, Slot &sl)
 {
-    const int tiles = sl.cam.tw * sl.cam.th;
-    const size_t ts = sas_tile_stride(tiles);
+    const size_t ts = sas_tile_stride(tiles_of(sl));
     SasMeshFrame m{};
     m.rec = (float4 *)sl.mrec.p;
     m.rect = (int4 *)sl.mrect.p;
@@ -522,184 +570,162 @@ SasMeshFrame mesh_frame_of(sas_ctx *c, Slot &sl)
     return m;
 }
 
-// Enqueue the slot's frame on its internal stream (the slot must be idle on the GPU).  The two frames of a view
-// pair (role, partner; both prepared by the caller) share the leader's projection.
-int enqueue_frame(sas_ctx *c, Slot &sl, int role = ROLE_SINGLE, Slot *partner = nullptr)
+// Frames wanted on the host (sas_render_batch_host) and not delivered by the tile kernel: one copy kernel for the
+// chain's views when the destination is pinned (no copy-engine hop), else a runtime copy per view.
+int deliver_to_host(sas_ctx *c, Slot *const *sl, int nv, hipStream_t st)
 {
-    const RenderArgs &a = sl.args;
-    int rc;
-    if (role == ROLE_SINGLE && (rc = prepare_frame(c, sl, sl.fs))) return rc;
-    const bool timing = (a.flags & SAS_TIMING) != 0;
+    SasHostCopy h{};
+    h.nv = nv;
+    h.bytes = 3 * (size_t)sl[0]->args.W * (size_t)sl[0]->args.H;
+    const uint8_t *first = nullptr;
+    for (int k = 0; k < nv; ++k) {
+        const ViewOut &o = sl[k]->args.out;
+        h.src[k] = (o.rgb8_host && !sl[k]->host_direct) ? o.rgb8 : nullptr;
+        h.dst[k] = o.rgb8_host;
+        if (h.src[k] && !first) first = o.rgb8_host;
+    }
+    if (!first) return SAS_OK;
+    if (kernel_can_write_host(c, first)) sas_launch_host_copy(st, h);
+    else
+        for (int k = 0; k < nv; ++k)
+            if (h.src[k]) HIP_TRY(c, hipMemcpyAsync(h.dst[k], h.src[k], h.bytes, hipMemcpyDeviceToHost, st));
+    return SAS_OK;
+}
+
+// The frames of nv prepared views as ONE chain of launches on the first view's stream (the slots must be idle on the
+// GPU).  nv > 1 is a launch group: same-sized views that share every launch (grid.y = view) -- a Gym step's cameras on a
+// small scene are launch-bound, and the group's kernels also fill more of the chip.  The two chains of a view pair
+// (sas_render_batch) share one projection: the leader's chain (`follower` set) runs one two-view pass over the scene,
+// whose tail scans both views' counts; the follower's chain (`leader` set) waits for it and continues with its own
+// binning and tiles.
+int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr, Slot *leader = nullptr)
+{
+    Slot &ld = *sl[0];
+    const RenderArgs &a = ld.args;   // (size and flags are the same for all views of a group)
+    hipStream_t st = ld.fs;
+    const int tiles = tiles_of(ld);
+    const bool timing = (a.flags & SAS_TIMING) != 0;   // timed and full-sort frames are one view per chain (render_batch_impl)
     const bool full = (a.flags & SAS_FULL_SORT) != 0;
     const bool ttiles = (a.flags & SAS_TIME_TILES) != 0 && !timing && !full;
-    hipStream_t st = sl.fs;
-    const SasCam &cam = sl.cam;
-    const int tiles = cam.tw * cam.th;
-    const SasFrame f = frame_of(c, sl, tiles);
-    const SasParams &P = sl.params;
+    const bool fast_exp = (a.flags & SAS_FAST_EXP) != 0;
+    int rc;
+    SasFrame fr[SAS_MAX_GROUP];
+    bool writes_caller = false, any_fill = false;
+    for (int k = 0; k < nv; ++k) {
+        fr[k] = frame_of(c, *sl[k]);
+        writes_caller = writes_caller || sl[k]->args.order_caller;
+        any_fill = any_fill || (sl[k]->args.out.depth && (a.flags & SAS_DEPTH_FILL_MAX));
+        sl[k]->mesh = full && c->has_mesh && c->mesh.nt > 0;   // a frame with meshes: always SAS_FULL_SORT, a view of its own
+    }
+    const SasFrame &f = fr[0];
+    const SasParams &P = ld.params;
+    SasMulti mf;   // a launch group's views as its launches take them (3 KB by value: not built for a single view)
+    if (nv > 1) {
+        mf = SasMulti{};
+        mf.nv = nv;
+        for (int k = 0; k < nv; ++k) { mf.f[k] = fr[k]; mf.P[k] = sl[k]->params; }
+    }
 
-    // after whatever the caller has enqueued on its stream so far: timed frames as a whole, the others from the
-    // tile kernel on (the first thing that writes an output buffer; everything before touches only the scene and
-    // the slot's scratch)
+    // ORDER.  The chain runs after whatever the caller has enqueued on its stream so far: `start` is recorded there
+    // and waited for -- by timed frames as a whole, by the others in front of the first launch that writes an output
+    // buffer (the tile / blend kernel, or the sort of a full-sort frame; everything before touches only the scene and
+    // the slots' scratch).
     // (a blocking single frame whose caller's stream has nothing pending needs no ordering: one query instead of an event
     // record, a stream wait and the wait packet between the scatter and the tile kernel -- +2.4 % on the blocking
     // config-3 frame; pipelined frames keep the event: no gain measured there)
-    const bool order = timing || (a.order_caller && !(a.solo && stream_idle(a.stream)));
-    if (order) HIP_TRY(c, hipEventRecord(sl.start, a.stream));
-    if (timing) HIP_TRY(c, hipStreamWaitEvent(st, sl.start, 0));
-    if (role != ROLE_FOLLOWER) {
-        Slot *mem[1] = {&sl};
-        if ((rc = enqueue_poses(c, mem, 1, st, false))) return rc;   // a pair shares its poses: the leader's block serves both views
-    }
-    if (role == ROLE_FOLLOWER) HIP_TRY(c, hipStreamWaitEvent(st, partner->pair_ev, 0));
-    // a frame with meshes (always SAS_FULL_SORT, a view of its own): the triangle setup reads the slot's poses on the device
-    sl.mesh = full && c->has_mesh && c->mesh.nt > 0;
-    if (sl.mesh && (rc = prepare_mesh(c, sl, tiles))) return rc;
-    if (sl.mesh && sas_poses_inline(c->scene.n_groups, 1, false)) {
-        SasPoseUpload u{};
-        u.nv = 1;
-        u.dst[0] = (float *)sl.poses_dev.p;
-        u.src_host[0] = sl.poses_host;
-        u.floats[0] = 12 * c->scene.n_groups;
-        sas_launch_pose_upload(st, u);
-    }
-    if (timing) HIP_TRY(c, hipEventRecord(sl.ev[0], st));
-    if (role == ROLE_LEADER) {
-        const int ptiles = partner->cam.tw * partner->cam.th;
-        sas_launch_project2(st, c->scene, P, f, partner->params, frame_of(c, *partner, ptiles));
-        HIP_TRY(c, hipEventRecord(sl.pair_ev, st));
-    } else if (role == ROLE_SINGLE) {
-        sas_launch_project(st, c->scene, P, f);
+    const bool order = timing || (writes_caller && !(a.solo && stream_idle(a.stream)));
+    if (order) HIP_TRY(c, hipEventRecord(ld.start, a.stream));
+    if (timing) HIP_TRY(c, hipStreamWaitEvent(st, ld.start, 0));
+
+    if (ld.mesh && (rc = prepare_mesh(c, ld))) return rc;
+    if (leader) {
+        HIP_TRY(c, hipStreamWaitEvent(st, leader->pair_ev, 0));   // projected by the leader's pass
+    } else {
+        // (a pair shares its poses: the leader's block serves both views; the triangle setup of a mesh frame reads the
+        // slot's poses on the device)
+        enqueue_poses(c, sl, nv, st, ld.mesh);
+        if (timing) HIP_TRY(c, hipEventRecord(ld.ev[0], st));
+        if (follower) {
+            sas_launch_project2(st, c->scene, P, f, follower->params, frame_of(c, *follower));
+            HIP_TRY(c, hipEventRecord(ld.pair_ev, st));
+        } else if (nv > 1) {
+            sas_launch_project_multi(st, c->scene, mf);
+        } else {
+            sas_launch_project(st, c->scene, P, f);
+        }
     }
     if (timing) {
-        HIP_TRY(c, hipEventRecord(sl.ev[1], st));
-        HIP_TRY(c, hipEventRecord(sl.ev[2], st));   // SAS_T_SCAN: the scan is the projection's tail
+        HIP_TRY(c, hipEventRecord(ld.ev[1], st));
+        HIP_TRY(c, hipEventRecord(ld.ev[2], st));   // SAS_T_SCAN: the scan is the projection's tail
     }
-    if (!sl.direct) sas_launch_scatter(st, c->scene, cam.tw, f);   // (single-pass binning: keys and tile order are in place when the projection ends)
-    if (timing) HIP_TRY(c, hipEventRecord(sl.ev[3], st));
-    if (!timing && order) HIP_TRY(c, hipStreamWaitEvent(st, sl.start, 0));
-    if (full) sas_launch_sort(st, c->scene, tiles, f, sl.sort_streams);
-    if (timing) HIP_TRY(c, hipEventRecord(sl.ev[4], st));
-    const bool fill = a.depth && (a.flags & SAS_DEPTH_FILL_MAX);
-    const bool quad = sl.quad;   // (prepare_frame; never for SAS_FULL_SORT frames)
-    if (sl.mesh) {
-        const SasMeshFrame mf = mesh_frame_of(c, sl);
-        sas_launch_mesh_bin(st, c->mesh, P, f, mf);
-        sas_launch_blend_mesh(st, c->scene, tiles, P, f, mf, (a.flags & SAS_FAST_EXP) != 0, fill);
+    if (!ld.direct) {   // (single-pass binning: keys and tile order are in place when the projection ends)
+        if (nv > 1) sas_launch_scatter_multi(st, c->scene, ld.cam.tw, mf);
+        else sas_launch_scatter(st, c->scene, ld.cam.tw, f);
+    }
+    if (timing) HIP_TRY(c, hipEventRecord(ld.ev[3], st));
+    if (order && !timing) HIP_TRY(c, hipStreamWaitEvent(st, ld.start, 0));
+    if (full) sas_launch_sort(st, c->scene, tiles, f, ld.sort_streams);
+    if (timing) HIP_TRY(c, hipEventRecord(ld.ev[4], st));
+    hipEvent_t tile_ev[2] = {ttiles ? ld.ev[4] : nullptr, ttiles ? ld.ev[5] : nullptr};
+    if (ld.mesh) {
+        const SasMeshFrame mesh = mesh_frame_of(c, ld);
+        sas_launch_mesh_bin(st, c->mesh, P, f, mesh);
+        sas_launch_blend_mesh(st, c->scene, tiles, P, f, mesh, fast_exp, any_fill);
     } else if (full) {
-        sas_launch_blend(st, c->scene, tiles, P, f, (a.flags & SAS_FAST_EXP) != 0, fill);
-        if (a.features) {   // a feature frame (sas_render_features): the same lists and records once more, per chunk of channels
+        sas_launch_blend(st, c->scene, tiles, P, f, fast_exp, any_fill);
+        if (a.out.features) {   // a feature frame (sas_render_features): the same lists and records once more, per chunk of channels
             SasFeatures F{};
             F.store = (const float *)c->feat.p;
-            F.out = a.features;
+            F.out = a.out.features;
             F.n_pad = c->scene.n_pad;
             F.C = a.feat_c;
             F.chunks = sas_feature_chunks(a.feat_c);
             memcpy(F.bg, a.fbg, sizeof(float) * (size_t)a.feat_c);
-            sas_launch_blend_features(st, c->scene, tiles, P, f, F, (a.flags & SAS_FAST_EXP) != 0);
+            sas_launch_blend_features(st, c->scene, tiles, P, f, F, fast_exp);
         }
+    } else if (nv > 1) {
+        // (quad: by the size of one view (prepare_frame): groups of four 300-tile views still gain (vec_env_probe))
+        sas_launch_tiles_lazy_multi(st, c->scene, tiles, mf, fast_exp, any_fill, ld.quad, tile_ev[0], tile_ev[1]);
     } else {
-        sas_launch_tiles_lazy(st, c->scene, tiles, P, f, (a.flags & SAS_FAST_EXP) != 0, fill, quad,
-                              ttiles ? sl.ev[4] : nullptr, ttiles ? sl.ev[5] : nullptr);
+        sas_launch_tiles_lazy(st, c->scene, tiles, P, f, fast_exp, any_fill, ld.quad, tile_ev[0], tile_ev[1]);
     }
-    if (timing) HIP_TRY(c, hipEventRecord(sl.ev[5], st));
-    const bool pts = a.depth && (a.points || a.mask);
-    if (fill || pts) sas_launch_depth_tail(st, tiles, P, f, fill, pts);
-    if (timing) HIP_TRY(c, hipEventRecord(sl.ev[6], st));
-    if (a.rgb8_host && a.rgb8 && !sl.host_direct) {   // frame wanted on the host and not delivered by the tile kernel: by a copy kernel when the destination is pinned (no copy-engine hop)
-        const size_t fb = 3 * (size_t)a.W * (size_t)a.H;
-        if (kernel_can_write_host(c, a.rgb8_host)) {
-            SasHostCopy h{};
-            h.nv = 1;
-            h.src[0] = a.rgb8;
-            h.dst[0] = a.rgb8_host;
-            h.bytes = fb;
-            sas_launch_host_copy(st, h);
-        } else {
-            HIP_TRY(c, hipMemcpyAsync(a.rgb8_host, a.rgb8, fb, hipMemcpyDeviceToHost, st));
-        }
+    if (timing) HIP_TRY(c, hipEventRecord(ld.ev[5], st));
+    for (int k = 0; k < nv; ++k) {
+        const ViewOut &o = sl[k]->args.out;
+        const bool fill = o.depth && (a.flags & SAS_DEPTH_FILL_MAX);
+        const bool pts = o.depth && (o.points || o.mask);
+        if (fill || pts) sas_launch_depth_tail(st, tiles, sl[k]->params, fr[k], fill, pts);
     }
+    if (timing) HIP_TRY(c, hipEventRecord(ld.ev[6], st));
+    if ((rc = deliver_to_host(c, sl, nv, st))) return rc;
     HIP_TRY(c, hipGetLastError());
-    sl.timed = timing;
-    sl.timed_tiles = ttiles;
-    HIP_TRY(c, hipEventRecord(sl.done, st));
-    sl.busy = true;
+    HIP_TRY(c, hipEventRecord(ld.done, st));   // the chain completes as a whole
+    for (int k = 0; k < nv; ++k) {
+        sl[k]->busy = true;
+        sl[k]->timed = k == 0 && timing;
+        sl[k]->timed_tiles = k == 0 && ttiles;
+        sl[k]->group = k == 0 ? nv : 0;
+    }
     c->has_frame = true;
     return SAS_OK;
 }
 
-// Enqueue n same-sized views (consecutive idle slots sl[0..n-1], args filled) as ONE launch group on the leader's
-// stream: one pose upload, one projection, one scatter and one tile launch with grid.y = view.  A Gym step's cameras
-// on a small scene are launch-bound; the group's kernels also fill more of the chip.
-int enqueue_group(sas_ctx *c, Slot **sl, int n)
+// Enqueue the views of the consecutive idle slots sl[0..n-1] (args and pose snapshots filled): one view, a launch
+// group of n, or -- `pair` -- two views that share one pass over the scene.  The only way frames reach the GPU.
+int enqueue_launch(sas_ctx *c, Slot *const *sl, int n, bool pair = false)
 {
     int rc;
-    Slot &ld = *sl[0];
-    hipStream_t st = ld.fs;
-    for (int k = 0; k < n; ++k)
-        if ((rc = prepare_frame(c, *sl[k], st))) return rc;
+    for (int k = 0; k < n; ++k)   // counters are cleared on the stream that runs the projection: the leader's
+        if ((rc = prepare_frame(c, *sl[k], sl[0]->fs))) return rc;
+    if (pair) {
+        if ((rc = enqueue_chain(c, sl, 1, sl[1], nullptr))) return rc;
+        return enqueue_chain(c, sl + 1, 1, nullptr, sl[0]);
+    }
     // one launch, one binning scheme: single-pass only when every view of the group has its segments
     bool all_direct = true;
     for (int k = 0; k < n; ++k) all_direct = all_direct && sl[k]->direct;
-    for (int k = 0; k < n; ++k) sl[k]->direct = all_direct;   // (the key buffers hold max(tiles * seg, cap) keys either way)
-    const RenderArgs &a = ld.args;
-    const int tiles = ld.cam.tw * ld.cam.th;
-    SasMulti mf{};
-    mf.nv = n;
-    for (int k = 0; k < n; ++k) {
-        mf.f[k] = frame_of(c, *sl[k], tiles);
-        mf.P[k] = sl[k]->params;
-    }
-    if ((rc = enqueue_poses(c, sl, n, st, true))) return rc;
-    bool order = false;
-    for (int k = 0; k < n; ++k) order = order || sl[k]->args.order_caller;
-    if (order) HIP_TRY(c, hipEventRecord(ld.start, a.stream));
-    sas_launch_project_multi(st, c->scene, mf);
-    if (!all_direct) sas_launch_scatter_multi(st, c->scene, ld.cam.tw, mf);
-    if (order) HIP_TRY(c, hipStreamWaitEvent(st, ld.start, 0));   // outputs are first written by the tile kernel
-    const bool ttiles = (a.flags & SAS_TIME_TILES) != 0;
-    bool any_fill = false;
-    for (int k = 0; k < n; ++k) any_fill = any_fill || (sl[k]->args.depth && (a.flags & SAS_DEPTH_FILL_MAX));
-    const bool quad = ld.quad;   // by the size of one view (prepare_frame): groups of four 300-tile views still gain (vec_env_probe)
-    sas_launch_tiles_lazy_multi(st, c->scene, tiles, mf, (a.flags & SAS_FAST_EXP) != 0, any_fill, quad,
-                                ttiles ? ld.ev[4] : nullptr, ttiles ? ld.ev[5] : nullptr);
-    for (int k = 0; k < n; ++k) {
-        const RenderArgs &ak = sl[k]->args;
-        const bool fill = ak.depth && (ak.flags & SAS_DEPTH_FILL_MAX);
-        const bool pts = ak.depth && (ak.points || ak.mask);
-        if (fill || pts) sas_launch_depth_tail(st, tiles, mf.P[k], mf.f[k], fill, pts);
-    }
-    {   // frames wanted on the host (sas_render_batch_host): by a kernel when the destination is pinned
-        const size_t fb = 3 * (size_t)a.W * (size_t)a.H;
-        bool any = false;
-        for (int k = 0; k < n; ++k) any = any || (sl[k]->args.rgb8_host && sl[k]->args.rgb8 && !sl[k]->host_direct);
-        if (any && kernel_can_write_host(c, a.rgb8_host ? a.rgb8_host : sl[n - 1]->args.rgb8_host)) {
-            SasHostCopy h{};
-            h.nv = n;
-            for (int k = 0; k < n; ++k) {
-                h.src[k] = (sl[k]->args.rgb8_host && !sl[k]->host_direct) ? sl[k]->args.rgb8 : nullptr;
-                h.dst[k] = sl[k]->args.rgb8_host;
-            }
-            h.bytes = fb;
-            sas_launch_host_copy(st, h);
-        } else if (any) {
-            for (int k = 0; k < n; ++k) {
-                const RenderArgs &ak = sl[k]->args;
-                if (ak.rgb8_host && ak.rgb8 && !sl[k]->host_direct) HIP_TRY(c, hipMemcpyAsync(ak.rgb8_host, ak.rgb8, fb, hipMemcpyDeviceToHost, st));
-            }
-        }
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(ld.done, st));
-    for (int k = 0; k < n; ++k) {
-        sl[k]->busy = true;
-        sl[k]->timed = false;
-        sl[k]->timed_tiles = false;
-        sl[k]->group = k == 0 ? n : 0;
-    }
-    ld.timed_tiles = ttiles;
-    c->has_frame = true;
-    return SAS_OK;
+    for (int k = 0; k < n; ++k) sl[k]->direct = all_direct;
+    return enqueue_chain(c, sl, n);
 }
 
 // After a failure somewhere inside a frame's enqueue the counters can no longer be assumed zero.
@@ -709,7 +735,71 @@ void mark_dirty(sas_ctx *c)
     for (Slot &sl : c->slots) sl.scr.counters_zero = false;
 }
 
-// Verify the oldest in-flight frame; on overflow grow its intersection buffer and render it again.
+// What the g frames of a finished launch report (sas_frame_stats: the last one stays).  Did one outgrow a buffer?
+bool read_stats(sas_ctx *c, Slot *const *mem, int g)
+{
+    bool overflow = false;
+    for (int k = 0; k < g; ++k) {
+        const volatile unsigned *s = mem[k]->stats_host;   // written by the projection's tail (+ the tile kernel's [6])
+        c->stats[SAS_S_NVISIBLE] = s[0];
+        c->stats[SAS_S_NISECT] = s[3];   // intersections with the contract's 16-pixel tiles ([1]: keys written, at the frame's own binning)
+        c->stats[SAS_S_NKEYS] = s[1];
+        c->stats[SAS_S_MAX_TILE_LEN] = s[4];
+        c->stats[SAS_S_CAPACITY] = frame_cap(*mem[k]);
+        c->stats[SAS_S_REGROWS] = c->regrows;
+        c->stats[SAS_S_WINDOW_MISSES] = s[5];
+        c->stats[SAS_S_FALLBACK_TILES] = s[6];
+        c->stats[SAS_S_QUAD_LAYOUT] = mem[k]->quad ? 1 : 0;
+        c->stats[SAS_S_LAUNCH_VIEWS] = g;
+        overflow = overflow || s[2] != 0 || (mem[k]->mesh && mem[k]->mesh_host[1] != 0);
+    }
+    return overflow;
+}
+
+void read_stage_times(sas_ctx *c, const Slot &sl)
+{
+    if (sl.timed) {
+        for (int k = 0; k < 6; ++k) (void)hipEventElapsedTime(&c->stage_ms[k], sl.ev[k], sl.ev[k + 1]);
+        (void)hipEventElapsedTime(&c->stage_ms[SAS_T_TOTAL], sl.ev[0], sl.ev[6]);
+        for (int k = 0; k < SAS_T_COUNT; ++k) c->stage_sum[k] += c->stage_ms[k];
+        c->stage_frames++;
+    } else if (sl.timed_tiles) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, sl.ev[4], sl.ev[5]) == hipSuccess) {
+            c->stage_ms[SAS_T_BLEND] = ms;
+            c->stage_sum[SAS_T_BLEND] += ms;
+            c->stage_frames++;
+        }
+    }
+}
+
+// A launch outgrew its intersection buffers (or a mesh frame its triangle lists): grow them to the measured need.
+void grow_scratch(sas_ctx *c, Slot *const *mem, int g)
+{
+    long long want = 0, want_seg = 0;
+    for (int k = 0; k < g; ++k) {
+        if (mem[k]->mesh && mem[k]->mesh_host[1] != 0)
+            mem[k]->mcap = std::max(mem[k]->mcap, grown((long long)mem[k]->mesh_host[0], 1024));
+        want = std::max(want, grown((long long)mem[k]->stats_host[1], 1024));
+        if (mem[k]->direct) {   // single-pass binning: the longest list, as a power of two
+            long long s2 = mem[k]->scr.seg;
+            while (s2 < grown((long long)mem[k]->stats_host[4], 0)) s2 <<= 1;
+            want_seg = std::max(want_seg, s2);
+        }
+    }
+    for (int k = 0; k < g; ++k) {
+        if (mem[k]->direct) { if (want_seg > mem[k]->scr.seg) mem[k]->scr.seg = want_seg; }
+        else if (want > mem[k]->scr.cap) mem[k]->scr.cap = want;
+    }
+    const Scratch &q = mem[0]->scr;
+    for (Slot &o : c->slots) {   // the other slots will need it too (those set up for the same frame size and scene)
+        if (o.busy) continue;
+        if (want_seg && o.scr.seg && o.scr.seg < want_seg && o.scr.seg_tiles == q.seg_tiles && o.scr.seg_n == q.seg_n) o.scr.seg = want_seg;
+        if (!want_seg && o.scr.cap && o.scr.cap < want) o.scr.cap = want;
+    }
+}
+
+// Verify the oldest in-flight launch; on overflow grow its buffers and render it again.
 int complete_oldest(sas_ctx *c)
 {
     if (c->inflight <= 0) return SAS_OK;
@@ -719,39 +809,8 @@ int complete_oldest(sas_ctx *c)
     for (int k = 0; k < g; ++k) mem[k] = &c->slots[(c->head + k) % c->n_slots];
     for (int attempt = 0; attempt < 4; ++attempt) {
         HIP_TRY(c, hipEventSynchronize(sl.done));
-        bool overflow = false;
-        for (int k = 0; k < g; ++k) {
-            const volatile unsigned *s = mem[k]->stats_host;   // written by the projection's tail (+ the tile kernel's [6])
-            c->stats[SAS_S_NVISIBLE] = s[0];
-            c->stats[SAS_S_NISECT] = s[3];   // intersections with the contract's 16-pixel tiles ([1]: keys written, at the frame's own binning)
-            c->stats[SAS_S_NKEYS] = s[1];
-            c->stats[SAS_S_MAX_TILE_LEN] = s[4];
-            c->stats[SAS_S_CAPACITY] = mem[k]->direct ? (long long)mem[k]->cam.tw * mem[k]->cam.th * mem[k]->scr.seg : mem[k]->scr.cap;   // keys the frame's buffer holds
-            c->stats[SAS_S_REGROWS] = c->regrows;
-            c->stats[SAS_S_WINDOW_MISSES] = s[5];
-            c->stats[SAS_S_FALLBACK_TILES] = s[6];
-            c->stats[SAS_S_QUAD_LAYOUT] = mem[k]->quad ? 1 : 0;
-            c->stats[SAS_S_LAUNCH_VIEWS] = g;
-            overflow = overflow || s[2] != 0;
-            if (mem[k]->mesh && mem[k]->mesh_host[1] != 0) {   // the triangle lists outgrew the slot's: grow to the need (+25 %)
-                const long long need = (long long)mem[k]->mesh_host[0];
-                mem[k]->mcap = std::max(mem[k]->mcap, need + need / 4 + 1024);
-                overflow = true;
-            }
-        }
-        if (sl.timed) {
-            for (int k = 0; k < 6; ++k) (void)hipEventElapsedTime(&c->stage_ms[k], sl.ev[k], sl.ev[k + 1]);
-            (void)hipEventElapsedTime(&c->stage_ms[SAS_T_TOTAL], sl.ev[0], sl.ev[6]);
-            for (int k = 0; k < SAS_T_COUNT; ++k) c->stage_sum[k] += c->stage_ms[k];
-            c->stage_frames++;
-        } else if (sl.timed_tiles) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, sl.ev[4], sl.ev[5]) == hipSuccess) {
-                c->stage_ms[SAS_T_BLEND] = ms;
-                c->stage_sum[SAS_T_BLEND] += ms;
-                c->stage_frames++;
-            }
-        }
+        const bool overflow = read_stats(c, mem, g);
+        read_stage_times(c, sl);
         if (!overflow) {
             // Only now -- the host has seen the frame finished AND that it did not overflow its intersection buffer -- may
             // the frame be consumed.  Whatever the caller puts on its stream from here on starts after the frame in real
@@ -766,30 +825,11 @@ int complete_oldest(sas_ctx *c)
             c->frames_completed += g;
             return SAS_OK;
         }
-        // intersection buffer too small: grow to the measured need (+25 %) and render the frame (group) again,
-        // with the poses it was submitted with (the slot's snapshot)
-        long long want = 0, want_seg = 0;
-        for (int k = 0; k < g; ++k) {
-            const long long need = (long long)mem[k]->stats_host[1];
-            want = std::max(want, need + need / 4 + 1024);
-            if (mem[k]->direct) {   // single-pass binning: the longest list (+25 %), as a power of two
-                const long long longest = (long long)mem[k]->stats_host[4];
-                long long s2 = mem[k]->scr.seg;
-                while (s2 < longest + longest / 4) s2 <<= 1;
-                want_seg = std::max(want_seg, s2);
-            }
-        }
-        for (int k = 0; k < g; ++k) {
-            if (mem[k]->direct) { if (want_seg > mem[k]->scr.seg) mem[k]->scr.seg = want_seg; }
-            else if (want > mem[k]->scr.cap) mem[k]->scr.cap = want;
-        }
-        for (Slot &o : c->slots) {   // the other slots will need it too (those set up for the same frame size and scene)
-            if (o.busy) continue;
-            if (want_seg && o.scr.seg && o.scr.seg < want_seg && o.scr.seg_tiles == sl.scr.seg_tiles && o.scr.seg_n == sl.scr.seg_n) o.scr.seg = want_seg;
-            if (!want_seg && o.scr.cap && o.scr.cap < want) o.scr.cap = want;
-        }
+        // render the launch again, with the poses it was submitted with (the slots' snapshots): a group as a group, a
+        // single view or a member of a view pair as a single view
+        grow_scratch(c, mem, g);
         c->regrows++;
-        int rc = g > 1 ? enqueue_group(c, mem, g) : enqueue_frame(c, sl);
+        const int rc = enqueue_launch(c, mem, g);
         if (rc) { mark_dirty(c); return rc; }
     }
     return fail(c, SAS_ERR_HIP, "intersection buffer kept overflowing");
@@ -1207,14 +1247,9 @@ int sas_get_group_poses(sas_ctx *c, int n_groups, float *Rt)
 
 struct ViewCall {
     const float *viewmat, *K;
-    float *rgb, *alpha, *depth;
-    uint8_t *rgb8;
-    float *points;
-    uint8_t *mask;
-    uint8_t *rgb8_host = nullptr;
+    ViewOut out;
     const float *poses = nullptr;   // [n_groups,12] group poses of THIS view (a pose set), or nullptr: the context's current poses
-    float *features = nullptr;      // sas_render_features: [H,W,feat_c] device output, feature background fbg [feat_c] (nullptr: 0)
-    const float *fbg = nullptr;
+    const float *fbg = nullptr;     // sas_render_features: feature background [feat_c] of out.features (nullptr: 0)
     int feat_c = 0;
 };
 
@@ -1225,30 +1260,27 @@ static int check_view(sas_ctx *c, const ViewCall &v, int width, int height)
     if (width <= 0 || height <= 0 || width > 65535 * SAS_TILE || height > 65535 * SAS_TILE)
         return fail(c, SAS_ERR_INVALID, "bad image size %dx%d", width, height);
     if (!(v.K[0] > 0.0f) || !(v.K[4] > 0.0f)) return fail(c, SAS_ERR_INVALID, "focal lengths must be positive");
-    if ((v.points || v.mask) && !v.depth) return fail(c, SAS_ERR_INVALID, "points / mask need the depth output");
+    if ((v.out.points || v.out.mask) && !v.out.depth) return fail(c, SAS_ERR_INVALID, "points / mask need the depth output");
     return SAS_OK;
 }
 
 static void fill_args(RenderArgs &a, const ViewCall &v, int width, int height, const float *background, unsigned flags,
                       const float *max_depth, hipStream_t st, bool solo)
 {
+    const ViewOut &o = v.out;
     a.solo = solo;
     // rgb8 beside rgb8_host is the context's own staging frame (sas_render_batch_host): nothing of the caller's on the device
-    a.order_caller = v.rgb || v.alpha || v.depth || v.points || v.mask || v.features || (v.rgb8 && !v.rgb8_host);
+    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || (o.rgb8 && !o.rgb8_host);
     memcpy(a.viewmat, v.viewmat, sizeof(a.viewmat));
     memcpy(a.K, v.K, sizeof(a.K));
     for (int k = 0; k < 3; ++k) a.bg[k] = background ? background[k] : 0.0f;
     a.W = width; a.H = height; a.flags = flags;
-    a.rgb = v.rgb; a.alpha = v.alpha; a.depth = v.depth; a.rgb8 = v.rgb8;
-    a.points = v.points; a.mask = v.mask;
-    a.rgb8_host = v.rgb8_host;
-    a.features = v.features;
-    a.feat_c = v.features ? v.feat_c : 0;
+    a.out = o;
+    a.feat_c = o.features ? v.feat_c : 0;
     for (int k = 0; k < a.feat_c; ++k) a.fbg[k] = v.fbg ? v.fbg[k] : 0.0f;
     a.use_max_depth = max_depth != nullptr;
     a.max_depth = max_depth ? *max_depth : 0.0f;
     a.stream = st;
-    a.valid = true;
 }
 
 // the poses the slot's frame is rendered with: the view's own set, else the context's current ones
@@ -1259,12 +1291,12 @@ static void snapshot_poses(sas_ctx *c, Slot &sl, const ViewCall &v)
 }
 
 // One view (n == 1), a pair of views that share one projection pass (n == 2), or -- `grouped` -- up to
-// SAS_MAX_GROUP views that share every launch (enqueue_group).
+// SAS_MAX_GROUP views that share every launch.
 static int render_views(sas_ctx *c, const ViewCall *views, int n, int width, int height, const float *background,
                         unsigned flags, const float *max_depth, void *stream, bool grouped = false, bool solo = false)
 {
     if (!c) return SAS_ERR_INVALID;
-    if (c->has_mesh) flags |= SAS_FULL_SORT;   // (sas_scene_meshes: the meshes are composited by the full path's k_blend_mesh)
+    flags = frame_flags(c, flags);
     for (int k = 0; k < n; ++k) {
         const int rc = check_view(c, views[k], width, height);
         if (rc) return rc;
@@ -1290,46 +1322,20 @@ static int render_views(sas_ctx *c, const ViewCall *views, int n, int width, int
         fill_args(sl[k]->args, views[k], width, height, background, flags, max_depth, st, solo && n == 1 && c->inflight == 0);
         snapshot_poses(c, *sl[k], views[k]);
     }
-    if (grouped) {
-        const int rc = enqueue_group(c, sl, n);
-        if (rc) { mark_dirty(c); return rc; }
-        c->inflight += n;
-        c->frames_submitted += n;
-        c->last_slot = (int)(sl[n - 1] - c->slots);
-        if (flags & SAS_ASYNC) return SAS_OK;
-        return complete_all(c);
-    }
-    if (n == 2) {
-        for (int k = 0; k < 2; ++k) {
-            const int rc = prepare_frame(c, *sl[k], sl[0]->fs);
-            if (rc) return rc;
-        }
-    }
-    for (int k = 0; k < n; ++k) {
-        const int role = n == 1 ? ROLE_SINGLE : (k == 0 ? ROLE_LEADER : ROLE_FOLLOWER);
-        int rc = enqueue_frame(c, *sl[k], role, n == 2 ? sl[1 - k] : nullptr);
-        if (rc) { mark_dirty(c); return rc; }
-        c->inflight++;
-        c->frames_submitted++;
-        c->last_slot = (int)(sl[k] - c->slots);
-    }
+    const int rc = enqueue_launch(c, sl, n, n == 2 && !grouped);
+    if (rc) { mark_dirty(c); return rc; }
+    c->inflight += n;
+    c->frames_submitted += n;
+    c->last_slot = (int)(sl[n - 1] - c->slots);
     if (flags & SAS_ASYNC) return SAS_OK;
     return complete_all(c);
-}
-
-static int render_impl(sas_ctx *c, const float *viewmat, const float *K, int width, int height, const float *background,
-                       unsigned flags, float *rgb, float *alpha, float *depth, uint8_t *rgb8, float *points,
-                       uint8_t *mask, const float *max_depth, void *stream)
-{
-    const ViewCall v = {viewmat, K, rgb, alpha, depth, rgb8, points, mask};
-    return render_views(c, &v, 1, width, height, background, flags, max_depth, stream, false, !(flags & SAS_ASYNC));
 }
 
 int sas_render(sas_ctx *c, const float *viewmat, const float *K, int width, int height, const float *background,
                unsigned flags, float *rgb, float *alpha, float *depth, uint8_t *rgb8, void *stream)
 {
-    return render_impl(c, viewmat, K, width, height, background, flags, rgb, alpha, depth, rgb8, nullptr, nullptr,
-                       nullptr, stream);
+    const ViewCall v = {viewmat, K, {rgb, alpha, depth, rgb8}};
+    return render_views(c, &v, 1, width, height, background, flags, nullptr, stream, false, !(flags & SAS_ASYNC));
 }
 
 int sas_scene_features(sas_ctx *c, int64_t n, int channels, const float *features)
@@ -1389,8 +1395,8 @@ int sas_render_features(sas_ctx *c, const float *viewmat, const float *K, int wi
     if (!c->has_feat) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
     if (c->has_mesh) return fail(c, SAS_ERR_INVALID, "feature frames of a context with meshes are not supported (sas_scene_meshes)");
     if (!features) return fail(c, SAS_ERR_INVALID, "the features output is required");
-    ViewCall v = {viewmat, K, rgb, alpha, depth, nullptr, nullptr, nullptr};
-    v.features = features;
+    ViewCall v = {viewmat, K, {rgb, alpha, depth}};
+    v.out.features = features;
     v.fbg = feature_background;
     v.feat_c = c->feat_c;
     return render_views(c, &v, 1, width, height, background, flags | SAS_FULL_SORT, nullptr, stream, false, !(flags & SAS_ASYNC));
@@ -1462,8 +1468,8 @@ int sas_render_rgbd(sas_ctx *c, const float *viewmat, const float *K, int width,
                     unsigned flags, const float *max_depth, float *rgb, float *alpha, float *depth, float *points,
                     uint8_t *mask, void *stream)
 {
-    return render_impl(c, viewmat, K, width, height, background, flags, rgb, alpha, depth, nullptr, points, mask,
-                       max_depth, stream);
+    const ViewCall v = {viewmat, K, {rgb, alpha, depth, nullptr, points, mask}};
+    return render_views(c, &v, 1, width, height, background, flags, max_depth, stream, false, !(flags & SAS_ASYNC));
 }
 
 // pose sets of a batch: view v is rendered with rows pose_sets[pose_set[v]] (each set [n_groups,12]); no sets: the
@@ -1479,7 +1485,7 @@ static int render_batch_impl(sas_ctx *c, int n_views, const float *viewmats, con
                              uint8_t *rgb8_host, void *stream, const PoseSets &ps = PoseSets())
 {
     if (!c) return SAS_ERR_INVALID;
-    if (c->has_mesh) flags |= SAS_FULL_SORT;   // one view per frame (sas_scene_meshes)
+    flags = frame_flags(c, flags);
     if (n_views < 0 || (n_views > 0 && (!viewmats || !Ks))) return fail(c, SAS_ERR_INVALID, "bad view batch");
     if (ps.Rt) {
         if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
@@ -1491,20 +1497,21 @@ static int render_batch_impl(sas_ctx *c, int n_views, const float *viewmats, con
     }
     const size_t px = (size_t)width * (size_t)height;
     auto view = [&](int v) {
-        ViewCall vc{viewmats + 16 * v, Ks + 9 * v, rgb ? rgb + 3 * px * v : nullptr, alpha ? alpha + px * v : nullptr,
-                    depth ? depth + px * v : nullptr, rgb8 ? rgb8 + 3 * px * v : nullptr, nullptr, nullptr};
-        vc.rgb8_host = rgb8_host ? rgb8_host + 3 * px * v : nullptr;
+        ViewCall vc{viewmats + 16 * v, Ks + 9 * v, {rgb ? rgb + 3 * px * v : nullptr, alpha ? alpha + px * v : nullptr,
+                    depth ? depth + px * v : nullptr, rgb8 ? rgb8 + 3 * px * v : nullptr}};
+        vc.out.rgb8_host = rgb8_host ? rgb8_host + 3 * px * v : nullptr;
         vc.poses = ps.Rt ? ps.Rt + (size_t)12 * c->scene.n_groups * ps.pose_set[v] : nullptr;
         return vc;
     };
     // Views go through the frame slots two at a time: one pass over the scene projects both
     // (timed and full-sort frames keep to one view per pass; so do two views of different pose sets).
     const bool want_pairs = c->pair_views < 0 ? c->scene.n >= sas_ctx::kPairMinGaussians : c->pair_views != 0;
-    const bool pair = want_pairs && c->n_slots >= 2 && !(flags & (SAS_TIMING | SAS_FULL_SORT));
+    const bool share = !(flags & (SAS_TIMING | SAS_FULL_SORT));
+    const bool pair = share && want_pairs && c->n_slots >= 2;
     // small scenes (not paired): launch groups, by default half of the slots each so that two can be in flight
     int gsz = c->group_views > 0 ? c->group_views : std::max(2, c->n_slots / 2);
     gsz = std::min(std::min(gsz, SAS_MAX_GROUP), c->n_slots);
-    const bool group = !pair && gsz >= 2 && n_views >= 2 && !(flags & (SAS_TIMING | SAS_FULL_SORT));
+    const bool group = share && !pair && gsz >= 2 && n_views >= 2;
     for (int v = 0; v < n_views;) {
         if (group && v + 1 < n_views) {
             const int n = std::min(gsz, n_views - v);
@@ -1537,8 +1544,7 @@ int sas_render_batch_posed(sas_ctx *c, int n_views, const float *viewmats, const
                            const float *Rt, int width, int height, const float *background, unsigned flags, float *rgb,
                            float *alpha, float *depth, uint8_t *rgb8, void *stream)
 {
-    PoseSets ps;
-    ps.pose_set = pose_set; ps.n_sets = n_sets; ps.Rt = Rt;
+    const PoseSets ps = {pose_set, n_sets, Rt};
     if (!Rt) return fail(c, SAS_ERR_INVALID, "sas_render_batch_posed: Rt is required");
     return render_batch_impl(c, n_views, viewmats, Ks, width, height, background, flags, rgb, alpha, depth, rgb8, nullptr, stream, ps);
 }
@@ -1548,7 +1554,7 @@ static int render_batch_host_impl(sas_ctx *c, int n_views, const float *viewmats
 {
     if (!c) return SAS_ERR_INVALID;
     if (!rgb8_host || (flags & SAS_ASYNC)) return fail(c, SAS_ERR_INVALID, "sas_render_batch_host: host buffer required, blocking only");
-    if (c->has_mesh) flags |= SAS_FULL_SORT;   // (sas_scene_meshes)
+    flags = frame_flags(c, flags);
     if (n_views <= 0) return n_views == 0 ? SAS_OK : fail(c, SAS_ERR_INVALID, "bad view batch");
     if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "bad image size");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1556,21 +1562,18 @@ static int render_batch_host_impl(sas_ctx *c, int n_views, const float *viewmats
         const int rc = complete_all(c);
         if (rc) return rc;
     }
-    const size_t bytes = 3 * (size_t)width * (size_t)height * (size_t)n_views;
+    const size_t frame_bytes = 3 * (size_t)width * (size_t)height;
     c->host_query_base = nullptr;
-    const bool pinned = kernel_can_write_host(c, rgb8_host);
-    // the staging frames are needed only when the tile kernel cannot deliver the frames itself (prepare_frame's rule)
-    const bool direct = pinned && width % SAS_TILE == 0 && height % SAS_TILE == 0 && ((size_t)rgb8_host & 15) == 0 &&
-                        ((3 * (size_t)width * (size_t)height) & 15) == 0 && !(flags & SAS_FULL_SORT);
-    if (!direct || !c->host_stage.p) {
-        const int rc = ensure(c, c->host_stage, bytes);
-        if (rc) return rc;
-    }
-    c->host_query_base = rgb8_host;
-    c->host_query_end = rgb8_host + bytes;
-    c->host_query_ok = pinned;
-    const int rc = render_batch_impl(c, n_views, viewmats, Ks, width, height, background, flags, nullptr, nullptr, nullptr,
-                                     (uint8_t *)c->host_stage.p, rgb8_host, stream, ps);
+    c->host_query_ok = kernel_can_write_host(c, rgb8_host);
+    c->host_query_base = rgb8_host;   // the answer holds for this call's views
+    c->host_query_end = rgb8_host + frame_bytes * (size_t)n_views;
+    // the staging frames are needed only when the tile kernel cannot deliver every frame itself
+    bool all_direct = true;
+    for (int v = 0; v < n_views; ++v) all_direct = all_direct && host_direct_ok(c, rgb8_host + frame_bytes * v, width, height, flags);
+    int rc = (all_direct && c->host_stage.p) ? SAS_OK : ensure(c, c->host_stage, frame_bytes * (size_t)n_views);
+    if (!rc)
+        rc = render_batch_impl(c, n_views, viewmats, Ks, width, height, background, flags, nullptr, nullptr, nullptr,
+                               (uint8_t *)c->host_stage.p, rgb8_host, stream, ps);
     c->host_query_base = nullptr;
     return rc;
 }
@@ -1585,8 +1588,7 @@ int sas_render_batch_host_posed(sas_ctx *c, int n_views, const float *viewmats, 
                                 const float *Rt, int width, int height, const float *background, unsigned flags,
                                 uint8_t *rgb8_host, void *stream)
 {
-    PoseSets ps;
-    ps.pose_set = pose_set; ps.n_sets = n_sets; ps.Rt = Rt;
+    const PoseSets ps = {pose_set, n_sets, Rt};
     if (!Rt) return fail(c, SAS_ERR_INVALID, "sas_render_batch_host_posed: Rt is required");
     return render_batch_host_impl(c, n_views, viewmats, Ks, width, height, background, flags, rgb8_host, stream, ps);
 }
@@ -1679,11 +1681,9 @@ int sas_read_projection(sas_ctx *c, int32_t *radii, float *means2d, float *depth
         // Single-pass product frames do not write info[] (rectangles, radii: nothing on the device reads them).  The hook
         // projects the slot's frame once more with it -- same camera, same pose snapshot, the slot's own scratch; that
         // launch bins again, so the slot's counters are cleared in front of its next frame.
-        const int tiles = ls.cam.tw * ls.cam.th;
         Slot *mem[1] = {&ls};
-        int rcp = enqueue_poses(c, mem, 1, ls.fs, false);   // (a pair's follower never uploaded its own copy of the snapshot)
-        if (rcp) return rcp;
-        sas_launch_project(ls.fs, c->scene, ls.params, frame_of(c, ls, tiles, true));
+        enqueue_poses(c, mem, 1, ls.fs);   // (a pair's follower never uploaded its own copy of the snapshot)
+        sas_launch_project(ls.fs, c->scene, ls.params, frame_of(c, ls, true));
         HIP_TRY(c, hipStreamSynchronize(ls.fs));
         ls.scr.counters_zero = false;
     }
@@ -1723,7 +1723,7 @@ int sas_read_tile_lists(sas_ctx *c, int32_t *tile_offsets, int32_t *sorted_ids, 
     }
     const Slot &ls = c->slots[c->last_slot];
     const Scratch &q = ls.scr;
-    const int tiles = ls.cam.tw * ls.cam.th;
+    const int tiles = tiles_of(ls);
     if (tile_offsets)
         HIP_TRY(c, hipMemcpy(tile_offsets, q.tilebuf.p, sizeof(int) * (size_t)(tiles + 1), hipMemcpyDeviceToHost));
     if (sorted_ids) {

@@ -448,7 +448,7 @@ def test_view_pairs_equal_single_views(monkeypatch):
 @pytest.mark.parametrize("group", [2, 4])
 def test_launch_groups_equal_single_views(monkeypatch, group):
     """sas_render_batch on a small scene renders the views in launch groups (one projection / scan / scatter /
-    tile launch with grid.y = view, enqueue_group): every output of every view of a 5-view batch (full groups +
+    tile launch with grid.y = view, enqueue_chain): every output of every view of a 5-view batch (full groups +
     a remainder), one view looking away from the scene, equals the one-view-at-a-time render; an overflowing
     group is rendered again as a group; asynchronous groups complete as a whole."""
     import torch
