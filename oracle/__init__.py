@@ -7,6 +7,9 @@ its HIP library is missing instead of falling back to this code.
 ``oracle.sas_oracle.c``  float32 C restatement (the checker; OpenMP for the CPU baseline timing)
 ``oracle.np_twin``       float64 NumPy twin used to cross-check the C file
 ``oracle.ref_math``      NumPy restatement of the in-tree host math (compute_cov, SH2RGB, poses)
+``oracle.mesh_ref``      float64 reference of the mesh rules (coverage, depth, shading; ``mesh_ref.c``), brute force per pixel,
+                         with the ``stable`` mask that says where float32 may decide otherwise; ``render(zlim=, bgmap=)`` takes
+                         its per-pixel depth limit and background
 
 Parity status: rows T0-T7 are **parity unpinned** (third-party arithmetic absent from
 /root/reference, no reference tests); in-tree rows are pinned by tests/golden/.
@@ -27,9 +30,9 @@ _lib = None
 
 
 def build(force: bool = False) -> Path:
-    """Compile oracle/sas_oracle.c with gcc (seconds)."""
-    src = _HERE / "sas_oracle.c"
-    if force or not _LIB_PATH.exists() or _LIB_PATH.stat().st_mtime < src.stat().st_mtime:
+    """Compile oracle/sas_oracle.c and oracle/mesh_ref.c with gcc (seconds)."""
+    newest = max((_HERE / f).stat().st_mtime for f in ("sas_oracle.c", "mesh_ref.c"))
+    if force or not _LIB_PATH.exists() or _LIB_PATH.stat().st_mtime < newest:
         subprocess.run(["make", "-C", str(_HERE), "-s"], check=True)
     return _LIB_PATH
 
@@ -62,6 +65,13 @@ def lib():
         _lib.sas_oracle_render.restype = ctypes.c_int
         _lib.sas_oracle_render.argtypes = [ctypes.POINTER(_Scene)] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + \
             [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 11 + [ctypes.c_int64, ctypes.c_void_p]
+        _lib.sas_oracle_render_limited.restype = ctypes.c_int
+        _lib.sas_oracle_render_limited.argtypes = _lib.sas_oracle_render.argtypes + [ctypes.c_void_p] * 2
+        _lib.sas_oracle_pose_points.restype = None
+        _lib.sas_oracle_pose_points.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 5
+        _lib.sas_mesh_ref.restype = ctypes.c_int
+        _lib.sas_mesh_ref.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                      ctypes.c_int] + [ctypes.c_void_p] * 7
         _lib.sas_oracle_unproject.restype = None
         _lib.sas_oracle_unproject.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + \
             [ctypes.c_void_p] * 3
@@ -125,8 +135,12 @@ def set_num_threads(n: int) -> None:
 def render(means, opacities, colors, viewmat, K, width: int, height: int, *, quats=None, scales=None,
            cov6=None, sh_degree: int = 3, group_id=None, group_Rt=None,
            background=(0.0, 0.0, 0.0), depth_mode: int = 0, want_rgb8: bool = False,
-           dump: bool = False) -> Dict[str, np.ndarray]:
-    """Render one frame with the C oracle.  ``sh_degree < 0`` means ``colors`` is final RGB [N,3]."""
+           dump: bool = False, zlim=None, bgmap=None) -> Dict[str, np.ndarray]:
+    """Render one frame with the C oracle.  ``sh_degree < 0`` means ``colors`` is final RGB [N,3].
+
+    ``zlim [H,W]`` and ``bgmap [H,W,3]`` (float32, optional) are the per-pixel depth limit and background of a frame with
+    meshes (DESIGN.md 3 "Meshes", rules 3 and 4; ``oracle.mesh_ref.frame_inputs``): the first list entry with
+    ``depth >= zlim[p]`` ends pixel ``p``, and ``bgmap[p]`` takes the background's place."""
     L = lib()
     means = _f32(means, (-1, 3))
     n = means.shape[0]
@@ -162,6 +176,8 @@ def render(means, opacities, colors, viewmat, K, width: int, height: int, *, qua
         cols = np.zeros((n, 3), np.float32)
         toff = np.zeros((tiles + 1,), np.int32)
     stats = np.zeros(3, np.int64)
+    zl = None if zlim is None else _f32(zlim, (H, W))
+    bm = None if bgmap is None else _f32(bgmap, (H, W, 3))
     if dump:
         # first call to learn M, second to fetch ids (cheap at test sizes)
         rc = L.sas_oracle_render(ctypes.byref(sc), _ptr(V), _ptr(Km), W, H, _ptr(bg), depth_mode,
@@ -170,10 +186,10 @@ def render(means, opacities, colors, viewmat, K, width: int, height: int, *, qua
             raise MemoryError("oracle allocation failed")
         cap = int(stats[1])
         sids = np.zeros((max(cap, 1),), np.int32)
-    rc = L.sas_oracle_render(ctypes.byref(sc), _ptr(V), _ptr(Km), W, H, _ptr(bg), int(depth_mode),
-                             _ptr(rgb), _ptr(alpha), _ptr(depth), _ptr(rgb8),
-                             _ptr(radii), _ptr(means2d), _ptr(depths), _ptr(conics), _ptr(cols),
-                             _ptr(toff), _ptr(sids), cap, _ptr(stats))
+    rc = L.sas_oracle_render_limited(ctypes.byref(sc), _ptr(V), _ptr(Km), W, H, _ptr(bg), int(depth_mode),
+                                     _ptr(rgb), _ptr(alpha), _ptr(depth), _ptr(rgb8),
+                                     _ptr(radii), _ptr(means2d), _ptr(depths), _ptr(conics), _ptr(cols),
+                                     _ptr(toff), _ptr(sids), cap, _ptr(stats), _ptr(zl), _ptr(bm))
     if rc != 0:
         raise MemoryError("oracle allocation failed")
     out.update(rgb=rgb, alpha=alpha, depth=depth, n_visible=int(stats[0]), n_isect=int(stats[1]))
@@ -211,6 +227,19 @@ def trace_pixel(means, opacities, colors, viewmat, K, width: int, height: int, p
     return dict(entry=int(out[0]), gaussian=int(out[1]), decision_a=DECISIONS[int(out[2])], decision_b=DECISIONS[int(out[3])],
                 alpha_a=float(vals[0]), alpha_b=float(vals[1]), next_T_a=float(vals[2]), next_T_b=float(vals[3]),
                 sigma_a=float(vals[4]), sigma_b=float(vals[5]))
+
+
+def pose_points(points, viewmat, groups=None, group_Rt=None):
+    """Mesh vertices moved as the oracle moves Gaussian means, in float32 with its fused chains: returns
+    ``(world [n,3], camera [n,3], campos [3])``, ``groups [n]`` the pose group of each point (``None``: unposed)."""
+    pts = _f32(points, (-1, 3))
+    n = pts.shape[0]
+    gid = None if groups is None or group_Rt is None else np.ascontiguousarray(np.broadcast_to(np.asarray(groups, np.uint8).reshape(-1), (n,)))
+    gRt = None if gid is None else _f32(group_Rt, (-1, 12))
+    world, camv, campos = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(3, np.float32)
+    lib().sas_oracle_pose_points(_ptr(pts), n, _ptr(gid), 0 if gRt is None else gRt.shape[0], _ptr(gRt), _ptr(_f32(viewmat, (16,))),
+                                 _ptr(world), _ptr(camv), _ptr(campos))
+    return world, camv, campos
 
 
 def unproject(depth, K, max_depth=1.0):

@@ -1,7 +1,9 @@
 /* Sanitizer leg of the CPU oracle (test infrastructure): renders a small seeded scene, including
- * ragged image sizes, group poses, culled and empty scenes and poisoned scenes (NaN, Inf, absurd magnitudes), under -fsanitize=address,undefined.
+ * ragged image sizes, group poses, culled and empty scenes and poisoned scenes (NaN, Inf, absurd magnitudes), under -fsanitize=address,undefined;
+ * then the mesh reference over the scene's own (possibly poisoned) means as triangle corners, and the frame with its depth limit and background map.
  * Exit code 0 and no sanitizer report = pass.  Built by `make -C oracle asan`. */
 #include "sas_oracle.c"
+#include "mesh_ref.c"
 #include <stdio.h>
 
 static unsigned long long rs = 88172645463325252ull;
@@ -50,6 +52,25 @@ static int run(int n, int W, int H, int groups, int degree, int poison)
     int32_t *ids = malloc(sizeof(int32_t) * (st[1] + 1));
     rc |= sas_oracle_render(&s, V, K, W, H, bg, 0, rgb, NULL, d, NULL, NULL, NULL, NULL, NULL, NULL, NULL, ids, st[1], st);
     printf("n=%d %dx%d groups=%d deg=%d -> visible %lld, intersections %lld\n", n, W, H, groups, degree, (long long)st[0], (long long)st[1]);
+    /* meshes: the first 60 means, three by three, as triangles */
+    const int nt = (n < 60 ? n : 60) / 3;
+    float *camv = malloc(sizeof(float) * 3 * (3 * nt + 1)), *zlim = malloc(sizeof(float) * W * H), *bgmap = malloc(sizeof(float) * 3 * W * H);
+    int32_t *tris = malloc(sizeof(int32_t) * (3 * nt + 1)), *win = malloc(sizeof(int32_t) * W * H);
+    double *mz = malloc(sizeof(double) * 4 * W * H);
+    uint8_t *probe = malloc(W * H), *valid = malloc(nt + 1);
+    const double K4[4] = {K[0], K[4], K[2], K[5]};
+    for (int i = 0; i < 3 * nt; ++i) tris[i] = i;
+    sas_oracle_pose_points(means, 3 * nt, groups ? gid : NULL, groups ? 4 : 0, groups ? Rt : NULL, V, NULL, camv, NULL);
+    rc |= sas_mesh_ref(camv, 3 * nt, tris, nt, K4, W, H, win, mz, mz + W * H, mz + 2 * W * H, mz + 3 * W * H, probe, valid);
+    int covered = 0;
+    for (int p = 0; p < W * H; ++p) {
+        zlim[p] = win[p] >= 0 ? (float)mz[p] : INFINITY;
+        covered += win[p] >= 0;
+        for (int ch = 0; ch < 3; ++ch) bgmap[3 * p + ch] = win[p] >= 0 ? 0.9f : bg[ch];
+    }
+    rc |= sas_oracle_render_limited(&s, V, K, W, H, bg, 1, rgb, a, d, r8, NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0, st, zlim, bgmap);
+    printf("   %d triangles cover %d pixels\n", nt, covered);
+    free(camv); free(zlim); free(bgmap); free(tris); free(win); free(mz); free(probe); free(valid);
     free(means); free(quats); free(scales); free(op); free(col); free(gid); free(rgb); free(a); free(d); free(r8);
     free(rad); free(toff); free(m2); free(dep); free(con); free(cc); free(ids);
     return rc;

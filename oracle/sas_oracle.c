@@ -421,13 +421,16 @@ static inline void tile_coefs(const proj_t *g, float X0, float Y0, tcoef_t *t)
 }
 
 /* T6 for one pixel; (x, y) = pixel centre relative to the tile's centre */
-static inline void blend_pixel(const proj_t *P, const int32_t *ids, const tcoef_t *tc, int64_t n, float x, float y,
+/* zlim: the pixel's depth limit (DESIGN.md 3 "Meshes", rule 3): the first entry with depth >= zlim ends the pixel -- it is not
+ * added, nor is anything after it.  +Inf (no limit) leaves every frame what it was: the depths of a list are finite. */
+static inline void blend_pixel(const proj_t *P, const int32_t *ids, const tcoef_t *tc, int64_t n, float x, float y, float zlim,
                                float out_acc[4], float *out_T)
 {
     float T = 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, ad = 0.0f;
     for (int64_t k = 0; k < n; ++k) {
         const proj_t *g = &P[ids[k]];
         const tcoef_t *t = &tc[k];
+        if (g->depth >= zlim) break;
         const float dx = t->u - x, dy = t->v - y;
         float sigma = fmaf(dx, fmaf(t->B, dy, t->hA * dx), (t->hC * dy) * dy);
         float alpha = fminf(OC_MAX_ALPHA, g->opac * sas_oracle_expf(-sigma));
@@ -578,12 +581,17 @@ int sas_oracle_trace_pixel(const sas_oracle_scene *s, const float viewmat[16], c
  * Optional outputs may be NULL.  Projection dumps are [n]-sized; tile_offsets is [tiles+1];
  * sorted_ids receives at most sorted_cap entries.  stats = {n_visible, n_intersections (gsplat's rectangles), 0}.
  * Returns 0, or -1 on allocation failure.
+ *
+ * sas_oracle_render_limited takes two more optional inputs, the rules 3 and 4 of DESIGN.md 3 "Meshes" and nothing else:
+ * zlim [H,W], a per-pixel depth limit (blend_pixel), and bgmap [H,W,3], a per-pixel background for the epilogue.  alpha, depth,
+ * rgb8 and the depth fill follow from those unchanged.  Both NULL: sas_oracle_render.  The variant study ignores zlim.
  */
-int sas_oracle_render(const sas_oracle_scene *s, const float viewmat[16], const float K[9], int W, int H,
-                      const float bg[3], int depth_mode,
-                      float *rgb, float *alpha, float *depth, uint8_t *rgb8,
-                      int32_t *o_radii, float *o_means2d, float *o_depths, float *o_conics, float *o_colors,
-                      int32_t *o_tile_offsets, int32_t *o_sorted_ids, int64_t sorted_cap, int64_t *stats)
+int sas_oracle_render_limited(const sas_oracle_scene *s, const float viewmat[16], const float K[9], int W, int H,
+                              const float bg[3], int depth_mode,
+                              float *rgb, float *alpha, float *depth, uint8_t *rgb8,
+                              int32_t *o_radii, float *o_means2d, float *o_depths, float *o_conics, float *o_colors,
+                              int32_t *o_tile_offsets, int32_t *o_sorted_ids, int64_t sorted_cap, int64_t *stats,
+                              const float *zlim, const float *bgmap)
 {
     cam_t c;
     cam_from(viewmat, K, W, H, &c);
@@ -652,18 +660,20 @@ int sas_oracle_render(const sas_oracle_scene *s, const float viewmat[16], const 
                 int j = tx * OC_TILE + xx;
                 if (j >= W) break;
                 float acc[4], T;
-                if (g_variant == 0) blend_pixel(P, tl, tc, tn, (float)xx + 0.5f - cen, (float)yy + 0.5f - cen, acc, &T);
+                const int64_t pix = (int64_t)i * W + j;
+                const float *pbg = bgmap ? bgmap + 3 * pix : bg;
+                if (g_variant == 0) blend_pixel(P, tl, tc, tn, (float)xx + 0.5f - cen, (float)yy + 0.5f - cen,
+                                                zlim ? zlim[pix] : INFINITY, acc, &T);
                 else blend_pixel_variant(g_variant, P, tl, tc, tn, (float)xx + 0.5f - cen, (float)yy + 0.5f - cen,
                                          (float)j + 0.5f, (float)i + 0.5f, acc, &T);
                 float a = 1.0f - T;
-                int64_t pix = (int64_t)i * W + j;
                 float ED = acc[3] / fmaxf(a, 1e-10f);
                 if (ED > maxED) maxED = ED;
                 if (alpha) alpha[pix] = a;
                 if (depth) depth[pix] = ED;
                 for (int ch = 0; ch < 3; ++ch) {
                     /* T0: rgb = clamp(render + (1 - alpha) * background, 0, 1), two roundings */
-                    float v = acc[ch] + (1.0f - a) * bg[ch];
+                    float v = acc[ch] + (1.0f - a) * pbg[ch];
                     v = fminf(fmaxf(v, 0.0f), 1.0f);
                     if (rgb) rgb[3 * pix + ch] = v;
                     if (rgb8) rgb8[3 * pix + ch] = (uint8_t)(int)floorf(fmaf(v, 255.0f, 0.5f));
@@ -701,6 +711,40 @@ int sas_oracle_render(const sas_oracle_scene *s, const float viewmat[16], const 
     if (stats) { stats[0] = n_vis; stats[1] = M; stats[2] = 0; }
     free(P); free(tcount); free(keys); free(ids); free(cursor); free(tc_all);
     return 0;
+}
+
+int sas_oracle_render(const sas_oracle_scene *s, const float viewmat[16], const float K[9], int W, int H,
+                      const float bg[3], int depth_mode,
+                      float *rgb, float *alpha, float *depth, uint8_t *rgb8,
+                      int32_t *o_radii, float *o_means2d, float *o_depths, float *o_conics, float *o_colors,
+                      int32_t *o_tile_offsets, int32_t *o_sorted_ids, int64_t sorted_cap, int64_t *stats)
+{
+    return sas_oracle_render_limited(s, viewmat, K, W, H, bg, depth_mode, rgb, alpha, depth, rgb8, o_radii, o_means2d, o_depths,
+                                     o_conics, o_colors, o_tile_offsets, o_sorted_ids, sorted_cap, stats, NULL, NULL);
+}
+
+/* Mesh vertices as the projection moves the Gaussian means (project_one): the group's pose, then the view, each one fused
+ * affine3 chain in float32.  group NULL or group_Rt NULL: unposed.  world [n,3] (posed), camv [n,3] (camera frame) and
+ * campos [3] (cam_from's) may each be NULL.  What oracle/mesh_ref.py starts from: everything after this is float64. */
+void sas_oracle_pose_points(const float *pts, int64_t n, const uint8_t *group, int32_t n_groups, const float *group_Rt,
+                            const float viewmat[16], float *world, float *camv, float *campos)
+{
+    const float K1[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    cam_t c;
+    cam_from(viewmat, K1, 16, 16, &c);
+    if (campos) { campos[0] = c.campos[0]; campos[1] = c.campos[1]; campos[2] = c.campos[2]; }
+    for (int64_t i = 0; i < n; ++i) {
+        float m[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+        if (group && group_Rt && (int32_t)group[i] < n_groups) {
+            const float *G = group_Rt + 12 * (int64_t)group[i];
+            float mg[3];
+            for (int r = 0; r < 3; ++r) mg[r] = affine3(G + 4 * r, G[4 * r + 3], m);
+            m[0] = mg[0]; m[1] = mg[1]; m[2] = mg[2];
+        }
+        if (world) { world[3 * i] = m[0]; world[3 * i + 1] = m[1]; world[3 * i + 2] = m[2]; }
+        if (camv)
+            for (int r = 0; r < 3; ++r) camv[3 * i + r] = affine3(c.R + 3 * r, c.t[r], m);
+    }
 }
 
 /* RGB-D consumer, nerfstudio_utils.py:424-445: x = (u - cx) * d / fx, y = (v - cy) * d / fy, z = d

@@ -100,8 +100,17 @@ __global__ __launch_bounds__(kMeshSetupThreads) void k_mesh_setup(SasMeshScene m
     }
     if (!ok) return;
     // shading: |n . v|, n the unit world-space face normal (two-sided), v the unit ray from the camera centre to the centroid
-    const double e1[3] = {(double)wv[1][0] - wv[0][0], (double)wv[1][1] - wv[0][1], (double)wv[1][2] - wv[0][2]};
-    const double e2[3] = {(double)wv[2][0] - wv[0][0], (double)wv[2][1] - wv[0][1], (double)wv[2][2] - wv[0][2]};
+    // (the two edges that leave the vertex NEAREST the origin: from a finite vertex at 1e30, as the mesh fuzzer drew one, both edges
+    // are that vertex's negative to sixteen digits, their cross product is exactly zero and the triangle was dropped as degenerate)
+    int b0 = 0;
+    float bmag = fabsf(wv[0][0]) + fabsf(wv[0][1]) + fabsf(wv[0][2]);
+    for (int k = 1; k < 3; ++k) {
+        const float mag = fabsf(wv[k][0]) + fabsf(wv[k][1]) + fabsf(wv[k][2]);
+        if (mag < bmag) { bmag = mag; b0 = k; }
+    }
+    const int b1 = (b0 + 1) % 3, b2 = (b0 + 2) % 3;
+    const double e1[3] = {(double)wv[b1][0] - wv[b0][0], (double)wv[b1][1] - wv[b0][1], (double)wv[b1][2] - wv[b0][2]};
+    const double e2[3] = {(double)wv[b2][0] - wv[b0][0], (double)wv[b2][1] - wv[b0][1], (double)wv[b2][2] - wv[b0][2]};
     double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
     const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
     if (!(nn > 0.0) || !isfinite(nn)) return;   // degenerate
@@ -113,7 +122,10 @@ __global__ __launch_bounds__(kMeshSetupThreads) void k_mesh_setup(SasMeshScene m
     const float4 col = m.color[t];
     const float cr = (float)fmin(fmax((double)col.x * shade, 0.0), 1.0), cg = (float)fmin(fmax((double)col.y * shade, 0.0), 1.0),
                 cb = (float)fmin(fmax((double)col.z * shade, 0.0), 1.0);
-    // near clip: the polygon's vertices in order, each edge that crosses z = kNear cut from its inside end
+    // near clip: the polygon's vertices in order, each edge that crosses z = kNear cut from its end NEARER the plane (a rule that
+    // does not depend on the direction the edge is walked: a neighbour gets the same point).  Cut from an end at z = 1e30 -- a
+    // finite vertex there, found by the mesh fuzzer -- the step back to the plane is the whole edge and i + s (o - i) cancels to
+    // rounding noise of 1e13: the clipped corner landed at the principal point.
     Vc poly[4];
     int np = 0;
     for (int k = 0; k < 3; ++k) {
@@ -121,7 +133,9 @@ __global__ __launch_bounds__(kMeshSetupThreads) void k_mesh_setup(SasMeshScene m
         const bool ain = a.z >= (double)kNear, bin = b.z >= (double)kNear;
         if (ain) poly[np++] = a;
         if (ain != bin) {
-            const Vc &i = ain ? a : b, &o = ain ? b : a;
+            const double da = fabs(a.z - (double)kNear), db = fabs(b.z - (double)kNear);
+            const bool from_a = da < db || (da == db && ain);   // (a tie: the inside end, whichever way the edge is walked)
+            const Vc &i = from_a ? a : b, &o = from_a ? b : a;
             const double s = ((double)kNear - i.z) / (o.z - i.z);
             poly[np++] = Vc{i.x + s * (o.x - i.x), i.y + s * (o.y - i.y), (double)kNear};
         }

@@ -5,111 +5,28 @@ a depth d, flat-coloured c, renders exactly the oracle's frame of the scene filt
 background c -- asserted bit for bit, with d in a gap of the GPU's own Gaussian depths.  Coverage (which triangle wins a
 pixel) is held to a float64 ray cast, away from edges.
 """
-import ctypes
+import sys
+from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
-import oracle
-from conftest import load_twin_fixture, twin_scene_kwargs
 from sim_a_splat_amd import _capi
 from sim_a_splat_amd.rasterizer import Rasterizer, SasError
-from sim_a_splat_amd.synthetic import config_scene_and_cameras, make_scene, random_group_poses, ring_camera
+from sim_a_splat_amd.synthetic import make_scene
+
+sys.path.insert(0, str(Path(__file__).resolve().parent / "tools"))
+from mesh_cases import (BG, OUTS, cam_to_world as _cam_to_world, colours as _colours, config3_window as _config3_window,  # noqa: E402
+                        full_quad as _full_quad, oracle_frame as _oracle, random_triangles as _random_triangles, ray_cast as _ray_cast,
+                        ring as _ring, same as _same, screen_quad as _screen_quad, stable_ref as _stable_ref, synthetic as _synthetic,
+                        to_numpy as _np, twin as _twin, upload as _upload)
 
 pytestmark = pytest.mark.gpu
-OUTS = ("rgb", "alpha", "depth", "rgb8")
-
-
-# ---- scenes ---------------------------------------------------------------------------------------------------------
-def _twin(name):
-    g = load_twin_fixture(name)
-    means, op, colors, kw = twin_scene_kwargs(g)
-    W, H = [int(v) for v in g["wh"]]
-    gid = kw.get("group_id")
-    sc = dict(means=means, op=op, colors=colors, sh=kw["sh_degree"], quats=kw.get("quats"), scales=kw.get("scales"),
-              cov6=kw.get("cov6"), gid=gid, G=int(g["group_Rt"].shape[0]) if gid is not None else 0,
-              Rt=g["group_Rt"] if gid is not None else None)
-    return sc, (np.asarray(g["viewmat"], np.float32).reshape(4, 4), np.asarray(g["K"], np.float32).reshape(3, 3), W, H)
-
-
-def _synthetic(n, seed, ls, n_groups=0):
-    s = make_scene(n, seed=seed, log_scale_mean=float(np.log(ls)), n_groups=n_groups)
-    G = n_groups if s.group_id is not None else 0
-    return dict(means=s.means, op=s.opacities, colors=s.sh, sh=s.sh_degree, quats=s.quats, scales=s.scales, cov6=None,
-                gid=s.group_id, G=G, Rt=random_group_poses(G, seed + 1) if G else None)
-
-
-def _config3_window():
-    s, cams = config_scene_and_cameras(3)
-    cam = cams[0]
-    K = np.array(cam.K, np.float32).copy()
-    K[0, 2] -= 800.0
-    K[1, 2] -= 420.0
-    sc = dict(means=s.means, op=s.opacities, colors=s.sh, sh=s.sh_degree, quats=s.quats, scales=s.scales, cov6=None,
-              gid=None, G=0, Rt=None)
-    return sc, (np.asarray(cam.viewmat, np.float32), K, 320, 240)
-
-
-def _ring(W=96, H=64, f=90.0, yaw=15.0):
-    c = ring_camera(W, H, f, yaw_deg=yaw, elev=0.2)
-    return np.asarray(c.viewmat, np.float32), np.asarray(c.K, np.float32), W, H
-
-
-def _upload(r, sc, keep=None):
-    sel = slice(None) if keep is None else keep
-    pick = lambda a: None if a is None else np.asarray(a)[sel]
-    r.upload(pick(sc["means"]), pick(sc["op"]), pick(sc["colors"]), quats=pick(sc["quats"]), scales=pick(sc["scales"]),
-             covariances=pick(sc["cov6"]), sh_degree=sc["sh"], group_id=pick(sc["gid"]), n_groups=sc["G"])
-    if sc["G"]:
-        r.set_group_poses(sc["Rt"])
-
-
-def _oracle(sc, cam, bg, keep=None):
-    V, K, W, H = cam
-    sel = slice(None) if keep is None else keep
-    pick = lambda a: None if a is None else np.asarray(a)[sel]
-    return oracle.render(pick(sc["means"]), pick(sc["op"]), pick(sc["colors"]), V, K, W, H, quats=pick(sc["quats"]),
-                         scales=pick(sc["scales"]), cov6=pick(sc["cov6"]), sh_degree=sc["sh"], group_id=pick(sc["gid"]),
-                         group_Rt=sc["Rt"], background=bg, want_rgb8=True)
-
-
-def _np(out):
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
 
 def _frame(r, cam, bg, want=OUTS):
     V, K, W, H = cam
     return _np(r.render(V, K, W, H, bg, want=want))
-
-
-def _same(a, b, keys=("rgb", "alpha", "depth", "rgb8"), where=None):
-    for k in keys:
-        x, y = np.asarray(a[k]), np.asarray(b[k])
-        if where is not None:
-            x, y = x[where], y[where]
-        assert x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8)), (k, np.abs(x.astype(np.float64) - y).max())
-
-
-# ---- meshes in camera space -------------------------------------------------------------------------------------------
-def _cam_to_world(cam, pc):
-    V = np.asarray(cam[0], np.float64).reshape(4, 4)
-    R, t = V[:3, :3], V[:3, 3]
-    return (pc - t) @ R          # R^T (p - t)
-
-
-def _screen_quad(cam, d, u0, u1, v0, v1):
-    """Two triangles at camera depth d whose corners project to (u, v) in [u0, u1] x [v0, v1]."""
-    V, K, W, H = cam
-    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
-    uv = np.array([[u0, v0], [u1, v0], [u1, v1], [u0, v1]], np.float64)
-    pc = np.stack([(uv[:, 0] - cx) * d / fx, (uv[:, 1] - cy) * d / fy, np.full(4, d)], 1)
-    return _cam_to_world(cam, pc).astype(np.float32), np.array([[0, 1, 2], [0, 2, 3]], np.int32)
-
-
-def _full_quad(cam, d):
-    W, H = cam[2], cam[3]
-    return _screen_quad(cam, d, -20.0, W + 20.0, -20.0, H + 20.0)
 
 
 def _visible_depths(r):
@@ -154,7 +71,6 @@ def _scene_with_gap(r, sc, cam):
     return sc, d
 
 
-BG = (0.12, 0.34, 0.56)
 C = (0.9, 0.2, 0.1)
 
 
@@ -261,56 +177,10 @@ def test_c_half_frame_quad(name):
 
 
 # ---- (d) coverage against a float64 ray cast ------------------------------------------------------------------------------
-def _ray_cast(cam, verts, tris, eps=0.0):
-    """Index of the nearest triangle hit by the ray through every pixel centre (+ eps offsets), -1 for none; float64.
-    A hit counts when its camera depth is >= 0.01 (the near plane)."""
-    V, K, W, H = cam
-    Vd = np.asarray(V, np.float64).reshape(4, 4)
-    pc = np.asarray(verts, np.float64) @ Vd[:3, :3].T + Vd[:3, 3]
-    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
-    ys, xs = np.mgrid[0:H, 0:W]
-    dx = ((xs + 0.5 + eps[0]) - cx) / fx
-    dy = ((ys + 0.5 + eps[1]) - cy) / fy
-    D = np.stack([dx, dy, np.ones_like(dx)], -1).reshape(-1, 3)
-    best = np.full(D.shape[0], np.inf)
-    idx = np.full(D.shape[0], -1)
-    for k, (a, b, c) in enumerate(tris):
-        A, B, Cc = pc[a], pc[b], pc[c]
-        e1, e2 = B - A, Cc - A
-        pv = np.cross(D, e2)
-        det = pv @ e1
-        with np.errstate(divide="ignore", invalid="ignore"):
-            inv = 1.0 / det
-            u = (pv @ -A) * inv
-            qv = np.cross(-A, e1)
-            v = (D @ qv) * inv
-            s = (e2 @ qv) * inv            # ray parameter = camera depth (D.z == 1)
-        hit = (np.abs(det) > 0) & (u >= 0) & (v >= 0) & (u + v <= 1) & (s >= 0.01) & (s < best)
-        best[hit] = s[hit]
-        idx[hit] = k
-    return idx.reshape(H, W)
-
-
-def _colours(n, seed):
-    rng = np.random.default_rng(seed)
-    cols = set()
-    while len(cols) < n:
-        cols.add(tuple(int(x) for x in rng.integers(10, 246, 3)))
-    cols = np.array(sorted(cols), np.float64)
-    rng.shuffle(cols)
-    return cols
-
-
 def _winner_map(rgb8, cols8):
     key = rgb8.astype(np.int64) @ np.array([1, 256, 65536])
     lut = {int(c @ np.array([1, 256, 65536])): i for i, c in enumerate(cols8.astype(np.int64))}
     return np.vectorize(lambda k: lut.get(int(k), -1))(key)
-
-
-def _stable_ref(cam, verts, tris, tol=1e-3):
-    maps = [_ray_cast(cam, verts, tris, e) for e in ((0, 0), (tol, 0), (-tol, 0), (0, tol), (0, -tol))]
-    stable = np.all([m == maps[0] for m in maps[1:]], axis=0)
-    return maps[0], stable
 
 
 def _empty_scene_rasterizer(n_groups=0):
@@ -319,29 +189,6 @@ def _empty_scene_rasterizer(n_groups=0):
     r.upload(z, np.zeros(0, np.float32), z, quats=np.zeros((0, 4), np.float32), scales=z, sh_degree=-1,
              group_id=np.zeros(0, np.uint8) if n_groups else None, n_groups=n_groups)
     return r
-
-
-def _random_triangles(cam, n, seed):
-    """Triangles in camera space: some cross the near plane, some reach beyond the frame, many overlap; then to world."""
-    rng = np.random.default_rng(seed)
-    V, K, W, H = cam
-    fx, cx, fy, cy = float(K[0, 0]), float(K[0, 2]), float(K[1, 1]), float(K[1, 2])
-    pts = []
-    for k in range(n):
-        zc = rng.uniform(0.5, 6.0)
-        u = rng.uniform(-0.3 * W, 1.3 * W, 3)
-        v = rng.uniform(-0.3 * H, 1.3 * H, 3)
-        z = zc + rng.uniform(-0.4, 0.4, 3)
-        if k % 7 == 0:
-            z[0] = -0.5                                   # crosses the near plane
-        pts.append(np.stack([(u - cx) * np.abs(z) / fx, (v - cy) * np.abs(z) / fy, z], 1))
-    pc = np.concatenate(pts)
-    tris = np.arange(3 * n, dtype=np.int32).reshape(n, 3)
-    # two triangles sharing an edge (a split quad), flat in depth
-    q, qt = _screen_quad(cam, 2.0, 0.3 * W, 0.7 * W, 0.2 * H, 0.8 * H)
-    verts = np.concatenate([_cam_to_world(cam, pc), q.astype(np.float64)]).astype(np.float32)
-    tris = np.concatenate([tris, qt + 3 * n]).astype(np.int32)
-    return verts, tris
 
 
 def test_d_coverage_matches_ray_cast():

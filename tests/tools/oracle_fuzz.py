@@ -15,6 +15,11 @@ bit for bit (the arithmetic contract); the seeded pytest cases fix 
 
     python tests/tools/oracle_fuzz.py [n_seeds] [first_seed] [poison-all]         (exit code 1 on the first difference; prints each case)
 
+  meshes     `--meshes`: every case also gets 1-60 triangles (draw_mesh_case), and the frames are held to oracle.mesh_ref + the
+             depth-limited oracle on the pixels the reference calls stable (oracle/mesh_ref.py); the excluded share is printed
+
+    python tests/tools/oracle_fuzz.py --meshes [n_seeds] [first_seed]
+
 Test infrastructure: lives under tests/ because it calls the oracle (the checker)."""
 import sys
 from pathlib import Path
@@ -195,6 +200,146 @@ def run_pipelined(r, c: dict, inp: dict, gid) -> list:
     return diffs
 
 
+# ---- meshes -----------------------------------------------------------------------------------------------------------------
+# The seeds the suite runs (test_gpu_d_oracle_fuzz.py): from 0 upward, skipping those whose excluded share, from the reference and
+# the oracle alone, exceeds 10 % (one-tile-wide strips, principal points far outside the image).  tests/test_mesh_ref_cpu.py
+# recomputes the list and asserts that no more than 5 of the first 45 seeds were skipped.
+MESH_FUZZ_SEEDS = tuple(range(40))
+MESH_MAX_EXCLUDED = 0.10
+# Found by `--meshes 400`: with a finite vertex at z = 1e30 as the inside end of an edge that crosses the near plane, k_mesh_setup's
+# cut i + s (o - i) cancelled to rounding noise and the clipped corner landed at the principal point (seeds 61, 161, 181; fixed:
+# the edge is cut from its end nearer the plane).  Seeds 177, 213, 387 are far vertices that the kernel always drew right and
+# the reference's first formulation did not.  Seeds 163, 279: the far vertex is the triangle's first, the shading normal's two edges
+# from it cancelled to exactly zero and the triangle was dropped as degenerate (fixed: the edges that leave the vertex nearest the
+# origin).  All eight are kept as named cases.
+MESH_SEEDS_VERTEX_AT_1E30 = (61, 161, 181, 163, 279, 177, 213, 387)
+
+
+def draw_mesh_case(seed: int, poison_all: bool = False) -> dict:
+    """draw_case(seed) plus, from a generator stream of its own, 1-60 triangles drawn in the first camera's space (the coverage
+    test's recipe: some across the near plane, some beyond the frame, a split quad, and a few large tilted ones through the cloud),
+    colours, ka / kd, and now and then a pose group.  Entry points: single, batch, posed, host (the pipelined arm becomes a single
+    frame or a batch: non-blocking mesh frames have a fixed case in test_gpu_h_mesh_oracle.py).  One case in eight has poisoned
+    vertices (NaN, +-Inf, 1e30): such triangles are dropped, in the reference too."""
+    import mesh_cases as mc
+    c = draw_case(seed, poison_all)
+    rng = np.random.default_rng(66_000 + seed)
+    if c["entry"] == "pipelined":
+        c["entry"] = "single" if len(c["cams"]) == 1 else "batch"
+    cm = c["cams"][0]
+    W, H = c["W"], c["H"]
+    V, K = np.asarray(cm.viewmat, np.float64).reshape(4, 4), np.asarray(cm.K, np.float64).reshape(3, 3)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    dist = float(np.linalg.norm(np.linalg.solve(V[:3, :3], V[:3, 3])))          # the camera's distance from the cloud's centre
+    n = int(rng.integers(1, 61))
+    tri = []                                                                     # camera-space triangles [3,3]
+    for _ in range(int(rng.integers(0, 3))):                                     # large tilted planes through the cloud
+        za, zb = sorted(rng.uniform(max(0.2, dist - 1.0), dist + 1.0, 2))
+        uv = np.array([[-20.0, -20.0], [W + 20.0, -20.0], [W + 20.0, H + 20.0], [-20.0, H + 20.0]])
+        w = 1.0 / za + (1.0 / zb - 1.0 / za) * (rng.uniform(0.2, 0.8) * uv[:, 0] / W + rng.uniform(0.2, 0.8) * uv[:, 1] / H)
+        z = 1.0 / np.maximum(w, 1e-3)
+        q = np.stack([(uv[:, 0] - cx) * z / fx, (uv[:, 1] - cy) * z / fy, z], 1)
+        tri += [q[[0, 1, 2]], q[[0, 2, 3]]]
+    d = float(rng.uniform(0.5, dist + 1.0))                                      # a split quad, flat in depth
+    uv = np.array([[0.3 * W, 0.2 * H], [0.7 * W, 0.2 * H], [0.7 * W, 0.8 * H], [0.3 * W, 0.8 * H]])
+    q = np.stack([(uv[:, 0] - cx) * d / fx, (uv[:, 1] - cy) * d / fy, np.full(4, d)], 1)
+    tri += [q[[0, 1, 2]], q[[0, 2, 3]]]
+    k = 0
+    while len(tri) < n:
+        zc = rng.uniform(0.3, dist + 2.0)
+        u, v = rng.uniform(-0.3 * W, 1.3 * W, 3), rng.uniform(-0.3 * H, 1.3 * H, 3)
+        z = zc + rng.uniform(-0.4, 0.4, 3)
+        if k % 7 == 0:
+            z[0] = -0.5                                                          # crosses the near plane
+        tri.append(np.stack([(u - cx) * np.abs(z) / fx, (v - cy) * np.abs(z) / fy, z], 1))
+        k += 1
+    order = rng.permutation(len(tri))[:n]
+    pc = np.concatenate([tri[i] for i in order])
+    world = np.linalg.solve(V[:3, :3], (pc - V[:3, 3]).T).T
+    T = len(order)
+    groups = None
+    if c["n_groups"] and rng.random() < 0.5:
+        g = int(rng.integers(0, c["n_groups"]))
+        world, groups = mc.to_group_local(world, c["poses"][0][g]), np.full(T, g, np.uint8)
+    verts = np.ascontiguousarray(world, dtype=np.float32)
+    poisoned_vertices = bool(rng.random() < 0.125)
+    if poisoned_vertices:
+        flat = verts.reshape(-1)
+        kk = int(rng.integers(1, 4))
+        flat[rng.integers(0, flat.size, size=kk)] = np.array([np.nan, np.inf, -np.inf, 1e30], np.float32)[rng.integers(0, 4, size=kk)]
+    ka, kd = (0.4, 0.6) if rng.random() < 0.5 else (float(rng.uniform(0.0, 1.0)), float(rng.uniform(0.0, 1.0)))
+    c["mesh"] = dict(verts=verts, tris=np.arange(3 * T, dtype=np.int32).reshape(T, 3), cols=rng.uniform(0, 1, size=(T, 3)).astype(np.float32),
+                     groups=groups, ka=ka, kd=kd, poisoned_vertices=poisoned_vertices)
+    c["full_sort"] = False
+    return c
+
+
+def _view_poses(c: dict) -> list:
+    if not c["poses"]:
+        return [None] * len(c["cams"])
+    return list(c["poses"][:len(c["cams"])]) if c["entry"] == "posed" else [c["poses"][0]] * len(c["cams"])
+
+
+def mesh_reference(c: dict, i: int, want_frame: bool = True) -> dict:
+    """View i of a mesh case from the reference and the oracle alone: stable mask, excluded share and (want_frame) the frame."""
+    from oracle import mesh_ref
+    sc, cm, m, W, H = c["scene"], c["cams"][i], c["mesh"], c["W"], c["H"]
+    inp = scene_inputs(c)
+    gid = sc.group_id if c["n_groups"] else None
+    pose = _view_poses(c)[i]
+    kw = dict(quats=inp["quats"], scales=inp["scales"], cov6=inp["cov6"], sh_degree=c["deg"], group_id=gid, group_Rt=pose, background=c["bg"])
+    dump = oracle.render(sc.means, sc.opacities, inp["colors"], cm.viewmat, cm.K, W, H, dump=True, **kw)
+    ref = mesh_ref.reference(m["verts"], m["tris"], m["cols"], m["groups"], pose if gid is not None else None, m["ka"], m["kd"], cm.viewmat, cm.K, W, H)
+    st = mesh_ref.stability(ref, dump)
+    out = dict(stable=st["stable"], excluded=float(1.0 - st["stable"].mean()), covered=float((ref["winner"] >= 0).mean()))
+    if want_frame:
+        zlim, bgmap = mesh_ref.frame_inputs(ref, c["bg"])
+        out["frame"] = oracle.render(sc.means, sc.opacities, inp["colors"], cm.viewmat, cm.K, W, H, want_rgb8=True, zlim=zlim, bgmap=bgmap, **kw)
+    return out
+
+
+def mesh_excluded_share(c: dict) -> float:
+    return max(mesh_reference(c, i, want_frame=False)["excluded"] for i in range(len(c["cams"])))
+
+
+def run_mesh_case(r, c: dict):
+    """Renders the mesh case on the GPU through its entry point; returns (differences on stable pixels, largest excluded share)."""
+    import mesh_cases as mc
+    sc, cams, W, H, fill, BG, m = c["scene"], c["cams"], c["W"], c["H"], c["fill"], c["bg"], c["mesh"]
+    inp = scene_inputs(c)
+    gid = sc.group_id if c["n_groups"] else None
+    r.upload(sc.means, sc.opacities, inp["colors"], quats=inp["quats"], scales=inp["scales"], covariances=inp["cov"], sh_degree=c["deg"],
+             group_id=gid, n_groups=c["n_groups"])
+    r.upload_meshes(m["verts"], m["tris"], m["cols"], groups=m["groups"], ambient=m["ka"], diffuse=m["kd"])
+    Vs, Ks = np.stack([cm.viewmat for cm in cams]), np.stack([cm.K for cm in cams])
+    if c["poses"]:
+        r.set_group_poses(c["poses"][0])
+    if c["entry"] == "single":
+        o = r.render(Vs[0], Ks[0], W, H, BG, want=KEYS, depth_fill_max=fill)
+        got = [{k: v.cpu().numpy() for k, v in o.items()}]
+    elif c["entry"] == "posed":
+        o = r.render_batch(Vs, Ks, W, H, BG, want=KEYS, depth_fill_max=fill, pose_sets=np.stack(c["poses"]), pose_set=list(range(len(cams))))
+        got = [{k: v[i].cpu().numpy() for k, v in o.items()} for i in range(len(cams))]
+    elif c["entry"] == "host":
+        frames = r.render_batch_host(Vs, Ks, W, H, BG).numpy()
+        got = [{"rgb8": frames[i]} for i in range(len(cams))]
+    else:
+        o = r.render_batch(Vs, Ks, W, H, BG, want=KEYS, depth_fill_max=fill)
+        got = [{k: v[i].cpu().numpy() for k, v in o.items()} for i in range(len(cams))]
+    diffs, excluded = [], 0.0
+    for i in range(len(cams)):
+        e = mesh_reference(c, i)
+        excluded = max(excluded, e["excluded"])
+        diffs += [f"view {i} {d}" for d in mc.compare_stable(got[i], e["frame"], e["stable"], fill=fill, bits=False)]
+    return diffs, excluded
+
+
+def describe_mesh(c: dict) -> str:
+    m = c["mesh"]
+    return describe(c) + (f" | triangles={len(m['tris'])} group={'-' if m['groups'] is None else int(m['groups'][0])} ka={m['ka']:.2f} kd={m['kd']:.2f}"
+                          f"{' POISONED VERTICES' if m['poisoned_vertices'] else ''}")
+
+
 def describe(c: dict) -> str:
     return (f"seed {c['seed']}: n={c['scene'].means.shape[0]} degree={c['deg']} groups={c['n_groups']} {c['W']}x{c['H']} views={len(c['cams'])} "
             f"entry={c['entry']}{'x%d' % c['steps'] if c['entry'] == 'pipelined' else ''} fill={c['fill']}{' full_sort' if c['full_sort'] else ''}{'' if c['bg'] is BG else ' bg=drawn'}{' POISONED' if c['poisoned'] else ''}")
@@ -202,12 +347,21 @@ def describe(c: dict) -> str:
 
 def main(argv) -> int:
     from sim_a_splat_amd.rasterizer import Rasterizer
+    meshes = "--meshes" in argv
+    argv = [a for a in argv if a != "--meshes"]
     n_seeds = int(argv[1]) if len(argv) > 1 else 60
     first = int(argv[2]) if len(argv) > 2 else 0
     poison_all = len(argv) > 3 and argv[3] == "poison-all"
     r = Rasterizer(0)
     bad = 0
     for seed in range(first, first + n_seeds):
+        if meshes:
+            c = draw_mesh_case(seed, poison_all)
+            diffs, excluded = run_mesh_case(r, c)
+            print(describe_mesh(c), f"excluded={100 * excluded:.2f} % ->", "bit-equal on stable pixels" if not diffs else "DIFFERENT: " + "; ".join(diffs),
+                  flush=True)
+            bad += bool(diffs)
+            continue
         c = draw_case(seed, poison_all)
         diffs = run_case(r, c)
         st = r.stats()
@@ -223,7 +377,9 @@ def main(argv) -> int:
         print(f"bounds-checked build: {out[0]} out-of-range accesses" + (f" (first: code {out[1]}, index {out[2]}, limit {out[3]})" if out[0] else ""))
         bad += int(out[0] != 0)
     r.close()
-    print(f"{n_seeds} cases from seed {first}: " + ("every output bit-equal to the oracle" if bad == 0 else f"{bad} cases differ"))
+    print(f"{n_seeds} {'mesh ' if meshes else ''}cases from seed {first}: " +
+          (("every output bit-equal to the reference on its stable pixels" if meshes else "every output bit-equal to the oracle") if bad == 0
+           else f"{bad} cases differ"))
     return 1 if bad else 0
 
 
