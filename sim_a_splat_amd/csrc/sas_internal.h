@@ -174,7 +174,8 @@ void sas_launch_host_copy(hipStream_t st, const SasHostCopy &h);
 
 // Per-Gaussian feature channels (sas_scene_features / sas_render_features; DESIGN.md 3, "Feature channels").
 // The store is [chunks][n_pad][SAS_FEAT_K] float32 in slot order, channels c >= C zero; k_blend_features composites one chunk
-// of SAS_FEAT_K channels per workgroup, from the complete lists a SAS_FULL_SORT frame keeps.
+// of SAS_FEAT_K channels per workgroup, from the complete lists a SAS_FULL_SORT frame keeps, through the frame's own compositing
+// loop (blend_range) with the chunk's channels in the colours' place.
 #define SAS_FEAT_K 8
 #define SAS_MAX_FEATURES 256
 struct SasFeatures {

@@ -17,6 +17,8 @@
 
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #pragma clang fp contract(off)
 
 namespace {
@@ -34,6 +36,15 @@ DEV bool key_greater(unsigned long long a, unsigned long long b, const int *perm
     const unsigned ha = hi32(a), hb = hi32(b);
     if (ha != hb) return ha > hb;
     return perm[lo32(a)] > perm[lo32(b)];
+}
+
+// A tile's segment [beg, end) of the frame's key / id arrays.  (The clamp to the arrays' capacity is a safety check: the
+// projection never hands out more.)
+DEV void tile_segment(const SasFrame &f, int tile, long long &beg, long long &end)
+{
+    beg = f.tile_offset[tile];
+    end = f.tile_offset[tile + 1];
+    if (end > f.cap) end = f.cap;
 }
 
 // ================================================================================================
@@ -247,6 +258,7 @@ __global__ __launch_bounds__(THREADS) void k_sort_radix(SasFrame f, const int *p
     const int tid = threadIdx.x, lane = tid & 63;
     for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x) {
         const int t = tl[oi];
+        // (tile_segment, written out: through the helper hipcc assigns this kernel's registers differently)
         const long long beg = f.tile_offset[t];
         long long end = f.tile_offset[t + 1];
         if (end > f.cap) end = f.cap;
@@ -297,9 +309,8 @@ __global__ __launch_bounds__(64) void k_sort_wave(SasFrame f, const int *perm, c
     const int lane = threadIdx.x;
     for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x) {
         const int t = tl[oi];
-        const long long beg = f.tile_offset[t];
-        long long end = f.tile_offset[t + 1];
-        if (end > f.cap) end = f.cap;
+        long long beg, end;
+        tile_segment(f, t, beg, end);
         const int n = (int)(end - beg);
         if (n <= 0 || n > CAP) continue;
         const unsigned long long *g = f.keys + beg;
@@ -416,13 +427,17 @@ __global__ __launch_bounds__(64) void k_sort_wave(SasFrame f, const int *perm, c
 // sigma(c - m) > (sqrt(thr + 0.05) + r)^2: no pixel of it can pass the loop's `sigma <= thr`.
 // The 0.05 margin is four orders of magnitude above any rounding difference between this
 // estimate and the contract's per-pixel sigma, so dropping a block never changes a pixel.
-DEV unsigned block_mask16(int tx, int ty, float mx, float my, float A, float B, float C, float thr)
+DEV float block_limit2(float A, float B, float C, float thr)
 {
     const float r2 = 1.125f * (A + C) + 2.25f * fabsf(B);
     // hardware square roots (1 ulp, no IEEE fix-up): the limit only feeds this conservative test, whose 0.05
     // margin is five orders of magnitude above their error (the IEEE forms cost 30 instructions per entry)
     const float lim = __builtin_amdgcn_sqrtf(thr + 0.05f) + __builtin_amdgcn_sqrtf(r2);
-    const float lim2 = lim * lim;
+    return lim * lim;
+}
+DEV unsigned block_mask16(int tx, int ty, float mx, float my, float A, float B, float C, float thr)
+{
+    const float lim2 = block_limit2(A, B, C, thr);
     float hx[4], bx[4], hy[4], dy[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -465,9 +480,7 @@ DEV void pixel_of_quad(int qd, int wv, int lane, int &ox, int &oy)
 // bit w = block w of quadrant qd can be reached (the test of block_mask16)
 DEV unsigned block_mask4(int tx, int ty, int qd, float mx, float my, float A, float B, float C, float thr)
 {
-    const float r2 = 1.125f * (A + C) + 2.25f * fabsf(B);
-    const float lim = __builtin_amdgcn_sqrtf(thr + 0.05f) + __builtin_amdgcn_sqrtf(r2);
-    const float lim2 = lim * lim;
+    const float lim2 = block_limit2(A, B, C, thr);
     float hx[2], bx[2], hy[2], dy[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -506,6 +519,17 @@ DEV PixConst pix_const(int ox, int oy)
     (void)ox;
     return PixConst{((float)oy + 0.5f) - kTileCentre};
 }
+// Pixel (ox, oy) of tile (tx, ty) starts: its image coordinates, whether it lies inside the image, its state; wdone: the wave has
+// no pixel inside.
+DEV PixState pixel_begin(const SasCam &c, int tx, int ty, int ox, int oy, int &ix, int &iy, bool &inside, bool &wdone)
+{
+    ix = tx * SAS_TILE + ox;
+    iy = ty * SAS_TILE + oy;
+    inside = ix < c.W && iy < c.H;
+    const PixState p = pix_init(inside, ox);
+    wdone = __all(!inside);
+    return p;
+}
 typedef float f32x3 __attribute__((ext_vector_type(3)));
 
 // Contract exp for an argument the caller has clamped to [-86, rounding noise] (sas_oracle_expf clamps to
@@ -524,6 +548,13 @@ DEV float c_expf_neg(float x, float e5 /* 0.0013400432653725147f, pinned in a re
     p = fma_(p, fr, 1.0000001192092896f);
     return __uint_as_float(__float_as_uint(p) + (__float_as_uint(tm) << 23));
 }
+
+// Contract T6 for one (pixel, splat) pair, step by step.  (dx, dy) = (u - x, v - y); K = (u, v, A/2, B), H = (C/2, opacity) as staged
+// by blend_range.  A trip runs the steps of its entries side by side, in this order: where they are called decides the loop's schedule.
+DEV float splat_sigma(const float4 K, const float2 H, float dx, float dy) { return fma_(dx, fma_(K.w, dy, K.z * dx), (H.x * dy) * dy); }
+template <bool FAST_EXP>
+DEV float splat_exp(float sigma, float sE5) { return FAST_EXP ? __expf(fmaxf(-sigma, -86.0f)) : c_expf_neg(fmaxf(-sigma, -86.0f), sE5); }
+DEV float splat_alpha(const float2 H, float E) { return fminf(kMaxAlpha, H.y * E); }
 
 // a constant pinned in a VGPR (the compiler would re-materialise it with a v_mov inside the loop:
 // an SGPR cannot sit beside the literal of v_fmaak on gfx9's one-read constant bus)
@@ -594,21 +625,100 @@ extern "C" int sas_debug_counters(unsigned long long *out, int reset)
 // pixel accepts) and, per wave, one compacted queue for each of its four 4x4 blocks.
 constexpr int kStage = 257;
 struct BlendLds {
-    float4 *q0, *q1, *q2;       // [257] each
+    float4 *q0, *q1, *q2;       // [257] each (q2: one plane of 257 per float4 of the payload)
     unsigned *mask;             // [256] 16 block bits per staged entry
     unsigned short *queue;      // [4 waves][4 blocks][256] byte offsets (16 * entry) into q0/q1/q2
 };
 constexpr int kBlendLdsBytes = 3 * kStage * 16 + 256 * 4 + 16 * 256 * 2;   // 21552
-DEV BlendLds blend_lds(unsigned char *raw)
+DEV BlendLds blend_lds(unsigned char *raw, int q2_planes = 1)
 {
     BlendLds L;
     L.q0 = reinterpret_cast<float4 *>(raw);
     L.q1 = L.q0 + kStage;
     L.q2 = L.q1 + kStage;
-    L.mask = reinterpret_cast<unsigned *>(L.q2 + kStage);
+    L.mask = reinterpret_cast<unsigned *>(L.q2 + q2_planes * kStage);
     L.queue = reinterpret_cast<unsigned short *>(L.mask + 256);
     return L;
 }
+
+// What an entry carries beside its geometry, and where a trip's weights go (blend_range's PAY): Rec is what fetch() requests a
+// batch ahead, V what a trip reads of it.  The frame's own payload: colour and depth, into p.r / g / b / d.
+struct RgbdPayload {
+    typedef float4 Rec;
+    typedef float4 V;
+    DEV Rec none() const { return make_float4(0, 0, 0, 0); }
+    DEV Rec fetch(const SasFrame &f, long long id) const { return f.col[SAS_CS * id]; }
+    DEV void stage(const BlendLds &L, int slot, const Rec &c, float depth) const { L.q2[slot] = make_float4(c.x, c.y, c.z, depth); }
+    DEV void stage_sentinel(const BlendLds &L, float z0) const { L.q2[256] = make_float4(z0, z0, z0, z0); }
+    DEV V load(const char *q2b, unsigned off) const { return *reinterpret_cast<const float4 *>(q2b + off); }
+    DEV float depth(const V &c) const { return c.w; }
+    // lanes that do not composite add with weight +0: fmaf(c, 0, x) == x for the finite colours and depths of the path
+    DEV void add(PixState &p, const V &c0, float vis0, const V &c1, float vis1)
+    {
+        p.r = fma_(c1.x, vis1, fma_(c0.x, vis0, p.r));
+        p.g = fma_(c1.y, vis1, fma_(c0.y, vis0, p.g));
+        p.b = fma_(c1.z, vis1, fma_(c0.z, vis0, p.b));
+        p.d = fma_(c1.w, vis1, fma_(c0.w, vis0, p.d));
+    }
+};
+// ... and one chunk of SAS_FEAT_K feature channels (k_blend_features): from the chunk's plane of the store, staged in kFeatQ
+// planes of q2, accumulated in registers.  Every channel takes the chain of p.r: entry 0 inside entry 1.
+constexpr int kFeatQ = SAS_FEAT_K / 4;   // float4 per entry of a chunk
+struct FeaturePayload {
+    struct Rec { float4 v[kFeatQ]; };
+    typedef Rec V;
+    const float4 *store;   // the chunk's plane: [n_pad][kFeatQ]
+    long long n_pad;
+    float acc[SAS_FEAT_K];
+    DEV Rec none() const
+    {
+        Rec r;
+#pragma unroll
+        for (int k = 0; k < kFeatQ; ++k) r.v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return r;
+    }
+    DEV Rec fetch(const SasFrame &, long long id) const
+    {
+        Rec r = none();
+        if (SAS_IN(id, n_pad, 319) && id < n_pad) {
+#pragma unroll
+            for (int k = 0; k < kFeatQ; ++k) r.v[k] = store[id * kFeatQ + k];
+        }
+        return r;
+    }
+    DEV void stage(const BlendLds &L, int slot, const Rec &c, float) const
+    {
+        if (!SAS_IN(slot, kStage, 320)) return;
+#pragma unroll
+        for (int k = 0; k < kFeatQ; ++k) L.q2[k * kStage + slot] = c.v[k];
+    }
+    DEV void stage_sentinel(const BlendLds &L, float z0) const
+    {
+        Rec r;
+#pragma unroll
+        for (int k = 0; k < kFeatQ; ++k) r.v[k] = make_float4(z0, z0, z0, z0);
+        stage(L, 256, r, z0);
+    }
+    DEV V load(const char *q2b, unsigned off) const
+    {
+        if (!SAS_IN(off >> 4, kStage, 321)) off = 256u << 4;
+        V r;
+#pragma unroll
+        for (int k = 0; k < kFeatQ; ++k) r.v[k] = *reinterpret_cast<const float4 *>(q2b + k * kStage * 16 + off);
+        return r;
+    }
+    DEV float depth(const V &) const { return 0.0f; }
+    DEV void add(PixState &, const V &c0, float vis0, const V &c1, float vis1)
+    {
+#pragma unroll
+        for (int k = 0; k < kFeatQ; ++k) {
+            acc[4 * k + 0] = fma_(c1.v[k].x, vis1, fma_(c0.v[k].x, vis0, acc[4 * k + 0]));
+            acc[4 * k + 1] = fma_(c1.v[k].y, vis1, fma_(c0.v[k].y, vis0, acc[4 * k + 1]));
+            acc[4 * k + 2] = fma_(c1.v[k].z, vis1, fma_(c0.v[k].z, vis0, acc[4 * k + 2]));
+            acc[4 * k + 3] = fma_(c1.v[k].w, vis1, fma_(c0.v[k].w, vis0, acc[4 * k + 3]));
+        }
+    }
+};
 
 // Composite entries [0, count) of a depth-ordered list onto this thread's pixel.  Wave w owns the
 // 8x8 quadrant w of the tile, its 16-lane group g the quadrant's 4x4 block g (pixel_of).  Per batch
@@ -616,20 +726,18 @@ DEV BlendLds blend_lds(unsigned char *raw)
 // ballots, per block, the entries that name it into that block's queue, and the four groups walk
 // their own queues in lockstep, front to back (a group that runs out reads the sentinel record,
 // which no pixel accepts).  Returns true when every pixel of the tile has terminated (uniform over
-// the workgroup).  `slot_at(i)` gives the storage slot of entry i.
-// KEEP IN STEP: k_blend_features (end of this file) restates this loop's per-pixel chain entry by entry -- which entries a
-// lane takes (block mask, a block whose pixels have all terminated at the start of a batch), alpha, the 1/255 skip, the stop
-// rule and the fma_ order of p.r -- so that feature channels get exactly these weights (tests/test_gpu_f_features.py).
+// the workgroup).  `slot_at(i)` gives the storage slot of entry i; `pay` is what the entries carry (RgbdPayload, FeaturePayload).
 // MESH (k_blend_mesh): `zlim` is the depth of the pixel's nearest triangle (+Inf: none).  The first entry whose depth is
-// >= zlim ends the pixel as the transmittance stop does: it is not added, nor is anything after it.  k_blend_features
-// has no such rule: feature frames of a context with meshes are refused (sas_render_features).
-template <bool FAST_EXP, bool MESH = false, typename SlotAt>
+// >= zlim ends the pixel as the transmittance stop does: it is not added, nor is anything after it.  (Only RgbdPayload stages
+// the depths this reads: sas_render_features refuses a context with meshes.)
+template <bool FAST_EXP, bool MESH = false, typename SlotAt, typename PAY>
 DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const PixConst pc, int count, SlotAt slot_at,
                      const BlendLds &L, PixState &p, bool &wdone, unsigned long long &ph_lap_, unsigned &sync_phase,
-                     float zlim = 0.0f)
+                     PAY &pay, float zlim = 0.0f)
 {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    float4 ra = make_float4(0, 0, 0, 0), rb = ra, rc = ra;
+    float4 ra = make_float4(0, 0, 0, 0), rb = ra;
+    typename PAY::Rec rc = pay.none();
     bool have = false;
 #ifdef SAS_TUNE_STATS
     unsigned dbg_rx = 0u, dbg_ry = 0u;
@@ -644,7 +752,7 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
             if (!SAS_IN(id, n_gauss, 201) || id >= n_gauss) id = n_gauss - 1;   // never dereference a bad index
             ra = f.rec[SAS_RS * id + 0];
             rb = f.rec[SAS_RS * id + 1];
-            rc = f.col[SAS_CS * id];
+            rc = pay.fetch(f, id);
 #ifdef SAS_TUNE_STATS
             dbg_rx = f.info[id].z;
             dbg_ry = f.info[id].w;
@@ -657,7 +765,7 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
         const float z0 = vgpr_const(0u);
         L.q0[256] = make_float4(z0, z0, z0, z0);
         L.q1[256] = make_float4(z0, z0, z0, z0);
-        L.q2[256] = make_float4(z0, z0, z0, z0);
+        pay.stage_sentinel(L, z0);
     }
     const float X0 = (float)(tx * SAS_TILE) + kTileCentre, Y0 = (float)(ty * SAS_TILE) + kTileCentre;   // the polynomial's origin: the tile's centre
     // this lane's block's queue; wx: the block column where the wave's quadrant starts (computed here, ahead of the staging:
@@ -707,9 +815,8 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
             DBG_ADD(15, c);
         }
 #endif
-        // Contract T6 (round 5): sigma on (dx, dy) = (u - x, v - y) in the frame of the tile's centre, u = mx - X0, v = my - Y0:
-        //   sigma = fma(dx, fma(B, dy, hA dx), (hC dy) dy),   hA = A/2, hC = C/2
-        // -- seven operations per pixel-splat pair.  (Rounds 1-4 expanded it into a polynomial in (x, y): five, but its terms
+        // Contract T6 (round 5): sigma on (dx, dy) = (u - x, v - y) in the frame of the tile's centre, u = mx - X0, v = my - Y0,
+        // with A/2 and C/2 staged (splat_sigma) -- seven operations per pixel-splat pair.  (Rounds 1-4 expanded it into a polynomial in (x, y): five, but its terms
         // cancel; the (dx, dy) form costs the tile kernel 3 % and sits at the float32 noise floor of gsplat's written form.)
         {
             const float u = ra.x - X0, v = ra.y - Y0;
@@ -717,7 +824,7 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
             // (what a trip reads is packed: q0 whole, q1's first half -- a 16-byte and an 8-byte LDS read per entry, six registers)
             L.q0[tid] = make_float4(u, v, 0.5f * A, B);
             L.q1[tid] = make_float4(0.5f * C, rb.y, 0.0f, 0.0f);   // .y opacity
-            L.q2[tid] = make_float4(rc.x, rc.y, rc.z, rb.w);     // colour, depth
+            pay.stage(L, tid, rc, rb.w);   // colour, depth
             L.mask[tid] = ment;
         }
         if (!wdone) {   // all four queues of the wave start as sentinels (2 KiB: 32 bytes per lane)
@@ -775,7 +882,7 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
             // Two queue entries per trip: their record loads, sigmas and exponentials are independent
             // (one wave alone cannot hide the two dependent LDS round trips of an entry); only the
             // transmittance chain is sequential.  A queue of odd length ends on the sentinel.
-            struct Trip { float4 K0, K1, C0, C1; float2 H0, H1; };
+            struct Trip { float4 K0, K1; typename PAY::V C0, C1; float2 H0, H1; };
             auto load_trip = [&](Trip &t, int k, unsigned pair) {   // pair = queue entries k, k + 1
                 unsigned off0 = pair & 0xffffu, off1 = pair >> 16;
 #ifdef SAS_TUNE_STATS
@@ -791,25 +898,23 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
                 t.H1 = *reinterpret_cast<const float2 *>(q1b + off1);
                 // colour, depth: read with the geometry (read once the alphas are known, they cost the tile kernel 2 %:
                 // docs/EXPERIMENTS.md R5.2)
-                t.C0 = *reinterpret_cast<const float4 *>(q2b + off0);
-                t.C1 = *reinterpret_cast<const float4 *>(q2b + off1);
+                t.C0 = pay.load(q2b, off0);
+                t.C1 = pay.load(q2b, off1);
             };
             // returns true when every pixel of the wave has terminated
             auto composite_trip = [&](const Trip &t) -> bool {
                 const float dx0 = t.K0.x - p.x, dy0 = t.K0.y - pc.y, dx1 = t.K1.x - p.x, dy1 = t.K1.y - pc.y;
-                const float sg0 = fma_(dx0, fma_(t.K0.w, dy0, t.K0.z * dx0), (t.H0.x * dy0) * dy0);
-                const float sg1 = fma_(dx1, fma_(t.K1.w, dy1, t.K1.z * dx1), (t.H1.x * dy1) * dy1);
+                const float sg0 = splat_sigma(t.K0, t.H0, dx0, dy0);
+                const float sg1 = splat_sigma(t.K1, t.H1, dx1, dy1);
                 // Every decision below is a per-lane select on a value, not a wave mask combined on the
                 // scalar unit (which the CU's four SIMDs share: a scalar instruction costs as much issue time
                 // as a vector one).  A lane the splat does not reach has a large sigma: the contract's clamp
                 // of the exponent argument makes its alpha underflow and fail the 1/255 test by itself; a
                 // parked pixel (x = NaN -> sigma = NaN) is clamped the same way (max returns the number).
                 DBG_ADD(0, 2);
-                float E0, E1;
-                if (FAST_EXP) { E0 = __expf(fmaxf(-sg0, -86.0f)); E1 = __expf(fmaxf(-sg1, -86.0f)); }
-                else { E0 = c_expf_neg(fmaxf(-sg0, -86.0f), sE5); E1 = c_expf_neg(fmaxf(-sg1, -86.0f), sE5); }
-                const float al0 = fminf(kMaxAlpha, t.H0.y * E0);
-                const float al1 = fminf(kMaxAlpha, t.H1.y * E1);
+                const float E0 = splat_exp<FAST_EXP>(sg0, sE5), E1 = splat_exp<FAST_EXP>(sg1, sE5);
+                const float al0 = splat_alpha(t.H0, E0);
+                const float al1 = splat_alpha(t.H1, E1);
                 // weight w = alpha T (0 when the splat is skipped), next T = T - w, for both entries as if no
                 // pixel terminated; T only falls, so one test of the last T tells whether any did
                 const float w0 = (al0 < kAlphaThr) ? 0.0f : al0 * p.T;
@@ -820,7 +925,7 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
                 bool all_dead = false;
                 if constexpr (MESH) {
                     // an entry at or behind the pixel's triangle (depth >= zlim) stops the pixel as the transmittance test does
-                    const bool cut0 = t.C0.w >= zlim, cut1 = t.C1.w >= zlim;
+                    const bool cut0 = pay.depth(t.C0) >= zlim, cut1 = pay.depth(t.C1) >= zlim;
                     if (__ballot(nT1 <= kTStop || cut0 || cut1)) {
                         const bool stop0 = nT0 <= kTStop || cut0, stopped = nT1 <= kTStop || cut0 || cut1;
                         vis0 = stop0 ? 0.0f : w0;
@@ -840,12 +945,7 @@ DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const
                     all_dead = __all(pix_dead(p));
                 }
                 p.T = Tn;
-                // lanes that do not composite add with weight +0: fmaf(c, 0, x) == x for the finite
-                // colours and depths of the path
-                p.r = fma_(t.C1.x, vis1, fma_(t.C0.x, vis0, p.r));
-                p.g = fma_(t.C1.y, vis1, fma_(t.C0.y, vis0, p.g));
-                p.b = fma_(t.C1.z, vis1, fma_(t.C0.z, vis0, p.b));
-                p.d = fma_(t.C1.w, vis1, fma_(t.C0.w, vis0, p.d));
+                pay.add(p, t.C0, vis0, t.C1, vis1);
 #ifdef SAS_TUNE_STATS
                 {
                     const unsigned long long m0 = __ballot(vis0 > 0.0f), m1 = __ballot(vis1 > 0.0f);
@@ -1002,9 +1102,7 @@ DEV bool blend_range_quad(const SasFrame &f, long long n_gauss, int tx, int ty, 
                     k += 4;
                     off = wq[k + e];   // next trip's entry, one trip ahead
                     const float dxq = K.x - p.x, dyq = K.y - pc.y;
-                    const float sg = fma_(dxq, fma_(K.w, dyq, K.z * dxq), (H.x * dyq) * dyq);
-                    const float E = FAST_EXP ? __expf(fmaxf(-sg, -86.0f)) : c_expf_neg(fmaxf(-sg, -86.0f), sE5);
-                    const float al = fminf(kMaxAlpha, H.y * E);
+                    const float al = splat_alpha(H, splat_exp<FAST_EXP>(splat_sigma(K, H, dxq, dyq), sE5));
                     // A skipped splat weighs 0: decided HERE, once per lane for its own entry, so that the chain below is one
                     // multiply (its operand the quad broadcast of entry j's alpha: v_mul_f32_dpp) and one subtraction per
                     // entry instead of broadcast + compare + multiply + select (0 * T == +0 for the finite T of the path:
@@ -1147,106 +1245,86 @@ DEV void store_tile_max(const SasFrame &f, int tile, float ED, unsigned *s_wmax)
 }
 
 // ---- full path, stage 2: composite the complete sorted lists -----------------------------------
-template <bool FAST_EXP, bool WANT_MAX>
-__global__ __launch_bounds__(256) void k_blend(SasParams P, SasFrame f, long long n_gauss,
-                                               const int *tl, const int *range)
+
+// The pixel's triangle in a frame with meshes: every thread resolves its own pixel over its tile's triangle list -- the minimum of
+// (depth bits, record) among the records whose interior holds the pixel centre, whatever the list's order (no z-buffer, no
+// atomics).  Returns that depth (+Inf: none) and puts the triangle's colour in the background's place.
+DEV float mesh_resolve(const SasMeshFrame &M, const SasCam &c, int tile, int ix, int iy, float *bg)
+{
+    // the pixel's triangle (records 2 t, 2 t + 1 belong to triangle t: the record index orders triangles as their index does)
+    // the pixel centre in the records' frame (the image centre; exact: halves of integers)
+    const float px = ((float)ix + 0.5f) - 0.5f * c.Wf, py = ((float)iy + 0.5f) - 0.5f * c.Hf;
+    unsigned long long best = ~0ull;
+    const long long mb = M.tile_offset[tile];
+    long long me = M.tile_offset[tile + 1];
+    if (me > M.cap) me = M.cap;
+    for (long long i = mb; i < me; ++i) {
+        const int r = M.list[i];
+        if (!SAS_IN(r, M.n_rec, 311)) continue;
+        const float4 r0 = M.rec[4 * r], r1 = M.rec[4 * r + 1], r2 = M.rec[4 * r + 2];
+        const float e0 = r0.x * px + r0.y * py + r0.z, e1 = r0.w * px + r1.x * py + r1.y, e2 = r1.z * px + r1.w * py + r2.x;
+        // top-left rule: an edge through the centre holds it when (a > 0) or (a == 0 and b > 0)
+        const bool in0 = e0 > 0.0f || (e0 == 0.0f && (r0.x > 0.0f || (r0.x == 0.0f && r0.y > 0.0f)));
+        const bool in1 = e1 > 0.0f || (e1 == 0.0f && (r0.w > 0.0f || (r0.w == 0.0f && r1.x > 0.0f)));
+        const bool in2 = e2 > 0.0f || (e2 == 0.0f && (r1.z > 0.0f || (r1.z == 0.0f && r1.w > 0.0f)));
+        const float iz = r2.y * px + r2.z * py + r2.w;
+        if (in0 && in1 && in2 && iz > 0.0f) {
+            const unsigned long long key = ((unsigned long long)__float_as_uint(1.0f / iz) << 32) | (unsigned)r;
+            best = key < best ? key : best;
+        }
+    }
+    if (best == ~0ull) return __builtin_inff();
+    const float4 m3 = M.rec[4 * (long long)(unsigned)(best & 0xffffffffu) + 3];
+    bg[0] = m3.x; bg[1] = m3.y; bg[2] = m3.z;
+    return __uint_as_float((unsigned)(best >> 32));
+}
+
+// MESH: a frame with meshes (its lists, records and tiles as any other's; SAS_FULL_SORT frames with meshes deliver no rgb8 to the
+// host from the tile kernel).  The splats are composited in front of the pixel's triangle (blend_range<.., MESH>), whose colour
+// takes the background's place in write_pixel.
+template <bool FAST_EXP, bool WANT_MAX, bool MESH>
+DEV void blend_tile(const SasParams &P, const SasFrame &f, long long n_gauss, int tile, unsigned &sync_phase, const SasMeshFrame *M)
 {
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[kBlendLdsBytes];
     __shared__ unsigned s_wmax[4];
     const SasCam &c = P.cam;
-    const SasOutputs &o = P.out;
     const BlendLds L = blend_lds(s_raw);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    unsigned sync_phase = 0u;
-    for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x) {
-        const int tile = tl[oi];
-        const int tx = tile % c.tw, ty = tile / c.tw;
-        int ox, oy;
-        pixel_of(wv, lane, ox, oy);
-        const int ix = tx * SAS_TILE + ox, iy = ty * SAS_TILE + oy;
-        const bool inside = ix < c.W && iy < c.H;
-        PixState p = pix_init(inside, ox);
-        bool wdone = __all(!inside);
-        const long long beg = f.tile_offset[tile];
-        long long end = f.tile_offset[tile + 1];
-        if (end > f.cap) end = f.cap;
-        const int *ids = f.sorted_ids + beg;
-        unsigned long long ph_lap_ = 0ull;
-        blend_range<FAST_EXP>(f, n_gauss, tx, ty, pix_const(ox, oy), (int)(end - beg),
-                              [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase);
-        unsigned packed;
-        const float ED = write_pixel(o, p, inside, ix, iy, c.W, packed);
-        if (o.rgb8_host) store_rows_to_host<16>(o.rgb8_host, c.W, tx * SAS_TILE, ty * SAS_TILE, ox, oy, true, packed, s_raw);
-        if (WANT_MAX) store_tile_max(f, tile, ED, s_wmax);
-        if (tid == 0) { f.tile_count[tile] = 0; f.tile_big[tile] = 0; }   // the frame's counters leave the frame zeroed (SasFrame invariant)
-    }
+    const int tx = tile % c.tw, ty = tile / c.tw;
+    int ox, oy, ix, iy;
+    bool inside, wdone;
+    pixel_of(wv, lane, ox, oy);
+    PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
+    SasOutputs o = P.out;
+    float zlim = 0.0f;
+    if constexpr (MESH) zlim = mesh_resolve(*M, c, tile, ix, iy, o.bg);
+    long long beg, end;
+    tile_segment(f, tile, beg, end);
+    const int *ids = f.sorted_ids + beg;
+    unsigned long long ph_lap_ = 0ull;
+    RgbdPayload pay;
+    blend_range<FAST_EXP, MESH>(f, n_gauss, tx, ty, pix_const(ox, oy), (int)(end - beg),
+                                [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay, zlim);
+    unsigned packed;
+    const float ED = write_pixel(o, p, inside, ix, iy, c.W, packed);
+    if (!MESH && o.rgb8_host) store_rows_to_host<16>(o.rgb8_host, c.W, tx * SAS_TILE, ty * SAS_TILE, ox, oy, true, packed, s_raw);
+    if (WANT_MAX) store_tile_max(f, tile, ED, s_wmax);
+    if (tid == 0) { f.tile_count[tile] = 0; f.tile_big[tile] = 0; }   // the frame's counters leave the frame zeroed (SasFrame invariant)
 }
-
-// k_blend for a frame with meshes (its lists, records and tiles as k_blend's; SAS_FULL_SORT frames deliver no rgb8 to the
-// host from the tile kernel).  In the tile prologue every thread resolves its own pixel over its tile's triangle list: the
-// minimum of (depth bits, record) among the records whose interior holds the pixel centre, whatever the list's order (no
-// z-buffer, no atomics).  The splats are then composited in front of that depth (blend_range<.., MESH>), and the triangle's
-// colour takes the background's place in write_pixel.
+template <bool FAST_EXP, bool WANT_MAX>
+__global__ __launch_bounds__(256) void k_blend(SasParams P, SasFrame f, long long n_gauss, const int *tl, const int *range)
+{
+    unsigned sync_phase = 0u;
+    for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x)
+        blend_tile<FAST_EXP, WANT_MAX, false>(P, f, n_gauss, tl[oi], sync_phase, nullptr);
+}
 template <bool FAST_EXP, bool WANT_MAX>
 __global__ __launch_bounds__(256) void k_blend_mesh(SasParams P, SasFrame f, long long n_gauss, const int *tl, const int *range,
                                                     SasMeshFrame M)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kBlendLdsBytes];
-    __shared__ unsigned s_wmax[4];
-    const SasCam &c = P.cam;
-    const BlendLds L = blend_lds(s_raw);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     unsigned sync_phase = 0u;
-    for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x) {
-        const int tile = tl[oi];
-        const int tx = tile % c.tw, ty = tile / c.tw;
-        int ox, oy;
-        pixel_of(wv, lane, ox, oy);
-        const int ix = tx * SAS_TILE + ox, iy = ty * SAS_TILE + oy;
-        const bool inside = ix < c.W && iy < c.H;
-        // the pixel's triangle (records 2 t, 2 t + 1 belong to triangle t: the record index orders triangles as their index does)
-        // the pixel centre in the records' frame (the image centre; exact: halves of integers)
-        const float px = ((float)ix + 0.5f) - 0.5f * c.Wf, py = ((float)iy + 0.5f) - 0.5f * c.Hf;
-        unsigned long long best = ~0ull;
-        const long long mb = M.tile_offset[tile];
-        long long me = M.tile_offset[tile + 1];
-        if (me > M.cap) me = M.cap;
-        for (long long i = mb; i < me; ++i) {
-            const int r = M.list[i];
-            if (!SAS_IN(r, M.n_rec, 311)) continue;
-            const float4 r0 = M.rec[4 * r], r1 = M.rec[4 * r + 1], r2 = M.rec[4 * r + 2];
-            const float e0 = r0.x * px + r0.y * py + r0.z, e1 = r0.w * px + r1.x * py + r1.y, e2 = r1.z * px + r1.w * py + r2.x;
-            // top-left rule: an edge through the centre holds it when (a > 0) or (a == 0 and b > 0)
-            const bool in0 = e0 > 0.0f || (e0 == 0.0f && (r0.x > 0.0f || (r0.x == 0.0f && r0.y > 0.0f)));
-            const bool in1 = e1 > 0.0f || (e1 == 0.0f && (r0.w > 0.0f || (r0.w == 0.0f && r1.x > 0.0f)));
-            const bool in2 = e2 > 0.0f || (e2 == 0.0f && (r1.z > 0.0f || (r1.z == 0.0f && r1.w > 0.0f)));
-            const float iz = r2.y * px + r2.z * py + r2.w;
-            if (in0 && in1 && in2 && iz > 0.0f) {
-                const unsigned long long key = ((unsigned long long)__float_as_uint(1.0f / iz) << 32) | (unsigned)r;
-                best = key < best ? key : best;
-            }
-        }
-        float zlim = __builtin_inff();
-        SasOutputs o = P.out;
-        if (best != ~0ull) {
-            zlim = __uint_as_float((unsigned)(best >> 32));
-            const float4 m3 = M.rec[4 * (long long)(unsigned)(best & 0xffffffffu) + 3];
-            o.bg[0] = m3.x; o.bg[1] = m3.y; o.bg[2] = m3.z;
-        }
-        PixState p = pix_init(inside, ox);
-        bool wdone = __all(!inside);
-        const long long beg = f.tile_offset[tile];
-        long long end = f.tile_offset[tile + 1];
-        if (end > f.cap) end = f.cap;
-        const int *ids = f.sorted_ids + beg;
-        unsigned long long ph_lap_ = 0ull;
-        blend_range<FAST_EXP, true>(f, n_gauss, tx, ty, pix_const(ox, oy), (int)(end - beg),
-                                    [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, zlim);
-        unsigned packed;
-        const float ED = write_pixel(o, p, inside, ix, iy, c.W, packed);
-        if (WANT_MAX) store_tile_max(f, tile, ED, s_wmax);
-        if (tid == 0) { f.tile_count[tile] = 0; f.tile_big[tile] = 0; }   // (SasFrame invariant)
-    }
+    for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x)
+        blend_tile<FAST_EXP, WANT_MAX, true>(P, f, n_gauss, tl[oi], sync_phase, &M);
 }
 
 // ================================================================================================
@@ -1359,13 +1437,12 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
     int ox, oy;
     if (QUAD) pixel_of_quad(qd, wv, lane, ox, oy);
     else pixel_of(wv, lane, ox, oy);
-    int ix = tx * SAS_TILE + ox, iy = ty * SAS_TILE + oy;
+    int ix, iy;
+    bool inside, wdone;
     PixConst pc = pix_const(ox, oy);
-    bool inside = ix < c.W && iy < c.H;
     const bool writer = !QUAD || (lane & 3) == 0;   // QUAD: the four lanes of a pixel hold the same state, one stores it
     const int out_side = QUAD ? 8 : 16;       // what this workgroup hands out: its quadrant or the whole tile
-    PixState p = pix_init(inside, ox);
-    bool wdone = __all(!inside);
+    PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
 #ifdef SAS_TUNE_WGTIME
     unsigned long long ph_lap_ = t_wg0;
     if (threadIdx.x == 0 && blockIdx.x < kDbgWgMax)
@@ -1379,7 +1456,7 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
         const unsigned long long t_b = PH_T();
         bool r;
         if constexpr (QUAD) r = blend_range_quad<FAST_EXP>(f, n_gauss, tx, ty, qd, pc, count, slot_at, L, p, wdone, sync_phase);
-        else r = blend_range<FAST_EXP>(f, n_gauss, tx, ty, pc, count, slot_at, L, p, wdone, ph_lap_, sync_phase);
+        else { RgbdPayload pay; r = blend_range<FAST_EXP>(f, n_gauss, tx, ty, pc, count, slot_at, L, p, wdone, ph_lap_, sync_phase, pay); }
         PH_ADD(1, PH_T() - t_b);
         return r;
     };
@@ -1389,9 +1466,7 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
         beg = (long long)tile * f.seg;
         end = beg + min(f.tile_count[tile], f.seg);   // (tile_big stays zero in this mode)
     } else {
-        beg = f.tile_offset[tile];
-        end = f.tile_offset[tile + 1];
-        if (end > f.cap) end = f.cap;
+        tile_segment(f, tile, beg, end);
     }
     const int n = (int)(end - beg);
     const unsigned long long *g = f.keys + beg;
@@ -1806,24 +1881,14 @@ void sas_launch_sort(hipStream_t st, const SasScene &s, int ntiles, const SasFra
     }
 }
 
-template <bool FAST, bool WMAX>
-static void launch_blend_list(hipStream_t st, unsigned grid, const SasParams &P, const SasFrame &f, long long n,
-                              const int *tl, const int *range)
+// fn(std::bool_constant<flags>...): the kernels' compile-time switches from the frame's run-time flags
+template <typename Fn>
+static void with_flags(Fn fn) { fn(); }
+template <typename Fn, typename... Rest>
+static void with_flags(Fn fn, bool flag, Rest... rest)
 {
-
-    hipLaunchKernelGGL((k_blend<FAST, WMAX>), dim3(grid), dim3(256), 0, st, P, f, n, tl, range);
-}
-
-static void blend_list(hipStream_t st, unsigned grid, const SasParams &P, const SasFrame &f, long long n, const int *tl,
-                       const int *range, bool fast_exp, bool want_max)
-{
-    if (fast_exp) {
-        if (want_max) launch_blend_list<true, true>(st, grid, P, f, n, tl, range);
-        else launch_blend_list<true, false>(st, grid, P, f, n, tl, range);
-    } else {
-        if (want_max) launch_blend_list<false, true>(st, grid, P, f, n, tl, range);
-        else launch_blend_list<false, false>(st, grid, P, f, n, tl, range);
-    }
+    if (flag) with_flags([&](auto... cs) { fn(std::true_type{}, cs...); }, rest...);
+    else with_flags([&](auto... cs) { fn(std::false_type{}, cs...); }, rest...);
 }
 
 // Full path, stage 2: composite all tiles from their complete lists (longest first).
@@ -1831,37 +1896,24 @@ void sas_launch_blend(hipStream_t st, const SasScene &s, int tiles, const SasPar
                       bool fast_exp, bool want_max)
 {
     const long long n = s.n > 0 ? s.n : 1;
-    blend_list(st, (unsigned)tiles, P, f, n, f.tile_order, f.sort_class + 4, fast_exp, want_max);
+    with_flags([&](auto fast, auto wmax) {
+        hipLaunchKernelGGL((k_blend<fast(), wmax()>), dim3((unsigned)tiles), dim3(256), 0, st, P, f, n, f.tile_order, f.sort_class + 4);
+    }, fast_exp, want_max);
 }
 
 void sas_launch_blend_mesh(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
                            const SasMeshFrame &mf, bool fast_exp, bool want_max)
 {
     const long long n = s.n > 0 ? s.n : 1;
-    const dim3 grid((unsigned)tiles), blk(256);
-    const int *tl = f.tile_order, *range = f.sort_class + 4;
-    if (fast_exp) {
-        if (want_max) hipLaunchKernelGGL((k_blend_mesh<true, true>), grid, blk, 0, st, P, f, n, tl, range, mf);
-        else hipLaunchKernelGGL((k_blend_mesh<true, false>), grid, blk, 0, st, P, f, n, tl, range, mf);
-    } else {
-        if (want_max) hipLaunchKernelGGL((k_blend_mesh<false, true>), grid, blk, 0, st, P, f, n, tl, range, mf);
-        else hipLaunchKernelGGL((k_blend_mesh<false, false>), grid, blk, 0, st, P, f, n, tl, range, mf);
-    }
+    with_flags([&](auto fast, auto wmax) {
+        hipLaunchKernelGGL((k_blend_mesh<fast(), wmax()>), dim3((unsigned)tiles), dim3(256), 0, st, P, f, n, f.tile_order, f.sort_class + 4, mf);
+    }, fast_exp, want_max);
 }
 
 // Production path: lazy ordering + compositing of every tile in one launch.
 // quad: frames of a few hundred tiles, binned in 8-pixel tiles by their projection (`tiles` counts those): one
 // workgroup per 8x8 quadrant (pixel_of_quad); exact exponential only (SAS_FAST_EXP frames take the ordinary layout).
-
-template <bool FAST, bool WMAX, bool QUAD>
-static void launch_lazy(hipStream_t st, unsigned grid, const SasParams &P, const SasFrame &f, long long n, const int *perm,
-                        hipEvent_t e0, hipEvent_t e1)
-{
-    if (e0 && e1)
-        hipExtLaunchKernelGGL((k_tile_lazy<FAST, WMAX, QUAD>), dim3(grid), dim3(kLazyThreads), 0, st, e0, e1, 0, P, f, n, perm);
-    else
-        hipLaunchKernelGGL((k_tile_lazy<FAST, WMAX, QUAD>), dim3(grid), dim3(kLazyThreads), 0, st, P, f, n, perm);
-}
+static constexpr bool sas_lazy_layout_built(bool fast_exp, bool quad) { return !(fast_exp && quad); }
 
 bool sas_tiles_lazy_quad_ok(bool fast_exp) { return !fast_exp; }
 
@@ -1870,25 +1922,13 @@ void sas_launch_tiles_lazy(hipStream_t st, const SasScene &s, int tiles, const S
 {
     const unsigned grid = ((unsigned)tiles + 3u) & ~3u;   // whole groups of four tiles (tile_lazy_body)
     const long long n = s.n > 0 ? s.n : 1;
-    if (fast_exp) {
-        if (want_max) launch_lazy<true, true, false>(st, grid, P, f, n, s.perm, ev_start, ev_stop);
-        else launch_lazy<true, false, false>(st, grid, P, f, n, s.perm, ev_start, ev_stop);
-    } else if (quad) {
-        if (want_max) launch_lazy<false, true, true>(st, grid, P, f, n, s.perm, ev_start, ev_stop);
-        else launch_lazy<false, false, true>(st, grid, P, f, n, s.perm, ev_start, ev_stop);
-    } else {
-        if (want_max) launch_lazy<false, true, false>(st, grid, P, f, n, s.perm, ev_start, ev_stop);
-        else launch_lazy<false, false, false>(st, grid, P, f, n, s.perm, ev_start, ev_stop);
-    }
-}
-
-template <bool FAST, bool WMAX, bool QUAD>
-static void launch_lazy_multi(hipStream_t st, dim3 grid, const SasMulti &mf, long long n, const int *perm, hipEvent_t e0, hipEvent_t e1)
-{
-    if (e0 && e1)
-        hipExtLaunchKernelGGL((k_tile_lazy_multi<FAST, WMAX, QUAD>), grid, dim3(kLazyThreads), 0, st, e0, e1, 0, mf, n, perm);
-    else
-        hipLaunchKernelGGL((k_tile_lazy_multi<FAST, WMAX, QUAD>), grid, dim3(kLazyThreads), 0, st, mf, n, perm);
+    with_flags([&](auto fast, auto wmax, auto qd) {
+        if constexpr (sas_lazy_layout_built(fast(), qd())) {
+            const auto k = k_tile_lazy<fast(), wmax(), qd()>;
+            if (ev_start && ev_stop) hipExtLaunchKernelGGL(k, dim3(grid), dim3(kLazyThreads), 0, st, ev_start, ev_stop, 0, P, f, n, s.perm);
+            else hipLaunchKernelGGL(k, dim3(grid), dim3(kLazyThreads), 0, st, P, f, n, s.perm);
+        }
+    }, fast_exp, want_max, quad && !fast_exp);
 }
 
 void sas_launch_tiles_lazy_multi(hipStream_t st, const SasScene &s, int tiles, const SasMulti &mf, bool fast_exp, bool want_max,
@@ -1896,16 +1936,13 @@ void sas_launch_tiles_lazy_multi(hipStream_t st, const SasScene &s, int tiles, c
 {
     const dim3 grid((((unsigned)tiles + 3u) & ~3u) * (unsigned)mf.nv);   // views interleaved (k_tile_lazy_multi); whole groups of four tiles per view
     const long long n = s.n > 0 ? s.n : 1;
-    if (fast_exp) {
-        if (want_max) launch_lazy_multi<true, true, false>(st, grid, mf, n, s.perm, ev_start, ev_stop);
-        else launch_lazy_multi<true, false, false>(st, grid, mf, n, s.perm, ev_start, ev_stop);
-    } else if (quad) {
-        if (want_max) launch_lazy_multi<false, true, true>(st, grid, mf, n, s.perm, ev_start, ev_stop);
-        else launch_lazy_multi<false, false, true>(st, grid, mf, n, s.perm, ev_start, ev_stop);
-    } else {
-        if (want_max) launch_lazy_multi<false, true, false>(st, grid, mf, n, s.perm, ev_start, ev_stop);
-        else launch_lazy_multi<false, false, false>(st, grid, mf, n, s.perm, ev_start, ev_stop);
-    }
+    with_flags([&](auto fast, auto wmax, auto qd) {
+        if constexpr (sas_lazy_layout_built(fast(), qd())) {
+            const auto k = k_tile_lazy_multi<fast(), wmax(), qd()>;
+            if (ev_start && ev_stop) hipExtLaunchKernelGGL(k, grid, dim3(kLazyThreads), 0, st, ev_start, ev_stop, 0, mf, n, s.perm);
+            else hipLaunchKernelGGL(k, grid, dim3(kLazyThreads), 0, st, mf, n, s.perm);
+        }
+    }, fast_exp, want_max, quad && !fast_exp);
 }
 
 void sas_launch_depth_tail(hipStream_t st, int tiles, const SasParams &P, const SasFrame &f, bool fill, bool points)
@@ -1920,8 +1957,6 @@ void sas_launch_depth_tail(hipStream_t st, int tiles, const SasParams &P, const 
 // Feature channels ("Feature channels"): C per-Gaussian channels through the frame's own weights
 // ================================================================================================
 namespace {
-
-constexpr int kFeatQ = SAS_FEAT_K / 4;   // float4 per entry of a chunk
 
 // store[(q n_pad + j) K + k] = channel q K + k of the Gaussian in slot j (the caller's Gaussian perm[j]), through finite_colour;
 // one-hot mode (src == nullptr): (gid8[j] == q K + k).  Channels >= C and slots >= n are zero.  One thread per (chunk, slot).
@@ -1958,110 +1993,43 @@ __global__ __launch_bounds__(256) void k_feature_store(long long n, long long n_
 }
 
 // One workgroup per (tile, chunk of SAS_FEAT_K channels), one lane per pixel (pixel_of), on the complete depth-ordered list the
-// full path's k_blend has just composited.  A lane takes the entries blend_range takes -- those whose block mask names its 4x4
-// block, none after its whole block had terminated at the start of a batch -- with blend_range's alpha, 1/255 skip, stop rule
-// and fma_ chain of p.r (composite_trip), entry by entry: a trip's pair of entries is the same chain.  A terminated pixel (x =
-// NaN) takes nothing more in either kernel: its alpha is opacity x exp(-86) < 1/255, or 0.999, which stops it again, for every
-// opacity up to 8.7e34 and for +-Inf and NaN.  The K channels are accumulated in registers; every chunk recomputes alpha and T.
+// full path's k_blend has just composited: the same blend_range, with the chunk's channels in the colours' place.  Every chunk
+// recomputes alpha and T.
 template <bool FAST_EXP>
-__global__ __launch_bounds__(256) void k_blend_features(SasParams P, SasFrame f, long long n_gauss, SasFeatures F)
+// Six waves per SIMD as before (80 VGPRs, 25 KiB of LDS): hipcc settles for five (92 VGPRs) unless told.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_blend_features(SasParams P, SasFrame f, long long n_gauss,
+                                                                                               SasFeatures F)
 {
-    __shared__ float4 s_g[256];               // (u, v, A/2, B): blend_range's q0
-    __shared__ float2 s_h[256];               // (C/2, opacity): its q1's first half
-    __shared__ float4 s_f[kFeatQ][256];       // the chunk's features
-    __shared__ unsigned s_m[256];             // block masks (block_mask16)
-    __shared__ unsigned char s_q[4][256];     // per wave: the batch's entries that name one of its four blocks
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kBlendLdsBytes + (kFeatQ - 1) * kStage * 16];
     const SasCam &c = P.cam;
+    const BlendLds L = blend_lds(s_raw, kFeatQ);   // the chunk's features in the colours' place
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int oi = (int)blockIdx.x, q = (int)blockIdx.y;
     if (!SAS_IN(oi, f.n_tiles, 310)) return;
     const int tile = f.tile_order[oi];
     if (!SAS_IN(tile, f.n_tiles, 311)) return;   // (uniform)
     const int tx = tile % c.tw, ty = tile / c.tw;
-    int ox, oy;
+    int ox, oy, ix, iy;
+    bool inside, wdone;
     pixel_of(wv, lane, ox, oy);
-    const int ix = tx * SAS_TILE + ox, iy = ty * SAS_TILE + oy;
-    const bool inside = ix < c.W && iy < c.H;
-    PixState p = pix_init(inside, ox);
-    const PixConst pc = pix_const(ox, oy);
-    float acc[SAS_FEAT_K];
-#pragma unroll
-    for (int k = 0; k < SAS_FEAT_K; ++k) acc[k] = 0.0f;
-    const long long beg = f.tile_offset[tile];
-    long long end = f.tile_offset[tile + 1];
-    if (end > f.cap) end = f.cap;
-    const int count = end > beg ? (int)(end - beg) : 0;
-    const float X0 = (float)(tx * SAS_TILE) + kTileCentre, Y0 = (float)(ty * SAS_TILE) + kTileCentre;
-    const float sE5 = vgpr_const(0x3aafa464u);
-    const int grp = lane >> 4;
-    const int my_bit = ((wv & 1) * 2 + (grp & 1)) + 4 * ((wv >> 1) * 2 + (grp >> 1));
-    const unsigned wbits = 0x33u << (2 * (wv & 1) + 8 * (wv >> 1));   // the wave's four blocks
-    bool wdone = __all(pix_dead(p));
-    for (int at = 0; at < count; at += 256) {
-        // (also the barrier behind the previous batch's reads)
-        if (__syncthreads_and(wdone ? 1 : 0)) break;
-        const int e = at + tid;
-        unsigned m = 0u;
-        if (e < count) {
-            const long long pos = beg + e;
-            long long id = SAS_IN(pos, f.cap, 312) ? (long long)(unsigned)f.sorted_ids[pos] : n_gauss - 1;
-            if (!SAS_IN(id, n_gauss, 313) || id >= n_gauss) id = n_gauss - 1;   // never dereference a bad index
-            const float4 ra = f.rec[SAS_RS * id + 0], rb = f.rec[SAS_RS * id + 1];
-            m = block_mask16(tx, ty, ra.x, ra.y, ra.z, ra.w, rb.x, rb.z);
-            s_g[tid] = make_float4(ra.x - X0, ra.y - Y0, 0.5f * ra.z, ra.w);
-            s_h[tid] = make_float2(0.5f * rb.x, rb.y);
-            const long long fo = ((long long)q * F.n_pad + id) * kFeatQ;
-            const bool fin = SAS_IN(id, F.n_pad, 314) && id < F.n_pad;
-#pragma unroll
-            for (int r = 0; r < kFeatQ; ++r)
-                s_f[r][tid] = fin ? reinterpret_cast<const float4 *>(F.store)[fo + r] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        s_m[tid] = m;
-        __syncthreads();
-        if (wdone) continue;
-        // blend_range's queue rules: a block whose 16 pixels have all terminated takes nothing more in this batch
-        const unsigned long long dm = __ballot(pix_dead(p));
-        const bool blk_live = ((dm >> (16 * grp)) & 0xffffull) != 0xffffull;
-        int qn = 0;
-        const int cnt = (count - at) < 256 ? (count - at) : 256;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ej = 64 * j + lane;
-            const bool has = ej < cnt && (s_m[ej] & wbits) != 0u;
-            const unsigned long long bm = __ballot(has);
-            if (has && SAS_IN(qn + (int)mbcnt64(bm), 256, 315)) s_q[wv][qn + (int)mbcnt64(bm)] = (unsigned char)ej;
-            qn += (int)__popcll(bm);
-        }
-        const int kend = __builtin_amdgcn_readfirstlane(qn);
-        for (int k = 0; k < kend; ++k) {
-            const int ent = s_q[wv][k];
-            const unsigned me = s_m[ent];
-            const float4 g = s_g[ent];
-            const float2 h = s_h[ent];
-            const float dx = g.x - p.x, dy = g.y - pc.y;
-            const float sg = fma_(dx, fma_(g.w, dy, g.z * dx), (h.x * dy) * dy);
-            const float E = FAST_EXP ? __expf(fmaxf(-sg, -86.0f)) : c_expf_neg(fmaxf(-sg, -86.0f), sE5);
-            const float al = fminf(kMaxAlpha, h.y * E);
-            const bool take = blk_live && ((me >> my_bit) & 1u);
-            const float w = (!take || al < kAlphaThr) ? 0.0f : al * p.T;
-            const float nT = p.T - w;
-            const bool stop = nT <= kTStop;
-            const float vis = stop ? 0.0f : w;
-            p.T = stop ? p.T : nT;
-            if (stop) p.x = __builtin_nanf("");
-#pragma unroll
-            for (int r = 0; r < kFeatQ; ++r) {
-                const float4 fv = s_f[r][ent];
-                acc[4 * r + 0] = fma_(fv.x, vis, acc[4 * r + 0]);
-                acc[4 * r + 1] = fma_(fv.y, vis, acc[4 * r + 1]);
-                acc[4 * r + 2] = fma_(fv.z, vis, acc[4 * r + 2]);
-                acc[4 * r + 3] = fma_(fv.w, vis, acc[4 * r + 3]);
-            }
-            if ((k & 7) == 7 && __all(pix_dead(p))) break;
-        }
-        wdone = __all(pix_dead(p));
-    }
+    PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
+    long long beg, end;
+    tile_segment(f, tile, beg, end);
+    const int *ids = f.sorted_ids + beg;
+    FeaturePayload pay{reinterpret_cast<const float4 *>(F.store) + (long long)q * F.n_pad * kFeatQ, F.n_pad, {}};
+    unsigned long long ph_lap_ = 0ull;
+    unsigned sync_phase = 0u;
+    blend_range<FAST_EXP>(f, n_gauss, tx, ty, pix_const(ox, oy), end > beg ? (int)(end - beg) : 0,
+                          [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay);
     // write_pixel's epilogue on the chunk's channels: a = 1 - T, w = 1 - a, v = acc + w bg (no clamp)
+    {   // (the pixel's coordinates again, from a thread index opaque to hipcc: kept alive across blend_range they cost the register
+        // that decides the kernel's sixth wave per SIMD)
+        int t2 = tid;
+        asm volatile("" : "+v"(t2));
+        pixel_of(t2 >> 6, t2 & 63, ox, oy);
+        bool w2;
+        pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, w2);
+    }
     if (!inside) return;
     const long long pix = (long long)iy * c.W + ix;
     if (!SAS_IN(pix, P.out.n_pixels, 316)) return;
@@ -2073,7 +2041,7 @@ __global__ __launch_bounds__(256) void k_blend_features(SasParams P, SasFrame f,
         const int ch = c0 + k;
         if (ch < F.C && SAS_IN(ch, SAS_MAX_FEATURES, 317)) {
             const long long o = pix * F.C + ch;
-            if (SAS_IN(o, P.out.n_pixels * F.C, 318)) F.out[o] = acc[k] + wb * F.bg[ch];
+            if (SAS_IN(o, P.out.n_pixels * F.C, 318)) F.out[o] = pay.acc[k] + wb * F.bg[ch];
         }
     }
 }
@@ -2096,6 +2064,5 @@ void sas_launch_blend_features(hipStream_t st, const SasScene &s, int tiles, con
     if (tiles <= 0 || F.chunks <= 0) return;
     const long long n = s.n > 0 ? s.n : 1;
     const dim3 grid((unsigned)tiles, (unsigned)F.chunks);
-    if (fast_exp) hipLaunchKernelGGL(k_blend_features<true>, grid, dim3(256), 0, st, P, f, n, F);
-    else hipLaunchKernelGGL(k_blend_features<false>, grid, dim3(256), 0, st, P, f, n, F);
+    with_flags([&](auto fast) { hipLaunchKernelGGL(k_blend_features<fast()>, grid, dim3(256), 0, st, P, f, n, F); }, fast_exp);
 }

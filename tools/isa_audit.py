@@ -79,6 +79,11 @@ def audit(lines):
             mm = re.search(r"This (?:Inner )?Loop Header: Depth=(\d+)", s)
             if mm:
                 loops[cur] = int(mm.group(1))
+            # ... and of a labelled block inside a loop (the label's own line carries the block's name only)
+            mm = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)", s) if s.startswith(";") else None
+            if mm:
+                cur = mm.group(1)
+                loops.setdefault(cur, int(mm.group(2)))
             continue
         op = s.split()[0]
         k = classify(op)
