@@ -26,7 +26,6 @@ namespace {
 constexpr int kSortThreads = 256;   // workgroup size of the lazy tile kernel (lds_bucket_rank_sort)
 
 DEV unsigned hi32(unsigned long long k) { return (unsigned)(k >> 32); }
-DEV unsigned *s_queue_u32(unsigned char *raw) { return reinterpret_cast<unsigned *>(raw); }   // scratch words in a free LDS region
 DEV unsigned lo32(unsigned long long k) { return (unsigned)k; }
 
 // order of the reference: depth bits, then the CALLER's Gaussian index.  Keys carry the storage
@@ -1339,6 +1338,20 @@ constexpr int kRankMax = 32;      // largest depth bucket a chunk is ordered by 
 constexpr int kPartitionMin = 8 * kChunk;
 constexpr int kLazyThreads = 256;
 
+// The 256 depth buckets of a tile's list: equal slices of the list's own range [dmin, dmin + span] of depth words.
+DEV unsigned depth_bucket(unsigned bits, unsigned dmin, int shift) { return (bits - dmin) >> shift; }
+struct DepthBuckets {
+    unsigned dmin, span;
+    int shift;
+    DEV DepthBuckets(unsigned mn, unsigned mx) : dmin(mn), span(mx - mn)
+    {
+        const int sbits = span ? 32 - __clz(span) : 0;
+        shift = sbits > 8 ? sbits - 8 : 0;
+    }
+    DEV unsigned bucket_of_depth(unsigned bits) const { return depth_bucket(bits, dmin, shift); }
+    DEV unsigned bucket(unsigned long long key) const { return bucket_of_depth(hi32(key)); }
+};
+
 // Lay the keys of buckets >= b_first out by bucket: slot ids into `ids` at the positions handed out by the
 // per-bucket cursors `cur` (LDS, preset to each bucket's start).  A real call, not inlined: it runs once for
 // the rare tile that needs many rounds, and inlining it costs the common path registers (+1 % at configs 2, 3).
@@ -1348,7 +1361,7 @@ __device__ __attribute__((noinline)) void partition_by_bucket(const unsigned lon
     const int tid = threadIdx.x;
     for (int i = tid; i < n; i += kLazyThreads) {
         const unsigned long long key = g[i];
-        const int b = (int)((hi32(key) - dmin) >> shift);
+        const int b = (int)depth_bucket(hi32(key), dmin, shift);
         if (b >= b_first && SAS_IN(b, 256, 214)) {
             const unsigned pos = atomicAdd(&cur[b], 1u);
             if (SAS_IN(pos, n, 215)) ids[pos] = (int)lo32(key);
@@ -1358,6 +1371,343 @@ __device__ __attribute__((noinline)) void partition_by_bucket(const unsigned lon
     __syncthreads();
 }
 
+// ---- tile_lazy_body's phases: what they share, then the phases in call order.  All inlined; hipcc's code for these kernels is
+// sensitive to their exact form: run tools/isa_gate.py after any edit (docs/EXPERIMENTS.md R5.4) ----
+
+// Lists of up to kKeyCache keys -- most of the long ones -- are read from memory ONCE: the min / max pass parks them in the
+// part of the staging region that the ordering scratch leaves free (15 KiB), the histogram and the first round's collect
+// pass read them from there (two dependent global round trips per tile less).  The first compositing overwrites the copy:
+// later rounds (the exception: the first chunk did not saturate the tile) read the segment again.
+constexpr int kKeyCache = (kBlendLdsBytes - 6 * 1024) / 8;   // behind cnt / dbase / cur (6 KiB)
+// The LDS of the ordering phases (declared in tile_lazy_body).  cnt, dbase, cur and kc lie in the blend staging region, which
+// is free while a chunk is ordered.
+struct LazyLds {
+    unsigned long long *ck;        // [CH] the chunk: (depth word relative to the chunk's base << 32 | storage slot)
+    unsigned *cnt, *dbase;         // [4][256], [256] lds_radix_sort's scratch; cnt[0 .. 7] also select_bucket_range's
+    unsigned *cur;                 // [256] per-bucket write cursor of the chunk being collected
+    unsigned long long *kc;        // [kKeyCache]
+    unsigned *hist, *wsum;         // [256] keys per bucket, [4]
+    unsigned *mn, *mx, *m, *rem;   // the list's depth range; entries in the chunk; keys not yet consumed
+    int *b1;
+};
+// One sweep over a list's n keys that keeps U independent loads per thread in flight: load(i) of U keys (`pad` past the
+// end), then use(i, value) of each.
+template <int U, typename T, typename Load, typename Use>
+DEV void for_each_key(int n, T pad, const Load &load, const Use &use)
+{
+    const int tid = threadIdx.x;
+    for (int i0 = 0; i0 < n; i0 += kLazyThreads * U) {
+        T v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * kLazyThreads + tid;
+            v[u] = (i < n) ? load(i) : pad;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * kLazyThreads + tid;
+            if (i < n) use(i, v[u]);
+        }
+    }
+}
+// The inclusive sum of v over threads 0 .. tid of the workgroup (thread t owns bucket t); a barrier inside.
+DEV unsigned wg_inclusive_sum(unsigned v, unsigned *wsum)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned incl = wave_inclusive_sum_u32(v);
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    for (int w = 0; w < wv; ++w) incl += wsum[w];
+    return incl;
+}
+DEV unsigned long long chunk_key(unsigned rel, unsigned slot) { return ((unsigned long long)rel << 32) | slot; }
+// A key into the next place of its bucket b in the chunk, its depth word relative to the chunk's base: leaves cur[b] at the
+// END of every bucket.
+DEV void place_key(const LazyLds &S, int cap, unsigned b, unsigned rel, unsigned slot, int code)
+{
+    const unsigned pos = atomicAdd(&S.cur[b], 1u);
+    if (SAS_IN(pos, cap, code)) S.ck[pos] = chunk_key(rel, slot);
+}
+// ... if it belongs to buckets b0 .. b1 (base: the first depth word of bucket b0)
+DEV void place_in_range(unsigned long long key, const DepthBuckets &B, int b0, int b1, unsigned base, const LazyLds &S, int cap)
+{
+    const int b = (int)B.bucket(key);
+    if (b >= b0 && b <= b1 && SAS_IN(b, 256, 206))
+        place_key(S, cap, (unsigned)b, hi32(key) - base, lo32(key), 207);
+}
+
+// The background into the (up to four) tiles g4 .. g4 + 3 of an empty group.
+template <bool WANT_MAX>
+DEV void paint_empty_group(const SasParams &P, const SasFrame &f, int g4, unsigned char *s_raw, unsigned *s_wmax)
+{
+    const SasCam &c = P.cam;
+    const SasOutputs &o = P.out;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int ox, oy;
+    pixel_of(wv, lane, ox, oy);
+    const bool pack4 = o.rgb8 && (c.W & 3) == 0 && ((size_t)o.rgb8 & 3) == 0;
+#pragma unroll 1
+    for (int q = 0; q < 4; ++q) {
+        const int t = g4 + q;
+        if (t >= f.n_tiles) break;
+        const int tx = t % c.tw, ty = t / c.tw;
+        const int ix = tx * SAS_TILE + ox, iy = ty * SAS_TILE + oy;
+        const bool inside = ix < c.W && iy < c.H;
+        const PixState p0 = pix_init(inside, ox);
+        unsigned packed;
+        const float ED = write_pixel<true>(o, p0, inside, ix, iy, c.W, packed, pack4);
+        if (o.rgb8_host) store_rows_to_host<16>(o.rgb8_host, c.W, tx * SAS_TILE, ty * SAS_TILE, ox, oy, true, packed, s_raw);
+        if (WANT_MAX) store_tile_max(f, t, ED, s_wmax);
+    }
+}
+// The tile's keys: the offset of its segment of the frame's key / id arrays; returns their number.
+DEV int lazy_tile_segment(const SasFrame &f, int tile, long long &beg)
+{
+    long long end;
+    if (f.seg > 0) {   // (uniform) single-pass binning: the tile's own segment, as many keys as were counted (at most the segment)
+        beg = (long long)tile * f.seg;
+        end = beg + min(f.tile_count[tile], f.seg);   // (tile_big stays zero in this mode)
+    } else {
+        tile_segment(f, tile, beg, end);
+    }
+    return (int)(end - beg);
+}
+// Short list (n <= CH): one pass, keys loaded once into registers, the whole list is the chunk.
+template <int CH>
+DEV void order_short_list(const unsigned long long *g, int n, const int *perm, const LazyLds &S, unsigned &sync_phase)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    constexpr int NK = CH / kLazyThreads;
+    if (tid == 0) { *S.mn = ~0u; *S.mx = 0u; }
+    S.hist[tid] = 0u;
+    __syncthreads();
+    unsigned long long kk[NK];
+    unsigned mn = ~0u, mx = 0u;
+    // (the list's base, opaque per phase: hipcc otherwise forms this thread's key address once per tile and parks the 64-bit
+    // value in scratch between the phases that read keys)
+    const unsigned long long *g1 = g;
+    asm volatile("" : "+s"(g1));
+#pragma unroll
+    for (int u = 0; u < NK; ++u) {
+        const int i = u * kLazyThreads + tid;
+        kk[u] = (i < n) ? g1[i] : ~0ull;
+        if (i < n) { mn = min(mn, hi32(kk[u])); mx = max(mx, hi32(kk[u])); }
+    }
+    mn = wave_min_u32(mn); mx = wave_max_u32(mx);   // (DPP steps: sas_device.h)
+    if (lane == 0) { atomicMin(S.mn, mn); atomicMax(S.mx, mx); }
+    __syncthreads();
+    const DepthBuckets B(*S.mn, *S.mx);
+    // Ordered as a chunk of a long list is: 256 depth buckets over the list's range, keys placed grouped by
+    // bucket, every key ranked inside its own bucket (a handful of compares) -- a third of the instructions
+    // of three radix passes (docs/EXPERIMENTS.md s5.20).  A crowded bucket (coplanar splats) falls back to the radix passes.
+#pragma unroll
+    for (int u = 0; u < NK; ++u)
+        if (u * kLazyThreads + tid < n && SAS_IN(B.bucket(kk[u]), 256, 219)) atomicAdd(&S.hist[B.bucket(kk[u])], 1u);
+    __syncthreads();
+    {
+        const unsigned hv = S.hist[tid];
+        const unsigned incl = wg_inclusive_sum(hv, S.wsum);
+        S.cur[tid] = incl - hv;   // start of bucket tid
+        const bool big = wg_reduce_wave_flags<false>(__any(hv > (unsigned)kRankMax), sync_phase);
+#pragma unroll
+        for (int u = 0; u < NK; ++u) {
+            if (u * kLazyThreads + tid < n) {
+                if (SAS_IN(B.bucket(kk[u]), 256, 220)) place_key(S, CH, B.bucket(kk[u]), hi32(kk[u]) - B.dmin, lo32(kk[u]), 221);
+            }
+        }
+        __syncthreads();
+        const unsigned long long t_s = PH_T();
+        if (!big) lds_bucket_rank_sort<NK>(S.ck, n, 0, B.shift, S.hist, S.cur, perm);
+        else lds_radix_sort<4, NK>(S.ck, n, B.span, perm, S.cnt, S.dbase, S.wsum);
+        PH_ADD(0, PH_T() - t_s);
+    }
+}
+// Long list (n > CH), before its rounds: the min / max pass and the histogram pass leave the list's buckets and S.hist.  Every
+// pass over the keys keeps U independent loads per thread in flight.
+template <bool QUAD>
+DEV DepthBuckets bucket_long_list(const unsigned long long *g, int n, const LazyLds &S, bool cached, unsigned long long &ph_lap_)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    constexpr int U = 8;
+    const unsigned long long t_p = PH_T();
+    if (tid == 0) { *S.mn = ~0u; *S.mx = 0u; }
+    S.hist[tid] = 0u;
+    __syncthreads();
+    unsigned mn = ~0u, mx = 0u;
+    if (cached) {
+        const unsigned long long *g2 = g;
+        asm volatile("" : "+s"(g2));
+        for_each_key<U>(n, 0ull, [&](int i) { return g2[i]; }, [&](int i, unsigned long long key) {
+            mn = min(mn, hi32(key)); mx = max(mx, hi32(key));
+            if (SAS_IN(i, kKeyCache, 222)) S.kc[i] = key;
+        });
+    } else {
+        for_each_key<U>(n, 0u, [&](int i) { return hi32(g[i]); }, [&](int, unsigned d) { mn = min(mn, d); mx = max(mx, d); });
+    }
+    mn = wave_min_u32(mn); mx = wave_max_u32(mx);   // (DPP steps: sas_device.h)
+    if (lane == 0) { atomicMin(S.mn, mn); atomicMax(S.mx, mx); }
+    __syncthreads();
+    PH_LAP(1);
+    const DepthBuckets B(*S.mn, *S.mx);
+    if (cached) {
+        for (int i = tid; i < n; i += kLazyThreads) {
+            const unsigned dd = hi32(S.kc[i]);
+            if (SAS_IN(B.bucket_of_depth(dd), 256, 208)) atomicAdd(&S.hist[B.bucket_of_depth(dd)], 1u);
+        }
+    } else {
+        for_each_key<U>(n, 0u, [&](int i) { return hi32(g[i]); }, [&](int, unsigned d) { if (SAS_IN(B.bucket_of_depth(d), 256, 208)) atomicAdd(&S.hist[B.bucket_of_depth(d)], 1u); });
+    }
+    __syncthreads();
+    PH_LAP(2);
+    if (!QUAD) PH_ADD(2, PH_T() - t_p);   // (ordinary layout: [2] = the passes over the keys, [3] = of which the rounds' collect passes)
+    return B;
+}
+// The next round's bucket range [b0, b1]: b0 = first non-empty bucket >= b_next, b1 = last bucket whose running count from b0
+// stays <= CH (256: nothing left; < 0: bucket b0 alone exceeds the chunk).  Thread t owns bucket t: hv = its count, incl = the
+// inclusive count of buckets b_next .. t.  *S.rem: keys not yet consumed (buckets >= b_next).
+struct BucketRange {
+    int b0, b1;
+    unsigned hv, incl;
+};
+template <int CH>
+DEV BucketRange select_bucket_range(const LazyLds &S, int b_next)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const unsigned hv = (tid >= b_next) ? S.hist[tid] : 0u;
+    const unsigned incl = wg_inclusive_sum(hv, S.wsum);
+    if (tid == kLazyThreads - 1) *S.rem = incl;
+    const unsigned long long nz = __ballot(hv != 0u);
+    const unsigned long long fit = __ballot(hv != 0u && incl <= (unsigned)CH);
+    if (lane == 0) {
+        S.cnt[wv] = nz ? (unsigned)(wv * 64 + __ffsll((long long)nz) - 1) : 256u;          // first non-empty
+        S.cnt[4 + wv] = fit ? (unsigned)(wv * 64 + 63 - __clzll((long long)fit)) : 0xffffffffu;   // last fitting
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned first = 256u;
+        int last = -1;
+        for (int w = 3; w >= 0; --w) {
+            if (S.cnt[w] != 256u) first = S.cnt[w];
+        }
+        for (int w = 0; w < 4; ++w)
+            if (S.cnt[4 + w] != 0xffffffffu) last = (int)S.cnt[4 + w];
+        *S.m = first;
+        *S.b1 = (first >= 256u) ? 256 : last;   // last < first (i.e. -1): first bucket alone exceeds the chunk
+    }
+    __syncthreads();
+    const int b0 = (int)*S.m, b1 = *S.b1;
+    __syncthreads();
+    return BucketRange{b0, b1, hv, incl};
+}
+// A SECOND round starts (the first chunk did not saturate the tile, which is the exception): lay the remaining keys out by
+// bucket, once, so that every later round reads only its own chunk instead of scanning the whole list again (n^2 / 512 key
+// reads on a long translucent list; only worth it when many rounds are still to come: kPartitionMin).  Bucket t of the
+// remainder starts at the exclusive count of buckets b_next .. t - 1: the selection's scan.
+DEV void lay_out_remainder(const unsigned long long *g, int n, const DepthBuckets &B, int b_next, const BucketRange &R, const LazyLds &S, int *ids)
+{
+    S.cur[threadIdx.x] = R.incl - R.hv;
+    __syncthreads();
+    partition_by_bucket(g, n, B.dmin, B.shift, b_next, S.cur, ids);
+}
+// A chunk's collect pass starts: *S.m = its entries, the cursors of its buckets (bucket t starts at the exclusive count of the
+// buckets before it); true: one of its buckets is too crowded to be ordered by counting.
+DEV bool begin_chunk(const BucketRange &R, bool partitioned, const LazyLds &S, unsigned &sync_phase)
+{
+    const int tid = threadIdx.x, b0 = R.b0, b1 = R.b1;
+    const unsigned my_hv = R.hv, my_incl = R.incl;
+    unsigned *const s_cur = S.cur;
+    unsigned &s_m = *S.m;
+    const bool mine = tid >= b0 && tid <= b1;
+    if (tid == b1) s_m = my_incl;
+    if (!partitioned) {
+        if (mine) s_cur[tid] = my_incl - my_hv;
+    } else if (mine) {
+        s_cur[tid] = my_incl;   // END of bucket t inside the chunk (what the collect pass leaves): b0 is the first non-empty bucket of the scan
+    }
+    return wg_reduce_wave_flags<false>(__any(mine && my_hv > (unsigned)kRankMax), sync_phase);
+}
+// The chunk is one contiguous run of the bucket-ordered slots (partition_by_bucket); depth words come from the projection's
+// records.  Buckets are consumed whole and in order, so the chunk starts where the previous ones ended (st).
+template <int CH>
+DEV void collect_partitioned_run(const SasFrame &f, long long n_gauss, const int *ids, int st, int n, int cnt_chunk, unsigned base, unsigned dmin, unsigned long long *ck)
+{
+    const int tid = threadIdx.x;
+    for (int i = tid; i < cnt_chunk; i += kLazyThreads) {
+        if (!SAS_IN(st + i, n, 216) || !SAS_IN(i, CH, 217)) continue;
+        const unsigned slot = (unsigned)ids[st + i];
+        const unsigned dbits = SAS_IN(slot, n_gauss, 218) ? __float_as_uint(f.rec[SAS_RS * (long long)slot + 1].w) : dmin;
+        ck[i] = chunk_key(dbits - base, slot);
+    }
+}
+// Collect the range's keys into the chunk grouped by bucket, depth words relative to the range's base, from the LDS key cache
+// (first round of a cached list), the global keys or the partitioned id run; returns begin_chunk's flag.
+template <bool QUAD>
+DEV bool collect_chunk(const SasFrame &f, long long n_gauss, const unsigned long long *g, int n, const int *ids, int p_consumed, const DepthBuckets &B,
+                       const BucketRange &R, const LazyLds &S, bool partitioned, bool cached, int b_next, unsigned &sync_phase)
+{
+    constexpr int CH = QUAD ? kChunkQuad : kChunk, U = 8;
+    const int tid = threadIdx.x;
+    const int b0 = R.b0, b1 = R.b1;
+    const unsigned base = B.dmin + ((unsigned)b0 << B.shift);
+    const bool big = begin_chunk(R, partitioned, S, sync_phase);
+    const unsigned long long t_c = PH_T();
+    if (!partitioned && cached && b_next == 0) {
+        for (int i = tid; i < n; i += kLazyThreads) place_in_range(S.kc[i], B, b0, b1, base, S, CH);
+    } else if (!partitioned) {
+        const unsigned long long *g3 = g;   // (opaque: see order_short_list)
+        asm volatile("" : "+s"(g3));
+        for_each_key<U>(n, ~0ull, [&](int i) { return g3[i]; }, [&](int, unsigned long long key) { place_in_range(key, B, b0, b1, base, S, CH); });
+    } else {
+        collect_partitioned_run<CH>(f, n_gauss, ids, p_consumed, n, (int)*S.m, base, B.dmin, S.ck);
+    }
+    __syncthreads();
+    if (!QUAD) { PH_ADD(2, PH_T() - t_c); PH_ADD(3, PH_T() - t_c); }
+    return big;
+}
+// Order the chunk's m keys, collected grouped by bucket.  (Plain pointers: with the LDS struct the quad-layout kernels' code differs.)
+template <int CH>
+DEV void order_chunk(unsigned long long *ck, int m, int b0, int b1, int shift, unsigned span, bool big, const int *perm, const unsigned *s_hist, const unsigned *s_cur,
+                     unsigned *cnt, unsigned *dbase, unsigned *s_wsum)
+{
+    const unsigned long long t_s = PH_T();
+    if (!big) {
+        lds_bucket_rank_sort<CH / kLazyThreads>(ck, m, b0, shift, s_hist, s_cur, perm);
+    } else {   // a crowded bucket (coplanar splats): radix passes cost the same whatever the distribution
+        const unsigned long long hi_excl = ((unsigned long long)(b1 - b0 + 1) << shift);
+        const unsigned rel_span = (unsigned)min((unsigned long long)(span - ((unsigned)b0 << shift)), hi_excl - 1ull);
+        lds_radix_sort<4, CH / kLazyThreads>(ck, m, rel_span, perm, cnt, dbase, s_wsum);
+    }
+    PH_ADD(0, PH_T() - t_s);
+}
+// More than CH entries in one depth bucket (e.g. thousands of coplanar splats): order the whole segment in place (slow, rare)
+// and composite it from scratch.
+template <typename Blend>
+DEV void bail_to_full_sort(const SasFrame &f, long long beg, int n, const int *perm, const Blend &blend, PixState &p, bool &wdone, bool inside, int ox)
+{
+    const int tid = threadIdx.x;
+    if (tid == 0) __hip_atomic_fetch_add(&f.stats_host[6], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    int *out = f.sorted_ids + beg;
+    sort_global_bitonic(f.keys + beg, out, n, perm, tid, kLazyThreads);
+    __syncthreads();
+    p = pix_init(inside, ox);
+    wdone = __all(!inside);
+    blend(n, [&](int i) { return (long long)(unsigned)out[i]; });
+}
+// The finished pixel to the frame's outputs: the workgroup hands out its whole tile, or (QUAD) its quadrant.  Returns the
+// pixel's expected depth.
+template <bool QUAD>
+DEV float write_tile(const SasCam &c, const SasOutputs &o, int tx, int ty, int qd, int ox, int oy, int ix, int iy, bool inside, bool writer, const PixState &p, unsigned char *s_raw)
+{
+    unsigned packed;
+    float ED;
+    if constexpr (QUAD) ED = write_pixel(o, p, inside && writer, ix, iy, c.W, packed);
+    else ED = write_pixel<true>(o, p, inside, ix, iy, c.W, packed, o.rgb8 && (c.W & 3) == 0 && ((size_t)o.rgb8 & 3) == 0);
+    if (o.rgb8_host) {   // (uniform: a frame property)
+        if constexpr (QUAD) store_rows_to_host<8>(o.rgb8_host, c.W, tx * SAS_TILE + (qd & 1) * 8, ty * SAS_TILE + (qd >> 1) * 8, ox & 7, oy & 7, writer, packed, s_raw);
+        else store_rows_to_host<16>(o.rgb8_host, c.W, tx * SAS_TILE, ty * SAS_TILE, ox, oy, writer, packed, s_raw);
+    }
+    return ED;
+}
 template <bool FAST_EXP, bool WANT_MAX, bool QUAD>
 DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss, const int *perm, unsigned wg /* workgroup index within the view */)
 {
@@ -1378,16 +1728,17 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
     unsigned *dbase = cnt + 4 * 256;                              // [256]
     unsigned *s_cur = dbase + 256;                                // [256] per-bucket write cursor of the chunk being collected (sort phase)
     __shared__ unsigned s_rem;
+    const LazyLds S = {ck, cnt, dbase, s_cur, reinterpret_cast<unsigned long long *>(s_raw + 6 * 1024), s_hist, s_wsum, &s_mn, &s_mx, &s_m, &s_rem, &s_b1};
 
 #ifdef SAS_TUNE_WGTIME
     const unsigned long long t_wg0 = wall_clock64();
     if (threadIdx.x == 0 && blockIdx.x < kDbgWgMax)
         for (int k = 0; k < 8; ++k) g_dbg_ph[8 * blockIdx.x + k] = 0ull;
 #endif
-    // QUAD: the frame is binned in 8-pixel tiles (c.tile_px == 8): this workgroup's tile is the 8x8 quadrant qd of the
+    // The workgroup's tile.  Single-pass frames: the projection's tail orders GROUPS of four consecutive tiles (by their longest
+    // list); two-pass frames: tiles (the grid is the tile count rounded up to whole groups: the last group may be ragged; all of
+    // this is uniform).  QUAD: the frame is binned in 8-pixel tiles (c.tile_px == 8): the tile is the 8x8 quadrant qd of the
     // contract's 16-pixel tile (tx, ty), whose origin the sigma polynomials refer to (pixel_of_quad); the list is its own
-    // single-pass frames: the projection's tail orders GROUPS of four consecutive tiles (by their longest list); two-pass frames: tiles
-    // (the grid is the tile count rounded up to whole groups: the last group may be ragged; all of this is uniform)
     int tile;
     if (f.seg > 0) {
         // Groups whose four tiles are all empty are the last class of the order; class_cursor[15] says where it starts.  Such a
@@ -1397,26 +1748,7 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
         // workgroup per tile (SasFrame::group_fill): there the kernel's END counts, and four tiles in a row lengthen it.
         if (!QUAD && f.group_fill && (int)(wg >> 2) >= f.class_cursor[15]) {
             if (wg & 3u) return;
-            const int g4 = 4 * f.tile_order[wg >> 2];
-            const SasCam &cc = P.cam;
-            const SasOutputs &oo = P.out;
-            const int tid_ = threadIdx.x, lane_ = tid_ & 63, wv_ = tid_ >> 6;
-            int ox_, oy_;
-            pixel_of(wv_, lane_, ox_, oy_);
-            const bool pack4 = oo.rgb8 && (cc.W & 3) == 0 && ((size_t)oo.rgb8 & 3) == 0;
-#pragma unroll 1
-            for (int q = 0; q < 4; ++q) {
-                const int t = g4 + q;
-                if (t >= f.n_tiles) break;
-                const int tx_ = t % cc.tw, ty_ = t / cc.tw;
-                const int ix_ = tx_ * SAS_TILE + ox_, iy_ = ty_ * SAS_TILE + oy_;
-                const bool in_ = ix_ < cc.W && iy_ < cc.H;
-                const PixState p0 = pix_init(in_, ox_);
-                unsigned packed_;
-                const float ED_ = write_pixel<true>(oo, p0, in_, ix_, iy_, cc.W, packed_, pack4);
-                if (oo.rgb8_host) store_rows_to_host<16>(oo.rgb8_host, cc.W, tx_ * SAS_TILE, ty_ * SAS_TILE, ox_, oy_, true, packed_, s_raw);
-                if (WANT_MAX) store_tile_max(f, t, ED_, s_wmax);
-            }
+            paint_empty_group<WANT_MAX>(P, f, 4 * f.tile_order[wg >> 2], s_raw, s_wmax);
             return;
         }
         tile = 4 * f.tile_order[wg >> 2] + (int)(wg & 3u);
@@ -1441,7 +1773,6 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
     bool inside, wdone;
     PixConst pc = pix_const(ox, oy);
     const bool writer = !QUAD || (lane & 3) == 0;   // QUAD: the four lanes of a pixel hold the same state, one stores it
-    const int out_side = QUAD ? 8 : 16;       // what this workgroup hands out: its quadrant or the whole tile
     PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
 #ifdef SAS_TUNE_WGTIME
     unsigned long long ph_lap_ = t_wg0;
@@ -1461,14 +1792,8 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
         return r;
     };
 
-    long long beg, end;
-    if (f.seg > 0) {   // (uniform) single-pass binning: the tile's own segment, as many keys as were counted (at most the segment)
-        beg = (long long)tile * f.seg;
-        end = beg + min(f.tile_count[tile], f.seg);   // (tile_big stays zero in this mode)
-    } else {
-        tile_segment(f, tile, beg, end);
-    }
-    const int n = (int)(end - beg);
+    long long beg;
+    const int n = lazy_tile_segment(f, tile, beg);
     const unsigned long long *g = f.keys + beg;
     if (n >= 0) PH_LAP(0);   // (n: the dependent loads of the tile's index and its offsets have returned)
     // the tile kernel's waves issue ahead of the co-resident binning waves of the next frames (+1.2 % frames/s at config 3:
@@ -1476,284 +1801,40 @@ DEV void tile_lazy_body(const SasParams &P, const SasFrame &f, long long n_gauss
     __builtin_amdgcn_s_setprio(3);
 
     if (n > 0 && n <= CH) {
-        // ---- short list: one pass, keys loaded once into registers, whole list is the chunk
-        constexpr int NK = CH / kLazyThreads;
-        if (tid == 0) { s_mn = ~0u; s_mx = 0u; }
-        s_hist[tid] = 0u;
-        __syncthreads();
-        unsigned long long kk[NK];
-        unsigned mn = ~0u, mx = 0u;
-        // (the list's base, opaque per phase: hipcc otherwise forms this thread's key address once per tile and parks the 64-bit
-        // value in scratch between the phases that read keys)
-        const unsigned long long *g1 = g;
-        asm volatile("" : "+s"(g1));
-#pragma unroll
-        for (int u = 0; u < NK; ++u) {
-            const int i = u * kLazyThreads + tid;
-            kk[u] = (i < n) ? g1[i] : ~0ull;
-            if (i < n) { mn = min(mn, hi32(kk[u])); mx = max(mx, hi32(kk[u])); }
-        }
-        mn = wave_min_u32(mn); mx = wave_max_u32(mx);   // (DPP steps: sas_device.h)
-        if (lane == 0) { atomicMin(&s_mn, mn); atomicMax(&s_mx, mx); }
-        __syncthreads();
-        const unsigned dmin = s_mn, span = s_mx - s_mn;
-        // Ordered as a chunk of a long list is: 256 depth buckets over the list's range, keys placed grouped by
-        // bucket, every key ranked inside its own bucket (a handful of compares) -- a third of the instructions
-        // of three radix passes (docs/EXPERIMENTS.md s5.20).  A crowded bucket (coplanar splats) falls back to the radix passes.
-        const int sbits = span ? 32 - __clz(span) : 0;
-        const int shift = sbits > 8 ? sbits - 8 : 0;
-#pragma unroll
-        for (int u = 0; u < NK; ++u)
-            if (u * kLazyThreads + tid < n && SAS_IN((hi32(kk[u]) - dmin) >> shift, 256, 219)) atomicAdd(&s_hist[(hi32(kk[u]) - dmin) >> shift], 1u);
-        __syncthreads();
-        {
-            const unsigned hv = s_hist[tid];
-            unsigned incl = wave_inclusive_sum_u32(hv);
-            if (lane == 63) s_wsum[wv] = incl;
-            __syncthreads();
-            for (int w = 0; w < wv; ++w) incl += s_wsum[w];
-            s_cur[tid] = incl - hv;   // start of bucket tid
-            const bool big = wg_reduce_wave_flags<false>(__any(hv > (unsigned)kRankMax), sync_phase);
-#pragma unroll
-            for (int u = 0; u < NK; ++u) {
-                if (u * kLazyThreads + tid < n) {
-                    const unsigned rel = hi32(kk[u]) - dmin;
-                    if (SAS_IN(rel >> shift, 256, 220)) {
-                        const unsigned pos = atomicAdd(&s_cur[rel >> shift], 1u);   // leaves the END of every bucket
-                        if (SAS_IN(pos, CH, 221)) ck[pos] = ((unsigned long long)rel << 32) | lo32(kk[u]);
-                    }
-                }
-            }
-            __syncthreads();
-            const unsigned long long t_s = PH_T();
-            if (!big) lds_bucket_rank_sort<NK>(ck, n, 0, shift, s_hist, s_cur, perm);
-            else lds_radix_sort<4, NK>(ck, n, span, perm, cnt, dbase, s_wsum);
-            PH_ADD(0, PH_T() - t_s);
-        }
+        order_short_list<CH>(g, n, perm, S, sync_phase);
         PH_LAP(13);
         blend(n, [&](int i) { return (long long)lo32(ck[i]); });
     } else if (n > CH) {
-        // ---- long list: every pass over the keys keeps U independent loads per thread in flight
-        constexpr int U = 8;
-        const unsigned long long t_p = PH_T();
-        if (tid == 0) { s_mn = ~0u; s_mx = 0u; }
-        s_hist[tid] = 0u;
-        __syncthreads();
-        // Lists of up to kKeyCache keys -- most of the long ones -- are read from memory ONCE: the min / max pass parks them in the
-        // part of the staging region that the ordering scratch leaves free (15 KiB), the histogram and the first round's collect
-        // pass read them from there (two dependent global round trips per tile less).  The first compositing overwrites the copy:
-        // later rounds (the exception: the first chunk did not saturate the tile) read the segment again.
-        constexpr int kKeyCache = (kBlendLdsBytes - 6 * 1024) / 8;   // behind cnt / dbase / s_cur (6 KiB)
-        unsigned long long *const kc = reinterpret_cast<unsigned long long *>(s_raw + 6 * 1024);
-        const bool cached = n <= kKeyCache;   // (uniform)
-        unsigned mn = ~0u, mx = 0u;
-        if (cached) {
-            const unsigned long long *g2 = g;
-            asm volatile("" : "+s"(g2));
-            for (int i0 = 0; i0 < n; i0 += kLazyThreads * U) {
-                unsigned long long kk[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int i = i0 + u * kLazyThreads + tid;
-                    kk[u] = (i < n) ? g2[i] : 0ull;
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int i = i0 + u * kLazyThreads + tid;
-                    if (i < n) { mn = min(mn, hi32(kk[u])); mx = max(mx, hi32(kk[u])); if (SAS_IN(i, kKeyCache, 222)) kc[i] = kk[u]; }
-                }
-            }
-        } else {
-            for (int i0 = 0; i0 < n; i0 += kLazyThreads * U) {
-                unsigned dd[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int i = i0 + u * kLazyThreads + tid;
-                    dd[u] = (i < n) ? hi32(g[i]) : 0u;
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (i0 + u * kLazyThreads + tid < n) { mn = min(mn, dd[u]); mx = max(mx, dd[u]); }
-            }
-        }
-        mn = wave_min_u32(mn); mx = wave_max_u32(mx);   // (DPP steps: sas_device.h)
-        if (lane == 0) { atomicMin(&s_mn, mn); atomicMax(&s_mx, mx); }
-        __syncthreads();
-        PH_LAP(1);
-        const unsigned dmin = s_mn, span = s_mx - s_mn;
-        const int sbits = span ? 32 - __clz(span) : 0;
-        const int shift = sbits > 8 ? sbits - 8 : 0;   // 256 depth buckets over the tile's range
-        if (cached) {
-            for (int i = tid; i < n; i += kLazyThreads) {
-                const unsigned dd = hi32(kc[i]);
-                if (SAS_IN((dd - dmin) >> shift, 256, 208)) atomicAdd(&s_hist[(dd - dmin) >> shift], 1u);
-            }
-        } else {
-            for (int i0 = 0; i0 < n; i0 += kLazyThreads * U) {
-                unsigned dd[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int i = i0 + u * kLazyThreads + tid;
-                    dd[u] = (i < n) ? hi32(g[i]) : 0u;
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (i0 + u * kLazyThreads + tid < n && SAS_IN((dd[u] - dmin) >> shift, 256, 208)) atomicAdd(&s_hist[(dd[u] - dmin) >> shift], 1u);
-            }
-        }
-        __syncthreads();
-        PH_LAP(2);
+        const bool cached = n <= kKeyCache;   // (uniform) the list fits the LDS key cache
+        const DepthBuckets B = bucket_long_list<QUAD>(g, n, S, cached, ph_lap_);
         int b_next = 0;
-        if (!QUAD) PH_ADD(2, PH_T() - t_p);   // (ordinary layout: [2] = the passes over the keys, [3] = of which the rounds' collect passes)
         bool bail = false;
         bool partitioned = false;                 // the keys left after the first round have been laid out by bucket
         int p_consumed = 0;                       // ... and this many of them have been composited since
         int *const ids = f.sorted_ids + beg;      // ... as storage slots in the tile's (otherwise unused) id segment
         while (!bail) {
-            // ---- next bucket range [b0, b1]: b0 = first non-empty bucket >= b_next, b1 = last bucket
-            //      whose running count from b0 stays <= CH.  Thread t owns bucket t.
-            unsigned my_hv, my_incl;
-            {
-                const unsigned hv = (tid >= b_next) ? s_hist[tid] : 0u;
-                unsigned incl = wave_inclusive_sum_u32(hv);
-                if (lane == 63) s_wsum[wv] = incl;
-                __syncthreads();
-                for (int w = 0; w < wv; ++w) incl += s_wsum[w];        // inclusive count of buckets b_next..tid
-                my_hv = hv;
-                my_incl = incl;
-                if (tid == kLazyThreads - 1) s_rem = incl;             // keys not yet consumed (buckets >= b_next)
-                const unsigned long long nz = __ballot(hv != 0u);
-                const unsigned long long fit = __ballot(hv != 0u && incl <= (unsigned)CH);
-                if (lane == 0) {
-                    s_queue_u32(s_raw)[wv] = nz ? (unsigned)(wv * 64 + __ffsll((long long)nz) - 1) : 256u;          // first non-empty
-                    s_queue_u32(s_raw)[4 + wv] = fit ? (unsigned)(wv * 64 + 63 - __clzll((long long)fit)) : 0xffffffffu;   // last fitting
-                }
-                __syncthreads();
-                if (tid == 0) {
-                    unsigned first = 256u;
-                    int last = -1;
-                    for (int w = 3; w >= 0; --w) {
-                        if (s_queue_u32(s_raw)[w] != 256u) first = s_queue_u32(s_raw)[w];
-                    }
-                    for (int w = 0; w < 4; ++w)
-                        if (s_queue_u32(s_raw)[4 + w] != 0xffffffffu) last = (int)s_queue_u32(s_raw)[4 + w];
-                    s_m = first;
-                    s_b1 = (first >= 256u) ? 256 : last;   // last < first (i.e. -1): first bucket alone exceeds the chunk
-                }
-            }
-            __syncthreads();
-            const int b0 = (int)s_m, b1 = s_b1;
-            __syncthreads();
+            const BucketRange R = select_bucket_range<CH>(S, b_next);
             PH_LAP(3);
-            if (b1 == 256) break;                 // nothing left
-            if (b1 < 0) { bail = true; break; }   // one bucket larger than the chunk: full path
-            // ---- a SECOND round starts (the first chunk did not saturate the tile, which is the exception):
-            //      lay the remaining keys out by bucket, once, so that every later round reads only its own
-            //      chunk instead of scanning the whole list again (n^2 / 512 key reads on a long translucent list;
-            //      only worth it when many rounds are still to come: kPartitionMin).
-            //      Bucket t of the remainder starts at the exclusive count of buckets b_next .. t - 1: the scan above.
+            if (R.b1 == 256) break;                 // nothing left
+            if (R.b1 < 0) { bail = true; break; }   // one bucket larger than the chunk: full path
             if (!partitioned && b_next > 0 && s_rem > (unsigned)kPartitionMin) {
-                s_cur[tid] = my_incl - my_hv;
-                __syncthreads();
-                partition_by_bucket(g, n, dmin, shift, b_next, s_cur, ids);
+                lay_out_remainder(g, n, B, b_next, R, S, ids);
                 partitioned = true;
                 PH_LAP(4);
             }
-            // ---- collect the range into LDS grouped by bucket (bucket t starts at the exclusive count of
-            //      the buckets before it), depth words relative to the range's base
-            const unsigned base = dmin + ((unsigned)b0 << shift);
-            const bool mine = tid >= b0 && tid <= b1;
-            if (tid == b1) s_m = my_incl;                            // entries in the chunk
-            if (!partitioned) {
-                if (mine) s_cur[tid] = my_incl - my_hv;
-            } else if (mine) {
-                s_cur[tid] = my_incl;   // END of bucket t inside the chunk (what the collect pass leaves): b0 is the first non-empty bucket of the scan
-            }
-            const bool big = wg_reduce_wave_flags<false>(__any(mine && my_hv > (unsigned)kRankMax), sync_phase);
-            const unsigned long long t_c = PH_T();
-            if (!partitioned && cached && b_next == 0) {
-                // first round of a cached list: the keys are in LDS
-                for (int i = tid; i < n; i += kLazyThreads) {
-                    const unsigned long long key = kc[i];
-                    const int b = (int)((hi32(key) - dmin) >> shift);
-                    if (b >= b0 && b <= b1 && SAS_IN(b, 256, 206)) {
-                        const unsigned pos = atomicAdd(&s_cur[b], 1u);
-                        if (SAS_IN(pos, CH, 207)) ck[pos] = ((unsigned long long)(hi32(key) - base) << 32) | lo32(key);
-                    }
-                }
-            } else if (!partitioned) {
-                const unsigned long long *g3 = g;
-                asm volatile("" : "+s"(g3));
-                for (int i0 = 0; i0 < n; i0 += kLazyThreads * U) {
-                    unsigned long long kk[U];
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int i = i0 + u * kLazyThreads + tid;
-                        kk[u] = (i < n) ? g3[i] : ~0ull;
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        if (i0 + u * kLazyThreads + tid < n) {
-                            const int b = (int)((hi32(kk[u]) - dmin) >> shift);
-                            if (b >= b0 && b <= b1 && SAS_IN(b, 256, 206)) {
-                                const unsigned pos = atomicAdd(&s_cur[b], 1u);
-                                if (SAS_IN(pos, CH, 207)) ck[pos] = ((unsigned long long)(hi32(kk[u]) - base) << 32) | lo32(kk[u]);
-                            }
-                        }
-                    }
-                }
-            } else {
-                // the chunk is one contiguous run of the bucket-ordered slots; depth words come from the projection's records
-                // buckets are consumed whole and in order, so the chunk starts where the previous ones ended
-                const int st = p_consumed, cnt_chunk = (int)s_m;
-                for (int i = tid; i < cnt_chunk; i += kLazyThreads) {
-                    if (!SAS_IN(st + i, n, 216) || !SAS_IN(i, CH, 217)) continue;
-                    const unsigned slot = (unsigned)ids[st + i];
-                    const unsigned dbits = SAS_IN(slot, n_gauss, 218) ? __float_as_uint(f.rec[SAS_RS * (long long)slot + 1].w) : dmin;
-                    ck[i] = ((unsigned long long)(dbits - base) << 32) | slot;
-                }
-            }
-            __syncthreads();
+            const bool big = collect_chunk<QUAD>(f, n_gauss, g, n, ids, p_consumed, B, R, S, partitioned, cached, b_next, sync_phase);
             PH_LAP(5);
-            if (!QUAD) { PH_ADD(2, PH_T() - t_c); PH_ADD(3, PH_T() - t_c); }
             const int m = (int)s_m;
-            // ---- order the chunk, then composite it
-            const unsigned long long t_s = PH_T();
-            if (!big) {
-                lds_bucket_rank_sort<CH / kLazyThreads>(ck, m, b0, shift, s_hist, s_cur, perm);
-            } else {   // a crowded bucket (coplanar splats): radix passes cost the same whatever the distribution
-                const unsigned long long hi_excl = ((unsigned long long)(b1 - b0 + 1) << shift);
-                const unsigned rel_span = (unsigned)min((unsigned long long)(span - ((unsigned)b0 << shift)), hi_excl - 1ull);
-                lds_radix_sort<4, CH / kLazyThreads>(ck, m, rel_span, perm, cnt, dbase, s_wsum);
-            }
-            PH_ADD(0, PH_T() - t_s);
+            order_chunk<CH>(ck, m, R.b0, R.b1, B.shift, B.span, big, perm, s_hist, s_cur, cnt, dbase, s_wsum);
             PH_LAP(6);
             if (blend(m, [&](int i) { return (long long)lo32(ck[i]); })) break;
             if (partitioned) p_consumed += m;
-            b_next = b1 + 1;
+            b_next = R.b1 + 1;
             if (b_next > 255) break;
         }
-        if (bail) {
-            // More than CH entries in one depth bucket (e.g. thousands of coplanar splats): order
-            // the whole segment in place (slow, rare) and composite it from scratch.
-            if (tid == 0) __hip_atomic_fetch_add(&f.stats_host[6], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            int *out = f.sorted_ids + beg;
-            sort_global_bitonic(f.keys + beg, out, n, perm, tid, kLazyThreads);
-            __syncthreads();
-            p = pix_init(inside, ox);
-            wdone = __all(!inside);
-            blend(n, [&](int i) { return (long long)(unsigned)out[i]; });
-        }
+        if (bail) bail_to_full_sort(f, beg, n, perm, blend, p, wdone, inside, ox);
     }
-    unsigned packed;
-    float ED;
-    if constexpr (QUAD) ED = write_pixel(o, p, inside && writer, ix, iy, c.W, packed);
-    else ED = write_pixel<true>(o, p, inside, ix, iy, c.W, packed, o.rgb8 && (c.W & 3) == 0 && ((size_t)o.rgb8 & 3) == 0);
-    if (o.rgb8_host) {   // (uniform: a frame property; out_side is uniform over the workgroup)
-        if (out_side == 16) store_rows_to_host<16>(o.rgb8_host, c.W, tx * SAS_TILE, ty * SAS_TILE, ox, oy, writer, packed, s_raw);
-        else if (out_side == 8) store_rows_to_host<8>(o.rgb8_host, c.W, tx * SAS_TILE + (qd & 1) * 8, ty * SAS_TILE + (qd >> 1) * 8,
-                                                      ox & 7, oy & 7, writer, packed, s_raw);
-    }
+    const float ED = write_tile<QUAD>(c, o, tx, ty, qd, ox, oy, ix, iy, inside, writer, p, s_raw);
     if (WANT_MAX) store_tile_max(f, tile, ED, s_wmax);
     if (tid == 0) { f.tile_count[tile] = 0; f.tile_big[tile] = 0; }   // the frame's counters leave the frame zeroed (SasFrame invariant)
     PH_LAP(12);
