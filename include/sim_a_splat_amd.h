@@ -52,6 +52,8 @@ typedef enum {
 #define SAS_TIMING 8u         /* record per-stage hipEvents (readable with sas_stage_times) */
 #define SAS_TIME_TILES 32u    /* HIP events around the tile kernel only (SAS_T_BLEND); frames still pipeline */
 #define SAS_FULL_SORT 16u     /* order every tile list completely and keep it (sas_read_tile_lists); same image */
+#define SAS_MESH_SURFACE 64u  /* frames with meshes: alpha, depth and the RGB-D points / mask describe the whole scene -- where a
+                                 triangle shows it closes the ray as a last entry of opacity 1 (sas_scene_meshes); nothing else changes */
 
 /* sas_stage_times slots (milliseconds of the last completed frame rendered with SAS_TIMING).  SAS_T_SCAN reads ~0:
  * the offsets scan is the tail of the projection kernel (its last workgroup), not a launch of its own.  SAS_T_SCATTER
@@ -214,12 +216,26 @@ int sas_render_features(sas_ctx *ctx, const float *viewmat, const float *K, int 
  * Every render call then composites the meshes: per pixel the nearest triangle whose interior holds the pixel centre (depth
  * interpolated linear in 1/z, ties to the smaller (depth bits, triangle index), shared edges by a top-left rule, triangles
  * clipped at z = 0.01, non-finite or degenerate ones dropped) hides every splat at or behind its depth and takes the
- * background's place: rgb = clamp(C + T m).  alpha, depth and the RGB-D points / mask describe the splats in front of it.
+ * background's place: rgb = clamp(C + T m).  alpha, depth and the RGB-D points / mask describe the splats in front of it,
+ * unless the frame is rendered with SAS_MESH_SURFACE: then a pixel that shows a triangle of depth z_m has
+ *   depth = fma(z_m, T, d) (the depth chain's own step, weight T) and alpha = 1.0f exactly,
+ * the tile maximum, the SAS_DEPTH_FILL_MAX fill and the RGB-D tail take that depth, rgb / rgb8 and every pixel without a
+ * triangle keep their bits.  The flag is accepted by sas_render, sas_render_rgbd, sas_render_batch[_posed] and
+ * sas_render_features; it does nothing without meshes or in the *_host calls (rgb8 only).
  * Frames with meshes are SAS_FULL_SORT frames (batches take them one view at a time); sas_render_features refuses a context
- * with meshes (SAS_ERR_INVALID).
+ * with meshes (SAS_ERR_INVALID) until the meshes have feature rows:
+ * sas_scene_mesh_features, after sas_scene_upload, sas_scene_meshes and sas_scene_features (each of which forgets the rows):
+ *   features  [n_triangles,channels] float32, host or device, one row per triangle, through the colours' finite mapping and NOT
+ *             shaded (ambient / diffuse belong to colours); NULL: one-hot of each triangle's pose group
+ *   SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID without meshes, without a feature store, when n_triangles is not the
+ *   meshes' or channels not the store's, or (one-hot) when a triangle's group is >= channels.  Frames in flight are completed first.
+ * sas_render_features then renders the frame with its meshes (rgb / alpha / depth bit-identical to sas_render) and
+ *   F[p,k] = sum_{i < cut(p)} vis_i f[i,k] + (1 - alpha_p) m[p,k],  m[p,k] = the row of the pixel's triangle, fbg[k] elsewhere,
+ * cut(p) the first list entry at or behind the triangle: the frame's own compositing loop, triangle and stop rule.
  */
 int sas_scene_meshes(sas_ctx *ctx, int64_t n_vertices, const float *vertices, int64_t n_triangles, const int32_t *triangles,
                      const float *colors, const uint8_t *group, float ambient, float diffuse);
+int sas_scene_mesh_features(sas_ctx *ctx, int64_t n_triangles, int channels, const float *features);
 
 /*
  * Render n_views views of the same size in one call.  Serves the per-camera loops of

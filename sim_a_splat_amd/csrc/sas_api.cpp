@@ -97,6 +97,7 @@ struct Slot {
     bool quad = false;   // the frame runs in the quad layout: projected, binned and composited in 8-pixel tiles (prepare_frame)
     bool mesh = false;   // the frame composites the context's meshes (enqueue_chain): mesh_host tells whether its lists fit
     DevBuf mrec, mrect, mtiles, mlist;   // its mesh scratch (SasMeshFrame): records, rectangles, [count | offset | cursor], lists
+    DevBuf mwin;                         // feature frames: every pixel's triangle as k_blend_mesh_scene resolved it (SasMeshExtra::win)
     long long mcap = 0;                  // entries mlist holds (grown like the splat keys when a frame outgrows it)
     unsigned *mesh_host = nullptr;       // pinned [2], written by k_mesh_scan
     bool direct = false; // single-pass binning (SasFrame::seg > 0): the projection emits the keys, no scatter launch (choose_binning)
@@ -126,6 +127,8 @@ struct sas_ctx {
     DevBuf mesh_vert, mesh_tri, mesh_col;   // meshes (sas_scene_meshes): float4 vertices, int4 (i0, i1, i2, group), float4 colours
     SasMeshScene mesh{};
     bool has_mesh = false;   // set for the current scene (an upload forgets the meshes)
+    DevBuf mesh_feat;        // per-triangle feature rows (sas_scene_mesh_features): [chunks][nt][SAS_FEAT_K], feat_c channels
+    bool has_mesh_feat = false;   // set for the current meshes and feature store (an upload, sas_scene_meshes and sas_scene_features forget them)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
     // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
     // the call returns: nothing is remembered across calls)
@@ -551,6 +554,7 @@ int prepare_mesh(sas_ctx *c, Slot &sl)
     if ((rc = ensure(c, sl.mrec, sizeof(float4) * 4 * nrec))) return rc;
     if ((rc = ensure(c, sl.mrect, sizeof(int4) * nrec))) return rc;
     if ((rc = ensure(c, sl.mtiles, sizeof(int) * (3 * sas_tile_stride(tiles_of(sl)) + 16)))) return rc;
+    if (sl.args.out.features && (rc = ensure(c, sl.mwin, sizeof(unsigned long long) * (size_t)sl.args.W * (size_t)sl.args.H))) return rc;
     return ensure(c, sl.mlist, sizeof(int) * (size_t)sl.mcap);
 }
 
@@ -568,6 +572,18 @@ SasMeshFrame mesh_frame_of(sas_ctx *c, Slot &sl)
     m.n_rec = 2 * c->mesh.nt;
     m.status_host = sl.mesh_host;
     return m;
+}
+
+SasFeatures features_of(const sas_ctx *c, const RenderArgs &a)
+{
+    SasFeatures F{};
+    F.store = (const float *)c->feat.p;
+    F.out = a.out.features;
+    F.n_pad = c->scene.n_pad;
+    F.C = a.feat_c;
+    F.chunks = sas_feature_chunks(a.feat_c);
+    memcpy(F.bg, a.fbg, sizeof(float) * (size_t)a.feat_c);
+    return F;
 }
 
 // Frames wanted on the host (sas_render_batch_host) and not delivered by the tile kernel: one copy kernel for the
@@ -670,19 +686,16 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
     if (ld.mesh) {
         const SasMeshFrame mesh = mesh_frame_of(c, ld);
         sas_launch_mesh_bin(st, c->mesh, P, f, mesh);
-        sas_launch_blend_mesh(st, c->scene, tiles, P, f, mesh, fast_exp, any_fill);
+        const SasMeshExtra extra{a.out.features ? (unsigned long long *)ld.mwin.p : nullptr, (a.flags & SAS_MESH_SURFACE) != 0};
+        sas_launch_blend_mesh(st, c->scene, tiles, P, f, mesh, extra, fast_exp, any_fill);
+        if (a.out.features) {   // ... in front of the triangles the blend kernel has just resolved (extra.win)
+            const SasMeshFeatures MF{extra.win, (const float *)c->mesh_feat.p, c->mesh.nt};
+            sas_launch_blend_features(st, c->scene, tiles, P, f, features_of(c, a), fast_exp, &MF);
+        }
     } else if (full) {
         sas_launch_blend(st, c->scene, tiles, P, f, fast_exp, any_fill);
-        if (a.out.features) {   // a feature frame (sas_render_features): the same lists and records once more, per chunk of channels
-            SasFeatures F{};
-            F.store = (const float *)c->feat.p;
-            F.out = a.out.features;
-            F.n_pad = c->scene.n_pad;
-            F.C = a.feat_c;
-            F.chunks = sas_feature_chunks(a.feat_c);
-            memcpy(F.bg, a.fbg, sizeof(float) * (size_t)a.feat_c);
-            sas_launch_blend_features(st, c->scene, tiles, P, f, F, fast_exp);
-        }
+        // a feature frame (sas_render_features): the same lists and records once more, per chunk of channels
+        if (a.out.features) sas_launch_blend_features(st, c->scene, tiles, P, f, features_of(c, a), fast_exp, nullptr);
     } else if (nv > 1) {
         // (quad: by the size of one view (prepare_frame): groups of four 300-tile views still gain (vec_env_probe))
         sas_launch_tiles_lazy_multi(st, c->scene, tiles, mf, fast_exp, any_fill, ld.quad, tile_ev[0], tile_ev[1]);
@@ -924,11 +937,11 @@ int sas_destroy(sas_ctx *c)
         for (auto &e : sl.ev)
             if (e) (void)hipEventDestroy(e);
         for (DevBuf *b : {&sl.scr.rec, &sl.scr.col, &sl.scr.info, &sl.scr.tilebuf, &sl.scr.keys, &sl.scr.ids, &sl.scr.counters,
-                          &sl.scr.wgvis, &sl.scr.wgbase, &sl.scr.tilemax, &sl.mrec, &sl.mrect, &sl.mtiles, &sl.mlist})
+                          &sl.scr.wgvis, &sl.scr.wgbase, &sl.scr.tilemax, &sl.mrec, &sl.mrect, &sl.mtiles, &sl.mlist, &sl.mwin})
             release(*b);
     }
     for (DevBuf *b : {&c->g0, &c->g1, &c->g2, &c->col, &c->gid8, &c->perm, &c->host_stage, &c->feat, &c->mesh_vert, &c->mesh_tri,
-                      &c->mesh_col})
+                      &c->mesh_col, &c->mesh_feat})
         release(*b);
     delete c;
     return SAS_OK;
@@ -956,6 +969,7 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
     c->has_scene = false;
     c->has_feat = false;
     c->has_mesh = false;
+    c->has_mesh_feat = false;
 
     const int deg = sh_degree < 0 ? -1 : sh_degree;
     const int coeff_floats = deg < 0 ? 3 : 3 * (deg + 1) * (deg + 1);
@@ -1338,10 +1352,28 @@ int sas_render(sas_ctx *c, const float *viewmat, const float *K, int width, int 
     return render_views(c, &v, 1, width, height, background, flags, nullptr, stream, false, !(flags & SAS_ASYNC));
 }
 
+// A caller's array of `count` floats where a kernel can read it: in place when it is device memory of this context's device, else
+// copied into `stage` (host memory), which the caller releases.
+static int device_floats(sas_ctx *c, const float *p, size_t count, DevBuf &stage, const float **out)
+{
+    hipPointerAttribute_t at{};
+    const bool on_device = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
+    (void)hipGetLastError();   // (a plain host pointer leaves an error behind on some runtimes)
+    *out = p;
+    if (on_device) return SAS_OK;
+    const int rc = ensure(c, stage, sizeof(float) * count);
+    if (rc) return rc;
+    const hipError_t e = hipMemcpy(stage.p, p, sizeof(float) * count, hipMemcpyDefault);
+    if (e != hipSuccess) { release(stage); return fail(c, SAS_ERR_HIP, "feature copy: %s", hipGetErrorString(e)); }
+    *out = (const float *)stage.p;
+    return SAS_OK;
+}
+
 int sas_scene_features(sas_ctx *c, int64_t n, int channels, const float *features)
 {
     if (!c) return SAS_ERR_INVALID;
     if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_features before sas_scene_upload");
+    c->has_mesh_feat = false;   // the triangles' rows belong to the store they were set beside
     if (n != c->scene.n) return fail(c, SAS_ERR_INVALID, "features for %lld Gaussians, the scene has %lld", (long long)n, (long long)c->scene.n);
     if (channels < 1 || channels > SAS_MAX_FEATURES) return fail(c, SAS_ERR_INVALID, "channels %d out of [1,%d]", channels, SAS_MAX_FEATURES);
     if (!features && c->scene.n_groups <= 0) return fail(c, SAS_ERR_INVALID, "one-hot group features need a scene with splat groups");
@@ -1357,23 +1389,9 @@ int sas_scene_features(sas_ctx *c, int64_t n, int channels, const float *feature
     const size_t np = (size_t)(n_pad > 0 ? n_pad : 64);
     int rc;
     if ((rc = ensure(c, c->feat, sizeof(float) * SAS_FEAT_K * (size_t)sas_feature_chunks(channels) * np))) return rc;
-    // the caller's array: read in place when it is device memory of this context's device, else staged (host memory)
     const float *src = nullptr;
     DevBuf s_src;
-    if (features && n > 0) {
-        hipPointerAttribute_t at{};
-        const bool on_device = hipPointerGetAttributes(&at, features) == hipSuccess && at.type == hipMemoryTypeDevice &&
-                               at.device == c->device;
-        (void)hipGetLastError();   // (a plain host pointer leaves an error behind on some runtimes)
-        if (on_device) {
-            src = features;
-        } else {
-            if ((rc = ensure(c, s_src, sizeof(float) * (size_t)n * (size_t)channels))) return rc;
-            const hipError_t e = hipMemcpy(s_src.p, features, sizeof(float) * (size_t)n * (size_t)channels, hipMemcpyDefault);
-            if (e != hipSuccess) { release(s_src); return fail(c, SAS_ERR_HIP, "feature copy: %s", hipGetErrorString(e)); }
-            src = (const float *)s_src.p;
-        }
-    }
+    if (features && n > 0 && (rc = device_floats(c, features, (size_t)n * (size_t)channels, s_src, &src))) return rc;
     // on the context's own (idle: complete_all above) stream, waited for alone -- not the whole device
     hipStream_t st = c->slots[0].fs;
     sas_launch_feature_store(st, n, n_pad, c->scene.perm, c->scene.gid8, src, channels, (float *)c->feat.p);
@@ -1393,7 +1411,9 @@ int sas_render_features(sas_ctx *c, const float *viewmat, const float *K, int wi
     if (!c) return SAS_ERR_INVALID;
     if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_render_features before sas_scene_upload");
     if (!c->has_feat) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
-    if (c->has_mesh) return fail(c, SAS_ERR_INVALID, "feature frames of a context with meshes are not supported (sas_scene_meshes)");
+    if (c->has_mesh && !c->has_mesh_feat)
+        return fail(c, SAS_ERR_INVALID, "feature frames of a context with meshes are not supported (sas_scene_meshes) until the meshes "
+                                        "have features (sas_scene_mesh_features)");
     if (!features) return fail(c, SAS_ERR_INVALID, "the features output is required");
     ViewCall v = {viewmat, K, {rgb, alpha, depth}};
     v.out.features = features;
@@ -1402,11 +1422,49 @@ int sas_render_features(sas_ctx *c, const float *viewmat, const float *K, int wi
     return render_views(c, &v, 1, width, height, background, flags | SAS_FULL_SORT, nullptr, stream, false, !(flags & SAS_ASYNC));
 }
 
+int sas_scene_mesh_features(sas_ctx *c, int64_t n_triangles, int channels, const float *features)
+{
+    if (!c) return SAS_ERR_INVALID;
+    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_mesh_features before sas_scene_upload");
+    if (!c->has_mesh) return fail(c, SAS_ERR_INVALID, "no meshes set for this scene (sas_scene_meshes)");
+    if (!c->has_feat) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
+    if (n_triangles != c->mesh.nt)
+        return fail(c, SAS_ERR_INVALID, "features for %lld triangles, the meshes have %d", (long long)n_triangles, c->mesh.nt);
+    if (channels != c->feat_c) return fail(c, SAS_ERR_INVALID, "%d channels, the feature store has %d", channels, c->feat_c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    {
+        const int rcw = complete_all(c);   // frames in flight read the rows
+        if (rcw) return rcw;
+    }
+    const size_t nt = (size_t)n_triangles;
+    if (!features) {   // one-hot of the triangles' pose groups: every group needs a channel
+        std::vector<int4> t4(nt);
+        HIP_TRY(c, hipMemcpy(t4.data(), c->mesh_tri.p, sizeof(int4) * nt, hipMemcpyDeviceToHost));
+        for (size_t t = 0; t < nt; ++t)
+            if (t4[t].w >= channels) return fail(c, SAS_ERR_INVALID, "one-hot: triangle %zu is of group %d >= %d channels", t, t4[t].w, channels);
+    }
+    c->has_mesh_feat = false;
+    int rc;
+    if ((rc = ensure(c, c->mesh_feat, sizeof(float) * SAS_FEAT_K * (size_t)sas_feature_chunks(channels) * nt))) return rc;
+    const float *src = nullptr;
+    DevBuf s_src;
+    if (features && (rc = device_floats(c, features, nt * (size_t)channels, s_src, &src))) return rc;
+    hipStream_t st = c->slots[0].fs;   // the context's own, idle stream, as sas_scene_features
+    sas_launch_mesh_feature_store(st, n_triangles, c->mesh.tri, src, channels, (float *)c->mesh_feat.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    release(s_src);
+    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "mesh feature store: %s", hipGetErrorString(e));
+    c->has_mesh_feat = true;
+    return SAS_OK;
+}
+
 int sas_scene_meshes(sas_ctx *c, int64_t n_vertices, const float *vertices, int64_t n_triangles, const int32_t *triangles,
                      const float *colors, const uint8_t *group, float ambient, float diffuse)
 {
     if (!c) return SAS_ERR_INVALID;
     if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_meshes before sas_scene_upload");
+    c->has_mesh_feat = false;   // every call forgets the triangles' feature rows (sas_scene_mesh_features)
     if (n_triangles < 0 || n_vertices < 0 || n_triangles > (1 << 29) || n_vertices > 0x7fffffffll)
         return fail(c, SAS_ERR_INVALID, "bad mesh sizes: %lld vertices, %lld triangles", (long long)n_vertices, (long long)n_triangles);
     if (!std::isfinite(ambient) || !std::isfinite(diffuse)) return fail(c, SAS_ERR_INVALID, "ambient and diffuse must be finite");

@@ -190,8 +190,18 @@ static inline int sas_feature_chunks(int C) { return (C + SAS_FEAT_K - 1) / SAS_
 void sas_launch_feature_store(hipStream_t st, int64_t n, int64_t n_pad, const int *perm, const uint8_t *gid8, const float *src,
                               int C, float *store);
 // after sas_launch_blend, on the same frame: the features of every pixel, one workgroup per (tile, chunk)
+// ... of a frame with meshes (sas_scene_mesh_features): what k_blend_mesh_scene resolved per pixel, and the per-triangle rows that take the
+// feature background's place where a triangle shows
+struct SasMeshFeatures {
+    const unsigned long long *win;   // [H W] (depth bits << 32 | record) of the pixel's triangle, ~0: none (SasMeshExtra::win)
+    const float *store;              // [chunks][nt][SAS_FEAT_K]
+    long long nt;
+};
+// MF: nullptr for a frame without meshes
 void sas_launch_blend_features(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
-                               const SasFeatures &F, bool fast_exp);
+                               const SasFeatures &F, bool fast_exp, const SasMeshFeatures *MF);
+// store <- features [nt,C] (device; nullptr: one-hot of the triangles' pose groups), through finite_colour
+void sas_launch_mesh_feature_store(hipStream_t st, int64_t nt, const int4 *tri, const float *src, int C, float *store);
 
 // launchers (sas_kernels.hip)
 void sas_launch_relayout(hipStream_t st, int64_t n, int64_t n_pad, const int *perm, const float *means, const float *quats,
@@ -264,7 +274,13 @@ struct SasMeshFrame {
     int n_rec;              // 2 nt
     unsigned *status_host;  // pinned [2]: [0] entries the lists needed, [1] 1 when that exceeds cap
 };
+// What a mesh frame with a features output and / or SAS_MESH_SURFACE asks of its blend kernel beyond the frame (k_blend_mesh_scene;
+// plain mesh frames run k_blend_mesh, which knows neither)
+struct SasMeshExtra {
+    unsigned long long *win;   // feature frames: [H W] every pixel's (depth bits << 32 | record), ~0: none, for k_blend_features_mesh; else nullptr
+    int surface;               // SAS_MESH_SURFACE: alpha / depth of a covered pixel close on the triangle
+};
 void sas_launch_mesh_bin(hipStream_t st, const SasMeshScene &m, const SasParams &P, const SasFrame &f, const SasMeshFrame &mf);
 // sas_launch_blend for a frame with meshes
 void sas_launch_blend_mesh(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
-                           const SasMeshFrame &mf, bool fast_exp, bool want_max);
+                           const SasMeshFrame &mf, const SasMeshExtra &x, bool fast_exp, bool want_max);

@@ -663,9 +663,16 @@ struct RgbdPayload {
 // ... and one chunk of SAS_FEAT_K feature channels (k_blend_features): from the chunk's plane of the store, staged in kFeatQ
 // planes of q2, accumulated in registers.  Every channel takes the chain of p.r: entry 0 inside entry 1.
 constexpr int kFeatQ = SAS_FEAT_K / 4;   // float4 per entry of a chunk
-struct FeaturePayload {
+// Z (a frame with meshes: k_blend_features_mesh): every staged entry also carries its depth, which blend_range<.., MESH> holds against
+// the pixel's triangle -- one float plane of kStage behind the queues, read with the entry's channels.
+constexpr int kFeatZOff = kFeatQ * kStage * 16 + 256 * 4 + 16 * 256 * 2;   // bytes from q2 to the depth plane
+constexpr int kFeatLdsBytes = kBlendLdsBytes + (kFeatQ - 1) * kStage * 16;
+constexpr int kFeatLdsBytesZ = kFeatLdsBytes + ((kStage * 4 + 15) & ~15);
+template <bool Z>
+struct FeaturePayloadT {
     struct Rec { float4 v[kFeatQ]; };
-    typedef Rec V;
+    struct RecZ { float4 v[kFeatQ]; float z; };
+    typedef std::conditional_t<Z, RecZ, Rec> V;
     const float4 *store;   // the chunk's plane: [n_pad][kFeatQ]
     long long n_pad;
     float acc[SAS_FEAT_K];
@@ -685,11 +692,12 @@ struct FeaturePayload {
         }
         return r;
     }
-    DEV void stage(const BlendLds &L, int slot, const Rec &c, float) const
+    DEV void stage(const BlendLds &L, int slot, const Rec &c, float depth) const
     {
         if (!SAS_IN(slot, kStage, 320)) return;
 #pragma unroll
         for (int k = 0; k < kFeatQ; ++k) L.q2[k * kStage + slot] = c.v[k];
+        if constexpr (Z) reinterpret_cast<float *>(reinterpret_cast<char *>(L.q2) + kFeatZOff)[slot] = depth;
     }
     DEV void stage_sentinel(const BlendLds &L, float z0) const
     {
@@ -704,9 +712,14 @@ struct FeaturePayload {
         V r;
 #pragma unroll
         for (int k = 0; k < kFeatQ; ++k) r.v[k] = *reinterpret_cast<const float4 *>(q2b + k * kStage * 16 + off);
+        if constexpr (Z) r.z = *reinterpret_cast<const float *>(q2b + kFeatZOff + (off >> 2));
         return r;
     }
-    DEV float depth(const V &) const { return 0.0f; }
+    DEV float depth(const V &c) const
+    {
+        if constexpr (Z) return c.z;
+        else return 0.0f;
+    }
     DEV void add(PixState &, const V &c0, float vis0, const V &c1, float vis1)
     {
 #pragma unroll
@@ -718,6 +731,7 @@ struct FeaturePayload {
         }
     }
 };
+typedef FeaturePayloadT<false> FeaturePayload;
 
 // Composite entries [0, count) of a depth-ordered list onto this thread's pixel.  Wave w owns the
 // 8x8 quadrant w of the tile, its 16-lane group g the quadrant's 4x4 block g (pixel_of).  Per batch
@@ -726,9 +740,9 @@ struct FeaturePayload {
 // their own queues in lockstep, front to back (a group that runs out reads the sentinel record,
 // which no pixel accepts).  Returns true when every pixel of the tile has terminated (uniform over
 // the workgroup).  `slot_at(i)` gives the storage slot of entry i; `pay` is what the entries carry (RgbdPayload, FeaturePayload).
-// MESH (k_blend_mesh): `zlim` is the depth of the pixel's nearest triangle (+Inf: none).  The first entry whose depth is
-// >= zlim ends the pixel as the transmittance stop does: it is not added, nor is anything after it.  (Only RgbdPayload stages
-// the depths this reads: sas_render_features refuses a context with meshes.)
+// MESH (k_blend_mesh, k_blend_features_mesh): `zlim` is the depth of the pixel's nearest triangle (+Inf: none).  The first entry whose
+// depth is >= zlim ends the pixel as the transmittance stop does: it is not added, nor is anything after it.  (RgbdPayload and
+// FeaturePayloadT<true> stage the depths this reads.)
 template <bool FAST_EXP, bool MESH = false, typename SlotAt, typename PAY>
 DEV bool blend_range(const SasFrame &f, long long n_gauss, int tx, int ty, const PixConst pc, int count, SlotAt slot_at,
                      const BlendLds &L, PixState &p, bool &wdone, unsigned long long &ph_lap_, unsigned &sync_phase,
@@ -1247,8 +1261,9 @@ DEV void store_tile_max(const SasFrame &f, int tile, float ED, unsigned *s_wmax)
 
 // The pixel's triangle in a frame with meshes: every thread resolves its own pixel over its tile's triangle list -- the minimum of
 // (depth bits, record) among the records whose interior holds the pixel centre, whatever the list's order (no z-buffer, no
-// atomics).  Returns that depth (+Inf: none) and puts the triangle's colour in the background's place.
-DEV float mesh_resolve(const SasMeshFrame &M, const SasCam &c, int tile, int ix, int iy, float *bg)
+// atomics).  Returns that depth (+Inf: none) and puts the triangle's colour in the background's place; `win` receives the winning
+// (depth bits << 32 | record), ~0: none.
+DEV float mesh_resolve(const SasMeshFrame &M, const SasCam &c, int tile, int ix, int iy, float *bg, unsigned long long &win)
 {
     // the pixel's triangle (records 2 t, 2 t + 1 belong to triangle t: the record index orders triangles as their index does)
     // the pixel centre in the records' frame (the image centre; exact: halves of integers)
@@ -1272,6 +1287,7 @@ DEV float mesh_resolve(const SasMeshFrame &M, const SasCam &c, int tile, int ix,
             best = key < best ? key : best;
         }
     }
+    win = best;
     if (best == ~0ull) return __builtin_inff();
     const float4 m3 = M.rec[4 * (long long)(unsigned)(best & 0xffffffffu) + 3];
     bg[0] = m3.x; bg[1] = m3.y; bg[2] = m3.z;
@@ -1281,8 +1297,11 @@ DEV float mesh_resolve(const SasMeshFrame &M, const SasCam &c, int tile, int ix,
 // MESH: a frame with meshes (its lists, records and tiles as any other's; SAS_FULL_SORT frames with meshes deliver no rgb8 to the
 // host from the tile kernel).  The splats are composited in front of the pixel's triangle (blend_range<.., MESH>), whose colour
 // takes the background's place in write_pixel.
-template <bool FAST_EXP, bool WANT_MAX, bool MESH>
-DEV void blend_tile(const SasParams &P, const SasFrame &f, long long n_gauss, int tile, unsigned &sync_phase, const SasMeshFrame *M)
+// SCENE (k_blend_mesh_scene: a mesh frame with a features output and / or SAS_MESH_SURFACE): the pixel's triangle is left in X->win
+// for k_blend_features_mesh, and alpha / depth close on the triangle.  Plain mesh frames keep the kernel without either.
+template <bool FAST_EXP, bool WANT_MAX, bool MESH, bool SCENE = false>
+DEV void blend_tile(const SasParams &P, const SasFrame &f, long long n_gauss, int tile, unsigned &sync_phase, const SasMeshFrame *M,
+                    const SasMeshExtra *X = nullptr)
 {
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[kBlendLdsBytes];
     __shared__ unsigned s_wmax[4];
@@ -1296,7 +1315,14 @@ DEV void blend_tile(const SasParams &P, const SasFrame &f, long long n_gauss, in
     PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
     SasOutputs o = P.out;
     float zlim = 0.0f;
-    if constexpr (MESH) zlim = mesh_resolve(*M, c, tile, ix, iy, o.bg);
+    if constexpr (MESH) {
+        unsigned long long win;
+        zlim = mesh_resolve(*M, c, tile, ix, iy, o.bg, win);
+        // a feature frame: k_blend_features_mesh's workgroups (one per chunk of channels) take the pixel's triangle and depth from
+        // here, so that rgb and features can never disagree about which triangle a pixel shows
+        if constexpr (SCENE)
+            if (X->win && inside && SAS_IN((long long)iy * c.W + ix, o.n_pixels, 322)) X->win[(long long)iy * c.W + ix] = win;
+    }
     long long beg, end;
     tile_segment(f, tile, beg, end);
     const int *ids = f.sorted_ids + beg;
@@ -1305,7 +1331,19 @@ DEV void blend_tile(const SasParams &P, const SasFrame &f, long long n_gauss, in
     blend_range<FAST_EXP, MESH>(f, n_gauss, tx, ty, pix_const(ox, oy), (int)(end - beg),
                                 [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay, zlim);
     unsigned packed;
-    const float ED = write_pixel(o, p, inside, ix, iy, c.W, packed);
+    float ED = write_pixel(o, p, inside, ix, iy, c.W, packed);
+    if constexpr (SCENE) {
+        // SAS_MESH_SURFACE: the triangle closes the ray as a last entry of opacity 1 -- depth chain d <- fma(z_m, T, d), alpha 1
+        // (ED's division is by max(1, 1e-10)).  rgb and rgb8 are already C + T m.
+        if (X->surface && inside && zlim < __builtin_inff()) {
+            const long long pix = (long long)iy * c.W + ix;
+            ED = fma_(zlim, p.T, p.d);
+            if (SAS_IN(pix, o.n_pixels, 323)) {
+                if (o.alpha) o.alpha[pix] = 1.0f;
+                if (o.depth) o.depth[pix] = ED;
+            }
+        }
+    }
     if (!MESH && o.rgb8_host) store_rows_to_host<16>(o.rgb8_host, c.W, tx * SAS_TILE, ty * SAS_TILE, ox, oy, true, packed, s_raw);
     if (WANT_MAX) store_tile_max(f, tile, ED, s_wmax);
     if (tid == 0) { f.tile_count[tile] = 0; f.tile_big[tile] = 0; }   // the frame's counters leave the frame zeroed (SasFrame invariant)
@@ -1324,6 +1362,14 @@ __global__ __launch_bounds__(256) void k_blend_mesh(SasParams P, SasFrame f, lon
     unsigned sync_phase = 0u;
     for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x)
         blend_tile<FAST_EXP, WANT_MAX, true>(P, f, n_gauss, tl[oi], sync_phase, &M);
+}
+template <bool FAST_EXP, bool WANT_MAX>
+__global__ __launch_bounds__(256) void k_blend_mesh_scene(SasParams P, SasFrame f, long long n_gauss, const int *tl, const int *range,
+                                                          SasMeshFrame M, SasMeshExtra X)
+{
+    unsigned sync_phase = 0u;
+    for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x)
+        blend_tile<FAST_EXP, WANT_MAX, true, true>(P, f, n_gauss, tl[oi], sync_phase, &M, &X);
 }
 
 // ================================================================================================
@@ -1983,11 +2029,14 @@ void sas_launch_blend(hipStream_t st, const SasScene &s, int tiles, const SasPar
 }
 
 void sas_launch_blend_mesh(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
-                           const SasMeshFrame &mf, bool fast_exp, bool want_max)
+                           const SasMeshFrame &mf, const SasMeshExtra &x, bool fast_exp, bool want_max)
 {
     const long long n = s.n > 0 ? s.n : 1;
     with_flags([&](auto fast, auto wmax) {
-        hipLaunchKernelGGL((k_blend_mesh<fast(), wmax()>), dim3((unsigned)tiles), dim3(256), 0, st, P, f, n, f.tile_order, f.sort_class + 4, mf);
+        if (x.win || x.surface)
+            hipLaunchKernelGGL((k_blend_mesh_scene<fast(), wmax()>), dim3((unsigned)tiles), dim3(256), 0, st, P, f, n, f.tile_order, f.sort_class + 4, mf, x);
+        else
+            hipLaunchKernelGGL((k_blend_mesh<fast(), wmax()>), dim3((unsigned)tiles), dim3(256), 0, st, P, f, n, f.tile_order, f.sort_class + 4, mf);
     }, fast_exp, want_max);
 }
 
@@ -2073,6 +2122,37 @@ __global__ __launch_bounds__(256) void k_feature_store(long long n, long long n_
     }
 }
 
+// store[(q nt + t) K + k] = channel q K + k of triangle t, through finite_colour (NOT shaded: ambient / diffuse belong to colours);
+// one-hot mode (src == nullptr): (the triangle's pose group == q K + k).  Channels >= C are zero.  One thread per (chunk, triangle).
+__global__ __launch_bounds__(256) void k_mesh_feature_store(long long nt, const int4 *tri, const float *src, int C, int chunks, float *store)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long total = (long long)chunks * nt;
+    if (i >= total) return;
+    const int q = (int)(i / nt);
+    const long long t = i - (long long)q * nt;
+    const int grp = SAS_IN(t, nt, 324) ? tri[t].w : -1;
+    float v[SAS_FEAT_K];
+#pragma unroll
+    for (int k = 0; k < SAS_FEAT_K; ++k) {
+        const int ch = q * SAS_FEAT_K + k;
+        v[k] = 0.0f;
+        if (ch < C) {
+            if (src) {
+                const long long at = t * C + ch;
+                if (SAS_IN(at, nt * C, 325)) v[k] = finite_colour(src[at]);
+            } else {
+                v[k] = grp == ch ? 1.0f : 0.0f;
+            }
+        }
+    }
+    float4 *dst = reinterpret_cast<float4 *>(store) + i * kFeatQ;
+    if (SAS_IN(i * kFeatQ + kFeatQ - 1, total * kFeatQ, 326)) {
+#pragma unroll
+        for (int r = 0; r < kFeatQ; ++r) dst[r] = make_float4(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
+    }
+}
+
 // One workgroup per (tile, chunk of SAS_FEAT_K channels), one lane per pixel (pixel_of), on the complete depth-ordered list the
 // full path's k_blend has just composited: the same blend_range, with the chunk's channels in the colours' place.  Every chunk
 // recomputes alpha and T.
@@ -2081,7 +2161,7 @@ template <bool FAST_EXP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_blend_features(SasParams P, SasFrame f, long long n_gauss,
                                                                                                SasFeatures F)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kBlendLdsBytes + (kFeatQ - 1) * kStage * 16];
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kFeatLdsBytes];
     const SasCam &c = P.cam;
     const BlendLds L = blend_lds(s_raw, kFeatQ);   // the chunk's features in the colours' place
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -2127,6 +2207,78 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     }
 }
 
+// k_blend_features for a frame with meshes: the pixel's triangle and its depth are the ones the frame's k_blend_mesh_scene resolved
+// (MF.win); the splats in front of it are composited (blend_range<.., MESH> on the entries' staged depths: FeaturePayloadT<true>)
+// and the triangle's feature row takes the feature background's place.  (A kernel of its own, as k_blend_mesh is beside k_blend:
+// hipcc's code for k_blend_features does not survive being shared -- tools/isa_gate.py -- and frames without meshes keep theirs.)
+// Six waves per SIMD too: 80 VGPRs, 26 KiB of LDS (profiles/mesh_features_kernel_resources.txt).
+template <bool FAST_EXP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_blend_features_mesh(SasParams P, SasFrame f, long long n_gauss,
+                                                                                                    SasFeatures F, SasMeshFeatures MF)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kFeatLdsBytesZ];
+    const SasCam &c = P.cam;
+    const BlendLds L = blend_lds(s_raw, kFeatQ);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int oi = (int)blockIdx.x, q = (int)blockIdx.y;
+    if (!SAS_IN(oi, f.n_tiles, 329)) return;
+    const int tile = f.tile_order[oi];
+    if (!SAS_IN(tile, f.n_tiles, 330)) return;   // (uniform)
+    const int tx = tile % c.tw, ty = tile / c.tw;
+    int ox, oy, ix, iy;
+    bool inside, wdone;
+    pixel_of(wv, lane, ox, oy);
+    PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
+    float zlim = __builtin_inff();
+    if (inside && SAS_IN((long long)iy * c.W + ix, P.out.n_pixels, 327)) {
+        const unsigned long long win = MF.win[(long long)iy * c.W + ix];
+        if (win != ~0ull) zlim = __uint_as_float((unsigned)(win >> 32));
+    }
+    long long beg, end;
+    tile_segment(f, tile, beg, end);
+    const int *ids = f.sorted_ids + beg;
+    FeaturePayloadT<true> pay{reinterpret_cast<const float4 *>(F.store) + (long long)q * F.n_pad * kFeatQ, F.n_pad, {}};
+    unsigned long long ph_lap_ = 0ull;
+    unsigned sync_phase = 0u;
+    blend_range<FAST_EXP, true>(f, n_gauss, tx, ty, pix_const(ox, oy), end > beg ? (int)(end - beg) : 0,
+                                [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay, zlim);
+    {   // (the pixel's coordinates again, as in k_blend_features)
+        int t2 = tid;
+        asm volatile("" : "+v"(t2));
+        pixel_of(t2 >> 6, t2 & 63, ox, oy);
+        bool w2;
+        pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, w2);
+    }
+    if (!inside) return;
+    const long long pix = (long long)iy * c.W + ix;
+    if (!SAS_IN(pix, P.out.n_pixels, 331)) return;
+    const float a = 1.0f - p.T;
+    const float wb = 1.0f - a;
+    const int c0 = q * SAS_FEAT_K;
+    // the triangle's row of this chunk (records 2 t, 2 t + 1 belong to triangle t); the pixel's entry is read again here rather
+    // than held across the loop
+    const unsigned long long win = MF.win[pix];
+    const long long t = (long long)((unsigned)win >> 1);
+    const bool covered = win != ~0ull && t < MF.nt && SAS_IN(t, MF.nt, 328);
+    float m[SAS_FEAT_K];
+    if (covered) {
+        const float4 *row = reinterpret_cast<const float4 *>(MF.store) + ((long long)q * MF.nt + t) * kFeatQ;
+#pragma unroll
+        for (int r = 0; r < kFeatQ; ++r) {
+            const float4 v = row[r];
+            m[4 * r] = v.x; m[4 * r + 1] = v.y; m[4 * r + 2] = v.z; m[4 * r + 3] = v.w;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < SAS_FEAT_K; ++k) {
+        const int ch = c0 + k;
+        if (ch < F.C && SAS_IN(ch, SAS_MAX_FEATURES, 332)) {
+            const long long o = pix * F.C + ch;
+            if (SAS_IN(o, P.out.n_pixels * F.C, 333)) F.out[o] = pay.acc[k] + wb * (covered ? m[k] : F.bg[ch]);
+        }
+    }
+}
+
 }  // namespace
 
 void sas_launch_feature_store(hipStream_t st, int64_t n, int64_t n_pad, const int *perm, const uint8_t *gid8, const float *src,
@@ -2140,10 +2292,21 @@ void sas_launch_feature_store(hipStream_t st, int64_t n, int64_t n_pad, const in
 }
 
 void sas_launch_blend_features(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
-                               const SasFeatures &F, bool fast_exp)
+                               const SasFeatures &F, bool fast_exp, const SasMeshFeatures *MF)
 {
     if (tiles <= 0 || F.chunks <= 0) return;
     const long long n = s.n > 0 ? s.n : 1;
     const dim3 grid((unsigned)tiles, (unsigned)F.chunks);
-    with_flags([&](auto fast) { hipLaunchKernelGGL(k_blend_features<fast()>, grid, dim3(256), 0, st, P, f, n, F); }, fast_exp);
+    with_flags([&](auto fast) {
+        if (MF) hipLaunchKernelGGL(k_blend_features_mesh<fast()>, grid, dim3(256), 0, st, P, f, n, F, *MF);
+        else hipLaunchKernelGGL(k_blend_features<fast()>, grid, dim3(256), 0, st, P, f, n, F);
+    }, fast_exp);
+}
+
+void sas_launch_mesh_feature_store(hipStream_t st, int64_t nt, const int4 *tri, const float *src, int C, float *store)
+{
+    const int chunks = sas_feature_chunks(C);
+    const long long total = (long long)chunks * nt;
+    if (total <= 0) return;
+    hipLaunchKernelGGL(k_mesh_feature_store, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (long long)nt, tri, src, C, chunks, store);
 }

@@ -307,6 +307,16 @@ class SplatHandler:
                 out[i] = np.asarray(imgs[j])
         return out
 
+    def render_segmentation(self, chs, cam_poses, render_size) -> List[np.ndarray]:
+        """``render`` for label images: one uint8 ``[H,W]`` per camera, the pose-row index of the splat group or mesh each
+        pixel shows (``chs.row_names()`` names the rows; 255: nothing) -- ``SplatScene.get_segmentation``, one view at a time
+        (feature frames are single views)."""
+        if cam_poses is None:
+            cam_poses = [(chs.camera.wxyz, chs.camera.position)]
+        cam = [poses.pose_wxyz_xyz(p) for p in cam_poses]
+        return [chs.get_segmentation(int(s[0]), int(s[1]), wxyz=w, position=p)["labels"].cpu().numpy()
+                for (w, p), s in zip(cam, render_size)]
+
 
 class CameraRig:
     """Camera dictionary ``{id: {link_name, local_frame, type, render_size}}`` of the reference

@@ -53,6 +53,36 @@ def feature_channels(shape: Sequence[int], n: int) -> int:
     return shape[1]
 
 
+def mesh_feature_channels(shape: Sequence[int], n_triangles: int, channels: int) -> int:
+    """Channels of a per-triangle feature array of ``shape`` for meshes of ``n_triangles`` triangles beside a feature store of
+    ``channels`` channels ([T,C] with C the store's); ValueError otherwise."""
+    if n_triangles <= 0:
+        raise ValueError("mesh features need meshes (upload_meshes)")
+    if channels <= 0:
+        raise ValueError("mesh features need a feature store (upload_features)")
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 2 or shape[0] != n_triangles:
+        raise ValueError(f"mesh features must be [T={n_triangles},C], got {list(shape)}")
+    if shape[1] != channels:
+        raise ValueError(f"mesh features must have the feature store's {channels} channels, got {shape[1]}")
+    return shape[1]
+
+
+def mesh_onehot_channels(groups: np.ndarray, n_triangles: int, channels: int) -> int:
+    """Channels of the one-hot mesh features (a triangle's pose group is its channel) beside a feature store of ``channels``
+    channels: every triangle's group must have a channel; ValueError otherwise."""
+    if n_triangles <= 0:
+        raise ValueError("mesh features need meshes (upload_meshes)")
+    if channels <= 0:
+        raise ValueError("mesh features need a feature store (upload_features)")
+    g = np.asarray(groups).reshape(-1)
+    if g.shape[0] != n_triangles:
+        raise ValueError(f"{g.shape[0]} mesh groups for {n_triangles} triangles")
+    if g.size and int(g.max()) >= channels:
+        raise ValueError(f"one-hot mesh features: pose group {int(g.max())} has no channel among {channels}")
+    return channels
+
+
 def feature_background_array(fbg, C: int) -> Optional[np.ndarray]:
     """The feature background as a float32 host array [C] (None: zeros, passed as NULL); ValueError on a wrong length."""
     if fbg is None:
@@ -113,6 +143,8 @@ class Rasterizer:
         self.n_features = 0     # channels of the feature store (upload_features); 0: none for this scene
         self._features_onehot = False
         self.n_mesh_triangles = 0   # triangles of the meshes (upload_meshes); 0: none for this scene
+        self._mesh_groups = np.zeros(0, np.uint8)   # their pose groups
+        self._mesh_features_onehot = False   # the meshes' feature rows are the one-hot of the triangles' pose groups (upload_mesh_features)
         self._keep = []  # outputs of in-flight async frames (the C ABI keeps up to four)
         self._argcache = {}  # id(argument) -> (argument, float32 array, address): _host_arg
 
@@ -174,12 +206,16 @@ class Rasterizer:
         self.n_features = 0     # (the upload forgot them)
         self._features_onehot = False
         self.n_mesh_triangles = 0
+        self._mesh_groups = np.zeros(0, np.uint8)
+        self._mesh_features_onehot = False
 
     @_locked
     def upload_features(self, features: Optional[ArrayLike] = None) -> None:
         """Per-Gaussian feature channels for ``render_features``: ``[N,C]`` numpy or torch (host or device, the order of
         ``upload``), 1 <= C <= 256; NaN and +-Inf are mapped to -+FLT_MAX as colours are.  ``None``: one-hot of the scene's
-        splat groups (C = n_groups), built on the device.  A new ``upload`` forgets them."""
+        splat groups (C = n_groups), built on the device.  A new ``upload`` forgets them.  Mesh features
+        (``upload_mesh_features``) belong to the store they were set beside: this call forgets them."""
+        self._mesh_features_onehot = False
         if features is None:
             if self.n_groups <= 0:
                 raise ValueError("one-hot group features need a scene uploaded with group_id")
@@ -199,7 +235,9 @@ class Rasterizer:
         """Triangle meshes composited into every frame (sas_scene_meshes; DESIGN.md 3, "Meshes"): ``vertices [V,3]`` (mesh-local,
         scale applied), ``triangles [T,3]`` vertex indices, ``colors [T,3]`` (or one ``[3]`` for all), ``groups [T]`` the pose
         group moving each triangle (``None``: group 0).  Shading ``clamp(c (ambient + diffuse |n . v|), 0, 1)``.  Frames then take
-        the full-sort path.  A new ``upload`` forgets the meshes; ``T == 0`` clears them."""
+        the full-sort path.  A new ``upload`` forgets the meshes; ``T == 0`` clears them.  Mesh features
+        (``upload_mesh_features``) are forgotten."""
+        self._mesh_features_onehot = False
         host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
         v = np.ascontiguousarray(np.asarray(host(vertices), dtype=np.float32).reshape(-1, 3))
         t = np.ascontiguousarray(np.asarray(host(triangles), dtype=np.int64).reshape(-1, 3))
@@ -216,11 +254,34 @@ class Rasterizer:
         self._check(self._L.sas_scene_meshes(self._ctx, v.shape[0], v.ctypes.data, T, t.ctypes.data, c.ctypes.data, g.ctypes.data,
                                              float(ambient), float(diffuse)), "sas_scene_meshes")
         self.n_mesh_triangles = T
+        self._mesh_groups = g
 
     @_locked
     def clear_meshes(self) -> None:
+        self._mesh_features_onehot = False
         self._check(self._L.sas_scene_meshes(self._ctx, 0, None, 0, None, None, None, 0.4, 0.6), "sas_scene_meshes")
         self.n_mesh_triangles = 0
+        self._mesh_groups = np.zeros(0, np.uint8)
+
+    @_locked
+    def upload_mesh_features(self, features: Optional[ArrayLike] = None) -> None:
+        """Per-triangle feature rows for ``render_features`` of a scene with meshes (sas_scene_mesh_features): ``[T,C]`` numpy
+        or torch, the triangle order of ``upload_meshes``, C the channels of ``upload_features``; taken as they are (not
+        shaded), NaN and +-Inf mapped as colours are.  ``None``: one-hot of each triangle's pose group.  Where a pixel
+        shows a triangle its row takes the feature background's place.  ``upload``, ``upload_meshes`` and
+        ``upload_features`` forget them -- and ``render_features`` refuses a scene with meshes until they are set."""
+        T = self.n_mesh_triangles
+        if features is None:
+            C = mesh_onehot_channels(self._mesh_groups, T, self.n_features)
+            self._check(self._L.sas_scene_mesh_features(self._ctx, T, C, None), "sas_scene_mesh_features")
+            self._mesh_features_onehot = True
+            return
+        C = mesh_feature_channels(features.shape, T, self.n_features)
+        f, pf = _as_f32(features, (T, C), "mesh features")
+        if isinstance(f, torch.Tensor) and f.is_cuda:
+            torch.cuda.synchronize(f.device)   # device-resident inputs must be complete before the copy
+        self._check(self._L.sas_scene_mesh_features(self._ctx, T, C, pf), "sas_scene_mesh_features")
+        self._mesh_features_onehot = False
 
     @_locked
     def set_group_poses(self, Rt: ArrayLike) -> None:
@@ -313,7 +374,7 @@ class Rasterizer:
     def render(self, viewmat: ArrayLike, K: ArrayLike, width: int, height: int,
                background: Sequence[float] = (0.0, 0.0, 0.0), *, want: Iterable[str] = ("rgb", "alpha", "depth"),
                depth_fill_max: bool = False, fast_exp: bool = False, timing: bool = False, block: bool = True,
-               full_sort: bool = False, time_tiles: bool = False,
+               full_sort: bool = False, time_tiles: bool = False, mesh_surface: bool = False,
                out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """Render one view; returns device tensors ``rgb [H,W,3]``, ``alpha [H,W,1]``,
         ``depth [H,W,1]`` (float32) and/or ``rgb8 [H,W,3]`` (uint8) as listed in ``want``.
@@ -322,7 +383,9 @@ class Rasterizer:
         submission order inside later ``render*`` calls or ``wait()``; a frame's outputs may be consumed
         (and work on the current stream is ordered behind it) only once it is complete --
         ``frames_completed()`` tells how many are.  ``full_sort=True`` orders every tile list
-        completely and keeps it for ``read_tile_lists`` (same image, slower)."""
+        completely and keeps it for ``read_tile_lists`` (same image, slower).  ``mesh_surface=True`` (SAS_MESH_SURFACE):
+        where a mesh triangle shows, ``alpha`` is 1 and ``depth`` closes on the triangle -- the scene's depth, not that of
+        the splats in front of the mesh; rgb and every other pixel keep their bits."""
         V, pV = self._host_arg(viewmat, 16)
         Kc, pK = self._host_arg(K, 9)
         bg, pbg = self._host_arg(background, 3)
@@ -340,7 +403,8 @@ class Rasterizer:
             ptrs[k] = t.data_ptr()
         flags = (_capi.SAS_DEPTH_FILL_MAX if depth_fill_max else 0) | (_capi.SAS_FAST_EXP if fast_exp else 0) | \
                 (_capi.SAS_TIMING if timing else 0) | (0 if block else _capi.SAS_ASYNC) | \
-                (_capi.SAS_FULL_SORT if full_sort else 0) | (_capi.SAS_TIME_TILES if time_tiles else 0)
+                (_capi.SAS_FULL_SORT if full_sort else 0) | (_capi.SAS_TIME_TILES if time_tiles else 0) | \
+                (_capi.SAS_MESH_SURFACE if mesh_surface else 0)
         stream = self._stream()
         rc = self._L.sas_render(self._ctx, pV, pK, W, H, pbg, flags,
                                 ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], stream)
@@ -352,10 +416,11 @@ class Rasterizer:
     @_locked
     def render_rgbd(self, viewmat: ArrayLike, K: ArrayLike, width: int, height: int,
                     background: Sequence[float] = (0.0, 0.0, 0.0), *, max_depth: Optional[float] = 1.0,
-                    depth_fill_max: bool = True) -> Dict[str, torch.Tensor]:
+                    depth_fill_max: bool = True, mesh_surface: bool = False) -> Dict[str, torch.Tensor]:
         """Render with the RGB-D consumer fused into the depth pass (sas_render_rgbd): besides
         ``rgb``/``alpha``/``depth`` returns ``points [H,W,3]`` (camera frame) and ``mask [H,W]``
-        (bool, ``depth < max_depth``; all true for ``max_depth=None``) -- nerfstudio_utils.py:424-445."""
+        (bool, ``depth < max_depth``; all true for ``max_depth=None``) -- nerfstudio_utils.py:424-445.
+        ``mesh_surface=True``: depth, points and mask include the meshes' surfaces (see ``render``)."""
         V = self._host_f32(viewmat, 16)
         Kc = self._host_f32(K, 9)
         bg = self._host_f32(background, 3)
@@ -365,7 +430,7 @@ class Rasterizer:
         res["points"] = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
         mask8 = torch.empty((H, W), dtype=torch.uint8, device=self.device)
         md = ctypes.c_float(max_depth) if max_depth is not None else None
-        flags = _capi.SAS_DEPTH_FILL_MAX if depth_fill_max else 0
+        flags = (_capi.SAS_DEPTH_FILL_MAX if depth_fill_max else 0) | (_capi.SAS_MESH_SURFACE if mesh_surface else 0)
         stream = self._stream()
         rc = self._L.sas_render_rgbd(self._ctx, V.ctypes.data, Kc.ctypes.data, W, H, bg.ctypes.data, flags,
                                      ctypes.addressof(md) if md is not None else None,
@@ -381,11 +446,14 @@ class Rasterizer:
     def render_features(self, viewmat: ArrayLike, K: ArrayLike, width: int, height: int,
                         background: Sequence[float] = (0.0, 0.0, 0.0), *, feature_background=None,
                         want: Iterable[str] = ("features",), fast_exp: bool = False, depth_fill_max: bool = False,
-                        block: bool = True, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                        block: bool = True, mesh_surface: bool = False,
+                        out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """Render one view with the feature channels of ``upload_features``: ``features [H,W,C]`` float32, not clamped,
         ``F = sum_i w_i f_i + (1 - alpha) feature_background`` with the frame's own weights w_i (``feature_background``:
         [C], default zeros), plus any of ``rgb`` / ``alpha`` / ``depth`` listed in ``want`` (bit-identical to ``render``).
-        ``block=False`` enqueues as ``render`` does."""
+        ``block=False`` enqueues as ``render`` does.  A scene with meshes needs ``upload_mesh_features``: the sum then
+        stops at the pixel's triangle, whose row stands in ``feature_background``'s place (the ``alpha`` of that formula is
+        the splats' whatever ``mesh_surface``, which only changes the alpha / depth outputs as in ``render``)."""
         C = self.n_features
         if C <= 0:
             raise SasError("render_features: no features uploaded for this scene (upload_features)")
@@ -409,7 +477,7 @@ class Rasterizer:
             res[k] = t
             ptrs[k] = t.data_ptr()
         flags = (_capi.SAS_DEPTH_FILL_MAX if depth_fill_max else 0) | (_capi.SAS_FAST_EXP if fast_exp else 0) | \
-                (0 if block else _capi.SAS_ASYNC)
+                (0 if block else _capi.SAS_ASYNC) | (_capi.SAS_MESH_SURFACE if mesh_surface else 0)
         rc = self._L.sas_render_features(self._ctx, pV, pK, W, H, pbg, fb.ctypes.data if fb is not None else None, flags,
                                          ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["features"], self._stream())
         if rc != 0:
@@ -420,12 +488,16 @@ class Rasterizer:
     @_locked
     def render_group_masks(self, viewmat: ArrayLike, K: ArrayLike, width: int, height: int, *,
                            min_alpha: float = 0.5) -> Dict[str, torch.Tensor]:
-        """Which splat group (robot link) each pixel shows: ``weights [H,W,G]`` (the one-hot group features composited, zero
+        """Which pose group (robot link, mesh) each pixel shows: ``weights [H,W,G]`` (the one-hot group features composited, zero
         background), ``labels [H,W]`` uint8 (``group_labels``: argmax, ties to the lowest id, 255 where alpha < min_alpha)
-        and ``alpha [H,W,1]``.  Selects the one-hot group store (replacing features uploaded before)."""
+        and ``alpha [H,W,1]``.  Selects the one-hot group store (replacing features uploaded before) for the Gaussians and,
+        when the scene holds meshes, for the triangles; ``alpha`` then counts a mesh as opaque (``mesh_surface``), so that
+        the weights still sum to it."""
         if not self._features_onehot:
             self.upload_features(None)
-        o = self.render_features(viewmat, K, width, height, want=("features", "alpha"))
+        if self.n_mesh_triangles > 0 and not self._mesh_features_onehot:
+            self.upload_mesh_features(None)
+        o = self.render_features(viewmat, K, width, height, want=("features", "alpha"), mesh_surface=self.n_mesh_triangles > 0)
         return {"weights": o["features"], "labels": group_labels(o["features"], o["alpha"], min_alpha), "alpha": o["alpha"]}
 
     def _pose_sets(self, pose_sets, pose_set, C: int):
@@ -442,7 +514,7 @@ class Rasterizer:
     @_locked
     def render_batch(self, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int,
                      background: Sequence[float] = (0.0, 0.0, 0.0), *, want: Iterable[str] = ("rgb",),
-                     depth_fill_max: bool = False, block: bool = True, time_tiles: bool = False,
+                     depth_fill_max: bool = False, block: bool = True, time_tiles: bool = False, mesh_surface: bool = False,
                      out: Optional[Dict[str, torch.Tensor]] = None, pose_sets: Optional[ArrayLike] = None,
                      pose_set: Optional[Sequence[int]] = None) -> Dict[str, torch.Tensor]:
         """Render C same-sized views in one C-ABI call: ``viewmats [C,4,4]``, ``Ks [C,3,3]`` ->
@@ -450,7 +522,7 @@ class Rasterizer:
         Views are projected two per pass over the scene.  ``block=False`` only enqueues (results valid
         after ``wait()``); ``out`` supplies the ``[C,H,W,...]`` output tensors.  ``pose_sets [S,G,12]`` +
         ``pose_set [C]``: view v is rendered with the group poses ``pose_sets[pose_set[v]]`` (vectorised envs:
-        sas_render_batch_posed)."""
+        sas_render_batch_posed).  ``mesh_surface``: as in ``render``."""
         C = int(np.asarray(viewmats).shape[0]) if not isinstance(viewmats, torch.Tensor) else int(viewmats.shape[0])
         V, pV = self._host_arg(viewmats, 16 * C)
         Kc, pK = self._host_arg(Ks, 9 * C)
@@ -468,7 +540,7 @@ class Rasterizer:
             res[k] = t
             ptrs[k] = t.data_ptr()
         flags = (_capi.SAS_DEPTH_FILL_MAX if depth_fill_max else 0) | (0 if block else _capi.SAS_ASYNC) | \
-                (_capi.SAS_TIME_TILES if time_tiles else 0)
+                (_capi.SAS_TIME_TILES if time_tiles else 0) | (_capi.SAS_MESH_SURFACE if mesh_surface else 0)
         stream = self._stream()
         if pose_sets is not None:
             Rt, idx = self._pose_sets(pose_sets, pose_set, C)

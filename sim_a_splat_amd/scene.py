@@ -315,11 +315,35 @@ class SplatScene:
             self._apply_link_constants(owner)
             return self._raster.link_attached_frame(q_link, p_link, local_xyz)
 
-    def get_render_float(self, height: int, width: int, wxyz, position, fov: Optional[float] = None) -> Dict[str, torch.Tensor]:
+    def get_render_float(self, height: int, width: int, wxyz, position, fov: Optional[float] = None,
+                         mesh_surface: bool = False) -> Dict[str, torch.Tensor]:
+        """float32 device tensors ``rgb`` / ``alpha`` / ``depth``; ``mesh_surface=True``: alpha and depth of the whole scene, the
+        meshes' surfaces included (``Rasterizer.render``)."""
         V, K = self._view_and_K(int(height), int(width), wxyz, position, self.camera.fov if fov is None else float(fov))
         with self.lock:
             self._sync()
-            return self._raster.render(V, K, int(width), int(height), self.background, want=("rgb", "alpha", "depth"))
+            return self._raster.render(V, K, int(width), int(height), self.background, want=("rgb", "alpha", "depth"),
+                                       mesh_surface=mesh_surface)
+
+    def row_names(self) -> List[str]:
+        """The handles' names by pose row: ``row_names()[label]`` names what a pixel of ``get_segmentation`` shows (splat groups
+        and meshes share one row numbering, in creation order)."""
+        with self.lock:
+            return [h.name for h in self._handles]
+
+    def get_segmentation(self, height: int, width: int, wxyz=None, position=None, fov: Optional[float] = None,
+                         min_alpha: float = 0.5) -> Dict[str, torch.Tensor]:
+        """Which handle each pixel shows (``Rasterizer.render_group_masks``): ``labels [H,W]`` uint8, the pose-row index of the
+        splat group or mesh (255: none, alpha < min_alpha), ``weights [H,W,rows]`` and ``alpha [H,W,1]`` (a mesh counts as
+        opaque).  Device tensors."""
+        wxyz = self.camera.wxyz if wxyz is None else wxyz
+        position = self.camera.position if position is None else position
+        V, K = self._view_and_K(int(height), int(width), wxyz, position, self.camera.fov if fov is None else float(fov))
+        with self.lock:
+            if not self._handles:
+                raise RuntimeError("get_segmentation needs at least one splat group or mesh")
+            self._sync()
+            return self._raster.render_group_masks(V, K, int(width), int(height), min_alpha=min_alpha)
 
     def close(self) -> None:
         with self.lock:
