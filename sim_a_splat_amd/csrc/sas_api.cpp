@@ -19,9 +19,31 @@
 
 namespace {
 
+// OWNERS.  What the context holds of the runtime (device memory, pinned blocks, streams, events) belongs to a move-only member that
+// gives it back in its destructor; a staging buffer is a local.  The four calls that give something back are written once, in these.
+template <class T, auto Free>
+struct Owned {
+    T h{};
+    Owned() = default;
+    Owned(Owned &&o) noexcept : h(o.h) { o.h = T{}; }
+    Owned &operator=(Owned &&o) noexcept { std::swap(h, o.h); return *this; }
+    ~Owned() { if (h) (void)Free(h); }
+    T *put() { return &h; }   // (of an empty owner: for the runtime's create calls)
+    operator T() const { return h; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+template <class T> using Pinned = Owned<T *, hipHostFree>;
+
+// Device memory that only ever grows (ensure) unless it is given back on purpose (release).
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    ~DevBuf() { (void)release(); }
+    int release(sas_ctx *c = nullptr);   // (behind HIP_TRY; c: where a failure is reported)
 };
 
 // Where one view's images go: device buffers of the caller, except rgb8_host.  A view carries them from the C ABI to
@@ -68,6 +90,14 @@ struct Scratch {
     bool counters_zero = false;   // the counter block is known to be all zero (SasFrame invariant)
 };
 
+// Mesh scratch of a slot's frame (SasMeshFrame), when the context holds meshes.
+struct MeshScratch {
+    DevBuf rec, rect, tiles, list;   // records, rectangles, [count | offset | cursor], lists
+    DevBuf win;                      // feature frames: every pixel's triangle as k_blend_mesh_scene resolved it (SasMeshExtra::win)
+    long long cap = 0;               // entries `list` holds (grown like the splat keys when a frame outgrows it)
+    Pinned<unsigned> status_host;    // [2], written by k_mesh_scan
+};
+
 // One in-flight frame.  Each slot has its own internal stream (plus two side streams for the
 // concurrent sort classes) and its own scratch: the stages of a frame are each too short on
 // parallelism to fill 256 CUs (a few thousand tiles), so consecutive frames overlap on the chip.
@@ -82,28 +112,49 @@ struct Scratch {
 // no memset, no upload and no read-back copy around a frame.
 struct Slot {
     RenderArgs args;
-    hipStream_t fs = nullptr;
+    Stream fs, side[2];              // the frame's stream; the side streams of the concurrent sort classes
+    Event fork, join[2];             // ... and their events: sort_streams names all five for sas_launch_sort
     SasSortStreams sort_streams{};
-    hipEvent_t start = nullptr, done = nullptr;
-    hipEvent_t pair_ev = nullptr;   // leader of a view pair: both projections are done
-    hipEvent_t ev[SAS_T_COUNT + 1] = {};
-    unsigned *stats_host = nullptr;  // pinned, 8 words, written by the projection's tail (SasFrame::stats_host)
-    float *poses_host = nullptr;     // pinned [256 * 12]: the group poses this slot's frame was submitted with
+    Event start, done, pair_ev;      // pair_ev: leader of a view pair: both projections are done
+    Event ev[SAS_T_COUNT + 1];
+    Pinned<unsigned> stats_host;     // 8 words, written by the projection's tail (SasFrame::stats_host)
+    Pinned<float> poses_host;        // [256 * 12]: the group poses this slot's frame was submitted with
     DevBuf poses_dev;                // ... and their device copy, uploaded in front of the projection
     Scratch scr;
+    MeshScratch msc;
     SasCam cam{};
     SasParams params{};
     bool busy = false, timed = false, timed_tiles = false;
     bool quad = false;   // the frame runs in the quad layout: projected, binned and composited in 8-pixel tiles (prepare_frame)
-    bool mesh = false;   // the frame composites the context's meshes (enqueue_chain): mesh_host tells whether its lists fit
-    DevBuf mrec, mrect, mtiles, mlist;   // its mesh scratch (SasMeshFrame): records, rectangles, [count | offset | cursor], lists
-    DevBuf mwin;                         // feature frames: every pixel's triangle as k_blend_mesh_scene resolved it (SasMeshExtra::win)
-    long long mcap = 0;                  // entries mlist holds (grown like the splat keys when a frame outgrows it)
-    unsigned *mesh_host = nullptr;       // pinned [2], written by k_mesh_scan
+    bool mesh = false;   // the frame composites the context's meshes (enqueue_chain): msc.status_host tells whether its lists fit
     bool direct = false; // single-pass binning (SasFrame::seg > 0): the projection emits the keys, no scatter launch (choose_binning)
     bool host_direct = false;   // the tile kernel delivers the uint8 frame to pinned host memory itself (host_direct_ok)
     bool info_kept = false;     // the frame's projection wrote info[] (SasFrame::keep_info): sas_read_projection need not project again
     int group = 1;   // slots of the launch group this slot LEADS (enqueue_chain); 0: member of the group led by an earlier slot
+    // The slot's streams, events and pinned words (zeroed).  On failure the slot keeps what it got: its destructor gives it back.
+    // (The order of creation is the one this code always had; whether it matters is open: profiles/host_owners_ab.txt, call C.)
+    hipError_t init()
+    {
+        hipError_t e = hipSuccess;
+        auto pinned = [&](auto &b, size_t count) {
+            if (e == hipSuccess) e = hipHostMalloc((void **)b.put(), count * sizeof(*b.h));
+            if (e == hipSuccess) memset(b.h, 0, count * sizeof(*b.h));
+        };
+        auto stream = [&](Stream &s) { if (e == hipSuccess) e = hipStreamCreateWithFlags(s.put(), hipStreamNonBlocking); };
+        auto event = [&](Event &v, bool timing) {
+            if (e == hipSuccess) e = timing ? hipEventCreate(v.put()) : hipEventCreateWithFlags(v.put(), hipEventDisableTiming);
+        };
+        pinned(stats_host, 8);
+        pinned(poses_host, 12 * 256);
+        pinned(msc.status_host, 2);
+        stream(fs);
+        for (Event *v : {&start, &done, &pair_ev}) event(*v, false);
+        for (Event &v : ev) event(v, true);
+        for (Stream &s : side) stream(s);
+        for (Event *v : {&fork, &join[0], &join[1]}) event(*v, false);
+        sort_streams = SasSortStreams{{side[0], side[1]}, fork, {join[0], join[1]}};
+        return e;
+    }
 };
 
 constexpr int kMaxSlots = 8;
@@ -116,42 +167,12 @@ struct LinkConsts {
     std::vector<int> group;         // [n] splat group driven by link k
 };
 
-struct sas_ctx {
-    int device = 0;
-    std::string err;
-    // scene
-    DevBuf g0, g1, g2, col, gid8, perm;
-    DevBuf feat;         // feature store (sas_scene_features): [chunks][n_pad][SAS_FEAT_K], slot order
-    int feat_c = 0;      // its channels; has_feat: set for the current scene (an upload forgets it)
-    bool has_feat = false;
-    DevBuf mesh_vert, mesh_tri, mesh_col;   // meshes (sas_scene_meshes): float4 vertices, int4 (i0, i1, i2, group), float4 colours
-    SasMeshScene mesh{};
-    bool has_mesh = false;   // set for the current scene (an upload forgets the meshes)
-    DevBuf mesh_feat;        // per-triangle feature rows (sas_scene_mesh_features): [chunks][nt][SAS_FEAT_K], feat_c channels
-    bool has_mesh_feat = false;   // set for the current meshes and feature store (an upload, sas_scene_meshes and sas_scene_features forget them)
-    DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
-    // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
-    // the call returns: nothing is remembered across calls)
-    const uint8_t *host_query_base = nullptr, *host_query_end = nullptr;
-    bool host_query_ok = false;
-    std::vector<int> perm_host;
-    SasScene scene{};
-    bool has_scene = false;
-    std::vector<float> group_host;    // [n_groups * 12] current poses: what a frame submitted now is rendered with
-    LinkConsts links;
-    // frames
-    Slot slots[kMaxSlots];
+// What the environment settles for a context, read once when it is created (from_env: the only getenv calls of this file).
+struct Settings {
     int n_slots = 4;     // frames that may be enqueued (SAS_SLOTS=1..8; 6 and 8 are slower)
-    int head = 0;        // oldest busy slot
-    int inflight = 0;
-    int last_slot = 0;   // most recently enqueued (parity hooks)
-    hipStream_t stream = nullptr;   // caller's stream of the in-flight frames
-    bool has_frame = false;
     // sas_render_batch projects two views per pass over the scene when that pass is long enough to pay
     // (measured: +5 % frames/s at 1 M Gaussians, +16 % at 5 M, -5 % at 0.3 M).  SAS_PAIR=0/1 forces it.
     int pair_views = -1;            // -1: by scene size
-    // quad layout (the frame binned in 8-pixel tiles, one workgroup per 8x8 quadrant): -1 = for views of at most
-    // quad_max_tiles 16-pixel tiles, 0 = never, 1 = always (SAS_QUAD, SAS_QUAD_TILES)
     // single-pass binning (fixed-stride tile segments, the projection emits the keys): -1 = whenever the segments fit
     // direct_budget bytes per CONTEXT (all its frame slots together: a slot's keys + ids may take direct_budget / n_slots), 0 =
     // never (SAS_DIRECT=0: the two-pass path of rounds 1-3).  24 GB: config 5's 6.4 GB per slot; of 288 GB of HBM
@@ -160,12 +181,67 @@ struct sas_ctx {
     // exact tile culling on single-pass frames (sas_kernels.hip: tile_reached); SAS_CULL=0 bins whole rectangles as T3 does
     int cull_mode = 1;
     int seg_guess_factor = 16;    // first guess of a tile segment = this x the mean list of a frame with five intersections per Gaussian (SAS_SEG_FACTOR)
+    // quad layout (the frame binned in 8-pixel tiles, one workgroup per 8x8 quadrant): -1 = for views of at most
+    // quad_max_tiles 16-pixel tiles, 0 = never, 1 = always (SAS_QUAD, SAS_QUAD_TILES)
     int quad_mode = -1;
     int quad_max_tiles = 640;        // views of frames that share the chip (SAS_ASYNC, batches): beyond, the layout's 4 x workgroups lose
     int quad_max_tiles_solo = 960;   // one blocking view alone on the GPU: its heaviest tile's chain is the frame (tools/quad_threshold.py)
     // sas_render_batch renders the views of a SMALL scene (< kPairMinGaussians: launch-bound frames, the Gym
     // cameras) in groups that share one set of launches (grid.y = view).  SAS_GROUP=1 disables, 2..4 sets the size.
     int group_views = -1;           // -1: half of the slots (two groups can be in flight)
+    // nothing in flight: the ring restarts at slot 0, so that a sequence of frames always meets the slots in the same order
+    // (SAS_RING_RESTART=0: the ring goes on where it stood -- bench passes of 25 steps then start on alternating slot pairs)
+    bool ring_restart = true;
+    static Settings from_env()
+    {
+        Settings s;
+        auto num = [](const char *name, long long &v) { const char *e = getenv(name); if (e) v = atoll(e); return e != nullptr; };
+        long long v = 0;
+        if (num("SAS_SLOTS", v) && v >= 1 && v <= kMaxSlots) s.n_slots = (int)v;
+        if (num("SAS_PAIR", v)) s.pair_views = v != 0 ? 1 : 0;
+        if (num("SAS_GROUP", v) && v >= 1 && v <= SAS_MAX_GROUP) s.group_views = (int)v;
+        if (num("SAS_QUAD", v)) s.quad_mode = v != 0 ? 1 : 0;
+        if (num("SAS_DIRECT", v)) s.direct_mode = v != 0 ? -1 : 0;
+        if (num("SAS_CULL", v)) s.cull_mode = v != 0;
+        if (num("SAS_SEG_FACTOR", v)) s.seg_guess_factor = (int)std::max(1ll, v);
+        if (num("SAS_DIRECT_BUDGET_MB", v)) s.direct_budget = std::max(1ll, v) << 20;
+        if (num("SAS_QUAD_TILES", v) && v >= 0) s.quad_max_tiles = s.quad_max_tiles_solo = (int)v;
+        if (num("SAS_RING_RESTART", v)) s.ring_restart = v != 0;
+        return s;
+    }
+};
+
+// What the context stores (sas_ctx::have).  Features and meshes sit beside a scene, mesh features beside both: forget() drops a
+// store together with what sits beside it, and is the only place a bit is cleared; each store has one line that sets its bit.
+enum : unsigned { HAVE_SCENE = 1, HAVE_FEAT = 2, HAVE_MESH = 4, HAVE_MESH_FEAT = 8 };
+
+struct sas_ctx : Settings {
+    int device = 0;
+    std::string err;
+    // scene
+    DevBuf g0, g1, g2, col, gid8, perm;
+    DevBuf feat;         // feature store (sas_scene_features): [chunks][n_pad][SAS_FEAT_K], slot order
+    int feat_c = 0;      // its channels
+    DevBuf mesh_vert, mesh_tri, mesh_col;   // meshes (sas_scene_meshes): float4 vertices, int4 (i0, i1, i2, group), float4 colours
+    SasMeshScene mesh{};
+    DevBuf mesh_feat;        // per-triangle feature rows (sas_scene_mesh_features): [chunks][nt][SAS_FEAT_K], feat_c channels
+    DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
+    // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
+    // the call returns: nothing is remembered across calls)
+    const uint8_t *host_query_base = nullptr, *host_query_end = nullptr;
+    bool host_query_ok = false;
+    std::vector<int> perm_host;
+    SasScene scene{};
+    unsigned have = 0;   // HAVE_*: the stores that are valid
+    std::vector<float> group_host;    // [n_groups * 12] current poses: what a frame submitted now is rendered with
+    LinkConsts links;
+    // frames
+    Slot slots[kMaxSlots];
+    int head = 0;        // oldest busy slot
+    int inflight = 0;
+    int last_slot = 0;   // most recently enqueued (parity hooks)
+    hipStream_t stream = nullptr;   // caller's stream of the in-flight frames
+    bool has_frame = false;
     static constexpr int64_t kPairMinGaussians = 500000;
     uint64_t scene_version = 0;
     int64_t frames_submitted = 0, frames_completed = 0;   // sas_frames_completed
@@ -175,7 +251,6 @@ struct sas_ctx {
     double stage_sum[SAS_T_COUNT] = {0, 0, 0, 0, 0, 0, 0};
     int64_t stage_frames = 0;
 };
-
 
 namespace {
 
@@ -190,6 +265,15 @@ int fail(sas_ctx *c, int code, const char *fmt, ...)
     return code;
 }
 
+bool has(const sas_ctx *c, unsigned stores) { return (c->have & stores) == stores; }
+
+void forget(sas_ctx *c, unsigned stores)
+{
+    if (stores & HAVE_SCENE) stores |= HAVE_FEAT | HAVE_MESH;
+    if (stores & (HAVE_FEAT | HAVE_MESH)) stores |= HAVE_MESH_FEAT;
+    c->have &= ~stores;
+}
+
 #define HIP_TRY(ctx, expr)                                                                         \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
@@ -198,25 +282,24 @@ int fail(sas_ctx *c, int code, const char *fmt, ...)
                         hipGetErrorString(e_));                                                    \
     } while (0)
 
+// (a failure reads "<the call>(b.p): ..." and leaves the buffer as it was, as it always did in ensure)
+int DevBuf::release(sas_ctx *c)
+{
+    DevBuf &b = *this;
+    if (b.p) HIP_TRY(c, hipFree(b.p));
+    b.p = nullptr;
+    b.bytes = 0;
+    return SAS_OK;
+}
+
 int ensure(sas_ctx *c, DevBuf &b, size_t bytes)
 {
     if (bytes <= b.bytes && b.p) return SAS_OK;
-    if (b.p) {
-        HIP_TRY(c, hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
-    }
+    if (const int rc = b.release(c)) return rc;
     if (bytes == 0) bytes = 16;
     HIP_TRY(c, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
     return SAS_OK;
-}
-
-void release(DevBuf &b)
-{
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
 }
 
 // 3-D Hilbert index (Skilling's transpose form), `bits` per axis.  Storage order of the scene:
@@ -350,7 +433,7 @@ SasFrame frame_of(sas_ctx *c, Slot &sl, bool keep_info = false)
     f.wg_isect16 = (sl.quad || f.cull) ? (int *)q.wgvis.p + f_wg_stride(c) : nullptr;   // the lists are not T3's: T3's count is kept beside them
     f.tile_max = (unsigned *)q.tilemax.p;
     f.group_Rt = c->scene.n_groups > 0 ? (const float *)sl.poses_dev.p : nullptr;
-    f.group_host = c->scene.n_groups > 0 ? sl.poses_host : nullptr;
+    f.group_host = c->scene.n_groups > 0 ? sl.poses_host.h : nullptr;
     f.n_wg = (int)std::max<int64_t>(1, (c->scene.n + 255) / 256);
     f.n_tiles = tiles;
     return f;
@@ -358,7 +441,7 @@ SasFrame frame_of(sas_ctx *c, Slot &sl, bool keep_info = false)
 
 // A context that holds meshes renders SAS_FULL_SORT frames: the meshes are composited by the full path's k_blend_mesh
 // (sas_scene_meshes), one view per frame.
-unsigned frame_flags(const sas_ctx *c, unsigned flags) { return c->has_mesh ? flags | SAS_FULL_SORT : flags; }
+unsigned frame_flags(const sas_ctx *c, unsigned flags) { return has(c, HAVE_MESH) ? flags | SAS_FULL_SORT : flags; }
 
 // quad layout for views of `launch_tiles` tiles each?  By the view's own size: counting the frames in
 // flight as well measured worse -- 32 Gym cameras per step in launch groups of two run 30 % faster in the quad
@@ -464,7 +547,7 @@ int ensure_keys(sas_ctx *c, Slot &sl)
     Scratch &q = sl.scr;
     // buffers sized for a much larger frame (or for segments the slot has since given up) go back to the allocator:
     // several contexts share a card (vectorised ranks, torch), and ensure() by itself only ever grows
-    if (q.keys.bytes > 4 * sizeof(unsigned long long) * key_slots(sl) && q.keys.bytes > (256u << 20)) { release(q.keys); release(q.ids); }
+    if (q.keys.bytes > 4 * sizeof(unsigned long long) * key_slots(sl) && q.keys.bytes > (256u << 20)) { (void)q.keys.release(); (void)q.ids.release(); }
     auto alloc = [&]() {
         const int rc = ensure(c, q.keys, sizeof(unsigned long long) * key_slots(sl));
         return rc ? rc : ensure(c, q.ids, sizeof(int) * key_slots(sl));
@@ -474,8 +557,8 @@ int ensure_keys(sas_ctx *c, Slot &sl)
         // (whatever of the segment-sized pair was allocated is released: the compact lists take a fraction of it)
         (void)hipGetLastError();
         c->err.clear();
-        release(q.keys);
-        release(q.ids);
+        (void)q.keys.release();
+        (void)q.ids.release();
         sl.direct = false;
         q.seg_too_big = true;
     }
@@ -546,32 +629,32 @@ int prepare_frame(sas_ctx *c, Slot &sl, hipStream_t init_st)
 
 // Mesh scratch of the slot's frame: 2 records per triangle, the tile counts / offsets / cursors, the lists (first guess: four
 // tiles per record; a frame whose lists outgrow it is rendered again with the measured need, as for the splat keys).
-int prepare_mesh(sas_ctx *c, Slot &sl)
+int prepare_mesh(sas_ctx *c, MeshScratch &m, int tiles, size_t feature_pixels)
 {
     const size_t nrec = 2 * (size_t)c->mesh.nt;
     int rc;
-    if (sl.mcap == 0) sl.mcap = std::max<long long>(1 << 16, 4 * (long long)nrec);
-    if ((rc = ensure(c, sl.mrec, sizeof(float4) * 4 * nrec))) return rc;
-    if ((rc = ensure(c, sl.mrect, sizeof(int4) * nrec))) return rc;
-    if ((rc = ensure(c, sl.mtiles, sizeof(int) * (3 * sas_tile_stride(tiles_of(sl)) + 16)))) return rc;
-    if (sl.args.out.features && (rc = ensure(c, sl.mwin, sizeof(unsigned long long) * (size_t)sl.args.W * (size_t)sl.args.H))) return rc;
-    return ensure(c, sl.mlist, sizeof(int) * (size_t)sl.mcap);
+    if (m.cap == 0) m.cap = std::max<long long>(1 << 16, 4 * (long long)nrec);
+    if ((rc = ensure(c, m.rec, sizeof(float4) * 4 * nrec))) return rc;
+    if ((rc = ensure(c, m.rect, sizeof(int4) * nrec))) return rc;
+    if ((rc = ensure(c, m.tiles, sizeof(int) * (3 * sas_tile_stride(tiles) + 16)))) return rc;
+    if (feature_pixels && (rc = ensure(c, m.win, sizeof(unsigned long long) * feature_pixels))) return rc;
+    return ensure(c, m.list, sizeof(int) * (size_t)m.cap);
 }
 
-SasMeshFrame mesh_frame_of(sas_ctx *c, Slot &sl)
+SasMeshFrame mesh_frame_of(const sas_ctx *c, const MeshScratch &m, int tiles)
 {
-    const size_t ts = sas_tile_stride(tiles_of(sl));
-    SasMeshFrame m{};
-    m.rec = (float4 *)sl.mrec.p;
-    m.rect = (int4 *)sl.mrect.p;
-    m.tile_count = (int *)sl.mtiles.p;
-    m.tile_offset = (int *)sl.mtiles.p + ts;
-    m.tile_cursor = (int *)sl.mtiles.p + 2 * ts;
-    m.list = (int *)sl.mlist.p;
-    m.cap = sl.mcap;
-    m.n_rec = 2 * c->mesh.nt;
-    m.status_host = sl.mesh_host;
-    return m;
+    const size_t ts = sas_tile_stride(tiles);
+    SasMeshFrame mf{};
+    mf.rec = (float4 *)m.rec.p;
+    mf.rect = (int4 *)m.rect.p;
+    mf.tile_count = (int *)m.tiles.p;
+    mf.tile_offset = (int *)m.tiles.p + ts;
+    mf.tile_cursor = (int *)m.tiles.p + 2 * ts;
+    mf.list = (int *)m.list.p;
+    mf.cap = m.cap;
+    mf.n_rec = 2 * c->mesh.nt;
+    mf.status_host = m.status_host;
+    return mf;
 }
 
 SasFeatures features_of(const sas_ctx *c, const RenderArgs &a)
@@ -631,7 +714,7 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
         fr[k] = frame_of(c, *sl[k]);
         writes_caller = writes_caller || sl[k]->args.order_caller;
         any_fill = any_fill || (sl[k]->args.out.depth && (a.flags & SAS_DEPTH_FILL_MAX));
-        sl[k]->mesh = full && c->has_mesh && c->mesh.nt > 0;   // a frame with meshes: always SAS_FULL_SORT, a view of its own
+        sl[k]->mesh = full && has(c, HAVE_MESH) && c->mesh.nt > 0;   // a frame with meshes: always SAS_FULL_SORT, a view of its own
     }
     const SasFrame &f = fr[0];
     const SasParams &P = ld.params;
@@ -653,7 +736,7 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
     if (order) HIP_TRY(c, hipEventRecord(ld.start, a.stream));
     if (timing) HIP_TRY(c, hipStreamWaitEvent(st, ld.start, 0));
 
-    if (ld.mesh && (rc = prepare_mesh(c, ld))) return rc;
+    if (ld.mesh && (rc = prepare_mesh(c, ld.msc, tiles, a.out.features ? (size_t)a.W * (size_t)a.H : 0))) return rc;
     if (leader) {
         HIP_TRY(c, hipStreamWaitEvent(st, leader->pair_ev, 0));   // projected by the leader's pass
     } else {
@@ -684,9 +767,9 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
     if (timing) HIP_TRY(c, hipEventRecord(ld.ev[4], st));
     hipEvent_t tile_ev[2] = {ttiles ? ld.ev[4] : nullptr, ttiles ? ld.ev[5] : nullptr};
     if (ld.mesh) {
-        const SasMeshFrame mesh = mesh_frame_of(c, ld);
+        const SasMeshFrame mesh = mesh_frame_of(c, ld.msc, tiles);
         sas_launch_mesh_bin(st, c->mesh, P, f, mesh);
-        const SasMeshExtra extra{a.out.features ? (unsigned long long *)ld.mwin.p : nullptr, (a.flags & SAS_MESH_SURFACE) != 0};
+        const SasMeshExtra extra{a.out.features ? (unsigned long long *)ld.msc.win.p : nullptr, (a.flags & SAS_MESH_SURFACE) != 0};
         sas_launch_blend_mesh(st, c->scene, tiles, P, f, mesh, extra, fast_exp, any_fill);
         if (a.out.features) {   // ... in front of the triangles the blend kernel has just resolved (extra.win)
             const SasMeshFeatures MF{extra.win, (const float *)c->mesh_feat.p, c->mesh.nt};
@@ -764,7 +847,7 @@ bool read_stats(sas_ctx *c, Slot *const *mem, int g)
         c->stats[SAS_S_FALLBACK_TILES] = s[6];
         c->stats[SAS_S_QUAD_LAYOUT] = mem[k]->quad ? 1 : 0;
         c->stats[SAS_S_LAUNCH_VIEWS] = g;
-        overflow = overflow || s[2] != 0 || (mem[k]->mesh && mem[k]->mesh_host[1] != 0);
+        overflow = overflow || s[2] != 0 || (mem[k]->mesh && mem[k]->msc.status_host[1] != 0);
     }
     return overflow;
 }
@@ -791,8 +874,8 @@ void grow_scratch(sas_ctx *c, Slot *const *mem, int g)
 {
     long long want = 0, want_seg = 0;
     for (int k = 0; k < g; ++k) {
-        if (mem[k]->mesh && mem[k]->mesh_host[1] != 0)
-            mem[k]->mcap = std::max(mem[k]->mcap, grown((long long)mem[k]->mesh_host[0], 1024));
+        MeshScratch &m = mem[k]->msc;
+        if (mem[k]->mesh && m.status_host[1] != 0) m.cap = std::max(m.cap, grown((long long)m.status_host[0], 1024));
         want = std::max(want, grown((long long)mem[k]->stats_host[1], 1024));
         if (mem[k]->direct) {   // single-pass binning: the longest list, as a power of two
             long long s2 = mem[k]->scr.seg;
@@ -850,10 +933,42 @@ int complete_oldest(sas_ctx *c)
 
 int complete_all(sas_ctx *c)
 {
-    while (c->inflight > 0) {
-        int rc = complete_oldest(c);
-        if (rc) return rc;
-    }
+    while (c->inflight > 0)
+        if (const int rc = complete_oldest(c)) return rc;
+    return SAS_OK;
+}
+
+// A caller's `count` floats where a kernel can read them: in place when device memory of this context's device, else copied into `stage`.
+int device_floats(sas_ctx *c, const float *p, size_t count, DevBuf &stage, const float **out)
+{
+    hipPointerAttribute_t at{};
+    const bool on_device = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
+    (void)hipGetLastError();   // (a plain host pointer leaves an error behind on some runtimes)
+    *out = p;
+    if (on_device) return SAS_OK;
+    if (const int rc = ensure(c, stage, sizeof(float) * count)) return rc;
+    const hipError_t e = hipMemcpy(stage.p, p, sizeof(float) * count, hipMemcpyDefault);
+    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "feature copy: %s", hipGetErrorString(e));
+    *out = (const float *)stage.p;
+    return SAS_OK;
+}
+
+// sas_scene_features / sas_scene_mesh_features once validated and with no frame in flight: size the store ([chunks][stride][SAS_FEAT_K]),
+// bring the caller's rows to the device (nullptr: one-hot), launch on the context's own, idle stream (slot 0's) and wait for it alone.
+template <class Launch>
+int fill_feature_store(sas_ctx *c, DevBuf &store, size_t stride, int channels, const float *rows, size_t n_rows, const char *what,
+                       Launch launch)
+{
+    int rc;
+    if ((rc = ensure(c, store, sizeof(float) * SAS_FEAT_K * (size_t)sas_feature_chunks(channels) * stride))) return rc;
+    const float *src = nullptr;
+    DevBuf stage;
+    if (rows && n_rows > 0 && (rc = device_floats(c, rows, n_rows * (size_t)channels, stage, &src))) return rc;
+    hipStream_t st = c->slots[0].fs;
+    launch(st, src, (float *)store.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     return SAS_OK;
 }
 
@@ -873,42 +988,11 @@ int sas_create(int device, sas_ctx **out)
     sas_ctx *c = new (std::nothrow) sas_ctx();
     if (!c) return SAS_ERR_OOM;
     c->device = device;
+    static_cast<Settings &>(*c) = Settings::from_env();
     bool ok = hipSetDevice(device) == hipSuccess;
-    if (const char *e = getenv("SAS_SLOTS")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= kMaxSlots) c->n_slots = v;
-    }
-    if (const char *e = getenv("SAS_PAIR")) c->pair_views = atoi(e) != 0 ? 1 : 0;
-    if (const char *e = getenv("SAS_GROUP")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= SAS_MAX_GROUP) c->group_views = v;
-    }
-    if (const char *e = getenv("SAS_QUAD")) c->quad_mode = atoi(e) != 0 ? 1 : 0;
-    if (const char *e = getenv("SAS_DIRECT")) c->direct_mode = atoi(e) != 0 ? -1 : 0;
-    if (const char *e = getenv("SAS_CULL")) c->cull_mode = atoi(e) != 0;
-    if (const char *e = getenv("SAS_SEG_FACTOR")) c->seg_guess_factor = std::max(1, atoi(e));
-    if (const char *e = getenv("SAS_DIRECT_BUDGET_MB")) c->direct_budget = std::max(1ll, atoll(e)) << 20;
-    if (const char *e = getenv("SAS_QUAD_TILES")) {
-        const int v = atoi(e);
-        if (v >= 0) c->quad_max_tiles = c->quad_max_tiles_solo = v;
-    }
-    for (Slot &sl : c->slots) {
-        ok = ok && hipHostMalloc((void **)&sl.stats_host, 8 * sizeof(unsigned)) == hipSuccess;
-        ok = ok && hipHostMalloc((void **)&sl.poses_host, sizeof(float) * 12 * 256) == hipSuccess;
-        ok = ok && hipHostMalloc((void **)&sl.mesh_host, 2 * sizeof(unsigned)) == hipSuccess;
-        ok = ok && hipStreamCreateWithFlags(&sl.fs, hipStreamNonBlocking) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&sl.start, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&sl.pair_ev, hipEventDisableTiming) == hipSuccess;
-        for (auto &e : sl.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-        for (auto &sd : sl.sort_streams.side) ok = ok && hipStreamCreateWithFlags(&sd, hipStreamNonBlocking) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&sl.sort_streams.fork, hipEventDisableTiming) == hipSuccess;
-        for (auto &e : sl.sort_streams.join) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-        if (ok) memset(sl.stats_host, 0, 8 * sizeof(unsigned));
-        if (ok) memset(sl.mesh_host, 0, 2 * sizeof(unsigned));
-    }
+    for (Slot &sl : c->slots) ok = ok && sl.init() == hipSuccess;
     if (!ok) {
-        sas_destroy(c);
+        delete c;
         return SAS_ERR_HIP;
     }
     *out = c;
@@ -919,30 +1003,9 @@ int sas_destroy(sas_ctx *c)
 {
     if (!c) return SAS_ERR_INVALID;
     (void)hipSetDevice(c->device);
-    for (Slot &sl : c->slots) {
-        if (sl.fs) (void)hipStreamSynchronize(sl.fs);
-        for (auto &sd : sl.sort_streams.side)
-            if (sd) { (void)hipStreamSynchronize(sd); (void)hipStreamDestroy(sd); }
-        if (sl.sort_streams.fork) (void)hipEventDestroy(sl.sort_streams.fork);
-        for (auto &e : sl.sort_streams.join)
-            if (e) (void)hipEventDestroy(e);
-        if (sl.fs) (void)hipStreamDestroy(sl.fs);
-        if (sl.stats_host) (void)hipHostFree(sl.stats_host);
-        if (sl.poses_host) (void)hipHostFree(sl.poses_host);
-        if (sl.mesh_host) (void)hipHostFree(sl.mesh_host);
-        release(sl.poses_dev);
-        if (sl.start) (void)hipEventDestroy(sl.start);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.pair_ev) (void)hipEventDestroy(sl.pair_ev);
-        for (auto &e : sl.ev)
-            if (e) (void)hipEventDestroy(e);
-        for (DevBuf *b : {&sl.scr.rec, &sl.scr.col, &sl.scr.info, &sl.scr.tilebuf, &sl.scr.keys, &sl.scr.ids, &sl.scr.counters,
-                          &sl.scr.wgvis, &sl.scr.wgbase, &sl.scr.tilemax, &sl.mrec, &sl.mrect, &sl.mtiles, &sl.mlist, &sl.mwin})
-            release(*b);
-    }
-    for (DevBuf *b : {&c->g0, &c->g1, &c->g2, &c->col, &c->gid8, &c->perm, &c->host_stage, &c->feat, &c->mesh_vert, &c->mesh_tri,
-                      &c->mesh_col, &c->mesh_feat})
-        release(*b);
+    for (Slot &sl : c->slots)   // frames may still be in flight: nothing is given back under them
+        for (hipStream_t st : {(hipStream_t)sl.fs, (hipStream_t)sl.side[0], (hipStream_t)sl.side[1]})
+            if (st) (void)hipStreamSynchronize(st);
     delete c;
     return SAS_OK;
 }
@@ -962,14 +1025,8 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
     if (n_groups < 0 || n_groups > 256) return fail(c, SAS_ERR_INVALID, "n_groups %d out of [0,256]", n_groups);
     if (group_id && n_groups <= 0) return fail(c, SAS_ERR_INVALID, "group_id given but n_groups == 0");
     HIP_TRY(c, hipSetDevice(c->device));
-    {
-        int rcw = complete_all(c);
-        if (rcw) return rcw;
-    }
-    c->has_scene = false;
-    c->has_feat = false;
-    c->has_mesh = false;
-    c->has_mesh_feat = false;
+    if (const int rc = complete_all(c)) return rc;
+    forget(c, HAVE_SCENE);
 
     const int deg = sh_degree < 0 ? -1 : sh_degree;
     const int coeff_floats = deg < 0 ? 3 : 3 * (deg + 1) * (deg + 1);
@@ -1002,8 +1059,7 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
         // stage the caller's arrays (host or device) and re-lay them out on the device
         DevBuf s_means, s_q, s_s, s_cov, s_op, s_col, s_gid;
         auto stage = [&](DevBuf &b, const void *src, size_t bytes) -> int {
-            int r = ensure(c, b, bytes);
-            if (r) return r;
+            if (const int rc = ensure(c, b, bytes)) return rc;
             HIP_TRY(c, hipMemcpy(b.p, src, bytes, hipMemcpyDefault));
             return SAS_OK;
         };
@@ -1023,7 +1079,6 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
             hipError_t e = hipDeviceSynchronize();
             if (e != hipSuccess) rc = fail(c, SAS_ERR_HIP, "relayout: %s", hipGetErrorString(e));
         }
-        for (DevBuf *b : {&s_means, &s_q, &s_s, &s_cov, &s_op, &s_col, &s_gid}) release(*b);
         if (rc) return rc;
     }
 
@@ -1048,14 +1103,14 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
     for (Slot &sl : c->slots) sl.scr.cap = 0;  // re-derive the intersection capacity for the new scene
     c->has_frame = false;
     c->scene_version++;
-    c->has_scene = true;
+    c->have |= HAVE_SCENE;
     return SAS_OK;
 }
 
 int sas_set_group_poses(sas_ctx *c, int n_groups, const float *Rt)
 {
     if (!c || !Rt) return SAS_ERR_INVALID;
-    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
     if (n_groups != c->scene.n_groups) return fail(c, SAS_ERR_INVALID, "scene has %d groups, got %d", c->scene.n_groups, n_groups);
     // Every frame carries a snapshot of the poses it was submitted with (its slot's block, uploaded in front of its
     // projection; kept for the case that it has to be rendered again), so frames in flight are not disturbed and
@@ -1121,7 +1176,7 @@ int sas_set_link_constants(sas_ctx *c, int n_links, double scale, const double *
                            const double *tfk, const double *weld, const int *group)
 {
     if (!c) return SAS_ERR_INVALID;
-    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
     if (n_links < 0 || n_links > c->scene.n_groups) return fail(c, SAS_ERR_INVALID, "n_links %d out of [0, %d groups]", n_links, c->scene.n_groups);
     if (n_links > 0 && (!Ri || !ti || !Rfk || !tfk)) return fail(c, SAS_ERR_INVALID, "Ri, ti, Rfk, tfk are required");
     LinkConsts L;
@@ -1229,7 +1284,7 @@ int sas_camera_matrices(int n, const double *wxyz, const double *position, doubl
 int sas_set_link_poses(sas_ctx *c, int k_links, const double *q_msg, const double *p_msg, float *Rt_out)
 {
     if (!c) return SAS_ERR_INVALID;
-    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
     const LinkConsts &L = c->links;
     if (k_links < 0 || k_links > L.n) return fail(c, SAS_ERR_INVALID, "%d link poses, constants for %d (sas_set_link_constants)", k_links, L.n);
     if (k_links > 0 && (!q_msg || !p_msg)) return fail(c, SAS_ERR_INVALID, "q_msg and p_msg are required");
@@ -1253,7 +1308,7 @@ int sas_link_attached_frame(sas_ctx *c, const double *q_link, const double *p_li
 int sas_get_group_poses(sas_ctx *c, int n_groups, float *Rt)
 {
     if (!c || !Rt) return SAS_ERR_INVALID;
-    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
     if (n_groups != c->scene.n_groups) return fail(c, SAS_ERR_INVALID, "scene has %d groups, got %d", c->scene.n_groups, n_groups);
     if (n_groups > 0) memcpy(Rt, c->group_host.data(), sizeof(float) * 12 * (size_t)n_groups);
     return SAS_OK;
@@ -1269,7 +1324,7 @@ struct ViewCall {
 
 static int check_view(sas_ctx *c, const ViewCall &v, int width, int height)
 {
-    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_render before sas_scene_upload");
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_render before sas_scene_upload");
     if (!v.viewmat || !v.K) return fail(c, SAS_ERR_INVALID, "viewmat and K are required");
     if (width <= 0 || height <= 0 || width > 65535 * SAS_TILE || height > 65535 * SAS_TILE)
         return fail(c, SAS_ERR_INVALID, "bad image size %dx%d", width, height);
@@ -1311,25 +1366,16 @@ static int render_views(sas_ctx *c, const ViewCall *views, int n, int width, int
 {
     if (!c) return SAS_ERR_INVALID;
     flags = frame_flags(c, flags);
-    for (int k = 0; k < n; ++k) {
-        const int rc = check_view(c, views[k], width, height);
-        if (rc) return rc;
-    }
+    for (int k = 0; k < n; ++k)
+        if (const int rc = check_view(c, views[k], width, height)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    if (c->inflight > 0 && (st != c->stream || (flags & SAS_TIMING))) {
-        int rc = complete_all(c);   // one caller stream at a time; timed frames run alone
-        if (rc) return rc;
-    }
-    while (c->inflight > c->n_slots - n) {
-        int rc = complete_oldest(c);
-        if (rc) return rc;
-    }
+    if (c->inflight > 0 && (st != c->stream || (flags & SAS_TIMING)))
+        if (const int rc = complete_all(c)) return rc;   // one caller stream at a time; timed frames run alone
+    while (c->inflight > c->n_slots - n)
+        if (const int rc = complete_oldest(c)) return rc;
     c->stream = st;
-    // nothing in flight: the ring restarts at slot 0, so that a sequence of frames always meets the slots in the same order
-    // (SAS_RING_RESTART=0: the ring goes on where it stood -- bench passes of 25 steps then start on alternating slot pairs)
-    static const bool ring_restart = [] { const char *e = getenv("SAS_RING_RESTART"); return !e || atoi(e) != 0; }();
-    if (ring_restart && c->inflight == 0) c->head = 0;
+    if (c->ring_restart && c->inflight == 0) c->head = 0;
     Slot *sl[SAS_MAX_GROUP] = {nullptr, nullptr, nullptr, nullptr};
     for (int k = 0; k < n; ++k) {
         sl[k] = &c->slots[(c->head + c->inflight + k) % c->n_slots];
@@ -1352,55 +1398,27 @@ int sas_render(sas_ctx *c, const float *viewmat, const float *K, int width, int 
     return render_views(c, &v, 1, width, height, background, flags, nullptr, stream, false, !(flags & SAS_ASYNC));
 }
 
-// A caller's array of `count` floats where a kernel can read it: in place when it is device memory of this context's device, else
-// copied into `stage` (host memory), which the caller releases.
-static int device_floats(sas_ctx *c, const float *p, size_t count, DevBuf &stage, const float **out)
-{
-    hipPointerAttribute_t at{};
-    const bool on_device = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
-    (void)hipGetLastError();   // (a plain host pointer leaves an error behind on some runtimes)
-    *out = p;
-    if (on_device) return SAS_OK;
-    const int rc = ensure(c, stage, sizeof(float) * count);
-    if (rc) return rc;
-    const hipError_t e = hipMemcpy(stage.p, p, sizeof(float) * count, hipMemcpyDefault);
-    if (e != hipSuccess) { release(stage); return fail(c, SAS_ERR_HIP, "feature copy: %s", hipGetErrorString(e)); }
-    *out = (const float *)stage.p;
-    return SAS_OK;
-}
-
 int sas_scene_features(sas_ctx *c, int64_t n, int channels, const float *features)
 {
     if (!c) return SAS_ERR_INVALID;
-    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_features before sas_scene_upload");
-    c->has_mesh_feat = false;   // the triangles' rows belong to the store they were set beside
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_features before sas_scene_upload");
+    forget(c, HAVE_MESH_FEAT);   // the triangles' rows belong to the store they were set beside
     if (n != c->scene.n) return fail(c, SAS_ERR_INVALID, "features for %lld Gaussians, the scene has %lld", (long long)n, (long long)c->scene.n);
     if (channels < 1 || channels > SAS_MAX_FEATURES) return fail(c, SAS_ERR_INVALID, "channels %d out of [1,%d]", channels, SAS_MAX_FEATURES);
     if (!features && c->scene.n_groups <= 0) return fail(c, SAS_ERR_INVALID, "one-hot group features need a scene with splat groups");
     if (!features && channels != c->scene.n_groups)
         return fail(c, SAS_ERR_INVALID, "one-hot group features have n_groups=%d channels, got %d", c->scene.n_groups, channels);
     HIP_TRY(c, hipSetDevice(c->device));
-    {
-        const int rcw = complete_all(c);   // frames in flight read the store
-        if (rcw) return rcw;
-    }
-    c->has_feat = false;
+    if (const int rc = complete_all(c)) return rc;   // frames in flight read the store
+    forget(c, HAVE_FEAT);
     const int64_t n_pad = c->scene.n_pad;
-    const size_t np = (size_t)(n_pad > 0 ? n_pad : 64);
-    int rc;
-    if ((rc = ensure(c, c->feat, sizeof(float) * SAS_FEAT_K * (size_t)sas_feature_chunks(channels) * np))) return rc;
-    const float *src = nullptr;
-    DevBuf s_src;
-    if (features && n > 0 && (rc = device_floats(c, features, (size_t)n * (size_t)channels, s_src, &src))) return rc;
-    // on the context's own (idle: complete_all above) stream, waited for alone -- not the whole device
-    hipStream_t st = c->slots[0].fs;
-    sas_launch_feature_store(st, n, n_pad, c->scene.perm, c->scene.gid8, src, channels, (float *)c->feat.p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    release(s_src);
-    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "feature store: %s", hipGetErrorString(e));
+    const int rc = fill_feature_store(c, c->feat, (size_t)(n_pad > 0 ? n_pad : 64), channels, features, (size_t)n, "feature store",
+                                      [&](hipStream_t st, const float *src, float *store) {
+                                          sas_launch_feature_store(st, n, n_pad, c->scene.perm, c->scene.gid8, src, channels, store);
+                                      });
+    if (rc) return rc;
     c->feat_c = channels;
-    c->has_feat = true;
+    c->have |= HAVE_FEAT;
     return SAS_OK;
 }
 
@@ -1409,9 +1427,9 @@ int sas_render_features(sas_ctx *c, const float *viewmat, const float *K, int wi
                         void *stream)
 {
     if (!c) return SAS_ERR_INVALID;
-    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_render_features before sas_scene_upload");
-    if (!c->has_feat) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
-    if (c->has_mesh && !c->has_mesh_feat)
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_render_features before sas_scene_upload");
+    if (!has(c, HAVE_FEAT)) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
+    if (has(c, HAVE_MESH) && !has(c, HAVE_MESH_FEAT))
         return fail(c, SAS_ERR_INVALID, "feature frames of a context with meshes are not supported (sas_scene_meshes) until the meshes "
                                         "have features (sas_scene_mesh_features)");
     if (!features) return fail(c, SAS_ERR_INVALID, "the features output is required");
@@ -1425,17 +1443,14 @@ int sas_render_features(sas_ctx *c, const float *viewmat, const float *K, int wi
 int sas_scene_mesh_features(sas_ctx *c, int64_t n_triangles, int channels, const float *features)
 {
     if (!c) return SAS_ERR_INVALID;
-    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_mesh_features before sas_scene_upload");
-    if (!c->has_mesh) return fail(c, SAS_ERR_INVALID, "no meshes set for this scene (sas_scene_meshes)");
-    if (!c->has_feat) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_mesh_features before sas_scene_upload");
+    if (!has(c, HAVE_MESH)) return fail(c, SAS_ERR_INVALID, "no meshes set for this scene (sas_scene_meshes)");
+    if (!has(c, HAVE_FEAT)) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
     if (n_triangles != c->mesh.nt)
         return fail(c, SAS_ERR_INVALID, "features for %lld triangles, the meshes have %d", (long long)n_triangles, c->mesh.nt);
     if (channels != c->feat_c) return fail(c, SAS_ERR_INVALID, "%d channels, the feature store has %d", channels, c->feat_c);
     HIP_TRY(c, hipSetDevice(c->device));
-    {
-        const int rcw = complete_all(c);   // frames in flight read the rows
-        if (rcw) return rcw;
-    }
+    if (const int rc = complete_all(c)) return rc;   // frames in flight read the rows
     const size_t nt = (size_t)n_triangles;
     if (!features) {   // one-hot of the triangles' pose groups: every group needs a channel
         std::vector<int4> t4(nt);
@@ -1443,19 +1458,13 @@ int sas_scene_mesh_features(sas_ctx *c, int64_t n_triangles, int channels, const
         for (size_t t = 0; t < nt; ++t)
             if (t4[t].w >= channels) return fail(c, SAS_ERR_INVALID, "one-hot: triangle %zu is of group %d >= %d channels", t, t4[t].w, channels);
     }
-    c->has_mesh_feat = false;
-    int rc;
-    if ((rc = ensure(c, c->mesh_feat, sizeof(float) * SAS_FEAT_K * (size_t)sas_feature_chunks(channels) * nt))) return rc;
-    const float *src = nullptr;
-    DevBuf s_src;
-    if (features && (rc = device_floats(c, features, nt * (size_t)channels, s_src, &src))) return rc;
-    hipStream_t st = c->slots[0].fs;   // the context's own, idle stream, as sas_scene_features
-    sas_launch_mesh_feature_store(st, n_triangles, c->mesh.tri, src, channels, (float *)c->mesh_feat.p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    release(s_src);
-    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "mesh feature store: %s", hipGetErrorString(e));
-    c->has_mesh_feat = true;
+    forget(c, HAVE_MESH_FEAT);
+    const int rc = fill_feature_store(c, c->mesh_feat, nt, channels, features, nt, "mesh feature store",
+                                      [&](hipStream_t st, const float *src, float *store) {
+                                          sas_launch_mesh_feature_store(st, n_triangles, c->mesh.tri, src, channels, store);
+                                      });
+    if (rc) return rc;
+    c->have |= HAVE_MESH_FEAT;
     return SAS_OK;
 }
 
@@ -1463,19 +1472,16 @@ int sas_scene_meshes(sas_ctx *c, int64_t n_vertices, const float *vertices, int6
                      const float *colors, const uint8_t *group, float ambient, float diffuse)
 {
     if (!c) return SAS_ERR_INVALID;
-    if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_meshes before sas_scene_upload");
-    c->has_mesh_feat = false;   // every call forgets the triangles' feature rows (sas_scene_mesh_features)
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_meshes before sas_scene_upload");
+    forget(c, HAVE_MESH_FEAT);   // every call forgets the triangles' feature rows (sas_scene_mesh_features)
     if (n_triangles < 0 || n_vertices < 0 || n_triangles > (1 << 29) || n_vertices > 0x7fffffffll)
         return fail(c, SAS_ERR_INVALID, "bad mesh sizes: %lld vertices, %lld triangles", (long long)n_vertices, (long long)n_triangles);
     if (!std::isfinite(ambient) || !std::isfinite(diffuse)) return fail(c, SAS_ERR_INVALID, "ambient and diffuse must be finite");
     if (n_triangles > 0 && (!vertices || !triangles || !colors || !group)) return fail(c, SAS_ERR_INVALID, "vertices, triangles, colors and group are required");
     HIP_TRY(c, hipSetDevice(c->device));
-    {
-        const int rcw = complete_all(c);   // frames in flight read the meshes
-        if (rcw) return rcw;
-    }
+    if (const int rc = complete_all(c)) return rc;   // frames in flight read the meshes
     if (n_triangles == 0) {
-        c->has_mesh = false;
+        forget(c, HAVE_MESH);
         return SAS_OK;
     }
     const size_t nv = (size_t)n_vertices, nt = (size_t)n_triangles;
@@ -1500,7 +1506,7 @@ int sas_scene_meshes(sas_ctx *c, int64_t n_vertices, const float *vertices, int6
     }
     // validated: only now are the previous meshes replaced (a rejected call leaves them in place; a failed device copy
     // below leaves none)
-    c->has_mesh = false;
+    forget(c, HAVE_MESH);
     int rc;
     if ((rc = ensure(c, c->mesh_vert, sizeof(float4) * std::max<size_t>(nv, 1)))) return rc;
     if ((rc = ensure(c, c->mesh_tri, sizeof(int4) * nt))) return rc;
@@ -1517,8 +1523,8 @@ int sas_scene_meshes(sas_ctx *c, int64_t n_vertices, const float *vertices, int6
     c->mesh.n_groups = c->scene.n_groups;
     c->mesh.ka = ambient;
     c->mesh.kd = diffuse;
-    for (Slot &sl : c->slots) sl.mcap = 0;   // re-derive the list capacity for the new meshes
-    c->has_mesh = true;
+    for (Slot &sl : c->slots) sl.msc.cap = 0;   // re-derive the list capacity for the new meshes
+    c->have |= HAVE_MESH;
     return SAS_OK;
 }
 
@@ -1546,7 +1552,7 @@ static int render_batch_impl(sas_ctx *c, int n_views, const float *viewmats, con
     flags = frame_flags(c, flags);
     if (n_views < 0 || (n_views > 0 && (!viewmats || !Ks))) return fail(c, SAS_ERR_INVALID, "bad view batch");
     if (ps.Rt) {
-        if (!c->has_scene) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
+        if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
         if (c->scene.n_groups <= 0) return fail(c, SAS_ERR_INVALID, "pose sets given but the scene has no splat groups");
         if (ps.n_sets <= 0 || !ps.pose_set) return fail(c, SAS_ERR_INVALID, "pose sets need pose_set[n_views] and n_sets > 0");
         for (int v = 0; v < n_views; ++v)
@@ -1617,8 +1623,7 @@ static int render_batch_host_impl(sas_ctx *c, int n_views, const float *viewmats
     if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "bad image size");
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->inflight > 0) {   // the staging buffer below may still be the target of frames in flight
-        const int rc = complete_all(c);
-        if (rc) return rc;
+        if (const int rc = complete_all(c)) return rc;
     }
     const size_t frame_bytes = 3 * (size_t)width * (size_t)height;
     c->host_query_base = nullptr;
@@ -1727,12 +1732,9 @@ int sas_frame_stats(sas_ctx *c, int64_t *stats, int n)
 int sas_read_projection(sas_ctx *c, int32_t *radii, float *means2d, float *depths, float *conics, float *colors)
 {
     if (!c) return SAS_ERR_INVALID;
-    if (!c->has_scene || !c->has_frame) return fail(c, SAS_ERR_NO_SCENE, "no frame rendered");
+    if (!has(c, HAVE_SCENE) || !c->has_frame) return fail(c, SAS_ERR_NO_SCENE, "no frame rendered");
     HIP_TRY(c, hipSetDevice(c->device));
-    {
-        int rc = complete_all(c);
-        if (rc) return rc;
-    }
+    if (const int rc = complete_all(c)) return rc;
     Slot &ls = c->slots[c->last_slot];
     const int64_t n = c->scene.n;
     if (!ls.info_kept && n > 0) {
@@ -1773,12 +1775,9 @@ int sas_read_projection(sas_ctx *c, int32_t *radii, float *means2d, float *depth
 int sas_read_tile_lists(sas_ctx *c, int32_t *tile_offsets, int32_t *sorted_ids, int64_t cap)
 {
     if (!c) return SAS_ERR_INVALID;
-    if (!c->has_scene || !c->has_frame) return fail(c, SAS_ERR_NO_SCENE, "no frame rendered");
+    if (!has(c, HAVE_SCENE) || !c->has_frame) return fail(c, SAS_ERR_NO_SCENE, "no frame rendered");
     HIP_TRY(c, hipSetDevice(c->device));
-    {
-        int rc = complete_all(c);
-        if (rc) return rc;
-    }
+    if (const int rc = complete_all(c)) return rc;
     const Slot &ls = c->slots[c->last_slot];
     const Scratch &q = ls.scr;
     const int tiles = tiles_of(ls);

@@ -2088,8 +2088,34 @@ void sas_launch_depth_tail(hipStream_t st, int tiles, const SasParams &P, const 
 // ================================================================================================
 namespace {
 
-// store[(q n_pad + j) K + k] = channel q K + k of the Gaussian in slot j (the caller's Gaussian perm[j]), through finite_colour;
-// one-hot mode (src == nullptr): (gid8[j] == q K + k).  Channels >= C and slots >= n are zero.  One thread per (chunk, slot).
+// The one store body of both feature stores ([chunks][stride][SAS_FEAT_K]): thread t = q stride + slot writes the channels q K .. q K + K - 1
+// of that slot -- the caller's row `row` of `rows` through finite_colour (NOT shaded: ambient / diffuse belong to colours), or in one-hot
+// mode (src == nullptr) (id == channel).  row < 0: the slot holds nothing; it and the channels >= C are zero.
+template <int CHK_SRC, int CHK_DST>
+DEV void feature_store_row(long long t, long long total, int q, long long row, long long rows, int id, const float *src, int C, float *store)
+{
+    float v[SAS_FEAT_K];
+#pragma unroll
+    for (int k = 0; k < SAS_FEAT_K; ++k) {
+        const int ch = q * SAS_FEAT_K + k;
+        v[k] = 0.0f;
+        if (row >= 0 && ch < C) {
+            if (src) {
+                const long long at = row * C + ch;
+                if (SAS_IN(at, rows * C, CHK_SRC)) v[k] = finite_colour(src[at]);
+            } else {
+                v[k] = id == ch ? 1.0f : 0.0f;
+            }
+        }
+    }
+    float4 *dst = reinterpret_cast<float4 *>(store) + t * kFeatQ;
+    if (SAS_IN(t * kFeatQ + kFeatQ - 1, total * kFeatQ, CHK_DST)) {
+#pragma unroll
+        for (int r = 0; r < kFeatQ; ++r) dst[r] = make_float4(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
+    }
+}
+
+// Gaussians: slot j holds the caller's Gaussian perm[j], its one-hot id is gid8[j]; stride n_pad, slots >= n zero.  One thread per (chunk, slot).
 __global__ __launch_bounds__(256) void k_feature_store(long long n, long long n_pad, const int *perm, const uint8_t *gid8,
                                                        const float *src, int C, int chunks, float *store)
 {
@@ -2098,32 +2124,14 @@ __global__ __launch_bounds__(256) void k_feature_store(long long n, long long n_
     if (t >= total) return;
     const int q = (int)(t / n_pad);
     const long long j = t - (long long)q * n_pad;
-    float v[SAS_FEAT_K];
-    long long i = 0;
+    long long i = -1;
     if (j < n && SAS_IN(j, n, 301)) i = perm[j];
-    const bool ok = j < n && SAS_IN(i, n, 302) && i >= 0 && i < n;
-#pragma unroll
-    for (int k = 0; k < SAS_FEAT_K; ++k) {
-        const int ch = q * SAS_FEAT_K + k;
-        v[k] = 0.0f;
-        if (ok && ch < C) {
-            if (src) {
-                const long long at = i * C + ch;
-                if (SAS_IN(at, n * C, 303)) v[k] = finite_colour(src[at]);
-            } else if (SAS_IN(j, n_pad, 304)) {
-                v[k] = gid8[j] == ch ? 1.0f : 0.0f;
-            }
-        }
-    }
-    float4 *dst = reinterpret_cast<float4 *>(store) + t * kFeatQ;
-    if (SAS_IN(t * kFeatQ + kFeatQ - 1, total * kFeatQ, 305)) {
-#pragma unroll
-        for (int r = 0; r < kFeatQ; ++r) dst[r] = make_float4(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
-    }
+    if (j < n && !(SAS_IN(i, n, 302) && i < n)) i = -1;
+    const int id = (!src && i >= 0 && SAS_IN(j, n_pad, 304)) ? (int)gid8[j] : -1;
+    feature_store_row<303, 305>(t, total, q, i, n, id, src, C, store);
 }
 
-// store[(q nt + t) K + k] = channel q K + k of triangle t, through finite_colour (NOT shaded: ambient / diffuse belong to colours);
-// one-hot mode (src == nullptr): (the triangle's pose group == q K + k).  Channels >= C are zero.  One thread per (chunk, triangle).
+// Triangles: row t, its one-hot id is the triangle's pose group tri[t].w; stride nt.  One thread per (chunk, triangle).
 __global__ __launch_bounds__(256) void k_mesh_feature_store(long long nt, const int4 *tri, const float *src, int C, int chunks, float *store)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -2132,25 +2140,7 @@ __global__ __launch_bounds__(256) void k_mesh_feature_store(long long nt, const 
     const int q = (int)(i / nt);
     const long long t = i - (long long)q * nt;
     const int grp = SAS_IN(t, nt, 324) ? tri[t].w : -1;
-    float v[SAS_FEAT_K];
-#pragma unroll
-    for (int k = 0; k < SAS_FEAT_K; ++k) {
-        const int ch = q * SAS_FEAT_K + k;
-        v[k] = 0.0f;
-        if (ch < C) {
-            if (src) {
-                const long long at = t * C + ch;
-                if (SAS_IN(at, nt * C, 325)) v[k] = finite_colour(src[at]);
-            } else {
-                v[k] = grp == ch ? 1.0f : 0.0f;
-            }
-        }
-    }
-    float4 *dst = reinterpret_cast<float4 *>(store) + i * kFeatQ;
-    if (SAS_IN(i * kFeatQ + kFeatQ - 1, total * kFeatQ, 326)) {
-#pragma unroll
-        for (int r = 0; r < kFeatQ; ++r) dst[r] = make_float4(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
-    }
+    feature_store_row<325, 326>(i, total, q, t, nt, grp, src, C, store);
 }
 
 // One workgroup per (tile, chunk of SAS_FEAT_K channels), one lane per pixel (pixel_of), on the complete depth-ordered list the

@@ -53,13 +53,18 @@ def feature_channels(shape: Sequence[int], n: int) -> int:
     return shape[1]
 
 
-def mesh_feature_channels(shape: Sequence[int], n_triangles: int, channels: int) -> int:
-    """Channels of a per-triangle feature array of ``shape`` for meshes of ``n_triangles`` triangles beside a feature store of
-    ``channels`` channels ([T,C] with C the store's); ValueError otherwise."""
+def _mesh_features_sit_beside(n_triangles: int, channels: int) -> None:
+    """Mesh features sit beside meshes and a feature store: ValueError without either."""
     if n_triangles <= 0:
         raise ValueError("mesh features need meshes (upload_meshes)")
     if channels <= 0:
         raise ValueError("mesh features need a feature store (upload_features)")
+
+
+def mesh_feature_channels(shape: Sequence[int], n_triangles: int, channels: int) -> int:
+    """Channels of a per-triangle feature array of ``shape`` for meshes of ``n_triangles`` triangles beside a feature store of
+    ``channels`` channels ([T,C] with C the store's); ValueError otherwise."""
+    _mesh_features_sit_beside(n_triangles, channels)
     shape = tuple(int(v) for v in shape)
     if len(shape) != 2 or shape[0] != n_triangles:
         raise ValueError(f"mesh features must be [T={n_triangles},C], got {list(shape)}")
@@ -71,10 +76,7 @@ def mesh_feature_channels(shape: Sequence[int], n_triangles: int, channels: int)
 def mesh_onehot_channels(groups: np.ndarray, n_triangles: int, channels: int) -> int:
     """Channels of the one-hot mesh features (a triangle's pose group is its channel) beside a feature store of ``channels``
     channels: every triangle's group must have a channel; ValueError otherwise."""
-    if n_triangles <= 0:
-        raise ValueError("mesh features need meshes (upload_meshes)")
-    if channels <= 0:
-        raise ValueError("mesh features need a feature store (upload_features)")
+    _mesh_features_sit_beside(n_triangles, channels)
     g = np.asarray(groups).reshape(-1)
     if g.shape[0] != n_triangles:
         raise ValueError(f"{g.shape[0]} mesh groups for {n_triangles} triangles")
@@ -104,6 +106,16 @@ def group_labels(weights: torch.Tensor, alpha: torch.Tensor, min_alpha: float = 
     lab = torch.where(weights == top, ids, torch.full_like(ids, G)).min(dim=-1).values.clamp_(max=255)
     lab = torch.where(alpha[..., 0] < min_alpha, torch.full_like(lab, 255), lab)
     return lab.to(torch.uint8)
+
+
+_ASYNC, _FILL, _MESH_SURFACE, _FAST_EXP, _TIMING, _FULL_SORT, _TIME_TILES = (
+    _capi.SAS_ASYNC, _capi.SAS_DEPTH_FILL_MAX, _capi.SAS_MESH_SURFACE, _capi.SAS_FAST_EXP, _capi.SAS_TIMING, _capi.SAS_FULL_SORT, _capi.SAS_TIME_TILES)
+
+
+def _flags(block=True, depth_fill_max=False, mesh_surface=False, fast_exp=False, timing=False, full_sort=False, time_tiles=False) -> int:
+    """The flags word of a render call (SAS_* of include/sim_a_splat_amd.h); module constants, called by position: render's path."""
+    return (0 if block else _ASYNC) | (_FILL if depth_fill_max else 0) | (_MESH_SURFACE if mesh_surface else 0) | \
+           (_FAST_EXP if fast_exp else 0) | (_TIMING if timing else 0) | (_FULL_SORT if full_sort else 0) | (_TIME_TILES if time_tiles else 0)
 
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # (private, but what torch.cuda.current_stream itself calls)
@@ -140,11 +152,7 @@ class Rasterizer:
             raise SasError(f"sas_create(device={self.device.index}) failed with status {rc}")
         self.n = 0
         self.n_groups = 0
-        self.n_features = 0     # channels of the feature store (upload_features); 0: none for this scene
-        self._features_onehot = False
-        self.n_mesh_triangles = 0   # triangles of the meshes (upload_meshes); 0: none for this scene
-        self._mesh_groups = np.zeros(0, np.uint8)   # their pose groups
-        self._mesh_features_onehot = False   # the meshes' feature rows are the one-hot of the triangles' pose groups (upload_mesh_features)
+        self._forget("scene")
         self._keep = []  # outputs of in-flight async frames (the C ABI keeps up to four)
         self._argcache = {}  # id(argument) -> (argument, float32 array, address): _host_arg
 
@@ -163,6 +171,30 @@ class Rasterizer:
 
     def _check(self, rc: int, what: str) -> None:
         _capi.check(self._ctx, rc, what)
+
+    def _forget(self, *stores: str) -> None:
+        """Reset what this object remembers of the library's stores, by the library's rule (sas_api.cpp: forget): features and meshes sit
+        beside a scene, mesh features beside both.  The only place the five fields are reset; each ``upload*`` sets its own in one line."""
+        s = set(stores)
+        if "scene" in s:
+            s |= {"features", "meshes"}
+        if s & {"features", "meshes"}:
+            s.add("mesh_features")
+        if "features" in s:        # channels of the feature store (upload_features; 0: none for this scene); it is the groups' one-hot
+            self.n_features, self._features_onehot = 0, False
+        if "meshes" in s:          # triangles of the meshes (upload_meshes; 0: none for this scene), their pose groups
+            self.n_mesh_triangles, self._mesh_groups = 0, np.zeros(0, np.uint8)
+        if "mesh_features" in s:   # the meshes' feature rows are the one-hot of the triangles' pose groups (upload_mesh_features)
+            self._mesh_features_onehot = False
+
+    def _store_rows(self, entry: str, rows: Optional[ArrayLike], count: int, C: int, name: str) -> None:
+        """``rows [count,C]`` (None: one-hot, built on the device) into the feature store that C-ABI ``entry`` fills."""
+        pf = None
+        if rows is not None:
+            f, pf = _as_f32(rows, (count, C), name)
+            if isinstance(f, torch.Tensor) and f.is_cuda:
+                torch.cuda.synchronize(f.device)   # device-resident inputs must be complete before the copy
+        self._check(getattr(self._L, entry)(self._ctx, count, C, pf), entry)
 
     # -- scene ------------------------------------------------------------------------------
     @_locked
@@ -203,11 +235,7 @@ class Rasterizer:
                     "sas_scene_upload")
         self.n = n
         self.n_groups = int(n_groups) if group_id is not None else 0
-        self.n_features = 0     # (the upload forgot them)
-        self._features_onehot = False
-        self.n_mesh_triangles = 0
-        self._mesh_groups = np.zeros(0, np.uint8)
-        self._mesh_features_onehot = False
+        self._forget("scene")
 
     @_locked
     def upload_features(self, features: Optional[ArrayLike] = None) -> None:
@@ -215,19 +243,12 @@ class Rasterizer:
         ``upload``), 1 <= C <= 256; NaN and +-Inf are mapped to -+FLT_MAX as colours are.  ``None``: one-hot of the scene's
         splat groups (C = n_groups), built on the device.  A new ``upload`` forgets them.  Mesh features
         (``upload_mesh_features``) belong to the store they were set beside: this call forgets them."""
-        self._mesh_features_onehot = False
-        if features is None:
-            if self.n_groups <= 0:
-                raise ValueError("one-hot group features need a scene uploaded with group_id")
-            self._check(self._L.sas_scene_features(self._ctx, self.n, self.n_groups, None), "sas_scene_features")
-            self.n_features, self._features_onehot = self.n_groups, True
-            return
-        C = feature_channels(features.shape, self.n)
-        f, pf = _as_f32(features, (self.n, C), "features")
-        if isinstance(f, torch.Tensor) and f.is_cuda:
-            torch.cuda.synchronize(f.device)   # device-resident inputs must be complete before the copy
-        self._check(self._L.sas_scene_features(self._ctx, self.n, C, pf), "sas_scene_features")
-        self.n_features, self._features_onehot = C, False
+        self._forget("mesh_features")
+        if features is None and self.n_groups <= 0:
+            raise ValueError("one-hot group features need a scene uploaded with group_id")
+        C = self.n_groups if features is None else feature_channels(features.shape, self.n)
+        self._store_rows("sas_scene_features", features, self.n, C, "features")
+        self.n_features, self._features_onehot = C, features is None
 
     @_locked
     def upload_meshes(self, vertices: ArrayLike, triangles: ArrayLike, colors: ArrayLike, groups: Optional[ArrayLike] = None,
@@ -237,7 +258,7 @@ class Rasterizer:
         group moving each triangle (``None``: group 0).  Shading ``clamp(c (ambient + diffuse |n . v|), 0, 1)``.  Frames then take
         the full-sort path.  A new ``upload`` forgets the meshes; ``T == 0`` clears them.  Mesh features
         (``upload_mesh_features``) are forgotten."""
-        self._mesh_features_onehot = False
+        self._forget("mesh_features")
         host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
         v = np.ascontiguousarray(np.asarray(host(vertices), dtype=np.float32).reshape(-1, 3))
         t = np.ascontiguousarray(np.asarray(host(triangles), dtype=np.int64).reshape(-1, 3))
@@ -253,15 +274,13 @@ class Rasterizer:
         g = np.ascontiguousarray(np.broadcast_to(g.astype(np.uint8).reshape(-1), (T,)))
         self._check(self._L.sas_scene_meshes(self._ctx, v.shape[0], v.ctypes.data, T, t.ctypes.data, c.ctypes.data, g.ctypes.data,
                                              float(ambient), float(diffuse)), "sas_scene_meshes")
-        self.n_mesh_triangles = T
-        self._mesh_groups = g
+        self.n_mesh_triangles, self._mesh_groups = T, g
 
     @_locked
     def clear_meshes(self) -> None:
-        self._mesh_features_onehot = False
+        self._forget("mesh_features")
         self._check(self._L.sas_scene_meshes(self._ctx, 0, None, 0, None, None, None, 0.4, 0.6), "sas_scene_meshes")
-        self.n_mesh_triangles = 0
-        self._mesh_groups = np.zeros(0, np.uint8)
+        self._forget("meshes")
 
     @_locked
     def upload_mesh_features(self, features: Optional[ArrayLike] = None) -> None:
@@ -271,17 +290,9 @@ class Rasterizer:
         shows a triangle its row takes the feature background's place.  ``upload``, ``upload_meshes`` and
         ``upload_features`` forget them -- and ``render_features`` refuses a scene with meshes until they are set."""
         T = self.n_mesh_triangles
-        if features is None:
-            C = mesh_onehot_channels(self._mesh_groups, T, self.n_features)
-            self._check(self._L.sas_scene_mesh_features(self._ctx, T, C, None), "sas_scene_mesh_features")
-            self._mesh_features_onehot = True
-            return
-        C = mesh_feature_channels(features.shape, T, self.n_features)
-        f, pf = _as_f32(features, (T, C), "mesh features")
-        if isinstance(f, torch.Tensor) and f.is_cuda:
-            torch.cuda.synchronize(f.device)   # device-resident inputs must be complete before the copy
-        self._check(self._L.sas_scene_mesh_features(self._ctx, T, C, pf), "sas_scene_mesh_features")
-        self._mesh_features_onehot = False
+        C = mesh_onehot_channels(self._mesh_groups, T, self.n_features) if features is None else mesh_feature_channels(features.shape, T, self.n_features)
+        self._store_rows("sas_scene_mesh_features", features, T, C, "mesh features")
+        self._mesh_features_onehot = features is None
 
     @_locked
     def set_group_poses(self, Rt: ArrayLike) -> None:
@@ -347,6 +358,34 @@ class Rasterizer:
             a = np.ascontiguousarray(np.asarray(a, dtype=np.float32)).reshape(count)
         return a
 
+    def _outputs(self, names: Iterable[str], shapes, H: int, W: int, out, views: Optional[int] = None):
+        """(tensors, addresses) of the outputs ``names``, ``[H,W,channels]`` by the table ``shapes`` (``[views,H,W,channels]`` for a
+        batch): ``out``'s where it holds one, validated, else allocated.  Addresses of outputs not asked for: None."""
+        res: Dict[str, torch.Tensor] = {}
+        ptrs = dict.fromkeys(shapes)
+        dev = self.device
+        given = out.get if out is not None else None
+        for k in names:
+            ch, dt = shapes[k]   # KeyError: unknown output
+            shape = (H, W, ch) if views is None else (views, H, W, ch)
+            t = given(k) if given else None
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device=dev)
+            elif t.shape != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor {shape} on {dev}")
+            res[k] = t
+            ptrs[k] = t.data_ptr()
+        return res, ptrs
+
+    @staticmethod
+    def _host_frames(out: Optional[torch.Tensor], shape: Tuple[int, int, int, int]) -> torch.Tensor:
+        """The ``[C,H,W,3]`` uint8 host tensor of the two host entry points: the caller's, validated, or a pinned one."""
+        if out is None:
+            return torch.empty(shape, dtype=torch.uint8, pin_memory=True)
+        if out.shape != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device.type != "cpu":
+            raise ValueError(f"out must be a contiguous uint8 CPU tensor {shape}")
+        return out
+
     def _stream(self) -> int:
         """The caller's current HIP stream on this context's device (1.9 us through torch.cuda.current_stream, 0.07 us
         through the raw getter it wraps: tools/py_overhead_probe.py)."""
@@ -390,21 +429,8 @@ class Rasterizer:
         Kc, pK = self._host_arg(K, 9)
         bg, pbg = self._host_arg(background, 3)
         W, H = int(width), int(height)
-        res: Dict[str, torch.Tensor] = {}
-        ptrs = {"rgb": None, "alpha": None, "depth": None, "rgb8": None}
-        for k in want:
-            ch, dt = self._SHAPES[k]   # KeyError: unknown output
-            t = out.get(k) if out is not None else None
-            if t is None:
-                t = torch.empty((H, W, ch), dtype=dt, device=self.device)
-            elif t.shape != (H, W, ch) or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
-                raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor {(H, W, ch)} on {self.device}")
-            res[k] = t
-            ptrs[k] = t.data_ptr()
-        flags = (_capi.SAS_DEPTH_FILL_MAX if depth_fill_max else 0) | (_capi.SAS_FAST_EXP if fast_exp else 0) | \
-                (_capi.SAS_TIMING if timing else 0) | (0 if block else _capi.SAS_ASYNC) | \
-                (_capi.SAS_FULL_SORT if full_sort else 0) | (_capi.SAS_TIME_TILES if time_tiles else 0) | \
-                (_capi.SAS_MESH_SURFACE if mesh_surface else 0)
+        res, ptrs = self._outputs(want, self._SHAPES, H, W, out)
+        flags = _flags(block, depth_fill_max, mesh_surface, fast_exp, timing, full_sort, time_tiles)
         stream = self._stream()
         rc = self._L.sas_render(self._ctx, pV, pK, W, H, pbg, flags,
                                 ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], stream)
@@ -430,7 +456,7 @@ class Rasterizer:
         res["points"] = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
         mask8 = torch.empty((H, W), dtype=torch.uint8, device=self.device)
         md = ctypes.c_float(max_depth) if max_depth is not None else None
-        flags = (_capi.SAS_DEPTH_FILL_MAX if depth_fill_max else 0) | (_capi.SAS_MESH_SURFACE if mesh_surface else 0)
+        flags = _flags(True, depth_fill_max, mesh_surface)
         stream = self._stream()
         rc = self._L.sas_render_rgbd(self._ctx, V.ctypes.data, Kc.ctypes.data, W, H, bg.ctypes.data, flags,
                                      ctypes.addressof(md) if md is not None else None,
@@ -465,19 +491,8 @@ class Rasterizer:
         shapes = dict(self._SHAPES, features=(C, torch.float32))
         shapes.pop("rgb8")
         want = tuple(want)
-        res: Dict[str, torch.Tensor] = {}
-        ptrs = {"rgb": None, "alpha": None, "depth": None, "features": None}
-        for k in set(want) | {"features"}:
-            ch, dt = shapes[k]   # KeyError: unknown output
-            t = out.get(k) if out is not None else None
-            if t is None:
-                t = torch.empty((H, W, ch), dtype=dt, device=self.device)
-            elif t.shape != (H, W, ch) or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
-                raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor {(H, W, ch)} on {self.device}")
-            res[k] = t
-            ptrs[k] = t.data_ptr()
-        flags = (_capi.SAS_DEPTH_FILL_MAX if depth_fill_max else 0) | (_capi.SAS_FAST_EXP if fast_exp else 0) | \
-                (0 if block else _capi.SAS_ASYNC) | (_capi.SAS_MESH_SURFACE if mesh_surface else 0)
+        res, ptrs = self._outputs(set(want) | {"features"}, shapes, H, W, out)
+        flags = _flags(block, depth_fill_max, mesh_surface, fast_exp)
         rc = self._L.sas_render_features(self._ctx, pV, pK, W, H, pbg, fb.ctypes.data if fb is not None else None, flags,
                                          ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["features"], self._stream())
         if rc != 0:
@@ -499,6 +514,16 @@ class Rasterizer:
             self.upload_mesh_features(None)
         o = self.render_features(viewmat, K, width, height, want=("features", "alpha"), mesh_surface=self.n_mesh_triangles > 0)
         return {"weights": o["features"], "labels": group_labels(o["features"], o["alpha"], min_alpha), "alpha": o["alpha"]}
+
+    def _batch_call(self, name: str, C: int, pV, pK, pose_sets, pose_set, *tail) -> None:
+        """``sas_<name>`` for C views; ``sas_<name>_posed`` when they come with pose sets."""
+        if pose_sets is None:
+            rc = getattr(self._L, name)(self._ctx, C, pV, pK, *tail)
+        else:
+            Rt, idx = self._pose_sets(pose_sets, pose_set, C)
+            rc = getattr(self._L, name + "_posed")(self._ctx, C, pV, pK, idx.ctypes.data, Rt.shape[0], Rt.ctypes.data, *tail)
+        if rc != 0:
+            self._check(rc, name)
 
     def _pose_sets(self, pose_sets, pose_set, C: int):
         """(Rt [S,G,12] float32, index [C] int32) of per-view pose sets, validated."""
@@ -528,29 +553,10 @@ class Rasterizer:
         Kc, pK = self._host_arg(Ks, 9 * C)
         bg, pbg = self._host_arg(background, 3)
         W, H = int(width), int(height)
-        res: Dict[str, torch.Tensor] = {}
-        ptrs = {"rgb": None, "alpha": None, "depth": None, "rgb8": None}
-        for k in want:
-            ch, dt = self._SHAPES[k]
-            t = out.get(k) if out is not None else None
-            if t is None:
-                t = torch.empty((C, H, W, ch), dtype=dt, device=self.device)
-            elif t.shape != (C, H, W, ch) or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
-                raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor {(C, H, W, ch)} on {self.device}")
-            res[k] = t
-            ptrs[k] = t.data_ptr()
-        flags = (_capi.SAS_DEPTH_FILL_MAX if depth_fill_max else 0) | (0 if block else _capi.SAS_ASYNC) | \
-                (_capi.SAS_TIME_TILES if time_tiles else 0) | (_capi.SAS_MESH_SURFACE if mesh_surface else 0)
-        stream = self._stream()
-        if pose_sets is not None:
-            Rt, idx = self._pose_sets(pose_sets, pose_set, C)
-            rc = self._L.sas_render_batch_posed(self._ctx, C, pV, pK, idx.ctypes.data, Rt.shape[0], Rt.ctypes.data,
-                                                W, H, pbg, flags, ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], stream)
-        else:
-            rc = self._L.sas_render_batch(self._ctx, C, pV, pK, W, H, pbg, flags,
-                                          ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], stream)
-        if rc != 0:
-            self._check(rc, "sas_render_batch")
+        res, ptrs = self._outputs(want, self._SHAPES, H, W, out, C)
+        flags = _flags(block, depth_fill_max, mesh_surface, time_tiles=time_tiles)
+        self._batch_call("sas_render_batch", C, pV, pK, pose_sets, pose_set, W, H, pbg, flags,
+                         ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], self._stream())
         self._keep = [] if block else (self._keep + [(res, V, Kc, bg)])[-4:]
         return res
 
@@ -568,20 +574,8 @@ class Rasterizer:
         Kc, pK = self._host_arg(Ks, 9 * C)
         bg, pbg = self._host_arg(background, 3)
         W, H = int(width), int(height)
-        if out is None:
-            out = torch.empty((C, H, W, 3), dtype=torch.uint8, pin_memory=True)
-        elif out.shape != (C, H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device.type != "cpu":
-            raise ValueError(f"out must be a contiguous uint8 CPU tensor {(C, H, W, 3)}")
-        stream = self._stream()
-        if pose_sets is not None:
-            Rt, idx = self._pose_sets(pose_sets, pose_set, C)
-            rc = self._L.sas_render_batch_host_posed(self._ctx, C, pV, pK, idx.ctypes.data, Rt.shape[0],
-                                                     Rt.ctypes.data, W, H, pbg, 0, out.data_ptr(), stream)
-        else:
-            rc = self._L.sas_render_batch_host(self._ctx, C, pV, pK, W, H, pbg, 0,
-                                               out.data_ptr(), stream)
-        if rc != 0:
-            self._check(rc, "sas_render_batch_host")
+        out = self._host_frames(out, (C, H, W, 3))
+        self._batch_call("sas_render_batch_host", C, pV, pK, pose_sets, pose_set, W, H, pbg, 0, out.data_ptr(), self._stream())
         return out
 
     @_locked
@@ -593,10 +587,7 @@ class Rasterizer:
         p = np.ascontiguousarray(np.asarray(position, dtype=np.float64).reshape(-1, 3))
         C, W, H = q.shape[0], int(width), int(height)
         bg = self._host_f32(background, 3)
-        if out is None:
-            out = torch.empty((C, H, W, 3), dtype=torch.uint8, pin_memory=True)
-        elif out.shape != (C, H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device.type != "cpu":
-            raise ValueError(f"out must be a contiguous uint8 CPU tensor {(C, H, W, 3)}")
+        out = self._host_frames(out, (C, H, W, 3))
         stream = self._stream()
         rc = self._L.sas_render_cameras_host(self._ctx, C, q.ctypes.data, p.ctypes.data, float(fov), W, H, bg.ctypes.data, 0,
                                              out.data_ptr(), stream)
