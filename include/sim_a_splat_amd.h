@@ -238,6 +238,22 @@ int sas_scene_meshes(sas_ctx *ctx, int64_t n_vertices, const float *vertices, in
 int sas_scene_mesh_features(sas_ctx *ctx, int64_t n_triangles, int channels, const float *features);
 
 /*
+ * Vertex attributes of the meshes: smooth shading ("Meshes", rule 2b) -- what the reference hands viser for the
+ * robot's URDF visuals (vertex normals and vertex colours, splat_handler.py:181-189).  After sas_scene_meshes:
+ *   n_vertices  the uploaded meshes' vertex count (SAS_ERR_INVALID otherwise)
+ *   normals     [n_vertices,3] float32 unit normals, mesh-local, or NULL; a zero or non-finite normal means "none"
+ *   colors      [n_vertices,3] float32, or NULL: a smooth triangle takes its own colour at its three vertices
+ *   Host or device pointers.  Both NULL clears the attributes and frees their device copies.
+ * A triangle whose three vertices carry a normal is SMOOTH: per vertex s_k = clamp(c_k (ambient + diffuse |n'_k . v_k|), 0, 1),
+ * n'_k the normal under the 3x3 block of the triangle's pose row, renormalised, v_k the unit ray from the camera centre to the
+ * posed vertex; per pixel m = sum_k beta_k s_k with the perspective-correct barycentric coordinates of the ray's hit point
+ * (s / z is affine in the pixel).  Every other triangle keeps the flat shade above.  Coverage, depth, ties, occlusion,
+ * SAS_MESH_SURFACE and mesh feature rows are untouched: a smooth frame differs from the flat one in rgb / rgb8 only.
+ * sas_scene_meshes and sas_scene_upload forget the attributes.  Frames in flight are completed first.
+ */
+int sas_scene_mesh_vertex_attributes(sas_ctx *ctx, int64_t n_vertices, const float *normals_or_null, const float *colors_or_null);
+
+/*
  * Render n_views views of the same size in one call.  Serves the per-camera loops of
  * SplatHandler.render / SplatEnvWrapper.render (splat_handler.py:337-345, splat_env_wrapper.py:147-158).
  *   viewmats [n_views,16], Ks [n_views,9] host arrays; outputs are [n_views,H,W,...] device arrays

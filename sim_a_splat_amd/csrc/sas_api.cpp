@@ -93,6 +93,7 @@ struct Scratch {
 // Mesh scratch of a slot's frame (SasMeshFrame), when the context holds meshes.
 struct MeshScratch {
     DevBuf rec, rect, tiles, list;   // records, rectangles, [count | offset | cursor], lists
+    DevBuf planes;                   // frames of meshes with vertex attributes: the records' attribute planes (SAS_MESH_PLANE_STRIDE float4 each)
     DevBuf win;                      // feature frames: every pixel's triangle as k_blend_mesh_scene resolved it (SasMeshExtra::win)
     long long cap = 0;               // entries `list` holds (grown like the splat keys when a frame outgrows it)
     Pinned<unsigned> status_host;    // [2], written by k_mesh_scan
@@ -213,7 +214,8 @@ struct Settings {
 
 // What the context stores (sas_ctx::have).  Features and meshes sit beside a scene, mesh features beside both: forget() drops a
 // store together with what sits beside it, and is the only place a bit is cleared; each store has one line that sets its bit.
-enum : unsigned { HAVE_SCENE = 1, HAVE_FEAT = 2, HAVE_MESH = 4, HAVE_MESH_FEAT = 8 };
+// Vertex attributes (sas_scene_mesh_vertex_attributes) sit beside the meshes.
+enum : unsigned { HAVE_SCENE = 1, HAVE_FEAT = 2, HAVE_MESH = 4, HAVE_MESH_FEAT = 8, HAVE_MESH_ATTR = 16 };
 
 struct sas_ctx : Settings {
     int device = 0;
@@ -224,6 +226,8 @@ struct sas_ctx : Settings {
     int feat_c = 0;      // its channels
     DevBuf mesh_vert, mesh_tri, mesh_col;   // meshes (sas_scene_meshes): float4 vertices, int4 (i0, i1, i2, group), float4 colours
     SasMeshScene mesh{};
+    DevBuf mesh_nrm, mesh_vcol;   // vertex attributes (sas_scene_mesh_vertex_attributes): float4 normals, float4 colours, [mesh.nv] each
+    bool mesh_has_vcol = false;   // ... colours were given
     DevBuf mesh_feat;        // per-triangle feature rows (sas_scene_mesh_features): [chunks][nt][SAS_FEAT_K], feat_c channels
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
     // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
@@ -271,6 +275,7 @@ void forget(sas_ctx *c, unsigned stores)
 {
     if (stores & HAVE_SCENE) stores |= HAVE_FEAT | HAVE_MESH;
     if (stores & (HAVE_FEAT | HAVE_MESH)) stores |= HAVE_MESH_FEAT;
+    if (stores & HAVE_MESH) stores |= HAVE_MESH_ATTR;
     c->have &= ~stores;
 }
 
@@ -629,6 +634,16 @@ int prepare_frame(sas_ctx *c, Slot &sl, hipStream_t init_st)
 
 // Mesh scratch of the slot's frame: 2 records per triangle, the tile counts / offsets / cursors, the lists (first guess: four
 // tiles per record; a frame whose lists outgrow it is rendered again with the measured need, as for the splat keys).
+// The meshes as a frame's setup kernel takes them: with their vertex attributes while the context holds any.
+SasMeshScene mesh_scene_of(const sas_ctx *c)
+{
+    SasMeshScene m = c->mesh;
+    const bool attr = has(c, HAVE_MESH_ATTR);
+    m.vnormal = attr ? (const float4 *)c->mesh_nrm.p : nullptr;
+    m.vcolor = attr && c->mesh_has_vcol ? (const float4 *)c->mesh_vcol.p : nullptr;
+    return m;
+}
+
 int prepare_mesh(sas_ctx *c, MeshScratch &m, int tiles, size_t feature_pixels)
 {
     const size_t nrec = 2 * (size_t)c->mesh.nt;
@@ -637,6 +652,7 @@ int prepare_mesh(sas_ctx *c, MeshScratch &m, int tiles, size_t feature_pixels)
     if ((rc = ensure(c, m.rec, sizeof(float4) * 4 * nrec))) return rc;
     if ((rc = ensure(c, m.rect, sizeof(int4) * nrec))) return rc;
     if ((rc = ensure(c, m.tiles, sizeof(int) * (3 * sas_tile_stride(tiles) + 16)))) return rc;
+    if (has(c, HAVE_MESH_ATTR) && (rc = ensure(c, m.planes, sizeof(float4) * SAS_MESH_PLANE_STRIDE * nrec))) return rc;
     if (feature_pixels && (rc = ensure(c, m.win, sizeof(unsigned long long) * feature_pixels))) return rc;
     return ensure(c, m.list, sizeof(int) * (size_t)m.cap);
 }
@@ -768,9 +784,10 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
     hipEvent_t tile_ev[2] = {ttiles ? ld.ev[4] : nullptr, ttiles ? ld.ev[5] : nullptr};
     if (ld.mesh) {
         const SasMeshFrame mesh = mesh_frame_of(c, ld.msc, tiles);
-        sas_launch_mesh_bin(st, c->mesh, P, f, mesh);
+        float4 *planes = has(c, HAVE_MESH_ATTR) ? (float4 *)ld.msc.planes.p : nullptr;
+        sas_launch_mesh_bin(st, mesh_scene_of(c), P, f, mesh, planes);
         const SasMeshExtra extra{a.out.features ? (unsigned long long *)ld.msc.win.p : nullptr, (a.flags & SAS_MESH_SURFACE) != 0};
-        sas_launch_blend_mesh(st, c->scene, tiles, P, f, mesh, extra, fast_exp, any_fill);
+        sas_launch_blend_mesh(st, c->scene, tiles, P, f, mesh, extra, planes, fast_exp, any_fill);
         if (a.out.features) {   // ... in front of the triangles the blend kernel has just resolved (extra.win)
             const SasMeshFeatures MF{extra.win, (const float *)c->mesh_feat.p, c->mesh.nt};
             sas_launch_blend_features(st, c->scene, tiles, P, f, features_of(c, a), fast_exp, &MF);
@@ -1473,7 +1490,7 @@ int sas_scene_meshes(sas_ctx *c, int64_t n_vertices, const float *vertices, int6
 {
     if (!c) return SAS_ERR_INVALID;
     if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_meshes before sas_scene_upload");
-    forget(c, HAVE_MESH_FEAT);   // every call forgets the triangles' feature rows (sas_scene_mesh_features)
+    forget(c, HAVE_MESH_FEAT | HAVE_MESH_ATTR);   // every call forgets the triangles' feature rows (sas_scene_mesh_features) and the vertex attributes
     if (n_triangles < 0 || n_vertices < 0 || n_triangles > (1 << 29) || n_vertices > 0x7fffffffll)
         return fail(c, SAS_ERR_INVALID, "bad mesh sizes: %lld vertices, %lld triangles", (long long)n_vertices, (long long)n_triangles);
     if (!std::isfinite(ambient) || !std::isfinite(diffuse)) return fail(c, SAS_ERR_INVALID, "ambient and diffuse must be finite");
@@ -1525,6 +1542,50 @@ int sas_scene_meshes(sas_ctx *c, int64_t n_vertices, const float *vertices, int6
     c->mesh.kd = diffuse;
     for (Slot &sl : c->slots) sl.msc.cap = 0;   // re-derive the list capacity for the new meshes
     c->have |= HAVE_MESH;
+    return SAS_OK;
+}
+
+int sas_scene_mesh_vertex_attributes(sas_ctx *c, int64_t n_vertices, const float *normals, const float *colors)
+{
+    if (!c) return SAS_ERR_INVALID;
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_mesh_vertex_attributes before sas_scene_upload");
+    if (!has(c, HAVE_MESH)) return fail(c, SAS_ERR_INVALID, "no meshes set for this scene (sas_scene_meshes)");
+    if (n_vertices != c->mesh.nv)
+        return fail(c, SAS_ERR_INVALID, "attributes for %lld vertices, the meshes have %d", (long long)n_vertices, c->mesh.nv);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;   // frames in flight read the attributes
+    if (!normals && !colors) {   // cleared: the device copies and the slots' planes go back (flat frames keep their footprint)
+        forget(c, HAVE_MESH_ATTR);
+        int rc;
+        if ((rc = c->mesh_nrm.release(c)) || (rc = c->mesh_vcol.release(c))) return rc;
+        for (Slot &sl : c->slots)
+            if ((rc = sl.msc.planes.release(c))) return rc;
+        return SAS_OK;
+    }
+    const size_t nv = (size_t)n_vertices;
+    std::vector<float> in(3 * nv);
+    std::vector<float4> n4(nv, make_float4(0.0f, 0.0f, 0.0f, 0.0f)), c4(nv);
+    if (normals) {
+        if (nv) HIP_TRY(c, hipMemcpy(in.data(), normals, sizeof(float) * 3 * nv, hipMemcpyDefault));
+        for (size_t i = 0; i < nv; ++i) {   // a non-finite normal counts as none
+            const float x = in[3 * i], y = in[3 * i + 1], z = in[3 * i + 2];
+            if (std::isfinite(x) && std::isfinite(y) && std::isfinite(z)) n4[i] = make_float4(x, y, z, 0.0f);
+        }
+    }
+    if (colors) {
+        if (nv) HIP_TRY(c, hipMemcpy(in.data(), colors, sizeof(float) * 3 * nv, hipMemcpyDefault));
+        for (size_t i = 0; i < nv; ++i) c4[i] = make_float4(in[3 * i], in[3 * i + 1], in[3 * i + 2], 0.0f);
+    }
+    forget(c, HAVE_MESH_ATTR);   // (a failed copy below leaves none)
+    int rc;
+    if ((rc = ensure(c, c->mesh_nrm, sizeof(float4) * std::max<size_t>(nv, 1)))) return rc;
+    if (nv) HIP_TRY(c, hipMemcpy(c->mesh_nrm.p, n4.data(), sizeof(float4) * nv, hipMemcpyHostToDevice));
+    if (colors) {
+        if ((rc = ensure(c, c->mesh_vcol, sizeof(float4) * std::max<size_t>(nv, 1)))) return rc;
+        if (nv) HIP_TRY(c, hipMemcpy(c->mesh_vcol.p, c4.data(), sizeof(float4) * nv, hipMemcpyHostToDevice));
+    }
+    c->mesh_has_vcol = colors != nullptr;
+    c->have |= HAVE_MESH_ATTR;
     return SAS_OK;
 }
 

@@ -262,6 +262,9 @@ struct SasMeshScene {
     int nv, nt;
     int n_groups;           // the scene's (0: no splat groups, every triangle unposed)
     float ka, kd;
+    // vertex attributes (sas_scene_mesh_vertex_attributes; DESIGN.md 3, "Meshes", rule 2b), nullptr: none
+    const float4 *vnormal;  // [nv] mesh-local unit normals (x, y, z, 0); zero: the vertex has none
+    const float4 *vcolor;   // [nv] (r, g, b, 0), or nullptr: a smooth triangle takes color[t] at its three vertices
 };
 struct SasMeshFrame {
     float4 *rec;            // [2 nt * 4]
@@ -280,7 +283,14 @@ struct SasMeshExtra {
     unsigned long long *win;   // feature frames: [H W] every pixel's (depth bits << 32 | record), ~0: none, for k_blend_features_mesh; else nullptr
     int surface;               // SAS_MESH_SURFACE: alpha / depth of a covered pixel close on the triangle
 };
-void sas_launch_mesh_bin(hipStream_t st, const SasMeshScene &m, const SasParams &P, const SasFrame &f, const SasMeshFrame &mf);
-// sas_launch_blend for a frame with meshes
+// Attribute planes of a frame whose meshes carry vertex attributes (rule 2b), an array of its own beside the records -- frames of
+// flat meshes neither allocate nor read it.  3 float4 per record, in the records' image-centre frame:
+//   [0] (Ar, Br, Cr, smooth) [1] (Ag, Bg, Cg, -) [2] (Ab, Bb, Cb, -)     shade / z = A x + B y + C per channel,
+// smooth != 0: the record's triangle is smooth and the pixel's colour is (A x + B y + C) / (za x + zb y + zc); 0: flat, rec[3].
+#define SAS_MESH_PLANE_STRIDE 3
+// planes: nullptr for a frame without vertex attributes
+void sas_launch_mesh_bin(hipStream_t st, const SasMeshScene &m, const SasParams &P, const SasFrame &f, const SasMeshFrame &mf,
+                         float4 *planes);
+// sas_launch_blend for a frame with meshes (planes != nullptr: k_blend_mesh_smooth)
 void sas_launch_blend_mesh(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
-                           const SasMeshFrame &mf, const SasMeshExtra &x, bool fast_exp, bool want_max);
+                           const SasMeshFrame &mf, const SasMeshExtra &x, const float4 *planes, bool fast_exp, bool want_max);

@@ -1294,14 +1294,34 @@ DEV float mesh_resolve(const SasMeshFrame &M, const SasCam &c, int tile, int ix,
     return __uint_as_float((unsigned)(best >> 32));
 }
 
+// Rule 2b (k_blend_mesh_smooth): the colour of the pixel's triangle when that triangle is smooth -- the WINNING record's attribute
+// planes alone are read, once, after the list walk: m = (A x + B y + C) / (za x + zb y + zc) per channel, the denominator the very
+// 1/z mesh_resolve evaluated for this record.  A flat winner keeps rec[3], which mesh_resolve has put in bg.
+DEV void mesh_smooth_colour(const SasMeshFrame &M, const float4 *planes, const SasCam &c, int ix, int iy, unsigned long long win, float *bg)
+{
+    if (win == ~0ull) return;
+    const long long r = (long long)(unsigned)(win & 0xffffffffu);
+    if (!SAS_IN(r, M.n_rec, 331)) return;
+    const float4 a0 = planes[SAS_MESH_PLANE_STRIDE * r];
+    if (a0.w == 0.0f) return;
+    const float4 a1 = planes[SAS_MESH_PLANE_STRIDE * r + 1], a2 = planes[SAS_MESH_PLANE_STRIDE * r + 2], r2 = M.rec[4 * r + 2];
+    const float px = ((float)ix + 0.5f) - 0.5f * c.Wf, py = ((float)iy + 0.5f) - 0.5f * c.Hf;
+    const float iz = r2.y * px + r2.z * py + r2.w;
+    bg[0] = fminf(fmaxf((a0.x * px + a0.y * py + a0.z) / iz, 0.0f), 1.0f);
+    bg[1] = fminf(fmaxf((a1.x * px + a1.y * py + a1.z) / iz, 0.0f), 1.0f);
+    bg[2] = fminf(fmaxf((a2.x * px + a2.y * py + a2.z) / iz, 0.0f), 1.0f);
+}
+
 // MESH: a frame with meshes (its lists, records and tiles as any other's; SAS_FULL_SORT frames with meshes deliver no rgb8 to the
 // host from the tile kernel).  The splats are composited in front of the pixel's triangle (blend_range<.., MESH>), whose colour
 // takes the background's place in write_pixel.
 // SCENE (k_blend_mesh_scene: a mesh frame with a features output and / or SAS_MESH_SURFACE): the pixel's triangle is left in X->win
 // for k_blend_features_mesh, and alpha / depth close on the triangle.  Plain mesh frames keep the kernel without either.
-template <bool FAST_EXP, bool WANT_MAX, bool MESH, bool SCENE = false>
+// SMOOTH (k_blend_mesh_smooth: a frame whose meshes carry vertex attributes; SCENE's extras with it): smooth triangles take their
+// colour from the record's attribute planes.  Frames of flat meshes keep the two kernels above, which know no planes.
+template <bool FAST_EXP, bool WANT_MAX, bool MESH, bool SCENE = false, bool SMOOTH = false>
 DEV void blend_tile(const SasParams &P, const SasFrame &f, long long n_gauss, int tile, unsigned &sync_phase, const SasMeshFrame *M,
-                    const SasMeshExtra *X = nullptr)
+                    const SasMeshExtra *X = nullptr, const float4 *planes = nullptr)
 {
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[kBlendLdsBytes];
     __shared__ unsigned s_wmax[4];
@@ -1318,6 +1338,7 @@ DEV void blend_tile(const SasParams &P, const SasFrame &f, long long n_gauss, in
     if constexpr (MESH) {
         unsigned long long win;
         zlim = mesh_resolve(*M, c, tile, ix, iy, o.bg, win);
+        if constexpr (SMOOTH) mesh_smooth_colour(*M, planes, c, ix, iy, win, o.bg);
         // a feature frame: k_blend_features_mesh's workgroups (one per chunk of channels) take the pixel's triangle and depth from
         // here, so that rgb and features can never disagree about which triangle a pixel shows
         if constexpr (SCENE)
@@ -1370,6 +1391,14 @@ __global__ __launch_bounds__(256) void k_blend_mesh_scene(SasParams P, SasFrame 
     unsigned sync_phase = 0u;
     for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x)
         blend_tile<FAST_EXP, WANT_MAX, true, true>(P, f, n_gauss, tl[oi], sync_phase, &M, &X);
+}
+template <bool FAST_EXP, bool WANT_MAX>
+__global__ __launch_bounds__(256) void k_blend_mesh_smooth(SasParams P, SasFrame f, long long n_gauss, const int *tl, const int *range,
+                                                           SasMeshFrame M, SasMeshExtra X, const float4 *planes)
+{
+    unsigned sync_phase = 0u;
+    for (int oi = range[0] + (int)blockIdx.x; oi < range[1]; oi += (int)gridDim.x)
+        blend_tile<FAST_EXP, WANT_MAX, true, true, true>(P, f, n_gauss, tl[oi], sync_phase, &M, &X, planes);
 }
 
 // ================================================================================================
@@ -2029,11 +2058,13 @@ void sas_launch_blend(hipStream_t st, const SasScene &s, int tiles, const SasPar
 }
 
 void sas_launch_blend_mesh(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
-                           const SasMeshFrame &mf, const SasMeshExtra &x, bool fast_exp, bool want_max)
+                           const SasMeshFrame &mf, const SasMeshExtra &x, const float4 *planes, bool fast_exp, bool want_max)
 {
     const long long n = s.n > 0 ? s.n : 1;
     with_flags([&](auto fast, auto wmax) {
-        if (x.win || x.surface)
+        if (planes)
+            hipLaunchKernelGGL((k_blend_mesh_smooth<fast(), wmax()>), dim3((unsigned)tiles), dim3(256), 0, st, P, f, n, f.tile_order, f.sort_class + 4, mf, x, planes);
+        else if (x.win || x.surface)
             hipLaunchKernelGGL((k_blend_mesh_scene<fast(), wmax()>), dim3((unsigned)tiles), dim3(256), 0, st, P, f, n, f.tile_order, f.sort_class + 4, mf, x);
         else
             hipLaunchKernelGGL((k_blend_mesh<fast(), wmax()>), dim3((unsigned)tiles), dim3(256), 0, st, P, f, n, f.tile_order, f.sort_class + 4, mf);

@@ -42,16 +42,51 @@ def _translation_of(x) -> np.ndarray:
 TASK_MESH_COLOR = (0.956, 0.396, 0.365)   # splat_handler.py:205
 
 
-def _mesh_arrays(meshes, task_assets_path=None, task_assets_name=None) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
-    """``meshes`` as names or arrays -> ``{"task": (vertices, faces)}`` (mesh-local, unscaled)."""
+ROBOT_MESH_DEFAULT_COLOR = (0.5, 0.5, 0.5)   # a visual without a material colour
+
+
+def robot_visual_meshes(robot, robot_description_dir: str, package_name: str, urdf_dir=None) -> list:
+    """The robot's visual meshes as ``_add_robot_meshes`` collects them (splat_handler.py:145-173): for every link in URDF
+    order, every visual with a mesh -> ``(vertices, faces, rgb)``.  ``package://{package_name}`` in a mesh filename is replaced
+    by ``robot_description_dir`` (the reference does so in the URDF text); any other relative filename is taken relative to the
+    URDF's directory.  rgb: the visual's material colour, (0.5, 0.5, 0.5) without one.  As in the reference, neither the
+    visual's ``<origin>`` nor the mesh ``scale`` is applied to the vertices."""
+    from pathlib import Path
     from . import mesh_io
-    out: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
+    out = []
+    for link in robot.links:
+        for vis in robot.visuals[link]:
+            if not vis.mesh:
+                continue
+            fn = vis.mesh.replace(f"package://{package_name}", robot_description_dir)
+            if fn.startswith("file://"):
+                fn = fn[len("file://"):]
+            path = Path(fn)
+            if not path.is_absolute() and urdf_dir is not None:
+                path = Path(urdf_dir) / path
+            v, f = mesh_io.load_mesh(path)
+            out.append((v, f, ROBOT_MESH_DEFAULT_COLOR if vis.color is None else tuple(float(x) for x in vis.color)))
+    return out
+
+
+def _mesh_arrays(meshes, task_assets_path=None, task_assets_name=None, robot_meshes=None) -> Dict[str, object]:
+    """``meshes`` as names or arrays -> ``{"task": (vertices, faces), "robot": [(vertices, faces, rgb), ...]}`` (mesh-local,
+    unscaled).  ``robot_meshes``: a callable that reads the URDF's visuals (the path constructor's), for ``"robot"`` by name."""
+    from . import mesh_io
+    out: Dict[str, object] = {}
     items = meshes.items() if isinstance(meshes, dict) else ((m, None) for m in (meshes or ()))
     for name, val in items:
         if name == "robot":
-            raise NotImplementedError("robot meshes (the URDF visuals) are not drawn yet; meshes=('task',) is")
+            if val is None:
+                if robot_meshes is None:
+                    raise NotImplementedError("meshes=('robot',) by name reads the URDF's visuals: the path constructor does; from arrays "
+                                              "pass them, {'robot': [(vertices, faces, rgb), ...]}")
+                val = robot_meshes()
+            out["robot"] = [(np.asarray(v, np.float64).reshape(-1, 3), np.asarray(f, np.int64).reshape(-1, 3),
+                             tuple(float(x) for x in np.asarray(rgb, np.float64).reshape(-1)[:3])) for v, f, rgb in val]
+            continue
         if name != "task":
-            raise ValueError(f"unknown mesh {name!r}: 'task'")
+            raise ValueError(f"unknown mesh {name!r}: 'task', 'robot'")
         if val is None:
             if not task_assets_name:
                 raise ValueError("meshes=('task',) needs task_assets_path and task_assets_name")
@@ -74,8 +109,9 @@ class SplatHandler:
       the client, a ``SplatScene`` (created on ``device`` when None);
     * ``meshes`` (not in the reference, default ``()``: splats only): ``"task"`` composites the task object
       ``{task_assets_path}/{task_assets_name}`` into every frame, in the reference's colour (0.956, 0.396, 0.365), scaled by the
-      ICP scale and posed by ``draw_handler`` as at :296-314 (``_add_task_meshes``, :199-219).  The robot's URDF visual
-      meshes (``"robot"``, :145-197) are not drawn yet: asking for them raises.
+      ICP scale and posed by ``draw_handler`` as at :296-314 (``_add_task_meshes``, :199-219).  ``"robot"`` composites the
+      robot's URDF visual meshes (``_add_robot_meshes``, :145-197): welded, smooth-shaded from computed vertex normals in the
+      visual's material colour ("Meshes", rule 2b), one mesh ``{uid}/mesh_robot/link{ii}`` each, posed as at :238-263.
 
     ``SplatHandler.from_arrays`` builds the same object from arrays already in memory."""
 
@@ -92,12 +128,14 @@ class SplatHandler:
         icp = io.load_icp_transformation(masks_dir / "icp_transformation.npy")
         loader = GSplatLoader.from_path(Path(f"{splat_assets_path}/splatfacto/{splat_config_name}").resolve())
         robot_description_dir = package_path + "/" + package_name
-        fk = urdf_fk.visual_mesh_fk(urdf_fk.load(Path(robot_description_dir + f"urdf/{urdf_name}")),
-                                    io.load_joint_config(masks_dir / "joint_config.npy"))
+        urdf_path = Path(robot_description_dir + f"urdf/{urdf_name}")
+        robot = urdf_fk.load(urdf_path)
+        fk = urdf_fk.visual_mesh_fk(robot, io.load_joint_config(masks_dir / "joint_config.npy"))
         keep = aabb_mask(loader.means.cpu().numpy(), bounds)
         arr = lambda t: t.cpu().numpy()[keep]
         masks = {k: np.asarray(v, dtype=bool)[keep] for k, v in masks.items()}
-        meshes = _mesh_arrays(meshes, task_assets_path, task_assets_name)
+        meshes = _mesh_arrays(meshes, task_assets_path, task_assets_name,
+                              robot_meshes=lambda: robot_visual_meshes(robot, robot_description_dir, package_name, urdf_path.parent))
         self._setup(arr(loader.means), arr(loader.covs), arr(loader.colors), arr(loader.opacities), masks, icp, fk,
                     instance_uid=match_object_name, weld=sim_robot_weld_frame_transform, scene=server, device=device, meshes=meshes)
         self.masks_dir = str(masks_dir)
@@ -113,7 +151,8 @@ class SplatHandler:
         """The same handler from arrays: Gaussians [N,...], the per-link boolean masks ``link0..``, the 4x4 ICP
         similarity and one 4x4 forward-kinematics pose per visual mesh at the mask-time joint configuration.
         ``meshes``: names (``"task"``: read from ``task_assets_path/task_assets_name``) or arrays,
-        ``{"task": (vertices [V,3], faces [F,3])}``."""
+        ``{"task": (vertices [V,3], faces [F,3]), "robot": [(vertices, faces, rgb), ...]}`` (the robot's visual meshes in
+        ``robot_visual_meshes`` order; by name they need the URDF, i.e. the path constructor)."""
         self = cls.__new__(cls)
         self._setup(means, covs, colors, opacities, link_masks, icp_transformation, fk_transforms, instance_uid=instance_uid,
                     weld=weld_translation, scene=scene, device=device, robot_num=robot_num,
@@ -151,6 +190,15 @@ class SplatHandler:
             v, f = meshes["task"]
             self.task_mesh_frame_handle = self.scene.add_mesh_simple(f"{instance_uid}/mesh_task/task", v, f, TASK_MESH_COLOR,
                                                                      scale=self.scale_factor)
+        # robot meshes (_add_robot_meshes, :175-197): one smooth mesh per visual, welded (an STL shares no vertex), with computed
+        # vertex normals, in the visual's material colour, vertices times the ICP scale
+        self.mesh_frame_handles = []
+        if meshes and meshes.get("robot"):
+            from . import mesh_io
+            for ii, (v, f, rgb) in enumerate(meshes["robot"]):
+                v, f = mesh_io.weld(v, f)
+                self.mesh_frame_handles.append(self.scene.add_mesh_simple(
+                    f"{instance_uid}/mesh_robot/link{ii}", v, f, rgb, scale=self.scale_factor, vertex_normals=mesh_io.vertex_normals(v, f)))
         # the draw message's pose algebra runs inside the library when the scene offers it (sas_set_link_poses)
         self._k_fast = min(len(self.fk), 7, len(self.splat_links_handler))
         self._fast = hasattr(self.scene, "set_link_poses") and self._k_fast > 0
@@ -178,18 +226,36 @@ class SplatHandler:
     def mesh_pose_rows(self, msg) -> Tuple[np.ndarray, np.ndarray]:
         """The pose rows ``draw_handler(msg)`` gives this handler's meshes, WITHOUT touching the scene: ``(rows [m], [m,12]
         float32)``.  Task mesh: the last entry with ``robot_num == blk_idx``, ``icp o SE3(q/|q|, p s)`` in float64 (:296-314),
-        through the handle's quaternion as ``draw_handler`` assigns it."""
+        through the handle's quaternion as ``draw_handler`` assigns it.  Robot meshes: the k-th entry with ``robot_num ==
+        rbt_idx`` poses the k-th mesh, ``icp o SE3(q/|q|, (p + weld) s)`` (:238-263); surplus entries are ignored."""
+        idx, found = [], []
         h = self.task_mesh_frame_handle
-        if h is None:
-            return np.zeros(0, np.int64), np.zeros((0, 12), np.float32)
-        hits = [i for i in range(msg.num_links) if msg.robot_num[i] == self.blk_idx]
-        if not hits:
-            return np.zeros(0, np.int64), np.zeros((0, 12), np.float32)
-        wxyz, t = self._task_pose(msg, hits[-1])
-        row = np.zeros((1, 3, 4), np.float32)
-        row[0, :, :3] = poses.quat_wxyz_to_matrix(wxyz)
-        row[0, :, 3] = t
-        return np.array([h.index], np.int64), row.reshape(1, 12)
+        hits = [i for i in range(msg.num_links) if msg.robot_num[i] == self.blk_idx] if h is not None else []
+        if hits:
+            idx.append(h.index)
+            found.append(self._task_pose(msg, hits[-1]))
+        for hk, i in self._robot_mesh_entries(msg):
+            idx.append(hk.index)
+            found.append(self._robot_mesh_pose(msg, i))
+        rows = np.zeros((len(idx), 3, 4), np.float32)
+        for k, (wxyz, t) in enumerate(found):
+            rows[k, :, :3] = poses.quat_wxyz_to_matrix(wxyz)
+            rows[k, :, 3] = t
+        return np.array(idx, np.int64), rows.reshape(len(idx), 12)
+
+    def _robot_mesh_entries(self, msg) -> list:
+        """(robot mesh handle, message entry) pairs: the k-th entry of the robot with the k-th mesh."""
+        handles = getattr(self, "mesh_frame_handles", None)
+        if not handles:
+            return []
+        return list(zip(handles, (i for i in range(msg.num_links) if msg.robot_num[i] == self.rbt_idx)))
+
+    def _robot_mesh_pose(self, msg, idx):
+        q = np.asarray(msg.quaternion[idx], dtype=np.float64)
+        q = q / np.linalg.norm(q)
+        R = self.Ri @ poses.quat_wxyz_to_matrix(q)
+        p = (np.asarray(msg.position[idx], dtype=np.float64) + self.weld_translation) * self.scale_factor
+        return poses.matrix_to_quat_wxyz(R), self.Ri @ p + self.ti
 
     def _task_pose(self, msg, idx):
         q = np.asarray(msg.quaternion[idx], dtype=np.float64)
@@ -199,6 +265,8 @@ class SplatHandler:
         return poses.matrix_to_quat_wxyz(R), t
 
     def _draw_meshes(self, msg) -> None:
+        for hk, idx in self._robot_mesh_entries(msg):
+            hk.wxyz, hk.position = self._robot_mesh_pose(msg, idx)
         h = self.task_mesh_frame_handle
         if h is None:
             return
@@ -212,7 +280,7 @@ class SplatHandler:
         """``msg``: lcmt_viewer_draw-shaped (num_links, robot_num[], position[][3], quaternion[][4] wxyz).  The
         k-th link of the robot (``robot_num == rbt_idx``, message order) drives splat group k, as in the reference
         (:227-314); all links are posed in one batch of small matrix products."""
-        if getattr(self, "task_mesh_frame_handle", None) is not None:
+        if getattr(self, "task_mesh_frame_handle", None) is not None or getattr(self, "mesh_frame_handles", None):
             self._draw_meshes(msg)
         rn, rbt = msg.robot_num, self.rbt_idx
         idxs = [idx for idx in range(msg.num_links) if rn[idx] == rbt]

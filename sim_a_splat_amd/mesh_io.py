@@ -2,7 +2,8 @@
 
 They need neither trimesh nor open3d: the reference loads the pushT task object (an OBJ) and the URDF visuals (STL or OBJ)
 through trimesh only to hand vertices and faces to viser (splat_handler.py:145-219).  Every reader returns
-``(vertices [V,3] float64, faces [F,3] int64)``.
+``(vertices [V,3] float64, faces [F,3] int64)``.  ``weld`` and ``vertex_normals`` prepare a loaded mesh for smooth shading (rule 2b): the
+reference gets its vertex normals from open3d / trimesh.
 """
 from __future__ import annotations
 
@@ -70,3 +71,46 @@ def load_mesh(path: PathLike) -> Tuple[np.ndarray, np.ndarray]:
     if suf == ".stl":
         return load_stl(path)
     raise ValueError(f"{path}: unsupported mesh format {suf!r} (OBJ and STL are read)")
+
+
+def weld(vertices, faces) -> Tuple[np.ndarray, np.ndarray]:
+    """Merge vertices whose float32 positions are bit-equal (``load_stl`` returns three private vertices per triangle, so that
+    no vertex is shared and no normal can be averaged).  Returns ``(vertices [U,3] float64, faces [F,3] int64)``: the unique
+    positions in order of first appearance, the faces re-indexed; +0 and -0 stay apart, as do NaNs of different bits."""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    if len(v) == 0:
+        return v.copy(), f.copy()
+    bits = np.ascontiguousarray(v.astype(np.float32)).view(np.uint32).reshape(-1, 3)
+    key = bits.astype(np.uint64)
+    _, first, inverse = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")                 # unique rows by first appearance
+    rank = np.empty(len(order), np.int64)
+    rank[order] = np.arange(len(order))
+    return v[first[order]].copy(), rank[np.asarray(inverse).reshape(-1)][f]
+
+
+def vertex_normals(vertices, faces) -> np.ndarray:
+    """Unit vertex normals ``[V,3]`` float64: the sum over a vertex's faces of the unit face normal weighted by the face's
+    interior angle at that vertex, normalised.  Degenerate faces contribute nothing; a vertex without a usable face gets a
+    zero normal ("no normal": its triangles stay flat)."""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    out = np.zeros_like(v)
+    if len(f) == 0:
+        return out
+    tri = v[f]                                               # [F,3,3]
+    fn = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    fl = np.linalg.norm(fn, axis=1)
+    ok = np.isfinite(fl) & (fl > 0)
+    fn = np.where(ok[:, None], fn / np.where(ok, fl, 1.0)[:, None], 0.0)
+    for k in range(3):
+        a, b = tri[:, (k + 1) % 3] - tri[:, k], tri[:, (k + 2) % 3] - tri[:, k]
+        la, lb = np.linalg.norm(a, axis=1), np.linalg.norm(b, axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ang = np.arccos(np.clip((a * b).sum(1) / (la * lb), -1.0, 1.0))
+        ang = np.where(ok & np.isfinite(ang), ang, 0.0)
+        np.add.at(out, f[:, k], fn * ang[:, None])
+    n = np.linalg.norm(out, axis=1)
+    good = np.isfinite(n) & (n > 0)
+    return np.where(good[:, None], out / np.where(good, n, 1.0)[:, None], 0.0)

@@ -174,16 +174,20 @@ class Rasterizer:
 
     def _forget(self, *stores: str) -> None:
         """Reset what this object remembers of the library's stores, by the library's rule (sas_api.cpp: forget): features and meshes sit
-        beside a scene, mesh features beside both.  The only place the five fields are reset; each ``upload*`` sets its own in one line."""
+        beside a scene, mesh features beside both.  The only place these fields are reset; each ``upload*`` sets its own in one line."""
         s = set(stores)
         if "scene" in s:
             s |= {"features", "meshes"}
         if s & {"features", "meshes"}:
             s.add("mesh_features")
+        if "meshes" in s:          # vertex attributes sit beside the meshes (upload_mesh_vertex_attributes)
+            s.add("mesh_attributes")
         if "features" in s:        # channels of the feature store (upload_features; 0: none for this scene); it is the groups' one-hot
             self.n_features, self._features_onehot = 0, False
         if "meshes" in s:          # triangles of the meshes (upload_meshes; 0: none for this scene), their pose groups
-            self.n_mesh_triangles, self._mesh_groups = 0, np.zeros(0, np.uint8)
+            self.n_mesh_triangles, self.n_mesh_vertices, self._mesh_groups = 0, 0, np.zeros(0, np.uint8)
+        if "mesh_attributes" in s:   # the meshes carry vertex normals and / or colours (smooth shading, rule 2b)
+            self.mesh_vertex_attributes = False
         if "mesh_features" in s:   # the meshes' feature rows are the one-hot of the triangles' pose groups (upload_mesh_features)
             self._mesh_features_onehot = False
 
@@ -252,13 +256,15 @@ class Rasterizer:
 
     @_locked
     def upload_meshes(self, vertices: ArrayLike, triangles: ArrayLike, colors: ArrayLike, groups: Optional[ArrayLike] = None,
-                      ambient: float = 0.4, diffuse: float = 0.6) -> None:
+                      ambient: float = 0.4, diffuse: float = 0.6, vertex_normals: Optional[ArrayLike] = None,
+                      vertex_colors: Optional[ArrayLike] = None) -> None:
         """Triangle meshes composited into every frame (sas_scene_meshes; DESIGN.md 3, "Meshes"): ``vertices [V,3]`` (mesh-local,
         scale applied), ``triangles [T,3]`` vertex indices, ``colors [T,3]`` (or one ``[3]`` for all), ``groups [T]`` the pose
         group moving each triangle (``None``: group 0).  Shading ``clamp(c (ambient + diffuse |n . v|), 0, 1)``.  Frames then take
         the full-sort path.  A new ``upload`` forgets the meshes; ``T == 0`` clears them.  Mesh features
-        (``upload_mesh_features``) are forgotten."""
-        self._forget("mesh_features")
+        (``upload_mesh_features``) and vertex attributes are forgotten; ``vertex_normals`` / ``vertex_colors`` ``[V,3]`` are then
+        handed to ``upload_mesh_vertex_attributes`` (smooth shading)."""
+        self._forget("mesh_features", "mesh_attributes")
         host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
         v = np.ascontiguousarray(np.asarray(host(vertices), dtype=np.float32).reshape(-1, 3))
         t = np.ascontiguousarray(np.asarray(host(triangles), dtype=np.int64).reshape(-1, 3))
@@ -274,7 +280,27 @@ class Rasterizer:
         g = np.ascontiguousarray(np.broadcast_to(g.astype(np.uint8).reshape(-1), (T,)))
         self._check(self._L.sas_scene_meshes(self._ctx, v.shape[0], v.ctypes.data, T, t.ctypes.data, c.ctypes.data, g.ctypes.data,
                                              float(ambient), float(diffuse)), "sas_scene_meshes")
-        self.n_mesh_triangles, self._mesh_groups = T, g
+        self.n_mesh_triangles, self.n_mesh_vertices, self._mesh_groups = T, v.shape[0], g
+        if T and (vertex_normals is not None or vertex_colors is not None):
+            self.upload_mesh_vertex_attributes(vertex_normals, vertex_colors)
+
+    @_locked
+    def upload_mesh_vertex_attributes(self, normals: Optional[ArrayLike] = None, colors: Optional[ArrayLike] = None) -> None:
+        """Vertex attributes of the uploaded meshes (sas_scene_mesh_vertex_attributes; DESIGN.md 3, "Meshes", rule 2b):
+        ``normals [V,3]`` unit, mesh-local (zero or non-finite: the vertex has none) and / or ``colors [V,3]`` in [0,1], V the
+        vertex count of ``upload_meshes``.  A triangle whose three vertices have a normal is shaded smoothly -- the headlight
+        shade evaluated per vertex and interpolated perspective-correctly over the triangle; the others stay flat.  Without
+        ``colors`` a smooth triangle keeps its own colour.  Both ``None`` clears the attributes; ``upload`` and
+        ``upload_meshes`` forget them."""
+        host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+        arr = lambda a: None if a is None else np.ascontiguousarray(np.asarray(host(a), dtype=np.float32).reshape(-1, 3))
+        n, c = arr(normals), arr(colors)
+        count = next((a.shape[0] for a in (n, c) if a is not None), self.n_mesh_vertices)
+        if n is not None and c is not None and n.shape[0] != c.shape[0]:
+            raise ValueError(f"{n.shape[0]} vertex normals, {c.shape[0]} vertex colours")
+        self._check(self._L.sas_scene_mesh_vertex_attributes(self._ctx, count, None if n is None else n.ctypes.data,
+                                                             None if c is None else c.ctypes.data), "sas_scene_mesh_vertex_attributes")
+        self.mesh_vertex_attributes = n is not None or c is not None
 
     @_locked
     def clear_meshes(self) -> None:

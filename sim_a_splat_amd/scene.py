@@ -133,8 +133,10 @@ class SplatScene:
         return h
 
     def add_mesh_simple(self, name: str, vertices, faces, color=(0.5, 0.5, 0.5), wxyz=(1.0, 0.0, 0.0, 0.0),
-                        position=(0.0, 0.0, 0.0), scale: float = 1.0) -> MeshHandle:
-        """viser's ``scene.add_mesh_simple``: ``vertices [V,3]`` (times ``scale``), ``faces [F,3]``, one colour (or ``[F,3]``)."""
+                        position=(0.0, 0.0, 0.0), scale: float = 1.0, vertex_normals=None, vertex_colors=None) -> MeshHandle:
+        """viser's ``scene.add_mesh_simple``: ``vertices [V,3]`` (times ``scale``), ``faces [F,3]``, one colour (or ``[F,3]``).
+        ``vertex_normals [V,3]`` (unit, mesh-local) make the mesh smooth-shaded ("Meshes", rule 2b), with
+        ``vertex_colors [V,3]`` (0-1 or 0-255) interpolated over its triangles when given."""
         v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3) * float(scale)
         f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
         col = np.asarray(color, dtype=np.float64)
@@ -142,12 +144,23 @@ class SplatScene:
         col = np.broadcast_to(col.reshape(-1, 3) if col.size != 3 else col.reshape(1, 3), (f.shape[0], 3))
         if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
             raise ValueError(f"{name}: face index out of range")
+        attr = {}
+        for key, a in (("normals", vertex_normals), ("vcolors", vertex_colors)):
+            if a is None:
+                continue
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim != 2 or a.shape[0] != v.shape[0] or a.shape[1] < 3:
+                raise ValueError(f"{name}: vertex {key} must be [V={v.shape[0]},3]")
+            a = a[:, :3]
+            if key == "vcolors" and (np.asarray(vertex_colors).dtype.kind in "iu" or a.max(initial=0.0) > 1.0):
+                a = a / 255.0
+            attr[key] = np.ascontiguousarray(a, dtype=np.float32)
         with self.lock:
             if len(self._handles) >= 256:
                 raise RuntimeError("at most 256 splat groups and meshes")
             h = MeshHandle(self, name, len(self._handles), wxyz, position)
             self._meshes.append(dict(row=h.index, vertices=v.astype(np.float32), faces=f.astype(np.int32),
-                                     colors=np.ascontiguousarray(col, dtype=np.float32)))
+                                     colors=np.ascontiguousarray(col, dtype=np.float32), **attr))
             self._handles.append(h)
             self._Rt = np.concatenate([self._Rt, np.zeros((1, 3, 4), np.float32)], axis=0)
             h._write_row()
@@ -156,9 +169,11 @@ class SplatScene:
         return h
 
     def add_mesh_trimesh(self, name: str, mesh, scale: float = 1.0, wxyz=(1.0, 0.0, 0.0, 0.0),
-                         position=(0.0, 0.0, 0.0)) -> MeshHandle:
+                         position=(0.0, 0.0, 0.0), smooth: bool = False) -> MeshHandle:
         """viser's ``scene.add_mesh_trimesh``, duck-typed: ``mesh.vertices``, ``mesh.faces`` and, when present,
-        ``mesh.visual.vertex_colors`` (RGB(A), 0-255 or 0-1) averaged over each face's three vertices."""
+        ``mesh.visual.vertex_colors`` (RGB(A), 0-255 or 0-1) averaged over each face's three vertices.  ``smooth=True``: shaded
+        from vertex normals (rule 2b) -- ``mesh.vertex_normals`` when present, else ``mesh_io.vertex_normals`` -- and the vertex
+        colours are interpolated per vertex instead of averaged."""
         v = np.asarray(mesh.vertices, dtype=np.float64).reshape(-1, 3)
         f = np.asarray(mesh.faces, dtype=np.int64).reshape(-1, 3)
         vc = getattr(getattr(mesh, "visual", None), "vertex_colors", None)
@@ -168,8 +183,14 @@ class SplatScene:
                 vc = vc / 255.0
             color = vc[f].mean(axis=1)
         else:
-            color = (0.5, 0.5, 0.5)
-        return self.add_mesh_simple(name, v, f, color, wxyz=wxyz, position=position, scale=scale)
+            color, vc = (0.5, 0.5, 0.5), None
+        if not smooth:
+            return self.add_mesh_simple(name, v, f, color, wxyz=wxyz, position=position, scale=scale)
+        vn = getattr(mesh, "vertex_normals", None)
+        if vn is None or len(vn) != len(v):
+            from .mesh_io import vertex_normals
+            vn = vertex_normals(v, f)
+        return self.add_mesh_simple(name, v, f, color, wxyz=wxyz, position=position, scale=scale, vertex_normals=vn, vertex_colors=vc)
 
     # -- the draw message's pose algebra inside the library (SplatHandler.draw_handler's fast path) ---------------
     def set_link_constants(self, scale: float, Ri, ti, Rfk, tfk, weld=None, groups=None, owner=None) -> None:
@@ -225,17 +246,33 @@ class SplatScene:
                                     covariances=cat("covariances", (0, 6)), sh_degree=-1, group_id=gid, n_groups=len(self._handles))
             if self._meshes:
                 off = np.cumsum([0] + [m["vertices"].shape[0] for m in self._meshes])[:-1]
+                # vertex attributes, when any mesh has them: zero normals keep the other meshes flat.  Vertex colours are one array
+                # for the whole upload, so once any mesh has them a smooth mesh without gets its face colours per vertex
+                attrs = {}
+                if any("normals" in m for m in self._meshes):
+                    attrs["vertex_normals"] = np.concatenate([m.get("normals", np.zeros_like(m["vertices"])) for m in self._meshes])
+                    if any("vcolors" in m for m in self._meshes):
+                        attrs["vertex_colors"] = np.concatenate([m["vcolors"] if "vcolors" in m else self._vertex_colours_of(m)
+                                                                 for m in self._meshes])
                 self._raster.upload_meshes(np.concatenate([m["vertices"] for m in self._meshes]),
                                            np.concatenate([m["faces"] + o for m, o in zip(self._meshes, off)]),
                                            np.concatenate([m["colors"] for m in self._meshes]),
                                            groups=np.concatenate([np.full(m["faces"].shape[0], m["row"], np.uint8) for m in self._meshes]),
-                                           ambient=self.mesh_ambient, diffuse=self.mesh_diffuse)
+                                           ambient=self.mesh_ambient, diffuse=self.mesh_diffuse, **attrs)
             self._uploaded = True
             self._poses_dirty = True
             self._link_owner_applied = _NO_OWNER_APPLIED    # a fresh upload: the context holds nobody's link constants
         if self._poses_dirty and self._handles:
             self._raster.set_group_poses(self._Rt.reshape(-1, 12))
         self._poses_dirty = False
+
+    @staticmethod
+    def _vertex_colours_of(m) -> np.ndarray:
+        """Per-vertex colours of a mesh registered without any, for an upload in which another mesh has them: each vertex takes
+        the colour of the last face that uses it (exact for the one-colour meshes this serves; unused vertices 0.5 grey)."""
+        vc = np.full(m["vertices"].shape, 0.5, np.float32)
+        vc[m["faces"].reshape(-1)] = np.repeat(m["colors"], 3, axis=0)
+        return vc
 
     @staticmethod
     def _view_and_K(height: int, width: int, wxyz, position, fov: float):

@@ -89,6 +89,7 @@ class Visual:
     origin: np.ndarray
     mesh: Optional[str]
     scale: Optional[np.ndarray]
+    color: Optional[np.ndarray] = None   # RGB of the visual's <material><color rgba>, inline or by name; None: no material colour
 
 
 @dataclass
@@ -110,6 +111,12 @@ def load(urdf: Union[str, Path]) -> Robot:
     text = str(urdf)
     root = ET.fromstring(text) if text.lstrip().startswith("<") else ET.parse(text).getroot()
     links, visuals = [], {}
+    # robot-level materials: a visual's <material name=...> without a colour of its own resolves against this table (urchin)
+    named = {}
+    for me in root.findall("material"):
+        ce = me.find("color")
+        if me.get("name") and ce is not None and ce.get("rgba"):
+            named[me.get("name")] = _floats(ce.get("rgba"), 4, (0, 0, 0, 1))[:3]
     for le in root.findall("link"):
         name = le.get("name")
         links.append(name)
@@ -117,7 +124,14 @@ def load(urdf: Union[str, Path]) -> Robot:
         for ve in le.findall("visual"):
             me = ve.find("geometry/mesh")
             scale = _floats(me.get("scale"), 3, (1, 1, 1)) if me is not None and me.get("scale") else None
-            vs.append(Visual(_origin(ve.find("origin")), me.get("filename") if me is not None else None, scale))
+            mat, color = ve.find("material"), None
+            if mat is not None:
+                ce = mat.find("color")
+                if ce is not None and ce.get("rgba"):
+                    color = _floats(ce.get("rgba"), 4, (0, 0, 0, 1))[:3]
+                elif mat.get("name") in named:
+                    color = named[mat.get("name")].copy()
+            vs.append(Visual(_origin(ve.find("origin")), me.get("filename") if me is not None else None, scale, color))
         visuals[name] = vs
     joints = []
     for je in root.findall("joint"):
