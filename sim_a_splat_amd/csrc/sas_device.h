@@ -1,4 +1,4 @@
-// sas_device.h -- device-side helpers shared by sas_kernels.hip and sas_tile.hip.
+// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip and sas_mesh.hip.
 // Everything here follows the arithmetic contract of DESIGN.md: IEEE binary32 operations, fused
 // only where fma_() is written (translation units are built with -ffp-contract=off).
 #pragma once
@@ -135,6 +135,21 @@ DEV float affine3(float r0, float r1, float r2, float t, float v0, float v1, flo
 DEV float dot3(float a0, float a1, float a2, float b0, float b1, float b2)
 {
     return fma_(a2, b2, fma_(a1, b1, a0 * b0));
+}
+// p moved by the 3x4 row block G = [R | t] (a group pose), in place
+DEV void pose_point(const float *G, float *p)
+{
+    const float x = affine3(G[0], G[1], G[2], G[3], p[0], p[1], p[2]);
+    const float y = affine3(G[4], G[5], G[6], G[7], p[0], p[1], p[2]);
+    const float z = affine3(G[8], G[9], G[10], G[11], p[0], p[1], p[2]);
+    p[0] = x; p[1] = y; p[2] = z;
+}
+// q = the world point p in the camera frame of c
+DEV void to_camera(const SasCam &c, const float *p, float *q)
+{
+    q[0] = affine3(c.R[0], c.R[1], c.R[2], c.t[0], p[0], p[1], p[2]);
+    q[1] = affine3(c.R[3], c.R[4], c.R[5], c.t[1], p[0], p[1], p[2]);
+    q[2] = affine3(c.R[6], c.R[7], c.R[8], c.t[2], p[0], p[1], p[2]);
 }
 
 // out = R s R^T, s = xx xy xz yy yz zz

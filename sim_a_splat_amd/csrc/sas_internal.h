@@ -1,4 +1,4 @@
-// Shared between sas_kernels.hip (device code + launchers) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

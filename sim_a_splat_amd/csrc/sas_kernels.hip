@@ -25,6 +25,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -212,10 +213,15 @@ extern "C" int sas_debug_proj_laps(unsigned long long *geo, unsigned long long *
     if (hipMemcpyFromSymbol(geo, HIP_SYMBOL(g_dbg_plap), sizeof(unsigned long long) * 16 * m) != hipSuccess) return -1;
     return hipMemcpyFromSymbol(col, HIP_SYMBOL(g_dbg_pcol), sizeof(unsigned long long) * 2 * m) == hipSuccess ? 0 : -1;
 }
-#define PL_LAP(i) do { if (threadIdx.x == 0 && pl_wg_ < (unsigned)kDbgPMax) { const unsigned long long now_ = wall_clock64(); g_dbg_plap[16 * pl_wg_ + (i)] = now_ - pl_t_; pl_t_ = now_; } } while (0)
+#define PL_LAP(i) do { if (threadIdx.x == 0 && pl_.wg < (unsigned)kDbgPMax) { const unsigned long long now_ = wall_clock64(); g_dbg_plap[16 * pl_.wg + (i)] = now_ - pl_.t; pl_.t = now_; } } while (0)
 #else
 #define PL_LAP(i) do { } while (0)
 #endif
+// what PL_LAP books on: the geometry workgroup and the time of its previous lap (a phase with a lap in it takes `ProjLap &pl_`)
+struct ProjLap {
+    unsigned wg;
+    unsigned long long t;
+};
 
 template <typename F>
 DEV void for_each_tile(bool active, int x0, int x1, int y0, int y1, int tw, unsigned v0, unsigned v1, F emit)
@@ -254,6 +260,17 @@ struct Window {
     bool fits;
 };
 
+// the window of the participants' extrema [X0, X1) x [Y0, Y1)
+DEV Window window_of(int X0, int Y0, int X1, int Y1)
+{
+    Window w;
+    w.X0 = X0; w.Y0 = Y0;
+    w.ww = X1 - X0;
+    w.area = (X1 > X0 && Y1 > Y0) ? w.ww * (Y1 - Y0) : 0;
+    w.fits = w.area > 0 && w.area <= kHistBins;
+    return w;
+}
+
 DEV Window wg_window(bool part, int x0, int x1, int y0, int y1, int *s_win)
 {
     int mnx = part ? x0 : 0x7fffffff, mny = part ? y0 : 0x7fffffff;
@@ -267,13 +284,7 @@ DEV Window wg_window(bool part, int x0, int x1, int y0, int y1, int *s_win)
         atomicMax(&s_win[2], mxx); atomicMax(&s_win[3], mxy);
     }
     __syncthreads();
-    Window w;
-    w.X0 = s_win[0]; w.Y0 = s_win[1];
-    const int X1 = s_win[2], Y1 = s_win[3];
-    w.ww = X1 - w.X0;
-    w.area = (X1 > w.X0 && Y1 > w.Y0) ? w.ww * (Y1 - w.Y0) : 0;
-    w.fits = w.area > 0 && w.area <= kHistBins;
-    return w;
+    return window_of(s_win[0], s_win[1], s_win[2], s_win[3]);
 }
 
 // The projection's form of wg_window: ONE barrier instead of two and no LDS atomics -- every wave leaves its four extrema in
@@ -293,17 +304,16 @@ DEV Window wg_window_zeroed(bool part, int x0, int x1, int y0, int y1, int *s_wi
     __syncthreads();
     const int4 a = reinterpret_cast<const int4 *>(s_win16)[0], b = reinterpret_cast<const int4 *>(s_win16)[1],
                c = reinterpret_cast<const int4 *>(s_win16)[2], d = reinterpret_cast<const int4 *>(s_win16)[3];
-    Window w;
-    w.X0 = min(min(a.x, b.x), min(c.x, d.x));
-    w.Y0 = min(min(a.y, b.y), min(c.y, d.y));
-    const int X1 = max(max(a.z, b.z), max(c.z, d.z)), Y1 = max(max(a.w, b.w), max(c.w, d.w));
-    w.ww = X1 - w.X0;
-    w.area = (X1 > w.X0 && Y1 > w.Y0) ? w.ww * (Y1 - w.Y0) : 0;
-    w.fits = w.area > 0 && w.area <= kHistBins;
-    return w;
+    return window_of(min(min(a.x, b.x), min(c.x, d.x)), min(min(a.y, b.y), min(c.y, d.y)),
+                     max(max(a.z, b.z), max(c.z, d.z)), max(max(a.w, b.w), max(c.w, d.w)));
 }
 
 // ---- k_project: T1 + T2 + T3 + T5 ----------------------------------------------------------------
+// What the mean (camera depth cz) and the opacity decide alone: near / far plane, transparent.  Both roles of the projection ask
+// this one function, so the colour role skips exactly what the geometry role culls before it looks at the covariance.  (The
+// opacity test stands in front of T1's determinant test: it has no side effect before it.)
+DEV bool mean_survives(float cz, float op) { return !(cz < kNear || cz > kFar) && !(op < kAlphaThr); }
+
 // camera-dependent results of one Gaussian for one view
 struct ViewGeom {
     bool vis;
@@ -465,110 +475,140 @@ DEV void for_each_reached_tile(bool active, bool cull, const CullGeom &q, float 
     }
 }
 
-// a store the projection's tail may read from another XCD (see the hand-off rule in count_tiles)
+// a store the projection's tail may read from another XCD (see the hand-off rule at hand_off_visible_counts)
 DEV void agent_store(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// per-tile counts of one view: LDS histogram over the workgroup's window, one global atomic per
-// touched tile; then the workgroup's visible count.  Reached by all 256 threads.
-DEV void count_tiles(const SasFrame &f, int tw, int tile_px, const ViewGeom &g, unsigned slot, unsigned wg /* this workgroup's chunk of 256 Gaussians */, int *s_win, int *s_hist, int *s_base, int *s_nvis, unsigned long long &pl_t_)
+// ---- count_tiles: the binning of one view by one geometry workgroup, phase by phase (defined in call order) ----------
+// the workgroup's LDS: the window reduction's words, the window's bins (count, then rank), where the workgroup's run starts
+// inside each window tile's segment (single-pass binning), the two-pass hand-off's sums, the ticket's verdict
+struct ProjLds {
+    int *win, *hist, *base, *nvis, *last;
+};
+// what a lane brings to the binning of its Gaussian
+struct BinLane {
+    bool vis, in_win;   // in_win: the rectangle takes part in the window (1 .. kWinRect tiles)
+    int x0, x1, y0, y1, rect_area;
+    unsigned long long key;   // depth bits << 32 | storage slot
+    CullGeom cg;
+};
+DEV BinLane bin_lane(const ViewGeom &g, unsigned slot)
 {
-    const unsigned pl_wg_ = wg;
-    (void)pl_wg_;
-    const bool vis = g.vis;
-    const int seg = f.seg;   // (uniform) > 0: single-pass binning -- this workgroup EMITS its keys as well
-    const bool cull = f.cull != 0;   // (uniform; single-pass frames only) tiles the Gaussian cannot reach are left out: tile_reached
-    const CullGeom cg = cull_geom(g);
-    const float px = (float)tile_px;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(g.z) << 32) | (unsigned long long)slot;
-    const int x0 = g.x0, x1 = g.x1, y0 = g.y0, y1 = g.y1;
-    const int rect_area = vis ? (x1 - x0) * (y1 - y0) : 0;
-    const bool in_win = rect_area > 0 && rect_area <= kWinRect;
-    const Window w = wg_window_zeroed(in_win, x0, x1, y0, y1, s_win, s_hist);   // (the bins are zero behind its barrier)
-    PL_LAP(1);
-    unsigned long long reached = 0ull;   // the tiles of the rectangle that were counted (kept for the emit pass)
-    if (w.fits) {
-        if (in_win) {
-            int k = 0;   // tile k of the rectangle, row by row (at most kWinRect = 64 of them: one mask bit each)
-            for (int ty = y0; ty < y1; ++ty) {
-                const CullRow r = cull_row(cg, ty, px);
-                for (int tx = x0; tx < x1; ++tx, ++k) {
-                    const int b = (ty - w.Y0) * w.ww + (tx - w.X0);
-                    if (cull && !tile_reached(cg, r, tx, px)) continue;
-                    reached |= 1ull << k;
-                    if (SAS_IN(b, kHistBins, 101)) atomicAdd(&s_hist[b], 1);
-                }
-            }
-        }
-        __syncthreads();
-        PL_LAP(2);
-        // one RETURNING atomic per touched tile: the workgroup's run inside the tile's segment is reserved here, and
-        // k_scatter (same workgroup, same window) reads where it starts instead of reserving it itself
-        int *wb = f.wg_base + (size_t)wg * SAS_WIN_BINS;
-        {   // bin b = row * ww + col of the window, walked in steps of 256 bins without a division per step
-            const unsigned ww = (unsigned)w.ww, tid = threadIdx.x;
-            unsigned row = tid / ww, col = tid - row * ww;
-            const unsigned drow = 256u / ww, dcol = 256u - drow * ww;
+    BinLane l;
+    l.vis = g.vis;
+    l.cg = cull_geom(g);
+    l.key = ((unsigned long long)__float_as_uint(g.z) << 32) | (unsigned long long)slot;
+    l.x0 = g.x0; l.x1 = g.x1; l.y0 = g.y0; l.y1 = g.y1;
+    l.rect_area = l.vis ? (l.x1 - l.x0) * (l.y1 - l.y0) : 0;
+    l.in_win = l.rect_area > 0 && l.rect_area <= kWinRect;
+    return l;
+}
+
+// Every bin b of the window with its tile: fn(b, tile), b = row * ww + col, walked by the workgroup in steps of 256 bins
+// without a division per step.
+template <typename F>
+DEV void for_each_window_bin(const Window &w, int tw, F fn)
+{
+    const unsigned ww = (unsigned)w.ww, tid = threadIdx.x;
+    unsigned row = tid / ww, col = tid - row * ww;
+    const unsigned drow = 256u / ww, dcol = 256u - drow * ww;
 #pragma clang loop unroll(disable)
-            for (unsigned b = tid; b < (unsigned)w.area; b += 256u) {
-                const int cnt = s_hist[b];
-                const int tile = (w.Y0 + (int)row) * tw + w.X0 + (int)col;
-                const int base = (cnt && SAS_IN(tile, f.n_tiles, 102)) ? atomicAdd(&f.tile_count[tile], cnt) : 0;
-                if (seg > 0) {   // where the workgroup's run starts inside the tile's segment stays in LDS; the bin becomes its rank counter
-                    s_base[b] = base;
-                    s_hist[b] = 0;
-                } else {
-                    wb[b] = base;
-                }
-                row += drow;
-                col += dcol;
-                if (col >= ww) { col -= ww; ++row; }
+    for (unsigned b = tid; b < (unsigned)w.area; b += 256u) {
+        fn(b, (w.Y0 + (int)row) * tw + w.X0 + (int)col);
+        row += drow;
+        col += dcol;
+        if (col >= ww) { col -= ww; ++row; }
+    }
+}
+
+// cull and count pass: the lane's rectangle into the window's bins.  Returns the tiles of the rectangle that were counted
+// (kept for the emit pass): bit k = tile k of the rectangle, row by row (at most kWinRect = 64 of them).
+DEV unsigned long long count_window_tiles(const BinLane &l, const Window &w, bool cull, float px, int *s_hist)
+{
+    unsigned long long reached = 0ull;
+    if (l.in_win) {
+        int k = 0;
+        for (int ty = l.y0; ty < l.y1; ++ty) {
+            const CullRow r = cull_row(l.cg, ty, px);
+            for (int tx = l.x0; tx < l.x1; ++tx, ++k) {
+                const int b = (ty - w.Y0) * w.ww + (tx - w.X0);
+                if (cull && !tile_reached(l.cg, r, tx, px)) continue;
+                reached |= 1ull << k;
+                if (SAS_IN(b, kHistBins, 101)) atomicAdd(&s_hist[b], 1);
             }
         }
-        if (seg > 0) {
-            // single-pass binning: position = tile segment + the run's start + the key's rank inside the run (LDS atomic)
-            __syncthreads();
-            PL_LAP(3);
-            if (in_win)
-#pragma unroll 1
-                for (int ty = y0; ty < y1; ++ty)
-#pragma unroll 1
-                    for (int tx = x0; tx < x1; ++tx, reached >>= 1) {
-                        const int b = (ty - w.Y0) * w.ww + (tx - w.X0);
-                        if (!SAS_IN(b, kHistBins, 117)) continue;
-                        if (!(reached & 1ull)) continue;   // (what the count pass found)
-                        const int pos = s_base[b] + atomicAdd(&s_hist[b], 1);
-                        // pos >= seg: the tile has outgrown its segment (the tail reports it; the frame is rendered again)
-                        if (pos < seg && SAS_IN((long long)(ty * tw + tx) * seg + pos, f.cap, 118)) f.keys[(long long)(ty * tw + tx) * seg + pos] = key;
-                    }
-        }
-    } else if (threadIdx.x == 0 && w.area > 0) {
-        atomicAdd(&f.stats[5], 1u);
     }
-    PL_LAP(4);
-    if (seg > 0) {   // rectangles outside the window scheme: one returning atomic per intersection, the key goes where it points
-        for_each_reached_tile(vis && !(w.fits && in_win), cull, cg, px, x0, x1, y0, y1, tw, (unsigned)key, (unsigned)(key >> 32), [&](int tile, unsigned lo, unsigned hi) {
+    return reached;
+}
+
+// one RETURNING atomic per touched tile: the workgroup's run inside the tile's segment is reserved here, and
+// k_scatter (same workgroup, same window) reads where it starts instead of reserving it itself
+DEV void reserve_window_runs(const SasFrame &f, int seg, const Window &w, int tw, unsigned wg, const ProjLds &L)
+{
+    // (the LDS words are addressed as LDS: left as generic pointers, hipcc merges the last stores of the loop's two branches into one
+    // FLAT store through a selected pointer)
+    typedef __attribute__((address_space(3))) int lds_int;
+    lds_int *hist = (lds_int *)L.hist, *base_of = (lds_int *)L.base;
+    int *wb = f.wg_base + (size_t)wg * SAS_WIN_BINS;
+    for_each_window_bin(w, tw, [&](unsigned b, int tile) {
+        const int cnt = hist[b];
+        const int base = (cnt && SAS_IN(tile, f.n_tiles, 102)) ? atomicAdd(&f.tile_count[tile], cnt) : 0;
+        if (seg > 0) {   // where the workgroup's run starts inside the tile's segment stays in LDS; the bin becomes its rank counter
+            base_of[b] = base;
+            hist[b] = 0;
+        } else {
+            wb[b] = base;
+        }
+    });
+}
+
+// single-pass binning: position = tile segment + the run's start + the key's rank inside the run (LDS atomic)
+DEV void emit_window_keys(const SasFrame &f, int seg, const Window &w, int tw, const BinLane &l, unsigned long long reached, const ProjLds &L)
+{
+    if (l.in_win)
+#pragma unroll 1
+        for (int ty = l.y0; ty < l.y1; ++ty)
+#pragma unroll 1
+            for (int tx = l.x0; tx < l.x1; ++tx, reached >>= 1) {
+                const int b = (ty - w.Y0) * w.ww + (tx - w.X0);
+                if (!SAS_IN(b, kHistBins, 117)) continue;
+                if (!(reached & 1ull)) continue;   // (what the count pass found)
+                const int pos = L.base[b] + atomicAdd(&L.hist[b], 1);
+                // pos >= seg: the tile has outgrown its segment (the tail reports it; the frame is rendered again)
+                if (pos < seg && SAS_IN((long long)(ty * tw + tx) * seg + pos, f.cap, 118)) f.keys[(long long)(ty * tw + tx) * seg + pos] = l.key;
+            }
+}
+
+// rectangles outside the window scheme (too large for it, or the window did not fit the bins): one atomic per intersection --
+// single-pass frames: returning, the key goes where it points; two-pass frames: the count of the `big` entries
+DEV void bin_outside_window(const SasFrame &f, int seg, bool outside, int tw, const BinLane &l, bool cull, float px)
+{
+    if (seg > 0) {
+        for_each_reached_tile(outside, cull, l.cg, px, l.x0, l.x1, l.y0, l.y1, tw, (unsigned)l.key, (unsigned)(l.key >> 32), [&](int tile, unsigned lo, unsigned hi) {
             if (!SAS_IN(tile, f.n_tiles, 103)) return;
             const int pos = atomicAdd(&f.tile_count[tile], 1);
             if (pos < seg && SAS_IN((long long)tile * seg + pos, f.cap, 119)) f.keys[(long long)tile * seg + pos] = ((unsigned long long)hi << 32) | lo;
         });
     } else {
-        for_each_tile(vis && !(w.fits && in_win), x0, x1, y0, y1, tw, 0u, 0u,
+        for_each_tile(outside, l.x0, l.x1, l.y0, l.y1, tw, 0u, 0u,
                       [&](int tile, unsigned, unsigned) { if (SAS_IN(tile, f.n_tiles, 103)) atomicAdd(&f.tile_big[tile], 1); });
     }
-    PL_LAP(5);
-    // visible count (and the contract's 16-pixel intersections where the lists are not T3's).
-    const unsigned long long vb = __ballot(vis);
+}
+
+// visible count (and the contract's 16-pixel intersections where the lists are not T3's), handed to the tail.
+// HAND-OFF RULE (projection workgroups -> the tail, possibly on another XCD, whose L2 is not coherent with this one):
+// everything the tail reads from other workgroups must be written by an AGENT-scope atomic (performed where all XCDs
+// see it): the per-tile counts (atomicAdd on tile_count / tile_big), the window-miss counter, and the sums below.
+// A plain store here -- e.g. a vectorised store of counts -- would sit in this XCD's L2 and reach the
+// tail stale, silently; the bounds build checks the rule's effect (the tail: the sum it collects against a counter that
+// every wave also adds its count to atomically).
+DEV void hand_off_visible_counts(const SasFrame &f, int seg, int tile_px, const BinLane &l, unsigned wg, int *s_nvis)
+{
+    const unsigned long long vb = __ballot(l.vis);
     int a16 = 0;
     if (f.wg_isect16) {   // (uniform) 8-pixel binning, culled lists: the frame still reports the intersections with the contract's 16-pixel tiles
-        a16 = !vis ? 0 : tile_px == 8 ? (((x1 + 1) >> 1) - (x0 >> 1)) * (((y1 + 1) >> 1) - (y0 >> 1)) : rect_area;
+        a16 = !l.vis ? 0 : tile_px == 8 ? (((l.x1 + 1) >> 1) - (l.x0 >> 1)) * (((l.y1 + 1) >> 1) - (l.y0 >> 1)) : l.rect_area;
         a16 = wave_sum_i32(a16);
     }
-    // HAND-OFF RULE (projection workgroups -> the tail, possibly on another XCD, whose L2 is not coherent with this one):
-    // everything the tail reads from other workgroups must be written by an AGENT-scope atomic (performed where all XCDs
-    // see it): the per-tile counts (atomicAdd on tile_count / tile_big), the window-miss counter, and the sums below.
-    // A plain store here -- e.g. a vectorised store of counts -- would sit in this XCD's L2 and reach the
-    // tail stale, silently; the bounds build checks the rule's effect (the tail: the sum it collects against a counter that
-    // every wave also adds its count to atomically).
     if (seg > 0) {
         // single-pass frames: every WAVE adds its sums to words 1 and 2 of the workgroup's ticket line (64 lines, ~240 adds
         // each per frame: far from the rate at which one address serialises), where the tail's first wave finds all of them --
@@ -596,6 +636,35 @@ DEV void count_tiles(const SasFrame &f, int tw, int tile_px, const ViewGeom &g, 
 #endif
         }
     }
+}
+
+DEV void count_tiles(const SasFrame &f, int tw, int tile_px, const ViewGeom &g, unsigned slot, unsigned wg /* this workgroup's chunk of 256 Gaussians */, const ProjLds &L, ProjLap &pl_)
+{
+    const int seg = f.seg;           // (uniform) > 0: single-pass binning -- this workgroup EMITS its keys as well
+    const bool cull = f.cull != 0;   // (uniform; single-pass frames only) tiles the Gaussian cannot reach are left out: tile_reached
+    const float px = (float)tile_px;
+    const BinLane l = bin_lane(g, slot);
+    const bool vis = l.vis, in_win = l.in_win;   // (locals: read from l at their uses, hipcc lays out the branch on w.fits differently)
+    const Window w = wg_window_zeroed(in_win, l.x0, l.x1, l.y0, l.y1, L.win, L.hist);   // (the bins are zero behind its barrier)
+    PL_LAP(1);
+    unsigned long long reached = 0ull;
+    if (w.fits) {
+        reached = count_window_tiles(l, w, cull, px, L.hist);
+        __syncthreads();
+        PL_LAP(2);
+        reserve_window_runs(f, seg, w, tw, wg, L);
+        if (seg > 0) {
+            __syncthreads();
+            PL_LAP(3);
+            emit_window_keys(f, seg, w, tw, l, reached, L);
+        }
+    } else if (threadIdx.x == 0 && w.area > 0) {
+        atomicAdd(&f.stats[5], 1u);   // a window miss: every rectangle of the workgroup goes the way of bin_outside_window
+    }
+    PL_LAP(4);
+    bin_outside_window(f, seg, vis && !(w.fits && in_win), tw, l, cull, px);
+    PL_LAP(5);
+    hand_off_visible_counts(f, seg, tile_px, l, wg, L.nvis);
     PL_LAP(6);
 }
 
@@ -612,6 +681,44 @@ DEV void count_tiles(const SasFrame &f, int tw, int tile_px, const ViewGeom &g, 
 // workgroups of k_scatter, off this critical path.
 DEV int len_class(int v) { return v ? min(15, 32 - __clz(v)) : 0; }
 
+// The end of both tails, by thread 0: the classes' first positions from their sizes (class_size[k]: class 15 - k), the sort classes
+// of the full path, the end of the lists, the frame's statistics.  carry: the sum of all list lengths; overflow: a tile outgrew its
+// segment (single-pass) or the compact lists the key buffer (two-pass) -- the frame is rendered again.
+DEV void tail_publish(const SasFrame &f, const int *class_size, int carry, bool overflow, int nvis, int n16, int maxlen)
+{
+    const int tiles = f.n_tiles;
+    int start = 0;
+    for (int k = 0; k < 16; ++k) {   // descending classes: entry k = class 15 - k
+        f.class_cursor[k] = start;
+        // the full path's sort classes are class ranges, hence contiguous in tile_order
+        if (k == 3) f.sort_class[1] = start;   // mid:   1024..4095     (classes 11, 12)
+        if (k == 5) f.sort_class[2] = start;   // small: < 1024         (classes <= 10)
+        start += class_size[k];
+    }
+    f.sort_class[0] = 0;             // large: length >= 4096 (classes >= 13)
+    f.sort_class[3] = tiles;
+    f.sort_class[4] = 0;             // every tile, for the full-path blend
+    f.sort_class[5] = tiles;
+    f.tile_offset[tiles] = carry;
+    unsigned *h = f.stats_host;      // the statistics, straight to pinned host memory
+    h[0] = (unsigned)nvis;
+    h[1] = (unsigned)carry;
+    h[2] = overflow ? 1u : 0u;
+    h[3] = f.wg_isect16 ? (unsigned)n16 : (unsigned)carry;   // intersections with the contract's 16-pixel tiles
+    h[4] = (unsigned)maxlen;
+    h[5] = f.stats[5];
+    h[6] = 0u;
+    h[7] = 0u;
+    f.stats[5] = 0u;
+#ifdef SAS_DEBUG_BOUNDS
+    {   // self-check of the hand-off: what the tail summed from the workgroups (ticket-line adds / per-workgroup stores) == what they added to one counter atomically
+        const unsigned twin = __hip_atomic_load(&f.stats[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)SAS_IN((long long)nvis == (long long)twin ? 0 : -1, 1, 130);
+        f.stats[6] = 0u;
+    }
+#endif
+}
+
 // ---- the tail of a single-pass frame (the product path), round 5 ----------------------------------------------------
 // Per-workgroup laps (tools/proj_time.py) showed the tail of rounds 3-4 taking 17-21 us on the launch's critical path, not
 // the ~10 its ablation had suggested: three passes over the counts (each a dependent burst of L2 round trips per thread),
@@ -621,9 +728,8 @@ DEV int len_class(int v) { return v ? min(15, 32 - __clz(v)) : 0; }
 // bins are free by now: 40 448 groups; larger frames re-read their counts for the second pass), and places the groups from there.
 // lds: 2 * kHistBins ints.
 constexpr int kTailScratch = 16 + 512 + 512 + 512 + 16;   // cross-wave words, class bins, (class, copy) offsets, ranks, class totals
-DEV void scan_tail_single(const SasFrame *fp, int *lds, unsigned pl_wg_, unsigned long long &pl_t_)
+DEV void scan_tail_single(const SasFrame *fp, int *lds, ProjLap &pl_)
 {
-    (void)pl_wg_;
     const SasFrame &f = *fp;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int tiles = f.n_tiles;
@@ -725,37 +831,7 @@ DEV void scan_tail_single(const SasFrame *fp, int *lds, unsigned pl_wg_, unsigne
     if (tid == 0) {
         const int carry = s_w[0] + s_w[1] + s_w[2] + s_w[3];
         const int maxlen_all = max(max(s_w[4], s_w[5]), max(s_w[6], s_w[7]));
-        const int nvis_all = s_w[8];
-        const int n16_all = s_w[12];
-        int start = 0;
-        for (int k = 0; k < 16; ++k) {   // descending classes: entry k = class 15 - k
-            f.class_cursor[k] = start;
-            if (k == 3) f.sort_class[1] = start;
-            if (k == 5) f.sort_class[2] = start;
-            start += s_ctot[k];
-        }
-        f.sort_class[0] = 0;
-        f.sort_class[3] = tiles;
-        f.sort_class[4] = 0;
-        f.sort_class[5] = tiles;
-        f.tile_offset[tiles] = carry;
-        unsigned *h = f.stats_host;      // the statistics, straight to pinned host memory
-        h[0] = (unsigned)nvis_all;
-        h[1] = (unsigned)carry;
-        h[2] = maxlen_all > f.seg ? 1u : 0u;   // a tile outgrew its segment
-        h[3] = f.wg_isect16 ? (unsigned)n16_all : (unsigned)carry;   // intersections with the contract's 16-pixel tiles
-        h[4] = (unsigned)maxlen_all;
-        h[5] = f.stats[5];
-        h[6] = 0u;
-        h[7] = 0u;
-        f.stats[5] = 0u;
-#ifdef SAS_DEBUG_BOUNDS
-        {   // self-check of the hand-off: what the tail summed from the workgroups' adds on the ticket lines == what they added to one counter
-            const unsigned twin = __hip_atomic_load(&f.stats[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            (void)SAS_IN((long long)nvis_all == (long long)twin ? 0 : -1, 1, 130);
-            f.stats[6] = 0u;
-        }
-#endif
+        tail_publish(f, s_ctot, carry, maxlen_all > f.seg /* a tile outgrew its segment */, s_w[8], s_w[12], maxlen_all);
     }
     PL_LAP(13);
 }
@@ -863,38 +939,7 @@ DEV void scan_tail_two_pass(const SasFrame *fp, int *lds /* >= 1568 ints */)
         s_w[tid] = sum;
     }
     __syncthreads();
-    if (tid == 0) {
-        int start = 0;
-        for (int k = 0; k < 16; ++k) {   // descending classes: entry k = class 15 - k
-            f.class_cursor[k] = start;
-            // the full path's sort classes are class ranges, hence contiguous in tile_order
-            if (k == 3) f.sort_class[1] = start;   // mid:   1024..4095     (classes 11, 12)
-            if (k == 5) f.sort_class[2] = start;   // small: < 1024         (classes <= 10)
-            start += s_w[k];
-        }
-        f.sort_class[0] = 0;             // large: length >= 4096 (classes >= 13)
-        f.sort_class[3] = tiles;
-        f.sort_class[4] = 0;             // every tile, for the full-path blend
-        f.sort_class[5] = tiles;
-        f.tile_offset[tiles] = carry;
-        unsigned *h = f.stats_host;      // the statistics, straight to pinned host memory
-        h[0] = (unsigned)nvis_all;
-        h[1] = (unsigned)carry;
-        h[2] = (long long)carry > f.cap ? 1u : 0u;   // the compact lists outgrew the key buffer
-        h[3] = f.wg_isect16 ? (unsigned)n16_all : (unsigned)carry;   // intersections with the contract's 16-pixel tiles
-        h[4] = (unsigned)maxlen_all;
-        h[5] = f.stats[5];
-        h[6] = 0u;
-        h[7] = 0u;
-        f.stats[5] = 0u;
-#ifdef SAS_DEBUG_BOUNDS
-        {   // self-check of the hand-off: what the tail summed from the per-workgroup stores == what the workgroups added atomically
-            const unsigned twin = __hip_atomic_load(&f.stats[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            (void)SAS_IN((long long)nvis_all == (long long)twin ? 0 : -1, 1, 130);
-            f.stats[6] = 0u;
-        }
-#endif
-    }
+    if (tid == 0) tail_publish(f, s_w, carry, (long long)carry > f.cap /* the compact lists outgrew the key buffer */, nvis_all, n16_all, maxlen_all);
 }
 
 // Scene loads.  A view pair streams the colour planes once, non-temporally, so that they do not evict the records
@@ -962,113 +1007,70 @@ struct ProjArgs {
     float pose_rows[12 * kProjInlineRows];
 };
 
-// GEOMETRY role: T1 of Gaussians [256 wg, 256 wg + 256) for ONE view, then that view's binning; reached by all 256 threads.
-template <typename RowFn>
-DEV void geom_role(const SasScene &s, const SasCam &c, const SasFrame &f, unsigned wg, const float *poses, bool poses_inline,
-                   RowFn inline_row, int *s_win, int *s_hist, int *s_base, int *s_nvis, int *s_last)
+// ---- geom_role's phases (defined in call order) -----------------------------------------------------------------------
+// 3-D covariance in the world frame, from either scene encoding (a1, a2: quaternion + scale, or the six covariances), turned by the
+// group's rotation where the scene has poses
+DEV void world_covariance(bool cov_mode, const float4 &a1, const float4 &a2, bool hasG, const float *G, float *cov)
 {
-    const int64_t i = (int64_t)wg * 256 + threadIdx.x;
-    unsigned long long pl_t_ = 0ull;
-    const unsigned pl_wg_ = wg;
-    (void)pl_wg_;
-#ifdef SAS_TUNE_PTIME
-    pl_t_ = wall_clock64();
-    if (threadIdx.x == 0 && wg < (unsigned)kDbgPMax) g_dbg_plap[16 * wg + 14] = pl_t_;
-#endif
-    ViewGeom g;
-    g.vis = false; g.x0 = g.x1 = g.y0 = g.y1 = 0; g.z = 0.0f;
-    if (i < s.n) {
-        const float4 a0 = s.g0[i];
-        const float4 a1 = s.g1[i];
-        const float4 a2 = s.g2[i];
-        float m[3] = {a0.x, a0.y, a0.z};
-        const float op = a0.w;
-        float G[12] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
-        const bool hasG = group_pose(__float_as_uint(a2.w) & 255u, poses, poses_inline, inline_row, G);
+    if (!cov_mode) {
+        float qw = a1.x, qx = a1.y, qy = a1.z, qz = a1.w;
+        float n2 = fma_(qz, qz, fma_(qy, qy, fma_(qx, qx, qw * qw)));
+        float inv = 1.0f / sqrtf(n2);
+        qw *= inv; qx *= inv; qy *= inv; qz *= inv;
+        float x2 = qx * qx, y2 = qy * qy, z2 = qz * qz;
+        float xy = qx * qy, xz = qx * qz, yz = qy * qz;
+        float wx = qw * qx, wy = qw * qy, wz = qw * qz;
+        float R[9];
+        R[0] = fma_(-2.0f, y2 + z2, 1.0f); R[1] = 2.0f * (xy - wz);           R[2] = 2.0f * (xz + wy);
+        R[3] = 2.0f * (xy + wz);           R[4] = fma_(-2.0f, x2 + z2, 1.0f); R[5] = 2.0f * (yz - wx);
+        R[6] = 2.0f * (xz - wy);           R[7] = 2.0f * (yz + wx);           R[8] = fma_(-2.0f, x2 + y2, 1.0f);
         if (hasG) {
-            float mg0 = affine3(G[0], G[1], G[2], G[3], m[0], m[1], m[2]);
-            float mg1 = affine3(G[4], G[5], G[6], G[7], m[0], m[1], m[2]);
-            float mg2 = affine3(G[8], G[9], G[10], G[11], m[0], m[1], m[2]);
-            m[0] = mg0; m[1] = mg1; m[2] = mg2;
+            float R2[9];
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    R2[3 * r + k] = dot3(G[4 * r + 0], G[4 * r + 1], G[4 * r + 2], R[0 + k], R[3 + k], R[6 + k]);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) R[k] = R2[k];
         }
-        const float cx = affine3(c.R[0], c.R[1], c.R[2], c.t[0], m[0], m[1], m[2]);   // argument segment: scalar loads
-        const float cy = affine3(c.R[3], c.R[4], c.R[5], c.t[1], m[0], m[1], m[2]);
-        const float cz = affine3(c.R[6], c.R[7], c.R[8], c.t[2], m[0], m[1], m[2]);
-        bool ok = !(cz < kNear || cz > kFar);
-        ok = ok && !(op < kAlphaThr);   // opacity cull moved up: it has no side effect before the det test
-        if (ok) {
-            // 3-D covariance in the world (group) frame
-            float cov[6];
-            if (!s.cov_mode) {
-                float qw = a1.x, qx = a1.y, qy = a1.z, qz = a1.w;
-                float n2 = fma_(qz, qz, fma_(qy, qy, fma_(qx, qx, qw * qw)));
-                float inv = 1.0f / sqrtf(n2);
-                qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-                float x2 = qx * qx, y2 = qy * qy, z2 = qz * qz;
-                float xy = qx * qy, xz = qx * qz, yz = qy * qz;
-                float wx = qw * qx, wy = qw * qy, wz = qw * qz;
-                float R[9];
-                R[0] = fma_(-2.0f, y2 + z2, 1.0f); R[1] = 2.0f * (xy - wz);           R[2] = 2.0f * (xz + wy);
-                R[3] = 2.0f * (xy + wz);           R[4] = fma_(-2.0f, x2 + z2, 1.0f); R[5] = 2.0f * (yz - wx);
-                R[6] = 2.0f * (xz - wy);           R[7] = 2.0f * (yz + wx);           R[8] = fma_(-2.0f, x2 + y2, 1.0f);
-                if (hasG) {
-                    float R2[9];
+        const float sc[3] = {a2.x, a2.y, a2.z};
+        float M[9];
 #pragma unroll
-                    for (int r = 0; r < 3; ++r)
+        for (int r = 0; r < 3; ++r)
 #pragma unroll
-                        for (int k = 0; k < 3; ++k)
-                            R2[3 * r + k] = dot3(G[4 * r + 0], G[4 * r + 1], G[4 * r + 2], R[0 + k], R[3 + k], R[6 + k]);
+            for (int k = 0; k < 3; ++k) M[3 * r + k] = R[3 * r + k] * sc[k];
+        cov[0] = dot3(M[0], M[1], M[2], M[0], M[1], M[2]);
+        cov[1] = dot3(M[0], M[1], M[2], M[3], M[4], M[5]);
+        cov[2] = dot3(M[0], M[1], M[2], M[6], M[7], M[8]);
+        cov[3] = dot3(M[3], M[4], M[5], M[3], M[4], M[5]);
+        cov[4] = dot3(M[3], M[4], M[5], M[6], M[7], M[8]);
+        cov[5] = dot3(M[6], M[7], M[8], M[6], M[7], M[8]);
+    } else {
+        cov[0] = a1.x; cov[1] = a1.y; cov[2] = a1.z; cov[3] = a1.w; cov[4] = a2.x; cov[5] = a2.y;
+        if (hasG) {
+            const float Rg[9] = {G[0], G[1], G[2], G[4], G[5], G[6], G[8], G[9], G[10]};
+            float c2[6];
+            rot_sym3(Rg, cov, c2);
 #pragma unroll
-                    for (int k = 0; k < 9; ++k) R[k] = R2[k];
-                }
-                const float sc[3] = {a2.x, a2.y, a2.z};
-                float M[9];
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) M[3 * r + k] = R[3 * r + k] * sc[k];
-                cov[0] = dot3(M[0], M[1], M[2], M[0], M[1], M[2]);
-                cov[1] = dot3(M[0], M[1], M[2], M[3], M[4], M[5]);
-                cov[2] = dot3(M[0], M[1], M[2], M[6], M[7], M[8]);
-                cov[3] = dot3(M[3], M[4], M[5], M[3], M[4], M[5]);
-                cov[4] = dot3(M[3], M[4], M[5], M[6], M[7], M[8]);
-                cov[5] = dot3(M[6], M[7], M[8], M[6], M[7], M[8]);
-            } else {
-                cov[0] = a1.x; cov[1] = a1.y; cov[2] = a1.z; cov[3] = a1.w; cov[4] = a2.x; cov[5] = a2.y;
-                if (hasG) {
-                    const float Rg[9] = {G[0], G[1], G[2], G[4], G[5], G[6], G[8], G[9], G[10]};
-                    float c2[6];
-                    rot_sym3(Rg, cov, c2);
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) cov[k] = c2[k];
-                }
-            }
-            project_view(c, cov, op, cx, cy, cz, g);
-        }
-        if (g.vis) {
-            f.rec[SAS_RS * i + 0] = make_float4(g.mx, g.my, g.ca, g.cb);
-            f.rec[SAS_RS * i + 1] = make_float4(g.ccn, op, g.thr, g.z);
-            // radii (parity hook only): full 32 bits each (a camera inside the cloud produces radii beyond 65535
-            // pixels); saturated to INT_MAX
-            const int irx = (int)fminf(g.rx, 2147483520.0f), iry = (int)fminf(g.ry, 2147483520.0f);
-            if (f.keep_info) f.info[i] = make_uint4((unsigned)g.x0 | ((unsigned)g.x1 << 16), (unsigned)g.y0 | ((unsigned)g.y1 << 16), (unsigned)irx, (unsigned)iry);
-        } else if (f.keep_info) {
-            f.info[i] = make_uint4(0u, 0u, 0u, 0u);
+            for (int k = 0; k < 6; ++k) cov[k] = c2[k];
         }
     }
-    PL_LAP(0);
-    count_tiles(f, c.tw, c.tile_px, g, (unsigned)i, wg, s_win, s_hist, s_base, s_nvis, pl_t_);
-    // ---- the last geometry workgroup of the view to get here scans the counts of its frame.
-    // Everything the tail reads from other workgroups was written by AGENT-scope atomics (the per-tile counts, the
-    // window-miss counter, wg_vis), which are performed at the point all XCDs share; what remains is ordering:
-    // every wave waits until its own outstanding stores and atomics have been acknowledged (s_waitcnt vmcnt(0) -- the
-    // wait an agent-scope release consists of, without its cache write-back; a workgroup-scope fence compiles to
-    // nothing here), the barrier collects the waves, then thread 0 takes the ticket.  A __threadfence() in this place
-    // -- a write-back of the XCD's whole L2 by every workgroup while the projection streams 60 MB of records through
-    // it -- cost 740 us per launch.
-    // The ticket has two levels: same-address atomics serialise at ~90 per us at the memory side, and 3 907
-    // workgroups taking one counter cost the projection 23 us; 64 sub-counters (one cache line each) take ~61
-    // tickets each, the last taker of each takes one of 64 master tickets.
+}
+
+// Whether this is the last geometry workgroup of the view to get here: that one scans the counts of its frame.
+// Everything the tail reads from other workgroups was written by AGENT-scope atomics (the per-tile counts, the
+// window-miss counter, wg_vis), which are performed at the point all XCDs share; what remains is ordering:
+// every wave waits until its own outstanding stores and atomics have been acknowledged (s_waitcnt vmcnt(0) -- the
+// wait an agent-scope release consists of, without its cache write-back; a workgroup-scope fence compiles to
+// nothing here), the barrier collects the waves, then thread 0 takes the ticket.  A __threadfence() in this place
+// -- a write-back of the XCD's whole L2 by every workgroup while the projection streams 60 MB of records through
+// it -- cost 740 us per launch.
+// The ticket has two levels: same-address atomics serialise at ~90 per us at the memory side, and 3 907
+// workgroups taking one counter cost the projection 23 us; 64 sub-counters (one cache line each) take ~61
+// tickets each, the last taker of each takes one of 64 master tickets.
+DEV bool last_workgroup_of_view(const SasFrame &f, unsigned wg, int *s_last, ProjLap &pl_)
+{
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     PL_LAP(7);
@@ -1086,13 +1088,66 @@ DEV void geom_role(const SasScene &s, const SasCam &c, const SasFrame &f, unsign
     }
     __syncthreads();
     PL_LAP(8);
+    return *s_last != 0;
+}
+
+// the view's tail, by its last geometry workgroup (lds: the window's bins, free by now)
+DEV void view_tail(const SasFrame &f, int *lds, ProjLap &pl_)
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the tail's loads below are not served from a stale cache line
+    if (f.seg > 0) scan_tail_single(&f, lds, pl_);   // (uniform)
+    else scan_tail_two_pass(&f, lds);
+}
+
+// GEOMETRY role: T1 of Gaussians [256 wg, 256 wg + 256) for ONE view, then that view's binning; reached by all 256 threads.
+template <typename RowFn>
+DEV void geom_role(const SasScene &s, const SasCam &c, const SasFrame &f, unsigned wg, const float *poses, bool poses_inline,
+                   RowFn inline_row, const ProjLds &L)
+{
+    const int64_t i = (int64_t)wg * 256 + threadIdx.x;
+    ProjLap pl_{wg, 0ull};
+#ifdef SAS_TUNE_PTIME
+    pl_.t = wall_clock64();
+    if (threadIdx.x == 0 && wg < (unsigned)kDbgPMax) g_dbg_plap[16 * wg + 14] = pl_.t;
+#endif
+    ViewGeom g;
+    g.vis = false; g.x0 = g.x1 = g.y0 = g.y1 = 0; g.z = 0.0f;
+    if (i < s.n) {
+        const float4 a0 = s.g0[i];
+        const float4 a1 = s.g1[i];
+        const float4 a2 = s.g2[i];
+        float m[3] = {a0.x, a0.y, a0.z};
+        const float op = a0.w;
+        float G[12] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+        const bool hasG = group_pose(__float_as_uint(a2.w) & 255u, poses, poses_inline, inline_row, G);
+        if (hasG) pose_point(G, m);
+        float q[3];
+        to_camera(c, m, q);   // (c: argument segment, scalar loads)
+        if (mean_survives(q[2], op)) {
+            float cov[6];
+            world_covariance(s.cov_mode != 0, a1, a2, hasG, G, cov);
+            project_view(c, cov, op, q[0], q[1], q[2], g);
+        }
+        // the record stores (written out: as a function of its own they cost the kernel eleven vector instructions, docs/EXPERIMENTS.md R5.5)
+        if (g.vis) {
+            f.rec[SAS_RS * i + 0] = make_float4(g.mx, g.my, g.ca, g.cb);
+            f.rec[SAS_RS * i + 1] = make_float4(g.ccn, op, g.thr, g.z);
+            // radii (parity hook only): full 32 bits each (a camera inside the cloud produces radii beyond 65535
+            // pixels); saturated to INT_MAX
+            const int irx = (int)fminf(g.rx, 2147483520.0f), iry = (int)fminf(g.ry, 2147483520.0f);
+            if (f.keep_info) f.info[i] = make_uint4((unsigned)g.x0 | ((unsigned)g.x1 << 16), (unsigned)g.y0 | ((unsigned)g.y1 << 16), (unsigned)irx, (unsigned)iry);
+        } else if (f.keep_info) {
+            f.info[i] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+    PL_LAP(0);
+    count_tiles(f, c.tw, c.tile_px, g, (unsigned)i, wg, L, pl_);
+    const bool last = last_workgroup_of_view(f, wg, L.last, pl_);
 #ifdef SAS_TUNE_PTIME
     if (threadIdx.x == 0 && wg < (unsigned)kDbgPMax) g_dbg_plap[16 * wg + 15] = wall_clock64();
 #endif
-    if (!*s_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the tail's loads below are not served from a stale cache line
-    if (f.seg > 0) scan_tail_single(&f, s_hist, pl_wg_, pl_t_);   // (uniform)
-    else scan_tail_two_pass(&f, s_hist);
+    if (!last) return;
+    view_tail(f, L.hist, pl_);
     PL_LAP(9);
 #ifdef SAS_TUNE_PTIME
     if (threadIdx.x == 0 && wg < (unsigned)kDbgPMax) g_dbg_plap[16 * wg + 15] = wall_clock64();
@@ -1101,8 +1156,8 @@ DEV void geom_role(const SasScene &s, const SasCam &c, const SasFrame &f, unsign
 
 // COLOUR role: T2 of Gaussians [256 wg, 256 wg + 256) for every view of the launch.  A pure stream: no LDS, no barrier.
 // The colour of a Gaussian that the geometry role culls (off screen, degenerate) is computed all the same -- nobody
-// reads it; only what is decided by the mean and the opacity alone is decided here too, with the geometry role's own
-// expressions (near / far plane, transparent), so that scenes mostly behind the camera do not stream their planes.
+// reads it; only what is decided by the mean and the opacity alone is decided here too, by the geometry role's own
+// function (mean_survives: near / far plane, transparent), so that scenes mostly behind the camera do not stream their planes.
 // Contract T2 (round 5): a colour is FINITE when it leaves the projection: clamped to +-FLT_MAX (the identity on every finite value; a
 // NaN becomes -FLT_MAX).  The compositing loop adds every staged entry to every pixel of its block with weight +0 where the entry is
 // skipped -- exact for finite colours, but 0 * Inf = NaN would spread one bad SH coefficient over whole blocks.
@@ -1120,19 +1175,14 @@ DEV void color_role(const SasScene &s, const ProjArgs &vs, unsigned wg, const fl
     const float op = a0.w;
     if (s.n_groups > 0) {   // (uniform)
         float G[12] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
-        if (group_pose((unsigned)s.gid8[i], poses, poses_inline, inline_row, G)) {
-            float mg0 = affine3(G[0], G[1], G[2], G[3], m[0], m[1], m[2]);
-            float mg1 = affine3(G[4], G[5], G[6], G[7], m[0], m[1], m[2]);
-            float mg2 = affine3(G[8], G[9], G[10], G[11], m[0], m[1], m[2]);
-            m[0] = mg0; m[1] = mg1; m[2] = mg2;
-        }
+        if (group_pose((unsigned)s.gid8[i], poses, poses_inline, inline_row, G)) pose_point(G, m);
     }
     bool ok[NV], any_ok = false;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-        const SasCam &c = vs.cam[v];
-        const float cz = affine3(c.R[6], c.R[7], c.R[8], c.t[2], m[0], m[1], m[2]);
-        ok[v] = !(cz < kNear || cz > kFar) && !(op < kAlphaThr);
+        float q[3];
+        to_camera(vs.cam[v], m, q);   // (only the depth is used)
+        ok[v] = mean_survives(q[2], op);
         any_ok = any_ok || ok[v];
     }
     if (!any_ok) return;
@@ -1221,17 +1271,24 @@ __host__ DEV Role block_role(unsigned b, unsigned n_geo, unsigned mix_k)
     return r;
 }
 
+// The LDS of a projection block, declared once for both kernels (each gets its own 16 460 bytes).  The role dispatch below it
+// is written per kernel: what it hands to the roles -- poses, pose_inline, the inline rows -- is read from the kernel's own
+// argument at the place of use (no address of it is taken, no load is hoisted in front of the role branch).
+DEV ProjLds proj_lds()
+{
+    __shared__ __attribute__((aligned(16))) int s_win[16];
+    __shared__ __attribute__((aligned(16))) int s_bins2[2 * kHistBins];   // one block: the tail uses all 16 KiB of it
+    __shared__ int s_nvis[2];
+    __shared__ int s_last;
+    return ProjLds{s_win, s_bins2, s_bins2 + kHistBins, s_nvis, &s_last};
+}
+
 // grid.x = (NV + 1) * n_wg: NV * n_wg geometry blocks (view = index % NV: the views' blocks of one chunk of Gaussians are
 // neighbours in dispatch order and share its 48 bytes through the cache) and n_wg colour blocks
 template <int DEG, int NV>
 __global__ __launch_bounds__(256) void k_project(SasScene s, ProjArgs vs)
 {
-    __shared__ __attribute__((aligned(16))) int s_win[16];
-    __shared__ __attribute__((aligned(16))) int s_bins2[2 * kHistBins];   // one block: the tail uses all 16 KiB of it
-    int *const s_hist = s_bins2;
-    int *const s_base = s_bins2 + kHistBins;   // single-pass binning: start of the workgroup's run inside each window tile's segment
-    __shared__ int s_nvis[2];
-    __shared__ int s_last;
+    const ProjLds L = proj_lds();
     const unsigned n_wg = (unsigned)vs.f[0].n_wg;
     const Role r = block_role(blockIdx.x, (unsigned)NV * kSpreadRows * spread_cols(n_wg), (unsigned)vs.mix_k);
     auto row = [&](unsigned g, int k) { return vs.pose_rows[12u * g + (unsigned)k]; };
@@ -1243,22 +1300,15 @@ __global__ __launch_bounds__(256) void k_project(SasScene s, ProjArgs vs)
     if (wg >= n_wg) return;
     // (two inlined copies for a pair, chosen by a uniform branch: the view's camera and frame are then read from the
     // argument segment at constant offsets; indexing them by a run-time view would copy them to registers or scratch)
-    if (NV == 1 || (r.idx & 1u) == 0u)
-        geom_role(s, vs.cam[0], vs.f[0], wg, vs.f[0].group_Rt, vs.pose_inline != 0, row, s_win, s_hist, s_base, s_nvis, &s_last);
-    else
-        geom_role(s, vs.cam[1], vs.f[1], wg, vs.f[0].group_Rt, vs.pose_inline != 0, row, s_win, s_hist, s_base, s_nvis, &s_last);
+    if (NV == 1 || (r.idx & 1u) == 0u) geom_role(s, vs.cam[0], vs.f[0], wg, vs.f[0].group_Rt, vs.pose_inline != 0, row, L);
+    else geom_role(s, vs.cam[1], vs.f[1], wg, vs.f[0].group_Rt, vs.pose_inline != 0, row, L);
 }
 
 // all views of a group in one launch: blockIdx.y = view, one pass over the (small) scene per view, both roles per view
 template <int DEG>
 __global__ __launch_bounds__(256) void k_project_multi(SasScene s, SasMulti mf)
 {
-    __shared__ __attribute__((aligned(16))) int s_win[16];
-    __shared__ __attribute__((aligned(16))) int s_bins2[2 * kHistBins];
-    int *const s_hist = s_bins2;
-    int *const s_base = s_bins2 + kHistBins;
-    __shared__ int s_nvis[2];
-    __shared__ int s_last;
+    const ProjLds L = proj_lds();
     ProjArgs vs;
     vs.cam[0] = vs.cam[1] = mf.P[blockIdx.y].cam;
     vs.f[0] = vs.f[1] = mf.f[blockIdx.y];
@@ -1272,7 +1322,7 @@ __global__ __launch_bounds__(256) void k_project_multi(SasScene s, SasMulti mf)
     }
     const unsigned wg = spread_chunk(r.idx, n_wg);
     if (wg >= n_wg) return;
-    geom_role(s, vs.cam[0], vs.f[0], wg, mf.f[blockIdx.y].group_Rt, mf.pose_inline != 0, row, s_win, s_hist, s_base, s_nvis, &s_last);
+    geom_role(s, vs.cam[0], vs.f[0], wg, mf.f[blockIdx.y].group_Rt, mf.pose_inline != 0, row, L);
 }
 
 // ---- small kernels around a frame ---------------------------------------------------------------------
@@ -1309,11 +1359,6 @@ __global__ __launch_bounds__(256) void k_host_copy(SasHostCopy h)
     }
 }
 
-// ---- k_scatter: T3 emit ---------------------------------------------------------------------------
-// Same window as k_project: count in LDS, reserve one contiguous run per touched tile with a
-// single returning global atomic, then rank inside the run with LDS atomics.  Key = depth bits << 32
-// | storage slot; the rare runs of identical depth are ordered by the caller's index (perm[slot])
-// when a tile is sorted, exactly as the reference's stable sort orders them.
 // ---- k_scatter: T3 emit + tile order --------------------------------------------------------------------------
 // Binning workgroups (one per projection workgroup, same 256 Gaussians, same window): the projection has already
 // reserved this workgroup's run in every tile its window touches (wg_base), so a key's position is
@@ -1378,20 +1423,10 @@ DEV void scatter_body(const SasScene &s, int tw, const SasFrame &f)
     const Window w = wg_window(in_win, x0, x1, y0, y1, s_win);
     if (w.fits) {
         const int *wb = f.wg_base + (size_t)wg * SAS_WIN_BINS;
-        {   // bin b = row * ww + col of the window, walked in steps of 256 bins without a division per step
-            const unsigned ww = (unsigned)w.ww, tid = threadIdx.x;
-            unsigned row = tid / ww, col = tid - row * ww;
-            const unsigned drow = 256u / ww, dcol = 256u - drow * ww;
-#pragma clang loop unroll(disable)
-            for (unsigned b = tid; b < (unsigned)w.area; b += 256u) {
-                const int tile = (w.Y0 + (int)row) * tw + w.X0 + (int)col;
-                s_base[b] = SAS_IN(tile, f.n_tiles, 112) ? f.tile_offset[tile] + wb[b] : 0;
-                s_hist[b] = 0;
-                row += drow;
-                col += dcol;
-                if (col >= ww) { col -= ww; ++row; }
-            }
-        }
+        for_each_window_bin(w, tw, [&](unsigned b, int tile) {
+            s_base[b] = SAS_IN(tile, f.n_tiles, 112) ? f.tile_offset[tile] + wb[b] : 0;
+            s_hist[b] = 0;
+        });
         __syncthreads();
         if (in_win)
 #pragma unroll 1
@@ -1469,18 +1504,25 @@ extern "C" int sas_debug_projection_block(unsigned b, unsigned n_wg, int nv, uns
     return 0;
 }
 
+// fn(std::integral_constant<int, DEG>): the run-time SH degree as the kernels' template argument (-1: plain colours)
+template <typename Fn>
+static void with_degree(int sh_degree, Fn fn)
+{
+    switch (sh_degree) {
+        case 0: fn(std::integral_constant<int, 0>{}); break;
+        case 1: fn(std::integral_constant<int, 1>{}); break;
+        case 2: fn(std::integral_constant<int, 2>{}); break;
+        case 3: fn(std::integral_constant<int, 3>{}); break;
+        default: fn(std::integral_constant<int, -1>{}); break;
+    }
+}
+
 template <int NV>
 static void launch_project(hipStream_t st, const SasScene &s, const ProjArgs &vs)
 {
     const unsigned n_wg = (unsigned)vs.f[0].n_wg;   // >= 1: an empty scene still takes the tail
     const unsigned grid = (unsigned)NV * sas_spread_blocks(n_wg) + n_wg;   // geometry blocks (per view, padded to the spread's rows) + colour blocks
-    switch (s.sh_degree) {
-        case 0: hipLaunchKernelGGL((k_project<0, NV>), dim3(grid), dim3(256), 0, st, s, vs); break;
-        case 1: hipLaunchKernelGGL((k_project<1, NV>), dim3(grid), dim3(256), 0, st, s, vs); break;
-        case 2: hipLaunchKernelGGL((k_project<2, NV>), dim3(grid), dim3(256), 0, st, s, vs); break;
-        case 3: hipLaunchKernelGGL((k_project<3, NV>), dim3(grid), dim3(256), 0, st, s, vs); break;
-        default: hipLaunchKernelGGL((k_project<-1, NV>), dim3(grid), dim3(256), 0, st, s, vs); break;
-    }
+    with_degree(s.sh_degree, [&](auto deg) { hipLaunchKernelGGL((k_project<decltype(deg)::value, NV>), dim3(grid), dim3(256), 0, st, s, vs); });
 }
 
 static void inline_poses(ProjArgs &vs, const SasScene &s)
@@ -1522,13 +1564,7 @@ void sas_launch_project_multi(hipStream_t st, const SasScene &s, const SasMulti 
     }
     mf.mix_k = project_mix(1, (unsigned)mf.f[0].n_wg);
     const dim3 grid(sas_spread_blocks((unsigned)mf.f[0].n_wg) + (unsigned)mf.f[0].n_wg, (unsigned)mf.nv);   // geometry + colour blocks per view
-    switch (s.sh_degree) {
-        case 0: hipLaunchKernelGGL((k_project_multi<0>), grid, dim3(256), 0, st, s, mf); break;
-        case 1: hipLaunchKernelGGL((k_project_multi<1>), grid, dim3(256), 0, st, s, mf); break;
-        case 2: hipLaunchKernelGGL((k_project_multi<2>), grid, dim3(256), 0, st, s, mf); break;
-        case 3: hipLaunchKernelGGL((k_project_multi<3>), grid, dim3(256), 0, st, s, mf); break;
-        default: hipLaunchKernelGGL((k_project_multi<-1>), grid, dim3(256), 0, st, s, mf); break;
-    }
+    with_degree(s.sh_degree, [&](auto deg) { hipLaunchKernelGGL((k_project_multi<decltype(deg)::value>), grid, dim3(256), 0, st, s, mf); });
 }
 
 void sas_launch_scatter_multi(hipStream_t st, const SasScene &s, int tw, const SasMulti &mf)

@@ -138,16 +138,11 @@ __global__ __launch_bounds__(kMeshSetupThreads) void k_mesh_setup(SasMeshScene m
     for (int k = 0; k < 3; ++k) {
         if (!SAS_IN(ids[k], m.nv, 301)) return;
         const float4 p = m.vert[ids[k]];
-        float x = p.x, y = p.y, z = p.z;
-        if (G) {
-            const float x2 = affine3(G[0], G[1], G[2], G[3], x, y, z), y2 = affine3(G[4], G[5], G[6], G[7], x, y, z),
-                        z2 = affine3(G[8], G[9], G[10], G[11], x, y, z);
-            x = x2; y = y2; z = z2;
-        }
-        wv[k][0] = x; wv[k][1] = y; wv[k][2] = z;
-        q[k].x = affine3(c.R[0], c.R[1], c.R[2], c.t[0], x, y, z);
-        q[k].y = affine3(c.R[3], c.R[4], c.R[5], c.t[1], x, y, z);
-        q[k].z = affine3(c.R[6], c.R[7], c.R[8], c.t[2], x, y, z);
+        float w[3] = {p.x, p.y, p.z}, cq[3];
+        if (G) pose_point(G, w);
+        wv[k][0] = w[0]; wv[k][1] = w[1]; wv[k][2] = w[2];
+        to_camera(c, w, cq);
+        q[k].x = cq[0]; q[k].y = cq[1]; q[k].z = cq[2];
         ok = ok && isfinite(q[k].x) && isfinite(q[k].y) && isfinite(q[k].z);
     }
     if (!ok) return;

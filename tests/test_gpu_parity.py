@@ -1004,6 +1004,13 @@ def test_single_pass_and_two_pass_binning_render_the_same_frames(monkeypatch):
     scams = [ring_camera(320, 240, 260.0, yaw_deg=72.0 * k) for k in range(5)]
     sV, sK = np.stack([c.viewmat for c in scams]), np.stack([c.K for c in scams])
     ref = oracle.render_scene(sc, cams[0], background=BG)
+    # A window miss: one projection workgroup (256 Gaussians, 210 of them visible) whose small rectangles (the largest covers 12
+    # tiles: all take part in the window) are spread over the whole 1280x720 view -- from oracle.render(..., dump=True), seed 91,
+    # the bounding box of the visible rectangles is 80 x 45 = 3 600 tiles, above the 2 048 bins of the window: the workgroup
+    # counts the miss and bins every rectangle with per-intersection atomics.
+    wide = make_scene(256, seed=91, log_scale_mean=float(np.log(0.004)))
+    wcam = ring_camera(1280, 720, 1500.0)
+    wref = oracle.render_scene(wide, wcam, background=BG)
     frames = {}
     for mode, env in (("single-pass", {"SAS_DIRECT": "1"}), ("two-pass", {"SAS_DIRECT": "0"}), ("budget", {"SAS_DIRECT": "1", "SAS_DIRECT_BUDGET_MB": "1"})):
         for k, v in env.items():
@@ -1019,6 +1026,12 @@ def test_single_pass_and_two_pass_binning_render_the_same_frames(monkeypatch):
         r.set_group_poses(random_group_poses(3, seed=9))
         out.append(r.render_batch(sV, sK, 320, 240, BG, want=("rgb8",))["rgb8"].cpu().numpy())
         frames[mode] = out
+        _upload(r, wide)
+        w = r.render(wcam.viewmat, wcam.K, 1280, 720, BG, want=("rgb", "alpha", "depth"))
+        st = r.stats()
+        assert st["window_misses"] >= 1 and st["n_isect"] == wref["n_isect"], (mode, st)
+        for name in ("rgb", "alpha", "depth"):
+            assert np.array_equal(w[name].cpu().numpy(), wref[name]), (mode, name)
         r.close()
         monkeypatch.delenv("SAS_DIRECT_BUDGET_MB", raising=False)
     assert np.array_equal(frames["single-pass"][0], ref["rgb"]) and np.array_equal(frames["single-pass"][3][0], ref["rgb"])

@@ -54,6 +54,7 @@ def audit(lines):
     loops = OrderedDict()          # header -> (depth, parent)
     per = defaultdict(lambda: defaultdict(int))
     cur = "(outside loops)"
+    label = None                   # the last labelled block
     hazards = []
     recent = []                    # (dst regs) of the last VALU instructions
     for ln, l in enumerate(lines):
@@ -72,12 +73,15 @@ def audit(lines):
                 loops.setdefault(cur, int(mh.group(2)))
             elif "Loop" not in c:
                 cur = "(outside loops)"
+            label = m.group(1)[2:] if m else None
             continue
         s = l.strip()
         if not s or s.startswith((";", ".")):
             # continuation comment lines of a header ("Parent Loop ... / => This Inner Loop Header: Depth=3")
             mm = re.search(r"This (?:Inner )?Loop Header: Depth=(\d+)", s)
             if mm:
+                if label:   # (a header whose label line carries the block's name only: the loop starts at that label)
+                    cur = label
                 loops[cur] = int(mm.group(1))
             # ... and of a labelled block inside a loop (the label's own line carries the block's name only)
             mm = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)", s) if s.startswith(";") else None

@@ -1,8 +1,9 @@
-"""Assembly gate of a refactor of csrc/sas_tile.hip: every kernel against another checkout's, per symbol.
+"""Assembly gate of a refactor of the device code: every kernel of every .hip file of build.SOURCES against another checkout's, per
+symbol, under a heading per file.
 
-    python tools/isa_gate.py <the other checkout's root>
+    python tools/isa_gate.py <the other checkout's root> [file.hip ...]     (files: only these, while iterating on one)
 
-Both files are compiled as tools/isa_audit.py compiles them.  'same': identical instruction for instruction (comments, directives and
+Both checkouts' files are compiled as tools/isa_audit.py compiles them.  'same': identical instruction for instruction (comments, directives and
 block numbers stripped).  Otherwise: the instruction counts per loop and issue class (isa_audit.audit) and the resources (VGPRs, SGPRs,
 spills, scratch, LDS, occupancy) of both, 'equal' when all of them agree.  CPU only: hipcc cross-compiles.
 """
@@ -19,11 +20,11 @@ from sim_a_splat_amd import build  # noqa: E402
 KEYS = ("VGPRs", "TotalSGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize", "LDS Size", "Occupancy")
 
 
-def kernels(root):
+def kernels(root, src):
     tmp = Path(tempfile.mkdtemp(prefix="sas_gate_"))
     cmd = [build.hipcc_path(), build.OPT_LEVEL, "-std=c++17", f"--offload-arch={build.ARCH}", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
            "-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage", f"-I{root / 'include'}", "-c", "-x", "hip",
-           str(root / "sim_a_splat_amd" / "csrc" / "sas_tile.hip"), "-o", "t.o", "-save-temps"]
+           str(root / "sim_a_splat_amd" / "csrc" / src), "-o", "t.o", "-save-temps"]
     err = subprocess.run(cmd, cwd=tmp, capture_output=True, text=True, check=True).stderr
     out, cur = {}, None
     for line in next(tmp.glob("*gfx950.s")).read_text().split("\n"):
@@ -48,8 +49,9 @@ def kernels(root):
     return out
 
 
-if __name__ == "__main__":
-    a, b = kernels(Path(sys.argv[1]).resolve()), kernels(build.PKG.parent)
+def gate(other, src):
+    a, b = kernels(other, src), kernels(build.PKG.parent, src)
+    print(f"==== {src}: {len(b)} kernels")
     for sym in sorted(set(a) | set(b)):
         name = subprocess.run(["c++filt", "-p", sym], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "")
         if sym not in a or sym not in b:
@@ -62,3 +64,8 @@ if __name__ == "__main__":
         if verdict == "DIFFER":
             for tag, k in (("other", ka), ("this", kb)):
                 print(f"    {tag:5s} {k['res']}\n          loops (depth, V S W L G X R): {k['loops']}")
+
+
+if __name__ == "__main__":
+    for src in sys.argv[2:] or [p.name for p in build.SOURCES if p.suffix == ".hip"]:
+        gate(Path(sys.argv[1]).resolve(), src)
