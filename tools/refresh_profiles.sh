@@ -60,28 +60,30 @@ timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_IN
 fi
 if [ "$part" = "a" ]; then tail -c 400 $out/bench.json; exit 0; fi
 mkdir -p $out
+# every GPU step below ends the script when it fails, as part a's do: nothing is started on a GPU after a program that faulted or hung
 # SQ counter groups of the tile kernel on isolated frames
-bash tools/pmc_tile.sh > $out/tile_sq_counters.txt 2>&1
-SAS_LIB_PATH=variants/lib_stats.so python3 tools/blend_stats.py 3 > $out/blend_stats.txt 2>&1
+python3 tools/pmc.py --kernels k_tile_lazy --set tile --out $out/pmc_tile > $out/tile_sq_counters.txt 2>&1 || exit 1
+SAS_LIB_PATH=variants/lib_stats.so timeout -k 10 300 python3 tools/blend_stats.py 3 > $out/blend_stats.txt 2>&1 || exit 1
 # the other BASELINE configs on this GPU, the Gym loops, the clock ramp
 timeout -k 10 300 python3 bench.py --config 4 --steps 100 > $out/config4.json 2> $out/config4.err || exit 1
 timeout -k 10 300 python3 bench.py --config 5 --steps 40 > $out/config5.json 2> $out/config5.err || exit 1
-timeout -k 10 300 python3 tools/config_fps.py 1 2 3 5 > $out/config_fps.txt 2>&1
-timeout -k 10 200 python3 tools/ramp_probe.py > $out/ramp.txt 2>&1
-{ timeout -k 10 200 python3 examples/demo_synthetic_env.py; timeout -k 10 200 python3 tools/door_b_breakdown.py; timeout -k 10 300 python3 tools/vec_env_probe.py 1 4 16; } > $out/env_steps.txt 2>&1
+timeout -k 10 300 python3 tools/config_fps.py 1 2 3 5 > $out/config_fps.txt 2>&1 || exit 1
+timeout -k 10 200 python3 tools/ramp_probe.py > $out/ramp.txt 2>&1 || exit 1
+{ timeout -k 10 200 python3 examples/demo_synthetic_env.py && timeout -k 10 200 python3 tools/door_b_breakdown.py && timeout -k 10 300 python3 tools/vec_env_probe.py 1 4 16; } > $out/env_steps.txt 2>&1 || exit 1
 # the issue-rate microbenchmarks are built here from their sources (no binaries in the tree)
 for mb in pk_f32_rate clock_probe issue_probe; do
   /opt/rocm/bin/hipcc -w -O3 --offload-arch=gfx950 tools/microbench/$mb.hip -o /tmp/$mb || exit 1
 done
-{ /tmp/pk_f32_rate | head -9; /tmp/clock_probe; } > $out/microbench.txt 2>&1
-/tmp/issue_probe > $out/issue_cost.txt 2>&1
+timeout -k 10 200 /tmp/pk_f32_rate > $out/pk_f32_rate.txt 2>&1 || exit 1
+{ head -9 $out/pk_f32_rate.txt; timeout -k 10 200 /tmp/clock_probe; } > $out/microbench.txt 2>&1 || exit 1
+timeout -k 10 200 /tmp/issue_probe > $out/issue_cost.txt 2>&1 || exit 1
 # where a tile workgroup's time goes (exclusive laps of thread 0: the -DSAS_TUNE_WGTIME build under variants/)
-SAS_LIB_PATH=variants/lib_wgtime.so timeout -k 10 300 python3 tools/wg_time.py 3 > $out/slot_time.txt 2>&1
+SAS_LIB_PATH=variants/lib_wgtime.so timeout -k 10 300 python3 tools/wg_time.py 3 > $out/slot_time.txt 2>&1 || exit 1
 # ... and a projection workgroup's (geometry role: exclusive laps; both roles: when they run inside the launch; -DSAS_TUNE_PTIME build)
-SAS_LIB_PATH=variants/lib_ptime.so timeout -k 10 300 python3 tools/proj_time.py 3 > $out/proj_laps.txt 2>&1
-bash tools/pmc_tile.sh k_project > $out/project_sq_counters.txt 2>&1
+SAS_LIB_PATH=variants/lib_ptime.so timeout -k 10 300 python3 tools/proj_time.py 3 > $out/proj_laps.txt 2>&1 || exit 1
+python3 tools/pmc.py --kernels k_project --set tile --out $out/pmc_project > $out/project_sq_counters.txt 2>&1 || exit 1
 # the GPU suite: product library, bounds-checked build, bounds-checked build with the quad layout forced
-timeout -k 10 600 python3 -m pytest tests -m gpu -q -s > $out/gpu_tests.log 2>&1
-SAS_LIB_PATH=variants/lib_bounds.so timeout -k 10 900 python3 -m pytest tests -m gpu -q > $out/bounds_tests.log 2>&1
-SAS_QUAD=1 SAS_LIB_PATH=variants/lib_bounds.so timeout -k 10 900 python3 -m pytest tests -m gpu -q > $out/bounds_quad_tests.log 2>&1
+timeout -k 10 600 python3 -m pytest tests -m gpu -q -s > $out/gpu_tests.log 2>&1 || exit 1
+SAS_LIB_PATH=variants/lib_bounds.so timeout -k 10 900 python3 -m pytest tests -m gpu -q > $out/bounds_tests.log 2>&1 || exit 1
+SAS_QUAD=1 SAS_LIB_PATH=variants/lib_bounds.so timeout -k 10 900 python3 -m pytest tests -m gpu -q > $out/bounds_quad_tests.log 2>&1 || exit 1
 [ -f $out/bench.json ] && tail -c 700 $out/bench.json; true
