@@ -7,7 +7,7 @@ its HIP library is missing instead of falling back to this code.
 ``oracle.sas_oracle.c``  float32 C restatement (the checker; OpenMP for the CPU baseline timing)
 ``oracle.np_twin``       float64 NumPy twin used to cross-check the C file
 ``oracle.ref_math``      NumPy restatement of the in-tree host math (compute_cov, SH2RGB, poses)
-``oracle.mesh_ref``      float64 reference of the mesh rules (coverage, depth, shading; ``mesh_ref.c``), brute force per pixel,
+``oracle.mesh_ref``      float64 reference of the mesh rules (coverage, depth, flat and smooth shading; ``mesh_ref.c``), brute force per pixel,
                          with the ``stable`` mask that says where float32 may decide otherwise; ``render(zlim=, bgmap=)`` takes
                          its per-pixel depth limit and background
 

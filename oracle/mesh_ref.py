@@ -1,9 +1,20 @@
-"""Float64 reference of a frame's triangle meshes (DESIGN.md 3 "Meshes", rules 1 and 2) -- TEST INFRASTRUCTURE ONLY.
+"""Float64 reference of a frame's triangle meshes (DESIGN.md 3 "Meshes", rules 1, 2 and 2b) -- TEST INFRASTRUCTURE ONLY.
 
 ``reference`` answers, per pixel and brute force over all triangles (``mesh_ref.c``: no tiles, no rectangles, no records), which
 triangle the pixel shows, at which camera depth and in which shaded colour.  The vertices are posed and moved to the camera
 frame in float32 by the oracle's own fused chain (``oracle.pose_points``: the contract's "float, as the projection moves the
 Gaussians"); near clip, projection, inside test, depth and shading are float64.
+
+The colour is the triangle's flat one (rule 2) unless the mesh carries vertex normals (rule 2b).  Then:
+
+* a triangle is smooth when its three vertices carry a finite, non-zero normal (and the pose leaves it one);
+* vertex shade ``s_k = clamp(c_k (ka + kd |n'_k . v_k|), 0, 1)``: ``n'_k`` the float32 normal under the 3x3 block of the float32 pose row,
+  in float64, renormalised; ``v_k`` the unit vector from the camera centre to the posed vertex (the float32 world corners the kernel
+  has); ``c_k`` the float32 vertex colour, or the triangle's colour without vertex colours;
+* pixel colour ``sum_k beta_k s_k``, ``beta`` the barycentric coordinates, in the unclipped camera-space triangle (the float32 camera
+  corners), of the point where the ray through the pixel centre meets the triangle's plane.
+
+Rule 2b knows no records, planes, tiles or clipping: the near clip changes nothing mathematically, so the reference has none.
 
 ``frame_inputs`` turns that into what ``oracle.render(zlim=, bgmap=)`` takes, and ``stability`` says on which pixels the HIP
 kernels, which evaluate edges and depth in float32, must reproduce the resulting frame bit for bit:
@@ -32,11 +43,54 @@ DELTA_ULPS = 16.0
 EPS32 = 2.0 ** -24
 
 
-def reference(vertices, triangles, colors, groups, group_Rt, ka: float, kd: float, viewmat, K, W: int, H: int) -> Dict[str, np.ndarray]:
-    """``vertices [V,3]``, ``triangles [T,3]``, ``colors [T,3]`` or ``[3]``, ``groups [T]`` or None, ``group_Rt [G,12]`` or None.
+def barycentric(winner, camera_vertices, K, W: int, H: int) -> np.ndarray:
+    """``beta [H,W,3]`` float64 (0 where no triangle): ray through the pixel centre against the plane of the winner's unclipped
+    camera-space triangle, then area ratios in that plane."""
+    Km = np.asarray(K, np.float32).reshape(3, 3).astype(np.float64)
+    ys, xs = np.mgrid[0:H, 0:W]
+    D = np.stack([((xs + 0.5) - Km[0, 2]) / Km[0, 0], ((ys + 0.5) - Km[1, 2]) / Km[1, 1], np.ones((H, W))], -1)
+    hit = winner >= 0
+    tri = camera_vertices.astype(np.float64)[winner[hit]]                # [P,3,3]
+    A, B, C = tri[:, 0], tri[:, 1], tri[:, 2]
+    N = np.cross(B - A, C - A)
+    d = D[hit]
+    X = d * ((N * A).sum(1) / (N * d).sum(1))[:, None]                   # the hit point
+    nn = (N * N).sum(1)
+    beta = np.zeros((H, W, 3))
+    beta[hit] = np.stack([(N * np.cross(C - B, X - B)).sum(1), (N * np.cross(A - C, X - C)).sum(1), (N * np.cross(B - A, X - A)).sum(1)], 1) / nn[:, None]
+    return beta
+
+
+def vertex_shades(world, campos, t, g, col, group_Rt, ka, kd, vertex_normals, vertex_colors=None):
+    """``(shade [T,3,3] float64 -- triangle, corner, channel --, smooth [T] bool)`` of rule 2b, from ``reference``'s posed corners
+    ``world [T,3,3]`` (float64), triangles ``t``, groups ``g`` and colours ``col [T,3]`` (float64)."""
+    n = np.asarray(vertex_normals, np.float32).reshape(-1, 3).astype(np.float64)
+    n = np.where(np.isfinite(n).all(1, keepdims=True), n, 0.0)[t]       # [T,3,3]; non-finite counts as zero
+    n_in = np.linalg.norm(n, axis=2)
+    if group_Rt is not None:
+        R = np.asarray(group_Rt, np.float32).reshape(-1, 3, 4)[:, :, :3].astype(np.float64)[g]     # [T,3,3]
+        n = np.einsum("tij,tkj->tki", R, n)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        nl = np.linalg.norm(n, axis=2)
+        smooth = ((n_in > 0) & (nl > 0) & np.isfinite(nl)).all(1)
+        d = world - campos.astype(np.float64)
+        dl = np.linalg.norm(d, axis=2)
+        ndv = np.where(dl > 0, np.abs((n * d).sum(2)) / (nl * dl), 1.0)
+        sh = float(np.float32(ka)) + float(np.float32(kd)) * ndv       # [T,3]
+        c = col[:, None, :].repeat(3, 1) if vertex_colors is None else np.asarray(vertex_colors, np.float32).reshape(-1, 3).astype(np.float64)[t]
+        shade = np.clip(c * sh[..., None], 0.0, 1.0)
+    return np.where(np.isfinite(shade), shade, 0.0), smooth
+
+
+def reference(vertices, triangles, colors, groups, group_Rt, ka: float, kd: float, viewmat, K, W: int, H: int,
+              vertex_normals=None, vertex_colors=None) -> Dict[str, np.ndarray]:
+    """``vertices [V,3]``, ``triangles [T,3]``, ``colors [T,3]`` or ``[3]``, ``groups [T]`` or None, ``group_Rt [G,12]`` or None,
+    ``vertex_normals`` / ``vertex_colors [V,3]`` or None.
     Returns ``winner [H,W]`` (int32, -1: none), ``z``, ``kappa``, ``delta`` (float64), ``color [H,W,3]`` (float32: the shaded
-    colour as the kernel stores it; 0 where no triangle), ``tri_color [T,3]``, ``valid [T]``, ``probe_differs`` and
-    ``near_second`` (bool: (a) and (b) above)."""
+    colour as the kernel stores it; 0 where no triangle), ``tri_color [T,3]`` (the flat colours), ``valid [T]``, ``probe_differs``
+    and ``near_second`` (bool: (a) and (b) above); of rule 2b ``smooth [T]``, ``smooth_pixel [H,W]`` (the winner is a smooth
+    triangle), ``beta [H,W,3]`` and ``color64`` (the colour before rounding to float32) -- without normals all-false, zero, and
+    ``color`` as float64."""
     L = oracle.lib()
     W, H = int(W), int(H)
     v = np.asarray(vertices, np.float32).reshape(-1, 3)
@@ -74,10 +128,19 @@ def reference(vertices, triangles, colors, groups, group_Rt, ka: float, kd: floa
     color = np.zeros((H, W, 3), np.float32)
     hit = winner >= 0
     color[hit] = tri_color[winner[hit]]
+    cam3 = camv.reshape(T, 3, 3)
+    smooth, sp, beta, color64 = np.zeros(T, bool), np.zeros((H, W), bool), np.zeros((H, W, 3)), color.astype(np.float64)
+    if vertex_normals is not None:
+        vshade, smooth = vertex_shades(w, campos, t, g, col, group_Rt, ka, kd, vertex_normals, vertex_colors)
+        beta = barycentric(winner, cam3, K, W, H)
+        sp = hit & smooth[np.maximum(winner, 0)]
+        color64[sp] = np.einsum("pk,pkc->pc", beta[sp], vshade[winner[sp]])
+        color[sp] = color64[sp].astype(np.float32)
     delta = DELTA_ULPS * EPS32 * kappa
     near_second = hit & (gap <= DELTA_ULPS * EPS32 * np.maximum(kappa, kappa2))
     return dict(winner=winner, z=z, kappa=kappa, delta=delta, color=color, tri_color=tri_color, valid=valid[:T].astype(bool),
-                probe_differs=probe.astype(bool), near_second=near_second, camera_vertices=camv.reshape(T, 3, 3))
+                probe_differs=probe.astype(bool), near_second=near_second, camera_vertices=cam3, smooth=smooth, smooth_pixel=sp,
+                beta=beta, color64=color64)
 
 
 def frame_inputs(ref: Dict[str, np.ndarray], background):

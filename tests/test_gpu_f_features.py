@@ -6,57 +6,23 @@ weights, unclamped, features through the colours' finite mapping.  Its consequen
 fbg = bg) -- on the lazy path, the full path and the C oracle.
 """
 import ctypes
+import sys
+from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
 import oracle
-from conftest import load_twin_fixture, twin_scene_kwargs
 from sim_a_splat_amd import _capi
 from sim_a_splat_amd.rasterizer import Rasterizer, SasError, group_labels
-from sim_a_splat_amd.synthetic import config_scene_and_cameras, make_scene, random_group_poses, ring_camera
+from sim_a_splat_amd.synthetic import make_scene, random_group_poses, ring_camera
+
+sys.path.insert(0, str(Path(__file__).resolve().parent / "tools"))
+from scene_cases import config3_window as _config3_window, synthetic as _synthetic, twin as _twin, upload as _upload  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 FMAX = np.float32(3.402823466e38)
-
-
-# ---- scenes ---------------------------------------------------------------------------------------------------------
-def _twin(name):
-    g = load_twin_fixture(name)
-    means, op, colors, kw = twin_scene_kwargs(g)
-    W, H = [int(v) for v in g["wh"]]
-    gid = kw.get("group_id")
-    sc = dict(means=means, op=op, colors=colors, sh=kw["sh_degree"], quats=kw.get("quats"), scales=kw.get("scales"),
-              cov6=kw.get("cov6"), gid=gid, G=int(g["group_Rt"].shape[0]) if gid is not None else 0,
-              Rt=g["group_Rt"] if gid is not None else None)
-    return sc, (g["viewmat"], g["K"], W, H)
-
-
-def _synthetic(n, seed, ls, n_groups=0):
-    s = make_scene(n, seed=seed, log_scale_mean=float(np.log(ls)), n_groups=n_groups)
-    G = n_groups if s.group_id is not None else 0
-    return dict(means=s.means, op=s.opacities, colors=s.sh, sh=s.sh_degree, quats=s.quats, scales=s.scales, cov6=None,
-                gid=s.group_id, G=G, Rt=random_group_poses(G, seed + 1) if G else None)
-
-
-def _config3_window():
-    s, cams = config_scene_and_cameras(3)
-    cam = cams[0]
-    K = np.array(cam.K, np.float32).copy()
-    K[0, 2] -= 800.0      # a 320 x 240 window of the 1080p view, around its centre
-    K[1, 2] -= 420.0
-    sc = dict(means=s.means, op=s.opacities, colors=s.sh, sh=s.sh_degree, quats=s.quats, scales=s.scales, cov6=None,
-              gid=None, G=0, Rt=None)
-    return sc, (cam.viewmat, K, 320, 240)
-
-
-def _upload(r, sc, colors=None):
-    """The scene, or (colors [n,3]) the same geometry recoloured with final RGB."""
-    r.upload(sc["means"], sc["op"], sc["colors"] if colors is None else colors, quats=sc["quats"], scales=sc["scales"],
-             covariances=sc["cov6"], sh_degree=sc["sh"] if colors is None else -1, group_id=sc["gid"], n_groups=sc["G"])
-    if sc["G"]:
-        r.set_group_poses(sc["Rt"])
 
 
 def _oracle_rgb(sc, colors, view, bg):

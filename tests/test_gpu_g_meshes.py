@@ -17,7 +17,7 @@ from sim_a_splat_amd.rasterizer import Rasterizer, SasError
 from sim_a_splat_amd.synthetic import make_scene
 
 sys.path.insert(0, str(Path(__file__).resolve().parent / "tools"))
-from mesh_cases import (BG, OUTS, cam_to_world as _cam_to_world, colours as _colours, config3_window as _config3_window,  # noqa: E402
+from mesh_cases import (BG, OUTS, DrawMsg as _DrawMsg, cam_to_world as _cam_to_world, colours as _colours, config3_window as _config3_window,  # noqa: E402
                         full_quad as _full_quad, oracle_frame as _oracle, random_triangles as _random_triangles, ray_cast as _ray_cast,
                         ring as _ring, same as _same, screen_quad as _screen_quad, stable_ref as _stable_ref, synthetic as _synthetic,
                         to_numpy as _np, twin as _twin, upload as _upload)
@@ -444,12 +444,6 @@ def test_top_left_rule_no_holes_no_overlap():
 
 
 # ---- (g) the T-block through SplatHandler(meshes=("task",)) ------------------------------------------------------------------
-class _DrawMsg:
-    def __init__(self, robot_num, quaternion, position):
-        self.num_links = len(robot_num)
-        self.robot_num, self.quaternion, self.position = robot_num, [np.asarray(q) for q in quaternion], [np.asarray(p) for p in position]
-
-
 def test_g_task_mesh_through_handler(golden_dir):
     from sim_a_splat_amd import poses
     from sim_a_splat_amd.covariance import compute_cov, sh2rgb

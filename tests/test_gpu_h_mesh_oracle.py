@@ -23,23 +23,12 @@ pytestmark = pytest.mark.gpu
 OUTS = mc.OUTS
 
 
-def _expect(name, case, view=0):
-    e = mc.expected(case, view)
-    print(mc.report(f"{name}[{view}]", case, e))
-    assert e["excluded"] <= mc.MAX_EXCLUDED, mc.report(name, case, e)
-    if name not in mc.COVERAGE_IS_DRAWN:
-        assert e["driven"] >= mc.MIN_DRIVEN, mc.report(name, case, e)
-    return e
+_expect, _single = mc.expect, mc.single
 
 
 def _check(got, e, what, fill=False):
-    diffs = mc.compare_stable(got, e["frame"], e["stable"], fill=fill)
+    diffs = mc.compare(got, e, fill=fill)[0]
     assert not diffs, (what, diffs)
-
-
-def _single(r, case, view=0, **kw):
-    V, K, W, H = case["cams"][view]
-    return mc.to_numpy(r.render(V, K, W, H, case["bg"], want=OUTS, **kw))
 
 
 def _run_single_view_case(name, case):
@@ -117,14 +106,7 @@ def test_ragged_sizes(size):
 
 
 def test_full_hd_thousands_of_triangles():
-    case = mc.case_1080p()
-    r = Rasterizer(0)
-    try:
-        mc.upload_case(r, case)
-        e = _expect("full_hd", case)
-        _check(_single(r, case), e, "full_hd")
-    finally:
-        r.close()
+    _run_single_view_case("full_hd", mc.case_1080p())
 
 
 # ---- entry points ---------------------------------------------------------------------------------------------------------------

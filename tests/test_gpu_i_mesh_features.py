@@ -44,7 +44,7 @@ def _case(name):
 
 def _setup(r, case, view=0):
     mc.upload_case(r, case)
-    Rt = mf.view_poses(case, view)
+    Rt = mc.view_poses(case, view)
     if Rt is not None:
         r.set_group_poses(Rt)
 

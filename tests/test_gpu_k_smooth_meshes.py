@@ -1,4 +1,4 @@
-"""GPU: smooth-shaded meshes (DESIGN.md 3 "Meshes", rule 2b) against the float64 reference of tests/tools/mesh_smooth_ref.py + the
+"""GPU: smooth-shaded meshes (DESIGN.md 3 "Meshes", rule 2b) against the float64 reference of oracle/mesh_ref.py + the
 depth-limited oracle, on the cases of tests/tools/mesh_smooth_cases.py (their caps are settled on the CPU: test_smooth_meshes_cpu.py).
 
 On the reference's stable pixels: alpha and depth bit-equal to the expected frame, rgb within 1e-4 (the project's parity gate: the
@@ -29,31 +29,22 @@ def rasterizer():
     r.close()
 
 
-def _expect(name, case, view=0):
-    e = ms.expected(case, view)
-    print(mc.report(f"{name}[{view}]", case, e))
-    assert e["excluded"] <= mc.MAX_EXCLUDED and e["driven"] >= mc.MIN_DRIVEN, mc.report(name, case, e)
-    return e
+_expect, _single = mc.expect, mc.single
 
 
 def _check(got, e, what):
-    probs, err, err8 = ms.compare(got, e)
+    probs, err, err8 = mc.compare(got, e)
     n = int((e["stable"] & e["ref"]["smooth_pixel"]).sum())
     print(f"  {what}: {n} stable smooth pixels, max |rgb - reference| = {err:.3e}, max rgb8 difference = {err8:.0f} LSB")
     assert not probs, (what, probs)
     assert n > 0
 
 
-def _single(r, case, view=0, **kw):
-    V, K, W, H = case["cams"][view]
-    return mc.to_numpy(r.render(V, K, W, H, case["bg"], want=OUTS, **kw))
-
-
 # ---- the spheres ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(ms.SPHERES))
 def test_smooth_sphere_among_the_splats(rasterizer, name):
     case = ms.FIXED_CASES[name]()
-    ms.upload_case(rasterizer, case)
+    mc.upload_case(rasterizer, case)
     rasterizer.set_group_poses(case["poses"][0])
     _check(_single(rasterizer, case), _expect(name, case), name)
 
@@ -61,7 +52,7 @@ def test_smooth_sphere_among_the_splats(rasterizer, name):
 def test_real_link_xarm6_base(rasterizer):
     case = ms.case_xarm6_base()
     assert len(case["mesh"]["verts"]) < 3 * len(case["mesh"]["tris"]) and case["mesh"]["vcols"] is None
-    ms.upload_case(rasterizer, case)
+    mc.upload_case(rasterizer, case)
     rasterizer.set_group_poses(case["poses"][0])
     _check(_single(rasterizer, case), _expect("xarm6_base", case), "xarm6_base")
 
@@ -71,7 +62,7 @@ def test_mixed_flat_block_and_smooth_sphere(rasterizer):
     case = ms.case_mixed()
     V, K, W, H = case["cams"][0]
     sets = np.stack(case["poses"]).astype(np.float32)
-    ms.upload_case(rasterizer, case)
+    mc.upload_case(rasterizer, case)
     es = [_expect("mixed", case, v) for v in range(2)]
     for v in range(2):
         w = es[v]["ref"]["winner"][es[v]["stable"]]
@@ -89,7 +80,7 @@ def test_mixed_flat_block_and_smooth_sphere(rasterizer):
 def test_near_clipped_quad_shows_the_affine_field(rasterizer):
     case = ms.case_near_clip()
     V, K, W, H = case["cams"][0]
-    ms.upload_case(rasterizer, case)
+    mc.upload_case(rasterizer, case)
     e = _expect("near_clip", case)
     got = _single(rasterizer, case)
     _check(got, e, "near_clip")
@@ -114,7 +105,7 @@ def test_entry_points(rasterizer):
     p0 = case["poses"][0]
     p1 = ms.pose_rows(case["sc"], 2, (0.2, -0.5, 1.1), (0.1, 0.0, 0.2))
     bg = case["bg"]
-    ms.upload_case(r, case)
+    mc.upload_case(r, case)
     r.set_group_poses(p0)
     e0, e1 = _expect("entry_points", case), _expect("entry_points", dict(case, poses=[p1]))
     assert not np.array_equal(e0["frame"]["rgb8"], e1["frame"]["rgb8"])
@@ -153,12 +144,12 @@ def test_attributes_are_set_cleared_and_forgotten(rasterizer):
     r = rasterizer
     case = ms.FIXED_CASES["sphere_small"]()
     m = case["mesh"]
-    ms.upload_case(r, case, attributes=False)
+    mc.upload_case(r, case, attributes=False)
     r.set_group_poses(case["poses"][0])
     e = _expect("sphere_small", case)
     assert not r.mesh_vertex_attributes and r.n_mesh_vertices == len(m["verts"])
     flat = _single(r, case)
-    assert not mc.compare_stable(flat, e["flat_frame"], e["stable"])
+    assert not mc.compare_stable(flat, mc.expected(case, attributes=False)["frame"], e["stable"])
     # all-zero normals: the flat frame, bit for bit
     r.upload_mesh_vertex_attributes(np.zeros_like(m["normals"]), m["vcols"])
     assert r.mesh_vertex_attributes
@@ -209,13 +200,13 @@ def test_task_and_robot_meshes_through_handler():
         H, W = hs["size"]
         got = h.render(h.scene, [hs["cam"]], [[H, W]])[0]
         rows = h.scene.group_pose_rows()
-        want_rows = ms.handler_predicted_rows(hs)
+        want_rows = mc.handler_predicted_rows(hs, robot=True)
         # the poses the CPU caps were settled with are the poses the scene holds; mesh_pose_rows gives the meshes' without the scene
         assert rows.shape == (6, 12) and np.abs(rows - want_rows).max() < 1e-5
         idx, mrows = h.mesh_pose_rows(hs["msg"])
         assert idx.tolist() == [3, 4, 5] and np.array_equal(mrows, rows[3:])
         V, K = h.scene._view_and_K(H, W, hs["cam"][0], hs["cam"][1], h.scene.camera.fov)
-        e = _expect("handler", ms.case_handler(hs, rows, V, K))
+        e = _expect("handler", mc.case_handler(hs, rows, V, K, robot=True))
         assert len(np.unique(e["ref"]["winner"][e["stable"] & e["ref"]["smooth_pixel"]])) > 20
         _check({"rgb8": np.asarray(got)}, e, "SplatHandler.render, meshes=('task', 'robot')")
         fl = mc.to_numpy(h.scene.get_render_float(H, W, hs["cam"][0], hs["cam"][1]))

@@ -1,5 +1,5 @@
 """CPU: smooth-shaded meshes (DESIGN.md 3 "Meshes", rule 2b) -- the reference and the caps of the fixed cases the GPU tests render
-(tests/tools/mesh_smooth_ref.py, mesh_smooth_cases.py), mesh welding and vertex normals, URDF material colours, and the robot
+(oracle/mesh_ref.py, tests/tools/mesh_smooth_cases.py), mesh welding and vertex normals, URDF material colours, and the robot
 meshes of SplatHandler over a stand-in scene."""
 import sys
 import types
@@ -11,7 +11,7 @@ import pytest
 sys.path.insert(0, str(Path(__file__).resolve().parent / "tools"))
 import mesh_cases as mc  # noqa: E402
 import mesh_smooth_cases as ms  # noqa: E402
-import mesh_smooth_ref as msr  # noqa: E402
+from oracle import mesh_ref  # noqa: E402
 
 from sim_a_splat_amd import mesh_io, poses, urdf_fk  # noqa: E402
 
@@ -22,7 +22,7 @@ def _expected(name, view=0):
     """Every case's reference is computed once and shared, unchanged, by the tests below."""
     if (name, view) not in _EXPECTED:
         case = ms.FIXED_CASES[name]()
-        _EXPECTED[(name, view)] = (case, ms.expected(case, view))
+        _EXPECTED[(name, view)] = (case, mc.expected(case, view))
     return _EXPECTED[(name, view)]
 
 
@@ -36,7 +36,8 @@ def test_caps_hold(name):
         sp = e["ref"]["smooth_pixel"] & e["stable"]
         assert sp.sum() >= 150, (name, int(sp.sum()))
         # the smooth frame is not the flat one: the new tests can tell them apart
-        assert np.abs(e["frame"]["rgb"].astype(np.float64) - e["flat_frame"]["rgb"])[sp].max() > 1e-3
+        flat = mc.expected(case, view, attributes=False)["frame"]
+        assert np.abs(e["frame"]["rgb"].astype(np.float64) - flat["rgb"])[sp].max() > 1e-3
     if name == "sphere_dense":       # sub-pixel triangles, tile lists of thousands of records (bounding-box count)
         assert len(case["mesh"]["tris"]) == 16128
     if name == "mixed":
@@ -79,13 +80,13 @@ def test_zero_normals_give_the_flat_reference_bit_for_bit():
     m = case["mesh"]
     V, K, W, H = case["cams"][0]
     args = (m["verts"], m["tris"], m["cols"], m["groups"], case["poses"][0], m["ka"], m["kd"], V, K, W, H)
-    flat = msr.mesh_ref.reference(*args)
-    zero = msr.reference(*args, vertex_normals=np.zeros_like(m["normals"]), vertex_colors=m["vcols"])
+    flat = mesh_ref.reference(*args)
+    zero = mesh_ref.reference(*args, vertex_normals=np.zeros_like(m["normals"]), vertex_colors=m["vcols"])
     assert not zero["smooth"].any() and np.array_equal(zero["color"].view(np.uint8), flat["color"].view(np.uint8))
     # one missing (or non-finite) normal keeps every triangle around that vertex flat, and only those
     n = m["normals"].copy()
     n[5] = np.nan
-    part = msr.reference(*args, vertex_normals=n, vertex_colors=m["vcols"])
+    part = mesh_ref.reference(*args, vertex_normals=n, vertex_colors=m["vcols"])
     around = (m["tris"] == 5).any(1)
     assert np.array_equal(part["smooth"], ~around) and around.sum() >= 4
 

@@ -1,75 +1,25 @@
-"""Shared by the mesh tests (test_gpu_g_meshes.py, test_gpu_h_mesh_oracle.py, test_mesh_ref_cpu.py) and the fuzzer: scenes,
-meshes in camera space, the float64 ray cast, and the FIXED CASES that hold the HIP mesh frames to oracle.mesh_ref + the
-depth-limited oracle.  Everything here runs on the CPU; the GPU tests render the same inputs and compare.
+"""Shared by the mesh tests (test_gpu_g_meshes.py, test_gpu_h_mesh_oracle.py, test_gpu_i_mesh_features.py, test_gpu_k_smooth_meshes.py
+and their CPU files) and the fuzzer: meshes in camera space, the float64 ray cast, and the FIXED CASES that hold the HIP mesh frames
+to oracle.mesh_ref + the depth-limited oracle.  Everything down to "GPU side" runs on the CPU; the GPU tests render the same inputs
+and compare.  The scenes, cameras and frame helpers are scene_cases.py's, re-exported here.
 
-A case is a dict: sc (scene arrays), cams [(V, K, W, H)], mesh (verts, tris, cols, groups, ka, kd), bg, poses (one [G,12]
-block per view, or None).  `expected(case, view)` gives the reference frame, its `stable` mask and the counts the caps are
-taken from."""
+A case is a dict: sc (scene arrays), cams [(V, K, W, H)], mesh (verts, tris, cols, groups, ka, kd, and normals / vcols [V,3] or None:
+smooth shading, DESIGN.md 3 rule 2b), bg, poses (one [G,12] block per view, or None).  `expected(case, view)` gives the reference
+frame, its `stable` mask and the counts the caps are taken from."""
 import sys
 from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent.parent
-if str(ROOT) not in sys.path:
-    sys.path.insert(0, str(ROOT))
-import oracle  # noqa: E402
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+from scene_cases import GOLDEN, OUTS, config3_window, oracle_frame, ring, same, synthetic, to_numpy, twin, upload  # noqa: E402,F401
 from oracle import mesh_ref  # noqa: E402
-from sim_a_splat_amd.synthetic import config_scene_and_cameras, make_scene, random_group_poses, ring_camera  # noqa: E402
+from sim_a_splat_amd.synthetic import make_scene  # noqa: E402
 
-GOLDEN = ROOT / "tests" / "golden"
-OUTS = ("rgb", "alpha", "depth", "rgb8")
 BG = (0.12, 0.34, 0.56)
 MAX_EXCLUDED = 0.10      # `stable` may be false on at most this share of a frame (the coverage test's own allowance)
 MIN_DRIVEN = 0.20        # share of a frame that is stable, mesh-covered, with list entries cut off AND entries kept
-
-
-# ---- scenes ---------------------------------------------------------------------------------------------------------
-def twin(name):
-    g = np.load(GOLDEN / f"render_twin_{name}.npz")
-    kw = dict(quats=None, scales=None, cov6=None)
-    if g["cov6"].size:
-        kw["cov6"] = g["cov6"]
-    else:
-        kw.update(quats=g["quats"], scales=g["scales"])
-    gid = g["group_id"] if g["group_id"].size else None
-    W, H = [int(v) for v in g["wh"]]
-    sc = dict(means=g["means"], op=g["opacities"], colors=g["colors"], sh=int(g["sh_degree"]), gid=gid,
-              G=int(g["group_Rt"].shape[0]) if gid is not None else 0, Rt=g["group_Rt"] if gid is not None else None, **kw)
-    return sc, (np.asarray(g["viewmat"], np.float32).reshape(4, 4), np.asarray(g["K"], np.float32).reshape(3, 3), W, H)
-
-
-def synthetic(n, seed, ls, n_groups=0):
-    s = make_scene(n, seed=seed, log_scale_mean=float(np.log(ls)), n_groups=n_groups)
-    G = n_groups if s.group_id is not None else 0
-    return dict(means=s.means, op=s.opacities, colors=s.sh, sh=s.sh_degree, quats=s.quats, scales=s.scales, cov6=None,
-                gid=s.group_id, G=G, Rt=random_group_poses(G, seed + 1) if G else None)
-
-
-def config3_window():
-    s, cams = config_scene_and_cameras(3)
-    cam = cams[0]
-    K = np.array(cam.K, np.float32).copy()
-    K[0, 2] -= 800.0
-    K[1, 2] -= 420.0
-    sc = dict(means=s.means, op=s.opacities, colors=s.sh, sh=s.sh_degree, quats=s.quats, scales=s.scales, cov6=None,
-              gid=None, G=0, Rt=None)
-    return sc, (np.asarray(cam.viewmat, np.float32), K, 320, 240)
-
-
-def ring(W=96, H=64, f=90.0, yaw=15.0, elev=0.2):
-    c = ring_camera(W, H, f, yaw_deg=yaw, elev=elev)
-    return np.asarray(c.viewmat, np.float32), np.asarray(c.K, np.float32), W, H
-
-
-def oracle_frame(sc, cam, bg, keep=None, Rt=None, **kw):
-    V, K, W, H = cam
-    sel = slice(None) if keep is None else keep
-    pick = lambda a: None if a is None else np.asarray(a)[sel]
-    return oracle.render(pick(sc["means"]), pick(sc["op"]), pick(sc["colors"]), V, K, W, H, quats=pick(sc["quats"]),
-                         scales=pick(sc["scales"]), cov6=pick(sc["cov6"]), sh_degree=sc["sh"], group_id=pick(sc["gid"]),
-                         group_Rt=(sc["Rt"] if Rt is None else Rt) if sc["gid"] is not None else None, background=bg,
-                         want_rgb8=True, **kw)
+RGB_TOL = 1e-4           # the project's parity gate: float32 attribute planes against the float64 reference
 
 
 # ---- meshes in camera space -------------------------------------------------------------------------------------------
@@ -210,20 +160,28 @@ def visible_depths(sc, cam, Rt=None):
     return np.sort(d["depths"][vis].astype(np.float64))
 
 
-def expected(case, view=0, depth_mode=0):
-    """The reference of one view of a case: frame (the depth-limited oracle's outputs), ref (oracle.mesh_ref.reference),
-    stable / cut / length per pixel, and the counts the caps are asserted on."""
+def view_poses(case, view=0):
+    """The pose rows view `view` of a case is rendered with (None: a scene without groups)."""
+    sc = case["sc"]
+    if sc["gid"] is None:
+        return None
+    Rt = None if case.get("poses") is None else case["poses"][view]
+    return np.asarray(sc["Rt"] if Rt is None else Rt, np.float32).reshape(-1, 12)
+
+
+def expected(case, view=0, depth_mode=0, want_frame=True, attributes=True):
+    """The reference of one view of a case: frame (the depth-limited oracle's outputs; want_frame), ref (oracle.mesh_ref.reference;
+    attributes=False: the mesh drawn flat, whatever normals it carries), stable / cut / length per pixel, and the counts the caps are
+    asserted on.  One dump render, one reference, one frame render."""
     sc, cam, m = case["sc"], case["cams"][view], case["mesh"]
     V, K, W, H = cam
-    Rt = None if case.get("poses") is None else case["poses"][view]
-    if Rt is None:
-        Rt = sc["Rt"]
+    Rt = view_poses(case, view)
     dump = oracle_frame(sc, cam, case["bg"], Rt=Rt, dump=True)
-    ref = mesh_ref.reference(m["verts"], m["tris"], m["cols"], m["groups"], Rt if sc["gid"] is not None else None, m["ka"], m["kd"],
-                             V, K, W, H)
+    attr = dict(vertex_normals=m["normals"], vertex_colors=m["vcols"]) if attributes else {}
+    ref = mesh_ref.reference(m["verts"], m["tris"], m["cols"], m["groups"], Rt, m["ka"], m["kd"], V, K, W, H, **attr)
     st = mesh_ref.stability(ref, dump)
     zlim, bgmap = mesh_ref.frame_inputs(ref, case["bg"])
-    frame = oracle_frame(sc, cam, case["bg"], Rt=Rt, zlim=zlim, bgmap=bgmap, depth_mode=depth_mode)
+    frame = oracle_frame(sc, cam, case["bg"], Rt=Rt, zlim=zlim, bgmap=bgmap, depth_mode=depth_mode) if want_frame else None
     stable, cut, length = st["stable"], st["cut"], st["length"]
     covered = ref["winner"] >= 0
     driven = stable & covered & (cut > 0) & (cut < length)
@@ -252,9 +210,10 @@ def report(name, case, e):
 C_PLANE = (0.9, 0.2, 0.1)
 
 
-def _mesh(verts, tris, cols, groups=None, ka=0.4, kd=0.6):
-    return dict(verts=np.asarray(verts, np.float32), tris=np.asarray(tris, np.int32), cols=np.asarray(cols, np.float32),
-                groups=None if groups is None else np.asarray(groups, np.uint8), ka=float(ka), kd=float(kd))
+def _mesh(verts, tris, cols, groups=None, ka=0.4, kd=0.6, normals=None, vcols=None):
+    f32 = lambda a: None if a is None else np.asarray(a, np.float32)
+    return dict(verts=f32(verts), tris=np.asarray(tris, np.int32), cols=f32(cols), groups=None if groups is None else np.asarray(groups, np.uint8),
+                ka=float(ka), kd=float(kd), normals=f32(normals), vcols=f32(vcols))
 
 
 def _plane_case(sc, cam, group=None, edges_inside=False):
@@ -297,6 +256,13 @@ def _rot(ax, ay, az):
     return Rz @ Ry @ Rx
 
 
+def pose_rows(sc, group, ang, t):
+    """The scene's pose rows with `group` rotated by the angles `ang` and moved to `t`."""
+    Rt = sc["Rt"].reshape(-1, 12).astype(np.float32).copy()
+    Rt[group] = np.concatenate([_rot(*ang), np.asarray(t, np.float64)[:, None]], 1).reshape(12)
+    return Rt
+
+
 TBLOCK_POSES = (((0.9, 0.3, 0.4), (0.0, 0.55, 0.0)), ((-0.6, 0.8, -0.2), (0.15, 0.45, 0.1)))
 
 
@@ -305,13 +271,9 @@ def case_tblock():
     sc = synthetic(6000, 31, 0.03, n_groups=3)
     cam = ring(320, 240, 560.0, yaw=20.0)
     v, f = tblock(6.0)
-    poses = []
-    for ang, t in TBLOCK_POSES:
-        Rt = sc["Rt"].reshape(-1, 12).astype(np.float32).copy()
-        Rt[2] = np.concatenate([_rot(*ang), np.asarray(t, np.float64)[:, None]], 1).reshape(12)
-        poses.append(Rt)
     from sim_a_splat_amd.handler import TASK_MESH_COLOR
-    return dict(sc=sc, cams=[cam, cam], mesh=_mesh(v, f, TASK_MESH_COLOR, np.full(len(f), 2)), bg=BG, poses=poses)
+    return dict(sc=sc, cams=[cam, cam], mesh=_mesh(v, f, TASK_MESH_COLOR, np.full(len(f), 2)), bg=BG,
+                poses=[pose_rows(sc, 2, ang, t) for ang, t in TBLOCK_POSES])
 
 
 def case_soup():
@@ -398,83 +360,95 @@ def handler_setup():
                 masks=masks, icp=icp, fk=fk)
 
 
-def handler_predicted_rows(hs):
-    """The pose rows draw_handler gives the groups (links, the static rest, the task mesh), restated on the CPU."""
+def handler_predicted_rows(hs, robot=False):
+    """The pose rows draw_handler gives the groups (links, the static rest, the task mesh), restated on the CPU.  robot: and the rows
+    of the two robot meshes.  The k-th message link poses its mesh with icp o SE3(q / |q|, (p + weld) s) (the weld is zero here),
+    through the handle's quaternion."""
     from sim_a_splat_amd import poses
     s, Ri, ti = poses.decompose_icp(hs["icp"])
     msg = hs["msg"]
+
+    def mesh_row(k):
+        q = np.asarray(msg.quaternion[k], np.float64)
+        R = Ri @ poses.quat_wxyz_to_matrix(q / np.linalg.norm(q))
+        t = Ri @ (np.asarray(msg.position[k], np.float64) * s) + ti
+        return poses.rt_to_row12(poses.quat_wxyz_to_matrix(poses.matrix_to_quat_wxyz(R)), t)
+
     q = np.asarray(msg.quaternion[:2], np.float64)
     p = np.asarray(msg.position[:2], np.float64)
     R, t = poses.link_splat_poses(s, Ri, ti, np.stack([T[:3, :3] for T in hs["fk"]]), np.stack([T[:3, 3] for T in hs["fk"]]), q, p,
                                   np.zeros(3))
     rows = [poses.rt_to_row12(poses.quat_wxyz_to_matrix(poses.matrix_to_quat_wxyz(R[k])), t[k]) for k in range(2)]
-    rows.append(poses.rt_to_row12(np.eye(3), np.zeros(3)))
-    qb = np.asarray(msg.quaternion[2], np.float64)
-    qb = qb / np.linalg.norm(qb)
-    Rb = Ri @ poses.quat_wxyz_to_matrix(qb)
-    tb = Ri @ (np.asarray(msg.position[2], np.float64) * s) + ti
-    rows.append(poses.rt_to_row12(poses.quat_wxyz_to_matrix(poses.matrix_to_quat_wxyz(Rb)), tb))
-    return np.stack(rows).astype(np.float32).reshape(4, 12)
+    rows += [poses.rt_to_row12(np.eye(3), np.zeros(3)), mesh_row(2)] + ([mesh_row(0), mesh_row(1)] if robot else [])
+    return np.stack(rows).astype(np.float32).reshape(-1, 12)
 
 
-def case_handler(hs, rows, V, K):
-    """The handler's frame as a case: the Gaussians in registration order (links, then the rest), the block on row 3."""
-    from sim_a_splat_amd import poses
+def case_handler(hs, rows, V, K, robot=False):
+    """The handler's frame as a case: the Gaussians in registration order (links, then the rest), the block, flat, on row 3.  robot:
+    mesh_smooth_cases.robot_links, smooth, on rows 4 and 5 (zero normals for the block's vertices)."""
+    from sim_a_splat_amd import mesh_io, poses
     from sim_a_splat_amd.handler import TASK_MESH_COLOR
-    from sim_a_splat_amd.mesh_io import load_obj
     sc, masks, covs = hs["scene"], hs["masks"], hs["covs"]
     idx = [np.nonzero(masks[f"link{i}"])[0] for i in range(2)]
     rest = np.nonzero(~np.logical_or.reduce(list(masks.values())))[0]
     order = np.concatenate(idx + [rest])
     gid = np.concatenate([np.full(len(ix), i, np.uint8) for i, ix in enumerate(idx)] + [np.full(len(rest), 2, np.uint8)])
     cov6 = np.stack([covs[:, 0, 0], covs[:, 0, 1], covs[:, 0, 2], covs[:, 1, 1], covs[:, 1, 2], covs[:, 2, 2]], 1)[order]
+    G = 6 if robot else 4
     scd = dict(means=sc.means[order], op=sc.opacities[order], colors=hs["cols"][order], sh=-1, quats=None, scales=None, cov6=cov6, gid=gid,
-               G=4, Rt=np.asarray(rows, np.float32).reshape(4, 12))
-    s = poses.decompose_icp(hs["icp"])[0]
-    v, f = load_obj(GOLDEN / "tblock_paper.obj")
+               G=G, Rt=np.asarray(rows, np.float32).reshape(G, 12))
+    s = float(poses.decompose_icp(hs["icp"])[0])
+    v, f = mesh_io.load_obj(GOLDEN / "tblock_paper.obj")
+    verts, tris, groups = [(np.asarray(v, np.float64) * s).astype(np.float32)], [np.asarray(f, np.int32)], [np.full(len(f), 3)]
+    cols, normals = TASK_MESH_COLOR, None
+    if robot:
+        from mesh_smooth_cases import robot_links
+        cols, normals = [np.tile(np.asarray(TASK_MESH_COLOR, np.float32), (len(f), 1))], [np.zeros_like(verts[0])]
+        for k, (lv, lf, rgb) in enumerate(robot_links()):
+            lv, lf = mesh_io.weld(lv, lf)
+            tris.append(lf + sum(len(x) for x in verts))
+            verts.append((lv * s).astype(np.float32))
+            cols.append(np.tile(np.asarray(rgb, np.float32), (len(lf), 1)))
+            groups.append(np.full(len(lf), 4 + k))
+            normals.append(mesh_io.vertex_normals(lv, lf))
+        cols, normals = np.concatenate(cols), np.concatenate(normals)
     H, W = hs["size"]
     return dict(sc=scd, cams=[(np.asarray(V, np.float32), np.asarray(K, np.float32), W, H)],
-                mesh=_mesh((np.asarray(v, np.float64) * float(s)).astype(np.float32), f, TASK_MESH_COLOR, np.full(len(f), 3)),
-                bg=(0.0, 0.0, 0.0), poses=None)
+                mesh=_mesh(np.concatenate(verts), np.concatenate(tris), cols, np.concatenate(groups), normals=normals), bg=(0.0, 0.0, 0.0), poses=None)
 
 
-def case_handler_cpu():
+def case_handler_cpu(robot=False):
     from sim_a_splat_amd.scene import DEFAULT_VERTICAL_FOV, SplatScene
     hs = handler_setup()
     H, W = hs["size"]
     V, K = SplatScene._view_and_K(H, W, hs["cam"][0], hs["cam"][1], DEFAULT_VERTICAL_FOV)
-    return case_handler(hs, handler_predicted_rows(hs), V, K)
+    return case_handler(hs, handler_predicted_rows(hs, robot), V, K, robot)
 
 
 FIXED_CASES["handler"] = case_handler_cpu
 
 
-# ---- GPU side: what the tests do with a Rasterizer ------------------------------------------------------------------------
-def upload(r, sc, keep=None):
-    sel = slice(None) if keep is None else keep
-    pick = lambda a: None if a is None else np.asarray(a)[sel]
-    r.upload(pick(sc["means"]), pick(sc["op"]), pick(sc["colors"]), quats=pick(sc["quats"]), scales=pick(sc["scales"]),
-             covariances=pick(sc["cov6"]), sh_degree=sc["sh"], group_id=pick(sc["gid"]), n_groups=sc["G"])
-    if sc["G"]:
-        r.set_group_poses(sc["Rt"])
-
-
-def upload_case(r, case):
+# ---- GPU side: what the tests do with a Rasterizer and an expectation -------------------------------------------------------
+def upload_case(r, case, attributes=True):
     m = case["mesh"]
     upload(r, case["sc"])
-    r.upload_meshes(m["verts"], m["tris"], m["cols"], groups=m["groups"], ambient=m["ka"], diffuse=m["kd"])
+    kw = dict(vertex_normals=m["normals"], vertex_colors=m["vcols"]) if attributes and m["normals"] is not None else {}
+    r.upload_meshes(m["verts"], m["tris"], m["cols"], groups=m["groups"], ambient=m["ka"], diffuse=m["kd"], **kw)
 
 
-def to_numpy(out):
-    return {k: v.cpu().numpy() for k, v in out.items()}
+def single(r, case, view=0, **kw):
+    V, K, W, H = case["cams"][view]
+    return to_numpy(r.render(V, K, W, H, case["bg"], want=OUTS, **kw))
 
 
-def same(a, b, keys=OUTS, where=None):
-    for k in keys:
-        x, y = np.asarray(a[k]), np.asarray(b[k])
-        if where is not None:
-            x, y = x[where], y[where]
-        assert x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8)), (k, np.abs(x.astype(np.float64) - y).max())
+def expect(name, case, view=0):
+    """expected(case, view), printed and held to the caps."""
+    e = expected(case, view)
+    print(report(f"{name}[{view}]", case, e))
+    assert e["excluded"] <= MAX_EXCLUDED, report(name, case, e)
+    if name not in COVERAGE_IS_DRAWN:
+        assert e["driven"] >= MIN_DRIVEN, report(name, case, e)
+    return e
 
 
 def compare_stable(got, frame, stable, fill=False, bits=True):
@@ -497,3 +471,24 @@ def compare_stable(got, frame, stable, fill=False, bits=True):
             d = np.abs(x.astype(np.float64) - y.astype(np.float64))
             diffs.append(f"{k}: {int((d > 0).sum())} values differ on stable pixels, max {np.nanmax(d):.3e}")
     return diffs
+
+
+def compare(got, e, fill=False, bits=True):
+    """A GPU frame against the expectation `e`, on the reference's stable pixels: alpha and depth bit-equal; rgb and rgb8 bit-equal
+    where the winner is a flat triangle or none, and where it is smooth rgb within RGB_TOL, rgb8 within 1 LSB (the kernel interpolates
+    float32 attribute planes, the reference float64 barycentrics).  Returns (problems, max |rgb| error, max rgb8 error) -- the figures
+    over the stable smooth pixels.  A frame without smooth pixels: compare_stable on every output."""
+    frame, stable, sp = e["frame"], e["stable"], e["ref"]["smooth_pixel"]
+    pick = lambda *keys: {k: v for k, v in got.items() if k in keys}
+    probs = compare_stable(pick("alpha", "depth"), frame, stable, fill, bits) + compare_stable(pick("rgb", "rgb8"), frame, stable & ~sp, fill, bits)
+    on = stable & sp
+    err = err8 = 0.0
+    if "rgb" in got and on.any():
+        err = float(np.abs(np.asarray(got["rgb"], np.float64)[on] - np.asarray(frame["rgb"], np.float64)[on]).max())
+        if not err <= RGB_TOL:
+            probs.append(f"rgb: max {err:.3e} on stable smooth pixels > {RGB_TOL}")
+    if "rgb8" in got and on.any():
+        err8 = float(np.abs(np.asarray(got["rgb8"]).astype(np.int64)[on] - np.asarray(frame["rgb8"]).astype(np.int64)[on]).max())
+        if err8 > 1:
+            probs.append(f"rgb8: max {err8:.0f} LSB on stable smooth pixels")
+    return probs, err, err8

@@ -10,6 +10,7 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import mesh_cases as mc  # noqa: E402
+import oracle_fuzz as fz  # noqa: E402
 
 EPS32 = 2.0 ** -24
 CHANNELS = (3, 9, 24)                    # one chunk of 8, a partial second chunk, three chunks
@@ -25,15 +26,6 @@ MAX_REL_TOL = 1e-4                       # the scene-depth tolerance stays below
 # through the recolouring identity, which compares GPU frames on every pixel and needs neither stability nor a tolerance.
 DRAWN_SEEDS_SKIPPED = (3, 11)
 DRAWN_SEEDS = tuple(s for s in range(22) if s not in DRAWN_SEEDS_SKIPPED)
-
-
-def view_poses(case, view=0):
-    """The pose rows view `view` of a case is rendered with (None: a scene without groups)."""
-    sc = case["sc"]
-    if sc["gid"] is None:
-        return None
-    Rt = None if case.get("poses") is None else case["poses"][view]
-    return np.asarray(sc["Rt"] if Rt is None else Rt, np.float32).reshape(-1, 12)
 
 
 def draw_features(case, C, seed):
@@ -61,7 +53,7 @@ def oracle_recoloured_rgb(case, e, view, col, mcol, bg):
     w = e["ref"]["winner"]
     bgmap = np.where((w >= 0)[..., None], np.asarray(mcol, np.float32)[np.maximum(w, 0)], np.asarray(bg, np.float32).reshape(1, 1, 3))
     rc = recoloured(case, col, mcol, bg)
-    return mc.oracle_frame(rc["sc"], case["cams"][view], rc["bg"], Rt=view_poses(case, view), zlim=e["zlim"],
+    return mc.oracle_frame(rc["sc"], case["cams"][view], rc["bg"], Rt=mc.view_poses(case, view), zlim=e["zlim"],
                            bgmap=np.ascontiguousarray(bgmap, dtype=np.float32))["rgb"]
 
 
@@ -153,13 +145,5 @@ def expected_labels(case, e, view=0, min_alpha=0.5):
 
 # ---- drawn cases -------------------------------------------------------------------------------------------------------------------
 def drawn_case(seed):
-    """oracle_fuzz.draw_mesh_case(seed), first view, as a case of mesh_cases' form."""
-    import oracle_fuzz as fz
-    c = fz.draw_mesh_case(seed)
-    s, inp, cm, m = c["scene"], fz.scene_inputs(c), c["cams"][0], c["mesh"]
-    G = c["n_groups"]
-    sc = dict(means=s.means, op=s.opacities, colors=inp["colors"], sh=c["deg"], quats=inp["quats"], scales=inp["scales"], cov6=inp["cov6"],
-              gid=s.group_id if G else None, G=G, Rt=np.asarray(c["poses"][0], np.float32).reshape(-1, 12) if G else None)
-    mesh = mc._mesh(m["verts"], m["tris"], m["cols"], m["groups"], m["ka"], m["kd"])
-    return dict(sc=sc, cams=[(np.asarray(cm.viewmat, np.float32), np.asarray(cm.K, np.float32), c["W"], c["H"])], mesh=mesh,
-                bg=tuple(float(v) for v in c["bg"]), poses=None, describe=fz.describe_mesh(c))
+    """oracle_fuzz.draw_mesh_case(seed) as a case of mesh_cases' form (the tests take its first view)."""
+    return fz.as_case(fz.draw_mesh_case(seed))

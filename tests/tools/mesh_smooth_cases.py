@@ -1,7 +1,5 @@
-"""The fixed cases of smooth-shaded meshes (DESIGN.md 3 "Meshes", rule 2b), built on mesh_cases (imported, not edited): the same
-case dicts, whose ``mesh`` additionally carries ``normals [V,3]`` and, optionally, ``vcols [V,3]``.  ``expected(case, view)`` is
-mesh_smooth_ref.expected: mesh_cases' stability and caps, the frame with the smooth reference's colours.  CPU only; the GPU tests
-render the same inputs and compare (``compare``)."""
+"""The fixed cases of smooth-shaded meshes (DESIGN.md 3 "Meshes", rule 2b): mesh_cases' case dicts whose ``mesh`` carries ``normals [V,3]``
+and, optionally, ``vcols [V,3]``.  mesh_cases.expected / upload_case / compare take them as they take the flat ones.  CPU only."""
 import sys
 from pathlib import Path
 
@@ -9,9 +7,8 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import mesh_cases as mc  # noqa: E402
-import mesh_smooth_ref as msr  # noqa: E402
 
-RGB_TOL = 1e-4      # the project's parity gate: float32 attribute planes against the float64 reference
+RGB_TOL, pose_rows = mc.RGB_TOL, mc.pose_rows
 SPHERE_POSE = ((0.9, 0.3, 0.4), (0.0, 0.1, 0.0))
 
 
@@ -32,19 +29,6 @@ def uv_sphere(r, nu, nv):
     return (r * n).astype(np.float32), np.asarray(tris, np.int32), n.astype(np.float32)
 
 
-def smooth_mesh(verts, tris, cols, groups, normals, vcols=None, ka=0.4, kd=0.6):
-    m = mc._mesh(verts, tris, cols, groups, ka, kd)
-    m["normals"] = np.asarray(normals, np.float32)
-    m["vcols"] = None if vcols is None else np.asarray(vcols, np.float32)
-    return m
-
-
-def pose_rows(sc, group, ang, t):
-    Rt = sc["Rt"].reshape(-1, 12).astype(np.float32).copy()
-    Rt[group] = np.concatenate([mc._rot(*ang), np.asarray(t, np.float64)[:, None]], 1).reshape(12)
-    return Rt
-
-
 def sphere_parts(r, nu, nv, seed=5):
     v, f, n = uv_sphere(r, nu, nv)
     vc = np.random.default_rng(seed).uniform(0.15, 1.0, size=v.shape).astype(np.float32)
@@ -55,7 +39,7 @@ def case_sphere(W, H, f, n, ls, r, nu, nv):
     sc = mc.synthetic(n, 31, ls, n_groups=3)
     cam = mc.ring(W, H, f, yaw=20.0)
     v, t, nr, vc = sphere_parts(r, nu, nv)
-    mesh = smooth_mesh(v, t, (0.7, 0.7, 0.7), np.full(len(t), 2), nr, vc)
+    mesh = mc._mesh(v, t, (0.7, 0.7, 0.7), np.full(len(t), 2), normals=nr, vcols=vc)
     return dict(sc=sc, cams=[cam], mesh=mesh, bg=mc.BG, poses=[pose_rows(sc, 2, *SPHERE_POSE)])
 
 
@@ -84,7 +68,7 @@ def case_mixed():
         Rt = pose_rows(sc, 1, bang, bt)
         Rt[2] = np.concatenate([mc._rot(*sang), np.asarray(st, np.float64)[:, None]], 1).reshape(12)
         poses.append(Rt)
-    return dict(sc=sc, cams=[cam, cam], mesh=smooth_mesh(verts, tris, cols, groups, normals, vcols), bg=mc.BG, poses=poses)
+    return dict(sc=sc, cams=[cam, cam], mesh=mc._mesh(verts, tris, cols, groups, normals=normals, vcols=vcols), bg=mc.BG, poses=poses)
 
 
 NEAR_A = np.array([[0.03125, -0.03125, 0.015625], [-0.03125, 0.046875, 0.03125], [0.015625, 0.03125, -0.046875]])   # colour channel x world axis
@@ -113,7 +97,7 @@ def case_near_clip():
     vcols = near_clip_field(verts.astype(np.float64))
     assert vcols.min() >= 0.0 and vcols.max() <= 1.0, (vcols.min(), vcols.max(), verts)
     normals = np.tile(np.array([[0.0, 0.6, 0.8]], np.float32), (4, 1))
-    mesh = smooth_mesh(verts, tris, (0.5, 0.5, 0.5), np.zeros(len(tris)), normals, vcols, ka=1.0, kd=0.0)
+    mesh = mc._mesh(verts, tris, (0.5, 0.5, 0.5), np.zeros(len(tris)), ka=1.0, kd=0.0, normals=normals, vcols=vcols)
     return dict(sc=sc, cams=[cam], mesh=mesh, bg=mc.BG, poses=None)
 
 
@@ -128,7 +112,7 @@ def case_xarm6_base():
     n = mesh_io.vertex_normals(v, f)
     sc = mc.synthetic(1500, 31, 0.05, n_groups=3)
     cam = mc.ring(96, 64, 90.0, yaw=20.0)
-    mesh = smooth_mesh((v - v.mean(0)) * 8.0, f, (0.75, 0.75, 0.8), np.full(T, 2), n)
+    mesh = mc._mesh((v - v.mean(0)) * 8.0, f, (0.75, 0.75, 0.8), np.full(T, 2), normals=n)
     return dict(sc=sc, cams=[cam], mesh=mesh, bg=mc.BG, poses=[pose_rows(sc, 2, (1.2, 0.3, 0.4), (0.0, 0.1, 0.2))])
 
 
@@ -144,82 +128,5 @@ def robot_links():
     return out
 
 
-def handler_predicted_rows(hs):
-    """mesh_cases.handler_predicted_rows + the rows of the robot meshes: the k-th message link of the robot poses mesh k with
-    icp o SE3(q / |q|, (p + weld) s) (splat_handler.py:238-263; the weld is zero here), through the handle's quaternion."""
-    from sim_a_splat_amd import poses
-    s, Ri, ti = poses.decompose_icp(hs["icp"])
-    msg = hs["msg"]
-    rows = [mc.handler_predicted_rows(hs)]
-    for k in range(2):
-        q = np.asarray(msg.quaternion[k], np.float64)
-        R = Ri @ poses.quat_wxyz_to_matrix(q / np.linalg.norm(q))
-        t = Ri @ (np.asarray(msg.position[k], np.float64) * s) + ti
-        rows.append(poses.rt_to_row12(poses.quat_wxyz_to_matrix(poses.matrix_to_quat_wxyz(R)), t).astype(np.float32).reshape(1, 12))
-    return np.concatenate(rows).astype(np.float32)
-
-
-def case_handler(hs, rows, V, K):
-    """The handler's frame as a case: mesh_cases.case_handler's Gaussians and block (flat, row 3), the two links smooth on rows 4, 5."""
-    from sim_a_splat_amd import mesh_io, poses
-    base = mc.case_handler(hs, np.asarray(rows, np.float32).reshape(6, 12)[:4], V, K)
-    base["sc"].update(G=6, Rt=np.asarray(rows, np.float32).reshape(6, 12))
-    s = float(poses.decompose_icp(hs["icp"])[0])
-    m = base["mesh"]
-    verts, tris, cols, groups, normals = [m["verts"]], [m["tris"]], [np.broadcast_to(m["cols"].reshape(-1, 3), (len(m["tris"]), 3))], \
-        [m["groups"]], [np.zeros_like(m["verts"])]
-    for k, (v, f, rgb) in enumerate(robot_links()):
-        v, f = mesh_io.weld(v, f)
-        tris.append(f + sum(len(x) for x in verts))
-        verts.append((v * s).astype(np.float32))
-        cols.append(np.tile(np.asarray(rgb, np.float32), (len(f), 1)))
-        groups.append(np.full(len(f), 4 + k))
-        normals.append(mesh_io.vertex_normals(v, f))
-    base["mesh"] = smooth_mesh(np.concatenate(verts), np.concatenate(tris), np.concatenate(cols), np.concatenate(groups), np.concatenate(normals))
-    return base
-
-
-def case_handler_cpu():
-    from sim_a_splat_amd.scene import DEFAULT_VERTICAL_FOV, SplatScene
-    hs = mc.handler_setup()
-    H, W = hs["size"]
-    V, K = SplatScene._view_and_K(H, W, hs["cam"][0], hs["cam"][1], DEFAULT_VERTICAL_FOV)
-    return case_handler(hs, handler_predicted_rows(hs), V, K)
-
-
 FIXED_CASES = {**{k: (lambda a=a: case_sphere(*a)) for k, a in SPHERES.items()}, "mixed": case_mixed, "near_clip": case_near_clip,
-               "entry_points": lambda: case_sphere(*SPHERES["sphere_small"]), "xarm6_base": case_xarm6_base, "handler": case_handler_cpu}
-
-
-def expected(case, view=0):
-    return msr.expected(case, view, mc)
-
-
-# ---- GPU side -------------------------------------------------------------------------------------------------------------
-def upload_case(r, case, attributes=True):
-    m = case["mesh"]
-    mc.upload(r, case["sc"])
-    kw = dict(vertex_normals=m["normals"], vertex_colors=m["vcols"]) if attributes else {}
-    r.upload_meshes(m["verts"], m["tris"], m["cols"], groups=m["groups"], ambient=m["ka"], diffuse=m["kd"], **kw)
-
-
-def compare(got, e):
-    """A GPU frame against the expectation, on the reference's stable pixels: alpha and depth bit-equal, rgb within RGB_TOL, rgb8
-    within 1 LSB; where the winner is a flat triangle or none, every output bit-equal.  Returns (problems, max |rgb| error, max rgb8
-    error) -- the figures over the stable smooth pixels."""
-    stable, sp = e["stable"], e["ref"]["smooth_pixel"]
-    frame = e["frame"]
-    flat = stable & ~sp
-    probs = mc.compare_stable({k: v for k, v in got.items() if k in ("alpha", "depth")}, frame, stable)
-    probs += mc.compare_stable({k: v for k, v in got.items() if k in ("rgb", "rgb8")}, frame, flat)
-    on = stable & sp
-    err = err8 = 0.0
-    if "rgb" in got and on.any():
-        err = float(np.abs(np.asarray(got["rgb"], np.float64)[on] - np.asarray(frame["rgb"], np.float64)[on]).max())
-        if not err <= RGB_TOL:
-            probs.append(f"rgb: max {err:.3e} on stable smooth pixels > {RGB_TOL}")
-    if "rgb8" in got and on.any():
-        err8 = float(np.abs(np.asarray(got["rgb8"]).astype(np.int64)[on] - np.asarray(frame["rgb8"]).astype(np.int64)[on]).max())
-        if err8 > 1:
-            probs.append(f"rgb8: max {err8:.0f} LSB on stable smooth pixels")
-    return probs, err, err8
+               "entry_points": lambda: case_sphere(*SPHERES["sphere_small"]), "xarm6_base": case_xarm6_base, "handler": lambda: mc.case_handler_cpu(robot=True)}

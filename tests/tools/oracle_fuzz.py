@@ -123,6 +123,31 @@ def scene_inputs(c: dict) -> dict:
     return dict(colors=colors, quats=None, scales=None, cov=cov, cov6=cov6)
 
 
+def pose_per_view(c: dict) -> list:
+    """The pose rows each view is rendered with (None: a scene without groups): its own set in a posed batch, else the first."""
+    n = len(c["cams"])
+    if not c["poses"]:
+        return [None] * n
+    return list(c["poses"][:n]) if c["entry"] == "posed" else [c["poses"][0]] * n
+
+
+def render_views(r, c: dict) -> list:
+    """The case's views through its entry point (single, batch, posed, host), one dict of outputs per view; the scene is uploaded."""
+    cams, W, H, fill, BG = c["cams"], c["W"], c["H"], c["fill"], c["bg"]
+    Vs, Ks = np.stack([cm.viewmat for cm in cams]), np.stack([cm.K for cm in cams])
+    if c["poses"] and c["entry"] != "posed":
+        r.set_group_poses(c["poses"][0])
+    if c["entry"] == "single":
+        o = r.render(Vs[0], Ks[0], W, H, BG, want=KEYS, depth_fill_max=fill, full_sort=c["full_sort"])
+        return [{k: v.cpu().numpy() for k, v in o.items()}]
+    if c["entry"] == "host":
+        frames = r.render_batch_host(Vs, Ks, W, H, BG).numpy()
+        return [{"rgb8": frames[i]} for i in range(len(cams))]
+    kw = dict(pose_sets=np.stack(c["poses"]), pose_set=list(range(len(cams)))) if c["entry"] == "posed" else {}
+    o = r.render_batch(Vs, Ks, W, H, BG, want=KEYS, depth_fill_max=fill, **kw)
+    return [{k: v[i].cpu().numpy() for k, v in o.items()} for i in range(len(cams))]
+
+
 def run_case(r, c: dict) -> list:
     """Renders the case on the GPU through its entry point and with the oracle view by view; returns the differences found."""
     sc, cams, W, H, fill, BG = c["scene"], c["cams"], c["W"], c["H"], c["fill"], c["bg"]
@@ -130,29 +155,9 @@ def run_case(r, c: dict) -> list:
     gid = sc.group_id if c["n_groups"] else None
     r.upload(sc.means, sc.opacities, inp["colors"], quats=inp["quats"], scales=inp["scales"], covariances=inp["cov"], sh_degree=c["deg"],
              group_id=gid, n_groups=c["n_groups"])
-    Vs, Ks = np.stack([cm.viewmat for cm in cams]), np.stack([cm.K for cm in cams])
-    view_pose = [None] * len(cams)
-    got = []
     if c["entry"] == "pipelined":
         return run_pipelined(r, c, inp, gid)
-    if c["entry"] == "single":
-        if c["poses"]:
-            r.set_group_poses(c["poses"][0]); view_pose[0] = c["poses"][0]
-        o = r.render(Vs[0], Ks[0], W, H, BG, want=KEYS, depth_fill_max=fill, full_sort=c["full_sort"])
-        got.append({k: v.cpu().numpy() for k, v in o.items()})
-    elif c["entry"] == "posed":
-        o = r.render_batch(Vs, Ks, W, H, BG, want=KEYS, depth_fill_max=fill, pose_sets=np.stack(c["poses"]), pose_set=list(range(len(cams))))
-        got = [{k: v[i].cpu().numpy() for k, v in o.items()} for i in range(len(cams))]
-        view_pose = list(c["poses"])
-    else:
-        if c["poses"]:
-            r.set_group_poses(c["poses"][0]); view_pose = [c["poses"][0]] * len(cams)
-        if c["entry"] == "host":
-            frames = r.render_batch_host(Vs, Ks, W, H, BG).numpy()
-            got = [{"rgb8": frames[i]} for i in range(len(cams))]
-        else:
-            o = r.render_batch(Vs, Ks, W, H, BG, want=KEYS, depth_fill_max=fill)
-            got = [{k: v[i].cpu().numpy() for k, v in o.items()} for i in range(len(cams))]
+    got, view_pose = render_views(r, c), pose_per_view(c)
     diffs = []
     for i, cm in enumerate(cams):
         ref = oracle.render(sc.means, sc.opacities, inp["colors"], cm.viewmat, cm.K, W, H, quats=inp["quats"], scales=inp["scales"], cov6=inp["cov6"],
@@ -274,28 +279,22 @@ def draw_mesh_case(seed: int, poison_all: bool = False) -> dict:
     return c
 
 
-def _view_poses(c: dict) -> list:
-    if not c["poses"]:
-        return [None] * len(c["cams"])
-    return list(c["poses"][:len(c["cams"])]) if c["entry"] == "posed" else [c["poses"][0]] * len(c["cams"])
+def as_case(c: dict) -> dict:
+    """A drawn mesh case in mesh_cases' form: every view, with the pose rows its entry point renders it with."""
+    import mesh_cases as mc
+    s, inp, m, G = c["scene"], scene_inputs(c), c["mesh"], c["n_groups"]
+    sc = dict(means=s.means, op=s.opacities, colors=inp["colors"], sh=c["deg"], quats=inp["quats"], scales=inp["scales"], cov6=inp["cov6"],
+              gid=s.group_id if G else None, G=G, Rt=np.asarray(c["poses"][0], np.float32).reshape(-1, 12) if G else None)
+    return dict(sc=sc, cams=[(np.asarray(cm.viewmat, np.float32), np.asarray(cm.K, np.float32), c["W"], c["H"]) for cm in c["cams"]],
+                mesh=mc._mesh(m["verts"], m["tris"], m["cols"], m["groups"], m["ka"], m["kd"]), bg=tuple(float(v) for v in c["bg"]),
+                poses=pose_per_view(c) if G else None, describe=describe_mesh(c))
 
 
 def mesh_reference(c: dict, i: int, want_frame: bool = True) -> dict:
-    """View i of a mesh case from the reference and the oracle alone: stable mask, excluded share and (want_frame) the frame."""
-    from oracle import mesh_ref
-    sc, cm, m, W, H = c["scene"], c["cams"][i], c["mesh"], c["W"], c["H"]
-    inp = scene_inputs(c)
-    gid = sc.group_id if c["n_groups"] else None
-    pose = _view_poses(c)[i]
-    kw = dict(quats=inp["quats"], scales=inp["scales"], cov6=inp["cov6"], sh_degree=c["deg"], group_id=gid, group_Rt=pose, background=c["bg"])
-    dump = oracle.render(sc.means, sc.opacities, inp["colors"], cm.viewmat, cm.K, W, H, dump=True, **kw)
-    ref = mesh_ref.reference(m["verts"], m["tris"], m["cols"], m["groups"], pose if gid is not None else None, m["ka"], m["kd"], cm.viewmat, cm.K, W, H)
-    st = mesh_ref.stability(ref, dump)
-    out = dict(stable=st["stable"], excluded=float(1.0 - st["stable"].mean()), covered=float((ref["winner"] >= 0).mean()))
-    if want_frame:
-        zlim, bgmap = mesh_ref.frame_inputs(ref, c["bg"])
-        out["frame"] = oracle.render(sc.means, sc.opacities, inp["colors"], cm.viewmat, cm.K, W, H, want_rgb8=True, zlim=zlim, bgmap=bgmap, **kw)
-    return out
+    """View i of a mesh case from the reference and the oracle alone: stable mask, excluded and covered share and (want_frame) the frame."""
+    import mesh_cases as mc
+    e = mc.expected(as_case(c), i, want_frame=want_frame)
+    return {k: e[k] for k in ("stable", "excluded", "covered") + (("frame",) if want_frame else ())}
 
 
 def mesh_excluded_share(c: dict) -> float:
@@ -305,32 +304,14 @@ def mesh_excluded_share(c: dict) -> float:
 def run_mesh_case(r, c: dict):
     """Renders the mesh case on the GPU through its entry point; returns (differences on stable pixels, largest excluded share)."""
     import mesh_cases as mc
-    sc, cams, W, H, fill, BG, m = c["scene"], c["cams"], c["W"], c["H"], c["fill"], c["bg"], c["mesh"]
-    inp = scene_inputs(c)
-    gid = sc.group_id if c["n_groups"] else None
-    r.upload(sc.means, sc.opacities, inp["colors"], quats=inp["quats"], scales=inp["scales"], covariances=inp["cov"], sh_degree=c["deg"],
-             group_id=gid, n_groups=c["n_groups"])
-    r.upload_meshes(m["verts"], m["tris"], m["cols"], groups=m["groups"], ambient=m["ka"], diffuse=m["kd"])
-    Vs, Ks = np.stack([cm.viewmat for cm in cams]), np.stack([cm.K for cm in cams])
-    if c["poses"]:
-        r.set_group_poses(c["poses"][0])
-    if c["entry"] == "single":
-        o = r.render(Vs[0], Ks[0], W, H, BG, want=KEYS, depth_fill_max=fill)
-        got = [{k: v.cpu().numpy() for k, v in o.items()}]
-    elif c["entry"] == "posed":
-        o = r.render_batch(Vs, Ks, W, H, BG, want=KEYS, depth_fill_max=fill, pose_sets=np.stack(c["poses"]), pose_set=list(range(len(cams))))
-        got = [{k: v[i].cpu().numpy() for k, v in o.items()} for i in range(len(cams))]
-    elif c["entry"] == "host":
-        frames = r.render_batch_host(Vs, Ks, W, H, BG).numpy()
-        got = [{"rgb8": frames[i]} for i in range(len(cams))]
-    else:
-        o = r.render_batch(Vs, Ks, W, H, BG, want=KEYS, depth_fill_max=fill)
-        got = [{k: v[i].cpu().numpy() for k, v in o.items()} for i in range(len(cams))]
+    case = as_case(c)
+    mc.upload_case(r, case)
+    got = render_views(r, c)
     diffs, excluded = [], 0.0
-    for i in range(len(cams)):
-        e = mesh_reference(c, i)
+    for i in range(len(got)):
+        e = mc.expected(case, i)
         excluded = max(excluded, e["excluded"])
-        diffs += [f"view {i} {d}" for d in mc.compare_stable(got[i], e["frame"], e["stable"], fill=fill, bits=False)]
+        diffs += [f"view {i} {d}" for d in mc.compare(got[i], e, fill=c["fill"], bits=False)[0]]
     return diffs, excluded
 
 
