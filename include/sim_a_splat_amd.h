@@ -254,6 +254,35 @@ int sas_scene_mesh_features(sas_ctx *ctx, int64_t n_triangles, int channels, con
 int sas_scene_mesh_vertex_attributes(sas_ctx *ctx, int64_t n_vertices, const float *normals_or_null, const float *colors_or_null);
 
 /*
+ * Point-to-mesh queries ("Mesh queries"): for every (mesh, point) pair the unsigned distance to the mesh and the mesh's
+ * generalised winding number at the point.  Serves the segmentation step that makes the per-link masks (match_splat.py:240-251:
+ * per link mesh, occupancy > 0.5 or distance < 0.015 of every Gaussian centre).
+ *   points        [n_points,3] float32; vertices [n_vertices,3] float32, ALREADY in the points' frame; triangles [n_triangles,3] int32
+ *                 vertex indices: host or device pointers
+ *   mesh_offsets  [n_meshes+1] HOST: mesh m owns triangles mesh_offsets[m] .. mesh_offsets[m+1]-1; non-decreasing, first 0, last
+ *                 n_triangles; an empty mesh is allowed; 1 <= n_meshes <= 256
+ *   max_distance  >= 0, INFINITY allowed: beyond it a distance need not be known (see culling)
+ *   distance      [n_meshes,n_points] f32 DEVICE or NULL: Euclidean distance to the nearest point of any kept triangle of the mesh
+ *   winding       [n_meshes,n_points] f32 DEVICE or NULL: sum_k Omega_k / (4 pi), Omega_k = 2 atan2(a . (b x c), |a||b||c| + (a . b)|c|
+ *                 + (b . c)|a| + (c . a)|b|) the signed solid angle of triangle k from the point (a, b, c: its vertices minus the
+ *                 point): 1 inside a closed mesh whose triangles are counter-clockwise seen from outside, 0 outside
+ * Kept triangles: those with three finite vertices.  A zero-area triangle (its edge cross product is zero in float32) counts for the
+ * distance with its three edges as segments, and for no solid angle.
+ * Culling: a pair is culled exactly when the point lies outside the box of the mesh's kept triangles' vertices inflated by
+ * max_distance -- p < lo - max_distance or p > hi + max_distance on some axis, in float32 -- when the mesh has no kept triangle, or
+ * when a coordinate of the point is not finite.  A culled pair reads distance = +inf, winding = 0; max_distance = INFINITY culls by
+ * the last two rules only.  No NaN is written.
+ * Two calls with the same inputs return the same bits, and a pair's result does not depend on the other meshes or points of the call.
+ * No scene is required and nothing the context stores is touched.  Frames in flight are completed first; the call returns with the
+ * outputs in place (`stream`: the caller's, behind whose pending work the outputs are written).
+ * SAS_ERR_INVALID: a vertex index out of range, bad offsets, n_meshes out of range, a negative or NaN max_distance, both outputs
+ * NULL, a negative size or a missing array.  n_points == 0 is SAS_OK.
+ */
+int sas_query_meshes(sas_ctx *ctx, int64_t n_points, const float *points, int64_t n_vertices, const float *vertices,
+                     int64_t n_triangles, const int32_t *triangles, int n_meshes, const int64_t *mesh_offsets, float max_distance,
+                     float *distance, float *winding, void *stream);
+
+/*
  * Render n_views views of the same size in one call.  Serves the per-camera loops of
  * SplatHandler.render / SplatEnvWrapper.render (splat_handler.py:337-345, splat_env_wrapper.py:147-158).
  *   viewmats [n_views,16], Ks [n_views,9] host arrays; outputs are [n_views,H,W,...] device arrays

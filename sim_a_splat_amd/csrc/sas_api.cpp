@@ -229,6 +229,7 @@ struct sas_ctx : Settings {
     DevBuf mesh_nrm, mesh_vcol;   // vertex attributes (sas_scene_mesh_vertex_attributes): float4 normals, float4 colours, [mesh.nv] each
     bool mesh_has_vcol = false;   // ... colours were given
     DevBuf mesh_feat;        // per-triangle feature rows (sas_scene_mesh_features): [chunks][nt][SAS_FEAT_K], feat_c channels
+    DevBuf query_pts, query_tri, query_mesh, query_list, query_count;   // scratch of sas_query_meshes (SasQuery)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
     // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
     // the call returns: nothing is remembered across calls)
@@ -1589,6 +1590,88 @@ int sas_scene_mesh_vertex_attributes(sas_ctx *c, int64_t n_vertices, const float
     return SAS_OK;
 }
 
+int sas_query_meshes(sas_ctx *c, int64_t n_points, const float *points, int64_t n_vertices, const float *vertices, int64_t n_triangles,
+                     const int32_t *triangles, int n_meshes, const int64_t *mesh_offsets, float max_distance, float *distance,
+                     float *winding, void *stream)
+{
+    if (!c) return SAS_ERR_INVALID;
+    if (n_points < 0 || n_points > 0x7fffff00ll || n_vertices < 0 || n_vertices > 0x7fffffffll || n_triangles < 0 || n_triangles > (1 << 29))
+        return fail(c, SAS_ERR_INVALID, "bad query sizes: %lld points, %lld vertices, %lld triangles", (long long)n_points,
+                    (long long)n_vertices, (long long)n_triangles);
+    if (n_meshes < 1 || n_meshes > 256) return fail(c, SAS_ERR_INVALID, "n_meshes %d out of [1,256]", n_meshes);
+    if (!(max_distance >= 0.0f)) return fail(c, SAS_ERR_INVALID, "max_distance must be >= 0 (INFINITY allowed), got %g", (double)max_distance);
+    if (!distance && !winding) return fail(c, SAS_ERR_INVALID, "distance and winding are both NULL");
+    if (!mesh_offsets || (n_points > 0 && !points) || (n_triangles > 0 && (!vertices || !triangles)))
+        return fail(c, SAS_ERR_INVALID, "points, vertices, triangles and mesh_offsets are required");
+    if (mesh_offsets[0] != 0 || mesh_offsets[n_meshes] != n_triangles)
+        return fail(c, SAS_ERR_INVALID, "mesh_offsets must run from 0 to n_triangles=%lld, got %lld .. %lld", (long long)n_triangles,
+                    (long long)mesh_offsets[0], (long long)mesh_offsets[n_meshes]);
+    for (int m = 0; m < n_meshes; ++m)
+        if (mesh_offsets[m + 1] < mesh_offsets[m])
+            return fail(c, SAS_ERR_INVALID, "mesh_offsets decrease at mesh %d: %lld > %lld", m, (long long)mesh_offsets[m], (long long)mesh_offsets[m + 1]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nv = (size_t)n_vertices, nt = (size_t)n_triangles, np = (size_t)n_points;
+    std::vector<float> v(3 * nv);
+    std::vector<int32_t> tri(3 * nt);
+    if (nv && nt) HIP_TRY(c, hipMemcpy(v.data(), vertices, sizeof(float) * 3 * nv, hipMemcpyDefault));
+    if (nt) HIP_TRY(c, hipMemcpy(tri.data(), triangles, sizeof(int32_t) * 3 * nt, hipMemcpyDefault));
+    // the kept triangles (three finite vertices) as records, mesh by mesh, and each mesh's box over their vertices
+    std::vector<float4> rec;
+    rec.reserve(3 * nt);
+    std::vector<SasQueryMesh> table((size_t)n_meshes);
+    for (int m = 0; m < n_meshes; ++m) {
+        SasQueryMesh &q = table[(size_t)m];
+        q.start = (int)(rec.size() / 3);
+        for (int k = 0; k < 3; ++k) { q.lo[k] = INFINITY; q.hi[k] = -INFINITY; }
+        for (size_t t = (size_t)mesh_offsets[m]; t < (size_t)mesh_offsets[m + 1]; ++t) {
+            bool finite = true;
+            for (int k = 0; k < 3; ++k) {
+                const int32_t id = tri[3 * t + k];
+                if (id < 0 || (int64_t)id >= n_vertices)
+                    return fail(c, SAS_ERR_INVALID, "triangles[%zu][%d]=%d out of [0,%lld)", t, k, id, (long long)n_vertices);
+                const float *p = &v[3 * (size_t)id];
+                finite = finite && std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+            }
+            if (!finite) continue;
+            for (int k = 0; k < 3; ++k) {
+                const float *p = &v[3 * (size_t)tri[3 * t + k]];
+                rec.push_back(make_float4(p[0], p[1], p[2], 0.0f));
+                for (int a = 0; a < 3; ++a) { q.lo[a] = std::min(q.lo[a], p[a]); q.hi[a] = std::max(q.hi[a], p[a]); }
+            }
+        }
+        q.count = (int)(rec.size() / 3) - q.start;
+    }
+    if (n_points == 0) return SAS_OK;
+    if (const int rc = complete_all(c)) return rc;
+    int rc;
+    if ((rc = ensure(c, c->query_pts, sizeof(float) * 3 * np))) return rc;
+    if ((rc = ensure(c, c->query_tri, sizeof(float4) * std::max<size_t>(rec.size(), 1)))) return rc;
+    if ((rc = ensure(c, c->query_mesh, sizeof(SasQueryMesh) * table.size()))) return rc;
+    if ((rc = ensure(c, c->query_list, sizeof(int) * np * table.size()))) return rc;
+    if ((rc = ensure(c, c->query_count, sizeof(int) * table.size()))) return rc;
+    HIP_TRY(c, hipMemcpy(c->query_pts.p, points, sizeof(float) * 3 * np, hipMemcpyDefault));
+    if (!rec.empty()) HIP_TRY(c, hipMemcpy(c->query_tri.p, rec.data(), sizeof(float4) * rec.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->query_mesh.p, table.data(), sizeof(SasQueryMesh) * table.size(), hipMemcpyHostToDevice));
+    SasQuery q{};
+    q.points = (const float *)c->query_pts.p;
+    q.tri = (const float4 *)c->query_tri.p;
+    q.mesh = (const SasQueryMesh *)c->query_mesh.p;
+    q.list = (int *)c->query_list.p;
+    q.count = (int *)c->query_count.p;
+    q.distance = distance;
+    q.winding = winding;
+    q.n = n_points;
+    q.n_tri = (long long)(rec.size() / 3);
+    q.n_meshes = n_meshes;
+    q.max_distance = max_distance;
+    hipStream_t st = (hipStream_t)stream;
+    sas_launch_query(st, q);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "mesh query: %s", hipGetErrorString(e));
+    return SAS_OK;
+}
+
 int sas_render_rgbd(sas_ctx *c, const float *viewmat, const float *K, int width, int height, const float *background,
                     unsigned flags, const float *max_depth, float *rgb, float *alpha, float *depth, float *points,
                     uint8_t *mask, void *stream)
@@ -1748,16 +1831,17 @@ int sas_frames_completed(sas_ctx *c, int64_t *submitted, int64_t *completed)
 extern "C" int sas_debug_bounds_kernels(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_tiles(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_mesh(unsigned long long *out, int reset);
+extern "C" int sas_debug_bounds_query(unsigned long long *out, int reset);
 /* Bounds-checked build only: out[0] = guarded accesses found out of range since the last reset (they were
  * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none). */
 int sas_debug_bounds(unsigned long long *out, int reset)
 {
-    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0};
+    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
     if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset) ||
-        sas_debug_bounds_mesh(m, reset))
+        sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset))
         return SAS_ERR_HIP;
-    const unsigned long long *first = a[0] ? a : (b[0] ? b : m);
-    out[0] = a[0] + b[0] + m[0];
+    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : q));
+    out[0] = a[0] + b[0] + m[0] + q[0];
     out[1] = first[1]; out[2] = first[2]; out[3] = first[3];
     return SAS_OK;
 }

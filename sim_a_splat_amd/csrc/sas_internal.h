@@ -1,4 +1,4 @@
-// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -294,3 +294,24 @@ void sas_launch_mesh_bin(hipStream_t st, const SasMeshScene &m, const SasParams 
 // sas_launch_blend for a frame with meshes (planes != nullptr: k_blend_mesh_smooth)
 void sas_launch_blend_mesh(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
                            const SasMeshFrame &mf, const SasMeshExtra &x, const float4 *planes, bool fast_exp, bool want_max);
+
+// Point-to-mesh queries (sas_query_meshes; DESIGN.md 3, "Mesh queries").  The host keeps a mesh's triangles with three finite vertices
+// as records of three float4 (A, B, C; w unused) and the float32 box of their vertices; both kernels take the whole query by value.
+#define SAS_QUERY_CHUNK 256   // triangles k_query_eval stages in LDS at a time (12 KiB)
+struct SasQueryMesh {
+    float lo[3], hi[3];   // box over the vertices of the kept triangles (lo > hi: none)
+    int start, count;     // its records: tri[3 start .. 3 (start + count))
+};
+struct SasQuery {
+    const float *points;        // [n,3]
+    const float4 *tri;          // [3 n_tri]
+    const SasQueryMesh *mesh;   // [n_meshes]
+    int *list;                  // [n_meshes][n] candidate point ids per mesh, count[m] of them, in no particular order
+    int *count;                 // [n_meshes]
+    float *distance, *winding;  // [n_meshes][n] device, either may be nullptr
+    long long n, n_tri;
+    int n_meshes;
+    float max_distance;
+};
+// count <- 0, the box pass (culled pairs read +inf / 0), the evaluation of the candidates
+void sas_launch_query(hipStream_t st, const SasQuery &q);

@@ -41,6 +41,28 @@ def cov3x3_to_cov6(cov: ArrayLike) -> ArrayLike:
 
 
 MAX_FEATURES = 256   # channels of a feature store (sas_scene_features)
+MESH_QUERY_CHUNK = _capi.SAS_QUERY_CHUNK   # triangles query_meshes' kernel stages at a time: mesh sizes around it take its chunk edges
+MAX_QUERY_MESHES = 256
+
+
+def pack_query_meshes(meshes) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``[(vertices [V,3], faces [F,3]), ...]`` as one call's arrays (sas_query_meshes): vertices float32 (rounded once), faces int32
+    re-based into the joint vertex array, triangle offsets int64 ``[M+1]``.  ValueError on a face index outside its own mesh."""
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+    if not 1 <= len(meshes) <= MAX_QUERY_MESHES:
+        raise ValueError(f"query_meshes takes 1..{MAX_QUERY_MESHES} meshes, got {len(meshes)}")
+    vs, fs, offsets, base = [], [], [0], 0
+    for k, (v, f) in enumerate(meshes):
+        v = np.asarray(host(v), dtype=np.float64).reshape(-1, 3).astype(np.float32)
+        f = np.asarray(host(f), dtype=np.int64).reshape(-1, 3)
+        if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+            raise ValueError(f"mesh {k}: face indices out of [0,{v.shape[0]})")
+        vs.append(v)
+        fs.append(f + base)
+        base += v.shape[0]
+        offsets.append(offsets[-1] + f.shape[0])
+    return (np.ascontiguousarray(np.concatenate(vs)), np.ascontiguousarray(np.concatenate(fs).astype(np.int32)),
+            np.asarray(offsets, dtype=np.int64))
 
 
 def feature_channels(shape: Sequence[int], n: int) -> int:
@@ -319,6 +341,29 @@ class Rasterizer:
         C = mesh_onehot_channels(self._mesh_groups, T, self.n_features) if features is None else mesh_feature_channels(features.shape, T, self.n_features)
         self._store_rows("sas_scene_mesh_features", features, T, C, "mesh features")
         self._mesh_features_onehot = features is None
+
+    # -- queries ----------------------------------------------------------------------------
+    @_locked
+    def query_meshes(self, points: ArrayLike, meshes, max_distance: float = float("inf")) -> Dict[str, torch.Tensor]:
+        """Distance and inside test of ``points [N,3]`` against ``meshes``, a list of ``(vertices [V,3], faces [F,3])`` already in
+        the points' frame (sas_query_meshes; DESIGN.md 3, "Mesh queries").  Returns float32 device tensors ``[M,N]``:
+        ``distance``, the unsigned Euclidean distance to mesh m, and ``winding``, its generalised winding number (1 inside a closed,
+        outward-oriented mesh, 0 outside).  A pair whose point lies outside the mesh's box inflated by ``max_distance`` is culled
+        and reads ``+inf`` / ``0``, as does a point with a non-finite coordinate; ``inf`` culls nothing else.  Needs no scene and
+        leaves the uploaded one alone."""
+        v, f, offsets = pack_query_meshes(meshes)
+        n = int(points.shape[0])
+        p, pp = _as_f32(points, (n, 3), "points")
+        if isinstance(p, torch.Tensor) and p.is_cuda:
+            torch.cuda.synchronize(p.device)   # device-resident inputs must be complete before the copy
+        M = len(offsets) - 1
+        res = {k: torch.empty((M, n), dtype=torch.float32, device=self.device) for k in ("distance", "winding")}
+        if n == 0:
+            return res
+        self._check(self._L.sas_query_meshes(self._ctx, n, pp, v.shape[0], v.ctypes.data, f.shape[0], f.ctypes.data, M,
+                                             offsets.ctypes.data, float(max_distance), res["distance"].data_ptr(), res["winding"].data_ptr(),
+                                             self._stream()), "sas_query_meshes")
+        return res
 
     @_locked
     def set_group_poses(self, Rt: ArrayLike) -> None:
