@@ -283,6 +283,34 @@ int sas_query_meshes(sas_ctx *ctx, int64_t n_points, const float *points, int64_
                      float *distance, float *winding, void *stream);
 
 /*
+ * Nearest-neighbour matching of two point clouds, with the moments a closed-form similarity fit needs: the hot path of the ICP
+ * registration (match_splat.py:208-223 runs open3d's registration_icp; sim_a_splat_amd/register.py runs the loop around this call).
+ * DESIGN.md 3, "Point matching".
+ *   source        [n_source,3] f32, host or device
+ *   target        [n_target,3] f32, host or device
+ *   transform     [12] HOST, row-major A|t (3x4: the upper rows of a 4x4), finite; NULL = identity.  Source point p is matched as
+ *                 p' = A p + t, each component ((A_k0 x + A_k1 y) + A_k2 z) + t_k in float32, nothing fused
+ *   max_distance  >= 0, INFINITY allowed: a match holds only if d2 <= max_distance * max_distance (the product in float32)
+ *   slices        0: the library's choice; > 0: the target is searched in that many slices (clamped to its number of chunks of
+ *                 SAS_MATCH_CHUNK = 256 targets).  No output depends on it
+ *   index         [n_source] i32, host or device, or NULL: the matched target, -1 without a held match
+ *   dist2         [n_source] f32, host or device, or NULL: d2 of the held match, +inf without one
+ *   moments       [18] f64 HOST or NULL, over the held matches, from the float32 p', q and d2 widened: n, sum p' (3), sum q (3),
+ *                 sum q p'^T (9, row-major), sum |p'|^2, sum d2
+ * Per source point: d2 to target j = ((dx dx + dy dy) + dz dz), d = q_j - p', in float32.  A target whose d2 is not < INFINITY (a
+ * non-finite coordinate, overflow) never matches, and a source with a non-finite p' has no match.  The match is the target with
+ * the smallest d2, among equal d2 the lowest index.  No NaN is written.
+ * Two calls with the same inputs return the same bits in all three outputs, and a point's result does not depend on the other
+ * source points of the call nor on `slices`.  No scene is required and nothing the context stores is touched.  Frames in flight
+ * are completed first; the call returns with the outputs in place (`stream`: the caller's).
+ * SAS_ERR_INVALID: a negative size or one beyond 2^31 - 256, a missing array, a negative or NaN max_distance, a non-finite
+ * transform, slices < 0, all three outputs NULL.  n_source == 0 is SAS_OK; n_target == 0 is SAS_OK with every index -1 and n = 0.
+ */
+int sas_match_points(sas_ctx *ctx, int64_t n_source, const float *source, int64_t n_target, const float *target,
+                     const float *transform, float max_distance, int slices, int32_t *index, float *dist2, double *moments,
+                     void *stream);
+
+/*
  * Render n_views views of the same size in one call.  Serves the per-camera loops of
  * SplatHandler.render / SplatEnvWrapper.render (splat_handler.py:337-345, splat_env_wrapper.py:147-158).
  *   viewmats [n_views,16], Ks [n_views,9] host arrays; outputs are [n_views,H,W,...] device arrays

@@ -230,6 +230,8 @@ struct sas_ctx : Settings {
     bool mesh_has_vcol = false;   // ... colours were given
     DevBuf mesh_feat;        // per-triangle feature rows (sas_scene_mesh_features): [chunks][nt][SAS_FEAT_K], feat_c channels
     DevBuf query_pts, query_tri, query_mesh, query_list, query_count;   // scratch of sas_query_meshes (SasQuery)
+    DevBuf match_src, match_tgt, match_keys, match_index, match_dist2, match_partial;   // scratch of sas_match_points (SasMatch)
+    int match_cus = 0;   // compute units of the device, asked once (the slice count of sas_match_points)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
     // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
     // the call returns: nothing is remembered across calls)
@@ -1672,6 +1674,76 @@ int sas_query_meshes(sas_ctx *c, int64_t n_points, const float *points, int64_t 
     return SAS_OK;
 }
 
+// The slice count of a sas_match_points call: `asked`, or (0) as many as bring the grid of k_match_slice to four workgroups per compute
+// unit; never more than the target has chunks (nor than a grid's y extent), at least one.
+static int match_slices(long long n_blocks, long long n_chunks, int asked, int cus)
+{
+    long long s = asked > 0 ? asked : (4ll * cus + n_blocks - 1) / std::max(1ll, n_blocks);
+    s = std::min(s, std::min(n_chunks, 65535ll));
+    return (int)std::max(1ll, s);
+}
+
+int sas_match_points(sas_ctx *c, int64_t n_source, const float *source, int64_t n_target, const float *target, const float *transform,
+                     float max_distance, int slices, int32_t *index, float *dist2, double *moments, void *stream)
+{
+    if (!c) return SAS_ERR_INVALID;
+    if (n_source < 0 || n_source > 0x7fffff00ll || n_target < 0 || n_target > 0x7fffff00ll)
+        return fail(c, SAS_ERR_INVALID, "bad match sizes: %lld source points, %lld target points", (long long)n_source, (long long)n_target);
+    if ((n_source > 0 && !source) || (n_target > 0 && !target)) return fail(c, SAS_ERR_INVALID, "source and target are required");
+    if (!(max_distance >= 0.0f)) return fail(c, SAS_ERR_INVALID, "max_distance must be >= 0 (INFINITY allowed), got %g", (double)max_distance);
+    if (slices < 0) return fail(c, SAS_ERR_INVALID, "slices must be >= 0 (0: the library's choice), got %d", slices);
+    if (!index && !dist2 && !moments) return fail(c, SAS_ERR_INVALID, "index, dist2 and moments are all NULL");
+    SasMatch m{};
+    for (int k = 0; k < 3; ++k) {
+        for (int j = 0; j < 3; ++j) m.A[3 * k + j] = transform ? transform[4 * k + j] : (k == j ? 1.0f : 0.0f);
+        m.t[k] = transform ? transform[4 * k + 3] : 0.0f;
+    }
+    for (int k = 0; transform && k < 12; ++k)
+        if (!std::isfinite(transform[k])) return fail(c, SAS_ERR_INVALID, "transform[%d] = %g is not finite", k, (double)transform[k]);
+    if (moments) std::fill(moments, moments + SAS_MATCH_MOMENTS, 0.0);
+    if (n_source == 0) return SAS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;
+    if (c->match_cus <= 0) {
+        HIP_TRY(c, hipDeviceGetAttribute(&c->match_cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        if (c->match_cus <= 0) c->match_cus = 1;
+    }
+    const size_t ns = (size_t)n_source, nt = (size_t)n_target;
+    m.n_source = n_source;
+    m.n_target = n_target;
+    m.n_blocks = (n_source + 255) / 256;
+    const long long n_chunks = (n_target + SAS_MATCH_CHUNK - 1) / SAS_MATCH_CHUNK;
+    m.slices = match_slices(m.n_blocks, n_chunks, slices, c->match_cus);
+    m.slice_targets = std::max(1ll, (n_chunks + m.slices - 1) / m.slices) * SAS_MATCH_CHUNK;
+    m.slices = (int)std::max(1ll, (n_target + m.slice_targets - 1) / m.slice_targets);   // (no slice is empty)
+    m.md2 = max_distance * max_distance;
+    int rc;
+    if ((rc = ensure(c, c->match_src, sizeof(float) * 3 * ns))) return rc;
+    if ((rc = ensure(c, c->match_tgt, sizeof(float) * 3 * std::max<size_t>(nt, 1)))) return rc;
+    if ((rc = ensure(c, c->match_keys, sizeof(unsigned long long) * ns * (size_t)m.slices))) return rc;
+    if ((rc = ensure(c, c->match_index, sizeof(int32_t) * ns))) return rc;
+    if ((rc = ensure(c, c->match_dist2, sizeof(float) * ns))) return rc;
+    if ((rc = ensure(c, c->match_partial, sizeof(double) * SAS_MATCH_MOMENTS * ((size_t)m.n_blocks + 1)))) return rc;
+    HIP_TRY(c, hipMemcpy(c->match_src.p, source, sizeof(float) * 3 * ns, hipMemcpyDefault));
+    if (nt) HIP_TRY(c, hipMemcpy(c->match_tgt.p, target, sizeof(float) * 3 * nt, hipMemcpyDefault));
+    m.source = (const float *)c->match_src.p;
+    m.target = (const float *)c->match_tgt.p;
+    m.keys = (unsigned long long *)c->match_keys.p;
+    m.index = index ? (int *)c->match_index.p : nullptr;
+    m.dist2 = dist2 ? (float *)c->match_dist2.p : nullptr;
+    m.partial = moments ? (double *)c->match_partial.p : nullptr;                                        // rows [0, n_blocks)
+    m.moments = moments ? (double *)c->match_partial.p + SAS_MATCH_MOMENTS * (size_t)m.n_blocks : nullptr;   // the row behind them
+    hipStream_t st = (hipStream_t)stream;
+    sas_launch_match(st, m);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "point matching: %s", hipGetErrorString(e));
+    if (index) HIP_TRY(c, hipMemcpy(index, c->match_index.p, sizeof(int32_t) * ns, hipMemcpyDefault));
+    if (dist2) HIP_TRY(c, hipMemcpy(dist2, c->match_dist2.p, sizeof(float) * ns, hipMemcpyDefault));
+    if (moments) HIP_TRY(c, hipMemcpy(moments, m.moments, sizeof(double) * SAS_MATCH_MOMENTS, hipMemcpyDeviceToHost));
+    return SAS_OK;
+}
+
 int sas_render_rgbd(sas_ctx *c, const float *viewmat, const float *K, int width, int height, const float *background,
                     unsigned flags, const float *max_depth, float *rgb, float *alpha, float *depth, float *points,
                     uint8_t *mask, void *stream)
@@ -1832,16 +1904,17 @@ extern "C" int sas_debug_bounds_kernels(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_tiles(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_mesh(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_query(unsigned long long *out, int reset);
+extern "C" int sas_debug_bounds_match(unsigned long long *out, int reset);
 /* Bounds-checked build only: out[0] = guarded accesses found out of range since the last reset (they were
  * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none). */
 int sas_debug_bounds(unsigned long long *out, int reset)
 {
-    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
+    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0};
     if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset) ||
-        sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset))
+        sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset) || sas_debug_bounds_match(p, reset))
         return SAS_ERR_HIP;
-    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : q));
-    out[0] = a[0] + b[0] + m[0] + q[0];
+    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : p)));
+    out[0] = a[0] + b[0] + m[0] + q[0] + p[0];
     out[1] = first[1]; out[2] = first[2]; out[3] = first[3];
     return SAS_OK;
 }

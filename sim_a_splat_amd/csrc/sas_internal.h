@@ -1,4 +1,4 @@
-// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -315,3 +315,24 @@ struct SasQuery {
 };
 // count <- 0, the box pass (culled pairs read +inf / 0), the evaluation of the candidates
 void sas_launch_query(hipStream_t st, const SasQuery &q);
+
+// Point matching (sas_match_points; DESIGN.md 3, "Point matching").  All three kernels take the whole call by value.
+#define SAS_MATCH_CHUNK 256     // targets k_match_slice stages in LDS at a time (4 KiB)
+#define SAS_MATCH_MOMENTS 18    // n, sum p' (3), sum q (3), sum q p'^T (9, row-major), sum |p'|^2, sum d2
+struct SasMatch {
+    const float *source;        // [n_source,3]
+    const float *target;        // [n_target,3]
+    unsigned long long *keys;   // [slices][n_source] slice minima: bits(d2) << 32 | target index (d2 = +inf: none)
+    int *index;                 // [n_source] device or nullptr
+    float *dist2;               // [n_source] device or nullptr
+    double *partial;            // [n_blocks][SAS_MATCH_MOMENTS] one row per workgroup of k_match_merge, or nullptr: no moments wanted
+    double *moments;            // [SAS_MATCH_MOMENTS] device (with partial)
+    long long n_source, n_target;
+    long long n_blocks;         // ceil(n_source / 256)
+    long long slice_targets;    // targets per slice, a multiple of SAS_MATCH_CHUNK
+    int slices;                 // slices * slice_targets >= n_target
+    float A[9], t[3];           // p' = A p + t
+    float md2;                  // max_distance^2 in float32 (INFINITY: every match holds)
+};
+// keys <- slice minima, index / dist2 / partial <- the merge, moments <- the partial rows in workgroup order
+void sas_launch_match(hipStream_t st, const SasMatch &m);

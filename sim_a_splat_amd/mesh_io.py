@@ -114,3 +114,33 @@ def vertex_normals(vertices, faces) -> np.ndarray:
     n = np.linalg.norm(out, axis=1)
     good = np.isfinite(n) & (n > 0)
     return np.where(good[:, None], out / np.where(good, n, 1.0)[:, None], 0.0)
+
+
+def sample_surface(vertices, faces, n: int, seed: int = 0) -> np.ndarray:
+    """``n`` points on the surface, ``[n,3]`` float64, area-weighted and stratified: point k takes the triangle that the cumulative
+    triangle areas assign to ``u_k = (k + r_k) / n``, and a place in it by the square-root rule (``s = sqrt(r1)``:
+    ``(1 - s) A + s (1 - r2) B + s r2 C``, uniform over the triangle).  ``r_k, r1, r2`` come from ``numpy.random.default_rng(seed)``:
+    the same arguments give the same bits.  Triangles of zero or non-finite area carry no weight and receive no point; a triangle
+    of area share ``a`` receives between ``n a - 2`` and ``n a + 2`` points.  ValueError when no triangle has an area.
+
+    The reference samples its robot with open3d's ``sample_points_poisson_disk`` (match_splat.py:103), which draws more points than
+    asked and eliminates the closest ones; that elimination is not reproduced here -- stratification spreads the points evenly over
+    the area, not by mutual distance."""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"n must be >= 0, got {n}")
+    tri = v[f]                                               # [F,3,3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        area = 0.5 * np.linalg.norm(np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]), axis=1) if len(f) else np.zeros(0)
+    area = np.where(np.isfinite(area) & np.isfinite(tri).all(axis=(1, 2)), area, 0.0)
+    cum = np.cumsum(area)
+    if len(cum) == 0 or not cum[-1] > 0.0 or not np.isfinite(cum[-1]):
+        raise ValueError("sample_surface: the mesh has no triangle with a finite, positive area")
+    r = np.random.default_rng(seed).random((n, 3))
+    u = (np.arange(n) + r[:, 0]) / max(n, 1)
+    t = np.minimum(np.searchsorted(cum, u * cum[-1], side="right"), int(np.flatnonzero(area > 0.0)[-1]))
+    s = np.sqrt(r[:, 1])
+    A, B, C = tri[t, 0], tri[t, 1], tri[t, 2]
+    return (1.0 - s)[:, None] * A + (s * (1.0 - r[:, 2]))[:, None] * B + (s * r[:, 2])[:, None] * C

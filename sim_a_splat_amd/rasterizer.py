@@ -43,6 +43,8 @@ def cov3x3_to_cov6(cov: ArrayLike) -> ArrayLike:
 MAX_FEATURES = 256   # channels of a feature store (sas_scene_features)
 MESH_QUERY_CHUNK = _capi.SAS_QUERY_CHUNK   # triangles query_meshes' kernel stages at a time: mesh sizes around it take its chunk edges
 MAX_QUERY_MESHES = 256
+MATCH_CHUNK = _capi.SAS_MATCH_CHUNK   # targets match_points' kernel stages at a time: target sizes around it take its chunk edges
+MATCH_MOMENTS = 18
 
 
 def pack_query_meshes(meshes) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -364,6 +366,35 @@ class Rasterizer:
                                              offsets.ctypes.data, float(max_distance), res["distance"].data_ptr(), res["winding"].data_ptr(),
                                              self._stream()), "sas_query_meshes")
         return res
+
+    @_locked
+    def match_points(self, source: ArrayLike, target: ArrayLike, transform=None, max_distance: float = float("inf"),
+                     slices: Optional[int] = None) -> Dict[str, object]:
+        """For every point of ``source [S,3]`` moved by ``transform`` (4x4 or 3x4, rounded to float32; None: the identity) the
+        nearest point of ``target [T,3]`` within ``max_distance`` (sas_match_points; DESIGN.md 3, "Point matching").  Returns
+        ``index`` (int32 ``[S]``, -1 without a match) and ``dist2`` (float32 ``[S]``, +inf without one) as device tensors, and
+        ``moments``, a float64 ndarray of 18 over the held matches: n, sum p' (3), sum q (3), sum q p'^T (9), sum |p'|^2, sum d2.
+        Ties go to the lowest target index.  Torch device tensors are read where they are: an ICP loop keeps both clouds on the
+        device.  ``slices``: None is the library's choice; no result depends on it.  Needs no scene."""
+        ns, nt = int(source.shape[0]), int(target.shape[0])
+        s, sp = _as_f32(source, (ns, 3), "source")
+        t, tp = _as_f32(target, (nt, 3), "target")
+        for a in (s, t):
+            if isinstance(a, torch.Tensor) and a.is_cuda:
+                torch.cuda.synchronize(a.device)   # device-resident inputs must be complete before the copy
+        A = None
+        if transform is not None:
+            A = np.asarray(transform.detach().cpu().numpy() if isinstance(transform, torch.Tensor) else transform, dtype=np.float64)
+            if A.shape not in ((4, 4), (3, 4)):
+                raise ValueError(f"transform must be 4x4 or 3x4, got {list(A.shape)}")
+            A = np.ascontiguousarray(A[:3].astype(np.float32)).reshape(12)
+        index = torch.full((ns,), -1, dtype=torch.int32, device=self.device)
+        dist2 = torch.full((ns,), float("inf"), dtype=torch.float32, device=self.device)
+        moments = np.zeros(MATCH_MOMENTS, np.float64)
+        self._check(self._L.sas_match_points(self._ctx, ns, sp, nt, tp, A.ctypes.data if A is not None else None, float(max_distance),
+                                             0 if slices is None else int(slices), index.data_ptr() if ns else None,
+                                             dist2.data_ptr() if ns else None, moments.ctypes.data, self._stream()), "sas_match_points")
+        return {"index": index, "dist2": dist2, "moments": moments}
 
     @_locked
     def set_group_poses(self, Rt: ArrayLike) -> None:

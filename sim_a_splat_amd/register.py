@@ -1,0 +1,242 @@
+"""Register the robot to the splat: the ICP step of the reference (match_splat.py:94-223) without open3d.
+
+The reference samples 20 000 points from the posed URDF meshes, crops the Gaussian centres to a polygon volume, guesses a transform
+from the two centroids and runs open3d's ``registration_icp`` with ``TransformationEstimationPointToPoint(with_scaling=True)`` and a
+correspondence distance of 0.2.  Here the sampling is ``mesh_io.sample_surface``, the crop ``segment.polygon_volume_mask``, the
+nearest-neighbour search of every iteration ``Rasterizer.match_points`` (a HIP kernel; DESIGN.md 3, "Point matching") and the
+similarity fit ``umeyama`` on the 18 moments that call returns.  Everything but the matcher is NumPy float64.
+
+    python -m sim_a_splat_amd.register --splat SCENE --urdf ROBOT.urdf --joint-config joint_config.npy \\
+        --robot-description-dir DIR --package-name NAME --polygon polygon_bounds.npy --axis-min -0.3 --axis-max 0.1 \\
+        [--rotation-xyz 0,0,0 --scale 1 --offset 0,0,0 --threshold 0.2 --points 20000 --seed 0] --out MASKS_DIR [--masks]
+
+writes ``icp_transformation.npy``, ``trans_init.npy``, ``polygon_bounds.npy`` and ``joint_config.npy``; with ``--masks`` it goes on
+through ``segment.segment_robot`` and writes ``link_masks_global_dict.npz`` too: the whole directory ``SplatHandler`` reads.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from pathlib import Path
+from typing import Callable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+N_MOMENTS = 18   # n, sum p' (3), sum q (3), sum q p'^T (9, row-major), sum |p'|^2, sum d2 (sas_match_points)
+
+
+@dataclass
+class RegistrationResult:
+    transformation: np.ndarray          # 4x4 float64, source -> target
+    fitness: float                      # held matches / source points
+    inlier_rmse: float                  # sqrt(sum d2 / held matches)
+    iterations: int                     # updates applied
+    history: List[Tuple[float, float]] = field(default_factory=list)   # (fitness, inlier_rmse) of every evaluation, the first included
+
+
+def umeyama(moments, with_scaling: bool = True) -> np.ndarray:
+    """The least-squares similarity ``q ~ c R p' + t`` of the held matches, 4x4 float64, from the moments of ``match_points``: the
+    closed form of Umeyama (1991) as Eigen's ``umeyama`` evaluates it, which open3d's point-to-point estimation calls.  Centred
+    cross-covariance ``Sigma = sum q p'^T / n - mu_q mu_p^T = U D V^T``; ``S = diag(1, 1, -1)`` when ``det U det V < 0`` (a reflection
+    would fit better: the proper rotation is taken); ``R = U S V^T``, ``c = tr(D S) / sigma_p^2`` (1 without scaling),
+    ``t = mu_q - c R mu_p``.  ValueError below 3 matches or when the matched source points coincide (``sigma_p^2 = 0``)."""
+    m = np.asarray(moments, np.float64).reshape(-1)
+    if m.shape[0] != N_MOMENTS:
+        raise ValueError(f"moments must hold {N_MOMENTS} values, got {m.shape[0]}")
+    n = m[0]
+    if not n >= 3:
+        raise ValueError(f"umeyama needs at least 3 matches, got {n:g}")
+    mu_p, mu_q = m[1:4] / n, m[4:7] / n
+    sigma = m[7:16].reshape(3, 3) / n - np.outer(mu_q, mu_p)
+    var_p = m[16] / n - float(mu_p @ mu_p)
+    if not var_p > 0.0 or not np.isfinite(sigma).all():
+        raise ValueError("umeyama: the matched source points are degenerate (zero variance)")
+    U, D, Vt = np.linalg.svd(sigma)
+    S = np.ones(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2] = -1.0
+    R = (U * S) @ Vt
+    c = float((D * S).sum() / var_p) if with_scaling else 1.0
+    T = np.eye(4)
+    T[:3, :3] = c * R
+    T[:3, 3] = mu_q - c * (R @ mu_p)
+    return T
+
+
+def rotation_from_xyz(rotation_xyz) -> np.ndarray:
+    """``Rx(a) Ry(b) Rz(c)``: open3d's ``get_rotation_matrix_from_xyz``."""
+    a, b, c = (float(x) for x in rotation_xyz)
+    ca, sa, cb, sb, cc, sc = np.cos(a), np.sin(a), np.cos(b), np.sin(b), np.cos(c), np.sin(c)
+    Rx = np.array([[1, 0, 0], [0, ca, -sa], [0, sa, ca]], np.float64)
+    Ry = np.array([[cb, 0, sb], [0, 1, 0], [-sb, 0, cb]], np.float64)
+    Rz = np.array([[cc, -sc, 0], [sc, cc, 0], [0, 0, 1]], np.float64)
+    return Rx @ Ry @ Rz
+
+
+def _host(a) -> np.ndarray:
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def initial_guess(source, target, rotation_xyz=(0.0, 0.0, 0.0), scale: float = 1.0, offset=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """The reference's first guess (match_splat.py:178-196), 4x4: ``scale * R(rotation_xyz) | centre(target) - centre(source) +
+    offset``.  As there, the UNROTATED, unscaled source centre is subtracted: with a rotation or a scale the guess does not bring the
+    centres together, and ``offset`` is how the reference's user makes up for it."""
+    T = np.eye(4)
+    T[:3, :3] = float(scale) * rotation_from_xyz(rotation_xyz)
+    T[:3, 3] = (np.asarray(_host(target), np.float64).reshape(-1, 3).mean(axis=0) - np.asarray(_host(source), np.float64).reshape(-1, 3).mean(axis=0)
+                + np.asarray(offset, np.float64).reshape(3))
+    return T
+
+
+def register_similarity(source, target, init=None, max_correspondence_distance: float = 0.2, max_iteration: int = 30,
+                        relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, with_scaling: bool = True, rasterizer=None,
+                        matcher: Optional[Callable] = None) -> RegistrationResult:
+    """Point-to-point ICP with a similarity (or, ``with_scaling=False``, rigid) update: ``source [S,3]`` onto ``target [T,3]`` from the
+    4x4 ``init``.  The loop is that of open3d's ``registration_icp`` as its public documentation and source describe it: evaluate
+    (match every moved source point to its nearest target within ``max_correspondence_distance``; ``fitness = n / S``,
+    ``inlier_rmse = sqrt(sum d2 / n)``); then per iteration ``T <- umeyama(matches) . T`` and evaluate again; stop when the absolute
+    changes of fitness and of inlier_rmse are both below their limits, or after ``max_iteration`` updates.
+
+    One deviation from open3d: it moves its source cloud by every update and so accumulates float64 roundings in the points; here
+    each iteration rounds the accumulated ``T`` to float32 once and the matcher applies it to the ORIGINAL source -- nothing is
+    re-transformed, and both clouds stay where they are (on the device, with a ``Rasterizer``) for the whole loop.
+
+    ``matcher``: any callable with ``Rasterizer.match_points``' signature and result (the seam for CPU tests); None uses
+    ``rasterizer.match_points``, and without a rasterizer either one is made on device 0 for the call.  ValueError when fewer than 3
+    points match (``umeyama``)."""
+    T = np.eye(4) if init is None else np.array(np.asarray(_host(init), np.float64).reshape(4, 4))
+    own = None
+    if matcher is None:
+        import torch
+        if rasterizer is None:
+            from .rasterizer import Rasterizer
+            rasterizer = own = Rasterizer(0)
+        dev = lambda a: (a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float32))
+                         ).to(device=rasterizer.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+        source, target = dev(source), dev(target)     # uploaded once
+        matcher = rasterizer.match_points
+    else:
+        source = np.ascontiguousarray(np.asarray(_host(source), np.float32).reshape(-1, 3))
+        target = np.ascontiguousarray(np.asarray(_host(target), np.float32).reshape(-1, 3))
+    n_source = int(source.shape[0])
+
+    def evaluate(T):
+        m = np.asarray(matcher(source, target, transform=T, max_distance=float(max_correspondence_distance))["moments"], np.float64)
+        n = float(m[0])
+        return m, (n / n_source if n_source else 0.0), (float(np.sqrt(m[17] / n)) if n > 0 else 0.0)
+
+    try:
+        m, fitness, rmse = evaluate(T)
+        history = [(fitness, rmse)]
+        iterations = 0
+        for _ in range(int(max_iteration)):
+            T = umeyama(m, with_scaling) @ T
+            iterations += 1
+            before = (fitness, rmse)
+            m, fitness, rmse = evaluate(T)
+            history.append((fitness, rmse))
+            if abs(before[0] - fitness) < relative_fitness and abs(before[1] - rmse) < relative_rmse:
+                break
+    finally:
+        if own is not None:
+            own.close()
+    return RegistrationResult(T, fitness, rmse, iterations, history)
+
+
+def robot_surface_points(urdf, joint_config, robot_description_dir: str, package_name: str, n_links: int = 7, n_points: int = 20000,
+                         seed: int = 0) -> np.ndarray:
+    """``n_points`` points ``[n,3]`` float64 on the robot's first ``n_links`` visual meshes posed at ``joint_config``, combined into
+    one surface as the reference does (match_splat.py:64-105): ``segment.robot_link_meshes`` with an identity ICP, then
+    ``mesh_io.sample_surface`` (whose note on open3d's Poisson-disk sampler applies)."""
+    from . import mesh_io, segment
+    meshes, transforms = segment.robot_link_meshes(urdf, joint_config, np.eye(4), robot_description_dir, package_name, n_links)
+    vs, fs, base = [], [], 0
+    for (v, f), T in zip(meshes, transforms):
+        vs.append(segment.transform_vertices(v, T))
+        fs.append(np.asarray(f, np.int64).reshape(-1, 3) + base)
+        base += len(v)
+    return mesh_io.sample_surface(np.concatenate(vs), np.concatenate(fs), n_points, seed)
+
+
+def register_robot(means, urdf, joint_config, robot_description_dir: str, package_name: str, *, polygon=None, axis_min: float = -np.inf,
+                   axis_max: float = np.inf, axis: str = "Z", rotation_xyz=(0.0, 0.0, 0.0), scale: float = 1.0, offset=(0.0, 0.0, 0.0),
+                   threshold: float = 0.2, n_links: int = 7, n_points: int = 20000, seed: int = 0, max_iteration: int = 30,
+                   rasterizer=None, matcher=None) -> Tuple[RegistrationResult, np.ndarray]:
+    """Steps 1-4 of the reference's match_splat.py for a splat's centres ``means [N,3]``: crop them to the polygon volume (None: no
+    crop), sample the posed robot, guess from the two centres, register.  Returns ``(result, trans_init)``;
+    ``result.transformation`` is what ``icp_transformation.npy`` holds."""
+    from . import segment
+    pts = np.asarray(_host(means), np.float32).reshape(-1, 3)
+    if polygon is not None:
+        pts = pts[segment.polygon_volume_mask(pts, polygon, axis_min, axis_max, axis)]
+    if len(pts) < 3:
+        raise ValueError(f"{len(pts)} Gaussian centres in the crop volume: nothing to register to")
+    robot = robot_surface_points(urdf, joint_config, robot_description_dir, package_name, n_links, n_points, seed)
+    trans_init = initial_guess(robot, pts, rotation_xyz, scale, offset)
+    result = register_similarity(robot, pts, trans_init, max_correspondence_distance=threshold, max_iteration=max_iteration,
+                                 rasterizer=rasterizer, matcher=matcher)
+    return result, trans_init
+
+
+def main(argv: Optional[Sequence[str]] = None, matcher=None) -> int:
+    import argparse
+    from . import io, poses, segment
+    vec3 = lambda s: [float(x) for x in s.split(",")]
+    ap = argparse.ArgumentParser(prog="python -m sim_a_splat_amd.register", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--splat", required=True, help="scene: .npy of centres, .npz / .json scene, splatfacto config.yml, run directory or .ckpt")
+    ap.add_argument("--urdf", required=True)
+    ap.add_argument("--joint-config", required=True, help=".npy, or comma-separated joint positions")
+    ap.add_argument("--robot-description-dir", required=True, help="what package://NAME in the URDF's mesh filenames stands for")
+    ap.add_argument("--package-name", required=True)
+    ap.add_argument("--polygon", required=True, help="polygon_bounds.npy of the crop volume")
+    ap.add_argument("--axis-min", type=float, required=True)
+    ap.add_argument("--axis-max", type=float, required=True)
+    ap.add_argument("--axis", default="Z")
+    ap.add_argument("--rotation-xyz", type=vec3, default=[0.0, 0.0, 0.0], help="initial rotation, radians about x, y, z (comma-separated)")
+    ap.add_argument("--scale", type=float, default=1.0, help="initial scale")
+    ap.add_argument("--offset", type=vec3, default=[0.0, 0.0, 0.0], help="added to the initial translation (comma-separated)")
+    ap.add_argument("--threshold", type=float, default=0.2, help="largest correspondence distance")
+    ap.add_argument("--points", type=int, default=20000, help="points sampled from the robot's meshes")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--links", type=int, default=7)
+    ap.add_argument("--distance", type=float, default=0.015, help="--masks: the mask rule's distance")
+    ap.add_argument("--out", required=True, help="masks directory to write")
+    ap.add_argument("--masks", action="store_true", help="go on through segment.segment_robot and write the link masks too")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    means = segment.load_means(a.splat)
+    jc = io.load_joint_config(a.joint_config) if Path(a.joint_config).exists() else np.array([float(x) for x in a.joint_config.split(",")])
+    polygon = np.load(a.polygon, allow_pickle=False)
+    r = None
+    if matcher is None or a.masks:
+        from .rasterizer import Rasterizer
+        r = Rasterizer(a.device)
+    try:
+        result, trans_init = register_robot(means, a.urdf, jc, a.robot_description_dir, a.package_name, polygon=polygon, axis_min=a.axis_min,
+                                            axis_max=a.axis_max, axis=a.axis, rotation_xyz=a.rotation_xyz, scale=a.scale, offset=a.offset,
+                                            threshold=a.threshold, n_links=a.links, n_points=a.points, seed=a.seed, rasterizer=r,
+                                            matcher=matcher)
+        icp = result.transformation
+        s, _, _ = poses.decompose_icp(icp)      # what SplatHandler will ask of the file: raises before anything is written
+        d = Path(a.out)
+        d.mkdir(parents=True, exist_ok=True)
+        if a.masks:
+            crop = segment.polygon_volume_mask(means, polygon, a.axis_min, a.axis_max, a.axis)
+            masks = segment.segment_robot(means, a.urdf, jc, icp, a.robot_description_dir, a.package_name, a.links, distance=a.distance,
+                                          crop=crop, rasterizer=r)
+            segment.write_masks_dir(d, masks, jc, icp)
+            for k, m in masks.items():
+                print(f"{k}: {int(m.sum())} of {len(m)} Gaussians")
+    finally:
+        if r is not None:
+            r.close()
+    np.save(d / "icp_transformation.npy", icp)
+    np.save(d / "trans_init.npy", trans_init)
+    np.save(d / "polygon_bounds.npy", np.asarray(polygon, np.float64))
+    np.save(d / "joint_config.npy", np.asarray(jc, np.float64).reshape(-1))
+    print(f"fitness {result.fitness:.4f}, inlier rmse {result.inlier_rmse:.6f}, {result.iterations} iterations, scale {s:.6f}")
+    print(f"-> {d}")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

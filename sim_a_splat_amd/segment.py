@@ -4,7 +4,8 @@ The reference poses the URDF visuals at the mask-time joint configuration, moves
 centres to a polygon volume and asks of every cropped centre and every link mesh "inside, or within 0.015 of it?"
 (``RaycastingScene.compute_occupancy / compute_distance``, :240-251).  Here the question is ``Rasterizer.query_meshes`` (a HIP
 kernel; DESIGN.md 3, "Mesh queries"), the crop is ``polygon_volume_mask`` and the result is a mask over ALL Gaussians in the
-caller's order -- what ``io.save_link_masks`` writes and ``SplatHandler`` reads.  The ICP registration itself is an input.
+caller's order -- what ``io.save_link_masks`` writes and ``SplatHandler`` reads.  The ICP registration itself is an input
+(``sim_a_splat_amd.register`` makes it).
 
     python -m sim_a_splat_amd.segment --splat SCENE --urdf ROBOT.urdf --joint-config joint_config.npy \\
         --icp icp_transformation.npy --robot-description-dir DIR --package-name NAME --out MASKS_DIR \\
