@@ -353,6 +353,35 @@ int sas_render_batch_host_posed(sas_ctx *ctx, int n_views, const float *viewmats
                                 int n_sets, const float *Rt, int width, int height, const float *background,
                                 unsigned flags, uint8_t *rgb8_host, void *stream);
 
+/*
+ * Label frames: sas_render_batch[_posed] plus, for every view, which pose group (robot link, mesh) each pixel shows, as one byte
+ * per pixel.  Serves the per-link segmentation a policy observes beside rgb and depth (splat_handler.py:62-83 makes the link
+ * groups; splat_env_wrapper.py:147-158 is the per-camera loop the observation comes from).  The contract, for every view v and
+ * pixel p:
+ *     labels[v,p] = L(w_v[p,:], a_v[p])
+ * where w_v [G] and a_v are bit for bit the features and alpha sas_render_features delivers for that view under that view's poses
+ * with the one-hot stores -- sas_scene_features(NULL) and, when the context holds meshes, sas_scene_mesh_features(NULL) -- a zero
+ * feature background and the call's flags (SAS_MESH_SURFACE included), and L is the smallest g with w_g == max_k w_k, clamped to
+ * 255, and 255 where a < min_alpha (a float32 compare).  G is the store's channel count (the scene's n_groups, 1..256); with 256
+ * groups, group 255 reads as "none".  No [H,W,G] array is written anywhere.
+ *   labels     [n_views,H,W] uint8 DEVICE, required
+ *   min_alpha  0 never labels a pixel 255 by the alpha rule
+ *   rgb / alpha / depth / rgb8: optional, as sas_render_batch[_posed], and bit-identical to it with the same flags
+ *   flags      SAS_MESH_SURFACE, SAS_DEPTH_FILL_MAX, SAS_FAST_EXP, SAS_TIMING; blocking only (SAS_ASYNC is rejected); any other
+ *              flag is SAS_ERR_INVALID.  n_views == 1 is the single-view call.
+ * The call selects no store itself: SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID without a feature store, with a store of
+ * the caller's own features, with meshes that lack their one-hot rows, or without `labels` (sas_last_error says which).
+ * Label frames are SAS_FULL_SORT frames: the views go through the frame slots one at a time, each with a snapshot of its own
+ * pose set; nothing drains between views and the context's current poses are not changed.
+ */
+int sas_render_batch_labels(sas_ctx *ctx, int n_views, const float *viewmats, const float *Ks, int width, int height,
+                            const float *background, float min_alpha, unsigned flags, float *rgb, float *alpha, float *depth,
+                            uint8_t *rgb8, uint8_t *labels, void *stream);
+int sas_render_batch_labels_posed(sas_ctx *ctx, int n_views, const float *viewmats, const float *Ks, const int *pose_set,
+                                  int n_sets, const float *Rt, int width, int height, const float *background, float min_alpha,
+                                  unsigned flags, float *rgb, float *alpha, float *depth, uint8_t *rgb8, uint8_t *labels,
+                                  void *stream);
+
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical
  * field of view; the view matrices and intrinsics are those of sas_camera_matrices. */

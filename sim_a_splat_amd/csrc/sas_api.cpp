@@ -55,6 +55,7 @@ struct ViewOut {
     uint8_t *mask = nullptr;
     uint8_t *rgb8_host = nullptr;   // sas_render_batch_host: host copy of rgb8, made on the frame's stream
     float *features = nullptr;      // sas_render_features: [H,W,feat_c] (device), composited behind the frame's k_blend
+    uint8_t *labels = nullptr;      // sas_render_batch_labels: [H,W] (device), the argmax of the one-hot stores' channels
 };
 
 struct RenderArgs {
@@ -70,6 +71,7 @@ struct RenderArgs {
     bool solo = false;         // a blocking call for this one view with nothing else in flight: the caller waits for the frame's chain
     int feat_c = 0;            // channels of out.features
     float fbg[SAS_MAX_FEATURES];   // feature background, [feat_c]
+    float min_alpha = 0.0f;        // of out.labels
 };
 
 }  // namespace
@@ -224,6 +226,7 @@ struct sas_ctx : Settings {
     DevBuf g0, g1, g2, col, gid8, perm;
     DevBuf feat;         // feature store (sas_scene_features): [chunks][n_pad][SAS_FEAT_K], slot order
     int feat_c = 0;      // its channels
+    bool feat_onehot = false, mesh_feat_onehot = false;   // the store / the triangles' rows are the one-hot of the groups (label frames)
     DevBuf mesh_vert, mesh_tri, mesh_col;   // meshes (sas_scene_meshes): float4 vertices, int4 (i0, i1, i2, group), float4 colours
     SasMeshScene mesh{};
     DevBuf mesh_nrm, mesh_vcol;   // vertex attributes (sas_scene_mesh_vertex_attributes): float4 normals, float4 colours, [mesh.nv] each
@@ -688,6 +691,19 @@ SasFeatures features_of(const sas_ctx *c, const RenderArgs &a)
     return F;
 }
 
+SasLabels labels_of(const sas_ctx *c, const RenderArgs &a)
+{
+    SasLabels B{};
+    B.store = (const float *)c->feat.p;
+    B.n_pad = c->scene.n_pad;
+    B.C = c->feat_c;
+    B.chunks = sas_feature_chunks(c->feat_c);
+    B.out = a.out.labels;
+    B.min_alpha = a.min_alpha;
+    B.surface = (a.flags & SAS_MESH_SURFACE) != 0;
+    return B;
+}
+
 // Frames wanted on the host (sas_render_batch_host) and not delivered by the tile kernel: one copy kernel for the
 // chain's views when the destination is pinned (no copy-engine hop), else a runtime copy per view.
 int deliver_to_host(sas_ctx *c, Slot *const *sl, int nv, hipStream_t st)
@@ -755,7 +771,8 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
     if (order) HIP_TRY(c, hipEventRecord(ld.start, a.stream));
     if (timing) HIP_TRY(c, hipStreamWaitEvent(st, ld.start, 0));
 
-    if (ld.mesh && (rc = prepare_mesh(c, ld.msc, tiles, a.out.features ? (size_t)a.W * (size_t)a.H : 0))) return rc;
+    const bool per_pixel_win = a.out.features || a.out.labels;   // the feature / label kernels take every pixel's triangle from the blend
+    if (ld.mesh && (rc = prepare_mesh(c, ld.msc, tiles, per_pixel_win ? (size_t)a.W * (size_t)a.H : 0))) return rc;
     if (leader) {
         HIP_TRY(c, hipStreamWaitEvent(st, leader->pair_ev, 0));   // projected by the leader's pass
     } else {
@@ -789,16 +806,21 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
         const SasMeshFrame mesh = mesh_frame_of(c, ld.msc, tiles);
         float4 *planes = has(c, HAVE_MESH_ATTR) ? (float4 *)ld.msc.planes.p : nullptr;
         sas_launch_mesh_bin(st, mesh_scene_of(c), P, f, mesh, planes);
-        const SasMeshExtra extra{a.out.features ? (unsigned long long *)ld.msc.win.p : nullptr, (a.flags & SAS_MESH_SURFACE) != 0};
+        const SasMeshExtra extra{per_pixel_win ? (unsigned long long *)ld.msc.win.p : nullptr, (a.flags & SAS_MESH_SURFACE) != 0};
         sas_launch_blend_mesh(st, c->scene, tiles, P, f, mesh, extra, planes, fast_exp, any_fill);
         if (a.out.features) {   // ... in front of the triangles the blend kernel has just resolved (extra.win)
             const SasMeshFeatures MF{extra.win, (const float *)c->mesh_feat.p, c->mesh.nt};
             sas_launch_blend_features(st, c->scene, tiles, P, f, features_of(c, a), fast_exp, &MF);
         }
+        if (a.out.labels) {
+            const SasMeshFeatures MF{extra.win, (const float *)c->mesh_feat.p, c->mesh.nt};
+            sas_launch_blend_labels(st, c->scene, tiles, P, f, labels_of(c, a), fast_exp, &MF);
+        }
     } else if (full) {
         sas_launch_blend(st, c->scene, tiles, P, f, fast_exp, any_fill);
         // a feature frame (sas_render_features): the same lists and records once more, per chunk of channels
         if (a.out.features) sas_launch_blend_features(st, c->scene, tiles, P, f, features_of(c, a), fast_exp, nullptr);
+        if (a.out.labels) sas_launch_blend_labels(st, c->scene, tiles, P, f, labels_of(c, a), fast_exp, nullptr);   // a label frame: likewise
     } else if (nv > 1) {
         // (quad: by the size of one view (prepare_frame): groups of four 300-tile views still gain (vec_env_probe))
         sas_launch_tiles_lazy_multi(st, c->scene, tiles, mf, fast_exp, any_fill, ld.quad, tile_ev[0], tile_ev[1]);
@@ -1340,6 +1362,7 @@ struct ViewCall {
     const float *poses = nullptr;   // [n_groups,12] group poses of THIS view (a pose set), or nullptr: the context's current poses
     const float *fbg = nullptr;     // sas_render_features: feature background [feat_c] of out.features (nullptr: 0)
     int feat_c = 0;
+    float min_alpha = 0.0f;         // sas_render_batch_labels: of out.labels
 };
 
 static int check_view(sas_ctx *c, const ViewCall &v, int width, int height)
@@ -1359,7 +1382,7 @@ static void fill_args(RenderArgs &a, const ViewCall &v, int width, int height, c
     const ViewOut &o = v.out;
     a.solo = solo;
     // rgb8 beside rgb8_host is the context's own staging frame (sas_render_batch_host): nothing of the caller's on the device
-    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || (o.rgb8 && !o.rgb8_host);
+    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || o.labels || (o.rgb8 && !o.rgb8_host);
     memcpy(a.viewmat, v.viewmat, sizeof(a.viewmat));
     memcpy(a.K, v.K, sizeof(a.K));
     for (int k = 0; k < 3; ++k) a.bg[k] = background ? background[k] : 0.0f;
@@ -1367,6 +1390,7 @@ static void fill_args(RenderArgs &a, const ViewCall &v, int width, int height, c
     a.out = o;
     a.feat_c = o.features ? v.feat_c : 0;
     for (int k = 0; k < a.feat_c; ++k) a.fbg[k] = v.fbg ? v.fbg[k] : 0.0f;
+    a.min_alpha = v.min_alpha;
     a.use_max_depth = max_depth != nullptr;
     a.max_depth = max_depth ? *max_depth : 0.0f;
     a.stream = st;
@@ -1438,6 +1462,7 @@ int sas_scene_features(sas_ctx *c, int64_t n, int channels, const float *feature
                                       });
     if (rc) return rc;
     c->feat_c = channels;
+    c->feat_onehot = features == nullptr;
     c->have |= HAVE_FEAT;
     return SAS_OK;
 }
@@ -1484,6 +1509,7 @@ int sas_scene_mesh_features(sas_ctx *c, int64_t n_triangles, int channels, const
                                           sas_launch_mesh_feature_store(st, n_triangles, c->mesh.tri, src, channels, store);
                                       });
     if (rc) return rc;
+    c->mesh_feat_onehot = features == nullptr;
     c->have |= HAVE_MESH_FEAT;
     return SAS_OK;
 }
@@ -1752,6 +1778,12 @@ int sas_render_rgbd(sas_ctx *c, const float *viewmat, const float *K, int width,
     return render_views(c, &v, 1, width, height, background, flags, max_depth, stream, false, !(flags & SAS_ASYNC));
 }
 
+// label frames of a batch (sas_render_batch_labels): every view also delivers labels [H,W]
+struct LabelOut {
+    uint8_t *labels = nullptr;   // [n_views,H,W] device
+    float min_alpha = 0.0f;
+};
+
 // pose sets of a batch: view v is rendered with rows pose_sets[pose_set[v]] (each set [n_groups,12]); no sets: the
 // context's current poses for every view
 struct PoseSets {
@@ -1762,10 +1794,11 @@ struct PoseSets {
 
 static int render_batch_impl(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height,
                              const float *background, unsigned flags, float *rgb, float *alpha, float *depth, uint8_t *rgb8,
-                             uint8_t *rgb8_host, void *stream, const PoseSets &ps = PoseSets())
+                             uint8_t *rgb8_host, void *stream, const PoseSets &ps = PoseSets(), const LabelOut &lab = LabelOut())
 {
     if (!c) return SAS_ERR_INVALID;
     flags = frame_flags(c, flags);
+    if (lab.labels) flags |= SAS_FULL_SORT;   // the labels are composited from the complete tile lists, one view per frame
     if (n_views < 0 || (n_views > 0 && (!viewmats || !Ks))) return fail(c, SAS_ERR_INVALID, "bad view batch");
     if (ps.Rt) {
         if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "no scene uploaded");
@@ -1781,6 +1814,8 @@ static int render_batch_impl(sas_ctx *c, int n_views, const float *viewmats, con
                     depth ? depth + px * v : nullptr, rgb8 ? rgb8 + 3 * px * v : nullptr}};
         vc.out.rgb8_host = rgb8_host ? rgb8_host + 3 * px * v : nullptr;
         vc.poses = ps.Rt ? ps.Rt + (size_t)12 * c->scene.n_groups * ps.pose_set[v] : nullptr;
+        vc.out.labels = lab.labels ? lab.labels + px * v : nullptr;
+        vc.min_alpha = lab.min_alpha;
         return vc;
     };
     // Views go through the frame slots two at a time: one pass over the scene projects both
@@ -1827,6 +1862,43 @@ int sas_render_batch_posed(sas_ctx *c, int n_views, const float *viewmats, const
     const PoseSets ps = {pose_set, n_sets, Rt};
     if (!Rt) return fail(c, SAS_ERR_INVALID, "sas_render_batch_posed: Rt is required");
     return render_batch_impl(c, n_views, viewmats, Ks, width, height, background, flags, rgb, alpha, depth, rgb8, nullptr, stream, ps);
+}
+
+// What a label frame needs in place, and the flags it takes: the call selects no store behind the caller's back.
+static int check_labels(sas_ctx *c, const char *who, unsigned flags, const uint8_t *labels)
+{
+    if (!c) return SAS_ERR_INVALID;
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (!labels) return fail(c, SAS_ERR_INVALID, "%s: the labels output is required", who);
+    if (flags & SAS_ASYNC) return fail(c, SAS_ERR_INVALID, "%s: blocking only (SAS_ASYNC is not supported)", who);
+    if (flags & ~(SAS_MESH_SURFACE | SAS_DEPTH_FILL_MAX | SAS_FAST_EXP | SAS_TIMING))
+        return fail(c, SAS_ERR_INVALID, "%s: flags 0x%x not accepted (SAS_MESH_SURFACE, SAS_DEPTH_FILL_MAX, SAS_FAST_EXP, SAS_TIMING)", who, flags);
+    if (!has(c, HAVE_FEAT)) return fail(c, SAS_ERR_INVALID, "%s: no feature store; label frames need the one-hot group store (sas_scene_features with NULL)", who);
+    if (!c->feat_onehot)
+        return fail(c, SAS_ERR_INVALID, "%s: the feature store holds the caller's features, not the one-hot group store (sas_scene_features with NULL)", who);
+    if (has(c, HAVE_MESH) && !(has(c, HAVE_MESH_FEAT) && c->mesh_feat_onehot))
+        return fail(c, SAS_ERR_INVALID, "%s: the meshes lack their one-hot rows (sas_scene_mesh_features with NULL)", who);
+    return SAS_OK;
+}
+
+int sas_render_batch_labels(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height,
+                            const float *background, float min_alpha, unsigned flags, float *rgb, float *alpha, float *depth,
+                            uint8_t *rgb8, uint8_t *labels, void *stream)
+{
+    if (const int rc = check_labels(c, "sas_render_batch_labels", flags, labels)) return rc;
+    const LabelOut lab = {labels, min_alpha};
+    return render_batch_impl(c, n_views, viewmats, Ks, width, height, background, flags, rgb, alpha, depth, rgb8, nullptr, stream, PoseSets(), lab);
+}
+
+int sas_render_batch_labels_posed(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, const int *pose_set, int n_sets,
+                                  const float *Rt, int width, int height, const float *background, float min_alpha, unsigned flags,
+                                  float *rgb, float *alpha, float *depth, uint8_t *rgb8, uint8_t *labels, void *stream)
+{
+    if (const int rc = check_labels(c, "sas_render_batch_labels_posed", flags, labels)) return rc;
+    if (!Rt) return fail(c, SAS_ERR_INVALID, "sas_render_batch_labels_posed: Rt is required");
+    const PoseSets ps = {pose_set, n_sets, Rt};
+    const LabelOut lab = {labels, min_alpha};
+    return render_batch_impl(c, n_views, viewmats, Ks, width, height, background, flags, rgb, alpha, depth, rgb8, nullptr, stream, ps, lab);
 }
 
 static int render_batch_host_impl(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height,

@@ -200,6 +200,19 @@ struct SasMeshFeatures {
 // MF: nullptr for a frame without meshes
 void sas_launch_blend_features(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
                                const SasFeatures &F, bool fast_exp, const SasMeshFeatures *MF);
+// Label frames (sas_render_batch_labels; DESIGN.md 3, "Label frames"): the argmax over the channels of what sas_launch_blend_features
+// would write with a zero feature background, kept per pixel as one byte.  One workgroup per tile walks the chunks of the store.
+struct SasLabels {
+    const float *store;   // [chunks][n_pad][SAS_FEAT_K]: the one-hot group store
+    long long n_pad;
+    int C, chunks;
+    uint8_t *out;         // [H,W] device
+    float min_alpha;      // 255 where alpha < min_alpha
+    int surface;          // SAS_MESH_SURFACE: alpha of a pixel that shows a triangle is 1
+};
+// after sas_launch_blend / sas_launch_blend_mesh (whose SasMeshExtra::win MF names), on the same frame; MF: nullptr without meshes
+void sas_launch_blend_labels(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f, const SasLabels &B,
+                             bool fast_exp, const SasMeshFeatures *MF);
 // store <- features [nt,C] (device; nullptr: one-hot of the triangles' pose groups), through finite_colour
 void sas_launch_mesh_feature_store(hipStream_t st, int64_t nt, const int4 *tri, const float *src, int C, float *store);
 

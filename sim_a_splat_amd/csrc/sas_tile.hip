@@ -2300,7 +2300,107 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     }
 }
 
+// Label frames: labels[p] = L(w[p,:], a[p]) with w and a what k_blend_features[_mesh] and the frame's alpha plane deliver for a zero
+// feature background, L the argmax over the C channels (ties to the lowest channel) and 255 where a < min_alpha.  One workgroup per
+// tile walks the chunks of the store: each pass is k_blend_features' -- the pixel starts afresh, blend_range composites the chunk's
+// channels (recomputing alpha and T), the epilogue value acc + (1 - a) m is formed as there -- and is folded into the lane's running
+// (best, arg) with a strict > in ascending channel order.  No weight leaves the registers; one byte per pixel is stored.
+template <bool FAST_EXP, bool MESH>
+DEV void label_tile(const SasParams &P, const SasFrame &f, long long n_gauss, const SasLabels &B, const SasMeshFeatures *MF, unsigned char *s_raw)
+{
+    const SasCam &c = P.cam;
+    const BlendLds L = blend_lds(s_raw, kFeatQ);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int oi = (int)blockIdx.x;
+    if (!SAS_IN(oi, f.n_tiles, 340)) return;
+    const int tile = f.tile_order[oi];
+    if (!SAS_IN(tile, f.n_tiles, 341)) return;   // (uniform)
+    const int tx = tile % c.tw, ty = tile / c.tw;
+    int ox, oy, ix, iy;
+    bool inside, wdone0;
+    pixel_of(wv, lane, ox, oy);
+    pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone0);
+    const long long pix = (long long)iy * c.W + ix;
+    // the pixel's triangle as the frame's k_blend_mesh_scene resolved it (MF->win): its depth stops the splats, its row closes the sum
+    unsigned long long win = ~0ull;
+    float zlim = __builtin_inff();
+    if constexpr (MESH) {
+        if (inside && SAS_IN(pix, P.out.n_pixels, 342)) win = MF->win[pix];
+        if (win != ~0ull) zlim = __uint_as_float((unsigned)(win >> 32));
+    }
+    const long long t = (long long)((unsigned)win >> 1);   // (records 2 t, 2 t + 1 belong to triangle t)
+    bool covered = false;
+    if constexpr (MESH) covered = win != ~0ull && t < MF->nt && SAS_IN(t, MF->nt, 343);
+    long long beg, end;
+    tile_segment(f, tile, beg, end);
+    const int *ids = f.sorted_ids + beg;
+    const int count = end > beg ? (int)(end - beg) : 0;
+    unsigned long long ph_lap_ = 0ull;
+    unsigned sync_phase = 0u;
+    float best = -__builtin_inff(), T = 1.0f;
+    int arg = 255;
+#pragma unroll 1
+    for (int q = 0; q < B.chunks; ++q) {
+        PixState p = pix_init(inside, ox);
+        bool wdone = wdone0;
+        FeaturePayloadT<MESH> pay{reinterpret_cast<const float4 *>(B.store) + (long long)q * B.n_pad * kFeatQ, B.n_pad, {}};
+        blend_range<FAST_EXP, MESH>(f, n_gauss, tx, ty, pix_const(ox, oy), count,
+                                    [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay, zlim);
+        T = p.T;   // (the same in every pass)
+        const float a = 1.0f - p.T;
+        const float wb = 1.0f - a;
+        float m[SAS_FEAT_K];
+#pragma unroll
+        for (int k = 0; k < SAS_FEAT_K; ++k) m[k] = 0.0f;
+        if constexpr (MESH) {
+            if (covered && SAS_IN((long long)q * MF->nt + t, (long long)B.chunks * MF->nt, 344)) {
+                const float4 *row = reinterpret_cast<const float4 *>(MF->store) + ((long long)q * MF->nt + t) * kFeatQ;
+#pragma unroll
+                for (int r = 0; r < kFeatQ; ++r) {
+                    const float4 v = row[r];
+                    m[4 * r] = v.x; m[4 * r + 1] = v.y; m[4 * r + 2] = v.z; m[4 * r + 3] = v.w;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < SAS_FEAT_K; ++k) {
+            const int ch = q * SAS_FEAT_K + k;
+            if (ch < B.C && SAS_IN(ch, SAS_MAX_FEATURES, 345)) {
+                const float v = pay.acc[k] + wb * m[k];
+                if (v > best) { best = v; arg = ch; }
+            }
+        }
+    }
+    if (!inside || !SAS_IN(pix, P.out.n_pixels, 346)) return;
+    // the frame's alpha: 1 - T, or 1 exactly where SAS_MESH_SURFACE closes the ray on a triangle
+    const float a = (MESH && B.surface && zlim < __builtin_inff()) ? 1.0f : 1.0f - T;
+    B.out[pix] = (uint8_t)(a < B.min_alpha ? 255 : (arg < 255 ? arg : 255));
+}
+template <bool FAST_EXP>
+__global__ __launch_bounds__(256) void k_blend_labels(SasParams P, SasFrame f, long long n_gauss, SasLabels B)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kFeatLdsBytes];
+    label_tile<FAST_EXP, false>(P, f, n_gauss, B, nullptr, s_raw);
+}
+template <bool FAST_EXP>
+__global__ __launch_bounds__(256) void k_blend_labels_mesh(SasParams P, SasFrame f, long long n_gauss, SasLabels B, SasMeshFeatures MF)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kFeatLdsBytesZ];
+    label_tile<FAST_EXP, true>(P, f, n_gauss, B, &MF, s_raw);
+}
+
 }  // namespace
+
+void sas_launch_blend_labels(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f, const SasLabels &B,
+                             bool fast_exp, const SasMeshFeatures *MF)
+{
+    if (tiles <= 0 || B.chunks <= 0) return;
+    const long long n = s.n > 0 ? s.n : 1;
+    with_flags([&](auto fast) {
+        if (MF) hipLaunchKernelGGL(k_blend_labels_mesh<fast()>, dim3((unsigned)tiles), dim3(256), 0, st, P, f, n, B, *MF);
+        else hipLaunchKernelGGL(k_blend_labels<fast()>, dim3((unsigned)tiles), dim3(256), 0, st, P, f, n, B);
+    }, fast_exp);
+}
 
 void sas_launch_feature_store(hipStream_t st, int64_t n, int64_t n_pad, const int *perm, const uint8_t *gid8, const float *src,
                               int C, float *store)

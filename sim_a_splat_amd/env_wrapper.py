@@ -30,16 +30,23 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import poses
-from .handler import CameraRig, SplatHandler
+from .handler import CameraRig, SplatHandler, camera_obs_dict
 
 
 class SplatEnvWrapper:
     def __init__(self, env, splat_assets_path: Optional[str] = None, match_object_name: Optional[str] = None,
                  splat_config_name: Optional[str] = None, task_assets_path: Optional[str] = None,
                  task_assets_name: Optional[str] = None, *, splat_handler: Optional[SplatHandler] = None, device=0,
-                 meshes=()):
+                 meshes=(), obs_modes=("rgb",)):
         """``splat_handler`` (keyword-only, not in the reference): a handler built elsewhere -- from arrays, or
-        shared between vectorised envs -- instead of loading the assets named by the path arguments."""
+        shared between vectorised envs -- instead of loading the assets named by the path arguments.
+        ``obs_modes`` (keyword-only): what every camera adds to the observation -- ``"rgb"`` (``camera_i``, the reference's
+        entry), ``"depth"`` (``camera_i_depth`` float32 [1,H,W]) and ``"segmentation"`` (``camera_i_segmentation`` uint8
+        [1,H,W], labels by ``ch.row_names()``); the default leaves the observation as the reference's."""
+        self.obs_modes = tuple(obs_modes)
+        bad = [m for m in self.obs_modes if m not in SplatHandler.OBS_MODES]
+        if bad:
+            raise ValueError(f"unknown obs_modes {bad}: choose from {SplatHandler.OBS_MODES}")
         self.env = env
         self._device = device
         self._meshes = tuple(meshes)   # SplatHandler(meshes=...): task / robot meshes in the frames
@@ -127,6 +134,9 @@ class SplatEnvWrapper:
     # -- :132-138 ------------------------------------------------------------------------------------------
     def _get_obs(self) -> Dict[str, np.ndarray]:
         obs = self.unwrapped._get_obs()
+        if self.obs_modes != ("rgb",):
+            obs.update(camera_obs_dict(self.render_observations(self.obs_modes), self.obs_modes))
+            return obs
         img_out = self.render()
         for ii in range(len(img_out)):
             img_out[ii] = img_out[ii].transpose(2, 0, 1)       # np.moveaxis(img, -1, 0): the same view
@@ -141,6 +151,15 @@ class SplatEnvWrapper:
         render_cam_poses = self.get_moving_camera_poses(self.draw_msg) + self.fixed_cam_poses
         sizes = [self.camera_setup_info[k]["render_size"] for k in self.render_cam_keys]
         return self.splat_handler.render(self.ch, render_cam_poses, sizes)
+
+    def render_observations(self, modes=("rgb", "depth", "segmentation")) -> List[Dict[str, np.ndarray]]:
+        """``render`` with further modalities: one dict per camera (``SplatHandler.render_observations``)."""
+        self.env.render()
+        if self._rig is None:
+            raise AttributeError("cameras are not configured: call _configure_cameras(camera_setup_info) first")
+        render_cam_poses = self.get_moving_camera_poses(self.draw_msg) + self.fixed_cam_poses
+        sizes = [self.camera_setup_info[k]["render_size"] for k in self.render_cam_keys]
+        return self.splat_handler.render_observations(self.ch, render_cam_poses, sizes, modes)
 
     # -- :161-163 ------------------------------------------------------------------------------------------
     def close(self):

@@ -386,6 +386,35 @@ class SplatHandler:
                 for (w, p), s in zip(cam, render_size)]
 
 
+    OBS_MODES = ("rgb", "depth", "segmentation")
+
+    def render_observations(self, chs, cam_poses, render_size, modes=("rgb",)) -> List[Dict[str, np.ndarray]]:
+        """``render`` for several modalities: one dict per camera with the ``modes`` asked for -- ``rgb`` uint8 ``[H,W,3]`` (the
+        frame ``render`` returns), ``depth`` float32 ``[H,W]`` (the scene's depth with meshes as surfaces, 0 where nothing is
+        seen) and ``segmentation`` uint8 ``[H,W]`` (``render_segmentation``'s labels).  Cameras of equal size are one call
+        (``SplatScene.get_observations``: label frames); ``modes=("rgb",)`` alone goes through ``render``."""
+        modes = tuple(modes)
+        bad = [m for m in modes if m not in self.OBS_MODES]
+        if bad:
+            raise ValueError(f"unknown observation modes {bad}: choose from {self.OBS_MODES}")
+        if cam_poses is None:
+            cam_poses = [(chs.camera.wxyz, chs.camera.position)]
+        if set(modes) <= {"rgb"}:
+            return [{m: img for m in modes} for img in self.render(chs, cam_poses, render_size)]
+        cam = [poses.pose_wxyz_xyz(p) for p in cam_poses]
+        sizes = [(int(s[0]), int(s[1])) for s in render_size][:len(cam)]
+        want = tuple(k for k, m in (("rgb8", "rgb"), ("depth", "depth")) if m in modes)
+        out: List[Dict[str, np.ndarray]] = [dict() for _ in cam]
+        for hw in dict.fromkeys(sizes):
+            idx = [i for i, s in enumerate(sizes) if s == hw]
+            o = chs.get_observations(hw[0], hw[1], [cam[i] for i in idx], want=want + ("labels",))
+            host = {k: v.cpu().numpy() for k, v in o.items()}
+            for j, i in enumerate(idx):
+                for m in modes:
+                    out[i][m] = host["rgb8"][j] if m == "rgb" else host["depth"][j, :, :, 0] if m == "depth" else host["labels"][j]
+        return out
+
+
 class CameraRig:
     """Camera dictionary ``{id: {link_name, local_frame, type, render_size}}`` of the reference
     (examples/demo_pusht_splat.py:54-78; ``local_frame`` SE3-like or ``(wxyz, xyz)``), resolved to render
@@ -406,8 +435,23 @@ class CameraRig:
     def sizes(self) -> List[Sequence[int]]:
         return [self.camera_setup_info[k]["render_size"] for k in self.render_cam_keys]
 
-    def get_obs(self, handler: SplatHandler, msg) -> Dict[str, np.ndarray]:
+    def get_obs(self, handler: SplatHandler, msg, obs_modes=("rgb",)) -> Dict[str, np.ndarray]:
         """``camera_i`` -> uint8 [3,H,W]  (splat_env_wrapper.py:132-138).  Uses the CURRENT message:
-        the reference reads the one stored at reset (its moving cameras lag)."""
-        imgs = handler.render(handler.scene, self.poses(handler, msg), self.sizes())
-        return {f"camera_{i}": np.moveaxis(img, -1, 0) for i, img in enumerate(imgs)}
+        the reference reads the one stored at reset (its moving cameras lag).  ``obs_modes`` beyond
+        ``("rgb",)``: ``"depth"`` adds ``camera_i_depth`` float32 [1,H,W], ``"segmentation"`` ``camera_i_segmentation`` uint8
+        [1,H,W] (``SplatHandler.render_observations``)."""
+        cam_poses, sizes = self.poses(handler, msg), self.sizes()
+        if tuple(obs_modes) == ("rgb",):
+            imgs = handler.render(handler.scene, cam_poses, sizes)
+            return {f"camera_{i}": np.moveaxis(img, -1, 0) for i, img in enumerate(imgs)}
+        return camera_obs_dict(handler.render_observations(handler.scene, cam_poses, sizes, obs_modes), obs_modes)
+
+
+def camera_obs_dict(per_camera: List[Dict[str, np.ndarray]], obs_modes) -> Dict[str, np.ndarray]:
+    """The per-camera dicts of ``render_observations`` as observation entries, channels first: ``camera_i`` uint8 [3,H,W],
+    ``camera_i_depth`` float32 [1,H,W], ``camera_i_segmentation`` uint8 [1,H,W], in the order of ``obs_modes``."""
+    obs: Dict[str, np.ndarray] = {}
+    for i, d in enumerate(per_camera):
+        for m in obs_modes:
+            obs[f"camera_{i}" if m == "rgb" else f"camera_{i}_{m}"] = np.moveaxis(d[m], -1, 0) if m == "rgb" else d[m][None]
+    return obs

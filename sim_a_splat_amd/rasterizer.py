@@ -610,10 +610,7 @@ class Rasterizer:
         and ``alpha [H,W,1]``.  Selects the one-hot group store (replacing features uploaded before) for the Gaussians and,
         when the scene holds meshes, for the triangles; ``alpha`` then counts a mesh as opaque (``mesh_surface``), so that
         the weights still sum to it."""
-        if not self._features_onehot:
-            self.upload_features(None)
-        if self.n_mesh_triangles > 0 and not self._mesh_features_onehot:
-            self.upload_mesh_features(None)
+        self._select_onehot_stores()
         o = self.render_features(viewmat, K, width, height, want=("features", "alpha"), mesh_surface=self.n_mesh_triangles > 0)
         return {"weights": o["features"], "labels": group_labels(o["features"], o["alpha"], min_alpha), "alpha": o["alpha"]}
 
@@ -661,6 +658,48 @@ class Rasterizer:
                          ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], self._stream())
         self._keep = [] if block else (self._keep + [(res, V, Kc, bg)])[-4:]
         return res
+
+    def _select_onehot_stores(self) -> None:
+        """The one-hot group store for the Gaussians and, when the scene holds meshes, for the triangles (replacing features
+        uploaded before): what ``render_group_masks`` and ``render_batch_labels`` composite."""
+        if not self._features_onehot:
+            self.upload_features(None)
+        if self.n_mesh_triangles > 0 and not self._mesh_features_onehot:
+            self.upload_mesh_features(None)
+
+    @_locked
+    def render_batch_labels(self, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int,
+                            background: Sequence[float] = (0.0, 0.0, 0.0), *, min_alpha: float = 0.5,
+                            want: Iterable[str] = ("labels",), depth_fill_max: bool = False, mesh_surface: Optional[bool] = None,
+                            pose_sets: Optional[ArrayLike] = None, pose_set: Optional[Sequence[int]] = None,
+                            out: Optional[Dict[str, torch.Tensor]] = None, timing: bool = False) -> Dict[str, torch.Tensor]:
+        """Label frames of C same-sized views in one C-ABI call (sas_render_batch_labels[_posed]): ``labels [C,H,W]`` uint8, per
+        pixel the pose group it shows -- ``group_labels`` of what ``render_group_masks`` composites for that view, made on the
+        device without the ``[H,W,G]`` weights ever being written -- plus any of ``rgb`` / ``alpha`` / ``depth`` / ``rgb8``
+        ``[C,H,W,...]`` listed in ``want`` (bit-identical to ``render_batch`` with the same flags).  ``pose_sets`` +
+        ``pose_set``: as in ``render_batch``; the context's poses stay as they are.  ``mesh_surface=None``: on when the scene
+        holds meshes (``render_group_masks``' rule: a mesh counts as opaque).  Selects the one-hot stores as
+        ``render_group_masks`` does.  Blocking.  ``timing``: per-stage events (``stage_time_means``; timed frames run alone)."""
+        self._select_onehot_stores()
+        C = int(np.asarray(viewmats).shape[0]) if not isinstance(viewmats, torch.Tensor) else int(viewmats.shape[0])
+        V, pV = self._host_arg(viewmats, 16 * C)
+        Kc, pK = self._host_arg(Ks, 9 * C)
+        bg, pbg = self._host_arg(background, 3)
+        W, H = int(width), int(height)
+        want = tuple(want)
+        res, ptrs = self._outputs([k for k in want if k != "labels"], self._SHAPES, H, W, out, C)
+        labels = out.get("labels") if out is not None else None
+        if labels is None:
+            labels = torch.empty((C, H, W), dtype=torch.uint8, device=self.device)
+        elif labels.shape != (C, H, W) or labels.dtype != torch.uint8 or not labels.is_contiguous() or labels.device != self.device:
+            raise ValueError(f"out['labels'] must be a contiguous uint8 tensor {(C, H, W)} on {self.device}")
+        res["labels"] = labels
+        surface = self.n_mesh_triangles > 0 if mesh_surface is None else bool(mesh_surface)
+        flags = _flags(True, depth_fill_max, surface, timing=timing)
+        self._batch_call("sas_render_batch_labels", C, pV, pK, pose_sets, pose_set, W, H, pbg, float(min_alpha), flags,
+                         ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], labels.data_ptr(), self._stream())
+        self._keep = []
+        return {k: res[k] for k in dict.fromkeys(want + ("labels",))}
 
     @_locked
     def render_batch_host(self, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int,

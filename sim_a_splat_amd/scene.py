@@ -382,6 +382,31 @@ class SplatScene:
             self._sync()
             return self._raster.render_group_masks(V, K, int(width), int(height), min_alpha=min_alpha)
 
+    def get_observations(self, height: int, width: int, cam_poses, fov: Optional[float] = None, pose_sets=None, pose_set=None,
+                         min_alpha: float = 0.5, want: Sequence[str] = ("labels",)) -> Dict[str, torch.Tensor]:
+        """Label frames of C same-sized cameras ``[(wxyz, position), ...]`` in one call (``Rasterizer.render_batch_labels``):
+        ``labels [C,H,W]`` uint8 and any of ``rgb8 [C,H,W,3]`` / ``depth [C,H,W,1]`` / ``alpha`` / ``rgb`` named in ``want``, device
+        tensors; meshes count as surfaces (depth closes on them, alpha is 1).  ``pose_sets`` / ``pose_set``: per-view pose sets."""
+        f = self.camera.fov if fov is None else float(fov)
+        C = len(cam_poses)
+        q, p = np.empty((C, 4), np.float64), np.empty((C, 3), np.float64)
+        for c, (w, x) in enumerate(cam_poses):
+            q[c], p[c] = w, x
+        V, K = self._views_and_Ks(int(height), int(width), q, p, f)
+        with self.lock:
+            if not self._handles:
+                raise RuntimeError("label frames need at least one splat group or mesh")
+            self._sync()
+            return self._raster.render_batch_labels(V, K, int(width), int(height), self.background, min_alpha=min_alpha, want=tuple(want),
+                                                    pose_sets=pose_sets, pose_set=pose_set)
+
+    def get_segmentations(self, height: int, width: int, cam_poses, fov: Optional[float] = None, pose_sets=None, pose_set=None,
+                          min_alpha: float = 0.5) -> torch.Tensor:
+        """``get_segmentation``'s ``labels`` for C same-sized cameras ``[(wxyz, position), ...]`` in one call: uint8 ``[C,H,W]`` on the
+        device, the pose-row index each pixel shows (``row_names()``; 255: none).  ``pose_sets [S,rows,12]`` + ``pose_set [C]``:
+        camera c sees the scene under ``pose_sets[pose_set[c]]`` (vectorised envs); the scene's own poses are not touched."""
+        return self.get_observations(height, width, cam_poses, fov, pose_sets, pose_set, min_alpha)["labels"]
+
     def close(self) -> None:
         with self.lock:
             self._raster.close()

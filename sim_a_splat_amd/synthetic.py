@@ -77,7 +77,8 @@ def make_scene(n: int, seed: int, log_scale_mean: float = float(np.log(0.01)), n
         # contiguous spatial-ish groups: robot links are a minority of the scene (a7)
         group_id = np.zeros(n, dtype=np.uint8)
         link = rng.uniform(size=n) < 0.25
-        group_id[link] = rng.integers(1, n_groups, size=int(link.sum()), dtype=np.uint8)
+        if n_groups > 1:   # (a single group: everything is group 0)
+            group_id[link] = rng.integers(1, n_groups, size=int(link.sum()), dtype=np.uint8)
     return SyntheticScene(
         means=means.astype(np.float32),
         quats=quats.astype(np.float32),
