@@ -30,7 +30,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import poses
-from .handler import CameraRig, SplatHandler, camera_obs_dict
+from .handler import CameraRig, SplatHandler, _checked_modes, camera_obs_dict
 
 
 class SplatEnvWrapper:
@@ -43,10 +43,7 @@ class SplatEnvWrapper:
         ``obs_modes`` (keyword-only): what every camera adds to the observation -- ``"rgb"`` (``camera_i``, the reference's
         entry), ``"depth"`` (``camera_i_depth`` float32 [1,H,W]) and ``"segmentation"`` (``camera_i_segmentation`` uint8
         [1,H,W], labels by ``ch.row_names()``); the default leaves the observation as the reference's."""
-        self.obs_modes = tuple(obs_modes)
-        bad = [m for m in self.obs_modes if m not in SplatHandler.OBS_MODES]
-        if bad:
-            raise ValueError(f"unknown obs_modes {bad}: choose from {SplatHandler.OBS_MODES}")
+        self.obs_modes = _checked_modes(obs_modes, "obs_modes")
         self.env = env
         self._device = device
         self._meshes = tuple(meshes)   # SplatHandler(meshes=...): task / robot meshes in the frames
@@ -134,32 +131,27 @@ class SplatEnvWrapper:
     # -- :132-138 ------------------------------------------------------------------------------------------
     def _get_obs(self) -> Dict[str, np.ndarray]:
         obs = self.unwrapped._get_obs()
-        if self.obs_modes != ("rgb",):
+        if self.obs_modes == ("rgb",):      # the reference's observation, straight from render (as CameraRig.get_obs): no dict per camera
+            obs.update({f"camera_{i}": img.transpose(2, 0, 1) for i, img in enumerate(self.render())})   # np.moveaxis(img, -1, 0): the same view
+        else:
             obs.update(camera_obs_dict(self.render_observations(self.obs_modes), self.obs_modes))
-            return obs
-        img_out = self.render()
-        for ii in range(len(img_out)):
-            img_out[ii] = img_out[ii].transpose(2, 0, 1)       # np.moveaxis(img, -1, 0): the same view
-        obs.update({f"camera_{ii}": img_out[ii] for ii in range(len(img_out))})
         return obs
 
     # -- :140-159 ------------------------------------------------------------------------------------------
-    def render(self, mode="rgb_array") -> List[np.ndarray]:
+    def _render_cameras(self):
+        """(poses, sizes) of the configured cameras for the current draw message, moving cameras first; the inner env renders too."""
         self.env.render()
         if self._rig is None:
             raise AttributeError("cameras are not configured: call _configure_cameras(camera_setup_info) first")
         render_cam_poses = self.get_moving_camera_poses(self.draw_msg) + self.fixed_cam_poses
-        sizes = [self.camera_setup_info[k]["render_size"] for k in self.render_cam_keys]
-        return self.splat_handler.render(self.ch, render_cam_poses, sizes)
+        return render_cam_poses, [self.camera_setup_info[k]["render_size"] for k in self.render_cam_keys]
+
+    def render(self, mode="rgb_array") -> List[np.ndarray]:
+        return self.splat_handler.render(self.ch, *self._render_cameras())
 
     def render_observations(self, modes=("rgb", "depth", "segmentation")) -> List[Dict[str, np.ndarray]]:
         """``render`` with further modalities: one dict per camera (``SplatHandler.render_observations``)."""
-        self.env.render()
-        if self._rig is None:
-            raise AttributeError("cameras are not configured: call _configure_cameras(camera_setup_info) first")
-        render_cam_poses = self.get_moving_camera_poses(self.draw_msg) + self.fixed_cam_poses
-        sizes = [self.camera_setup_info[k]["render_size"] for k in self.render_cam_keys]
-        return self.splat_handler.render_observations(self.ch, render_cam_poses, sizes, modes)
+        return self.splat_handler.render_observations(self.ch, *self._render_cameras(), modes)
 
     # -- :161-163 ------------------------------------------------------------------------------------------
     def close(self):

@@ -39,6 +39,36 @@ def _translation_of(x) -> np.ndarray:
     return np.asarray(x, dtype=np.float64).reshape(3)
 
 
+def _entries(msg, robot_num: int) -> List[int]:
+    """The draw message's entries of one ``robot_num``, in message order."""
+    rn = msg.robot_num
+    return [i for i in range(msg.num_links) if rn[i] == robot_num]
+
+
+def _cameras(chs, cam_poses) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """``cam_poses`` (SE3-like objects or pairs; None: the client's own camera) as ``(wxyz, xyz)`` pairs."""
+    if cam_poses is None:
+        cam_poses = [(chs.camera.wxyz, chs.camera.position)]
+    return [poses.pose_wxyz_xyz(p) for p in cam_poses]
+
+
+def _by_size(render_size, n: int) -> Dict[Tuple[int, int], List[int]]:
+    """``{(H, W): [cameras of that size]}`` over the first ``n`` cameras, sizes in order of first appearance: one batch each."""
+    groups: Dict[Tuple[int, int], List[int]] = {}
+    for i, s in enumerate(render_size[:n]):
+        groups.setdefault((int(s[0]), int(s[1])), []).append(i)
+    return groups
+
+
+def _checked_modes(modes, what: str = "observation modes") -> Tuple[str, ...]:
+    """Observation modes as a tuple; ValueError (naming them ``what``) on one that is not among ``SplatHandler.OBS_MODES``."""
+    modes = tuple(modes)
+    bad = [m for m in modes if m not in SplatHandler.OBS_MODES]
+    if bad:
+        raise ValueError(f"unknown {what} {bad}: choose from {SplatHandler.OBS_MODES}")
+    return modes
+
+
 TASK_MESH_COLOR = (0.956, 0.396, 0.365)   # splat_handler.py:205
 
 
@@ -115,28 +145,24 @@ class SplatHandler:
 
     ``SplatHandler.from_arrays`` builds the same object from arrays already in memory."""
 
+    task_mesh_frame_handle = None    # a handler has no meshes until _setup registers some
+    mesh_frame_handles = ()
+
     def __init__(self, splat_assets_path: str, match_object_name: str, splat_config_name: str, package_path: str,
                  package_name: str, urdf_name: str, task_assets_path: Optional[str] = None,
                  task_assets_name: Optional[str] = None, sim_robot_weld_frame_transform=None, server: Optional[SplatScene] = None,
                  *, device=0, bounds=None, meshes=()):
         from pathlib import Path
-        from . import io, urdf_fk
+        from . import urdf_fk
         from .covariance import GSplatLoader
         masks_dir = Path(f"{splat_assets_path}/masks/{match_object_name}/").resolve()
-        mfile = masks_dir / "link_masks_global_dict.npz"
-        masks = io.load_link_masks(mfile if mfile.exists() else masks_dir / "link_masks_global_dict.npy")
-        icp = io.load_icp_transformation(masks_dir / "icp_transformation.npy")
         loader = GSplatLoader.from_path(Path(f"{splat_assets_path}/splatfacto/{splat_config_name}").resolve())
         robot_description_dir = package_path + "/" + package_name
         urdf_path = Path(robot_description_dir + f"urdf/{urdf_name}")
         robot = urdf_fk.load(urdf_path)
-        fk = urdf_fk.visual_mesh_fk(robot, io.load_joint_config(masks_dir / "joint_config.npy"))
-        keep = aabb_mask(loader.means.cpu().numpy(), bounds)
-        arr = lambda t: t.cpu().numpy()[keep]
-        masks = {k: np.asarray(v, dtype=bool)[keep] for k, v in masks.items()}
         meshes = _mesh_arrays(meshes, task_assets_path, task_assets_name,
                               robot_meshes=lambda: robot_visual_meshes(robot, robot_description_dir, package_name, urdf_path.parent))
-        self._setup(arr(loader.means), arr(loader.covs), arr(loader.colors), arr(loader.opacities), masks, icp, fk,
+        self._setup(*self._load_assets(loader, masks_dir, robot, bounds),
                     instance_uid=match_object_name, weld=sim_robot_weld_frame_transform, scene=server, device=device, meshes=meshes)
         self.masks_dir = str(masks_dir)
         self.robot_description_dir = robot_description_dir
@@ -211,84 +237,74 @@ class SplatHandler:
     def from_assets(cls, loader, masks_dir, urdf_path, bounds=None, **kw) -> "SplatHandler":
         """Like the path constructor, with the Gaussians already loaded (a ``GSplatLoader``) and the masks
         directory / URDF file given directly; ``bounds`` is the AABB crop of ``_load_saved_splats``."""
+        from . import urdf_fk
+        return cls.from_arrays(*cls._load_assets(loader, masks_dir, urdf_fk.load(urdf_path), bounds), **kw)
+
+    @staticmethod
+    def _load_assets(loader, masks_dir, robot, bounds) -> tuple:
+        """What a handler reads from disk, as the leading arguments of ``from_arrays``: the loader's Gaussians and the link masks
+        of ``masks_dir`` cropped to ``bounds``, the ICP similarity, and ``robot``'s visual-mesh forward kinematics at the mask-time
+        joint configuration."""
         from pathlib import Path
         from . import io, urdf_fk
         d = Path(masks_dir)
         mfile = d / "link_masks_global_dict.npz"
         masks = io.load_link_masks(mfile if mfile.exists() else d / "link_masks_global_dict.npy")
         icp = io.load_icp_transformation(d / "icp_transformation.npy")
-        fk = urdf_fk.visual_mesh_fk(urdf_fk.load(urdf_path), io.load_joint_config(d / "joint_config.npy"))
+        fk = urdf_fk.visual_mesh_fk(robot, io.load_joint_config(d / "joint_config.npy"))
         keep = aabb_mask(loader.means.cpu().numpy(), bounds)
         arr = lambda t: t.cpu().numpy()[keep]
         masks = {k: np.asarray(v, dtype=bool)[keep] for k, v in masks.items()}
-        return cls.from_arrays(arr(loader.means), arr(loader.covs), arr(loader.colors), arr(loader.opacities), masks, icp, fk, **kw)
+        return arr(loader.means), arr(loader.covs), arr(loader.colors), arr(loader.opacities), masks, icp, fk
 
     def mesh_pose_rows(self, msg) -> Tuple[np.ndarray, np.ndarray]:
         """The pose rows ``draw_handler(msg)`` gives this handler's meshes, WITHOUT touching the scene: ``(rows [m], [m,12]
         float32)``.  Task mesh: the last entry with ``robot_num == blk_idx``, ``icp o SE3(q/|q|, p s)`` in float64 (:296-314),
         through the handle's quaternion as ``draw_handler`` assigns it.  Robot meshes: the k-th entry with ``robot_num ==
         rbt_idx`` poses the k-th mesh, ``icp o SE3(q/|q|, (p + weld) s)`` (:238-263); surplus entries are ignored."""
-        idx, found = [], []
-        h = self.task_mesh_frame_handle
-        hits = [i for i in range(msg.num_links) if msg.robot_num[i] == self.blk_idx] if h is not None else []
-        if hits:
-            idx.append(h.index)
-            found.append(self._task_pose(msg, hits[-1]))
-        for hk, i in self._robot_mesh_entries(msg):
-            idx.append(hk.index)
-            found.append(self._robot_mesh_pose(msg, i))
-        rows = np.zeros((len(idx), 3, 4), np.float32)
-        for k, (wxyz, t) in enumerate(found):
+        found = list(self._mesh_entries(msg))
+        rows = np.zeros((len(found), 3, 4), np.float32)
+        for k, (_, wxyz, t) in enumerate(found):
             rows[k, :, :3] = poses.quat_wxyz_to_matrix(wxyz)
             rows[k, :, 3] = t
-        return np.array(idx, np.int64), rows.reshape(len(idx), 12)
+        return np.array([h.index for h, _, _ in found], np.int64), rows.reshape(len(found), 12)
 
-    def _robot_mesh_entries(self, msg) -> list:
-        """(robot mesh handle, message entry) pairs: the k-th entry of the robot with the k-th mesh."""
-        handles = getattr(self, "mesh_frame_handles", None)
-        if not handles:
-            return []
-        return list(zip(handles, (i for i in range(msg.num_links) if msg.robot_num[i] == self.rbt_idx)))
+    def _mesh_entries(self, msg):
+        """``(handle, wxyz, t)`` for every mesh the message poses: the task mesh at its last ``blk_idx`` entry (the reference assigns
+        every one in turn), the k-th robot mesh at the k-th ``rbt_idx`` entry."""
+        hits = _entries(msg, self.blk_idx) if self.task_mesh_frame_handle is not None else []
+        if hits:
+            yield (self.task_mesh_frame_handle, *self._mesh_pose(msg, hits[-1], None))
+        if self.mesh_frame_handles:
+            for h, i in zip(self.mesh_frame_handles, _entries(msg, self.rbt_idx)):
+                yield (h, *self._mesh_pose(msg, i, self.weld_translation))
 
-    def _robot_mesh_pose(self, msg, idx):
+    def _mesh_pose(self, msg, idx: int, weld):
+        """``icp o SE3(q/|q|, (p + weld) s)`` of message entry ``idx`` as (wxyz, t), float64; ``weld`` None: the task mesh, not welded."""
         q = np.asarray(msg.quaternion[idx], dtype=np.float64)
         q = q / np.linalg.norm(q)
         R = self.Ri @ poses.quat_wxyz_to_matrix(q)
-        p = (np.asarray(msg.position[idx], dtype=np.float64) + self.weld_translation) * self.scale_factor
-        return poses.matrix_to_quat_wxyz(R), self.Ri @ p + self.ti
+        p = np.asarray(msg.position[idx], dtype=np.float64)
+        if weld is not None:
+            p = p + weld
+        return poses.matrix_to_quat_wxyz(R), self.Ri @ (p * self.scale_factor) + self.ti
 
-    def _task_pose(self, msg, idx):
-        q = np.asarray(msg.quaternion[idx], dtype=np.float64)
-        q = q / np.linalg.norm(q)
-        R = self.Ri @ poses.quat_wxyz_to_matrix(q)
-        t = self.Ri @ (np.asarray(msg.position[idx], dtype=np.float64) * self.scale_factor) + self.ti
-        return poses.matrix_to_quat_wxyz(R), t
-
-    def _draw_meshes(self, msg) -> None:
-        for hk, idx in self._robot_mesh_entries(msg):
-            hk.wxyz, hk.position = self._robot_mesh_pose(msg, idx)
-        h = self.task_mesh_frame_handle
-        if h is None:
-            return
-        for idx in range(msg.num_links):
-            if msg.robot_num[idx] == self.blk_idx:
-                wxyz, t = self._task_pose(msg, idx)
-                h.wxyz = wxyz
-                h.position = t
+    def _link_entries(self, msg) -> Tuple[List[int], int]:
+        """``(idxs, k)``: the message entries of the robot's links, and how many of them drive link groups -- no more than there are
+        forward-kinematics poses, link groups, or seven (:282)."""
+        idxs = _entries(msg, self.rbt_idx)
+        return idxs, min(len(idxs), len(self.fk), 7, len(self.splat_links_handler))
 
     def draw_handler(self, msg) -> None:
         """``msg``: lcmt_viewer_draw-shaped (num_links, robot_num[], position[][3], quaternion[][4] wxyz).  The
         k-th link of the robot (``robot_num == rbt_idx``, message order) drives splat group k, as in the reference
         (:227-314); all links are posed in one batch of small matrix products."""
-        if getattr(self, "task_mesh_frame_handle", None) is not None or getattr(self, "mesh_frame_handles", None):
-            self._draw_meshes(msg)
-        rn, rbt = msg.robot_num, self.rbt_idx
-        idxs = [idx for idx in range(msg.num_links) if rn[idx] == rbt]
-        if len(idxs) > len(self.fk):
-            for idx in idxs[len(self.fk):]:
-                logging.warning(f"Warning: Received draw command for non-existent Link index {idx}.")
-            idxs = idxs[:len(self.fk)]
-        k = min(len(idxs), 7, len(self.splat_links_handler))               # :282: at most seven link groups
+        if self.task_mesh_frame_handle is not None or self.mesh_frame_handles:
+            for h, wxyz, t in self._mesh_entries(msg):
+                h.wxyz, h.position = wxyz, t
+        idxs, k = self._link_entries(msg)
+        for idx in idxs[len(self.fk):]:
+            logging.warning(f"Warning: Received draw command for non-existent Link index {idx}.")
         if k == 0:
             return
         if self._fast and idxs[k - 1] == k - 1:          # the robot's links lead the message (Drake's order): no gather
@@ -319,9 +335,7 @@ class SplatHandler:
         (``SplatVecEnv``); the rows are the library's context-free ``sas_link_group_poses`` (float64 in C, the
         arithmetic of splat_handler.py:265-288), the same bits ``sas_set_link_poses`` writes."""
         from . import _capi
-        rn, rbt = msg.robot_num, self.rbt_idx
-        idxs = [idx for idx in range(msg.num_links) if rn[idx] == rbt][:len(self.fk)]
-        k = min(len(idxs), 7, len(self.splat_links_handler))
+        idxs, k = self._link_entries(msg)
         groups = np.array([h.index for h in self.splat_links_handler[:k]], dtype=np.int64)
         rows = np.zeros((k, 12), np.float32)
         if k == 0:
@@ -356,21 +370,17 @@ class SplatHandler:
         ``(wxyz, xyz)`` pairs (None: the client's own camera), ``render_size[i] = [H, W]``.  Returns uint8
         [H,W,3] frames in camera order.  Cameras of equal size go to the GPU as one batch when the client
         offers ``get_renders`` (the reference renders them one by one)."""
-        if cam_poses is None:
-            cam_poses = [(chs.camera.wxyz, chs.camera.position)]
-        cam = [poses.pose_wxyz_xyz(p) for p in cam_poses]
+        cam = _cameras(chs, cam_poses)
         n = len(cam)
         s0 = render_size[0] if n else None
         if n and hasattr(chs, "get_renders") and all(s[0] == s0[0] and s[1] == s0[1] for s in render_size[1:n]):
             return list(chs.get_renders(int(s0[0]), int(s0[1]), cam))      # the usual rig: every camera the same size, one batch
-        sizes = [(int(s[0]), int(s[1])) for s in render_size]
-        out: List[Optional[np.ndarray]] = [None] * len(cam)
-        for hw in dict.fromkeys(sizes[:len(cam)]):
-            idx = [i for i, s in enumerate(sizes[:len(cam)]) if s == hw]
+        out: List[Optional[np.ndarray]] = [None] * n
+        for (H, W), idx in _by_size(render_size, n).items():
             if hasattr(chs, "get_renders"):
-                imgs = chs.get_renders(hw[0], hw[1], [cam[i] for i in idx])
+                imgs = chs.get_renders(H, W, [cam[i] for i in idx])
             else:
-                imgs = [chs.get_render(height=hw[0], width=hw[1], wxyz=cam[i][0], position=cam[i][1]) for i in idx]
+                imgs = [chs.get_render(height=H, width=W, wxyz=cam[i][0], position=cam[i][1]) for i in idx]
             for j, i in enumerate(idx):
                 out[i] = np.asarray(imgs[j])
         return out
@@ -379,12 +389,8 @@ class SplatHandler:
         """``render`` for label images: one uint8 ``[H,W]`` per camera, the pose-row index of the splat group or mesh each
         pixel shows (``chs.row_names()`` names the rows; 255: nothing) -- ``SplatScene.get_segmentation``, one view at a time
         (feature frames are single views)."""
-        if cam_poses is None:
-            cam_poses = [(chs.camera.wxyz, chs.camera.position)]
-        cam = [poses.pose_wxyz_xyz(p) for p in cam_poses]
         return [chs.get_segmentation(int(s[0]), int(s[1]), wxyz=w, position=p)["labels"].cpu().numpy()
-                for (w, p), s in zip(cam, render_size)]
-
+                for (w, p), s in zip(_cameras(chs, cam_poses), render_size)]
 
     OBS_MODES = ("rgb", "depth", "segmentation")
 
@@ -393,21 +399,14 @@ class SplatHandler:
         frame ``render`` returns), ``depth`` float32 ``[H,W]`` (the scene's depth with meshes as surfaces, 0 where nothing is
         seen) and ``segmentation`` uint8 ``[H,W]`` (``render_segmentation``'s labels).  Cameras of equal size are one call
         (``SplatScene.get_observations``: label frames); ``modes=("rgb",)`` alone goes through ``render``."""
-        modes = tuple(modes)
-        bad = [m for m in modes if m not in self.OBS_MODES]
-        if bad:
-            raise ValueError(f"unknown observation modes {bad}: choose from {self.OBS_MODES}")
-        if cam_poses is None:
-            cam_poses = [(chs.camera.wxyz, chs.camera.position)]
+        modes = _checked_modes(modes)
         if set(modes) <= {"rgb"}:
             return [{m: img for m in modes} for img in self.render(chs, cam_poses, render_size)]
-        cam = [poses.pose_wxyz_xyz(p) for p in cam_poses]
-        sizes = [(int(s[0]), int(s[1])) for s in render_size][:len(cam)]
+        cam = _cameras(chs, cam_poses)
         want = tuple(k for k, m in (("rgb8", "rgb"), ("depth", "depth")) if m in modes)
         out: List[Dict[str, np.ndarray]] = [dict() for _ in cam]
-        for hw in dict.fromkeys(sizes):
-            idx = [i for i, s in enumerate(sizes) if s == hw]
-            o = chs.get_observations(hw[0], hw[1], [cam[i] for i in idx], want=want + ("labels",))
+        for (H, W), idx in _by_size(render_size, len(cam)).items():
+            o = chs.get_observations(H, W, [cam[i] for i in idx], want=want + ("labels",))
             host = {k: v.cpu().numpy() for k, v in o.items()}
             for j, i in enumerate(idx):
                 for m in modes:

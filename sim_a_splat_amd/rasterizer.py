@@ -19,6 +19,18 @@ from ._capi import SasError
 ArrayLike = Union[np.ndarray, torch.Tensor]
 
 
+def _host(a):
+    """A torch tensor as a detached host NumPy array; anything else as it is."""
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+
+
+def _wait_for(*inputs) -> None:
+    """Device-resident torch inputs must be complete before the library copies them."""
+    for a in inputs:
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            torch.cuda.synchronize(a.device)
+
+
 def _as_f32(a: ArrayLike, shape: Tuple[int, ...], name: str):
     """Return (keepalive, pointer) of a contiguous float32 array with the given shape."""
     if isinstance(a, torch.Tensor):
@@ -50,13 +62,12 @@ MATCH_MOMENTS = 18
 def pack_query_meshes(meshes) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """``[(vertices [V,3], faces [F,3]), ...]`` as one call's arrays (sas_query_meshes): vertices float32 (rounded once), faces int32
     re-based into the joint vertex array, triangle offsets int64 ``[M+1]``.  ValueError on a face index outside its own mesh."""
-    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
     if not 1 <= len(meshes) <= MAX_QUERY_MESHES:
         raise ValueError(f"query_meshes takes 1..{MAX_QUERY_MESHES} meshes, got {len(meshes)}")
     vs, fs, offsets, base = [], [], [0], 0
     for k, (v, f) in enumerate(meshes):
-        v = np.asarray(host(v), dtype=np.float64).reshape(-1, 3).astype(np.float32)
-        f = np.asarray(host(f), dtype=np.int64).reshape(-1, 3)
+        v = np.asarray(_host(v), dtype=np.float64).reshape(-1, 3).astype(np.float32)
+        f = np.asarray(_host(f), dtype=np.int64).reshape(-1, 3)
         if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
             raise ValueError(f"mesh {k}: face indices out of [0,{v.shape[0]})")
         vs.append(v)
@@ -113,9 +124,7 @@ def feature_background_array(fbg, C: int) -> Optional[np.ndarray]:
     """The feature background as a float32 host array [C] (None: zeros, passed as NULL); ValueError on a wrong length."""
     if fbg is None:
         return None
-    if isinstance(fbg, torch.Tensor):
-        fbg = fbg.detach().cpu().numpy()
-    a = np.ascontiguousarray(np.asarray(fbg, dtype=np.float32)).reshape(-1)
+    a = np.ascontiguousarray(np.asarray(_host(fbg), dtype=np.float32)).reshape(-1)
     if a.shape[0] != C:
         raise ValueError(f"feature_background must have {C} values, got {a.shape[0]}")
     return a
@@ -220,8 +229,7 @@ class Rasterizer:
         pf = None
         if rows is not None:
             f, pf = _as_f32(rows, (count, C), name)
-            if isinstance(f, torch.Tensor) and f.is_cuda:
-                torch.cuda.synchronize(f.device)   # device-resident inputs must be complete before the copy
+            _wait_for(f)
         self._check(getattr(self._L, entry)(self._ctx, count, C, pf), entry)
 
     # -- scene ------------------------------------------------------------------------------
@@ -289,16 +297,15 @@ class Rasterizer:
         (``upload_mesh_features``) and vertex attributes are forgotten; ``vertex_normals`` / ``vertex_colors`` ``[V,3]`` are then
         handed to ``upload_mesh_vertex_attributes`` (smooth shading)."""
         self._forget("mesh_features", "mesh_attributes")
-        host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
-        v = np.ascontiguousarray(np.asarray(host(vertices), dtype=np.float32).reshape(-1, 3))
-        t = np.ascontiguousarray(np.asarray(host(triangles), dtype=np.int64).reshape(-1, 3))
+        v = np.ascontiguousarray(np.asarray(_host(vertices), dtype=np.float32).reshape(-1, 3))
+        t = np.ascontiguousarray(np.asarray(_host(triangles), dtype=np.int64).reshape(-1, 3))
         if t.size and (t.min() < 0 or t.max() >= v.shape[0]):
             raise ValueError(f"triangle indices out of [0,{v.shape[0]})")
         t = np.ascontiguousarray(t.astype(np.int32))
         T = t.shape[0]
-        c = np.asarray(host(colors), dtype=np.float32)
+        c = np.asarray(_host(colors), dtype=np.float32)
         c = np.ascontiguousarray(np.broadcast_to(c.reshape(-1, 3) if c.size != 3 else c.reshape(1, 3), (T, 3)))
-        g = np.zeros(T, np.uint8) if groups is None else np.asarray(host(groups))
+        g = np.zeros(T, np.uint8) if groups is None else np.asarray(_host(groups))
         if g.size and (g.min() < 0 or g.max() > 255):
             raise ValueError("mesh groups must be in [0,255]")
         g = np.ascontiguousarray(np.broadcast_to(g.astype(np.uint8).reshape(-1), (T,)))
@@ -316,8 +323,7 @@ class Rasterizer:
         shade evaluated per vertex and interpolated perspective-correctly over the triangle; the others stay flat.  Without
         ``colors`` a smooth triangle keeps its own colour.  Both ``None`` clears the attributes; ``upload`` and
         ``upload_meshes`` forget them."""
-        host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
-        arr = lambda a: None if a is None else np.ascontiguousarray(np.asarray(host(a), dtype=np.float32).reshape(-1, 3))
+        arr = lambda a: None if a is None else np.ascontiguousarray(np.asarray(_host(a), dtype=np.float32).reshape(-1, 3))
         n, c = arr(normals), arr(colors)
         count = next((a.shape[0] for a in (n, c) if a is not None), self.n_mesh_vertices)
         if n is not None and c is not None and n.shape[0] != c.shape[0]:
@@ -356,8 +362,7 @@ class Rasterizer:
         v, f, offsets = pack_query_meshes(meshes)
         n = int(points.shape[0])
         p, pp = _as_f32(points, (n, 3), "points")
-        if isinstance(p, torch.Tensor) and p.is_cuda:
-            torch.cuda.synchronize(p.device)   # device-resident inputs must be complete before the copy
+        _wait_for(p)
         M = len(offsets) - 1
         res = {k: torch.empty((M, n), dtype=torch.float32, device=self.device) for k in ("distance", "winding")}
         if n == 0:
@@ -379,12 +384,10 @@ class Rasterizer:
         ns, nt = int(source.shape[0]), int(target.shape[0])
         s, sp = _as_f32(source, (ns, 3), "source")
         t, tp = _as_f32(target, (nt, 3), "target")
-        for a in (s, t):
-            if isinstance(a, torch.Tensor) and a.is_cuda:
-                torch.cuda.synchronize(a.device)   # device-resident inputs must be complete before the copy
+        _wait_for(s, t)
         A = None
         if transform is not None:
-            A = np.asarray(transform.detach().cpu().numpy() if isinstance(transform, torch.Tensor) else transform, dtype=np.float64)
+            A = np.asarray(_host(transform), dtype=np.float64)
             if A.shape not in ((4, 4), (3, 4)):
                 raise ValueError(f"transform must be 4x4 or 3x4, got {list(A.shape)}")
             A = np.ascontiguousarray(A[:3].astype(np.float32)).reshape(12)
@@ -400,7 +403,7 @@ class Rasterizer:
     def set_group_poses(self, Rt: ArrayLike) -> None:
         """[G,12] (or [G,3,4]) row-major (R|t) per splat group: the poses of the frames submitted from now on
         (frames in flight keep the poses they were submitted with; nothing is waited for)."""
-        arr = np.ascontiguousarray(np.asarray(Rt.cpu() if isinstance(Rt, torch.Tensor) else Rt, dtype=np.float32)).reshape(-1, 12)
+        arr = np.ascontiguousarray(np.asarray(_host(Rt), dtype=np.float32)).reshape(-1, 12)
         self._check(self._L.sas_set_group_poses(self._ctx, arr.shape[0], arr.ctypes.data_as(ctypes.c_void_p)),
                     "sas_set_group_poses")
 
@@ -451,25 +454,28 @@ class Rasterizer:
     # -- frames -----------------------------------------------------------------------------
     _SHAPES = {"rgb": (3, torch.float32), "alpha": (1, torch.float32), "depth": (1, torch.float32),
                "rgb8": (3, torch.uint8)}
+    _LABEL_SHAPES = dict(_SHAPES, labels=(None, torch.uint8))   # channels None: no channel axis
 
     @staticmethod
     def _host_f32(a, count: int) -> np.ndarray:
-        if isinstance(a, torch.Tensor):
-            a = a.detach().cpu().numpy()
+        a = _host(a)
         if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous and a.size == count):
             a = np.ascontiguousarray(np.asarray(a, dtype=np.float32)).reshape(count)
         return a
 
     def _outputs(self, names: Iterable[str], shapes, H: int, W: int, out, views: Optional[int] = None):
-        """(tensors, addresses) of the outputs ``names``, ``[H,W,channels]`` by the table ``shapes`` (``[views,H,W,channels]`` for a
-        batch): ``out``'s where it holds one, validated, else allocated.  Addresses of outputs not asked for: None."""
+        """(tensors, addresses) of the outputs ``names``, ``[H,W,channels]`` by the table ``shapes`` (``[H,W]`` where it gives no
+        channels; ``[views,...]`` for a batch): ``out``'s where it holds one, validated, else allocated.  Addresses of outputs not
+        asked for: None."""
         res: Dict[str, torch.Tensor] = {}
         ptrs = dict.fromkeys(shapes)
         dev = self.device
         given = out.get if out is not None else None
         for k in names:
             ch, dt = shapes[k]   # KeyError: unknown output
-            shape = (H, W, ch) if views is None else (views, H, W, ch)
+            shape = (H, W) if ch is None else (H, W, ch)
+            if views is not None:
+                shape = (views,) + shape
             t = given(k) if given else None
             if t is None:
                 t = torch.empty(shape, dtype=dt, device=dev)
@@ -511,6 +517,19 @@ class Rasterizer:
             self._argcache[id(a)] = (a, arr, ptr)   # (holds `a`: its id cannot be reused while the entry lives)
         return arr, ptr
 
+    def _views(self, viewmats, Ks, background, width, height, batch: bool):
+        """The prologue of a render call: ((view, K, background) host arrays to keep alive, their three addresses, C, W, H);
+        ``batch``: ``viewmats [C,4,4]`` and ``Ks [C,3,3]``, else one view."""
+        C = int(viewmats.shape[0] if isinstance(viewmats, torch.Tensor) else np.asarray(viewmats).shape[0]) if batch else 1
+        V, pV = self._host_arg(viewmats, 16 * C)
+        Kc, pK = self._host_arg(Ks, 9 * C)
+        bg, pbg = self._host_arg(background, 3)
+        return (V, Kc, bg), pV, pK, pbg, C, int(width), int(height)
+
+    def _in_flight(self, block: bool, *keep) -> None:
+        """The ring of what in-flight frames read and write: cleared by a blocking call, else ``keep`` joins the last four."""
+        self._keep = [] if block else (self._keep + [keep])[-4:]
+
     @_locked
     def render(self, viewmat: ArrayLike, K: ArrayLike, width: int, height: int,
                background: Sequence[float] = (0.0, 0.0, 0.0), *, want: Iterable[str] = ("rgb", "alpha", "depth"),
@@ -527,7 +546,7 @@ class Rasterizer:
         completely and keeps it for ``read_tile_lists`` (same image, slower).  ``mesh_surface=True`` (SAS_MESH_SURFACE):
         where a mesh triangle shows, ``alpha`` is 1 and ``depth`` closes on the triangle -- the scene's depth, not that of
         the splats in front of the mesh; rgb and every other pixel keep their bits."""
-        V, pV = self._host_arg(viewmat, 16)
+        V, pV = self._host_arg(viewmat, 16)      # _views and _in_flight written out: a method call is 0.1 - 0.2 us of this per-frame path
         Kc, pK = self._host_arg(K, 9)
         bg, pbg = self._host_arg(background, 3)
         W, H = int(width), int(height)
@@ -549,10 +568,7 @@ class Rasterizer:
         ``rgb``/``alpha``/``depth`` returns ``points [H,W,3]`` (camera frame) and ``mask [H,W]``
         (bool, ``depth < max_depth``; all true for ``max_depth=None``) -- nerfstudio_utils.py:424-445.
         ``mesh_surface=True``: depth, points and mask include the meshes' surfaces (see ``render``)."""
-        V = self._host_f32(viewmat, 16)
-        Kc = self._host_f32(K, 9)
-        bg = self._host_f32(background, 3)
-        W, H = int(width), int(height)
+        keep, pV, pK, pbg, _, W, H = self._views(viewmat, K, background, width, height, False)   # (keep: the host arrays live to the end of this blocking call)
         res = {k: torch.empty((H, W, ch), dtype=dt, device=self.device)
                for k, (ch, dt) in self._SHAPES.items() if k != "rgb8"}
         res["points"] = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
@@ -560,13 +576,13 @@ class Rasterizer:
         md = ctypes.c_float(max_depth) if max_depth is not None else None
         flags = _flags(True, depth_fill_max, mesh_surface)
         stream = self._stream()
-        rc = self._L.sas_render_rgbd(self._ctx, V.ctypes.data, Kc.ctypes.data, W, H, bg.ctypes.data, flags,
+        rc = self._L.sas_render_rgbd(self._ctx, pV, pK, W, H, pbg, flags,
                                      ctypes.addressof(md) if md is not None else None,
                                      res["rgb"].data_ptr(), res["alpha"].data_ptr(), res["depth"].data_ptr(),
                                      res["points"].data_ptr(), mask8.data_ptr(), stream)
         if rc != 0:
             self._check(rc, "sas_render_rgbd")
-        self._keep = []
+        self._in_flight(True)
         res["mask"] = mask8.view(torch.bool)
         return res
 
@@ -586,10 +602,7 @@ class Rasterizer:
         if C <= 0:
             raise SasError("render_features: no features uploaded for this scene (upload_features)")
         fb = feature_background_array(feature_background, C)
-        V, pV = self._host_arg(viewmat, 16)
-        Kc, pK = self._host_arg(K, 9)
-        bg, pbg = self._host_arg(background, 3)
-        W, H = int(width), int(height)
+        keep, pV, pK, pbg, _, W, H = self._views(viewmat, K, background, width, height, False)
         shapes = dict(self._SHAPES, features=(C, torch.float32))
         shapes.pop("rgb8")
         want = tuple(want)
@@ -599,7 +612,7 @@ class Rasterizer:
                                          ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["features"], self._stream())
         if rc != 0:
             self._check(rc, "sas_render_features")
-        self._keep = [] if block else (self._keep + [(dict(res), V, Kc, bg, fb)])[-4:]
+        self._in_flight(block, res, keep, fb)
         return {k: res[k] for k in want}
 
     @_locked
@@ -626,7 +639,7 @@ class Rasterizer:
 
     def _pose_sets(self, pose_sets, pose_set, C: int):
         """(Rt [S,G,12] float32, index [C] int32) of per-view pose sets, validated."""
-        Rt = np.ascontiguousarray(np.asarray(pose_sets.cpu() if isinstance(pose_sets, torch.Tensor) else pose_sets, dtype=np.float32))
+        Rt = np.ascontiguousarray(np.asarray(_host(pose_sets), dtype=np.float32))
         if self.n_groups <= 0 or Rt.size % (12 * self.n_groups):
             raise ValueError(f"pose_sets must be [S,{self.n_groups},12] for this scene")
         Rt = Rt.reshape(-1, self.n_groups, 12)
@@ -647,16 +660,12 @@ class Rasterizer:
         after ``wait()``); ``out`` supplies the ``[C,H,W,...]`` output tensors.  ``pose_sets [S,G,12]`` +
         ``pose_set [C]``: view v is rendered with the group poses ``pose_sets[pose_set[v]]`` (vectorised envs:
         sas_render_batch_posed).  ``mesh_surface``: as in ``render``."""
-        C = int(np.asarray(viewmats).shape[0]) if not isinstance(viewmats, torch.Tensor) else int(viewmats.shape[0])
-        V, pV = self._host_arg(viewmats, 16 * C)
-        Kc, pK = self._host_arg(Ks, 9 * C)
-        bg, pbg = self._host_arg(background, 3)
-        W, H = int(width), int(height)
+        keep, pV, pK, pbg, C, W, H = self._views(viewmats, Ks, background, width, height, True)
         res, ptrs = self._outputs(want, self._SHAPES, H, W, out, C)
         flags = _flags(block, depth_fill_max, mesh_surface, time_tiles=time_tiles)
         self._batch_call("sas_render_batch", C, pV, pK, pose_sets, pose_set, W, H, pbg, flags,
                          ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], self._stream())
-        self._keep = [] if block else (self._keep + [(res, V, Kc, bg)])[-4:]
+        self._in_flight(block, res, keep)
         return res
 
     def _select_onehot_stores(self) -> None:
@@ -681,25 +690,14 @@ class Rasterizer:
         holds meshes (``render_group_masks``' rule: a mesh counts as opaque).  Selects the one-hot stores as
         ``render_group_masks`` does.  Blocking.  ``timing``: per-stage events (``stage_time_means``; timed frames run alone)."""
         self._select_onehot_stores()
-        C = int(np.asarray(viewmats).shape[0]) if not isinstance(viewmats, torch.Tensor) else int(viewmats.shape[0])
-        V, pV = self._host_arg(viewmats, 16 * C)
-        Kc, pK = self._host_arg(Ks, 9 * C)
-        bg, pbg = self._host_arg(background, 3)
-        W, H = int(width), int(height)
-        want = tuple(want)
-        res, ptrs = self._outputs([k for k in want if k != "labels"], self._SHAPES, H, W, out, C)
-        labels = out.get("labels") if out is not None else None
-        if labels is None:
-            labels = torch.empty((C, H, W), dtype=torch.uint8, device=self.device)
-        elif labels.shape != (C, H, W) or labels.dtype != torch.uint8 or not labels.is_contiguous() or labels.device != self.device:
-            raise ValueError(f"out['labels'] must be a contiguous uint8 tensor {(C, H, W)} on {self.device}")
-        res["labels"] = labels
+        keep, pV, pK, pbg, C, W, H = self._views(viewmats, Ks, background, width, height, True)
+        res, ptrs = self._outputs(dict.fromkeys(tuple(want) + ("labels",)), self._LABEL_SHAPES, H, W, out, C)
         surface = self.n_mesh_triangles > 0 if mesh_surface is None else bool(mesh_surface)
         flags = _flags(True, depth_fill_max, surface, timing=timing)
         self._batch_call("sas_render_batch_labels", C, pV, pK, pose_sets, pose_set, W, H, pbg, float(min_alpha), flags,
-                         ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], labels.data_ptr(), self._stream())
-        self._keep = []
-        return {k: res[k] for k in dict.fromkeys(want + ("labels",))}
+                         ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], ptrs["labels"], self._stream())
+        self._in_flight(True)
+        return res
 
     @_locked
     def render_batch_host(self, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int,
@@ -710,11 +708,7 @@ class Rasterizer:
         hands out (np.uint8 arrays), without a second round trip for the device-to-host copy.  ``out`` supplies the
         tensor (CPU, uint8, contiguous; pinned for speed); otherwise a pinned one comes from torch's caching host
         allocator, so a caller may keep what it gets."""
-        C = int(np.asarray(viewmats).shape[0]) if not isinstance(viewmats, torch.Tensor) else int(viewmats.shape[0])
-        V, pV = self._host_arg(viewmats, 16 * C)
-        Kc, pK = self._host_arg(Ks, 9 * C)
-        bg, pbg = self._host_arg(background, 3)
-        W, H = int(width), int(height)
+        keep, pV, pK, pbg, C, W, H = self._views(viewmats, Ks, background, width, height, True)   # (keep: the host arrays live to the end of this blocking call)
         out = self._host_frames(out, (C, H, W, 3))
         self._batch_call("sas_render_batch_host", C, pV, pK, pose_sets, pose_set, W, H, pbg, 0, out.data_ptr(), self._stream())
         return out

@@ -21,6 +21,8 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .rasterizer import _host
+
 N_MOMENTS = 18   # n, sum p' (3), sum q (3), sum q p'^T (9, row-major), sum |p'|^2, sum d2 (sas_match_points)
 
 
@@ -70,10 +72,6 @@ def rotation_from_xyz(rotation_xyz) -> np.ndarray:
     Ry = np.array([[cb, 0, sb], [0, 1, 0], [-sb, 0, cb]], np.float64)
     Rz = np.array([[cc, -sc, 0], [sc, cc, 0], [0, 0, 1]], np.float64)
     return Rx @ Ry @ Rz
-
-
-def _host(a) -> np.ndarray:
-    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
 
 
 def initial_guess(source, target, rotation_xyz=(0.0, 0.0, 0.0), scale: float = 1.0, offset=(0.0, 0.0, 0.0)) -> np.ndarray:

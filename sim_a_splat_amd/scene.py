@@ -82,6 +82,15 @@ class _Camera:
         self.fov = DEFAULT_VERTICAL_FOV
 
 
+def _camera_arrays(cam_poses):
+    """Cameras ``[(wxyz, position), ...]`` as float64 arrays ``(q [C,4], p [C,3])``."""
+    C = len(cam_poses)
+    q, p = np.empty((C, 4), np.float64), np.empty((C, 3), np.float64)
+    for c, (w, x) in enumerate(cam_poses):
+        q[c], p[c] = w, x
+    return q, p
+
+
 class SplatScene:
     """Registered splat groups + the renderer (plays both ``server.scene`` and the client).
 
@@ -110,26 +119,26 @@ class SplatScene:
         self.mesh_ambient, self.mesh_diffuse = 0.4, 0.6   # mesh shading ("Meshes"); set before the first render
         self.camera = _Camera()
 
+    def _register(self, handle_class, name: str, wxyz, position):
+        """(lock held)  A new handle on a pose row of its own, written into the block; the scene is uploaded again before the next frame."""
+        if len(self._handles) >= 256:
+            raise RuntimeError("at most 256 splat groups and meshes")
+        h = handle_class(self, name, len(self._handles), wxyz, position)
+        self._handles.append(h)
+        self._Rt = np.concatenate([self._Rt, np.zeros((1, 3, 4), np.float32)], axis=0)
+        h._write_row()
+        self._uploaded = False
+        return h
+
     def add_gaussian_splats(self, name: str, centers, covariances, rgbs, opacities, wxyz=(1.0, 0.0, 0.0, 0.0),
                             position=(0.0, 0.0, 0.0)) -> GaussianSplatHandle:
         c = np.ascontiguousarray(np.asarray(centers, dtype=np.float32).reshape(-1, 3))
         n = c.shape[0]
+        group = dict(centers=c, covariances=np.asarray(covariances, dtype=np.float32).reshape(n, 3, 3),
+                     rgbs=np.asarray(rgbs, dtype=np.float32).reshape(n, 3), opacities=np.asarray(opacities, dtype=np.float32).reshape(n))
         with self.lock:
-            if len(self._groups) >= 256:
-                raise RuntimeError("at most 256 splat groups")
-            self._groups.append(dict(
-                row=len(self._handles),
-                centers=c,
-                covariances=np.asarray(covariances, dtype=np.float32).reshape(n, 3, 3),
-                rgbs=np.asarray(rgbs, dtype=np.float32).reshape(n, 3),
-                opacities=np.asarray(opacities, dtype=np.float32).reshape(n)))
-            h = GaussianSplatHandle(self, name, len(self._handles), wxyz, position)
-            self._handles.append(h)
-            row = np.zeros((1, 3, 4), np.float32)
-            self._Rt = np.concatenate([self._Rt, row], axis=0)
-            h._write_row()
-            self._uploaded = False
-            self._poses_dirty = True
+            h = self._register(GaussianSplatHandle, name, wxyz, position)
+            self._groups.append(dict(group, row=h.index))
         return h
 
     def add_mesh_simple(self, name: str, vertices, faces, color=(0.5, 0.5, 0.5), wxyz=(1.0, 0.0, 0.0, 0.0),
@@ -156,16 +165,9 @@ class SplatScene:
                 a = a / 255.0
             attr[key] = np.ascontiguousarray(a, dtype=np.float32)
         with self.lock:
-            if len(self._handles) >= 256:
-                raise RuntimeError("at most 256 splat groups and meshes")
-            h = MeshHandle(self, name, len(self._handles), wxyz, position)
+            h = self._register(MeshHandle, name, wxyz, position)
             self._meshes.append(dict(row=h.index, vertices=v.astype(np.float32), faces=f.astype(np.int32),
                                      colors=np.ascontiguousarray(col, dtype=np.float32), **attr))
-            self._handles.append(h)
-            self._Rt = np.concatenate([self._Rt, np.zeros((1, 3, 4), np.float32)], axis=0)
-            h._write_row()
-            self._uploaded = False
-            self._poses_dirty = True
         return h
 
     def add_mesh_trimesh(self, name: str, mesh, scale: float = 1.0, wxyz=(1.0, 0.0, 0.0, 0.0),
@@ -276,52 +278,47 @@ class SplatScene:
 
     @staticmethod
     def _view_and_K(height: int, width: int, wxyz, position, fov: float):
-        R = quat_wxyz_to_matrix(wxyz)                      # camera-to-world, OpenCV axes (+z forward, +y down)
-        V = np.eye(4)
-        V[:3, :3] = R.T
-        V[:3, 3] = -mv3(R.T, np.asarray(position, dtype=np.float64))
-        f = 0.5 * height / np.tan(0.5 * fov)               # vertical FOV, square pixels
-        K = np.array([[f, 0, 0.5 * width], [0, f, 0.5 * height], [0, 0, 1]])
-        return V.astype(np.float32), K.astype(np.float32)
+        """``_views_and_Ks`` of one camera: ([4,4], [3,3]) float32."""
+        V, K = SplatScene._views_and_Ks(height, width, wxyz, position, fov)
+        return V[0], K[0]
 
     @staticmethod
     def _views_and_Ks(height: int, width: int, wxyz: np.ndarray, position: np.ndarray, fov: float):
-        """``_view_and_K`` for C cameras at once: ([C,4,4], [C,3,3]) float32, the same arithmetic per camera."""
-        R = quats_wxyz_to_matrices(wxyz)
+        """World-to-camera matrices and intrinsics of C cameras ``wxyz [C,4]``, ``position [C,3]``: ([C,4,4], [C,3,3]) float32."""
+        R = quats_wxyz_to_matrices(wxyz)                   # camera-to-world, OpenCV axes (+z forward, +y down)
         C = R.shape[0]
         V = np.zeros((C, 4, 4))
         Rt = np.transpose(R, (0, 2, 1))
         V[:, :3, :3] = Rt
         V[:, :3, 3] = -mv3(Rt, np.asarray(position, dtype=np.float64).reshape(C, 3))
         V[:, 3, 3] = 1.0
-        f = 0.5 * height / np.tan(0.5 * fov)
+        f = 0.5 * height / np.tan(0.5 * fov)               # vertical FOV, square pixels
         K = np.array([[f, 0, 0.5 * width], [0, f, 0.5 * height], [0, 0, 1]])
         return V.astype(np.float32), np.broadcast_to(K.astype(np.float32), (C, 3, 3)).copy()
 
     # -- client side ---------------------------------------------------------------------------
+    def _camera_or(self, wxyz=None, position=None, fov: Optional[float] = None):
+        """(wxyz, position, fov) with the client's own camera standing in for whatever is None."""
+        cam = self.camera
+        return cam.wxyz if wxyz is None else wxyz, cam.position if position is None else position, cam.fov if fov is None else float(fov)
+
     def get_render(self, height: int, width: int, wxyz=None, position=None, fov: Optional[float] = None) -> np.ndarray:
         """uint8 [H,W,3] frame from a camera pose (camera-to-world, OpenCV axes)."""
-        wxyz = self.camera.wxyz if wxyz is None else wxyz
-        position = self.camera.position if position is None else position
+        wxyz, position, f = self._camera_or(wxyz, position, fov)
         with self.lock:
             self._sync()
             # view matrix and intrinsics inside the library (sas_camera_matrices: the arithmetic of _view_and_K)
-            return self._raster.render_cameras_host(wxyz, position, self.camera.fov if fov is None else float(fov), int(width), int(height),
-                                                    self.background).numpy()[0]
+            return self._raster.render_cameras_host(wxyz, position, f, int(width), int(height), self.background).numpy()[0]
 
     def get_renders(self, height: int, width: int, cam_poses, fov: Optional[float] = None) -> np.ndarray:
         """uint8 [C,H,W,3] for C same-sized cameras ``[(wxyz, position), ...]`` in one batched call."""
-        f = self.camera.fov if fov is None else float(fov)
-        C = len(cam_poses)
-        qp = np.empty((2, C, 4), np.float64)               # wxyz rows, then xyz rows (padded): one allocation
-        for c, (w, p) in enumerate(cam_poses):
-            qp[0, c] = w
-            qp[1, c, :3] = p
+        q, p = _camera_arrays(cam_poses)
+        f = self._camera_or(fov=fov)[2]
         with self.lock:
             self._sync()
             # view matrices and intrinsics inside the library (sas_camera_matrices: the arithmetic of _views_and_Ks); frames
             # land in pinned host memory on the frames' own streams (sas_render_batch_host): no second round trip
-            return self._raster.render_cameras_host(qp[0], qp[1, :, :3], f, int(width), int(height), self.background).numpy()
+            return self._raster.render_cameras_host(q, p, f, int(width), int(height), self.background).numpy()
 
     def get_renders_posed(self, height: int, width: int, cam_poses, pose_sets, pose_set, fov: Optional[float] = None,
                           out: Optional[torch.Tensor] = None, device_out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -330,12 +327,7 @@ class SplatScene:
         instead of the scene's current ones; ``out`` supplies the tensor.  ``device_out`` (a uint8 [C,H,W,3] tensor on the
         scene's GPU) keeps the frames ON THE DEVICE instead (sas_render_batch_posed): what a multi-GPU rollout gathers
         over RCCL without the frames ever visiting the host on the way."""
-        f = self.camera.fov if fov is None else float(fov)
-        C = len(cam_poses)
-        q, p = np.empty((C, 4), np.float64), np.empty((C, 3), np.float64)
-        for c, (w, x) in enumerate(cam_poses):
-            q[c], p[c] = w, x
-        V, K = self._views_and_Ks(int(height), int(width), q, p, f)
+        V, K = self._views_and_Ks(int(height), int(width), *_camera_arrays(cam_poses), self._camera_or(fov=fov)[2])
         with self.lock:
             self._sync()
             if device_out is not None:
@@ -356,7 +348,7 @@ class SplatScene:
                          mesh_surface: bool = False) -> Dict[str, torch.Tensor]:
         """float32 device tensors ``rgb`` / ``alpha`` / ``depth``; ``mesh_surface=True``: alpha and depth of the whole scene, the
         meshes' surfaces included (``Rasterizer.render``)."""
-        V, K = self._view_and_K(int(height), int(width), wxyz, position, self.camera.fov if fov is None else float(fov))
+        V, K = self._view_and_K(int(height), int(width), *self._camera_or(wxyz, position, fov))
         with self.lock:
             self._sync()
             return self._raster.render(V, K, int(width), int(height), self.background, want=("rgb", "alpha", "depth"),
@@ -373,9 +365,7 @@ class SplatScene:
         """Which handle each pixel shows (``Rasterizer.render_group_masks``): ``labels [H,W]`` uint8, the pose-row index of the
         splat group or mesh (255: none, alpha < min_alpha), ``weights [H,W,rows]`` and ``alpha [H,W,1]`` (a mesh counts as
         opaque).  Device tensors."""
-        wxyz = self.camera.wxyz if wxyz is None else wxyz
-        position = self.camera.position if position is None else position
-        V, K = self._view_and_K(int(height), int(width), wxyz, position, self.camera.fov if fov is None else float(fov))
+        V, K = self._view_and_K(int(height), int(width), *self._camera_or(wxyz, position, fov))
         with self.lock:
             if not self._handles:
                 raise RuntimeError("get_segmentation needs at least one splat group or mesh")
@@ -387,12 +377,7 @@ class SplatScene:
         """Label frames of C same-sized cameras ``[(wxyz, position), ...]`` in one call (``Rasterizer.render_batch_labels``):
         ``labels [C,H,W]`` uint8 and any of ``rgb8 [C,H,W,3]`` / ``depth [C,H,W,1]`` / ``alpha`` / ``rgb`` named in ``want``, device
         tensors; meshes count as surfaces (depth closes on them, alpha is 1).  ``pose_sets`` / ``pose_set``: per-view pose sets."""
-        f = self.camera.fov if fov is None else float(fov)
-        C = len(cam_poses)
-        q, p = np.empty((C, 4), np.float64), np.empty((C, 3), np.float64)
-        for c, (w, x) in enumerate(cam_poses):
-            q[c], p[c] = w, x
-        V, K = self._views_and_Ks(int(height), int(width), q, p, f)
+        V, K = self._views_and_Ks(int(height), int(width), *_camera_arrays(cam_poses), self._camera_or(fov=fov)[2])
         with self.lock:
             if not self._handles:
                 raise RuntimeError("label frames need at least one splat group or mesh")

@@ -18,6 +18,8 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
+from .rasterizer import _host
+
 AXES = {"X": (1, 2, 0), "Y": (0, 2, 1), "Z": (0, 1, 2)}   # (u, v, w): the polygon's plane and the prism's axis
 
 
@@ -51,10 +53,6 @@ def transform_vertices(vertices, T) -> np.ndarray:
     v = np.asarray(vertices, np.float64).reshape(-1, 3)
     T = np.asarray(T, np.float64).reshape(4, 4)
     return v @ T[:3, :3].T + T[:3, 3]
-
-
-def _host(a) -> np.ndarray:
-    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
 
 
 def link_masks_from_meshes(means, meshes, transforms, *, distance: float = 0.015, crop=None, rasterizer=None) -> Dict[str, np.ndarray]:

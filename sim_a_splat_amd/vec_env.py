@@ -97,12 +97,7 @@ class SplatVecEnv:
         gather's common shape: zeroed, not whatever the block held."""
         shape = (self.per_rank * self.C, self.H, self.W, 3)
         n_mine = len(self.mine) * self.C
-        if self._device_payload:
-            buf = torch.empty(shape, dtype=torch.uint8, device=self._device)
-            if n_mine < shape[0]:
-                buf[n_mine:].zero_()
-            return buf
-        buf = self._new_host_buffer(shape)
+        buf = torch.empty(shape, dtype=torch.uint8, device=self._device) if self._device_payload else self._new_host_buffer(shape)
         if n_mine < shape[0]:
             buf[n_mine:].zero_()
         return buf
@@ -156,11 +151,8 @@ class SplatVecEnv:
             cams = [self.rig.poses(self.handler, m) for m in msgs]                         # E_local x C (wxyz, xyz)
             flat = [c for env_c in cams for c in env_c]
             idx = [k for k in range(len(msgs)) for _ in range(self.C)]
-            n = len(flat)
-            if self._device_payload:
-                self.scene.get_renders_posed(self.H, self.W, flat, pose_sets, idx, fov=self.fov, device_out=buf[:n])
-            else:
-                self.scene.get_renders_posed(self.H, self.W, flat, pose_sets, idx, fov=self.fov, out=buf[:n])
+            dest = {"device_out" if self._device_payload else "out": buf[:len(flat)]}
+            self.scene.get_renders_posed(self.H, self.W, flat, pose_sets, idx, fov=self.fov, **dest)
         self._done_steps += 1
 
     def _on_gathered(self, step: int, got) -> None:
