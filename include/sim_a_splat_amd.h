@@ -382,6 +382,34 @@ int sas_render_batch_labels_posed(sas_ctx *ctx, int n_views, const float *viewma
                                   unsigned flags, float *rgb, float *alpha, float *depth, uint8_t *rgb8, uint8_t *labels,
                                   void *stream);
 
+/*
+ * Label lifting: the transpose of a label frame, pixel -> Gaussian.  Serves per-Gaussian masks for objects without a mesh
+ * (splat_handler.py:62-83 takes {"link": bool[N]}): label a few images, push the labels back through the renderer.  The contract:
+ * for view v, pixel p inside the image, and every list entry i (a Gaussian, in the CALLER's order) that the frame's compositing ADDS
+ * at p, let vis be the float32 weight -- the same weight that multiplies the colours in sas_render and the channels in
+ * sas_render_features, under the context's current group poses and the call's flags -- and
+ *     q = (int64) floorf(vis * 2^32)          (SAS_LIFT_ONE; the product is exact in float32 and 0 <= vis < 1).
+ * Then seen[i] += q and, if labels[v,p] < n_labels, votes[i, labels[v,p]] += q.  Nothing is added for: entries skipped for
+ * alpha < 1/255 or sigma < 0; the entry that trips T' <= 1e-4 and everything behind it; pixels of a ragged tile beyond W or H;
+ * labels >= n_labels (so 255 means "unlabelled" for every n_labels <= 255).
+ *   labels    [n_views,H,W] uint8 DEVICE, required
+ *   n_labels  1..256
+ *   votes     [N,n_labels] int64 DEVICE, or NULL
+ *   seen      [N] int64 DEVICE, or NULL; at least one of votes and seen
+ *   flags     SAS_FAST_EXP and SAS_TIMING only.  The call is blocking: SAS_ASYNC and every other flag is SAS_ERR_INVALID.
+ * The call ADDS to what the buffers hold: the caller zeroes them once and may accumulate over many calls.  The sums are integers,
+ * so the result does not depend on any order of addition: two calls with the same inputs give the same bits, and n_views views in
+ * one call equal the same views one call each.  No overflow occurs while the pixels accumulated into one buffer (sum of W*H over
+ * the views) stay below 2^31; the call does not check it.
+ * Frames in flight are completed first.  Lift frames are SAS_FULL_SORT frames, one view at a time through the frame slots, as label
+ * frames are.  SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID for n_labels out of range, missing labels, both outputs NULL,
+ * n_views < 1, non-positive sizes, or a context that holds meshes (occlusion by meshes is not lifted: clear the meshes first).
+ * After any error the context stays usable.
+ */
+#define SAS_LIFT_ONE 4294967296.0f   /* 2^32: the fixed-point unit of a vote */
+int sas_lift_labels(sas_ctx *ctx, int n_views, const float *viewmats, const float *Ks, int width, int height,
+                    const uint8_t *labels, int n_labels, unsigned flags, int64_t *votes, int64_t *seen, void *stream);
+
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical
  * field of view; the view matrices and intrinsics are those of sas_camera_matrices. */

@@ -56,6 +56,10 @@ struct ViewOut {
     uint8_t *rgb8_host = nullptr;   // sas_render_batch_host: host copy of rgb8, made on the frame's stream
     float *features = nullptr;      // sas_render_features: [H,W,feat_c] (device), composited behind the frame's k_blend
     uint8_t *labels = nullptr;      // sas_render_batch_labels: [H,W] (device), the argmax of the one-hot stores' channels
+    // sas_lift_labels: the view's label image [H,W] (device) and the per-Gaussian sums the frame ADDS to (either may be nullptr)
+    const uint8_t *lift_labels = nullptr;
+    int64_t *lift_votes = nullptr, *lift_seen = nullptr;
+    int lift_n = 0;                 // n_labels
 };
 
 struct RenderArgs {
@@ -821,6 +825,10 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
         // a feature frame (sas_render_features): the same lists and records once more, per chunk of channels
         if (a.out.features) sas_launch_blend_features(st, c->scene, tiles, P, f, features_of(c, a), fast_exp, nullptr);
         if (a.out.labels) sas_launch_blend_labels(st, c->scene, tiles, P, f, labels_of(c, a), fast_exp, nullptr);   // a label frame: likewise
+        if (a.out.lift_labels) {   // a lift frame: the same lists, the weights handed back to their Gaussians
+            const SasLift B{a.out.lift_labels, (unsigned long long *)a.out.lift_votes, (unsigned long long *)a.out.lift_seen, c->scene.n, a.out.lift_n};
+            sas_launch_lift_labels(st, c->scene, tiles, P, f, B, fast_exp);
+        }
     } else if (nv > 1) {
         // (quad: by the size of one view (prepare_frame): groups of four 300-tile views still gain (vec_env_probe))
         sas_launch_tiles_lazy_multi(st, c->scene, tiles, mf, fast_exp, any_fill, ld.quad, tile_ev[0], tile_ev[1]);
@@ -1382,7 +1390,7 @@ static void fill_args(RenderArgs &a, const ViewCall &v, int width, int height, c
     const ViewOut &o = v.out;
     a.solo = solo;
     // rgb8 beside rgb8_host is the context's own staging frame (sas_render_batch_host): nothing of the caller's on the device
-    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || o.labels || (o.rgb8 && !o.rgb8_host);
+    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || o.labels || o.lift_labels || (o.rgb8 && !o.rgb8_host);
     memcpy(a.viewmat, v.viewmat, sizeof(a.viewmat));
     memcpy(a.K, v.K, sizeof(a.K));
     for (int k = 0; k < 3; ++k) a.bg[k] = background ? background[k] : 0.0f;
@@ -1899,6 +1907,36 @@ int sas_render_batch_labels_posed(sas_ctx *c, int n_views, const float *viewmats
     const PoseSets ps = {pose_set, n_sets, Rt};
     const LabelOut lab = {labels, min_alpha};
     return render_batch_impl(c, n_views, viewmats, Ks, width, height, background, flags, rgb, alpha, depth, rgb8, nullptr, stream, ps, lab);
+}
+
+int sas_lift_labels(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height, const uint8_t *labels,
+                    int n_labels, unsigned flags, int64_t *votes, int64_t *seen, void *stream)
+{
+    if (!c) return SAS_ERR_INVALID;
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_lift_labels before sas_scene_upload");
+    if (flags & ~(SAS_FAST_EXP | SAS_TIMING))
+        return fail(c, SAS_ERR_INVALID, "sas_lift_labels: flags 0x%x not accepted (SAS_FAST_EXP, SAS_TIMING; blocking only)", flags);
+    if (has(c, HAVE_MESH))
+        return fail(c, SAS_ERR_INVALID, "sas_lift_labels: lift frames do not take occlusion by meshes; clear the meshes first (sas_scene_meshes with none)");
+    if (n_labels < 1 || n_labels > 256) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: n_labels %d out of [1,256]", n_labels);
+    if (!labels) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: the label images are required");
+    if (!votes && !seen) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: votes and seen are both NULL");
+    if (n_views < 1 || !viewmats || !Ks) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: bad view batch (n_views %d)", n_views);
+    if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: bad image size %dx%d", width, height);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;   // frames in flight are completed first
+    // Lift frames are SAS_FULL_SORT frames: one view at a time through the frame slots, nothing drains between views.  (A frame that
+    // outgrew its key buffer adds nothing and is rendered again: k_lift_labels.)
+    const size_t px = (size_t)width * (size_t)height;
+    for (int v = 0; v < n_views; ++v) {
+        ViewCall vc{viewmats + 16 * v, Ks + 9 * v, {}};
+        vc.out.lift_labels = labels + px * v;
+        vc.out.lift_votes = votes;
+        vc.out.lift_seen = seen;
+        vc.out.lift_n = n_labels;
+        if (const int rc = render_views(c, &vc, 1, width, height, nullptr, flags | SAS_FULL_SORT | SAS_ASYNC, nullptr, stream)) return rc;
+    }
+    return sas_wait(c);
 }
 
 static int render_batch_host_impl(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height,

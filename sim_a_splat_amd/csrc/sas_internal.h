@@ -213,6 +213,19 @@ struct SasLabels {
 // after sas_launch_blend / sas_launch_blend_mesh (whose SasMeshExtra::win MF names), on the same frame; MF: nullptr without meshes
 void sas_launch_blend_labels(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f, const SasLabels &B,
                              bool fast_exp, const SasMeshFeatures *MF);
+// Label lifting (sas_lift_labels; DESIGN.md 3, "Label lifting"): the transpose of a label frame.  Every weight the frame's
+// compositing adds at a pixel goes, as q = floor(weight 2^32), to the entry's Gaussian (caller's index perm[slot]): seen[i] += q and,
+// where the pixel's label is below n_labels, votes[i, label] += q.  64-bit integer atomics: the sums do not depend on their order.
+struct SasLift {
+    const uint8_t *labels;        // [H,W] device: the view's label image
+    unsigned long long *votes;    // [n,n_labels] device (the caller's int64), or nullptr
+    unsigned long long *seen;     // [n] device, or nullptr
+    long long n;                  // Gaussians of the scene
+    int n_labels;                 // 1..256
+};
+// after sas_launch_blend, on the same frame (no meshes): one workgroup per tile
+void sas_launch_lift_labels(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f, const SasLift &B,
+                            bool fast_exp);
 // store <- features [nt,C] (device; nullptr: one-hot of the triangles' pose groups), through finite_colour
 void sas_launch_mesh_feature_store(hipStream_t st, int64_t nt, const int4 *tri, const float *src, int C, float *store);
 

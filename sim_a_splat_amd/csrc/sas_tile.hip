@@ -2389,7 +2389,129 @@ __global__ __launch_bounds__(256) void k_blend_labels_mesh(SasParams P, SasFrame
     label_tile<FAST_EXP, true>(P, f, n_gauss, B, &MF, s_raw);
 }
 
+// Label lifting (sas_lift_labels): blend_range once more on the frame's complete lists, with the entry's Gaussian in the colours' place.
+// An entry carries the CALLER's index of its Gaussian (perm[slot]: one int, staged in the first word of its q2 record) and nothing else;
+// add() turns the two weights of a trip into q = floor(weight 2^32) (a lane that does not composite carries weight +0: q = 0) and
+// hands them to the Gaussian.  The 16 lanes of a 4x4 block walk the same entry in lockstep (blend_range), so their q are summed
+// first -- over the block for `seen`, over the block's lanes of one label for `votes` -- and one lane issues one 64-bit integer
+// atomic per (entry, block[, label]).  The four waves are not combined through LDS: they own different quadrants of the tile and
+// walk a batch at their own pace, and an entry reaches few blocks ("Label lifting").
+struct LiftPayload {
+    typedef int Rec;
+    typedef int V;
+    const int *perm;               // slot j holds the caller's Gaussian perm[j]
+    unsigned long long *votes;     // [n][n_labels], or nullptr
+    unsigned long long *seen;      // [n], or nullptr
+    long long n;
+    int n_labels;
+    int label;                     // of this lane's pixel; >= n_labels: unlabelled (255, and pixels outside the image)
+    DEV Rec none() const { return 0; }
+    DEV Rec fetch(const SasFrame &, long long id) const { return (SAS_IN(id, n, 350) && id < n) ? perm[id] : 0; }
+    DEV void stage(const BlendLds &L, int slot, const Rec &c, float) const
+    {
+        if (SAS_IN(slot, kStage, 351)) *reinterpret_cast<int *>(L.q2 + slot) = c;
+    }
+    DEV void stage_sentinel(const BlendLds &L, float z0) const { L.q2[256] = make_float4(z0, z0, z0, z0); }   // Gaussian 0, weight 0
+    DEV V load(const char *q2b, unsigned off) const
+    {
+        if (!SAS_IN(off >> 4, kStage, 352)) off = 256u << 4;
+        return *reinterpret_cast<const int *>(q2b + off);
+    }
+    DEV float depth(const V &) const { return 0.0f; }
+    // sum over the 16 lanes of this lane's 4x4 block (lanes 16 g .. 16 g + 15 of the wave); q < 2^32 each, so the halves cannot overflow
+    // (a DPP row IS a block's 16 lanes: neighbours in a quad, the quad's other pair, then -- every lane of a quad holding the quad's
+    // sum -- the row's half mirror swaps the quads of a half and the row mirror the halves.  Every lane of the wave is active here.)
+    template <int CTRL>
+    static DEV unsigned row_move(unsigned v) { return (unsigned)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true); }
+    static DEV unsigned row_sum(unsigned v)
+    {
+        v += row_move<0xB1>(v);    // quad_perm:[1,0,3,2]
+        v += row_move<0x4E>(v);    // quad_perm:[2,3,0,1]
+        v += row_move<0x141>(v);   // row_half_mirror
+        v += row_move<0x140>(v);   // row_mirror
+        return v;
+    }
+    static DEV unsigned long long block_sum(unsigned q)
+    {
+        const unsigned lo = row_sum(q & 0xffffu), hi = row_sum(q >> 16);
+        return ((unsigned long long)hi << 16) + lo;
+    }
+    // one entry: the block's lanes hold the same Gaussian `idx` (they read the same queue slot)
+    DEV void give(int idx, float vis) const
+    {
+        // floorf(vis 2^32): the product is exact (a power of two), 0 <= vis < 1, and the conversion truncates
+        const unsigned q = (unsigned)(vis * 4294967296.0f);
+        if (!__ballot(q != 0u)) return;   // (uniform) nobody in the wave composited this entry
+        const int lane = (int)(threadIdx.x & 63u), l16 = lane & 15, base = lane & 48;
+        const bool ok = idx >= 0 && (long long)idx < n && SAS_IN(idx, n, 353);
+        if (seen) {
+            const unsigned long long s = block_sum(q);
+            if (l16 == 0 && s != 0ull && ok) atomicAdd(seen + idx, s);
+        }
+        if (votes) {
+            const bool mine = q != 0u && label < n_labels;
+            unsigned long long pend = __ballot(mine);   // lanes whose vote is still to be served
+            while (pend) {   // (uniform) one label per block and turn: usually one turn
+                const unsigned gm = (unsigned)(pend >> base) & 0xffffu;
+                const int lead = gm ? __ffs((int)gm) - 1 : 0;
+                const int lab = __shfl(label, base + lead);
+                const bool take = mine && gm != 0u && label == lab;
+                const unsigned long long s = block_sum(take ? q : 0u);
+                const long long at = (long long)idx * n_labels + lab;
+                if (l16 == lead && gm != 0u && ok && lab >= 0 && lab < n_labels && SAS_IN(at, n * n_labels, 354)) atomicAdd(votes + at, s);
+                pend &= ~__ballot(take);
+            }
+        }
+    }
+    DEV void add(PixState &, const V &c0, float vis0, const V &c1, float vis1) const
+    {
+        give(c0, vis0);
+        give(c1, vis1);
+    }
+};
+
+// One workgroup per tile, one lane per pixel (pixel_of), on the complete depth-ordered lists the frame's k_blend has just composited.
+// A frame whose lists outgrew the key buffer (it is rendered again: complete_oldest) adds nothing.
+template <bool FAST_EXP>
+__global__ __launch_bounds__(256) void k_lift_labels(SasParams P, SasFrame f, long long n_gauss, SasLift B, const int *perm)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kBlendLdsBytes];
+    const SasCam &c = P.cam;
+    const BlendLds L = blend_lds(s_raw);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int oi = (int)blockIdx.x;
+    if (!SAS_IN(oi, f.n_tiles, 355) || oi >= f.n_tiles) return;
+    if ((long long)f.tile_offset[f.n_tiles] > f.cap) return;   // (uniform) truncated lists: the frame's second rendering votes
+    const int tile = f.tile_order[oi];
+    if (!SAS_IN(tile, f.n_tiles, 356) || tile < 0 || tile >= f.n_tiles) return;   // (uniform)
+    const int tx = tile % c.tw, ty = tile / c.tw;
+    int ox, oy, ix, iy;
+    bool inside, wdone;
+    pixel_of(wv, lane, ox, oy);
+    PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
+    const long long pix = (long long)iy * c.W + ix;
+    int label = 256;
+    if (inside && SAS_IN(pix, P.out.n_pixels, 357)) label = (int)B.labels[pix];
+    long long beg, end;
+    tile_segment(f, tile, beg, end);
+    const int *ids = f.sorted_ids + beg;
+    LiftPayload pay{perm, B.votes, B.seen, B.n, B.n_labels, label};
+    unsigned long long ph_lap_ = 0ull;
+    unsigned sync_phase = 0u;
+    blend_range<FAST_EXP>(f, n_gauss, tx, ty, pix_const(ox, oy), end > beg ? (int)(end - beg) : 0,
+                          [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay);
+}
+
 }  // namespace
+
+void sas_launch_lift_labels(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f, const SasLift &B,
+                            bool fast_exp)
+{
+    if (tiles <= 0 || s.n <= 0 || (!B.votes && !B.seen)) return;
+    with_flags([&](auto fast) {
+        hipLaunchKernelGGL(k_lift_labels<fast()>, dim3((unsigned)tiles), dim3(256), 0, st, P, f, (long long)s.n, B, s.perm);
+    }, fast_exp);
+}
 
 void sas_launch_blend_labels(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f, const SasLabels &B,
                              bool fast_exp, const SasMeshFeatures *MF)

@@ -274,6 +274,21 @@ class GaussianSplat:
     def model(self) -> SplatModel:
         return self.pipeline.model
 
+    def lift_labels(self, poses, label_images, n_labels: int, views_per_call: int = 8) -> Dict[str, torch.Tensor]:
+        """Lift label images of the views ``poses`` onto the model's Gaussians (``Rasterizer.lift_labels``): ``poses [C,>=3,4]``
+        camera-to-world, OpenGL axes, as ``render(pose)`` takes one; ``label_images [C,H,W]`` uint8 at camera 0's size, 255
+        unlabelled -- hand-painted masks, a 2D segmenter's output, label frames.  The intrinsics are training camera 0's: the
+        camera path of ``render``.  Returns ``{"votes": int64 [N,n_labels], "seen": int64 [N]}`` (device), for
+        ``segment.masks_from_votes``."""
+        from .segment import lift_label_views
+        model = self.pipeline.model
+        if not isinstance(model, SplatModel):
+            raise TypeError("lift_labels needs a SplatModel")
+        _, K, W, H = self._camera0()
+        c2w = [p[:3] if isinstance(p, (np.ndarray, torch.Tensor)) else np.asarray(p, dtype=np.float32)[:3] for p in poses]
+        V = np.stack([viewmat_from_c2w_opengl(p) for p in c2w])
+        return lift_label_views(model._rasterizer(), V, np.broadcast_to(K, (len(V), 3, 3)), W, H, label_images, n_labels, views_per_call)
+
     def generate_RGBD_point_cloud(self, pose, max_depth: Optional[float] = 1.0):
         """RGB-D consumer of nerfstudio_utils.py:375-472 (tensor results only; the open3d cloud is
         ``points[mask]`` / ``rgb[mask]``).  Render and unprojection are one C-ABI call: the depth

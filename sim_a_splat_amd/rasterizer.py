@@ -57,6 +57,7 @@ MESH_QUERY_CHUNK = _capi.SAS_QUERY_CHUNK   # triangles query_meshes' kernel stag
 MAX_QUERY_MESHES = 256
 MATCH_CHUNK = _capi.SAS_MATCH_CHUNK   # targets match_points' kernel stages at a time: target sizes around it take its chunk edges
 MATCH_MOMENTS = 18
+LIFT_ONE = _capi.SAS_LIFT_ONE   # 2**32: the fixed-point unit of lift_labels' votes (a weight of 1.0)
 
 
 def pack_query_meshes(meshes) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -696,6 +697,50 @@ class Rasterizer:
         flags = _flags(True, depth_fill_max, surface, timing=timing)
         self._batch_call("sas_render_batch_labels", C, pV, pK, pose_sets, pose_set, W, H, pbg, float(min_alpha), flags,
                          ptrs["rgb"], ptrs["alpha"], ptrs["depth"], ptrs["rgb8"], ptrs["labels"], self._stream())
+        self._in_flight(True)
+        return res
+
+    def _lift_buffer(self, t: Optional[torch.Tensor], shape: Tuple[int, ...], name: str) -> torch.Tensor:
+        """A sum buffer of ``lift_labels``: the caller's (accumulated into), validated, or a zeroed one."""
+        if t is None:
+            return torch.zeros(shape, dtype=torch.int64, device=self.device)
+        if not isinstance(t, torch.Tensor) or t.shape != shape or t.dtype != torch.int64 or not t.is_contiguous() or t.device != self.device:
+            raise ValueError(f"{name} must be a contiguous int64 tensor {shape} on {self.device}")
+        return t
+
+    @_locked
+    def lift_labels(self, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int, labels: ArrayLike, n_labels: int, *,
+                    votes: Union[torch.Tensor, None, bool] = None, seen: Union[torch.Tensor, None, bool] = None,
+                    fast_exp: bool = False, timing: bool = False) -> Dict[str, torch.Tensor]:
+        """Lift label images onto the Gaussians (sas_lift_labels), the transpose of a label frame: ``labels [C,H,W]`` uint8 (a
+        NumPy array or a tensor; copied to the device as uint8) for the views ``viewmats [C,4,4]``, ``Ks [C,3,3]``.  Every
+        Gaussian collects, from every pixel it is composited into, ``q = floor(weight * LIFT_ONE)`` of its compositing weight:
+        ``seen [N]`` takes all of them, ``votes [N,n_labels]`` those of pixels labelled below ``n_labels`` (255: unlabelled), in
+        the caller's Gaussian order, as int64 device tensors.  ``votes`` / ``seen``: a tensor is ACCUMULATED into (zero it
+        once, lift many batches), ``None`` allocates a zeroed one, ``False`` leaves that output out (not both).  Integer sums:
+        the result does not depend on the order or the batching of the views.  The context's current group poses apply; a
+        scene with meshes is refused (``clear_meshes`` first).  Blocking."""
+        keep, pV, pK, _, C, W, H = self._views(viewmats, Ks, (0.0, 0.0, 0.0), width, height, True)
+        G = int(n_labels)
+        if isinstance(labels, torch.Tensor):
+            lab = labels.detach().to(device=self.device, dtype=torch.uint8).contiguous()
+        else:
+            lab = torch.from_numpy(np.ascontiguousarray(np.asarray(labels, dtype=np.uint8))).to(self.device)
+        if lab.numel() != C * H * W:
+            raise ValueError(f"labels must be [{C},{H},{W}], got {tuple(lab.shape)}")
+        if votes is False and seen is False:
+            raise ValueError("lift_labels: votes and seen are both left out")
+        res: Dict[str, torch.Tensor] = {}
+        if votes is not False:
+            res["votes"] = self._lift_buffer(votes, (self.n, max(G, 0)), "votes")
+        if seen is not False:
+            res["seen"] = self._lift_buffer(seen, (self.n,), "seen")
+        stream = self._stream()   # (the frames run behind what this stream holds: the label copy, the zeroing)
+        rc = self._L.sas_lift_labels(self._ctx, C, pV, pK, W, H, lab.data_ptr(), G, _flags(True, fast_exp=fast_exp, timing=timing),
+                                     res["votes"].data_ptr() if "votes" in res else None,
+                                     res["seen"].data_ptr() if "seen" in res else None, stream)
+        if rc != 0:
+            self._check(rc, "sas_lift_labels")
         self._in_flight(True)
         return res
 

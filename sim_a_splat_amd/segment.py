@@ -115,6 +115,50 @@ def segment_robot(means, urdf_path, joint_config, icp_transformation, robot_desc
     return link_masks_from_meshes(means, meshes, transforms, **kw)
 
 
+def masks_from_votes(votes, seen, names: Sequence[str], *, min_share: float = 0.5, min_seen: int = 0) -> Dict[str, np.ndarray]:
+    """``{name: bool[N]}`` from the sums of ``Rasterizer.lift_labels``: ``votes [N,G]`` and ``seen [N]`` (int64; arrays or tensors),
+    ``names [G]``.  Gaussian ``i`` belongs to label ``g`` when ``g`` is the lowest index that reaches ``max_k votes[i,k]`` and
+    ``votes[i,g] >= min_share * seen[i]``, ``seen[i] > min_seen`` and ``votes[i,g] > 0``: a Gaussian no labelled pixel showed, or
+    one seen mostly through unlabelled pixels, belongs to nobody.  The masks are disjoint by construction and are what
+    ``io.save_link_masks``, ``write_masks_dir`` and ``SplatHandler.from_arrays(link_masks=...)`` take.  For objects without a mesh
+    (the masks of ``segment_robot`` need one): label a few images, lift them, threshold here."""
+    v = np.asarray(_host(votes), np.int64)
+    s = np.asarray(_host(seen), np.int64).reshape(-1)
+    names = list(names)
+    if v.ndim != 2 or v.shape[0] != s.shape[0] or v.shape[1] != len(names):
+        raise ValueError(f"votes must be [N,{len(names)}] beside seen [N], got {list(v.shape)} and {list(s.shape)}")
+    if len(set(names)) != len(names):
+        raise ValueError("label names must be distinct")
+    if not names:
+        return {}
+    arg = v.argmax(axis=1)   # (the first index of the maximum: ties go to the lowest label)
+    top = v[np.arange(len(s)), arg]
+    own = (top > 0) & (s > int(min_seen)) & (top >= float(min_share) * s)
+    return {name: own & (arg == g) for g, name in enumerate(names)}
+
+
+def lift_label_views(rasterizer, viewmats, Ks, W: int, H: int, label_images, n_labels: int, views_per_call: int = 8):
+    """``Rasterizer.lift_labels`` over a long list of views, ``views_per_call`` at a time, into ONE pair of buffers: returns
+    ``{"votes": int64 [N,n_labels], "seen": int64 [N]}`` (device tensors).  ``viewmats [C,4,4]``, ``Ks [C,3,3]``,
+    ``label_images [C,H,W]`` uint8 (an array, a tensor, or a sequence of ``[H,W]`` images).  Integer sums: the result does not
+    depend on ``views_per_call``."""
+    V = np.asarray(_host(viewmats), np.float32).reshape(-1, 4, 4)
+    K = np.asarray(_host(Ks), np.float32).reshape(-1, 3, 3)
+    C = V.shape[0]
+    if K.shape[0] != C or len(label_images) != C:
+        raise ValueError(f"{C} view matrices, {K.shape[0]} intrinsics, {len(label_images)} label images")
+    if C == 0 or views_per_call < 1:
+        raise ValueError("lift_label_views needs at least one view and views_per_call >= 1")
+    out = None
+    for a in range(0, C, int(views_per_call)):
+        b = min(C, a + int(views_per_call))
+        lab = label_images[a:b]
+        if not hasattr(lab, "shape"):   # a sequence of images
+            lab = np.stack([np.asarray(_host(x), np.uint8) for x in lab])
+        out = rasterizer.lift_labels(V[a:b], K[a:b], W, H, lab, n_labels, **(out or {}))
+    return out
+
+
 def load_means(path) -> np.ndarray:
     """Gaussian centres [N,3] of a scene file: an ``.npy`` of centres, or whatever ``GSplatLoader.from_path`` reads."""
     p = Path(path)
