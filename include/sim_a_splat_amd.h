@@ -311,6 +311,46 @@ int sas_match_points(sas_ctx *ctx, int64_t n_source, const float *source, int64_
                      void *stream);
 
 /*
+ * Fixed-size point clouds from depth frames: the pixels of n_views same-sized views are unprojected, moved into an output frame,
+ * cropped, thinned on a voxel grid and cut to n_points points per cloud by farthest-point sampling, with colour and label.  The
+ * consumer behind sas_render_batch_labels: depth, rgb8 and labels are read where they are.  DESIGN.md 3, "Point clouds".
+ *   depth       [n_views,H,W] f32 DEVICE
+ *   rgb8        [n_views,H,W,3] u8 DEVICE or NULL;  labels  [n_views,H,W] u8 DEVICE or NULL
+ *   Ks          [n_views,9] HOST, row-major (fx = K[0], cx = K[2], fy = K[4], cy = K[5]), finite, fx and fy > 0
+ *   transform   [n_views,12] HOST, row-major A|t, camera -> output frame, any finite affine map; NULL = identity
+ *   cloud       [n_views] HOST, the cloud in [0,n_clouds) a view feeds; NULL: every view feeds cloud 0
+ *   keep        [256] HOST or NULL: with labels, a pixel is looked at only if keep[labels[p]] != 0
+ *   bounds      [6] HOST lo[3], hi[3] (lo <= hi) or NULL;  voxel >= 0 (0: no grid; > 0 needs bounds);  stride >= 1
+ *   flags       SAS_TIMING only: sas_stage_times then reads the call's kernels, k_cloud_mark as SAS_T_PROJECT, the compaction as
+ *               SAS_T_SCATTER, k_cloud_fps as SAS_T_BLEND, all of them as SAS_T_TOTAL (the other slots 0)
+ *   points      [n_clouds,n_points,3] f32, index [n_clouds,n_points] i32, colors [n_clouds,n_points,3] u8 (needs rgb8), labels_out
+ *               [n_clouds,n_points] u8 (needs labels), count [n_clouds] i32: DEVICE, in pick order; any but index may be NULL
+ * Per pixel, flat index p = (c H + v) W + u, all arithmetic float32 with nothing fused:
+ *   stride      only u % stride == 0 and v % stride == 0 are looked at
+ *   candidate   d = depth[p] with d > 0 and d < INFINITY (a NaN, 0, a negative and Inf drop out), and the keep rule
+ *   camera      x = ((float)u - cx) d / fx, y = ((float)v - cy) d / fy, z = d: the bits of sas_render_rgbd's points
+ *   output      w_k = ((A_k0 x + A_k1 y) + A_k2 z) + t_k; a candidate with a non-finite w drops out
+ *   crop        with bounds: lo_k <= w_k <= hi_k for every k
+ *   voxel grid  n_k = max(1, (int)ceilf((hi_k - lo_k) / voxel)), n_x n_y n_z <= 2^24; cell i_k = min((int)floorf((w_k - lo_k) /
+ *               voxel), n_k - 1); of a cloud's candidates in one cell the one with the lowest p survives
+ *   order       a cloud's survivors sorted by p have ranks 0 .. M - 1; count = M
+ *   sampling    pick 0 is rank 0; dist_i starts at +inf; after a pick s, dist_i = fminf(dist_i, (dx dx + dy dy) + dz dz), d = w_i -
+ *               w_s; the next pick is the unpicked survivor with the largest dist, among equals the lowest rank; min(n_points, M)
+ *               picks.  Rows beyond them are padding: points 0, index -1, colors 0, labels_out 255
+ * A cloud's result depends on its own views' pixels only; the first K' rows of a K-point result are the K'-point result; two calls
+ * return the same bytes.  No scene is required and nothing else the context stores is touched.  Frames in flight are completed
+ * first; the call returns with the outputs in place (`stream`: the caller's, behind whose pending work the inputs are read).
+ * SAS_ERR_INVALID: a negative size, an image size <= 0 or n_views H W > 2^31 - 256 (n_views > 65535), n_points < 0, stride < 1,
+ * n_clouds < 1, a cloud[v] out of range, a non-finite transform or K entry, fx or fy not > 0, lo_k > hi_k, a NaN, infinite or negative
+ * voxel, voxel > 0 without bounds, a grid of more than 2^24 cells, a missing depth, Ks or index, colors without rgb8, labels_out
+ * without labels, any other flag.  n_points == 0 and n_views == 0 are SAS_OK (no view: every count 0, all rows padding).
+ */
+int sas_sample_points(sas_ctx *ctx, int n_views, int width, int height, const float *depth, const uint8_t *rgb8,
+                      const uint8_t *labels, const float *Ks, const float *transform, const int32_t *cloud, int n_clouds,
+                      const uint8_t *keep, const float *bounds, float voxel, int stride, int n_points, unsigned flags,
+                      float *points, int32_t *index, uint8_t *colors, uint8_t *labels_out, int32_t *count, void *stream);
+
+/*
  * Render n_views views of the same size in one call.  Serves the per-camera loops of
  * SplatHandler.render / SplatEnvWrapper.render (splat_handler.py:337-345, splat_env_wrapper.py:147-158).
  *   viewmats [n_views,16], Ks [n_views,9] host arrays; outputs are [n_views,H,W,...] device arrays

@@ -238,6 +238,7 @@ struct sas_ctx : Settings {
     DevBuf mesh_feat;        // per-triangle feature rows (sas_scene_mesh_features): [chunks][nt][SAS_FEAT_K], feat_c channels
     DevBuf query_pts, query_tri, query_mesh, query_list, query_count;   // scratch of sas_query_meshes (SasQuery)
     DevBuf match_src, match_tgt, match_keys, match_index, match_dist2, match_partial;   // scratch of sas_match_points (SasMatch)
+    DevBuf cloud_par, cloud_grid, cloud_cand, cloud_blk, cloud_rows, cloud_dist, cloud_count;   // scratch of sas_sample_points (SasCloud)
     int match_cus = 0;   // compute units of the device, asked once (the slice count of sas_match_points)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
     // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
@@ -1778,6 +1779,138 @@ int sas_match_points(sas_ctx *c, int64_t n_source, const float *source, int64_t 
     return SAS_OK;
 }
 
+int sas_sample_points(sas_ctx *c, int n_views, int width, int height, const float *depth, const uint8_t *rgb8, const uint8_t *labels,
+                      const float *Ks, const float *transform, const int32_t *cloud, int n_clouds, const uint8_t *keep,
+                      const float *bounds, float voxel, int stride, int n_points, unsigned flags, float *points, int32_t *index,
+                      uint8_t *colors, uint8_t *labels_out, int32_t *count, void *stream)
+{
+    if (!c) return SAS_ERR_INVALID;
+    const char *who = "sas_sample_points";
+    const int C = n_views, E = n_clouds, K = n_points;
+    if (flags & ~SAS_TIMING) return fail(c, SAS_ERR_INVALID, "%s: flags 0x%x not accepted (SAS_TIMING; blocking only)", who, flags);
+    if (C < 0 || C > 65535) return fail(c, SAS_ERR_INVALID, "%s: n_views %d out of [0,65535]", who, C);
+    if (E < 1) return fail(c, SAS_ERR_INVALID, "%s: n_clouds %d, at least one is needed", who, E);
+    if (K < 0) return fail(c, SAS_ERR_INVALID, "%s: n_points %d is negative", who, K);
+    if (stride < 1) return fail(c, SAS_ERR_INVALID, "%s: stride %d, must be >= 1", who, stride);
+    if ((long long)E * std::max(K, 1) > 0x7fffff00ll) return fail(c, SAS_ERR_INVALID, "%s: %d clouds of %d points are too many", who, E, K);
+    if (C > 0 && (width <= 0 || height <= 0)) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
+    if (C > 0 && (long long)C * height * width > 0x7fffffffll - 256)
+        return fail(c, SAS_ERR_INVALID, "%s: %d views of %dx%d are more than 2^31 - 256 pixels", who, C, width, height);
+    if (C > 0 && (!depth || !Ks)) return fail(c, SAS_ERR_INVALID, "%s: depth and Ks are required", who);
+    if (K > 0 && !index) return fail(c, SAS_ERR_INVALID, "%s: the index output is required", who);
+    if (colors && !rgb8) return fail(c, SAS_ERR_INVALID, "%s: colors without rgb8", who);
+    if (labels_out && !labels) return fail(c, SAS_ERR_INVALID, "%s: labels_out without labels", who);
+    if (!(voxel >= 0.0f) || !(voxel < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: voxel %g, must be finite and >= 0", who, (double)voxel);
+    if (voxel > 0.0f && !bounds) return fail(c, SAS_ERR_INVALID, "%s: a voxel grid needs bounds", who);
+    SasCloud q{};
+    q.cells = 0;
+    for (int k = 0; bounds && k < 3; ++k) {
+        q.lo[k] = bounds[k];
+        q.hi[k] = bounds[3 + k];
+        if (!(q.lo[k] <= q.hi[k])) return fail(c, SAS_ERR_INVALID, "%s: bounds lo[%d] = %g, hi[%d] = %g", who, k, (double)q.lo[k], k, (double)q.hi[k]);
+    }
+    q.has_bounds = bounds != nullptr;
+    q.voxel = voxel;
+    if (voxel > 0.0f) {
+        q.cells = 1;
+        for (int k = 0; k < 3; ++k) {
+            const float cells = ceilf((q.hi[k] - q.lo[k]) / voxel);   // float32, as the contract has it
+            if (!(cells <= 16777216.0f)) return fail(c, SAS_ERR_INVALID, "%s: the voxel grid is too large along axis %d", who, k);
+            q.n[k] = std::max(1, (int)cells);
+            q.cells *= q.n[k];
+            if (q.cells > (1ll << 24))
+                return fail(c, SAS_ERR_INVALID, "%s: a voxel grid of more than 2^24 cells (%d x %d x ...)", who, q.n[0], q.n[1]);
+        }
+    }
+    for (int v = 0; v < C; ++v) {
+        const float *Kv = Ks + 9 * v;
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(Kv[k])) return fail(c, SAS_ERR_INVALID, "%s: Ks[%d][%d] = %g is not finite", who, v, k, (double)Kv[k]);
+        if (!(Kv[0] > 0.0f) || !(Kv[4] > 0.0f)) return fail(c, SAS_ERR_INVALID, "%s: view %d: fx = %g, fy = %g must be > 0", who, v, (double)Kv[0], (double)Kv[4]);
+        for (int k = 0; transform && k < 12; ++k)
+            if (!std::isfinite(transform[12 * v + k]))
+                return fail(c, SAS_ERR_INVALID, "%s: transform[%d][%d] = %g is not finite", who, v, k, (double)transform[12 * v + k]);
+        if (cloud && (cloud[v] < 0 || cloud[v] >= E)) return fail(c, SAS_ERR_INVALID, "%s: cloud[%d] = %d out of [0,%d)", who, v, cloud[v], E);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;
+    q.C = C; q.E = E; q.W = width; q.H = height; q.stride = stride; q.K = K;
+    q.Ws = C > 0 ? (width + stride - 1) / stride : 0;
+    q.S = C > 0 ? (long long)q.Ws * ((height + stride - 1) / stride) : 0;
+    q.n_rows = (long long)C * q.S;
+    q.n_pix = (long long)C * height * width;
+    q.bpv = (int)((q.S + 255) / 256);
+    q.n_blocks = (long long)C * q.bpv;
+    q.n_grid = (long long)E * q.cells;
+    // the per-view rows, the clouds' first rows and the keep table: one host block, one copy
+    const size_t off_base = sizeof(SasCloudView) * (size_t)C, off_keep = off_base + sizeof(long long) * (size_t)E;
+    std::vector<unsigned char> par(off_keep + 256);
+    SasCloudView *view = reinterpret_cast<SasCloudView *>(par.data());
+    long long *base = reinterpret_cast<long long *>(par.data() + off_base);
+    std::vector<long long> views_of(E, 0);
+    for (int v = 0; v < C; ++v) ++views_of[cloud ? cloud[v] : 0];
+    long long first = 0;
+    for (int e = 0; e < E; ++e) { base[e] = first; first += views_of[e] * q.S; }
+    for (int v = 0; v < C; ++v) {
+        SasCloudView &V = view[v];
+        const float *Kv = Ks + 9 * v;
+        V.fx = Kv[0]; V.fy = Kv[4]; V.cx = Kv[2]; V.cy = Kv[5];
+        for (int k = 0; k < 3; ++k) {
+            for (int j = 0; j < 3; ++j) V.A[3 * k + j] = transform ? transform[12 * v + 4 * k + j] : (k == j ? 1.0f : 0.0f);
+            V.t[k] = transform ? transform[12 * v + 4 * k + 3] : 0.0f;
+        }
+        V.cloud = cloud ? cloud[v] : 0;
+        V.pad = 0;
+        V.base = base[V.cloud];
+    }
+    const bool use_keep = keep && labels;
+    if (use_keep) std::copy(keep, keep + 256, par.data() + off_keep);
+    int rc;
+    const size_t rows = (size_t)std::max(q.n_rows, 1ll), blocks = (size_t)std::max(q.n_blocks, 1ll);
+    if ((rc = ensure(c, c->cloud_par, par.size()))) return rc;
+    if ((rc = ensure(c, c->cloud_grid, sizeof(unsigned) * (size_t)std::max(q.n_grid, 1ll)))) return rc;
+    if ((rc = ensure(c, c->cloud_cand, sizeof(float4) * rows))) return rc;
+    if ((rc = ensure(c, c->cloud_blk, sizeof(unsigned) * 2 * blocks))) return rc;
+    if ((rc = ensure(c, c->cloud_rows, sizeof(float4) * rows))) return rc;
+    if ((rc = ensure(c, c->cloud_dist, sizeof(float) * rows))) return rc;
+    if ((rc = ensure(c, c->cloud_count, sizeof(int) * (size_t)E))) return rc;
+    HIP_TRY(c, hipMemcpy(c->cloud_par.p, par.data(), par.size(), hipMemcpyHostToDevice));
+    unsigned char *dpar = (unsigned char *)c->cloud_par.p;
+    q.depth = depth; q.rgb8 = rgb8; q.labels = labels;
+    q.view = reinterpret_cast<const SasCloudView *>(dpar);
+    q.cloud_base = reinterpret_cast<const long long *>(dpar + off_base);
+    q.keep = use_keep ? dpar + off_keep : nullptr;
+    q.grid = (unsigned *)c->cloud_grid.p;
+    q.cand = (float4 *)c->cloud_cand.p;
+    q.blk_count = (unsigned *)c->cloud_blk.p;
+    q.blk_off = q.blk_count + blocks;
+    q.rows = (float4 *)c->cloud_rows.p;
+    q.dist = (float *)c->cloud_dist.p;
+    q.m_count = (int *)c->cloud_count.p;
+    q.points = points; q.index = index; q.colors = colors; q.labels_out = labels_out; q.count = count;
+    hipStream_t st = (hipStream_t)stream;
+    if (q.n_grid > 0) HIP_TRY(c, hipMemsetAsync(q.grid, 0xff, sizeof(unsigned) * (size_t)q.n_grid, st));
+    Event ev[4];
+    hipEvent_t evh[4];
+    if (flags & SAS_TIMING)
+        for (int k = 0; k < 4; ++k) {
+            HIP_TRY(c, hipEventCreate(ev[k].put()));
+            evh[k] = ev[k];
+        }
+    sas_launch_cloud(st, q, (flags & SAS_TIMING) ? evh : nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "point cloud: %s", hipGetErrorString(e));
+    if (flags & SAS_TIMING) {
+        std::fill(c->stage_ms, c->stage_ms + SAS_T_COUNT, 0.0f);
+        (void)hipEventElapsedTime(&c->stage_ms[SAS_T_PROJECT], evh[0], evh[1]);
+        (void)hipEventElapsedTime(&c->stage_ms[SAS_T_SCATTER], evh[1], evh[2]);
+        (void)hipEventElapsedTime(&c->stage_ms[SAS_T_BLEND], evh[2], evh[3]);
+        (void)hipEventElapsedTime(&c->stage_ms[SAS_T_TOTAL], evh[0], evh[3]);
+    }
+    return SAS_OK;
+}
+
 int sas_render_rgbd(sas_ctx *c, const float *viewmat, const float *K, int width, int height, const float *background,
                     unsigned flags, const float *max_depth, float *rgb, float *alpha, float *depth, float *points,
                     uint8_t *mask, void *stream)
@@ -2015,16 +2148,18 @@ extern "C" int sas_debug_bounds_tiles(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_mesh(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_query(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_match(unsigned long long *out, int reset);
+extern "C" int sas_debug_bounds_cloud(unsigned long long *out, int reset);
 /* Bounds-checked build only: out[0] = guarded accesses found out of range since the last reset (they were
  * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none). */
 int sas_debug_bounds(unsigned long long *out, int reset)
 {
-    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0};
+    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0};
     if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset) ||
-        sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset) || sas_debug_bounds_match(p, reset))
+        sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset) || sas_debug_bounds_match(p, reset) ||
+        sas_debug_bounds_cloud(s, reset))
         return SAS_ERR_HIP;
-    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : p)));
-    out[0] = a[0] + b[0] + m[0] + q[0] + p[0];
+    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : s))));
+    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0];
     out[1] = first[1]; out[2] = first[2]; out[3] = first[3];
     return SAS_OK;
 }

@@ -1,4 +1,4 @@
-// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -362,3 +362,44 @@ struct SasMatch {
 };
 // keys <- slice minima, index / dist2 / partial <- the merge, moments <- the partial rows in workgroup order
 void sas_launch_match(hipStream_t st, const SasMatch &m);
+
+// Point clouds (sas_sample_points; DESIGN.md 3, "Point clouds").  Every kernel takes the whole call by value; the per-view and per-cloud
+// rows live in one device block beside the keep table.
+#define SAS_CLOUD_RESIDENT 16384   // survivors k_cloud_fps keeps in registers: 16 per lane of its 1024 (4 registers each; 128 are a lane's share)
+struct SasCloudView {
+    float fx, fy, cx, cy;
+    float A[9], t[3];      // camera -> output frame
+    int cloud, pad;
+    long long base;        // first row of its cloud in rows / dist (SasCloud::cloud_base[cloud])
+};
+struct SasCloud {
+    const float *depth;         // [C,H,W]
+    const uint8_t *rgb8;        // [C,H,W,3] or nullptr
+    const uint8_t *labels;      // [C,H,W] or nullptr
+    const SasCloudView *view;   // [C] device
+    const long long *cloud_base;   // [E] device: S times the views of the clouds before
+    const uint8_t *keep;        // [256] device, or nullptr
+    unsigned *grid;             // [E][cells] lowest p per cell, 0xffffffff: empty (voxel > 0)
+    float4 *cand;               // [C S] (w, cell bits; 0xffffffff: no candidate) per strided pixel
+    unsigned *blk_count, *blk_off;   // [C bpv] survivors per block of k_cloud_compact, and where its first goes within its cloud
+    float4 *rows;               // [C S] survivors (w, bits(p)), cloud e's from cloud_base[e], in p order
+    float *dist;                // [C S] running distances of k_cloud_fps<false>, laid out as rows
+    int *m_count;               // [E] survivors per cloud
+    float *points;              // outputs (device): [E,K,3] or nullptr
+    int32_t *index;             // [E,K]
+    uint8_t *colors;            // [E,K,3] or nullptr
+    uint8_t *labels_out;        // [E,K] or nullptr
+    int32_t *count;             // [E] or nullptr
+    long long S;                // strided pixels per view, Ws * Hs
+    long long n_rows;           // C S
+    long long n_pix;            // C H W
+    long long n_blocks;         // C bpv
+    long long cells, n_grid;    // nx ny nz, E cells
+    int bpv;                    // ceil(S / 256)
+    int C, E, W, H, Ws, stride, K;
+    int has_bounds;
+    int n[3];
+    float lo[3], hi[3], voxel;
+};
+// ev (optional, 4 events): stamped in front of k_cloud_mark, k_cloud_compact, k_cloud_fps and behind the last kernel
+void sas_launch_cloud(hipStream_t st, const SasCloud &q, hipEvent_t *ev);

@@ -37,13 +37,23 @@ class SplatEnvWrapper:
     def __init__(self, env, splat_assets_path: Optional[str] = None, match_object_name: Optional[str] = None,
                  splat_config_name: Optional[str] = None, task_assets_path: Optional[str] = None,
                  task_assets_name: Optional[str] = None, *, splat_handler: Optional[SplatHandler] = None, device=0,
-                 meshes=(), obs_modes=("rgb",)):
+                 meshes=(), obs_modes=("rgb",), point_cloud: Optional[dict] = None):
         """``splat_handler`` (keyword-only, not in the reference): a handler built elsewhere -- from arrays, or
         shared between vectorised envs -- instead of loading the assets named by the path arguments.
         ``obs_modes`` (keyword-only): what every camera adds to the observation -- ``"rgb"`` (``camera_i``, the reference's
         entry), ``"depth"`` (``camera_i_depth`` float32 [1,H,W]) and ``"segmentation"`` (``camera_i_segmentation`` uint8
-        [1,H,W], labels by ``ch.row_names()``); the default leaves the observation as the reference's."""
+        [1,H,W], labels by ``ch.row_names()``); the default leaves the observation as the reference's.  ``"pointcloud"`` adds ONE
+        entry for all cameras, ``point_cloud`` float32 [K,6] (xyz, then rgb in 0..1; padding rows zero), configured by
+        ``point_cloud=dict(n_points=..., bounds=..., voxel_size=..., stride=..., keep=..., frame="robot")``
+        (``SplatHandler.render_point_cloud``); the cameras must then be one size."""
         self.obs_modes = _checked_modes(obs_modes, "obs_modes")
+        if "pointcloud" in self.obs_modes:
+            if not point_cloud or "n_points" not in point_cloud:
+                raise ValueError("obs_modes has 'pointcloud': point_cloud=dict(n_points=..., ...) is required")
+        elif point_cloud is not None:
+            raise ValueError("point_cloud= given without 'pointcloud' among obs_modes")
+        self._point_cloud = dict(point_cloud) if point_cloud else None
+        self._camera_modes = tuple(m for m in self.obs_modes if m != "pointcloud")
         self.env = env
         self._device = device
         self._meshes = tuple(meshes)   # SplatHandler(meshes=...): task / robot meshes in the frames
@@ -131,7 +141,12 @@ class SplatEnvWrapper:
     # -- :132-138 ------------------------------------------------------------------------------------------
     def _get_obs(self) -> Dict[str, np.ndarray]:
         obs = self.unwrapped._get_obs()
-        if self.obs_modes == ("rgb",):      # the reference's observation, straight from render (as CameraRig.get_obs): no dict per camera
+        if self._point_cloud is not None:      # one look at the cameras serves the frames and the cloud
+            cams = self._render_cameras()
+            if self._camera_modes:
+                obs.update(camera_obs_dict(self.splat_handler.render_observations(self.ch, *cams, self._camera_modes), self._camera_modes))
+            obs["point_cloud"] = self.splat_handler.point_cloud_obs(self.ch, *cams, **self._point_cloud)
+        elif self.obs_modes == ("rgb",):      # the reference's observation, straight from render (as CameraRig.get_obs): no dict per camera
             obs.update({f"camera_{i}": img.transpose(2, 0, 1) for i, img in enumerate(self.render())})   # np.moveaxis(img, -1, 0): the same view
         else:
             obs.update(camera_obs_dict(self.render_observations(self.obs_modes), self.obs_modes))

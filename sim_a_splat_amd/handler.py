@@ -392,7 +392,41 @@ class SplatHandler:
         return [chs.get_segmentation(int(s[0]), int(s[1]), wxyz=w, position=p)["labels"].cpu().numpy()
                 for (w, p), s in zip(_cameras(chs, cam_poses), render_size)]
 
-    OBS_MODES = ("rgb", "depth", "segmentation")
+    def robot_frame(self) -> np.ndarray:
+        """4x4 float64, splat scene -> the robot's metric frame: the inverse of the ICP similarity ``x_scene = s Ri x_robot + ti``
+        (``poses.decompose_icp``), ``x_robot = Ri^T (x_scene - ti) / s``."""
+        F = np.eye(4)
+        F[:3, :3] = self.Ri.T / self.scale_factor
+        F[:3, 3] = -(self.Ri.T @ self.ti) / self.scale_factor
+        return F
+
+    def render_point_cloud(self, chs, cam_poses, render_size, n_points: int, *, frame="scene", bounds=None, voxel_size: float = 0.0,
+                           stride: int = 1, keep=None, **kw):
+        """One fixed-size point cloud from all cameras of a step (``SplatScene.get_point_clouds``): ``n_points`` rows by
+        farthest-point sampling over the cameras' depth pixels.  ``frame="scene"``: the splat's own frame; ``"robot"``: the
+        robot's metric frame (``robot_frame()``: the inverse of the handler's ICP similarity) -- ``bounds`` and ``voxel_size`` are
+        then metres of the simulator; a 4x4 array: that map from the scene.  The cameras must be one size (ValueError).  Returns
+        the device tensors of ``get_point_clouds``."""
+        cam = _cameras(chs, cam_poses)
+        sizes = {(int(s[0]), int(s[1])) for s in render_size[:len(cam)]}
+        if len(sizes) != 1:
+            raise ValueError(f"render_point_cloud needs cameras of one size, got {sorted(sizes)}")
+        if isinstance(frame, str):
+            if frame not in ("scene", "robot"):
+                raise ValueError(f"frame must be 'scene', 'robot' or a 4x4 matrix, got {frame!r}")
+            frame = self.robot_frame() if frame == "robot" else None
+        (H, W), = sizes
+        return chs.get_point_clouds(H, W, cam, int(n_points), bounds=bounds, voxel_size=voxel_size, stride=stride, keep=keep, frame=frame, **kw)
+
+    def point_cloud_obs(self, chs, cam_poses, render_size, n_points: int, **cfg) -> np.ndarray:
+        """``render_point_cloud`` as an observation entry: float32 ``[n_points,6]``, xyz then rgb in 0..1; padding rows are zero."""
+        o = self.render_point_cloud(chs, cam_poses, render_size, n_points, **cfg)
+        out = np.zeros((int(n_points), 6), np.float32)
+        out[:, :3] = o["points"][0].cpu().numpy()
+        out[:, 3:] = o["colors"][0].cpu().numpy().astype(np.float32) / np.float32(255.0)
+        return out
+
+    OBS_MODES = ("rgb", "depth", "segmentation", "pointcloud")
 
     def render_observations(self, chs, cam_poses, render_size, modes=("rgb",)) -> List[Dict[str, np.ndarray]]:
         """``render`` for several modalities: one dict per camera with the ``modes`` asked for -- ``rgb`` uint8 ``[H,W,3]`` (the
@@ -400,6 +434,8 @@ class SplatHandler:
         seen) and ``segmentation`` uint8 ``[H,W]`` (``render_segmentation``'s labels).  Cameras of equal size are one call
         (``SplatScene.get_observations``: label frames); ``modes=("rgb",)`` alone goes through ``render``."""
         modes = _checked_modes(modes)
+        if "pointcloud" in modes:
+            raise ValueError("'pointcloud' is one cloud of all cameras, not a per-camera mode: render_point_cloud")
         if set(modes) <= {"rgb"}:
             return [{m: img for m in modes} for img in self.render(chs, cam_poses, render_size)]
         cam = _cameras(chs, cam_poses)

@@ -57,7 +57,50 @@ MESH_QUERY_CHUNK = _capi.SAS_QUERY_CHUNK   # triangles query_meshes' kernel stag
 MAX_QUERY_MESHES = 256
 MATCH_CHUNK = _capi.SAS_MATCH_CHUNK   # targets match_points' kernel stages at a time: target sizes around it take its chunk edges
 MATCH_MOMENTS = 18
+CLOUD_RESIDENT = _capi.SAS_CLOUD_RESIDENT   # survivors per cloud sample_point_cloud's sampling kernel keeps in registers: beyond it they stream
 LIFT_ONE = _capi.SAS_LIFT_ONE   # 2**32: the fixed-point unit of lift_labels' votes (a weight of 1.0)
+
+
+def cloud_transforms(viewmats, frame=None) -> np.ndarray:
+    """Camera-to-output-frame maps of ``sample_point_cloud``: ``[C,12]`` float32 rows ``A|t``, the rigid inverse of every world-to-camera
+    ``viewmats [C,4,4]`` (``R^T | -R^T t``, in float64) with ``frame`` (4x4, world to output frame; any affine map) multiplied on from
+    the left, rounded to float32 once.  ValueError on a wrong shape."""
+    V = np.asarray(_host(viewmats), dtype=np.float64)
+    if V.ndim != 3 or V.shape[1:] != (4, 4):
+        raise ValueError(f"viewmats must be [C,4,4], got {list(V.shape)}")
+    inv = np.zeros_like(V)
+    Rt = np.transpose(V[:, :3, :3], (0, 2, 1))
+    inv[:, :3, :3] = Rt
+    inv[:, :3, 3] = -np.einsum("cij,cj->ci", Rt, V[:, :3, 3])
+    inv[:, 3, 3] = 1.0
+    if frame is not None:
+        F = np.asarray(_host(frame), dtype=np.float64)
+        if F.shape != (4, 4):
+            raise ValueError(f"frame must be 4x4, got {list(F.shape)}")
+        inv = F[None] @ inv
+    return np.ascontiguousarray(inv[:, :3, :].reshape(-1, 12).astype(np.float32))
+
+
+def cloud_keep_table(keep_labels) -> Optional[np.ndarray]:
+    """The 256-byte keep table of ``sample_point_cloud`` from the labels to keep (integers in 0..255); None stays None."""
+    if keep_labels is None:
+        return None
+    ids = np.asarray(list(keep_labels), dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() > 255):
+        raise ValueError("keep_labels must be labels in 0..255")
+    table = np.zeros(256, np.uint8)
+    table[ids] = 1
+    return table
+
+
+def cloud_bounds(bounds) -> Optional[np.ndarray]:
+    """``bounds`` ((lo[3], hi[3]) or [2,3] / [6]) as the float32 ``lo, hi`` row of ``sample_point_cloud``; None stays None."""
+    if bounds is None:
+        return None
+    b = np.asarray(_host(bounds), dtype=np.float32)
+    if b.size != 6:
+        raise ValueError(f"bounds must be (lo[3], hi[3]), got shape {list(b.shape)}")
+    return np.ascontiguousarray(b.reshape(6))
 
 
 def pack_query_meshes(meshes) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -399,6 +442,72 @@ class Rasterizer:
                                              0 if slices is None else int(slices), index.data_ptr() if ns else None,
                                              dist2.data_ptr() if ns else None, moments.ctypes.data, self._stream()), "sas_match_points")
         return {"index": index, "dist2": dist2, "moments": moments}
+
+    def _device_image(self, a, dtype, count: int, name: str, shape) -> torch.Tensor:
+        """A per-pixel input of ``sample_point_cloud`` on this context's device: a device tensor of the right type as it is (read in
+        place), anything else converted and copied."""
+        if isinstance(a, torch.Tensor):
+            t = a.detach().to(device=self.device, dtype=dtype).contiguous()
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype={torch.float32: np.float32, torch.uint8: np.uint8}[dtype]))).to(self.device)
+        if t.numel() != count:
+            raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+        return t
+
+    @_locked
+    def sample_point_cloud(self, depth: ArrayLike, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int, n_points: int, *,
+                           rgb8: Optional[ArrayLike] = None, labels: Optional[ArrayLike] = None, keep_labels=None, bounds=None,
+                           voxel_size: float = 0.0, stride: int = 1, frame=None, clouds: Optional[Sequence[int]] = None,
+                           n_clouds: int = 1, timing: bool = False) -> Dict[str, torch.Tensor]:
+        """Fixed-size point clouds from the depth frames of C same-sized views (sas_sample_points; DESIGN.md 3, "Point clouds"):
+        ``depth [C,H,W]`` (or ``[C,H,W,1]``) float32 with ``viewmats [C,4,4]`` (world to camera) and ``Ks [C,3,3]``, optionally
+        ``rgb8 [C,H,W,3]`` and ``labels [C,H,W]`` uint8 -- device tensors are read where they are (the outputs of
+        ``render_batch_labels``), NumPy arrays are copied.  Every pixel with a depth in (0, inf) is unprojected and moved by
+        ``cloud_transforms(viewmats, frame)`` -- into the world, or with ``frame`` (4x4, world to output frame) beyond it --
+        kept if it lies within ``bounds`` ``(lo[3], hi[3])`` (inclusive) and, with ``labels`` and ``keep_labels`` (the labels to
+        keep), shows one of them; ``stride`` looks at every stride-th row and column only; ``voxel_size > 0`` keeps one point (the
+        lowest pixel index) per cell of a grid over ``bounds``.  View v feeds cloud ``clouds[v]`` of ``n_clouds`` (None: all feed
+        cloud 0).  Each cloud is cut to ``n_points`` by farthest-point sampling from its first survivor.  Returns device tensors
+        in pick order: ``points [E,K,3]`` float32, ``index [E,K]`` int32 (the flat pixel ``(c H + v) W + u``; -1 padding),
+        ``count [E]`` int32 (survivors before sampling) and, with the inputs, ``colors [E,K,3]`` uint8 and ``labels [E,K]`` uint8
+        (255 padding).  Deterministic; blocking; needs no scene.  ``timing``: ``stage_times()`` then holds the call's kernels
+        (project: marking, scatter: compaction, blend: sampling)."""
+        T = cloud_transforms(viewmats, frame)
+        C, W, H, K, E = T.shape[0], int(width), int(height), int(n_points), int(n_clouds)
+        Kc = np.ascontiguousarray(np.asarray(_host(Ks), dtype=np.float32)).reshape(-1)
+        if Kc.size != 9 * C:
+            raise ValueError(f"Ks must be [{C},3,3], got {Kc.size} values")
+        if K < 0 or E < 1 or W < 0 or H < 0:
+            raise ValueError(f"sample_point_cloud: n_points {K}, n_clouds {E}, size {W}x{H}")
+        if keep_labels is not None and labels is None:
+            raise ValueError("keep_labels needs labels")
+        keep = cloud_keep_table(keep_labels)
+        b = cloud_bounds(bounds)
+        cl = None
+        if clouds is not None:
+            cl = np.ascontiguousarray(np.asarray(clouds, dtype=np.int32).reshape(-1))
+            if cl.shape[0] != C:
+                raise ValueError(f"clouds must name one cloud per view ({C}), got {cl.shape[0]}")
+        d = self._device_image(depth, torch.float32, C * H * W, "depth", (C, H, W))
+        c8 = None if rgb8 is None else self._device_image(rgb8, torch.uint8, 3 * C * H * W, "rgb8", (C, H, W, 3))
+        lab = None if labels is None else self._device_image(labels, torch.uint8, C * H * W, "labels", (C, H, W))
+        dev = self.device
+        res = {"points": torch.empty((E, K, 3), dtype=torch.float32, device=dev), "index": torch.empty((E, K), dtype=torch.int32, device=dev),
+               "count": torch.empty((E,), dtype=torch.int32, device=dev)}
+        if c8 is not None:
+            res["colors"] = torch.empty((E, K, 3), dtype=torch.uint8, device=dev)
+        if lab is not None:
+            res["labels"] = torch.empty((E, K), dtype=torch.uint8, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        host = lambda a: a.ctypes.data if a is not None and a.size else None
+        stream = self._stream()   # (the call runs behind what this stream holds: the copies above)
+        rc = self._L.sas_sample_points(self._ctx, C, W, H, ptr(d), ptr(c8), ptr(lab), host(Kc), host(T), host(cl), E, host(keep), host(b),
+                                       float(voxel_size), int(stride), K, _capi.SAS_TIMING if timing else 0, ptr(res["points"]),
+                                       ptr(res["index"]), ptr(res.get("colors")), ptr(res.get("labels")), res["count"].data_ptr(), stream)
+        if rc != 0:
+            self._check(rc, "sas_sample_points")
+        self._in_flight(True)
+        return res
 
     @_locked
     def set_group_poses(self, Rt: ArrayLike) -> None:

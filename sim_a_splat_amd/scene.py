@@ -385,6 +385,48 @@ class SplatScene:
             return self._raster.render_batch_labels(V, K, int(width), int(height), self.background, min_alpha=min_alpha, want=tuple(want),
                                                     pose_sets=pose_sets, pose_set=pose_set)
 
+    def _keep_rows(self, keep) -> Optional[List[int]]:
+        """``keep`` of ``get_point_clouds`` -- row names (``row_names()``) or row indices -- as row indices; None stays None."""
+        if keep is None:
+            return None
+        names = self.row_names()
+        rows = []
+        for k in keep:
+            if isinstance(k, str):
+                if k not in names:
+                    raise ValueError(f"keep: no row named {k!r} (rows: {names})")
+                rows.append(names.index(k))
+            else:
+                if not 0 <= int(k) < len(names):
+                    raise ValueError(f"keep: row {int(k)} out of [0,{len(names)})")
+                rows.append(int(k))
+        return rows
+
+    def get_point_clouds(self, height: int, width: int, cam_poses, n_points: int, *, bounds=None, voxel_size: float = 0.0,
+                         stride: int = 1, keep=None, frame=None, pose_sets=None, pose_set=None, clouds=None, n_clouds: int = 1,
+                         fov: Optional[float] = None, min_alpha: float = 0.5) -> Dict[str, torch.Tensor]:
+        """Fixed-size point clouds of C same-sized cameras ``[(wxyz, position), ...]``: one label-frame call
+        (``Rasterizer.render_batch_labels`` with rgb8 and depth) and one sampling call (``Rasterizer.sample_point_cloud``) on its
+        device outputs -- nothing visits the host.  ``n_points`` per cloud by farthest-point sampling, in the world frame or,
+        with ``frame`` (4x4, world to output frame), beyond it; ``bounds`` ``(lo[3], hi[3])``, ``voxel_size`` and ``stride`` thin
+        the pixels first; ``keep``: the rows whose pixels count, by name (``row_names()``) or index.  ``pose_sets`` /
+        ``pose_set``: per-view pose sets; ``clouds [C]`` / ``n_clouds``: the cloud each camera feeds (vectorised envs: one cloud
+        per env).  Returns device tensors ``points [E,K,3]``, ``index [E,K]``, ``colors [E,K,3]``, ``labels [E,K]`` (row
+        indices; 255 padding), ``count [E]``, and ``frames``, the label-frame call's own outputs."""
+        V, K = self._views_and_Ks(int(height), int(width), *_camera_arrays(cam_poses), self._camera_or(fov=fov)[2])
+        with self.lock:
+            if not self._handles:
+                raise RuntimeError("point clouds need at least one splat group or mesh")
+            rows = self._keep_rows(keep)
+            self._sync()
+            o = self._raster.render_batch_labels(V, K, int(width), int(height), self.background, min_alpha=min_alpha,
+                                                 want=("rgb8", "depth"), pose_sets=pose_sets, pose_set=pose_set)
+            res = self._raster.sample_point_cloud(o["depth"], V, K, int(width), int(height), int(n_points), rgb8=o["rgb8"],
+                                                  labels=o["labels"], keep_labels=rows, bounds=bounds, voxel_size=voxel_size,
+                                                  stride=stride, frame=frame, clouds=clouds, n_clouds=n_clouds)
+            res["frames"] = o
+            return res
+
     def get_segmentations(self, height: int, width: int, cam_poses, fov: Optional[float] = None, pose_sets=None, pose_set=None,
                           min_alpha: float = 0.5) -> torch.Tensor:
         """``get_segmentation``'s ``labels`` for C same-sized cameras ``[(wxyz, position), ...]`` in one call: uint8 ``[C,H,W]`` on the
