@@ -2439,8 +2439,10 @@ struct LiftPayload {
     // one entry: the block's lanes hold the same Gaussian `idx` (they read the same queue slot)
     DEV void give(int idx, float vis) const
     {
-        // floorf(vis 2^32): the product is exact (a power of two), 0 <= vis < 1, and the conversion truncates
-        const unsigned q = (unsigned)(vis * 4294967296.0f);
+        // floorf(vis 2^32): the product is exact (a power of two), 0 <= vis < 1, and the conversion truncates.  A lane outside the
+        // image (label 256) gives nothing: it is parked at x = NaN with T = 1, which keeps it from every splat whose alpha falls
+        // with sigma, but a Gaussian with opacity NaN or +Inf has alpha fminf(0.999, .) = 0.999 at any sigma and would be seen by it
+        const unsigned q = label > 255 ? 0u : (unsigned)(vis * 4294967296.0f);
         if (!__ballot(q != 0u)) return;   // (uniform) nobody in the wave composited this entry
         const int lane = (int)(threadIdx.x & 63u), l16 = lane & 15, base = lane & 48;
         const bool ok = idx >= 0 && (long long)idx < n && SAS_IN(idx, n, 353);

@@ -8,7 +8,9 @@ Every index the kernels compute into the key buffers, the LDS queues / chunk / h
 records, the tile tables and the output images is tested on the device; a violation is counted and the
 access skipped.  After the whole GPU suite (all parity cases: ragged and empty inputs, overflow + regrow,
 coplanar fallback, launch groups, camera inside the cloud, the mesh frames of test_gpu_h_mesh_oracle.py -- tilted planes,
-the T-block among the splats, ragged sizes, 1920x1080 with thousands of triangles, the mesh fuzz seeds: codes 301, 302, 311 ...)
+the T-block among the splats, ragged sizes, 1920x1080 with thousands of triangles, the mesh fuzz seeds: codes 301, 302, 311 ...;
+the drawn observation cases of test_gpu_q_obs_fuzz.py: RGB-D tails, label frames, lift frames and point clouds on strips, odd cameras
+and poisoned scenes)
 the count must be zero.  With the product
 library these tests skip.
 """

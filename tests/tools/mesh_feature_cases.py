@@ -11,6 +11,7 @@ import numpy as np
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import mesh_cases as mc  # noqa: E402
 import oracle_fuzz as fz  # noqa: E402
+from obs_fuzz import label_rule  # noqa: E402
 
 EPS32 = 2.0 ** -24
 CHANNELS = (3, 9, 24)                    # one chunk of 8, a partial second chunk, three chunks
@@ -109,10 +110,7 @@ def moved_share(with_flag, without_flag, s):
 
 
 # ---- labels ----------------------------------------------------------------------------------------------------------------------
-def labels_of(weights, alpha, min_alpha=0.5):
-    """rasterizer.group_labels in NumPy: argmax over the rows (ties to the lowest), 255 where alpha < min_alpha."""
-    lab = np.argmax(weights, axis=-1).astype(np.int64)
-    return np.where(np.asarray(alpha).reshape(lab.shape) < min_alpha, 255, np.minimum(lab, 255)).astype(np.uint8)
+labels_of = label_rule   # rasterizer.group_labels in NumPy (obs_fuzz.py: the one text of the rule the label references share)
 
 
 def case_labels():

@@ -20,6 +20,9 @@ bit for bit (the arithmetic contract); the seeded pytest cases fix 
 
     python tests/tools/oracle_fuzz.py --meshes [n_seeds] [first_seed]
 
+The entry points this tool does not draw -- render_rgbd's points and mask, render_cameras_host, label frames, label lifting, point clouds --
+are drawn by tests/tools/obs_fuzz.py, from the recipes below (shape_scene, poison_scene, draw_strip, draw_camera).
+
 Test infrastructure: lives under tests/ because it calls the oracle (the checker)."""
 import sys
 from pathlib import Path
@@ -35,48 +38,76 @@ from sim_a_splat_amd.synthetic import (NERFSTUDIO_EVAL_BACKGROUND as BG, Camera,
 KEYS = ("rgb", "alpha", "depth", "rgb8")
 
 
-def draw_case(seed: int, poison_all: bool = False) -> dict:
-    rng = np.random.default_rng(77_000 + seed)
-    n = int(rng.choice([1, 7, 50, 800, 6000, 30000, 120000], p=[0.04, 0.06, 0.1, 0.25, 0.25, 0.2, 0.1]))
-    ls = float(rng.uniform(np.log(0.003), np.log(0.3)))
-    n_groups = int(rng.choice([0, 0, 0, 3, 3, 7, 7, 40, 200]))      # (40, 200: beyond the pose rows a launch carries in its arguments)
-    sc = make_scene(n, seed=88_000 + seed, log_scale_mean=ls, n_groups=n_groups)
+BAD_VALUES = np.array([np.nan, np.inf, -np.inf, 1e30, -1e30, 1e-30, 0.0, 3e6, 1e12, -1.0], np.float32)
+
+
+# ---- the recipes of a drawn case: draw_case below and tests/tools/obs_fuzz.py draw from them, each from generator streams of its own
+def shape_scene(rng, sc) -> None:
+    """Opacity bands, now and then depth planes (crowded buckets, ties) and everything in a few tiles (long lists); in place."""
     lo = float(rng.choice([0.004, 0.05, 0.5]))
     sc.opacities[:] = np.clip(sc.opacities, lo, min(1.0, lo * 20 + 0.01)).astype(np.float32)
     if rng.random() < 0.25:
         sc.means[:, 2] = np.round(sc.means[:, 2] * 4) / 4                    # depth planes: crowded buckets, ties
     if rng.random() < 0.15:
         sc.means *= np.float32(0.05)                                         # everything in a few tiles: long lists
+
+
+def draw_strip(rng, long_w=(1000, 4000), long_h=(1000, 3000)):
+    """(W, H) of a strip: one row or one column of tiles, thousands of pixels long."""
+    return (int(rng.integers(*long_w)), int(rng.integers(1, 17))) if rng.random() < 0.5 else (int(rng.integers(1, 17)), int(rng.integers(*long_h)))
+
+
+def poison_scene(rng, sc) -> None:
+    """Non-finite and absurd values in ~1 % of the Gaussians, in place: both sides must cull or clamp them the same way, and the
+    device must not leave its buffers (the bounds-checked build counts)."""
+    for arr in (sc.means, sc.scales, sc.quats, sc.opacities, sc.sh):
+        flat = arr.reshape(-1)
+        k = max(1, flat.size // 100)
+        flat[rng.integers(0, flat.size, size=k)] = BAD_VALUES[rng.integers(0, BAD_VALUES.size, size=k)]
+
+
+RADII = (0.3, 1.0, 3.0, 3.0, 6.0)                                            # 0.3 / 1.0: inside the cloud
+
+
+def draw_camera(rng, W: int, H: int, odd: list = None) -> Camera:
+    """One camera on a ring around the cloud, looking at its centre; one in ten is odd (``odd``, a list, is told which: it
+    receives True or False)."""
+    radius = float(rng.choice(RADII))
+    yaw, elev = float(rng.uniform(0, 2 * np.pi)), float(rng.uniform(-0.8, 0.8)) * radius
+    eye = (radius * np.sin(yaw), elev, radius * np.cos(yaw))
+    f = float(rng.uniform(0.4, 1.5)) * W
+    cx, cy = W / 2.0 + float(rng.uniform(-0.2, 0.2)) * W, H / 2.0 + float(rng.uniform(-0.2, 0.2)) * H
+    V = look_at_viewmat(eye)
+    is_odd = bool(rng.random() < 0.1)
+    if is_odd:                                                           # odd cameras: fish-eye-short or telescope-long focal lengths, the
+        f = float(rng.choice([0.03, 0.1, 8.0, 40.0])) * max(W, H)        # principal point outside the image, a view matrix that is not quite a rotation
+        cx, cy = float(rng.uniform(-1.0, 2.0)) * W, float(rng.uniform(-1.0, 2.0)) * H
+        V = V.copy(); V[:3, :3] *= np.float32(rng.uniform(0.97, 1.03))
+    if odd is not None:
+        odd.append(is_odd)
+    return Camera(V, intrinsics(f, f * float(rng.uniform(0.8, 1.25)), cx, cy), W, H)
+
+
+def draw_case(seed: int, poison_all: bool = False) -> dict:
+    rng = np.random.default_rng(77_000 + seed)
+    n = int(rng.choice([1, 7, 50, 800, 6000, 30000, 120000], p=[0.04, 0.06, 0.1, 0.25, 0.25, 0.2, 0.1]))
+    ls = float(rng.uniform(np.log(0.003), np.log(0.3)))
+    n_groups = int(rng.choice([0, 0, 0, 3, 3, 7, 7, 40, 200]))      # (40, 200: beyond the pose rows a launch carries in its arguments)
+    sc = make_scene(n, seed=88_000 + seed, log_scale_mean=ls, n_groups=n_groups)
+    shape_scene(rng, sc)
     deg = int(rng.choice([-1, 0, 1, 2, 3, 3, 3]))
     W, H = int(rng.integers(17, 420)), int(rng.integers(17, 300))
     if rng.random() < 0.05:                                                  # a strip: one row or one column of tiles, thousands of pixels long
-        W, H = (int(rng.integers(1000, 4000)), int(rng.integers(1, 17))) if rng.random() < 0.5 else (int(rng.integers(1, 17)), int(rng.integers(1000, 3000)))
+        W, H = draw_strip(rng)
     poisoned = bool(rng.random() < 0.08) or poison_all
     if rng.random() < 0.06:                                                  # now and then a large frame and a large scene
         W, H = int(rng.integers(640, 1921)), int(rng.integers(480, 1081))
         n = int(rng.choice([120000, 500000, 1000000]))
         sc = make_scene(n, seed=88_000 + seed, log_scale_mean=float(rng.uniform(np.log(0.004), np.log(0.03))), n_groups=n_groups)
-    if poisoned:     # non-finite and absurd values in ~1 % of the Gaussians: both sides must cull or clamp them the same way, and the
-        # device must not leave its buffers (the bounds-checked build counts)
-        bad_vals = np.array([np.nan, np.inf, -np.inf, 1e30, -1e30, 1e-30, 0.0, 3e6, 1e12, -1.0], np.float32)
-        for arr in (sc.means, sc.scales, sc.quats, sc.opacities, sc.sh):
-            flat = arr.reshape(-1)
-            k = max(1, flat.size // 100)
-            flat[rng.integers(0, flat.size, size=k)] = bad_vals[rng.integers(0, bad_vals.size, size=k)]
+    if poisoned:
+        poison_scene(rng, sc)
     n_views = int(rng.choice([1, 1, 2, 3]))
-    cams = []
-    for _ in range(n_views):
-        radius = float(rng.choice([0.3, 1.0, 3.0, 3.0, 6.0]))               # 0.3 / 1.0: inside the cloud
-        yaw, elev = float(rng.uniform(0, 2 * np.pi)), float(rng.uniform(-0.8, 0.8)) * radius
-        eye = (radius * np.sin(yaw), elev, radius * np.cos(yaw))
-        f = float(rng.uniform(0.4, 1.5)) * W
-        cx, cy = W / 2.0 + float(rng.uniform(-0.2, 0.2)) * W, H / 2.0 + float(rng.uniform(-0.2, 0.2)) * H
-        V = look_at_viewmat(eye)
-        if rng.random() < 0.1:                                               # odd cameras: fish-eye-short or telescope-long focal lengths, the
-            f = float(rng.choice([0.03, 0.1, 8.0, 40.0])) * max(W, H)        # principal point outside the image, a view matrix that is not quite a rotation
-            cx, cy = float(rng.uniform(-1.0, 2.0)) * W, float(rng.uniform(-1.0, 2.0)) * H
-            V = V.copy(); V[:3, :3] *= np.float32(rng.uniform(0.97, 1.03))
-        cams.append(Camera(V, intrinsics(f, f * float(rng.uniform(0.8, 1.25)), cx, cy), W, H))
+    cams = [draw_camera(rng, W, H) for _ in range(n_views)]
     entry = "single" if n_views == 1 else str(rng.choice(["batch", "batch", "posed", "host"]))
     if n_groups == 0 and entry == "posed":
         entry = "batch"
