@@ -351,6 +351,48 @@ int sas_sample_points(sas_ctx *ctx, int n_views, int width, int height, const fl
                       float *points, int32_t *index, uint8_t *colors, uint8_t *labels_out, int32_t *count, void *stream);
 
 /*
+ * Depth fusion: n_views same-sized depth frames are integrated, in view order, into a truncated-signed-distance (TSDF) volume the
+ * CALLER owns as device arrays.  The consumer behind sas_render_batch_labels that gives a splat geometry: a surface is extracted from
+ * the volume on the host (sim_a_splat_amd.reconstruct.surface_nets).  DESIGN.md 3, "Depth fusion".
+ *   depth       [n_views,H,W] f32 DEVICE
+ *   rgb8        [n_views,H,W,3] u8 DEVICE or NULL;  labels  [n_views,H,W] u8 DEVICE or NULL
+ *   Ks          [n_views,9] HOST, row-major (fx = K[0], cx = K[2], fy = K[4], cy = K[5]), finite, fx and fy > 0
+ *   transform   [n_views,12] HOST, row-major A|t, VOLUME frame -> camera, any finite affine map (a similarity such as the robot
+ *               frame folds in); NULL = identity.  trunc and near_z are in camera units
+ *   keep        [256] HOST or NULL (needs labels): a pixel with keep[labels[p]] == 0 shows something else -- it carves, see below
+ *   lo, voxel, dims   the volume: dims = (nx, ny, nz), each in [1,1024], nx ny nz <= 2^27; voxel (i,j,k) has flat index
+ *               g = (k ny + j) nx + i and centre c_x = lo_x + ((float)i + 0.5f) voxel, likewise y and z
+ *   pixel_centre  0.5: where the rasterizer samples a pixel; 0: the convention of sas_render_rgbd's points
+ *   flags       SAS_TIMING only: sas_stage_times then reads the call's launches as SAS_T_BLEND and SAS_T_TOTAL (the other slots 0)
+ *   tsdf, weight  [nz,ny,nx] f32 DEVICE, in/out;  color  [nz,ny,nx,3] f32 DEVICE in/out, or NULL (needs rgb8 when given)
+ * Per voxel, for the views v = 0 .. n_views - 1 in ascending order, all arithmetic float32 with nothing fused:
+ *   camera      q_m = ((A_m0 c_x + A_m1 c_y) + A_m2 c_z) + t_m
+ *   in front    q_z >= near_z (near_z > 0), else the view is skipped for this voxel
+ *   pixel       uf = ((fx (q_x / q_z)) + cx) - pixel_centre, then uf = uf + 0.5f; vf likewise from fy, q_y, cy.  The voxel proceeds
+ *               only if uf >= 0 && uf < (float)W && vf >= 0 && vf < (float)H (a NaN fails; tested before any conversion); then
+ *               u = (int)floorf(uf), v = (int)floorf(vf), p = (view H + v) W + u
+ *   depth       d = depth[p] with d > 0 and d < INFINITY (a NaN, 0, a negative and Inf skip the view)
+ *   distance    sdf = d - q_z
+ *   surface     (no labels, no keep, or keep[labels[p]] != 0)  sdf < -trunc: skip; else val = fminf(1.0f, sdf / trunc)
+ *   carving     (keep[labels[p]] == 0)  sdf >= trunc: val = 1.0f; else skip
+ *   update      w = weight[g]; tsdf[g] = ((tsdf[g] w) + val) / (w + 1.0f); with color, on a surface update, every channel
+ *               col = ((col w) + (float)rgb8[3 p + ch]) / (w + 1.0f) (a carving update leaves the colour); weight[g] = fminf(w + 1.0f,
+ *               max_weight)
+ * A voxel's result depends on its own pixels only; one call with views 0 .. C - 1 returns the bytes of C one-view calls in that
+ * order; two equal calls on equal volumes return equal bytes; a voxel no view updates keeps its bytes (a NaN the caller left there
+ * included).  No atomics.  No scene is required and nothing the context stores is touched.  Frames in flight are completed first; the
+ * call returns with the volume updated (`stream`: the caller's, behind whose pending work the inputs are read).
+ * SAS_ERR_INVALID: a negative n_views, an image size <= 0 or n_views H W > 2^31 - 256, a dims entry < 1 or > 1024 or nx ny nz > 2^27,
+ * a non-finite lo, transform or K entry, fx or fy not > 0, voxel, trunc, near_z or max_weight not finite and > 0, max_weight < 1, a
+ * non-finite pixel_centre, keep without labels, color without rgb8, a missing depth, Ks, tsdf or weight, any other flag.
+ * n_views == 0 is SAS_OK and changes nothing.
+ */
+int sas_fuse_depth(sas_ctx *ctx, int n_views, int width, int height, const float *depth, const uint8_t *rgb8,
+                   const uint8_t *labels, const float *Ks, const float *transform, const uint8_t *keep, const float lo[3],
+                   float voxel, const int dims[3], float trunc, float near_z, float pixel_centre, float max_weight,
+                   unsigned flags, float *tsdf, float *weight, float *color, void *stream);
+
+/*
  * Render n_views views of the same size in one call.  Serves the per-camera loops of
  * SplatHandler.render / SplatEnvWrapper.render (splat_handler.py:337-345, splat_env_wrapper.py:147-158).
  *   viewmats [n_views,16], Ks [n_views,9] host arrays; outputs are [n_views,H,W,...] device arrays

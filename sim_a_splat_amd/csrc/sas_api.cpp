@@ -239,6 +239,7 @@ struct sas_ctx : Settings {
     DevBuf query_pts, query_tri, query_mesh, query_list, query_count;   // scratch of sas_query_meshes (SasQuery)
     DevBuf match_src, match_tgt, match_keys, match_index, match_dist2, match_partial;   // scratch of sas_match_points (SasMatch)
     DevBuf cloud_par, cloud_grid, cloud_cand, cloud_blk, cloud_rows, cloud_dist, cloud_count;   // scratch of sas_sample_points (SasCloud)
+    DevBuf fuse_par;   // per-view rows and keep table of sas_fuse_depth (SasFuse)
     int match_cus = 0;   // compute units of the device, asked once (the slice count of sas_match_points)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
     // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
@@ -1911,6 +1912,106 @@ int sas_sample_points(sas_ctx *c, int n_views, int width, int height, const floa
     return SAS_OK;
 }
 
+int sas_fuse_depth(sas_ctx *c, int n_views, int width, int height, const float *depth, const uint8_t *rgb8, const uint8_t *labels,
+                   const float *Ks, const float *transform, const uint8_t *keep, const float lo[3], float voxel, const int dims[3],
+                   float trunc, float near_z, float pixel_centre, float max_weight, unsigned flags, float *tsdf, float *weight,
+                   float *color, void *stream)
+{
+    if (!c) return SAS_ERR_INVALID;
+    const char *who = "sas_fuse_depth";
+    const int C = n_views;
+    if (flags & ~SAS_TIMING) return fail(c, SAS_ERR_INVALID, "%s: flags 0x%x not accepted (SAS_TIMING; blocking only)", who, flags);
+    if (C < 0) return fail(c, SAS_ERR_INVALID, "%s: n_views %d is negative", who, C);
+    if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
+    const long long px_max = 0x7fffffffll - 256, px_view = (long long)height * width;   // (no product beyond 2^62)
+    if (px_view > px_max || (long long)C * px_view > px_max)
+        return fail(c, SAS_ERR_INVALID, "%s: %d views of %dx%d are more than 2^31 - 256 pixels", who, C, width, height);
+    if (!lo || !dims) return fail(c, SAS_ERR_INVALID, "%s: lo and dims are required", who);
+    SasFuse q{};
+    q.n_vox = 1;
+    for (int k = 0; k < 3; ++k) {
+        if (dims[k] < 1 || dims[k] > 1024) return fail(c, SAS_ERR_INVALID, "%s: dims[%d] = %d out of [1,1024]", who, k, dims[k]);
+        if (!std::isfinite(lo[k])) return fail(c, SAS_ERR_INVALID, "%s: lo[%d] = %g is not finite", who, k, (double)lo[k]);
+        q.n_vox *= dims[k];
+        q.lo[k] = lo[k];
+    }
+    if (q.n_vox > (1ll << 27)) return fail(c, SAS_ERR_INVALID, "%s: a volume of more than 2^27 voxels (%d x %d x %d)", who, dims[0], dims[1], dims[2]);
+    const struct { const char *name; float v; } positive[] = {{"voxel", voxel}, {"trunc", trunc}, {"near_z", near_z}, {"max_weight", max_weight}};
+    for (const auto &a : positive)
+        if (!(a.v > 0.0f) || !(a.v < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: %s %g, must be finite and > 0", who, a.name, (double)a.v);
+    if (max_weight < 1.0f) return fail(c, SAS_ERR_INVALID, "%s: max_weight %g, must be >= 1", who, (double)max_weight);
+    if (!std::isfinite(pixel_centre)) return fail(c, SAS_ERR_INVALID, "%s: pixel_centre %g is not finite", who, (double)pixel_centre);
+    if (keep && !labels) return fail(c, SAS_ERR_INVALID, "%s: keep without labels", who);
+    if (color && !rgb8) return fail(c, SAS_ERR_INVALID, "%s: color without rgb8", who);
+    if (!tsdf || !weight) return fail(c, SAS_ERR_INVALID, "%s: tsdf and weight are required", who);
+    if (C > 0 && (!depth || !Ks)) return fail(c, SAS_ERR_INVALID, "%s: depth and Ks are required", who);
+    for (int v = 0; v < C; ++v) {
+        const float *Kv = Ks + 9 * (size_t)v;
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(Kv[k])) return fail(c, SAS_ERR_INVALID, "%s: Ks[%d][%d] = %g is not finite", who, v, k, (double)Kv[k]);
+        if (!(Kv[0] > 0.0f) || !(Kv[4] > 0.0f)) return fail(c, SAS_ERR_INVALID, "%s: view %d: fx = %g, fy = %g must be > 0", who, v, (double)Kv[0], (double)Kv[4]);
+        for (int k = 0; transform && k < 12; ++k)
+            if (!std::isfinite(transform[12 * (size_t)v + k]))
+                return fail(c, SAS_ERR_INVALID, "%s: transform[%d][%d] = %g is not finite", who, v, k, (double)transform[12 * (size_t)v + k]);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;
+    if (C == 0) return SAS_OK;
+    q.W = width; q.H = height;
+    q.nx = dims[0]; q.ny = dims[1]; q.nz = dims[2];
+    q.voxel = voxel; q.trunc = trunc; q.near_z = near_z; q.pixel_centre = pixel_centre; q.max_weight = max_weight;
+    q.tsdf = tsdf; q.weight = weight; q.color = color;
+    // the per-view rows and the keep table: one host block, one copy per launch (one launch unless the call has more than
+    // SAS_FUSE_MAX_ROWS views: then launches in view order, which is what the contract's view order asks for)
+    const int rows_max = std::min(C, SAS_FUSE_MAX_ROWS);
+    const size_t off_keep = sizeof(SasFuseView) * (size_t)rows_max;
+    std::vector<unsigned char> par(off_keep + 256);
+    if (keep) std::copy(keep, keep + 256, par.data() + off_keep);
+    if (const int rc = ensure(c, c->fuse_par, par.size())) return rc;
+    unsigned char *dpar = (unsigned char *)c->fuse_par.p;
+    q.view = reinterpret_cast<const SasFuseView *>(dpar);
+    q.keep = keep ? dpar + off_keep : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    Event ev[2];
+    if (flags & SAS_TIMING) {
+        for (int k = 0; k < 2; ++k) HIP_TRY(c, hipEventCreate(ev[k].put()));
+        HIP_TRY(c, hipEventRecord(ev[0], st));
+    }
+    const size_t px = (size_t)width * (size_t)height;
+    for (int v0 = 0; v0 < C; v0 += rows_max) {
+        const int n = std::min(rows_max, C - v0);
+        SasFuseView *view = reinterpret_cast<SasFuseView *>(par.data());
+        for (int r = 0; r < n; ++r) {
+            const int v = v0 + r;
+            SasFuseView &V = view[r];
+            const float *Kv = Ks + 9 * (size_t)v;
+            V.fx = Kv[0]; V.cx = Kv[2]; V.fy = Kv[4]; V.cy = Kv[5];
+            for (int k = 0; k < 3; ++k) {
+                for (int j = 0; j < 3; ++j) V.A[3 * k + j] = transform ? transform[12 * (size_t)v + 4 * k + j] : (k == j ? 1.0f : 0.0f);
+                V.t[k] = transform ? transform[12 * (size_t)v + 4 * k + 3] : 0.0f;
+            }
+        }
+        // (the block is the call's own: the launch before this one, if any, has been waited for)
+        HIP_TRY(c, hipMemcpy(dpar, par.data(), par.size(), hipMemcpyHostToDevice));
+        q.C = q.n_rows = n;
+        q.n_pix = (long long)n * (long long)px;
+        q.depth = depth + (size_t)v0 * px;
+        q.rgb8 = rgb8 ? rgb8 + 3 * (size_t)v0 * px : nullptr;
+        q.labels = labels ? labels + (size_t)v0 * px : nullptr;
+        sas_launch_fuse(st, q);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess && v0 + n == C && (flags & SAS_TIMING)) e = hipEventRecord(ev[1], st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "depth fusion: %s", hipGetErrorString(e));
+    }
+    if (flags & SAS_TIMING) {
+        std::fill(c->stage_ms, c->stage_ms + SAS_T_COUNT, 0.0f);
+        (void)hipEventElapsedTime(&c->stage_ms[SAS_T_BLEND], ev[0], ev[1]);
+        c->stage_ms[SAS_T_TOTAL] = c->stage_ms[SAS_T_BLEND];
+    }
+    return SAS_OK;
+}
+
 int sas_render_rgbd(sas_ctx *c, const float *viewmat, const float *K, int width, int height, const float *background,
                     unsigned flags, const float *max_depth, float *rgb, float *alpha, float *depth, float *points,
                     uint8_t *mask, void *stream)
@@ -2149,17 +2250,18 @@ extern "C" int sas_debug_bounds_mesh(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_query(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_match(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_cloud(unsigned long long *out, int reset);
+extern "C" int sas_debug_bounds_fuse(unsigned long long *out, int reset);
 /* Bounds-checked build only: out[0] = guarded accesses found out of range since the last reset (they were
  * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none). */
 int sas_debug_bounds(unsigned long long *out, int reset)
 {
-    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0};
+    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0};
     if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset) ||
         sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset) || sas_debug_bounds_match(p, reset) ||
-        sas_debug_bounds_cloud(s, reset))
+        sas_debug_bounds_cloud(s, reset) || sas_debug_bounds_fuse(f, reset))
         return SAS_ERR_HIP;
-    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : s))));
-    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0];
+    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : (s[0] ? s : f)))));
+    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0] + f[0];
     out[1] = first[1]; out[2] = first[2]; out[3] = first[3];
     return SAS_OK;
 }

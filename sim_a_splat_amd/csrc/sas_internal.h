@@ -1,4 +1,4 @@
-// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -403,3 +403,28 @@ struct SasCloud {
 };
 // ev (optional, 4 events): stamped in front of k_cloud_mark, k_cloud_compact, k_cloud_fps and behind the last kernel
 void sas_launch_cloud(hipStream_t st, const SasCloud &q, hipEvent_t *ev);
+
+// Depth fusion (sas_fuse_depth; DESIGN.md 3, "Depth fusion").  The kernel takes the whole call by value; the per-view rows live in one
+// device block beside the keep table.
+#define SAS_FUSE_THREADS 256      // voxels per workgroup of k_fuse
+#define SAS_FUSE_MAX_ROWS 4096    // per-view rows of one launch: a call of more views is served by launches in view order
+struct SasFuseView {
+    float fx, cx, fy, cy;
+    float A[9], t[3];           // volume frame -> camera
+};
+struct SasFuse {
+    const float *depth;         // [C,H,W], the first view of this launch
+    const uint8_t *rgb8;        // [C,H,W,3] or nullptr
+    const uint8_t *labels;      // [C,H,W] or nullptr
+    const SasFuseView *view;    // [C] device
+    const uint8_t *keep;        // [256] device, or nullptr (non-null only with labels)
+    float *tsdf, *weight;       // [nz,ny,nx]
+    float *color;               // [nz,ny,nx,3] or nullptr (non-null only with rgb8)
+    long long n_vox;            // nx ny nz
+    long long n_pix;            // C H W
+    int n_rows;                 // rows of `view`
+    int C, W, H;
+    int nx, ny, nz;
+    float lo[3], voxel, trunc, near_z, pixel_centre, max_weight;
+};
+void sas_launch_fuse(hipStream_t st, const SasFuse &q);

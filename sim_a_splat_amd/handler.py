@@ -418,6 +418,37 @@ class SplatHandler:
         (H, W), = sizes
         return chs.get_point_clouds(H, W, cam, int(n_points), bounds=bounds, voxel_size=voxel_size, stride=stride, keep=keep, frame=frame, **kw)
 
+    def reconstruct_mesh(self, rows, bounds, voxel_size: float, *, frame="robot", n_azimuth: int = 12, elevations=(20, 50, 80),
+                         radius: Optional[float] = None, render_size=(240, 320), scene: Optional[SplatScene] = None, **fuse_kw) -> Dict[str, np.ndarray]:
+        """A triangle mesh of what the rows ``rows`` (names or indices of ``scene.row_names()``; None: everything) show inside
+        ``bounds`` ``(lo[3], hi[3])``: ``reconstruct.orbit_cameras`` around the bounds' centre, ``SplatScene.fuse_views`` into a
+        volume of ``voxel_size`` cubes, ``surface_nets``.  ``frame`` as in ``render_point_cloud`` -- ``"robot"``: bounds, voxel size and
+        the mesh are metres of the simulator; the orbit's up is that frame's +z.  ``radius`` (frame units; default: the bounds fit
+        the view).  Returns ``{"vertices" [V,3] float64, "faces" [F,3] int32, "colors" [V,3] uint8}`` in that frame: ready for
+        ``upload_meshes``, ``query_meshes`` or ``mesh_io.save_obj``."""
+        from . import reconstruct
+        chs = self.scene if scene is None else scene
+        if isinstance(frame, str):
+            if frame not in ("scene", "robot"):
+                raise ValueError(f"frame must be 'scene', 'robot' or a 4x4 matrix, got {frame!r}")
+            frame = self.robot_frame() if frame == "robot" else None
+        F = np.eye(4) if frame is None else np.asarray(frame, np.float64).reshape(4, 4)
+        b = np.asarray(bounds, np.float64).reshape(2, 3)
+        vol = reconstruct.TsdfVolume(chs._raster, b[0], voxel_size, hi=b[1])
+        H, W = int(render_size[0]), int(render_size[1])
+        if radius is None:
+            radius = reconstruct.orbit_radius(0.5 * float(np.linalg.norm(b[1] - b[0])), chs.camera.fov, H, W)
+        # the orbit is laid out in the volume's frame and carried into the scene's: positions through inv(F), the cameras' axes
+        # through its rotation (F is a similarity: a scaled rotation keeps the axes orthogonal)
+        cams = reconstruct.orbit_cameras(0.5 * (b[0] + b[1]), radius, n_azimuth, elevations)
+        if frame is not None:
+            inv = np.linalg.inv(F)
+            s = float(np.cbrt(abs(np.linalg.det(inv[:3, :3]))))
+            cams = [(poses.matrix_to_quat_wxyz((inv[:3, :3] / s) @ poses.quat_wxyz_to_matrix(q)), inv[:3, :3] @ p + inv[:3, 3]) for q, p in cams]
+        chs.fuse_views(vol, H, W, cams, keep=rows, frame=frame, **fuse_kw)
+        v, f, c = vol.extract_mesh()
+        return {"vertices": v, "faces": f, "colors": c}
+
     def point_cloud_obs(self, chs, cam_poses, render_size, n_points: int, **cfg) -> np.ndarray:
         """``render_point_cloud`` as an observation entry: float32 ``[n_points,6]``, xyz then rgb in 0..1; padding rows are zero."""
         o = self.render_point_cloud(chs, cam_poses, render_size, n_points, **cfg)

@@ -1,4 +1,4 @@
-"""Triangle mesh readers for the meshes a scene composites (Rasterizer.upload_meshes; DESIGN.md 3, "Meshes").
+"""Triangle mesh readers (and an OBJ writer) for the meshes a scene composites (Rasterizer.upload_meshes; DESIGN.md 3, "Meshes").
 
 They need neither trimesh nor open3d: the reference loads the pushT task object (an OBJ) and the URDF visuals (STL or OBJ)
 through trimesh only to hand vertices and faces to viser (splat_handler.py:145-219).  Every reader returns
@@ -38,6 +38,40 @@ def load_obj(path: PathLike) -> Tuple[np.ndarray, np.ndarray]:
     if f.size and (f.min() < 0 or f.max() >= len(v)):
         raise ValueError(f"{path}: face index out of range")
     return v, f
+
+
+def load_obj_colors(path: PathLike):
+    """The per-vertex colours ``save_obj`` writes behind the coordinates (``v x y z r g b``, 0..1): ``[V,3]`` uint8, or None when any
+    vertex has none."""
+    cols = []
+    for line in Path(path).read_text(errors="replace").splitlines():
+        parts = line.split()
+        if parts and parts[0] == "v":
+            if len(parts) < 7:
+                return None
+            cols.append([float(x) for x in parts[4:7]])
+    return np.clip(np.rint(np.asarray(cols, np.float64).reshape(-1, 3) * 255.0), 0, 255).astype(np.uint8)
+
+
+def save_obj(path: PathLike, vertices, faces, colors=None) -> None:
+    """Wavefront OBJ: one ``v x y z`` line per vertex (17 significant digits: ``load_obj`` reads the float64 back exactly), with
+    ``colors [V,3]`` uint8 as ``r g b`` in 0..1 behind the coordinates (the common vertex-colour extension; k/255 in 6 decimals reads
+    back as k), and one 1-based ``f`` line per triangle."""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError("save_obj: face index out of range")
+    c = None
+    if colors is not None:
+        c = np.asarray(colors, np.uint8).reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError(f"save_obj: {len(c)} colours for {len(v)} vertices")
+    lines = []
+    for k in range(len(v)):
+        tail = "" if c is None else " " + " ".join(f"{x / 255.0:.6f}" for x in c[k])
+        lines.append("v " + " ".join(repr(float(x)) for x in v[k]) + tail)
+    lines += [f"f {a + 1} {b + 1} {d + 1}" for a, b, d in f.tolist()]
+    Path(path).write_text("\n".join(lines) + "\n")
 
 
 def _stl_is_binary(data: bytes) -> bool:

@@ -81,6 +81,21 @@ def cloud_transforms(viewmats, frame=None) -> np.ndarray:
     return np.ascontiguousarray(inv[:, :3, :].reshape(-1, 12).astype(np.float32))
 
 
+def fuse_transforms(viewmats, frame=None) -> np.ndarray:
+    """Volume-frame-to-camera maps of ``fuse_depth``: ``[C,12]`` float32 rows ``A|t``, every world-to-camera ``viewmats [C,4,4]`` with
+    the inverse of ``frame`` (4x4, world to volume frame; any invertible affine map -- ``cloud_transforms``' argument) multiplied on
+    from the right, ``viewmat @ inv(frame)`` in float64, rounded to float32 once.  ValueError on a wrong shape."""
+    V = np.asarray(_host(viewmats), dtype=np.float64)
+    if V.ndim != 3 or V.shape[1:] != (4, 4):
+        raise ValueError(f"viewmats must be [C,4,4], got {list(V.shape)}")
+    if frame is not None:
+        F = np.asarray(_host(frame), dtype=np.float64)
+        if F.shape != (4, 4):
+            raise ValueError(f"frame must be 4x4, got {list(F.shape)}")
+        V = V @ np.linalg.inv(F)[None]
+    return np.ascontiguousarray(V[:, :3, :].reshape(-1, 12).astype(np.float32))
+
+
 def cloud_keep_table(keep_labels) -> Optional[np.ndarray]:
     """The 256-byte keep table of ``sample_point_cloud`` from the labels to keep (integers in 0..255); None stays None."""
     if keep_labels is None:
@@ -508,6 +523,64 @@ class Rasterizer:
             self._check(rc, "sas_sample_points")
         self._in_flight(True)
         return res
+
+    @_locked
+    def fuse_depth(self, volume, depth: ArrayLike, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int, *,
+                   rgb8: Optional[ArrayLike] = None, labels: Optional[ArrayLike] = None, keep_labels=None, frame=None,
+                   trunc: Optional[float] = None, near: float = 0.01, pixel_centre: float = 0.5, max_weight: float = 64.0,
+                   timing: bool = False) -> None:
+        """Integrate the depth frames of C same-sized views into ``volume`` (sas_fuse_depth; DESIGN.md 3, "Depth fusion"), in view
+        order.  ``volume`` (``reconstruct.TsdfVolume``) owns the device tensors ``tsdf`` / ``weight [nz,ny,nx]`` and ``color
+        [nz,ny,nx,3]`` (or None), updated in place, with ``lo``, ``voxel_size`` and ``dims = (nx, ny, nz)``.  ``depth [C,H,W]`` (or
+        ``[C,H,W,1]``) float32 with ``viewmats [C,4,4]`` (world to camera) and ``Ks [C,3,3]``, optionally ``rgb8 [C,H,W,3]`` (needed
+        when the volume has colour) and ``labels [C,H,W]`` uint8 -- device tensors are read where they are (the outputs of
+        ``render_batch_labels``), NumPy arrays are copied.  The volume lives in the world or, with ``frame`` (4x4, world to volume
+        frame), beyond it: ``fuse_transforms(viewmats, frame)``.  With ``labels`` and ``keep_labels`` a pixel that shows another
+        label only carves free space in front of itself.  ``trunc``: the truncation distance in volume units (default 4 voxels),
+        scaled by the cube root of ``|det A|`` of the first view's map into camera units; ``near``: camera units; ``pixel_centre``:
+        0.5 for rendered depth, 0 for the convention of ``render_rgbd``'s points.  Deterministic; blocking; needs no scene.
+        ``timing``: ``stage_times()`` then holds the call's kernel (blend, total)."""
+        T = fuse_transforms(viewmats, frame)
+        C, W, H = T.shape[0], int(width), int(height)
+        Kc = np.ascontiguousarray(np.asarray(_host(Ks), dtype=np.float32)).reshape(-1)
+        if Kc.size != 9 * C:
+            raise ValueError(f"Ks must be [{C},3,3], got {Kc.size} values")
+        if W < 0 or H < 0:
+            raise ValueError(f"fuse_depth: size {W}x{H}")
+        if keep_labels is not None and labels is None:
+            raise ValueError("keep_labels needs labels")
+        keep = cloud_keep_table(keep_labels)
+        nx, ny, nz = (int(n) for n in volume.dims)
+        for name, t, shape in (("tsdf", volume.tsdf, (nz, ny, nx)), ("weight", volume.weight, (nz, ny, nx)), ("color", volume.color, (nz, ny, nx, 3))):
+            if t is None and name == "color":
+                continue
+            if not (isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"volume.{name} must be a contiguous float32 tensor {list(shape)} on {self.device}")
+        if volume.color is not None and rgb8 is None:
+            raise ValueError("a volume with colour needs rgb8")
+        voxel = float(volume.voxel_size)
+        scale = 1.0
+        if C > 0:
+            A = np.asarray(_host(viewmats), dtype=np.float64)[0, :3, :3]
+            if frame is not None:
+                A = A @ np.linalg.inv(np.asarray(_host(frame), dtype=np.float64))[:3, :3]
+            scale = float(np.cbrt(abs(np.linalg.det(A))))
+        tr = (4.0 * voxel if trunc is None else float(trunc)) * scale
+        d = self._device_image(depth, torch.float32, C * H * W, "depth", (C, H, W))
+        c8 = None if rgb8 is None else self._device_image(rgb8, torch.uint8, 3 * C * H * W, "rgb8", (C, H, W, 3))
+        lab = None if labels is None else self._device_image(labels, torch.uint8, C * H * W, "labels", (C, H, W))
+        lo = np.ascontiguousarray(np.asarray(_host(volume.lo), dtype=np.float32).reshape(3))
+        dims = np.array([nx, ny, nz], np.int32)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        host = lambda a: a.ctypes.data if a is not None and a.size else None
+        stream = self._stream()   # (the call runs behind what this stream holds: the copies above)
+        rc = self._L.sas_fuse_depth(self._ctx, C, W, H, ptr(d), ptr(c8), ptr(lab), host(Kc), host(T), host(keep), lo.ctypes.data, voxel,
+                                    dims.ctypes.data, tr, float(near), float(pixel_centre), float(max_weight),
+                                    _capi.SAS_TIMING if timing else 0, ptr(volume.tsdf), ptr(volume.weight),
+                                    ptr(volume.color) if c8 is not None else None, stream)
+        if rc != 0:
+            self._check(rc, "sas_fuse_depth")
+        self._in_flight(True)
 
     @_locked
     def set_group_poses(self, Rt: ArrayLike) -> None:

@@ -427,6 +427,26 @@ class SplatScene:
             res["frames"] = o
             return res
 
+    def fuse_views(self, volume, height: int, width: int, cam_poses, *, keep=None, fov: Optional[float] = None, frame=None,
+                   min_alpha: float = 0.5, **fuse_kw) -> Dict[str, torch.Tensor]:
+        """Integrate what C same-sized cameras ``[(wxyz, position), ...]`` see into ``volume`` (``reconstruct.TsdfVolume``): one
+        label-frame call (``Rasterizer.render_batch_labels`` with depth and rgb8, the background's depth filled) and one fusion
+        call (``Rasterizer.fuse_depth``) on its device outputs -- nothing visits the host.  ``keep``: the rows that are the surface,
+        by name (``row_names()``) or index; pixels of other rows, and the filled background, carve the free space in front of
+        themselves -- which is what closes the surface behind the object's silhouette.  ``frame`` (4x4, world to volume frame) and
+        ``fuse_kw`` (``trunc``, ``near``, ``max_weight``) go to ``fuse_depth``.  Returns the label-frame call's outputs."""
+        V, K = self._views_and_Ks(int(height), int(width), *_camera_arrays(cam_poses), self._camera_or(fov=fov)[2])
+        with self.lock:
+            if not self._handles:
+                raise RuntimeError("fusion needs at least one splat group or mesh")
+            rows = self._keep_rows(keep)
+            self._sync()
+            o = self._raster.render_batch_labels(V, K, int(width), int(height), self.background, min_alpha=min_alpha,
+                                                 want=("depth", "rgb8"), depth_fill_max=True)
+            self._raster.fuse_depth(volume, o["depth"], V, K, int(width), int(height), rgb8=o["rgb8"], labels=o["labels"],
+                                    keep_labels=rows, frame=frame, pixel_centre=0.5, **fuse_kw)
+            return o
+
     def get_segmentations(self, height: int, width: int, cam_poses, fov: Optional[float] = None, pose_sets=None, pose_set=None,
                           min_alpha: float = 0.5) -> torch.Tensor:
         """``get_segmentation``'s ``labels`` for C same-sized cameras ``[(wxyz, position), ...]`` in one call: uint8 ``[C,H,W]`` on the
