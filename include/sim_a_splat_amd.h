@@ -492,6 +492,39 @@ int sas_render_batch_labels_posed(sas_ctx *ctx, int n_views, const float *viewma
 int sas_lift_labels(sas_ctx *ctx, int n_views, const float *viewmats, const float *Ks, int width, int height,
                     const uint8_t *labels, int n_labels, unsigned flags, int64_t *votes, int64_t *seen, void *stream);
 
+/*
+ * Feature lifting: sas_lift_labels with `channels` real-valued channels in one label's place -- per-Gaussian embeddings from the
+ * feature maps (DINO / CLIP patch features, or colours) of a few views, each Gaussian taking the compositing-weighted mean of the
+ * pixels it shows in.  The contract: for view v, pixel p inside the image, and every list entry i (a Gaussian, in the CALLER's
+ * order) that the frame's compositing ADDS at p, let vis be the float32 weight that multiplies the colours in sas_render, under the
+ * context's current group poses and the call's flags, and
+ *     q         = (int64) floorf(vis * 2^24)          (SAS_LIFT_FEATURE_ONE; the product is exact in float32 and 0 <= vis < 1)
+ *     fq[v,p,k] = (int32) rintf(min(max(images[v,p,k] * feature_scale, -32767), 32767))
+ *                 (the float32 product, rounded half to even; NaN -> 0, +-Inf -> +-32767).
+ * Then, where mask is NULL or mask[v,p] != 0:  weight[i] += q  and  sums[i,k] += q * fq[v,p,k] for k < channels.  Nothing is added
+ * for: entries skipped for alpha < 1/255 or sigma < 0; the entry that trips T' <= 1e-4 and everything behind it; pixels of a ragged
+ * tile beyond W or H; pixels whose mask is 0.  The weighted mean of Gaussian i is sums[i,k] / (weight[i] * feature_scale).
+ *   images         [n_views,H,W,channels] float32 DEVICE, required
+ *   channels       1..256
+ *   feature_scale  finite, > 0: what one unit of the features is worth in fq (32767 / max|f| uses the whole range)
+ *   mask           [n_views,H,W] uint8 DEVICE, or NULL
+ *   sums           [N,channels] int64 DEVICE, or NULL
+ *   weight         [N] int64 DEVICE, or NULL; at least one of sums and weight
+ *   flags          SAS_FAST_EXP and SAS_TIMING only.  The call is blocking: SAS_ASYNC and every other flag is SAS_ERR_INVALID.
+ * The call ADDS to what the buffers hold: the caller zeroes them once and may accumulate over many calls (with ONE feature_scale).
+ * The sums are integers, so the result does not depend on any order of addition or batching of views and calls.
+ * |sums[i,k]| <= 32767 * weight[i], so no sum can have overflowed while weight[i] < 2^48: check weight afterwards (it cannot wrap
+ * before 2^63 itself) instead of budgeting pixels in advance; the call does not check it.
+ * Frames in flight are completed first.  Lift frames are SAS_FULL_SORT frames, one view at a time through the frame slots; a frame
+ * whose first rendering outgrew its key buffer adds nothing until it is rendered again.  SAS_ERR_NO_SCENE before an upload;
+ * SAS_ERR_INVALID for channels or feature_scale out of range, images NULL, both outputs NULL, n_views < 1, non-positive sizes, any
+ * other flag, or a context that holds meshes.  After any error the context stays usable.
+ */
+#define SAS_LIFT_FEATURE_ONE 16777216.0f   /* 2^24: the fixed-point unit of a feature-lift weight */
+int sas_lift_features(sas_ctx *ctx, int n_views, const float *viewmats, const float *Ks, int width, int height,
+                      const float *images, int channels, float feature_scale, const uint8_t *mask, unsigned flags,
+                      int64_t *sums, int64_t *weight, void *stream);
+
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical
  * field of view; the view matrices and intrinsics are those of sas_camera_matrices. */

@@ -6,6 +6,7 @@
 #include "sas_internal.h"
 
 #include <cmath>
+#include <functional>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -60,6 +61,12 @@ struct ViewOut {
     const uint8_t *lift_labels = nullptr;
     int64_t *lift_votes = nullptr, *lift_seen = nullptr;
     int lift_n = 0;                 // n_labels
+    // sas_lift_features: the view's feature image [H,W,lift_c] and mask [H,W] (device; the mask may be nullptr) and the sums likewise
+    const float *lift_images = nullptr;
+    const uint8_t *lift_mask = nullptr;
+    int64_t *lift_sums = nullptr, *lift_weight = nullptr;
+    int lift_c = 0;
+    float lift_scale = 0.0f;
 };
 
 struct RenderArgs {
@@ -831,6 +838,11 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
             const SasLift B{a.out.lift_labels, (unsigned long long *)a.out.lift_votes, (unsigned long long *)a.out.lift_seen, c->scene.n, a.out.lift_n};
             sas_launch_lift_labels(st, c->scene, tiles, P, f, B, fast_exp);
         }
+        if (a.out.lift_images) {   // ... or, channel by channel, the pixels' features weighted by them
+            const SasLiftFeatures B{a.out.lift_images, a.out.lift_mask, (unsigned long long *)a.out.lift_sums,
+                                    (unsigned long long *)a.out.lift_weight, c->scene.n, a.out.lift_c, a.out.lift_scale};
+            sas_launch_lift_features(st, c->scene, tiles, P, f, B, fast_exp);
+        }
     } else if (nv > 1) {
         // (quad: by the size of one view (prepare_frame): groups of four 300-tile views still gain (vec_env_probe))
         sas_launch_tiles_lazy_multi(st, c->scene, tiles, mf, fast_exp, any_fill, ld.quad, tile_ev[0], tile_ev[1]);
@@ -1392,7 +1404,7 @@ static void fill_args(RenderArgs &a, const ViewCall &v, int width, int height, c
     const ViewOut &o = v.out;
     a.solo = solo;
     // rgb8 beside rgb8_host is the context's own staging frame (sas_render_batch_host): nothing of the caller's on the device
-    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || o.labels || o.lift_labels || (o.rgb8 && !o.rgb8_host);
+    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || o.labels || o.lift_labels || o.lift_images || (o.rgb8 && !o.rgb8_host);
     memcpy(a.viewmat, v.viewmat, sizeof(a.viewmat));
     memcpy(a.K, v.K, sizeof(a.K));
     for (int k = 0; k < 3; ++k) a.bg[k] = background ? background[k] : 0.0f;
@@ -2143,34 +2155,75 @@ int sas_render_batch_labels_posed(sas_ctx *c, int n_views, const float *viewmats
     return render_batch_impl(c, n_views, viewmats, Ks, width, height, background, flags, rgb, alpha, depth, rgb8, nullptr, stream, ps, lab);
 }
 
-int sas_lift_labels(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height, const uint8_t *labels,
-                    int n_labels, unsigned flags, int64_t *votes, int64_t *seen, void *stream)
+// What every lift call checks first, and the flags it takes.
+static int check_lift(sas_ctx *c, const char *who, unsigned flags)
 {
     if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_lift_labels before sas_scene_upload");
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
     if (flags & ~(SAS_FAST_EXP | SAS_TIMING))
-        return fail(c, SAS_ERR_INVALID, "sas_lift_labels: flags 0x%x not accepted (SAS_FAST_EXP, SAS_TIMING; blocking only)", flags);
+        return fail(c, SAS_ERR_INVALID, "%s: flags 0x%x not accepted (SAS_FAST_EXP, SAS_TIMING; blocking only)", who, flags);
     if (has(c, HAVE_MESH))
-        return fail(c, SAS_ERR_INVALID, "sas_lift_labels: lift frames do not take occlusion by meshes; clear the meshes first (sas_scene_meshes with none)");
-    if (n_labels < 1 || n_labels > 256) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: n_labels %d out of [1,256]", n_labels);
-    if (!labels) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: the label images are required");
-    if (!votes && !seen) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: votes and seen are both NULL");
-    if (n_views < 1 || !viewmats || !Ks) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: bad view batch (n_views %d)", n_views);
-    if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: bad image size %dx%d", width, height);
+        return fail(c, SAS_ERR_INVALID, "%s: lift frames do not take occlusion by meshes; clear the meshes first (sas_scene_meshes with none)", who);
+    return SAS_OK;
+}
+
+// The views of a lift call; `view_out(v)` names view v's image and the sums it adds to.
+// Lift frames are SAS_FULL_SORT frames: one view at a time through the frame slots, nothing drains between views.  (A frame that
+// outgrew its key buffer adds nothing and is rendered again: k_lift_labels, k_lift_features.)
+static int lift_views(sas_ctx *c, const char *who, int n_views, const float *viewmats, const float *Ks, int width, int height,
+                      unsigned flags, void *stream, const std::function<ViewOut(int)> &view_out)
+{
+    if (n_views < 1 || !viewmats || !Ks) return fail(c, SAS_ERR_INVALID, "%s: bad view batch (n_views %d)", who, n_views);
+    if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;   // frames in flight are completed first
-    // Lift frames are SAS_FULL_SORT frames: one view at a time through the frame slots, nothing drains between views.  (A frame that
-    // outgrew its key buffer adds nothing and is rendered again: k_lift_labels.)
-    const size_t px = (size_t)width * (size_t)height;
     for (int v = 0; v < n_views; ++v) {
-        ViewCall vc{viewmats + 16 * v, Ks + 9 * v, {}};
-        vc.out.lift_labels = labels + px * v;
-        vc.out.lift_votes = votes;
-        vc.out.lift_seen = seen;
-        vc.out.lift_n = n_labels;
+        ViewCall vc{viewmats + 16 * v, Ks + 9 * v, view_out(v)};
         if (const int rc = render_views(c, &vc, 1, width, height, nullptr, flags | SAS_FULL_SORT | SAS_ASYNC, nullptr, stream)) return rc;
     }
     return sas_wait(c);
+}
+
+int sas_lift_labels(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height, const uint8_t *labels,
+                    int n_labels, unsigned flags, int64_t *votes, int64_t *seen, void *stream)
+{
+    if (const int rc = check_lift(c, "sas_lift_labels", flags)) return rc;
+    if (n_labels < 1 || n_labels > 256) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: n_labels %d out of [1,256]", n_labels);
+    if (!labels) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: the label images are required");
+    if (!votes && !seen) return fail(c, SAS_ERR_INVALID, "sas_lift_labels: votes and seen are both NULL");
+    const size_t px = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
+    return lift_views(c, "sas_lift_labels", n_views, viewmats, Ks, width, height, flags, stream, [&](int v) {
+        ViewOut o;
+        o.lift_labels = labels + px * v;
+        o.lift_votes = votes;
+        o.lift_seen = seen;
+        o.lift_n = n_labels;
+        return o;
+    });
+}
+
+int sas_lift_features(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height, const float *images,
+                      int channels, float feature_scale, const uint8_t *mask, unsigned flags, int64_t *sums, int64_t *weight,
+                      void *stream)
+{
+    if (const int rc = check_lift(c, "sas_lift_features", flags)) return rc;
+    if (channels < 1 || channels > SAS_MAX_FEATURES)
+        return fail(c, SAS_ERR_INVALID, "sas_lift_features: channels %d out of [1,%d]", channels, SAS_MAX_FEATURES);
+    if (!(feature_scale > 0.0f) || !std::isfinite(feature_scale))
+        return fail(c, SAS_ERR_INVALID, "sas_lift_features: feature_scale %g is not finite and positive", (double)feature_scale);
+    if (!images) return fail(c, SAS_ERR_INVALID, "sas_lift_features: the feature images are required");
+    if (!sums && !weight) return fail(c, SAS_ERR_INVALID, "sas_lift_features: sums and weight are both NULL");
+    const size_t px = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
+    return lift_views(c, "sas_lift_features", n_views, viewmats, Ks, width, height, flags, stream, [&](int v) {
+        ViewOut o;
+        o.lift_images = images + px * (size_t)channels * v;
+        o.lift_mask = mask ? mask + px * v : nullptr;
+        o.lift_sums = sums;
+        o.lift_weight = weight;
+        o.lift_c = channels;
+        o.lift_scale = feature_scale;
+        return o;
+    });
 }
 
 static int render_batch_host_impl(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height,

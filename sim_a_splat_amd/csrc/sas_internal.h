@@ -226,6 +226,21 @@ struct SasLift {
 // after sas_launch_blend, on the same frame (no meshes): one workgroup per tile
 void sas_launch_lift_labels(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f, const SasLift &B,
                             bool fast_exp);
+// Feature lifting (sas_lift_features; DESIGN.md 3, "Feature lifting"): sas_lift_labels with C real-valued channels in one label's
+// place.  Every weight the frame's compositing adds at a pixel goes, as q = floor(weight 2^24), to the entry's Gaussian: weight[i] += q
+// and sums[i,k] += q fq[p,k], fq the pixel's channels quantised to [-32767, 32767] by `scale`.  64-bit integer atomics as there.
+struct SasLiftFeatures {
+    const float *images;          // [H,W,C] device: the view's feature image
+    const uint8_t *mask;          // [H,W] device, or nullptr: a pixel with mask 0 adds nothing
+    unsigned long long *sums;     // [n,C] device (the caller's int64, two's complement), or nullptr
+    unsigned long long *weight;   // [n] device, or nullptr
+    long long n;                  // Gaussians of the scene
+    int C;                        // 1..SAS_MAX_FEATURES
+    float scale;                  // feature_scale
+};
+// after sas_launch_blend, on the same frame (no meshes): one workgroup per (tile, chunk of SAS_FEAT_K channels)
+void sas_launch_lift_features(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
+                              const SasLiftFeatures &B, bool fast_exp);
 // store <- features [nt,C] (device; nullptr: one-hot of the triangles' pose groups), through finite_colour
 void sas_launch_mesh_feature_store(hipStream_t st, int64_t nt, const int4 *tri, const float *src, int C, float *store);
 

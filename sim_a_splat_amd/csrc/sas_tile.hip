@@ -2504,6 +2504,116 @@ __global__ __launch_bounds__(256) void k_lift_labels(SasParams P, SasFrame f, lo
                           [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay);
 }
 
+// Feature lifting (sas_lift_features): LiftPayload with the pixel's SAS_FEAT_K quantised channels of one chunk in the label's place.
+// q = floor(weight 2^24) < 2^24 and |fq| <= 32767, so q fq is a signed 40-bit product: q is split into two 12-bit halves, whose
+// products with fq stay below 2^27 and whose sums over the 16 lanes of a 4x4 block (a DPP row: LiftPayload::row_sum, which is
+// modular and therefore sums two's complement values as well) stay below 2^31.  Every lane of the row then holds the block's eight
+// channel sums; lane k < 8 issues channel k's 64-bit atomic, so one atomic wave-instruction writes one contiguous 64-byte segment
+// sums[i, 8c .. 8c + 7] per block.  Chunk 0 alone adds `weight`.  No float atomics, no combining across waves.
+struct LiftFeaturePayload {
+    typedef int Rec;
+    typedef int V;
+    const int *perm;               // slot j holds the caller's Gaussian perm[j]
+    unsigned long long *sums;      // [n][C], or nullptr
+    unsigned long long *weight;    // [n], or nullptr (and in every chunk but the first)
+    long long n;
+    int C, c0;                     // channels of the image; first channel of this workgroup's chunk
+    bool live;                     // this lane's pixel is inside the image and not masked out
+    int fq[SAS_FEAT_K];            // the pixel's quantised channels c0 .. c0 + 7 (0 beyond C)
+    DEV Rec none() const { return 0; }
+    DEV Rec fetch(const SasFrame &, long long id) const { return (SAS_IN(id, n, 360) && id < n) ? perm[id] : 0; }
+    DEV void stage(const BlendLds &L, int slot, const Rec &c, float) const
+    {
+        if (SAS_IN(slot, kStage, 361)) *reinterpret_cast<int *>(L.q2 + slot) = c;
+    }
+    DEV void stage_sentinel(const BlendLds &L, float z0) const { L.q2[256] = make_float4(z0, z0, z0, z0); }   // Gaussian 0, weight 0
+    DEV V load(const char *q2b, unsigned off) const
+    {
+        if (!SAS_IN(off >> 4, kStage, 362)) off = 256u << 4;
+        return *reinterpret_cast<const int *>(q2b + off);
+    }
+    DEV float depth(const V &) const { return 0.0f; }
+    // (int32) rintf(min(max(x scale, -32767), 32767)), NaN -> 0: fminf / fmaxf return the operand that is a number, so NaN is tested
+    static DEV int quantise(float x, float scale)
+    {
+        const float y = x * scale;
+        return y != y ? 0 : (int)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(y, -32767.0f), 32767.0f));
+    }
+    // one entry: the block's lanes hold the same Gaussian `idx` (they read the same queue slot)
+    DEV void give(int idx, float vis) const
+    {
+        // floorf(vis 2^24): exact product, 0 <= vis < 1, the conversion truncates.  A lane outside the image gives nothing, as in
+        // LiftPayload::give (a Gaussian with opacity NaN or +Inf would otherwise be seen by the parked lane).
+        const unsigned q = live ? (unsigned)(vis * 16777216.0f) : 0u;
+        if (!__ballot(q != 0u)) return;   // (uniform) nobody in the wave composited this entry
+        const int l16 = (int)(threadIdx.x & 15u);
+        const bool ok = idx >= 0 && (long long)idx < n && SAS_IN(idx, n, 363);
+        const unsigned qs = LiftPayload::row_sum(q);   // 16 q < 2^28
+        if (weight && l16 == 0 && qs != 0u && ok) atomicAdd(weight + idx, (unsigned long long)qs);
+        if (!sums) return;   // (uniform)
+        const int ql = (int)(q & 0xfffu), qh = (int)(q >> 12);
+        int lo = 0, hi = 0;   // of this lane's channel, l16
+#pragma unroll
+        for (int k = 0; k < SAS_FEAT_K; ++k) {
+            const int sl = (int)LiftPayload::row_sum((unsigned)__mul24(ql, fq[k]));   // (both factors fit 24 bits: full-rate multiplies)
+            const int sh = (int)LiftPayload::row_sum((unsigned)__mul24(qh, fq[k]));
+            if (l16 == k) { lo = sl; hi = sh; }
+        }
+        const long long s = (long long)hi * 4096 + (long long)lo;
+        const int ch = c0 + l16;
+        const long long at = (long long)idx * C + ch;
+        if (l16 < SAS_FEAT_K && ch < C && qs != 0u && s != 0 && ok && SAS_IN(at, n * C, 364)) atomicAdd(sums + at, (unsigned long long)s);
+    }
+    DEV void add(PixState &, const V &c0_, float vis0, const V &c1_, float vis1) const
+    {
+        give(c0_, vis0);
+        give(c1_, vis1);
+    }
+};
+
+// One workgroup per (tile, chunk of SAS_FEAT_K channels), one lane per pixel (pixel_of), on the complete depth-ordered lists the
+// frame's k_blend has just composited; every chunk recomputes alpha and T, as k_blend_features does.  Each lane reads its pixel's
+// channels of the chunk once and quantises them in registers.  A frame whose lists outgrew the key buffer adds nothing.
+template <bool FAST_EXP>
+__global__ __launch_bounds__(256) void k_lift_features(SasParams P, SasFrame f, long long n_gauss, SasLiftFeatures B, const int *perm)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kBlendLdsBytes];
+    const SasCam &c = P.cam;
+    const BlendLds L = blend_lds(s_raw);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int oi = (int)blockIdx.x, chunk = (int)blockIdx.y;
+    if (!SAS_IN(oi, f.n_tiles, 365) || oi >= f.n_tiles) return;
+    if ((long long)f.tile_offset[f.n_tiles] > f.cap) return;   // (uniform) truncated lists: the frame's second rendering adds
+    const int tile = f.tile_order[oi];
+    if (!SAS_IN(tile, f.n_tiles, 366) || tile < 0 || tile >= f.n_tiles) return;   // (uniform)
+    const int c0 = chunk * SAS_FEAT_K;
+    if (c0 >= B.C) return;   // (uniform)
+    const int tx = tile % c.tw, ty = tile / c.tw;
+    int ox, oy, ix, iy;
+    bool inside, wdone;
+    pixel_of(wv, lane, ox, oy);
+    PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
+    const long long pix = (long long)iy * c.W + ix;
+    LiftFeaturePayload pay{perm, B.sums, chunk == 0 ? B.weight : nullptr, B.n, B.C, c0, false, {}};
+    bool live = inside && SAS_IN(pix, P.out.n_pixels, 367);
+    if (live && B.mask) live = B.mask[pix] != 0;
+#pragma unroll
+    for (int k = 0; k < SAS_FEAT_K; ++k) {
+        const long long at = pix * B.C + c0 + k;
+        float x = 0.0f;
+        if (live && c0 + k < B.C && SAS_IN(at, P.out.n_pixels * B.C, 368)) x = B.images[at];
+        pay.fq[k] = LiftFeaturePayload::quantise(x, B.scale);
+    }
+    pay.live = live;
+    long long beg, end;
+    tile_segment(f, tile, beg, end);
+    const int *ids = f.sorted_ids + beg;
+    unsigned long long ph_lap_ = 0ull;
+    unsigned sync_phase = 0u;
+    blend_range<FAST_EXP>(f, n_gauss, tx, ty, pix_const(ox, oy), end > beg ? (int)(end - beg) : 0,
+                          [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay);
+}
+
 }  // namespace
 
 void sas_launch_lift_labels(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f, const SasLift &B,
@@ -2512,6 +2622,17 @@ void sas_launch_lift_labels(hipStream_t st, const SasScene &s, int tiles, const 
     if (tiles <= 0 || s.n <= 0 || (!B.votes && !B.seen)) return;
     with_flags([&](auto fast) {
         hipLaunchKernelGGL(k_lift_labels<fast()>, dim3((unsigned)tiles), dim3(256), 0, st, P, f, (long long)s.n, B, s.perm);
+    }, fast_exp);
+}
+
+void sas_launch_lift_features(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
+                              const SasLiftFeatures &B, bool fast_exp)
+{
+    if (tiles <= 0 || s.n <= 0 || (!B.sums && !B.weight)) return;
+    // (without `sums` only the first chunk has anything to add)
+    const dim3 grid((unsigned)tiles, (unsigned)(B.sums ? sas_feature_chunks(B.C) : 1));
+    with_flags([&](auto fast) {
+        hipLaunchKernelGGL(k_lift_features<fast()>, grid, dim3(256), 0, st, P, f, (long long)s.n, B, s.perm);
     }, fast_exp);
 }
 

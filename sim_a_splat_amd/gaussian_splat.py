@@ -73,6 +73,9 @@ class SplatModel:
         self.background_color = torch.tensor(list(background_color), dtype=torch.float32)
         self._raster: Optional[Rasterizer] = None
         self._bg_src = None
+        self.clip_embeds: Optional[torch.Tensor] = None   # per-Gaussian embeddings [N,D] (set_clip_embeds): what compute_semantics needs
+        self.positives: Optional[torch.Tensor] = None     # query embeddings [P,D] / [Q,D] (GaussianSplat.set_language_queries)
+        self.negatives: Optional[torch.Tensor] = None
 
     @property
     def num_points(self) -> int:
@@ -93,12 +96,49 @@ class SplatModel:
             self._raster = r
         return self._raster
 
+    def set_clip_embeds(self, embeds) -> None:
+        """Per-Gaussian embeddings ``[N,D]`` float32 in the order of the model's Gaussians (``semantics.features_from_sums`` of
+        lifted feature images, or a trained semantic field's); ``None`` forgets them."""
+        if embeds is None:
+            self.clip_embeds = None
+            return
+        e = torch.as_tensor(embeds, dtype=torch.float32)
+        if e.dim() != 2 or e.shape[0] != self.num_points or e.shape[1] < 1:
+            raise ValueError(f"clip_embeds must be [{self.num_points},D], got {tuple(e.shape)}")
+        self.clip_embeds = e
+
+    def relevancy(self, positives=None, negatives=None) -> torch.Tensor:
+        """Per-Gaussian relevancy ``[N,P]`` (``semantics.relevancy``) of ``clip_embeds`` to the queries (default: the ones set)."""
+        from .semantics import relevancy
+        if self.clip_embeds is None:
+            raise TypeError("compute_semantics is not supported by a splatfacto model")
+        p = self.positives if positives is None else positives
+        n = self.negatives if negatives is None else negatives
+        if p is None or n is None:
+            raise ValueError("no language queries: GaussianSplat.set_language_queries(positives, negatives) first")
+        return relevancy(self.clip_embeds, p, n)
+
+    def _semantic_outputs(self, V: np.ndarray, K: np.ndarray, W: int, H: int) -> Dict[str, torch.Tensor]:
+        """``relevancy [H,W,P]``: ``render_features`` of the per-Gaussian relevancy, zero background; ``clip [H,W,D]`` likewise of
+        the embeddings when ``D <= 256`` (the feature store's limit)."""
+        r = self._rasterizer()
+        out = {}
+        rel = self.relevancy()
+        for key, rows in (("relevancy", rel), ("clip", self.clip_embeds)):
+            if rows.shape[1] > 256:
+                if key == "relevancy":
+                    raise ValueError(f"{rows.shape[1]} positive queries: a frame renders at most 256")
+                continue
+            r.upload_features(rows.to(torch.float32))
+            out[key] = r.render_features(V, K, W, H, want=("features",))["features"]
+        return out
+
     @torch.no_grad()
     def get_outputs_for_camera(self, camera, obb_box=None, compute_semantics: bool = False) -> Dict[str, torch.Tensor]:
         """``camera``: a one-camera ``ns_run.Cameras`` or a ``PinholeCamera``."""
         if obb_box is not None:
             raise NotImplementedError("crop boxes are outside the render-image path (the reference passes None)")
-        if compute_semantics:
+        if compute_semantics and self.clip_embeds is None:
             raise TypeError("compute_semantics is not supported by a splatfacto model")  # reference retries without it
         c2w = camera.camera_to_worlds
         c2w = c2w[0] if c2w.dim() == 3 else c2w
@@ -106,7 +146,10 @@ class SplatModel:
         K = np.array([[_scalar(camera.fx), 0.0, _scalar(camera.cx)], [0.0, _scalar(camera.fy), _scalar(camera.cy)],
                       [0.0, 0.0, 1.0]], dtype=np.float32)
         W, H = int(_scalar(camera.width)), int(_scalar(camera.height))
-        return self.render_view(V, K, W, H)
+        out = self.render_view(V, K, W, H)
+        if compute_semantics:
+            out.update(self._semantic_outputs(V, K, W, H))
+        return out
 
     def render_view(self, V: np.ndarray, K: np.ndarray, W: int, H: int) -> Dict[str, torch.Tensor]:
         """The outputs of ``get_outputs_for_camera`` from a world-to-camera matrix and intrinsics (what ``GaussianSplat.render``
@@ -288,6 +331,62 @@ class GaussianSplat:
         c2w = [p[:3] if isinstance(p, (np.ndarray, torch.Tensor)) else np.asarray(p, dtype=np.float32)[:3] for p in poses]
         V = np.stack([viewmat_from_c2w_opengl(p) for p in c2w])
         return lift_label_views(model._rasterizer(), V, np.broadcast_to(K, (len(V), 3, 3)), W, H, label_images, n_labels, views_per_call)
+
+    def lift_features(self, poses, feature_images, feature_scale: Optional[float] = None, mask=None,
+                      views_per_call: int = 8) -> Dict[str, object]:
+        """Lift feature images of the views ``poses`` onto the model's Gaussians (``semantics.lift_feature_views``): ``poses
+        [C,>=3,4]`` as in ``lift_labels``, ``feature_images [C,H,W,D]`` float32 at camera 0's size -- a 2-D feature extractor's
+        per-pixel maps (DINO / CLIP patch features upsampled to the image), or photographs (``D = 3``) -- and ``mask [C,H,W]``
+        (0: the pixel adds nothing) or None.  ``feature_scale=None``: ``32767 / max|finite f|`` over ALL the images.  Returns
+        ``{"sums": int64 [N,D], "weight": int64 [N], "feature_scale"}`` for ``semantics.features_from_sums``, whose features
+        ``set_clip_embeds`` takes."""
+        from .semantics import lift_feature_views
+        model = self.pipeline.model
+        if not isinstance(model, SplatModel):
+            raise TypeError("lift_features needs a SplatModel")
+        _, K, W, H = self._camera0()
+        c2w = [p[:3] if isinstance(p, (np.ndarray, torch.Tensor)) else np.asarray(p, dtype=np.float32)[:3] for p in poses]
+        V = np.stack([viewmat_from_c2w_opengl(p) for p in c2w])
+        if feature_scale is None:
+            top = 0.0
+            for img in feature_images:
+                x = torch.as_tensor(img, dtype=torch.float32)
+                x = x[torch.isfinite(x)]
+                top = max(top, float(x.abs().max()) if x.numel() else 0.0)
+            feature_scale = 32767.0 / top if top > 0.0 else 1.0
+        return lift_feature_views(model._rasterizer(), V, np.broadcast_to(K, (len(V), 3, 3)), W, H, feature_images, feature_scale,
+                                  mask=mask, views_per_call=views_per_call)
+
+    def set_language_queries(self, positives, negatives, encoder=None) -> None:
+        """The queries of ``compute_semantics``: ``positives [P,D]`` and ``negatives [Q,D]`` (``Q >= 1``) as embeddings in the space
+        of the model's ``clip_embeds``.  Strings are taken only with ``encoder``, a callable mapping a list of strings to ``[*,D]``
+        embeddings: no text encoder ships here."""
+        def embed(q, name):
+            q = [q] if isinstance(q, str) else q
+            if isinstance(q, (list, tuple)) and len(q) and all(isinstance(x, str) for x in q):
+                if encoder is None:
+                    raise ValueError(f"{name} are strings and no text encoder ships here: pass embeddings [*,D], or encoder=callable "
+                                     "(list of str -> [*,D]), e.g. an OpenCLIP text tower")
+                q = encoder(list(q))
+            t = torch.as_tensor(q, dtype=torch.float32)
+            t = t.reshape(1, -1) if t.dim() == 1 else t
+            if t.dim() != 2 or t.shape[0] < 1:
+                raise ValueError(f"{name} must be [*,D] with at least one row, got {tuple(t.shape)}")
+            return t
+        p, n = embed(positives, "positives"), embed(negatives, "negatives")
+        if p.shape[1] != n.shape[1]:
+            raise ValueError(f"positives of {p.shape[1]} and negatives of {n.shape[1]} dimensions")
+        model = self.pipeline.model
+        model.positives, model.negatives = p, n
+
+    def get_semantic_point_cloud(self, positives, negatives, pcd_attr={}) -> torch.Tensor:
+        """Per-Gaussian relevancy ``[N,P]`` of the model's ``clip_embeds`` to the queries (embeddings; ``semantics.relevancy``), the
+        quantity the reference's ``get_semantic_point_cloud(positives, negatives, pcd_attr)`` thresholds its cloud by
+        (nerfstudio_utils.py:343-372).  ``pcd_attr["clip_embeds"]``, when present, stands in for the model's, as there."""
+        from .semantics import relevancy
+        if pcd_attr and "clip_embeds" in pcd_attr:
+            return relevancy(pcd_attr["clip_embeds"], positives, negatives)
+        return self.pipeline.model.relevancy(positives, negatives)
 
     def generate_RGBD_point_cloud(self, pose, max_depth: Optional[float] = 1.0):
         """RGB-D consumer of nerfstudio_utils.py:375-472 (tensor results only; the open3d cloud is

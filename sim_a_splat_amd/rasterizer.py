@@ -59,6 +59,7 @@ MATCH_CHUNK = _capi.SAS_MATCH_CHUNK   # targets match_points' kernel stages at a
 MATCH_MOMENTS = 18
 CLOUD_RESIDENT = _capi.SAS_CLOUD_RESIDENT   # survivors per cloud sample_point_cloud's sampling kernel keeps in registers: beyond it they stream
 LIFT_ONE = _capi.SAS_LIFT_ONE   # 2**32: the fixed-point unit of lift_labels' votes (a weight of 1.0)
+LIFT_FEATURE_ONE = _capi.SAS_LIFT_FEATURE_ONE   # 2**24: the fixed-point unit of lift_features' weights
 
 
 def cloud_transforms(viewmats, frame=None) -> np.ndarray:
@@ -923,6 +924,65 @@ class Rasterizer:
                                      res["seen"].data_ptr() if "seen" in res else None, stream)
         if rc != 0:
             self._check(rc, "sas_lift_labels")
+        self._in_flight(True)
+        return res
+
+    @_locked
+    def lift_features(self, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int, images: ArrayLike, *,
+                      feature_scale: Optional[float] = None, mask: Optional[ArrayLike] = None,
+                      sums: Union[torch.Tensor, None, bool] = None, weight: Union[torch.Tensor, None, bool] = None,
+                      fast_exp: bool = False, timing: bool = False) -> Dict[str, Union[torch.Tensor, float]]:
+        """Lift feature images onto the Gaussians (sas_lift_features), ``lift_labels`` with real-valued channels: ``images
+        [C,H,W,D]`` float32 (a NumPy array or a tensor; ``D`` up to 256) for the views ``viewmats [C,4,4]``, ``Ks [C,3,3]``.
+        Every Gaussian collects, from every pixel it is composited into, ``q = floor(weight * LIFT_FEATURE_ONE)`` of its
+        compositing weight into ``weight [N]`` and ``q * fq`` into ``sums [N,D]`` (int64 device tensors, the caller's Gaussian
+        order), ``fq = rint(clip(f * feature_scale, -32767, 32767))`` the pixel's quantised channels (NaN counts as 0): the
+        weighted mean feature is ``sums / (weight * feature_scale)`` (``semantics.features_from_sums``).  ``mask [C,H,W]``: pixels
+        where it is 0 add nothing.  ``sums`` / ``weight``: a tensor is ACCUMULATED into, ``None`` allocates a zeroed one,
+        ``False`` leaves that output out (not both).  ``feature_scale=None`` picks ``32767 / max|finite f|`` of THIS call's
+        images (1 if they are all zero); it is returned as ``"feature_scale"``.  Accumulating over several calls requires
+        passing one scale explicitly to all of them: sums made with different scales do not add.  Integer sums: the result
+        does not depend on the order or the batching of the views.  No sum can have overflowed while ``weight < 2**48``
+        (``features_from_sums`` checks it).  The context's current group poses apply; a scene with meshes is refused.
+        Blocking."""
+        keep, pV, pK, _, C, W, H = self._views(viewmats, Ks, (0.0, 0.0, 0.0), width, height, True)
+        if isinstance(images, torch.Tensor):
+            img = images.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        else:
+            img = torch.from_numpy(np.ascontiguousarray(np.asarray(images, dtype=np.float32))).to(self.device)
+        if img.dim() == 3:   # one channel
+            img = img[..., None]
+        if img.dim() != 4 or tuple(img.shape[:3]) != (C, H, W) or img.shape[3] < 1:
+            raise ValueError(f"images must be [{C},{H},{W},D], got {tuple(img.shape)}")
+        D = int(img.shape[3])
+        m = None
+        if mask is not None:
+            if isinstance(mask, torch.Tensor):
+                m = (mask.detach().to(self.device) != 0).to(torch.uint8).contiguous()
+            else:
+                m = torch.from_numpy(np.ascontiguousarray((np.asarray(mask) != 0).astype(np.uint8))).to(self.device)
+            if m.numel() != C * H * W:
+                raise ValueError(f"mask must be [{C},{H},{W}], got {tuple(m.shape)}")
+        if feature_scale is None:
+            finite = torch.where(torch.isfinite(img), img.abs(), torch.zeros_like(img))
+            top = float(finite.max())
+            feature_scale = 32767.0 / top if top > 0.0 else 1.0
+        scale = float(np.float32(feature_scale))
+        if sums is False and weight is False:
+            raise ValueError("lift_features: sums and weight are both left out")
+        res: Dict[str, Union[torch.Tensor, float]] = {}
+        if sums is not False:
+            res["sums"] = self._lift_buffer(sums, (self.n, D), "sums")
+        if weight is not False:
+            res["weight"] = self._lift_buffer(weight, (self.n,), "weight")
+        res["feature_scale"] = scale
+        stream = self._stream()   # (the frames run behind what this stream holds: the image copy, the zeroing)
+        rc = self._L.sas_lift_features(self._ctx, C, pV, pK, W, H, img.data_ptr(), D, scale, m.data_ptr() if m is not None else None,
+                                       _flags(True, fast_exp=fast_exp, timing=timing),
+                                       res["sums"].data_ptr() if "sums" in res else None,
+                                       res["weight"].data_ptr() if "weight" in res else None, stream)
+        if rc != 0:
+            self._check(rc, "sas_lift_features")
         self._in_flight(True)
         return res
 
