@@ -525,6 +525,52 @@ int sas_lift_features(sas_ctx *ctx, int n_views, const float *viewmats, const fl
                       const float *images, int channels, float feature_scale, const uint8_t *mask, unsigned flags,
                       int64_t *sums, int64_t *weight, void *stream);
 
+/*
+ * Backward pass of one view's compositing, in screen space ("Backward pass").  Given the gradients of a loss with
+ * respect to the frame's RAW accumulators per pixel --
+ *   g_rgb    [H,W,3] float32 DEVICE or NULL: of  sum_i c_i alpha_i T_i        (sas_render's rgb before background and clamp)
+ *   g_alpha  [H,W]   float32 DEVICE or NULL: of  1 - T_final
+ *   g_depth  [H,W]   float32 DEVICE or NULL: of  sum_i z_i alpha_i T_i        (sas_render's depth before the division by alpha)
+ * -- the call ADDS, for every Gaussian i in the CALLER's order, the gradients with respect to what the projection hands the tile
+ * kernel (contract T2/T3): d_means2d [N,2], d_conics [N,3] (a, b, c), d_opacities [N], d_colors [N,3] (the SH colour after its
+ * clamp, or the uploaded colour), d_depths [N]; float32 DEVICE, each may be NULL, not all.  With contract T6's
+ *   sigma = (a dx^2 + c dy^2) / 2 + b dx dy,   alpha = min(0.999, o e^-sigma),   w_i = alpha_i T_i,
+ *   S_i = sum_{j>i} w_j (c_j . g_rgb + z_j g_depth):
+ *   dL/dalpha_i = T_i (c_i . g_rgb + z_i g_depth) - S_i / (1 - alpha_i) + g_alpha T_final / (1 - alpha_i)
+ *   dL/dsigma_i = -alpha_i dL/dalpha_i,   dL/do_i = e^-sigma_i dL/dalpha_i,   d_colors_i += w_i g_rgb,   d_depths_i += w_i g_depth.
+ * Decisions are constants of the derivative: an entry skipped for alpha < 1/255 or sigma < 0, the entry that trips
+ * T (1 - alpha) <= 1e-4 and everything behind it, and culled Gaussians receive nothing; a clamped alpha (o e^-sigma > 0.999) passes
+ * nothing to o, the conic or the mean.  The sums over pixels are float32 atomic additions: they vary in their last bits from run
+ * to run (the lift calls' integer exactness is NOT promised here).  Gradients with respect to K, to the group poses and to mesh
+ * vertices are not computed.
+ *   flags   SAS_FAST_EXP and SAS_TIMING only.  Blocking, one view per call; several views sum by calling again on the same buffers.
+ * The frame is a SAS_FULL_SORT frame like a lift frame's: frames in flight are completed first, a frame that outgrew its key buffer
+ * adds nothing until it is rendered again, the context's current group poses apply.  SAS_ERR_NO_SCENE before an upload;
+ * SAS_ERR_INVALID for all three gradients NULL, all outputs NULL, non-positive sizes, any other flag, or a context that holds meshes.
+ */
+int sas_render_backward_screen(sas_ctx *ctx, const float *viewmat, const float *K, int width, int height, unsigned flags,
+                               const float *g_rgb, const float *g_alpha, const float *g_depth, float *d_means2d, float *d_conics,
+                               float *d_opacities, float *d_colors, float *d_depths, void *stream);
+
+/*
+ * ... and chained through the view's projection (contract T1 / T2), cull and clamp decisions as constants: the pinhole EWA Jacobian
+ * (its tx / ty clamp a constant where it binds), Sigma2 = J Sigma_c J^T + 0.3 I, the conic as its inverse, mean2d, the depth,
+ * Sigma_c = R Sigma3 R^T, the group pose of posed groups, and the SH colour max(SH(d) . coeffs + 0.5, 0) with
+ * d = normalize(mean - campos), through d to the mean and to the camera position.  The call ADDS, in the CALLER's order and with
+ * respect to the arrays last uploaded (the canonical ones: before any group pose):
+ *   d_means [N,3], d_opacities [N], d_sh [N,(L+1)^2,3] ([N,3] for a scene of plain colours),
+ *   d_quats [N,4] (the quaternion as uploaded, not normalised) and d_scales [N,3] -- or d_cov6 [N,6] (xx xy xz yy yz zz, each of the
+ *   six taken as one variable), whichever form the scene was uploaded in; asking for the other form is SAS_ERR_INVALID,
+ *   d_viewmat [3,4] row-major rows [R | t] of the view matrix, its twelve entries taken as independent, summed over the Gaussians
+ *   in a fixed order (no atomics): reproducible given the screen-space sums.
+ * float32 DEVICE, each may be NULL, not all.  A culled Gaussian receives exact zeros.  NOT differentiated: K, the group poses
+ * themselves, mesh vertices, and every decision (culls, the radius' ceil, the tile rectangle, the compositing thresholds).
+ * Everything else is as in sas_render_backward_screen, whose sums this call keeps in scratch of the context.
+ */
+int sas_render_backward(sas_ctx *ctx, const float *viewmat, const float *K, int width, int height, unsigned flags,
+                        const float *g_rgb, const float *g_alpha, const float *g_depth, float *d_means, float *d_opacities,
+                        float *d_sh, float *d_quats, float *d_scales, float *d_cov6, float *d_viewmat, void *stream);
+
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical
  * field of view; the view matrices and intrinsics are those of sas_camera_matrices. */

@@ -1,0 +1,93 @@
+"""Frames as differentiable functions of the camera and of the Gaussians ("Backward pass").
+
+``render_differentiable`` is a ``torch.autograd.Function`` around ``Rasterizer.render`` and ``Rasterizer.render_backward``: forward is
+the ordinary frame, backward chains the frame's pointwise tail in torch (``prechain``) and hands the gradients of the raw
+accumulators to the HIP backward pass.  The scene lives in the rasterizer: ``params`` only NAMES the arrays last uploaded, so that
+their gradients have somewhere to go -- after an optimiser step the caller uploads them again (``Rasterizer.upload``), or the next
+frame still shows the old scene.  The view matrix is an argument of every call and needs no upload.
+
+Not differentiated: K, the group poses, meshes (a scene with meshes is refused), and every decision of the renderer (culls, clamps,
+the alpha and transmittance thresholds), which are constants of the derivative.  The per-Gaussian sums are float atomics: gradients
+vary in their last bits from run to run.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+# params key -> key of Rasterizer.render_backward's result
+PARAM_KEYS = ("means", "opacities", "colors", "quats", "scales", "covariances")
+
+
+def prechain(rgb: torch.Tensor, alpha: torch.Tensor, depth: torch.Tensor, background, g_rgb: Optional[torch.Tensor],
+             g_alpha: Optional[torch.Tensor], g_depth: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Gradients of the raw accumulators (``sum c alpha T`` [H,W,3], ``1 - T_final`` [H,W], ``sum z alpha T`` [H,W]) from those of the
+    delivered frame ``rgb = clamp(acc + (1 - alpha) bg, 0, 1)``, ``alpha``, ``depth = acc_z / max(alpha, 1e-10)``.  The clamp passes
+    where ``rgb < 1``: with non-negative colours and background (SH colours are clamped at 0) the sum never falls below 0, so a pixel
+    at 0 sits ON the bound, where torch's clamp passes too."""
+    a = alpha.reshape(alpha.shape[0], alpha.shape[1])
+    d = depth.reshape(a.shape)
+    bg = torch.as_tensor(background, dtype=rgb.dtype, device=rgb.device).reshape(3)
+    zero = torch.zeros_like(a)
+    g_acc = torch.zeros_like(rgb) if g_rgb is None else torch.where(rgb < 1, g_rgb.reshape(rgb.shape), torch.zeros_like(rgb))
+    g_a = (zero if g_alpha is None else g_alpha.reshape(a.shape)) - (g_acc * bg).sum(dim=-1)
+    if g_depth is None:
+        g_z = zero
+    else:
+        gd = g_depth.reshape(a.shape)
+        g_z = gd / torch.clamp(a, min=1e-10)
+        g_a = g_a - torch.where(a > 1e-10, gd * d / torch.clamp(a, min=1e-10), zero)
+    return g_acc, g_a, g_z
+
+
+class _Render(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, viewmat, K, W, H, background, keys, *tensors):
+        V = np.eye(4, dtype=np.float32)
+        V[:viewmat.shape[0]] = viewmat.detach().cpu().numpy().astype(np.float32)
+        out = r.render(V, K, W, H, background)
+        rgb, alpha, depth = out["rgb"].clone(), out["alpha"].clone(), out["depth"].clone()
+        ctx.save_for_backward(rgb, alpha, depth)
+        ctx.call = (r, V, K, W, H, background, keys, tuple(viewmat.shape), viewmat.device, viewmat.dtype,
+                    [(t.device, t.dtype, tuple(t.shape)) for t in tensors])
+        return rgb, alpha, depth
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_alpha, g_depth):
+        rgb, alpha, depth = ctx.saved_tensors
+        r, V, K, W, H, background, keys, vshape, vdev, vdt, metas = ctx.call
+        g_acc, g_a, g_z = prechain(rgb, alpha, depth, background, g_rgb, g_alpha, g_depth)
+        # only what some input needs: the projection's backward neither reads nor writes the rest
+        needs = ctx.needs_input_grad[7:]
+        want = (("viewmat",) if ctx.needs_input_grad[1] else ()) + tuple(k for k, need in zip(keys, needs) if need)
+        if not want:
+            return (None,) * (7 + len(keys))
+        res = r.render_backward(V, K, W, H, g_acc, g_a, g_z, want=want)
+        grads = [None]
+        if ctx.needs_input_grad[1]:
+            gv = torch.zeros(vshape, dtype=torch.float32, device=res["viewmat"].device)
+            gv[:3] = res["viewmat"]
+            grads = [gv.to(device=vdev, dtype=vdt)]
+        for k, (dev, dt, shape), need in zip(keys, metas, needs):
+            grads.append(res[k].reshape(shape).to(device=dev, dtype=dt) if need else None)
+        return (None, grads[0], None, None, None, None, None, *grads[1:])
+
+
+def render_differentiable(r, viewmat: torch.Tensor, K, width: int, height: int, params: Optional[Dict[str, torch.Tensor]] = None,
+                          background: Optional[Sequence[float]] = None) -> Dict[str, torch.Tensor]:
+    """One frame of rasterizer ``r`` -- ``rgb [H,W,3]``, ``alpha [H,W,1]``, ``depth [H,W,1]`` on its device -- through which gradients
+    flow to ``viewmat`` (``[4,4]`` or ``[3,4]``, world to camera; its twelve upper entries are independent variables) and to those
+    tensors of ``params`` that require grad.  ``params`` maps ``means``, ``opacities``, ``colors``, ``quats``, ``scales`` or
+    ``covariances`` (``[N,6]``) to THE ARRAYS LAST UPLOADED to ``r``: the frame is rendered from the uploaded copy, not from these
+    tensors, so upload again after changing them.  ``K`` is a constant."""
+    bg = (0.0, 0.0, 0.0) if background is None else tuple(float(v) for v in background)
+    params = params or {}
+    unknown = [k for k in params if k not in PARAM_KEYS]
+    if unknown:
+        raise ValueError(f"render_differentiable: unknown params {unknown}; expected some of {PARAM_KEYS}")
+    keys = tuple(k for k in PARAM_KEYS if k in params)
+    Kc = np.ascontiguousarray(K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K), dtype=np.float32)
+    rgb, alpha, depth = _Render.apply(r, viewmat, Kc, int(width), int(height), bg, keys, *[params[k] for k in keys])
+    return dict(rgb=rgb, alpha=alpha, depth=depth)

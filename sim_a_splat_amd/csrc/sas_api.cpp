@@ -67,6 +67,14 @@ struct ViewOut {
     int64_t *lift_sums = nullptr, *lift_weight = nullptr;
     int lift_c = 0;
     float lift_scale = 0.0f;
+    // sas_render_backward_screen: the view's pixel gradients (device, each may be nullptr) and the per-Gaussian gradients the frame ADDS to
+    bool grad = false;
+    const float *grad_rgb = nullptr, *grad_alpha = nullptr, *grad_depth = nullptr;
+    float *grad_means2d = nullptr, *grad_conics = nullptr, *grad_opacities = nullptr, *grad_colors = nullptr, *grad_depths = nullptr;
+    // sas_render_backward: the chain through the projection behind it (the five sums above are then all set), what it ADDS to
+    bool grad_chain = false;
+    float *chain_means = nullptr, *chain_opacities = nullptr, *chain_sh = nullptr, *chain_quats = nullptr, *chain_scales = nullptr,
+          *chain_cov6 = nullptr, *chain_viewmat = nullptr, *chain_partial = nullptr;
 };
 
 struct RenderArgs {
@@ -247,6 +255,7 @@ struct sas_ctx : Settings {
     DevBuf match_src, match_tgt, match_keys, match_index, match_dist2, match_partial;   // scratch of sas_match_points (SasMatch)
     DevBuf cloud_par, cloud_grid, cloud_cand, cloud_blk, cloud_rows, cloud_dist, cloud_count;   // scratch of sas_sample_points (SasCloud)
     DevBuf fuse_par;   // per-view rows and keep table of sas_fuse_depth (SasFuse)
+    DevBuf grad_screen;   // sas_render_backward: [10 n] screen-space sums + [ceil(n / 256)][12] view-matrix rows (SasGradProj)
     int match_cus = 0;   // compute units of the device, asked once (the slice count of sas_match_points)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
     // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
@@ -791,7 +800,7 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
     } else {
         // (a pair shares its poses: the leader's block serves both views; the triangle setup of a mesh frame reads the
         // slot's poses on the device)
-        enqueue_poses(c, sl, nv, st, ld.mesh);
+        enqueue_poses(c, sl, nv, st, ld.mesh || a.out.grad_chain);   // (k_grad_project reads the poses on the device)
         if (timing) HIP_TRY(c, hipEventRecord(ld.ev[0], st));
         if (follower) {
             sas_launch_project2(st, c->scene, P, f, follower->params, frame_of(c, *follower));
@@ -842,6 +851,17 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
             const SasLiftFeatures B{a.out.lift_images, a.out.lift_mask, (unsigned long long *)a.out.lift_sums,
                                     (unsigned long long *)a.out.lift_weight, c->scene.n, a.out.lift_c, a.out.lift_scale};
             sas_launch_lift_features(st, c->scene, tiles, P, f, B, fast_exp);
+        }
+        if (a.out.grad) {   // a backward frame: the same lists walked there and back (sas_grad.hip)
+            const SasGrad B{a.out.grad_rgb, a.out.grad_alpha, a.out.grad_depth, a.out.grad_means2d, a.out.grad_conics,
+                            a.out.grad_opacities, a.out.grad_colors, a.out.grad_depths, c->scene.n};
+            sas_launch_grad_tiles(st, c->scene, tiles, P, f, B, fast_exp);
+            if (a.out.grad_chain) {
+                const SasGradProj Q{a.out.grad_means2d, a.out.grad_conics, a.out.grad_opacities, a.out.grad_colors, a.out.grad_depths,
+                                    a.out.chain_means, a.out.chain_opacities, a.out.chain_sh, a.out.chain_quats, a.out.chain_scales,
+                                    a.out.chain_cov6, a.out.chain_viewmat ? a.out.chain_partial : nullptr, a.out.chain_viewmat, c->scene.n};
+                sas_launch_grad_project(st, c->scene, P, f, Q);
+            }
         }
     } else if (nv > 1) {
         // (quad: by the size of one view (prepare_frame): groups of four 300-tile views still gain (vec_env_probe))
@@ -1404,7 +1424,7 @@ static void fill_args(RenderArgs &a, const ViewCall &v, int width, int height, c
     const ViewOut &o = v.out;
     a.solo = solo;
     // rgb8 beside rgb8_host is the context's own staging frame (sas_render_batch_host): nothing of the caller's on the device
-    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || o.labels || o.lift_labels || o.lift_images || (o.rgb8 && !o.rgb8_host);
+    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || o.labels || o.lift_labels || o.lift_images || o.grad || (o.rgb8 && !o.rgb8_host);
     memcpy(a.viewmat, v.viewmat, sizeof(a.viewmat));
     memcpy(a.K, v.K, sizeof(a.K));
     for (int k = 0; k < 3; ++k) a.bg[k] = background ? background[k] : 0.0f;
@@ -2226,6 +2246,75 @@ int sas_lift_features(sas_ctx *c, int n_views, const float *viewmats, const floa
     });
 }
 
+// The backward pass of one view on its complete lists (k_grad_tiles): a lift frame whose sums are the screen-space gradients.
+int sas_render_backward_screen(sas_ctx *c, const float *viewmat, const float *K, int width, int height, unsigned flags,
+                               const float *g_rgb, const float *g_alpha, const float *g_depth, float *d_means2d, float *d_conics,
+                               float *d_opacities, float *d_colors, float *d_depths, void *stream)
+{
+    if (const int rc = check_lift(c, "sas_render_backward_screen", flags)) return rc;
+    if (!g_rgb && !g_alpha && !g_depth) return fail(c, SAS_ERR_INVALID, "sas_render_backward_screen: g_rgb, g_alpha and g_depth are all NULL");
+    if (!d_means2d && !d_conics && !d_opacities && !d_colors && !d_depths)
+        return fail(c, SAS_ERR_INVALID, "sas_render_backward_screen: every output is NULL");
+    return lift_views(c, "sas_render_backward_screen", 1, viewmat, K, width, height, flags, stream, [&](int) {
+        ViewOut o;
+        o.grad = true;
+        o.grad_rgb = g_rgb;
+        o.grad_alpha = g_alpha;
+        o.grad_depth = g_depth;
+        o.grad_means2d = d_means2d;
+        o.grad_conics = d_conics;
+        o.grad_opacities = d_opacities;
+        o.grad_colors = d_colors;
+        o.grad_depths = d_depths;
+        return o;
+    });
+}
+
+// ... and chained through the view's projection (k_grad_project): the screen-space sums live in the context's scratch, zeroed on the
+// caller's stream in front of the frame.
+int sas_render_backward(sas_ctx *c, const float *viewmat, const float *K, int width, int height, unsigned flags, const float *g_rgb,
+                        const float *g_alpha, const float *g_depth, float *d_means, float *d_opacities, float *d_sh, float *d_quats,
+                        float *d_scales, float *d_cov6, float *d_viewmat, void *stream)
+{
+    const char *who = "sas_render_backward";
+    if (const int rc = check_lift(c, who, flags)) return rc;
+    if (!g_rgb && !g_alpha && !g_depth) return fail(c, SAS_ERR_INVALID, "%s: g_rgb, g_alpha and g_depth are all NULL", who);
+    if (!d_means && !d_opacities && !d_sh && !d_quats && !d_scales && !d_cov6 && !d_viewmat)
+        return fail(c, SAS_ERR_INVALID, "%s: every output is NULL", who);
+    if (c->scene.cov_mode ? (d_quats || d_scales) : d_cov6 != nullptr)
+        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as %s: ask for %s", who, c->scene.cov_mode ? "covariances" : "quaternions and scales",
+                    c->scene.cov_mode ? "d_cov6" : "d_quats / d_scales");
+    if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->scene.n, n_wg = (n + 255) / 256;
+    const size_t floats = 10 * n + 12 * n_wg;
+    if (const int rc = ensure(c, c->grad_screen, floats * sizeof(float))) return rc;
+    float *s = (float *)c->grad_screen.p;
+    if (const int rc = complete_all(c)) return rc;   // (nothing in flight reads the scratch)
+    HIP_TRY(c, hipMemsetAsync(s, 0, floats * sizeof(float), (hipStream_t)stream));
+    return lift_views(c, who, 1, viewmat, K, width, height, flags, stream, [&](int) {
+        ViewOut o;
+        o.grad = o.grad_chain = true;
+        o.grad_rgb = g_rgb;
+        o.grad_alpha = g_alpha;
+        o.grad_depth = g_depth;
+        o.grad_means2d = s;
+        o.grad_conics = s + 2 * n;
+        o.grad_opacities = s + 5 * n;
+        o.grad_colors = s + 6 * n;
+        o.grad_depths = s + 9 * n;
+        o.chain_partial = s + 10 * n;
+        o.chain_means = d_means;
+        o.chain_opacities = d_opacities;
+        o.chain_sh = d_sh;
+        o.chain_quats = d_quats;
+        o.chain_scales = d_scales;
+        o.chain_cov6 = d_cov6;
+        o.chain_viewmat = d_viewmat;
+        return o;
+    });
+}
+
 static int render_batch_host_impl(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height,
                                   const float *background, unsigned flags, uint8_t *rgb8_host, void *stream, const PoseSets &ps)
 {
@@ -2304,17 +2393,18 @@ extern "C" int sas_debug_bounds_query(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_match(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_cloud(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_fuse(unsigned long long *out, int reset);
+extern "C" int sas_debug_bounds_grad(unsigned long long *out, int reset);
 /* Bounds-checked build only: out[0] = guarded accesses found out of range since the last reset (they were
  * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none). */
 int sas_debug_bounds(unsigned long long *out, int reset)
 {
-    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0};
+    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0};
     if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset) ||
         sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset) || sas_debug_bounds_match(p, reset) ||
-        sas_debug_bounds_cloud(s, reset) || sas_debug_bounds_fuse(f, reset))
+        sas_debug_bounds_cloud(s, reset) || sas_debug_bounds_fuse(f, reset) || sas_debug_bounds_grad(g, reset))
         return SAS_ERR_HIP;
-    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : (s[0] ? s : f)))));
-    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0] + f[0];
+    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : (s[0] ? s : (f[0] ? f : g))))));
+    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0] + f[0] + g[0];
     out[1] = first[1]; out[2] = first[2]; out[3] = first[3];
     return SAS_OK;
 }

@@ -1,4 +1,4 @@
-// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip and sas_fuse.hip.
+// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip and sas_grad.hip.
 // Everything here follows the arithmetic contract of DESIGN.md: IEEE binary32 operations, fused
 // only where fma_() is written (translation units are built with -ffp-contract=off).
 #pragma once
@@ -109,8 +109,7 @@ DEV int lane_get(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 DEV unsigned lane_get(unsigned v, int src) { return (unsigned)__builtin_amdgcn_readlane((int)v, src); }
 DEV float lane_get(float v, int src) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src)); }
 
-// ---- contract logarithm (mirrors sas_oracle_logf; the contract exponential lives with its only
-//      user, the compositing loop: c_expf_neg in sas_tile.hip) ------------------------------------
+// ---- contract logarithm (mirrors sas_oracle_logf) ------------------------------------------------
 DEV float c_logf(float x)
 {
     unsigned u = __float_as_uint(x);
@@ -170,3 +169,27 @@ DEV void rot_sym3(const float *R, const float *s, float *out)
     out[5] = dot3(T[2][0], T[2][1], T[2][2], R[6], R[7], R[8]);
 }
 
+// ---- contract T6 per (pixel, splat) pair: shared by the compositing loop (sas_tile.hip) and its backward pass (sas_grad.hip) ----------
+// Contract exp for an argument the caller has clamped to [-86, rounding noise] (sas_oracle_expf clamps to
+// [-86, 86]; -sigma never comes near the upper end).  n = round(x log2 e) is read off the low mantissa bits
+// of x log2 e + 1.5 * 2^23 and added straight into the exponent field.
+DEV float c_expf_neg(float x, float e5 /* 0.0013400432653725147f, pinned in a register */)
+{
+    const float magic = 12582912.0f;
+    const float tm = fma_(x, 1.4426950408889634f, magic);
+    const float n = tm - magic;
+    const float fr = fma_(x, 1.4426950408889634f, -n);
+    float p = fma_(e5, fr, 0.009676037356257439f);
+    p = fma_(p, fr, 0.05550327152013779f);
+    p = fma_(p, fr, 0.2402210682630539f);
+    p = fma_(p, fr, 0.6931471824645996f);
+    p = fma_(p, fr, 1.0000001192092896f);
+    return __uint_as_float(__float_as_uint(p) + (__float_as_uint(tm) << 23));
+}
+
+// Contract T6 for one (pixel, splat) pair, step by step.  (dx, dy) = (u - x, v - y); K = (u, v, A/2, B), H = (C/2, opacity) as staged
+// by blend_range.  A trip runs the steps of its entries side by side, in this order: where they are called decides the loop's schedule.
+DEV float splat_sigma(const float4 K, const float2 H, float dx, float dy) { return fma_(dx, fma_(K.w, dy, K.z * dx), (H.x * dy) * dy); }
+template <bool FAST_EXP>
+DEV float splat_exp(float sigma, float sE5) { return FAST_EXP ? __expf(fmaxf(-sigma, -86.0f)) : c_expf_neg(fmaxf(-sigma, -86.0f), sE5); }
+DEV float splat_alpha(const float2 H, float E) { return fminf(kMaxAlpha, H.y * E); }

@@ -1,4 +1,4 @@
-// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -241,6 +241,38 @@ struct SasLiftFeatures {
 // after sas_launch_blend, on the same frame (no meshes): one workgroup per (tile, chunk of SAS_FEAT_K channels)
 void sas_launch_lift_features(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f,
                               const SasLiftFeatures &B, bool fast_exp);
+// Backward pass (sas_render_backward_screen; DESIGN.md 3, "Backward pass"): the derivative of a frame's raw accumulators with respect to
+// what the projection staged per Gaussian.  Every output is float32 in the caller's Gaussian order and is ADDED to (float atomics).
+struct SasGrad {
+    const float *g_rgb;      // [H,W,3] device, or nullptr: gradient of sum c alpha T
+    const float *g_alpha;    // [H,W] or nullptr: of 1 - T_final
+    const float *g_depth;    // [H,W] or nullptr: of sum z alpha T
+    float *d_means2d;        // [n,2] or nullptr
+    float *d_conics;         // [n,3] (a, b, c) or nullptr
+    float *d_opacities;      // [n] or nullptr
+    float *d_colors;         // [n,3] or nullptr
+    float *d_depths;         // [n] or nullptr
+    long long n;             // Gaussians of the scene
+};
+// after sas_launch_blend, on the same frame (no meshes): one workgroup per tile (sas_grad.hip)
+void sas_launch_grad_tiles(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f, const SasGrad &B,
+                           bool fast_exp);
+// ... and the chain through the view's projection (sas_render_backward): from the screen-space sums of sas_launch_grad_tiles (s_*, all
+// five required, the caller's order) to the uploaded arrays and the view matrix.  Every output is ADDED to and may be nullptr.
+struct SasGradProj {
+    const float *s_means2d, *s_conics, *s_opacities, *s_colors, *s_depths;
+    float *d_means;          // [n,3]
+    float *d_opacities;      // [n]
+    float *d_sh;             // [n,(L+1)^2,3]; [n,3] for a scene of plain colours
+    float *d_quats;          // [n,4]  (scenes uploaded as quaternion and scale)
+    float *d_scales;         // [n,3]
+    float *d_cov6;           // [n,6]  (scenes uploaded as covariances)
+    float *partial;          // [ceil(n / 256)][12] scratch: one row per workgroup, or nullptr: no view-matrix gradient
+    float *d_viewmat;        // [3,4] rows [R | t] (with partial)
+    long long n;
+};
+// behind sas_launch_grad_tiles on the same frame, which keeps its info records and has its group poses on the device
+void sas_launch_grad_project(hipStream_t st, const SasScene &s, const SasParams &P, const SasFrame &f, const SasGradProj &B);
 // store <- features [nt,C] (device; nullptr: one-hot of the triangles' pose groups), through finite_colour
 void sas_launch_mesh_feature_store(hipStream_t st, int64_t nt, const int4 *tri, const float *src, int C, float *store);
 

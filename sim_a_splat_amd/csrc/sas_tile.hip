@@ -531,29 +531,8 @@ DEV PixState pixel_begin(const SasCam &c, int tx, int ty, int ox, int oy, int &i
 }
 typedef float f32x3 __attribute__((ext_vector_type(3)));
 
-// Contract exp for an argument the caller has clamped to [-86, rounding noise] (sas_oracle_expf clamps to
-// [-86, 86]; -sigma never comes near the upper end).  n = round(x log2 e) is read off the low mantissa bits
-// of x log2 e + 1.5 * 2^23 and added straight into the exponent field.
-DEV float c_expf_neg(float x, float e5 /* 0.0013400432653725147f, pinned in a register */)
-{
-    const float magic = 12582912.0f;
-    const float tm = fma_(x, 1.4426950408889634f, magic);
-    const float n = tm - magic;
-    const float fr = fma_(x, 1.4426950408889634f, -n);
-    float p = fma_(e5, fr, 0.009676037356257439f);
-    p = fma_(p, fr, 0.05550327152013779f);
-    p = fma_(p, fr, 0.2402210682630539f);
-    p = fma_(p, fr, 0.6931471824645996f);
-    p = fma_(p, fr, 1.0000001192092896f);
-    return __uint_as_float(__float_as_uint(p) + (__float_as_uint(tm) << 23));
-}
-
-// Contract T6 for one (pixel, splat) pair, step by step.  (dx, dy) = (u - x, v - y); K = (u, v, A/2, B), H = (C/2, opacity) as staged
-// by blend_range.  A trip runs the steps of its entries side by side, in this order: where they are called decides the loop's schedule.
-DEV float splat_sigma(const float4 K, const float2 H, float dx, float dy) { return fma_(dx, fma_(K.w, dy, K.z * dx), (H.x * dy) * dy); }
-template <bool FAST_EXP>
-DEV float splat_exp(float sigma, float sE5) { return FAST_EXP ? __expf(fmaxf(-sigma, -86.0f)) : c_expf_neg(fmaxf(-sigma, -86.0f), sE5); }
-DEV float splat_alpha(const float2 H, float E) { return fminf(kMaxAlpha, H.y * E); }
+// (the contract exponential c_expf_neg and the per-pair steps splat_sigma / splat_exp / splat_alpha live in sas_device.h: the backward pass
+// of sas_grad.hip recomputes the alpha this loop composited with the same functions)
 
 // a constant pinned in a VGPR (the compiler would re-materialise it with a v_mov inside the loop:
 // an SGPR cannot sit beside the literal of v_fmaak on gfx9's one-read constant bus)

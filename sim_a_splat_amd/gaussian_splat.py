@@ -357,6 +357,22 @@ class GaussianSplat:
         return lift_feature_views(model._rasterizer(), V, np.broadcast_to(K, (len(V), 3, 3)), W, H, feature_images, feature_scale,
                                   mask=mask, views_per_call=views_per_call)
 
+    def refine_pose(self, pose, image, iters: int = 300, mask=None) -> np.ndarray:
+        """The camera pose near ``pose`` (``[>=3,4]`` camera-to-world, OpenGL axes, as ``render(pose)`` takes one) from which the model
+        looks like ``image [H,W,3]`` (float, 0..1, camera 0's size): ``register.refine_camera_pose`` by render-and-compare through the
+        HIP backward pass, over the model's background colour.  Returns the refined camera-to-world ``[4,4]`` float64.  The intrinsics are
+        camera 0's and stay fixed."""
+        from .register import refine_camera_pose
+        from .synthetic import c2w_opengl_from_viewmat
+        model = self.pipeline.model
+        if not isinstance(model, SplatModel):
+            raise TypeError("refine_pose needs a SplatModel")
+        _, K, W, H = self._camera0()
+        c2w = pose[:3] if isinstance(pose, (np.ndarray, torch.Tensor)) else np.asarray(pose, dtype=np.float32)[:3]
+        bg = tuple(float(v) for v in model.background_color.reshape(-1))   # the frames are compared as render(pose) delivers them
+        res = refine_camera_pose(model._rasterizer(), image, viewmat_from_c2w_opengl(c2w), K, W, H, iters, mask=mask, background=bg)
+        return c2w_opengl_from_viewmat(res.viewmat)
+
     def set_language_queries(self, positives, negatives, encoder=None) -> None:
         """The queries of ``compute_semantics``: ``positives [P,D]`` and ``negatives [Q,D]`` (``Q >= 1``) as embeddings in the space
         of the model's ``clip_embeds``.  Strings are taken only with ``encoder``, a callable mapping a list of strings to ``[*,D]``

@@ -245,6 +245,7 @@ class Rasterizer:
             raise SasError(f"sas_create(device={self.device.index}) failed with status {rc}")
         self.n = 0
         self.n_groups = 0
+        self.sh_degree, self.covariance_form = 3, "quats"   # of the scene last uploaded (render_backward shapes its outputs by them)
         self._forget("scene")
         self._keep = []  # outputs of in-flight async frames (the C ABI keeps up to four)
         self._argcache = {}  # id(argument) -> (argument, float32 array, address): _host_arg
@@ -331,6 +332,7 @@ class Rasterizer:
                     "sas_scene_upload")
         self.n = n
         self.n_groups = int(n_groups) if group_id is not None else 0
+        self.sh_degree, self.covariance_form = int(sh_degree), "quats" if pq is not None else "cov6"
         self._forget("scene")
 
     @_locked
@@ -983,6 +985,76 @@ class Rasterizer:
                                        res["weight"].data_ptr() if "weight" in res else None, stream)
         if rc != 0:
             self._check(rc, "sas_lift_features")
+        self._in_flight(True)
+        return res
+
+    def _grad_image(self, g, shape: Tuple[int, ...], name: str) -> Optional[torch.Tensor]:
+        """A pixel-gradient image of ``render_backward`` on the device, float32, or None."""
+        if g is None:
+            return None
+        t = g.detach() if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(g, dtype=np.float32)))
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if t.numel() != int(np.prod(shape)):
+            raise ValueError(f"{name} must be {list(shape)}, got {tuple(t.shape)}")
+        return t
+
+    @_locked
+    def render_backward(self, viewmat: ArrayLike, K: ArrayLike, width: int, height: int, g_rgb=None, g_alpha=None, g_depth=None, *,
+                        screen_space: bool = False, out: Optional[Dict[str, torch.Tensor]] = None,
+                        want: Optional[Iterable[str]] = None, fast_exp: bool = False) -> Dict[str, torch.Tensor]:
+        """The backward pass of one view (sas_render_backward; DESIGN.md 3, "Backward pass").  ``g_rgb [H,W,3]``, ``g_alpha [H,W]``,
+        ``g_depth [H,W]`` (tensors or arrays, each may be None, not all) are the gradients of a loss with respect to the frame's RAW
+        accumulators: ``sum c alpha T`` (rgb before background and clamp), ``1 - T_final`` and ``sum z alpha T`` (depth before the
+        division by alpha); ``autograd.render_differentiable`` does that pre-chain.  Returns float32 device tensors in the caller's
+        Gaussian order, with respect to the arrays last uploaded: ``means [N,3]``, ``opacities [N]``, ``colors [N,K,3]`` (the SH
+        coefficients; ``[N,1,3]`` plain colours), ``quats [N,4]`` and ``scales [N,3]`` or ``covariances [N,6]`` as the scene was
+        uploaded, and ``viewmat [3,4]`` (rows ``[R | t]``, twelve independent entries).  ``screen_space=True`` (sas_render_backward_screen)
+        stops in front of the projection: ``means2d [N,2]``, ``conics [N,3]``, ``opacities [N]``, ``colors [N,3]``, ``depths [N]``.
+        ``out``: a dict of such tensors to ACCUMULATE into (several views sum); missing keys are allocated zeroed.  ``want``: only
+        these keys are computed and returned (the others are NULL to the C call, whose kernels then neither read nor write them):
+        a pose optimiser asks for ``("viewmat",)`` alone.
+        Decisions (culls, clamps, the compositing thresholds) are constants; K, the group poses and meshes are not differentiated (a
+        scene with meshes is refused).  The sums over pixels are float atomics: last bits vary from run to run.  Blocking."""
+        V, pV = self._host_arg(viewmat, 16)
+        Kc, pK = self._host_arg(K, 9)
+        W, H = int(width), int(height)
+        gr = self._grad_image(g_rgb, (H, W, 3), "g_rgb")
+        ga = self._grad_image(g_alpha, (H, W), "g_alpha")
+        gd = self._grad_image(g_depth, (H, W), "g_depth")
+        if gr is None and ga is None and gd is None:
+            raise ValueError("render_backward: g_rgb, g_alpha and g_depth are all None")
+        n = self.n
+        if screen_space:
+            shapes = dict(means2d=(n, 2), conics=(n, 3), opacities=(n,), colors=(n, 3), depths=(n,))
+        else:
+            kk = (self.sh_degree + 1) ** 2 if self.sh_degree >= 0 else 1
+            shapes = dict(means=(n, 3), opacities=(n,), colors=(n, kk, 3), viewmat=(3, 4))
+            shapes.update(dict(quats=(n, 4), scales=(n, 3)) if self.covariance_form == "quats" else dict(covariances=(n, 6)))
+        if want is not None:
+            want = tuple(want)
+            unknown = [k for k in want if k not in shapes]
+            if unknown or not want:
+                raise ValueError(f"render_backward: want must name some of {tuple(shapes)}, got {want}")
+            shapes = {k: v for k, v in shapes.items() if k in want}
+        res: Dict[str, torch.Tensor] = {}
+        for name, shape in shapes.items():
+            t = out.get(name) if out else None
+            if t is None:
+                t = torch.zeros(shape, dtype=torch.float32, device=self.device)
+            elif not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor {shape} on {self.device}")
+            res[name] = t
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        flags, stream = _flags(True, fast_exp=fast_exp), self._stream()
+        if screen_space:
+            rc = self._L.sas_render_backward_screen(self._ctx, pV, pK, W, H, flags, ptr(gr), ptr(ga), ptr(gd), ptr(res.get("means2d")),
+                                                    ptr(res.get("conics")), ptr(res.get("opacities")), ptr(res.get("colors")), ptr(res.get("depths")), stream)
+        else:
+            rc = self._L.sas_render_backward(self._ctx, pV, pK, W, H, flags, ptr(gr), ptr(ga), ptr(gd), ptr(res.get("means")), ptr(res.get("opacities")),
+                                             ptr(res.get("colors")), ptr(res.get("quats")), ptr(res.get("scales")), ptr(res.get("covariances")),
+                                             ptr(res.get("viewmat")), stream)
+        if rc != 0:
+            self._check(rc, "sas_render_backward_screen" if screen_space else "sas_render_backward")
         self._in_flight(True)
         return res
 

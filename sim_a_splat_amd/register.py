@@ -175,6 +175,114 @@ def register_robot(means, urdf, joint_config, robot_description_dir: str, packag
     return result, trans_init
 
 
+# ---- camera pose from a picture: render and compare ("Backward pass") -----------------------------------------------------
+@dataclass
+class PoseRefinement:
+    viewmat: np.ndarray                 # 4x4 float64, world -> camera (OpenCV axes)
+    loss: float                         # mean squared colour difference of the last evaluation, at full size
+    history: List[Tuple[int, float]] = field(default_factory=list)   # (downsampling factor, loss) of every evaluation
+
+
+def se3_exp(xi) -> np.ndarray:
+    """4x4 rigid motion of the twist ``xi = (omega, v)``: rotation by Rodrigues' formula, translation ``V(omega) v``."""
+    xi = np.asarray(xi, np.float64).reshape(6)
+    w, v = xi[:3], xi[3:]
+    th = float(np.linalg.norm(w))
+    Wx = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-8:
+        A, B, C = 1.0 - th * th / 6.0, 0.5 - th * th / 24.0, 1.0 / 6.0 - th * th / 120.0
+    else:
+        A, B, C = np.sin(th) / th, (1.0 - np.cos(th)) / (th * th), (th - np.sin(th)) / th ** 3
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + A * Wx + B * (Wx @ Wx)
+    T[:3, 3] = (np.eye(3) + B * Wx + C * (Wx @ Wx)) @ v
+    return T
+
+
+def twist_gradient(d_viewmat, viewmat) -> np.ndarray:
+    """Gradient with respect to a camera-frame twist ``xi`` at 0 of a loss whose gradient with respect to the rows ``[R | t]`` of
+    ``viewmat`` is ``d_viewmat [3,4]``, for ``viewmat(xi) = se3_exp(xi) viewmat``."""
+    G = np.asarray(d_viewmat, np.float64).reshape(-1, 4)[:3]
+    A = np.asarray(viewmat, np.float64).reshape(4, 4)[:3]
+    g = np.zeros(6)
+    for k in range(3):
+        e = np.zeros(3)
+        e[k] = 1.0
+        Ek = np.array([[0.0, -e[2], e[1]], [e[2], 0.0, -e[0]], [-e[1], e[0], 0.0]])
+        g[k] = float(np.sum(G * (Ek @ A)))
+    g[3:] = G[:, 3]
+    return g
+
+
+def refine_camera_pose(r, image, V0, K, W: int, H: int, iters: int = 300, mask=None, *, factors: Sequence[int] = (4, 2, 1),
+                       step: Tuple[float, float] = (0.01, 0.01), background=(0.0, 0.0, 0.0),
+                       pivot_depth: Optional[float] = None, loss_and_grad: Optional[Callable] = None) -> PoseRefinement:
+    """Refine the camera pose ``V0`` (4x4 world -> camera) so that rasterizer ``r``'s frame looks like ``image [H,W,3]`` (float, 0..1):
+    Adam on an se(3) increment of the camera (a twist about the point ``pivot_depth`` in front of the camera -- None: the median depth
+    of the first frame's covered pixels -- re-centred on the current pose after every step: turning about the scene instead of about the
+    camera keeps rotation and translation from trading against each other), minimising
+    the mean squared colour difference over the pixels where ``mask [H,W]`` is non-zero, coarse to fine: the iterations are split
+    evenly over ``factors``, each rendering at ``K / factor`` against the area-averaged image.  ``step``: Adam's step in radians and in
+    scene units at the start of a level; it falls to a twentieth over the level.  Gradients come from
+    ``autograd.render_differentiable``; ``loss_and_grad(V, K, W, H, target, mask) -> (loss, d_viewmat [3,4])`` replaces the renderer
+    (tests run the same optimiser on a CPU reference).  What the renderer does not differentiate -- K, decisions -- stays fixed."""
+    import torch
+    import torch.nn.functional as Fn
+    dev = getattr(r, "device", "cpu")
+    img = torch.as_tensor(np.asarray(_host(image), np.float32)).reshape(H, W, 3)
+    m = torch.ones((H, W), dtype=torch.float32) if mask is None else (torch.as_tensor(np.asarray(_host(mask))) != 0).to(torch.float32).reshape(H, W)
+    K0 = np.asarray(_host(K), np.float64).reshape(3, 3)
+    V = np.asarray(_host(V0), np.float64).reshape(4, 4).copy()
+
+    def evaluate(Vc, Kc, w, h, target, tm):
+        if loss_and_grad is not None:
+            return loss_and_grad(Vc, Kc, w, h, target, tm)
+        from .autograd import render_differentiable
+        vm = torch.tensor(Vc, dtype=torch.float32, device=dev, requires_grad=True)
+        out = render_differentiable(r, vm, Kc.astype(np.float32), w, h, background=background)
+        t, k = target.to(out["rgb"].device), tm.to(out["rgb"].device)
+        loss = (k[..., None] * (out["rgb"] - t) ** 2).sum() / (3.0 * torch.clamp(k.sum(), min=1.0))
+        loss.backward()
+        return float(loss.detach()), vm.grad[:3].double().cpu().numpy()
+
+    if pivot_depth is None and loss_and_grad is None:
+        first = r.render(V.astype(np.float32), K0.astype(np.float32), W, H, background)
+        seen = first["depth"][first["alpha"] > 0.5]
+        pivot_depth = float(seen.median()) if seen.numel() else 1.0
+    Tp = np.eye(4)
+    Tp[2, 3] = 1.0 if pivot_depth is None else float(pivot_depth)
+    Tpi = np.linalg.inv(Tp)
+    res = PoseRefinement(V, float("nan"))
+    per = max(1, int(iters) // max(1, len(factors)))
+    for f in factors:
+        w, h = max(1, W // f), max(1, H // f)
+        if f == 1:
+            target, tm = img, m
+        else:
+            # area average of the masked image, renormalised by the mask's coverage
+            cover = Fn.interpolate(m[None, None], size=(h, w), mode="area")[0, 0]
+            target = Fn.interpolate((img * m[..., None]).permute(2, 0, 1)[None], size=(h, w), mode="area")[0].permute(1, 2, 0) / torch.clamp(cover, min=1e-6)[..., None]
+            tm = (cover > 0.5).to(torch.float32)
+        Kc = K0.copy()
+        Kc[0] *= w / W
+        Kc[1] *= h / H
+        m1, m2 = np.zeros(6), np.zeros(6)
+        for it in range(per):
+            loss, dV = evaluate(V, Kc, w, h, target, tm)
+            res.history.append((int(f), loss))
+            g = twist_gradient(dV, V)
+            g[:3] += np.cross(g[3:], Tp[:3, 3])   # the same twist about the pivot
+            m1 = 0.9 * m1 + 0.1 * g
+            m2 = 0.999 * m2 + 0.001 * g * g
+            hat = (m1 / (1 - 0.9 ** (it + 1))) / (np.sqrt(m2 / (1 - 0.999 ** (it + 1))) + 1e-12)
+            decay = 0.05 ** (it / max(1, per - 1))
+            V = Tp @ se3_exp(-np.concatenate([step[0] * decay * hat[:3], step[1] * decay * hat[3:]])) @ Tpi @ V
+    res.viewmat = V
+    res.loss = evaluate(V, K0, W, H, img, m)[0]
+    res.history.append((1, res.loss))
+    return res
+
+
 def main(argv: Optional[Sequence[str]] = None, matcher=None) -> int:
     import argparse
     from . import io, poses, segment
