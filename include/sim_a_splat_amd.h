@@ -571,6 +571,53 @@ int sas_render_backward(sas_ctx *ctx, const float *viewmat, const float *K, int 
                         const float *g_rgb, const float *g_alpha, const float *g_depth, float *d_means, float *d_opacities,
                         float *d_sh, float *d_quats, float *d_scales, float *d_cov6, float *d_viewmat, void *stream);
 
+/*
+ * Optimiser step on the resident scene ("Optimiser step"): one fused Adam update, in place, of the planes the frames read.
+ * The gradients are what sas_render_backward writes -- float32 DEVICE arrays in the CALLER's order, with respect to the activated arrays
+ * last uploaded; summed over as many views as the caller likes -- and each may be NULL.
+ *   VARIABLES  means [N,3]; log(scales) [N,3]; logit(opacities) [N]; quats [N,4] as uploaded (not normalised); the SH coefficients
+ *              [N,(L+1)^2,3] (or the plain colour [N,3]), whose DC triple steps with lr_sh_dc and the rest with lr_sh_rest.  The
+ *              gradients are chained through the activations: d_logit = d_o o (1 - o), d_logscale = d_s s, per element.
+ *   FIXED      the covariances of a scene uploaded as cov6 (d_quats or d_scales is then SAS_ERR_INVALID; means, opacities and colours
+ *              step), the group ids, N and the storage order, and a group whose gradient is NULL or whose learning rate is 0: it is
+ *              neither read nor written and holds no state.  An opacity outside (0, 1), and a scale component that is not a positive
+ *              finite number, have no raw value: they stay as they are.
+ *   UPDATE     per element, with t = step (1-based), all in float32:  m = beta1 m + (1 - beta1) g,  v = beta2 v + (1 - beta2) g^2,
+ *              x -= lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps);  then scales = exp, opacities = 1 / (1 + exp(-x)).
+ *              A non-finite gradient element (after the chain) leaves its variable and both moments untouched.
+ *              SAS_ADAM_VISIBLE_ONLY: a Gaussian whose gradient is an exact zero in every stepped array is skipped whole -- the
+ *              backward pass gives exact zeros to culled Gaussians, so momentum does not drag what no view of the batch saw.
+ *   STATE      the moments, log(scale) and logit(opacity) belong to the context, in storage order, allocated for a group the first
+ *              time it is stepped (the raw values then come from the resident ones; later steps never invert an activation).
+ *              sas_scene_upload and sas_scene_adam_reset drop it; the caller owns the step count.
+ * The call completes the frames in flight, then only enqueues on `stream` (behind whatever produced the gradients there); frames
+ * submitted afterwards run behind the step.  No host copy, no sort, no device-wide synchronisation.  It INVALIDATES the last frame:
+ * sas_read_projection and sas_read_tile_lists report SAS_ERR_NO_SCENE until a frame has been rendered again.  Features, meshes, group
+ * poses and link constants stay.  SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID for cfg NULL, every gradient NULL, step < 1, a
+ * negative or non-finite learning rate, beta outside [0, 1), a negative or non-finite eps, an unknown flag, d_quats or d_scales on a
+ * cov6 scene.
+ */
+#define SAS_ADAM_VISIBLE_ONLY 1u
+typedef struct sas_adam_config {
+    float lr_means, lr_opacities, lr_sh_dc, lr_sh_rest, lr_quats, lr_scales;
+    float beta1, beta2, eps;
+    int step;         /* 1-based */
+    unsigned flags;   /* SAS_ADAM_VISIBLE_ONLY */
+} sas_adam_config;
+int sas_scene_adam_step(sas_ctx *ctx, const sas_adam_config *cfg, const float *d_means, const float *d_opacities, const float *d_sh,
+                        const float *d_quats, const float *d_scales, void *stream);
+
+/* Free the optimiser state: the next step of a group starts from zero moments and the resident values.  Frames in flight are completed. */
+int sas_scene_adam_reset(sas_ctx *ctx);
+
+/*
+ * The resident scene, in the CALLER's order and the upload's shapes: means [N,3], quats [N,4] and scales [N,3] or cov6 [N,6], opacities
+ * [N], colors [N,(L+1)^2,3] ([N,3] plain colours), float32, HOST or DEVICE, each may be NULL.  Straight after an upload these are the
+ * uploaded bits; after optimiser steps, the fitted scene (how it is saved, or uploaded again to renew the storage order).  The form the
+ * scene was not uploaded in is SAS_ERR_INVALID; SAS_ERR_NO_SCENE before an upload.  Blocking; frames in flight are completed.
+ */
+int sas_scene_read(sas_ctx *ctx, float *means, float *quats, float *scales, float *cov6, float *opacities, float *colors);
+
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical
  * field of view; the view matrices and intrinsics are those of sas_camera_matrices. */

@@ -3,8 +3,10 @@
 ``render_differentiable`` is a ``torch.autograd.Function`` around ``Rasterizer.render`` and ``Rasterizer.render_backward``: forward is
 the ordinary frame, backward chains the frame's pointwise tail in torch (``prechain``) and hands the gradients of the raw
 accumulators to the HIP backward pass.  The scene lives in the rasterizer: ``params`` only NAMES the arrays last uploaded, so that
-their gradients have somewhere to go -- after an optimiser step the caller uploads them again (``Rasterizer.upload``), or the next
-frame still shows the old scene.  The view matrix is an argument of every call and needs no upload.
+their gradients have somewhere to go -- after an optimiser step of the caller's own the caller uploads them again
+(``Rasterizer.upload``), or the next frame still shows the old scene.  The alternative that needs no upload is
+``Rasterizer.adam_step``: a fused Adam step on the resident scene from the gradients ``Rasterizer.render_backward`` returns
+(``fit.fit_scene`` is the loop).  The view matrix is an argument of every call and needs no upload.
 
 Not differentiated: K, the group poses, meshes (a scene with meshes is refused), and every decision of the renderer (culls, clamps,
 the alpha and transmittance thresholds), which are constants of the derivative.  The per-Gaussian sums are float atomics: gradients

@@ -255,6 +255,12 @@ struct sas_ctx : Settings {
     DevBuf match_src, match_tgt, match_keys, match_index, match_dist2, match_partial;   // scratch of sas_match_points (SasMatch)
     DevBuf cloud_par, cloud_grid, cloud_cand, cloud_blk, cloud_rows, cloud_dist, cloud_count;   // scratch of sas_sample_points (SasCloud)
     DevBuf fuse_par;   // per-view rows and keep table of sas_fuse_depth (SasFuse)
+    // optimiser state (sas_scene_adam_step), slot order; a group's buffers exist from its first step to the next upload or reset
+    struct Adam {
+        DevBuf means_m, means_v, opac, quats_m, quats_v, scales_m, scales_v, scales_raw, sh_m, sh_v;
+        bool means = false, opacities = false, quats = false, scales = false, sh = false;
+    } adam;
+    Event adam_done;      // recorded behind a step on the caller's stream: the slots' streams wait for it
     DevBuf grad_screen;   // sas_render_backward: [10 n] screen-space sums + [ceil(n / 256)][12] view-matrix rows (SasGradProj)
     int match_cus = 0;   // compute units of the device, asked once (the slice count of sas_match_points)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
@@ -332,6 +338,16 @@ int ensure(sas_ctx *c, DevBuf &b, size_t bytes)
     if (bytes == 0) bytes = 16;
     HIP_TRY(c, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
+    return SAS_OK;
+}
+
+// The optimiser state goes (a new scene, sas_scene_adam_reset): hipFree waits for the step that may still be using it.
+int adam_drop(sas_ctx *c)
+{
+    sas_ctx::Adam &a = c->adam;
+    for (DevBuf *b : {&a.means_m, &a.means_v, &a.opac, &a.quats_m, &a.quats_v, &a.scales_m, &a.scales_v, &a.scales_raw, &a.sh_m, &a.sh_v})
+        if (const int rc = b->release(c)) return rc;
+    a.means = a.opacities = a.quats = a.scales = a.sh = false;
     return SAS_OK;
 }
 
@@ -1111,6 +1127,7 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;
     forget(c, HAVE_SCENE);
+    if (const int rc = adam_drop(c)) return rc;
 
     const int deg = sh_degree < 0 ? -1 : sh_degree;
     const int coeff_floats = deg < 0 ? 3 : 3 * (deg + 1) * (deg + 1);
@@ -2315,6 +2332,149 @@ int sas_render_backward(sas_ctx *c, const float *viewmat, const float *K, int wi
     });
 }
 
+// The fused Adam step on the resident planes (k_adam_scene).  Host work: validation, the first-step allocations, one launch, one event.
+int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_means, const float *d_opacities, const float *d_sh,
+                        const float *d_quats, const float *d_scales, void *stream)
+{
+    const char *who = "sas_scene_adam_step";
+    if (!c) return SAS_ERR_INVALID;
+    if (!cfg) return fail(c, SAS_ERR_INVALID, "%s: cfg is NULL", who);
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (!d_means && !d_opacities && !d_sh && !d_quats && !d_scales) return fail(c, SAS_ERR_INVALID, "%s: every gradient is NULL", who);
+    if (cfg->step < 1) return fail(c, SAS_ERR_INVALID, "%s: step %d < 1 (the count is 1-based)", who, cfg->step);
+    const float lrs[6] = {cfg->lr_means, cfg->lr_opacities, cfg->lr_sh_dc, cfg->lr_sh_rest, cfg->lr_quats, cfg->lr_scales};
+    for (const float lr : lrs)
+        if (!(lr >= 0.0f && lr < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: learning rate %g is negative or not finite", who, (double)lr);
+    if (!(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f) || !(cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f))
+        return fail(c, SAS_ERR_INVALID, "%s: betas (%g, %g) outside [0, 1)", who, (double)cfg->beta1, (double)cfg->beta2);
+    if (!(cfg->eps >= 0.0f && cfg->eps < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: eps %g is negative or not finite", who, (double)cfg->eps);
+    if (cfg->flags & ~SAS_ADAM_VISIBLE_ONLY) return fail(c, SAS_ERR_INVALID, "%s: unknown flags 0x%x", who, cfg->flags);
+    if (c->scene.cov_mode && (d_quats || d_scales))
+        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as covariances, which are not variables: d_quats / d_scales must be NULL", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;   // (no frame reads the planes while they change)
+    const SasScene &sc = c->scene;
+    const bool on_means = d_means && cfg->lr_means > 0.0f, on_opac = d_opacities && cfg->lr_opacities > 0.0f,
+               on_sh = d_sh && (cfg->lr_sh_dc > 0.0f || cfg->lr_sh_rest > 0.0f), on_quats = d_quats && cfg->lr_quats > 0.0f,
+               on_scales = d_scales && cfg->lr_scales > 0.0f;
+    if (sc.n <= 0 || !(on_means || on_opac || on_sh || on_quats || on_scales)) return SAS_OK;   // nothing moves: the last frame stays valid
+    hipStream_t st = (hipStream_t)stream;
+    const int coeff_floats = sc.sh_degree < 0 ? 3 : 3 * (sc.sh_degree + 1) * (sc.sh_degree + 1);
+    const int planes = (coeff_floats + 3) / 4;
+    const size_t plane = sizeof(float4) * (size_t)sc.n_pad;
+    sas_ctx::Adam &a = c->adam;
+    int rc;
+    // a group stepped for the first time: zero moments (and raw values from the resident ones), on the caller's stream
+    auto fresh = [&](DevBuf &b, size_t bytes, bool zero) -> int {
+        if (const int r = ensure(c, b, bytes)) return r;
+        if (zero) HIP_TRY(c, hipMemsetAsync(b.p, 0, bytes, st));
+        return SAS_OK;
+    };
+    if (on_means && !a.means) {
+        if ((rc = fresh(a.means_m, plane, true)) || (rc = fresh(a.means_v, plane, true))) return rc;
+        a.means = true;
+    }
+    if (on_quats && !a.quats) {
+        if ((rc = fresh(a.quats_m, plane, true)) || (rc = fresh(a.quats_v, plane, true))) return rc;
+        a.quats = true;
+    }
+    if (on_sh && !a.sh) {
+        if ((rc = fresh(a.sh_m, plane * planes, true)) || (rc = fresh(a.sh_v, plane * planes, true))) return rc;
+        a.sh = true;
+    }
+    const bool new_opac = on_opac && !a.opacities, new_scales = on_scales && !a.scales;
+    if (new_opac && (rc = fresh(a.opac, plane, false))) return rc;
+    if (new_scales && ((rc = fresh(a.scales_m, plane, true)) || (rc = fresh(a.scales_v, plane, true)) || (rc = fresh(a.scales_raw, plane, false)))) return rc;
+    if (new_opac || new_scales) {
+        sas_launch_adam_init(st, sc.n, sc.g0, sc.g2, new_opac ? (float4 *)a.opac.p : nullptr, new_scales ? (float4 *)a.scales_raw.p : nullptr);
+        HIP_TRY(c, hipGetLastError());
+        a.opacities = a.opacities || new_opac;
+        a.scales = a.scales || new_scales;
+    }
+    SasAdam k{};
+    k.g0 = (float4 *)c->g0.p; k.g1 = (float4 *)c->g1.p; k.g2 = (float4 *)c->g2.p; k.col = (float4 *)c->col.p;
+    k.perm = sc.perm;
+    k.n = sc.n; k.n_pad = sc.n_pad;
+    k.coeff_floats = coeff_floats; k.planes = planes;
+    k.d_means = on_means ? d_means : nullptr;
+    k.d_opac = on_opac ? d_opacities : nullptr;
+    k.d_sh = on_sh ? d_sh : nullptr;
+    k.d_quats = on_quats ? d_quats : nullptr;
+    k.d_scales = on_scales ? d_scales : nullptr;
+    k.means_m = (float4 *)a.means_m.p; k.means_v = (float4 *)a.means_v.p;
+    k.opac = (float4 *)a.opac.p;
+    k.quats_m = (float4 *)a.quats_m.p; k.quats_v = (float4 *)a.quats_v.p;
+    k.scales_m = (float4 *)a.scales_m.p; k.scales_v = (float4 *)a.scales_v.p; k.scales_raw = (float4 *)a.scales_raw.p;
+    k.sh_m = (float4 *)a.sh_m.p; k.sh_v = (float4 *)a.sh_v.p;
+    k.lr_means = cfg->lr_means; k.lr_opac = cfg->lr_opacities; k.lr_sh_dc = cfg->lr_sh_dc; k.lr_sh_rest = cfg->lr_sh_rest;
+    k.lr_quats = cfg->lr_quats; k.lr_scales = cfg->lr_scales;
+    k.beta1 = cfg->beta1; k.beta2 = cfg->beta2;
+    k.omb1 = 1.0f - cfg->beta1; k.omb2 = 1.0f - cfg->beta2;
+    k.bc1 = (float)(1.0 - std::pow((double)cfg->beta1, (double)cfg->step));
+    k.bc2 = (float)(1.0 - std::pow((double)cfg->beta2, (double)cfg->step));
+    k.eps = cfg->eps;
+    k.visible_only = (cfg->flags & SAS_ADAM_VISIBLE_ONLY) != 0;
+    k.sh_aligned = coeff_floats % 4 == 0 && ((uintptr_t)d_sh & 15u) == 0;
+    sas_launch_adam_scene(st, k);
+    HIP_TRY(c, hipGetLastError());
+    // A frame's projection does not wait for the caller's stream (enqueue_chain, ORDER): every slot's stream is put behind the step.
+    if (!c->adam_done.h) HIP_TRY(c, hipEventCreateWithFlags(c->adam_done.put(), hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(c->adam_done, st));
+    for (int s = 0; s < c->n_slots; ++s) HIP_TRY(c, hipStreamWaitEvent(c->slots[s].fs, c->adam_done, 0));
+    // the last frame showed the scene before the step
+    c->has_frame = false;
+    for (Slot &sl : c->slots) sl.info_kept = false;
+    c->scene_version++;
+    return SAS_OK;
+}
+
+int sas_scene_adam_reset(sas_ctx *c)
+{
+    if (!c) return SAS_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;
+    return adam_drop(c);
+}
+
+// The planes back in the caller's order (k_scene_gather), on the context's own stream, which runs behind every optimiser step.
+int sas_scene_read(sas_ctx *c, float *means, float *quats, float *scales, float *cov6, float *opacities, float *colors)
+{
+    const char *who = "sas_scene_read";
+    if (!c) return SAS_ERR_INVALID;
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (c->scene.cov_mode ? (quats || scales) : cov6 != nullptr)
+        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as %s: ask for %s", who, c->scene.cov_mode ? "covariances" : "quaternions and scales",
+                    c->scene.cov_mode ? "cov6" : "quats / scales");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;
+    const SasScene &sc = c->scene;
+    const size_t n = (size_t)sc.n;
+    if (n == 0) return SAS_OK;
+    const int coeff_floats = sc.sh_degree < 0 ? 3 : 3 * (sc.sh_degree + 1) * (sc.sh_degree + 1);
+    float *user[6] = {means, quats, scales, cov6, opacities, colors};
+    const size_t floats[6] = {3 * n, 4 * n, 3 * n, 6 * n, n, (size_t)coeff_floats * n};
+    float *dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf stage[6];
+    for (int k = 0; k < 6; ++k) {   // a device array of this context's device is written in place, anything else through a staging buffer
+        if (!user[k]) continue;
+        hipPointerAttribute_t at{};
+        const bool on_device = hipPointerGetAttributes(&at, user[k]) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
+        (void)hipGetLastError();
+        if (on_device) { dev[k] = user[k]; continue; }
+        if (const int rc = ensure(c, stage[k], sizeof(float) * floats[k])) return rc;
+        dev[k] = (float *)stage[k].p;
+    }
+    const SasGather q{sc.g0, sc.g1, sc.g2, sc.col, sc.perm, sc.n, sc.n_pad, coeff_floats, (coeff_floats + 3) / 4,
+                      dev[0], dev[1], dev[2], dev[3], dev[4], dev[5]};
+    hipStream_t st = c->slots[0].fs;
+    sas_launch_scene_gather(st, q);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    for (int k = 0; k < 6; ++k)
+        if (user[k] && dev[k] != user[k]) HIP_TRY(c, hipMemcpy(user[k], dev[k], sizeof(float) * floats[k], hipMemcpyDefault));
+    return SAS_OK;
+}
+
 static int render_batch_host_impl(sas_ctx *c, int n_views, const float *viewmats, const float *Ks, int width, int height,
                                   const float *background, unsigned flags, uint8_t *rgb8_host, void *stream, const PoseSets &ps)
 {
@@ -2394,17 +2554,18 @@ extern "C" int sas_debug_bounds_match(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_cloud(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_fuse(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_grad(unsigned long long *out, int reset);
+extern "C" int sas_debug_bounds_fit(unsigned long long *out, int reset);
 /* Bounds-checked build only: out[0] = guarded accesses found out of range since the last reset (they were
  * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none). */
 int sas_debug_bounds(unsigned long long *out, int reset)
 {
-    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0};
+    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0};
     if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset) ||
         sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset) || sas_debug_bounds_match(p, reset) ||
-        sas_debug_bounds_cloud(s, reset) || sas_debug_bounds_fuse(f, reset) || sas_debug_bounds_grad(g, reset))
+        sas_debug_bounds_cloud(s, reset) || sas_debug_bounds_fuse(f, reset) || sas_debug_bounds_grad(g, reset) || sas_debug_bounds_fit(t, reset))
         return SAS_ERR_HIP;
-    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : (s[0] ? s : (f[0] ? f : g))))));
-    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0] + f[0] + g[0];
+    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : (s[0] ? s : (f[0] ? f : (g[0] ? g : t)))))));
+    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0] + f[0] + g[0] + t[0];
     out[1] = first[1]; out[2] = first[2]; out[3] = first[3];
     return SAS_OK;
 }

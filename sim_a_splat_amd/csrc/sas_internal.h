@@ -1,4 +1,4 @@
-// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -475,3 +475,37 @@ struct SasFuse {
     float lo[3], voxel, trunc, near_z, pixel_centre, max_weight;
 };
 void sas_launch_fuse(hipStream_t st, const SasFuse &q);
+
+// Optimiser step (sas_scene_adam_step; DESIGN.md 3, "Optimiser step").  k_adam_scene takes the whole call by value: the planes of the resident
+// scene (written in place), the caller's gradients, and the state the context keeps in slot order.  A group whose gradient is nullptr is
+// neither read nor written, and its state pointers may be nullptr.
+struct SasAdam {
+    float4 *g0, *g1, *g2, *col;    // the scene's planes (SasScene), writable
+    const int *perm;               // [n] slot -> caller's index
+    long long n, n_pad;
+    int coeff_floats, planes;      // floats of a Gaussian's coefficient block, colour planes
+    const float *d_means, *d_opac, *d_sh, *d_quats, *d_scales;   // gradients in the caller's order (device), nullptr: not stepped
+    float4 *means_m, *means_v;     // [n_pad] (x, y, z, -) first and second moments
+    float4 *opac;                  // [n_pad] (m, v, logit(opacity), -)
+    float4 *quats_m, *quats_v;     // [n_pad]
+    float4 *scales_m, *scales_v, *scales_raw;   // [n_pad] (x, y, z, -); raw = log(scale)
+    float4 *sh_m, *sh_v;           // [planes][n_pad], laid out as col
+    float lr_means, lr_opac, lr_sh_dc, lr_sh_rest, lr_quats, lr_scales;
+    float beta1, beta2, omb1, omb2;   // omb = 1 - beta (float32)
+    float bc1, bc2;                   // 1 - beta^step (float64 on the host, rounded once)
+    float eps;
+    int visible_only;
+    int sh_aligned;                   // coeff_floats % 4 == 0 and d_sh 16-byte aligned: the coefficient gradients load as float4
+};
+void sas_launch_adam_scene(hipStream_t st, const SasAdam &a);
+// opac / scales_raw (either may be nullptr) <- (0, 0, logit(g0.w), 0) / (log(g2.xyz), 0); NaN where the value is outside the domain
+void sas_launch_adam_init(hipStream_t st, int64_t n, const float4 *g0, const float4 *g2, float4 *opac, float4 *scales_raw);
+// sas_scene_read: the inverse of sas_launch_relayout.  Every output is a device array in the caller's order, or nullptr.
+struct SasGather {
+    const float4 *g0, *g1, *g2, *col;
+    const int *perm;
+    long long n, n_pad;
+    int coeff_floats, planes;
+    float *means, *quats, *scales, *cov6, *opac, *colors;
+};
+void sas_launch_scene_gather(hipStream_t st, const SasGather &q);

@@ -373,6 +373,41 @@ class GaussianSplat:
         res = refine_camera_pose(model._rasterizer(), image, viewmat_from_c2w_opengl(c2w), K, W, H, iters, mask=mask, background=bg)
         return c2w_opengl_from_viewmat(res.viewmat)
 
+    def fit(self, poses, images, iters: int = 200, what: Sequence[str] = ("colors", "opacities"), masks=None, views_per_step: int = 1,
+            lrs: Optional[Dict[str, float]] = None, seed: int = 0):
+        """Fit the model's Gaussians to ``images [C,H,W,3]`` (float, 0..1, camera 0's size) taken from ``poses [C,>=3,4]`` (camera-to-world,
+        OpenGL axes, as ``render(pose)`` takes one): ``fit.fit_scene`` on the model's rasterizer, over the model's background colour, with
+        camera 0's intrinsics.  ``what``: the variable groups (``means``, ``opacities``, ``colors``, ``quats``, ``scales``); N stays fixed.
+        The fitted arrays are written back into the model's raw parameters, so a later save holds them.  Returns the ``FitResult``."""
+        from .fit import fit_scene
+        model = self.pipeline.model
+        if not isinstance(model, SplatModel):
+            raise TypeError("fit needs a SplatModel")
+        _, K, W, H = self._camera0()
+        P = poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else np.asarray(poses, dtype=np.float32)
+        V = np.stack([viewmat_from_c2w_opengl(p[:3]) for p in P.reshape(-1, P.shape[-2], 4)])
+        bg = tuple(float(v) for v in model.background_color.reshape(-1))
+        r = model._rasterizer()
+        res = fit_scene(r, V, np.broadcast_to(np.asarray(K, np.float32), (len(V), 3, 3)), W, H, images, iters, what=what, lrs=lrs, masks=masks,
+                        views_per_step=views_per_step, background=bg, seed=seed)
+        x = r.read_scene()
+        to = lambda t, like: t.to(device=like.device, dtype=like.dtype).reshape(like.shape)
+        if "means" in what:
+            model.means = to(x["means"], model.means)
+        if "quats" in what:
+            model.quats = to(x["quats"], model.quats)
+        if "scales" in what:
+            model.scales = to(torch.log(x["scales"]), model.scales)
+        if "opacities" in what:
+            model.opacities = to(torch.logit(x["opacities"]), model.opacities)
+        if "colors" in what:
+            kk = x["colors"].shape[1]
+            model.features_dc = to(x["colors"][:, 0], model.features_dc)
+            rest = model.features_rest.reshape(model.num_points, -1, 3).clone()
+            rest[:, :kk - 1] = x["colors"][:, 1:].to(device=rest.device, dtype=rest.dtype)
+            model.features_rest = rest.reshape(model.features_rest.shape)
+        return res
+
     def set_language_queries(self, positives, negatives, encoder=None) -> None:
         """The queries of ``compute_semantics``: ``positives [P,D]`` and ``negatives [Q,D]`` (``Q >= 1``) as embeddings in the space
         of the model's ``clip_embeds``.  Strings are taken only with ``encoder``, a callable mapping a list of strings to ``[*,D]``

@@ -1058,6 +1058,72 @@ class Rasterizer:
         self._in_flight(True)
         return res
 
+    # -- fitting ------------------------------------------------------------------------------
+    _ADAM_LRS = ("means", "opacities", "sh_dc", "sh_rest", "quats", "scales")
+
+    def _scene_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """The arrays of the scene last uploaded, by the keys ``render_backward`` and ``read_scene`` use."""
+        n = self.n
+        kk = (self.sh_degree + 1) ** 2 if self.sh_degree >= 0 else 1
+        shapes = dict(means=(n, 3), opacities=(n,), colors=(n, kk, 3))
+        shapes.update(dict(quats=(n, 4), scales=(n, 3)) if self.covariance_form == "quats" else dict(covariances=(n, 6)))
+        return shapes
+
+    @_locked
+    def adam_step(self, grads: Dict[str, torch.Tensor], lrs: Dict[str, float], step: int, betas: Tuple[float, float] = (0.9, 0.999),
+                  eps: float = 1e-15, visible_only: bool = False) -> None:
+        """One fused Adam step on the RESIDENT scene (sas_scene_adam_step; DESIGN.md 3, "Optimiser step"): the next frame shows the
+        stepped scene, with no upload.  ``grads``: what ``render_backward`` returns or accumulates into through ``out=`` -- float32
+        device tensors under ``means``, ``opacities``, ``colors``, ``quats``, ``scales``, with respect to the activated arrays; other
+        keys (``viewmat``) are ignored.  ``lrs``: learning rates under ``means``, ``opacities``, ``sh_dc``, ``sh_rest``, ``quats``,
+        ``scales``; a group without a gradient or with rate 0 (or none) is neither read nor written.  The variables are the means,
+        log(scales), logit(opacities), the quaternions as uploaded and the SH coefficients; the covariances of a scene uploaded as
+        covariances are fixed.  ``step``: 1-based, the caller's count.  ``visible_only``: Gaussians whose gradient is exactly zero
+        in every stepped array (culled in every view of the batch) are skipped, moments included.  The moments live in the context
+        until ``adam_reset`` or the next ``upload``.  ``n``, ``sh_degree``, groups, group poses, features and meshes stay; the last
+        frame's ``read_projection`` / ``read_tile_lists`` do not.  The call only enqueues, on the current stream."""
+        unknown = [k for k in lrs if k not in self._ADAM_LRS]
+        if unknown:
+            raise ValueError(f"adam_step: unknown learning rates {unknown}; expected some of {self._ADAM_LRS}")
+        shapes = self._scene_shapes()
+        ptrs = {}
+        for k in ("means", "opacities", "colors", "quats", "scales"):
+            t = grads.get(k)
+            if t is None:
+                ptrs[k] = None
+                continue
+            if k not in shapes:
+                raise ValueError(f"adam_step: the scene was uploaded as covariances, which are not variables: drop grads[{k!r}]")
+            if not isinstance(t, torch.Tensor) or t.numel() != int(np.prod(shapes[k])) or t.dtype != torch.float32 or not t.is_contiguous() \
+                    or t.device != self.device:
+                raise ValueError(f"grads[{k!r}] must be a contiguous float32 tensor {shapes[k]} on {self.device}")
+            ptrs[k] = t.data_ptr()
+        cfg = _capi.AdamConfig(*[float(lrs.get(k, 0.0)) for k in self._ADAM_LRS], float(betas[0]), float(betas[1]), float(eps), int(step),
+                               _capi.SAS_ADAM_VISIBLE_ONLY if visible_only else 0)
+        rc = self._L.sas_scene_adam_step(self._ctx, ctypes.byref(cfg), ptrs["means"], ptrs["opacities"], ptrs["colors"], ptrs["quats"],
+                                         ptrs["scales"], self._stream())
+        if rc != 0:
+            self._check(rc, "sas_scene_adam_step")
+        self._in_flight(True)
+
+    @_locked
+    def adam_reset(self) -> None:
+        """Drop the optimiser state (sas_scene_adam_reset): the next ``adam_step`` starts from zero moments, with ``step=1``."""
+        self._check(self._L.sas_scene_adam_reset(self._ctx), "sas_scene_adam_reset")
+
+    @_locked
+    def read_scene(self) -> Dict[str, torch.Tensor]:
+        """The resident scene as float32 device tensors in the caller's order and ``upload``'s shapes (sas_scene_read): ``means``,
+        ``opacities``, ``colors [N,K,3]`` and ``quats`` + ``scales`` or ``covariances [N,6]``.  Straight after ``upload``: the uploaded
+        bits.  After ``adam_step``s: the fitted scene -- save it, or ``upload(**r.read_scene(), sh_degree=r.sh_degree, ...)`` to renew
+        the storage order once the means have moved far."""
+        res = {k: torch.empty(s, dtype=torch.float32, device=self.device) for k, s in self._scene_shapes().items()}
+        p = lambda k: res[k].data_ptr() if k in res and res[k].numel() else None
+        torch.cuda.synchronize(self.device)   # (the allocator may hand out memory that work in flight still uses)
+        self._check(self._L.sas_scene_read(self._ctx, p("means"), p("quats"), p("scales"), p("covariances"), p("opacities"), p("colors")),
+                    "sas_scene_read")
+        return res
+
     @_locked
     def render_batch_host(self, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int,
                           background: Sequence[float] = (0.0, 0.0, 0.0), *, out: Optional[torch.Tensor] = None,
