@@ -31,6 +31,7 @@ def main(argv=None) -> int:
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--views", type=int, default=6)
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--loss", choices=("l1", "dssim"), default="l1", help="dssim: descend 0.8 L1 + 0.2 (1 - SSIM) through Rasterizer.photometric_loss")
     a = ap.parse_args(argv)
     sc = make_scene(a.gaussians, seed=4, log_scale_mean=float(np.log(0.03)))
     cams = [ring_camera(a.size, a.size, 1.1 * a.size, yaw_deg=360.0 * k / a.views, elev=0.3) for k in range(a.views)]
@@ -43,7 +44,8 @@ def main(argv=None) -> int:
     r.upload(sc.means, sc.opacities * np.float32(0.7), tinted, quats=sc.quats, scales=sc.scales, sh_degree=sc.sh_degree)
     l0, p0 = mean_loss(r, V, K, a.size, a.size, pictures), psnr(r, V, K, a.size, pictures)
     t = time.perf_counter()
-    res = fit_scene(r, V, K, a.size, a.size, pictures, a.iters, what=("colors", "opacities"), lrs=dict(sh_dc=2e-2, sh_rest=1e-3), views_per_step=2)
+    res = fit_scene(r, V, K, a.size, a.size, pictures, a.iters, what=("colors", "opacities"), lrs=dict(sh_dc=2e-2, sh_rest=1e-3), views_per_step=2,
+                    loss=None if a.loss == "l1" else a.loss)
     dt = time.perf_counter() - t
     l1, p1 = mean_loss(r, V, K, a.size, a.size, pictures), psnr(r, V, K, a.size, pictures)
     print(f"start : loss {l0:.4e}  PSNR {p0:.2f} dB")

@@ -611,6 +611,28 @@ int sas_scene_adam_step(sas_ctx *ctx, const sas_adam_config *cfg, const float *d
 int sas_scene_adam_reset(sas_ctx *ctx);
 
 /*
+ * Photometric loss of 3DGS training and its gradient ("Photometric loss"): for a delivered frame x = rgb [H,W,3] and a
+ * target y [H,W,3] (float32 DEVICE, 0..1) and an optional mask w [H,W] (uint8 DEVICE, non-zero counts; NULL: every pixel counts),
+ *   loss = (1 - lambda) l1 + lambda (1 - ssim),   l1 = sum w |x - y| / D,   ssim = sum w ssim_p / D,   mse = sum w (x - y)^2 / D,
+ *   D = max(3 sum w, 1),
+ * where ssim_p is the per pixel and channel SSIM map under the 11x11 Gaussian window (sigma 1.5, normalised, ZERO padding) with
+ * C1 = 0.01^2, C2 = 0.03^2.  The mask weights the map; the window statistics see the whole image.
+ *   terms          float32[4] DEVICE: (loss, l1, ssim, mse).  lambda == 0 does no SSIM work: ssim is then NaN, loss == l1.
+ *   g_rgb_or_null  [H,W,3] DEVICE: the exact derivative of loss with respect to x (sign(0) = 0; none with respect to y).
+ *   alpha_or_null  non-NULL selects the PRECHAINED form (its values are not read: with no depth gradient the prechain needs none): g_rgb is the gradient of the raw accumulator sas_render_backward takes -- 0 where x >= 1, where
+ *                  the frame's clamp binds -- and g_alpha_or_null [H,W] = -sum_c g_rgb[c] background[c].  g_alpha requires alpha.
+ * Both gradient pointers NULL: only the terms are computed (the metrics path: no second stencil).
+ * Nothing is summed with atomics: the same inputs give the same bits in every output.  A non-finite value in x or y propagates: the
+ * terms become NaN, and so do the gradients within 10 pixels of it (only the pixel's own when lambda == 0); nothing else changes.
+ * The call only enqueues on `stream` and never waits for the host; its scratch belongs to the context (calls of one context are
+ * ordered by one stream).  It needs no uploaded scene.  SAS_ERR_INVALID for a non-positive size, NULL rgb / target / terms, lambda
+ * outside [0, 1] (NaN included), g_alpha without alpha, alpha without a background.
+ */
+int sas_photometric_loss(sas_ctx *ctx, int width, int height, const float *rgb, const float *target, const uint8_t *mask_or_null,
+                         const float *alpha_or_null, const float *background, float lambda_dssim, float *terms,
+                         float *g_rgb_or_null, float *g_alpha_or_null, void *stream);
+
+/*
  * The resident scene, in the CALLER's order and the upload's shapes: means [N,3], quats [N,4] and scales [N,3] or cov6 [N,6], opacities
  * [N], colors [N,(L+1)^2,3] ([N,3] plain colours), float32, HOST or DEVICE, each may be NULL.  Straight after an upload these are the
  * uploaded bits; after optimiser steps, the fitted scene (how it is saved, or uploaded again to renew the storage order).  The form the

@@ -77,6 +77,30 @@ class _Render(torch.autograd.Function):
         return (None, grads[0], None, None, None, None, None, *grads[1:])
 
 
+class _PhotometricLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, rgb, target, mask, lambda_dssim):
+        res = r.photometric_loss(rgb, target, mask=mask, lambda_dssim=lambda_dssim, want_grad=ctx.needs_input_grad[1])
+        if ctx.needs_input_grad[1]:
+            ctx.save_for_backward(res["g_rgb"].reshape(rgb.shape))
+        ctx.like = (rgb.device, rgb.dtype)
+        return res["loss"].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        (g_rgb,) = ctx.saved_tensors
+        return None, (g_rgb * g.to(g_rgb.device)).to(device=ctx.like[0], dtype=ctx.like[1]), None, None, None
+
+
+def photometric_loss(r, rgb: torch.Tensor, target, mask=None, lambda_dssim: float = 0.2) -> torch.Tensor:
+    """The scalar 3DGS photometric loss ``(1 - lambda) L1 + lambda (1 - SSIM)`` of ``rgb [H,W,3]`` against ``target`` over ``mask``
+    (``Rasterizer.photometric_loss`` of rasterizer ``r``, in its plain form), through which a gradient flows to ``rgb`` -- a frame of
+    ``render_differentiable``, whose backward does the pre-chain.  No gradient flows to ``target``."""
+    return _PhotometricLoss.apply(r, rgb, target, mask, float(lambda_dssim))
+
+
 def render_differentiable(r, viewmat: torch.Tensor, K, width: int, height: int, params: Optional[Dict[str, torch.Tensor]] = None,
                           background: Optional[Sequence[float]] = None) -> Dict[str, torch.Tensor]:
     """One frame of rasterizer ``r`` -- ``rgb [H,W,3]``, ``alpha [H,W,1]``, ``depth [H,W,1]`` on its device -- through which gradients

@@ -262,6 +262,7 @@ struct sas_ctx : Settings {
     } adam;
     Event adam_done;      // recorded behind a step on the caller's stream: the slots' streams wait for it
     DevBuf grad_screen;   // sas_render_backward: [10 n] screen-space sums + [ceil(n / 256)][12] view-matrix rows (SasGradProj)
+    DevBuf loss_scratch;  // sas_photometric_loss: [9 H W] partial planes + [tiles][4] workgroup sums + D (SasLoss)
     int match_cus = 0;   // compute units of the device, asked once (the slice count of sas_match_points)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
     // answer of the pinned-memory query for the host buffer of the sas_render_batch_host call being served (cleared when
@@ -2428,6 +2429,44 @@ int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_m
     return SAS_OK;
 }
 
+// The photometric loss and its gradient (k_loss_stats, k_loss_tail, k_loss_grad).  Host work: validation, the scratch, the window, the launches.
+int sas_photometric_loss(sas_ctx *c, int width, int height, const float *rgb, const float *target, const uint8_t *mask_or_null,
+                         const float *alpha_or_null, const float *background, float lambda_dssim, float *terms, float *g_rgb_or_null,
+                         float *g_alpha_or_null, void *stream)
+{
+    const char *who = "sas_photometric_loss";
+    if (!c) return SAS_ERR_INVALID;
+    if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
+    if (!rgb || !target || !terms) return fail(c, SAS_ERR_INVALID, "%s: rgb, target and terms are required", who);
+    if (!(lambda_dssim >= 0.0f && lambda_dssim <= 1.0f)) return fail(c, SAS_ERR_INVALID, "%s: lambda_dssim %g outside [0, 1]", who, (double)lambda_dssim);
+    if (g_alpha_or_null && !alpha_or_null) return fail(c, SAS_ERR_INVALID, "%s: g_alpha is the prechained form: it requires alpha", who);
+    if (alpha_or_null && !background) return fail(c, SAS_ERR_INVALID, "%s: alpha given without a background", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    SasLoss q{};
+    q.x = rgb; q.y = target; q.mask = mask_or_null;
+    q.W = width; q.H = height;
+    q.tiles_x = (width + 15) / 16; q.tiles_y = (height + 15) / 16;
+    q.lambda = lambda_dssim;
+    double g[11], sum = 0.0;
+    for (int k = 0; k < 11; ++k) sum += g[k] = std::exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
+    for (int k = 0; k < 11; ++k) q.win[k] = (float)(g[k] / sum);
+    for (int k = 0; k < 3; ++k) q.bg[k] = alpha_or_null ? background[k] : 0.0f;
+    q.gate = alpha_or_null != nullptr;
+    const bool grad = g_rgb_or_null || g_alpha_or_null;
+    const size_t n_pix = (size_t)width * (size_t)height, tiles = (size_t)q.tiles_x * (size_t)q.tiles_y;
+    const size_t map_floats = grad && lambda_dssim != 0.0f ? 9 * n_pix : 0;
+    if (const int rc = ensure(c, c->loss_scratch, sizeof(float) * (map_floats + 4 * tiles + 4))) return rc;
+    float *s = (float *)c->loss_scratch.p;
+    q.maps = map_floats ? s : nullptr;
+    q.partial = s + map_floats;
+    q.norm = q.partial + 4 * tiles;
+    q.terms = terms;
+    q.g_rgb = g_rgb_or_null; q.g_alpha = g_alpha_or_null;
+    sas_launch_loss((hipStream_t)stream, q);
+    HIP_TRY(c, hipGetLastError());
+    return SAS_OK;
+}
+
 int sas_scene_adam_reset(sas_ctx *c)
 {
     if (!c) return SAS_ERR_INVALID;
@@ -2555,17 +2594,18 @@ extern "C" int sas_debug_bounds_cloud(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_fuse(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_grad(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_fit(unsigned long long *out, int reset);
+extern "C" int sas_debug_bounds_loss(unsigned long long *out, int reset);
 /* Bounds-checked build only: out[0] = guarded accesses found out of range since the last reset (they were
  * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none). */
 int sas_debug_bounds(unsigned long long *out, int reset)
 {
-    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0};
+    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0}, l[4] = {0, 0, 0, 0};
     if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset) ||
         sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset) || sas_debug_bounds_match(p, reset) ||
-        sas_debug_bounds_cloud(s, reset) || sas_debug_bounds_fuse(f, reset) || sas_debug_bounds_grad(g, reset) || sas_debug_bounds_fit(t, reset))
+        sas_debug_bounds_cloud(s, reset) || sas_debug_bounds_fuse(f, reset) || sas_debug_bounds_grad(g, reset) || sas_debug_bounds_fit(t, reset) || sas_debug_bounds_loss(l, reset))
         return SAS_ERR_HIP;
-    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : (s[0] ? s : (f[0] ? f : (g[0] ? g : t)))))));
-    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0] + f[0] + g[0] + t[0];
+    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : (s[0] ? s : (f[0] ? f : (g[0] ? g : (t[0] ? t : l))))))));
+    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0] + f[0] + g[0] + t[0] + l[0];
     out[1] = first[1]; out[2] = first[2]; out[3] = first[3];
     return SAS_OK;
 }

@@ -509,3 +509,23 @@ struct SasGather {
     float *means, *quats, *scales, *cov6, *opac, *colors;
 };
 void sas_launch_scene_gather(hipStream_t st, const SasGather &q);
+
+// Photometric loss (sas_photometric_loss; DESIGN.md 3, "Photometric loss"): (1 - lambda) L1 + lambda (1 - SSIM) of a frame against a target
+// and its gradient with respect to the frame, prechained to the raw accumulators where `gate` is set.  Three launches on one stream:
+// k_loss_stats (per-tile statistics, partial maps, per-workgroup sums), k_loss_tail (the sums in a fixed order -> terms and D),
+// k_loss_grad (the second stencil and the composition).  lambda == 0 runs the L1 variants, which have no stencil and no maps.
+struct SasLoss {
+    const float *x, *y;            // [H][W][3] frame and target
+    const unsigned char *mask;     // [H][W] or nullptr: != 0 counts
+    int W, H, tiles_x, tiles_y;    // 16x16 pixel tiles
+    float lambda;
+    float win[11];                 // the Gaussian window, computed in double on the host and rounded once
+    float bg[3];
+    int gate;                      // prechain: g = 0 where x >= 1, g_alpha = -sum_c g[c] bg[c]
+    float *maps;                   // [9][H W] scratch: (d/dmu_x, d/dsigma_x^2, d/dsigma_xy) x channel, times w; nullptr: terms only
+    float *partial;                // [tiles][4] scratch: (sum w |x-y|, sum w ssim, sum w (x-y)^2, sum w) per workgroup
+    float *norm;                   // [1] scratch: D = max(3 sum w, 1), written by the tail
+    float *terms;                  // [4] (loss, l1, ssim, mse); ssim is NaN (not computed) when lambda == 0
+    float *g_rgb, *g_alpha;        // [H][W][3], [H][W] or nullptr
+};
+void sas_launch_loss(hipStream_t st, const SasLoss &q);

@@ -4,8 +4,13 @@
 accumulate through ``out=``), ``adam_step`` the scene where it lives.  Nothing is uploaded between steps, so the storage order, the
 groups, the features and the meshes of the context stay as they are.
 
-Out of scope, and why: densification, pruning and opacity reset (N is fixed); an SSIM term (pass one through ``loss_and_grad``);
-re-sorting the storage order as the means move (the order is a locality heuristic: ``r.upload(**r.read_scene(), ...)`` renews it);
+The loss: ``loss=None`` descends a mean absolute difference (or the caller's ``loss_and_grad``) with the chain to the raw accumulators in
+torch; ``loss="dssim"`` descends the 3DGS photometric loss ``(1 - lambda) L1 + lambda (1 - SSIM)`` through ``Rasterizer.photometric_loss``,
+whose kernels deliver the gradients ``render_backward`` takes ("Photometric loss").  ``image_metrics`` reports L1, SSIM and
+PSNR of the scene as it stands.
+
+Out of scope, and why: densification, pruning and opacity reset (N is fixed); multi-scale SSIM, LPIPS, depth and alpha loss terms
+(pass one through ``loss_and_grad``); re-sorting the storage order as the means move (the order is a locality heuristic: ``r.upload(**r.read_scene(), ...)`` renews it);
 gradients for K, the group poses and meshes (the limits of the backward pass).
 """
 from __future__ import annotations
@@ -56,9 +61,34 @@ def step_rates(lrs: Dict[str, float], what: Sequence[str], extent: float, t: int
     return out
 
 
+LOSSES = ("dssim",)
+
+
+def _check_loss(who: str, loss: Optional[str], loss_and_grad: Optional[Callable], lambda_dssim: float) -> None:
+    if loss is None:
+        return
+    if loss not in LOSSES:
+        raise ValueError(f"{who}: loss must be None or one of {LOSSES}, got {loss!r}")
+    if loss_and_grad is not None:
+        raise ValueError(f"{who}: loss={loss!r} and loss_and_grad are two answers to one question: give one")
+    if not 0.0 <= float(lambda_dssim) <= 1.0:
+        raise ValueError(f"{who}: lambda_dssim {lambda_dssim} outside [0, 1]")
+
+
 def mean_loss(r, viewmats, Ks, W: int, H: int, images, masks=None, background: Sequence[float] = (0.0, 0.0, 0.0),
-              loss_and_grad: Optional[Callable] = None) -> float:
+              loss_and_grad: Optional[Callable] = None, loss: Optional[str] = None, lambda_dssim: float = 0.2) -> float:
     """The loss ``fit_scene`` descends, averaged over ALL the views, for the scene as it stands in ``r`` (or a stand-in)."""
+    _check_loss("mean_loss", loss, loss_and_grad, lambda_dssim)
+    if loss is not None:
+        bg = tuple(float(v) for v in background)
+        V = np.asarray(viewmats, dtype=np.float32).reshape(-1, 4, 4)
+        K = np.asarray(Ks, dtype=np.float32).reshape(-1, 3, 3)
+        vals = []
+        for v in range(V.shape[0]):
+            rgb = r.render(V[v], K[v], W, H, bg)["rgb"]
+            vals.append(r.photometric_loss(rgb, torch.as_tensor(images[v]), mask=None if masks is None else torch.as_tensor(masks[v]),
+                                           lambda_dssim=lambda_dssim, want_grad=False)["loss"].detach().reshape(()))
+        return float(torch.stack(vals).mean()) if vals else 0.0
     lg = l1_loss_and_grad if loss_and_grad is None else loss_and_grad
     bg = tuple(float(v) for v in background)
     V = np.asarray(viewmats, dtype=np.float32).reshape(-1, 4, 4)
@@ -74,7 +104,7 @@ def mean_loss(r, viewmats, Ks, W: int, H: int, images, masks=None, background: S
 def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequence[str] = ("colors", "opacities"),
               lrs: Optional[Dict[str, float]] = None, masks=None, views_per_step: int = 1,
               background: Sequence[float] = (0.0, 0.0, 0.0), loss_and_grad: Optional[Callable] = None, renderer=None, seed: int = 0,
-              extent: Optional[float] = None, visible_only: bool = True) -> FitResult:
+              extent: Optional[float] = None, visible_only: bool = True, loss: Optional[str] = None, lambda_dssim: float = 0.2) -> FitResult:
     """``iters`` Adam steps of the scene resident in ``r`` towards ``images [C,H,W,3]`` (float, 0..1) seen from ``viewmats [C,4,4]``,
     ``Ks [C,3,3]``.  Each step draws ``views_per_step`` views (without replacement, ``seed``), renders each, takes the loss gradient
     with respect to the delivered frame in torch on the frame's device, runs it through ``autograd.prechain``, accumulates
@@ -86,8 +116,14 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
     ``loss_and_grad(rgb, target, mask) -> (loss, g_rgb)`` replaces the default, the mean absolute colour difference over the mask.
     ``renderer``: an object with ``render``, ``render_backward`` and ``adam_step`` of ``Rasterizer``'s signatures used in ``r``'s
     place (a CPU stand-in runs the loop in tests).  ``visible_only``: Gaussians no view of a step saw keep their moments.
-    Moments left by an earlier fit are dropped first where the renderer has ``adam_reset``."""
+    Moments left by an earlier fit are dropped first where the renderer has ``adam_reset``.
+
+    ``loss="dssim"``: the 3DGS photometric loss ``(1 - lambda_dssim) L1 + lambda_dssim (1 - SSIM)`` instead: the renderer's
+    ``photometric_loss`` takes the frame, the target, the mask, the frame's alpha and the background and returns the prechained
+    ``g_rgb`` and ``g_alpha``, which go to ``render_backward`` as they are -- no torch op lies between the frame and its backward pass.
+    ``history`` then holds that combined loss.  ``loss`` together with ``loss_and_grad`` is refused."""
     R = r if renderer is None else renderer
+    _check_loss("fit_scene", loss, loss_and_grad, lambda_dssim)
     what = tuple(what)
     bad = [k for k in what if k not in _WHAT]
     if bad or not what:
@@ -123,12 +159,34 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
             if v not in targets:   # a view's target and mask move to the frames' device once
                 tm = None if masks is None else torch.as_tensor(masks[v]).to(rgb.device)
                 targets[v] = (torch.as_tensor(images[v]).to(device=rgb.device, dtype=rgb.dtype).reshape(rgb.shape), tm)
-            loss, g_rgb = lg(rgb, *targets[v])
-            g_acc, g_a, _ = prechain(rgb, out["alpha"], out["depth"], bg, g_rgb, None, None)
+            if loss is None:
+                value, g_rgb = lg(rgb, *targets[v])
+                g_acc, g_a, _ = prechain(rgb, out["alpha"], out["depth"], bg, g_rgb, None, None)
+            else:
+                pl = R.photometric_loss(rgb, targets[v][0], mask=targets[v][1], alpha=out["alpha"], background=bg, lambda_dssim=lambda_dssim)
+                value, g_acc, g_a = pl["loss"], pl["g_rgb"], pl["g_alpha"]
             acc = R.render_backward(V[v], K[v], W, H, g_acc, g_a, None, out=acc, want=what)
-            loss = torch.as_tensor(loss).detach().reshape(())
-            total = loss if total is None else total + loss
+            value = torch.as_tensor(value).detach().reshape(())
+            total = value if total is None else total + value
         R.adam_step(acc, step_rates(rates, what, extent, t, int(iters)), t, visible_only=visible_only)
         losses.append(total / per)
     history = [float(x) for x in torch.stack(losses).cpu()] if losses else []   # (one read-back for the run: no step waits for its loss)
     return FitResult(history=history, steps=len(history))
+
+
+def image_metrics(r, viewmats, Ks, W: int, H: int, images, masks=None, background: Sequence[float] = (0.0, 0.0, 0.0)) -> Dict[str, torch.Tensor]:
+    """Per-view ``l1``, ``ssim``, ``mse`` and ``psnr`` (``-10 log10 mse``; images in 0..1) of the scene as it stands in ``r`` against ``images
+    [C,H,W,3]`` over ``masks [C,H,W]``: float32 host tensors ``[C]``.  Each view is one frame and one terms-only
+    ``Rasterizer.photometric_loss``; the terms of all the views are read back once, at the end."""
+    bg = tuple(float(v) for v in background)
+    V = np.asarray(viewmats.detach().cpu() if isinstance(viewmats, torch.Tensor) else viewmats, dtype=np.float32).reshape(-1, 4, 4)
+    K = np.asarray(Ks.detach().cpu() if isinstance(Ks, torch.Tensor) else Ks, dtype=np.float32).reshape(-1, 3, 3)
+    if K.shape[0] != V.shape[0] or len(images) != V.shape[0] or (masks is not None and len(masks) != V.shape[0]):
+        raise ValueError(f"image_metrics: {V.shape[0]} views, {K.shape[0]} Ks, {len(images)} images" + ("" if masks is None else f", {len(masks)} masks"))
+    rows = []
+    for v in range(V.shape[0]):
+        rgb = r.render(V[v], K[v], W, H, bg)["rgb"]
+        rows.append(r.photometric_loss(rgb, torch.as_tensor(images[v]), mask=None if masks is None else torch.as_tensor(masks[v]),
+                                       want_grad=False)["terms"])
+    t = torch.stack(rows).cpu() if rows else torch.zeros((0, 4))
+    return dict(l1=t[:, 1], ssim=t[:, 2], mse=t[:, 3], psnr=-10.0 * torch.log10(t[:, 3]))

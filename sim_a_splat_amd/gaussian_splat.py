@@ -374,10 +374,11 @@ class GaussianSplat:
         return c2w_opengl_from_viewmat(res.viewmat)
 
     def fit(self, poses, images, iters: int = 200, what: Sequence[str] = ("colors", "opacities"), masks=None, views_per_step: int = 1,
-            lrs: Optional[Dict[str, float]] = None, seed: int = 0):
+            lrs: Optional[Dict[str, float]] = None, seed: int = 0, loss: Optional[str] = None, lambda_dssim: float = 0.2):
         """Fit the model's Gaussians to ``images [C,H,W,3]`` (float, 0..1, camera 0's size) taken from ``poses [C,>=3,4]`` (camera-to-world,
         OpenGL axes, as ``render(pose)`` takes one): ``fit.fit_scene`` on the model's rasterizer, over the model's background colour, with
         camera 0's intrinsics.  ``what``: the variable groups (``means``, ``opacities``, ``colors``, ``quats``, ``scales``); N stays fixed.
+        ``loss="dssim"`` descends the 3DGS photometric loss with weight ``lambda_dssim`` on its SSIM term (``fit.fit_scene``).
         The fitted arrays are written back into the model's raw parameters, so a later save holds them.  Returns the ``FitResult``."""
         from .fit import fit_scene
         model = self.pipeline.model
@@ -389,7 +390,7 @@ class GaussianSplat:
         bg = tuple(float(v) for v in model.background_color.reshape(-1))
         r = model._rasterizer()
         res = fit_scene(r, V, np.broadcast_to(np.asarray(K, np.float32), (len(V), 3, 3)), W, H, images, iters, what=what, lrs=lrs, masks=masks,
-                        views_per_step=views_per_step, background=bg, seed=seed)
+                        views_per_step=views_per_step, background=bg, seed=seed, loss=loss, lambda_dssim=lambda_dssim)
         x = r.read_scene()
         to = lambda t, like: t.to(device=like.device, dtype=like.dtype).reshape(like.shape)
         if "means" in what:

@@ -1112,6 +1112,53 @@ class Rasterizer:
         self._check(self._L.sas_scene_adam_reset(self._ctx), "sas_scene_adam_reset")
 
     @_locked
+    def photometric_loss(self, rgb, target, *, mask=None, alpha=None, background: Sequence[float] = (0.0, 0.0, 0.0),
+                         lambda_dssim: float = 0.2, want_grad: bool = True) -> Dict[str, torch.Tensor]:
+        """The 3DGS photometric loss ``(1 - lambda) L1 + lambda (1 - SSIM)`` of a frame ``rgb [H,W,3]`` against ``target [H,W,3]`` and
+        its gradient, on the device (sas_photometric_loss; DESIGN.md 3, "Photometric loss").  ``mask [H,W]`` (bool or integer,
+        non-zero counts) weights the per-pixel maps; the window statistics see the whole image.  Returns ``terms`` (device float32[4]:
+        loss, l1, ssim, mse) and ``loss``, ``l1``, ``ssim``, ``mse`` as 0-d views of it; with ``want_grad`` (a bool, or the names wanted
+        of ``g_rgb``, ``g_alpha``) also ``g_rgb [H,W,3]``, the exact derivative of ``loss`` with respect to ``rgb``.  With ``alpha`` (the frame's own, ``render``'s output) the gradient
+        is PRECHAINED as ``autograd.prechain`` does with no depth gradient -- ``g_rgb`` is zero where ``rgb >= 1`` and
+        ``g_alpha [H,W] = -sum_c g_rgb[c] background[c]`` comes with it: both go straight to ``render_backward``.
+        ``lambda_dssim = 0`` is the L1 loss alone and does no SSIM work (``ssim`` is NaN).  Nothing is summed with atomics: the same
+        inputs give the same bits.  Non-finite pixels propagate: the terms become NaN, and the gradients within 10 pixels.  The call
+        only enqueues, on the current stream; nothing is read back."""
+        shape = tuple(rgb.shape) if hasattr(rgb, "shape") else np.asarray(rgb).shape
+        if len(shape) != 3 or shape[2] != 3 or min(shape) <= 0:
+            raise ValueError(f"rgb must be [H,W,3], got {shape}")
+        H, W = int(shape[0]), int(shape[1])
+        lam = float(lambda_dssim)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lambda_dssim {lambda_dssim} outside [0, 1]")
+        x = self._grad_image(rgb, (H, W, 3), "rgb")
+        y = self._grad_image(target, (H, W, 3), "target")
+        a = self._grad_image(alpha, (H, W), "alpha")
+        m = None
+        if mask is not None:
+            m = mask.detach() if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask)))
+            if m.numel() != H * W:
+                raise ValueError(f"mask must be {[H, W]}, got {tuple(m.shape)}")
+            m = m.to(self.device).contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else m if m.dtype == torch.uint8 else (m != 0).view(torch.uint8)
+        bg, pbg = self._host_arg(background, 3)
+        terms = torch.empty(4, dtype=torch.float32, device=self.device)
+        res = dict(terms=terms, loss=terms[0], l1=terms[1], ssim=terms[2], mse=terms[3])
+        grads = (("g_rgb", "g_alpha") if a is not None else ("g_rgb",)) if want_grad is True else tuple(want_grad or ())
+        if [k for k in grads if k not in ("g_rgb", "g_alpha")]:
+            raise ValueError(f"want_grad must be a bool or name some of ('g_rgb', 'g_alpha'), got {want_grad}")
+        if "g_alpha" in grads and a is None:
+            raise ValueError("g_alpha belongs to the prechained form: pass the frame's alpha")
+        for k in grads:
+            res[k] = torch.empty((H, W, 3) if k == "g_rgb" else (H, W), dtype=torch.float32, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = self._L.sas_photometric_loss(self._ctx, W, H, x.data_ptr(), y.data_ptr(), ptr(m), ptr(a), pbg, lam, terms.data_ptr(),
+                                          ptr(res.get("g_rgb")), ptr(res.get("g_alpha")), self._stream())
+        if rc != 0:
+            self._check(rc, "sas_photometric_loss")
+        return res
+
+    @_locked
     def read_scene(self) -> Dict[str, torch.Tensor]:
         """The resident scene as float32 device tensors in the caller's order and ``upload``'s shapes (sas_scene_read): ``means``,
         ``opacities``, ``colors [N,K,3]`` and ``quats`` + ``scales`` or ``covariances [N,6]``.  Straight after ``upload``: the uploaded
