@@ -611,6 +611,68 @@ int sas_scene_adam_step(sas_ctx *ctx, const sas_adam_config *cfg, const float *d
 int sas_scene_adam_reset(sas_ctx *ctx);
 
 /*
+ * Density control on the resident scene ("Density control"): the adaptive densification, pruning and opacity reset of 3DGS
+ * training (Kerbl et al. 2023) in the form of gsplat's default strategy, with the optimiser state carried along.
+ *
+ * STATISTICS are the caller's: float32 / int32 DEVICE arrays of N entries in the CALLER's order, zeroed by the caller, ADDED to.
+ * sas_density_accumulate adds, for every Gaussian i the last backward frame saw (radius > 0),
+ *   grad_sum[i] += sqrt((0.5 W du)^2 + (0.5 H dv)^2),   count[i] += 1,   max_radius[i] = max(max_radius[i], radius),
+ * radius the larger of the two pixel radii sas_read_projection reports.  (du, dv) = d_means2d_or_null [N,2] (float32 DEVICE), what
+ * sas_render_backward_screen wrote for that frame; NULL: the screen-space sums the last sas_render_backward left in the context's scratch.
+ * IEEE binary32, nothing fused, correctly rounded sqrt, one add per call.  The call only enqueues on `stream`; frames submitted
+ * afterwards run behind it.  SAS_ERR_NO_SCENE when no backward frame has been made since the last upload, optimiser step, densify or
+ * opacity reset (or any other frame was rendered since), and for NULL d_means2d when that frame came from sas_render_backward_screen.
+ */
+int sas_density_accumulate(sas_ctx *ctx, int width, int height, const float *d_means2d_or_null, float *grad_sum, int32_t *count,
+                           float *max_radius_or_null, void *stream);
+
+/*
+ * sas_scene_densify replaces the resident scene of N Gaussians by one of N_new.  Every decision is made on the OLD set, per Gaussian:
+ *   avg = grad_sum / max(count, 1);  high = count > 0 && avg > grow_grad2d;  small = max(scale) <= grow_scale3d * scene_extent;
+ *   prune_o = opacity < prune_opacity;  prune_s = max(scale) > prune_scale3d * scene_extent;
+ *   PRUNED  prune_o || (prune_s && !(high && !small))      CLONED  high && small && !pruned      SPLIT  high && !small && !pruned
+ * (a flag that is not set makes its test false: SAS_DENSIFY_GROW high, SAS_DENSIFY_PRUNE_OPACITY prune_o, SAS_DENSIFY_PRUNE_SCALE
+ * prune_s).  The new scene, in the new caller's order: the survivors (neither pruned nor split) in their old order; one clone per cloned
+ * Gaussian, in parent order, a bit-identical copy; two adjacent children per split Gaussian, in parent order:
+ *   mean + R(q / |q|) (scale * xi),  scale / split_factor,  quaternion, opacity, coefficients and group id inherited bit for bit,
+ * xi three standard normals of the counter-based generator of DESIGN.md, keyed by (seed, the parent's old index, child, axis).
+ * max_gaussians > 0: the growth candidates are ranked clones first, then splits, each by parent index; those whose rank is beyond
+ * max_gaussians - (N - pruned) stay as they are, as survivors.
+ *   OPTIMISER STATE  survivors keep moments and raw values bit for bit; clones and children get zero moments and, where a group has raw
+ *                    values, fresh ones from their new resident values.  Groups never stepped stay without state.
+ *   parents_out_or_null  int32 DEVICE with room for 2 N entries (the most a call can make); [0, N_new) <- each new Gaussian's old index.
+ *   counts_out       HOST: (N_new, cloned, split, pruned).
+ * The storage order is computed anew from the new means (so a call that changes nothing renews it, state kept).  Group poses, link
+ * constants, meshes and sh_degree stay; the feature store and the last frame are dropped as an upload drops them -- upload
+ * features[parents] again; the statistics arrays have the old length: make new ones.  Blocking; completes the frames in flight.
+ * SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID for cfg / grad_sum / count / counts_out NULL, unknown flags, a negative or
+ * non-finite threshold, scene_extent <= 0, split_factor <= 1, max_gaussians < 0, SAS_DENSIFY_GROW or SAS_DENSIFY_PRUNE_SCALE on a cov6
+ * scene (it has no scales), an empty scene, and N_new == 0: pruning everything is refused and the scene stays as it is.
+ */
+#define SAS_DENSIFY_GROW 1u
+#define SAS_DENSIFY_PRUNE_OPACITY 2u
+#define SAS_DENSIFY_PRUNE_SCALE 4u
+typedef struct sas_densify_config {
+    float grow_grad2d, grow_scale3d, prune_opacity, prune_scale3d, scene_extent;
+    float split_factor;       /* 1.6 */
+    int64_t max_gaussians;    /* 0: no cap */
+    unsigned seed;
+    unsigned flags;           /* SAS_DENSIFY_* */
+} sas_densify_config;
+int sas_scene_densify(sas_ctx *ctx, const sas_densify_config *cfg, const float *grad_sum, const int32_t *count,
+                      int32_t *parents_out_or_null, int64_t counts_out[4], void *stream);
+/* Host clock of the last successful sas_scene_densify, ms[0..n) of: the classes and their totals' read-back; the scatter and the read-back
+ * of the new means and group ids; the storage order (the host sort); allocation, relayout, state and commit (tools/densify_probe.py). */
+int sas_scene_densify_times(sas_ctx *ctx, float *ms, int n);
+
+/*
+ * Every opacity > max_opacity becomes max_opacity (the published reset: min(o, 0.01)); where the opacities have optimiser state, the
+ * raw logit of a changed Gaussian is set anew and both its moments are zeroed.  Only enqueues on `stream`, behind the frames in flight;
+ * invalidates the last frame as sas_scene_adam_step does.  SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID unless 0 < max_opacity < 1.
+ */
+int sas_scene_reset_opacity(sas_ctx *ctx, float max_opacity, void *stream);
+
+/*
  * Photometric loss of 3DGS training and its gradient ("Photometric loss"): for a delivered frame x = rgb [H,W,3] and a
  * target y [H,W,3] (float32 DEVICE, 0..1) and an optional mask w [H,W] (uint8 DEVICE, non-zero counts; NULL: every pixel counts),
  *   loss = (1 - lambda) l1 + lambda (1 - ssim),   l1 = sum w |x - y| / D,   ssim = sum w ssim_p / D,   mse = sum w (x - y)^2 / D,

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <chrono>
 #include <new>
 #include <string>
 #include <vector>
@@ -262,6 +263,10 @@ struct sas_ctx : Settings {
     } adam;
     Event adam_done;      // recorded behind a step on the caller's stream: the slots' streams wait for it
     DevBuf grad_screen;   // sas_render_backward: [10 n] screen-space sums + [ceil(n / 256)][12] view-matrix rows (SasGradProj)
+    int grad_frame = 0;   // the last frame is a backward frame: 1 of sas_render_backward_screen, 2 of sas_render_backward (grad_screen holds its sums); 0: none
+    Event density_done;   // recorded behind sas_density_accumulate / sas_scene_reset_opacity on the caller's stream: the slots' streams wait for it
+    DevBuf density_inv, density_cls, density_blk;   // scratch of sas_scene_densify (SasDensity)
+    float densify_ms[4] = {0, 0, 0, 0};   // host clock of the last sas_scene_densify: classes, scatter, storage_order, relayout + state + commit
     DevBuf loss_scratch;  // sas_photometric_loss: [9 H W] partial planes + [tiles][4] workgroup sums + D (SasLoss)
     int match_cus = 0;   // compute units of the device, asked once (the slice count of sas_match_points)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
@@ -904,6 +909,7 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
         sl[k]->group = k == 0 ? nv : 0;
     }
     c->has_frame = true;
+    c->grad_frame = 0;   // (the backward calls set it once their frame is complete)
     return SAS_OK;
 }
 
@@ -1204,6 +1210,7 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
     }
     for (Slot &sl : c->slots) sl.scr.cap = 0;  // re-derive the intersection capacity for the new scene
     c->has_frame = false;
+    c->grad_frame = 0;
     c->scene_version++;
     c->have |= HAVE_SCENE;
     return SAS_OK;
@@ -2273,7 +2280,7 @@ int sas_render_backward_screen(sas_ctx *c, const float *viewmat, const float *K,
     if (!g_rgb && !g_alpha && !g_depth) return fail(c, SAS_ERR_INVALID, "sas_render_backward_screen: g_rgb, g_alpha and g_depth are all NULL");
     if (!d_means2d && !d_conics && !d_opacities && !d_colors && !d_depths)
         return fail(c, SAS_ERR_INVALID, "sas_render_backward_screen: every output is NULL");
-    return lift_views(c, "sas_render_backward_screen", 1, viewmat, K, width, height, flags, stream, [&](int) {
+    const int rc = lift_views(c, "sas_render_backward_screen", 1, viewmat, K, width, height, flags, stream, [&](int) {
         ViewOut o;
         o.grad = true;
         o.grad_rgb = g_rgb;
@@ -2286,6 +2293,8 @@ int sas_render_backward_screen(sas_ctx *c, const float *viewmat, const float *K,
         o.grad_depths = d_depths;
         return o;
     });
+    if (!rc) c->grad_frame = 1;
+    return rc;
 }
 
 // ... and chained through the view's projection (k_grad_project): the screen-space sums live in the context's scratch, zeroed on the
@@ -2310,7 +2319,7 @@ int sas_render_backward(sas_ctx *c, const float *viewmat, const float *K, int wi
     float *s = (float *)c->grad_screen.p;
     if (const int rc = complete_all(c)) return rc;   // (nothing in flight reads the scratch)
     HIP_TRY(c, hipMemsetAsync(s, 0, floats * sizeof(float), (hipStream_t)stream));
-    return lift_views(c, who, 1, viewmat, K, width, height, flags, stream, [&](int) {
+    const int rc = lift_views(c, who, 1, viewmat, K, width, height, flags, stream, [&](int) {
         ViewOut o;
         o.grad = o.grad_chain = true;
         o.grad_rgb = g_rgb;
@@ -2331,6 +2340,8 @@ int sas_render_backward(sas_ctx *c, const float *viewmat, const float *K, int wi
         o.chain_viewmat = d_viewmat;
         return o;
     });
+    if (!rc) c->grad_frame = 2;   // (sas_density_accumulate may read the sums in grad_screen)
+    return rc;
 }
 
 // The fused Adam step on the resident planes (k_adam_scene).  Host work: validation, the first-step allocations, one launch, one event.
@@ -2424,6 +2435,7 @@ int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_m
     for (int s = 0; s < c->n_slots; ++s) HIP_TRY(c, hipStreamWaitEvent(c->slots[s].fs, c->adam_done, 0));
     // the last frame showed the scene before the step
     c->has_frame = false;
+    c->grad_frame = 0;
     for (Slot &sl : c->slots) sl.info_kept = false;
     c->scene_version++;
     return SAS_OK;
@@ -2473,6 +2485,242 @@ int sas_scene_adam_reset(sas_ctx *c)
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;
     return adam_drop(c);
+}
+
+// Behind work on the caller's stream that reads or writes what the frames' own streams touch (a frame's projection does not wait for the
+// caller's stream: enqueue_chain, ORDER): every slot's stream is put behind it.
+static int slots_wait_for(sas_ctx *c, Event &ev, hipStream_t st)
+{
+    if (!ev.h) HIP_TRY(c, hipEventCreateWithFlags(ev.put(), hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(ev, st));
+    for (int s = 0; s < c->n_slots; ++s) HIP_TRY(c, hipStreamWaitEvent(c->slots[s].fs, ev, 0));
+    return SAS_OK;
+}
+
+// The statistics of the last backward frame (k_density_accumulate): its info records are in the slot's scratch, its screen-space sums in the
+// caller's array or in grad_screen.
+int sas_density_accumulate(sas_ctx *c, int width, int height, const float *d_means2d, float *grad_sum, int32_t *count, float *max_radius,
+                           void *stream)
+{
+    const char *who = "sas_density_accumulate";
+    if (!c) return SAS_ERR_INVALID;
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
+    if (!grad_sum || !count) return fail(c, SAS_ERR_INVALID, "%s: grad_sum and count are required", who);
+    if (!c->has_frame || c->grad_frame == 0)
+        return fail(c, SAS_ERR_NO_SCENE, "%s: no backward frame since the last upload, optimiser step, densify or opacity reset", who);
+    if (!d_means2d && c->grad_frame != 2)
+        return fail(c, SAS_ERR_NO_SCENE, "%s: d_means2d is NULL and the last backward frame was not sas_render_backward's: the context holds no sums", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;
+    const Slot &ls = c->slots[c->last_slot];
+    if (!ls.info_kept) return fail(c, SAS_ERR_INVALID, "%s: the backward frame kept no radii", who);
+    SasDensityStats q{};
+    q.info = (const uint4 *)ls.scr.info.p;
+    q.perm = c->scene.perm;
+    q.d_means2d = d_means2d ? d_means2d : (const float *)c->grad_screen.p;
+    q.grad_sum = grad_sum; q.count = count; q.max_radius = max_radius;
+    q.n = c->scene.n;
+    q.half_w = 0.5f * (float)width; q.half_h = 0.5f * (float)height;
+    hipStream_t st = (hipStream_t)stream;
+    sas_launch_density_accumulate(st, q);
+    HIP_TRY(c, hipGetLastError());
+    return slots_wait_for(c, c->density_done, st);   // (the next frame of that slot writes its info records anew)
+}
+
+// Densify, prune and re-order (sas_density.hip).  Host work: validation, two read-backs (the class totals; the new means and group ids
+// for storage_order), the allocations.  Everything the new scene needs is allocated before the context changes.
+int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *grad_sum, const int32_t *count, int32_t *parents_out,
+                      int64_t counts_out[4], void *stream)
+{
+    const char *who = "sas_scene_densify";
+    if (!c) return SAS_ERR_INVALID;
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (!cfg) return fail(c, SAS_ERR_INVALID, "%s: cfg is NULL", who);
+    if (!grad_sum || !count || !counts_out) return fail(c, SAS_ERR_INVALID, "%s: grad_sum, count and counts_out are required", who);
+    if (cfg->flags & ~(SAS_DENSIFY_GROW | SAS_DENSIFY_PRUNE_OPACITY | SAS_DENSIFY_PRUNE_SCALE))
+        return fail(c, SAS_ERR_INVALID, "%s: unknown flags 0x%x", who, cfg->flags);
+    const float thr[4] = {cfg->grow_grad2d, cfg->grow_scale3d, cfg->prune_opacity, cfg->prune_scale3d};
+    for (const float t : thr)
+        if (!(t >= 0.0f && t < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: threshold %g is negative or not finite", who, (double)t);
+    if (!(cfg->scene_extent > 0.0f && cfg->scene_extent < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: scene_extent %g is not positive and finite", who, (double)cfg->scene_extent);
+    if (!(cfg->split_factor > 1.0f && cfg->split_factor < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: split_factor %g <= 1", who, (double)cfg->split_factor);
+    if (cfg->max_gaussians < 0 || cfg->max_gaussians > 0x7fffffffll) return fail(c, SAS_ERR_INVALID, "%s: max_gaussians %lld out of range", who, (long long)cfg->max_gaussians);
+    if (c->scene.cov_mode && (cfg->flags & (SAS_DENSIFY_GROW | SAS_DENSIFY_PRUNE_SCALE)))
+        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as covariances, which have no scales: only SAS_DENSIFY_PRUNE_OPACITY applies", who);
+    const SasScene sc = c->scene;
+    if (sc.n <= 0) return fail(c, SAS_ERR_INVALID, "%s: the scene is empty", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int coeff_floats = sc.sh_degree < 0 ? 3 : 3 * (sc.sh_degree + 1) * (sc.sh_degree + 1);
+    const int planes = (coeff_floats + 3) / 4;
+    const size_t n = (size_t)sc.n, nb = (n + 255) / 256;
+    int rc;
+    if ((rc = ensure(c, c->density_inv, sizeof(int) * n)) || (rc = ensure(c, c->density_cls, n)) ||
+        (rc = ensure(c, c->density_blk, sizeof(unsigned) * (6 * nb + 4))))
+        return rc;
+    SasDensity q{};
+    q.g0 = sc.g0; q.g1 = sc.g1; q.g2 = sc.g2; q.col = sc.col; q.gid8 = sc.gid8; q.perm = sc.perm;
+    q.inv = (int *)c->density_inv.p;
+    q.n = sc.n; q.n_pad = sc.n_pad;
+    q.coeff_floats = coeff_floats; q.planes = planes; q.cov_mode = sc.cov_mode;
+    q.grad_sum = grad_sum; q.count = count;
+    q.grow_grad2d = cfg->grow_grad2d;
+    q.grow_scale = cfg->grow_scale3d * cfg->scene_extent;
+    q.prune_opacity = cfg->prune_opacity;
+    q.prune_scale = cfg->prune_scale3d * cfg->scene_extent;
+    q.split_factor = cfg->split_factor;
+    q.flags = cfg->flags; q.seed = cfg->seed;
+    q.max_gaussians = cfg->max_gaussians;
+    q.cls = (uint8_t *)c->density_cls.p;
+    q.blk_count = (unsigned *)c->density_blk.p;
+    q.blk_off = q.blk_count + 3 * nb;
+    q.totals = q.blk_off + 3 * nb;
+    q.nb = (long long)nb;
+    using clock = std::chrono::steady_clock;
+    auto t0 = clock::now();
+    auto lap = [&](int k) {
+        const auto t1 = clock::now();
+        c->densify_ms[k] = std::chrono::duration<float, std::milli>(t1 - t0).count();
+        t0 = t1;
+    };
+    sas_launch_density_classes(st, q);
+    HIP_TRY(c, hipGetLastError());
+    unsigned totals[3] = {0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(totals, q.totals, sizeof(totals), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    const SasDensityPlan pl = sas_density_plan(totals[0], totals[1], totals[2], cfg->max_gaussians);
+    if (pl.n_new <= 0) return fail(c, SAS_ERR_INVALID, "%s: every Gaussian would be pruned: refused, the scene stays", who);
+    if (pl.n_new > 0x7fffffffll) return fail(c, SAS_ERR_INVALID, "%s: %lld Gaussians are out of range", who, pl.n_new);
+
+    lap(0);
+    // the new scene in the caller's order
+    const size_t m = (size_t)pl.n_new;
+    DevBuf a_means, a_q, a_s, a_cov, a_op, a_col, a_gid, a_par;
+    if ((rc = ensure(c, a_means, sizeof(float) * 3 * m)) || (rc = ensure(c, a_op, sizeof(float) * m)) ||
+        (rc = ensure(c, a_col, sizeof(float) * (size_t)coeff_floats * m)))
+        return rc;
+    if (sc.cov_mode ? (rc = ensure(c, a_cov, sizeof(float) * 6 * m)) : ((rc = ensure(c, a_q, sizeof(float) * 4 * m)) || (rc = ensure(c, a_s, sizeof(float) * 3 * m)))) return rc;
+    if (sc.n_groups > 0 && (rc = ensure(c, a_gid, m))) return rc;
+    if (!parents_out && (rc = ensure(c, a_par, sizeof(int) * m))) return rc;
+    q.means = (float *)a_means.p; q.quats = (float *)a_q.p; q.scales = (float *)a_s.p; q.cov6 = (float *)a_cov.p;
+    q.opac = (float *)a_op.p; q.colors = (float *)a_col.p;
+    q.gid = (uint8_t *)a_gid.p;
+    q.parents = parents_out ? parents_out : (int *)a_par.p;
+    q.n_new = pl.n_new;
+    sas_launch_density_scatter(st, q);
+    HIP_TRY(c, hipGetLastError());
+    // its storage order, on the host as for an upload
+    std::vector<float> h_means(3 * m);
+    std::vector<uint8_t> h_gid;
+    HIP_TRY(c, hipMemcpyAsync(h_means.data(), q.means, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, st));
+    if (q.gid) {
+        h_gid.resize(m);
+        HIP_TRY(c, hipMemcpyAsync(h_gid.data(), q.gid, m, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));
+    lap(1);
+    std::vector<int> perm_host;
+    storage_order(pl.n_new, h_means.data(), q.gid ? h_gid.data() : nullptr, perm_host);
+    lap(2);
+
+    // new planes and new state, beside the old ones
+    const int64_t n_pad = (pl.n_new + 63) & ~63ll;
+    const size_t np = (size_t)n_pad, plane = sizeof(float4) * np;
+    DevBuf g0, g1, g2, col, gid8, perm;
+    if ((rc = ensure(c, g0, plane)) || (rc = ensure(c, g1, plane)) || (rc = ensure(c, g2, plane)) || (rc = ensure(c, col, plane * planes)) ||
+        (rc = ensure(c, gid8, np)) || (rc = ensure(c, perm, sizeof(int) * np)))
+        return rc;
+    sas_ctx::Adam &a = c->adam;
+    sas_ctx::Adam na;
+    auto fresh = [&](bool on, DevBuf &b, size_t bytes) -> int {
+        if (!on) return SAS_OK;
+        if (const int r = ensure(c, b, bytes)) return r;
+        HIP_TRY(c, hipMemsetAsync(b.p, 0, bytes, st));
+        return SAS_OK;
+    };
+    if ((rc = fresh(a.means, na.means_m, plane)) || (rc = fresh(a.means, na.means_v, plane)) || (rc = fresh(a.opacities, na.opac, plane)) ||
+        (rc = fresh(a.quats, na.quats_m, plane)) || (rc = fresh(a.quats, na.quats_v, plane)) || (rc = fresh(a.scales, na.scales_m, plane)) ||
+        (rc = fresh(a.scales, na.scales_v, plane)) || (rc = fresh(a.scales, na.scales_raw, plane)) || (rc = fresh(a.sh, na.sh_m, plane * planes)) ||
+        (rc = fresh(a.sh, na.sh_v, plane * planes)))
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(perm.p, perm_host.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+    sas_launch_relayout(st, pl.n_new, n_pad, (const int *)perm.p, q.means, q.quats, q.scales, q.cov6, q.opac, q.colors, coeff_floats, planes,
+                        q.gid, (float4 *)g0.p, (float4 *)g1.p, (float4 *)g2.p, (float4 *)col.p, (uint8_t *)gid8.p);
+    SasDensityState s{};
+    s.perm_new = (const int *)perm.p; s.parents = q.parents; s.inv_old = q.inv;
+    s.g0_new = (const float4 *)g0.p; s.g2_new = (const float4 *)g2.p;
+    s.n_new = pl.n_new; s.n_survivors = pl.survivors; s.n_old = sc.n; s.n_pad_old = sc.n_pad; s.n_pad_new = n_pad;
+    s.planes = planes;
+    s.old_means_m = (const float4 *)a.means_m.p; s.old_means_v = (const float4 *)a.means_v.p; s.old_opac = (const float4 *)a.opac.p;
+    s.old_quats_m = (const float4 *)a.quats_m.p; s.old_quats_v = (const float4 *)a.quats_v.p;
+    s.old_scales_m = (const float4 *)a.scales_m.p; s.old_scales_v = (const float4 *)a.scales_v.p; s.old_scales_raw = (const float4 *)a.scales_raw.p;
+    s.old_sh_m = (const float4 *)a.sh_m.p; s.old_sh_v = (const float4 *)a.sh_v.p;
+    s.means_m = (float4 *)na.means_m.p; s.means_v = (float4 *)na.means_v.p; s.opac = (float4 *)na.opac.p;
+    s.quats_m = (float4 *)na.quats_m.p; s.quats_v = (float4 *)na.quats_v.p;
+    s.scales_m = (float4 *)na.scales_m.p; s.scales_v = (float4 *)na.scales_v.p; s.scales_raw = (float4 *)na.scales_raw.p;
+    s.sh_m = (float4 *)na.sh_m.p; s.sh_v = (float4 *)na.sh_v.p;
+    sas_launch_density_state(st, s);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));   // (nothing above has changed the context: a failure so far leaves the scene as it was)
+
+    // the context takes the new scene (the old buffers go with this scope)
+    c->g0 = std::move(g0); c->g1 = std::move(g1); c->g2 = std::move(g2); c->col = std::move(col); c->gid8 = std::move(gid8); c->perm = std::move(perm);
+    a.means_m = std::move(na.means_m); a.means_v = std::move(na.means_v); a.opac = std::move(na.opac);
+    a.quats_m = std::move(na.quats_m); a.quats_v = std::move(na.quats_v);
+    a.scales_m = std::move(na.scales_m); a.scales_v = std::move(na.scales_v); a.scales_raw = std::move(na.scales_raw);
+    a.sh_m = std::move(na.sh_m); a.sh_v = std::move(na.sh_v);
+    c->perm_host = std::move(perm_host);
+    c->scene.g0 = (const float4 *)c->g0.p;
+    c->scene.g1 = (const float4 *)c->g1.p;
+    c->scene.g2 = (const float4 *)c->g2.p;
+    c->scene.col = (const float4 *)c->col.p;
+    c->scene.gid8 = (const uint8_t *)c->gid8.p;
+    c->scene.perm = (const int *)c->perm.p;
+    c->scene.n = pl.n_new;
+    c->scene.n_pad = n_pad;
+    forget(c, HAVE_FEAT);
+    for (Slot &sl : c->slots) {
+        sl.scr.cap = 0;   // re-derive the intersection capacity for the new scene
+        sl.info_kept = false;
+    }
+    c->has_frame = false;
+    c->grad_frame = 0;
+    c->scene_version++;
+    counts_out[0] = pl.n_new;
+    counts_out[1] = pl.clones;
+    counts_out[2] = pl.splits;
+    counts_out[3] = sc.n - (long long)totals[0];
+    lap(3);
+    return SAS_OK;
+}
+
+int sas_scene_densify_times(sas_ctx *c, float *ms, int n)
+{
+    if (!c || !ms) return SAS_ERR_INVALID;
+    for (int k = 0; k < n && k < 4; ++k) ms[k] = c->densify_ms[k];
+    return SAS_OK;
+}
+
+int sas_scene_reset_opacity(sas_ctx *c, float max_opacity, void *stream)
+{
+    const char *who = "sas_scene_reset_opacity";
+    if (!c) return SAS_ERR_INVALID;
+    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (!(max_opacity > 0.0f && max_opacity < 1.0f)) return fail(c, SAS_ERR_INVALID, "%s: max_opacity %g outside (0, 1)", who, (double)max_opacity);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;   // (no frame reads the planes while they change)
+    if (c->scene.n <= 0) return SAS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    sas_launch_opacity_reset(st, c->scene.n, max_opacity, (float4 *)c->g0.p, c->adam.opacities ? (float4 *)c->adam.opac.p : nullptr);
+    HIP_TRY(c, hipGetLastError());
+    if (const int rc = slots_wait_for(c, c->density_done, st)) return rc;
+    c->has_frame = false;
+    c->grad_frame = 0;
+    for (Slot &sl : c->slots) sl.info_kept = false;
+    c->scene_version++;
+    return SAS_OK;
 }
 
 // The planes back in the caller's order (k_scene_gather), on the context's own stream, which runs behind every optimiser step.
@@ -2595,17 +2843,18 @@ extern "C" int sas_debug_bounds_fuse(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_grad(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_fit(unsigned long long *out, int reset);
 extern "C" int sas_debug_bounds_loss(unsigned long long *out, int reset);
+extern "C" int sas_debug_bounds_density(unsigned long long *out, int reset);
 /* Bounds-checked build only: out[0] = guarded accesses found out of range since the last reset (they were
  * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none). */
 int sas_debug_bounds(unsigned long long *out, int reset)
 {
-    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0}, l[4] = {0, 0, 0, 0};
+    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0}, l[4] = {0, 0, 0, 0}, d[4] = {0, 0, 0, 0};
     if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset) ||
         sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset) || sas_debug_bounds_match(p, reset) ||
-        sas_debug_bounds_cloud(s, reset) || sas_debug_bounds_fuse(f, reset) || sas_debug_bounds_grad(g, reset) || sas_debug_bounds_fit(t, reset) || sas_debug_bounds_loss(l, reset))
+        sas_debug_bounds_cloud(s, reset) || sas_debug_bounds_fuse(f, reset) || sas_debug_bounds_grad(g, reset) || sas_debug_bounds_fit(t, reset) || sas_debug_bounds_loss(l, reset) || sas_debug_bounds_density(d, reset))
         return SAS_ERR_HIP;
-    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : (s[0] ? s : (f[0] ? f : (g[0] ? g : (t[0] ? t : l))))))));
-    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0] + f[0] + g[0] + t[0] + l[0];
+    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : (s[0] ? s : (f[0] ? f : (g[0] ? g : (t[0] ? t : (l[0] ? l : d)))))))));
+    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0] + f[0] + g[0] + t[0] + l[0] + d[0];
     out[1] = first[1]; out[2] = first[2]; out[3] = first[3];
     return SAS_OK;
 }

@@ -1,4 +1,4 @@
-// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -529,3 +529,80 @@ struct SasLoss {
     float *g_rgb, *g_alpha;        // [H][W][3], [H][W] or nullptr
 };
 void sas_launch_loss(hipStream_t st, const SasLoss &q);
+
+// Density control (sas_density_accumulate, sas_scene_densify, sas_scene_reset_opacity; DESIGN.md 3, "Density control").  Every kernel takes
+// its call by value.
+struct SasDensityStats {
+    const uint4 *info;          // [n] the backward frame's info records (slot order): z, w = the radii, 0: culled
+    const int *perm;            // [n] slot -> caller's index
+    const float *d_means2d;     // [n,2] the frame's screen-space gradient (caller's order)
+    float *grad_sum;            // [n] caller's order, ADDED to
+    int *count;                 // [n]
+    float *max_radius;          // [n] or nullptr
+    long long n;
+    float half_w, half_h;       // 0.5 W, 0.5 H
+};
+void sas_launch_density_accumulate(hipStream_t st, const SasDensityStats &q);
+
+#define SAS_DENSIFY_GROW 1u
+#define SAS_DENSIFY_PRUNE_OPACITY 2u
+#define SAS_DENSIFY_PRUNE_SCALE 4u
+// What a densify call makes of its class totals: the growth candidates are ranked clones first, then splits, each by parent index; the
+// first `budget` of them happen (every one adds one Gaussian), the others stay survivors.  Host and device compute it alike.
+struct SasDensityPlan {
+    long long survivors, clones, splits, n_new;
+};
+static inline __host__ __device__ SasDensityPlan sas_density_plan(long long kept, long long clone_cand, long long split_cand, long long max_gaussians)
+{
+    long long budget = clone_cand + split_cand;
+    if (max_gaussians > 0) {
+        const long long room = max_gaussians > kept ? max_gaussians - kept : 0;
+        budget = budget < room ? budget : room;
+    }
+    SasDensityPlan p;
+    p.clones = clone_cand < budget ? clone_cand : budget;
+    p.splits = split_cand < budget - p.clones ? split_cand : budget - p.clones;
+    p.survivors = kept - p.splits;
+    p.n_new = p.survivors + p.clones + 2 * p.splits;
+    return p;
+}
+struct SasDensity {
+    const float4 *g0, *g1, *g2, *col;   // the old scene's planes
+    const uint8_t *gid8;
+    const int *perm;            // [n] old slot -> caller's index
+    int *inv;                   // [n] scratch: caller's index -> old slot
+    long long n, n_pad;
+    int coeff_floats, planes, cov_mode;
+    const float *grad_sum;      // [n] the caller's statistics
+    const int *count;           // [n]
+    float grow_grad2d, grow_scale, prune_opacity, prune_scale;   // the scale thresholds are times the extent already
+    float split_factor;
+    unsigned flags, seed;
+    long long max_gaussians;
+    uint8_t *cls;               // [n] scratch: class bits per Gaussian
+    unsigned *blk_count, *blk_off;   // [3][nb] scratch: kept, clone candidates, split candidates per workgroup, and their exclusive offsets
+    unsigned *totals;           // [3] scratch
+    long long nb;               // ceil(n / 256)
+    // the new scene in the caller's order (sas_launch_density_scatter), as sas_scene_upload takes it
+    float *means, *quats, *scales, *cov6, *opac, *colors;
+    uint8_t *gid;               // or nullptr: no groups
+    int *parents;               // [n_new]
+    long long n_new;
+};
+// inv, cls, blk_count, blk_off, totals <- the classes of the old set
+void sas_launch_density_classes(hipStream_t st, const SasDensity &q);
+// ... and, once the host has sized the new scene from the totals, its rows
+void sas_launch_density_scatter(hipStream_t st, const SasDensity &q);
+// The optimiser state of the new scene, in its storage order: a survivor's is its parent's, a clone's and a child's is fresh (zero
+// moments, raw values from the new planes as sas_launch_adam_init computes them).  A group without state has nullptr on both sides.
+struct SasDensityState {
+    const int *perm_new, *parents, *inv_old;
+    const float4 *g0_new, *g2_new;
+    long long n_new, n_survivors, n_old, n_pad_old, n_pad_new;
+    int planes;
+    const float4 *old_means_m, *old_means_v, *old_opac, *old_quats_m, *old_quats_v, *old_scales_m, *old_scales_v, *old_scales_raw, *old_sh_m, *old_sh_v;
+    float4 *means_m, *means_v, *opac, *quats_m, *quats_v, *scales_m, *scales_v, *scales_raw, *sh_m, *sh_v;
+};
+void sas_launch_density_state(hipStream_t st, const SasDensityState &q);
+// opacity <- min(opacity, cap) in g0; opac (nullptr: no state) <- (0, 0, logit(cap), -) where it changed
+void sas_launch_opacity_reset(hipStream_t st, int64_t n, float cap, float4 *g0, float4 *opac);

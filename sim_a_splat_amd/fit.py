@@ -2,16 +2,17 @@
 
 ``fit_scene`` is the loop around three calls of a ``Rasterizer``: ``render`` a view, ``render_backward`` the loss gradient (several views
 accumulate through ``out=``), ``adam_step`` the scene where it lives.  Nothing is uploaded between steps, so the storage order, the
-groups, the features and the meshes of the context stay as they are.
+groups, the features and the meshes of the context stay as they are.  With ``densify=DensifyConfig(...)`` the loop also keeps the density
+statistics (``density_accumulate`` after every backward pass) and, on the config's schedule, calls ``densify`` and ``reset_opacity``: N changes
+where the scene lives, the optimiser state follows the survivors ("Density control").
 
 The loss: ``loss=None`` descends a mean absolute difference (or the caller's ``loss_and_grad``) with the chain to the raw accumulators in
 torch; ``loss="dssim"`` descends the 3DGS photometric loss ``(1 - lambda) L1 + lambda (1 - SSIM)`` through ``Rasterizer.photometric_loss``,
 whose kernels deliver the gradients ``render_backward`` takes ("Photometric loss").  ``image_metrics`` reports L1, SSIM and
 PSNR of the scene as it stands.
 
-Out of scope, and why: densification, pruning and opacity reset (N is fixed); multi-scale SSIM, LPIPS, depth and alpha loss terms
-(pass one through ``loss_and_grad``); re-sorting the storage order as the means move (the order is a locality heuristic: ``r.upload(**r.read_scene(), ...)`` renews it);
-gradients for K, the group poses and meshes (the limits of the backward pass).
+Out of scope, and why: multi-scale SSIM, LPIPS, depth and alpha loss terms (pass one through ``loss_and_grad``); screen-size splits and
+prunes and ``revised_opacity`` of gsplat's strategy; gradients for K, the group poses and meshes (the limits of the backward pass).
 """
 from __future__ import annotations
 
@@ -37,10 +38,54 @@ class FitResult:
     the rasterizer (``read_scene`` returns it)."""
     history: List[float] = field(default_factory=list)
     steps: int = 0
+    n_history: List[int] = field(default_factory=list)   # with ``densify``: the scene's N after step ``t + 1`` (empty without)
 
     @property
     def loss(self) -> float:
         return self.history[-1] if self.history else float("nan")
+
+
+@dataclass
+class DensifyConfig:
+    """The schedule and thresholds of density control in ``fit_scene``, gsplat's default strategy's: after step ``t`` (1-based) with
+    ``start <= t < stop`` and ``t % every == 0`` the scene is densified and pruned by the statistics gathered since the last time; after
+    every ``reset_every``-th step (0: never) below ``stop`` the opacities are reset to at most ``reset_opacity``.  Scales are pruned only
+    once a reset has happened.  ``grow_scale3d`` and ``prune_scale3d`` are fractions of the scene extent."""
+    start: int = 500
+    stop: int = 15000
+    every: int = 100
+    reset_every: int = 3000
+    grow_grad2d: float = 2e-4
+    grow_scale3d: float = 0.01
+    prune_opacity: float = 0.005
+    prune_scale3d: float = 0.1
+    max_gaussians: int = 0
+    seed: int = 0
+    split_factor: float = 1.6
+    reset_opacity: float = 0.01
+
+    def densify_at(self, t: int) -> bool:
+        return self.start <= t < self.stop and self.every > 0 and t % self.every == 0
+
+    def reset_at(self, t: int) -> bool:
+        return self.reset_every > 0 and t < self.stop and t % self.reset_every == 0
+
+    def check(self) -> None:
+        if self.every < 1 or self.start < 0 or self.reset_every < 0:
+            raise ValueError(f"DensifyConfig: every {self.every} < 1, or a negative start {self.start} / reset_every {self.reset_every}")
+        for k in ("grow_grad2d", "grow_scale3d", "prune_opacity", "prune_scale3d"):
+            if not (0.0 <= float(getattr(self, k)) < float("inf")):
+                raise ValueError(f"DensifyConfig: {k} {getattr(self, k)} is negative or not finite")
+        if not float(self.split_factor) > 1.0 or self.max_gaussians < 0 or not 0.0 < float(self.reset_opacity) < 1.0:
+            raise ValueError(f"DensifyConfig: split_factor {self.split_factor} <= 1, max_gaussians {self.max_gaussians} < 0 or reset_opacity "
+                             f"{self.reset_opacity} outside (0, 1)")
+
+
+def _new_density_stats(R) -> Dict[str, torch.Tensor]:
+    if hasattr(R, "new_density_stats"):
+        return R.new_density_stats()
+    n = int(R.read_scene()["means"].shape[0])
+    return dict(grad_sum=torch.zeros(n), count=torch.zeros(n, dtype=torch.int32), max_radius=torch.zeros(n))
 
 
 def l1_loss_and_grad(rgb: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -104,7 +149,8 @@ def mean_loss(r, viewmats, Ks, W: int, H: int, images, masks=None, background: S
 def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequence[str] = ("colors", "opacities"),
               lrs: Optional[Dict[str, float]] = None, masks=None, views_per_step: int = 1,
               background: Sequence[float] = (0.0, 0.0, 0.0), loss_and_grad: Optional[Callable] = None, renderer=None, seed: int = 0,
-              extent: Optional[float] = None, visible_only: bool = True, loss: Optional[str] = None, lambda_dssim: float = 0.2) -> FitResult:
+              extent: Optional[float] = None, visible_only: bool = True, loss: Optional[str] = None, lambda_dssim: float = 0.2,
+              densify: Optional[DensifyConfig] = None) -> FitResult:
     """``iters`` Adam steps of the scene resident in ``r`` towards ``images [C,H,W,3]`` (float, 0..1) seen from ``viewmats [C,4,4]``,
     ``Ks [C,3,3]``.  Each step draws ``views_per_step`` views (without replacement, ``seed``), renders each, takes the loss gradient
     with respect to the delivered frame in torch on the frame's device, runs it through ``autograd.prechain``, accumulates
@@ -121,7 +167,12 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
     ``loss="dssim"``: the 3DGS photometric loss ``(1 - lambda_dssim) L1 + lambda_dssim (1 - SSIM)`` instead: the renderer's
     ``photometric_loss`` takes the frame, the target, the mask, the frame's alpha and the background and returns the prechained
     ``g_rgb`` and ``g_alpha``, which go to ``render_backward`` as they are -- no torch op lies between the frame and its backward pass.
-    ``history`` then holds that combined loss.  ``loss`` together with ``loss_and_grad`` is refused."""
+    ``history`` then holds that combined loss.  ``loss`` together with ``loss_and_grad`` is refused.
+
+    ``densify``: a ``DensifyConfig`` turns adaptive density control on: ``density_accumulate`` follows every ``render_backward``, and after
+    the steps of the config's schedule ``densify`` (then new statistics; the gradient buffers are made anew every step anyway) and
+    ``reset_opacity`` are called, with the scene extent the means' rate uses.  ``n_history`` then holds N after every step.  A stand-in
+    ``renderer`` needs those three methods too.  ``None``: the loop above, unchanged."""
     R = r if renderer is None else renderer
     _check_loss("fit_scene", loss, loss_and_grad, lambda_dssim)
     what = tuple(what)
@@ -139,7 +190,7 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
         raise ValueError(f"fit_scene: views_per_step {per} out of [1, {C}]")
     if extent is None:
         extent = 1.0
-        if "means" in what:
+        if "means" in what or densify is not None:
             m = R.read_scene()["means"]
             extent = float((m - m.mean(dim=0)).norm(dim=1).max()) if m.shape[0] else 1.0
     lg = l1_loss_and_grad if loss_and_grad is None else loss_and_grad
@@ -149,6 +200,13 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
     rng = np.random.default_rng(seed)
     targets: Dict[int, Tuple[torch.Tensor, Optional[torch.Tensor]]] = {}
     losses = []
+    stats, n_history, was_reset = None, [], False
+    if densify is not None:
+        densify.check()
+        missing = [k for k in ("density_accumulate", "densify", "reset_opacity") if not hasattr(R, k)]
+        if missing:
+            raise ValueError(f"fit_scene: densify needs a renderer with {missing}")
+        stats = _new_density_stats(R)
     for t in range(1, int(iters) + 1):
         acc = None
         total = None
@@ -166,12 +224,24 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
                 pl = R.photometric_loss(rgb, targets[v][0], mask=targets[v][1], alpha=out["alpha"], background=bg, lambda_dssim=lambda_dssim)
                 value, g_acc, g_a = pl["loss"], pl["g_rgb"], pl["g_alpha"]
             acc = R.render_backward(V[v], K[v], W, H, g_acc, g_a, None, out=acc, want=what)
+            if stats is not None:
+                R.density_accumulate(W, H, stats)
             value = torch.as_tensor(value).detach().reshape(())
             total = value if total is None else total + value
         R.adam_step(acc, step_rates(rates, what, extent, t, int(iters)), t, visible_only=visible_only)
         losses.append(total / per)
+        if stats is not None:
+            if densify.densify_at(t):
+                R.densify(stats, grow_grad2d=densify.grow_grad2d, grow_scale3d=densify.grow_scale3d, prune_opacity=densify.prune_opacity,
+                          prune_scale3d=densify.prune_scale3d, scene_extent=extent, split_factor=densify.split_factor,
+                          max_gaussians=densify.max_gaussians, seed=densify.seed + t, prune_scale_on=was_reset)
+                stats = _new_density_stats(R)
+            if densify.reset_at(t):
+                R.reset_opacity(densify.reset_opacity)
+                was_reset = True
+            n_history.append(int(stats["count"].shape[0]))
     history = [float(x) for x in torch.stack(losses).cpu()] if losses else []   # (one read-back for the run: no step waits for its loss)
-    return FitResult(history=history, steps=len(history))
+    return FitResult(history=history, steps=len(history), n_history=n_history)
 
 
 def image_metrics(r, viewmats, Ks, W: int, H: int, images, masks=None, background: Sequence[float] = (0.0, 0.0, 0.0)) -> Dict[str, torch.Tensor]:

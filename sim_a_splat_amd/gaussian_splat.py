@@ -374,10 +374,12 @@ class GaussianSplat:
         return c2w_opengl_from_viewmat(res.viewmat)
 
     def fit(self, poses, images, iters: int = 200, what: Sequence[str] = ("colors", "opacities"), masks=None, views_per_step: int = 1,
-            lrs: Optional[Dict[str, float]] = None, seed: int = 0, loss: Optional[str] = None, lambda_dssim: float = 0.2):
+            lrs: Optional[Dict[str, float]] = None, seed: int = 0, loss: Optional[str] = None, lambda_dssim: float = 0.2, densify=None):
         """Fit the model's Gaussians to ``images [C,H,W,3]`` (float, 0..1, camera 0's size) taken from ``poses [C,>=3,4]`` (camera-to-world,
         OpenGL axes, as ``render(pose)`` takes one): ``fit.fit_scene`` on the model's rasterizer, over the model's background colour, with
-        camera 0's intrinsics.  ``what``: the variable groups (``means``, ``opacities``, ``colors``, ``quats``, ``scales``); N stays fixed.
+        camera 0's intrinsics.  ``what``: the variable groups (``means``, ``opacities``, ``colors``, ``quats``, ``scales``); N stays fixed unless
+        ``densify`` (a ``fit.DensifyConfig``) turns density control on -- every per-Gaussian parameter of the model is then replaced at the
+        new N (SH bands beyond the uploaded degree start at zero).
         ``loss="dssim"`` descends the 3DGS photometric loss with weight ``lambda_dssim`` on its SSIM term (``fit.fit_scene``).
         The fitted arrays are written back into the model's raw parameters, so a later save holds them.  Returns the ``FitResult``."""
         from .fit import fit_scene
@@ -390,8 +392,22 @@ class GaussianSplat:
         bg = tuple(float(v) for v in model.background_color.reshape(-1))
         r = model._rasterizer()
         res = fit_scene(r, V, np.broadcast_to(np.asarray(K, np.float32), (len(V), 3, 3)), W, H, images, iters, what=what, lrs=lrs, masks=masks,
-                        views_per_step=views_per_step, background=bg, seed=seed, loss=loss, lambda_dssim=lambda_dssim)
+                        views_per_step=views_per_step, background=bg, seed=seed, loss=loss, lambda_dssim=lambda_dssim, densify=densify)
         x = r.read_scene()
+        if densify is not None:   # N may have changed: every array is the resident one
+            n = int(x["means"].shape[0])
+            to_n = lambda t, like: t.to(device=like.device, dtype=like.dtype).reshape((n,) + tuple(like.shape[1:]))
+            kk = x["colors"].shape[1]
+            rest = torch.zeros((n,) + tuple(model.features_rest.reshape(model.num_points, -1, 3).shape[1:]), dtype=model.features_rest.dtype,
+                               device=model.features_rest.device)
+            rest[:, :kk - 1] = x["colors"][:, 1:].to(device=rest.device, dtype=rest.dtype)
+            model.means, model.quats = to_n(x["means"], model.means), to_n(x["quats"], model.quats)
+            model.scales, model.opacities = to_n(torch.log(x["scales"]), model.scales), to_n(torch.logit(x["opacities"]), model.opacities)
+            model.features_dc = to_n(x["colors"][:, 0], model.features_dc)
+            model.features_rest = rest.reshape((n,) + tuple(model.features_rest.shape[1:]))
+            if model.clip_embeds is not None and model.clip_embeds.shape[0] != n:
+                model.clip_embeds = None   # (per-Gaussian embeddings of the old set: lift them again)
+            return res
         to = lambda t, like: t.to(device=like.device, dtype=like.dtype).reshape(like.shape)
         if "means" in what:
             model.means = to(x["means"], model.means)

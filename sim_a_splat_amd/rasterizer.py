@@ -1111,6 +1111,79 @@ class Rasterizer:
         """Drop the optimiser state (sas_scene_adam_reset): the next ``adam_step`` starts from zero moments, with ``step=1``."""
         self._check(self._L.sas_scene_adam_reset(self._ctx), "sas_scene_adam_reset")
 
+    # -- density control ------------------------------------------------------------------------
+    _DENSITY_STATS = dict(grad_sum=torch.float32, count=torch.int32, max_radius=torch.float32)
+    _DENSIFY_CONFIG = dict(grow_grad2d=2e-4, grow_scale3d=0.01, prune_opacity=0.005, prune_scale3d=0.1, scene_extent=1.0, split_factor=1.6,
+                           max_gaussians=0, seed=0, grow=True, prune_opacity_on=True, prune_scale_on=True)
+
+    def new_density_stats(self) -> Dict[str, torch.Tensor]:
+        """Zeroed statistics for ``density_accumulate`` / ``densify``: ``grad_sum``, ``max_radius`` (float32) and ``count`` (int32), each
+        ``[N]`` on the device, in the caller's order."""
+        return {k: torch.zeros(self.n, dtype=dt, device=self.device) for k, dt in self._DENSITY_STATS.items()}
+
+    def _density_stat(self, stats, k: str) -> torch.Tensor:
+        t = stats.get(k)
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (self.n,) or t.dtype != self._DENSITY_STATS[k] or not t.is_contiguous() \
+                or t.device != self.device:
+            raise ValueError(f"stats[{k!r}] must be a contiguous {self._DENSITY_STATS[k]} tensor ({self.n},) on {self.device}: new_density_stats() makes them")
+        return t
+
+    @_locked
+    def density_accumulate(self, width: int, height: int, stats: Dict[str, torch.Tensor], d_means2d: Optional[torch.Tensor] = None) -> None:
+        """Add the last backward frame to the density statistics (sas_density_accumulate; DESIGN.md 3, "Density control"): for every
+        Gaussian that frame saw, ``grad_sum += |(0.5 W du, 0.5 H dv)|``, ``count += 1``, ``max_radius = max(max_radius, radius)``.
+        ``d_means2d [N,2]``: what ``render_backward(screen_space=True)`` returned for that frame; None: the sums the last
+        ``render_backward`` left in the context.  ``stats`` may leave ``max_radius`` out.  Only enqueues, on the current stream."""
+        gs, cn = self._density_stat(stats, "grad_sum"), self._density_stat(stats, "count")
+        mr = self._density_stat(stats, "max_radius") if stats.get("max_radius") is not None else None
+        pm = None
+        if d_means2d is not None:
+            if not isinstance(d_means2d, torch.Tensor) or tuple(d_means2d.shape) != (self.n, 2) or d_means2d.dtype != torch.float32 \
+                    or not d_means2d.is_contiguous() or d_means2d.device != self.device:
+                raise ValueError(f"d_means2d must be a contiguous float32 tensor ({self.n}, 2) on {self.device}")
+            pm = d_means2d.data_ptr()
+        rc = self._L.sas_density_accumulate(self._ctx, int(width), int(height), pm, gs.data_ptr(), cn.data_ptr(),
+                                            mr.data_ptr() if mr is not None else None, self._stream())
+        if rc != 0:
+            self._check(rc, "sas_density_accumulate")
+
+    @_locked
+    def densify(self, stats: Dict[str, torch.Tensor], **config) -> Dict[str, object]:
+        """Densify and prune the RESIDENT scene by the statistics (sas_scene_densify; DESIGN.md 3, "Density control").  ``config``:
+        ``grow_grad2d`` (2e-4), ``grow_scale3d`` (0.01), ``prune_opacity`` (0.005), ``prune_scale3d`` (0.1), ``scene_extent`` (1),
+        ``split_factor`` (1.6), ``max_gaussians`` (0: no cap), ``seed`` (0) and the switches ``grow``, ``prune_opacity_on``,
+        ``prune_scale_on`` (all on; all off renews the storage order alone).  Returns ``n`` (the new count, also ``self.n``), ``parents``
+        (int32 ``[n]`` device: each new Gaussian's old index), ``cloned``, ``split``, ``pruned``.  The optimiser state follows the
+        survivors; features are dropped (``upload_features(f[parents])``), ``stats`` has the old length (``new_density_stats()``).
+        Blocking."""
+        unknown = [k for k in config if k not in self._DENSIFY_CONFIG]
+        if unknown:
+            raise ValueError(f"densify: unknown settings {unknown}; expected some of {tuple(self._DENSIFY_CONFIG)}")
+        cf = dict(self._DENSIFY_CONFIG, **config)
+        gs, cn = self._density_stat(stats, "grad_sum"), self._density_stat(stats, "count")
+        flags = (_capi.SAS_DENSIFY_GROW if cf["grow"] else 0) | (_capi.SAS_DENSIFY_PRUNE_OPACITY if cf["prune_opacity_on"] else 0) | \
+                (_capi.SAS_DENSIFY_PRUNE_SCALE if cf["prune_scale_on"] else 0)
+        cfg = _capi.DensifyConfig(float(cf["grow_grad2d"]), float(cf["grow_scale3d"]), float(cf["prune_opacity"]), float(cf["prune_scale3d"]),
+                                  float(cf["scene_extent"]), float(cf["split_factor"]), int(cf["max_gaussians"]), int(cf["seed"]) & 0xffffffff, flags)
+        parents = torch.empty(max(2 * self.n, 1), dtype=torch.int32, device=self.device)
+        counts = (ctypes.c_int64 * 4)()
+        rc = self._L.sas_scene_densify(self._ctx, ctypes.byref(cfg), gs.data_ptr(), cn.data_ptr(), parents.data_ptr(), counts, self._stream())
+        if rc != 0:
+            self._check(rc, "sas_scene_densify")
+        self._in_flight(True)
+        self.n = int(counts[0])
+        self._forget("features")
+        return dict(n=self.n, parents=parents[:self.n], cloned=int(counts[1]), split=int(counts[2]), pruned=int(counts[3]))
+
+    @_locked
+    def reset_opacity(self, max_opacity: float = 0.01) -> None:
+        """Every resident opacity above ``max_opacity`` becomes ``max_opacity`` (sas_scene_reset_opacity), its optimiser state is started
+        anew.  Only enqueues, on the current stream."""
+        rc = self._L.sas_scene_reset_opacity(self._ctx, float(max_opacity), self._stream())
+        if rc != 0:
+            self._check(rc, "sas_scene_reset_opacity")
+        self._in_flight(True)
+
     @_locked
     def photometric_loss(self, rgb, target, *, mask=None, alpha=None, background: Sequence[float] = (0.0, 0.0, 0.0),
                          lambda_dssim: float = 0.2, want_grad: bool = True) -> Dict[str, torch.Tensor]:
