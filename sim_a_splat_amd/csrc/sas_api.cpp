@@ -94,6 +94,46 @@ struct RenderArgs {
     float min_alpha = 0.0f;        // of out.labels
 };
 
+// The resident scene's planes (k_relayout's layout) and its storage order; sas_scene_densify builds a second record and swaps it in.
+struct Planes {
+    DevBuf g0, g1, g2, col, gid8, perm;
+    std::vector<int> perm_host;   // perm's host copy: slot -> caller's index
+    int64_t n = 0, n_pad = 0;
+    int alloc(sas_ctx *c, int64_t count, int colour_planes);   // (the device buffers alone: perm_host is the caller's to fill)
+    void bind(SasScene &s) const
+    {
+        s.g0 = (const float4 *)g0.p; s.g1 = (const float4 *)g1.p; s.g2 = (const float4 *)g2.p; s.col = (const float4 *)col.p;
+        s.gid8 = (const uint8_t *)gid8.p; s.perm = (const int *)perm.p;
+        s.n = n; s.n_pad = n_pad;
+    }
+};
+
+// Optimiser state (sas_scene_adam_step), slot order; a group's buffers exist from its first step to the next upload or reset.  `rows` is
+// THE description of the state: which group a buffer belongs to (its flag in `on` guards it), whether it spans the colour planes, and
+// whether a first step finds it zeroed or filled by k_adam_init.  Everything else here is derived from it.
+struct Adam {
+    enum Group { MEANS, QUATS, SH, OPACITIES, SCALES, GROUPS };   // (in the order a first step allocates them)
+    struct Row { float4 *SasAdamState::*field; Group group; bool colour, zeroed; };
+    static constexpr int kRows = 10;
+    static constexpr Row rows[kRows] = {
+        {&SasAdamState::means_m, MEANS, false, true},   {&SasAdamState::means_v, MEANS, false, true},
+        {&SasAdamState::opac, OPACITIES, false, false},
+        {&SasAdamState::quats_m, QUATS, false, true},   {&SasAdamState::quats_v, QUATS, false, true},
+        {&SasAdamState::scales_m, SCALES, false, true}, {&SasAdamState::scales_v, SCALES, false, true}, {&SasAdamState::scales_raw, SCALES, false, false},
+        {&SasAdamState::sh_m, SH, true, true},          {&SasAdamState::sh_v, SH, true, true}};
+    DevBuf buf[kRows];
+    bool on[GROUPS] = {false, false, false, false, false};
+    int drop(sas_ctx *c);
+    int alloc(sas_ctx *c, int row, int64_t n_pad, int colour_planes, hipStream_t st, bool zero);   // buf[row] for n_pad slots, zeroed on st
+    SasAdamState view(const bool *which = nullptr) const   // (which: the buffers of those groups alone, nullptr for the others)
+    {
+        SasAdamState s{};
+        for (int k = 0; k < kRows; ++k)
+            if (!which || which[rows[k].group]) s.*rows[k].field = (float4 *)buf[k].p;
+        return s;
+    }
+};
+
 }  // namespace
 
 // Per-frame scratch.  Every slot owns one, so several frames can be on the GPU at the same time.
@@ -243,8 +283,8 @@ struct sas_ctx : Settings {
     int device = 0;
     std::string err;
     // scene
-    DevBuf g0, g1, g2, col, gid8, perm;
-    DevBuf feat;         // feature store (sas_scene_features): [chunks][n_pad][SAS_FEAT_K], slot order
+    Planes planes;
+    DevBuf feat;        // feature store (sas_scene_features): [chunks][n_pad][SAS_FEAT_K], slot order
     int feat_c = 0;      // its channels
     bool feat_onehot = false, mesh_feat_onehot = false;   // the store / the triangles' rows are the one-hot of the groups (label frames)
     DevBuf mesh_vert, mesh_tri, mesh_col;   // meshes (sas_scene_meshes): float4 vertices, int4 (i0, i1, i2, group), float4 colours
@@ -256,11 +296,7 @@ struct sas_ctx : Settings {
     DevBuf match_src, match_tgt, match_keys, match_index, match_dist2, match_partial;   // scratch of sas_match_points (SasMatch)
     DevBuf cloud_par, cloud_grid, cloud_cand, cloud_blk, cloud_rows, cloud_dist, cloud_count;   // scratch of sas_sample_points (SasCloud)
     DevBuf fuse_par;   // per-view rows and keep table of sas_fuse_depth (SasFuse)
-    // optimiser state (sas_scene_adam_step), slot order; a group's buffers exist from its first step to the next upload or reset
-    struct Adam {
-        DevBuf means_m, means_v, opac, quats_m, quats_v, scales_m, scales_v, scales_raw, sh_m, sh_v;
-        bool means = false, opacities = false, quats = false, scales = false, sh = false;
-    } adam;
+    Adam adam;            // optimiser state of the resident scene
     Event adam_done;      // recorded behind a step on the caller's stream: the slots' streams wait for it
     DevBuf grad_screen;   // sas_render_backward: [10 n] screen-space sums + [ceil(n / 256)][12] view-matrix rows (SasGradProj)
     int grad_frame = 0;   // the last frame is a backward frame: 1 of sas_render_backward_screen, 2 of sas_render_backward (grad_screen holds its sums); 0: none
@@ -274,7 +310,6 @@ struct sas_ctx : Settings {
     // the call returns: nothing is remembered across calls)
     const uint8_t *host_query_base = nullptr, *host_query_end = nullptr;
     bool host_query_ok = false;
-    std::vector<int> perm_host;
     SasScene scene{};
     unsigned have = 0;   // HAVE_*: the stores that are valid
     std::vector<float> group_host;    // [n_groups * 12] current poses: what a frame submitted now is rendered with
@@ -285,7 +320,7 @@ struct sas_ctx : Settings {
     int inflight = 0;
     int last_slot = 0;   // most recently enqueued (parity hooks)
     hipStream_t stream = nullptr;   // caller's stream of the in-flight frames
-    bool has_frame = false;
+    bool has_frame{};    // a frame of the scene as it stands has been rendered (cleared by scene_changed alone)
     static constexpr int64_t kPairMinGaussians = 500000;
     uint64_t scene_version = 0;
     int64_t frames_submitted = 0, frames_completed = 0;   // sas_frames_completed
@@ -310,6 +345,13 @@ int fail(sas_ctx *c, int code, const char *fmt, ...)
 }
 
 bool has(const sas_ctx *c, unsigned stores) { return (c->have & stores) == stores; }
+
+// the prologue of every call that needs a scene in place
+int need_scene(sas_ctx *c, const char *who)
+{
+    if (!c) return SAS_ERR_INVALID;
+    return has(c, HAVE_SCENE) ? SAS_OK : fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+}
 
 void forget(sas_ctx *c, unsigned stores)
 {
@@ -348,13 +390,54 @@ int ensure(sas_ctx *c, DevBuf &b, size_t bytes)
 }
 
 // The optimiser state goes (a new scene, sas_scene_adam_reset): hipFree waits for the step that may still be using it.
-int adam_drop(sas_ctx *c)
+int Adam::drop(sas_ctx *c)
 {
-    sas_ctx::Adam &a = c->adam;
-    for (DevBuf *b : {&a.means_m, &a.means_v, &a.opac, &a.quats_m, &a.quats_v, &a.scales_m, &a.scales_v, &a.scales_raw, &a.sh_m, &a.sh_v})
-        if (const int rc = b->release(c)) return rc;
-    a.means = a.opacities = a.quats = a.scales = a.sh = false;
+    for (DevBuf &b : buf)
+        if (const int rc = b.release(c)) return rc;
+    for (bool &g : on) g = false;
     return SAS_OK;
+}
+
+int Adam::alloc(sas_ctx *c, int row, int64_t n_pad, int colour_planes, hipStream_t st, bool zero)
+{
+    const size_t bytes = sizeof(float4) * (size_t)n_pad * (rows[row].colour ? colour_planes : 1);
+    if (const int rc = ensure(c, buf[row], bytes)) return rc;
+    if (zero) HIP_TRY(c, hipMemsetAsync(buf[row].p, 0, bytes, st));
+    return SAS_OK;
+}
+
+// Room for `count` Gaussians: whole waves of 64 slots, and 64 slots for an empty scene.
+int Planes::alloc(sas_ctx *c, int64_t count, int colour_planes)
+{
+    n = count;
+    n_pad = (count + 63) & ~63ll;
+    const size_t np = (size_t)(n_pad > 0 ? n_pad : 64), plane = sizeof(float4) * np;
+    int rc;
+    if ((rc = ensure(c, g0, plane)) || (rc = ensure(c, g1, plane)) || (rc = ensure(c, g2, plane)) || (rc = ensure(c, col, plane * colour_planes)) ||
+        (rc = ensure(c, gid8, np)) || (rc = ensure(c, perm, sizeof(int) * np)))
+        return rc;
+    return SAS_OK;
+}
+
+// What of the resident scene a call has changed: the values in the planes; the count and the storage order too; or everything.
+enum class Changed { Values, CountAndOrder, Everything };
+
+// The one place where the context forgets what it derived from the scene as it was: the last frame and its backward status, every slot's
+// kept projection records, and -- once more than values changed -- the intersection capacity and the stores that sit in storage order.
+void scene_changed(sas_ctx *c, Changed what)
+{
+    c->has_frame = false;
+    c->grad_frame = 0;
+    for (Slot &sl : c->slots) {
+        sl.info_kept = false;
+        if (what != Changed::Values) sl.scr.cap = 0;   // re-derive the intersection capacity for the new scene
+    }
+    if (what != Changed::Values) forget(c, HAVE_FEAT);
+    if (what == Changed::Everything) {
+        c->group_host.clear();
+        c->links = LinkConsts{};
+    }
+    c->scene_version++;
 }
 
 // 3-D Hilbert index (Skilling's transpose form), `bits` per axis.  Storage order of the scene:
@@ -409,6 +492,28 @@ void storage_order(int64_t n, const float *means, const uint8_t *gid, std::vecto
     for (int64_t i = 0; i < n; ++i) perm[(size_t)i] = (int)i;
     std::sort(perm.begin(), perm.end(), [&](int a, int b) { return key[a] != key[b] ? key[a] < key[b] : a < b; });
 }
+
+// Host copies of a scene's means and group ids (host or device arrays; gid nullptr: no groups), and its storage order from them.  fetch
+// copies with blocking calls, or on a stream it then waits for; what lies between the copies and order() is the caller's.
+struct OrderInput {
+    int64_t n = 0;
+    std::vector<float> means;
+    std::vector<uint8_t> gid;   // (empty: no groups)
+    int fetch(sas_ctx *c, int64_t count, const float *src_means, const uint8_t *src_gid, bool on_stream, hipStream_t st)
+    {
+        n = count;
+        means.resize((size_t)3 * n);
+        gid.resize(src_gid ? (size_t)n : 0);
+        auto copy = [&](void *dst, const void *src, size_t bytes) {
+            return on_stream ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipMemcpy(dst, src, bytes, hipMemcpyDefault);
+        };
+        HIP_TRY(c, copy(means.data(), src_means, sizeof(float) * 3 * n));
+        if (src_gid) HIP_TRY(c, copy(gid.data(), src_gid, (size_t)n));
+        if (on_stream) HIP_TRY(c, hipStreamSynchronize(st));
+        return SAS_OK;
+    }
+    void order(std::vector<int> &perm) const { storage_order(n, means.data(), gid.empty() ? nullptr : gid.data(), perm); }
+};
 
 // Camera constants in the oracle's operation order (oracle/sas_oracle.c cam_from, project_one).
 void make_cam(const float *V, const float *K, int W, int H, int tile_px, SasCam &c)
@@ -1134,35 +1239,22 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;
     forget(c, HAVE_SCENE);
-    if (const int rc = adam_drop(c)) return rc;
+    if (const int rc = c->adam.drop(c)) return rc;   // (hipFree waits for the step that may still be using the state)
 
     const int deg = sh_degree < 0 ? -1 : sh_degree;
-    const int coeff_floats = deg < 0 ? 3 : 3 * (deg + 1) * (deg + 1);
-    const int planes = (coeff_floats + 3) / 4;
-    const int64_t n_pad = (n + 63) & ~63ll;
+    const int coeff_floats = sas_coeff_floats(deg), planes = sas_colour_planes(deg);
+    Planes &pl = c->planes;
     int rc;
-    const size_t np = (size_t)(n_pad > 0 ? n_pad : 64);
-    if ((rc = ensure(c, c->g0, sizeof(float4) * np))) return rc;
-    if ((rc = ensure(c, c->g1, sizeof(float4) * np))) return rc;
-    if ((rc = ensure(c, c->g2, sizeof(float4) * np))) return rc;
-    if ((rc = ensure(c, c->col, sizeof(float4) * np * planes))) return rc;
-    if ((rc = ensure(c, c->gid8, np))) return rc;
-
-    c->perm_host.clear();
-    if ((rc = ensure(c, c->perm, sizeof(int) * np))) return rc;
+    if ((rc = pl.alloc(c, n, planes))) return rc;
+    pl.perm_host.clear();
     if (n > 0) {
         // storage order from host copies of the means / group ids
-        std::vector<float> h_means((size_t)3 * n);
-        std::vector<uint8_t> h_gid;
-        HIP_TRY(c, hipMemcpy(h_means.data(), means, sizeof(float) * 3 * n, hipMemcpyDefault));
-        if (group_id) {
-            h_gid.resize((size_t)n);
-            HIP_TRY(c, hipMemcpy(h_gid.data(), group_id, (size_t)n, hipMemcpyDefault));
-            for (int64_t i = 0; i < n; ++i)
-                if (h_gid[(size_t)i] >= n_groups) return fail(c, SAS_ERR_INVALID, "group_id[%lld]=%d >= n_groups=%d", (long long)i, (int)h_gid[(size_t)i], n_groups);
-        }
-        storage_order(n, h_means.data(), group_id ? h_gid.data() : nullptr, c->perm_host);
-        HIP_TRY(c, hipMemcpy(c->perm.p, c->perm_host.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        OrderInput in;
+        if ((rc = in.fetch(c, n, means, group_id, false, nullptr))) return rc;
+        for (int64_t i = 0; i < n && group_id; ++i)
+            if (in.gid[(size_t)i] >= n_groups) return fail(c, SAS_ERR_INVALID, "group_id[%lld]=%d >= n_groups=%d", (long long)i, (int)in.gid[(size_t)i], n_groups);
+        in.order(pl.perm_host);
+        HIP_TRY(c, hipMemcpy(pl.perm.p, pl.perm_host.data(), sizeof(int) * n, hipMemcpyHostToDevice));
 
         // stage the caller's arrays (host or device) and re-lay them out on the device
         DevBuf s_means, s_q, s_s, s_cov, s_op, s_col, s_gid;
@@ -1179,11 +1271,11 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
         if (!rc) rc = stage(s_col, colors, sizeof(float) * (size_t)coeff_floats * n);
         if (!rc && group_id) rc = stage(s_gid, group_id, (size_t)n);
         if (!rc) {
-            sas_launch_relayout(nullptr, n, n_pad, (const int *)c->perm.p, (const float *)s_means.p,
+            sas_launch_relayout(nullptr, n, pl.n_pad, (const int *)pl.perm.p, (const float *)s_means.p,
                                 (const float *)s_q.p, (const float *)s_s.p, (const float *)s_cov.p,
                                 (const float *)s_op.p, (const float *)s_col.p, coeff_floats, planes,
-                                (const uint8_t *)s_gid.p, (float4 *)c->g0.p, (float4 *)c->g1.p, (float4 *)c->g2.p,
-                                (float4 *)c->col.p, (uint8_t *)c->gid8.p);
+                                (const uint8_t *)s_gid.p, (float4 *)pl.g0.p, (float4 *)pl.g1.p, (float4 *)pl.g2.p,
+                                (float4 *)pl.col.p, (uint8_t *)pl.gid8.p);
             hipError_t e = hipDeviceSynchronize();
             if (e != hipSuccess) rc = fail(c, SAS_ERR_HIP, "relayout: %s", hipGetErrorString(e));
         }
@@ -1191,27 +1283,15 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
     }
 
     c->scene = SasScene{};
-    c->scene.g0 = (const float4 *)c->g0.p;
-    c->scene.g1 = (const float4 *)c->g1.p;
-    c->scene.g2 = (const float4 *)c->g2.p;
-    c->scene.col = (const float4 *)c->col.p;
-    c->scene.gid8 = (const uint8_t *)c->gid8.p;
-    c->scene.perm = (const int *)c->perm.p;
-    c->scene.n = n;
-    c->scene.n_pad = n_pad;
+    pl.bind(c->scene);
     c->scene.sh_degree = deg;
     c->scene.cov_mode = quat_mode ? 0 : 1;
     c->scene.n_groups = group_id ? n_groups : 0;
-    c->group_host.clear();
-    c->links = LinkConsts{};
+    scene_changed(c, Changed::Everything);
     if (group_id) {   // poses start as identity
         c->group_host.assign((size_t)12 * n_groups, 0.0f);
         for (int g = 0; g < n_groups; ++g) c->group_host[12 * g + 0] = c->group_host[12 * g + 5] = c->group_host[12 * g + 10] = 1.0f;
     }
-    for (Slot &sl : c->slots) sl.scr.cap = 0;  // re-derive the intersection capacity for the new scene
-    c->has_frame = false;
-    c->grad_frame = 0;
-    c->scene_version++;
     c->have |= HAVE_SCENE;
     return SAS_OK;
 }
@@ -1511,8 +1591,7 @@ int sas_render(sas_ctx *c, const float *viewmat, const float *K, int width, int 
 
 int sas_scene_features(sas_ctx *c, int64_t n, int channels, const float *features)
 {
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_features before sas_scene_upload");
+    if (const int rc = need_scene(c, "sas_scene_features")) return rc;
     forget(c, HAVE_MESH_FEAT);   // the triangles' rows belong to the store they were set beside
     if (n != c->scene.n) return fail(c, SAS_ERR_INVALID, "features for %lld Gaussians, the scene has %lld", (long long)n, (long long)c->scene.n);
     if (channels < 1 || channels > SAS_MAX_FEATURES) return fail(c, SAS_ERR_INVALID, "channels %d out of [1,%d]", channels, SAS_MAX_FEATURES);
@@ -1538,8 +1617,7 @@ int sas_render_features(sas_ctx *c, const float *viewmat, const float *K, int wi
                         const float *feature_background, unsigned flags, float *rgb, float *alpha, float *depth, float *features,
                         void *stream)
 {
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_render_features before sas_scene_upload");
+    if (const int rc = need_scene(c, "sas_render_features")) return rc;
     if (!has(c, HAVE_FEAT)) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
     if (has(c, HAVE_MESH) && !has(c, HAVE_MESH_FEAT))
         return fail(c, SAS_ERR_INVALID, "feature frames of a context with meshes are not supported (sas_scene_meshes) until the meshes "
@@ -1554,8 +1632,7 @@ int sas_render_features(sas_ctx *c, const float *viewmat, const float *K, int wi
 
 int sas_scene_mesh_features(sas_ctx *c, int64_t n_triangles, int channels, const float *features)
 {
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_mesh_features before sas_scene_upload");
+    if (const int rc = need_scene(c, "sas_scene_mesh_features")) return rc;
     if (!has(c, HAVE_MESH)) return fail(c, SAS_ERR_INVALID, "no meshes set for this scene (sas_scene_meshes)");
     if (!has(c, HAVE_FEAT)) return fail(c, SAS_ERR_INVALID, "no features set for this scene (sas_scene_features)");
     if (n_triangles != c->mesh.nt)
@@ -1584,8 +1661,7 @@ int sas_scene_mesh_features(sas_ctx *c, int64_t n_triangles, int channels, const
 int sas_scene_meshes(sas_ctx *c, int64_t n_vertices, const float *vertices, int64_t n_triangles, const int32_t *triangles,
                      const float *colors, const uint8_t *group, float ambient, float diffuse)
 {
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_meshes before sas_scene_upload");
+    if (const int rc = need_scene(c, "sas_scene_meshes")) return rc;
     forget(c, HAVE_MESH_FEAT | HAVE_MESH_ATTR);   // every call forgets the triangles' feature rows (sas_scene_mesh_features) and the vertex attributes
     if (n_triangles < 0 || n_vertices < 0 || n_triangles > (1 << 29) || n_vertices > 0x7fffffffll)
         return fail(c, SAS_ERR_INVALID, "bad mesh sizes: %lld vertices, %lld triangles", (long long)n_vertices, (long long)n_triangles);
@@ -1643,8 +1719,7 @@ int sas_scene_meshes(sas_ctx *c, int64_t n_vertices, const float *vertices, int6
 
 int sas_scene_mesh_vertex_attributes(sas_ctx *c, int64_t n_vertices, const float *normals, const float *colors)
 {
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "sas_scene_mesh_vertex_attributes before sas_scene_upload");
+    if (const int rc = need_scene(c, "sas_scene_mesh_vertex_attributes")) return rc;
     if (!has(c, HAVE_MESH)) return fail(c, SAS_ERR_INVALID, "no meshes set for this scene (sas_scene_meshes)");
     if (n_vertices != c->mesh.nv)
         return fail(c, SAS_ERR_INVALID, "attributes for %lld vertices, the meshes have %d", (long long)n_vertices, c->mesh.nv);
@@ -2166,8 +2241,7 @@ int sas_render_batch_posed(sas_ctx *c, int n_views, const float *viewmats, const
 // What a label frame needs in place, and the flags it takes: the call selects no store behind the caller's back.
 static int check_labels(sas_ctx *c, const char *who, unsigned flags, const uint8_t *labels)
 {
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (const int rc = need_scene(c, who)) return rc;
     if (!labels) return fail(c, SAS_ERR_INVALID, "%s: the labels output is required", who);
     if (flags & SAS_ASYNC) return fail(c, SAS_ERR_INVALID, "%s: blocking only (SAS_ASYNC is not supported)", who);
     if (flags & ~(SAS_MESH_SURFACE | SAS_DEPTH_FILL_MAX | SAS_FAST_EXP | SAS_TIMING))
@@ -2203,8 +2277,7 @@ int sas_render_batch_labels_posed(sas_ctx *c, int n_views, const float *viewmats
 // What every lift call checks first, and the flags it takes.
 static int check_lift(sas_ctx *c, const char *who, unsigned flags)
 {
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (const int rc = need_scene(c, who)) return rc;
     if (flags & ~(SAS_FAST_EXP | SAS_TIMING))
         return fail(c, SAS_ERR_INVALID, "%s: flags 0x%x not accepted (SAS_FAST_EXP, SAS_TIMING; blocking only)", who, flags);
     if (has(c, HAVE_MESH))
@@ -2271,6 +2344,43 @@ int sas_lift_features(sas_ctx *c, int n_views, const float *viewmats, const floa
     });
 }
 
+// a rate or a threshold: finite and not negative
+static int check_rate(sas_ctx *c, const char *who, const char *what, float v)
+{
+    return v >= 0.0f && v < INFINITY ? SAS_OK : fail(c, SAS_ERR_INVALID, "%s: %s %g is negative or not finite", who, what, (double)v);
+}
+
+// A scene holds quaternions and scales or covariances: the arrays of the other form are refused (`d`: "d_" for gradients, "" for values).
+static int check_form(sas_ctx *c, const char *who, bool quats_or_scales, bool cov6, const char *d)
+{
+    const bool cov = c->scene.cov_mode != 0;
+    if (cov ? !quats_or_scales : !cov6) return SAS_OK;
+    char ask[48];
+    snprintf(ask, sizeof(ask), cov ? "%scov6" : "%squats / %sscales", d, d);
+    return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as %s: ask for %s", who, cov ? "covariances" : "quaternions and scales", ask);
+}
+
+// Behind work on the caller's stream that reads or writes what the frames' own streams touch (a frame's projection does not wait for the
+// caller's stream: enqueue_chain, ORDER): every slot's stream is put behind it.
+static int slots_wait_for(sas_ctx *c, Event &ev, hipStream_t st)
+{
+    if (!ev.h) HIP_TRY(c, hipEventCreateWithFlags(ev.put(), hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(ev, st));
+    for (int s = 0; s < c->n_slots; ++s) HIP_TRY(c, hipStreamWaitEvent(c->slots[s].fs, ev, 0));
+    return SAS_OK;
+}
+
+// A backward frame's ViewOut: the view's pixel gradients and the five screen-space sums it adds to.
+static ViewOut grad_view(const float *g_rgb, const float *g_alpha, const float *g_depth, float *d_means2d, float *d_conics, float *d_opacities,
+                         float *d_colors, float *d_depths)
+{
+    ViewOut o;
+    o.grad = true;
+    o.grad_rgb = g_rgb; o.grad_alpha = g_alpha; o.grad_depth = g_depth;
+    o.grad_means2d = d_means2d; o.grad_conics = d_conics; o.grad_opacities = d_opacities; o.grad_colors = d_colors; o.grad_depths = d_depths;
+    return o;
+}
+
 // The backward pass of one view on its complete lists (k_grad_tiles): a lift frame whose sums are the screen-space gradients.
 int sas_render_backward_screen(sas_ctx *c, const float *viewmat, const float *K, int width, int height, unsigned flags,
                                const float *g_rgb, const float *g_alpha, const float *g_depth, float *d_means2d, float *d_conics,
@@ -2280,19 +2390,8 @@ int sas_render_backward_screen(sas_ctx *c, const float *viewmat, const float *K,
     if (!g_rgb && !g_alpha && !g_depth) return fail(c, SAS_ERR_INVALID, "sas_render_backward_screen: g_rgb, g_alpha and g_depth are all NULL");
     if (!d_means2d && !d_conics && !d_opacities && !d_colors && !d_depths)
         return fail(c, SAS_ERR_INVALID, "sas_render_backward_screen: every output is NULL");
-    const int rc = lift_views(c, "sas_render_backward_screen", 1, viewmat, K, width, height, flags, stream, [&](int) {
-        ViewOut o;
-        o.grad = true;
-        o.grad_rgb = g_rgb;
-        o.grad_alpha = g_alpha;
-        o.grad_depth = g_depth;
-        o.grad_means2d = d_means2d;
-        o.grad_conics = d_conics;
-        o.grad_opacities = d_opacities;
-        o.grad_colors = d_colors;
-        o.grad_depths = d_depths;
-        return o;
-    });
+    const int rc = lift_views(c, "sas_render_backward_screen", 1, viewmat, K, width, height, flags, stream,
+                              [&](int) { return grad_view(g_rgb, g_alpha, g_depth, d_means2d, d_conics, d_opacities, d_colors, d_depths); });
     if (!rc) c->grad_frame = 1;
     return rc;
 }
@@ -2308,9 +2407,7 @@ int sas_render_backward(sas_ctx *c, const float *viewmat, const float *K, int wi
     if (!g_rgb && !g_alpha && !g_depth) return fail(c, SAS_ERR_INVALID, "%s: g_rgb, g_alpha and g_depth are all NULL", who);
     if (!d_means && !d_opacities && !d_sh && !d_quats && !d_scales && !d_cov6 && !d_viewmat)
         return fail(c, SAS_ERR_INVALID, "%s: every output is NULL", who);
-    if (c->scene.cov_mode ? (d_quats || d_scales) : d_cov6 != nullptr)
-        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as %s: ask for %s", who, c->scene.cov_mode ? "covariances" : "quaternions and scales",
-                    c->scene.cov_mode ? "d_cov6" : "d_quats / d_scales");
+    if (const int rc = check_form(c, who, d_quats || d_scales, d_cov6 != nullptr, "d_")) return rc;
     if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->scene.n, n_wg = (n + 255) / 256;
@@ -2320,24 +2417,11 @@ int sas_render_backward(sas_ctx *c, const float *viewmat, const float *K, int wi
     if (const int rc = complete_all(c)) return rc;   // (nothing in flight reads the scratch)
     HIP_TRY(c, hipMemsetAsync(s, 0, floats * sizeof(float), (hipStream_t)stream));
     const int rc = lift_views(c, who, 1, viewmat, K, width, height, flags, stream, [&](int) {
-        ViewOut o;
-        o.grad = o.grad_chain = true;
-        o.grad_rgb = g_rgb;
-        o.grad_alpha = g_alpha;
-        o.grad_depth = g_depth;
-        o.grad_means2d = s;
-        o.grad_conics = s + 2 * n;
-        o.grad_opacities = s + 5 * n;
-        o.grad_colors = s + 6 * n;
-        o.grad_depths = s + 9 * n;
+        ViewOut o = grad_view(g_rgb, g_alpha, g_depth, s, s + 2 * n, s + 5 * n, s + 6 * n, s + 9 * n);
+        o.grad_chain = true;
         o.chain_partial = s + 10 * n;
-        o.chain_means = d_means;
-        o.chain_opacities = d_opacities;
-        o.chain_sh = d_sh;
-        o.chain_quats = d_quats;
-        o.chain_scales = d_scales;
-        o.chain_cov6 = d_cov6;
-        o.chain_viewmat = d_viewmat;
+        o.chain_means = d_means; o.chain_opacities = d_opacities; o.chain_sh = d_sh; o.chain_quats = d_quats; o.chain_scales = d_scales;
+        o.chain_cov6 = d_cov6; o.chain_viewmat = d_viewmat;
         return o;
     });
     if (!rc) c->grad_frame = 2;   // (sas_density_accumulate may read the sums in grad_screen)
@@ -2351,15 +2435,14 @@ int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_m
     const char *who = "sas_scene_adam_step";
     if (!c) return SAS_ERR_INVALID;
     if (!cfg) return fail(c, SAS_ERR_INVALID, "%s: cfg is NULL", who);
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (const int rc = need_scene(c, who)) return rc;
     if (!d_means && !d_opacities && !d_sh && !d_quats && !d_scales) return fail(c, SAS_ERR_INVALID, "%s: every gradient is NULL", who);
     if (cfg->step < 1) return fail(c, SAS_ERR_INVALID, "%s: step %d < 1 (the count is 1-based)", who, cfg->step);
-    const float lrs[6] = {cfg->lr_means, cfg->lr_opacities, cfg->lr_sh_dc, cfg->lr_sh_rest, cfg->lr_quats, cfg->lr_scales};
-    for (const float lr : lrs)
-        if (!(lr >= 0.0f && lr < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: learning rate %g is negative or not finite", who, (double)lr);
+    for (const float lr : {cfg->lr_means, cfg->lr_opacities, cfg->lr_sh_dc, cfg->lr_sh_rest, cfg->lr_quats, cfg->lr_scales})
+        if (const int rc = check_rate(c, who, "learning rate", lr)) return rc;
     if (!(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f) || !(cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f))
         return fail(c, SAS_ERR_INVALID, "%s: betas (%g, %g) outside [0, 1)", who, (double)cfg->beta1, (double)cfg->beta2);
-    if (!(cfg->eps >= 0.0f && cfg->eps < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: eps %g is negative or not finite", who, (double)cfg->eps);
+    if (const int rc = check_rate(c, who, "eps", cfg->eps)) return rc;
     if (cfg->flags & ~SAS_ADAM_VISIBLE_ONLY) return fail(c, SAS_ERR_INVALID, "%s: unknown flags 0x%x", who, cfg->flags);
     if (c->scene.cov_mode && (d_quats || d_scales))
         return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as covariances, which are not variables: d_quats / d_scales must be NULL", who);
@@ -2370,41 +2453,26 @@ int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_m
                on_sh = d_sh && (cfg->lr_sh_dc > 0.0f || cfg->lr_sh_rest > 0.0f), on_quats = d_quats && cfg->lr_quats > 0.0f,
                on_scales = d_scales && cfg->lr_scales > 0.0f;
     if (sc.n <= 0 || !(on_means || on_opac || on_sh || on_quats || on_scales)) return SAS_OK;   // nothing moves: the last frame stays valid
+    bool stepped[Adam::GROUPS];
+    stepped[Adam::MEANS] = on_means; stepped[Adam::OPACITIES] = on_opac; stepped[Adam::SH] = on_sh; stepped[Adam::QUATS] = on_quats; stepped[Adam::SCALES] = on_scales;
     hipStream_t st = (hipStream_t)stream;
-    const int coeff_floats = sc.sh_degree < 0 ? 3 : 3 * (sc.sh_degree + 1) * (sc.sh_degree + 1);
-    const int planes = (coeff_floats + 3) / 4;
-    const size_t plane = sizeof(float4) * (size_t)sc.n_pad;
-    sas_ctx::Adam &a = c->adam;
-    int rc;
-    // a group stepped for the first time: zero moments (and raw values from the resident ones), on the caller's stream
-    auto fresh = [&](DevBuf &b, size_t bytes, bool zero) -> int {
-        if (const int r = ensure(c, b, bytes)) return r;
-        if (zero) HIP_TRY(c, hipMemsetAsync(b.p, 0, bytes, st));
-        return SAS_OK;
-    };
-    if (on_means && !a.means) {
-        if ((rc = fresh(a.means_m, plane, true)) || (rc = fresh(a.means_v, plane, true))) return rc;
-        a.means = true;
+    const int coeff_floats = sas_coeff_floats(sc.sh_degree), planes = sas_colour_planes(sc.sh_degree);
+    Adam &a = c->adam;
+    // a group stepped for the first time: zero moments (and raw values from the resident ones), on the caller's stream, group by group
+    bool fresh[Adam::GROUPS];
+    for (int g = 0; g < Adam::GROUPS; ++g) {
+        fresh[g] = stepped[g] && !a.on[g];
+        for (int k = 0; k < Adam::kRows && fresh[g]; ++k)
+            if (Adam::rows[k].group == g)
+                if (const int rc = a.alloc(c, k, sc.n_pad, planes, st, Adam::rows[k].zeroed)) return rc;
     }
-    if (on_quats && !a.quats) {
-        if ((rc = fresh(a.quats_m, plane, true)) || (rc = fresh(a.quats_v, plane, true))) return rc;
-        a.quats = true;
-    }
-    if (on_sh && !a.sh) {
-        if ((rc = fresh(a.sh_m, plane * planes, true)) || (rc = fresh(a.sh_v, plane * planes, true))) return rc;
-        a.sh = true;
-    }
-    const bool new_opac = on_opac && !a.opacities, new_scales = on_scales && !a.scales;
-    if (new_opac && (rc = fresh(a.opac, plane, false))) return rc;
-    if (new_scales && ((rc = fresh(a.scales_m, plane, true)) || (rc = fresh(a.scales_v, plane, true)) || (rc = fresh(a.scales_raw, plane, false)))) return rc;
-    if (new_opac || new_scales) {
-        sas_launch_adam_init(st, sc.n, sc.g0, sc.g2, new_opac ? (float4 *)a.opac.p : nullptr, new_scales ? (float4 *)a.scales_raw.p : nullptr);
+    if (fresh[Adam::OPACITIES] || fresh[Adam::SCALES]) {
+        sas_launch_adam_init(st, sc.n, sc.g0, sc.g2, a.view(fresh));
         HIP_TRY(c, hipGetLastError());
-        a.opacities = a.opacities || new_opac;
-        a.scales = a.scales || new_scales;
     }
+    for (int g = 0; g < Adam::GROUPS; ++g) a.on[g] = a.on[g] || fresh[g];
     SasAdam k{};
-    k.g0 = (float4 *)c->g0.p; k.g1 = (float4 *)c->g1.p; k.g2 = (float4 *)c->g2.p; k.col = (float4 *)c->col.p;
+    k.g0 = (float4 *)c->planes.g0.p; k.g1 = (float4 *)c->planes.g1.p; k.g2 = (float4 *)c->planes.g2.p; k.col = (float4 *)c->planes.col.p;
     k.perm = sc.perm;
     k.n = sc.n; k.n_pad = sc.n_pad;
     k.coeff_floats = coeff_floats; k.planes = planes;
@@ -2413,11 +2481,7 @@ int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_m
     k.d_sh = on_sh ? d_sh : nullptr;
     k.d_quats = on_quats ? d_quats : nullptr;
     k.d_scales = on_scales ? d_scales : nullptr;
-    k.means_m = (float4 *)a.means_m.p; k.means_v = (float4 *)a.means_v.p;
-    k.opac = (float4 *)a.opac.p;
-    k.quats_m = (float4 *)a.quats_m.p; k.quats_v = (float4 *)a.quats_v.p;
-    k.scales_m = (float4 *)a.scales_m.p; k.scales_v = (float4 *)a.scales_v.p; k.scales_raw = (float4 *)a.scales_raw.p;
-    k.sh_m = (float4 *)a.sh_m.p; k.sh_v = (float4 *)a.sh_v.p;
+    k.s = a.view();
     k.lr_means = cfg->lr_means; k.lr_opac = cfg->lr_opacities; k.lr_sh_dc = cfg->lr_sh_dc; k.lr_sh_rest = cfg->lr_sh_rest;
     k.lr_quats = cfg->lr_quats; k.lr_scales = cfg->lr_scales;
     k.beta1 = cfg->beta1; k.beta2 = cfg->beta2;
@@ -2429,15 +2493,8 @@ int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_m
     k.sh_aligned = coeff_floats % 4 == 0 && ((uintptr_t)d_sh & 15u) == 0;
     sas_launch_adam_scene(st, k);
     HIP_TRY(c, hipGetLastError());
-    // A frame's projection does not wait for the caller's stream (enqueue_chain, ORDER): every slot's stream is put behind the step.
-    if (!c->adam_done.h) HIP_TRY(c, hipEventCreateWithFlags(c->adam_done.put(), hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->adam_done, st));
-    for (int s = 0; s < c->n_slots; ++s) HIP_TRY(c, hipStreamWaitEvent(c->slots[s].fs, c->adam_done, 0));
-    // the last frame showed the scene before the step
-    c->has_frame = false;
-    c->grad_frame = 0;
-    for (Slot &sl : c->slots) sl.info_kept = false;
-    c->scene_version++;
+    if (const int rc = slots_wait_for(c, c->adam_done, st)) return rc;
+    scene_changed(c, Changed::Values);   // the last frame showed the scene before the step
     return SAS_OK;
 }
 
@@ -2484,17 +2541,7 @@ int sas_scene_adam_reset(sas_ctx *c)
     if (!c) return SAS_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;
-    return adam_drop(c);
-}
-
-// Behind work on the caller's stream that reads or writes what the frames' own streams touch (a frame's projection does not wait for the
-// caller's stream: enqueue_chain, ORDER): every slot's stream is put behind it.
-static int slots_wait_for(sas_ctx *c, Event &ev, hipStream_t st)
-{
-    if (!ev.h) HIP_TRY(c, hipEventCreateWithFlags(ev.put(), hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(ev, st));
-    for (int s = 0; s < c->n_slots; ++s) HIP_TRY(c, hipStreamWaitEvent(c->slots[s].fs, ev, 0));
-    return SAS_OK;
+    return c->adam.drop(c);   // (hipFree waits for the step that may still be using the state)
 }
 
 // The statistics of the last backward frame (k_density_accumulate): its info records are in the slot's scratch, its screen-space sums in the
@@ -2503,8 +2550,7 @@ int sas_density_accumulate(sas_ctx *c, int width, int height, const float *d_mea
                            void *stream)
 {
     const char *who = "sas_density_accumulate";
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (const int rc = need_scene(c, who)) return rc;
     if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
     if (!grad_sum || !count) return fail(c, SAS_ERR_INVALID, "%s: grad_sum and count are required", who);
     if (!c->has_frame || c->grad_frame == 0)
@@ -2534,15 +2580,13 @@ int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *gr
                       int64_t counts_out[4], void *stream)
 {
     const char *who = "sas_scene_densify";
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (const int rc = need_scene(c, who)) return rc;
     if (!cfg) return fail(c, SAS_ERR_INVALID, "%s: cfg is NULL", who);
     if (!grad_sum || !count || !counts_out) return fail(c, SAS_ERR_INVALID, "%s: grad_sum, count and counts_out are required", who);
     if (cfg->flags & ~(SAS_DENSIFY_GROW | SAS_DENSIFY_PRUNE_OPACITY | SAS_DENSIFY_PRUNE_SCALE))
         return fail(c, SAS_ERR_INVALID, "%s: unknown flags 0x%x", who, cfg->flags);
-    const float thr[4] = {cfg->grow_grad2d, cfg->grow_scale3d, cfg->prune_opacity, cfg->prune_scale3d};
-    for (const float t : thr)
-        if (!(t >= 0.0f && t < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: threshold %g is negative or not finite", who, (double)t);
+    for (const float t : {cfg->grow_grad2d, cfg->grow_scale3d, cfg->prune_opacity, cfg->prune_scale3d})
+        if (const int rc = check_rate(c, who, "threshold", t)) return rc;
     if (!(cfg->scene_extent > 0.0f && cfg->scene_extent < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: scene_extent %g is not positive and finite", who, (double)cfg->scene_extent);
     if (!(cfg->split_factor > 1.0f && cfg->split_factor < INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: split_factor %g <= 1", who, (double)cfg->split_factor);
     if (cfg->max_gaussians < 0 || cfg->max_gaussians > 0x7fffffffll) return fail(c, SAS_ERR_INVALID, "%s: max_gaussians %lld out of range", who, (long long)cfg->max_gaussians);
@@ -2553,8 +2597,7 @@ int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *gr
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int coeff_floats = sc.sh_degree < 0 ? 3 : 3 * (sc.sh_degree + 1) * (sc.sh_degree + 1);
-    const int planes = (coeff_floats + 3) / 4;
+    const int coeff_floats = sas_coeff_floats(sc.sh_degree), planes = sas_colour_planes(sc.sh_degree);
     const size_t n = (size_t)sc.n, nb = (n + 255) / 256;
     int rc;
     if ((rc = ensure(c, c->density_inv, sizeof(int) * n)) || (rc = ensure(c, c->density_cls, n)) ||
@@ -2612,82 +2655,36 @@ int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *gr
     sas_launch_density_scatter(st, q);
     HIP_TRY(c, hipGetLastError());
     // its storage order, on the host as for an upload
-    std::vector<float> h_means(3 * m);
-    std::vector<uint8_t> h_gid;
-    HIP_TRY(c, hipMemcpyAsync(h_means.data(), q.means, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, st));
-    if (q.gid) {
-        h_gid.resize(m);
-        HIP_TRY(c, hipMemcpyAsync(h_gid.data(), q.gid, m, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(c, hipStreamSynchronize(st));
+    OrderInput in;
+    if ((rc = in.fetch(c, pl.n_new, q.means, q.gid, true, st))) return rc;
     lap(1);
-    std::vector<int> perm_host;
-    storage_order(pl.n_new, h_means.data(), q.gid ? h_gid.data() : nullptr, perm_host);
+    Planes np;   // new planes and new state, beside the old ones
+    Adam na;
+    in.order(np.perm_host);
     lap(2);
-
-    // new planes and new state, beside the old ones
-    const int64_t n_pad = (pl.n_new + 63) & ~63ll;
-    const size_t np = (size_t)n_pad, plane = sizeof(float4) * np;
-    DevBuf g0, g1, g2, col, gid8, perm;
-    if ((rc = ensure(c, g0, plane)) || (rc = ensure(c, g1, plane)) || (rc = ensure(c, g2, plane)) || (rc = ensure(c, col, plane * planes)) ||
-        (rc = ensure(c, gid8, np)) || (rc = ensure(c, perm, sizeof(int) * np)))
-        return rc;
-    sas_ctx::Adam &a = c->adam;
-    sas_ctx::Adam na;
-    auto fresh = [&](bool on, DevBuf &b, size_t bytes) -> int {
-        if (!on) return SAS_OK;
-        if (const int r = ensure(c, b, bytes)) return r;
-        HIP_TRY(c, hipMemsetAsync(b.p, 0, bytes, st));
-        return SAS_OK;
-    };
-    if ((rc = fresh(a.means, na.means_m, plane)) || (rc = fresh(a.means, na.means_v, plane)) || (rc = fresh(a.opacities, na.opac, plane)) ||
-        (rc = fresh(a.quats, na.quats_m, plane)) || (rc = fresh(a.quats, na.quats_v, plane)) || (rc = fresh(a.scales, na.scales_m, plane)) ||
-        (rc = fresh(a.scales, na.scales_v, plane)) || (rc = fresh(a.scales, na.scales_raw, plane)) || (rc = fresh(a.sh, na.sh_m, plane * planes)) ||
-        (rc = fresh(a.sh, na.sh_v, plane * planes)))
-        return rc;
-    HIP_TRY(c, hipMemcpyAsync(perm.p, perm_host.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
-    sas_launch_relayout(st, pl.n_new, n_pad, (const int *)perm.p, q.means, q.quats, q.scales, q.cov6, q.opac, q.colors, coeff_floats, planes,
-                        q.gid, (float4 *)g0.p, (float4 *)g1.p, (float4 *)g2.p, (float4 *)col.p, (uint8_t *)gid8.p);
+    if ((rc = np.alloc(c, pl.n_new, planes))) return rc;
+    std::copy(c->adam.on, c->adam.on + Adam::GROUPS, na.on);
+    for (int k = 0; k < Adam::kRows; ++k)   // (every buffer zeroed: the lanes n .. n_pad)
+        if (na.on[Adam::rows[k].group] && (rc = na.alloc(c, k, np.n_pad, planes, st, true))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(np.perm.p, np.perm_host.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+    sas_launch_relayout(st, pl.n_new, np.n_pad, (const int *)np.perm.p, q.means, q.quats, q.scales, q.cov6, q.opac, q.colors, coeff_floats, planes,
+                        q.gid, (float4 *)np.g0.p, (float4 *)np.g1.p, (float4 *)np.g2.p, (float4 *)np.col.p, (uint8_t *)np.gid8.p);
     SasDensityState s{};
-    s.perm_new = (const int *)perm.p; s.parents = q.parents; s.inv_old = q.inv;
-    s.g0_new = (const float4 *)g0.p; s.g2_new = (const float4 *)g2.p;
-    s.n_new = pl.n_new; s.n_survivors = pl.survivors; s.n_old = sc.n; s.n_pad_old = sc.n_pad; s.n_pad_new = n_pad;
+    s.perm_new = (const int *)np.perm.p; s.parents = q.parents; s.inv_old = q.inv;
+    s.g0_new = (const float4 *)np.g0.p; s.g2_new = (const float4 *)np.g2.p;
+    s.n_new = pl.n_new; s.n_survivors = pl.survivors; s.n_old = sc.n; s.n_pad_old = sc.n_pad; s.n_pad_new = np.n_pad;
     s.planes = planes;
-    s.old_means_m = (const float4 *)a.means_m.p; s.old_means_v = (const float4 *)a.means_v.p; s.old_opac = (const float4 *)a.opac.p;
-    s.old_quats_m = (const float4 *)a.quats_m.p; s.old_quats_v = (const float4 *)a.quats_v.p;
-    s.old_scales_m = (const float4 *)a.scales_m.p; s.old_scales_v = (const float4 *)a.scales_v.p; s.old_scales_raw = (const float4 *)a.scales_raw.p;
-    s.old_sh_m = (const float4 *)a.sh_m.p; s.old_sh_v = (const float4 *)a.sh_v.p;
-    s.means_m = (float4 *)na.means_m.p; s.means_v = (float4 *)na.means_v.p; s.opac = (float4 *)na.opac.p;
-    s.quats_m = (float4 *)na.quats_m.p; s.quats_v = (float4 *)na.quats_v.p;
-    s.scales_m = (float4 *)na.scales_m.p; s.scales_v = (float4 *)na.scales_v.p; s.scales_raw = (float4 *)na.scales_raw.p;
-    s.sh_m = (float4 *)na.sh_m.p; s.sh_v = (float4 *)na.sh_v.p;
+    s.old_ = c->adam.view();
+    s.new_ = na.view();
     sas_launch_density_state(st, s);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(st));   // (nothing above has changed the context: a failure so far leaves the scene as it was)
 
     // the context takes the new scene (the old buffers go with this scope)
-    c->g0 = std::move(g0); c->g1 = std::move(g1); c->g2 = std::move(g2); c->col = std::move(col); c->gid8 = std::move(gid8); c->perm = std::move(perm);
-    a.means_m = std::move(na.means_m); a.means_v = std::move(na.means_v); a.opac = std::move(na.opac);
-    a.quats_m = std::move(na.quats_m); a.quats_v = std::move(na.quats_v);
-    a.scales_m = std::move(na.scales_m); a.scales_v = std::move(na.scales_v); a.scales_raw = std::move(na.scales_raw);
-    a.sh_m = std::move(na.sh_m); a.sh_v = std::move(na.sh_v);
-    c->perm_host = std::move(perm_host);
-    c->scene.g0 = (const float4 *)c->g0.p;
-    c->scene.g1 = (const float4 *)c->g1.p;
-    c->scene.g2 = (const float4 *)c->g2.p;
-    c->scene.col = (const float4 *)c->col.p;
-    c->scene.gid8 = (const uint8_t *)c->gid8.p;
-    c->scene.perm = (const int *)c->perm.p;
-    c->scene.n = pl.n_new;
-    c->scene.n_pad = n_pad;
-    forget(c, HAVE_FEAT);
-    for (Slot &sl : c->slots) {
-        sl.scr.cap = 0;   // re-derive the intersection capacity for the new scene
-        sl.info_kept = false;
-    }
-    c->has_frame = false;
-    c->grad_frame = 0;
-    c->scene_version++;
+    std::swap(c->planes, np);
+    std::swap(c->adam, na);
+    c->planes.bind(c->scene);
+    scene_changed(c, Changed::CountAndOrder);
     counts_out[0] = pl.n_new;
     counts_out[1] = pl.clones;
     counts_out[2] = pl.splits;
@@ -2706,20 +2703,16 @@ int sas_scene_densify_times(sas_ctx *c, float *ms, int n)
 int sas_scene_reset_opacity(sas_ctx *c, float max_opacity, void *stream)
 {
     const char *who = "sas_scene_reset_opacity";
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
+    if (const int rc = need_scene(c, who)) return rc;
     if (!(max_opacity > 0.0f && max_opacity < 1.0f)) return fail(c, SAS_ERR_INVALID, "%s: max_opacity %g outside (0, 1)", who, (double)max_opacity);
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;   // (no frame reads the planes while they change)
     if (c->scene.n <= 0) return SAS_OK;
     hipStream_t st = (hipStream_t)stream;
-    sas_launch_opacity_reset(st, c->scene.n, max_opacity, (float4 *)c->g0.p, c->adam.opacities ? (float4 *)c->adam.opac.p : nullptr);
+    sas_launch_opacity_reset(st, c->scene.n, max_opacity, (float4 *)c->planes.g0.p, c->adam.on[Adam::OPACITIES] ? c->adam.view().opac : nullptr);
     HIP_TRY(c, hipGetLastError());
     if (const int rc = slots_wait_for(c, c->density_done, st)) return rc;
-    c->has_frame = false;
-    c->grad_frame = 0;
-    for (Slot &sl : c->slots) sl.info_kept = false;
-    c->scene_version++;
+    scene_changed(c, Changed::Values);
     return SAS_OK;
 }
 
@@ -2727,17 +2720,14 @@ int sas_scene_reset_opacity(sas_ctx *c, float max_opacity, void *stream)
 int sas_scene_read(sas_ctx *c, float *means, float *quats, float *scales, float *cov6, float *opacities, float *colors)
 {
     const char *who = "sas_scene_read";
-    if (!c) return SAS_ERR_INVALID;
-    if (!has(c, HAVE_SCENE)) return fail(c, SAS_ERR_NO_SCENE, "%s before sas_scene_upload", who);
-    if (c->scene.cov_mode ? (quats || scales) : cov6 != nullptr)
-        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as %s: ask for %s", who, c->scene.cov_mode ? "covariances" : "quaternions and scales",
-                    c->scene.cov_mode ? "cov6" : "quats / scales");
+    if (const int rc = need_scene(c, who)) return rc;
+    if (const int rc = check_form(c, who, quats || scales, cov6 != nullptr, "")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;
     const SasScene &sc = c->scene;
     const size_t n = (size_t)sc.n;
     if (n == 0) return SAS_OK;
-    const int coeff_floats = sc.sh_degree < 0 ? 3 : 3 * (sc.sh_degree + 1) * (sc.sh_degree + 1);
+    const int coeff_floats = sas_coeff_floats(sc.sh_degree);
     float *user[6] = {means, quats, scales, cov6, opacities, colors};
     const size_t floats[6] = {3 * n, 4 * n, 3 * n, 6 * n, n, (size_t)coeff_floats * n};
     float *dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -2751,7 +2741,7 @@ int sas_scene_read(sas_ctx *c, float *means, float *quats, float *scales, float 
         if (const int rc = ensure(c, stage[k], sizeof(float) * floats[k])) return rc;
         dev[k] = (float *)stage[k].p;
     }
-    const SasGather q{sc.g0, sc.g1, sc.g2, sc.col, sc.perm, sc.n, sc.n_pad, coeff_floats, (coeff_floats + 3) / 4,
+    const SasGather q{sc.g0, sc.g1, sc.g2, sc.col, sc.perm, sc.n, sc.n_pad, coeff_floats, sas_colour_planes(sc.sh_degree),
                       dev[0], dev[1], dev[2], dev[3], dev[4], dev[5]};
     hipStream_t st = c->slots[0].fs;
     sas_launch_scene_gather(st, q);
@@ -2914,7 +2904,7 @@ int sas_read_projection(sas_ctx *c, int32_t *radii, float *means2d, float *depth
         HIP_TRY(c, hipMemcpy(info.data(), q.info.p, sizeof(uint32_t) * 4 * n, hipMemcpyDeviceToHost));
     }
     for (int64_t j = 0; j < n; ++j) {
-        const int64_t i = c->perm_host[(size_t)j];   // slot j holds the caller's Gaussian i
+        const int64_t i = c->planes.perm_host[(size_t)j];   // slot j holds the caller's Gaussian i
         const uint32_t rx = info[4 * j + 2], ry = info[4 * j + 3];   // radii: 32 bits each
         const bool vis = rx != 0;
         const float *r = &rec[8 * j], *cl = &col[4 * j];
@@ -2948,7 +2938,7 @@ int sas_read_tile_lists(sas_ctx *c, int32_t *tile_offsets, int32_t *sorted_ids, 
         if (m > 0) HIP_TRY(c, hipMemcpy(sorted_ids, q.ids.p, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost));
         for (int64_t k = 0; k < m; ++k) {   // storage slots -> caller indices
             const int j = sorted_ids[k];
-            sorted_ids[k] = (j >= 0 && j < c->scene.n) ? c->perm_host[(size_t)j] : -1;
+            sorted_ids[k] = (j >= 0 && j < c->scene.n) ? c->planes.perm_host[(size_t)j] : -1;
         }
     }
     return SAS_OK;

@@ -217,29 +217,25 @@ __global__ __launch_bounds__(kThreads) void k_density_state(const SasDensityStat
     if (!SAS_IN(p, q.n_old, 1012)) return;
     const long long js = q.inv_old[p];                                    // the parent's old slot
     if (!SAS_IN(js, q.n_pad_old, 1013) || !SAS_IN(j, q.n_pad_new, 1014)) return;
-    if (q.means_m) { q.means_m[j] = state_or_zero(q.old_means_m, js, fresh); q.means_v[j] = state_or_zero(q.old_means_v, js, fresh); }
-    if (q.quats_m) { q.quats_m[j] = state_or_zero(q.old_quats_m, js, fresh); q.quats_v[j] = state_or_zero(q.old_quats_v, js, fresh); }
-    if (q.opac) {   // fresh: as k_adam_init
-        const float o = q.g0_new[j].w;
-        q.opac[j] = fresh ? make_float4(0.0f, 0.0f, (o > 0.0f && o < 1.0f) ? logf(o / (1.0f - o)) : NAN, 0.0f) : q.old_opac[js];
-    }
-    if (q.scales_m) {
-        q.scales_m[j] = state_or_zero(q.old_scales_m, js, fresh);
-        q.scales_v[j] = state_or_zero(q.old_scales_v, js, fresh);
-        float4 r = fresh ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : q.old_scales_raw[js];
+    const SasAdamState &o = q.old_, &s = q.new_;
+    if (s.means_m) { s.means_m[j] = state_or_zero(o.means_m, js, fresh); s.means_v[j] = state_or_zero(o.means_v, js, fresh); }
+    if (s.quats_m) { s.quats_m[j] = state_or_zero(o.quats_m, js, fresh); s.quats_v[j] = state_or_zero(o.quats_v, js, fresh); }
+    if (s.opac) s.opac[j] = fresh ? make_float4(0.0f, 0.0f, raw_opacity(q.g0_new[j].w), 0.0f) : o.opac[js];
+    if (s.scales_m) {
+        s.scales_m[j] = state_or_zero(o.scales_m, js, fresh);
+        s.scales_v[j] = state_or_zero(o.scales_v, js, fresh);
+        float4 r = fresh ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : o.scales_raw[js];
         if (fresh) {
             const float4 G = q.g2_new[j];
-            r.x = (G.x > 0.0f && G.x < INFINITY) ? logf(G.x) : NAN;
-            r.y = (G.y > 0.0f && G.y < INFINITY) ? logf(G.y) : NAN;
-            r.z = (G.z > 0.0f && G.z < INFINITY) ? logf(G.z) : NAN;
+            r.x = raw_scale(G.x); r.y = raw_scale(G.y); r.z = raw_scale(G.z);
         }
-        q.scales_raw[j] = r;
+        s.scales_raw[j] = r;
     }
-    if (q.sh_m)
+    if (s.sh_m)
         for (int pl = 0; pl < q.planes; ++pl) {
-            const long long o = (long long)pl * q.n_pad_new + j, os = (long long)pl * q.n_pad_old + js;
-            q.sh_m[o] = state_or_zero(q.old_sh_m, os, fresh);
-            q.sh_v[o] = state_or_zero(q.old_sh_v, os, fresh);
+            const long long on = (long long)pl * q.n_pad_new + j, os = (long long)pl * q.n_pad_old + js;
+            s.sh_m[on] = state_or_zero(o.sh_m, os, fresh);
+            s.sh_v[on] = state_or_zero(o.sh_v, os, fresh);
         }
 }
 
@@ -250,7 +246,7 @@ __global__ __launch_bounds__(kThreads) void k_opacity_reset(long long n, float c
     float *o = reinterpret_cast<float *>(g0 + j) + 3;
     if (!(*o > cap)) return;   // (a NaN stays)
     *o = cap;
-    if (opac) opac[j] = make_float4(0.0f, 0.0f, logf(cap / (1.0f - cap)), opac[j].w);
+    if (opac) opac[j] = make_float4(0.0f, 0.0f, raw_opacity(cap), opac[j].w);
 }
 
 unsigned grid_of(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }

@@ -59,6 +59,11 @@ DEV float4 nt_load(const float4 *p)
     return make_float4(v.x, v.y, v.z, v.w);
 }
 
+// The inverse activations of the optimiser's raw variables (sas_fit.hip, sas_density.hip): logit(opacity) and log(scale).  NaN marks a
+// value outside the domain -- an opacity outside (0, 1), a scale that is no positive finite number: that variable stays fixed.
+DEV float raw_opacity(float o) { return (o > 0.0f && o < 1.0f) ? logf(o / (1.0f - o)) : NAN; }
+DEV float raw_scale(float s) { return (s > 0.0f && s < INFINITY) ? logf(s) : NAN; }
+
 // ---- wave64 reductions and scan on the DPP network --------------------------------------------------------------------------------
 // hipcc lowers __shfl_xor / __shfl_up to ds_bpermute_b32: a trip through the LDS crossbar per step, six DEPENDENT trips per reduction
 // (~0.3 us on the chain of a workgroup that does nothing else meanwhile).  The same steps as DPP operand modifiers cost a few

@@ -9,7 +9,7 @@
 //                   to its cache lines) and the planes are stored plainly -- the next frame's projection reads them.  Never written: g2.w (the group bits), the zero padding of the last colour plane, the lanes
 //                   n .. n_pad of any plane.
 //   k_adam_init     the raw values log(scale) and logit(opacity) of a group that is stepped for the first time, from the resident
-//                   values; NaN marks a value outside the domain of its inverse activation: that variable stays fixed.
+//                   values (raw_scale, raw_opacity); NaN marks a value outside the domain of its inverse activation: that variable stays fixed.
 //   k_scene_gather  the inverse of k_relayout: planes -> the caller's AoS arrays through perm.
 // No LDS, no atomics, no wait between workgroups: a Gaussian's step depends on its own slot only.
 // Arithmetic: IEEE binary32, nothing fused (-ffp-contract=off, no fma_); correctly rounded / and sqrt, libm expf / logf.
@@ -78,38 +78,38 @@ __global__ __launch_bounds__(256) void k_adam_scene(const SasAdam A)
     if (A.d_means || A.d_opac) {   // g0 = (mean, opacity)
         float4 P = A.g0[j];
         if (A.d_means) {
-            float4 M = nt_load(A.means_m + j), V = nt_load(A.means_v + j);
+            float4 M = nt_load(A.s.means_m + j), V = nt_load(A.s.means_v + j);
             adam_elem(A, A.d_means[3 * i + 0], A.lr_means, M.x, V.x, P.x);
             adam_elem(A, A.d_means[3 * i + 1], A.lr_means, M.y, V.y, P.y);
             adam_elem(A, A.d_means[3 * i + 2], A.lr_means, M.z, V.z, P.z);
-            nt_store(A.means_m + j, M);
-            nt_store(A.means_v + j, V);
+            nt_store(A.s.means_m + j, M);
+            nt_store(A.s.means_v + j, V);
         }
         if (A.d_opac) {
-            float4 S = nt_load(A.opac + j);   // (m, v, logit, -)
+            float4 S = nt_load(A.s.opac + j);   // (m, v, logit, -)
             if (S.z == S.z) {                 // (NaN: the resident opacity was outside (0, 1) -- fixed)
                 const float g = A.d_opac[i] * (P.w * (1.0f - P.w));
                 if (adam_elem(A, g, A.lr_opac, S.x, S.y, S.z)) {
                     P.w = 1.0f / (1.0f + expf(-S.z));
-                    nt_store(A.opac + j, S);
+                    nt_store(A.s.opac + j, S);
                 }
             }
         }
         A.g0[j] = P;
     }
     if (A.d_quats) {   // g1 = the quaternion as uploaded
-        float4 Q = A.g1[j], M = nt_load(A.quats_m + j), V = nt_load(A.quats_v + j);
+        float4 Q = A.g1[j], M = nt_load(A.s.quats_m + j), V = nt_load(A.s.quats_v + j);
         adam_elem(A, A.d_quats[4 * i + 0], A.lr_quats, M.x, V.x, Q.x);
         adam_elem(A, A.d_quats[4 * i + 1], A.lr_quats, M.y, V.y, Q.y);
         adam_elem(A, A.d_quats[4 * i + 2], A.lr_quats, M.z, V.z, Q.z);
         adam_elem(A, A.d_quats[4 * i + 3], A.lr_quats, M.w, V.w, Q.w);
-        nt_store(A.quats_m + j, M);
-        nt_store(A.quats_v + j, V);
+        nt_store(A.s.quats_m + j, M);
+        nt_store(A.s.quats_v + j, V);
         A.g1[j] = Q;
     }
     if (A.d_scales) {   // g2 = (scale, group bits): the bits are neither changed nor stored
         const float4 G = A.g2[j];
-        const float4 M = nt_load(A.scales_m + j), V = nt_load(A.scales_v + j), R = nt_load(A.scales_raw + j);
+        const float4 M = nt_load(A.s.scales_m + j), V = nt_load(A.s.scales_v + j), R = nt_load(A.s.scales_raw + j);
         float s[3] = {G.x, G.y, G.z}, m[3] = {M.x, M.y, M.z}, v[3] = {V.x, V.y, V.z}, raw[3] = {R.x, R.y, R.z};
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -117,9 +117,9 @@ __global__ __launch_bounds__(256) void k_adam_scene(const SasAdam A)
             const float g = A.d_scales[3 * i + k] * s[k];
             if (adam_elem(A, g, A.lr_scales, m[k], v[k], raw[k])) s[k] = expf(raw[k]);
         }
-        nt_store(A.scales_m + j, make_float4(m[0], m[1], m[2], M.w));
-        nt_store(A.scales_v + j, make_float4(v[0], v[1], v[2], V.w));
-        nt_store(A.scales_raw + j, make_float4(raw[0], raw[1], raw[2], R.w));
+        nt_store(A.s.scales_m + j, make_float4(m[0], m[1], m[2], M.w));
+        nt_store(A.s.scales_v + j, make_float4(v[0], v[1], v[2], V.w));
+        nt_store(A.s.scales_raw + j, make_float4(raw[0], raw[1], raw[2], R.w));
         float *dst = reinterpret_cast<float *>(A.g2 + j);
         dst[0] = s[0]; dst[1] = s[1]; dst[2] = s[2];
     }
@@ -137,8 +137,8 @@ __global__ __launch_bounds__(256) void k_adam_scene(const SasAdam A)
             live[b] = p < sh_planes && SAS_IN(o, (long long)A.planes * A.n_pad, 903) && SAS_IN(base + cnt - 1, A.coeff_floats, 904);
             if (!live[b]) continue;
             C[b] = A.col[o];
-            M[b] = nt_load(A.sh_m + o);
-            V[b] = nt_load(A.sh_v + o);
+            M[b] = nt_load(A.s.sh_m + o);
+            V[b] = nt_load(A.s.sh_v + o);
             load_sh_grad(A, gs, base, cnt, g[b]);
         }
 #pragma unroll
@@ -153,8 +153,8 @@ __global__ __launch_bounds__(256) void k_adam_scene(const SasAdam A)
                 const float lr = base + k < 3 ? A.lr_sh_dc : A.lr_sh_rest;
                 if (k < cnt && lr != 0.0f) adam_elem(A, g[b][k], lr, m[k], v[k], c[k]);
             }
-            nt_store(A.sh_m + o, make_float4(m[0], m[1], m[2], m[3]));
-            nt_store(A.sh_v + o, make_float4(v[0], v[1], v[2], v[3]));
+            nt_store(A.s.sh_m + o, make_float4(m[0], m[1], m[2], m[3]));
+            nt_store(A.s.sh_v + o, make_float4(v[0], v[1], v[2], v[3]));
             if (cnt == 4) {
                 A.col[o] = make_float4(c[0], c[1], c[2], c[3]);
             } else {   // the last plane of a block that is no multiple of four floats: its zero padding is not stored
@@ -171,15 +171,11 @@ __global__ __launch_bounds__(256) void k_adam_init(long long n, const float4 *g0
     if (j >= n) return;
     if (opac) {
         const float o = g0[j].w;
-        opac[j] = make_float4(0.0f, 0.0f, (o > 0.0f && o < 1.0f) ? logf(o / (1.0f - o)) : NAN, 0.0f);
+        opac[j] = make_float4(0.0f, 0.0f, raw_opacity(o), 0.0f);
     }
     if (scales_raw) {
         const float4 G = g2[j];
-        const float s[3] = {G.x, G.y, G.z};
-        float r[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) r[k] = (s[k] > 0.0f && s[k] < INFINITY) ? logf(s[k]) : NAN;
-        scales_raw[j] = make_float4(r[0], r[1], r[2], 0.0f);
+        scales_raw[j] = make_float4(raw_scale(G.x), raw_scale(G.y), raw_scale(G.z), 0.0f);
     }
 }
 
@@ -217,10 +213,10 @@ __global__ __launch_bounds__(256) void k_scene_gather(const SasGather Q)
 
 SAS_BOUNDS_ACCESSOR(sas_debug_bounds_fit)
 
-void sas_launch_adam_init(hipStream_t st, int64_t n, const float4 *g0, const float4 *g2, float4 *opac, float4 *scales_raw)
+void sas_launch_adam_init(hipStream_t st, int64_t n, const float4 *g0, const float4 *g2, const SasAdamState &fresh)
 {
-    if (n <= 0 || (!opac && !scales_raw)) return;
-    hipLaunchKernelGGL(k_adam_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n, g0, g2, opac, scales_raw);
+    if (n <= 0 || (!fresh.opac && !fresh.scales_raw)) return;
+    hipLaunchKernelGGL(k_adam_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n, g0, g2, fresh.opac, fresh.scales_raw);
 }
 
 void sas_launch_adam_scene(hipStream_t st, const SasAdam &a)

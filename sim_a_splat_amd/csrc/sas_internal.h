@@ -476,6 +476,20 @@ struct SasFuse {
 };
 void sas_launch_fuse(hipStream_t st, const SasFuse &q);
 
+// Floats of a Gaussian's coefficient block (sh_degree < 0: a plain colour) and the colour planes (float4 per Gaussian) that hold them.
+static inline int sas_coeff_floats(int sh_degree) { return sh_degree < 0 ? 3 : 3 * (sh_degree + 1) * (sh_degree + 1); }
+static inline int sas_colour_planes(int sh_degree) { return (sas_coeff_floats(sh_degree) + 3) / 4; }
+
+// The optimiser state the context keeps for the resident scene, in slot order: the one list of its buffers, on the host (Adam in sas_api.cpp)
+// and in the kernels' arguments.  A group that has no state has nullptr.
+struct SasAdamState {
+    float4 *means_m, *means_v;     // [n_pad] (x, y, z, -) first and second moments
+    float4 *opac;                  // [n_pad] (m, v, logit(opacity), -)
+    float4 *quats_m, *quats_v;     // [n_pad]
+    float4 *scales_m, *scales_v, *scales_raw;   // [n_pad] (x, y, z, -); raw = log(scale)
+    float4 *sh_m, *sh_v;           // [planes][n_pad], laid out as col
+};
+
 // Optimiser step (sas_scene_adam_step; DESIGN.md 3, "Optimiser step").  k_adam_scene takes the whole call by value: the planes of the resident
 // scene (written in place), the caller's gradients, and the state the context keeps in slot order.  A group whose gradient is nullptr is
 // neither read nor written, and its state pointers may be nullptr.
@@ -485,11 +499,7 @@ struct SasAdam {
     long long n, n_pad;
     int coeff_floats, planes;      // floats of a Gaussian's coefficient block, colour planes
     const float *d_means, *d_opac, *d_sh, *d_quats, *d_scales;   // gradients in the caller's order (device), nullptr: not stepped
-    float4 *means_m, *means_v;     // [n_pad] (x, y, z, -) first and second moments
-    float4 *opac;                  // [n_pad] (m, v, logit(opacity), -)
-    float4 *quats_m, *quats_v;     // [n_pad]
-    float4 *scales_m, *scales_v, *scales_raw;   // [n_pad] (x, y, z, -); raw = log(scale)
-    float4 *sh_m, *sh_v;           // [planes][n_pad], laid out as col
+    SasAdamState s;                // the state of the groups that are stepped
     float lr_means, lr_opac, lr_sh_dc, lr_sh_rest, lr_quats, lr_scales;
     float beta1, beta2, omb1, omb2;   // omb = 1 - beta (float32)
     float bc1, bc2;                   // 1 - beta^step (float64 on the host, rounded once)
@@ -498,8 +508,8 @@ struct SasAdam {
     int sh_aligned;                   // coeff_floats % 4 == 0 and d_sh 16-byte aligned: the coefficient gradients load as float4
 };
 void sas_launch_adam_scene(hipStream_t st, const SasAdam &a);
-// opac / scales_raw (either may be nullptr) <- (0, 0, logit(g0.w), 0) / (log(g2.xyz), 0); NaN where the value is outside the domain
-void sas_launch_adam_init(hipStream_t st, int64_t n, const float4 *g0, const float4 *g2, float4 *opac, float4 *scales_raw);
+// fresh.opac / fresh.scales_raw (either may be nullptr) <- (0, 0, logit(g0.w), 0) / (log(g2.xyz), 0); NaN where the value is outside the domain
+void sas_launch_adam_init(hipStream_t st, int64_t n, const float4 *g0, const float4 *g2, const SasAdamState &fresh);
 // sas_scene_read: the inverse of sas_launch_relayout.  Every output is a device array in the caller's order, or nullptr.
 struct SasGather {
     const float4 *g0, *g1, *g2, *col;
@@ -600,8 +610,7 @@ struct SasDensityState {
     const float4 *g0_new, *g2_new;
     long long n_new, n_survivors, n_old, n_pad_old, n_pad_new;
     int planes;
-    const float4 *old_means_m, *old_means_v, *old_opac, *old_quats_m, *old_quats_v, *old_scales_m, *old_scales_v, *old_scales_raw, *old_sh_m, *old_sh_v;
-    float4 *means_m, *means_v, *opac, *quats_m, *quats_v, *scales_m, *scales_v, *scales_raw, *sh_m, *sh_v;
+    SasAdamState old_, new_;   // (old_ is only read)
 };
 void sas_launch_density_state(hipStream_t st, const SasDensityState &q);
 // opacity <- min(opacity, cap) in g0; opac (nullptr: no state) <- (0, 0, logit(cap), -) where it changed

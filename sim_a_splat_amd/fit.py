@@ -120,30 +120,35 @@ def _check_loss(who: str, loss: Optional[str], loss_and_grad: Optional[Callable]
         raise ValueError(f"{who}: lambda_dssim {lambda_dssim} outside [0, 1]")
 
 
+def _pack_views(who: str, viewmats, Ks, images, masks) -> Tuple[np.ndarray, np.ndarray]:
+    """``viewmats [C,4,4]`` and ``Ks [C,3,3]`` (arrays or tensors) as float32 host arrays, once the counts of views, images and masks agree."""
+    V = np.asarray(viewmats.detach().cpu() if isinstance(viewmats, torch.Tensor) else viewmats, dtype=np.float32).reshape(-1, 4, 4)
+    K = np.asarray(Ks.detach().cpu() if isinstance(Ks, torch.Tensor) else Ks, dtype=np.float32).reshape(-1, 3, 3)
+    C = V.shape[0]
+    if K.shape[0] != C or len(images) != C or (masks is not None and len(masks) != C):
+        raise ValueError(f"{who}: {C} views, {K.shape[0]} Ks, {len(images)} images" + ("" if masks is None else f", {len(masks)} masks"))
+    return V, K
+
+
 def mean_loss(r, viewmats, Ks, W: int, H: int, images, masks=None, background: Sequence[float] = (0.0, 0.0, 0.0),
               loss_and_grad: Optional[Callable] = None, loss: Optional[str] = None, lambda_dssim: float = 0.2) -> float:
     """The loss ``fit_scene`` descends, averaged over ALL the views, for the scene as it stands in ``r`` (or a stand-in)."""
     _check_loss("mean_loss", loss, loss_and_grad, lambda_dssim)
-    if loss is not None:
-        bg = tuple(float(v) for v in background)
-        V = np.asarray(viewmats, dtype=np.float32).reshape(-1, 4, 4)
-        K = np.asarray(Ks, dtype=np.float32).reshape(-1, 3, 3)
-        vals = []
-        for v in range(V.shape[0]):
-            rgb = r.render(V[v], K[v], W, H, bg)["rgb"]
-            vals.append(r.photometric_loss(rgb, torch.as_tensor(images[v]), mask=None if masks is None else torch.as_tensor(masks[v]),
-                                           lambda_dssim=lambda_dssim, want_grad=False)["loss"].detach().reshape(()))
-        return float(torch.stack(vals).mean()) if vals else 0.0
     lg = l1_loss_and_grad if loss_and_grad is None else loss_and_grad
     bg = tuple(float(v) for v in background)
-    V = np.asarray(viewmats, dtype=np.float32).reshape(-1, 4, 4)
-    K = np.asarray(Ks, dtype=np.float32).reshape(-1, 3, 3)
-    total = 0.0
+    V, K = _pack_views("mean_loss", viewmats, Ks, images, masks)
+    vals = []
     for v in range(V.shape[0]):
         rgb = r.render(V[v], K[v], W, H, bg)["rgb"]
-        mask = None if masks is None else torch.as_tensor(masks[v]).to(rgb.device)
-        total += float(torch.as_tensor(lg(rgb, torch.as_tensor(images[v]).to(device=rgb.device, dtype=rgb.dtype).reshape(rgb.shape), mask)[0]))
-    return total / max(V.shape[0], 1)
+        if loss is not None:
+            vals.append(r.photometric_loss(rgb, torch.as_tensor(images[v]), mask=None if masks is None else torch.as_tensor(masks[v]),
+                                           lambda_dssim=lambda_dssim, want_grad=False)["loss"].detach().reshape(()))
+        else:
+            mask = None if masks is None else torch.as_tensor(masks[v]).to(rgb.device)
+            vals.append(float(torch.as_tensor(lg(rgb, torch.as_tensor(images[v]).to(device=rgb.device, dtype=rgb.dtype).reshape(rgb.shape), mask)[0])))
+    if not vals:
+        return 0.0
+    return float(torch.stack(vals).mean()) if loss is not None else sum(vals) / len(vals)
 
 
 def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequence[str] = ("colors", "opacities"),
@@ -180,11 +185,8 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
     if bad or not what:
         raise ValueError(f"fit_scene: what must name some of {_WHAT}, got {what}")
     rates = dict(DEFAULT_LRS, **(lrs or {}))
-    V = np.asarray(viewmats.detach().cpu() if isinstance(viewmats, torch.Tensor) else viewmats, dtype=np.float32).reshape(-1, 4, 4)
-    K = np.asarray(Ks.detach().cpu() if isinstance(Ks, torch.Tensor) else Ks, dtype=np.float32).reshape(-1, 3, 3)
+    V, K = _pack_views("fit_scene", viewmats, Ks, images, masks)
     C = V.shape[0]
-    if K.shape[0] != C or len(images) != C or (masks is not None and len(masks) != C):
-        raise ValueError(f"fit_scene: {C} views, {K.shape[0]} Ks, {len(images)} images" + ("" if masks is None else f", {len(masks)} masks"))
     per = int(views_per_step)
     if not 1 <= per <= C:
         raise ValueError(f"fit_scene: views_per_step {per} out of [1, {C}]")
@@ -249,10 +251,7 @@ def image_metrics(r, viewmats, Ks, W: int, H: int, images, masks=None, backgroun
     [C,H,W,3]`` over ``masks [C,H,W]``: float32 host tensors ``[C]``.  Each view is one frame and one terms-only
     ``Rasterizer.photometric_loss``; the terms of all the views are read back once, at the end."""
     bg = tuple(float(v) for v in background)
-    V = np.asarray(viewmats.detach().cpu() if isinstance(viewmats, torch.Tensor) else viewmats, dtype=np.float32).reshape(-1, 4, 4)
-    K = np.asarray(Ks.detach().cpu() if isinstance(Ks, torch.Tensor) else Ks, dtype=np.float32).reshape(-1, 3, 3)
-    if K.shape[0] != V.shape[0] or len(images) != V.shape[0] or (masks is not None and len(masks) != V.shape[0]):
-        raise ValueError(f"image_metrics: {V.shape[0]} views, {K.shape[0]} Ks, {len(images)} images" + ("" if masks is None else f", {len(masks)} masks"))
+    V, K = _pack_views("image_metrics", viewmats, Ks, images, masks)
     rows = []
     for v in range(V.shape[0]):
         rgb = r.render(V[v], K[v], W, H, bg)["rgb"]

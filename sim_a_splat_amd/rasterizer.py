@@ -885,11 +885,16 @@ class Rasterizer:
         self._in_flight(True)
         return res
 
+    def _is_mine(self, t, dtype: torch.dtype, shape: Tuple[int, ...], same_count: bool = False) -> bool:
+        """Is ``t`` a contiguous tensor of ``dtype`` and ``shape`` (``same_count``: of as many elements) on this context's device?"""
+        return isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.device == self.device and \
+            (t.numel() == int(np.prod(shape)) if same_count else tuple(t.shape) == tuple(shape))
+
     def _lift_buffer(self, t: Optional[torch.Tensor], shape: Tuple[int, ...], name: str) -> torch.Tensor:
         """A sum buffer of ``lift_labels``: the caller's (accumulated into), validated, or a zeroed one."""
         if t is None:
             return torch.zeros(shape, dtype=torch.int64, device=self.device)
-        if not isinstance(t, torch.Tensor) or t.shape != shape or t.dtype != torch.int64 or not t.is_contiguous() or t.device != self.device:
+        if not self._is_mine(t, torch.int64, shape):
             raise ValueError(f"{name} must be a contiguous int64 tensor {shape} on {self.device}")
         return t
 
@@ -1027,9 +1032,9 @@ class Rasterizer:
         if screen_space:
             shapes = dict(means2d=(n, 2), conics=(n, 3), opacities=(n,), colors=(n, 3), depths=(n,))
         else:
-            kk = (self.sh_degree + 1) ** 2 if self.sh_degree >= 0 else 1
-            shapes = dict(means=(n, 3), opacities=(n,), colors=(n, kk, 3), viewmat=(3, 4))
-            shapes.update(dict(quats=(n, 4), scales=(n, 3)) if self.covariance_form == "quats" else dict(covariances=(n, 6)))
+            scene = self._scene_shapes()
+            shapes = {k: scene.pop(k) for k in ("means", "opacities", "colors")}
+            shapes.update(viewmat=(3, 4), **scene)   # (the keys keep the order they always had: it shows in results and messages)
         if want is not None:
             want = tuple(want)
             unknown = [k for k in want if k not in shapes]
@@ -1041,7 +1046,7 @@ class Rasterizer:
             t = out.get(name) if out else None
             if t is None:
                 t = torch.zeros(shape, dtype=torch.float32, device=self.device)
-            elif not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+            elif not self._is_mine(t, torch.float32, shape):
                 raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor {shape} on {self.device}")
             res[name] = t
         ptr = lambda t: t.data_ptr() if t is not None else None
@@ -1094,8 +1099,7 @@ class Rasterizer:
                 continue
             if k not in shapes:
                 raise ValueError(f"adam_step: the scene was uploaded as covariances, which are not variables: drop grads[{k!r}]")
-            if not isinstance(t, torch.Tensor) or t.numel() != int(np.prod(shapes[k])) or t.dtype != torch.float32 or not t.is_contiguous() \
-                    or t.device != self.device:
+            if not self._is_mine(t, torch.float32, shapes[k], same_count=True):
                 raise ValueError(f"grads[{k!r}] must be a contiguous float32 tensor {shapes[k]} on {self.device}")
             ptrs[k] = t.data_ptr()
         cfg = _capi.AdamConfig(*[float(lrs.get(k, 0.0)) for k in self._ADAM_LRS], float(betas[0]), float(betas[1]), float(eps), int(step),
@@ -1123,8 +1127,7 @@ class Rasterizer:
 
     def _density_stat(self, stats, k: str) -> torch.Tensor:
         t = stats.get(k)
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (self.n,) or t.dtype != self._DENSITY_STATS[k] or not t.is_contiguous() \
-                or t.device != self.device:
+        if not self._is_mine(t, self._DENSITY_STATS[k], (self.n,)):
             raise ValueError(f"stats[{k!r}] must be a contiguous {self._DENSITY_STATS[k]} tensor ({self.n},) on {self.device}: new_density_stats() makes them")
         return t
 
@@ -1138,8 +1141,7 @@ class Rasterizer:
         mr = self._density_stat(stats, "max_radius") if stats.get("max_radius") is not None else None
         pm = None
         if d_means2d is not None:
-            if not isinstance(d_means2d, torch.Tensor) or tuple(d_means2d.shape) != (self.n, 2) or d_means2d.dtype != torch.float32 \
-                    or not d_means2d.is_contiguous() or d_means2d.device != self.device:
+            if not self._is_mine(d_means2d, torch.float32, (self.n, 2)):
                 raise ValueError(f"d_means2d must be a contiguous float32 tensor ({self.n}, 2) on {self.device}")
             pm = d_means2d.data_ptr()
         rc = self._L.sas_density_accumulate(self._ctx, int(width), int(height), pm, gs.data_ptr(), cn.data_ptr(),

@@ -1,5 +1,6 @@
 """GPU: the host layer around the frames -- which stores a context holds after each upload call ("What forgets
-what"), that contexts give back what they took, and the triangles' feature rows through the one store body.
+what"), that contexts give back what they took, the triangles' feature rows through the one store body, and what each call that
+changes the resident scene invalidates ("What a change of the resident scene invalidates").
 
 Shapes: the 64-Gaussian twin fixture in 3 splat groups, 2 triangles behind the splats, 9 channels (two chunks), 32x32 frames.
 """
@@ -266,3 +267,124 @@ def test_poisoned_mesh_features_render_as_their_finite_mapping(rasterizer):
     bare = a[alpha == 0]                                   # no splat in front: the triangle's row as it was stored
     rows = [(bare.view(np.uint32) == mapped[t].view(np.uint32)).all(-1) for t in (0, 1)]
     assert rows[0].any() and rows[1].any() and (rows[0] | rows[1]).all(), (len(bare), int(rows[0].sum()), int(rows[1].sum()))
+
+
+# ---- 4. what a change of the resident scene invalidates ----------------------------------------------------------------------
+# Start: scene and features uploaded, the last frame a render_backward frame (its sums in the context).  One call is applied, then
+# the context is asked, in this order (the first three change nothing, the last renders a frame): sas_read_projection,
+# sas_read_tile_lists, sas_density_accumulate without d_means2d (the scratch path), sas_render_features.  INVALIDATES[call] = their
+# (status, words of sas_last_error), written from the parent commit's sas_api.cpp:
+#   a step that moves something and an opacity reset change VALUES: the last frame and its backward status go, the stores stay;
+#   densify changes COUNT AND ORDER: the features go as well;  upload changes EVERYTHING: every store beside the scene goes;
+#   a step whose rates are all zero returns before it touches anything;  adam_reset, density_accumulate and photometric_loss do not
+#   touch the scene.
+OK = (0, "")
+NO_FRAME = (-3, "no frame rendered")
+NO_BACKWARD = (-3, "no backward frame since the last upload, optimiser step, densify or opacity reset")
+NO_FEATURES = (-1, "no features set for this scene")
+INVALIDATES = {
+    "adam_step":          (NO_FRAME, NO_FRAME, NO_BACKWARD, OK),
+    "adam_step_zero":     (OK, OK, OK, OK),
+    "adam_reset":         (OK, OK, OK, OK),
+    "density_accumulate": (OK, OK, OK, OK),
+    "reset_opacity":      (NO_FRAME, NO_FRAME, NO_BACKWARD, OK),
+    "densify_off":        (NO_FRAME, NO_FRAME, NO_BACKWARD, NO_FEATURES),
+    "upload":             (NO_FRAME, NO_FRAME, NO_BACKWARD, NO_FEATURES),
+    "photometric_loss":   (OK, OK, OK, OK),
+}
+
+
+def _backward_start(r):
+    """The section's start on ``r``; returns the backward frame's gradients (what adam_step takes)."""
+    s = _scene()
+    assert _py_call(r, "upload") == 0 and _py_call(r, "features") == 0
+    return r.render_backward(s["V"], s["K"], W, H, g_rgb=np.ones((H, W, 3), np.float32))
+
+
+def _stats(r, grad=0.0, count=0):
+    return dict(grad_sum=torch.full((r.n,), grad, device=r.device), count=torch.full((r.n,), count, dtype=torch.int32, device=r.device))
+
+
+def _change(r, call, grads):
+    if call == "adam_step":
+        r.adam_step(grads, dict(opacities=5e-2, sh_dc=1e-2, sh_rest=1e-2, scales=5e-3), 1)
+    elif call == "adam_step_zero":
+        r.adam_step(grads, {}, 1)
+    elif call == "adam_reset":
+        r.adam_reset()
+    elif call == "density_accumulate":
+        r.density_accumulate(W, H, _stats(r))
+    elif call == "reset_opacity":
+        r.reset_opacity(0.01)
+    elif call == "densify_off":
+        r.densify(_stats(r), grow=False, prune_opacity_on=False, prune_scale_on=False)
+    elif call == "densify":
+        return r.densify(_stats(r, 1.0, 1), prune_opacity_on=False, prune_scale_on=False, seed=7)
+    elif call == "upload":
+        assert _py_call(r, "upload") == 0
+    else:
+        assert call == "photometric_loss", call
+        rgb = torch.rand((H, W, 3), generator=torch.Generator().manual_seed(4))
+        r.photometric_loss(rgb, 1.0 - rgb)
+
+
+def _asked(L, r):
+    """The four answers of INVALIDATES as the library gives them now."""
+    s = _scene()
+    ctx = r._ctx
+    off, ids = np.zeros(257, np.int32), np.zeros(1 << 16, np.int32)   # (16 tiles of 8 pixels at the most; 64 Gaussians reach far fewer)
+    st = _stats(r)
+    feat = torch.empty((H, W, C), device=r.device)
+    asks = (lambda: L.sas_read_projection(ctx, None, None, None, None, None),
+            lambda: L.sas_read_tile_lists(ctx, _p(off), _p(ids), ids.size),
+            lambda: L.sas_density_accumulate(ctx, W, H, None, st["grad_sum"].data_ptr(), st["count"].data_ptr(), None, r._stream()),
+            lambda: L.sas_render_features(ctx, _p(s["V"]), _p(s["K"]), W, H, None, None, 0, None, None, None, feat.data_ptr(), None))
+    got = []
+    for ask in asks:
+        rc = ask()
+        got.append((rc, L.sas_last_error(ctx).decode() if rc else ""))
+    torch.cuda.synchronize()
+    return got
+
+
+def test_what_a_change_of_the_resident_scene_invalidates():
+    L = _capi.lib()
+    r = Rasterizer(0)                                      # (every start begins with an upload, which forgets everything)
+    try:
+        for call, want in INVALIDATES.items():
+            _change(r, call, _backward_start(r))
+            got = _asked(L, r)
+            for (rc, msg), (status, words) in zip(got, want):
+                assert rc == status and words in msg, (call, got)
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("call", ["adam_step", "reset_opacity", "densify"])
+def test_a_frame_straight_behind_a_change_shows_the_changed_scene(call):
+    """The order promise of the three calls that change values: a render enqueued straight behind the call, with no wait in between,
+    is the frame of the changed scene -- bit for bit the frame of a fresh context uploaded read_scene's arrays.  (The step moves no
+    mean and densify's storage order is the upload's, so both contexts hold the same planes.)  tests/test_gpu_u_fit.py::
+    test_planes_stay_well_formed and tests/test_gpu_w_densify.py hold the same equality behind a read_scene, which waits."""
+    s = _scene()
+    outs = ("rgb", "alpha", "depth")
+    frame = lambda q: {k: v.cpu().numpy() for k, v in q.render(s["V"], s["K"], W, H, s["bg"], want=outs).items()}
+    r, fresh = Rasterizer(0), Rasterizer(0)
+    try:
+        assert _py_call(r, "upload") == 0
+        before = frame(r)
+        grads = _backward_start(r)
+        torch.cuda.synchronize()
+        res = _change(r, call, grads)
+        a = frame(r)
+        x = r.read_scene()
+        gid = s["gid"] if res is None else s["gid"][res["parents"].cpu().numpy()]
+        assert r.n == (64 if res is None else res["n"]) and (res is None or res["n"] > 64)
+        fresh.upload(x["means"], x["opacities"], x["colors"], quats=x["quats"], scales=x["scales"], sh_degree=3, group_id=gid, n_groups=3)
+        b = frame(fresh)
+        for k in outs:
+            assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), (call, k)
+        assert not np.array_equal(a["rgb"], before["rgb"]), call
+    finally:
+        r.close()
+        fresh.close()
