@@ -541,8 +541,8 @@ int sas_lift_features(sas_ctx *ctx, int n_views, const float *viewmats, const fl
  * Decisions are constants of the derivative: an entry skipped for alpha < 1/255 or sigma < 0, the entry that trips
  * T (1 - alpha) <= 1e-4 and everything behind it, and culled Gaussians receive nothing; a clamped alpha (o e^-sigma > 0.999) passes
  * nothing to o, the conic or the mean.  The sums over pixels are float32 atomic additions: they vary in their last bits from run
- * to run (the lift calls' integer exactness is NOT promised here).  Gradients with respect to K, to the group poses and to mesh
- * vertices are not computed.
+ * to run (the lift calls' integer exactness is NOT promised here).  Gradients with respect to K and to mesh vertices are not
+ * computed; those of the group poses come from sas_render_backward_poses.
  *   flags   SAS_FAST_EXP and SAS_TIMING only.  Blocking, one view per call; several views sum by calling again on the same buffers.
  * The frame is a SAS_FULL_SORT frame like a lift frame's: frames in flight are completed first, a frame that outgrew its key buffer
  * adds nothing until it is rendered again, the context's current group poses apply.  SAS_ERR_NO_SCENE before an upload;
@@ -563,13 +563,32 @@ int sas_render_backward_screen(sas_ctx *ctx, const float *viewmat, const float *
  *   six taken as one variable), whichever form the scene was uploaded in; asking for the other form is SAS_ERR_INVALID,
  *   d_viewmat [3,4] row-major rows [R | t] of the view matrix, its twelve entries taken as independent, summed over the Gaussians
  *   in a fixed order (no atomics): reproducible given the screen-space sums.
- * float32 DEVICE, each may be NULL, not all.  A culled Gaussian receives exact zeros.  NOT differentiated: K, the group poses
- * themselves, mesh vertices, and every decision (culls, the radius' ceil, the tile rectangle, the compositing thresholds).
+ * float32 DEVICE, each may be NULL, not all.  A culled Gaussian receives exact zeros.  NOT differentiated: K, mesh vertices, joint
+ * angles, and every decision (culls, the radius' ceil, the tile rectangle, the compositing thresholds); the group poses themselves
+ * are differentiated by sas_render_backward_poses, which this call is with n_sel = 0.
  * Everything else is as in sas_render_backward_screen, whose sums this call keeps in scratch of the context.
  */
 int sas_render_backward(sas_ctx *ctx, const float *viewmat, const float *K, int width, int height, unsigned flags,
                         const float *g_rgb, const float *g_alpha, const float *g_depth, float *d_means, float *d_opacities,
                         float *d_sh, float *d_quats, float *d_scales, float *d_cov6, float *d_viewmat, void *stream);
+
+/*
+ * ... and to the poses of up to SAS_MAX_POSE_GRAD_GROUPS splat groups: sel [n_sel] uint8 HOST names distinct group ids, and the call
+ * ADDS to d_group_poses [n_sel,12] float32 DEVICE, in sel's order, the gradient with respect to the rows [R | t] of each named group's
+ * current pose (sas_set_group_poses / sas_set_link_poses), its twelve entries taken as independent, exactly as d_viewmat treats the
+ * view matrix:  dL/dt = sum_i gm_i,  dL/dR = sum_i gm_i m0_i^T + 2 GSw_i R S0_i  over the group's Gaussians, gm the gradient of the
+ * posed mean (the SH direction term included), GSw that of the posed covariance, m0 and S0 the canonical mean and covariance.  A culled
+ * Gaussian adds exact zeros, a group whose Gaussians are all culled gets a zero row, groups that are not named are not reduced.  The
+ * sums run in a fixed order without atomics: reproducible given the screen-space sums.  d_group_poses alone, every other output NULL,
+ * is a valid call; more than 32 groups: call again with the next 32.  Everything else is sas_render_backward.  SAS_ERR_INVALID also
+ * for n_sel outside 0..SAS_MAX_POSE_GRAD_GROUPS, n_sel > 0 with sel or d_group_poses NULL, a duplicate id, an id >= n_groups, and a
+ * scene uploaded without group ids.  After any error the context stays usable.
+ */
+#define SAS_MAX_POSE_GRAD_GROUPS 32
+int sas_render_backward_poses(sas_ctx *ctx, const float *viewmat, const float *K, int width, int height, unsigned flags,
+                              const float *g_rgb, const float *g_alpha, const float *g_depth, float *d_means, float *d_opacities,
+                              float *d_sh, float *d_quats, float *d_scales, float *d_cov6, float *d_viewmat,
+                              int n_sel, const uint8_t *sel /* host */, float *d_group_poses /* device [n_sel,12] */, void *stream);
 
 /*
  * Optimiser step on the resident scene ("Optimiser step"): one fused Adam update, in place, of the planes the frames read.

@@ -8,8 +8,9 @@ their gradients have somewhere to go -- after an optimiser step of the caller's 
 ``Rasterizer.adam_step``: a fused Adam step on the resident scene from the gradients ``Rasterizer.render_backward`` returns
 (``fit.fit_scene`` is the loop).  The view matrix is an argument of every call and needs no upload.
 
-Not differentiated: K, the group poses, meshes (a scene with meshes is refused), and every decision of the renderer (culls, clamps,
-the alpha and transmittance thresholds), which are constants of the derivative.  The per-Gaussian sums are float atomics: gradients
+The poses of the splat groups are a variable too (``group_poses=``, up to 32 groups per frame).  Not differentiated: K, meshes (a
+scene with meshes is refused), joint angles, and every decision of the renderer (culls, clamps, the alpha and transmittance
+thresholds), which are constants of the derivative.  The per-Gaussian sums are float atomics: gradients
 vary in their last bits from run to run.
 """
 from __future__ import annotations
@@ -46,35 +47,46 @@ def prechain(rgb: torch.Tensor, alpha: torch.Tensor, depth: torch.Tensor, backgr
 
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, r, viewmat, K, W, H, background, keys, *tensors):
+    def forward(ctx, r, viewmat, K, W, H, background, keys, pose_groups, group_poses, *tensors):
         V = np.eye(4, dtype=np.float32)
         V[:viewmat.shape[0]] = viewmat.detach().cpu().numpy().astype(np.float32)
+        if group_poses is not None:   # the frame is rendered under these poses, and they stay set
+            r.set_group_poses(group_poses.detach().to(torch.float32).cpu().numpy().reshape(-1, 12))
         out = r.render(V, K, W, H, background)
         rgb, alpha, depth = out["rgb"].clone(), out["alpha"].clone(), out["depth"].clone()
         ctx.save_for_backward(rgb, alpha, depth)
+        pmeta = None if group_poses is None else (group_poses.device, group_poses.dtype, tuple(group_poses.shape))
         ctx.call = (r, V, K, W, H, background, keys, tuple(viewmat.shape), viewmat.device, viewmat.dtype,
-                    [(t.device, t.dtype, tuple(t.shape)) for t in tensors])
+                    [(t.device, t.dtype, tuple(t.shape)) for t in tensors], pose_groups, pmeta)
         return rgb, alpha, depth
 
     @staticmethod
     def backward(ctx, g_rgb, g_alpha, g_depth):
         rgb, alpha, depth = ctx.saved_tensors
-        r, V, K, W, H, background, keys, vshape, vdev, vdt, metas = ctx.call
+        r, V, K, W, H, background, keys, vshape, vdev, vdt, metas, pose_groups, pmeta = ctx.call
         g_acc, g_a, g_z = prechain(rgb, alpha, depth, background, g_rgb, g_alpha, g_depth)
         # only what some input needs: the projection's backward neither reads nor writes the rest
-        needs = ctx.needs_input_grad[7:]
-        want = (("viewmat",) if ctx.needs_input_grad[1] else ()) + tuple(k for k, need in zip(keys, needs) if need)
+        needs = ctx.needs_input_grad[9:]
+        need_poses = pmeta is not None and ctx.needs_input_grad[8]
+        want = (("viewmat",) if ctx.needs_input_grad[1] else ()) + tuple(k for k, need in zip(keys, needs) if need) + \
+            (("group_poses",) if need_poses else ())
         if not want:
-            return (None,) * (7 + len(keys))
-        res = r.render_backward(V, K, W, H, g_acc, g_a, g_z, want=want)
+            return (None,) * (9 + len(keys))
+        res = r.render_backward(V, K, W, H, g_acc, g_a, g_z, want=want, pose_groups=pose_groups if need_poses else None)
         grads = [None]
         if ctx.needs_input_grad[1]:
             gv = torch.zeros(vshape, dtype=torch.float32, device=res["viewmat"].device)
             gv[:3] = res["viewmat"]
             grads = [gv.to(device=vdev, dtype=vdt)]
+        gp = None
+        if need_poses:   # the rows of pose_groups are filled, the rest are zero
+            pdev, pdt, pshape = pmeta
+            full = torch.zeros((pshape[0], 12), dtype=torch.float32, device=res["group_poses"].device)
+            full[torch.as_tensor(list(pose_groups), dtype=torch.long, device=full.device)] = res["group_poses"].reshape(-1, 12)
+            gp = full.reshape(pshape).to(device=pdev, dtype=pdt)
         for k, (dev, dt, shape), need in zip(keys, metas, needs):
             grads.append(res[k].reshape(shape).to(device=dev, dtype=dt) if need else None)
-        return (None, grads[0], None, None, None, None, None, *grads[1:])
+        return (None, grads[0], None, None, None, None, None, None, gp, *grads[1:])
 
 
 class _PhotometricLoss(torch.autograd.Function):
@@ -102,12 +114,18 @@ def photometric_loss(r, rgb: torch.Tensor, target, mask=None, lambda_dssim: floa
 
 
 def render_differentiable(r, viewmat: torch.Tensor, K, width: int, height: int, params: Optional[Dict[str, torch.Tensor]] = None,
-                          background: Optional[Sequence[float]] = None) -> Dict[str, torch.Tensor]:
+                          background: Optional[Sequence[float]] = None, group_poses: Optional[torch.Tensor] = None,
+                          pose_groups: Optional[Sequence[int]] = None) -> Dict[str, torch.Tensor]:
     """One frame of rasterizer ``r`` -- ``rgb [H,W,3]``, ``alpha [H,W,1]``, ``depth [H,W,1]`` on its device -- through which gradients
     flow to ``viewmat`` (``[4,4]`` or ``[3,4]``, world to camera; its twelve upper entries are independent variables) and to those
     tensors of ``params`` that require grad.  ``params`` maps ``means``, ``opacities``, ``colors``, ``quats``, ``scales`` or
     ``covariances`` (``[N,6]``) to THE ARRAYS LAST UPLOADED to ``r``: the frame is rendered from the uploaded copy, not from these
-    tensors, so upload again after changing them.  ``K`` is a constant."""
+    tensors, so upload again after changing them.  ``K`` is a constant.
+
+    ``group_poses``: ``[G,3,4]`` or ``[G,12]``, rows ``[R | t]`` of ALL the scene's splat groups.  Unlike ``params`` it is a value: its
+    detached float32 copy is set with ``set_group_poses`` before the frame (and stays set), and its gradient comes back in its shape,
+    device and dtype, twelve independent entries per group, the rows of ``pose_groups`` filled and the rest zero.  ``pose_groups``
+    defaults to all groups when there are at most 32 of them; with more it is required (32 ids at the most per frame)."""
     bg = (0.0, 0.0, 0.0) if background is None else tuple(float(v) for v in background)
     params = params or {}
     unknown = [k for k in params if k not in PARAM_KEYS]
@@ -115,5 +133,17 @@ def render_differentiable(r, viewmat: torch.Tensor, K, width: int, height: int, 
         raise ValueError(f"render_differentiable: unknown params {unknown}; expected some of {PARAM_KEYS}")
     keys = tuple(k for k in PARAM_KEYS if k in params)
     Kc = np.ascontiguousarray(K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K), dtype=np.float32)
-    rgb, alpha, depth = _Render.apply(r, viewmat, Kc, int(width), int(height), bg, keys, *[params[k] for k in keys])
+    sel = None
+    if group_poses is not None:
+        n_groups = int(group_poses.shape[0])
+        if group_poses.numel() != 12 * n_groups or group_poses.dim() not in (2, 3):
+            raise ValueError(f"render_differentiable: group_poses must be [G,3,4] or [G,12], got {tuple(group_poses.shape)}")
+        if pose_groups is None:
+            if n_groups > 32:
+                raise ValueError(f"render_differentiable: {n_groups} groups: name up to 32 of them in pose_groups")
+            pose_groups = range(n_groups)
+        sel = tuple(int(g) for g in pose_groups)
+    elif pose_groups is not None:
+        raise ValueError("render_differentiable: pose_groups without group_poses")
+    rgb, alpha, depth = _Render.apply(r, viewmat, Kc, int(width), int(height), bg, keys, sel, group_poses, *[params[k] for k in keys])
     return dict(rgb=rgb, alpha=alpha, depth=depth)

@@ -76,6 +76,7 @@ struct ViewOut {
     bool grad_chain = false;
     float *chain_means = nullptr, *chain_opacities = nullptr, *chain_sh = nullptr, *chain_quats = nullptr, *chain_scales = nullptr,
           *chain_cov6 = nullptr, *chain_viewmat = nullptr, *chain_partial = nullptr;
+    SasPoseSel chain_poses{};       // sas_render_backward_poses: the selected groups, their scratch rows and what they ADD to (n_sel 0: none)
 };
 
 struct RenderArgs {
@@ -987,7 +988,7 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
                 const SasGradProj Q{a.out.grad_means2d, a.out.grad_conics, a.out.grad_opacities, a.out.grad_colors, a.out.grad_depths,
                                     a.out.chain_means, a.out.chain_opacities, a.out.chain_sh, a.out.chain_quats, a.out.chain_scales,
                                     a.out.chain_cov6, a.out.chain_viewmat ? a.out.chain_partial : nullptr, a.out.chain_viewmat, c->scene.n};
-                sas_launch_grad_project(st, c->scene, P, f, Q);
+                sas_launch_grad_project(st, c->scene, P, f, Q, a.out.chain_poses);
             }
         }
     } else if (nv > 1) {
@@ -2398,34 +2399,71 @@ int sas_render_backward_screen(sas_ctx *c, const float *viewmat, const float *K,
 
 // ... and chained through the view's projection (k_grad_project): the screen-space sums live in the context's scratch, zeroed on the
 // caller's stream in front of the frame.
-int sas_render_backward(sas_ctx *c, const float *viewmat, const float *K, int width, int height, unsigned flags, const float *g_rgb,
-                        const float *g_alpha, const float *g_depth, float *d_means, float *d_opacities, float *d_sh, float *d_quats,
-                        float *d_scales, float *d_cov6, float *d_viewmat, void *stream)
+static int render_backward(sas_ctx *c, const char *who, const float *viewmat, const float *K, int width, int height, unsigned flags,
+                           const float *g_rgb, const float *g_alpha, const float *g_depth, float *d_means, float *d_opacities, float *d_sh,
+                           float *d_quats, float *d_scales, float *d_cov6, float *d_viewmat, int n_sel, const uint8_t *sel,
+                           float *d_group_poses, void *stream)
 {
-    const char *who = "sas_render_backward";
     if (const int rc = check_lift(c, who, flags)) return rc;
     if (!g_rgb && !g_alpha && !g_depth) return fail(c, SAS_ERR_INVALID, "%s: g_rgb, g_alpha and g_depth are all NULL", who);
-    if (!d_means && !d_opacities && !d_sh && !d_quats && !d_scales && !d_cov6 && !d_viewmat)
+    if (n_sel < 0 || n_sel > SAS_MAX_POSE_GRAD_GROUPS)
+        return fail(c, SAS_ERR_INVALID, "%s: n_sel %d out of [0,%d]", who, n_sel, SAS_MAX_POSE_GRAD_GROUPS);
+    if (!d_means && !d_opacities && !d_sh && !d_quats && !d_scales && !d_cov6 && !d_viewmat && !(n_sel > 0 && d_group_poses))
         return fail(c, SAS_ERR_INVALID, "%s: every output is NULL", who);
+    SasPoseSel S{};
+    if (n_sel > 0) {
+        if (!sel || !d_group_poses) return fail(c, SAS_ERR_INVALID, "%s: n_sel %d but sel or d_group_poses is NULL", who, n_sel);
+        if (c->scene.n_groups <= 0) return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded without splat groups: it has no group poses", who);
+        bool seen[256] = {};
+        for (int q = 0; q < n_sel; ++q) {
+            if ((int)sel[q] >= c->scene.n_groups) return fail(c, SAS_ERR_INVALID, "%s: sel[%d]=%d >= n_groups=%d", who, q, (int)sel[q], c->scene.n_groups);
+            if (seen[sel[q]]) return fail(c, SAS_ERR_INVALID, "%s: sel[%d]=%d is a duplicate", who, q, (int)sel[q]);
+            seen[sel[q]] = true;
+            S.ids[q >> 2] |= (unsigned)sel[q] << (8 * (q & 3));
+        }
+        S.n_sel = n_sel;
+        S.d_group_poses = d_group_poses;
+    }
     if (const int rc = check_form(c, who, d_quats || d_scales, d_cov6 != nullptr, "d_")) return rc;
     if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->scene.n, n_wg = (n + 255) / 256;
-    const size_t floats = 10 * n + 12 * n_wg;
-    if (const int rc = ensure(c, c->grad_screen, floats * sizeof(float))) return rc;
+    const size_t floats = 10 * n + 12 * n_wg;   // (zeroed; the pose rows behind them are all written by the kernel)
+    if (const int rc = ensure(c, c->grad_screen, (floats + 12 * n_wg * (size_t)n_sel) * sizeof(float))) return rc;
     float *s = (float *)c->grad_screen.p;
     if (const int rc = complete_all(c)) return rc;   // (nothing in flight reads the scratch)
     HIP_TRY(c, hipMemsetAsync(s, 0, floats * sizeof(float), (hipStream_t)stream));
+    S.partial = n_sel > 0 ? s + floats : nullptr;
     const int rc = lift_views(c, who, 1, viewmat, K, width, height, flags, stream, [&](int) {
         ViewOut o = grad_view(g_rgb, g_alpha, g_depth, s, s + 2 * n, s + 5 * n, s + 6 * n, s + 9 * n);
         o.grad_chain = true;
         o.chain_partial = s + 10 * n;
         o.chain_means = d_means; o.chain_opacities = d_opacities; o.chain_sh = d_sh; o.chain_quats = d_quats; o.chain_scales = d_scales;
         o.chain_cov6 = d_cov6; o.chain_viewmat = d_viewmat;
+        o.chain_poses = S;
         return o;
     });
     if (!rc) c->grad_frame = 2;   // (sas_density_accumulate may read the sums in grad_screen)
     return rc;
+}
+
+int sas_render_backward(sas_ctx *c, const float *viewmat, const float *K, int width, int height, unsigned flags, const float *g_rgb,
+                        const float *g_alpha, const float *g_depth, float *d_means, float *d_opacities, float *d_sh, float *d_quats,
+                        float *d_scales, float *d_cov6, float *d_viewmat, void *stream)
+{
+    return render_backward(c, "sas_render_backward", viewmat, K, width, height, flags, g_rgb, g_alpha, g_depth, d_means, d_opacities, d_sh,
+                           d_quats, d_scales, d_cov6, d_viewmat, 0, nullptr, nullptr, stream);
+}
+
+// ... and to the poses of the selected groups (k_grad_project<true>): one row of scratch per (workgroup, selected group) behind the
+// view-matrix rows.
+int sas_render_backward_poses(sas_ctx *c, const float *viewmat, const float *K, int width, int height, unsigned flags, const float *g_rgb,
+                              const float *g_alpha, const float *g_depth, float *d_means, float *d_opacities, float *d_sh, float *d_quats,
+                              float *d_scales, float *d_cov6, float *d_viewmat, int n_sel, const uint8_t *sel, float *d_group_poses,
+                              void *stream)
+{
+    return render_backward(c, "sas_render_backward_poses", viewmat, K, width, height, flags, g_rgb, g_alpha, g_depth, d_means, d_opacities,
+                           d_sh, d_quats, d_scales, d_cov6, d_viewmat, n_sel, sel, d_group_poses, stream);
 }
 
 // The fused Adam step on the resident planes (k_adam_scene).  Host work: validation, the first-step allocations, one launch, one event.

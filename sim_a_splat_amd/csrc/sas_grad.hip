@@ -14,7 +14,7 @@
 // batch's [256][10] block, so the lanes of a wave-instruction that belong to one entry write neighbouring floats of its rows.  Sizing: DESIGN.md 3.
 // Float atomics: the sums depend on arrival order and vary in their last bits from run to run.
 // Decisions (alpha against 1/255 and 0.999, T (1 - alpha) against 1e-4) are constants of the derivative.  Arithmetic: contract T6's
-// sigma on (dx, dy) and its exponential; gradients of K, of the group poses and of mesh vertices are not computed anywhere.
+// sigma on (dx, dy) and its exponential; gradients of K and of mesh vertices are not computed anywhere.
 #include "sas_device.h"
 
 #pragma clang fp contract(off)
@@ -216,6 +216,10 @@ __global__ __launch_bounds__(256) void k_grad_tiles(SasParams P, SasFrame f, lon
 //                    The view matrix' gradient is summed in a fixed order: butterflies over the wave, the four waves through LDS, one
 //                    row of 12 per workgroup; k_grad_viewmat adds the rows in workgroup order.  One view's pose gradient is therefore
 //                    reproducible given the screen-space gradients (which are float atomic sums).
+//                    <POSES> (sas_render_backward_poses) forms the same kind of sum per selected group for dL/dG, G = [Rg | t] the group's
+//                    pose: dL/dt = gm (the posed mean's gradient), dL/dRg = gm m0^T + 2 GSw Rg S0.  A lane's slot is its group's place in
+//                    the selection; per wave each slot present (a ballot) is summed over its lanes, absent slots are skipped, the waves
+//                    and then the workgroups (k_grad_poses) are added in order: no atomics.  <false> is the kernel without any of it.
 struct Sym3 { float m[3][3]; };
 
 // real SH basis and its derivatives with respect to the unit direction's components taken as independent (gsplat's signs)
@@ -250,13 +254,18 @@ DEV void sh_basis_grad(int deg, float x, float y, float z, float *Bv, float *Bx,
     Bv[15] = -k9 * fC2;      Bx[15] = -k9 * 3.0f * fC1;           By[15] = k9 * 6.0f * x * y;
 }
 
-__global__ __launch_bounds__(256) void k_grad_project(SasScene s, SasCam c, const uint4 *info, const float *poses, SasGradProj B)
+template <bool POSES>
+__global__ __launch_bounds__(256) void k_grad_project(SasScene s, SasCam c, const uint4 *info, const float *poses, SasGradProj B, SasPoseSel S)
 {
     __shared__ float s_part[4][12];
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     float gV[12];   // this lane's share of d_viewmat, rows [R | t]
 #pragma unroll
     for (int k = 0; k < 12; ++k) gV[k] = 0.0f;
+    float gP[12];   // POSES: this lane's dL/dG of its own group, rows [R | t]; slot: the group's place in the selection, or none
+    int slot = -1;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) gP[k] = 0.0f;
     bool live = j < s.n && SAS_IN(j, s.n, 810);
     if (live) {
         const uint4 inf = info[j];
@@ -504,6 +513,64 @@ __global__ __launch_bounds__(256) void k_grad_project(SasScene s, SasCam c, cons
                 o[0] += G0[0][0]; o[1] += 2.0f * G0[0][1]; o[2] += 2.0f * G0[0][2];
                 o[3] += G0[1][1]; o[4] += 2.0f * G0[1][2]; o[5] += G0[2][2];
             }
+            // ---- the group's pose, G's twelve entries taken as independent: t from the posed mean, Rg from the mean and from Sigma3 = Rg S0 Rg^T
+            if constexpr (POSES) {
+                if (hasG)
+                    for (int q = 0; q < S.n_sel; ++q)   // (uniform trip count; the ids are distinct)
+                        if (((S.ids[q >> 2] >> (8 * (q & 3))) & 255u) == gid) slot = q;
+                if (slot >= 0) {
+                    float X[9], Y[9];   // dL/dRg = X Y^T
+                    if (!s.cov_mode) {  // 2 GSw Rg S0 = GM (Rq diag(sc))^T
+#pragma unroll
+                        for (int r = 0; r < 3; ++r)
+#pragma unroll
+                            for (int k = 0; k < 3; ++k) {
+                                X[3 * r + k] = 2.0f * (GSw[r][0] * Mw[k] + GSw[r][1] * Mw[3 + k] + GSw[r][2] * Mw[6 + k]);
+                                Y[3 * r + k] = Rq[3 * r + k] * sc[k];
+                            }
+                    } else {            // 2 GSw (Rg S0)
+                        const float S0[3][3] = {{a1.x, a1.y, a1.z}, {a1.y, a1.w, a2.x}, {a1.z, a2.x, a2.y}};
+#pragma unroll
+                        for (int r = 0; r < 3; ++r)
+#pragma unroll
+                            for (int k = 0; k < 3; ++k) {
+                                X[3 * r + k] = 2.0f * GSw[r][k];
+                                Y[3 * r + k] = Rg[3 * k] * S0[0][r] + Rg[3 * k + 1] * S0[1][r] + Rg[3 * k + 2] * S0[2][r];   // (Rg S0)^T
+                            }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                        for (int k = 0; k < 3; ++k)
+                            gP[4 * r + k] = gm[r] * m0[k] + (X[3 * r] * Y[3 * k] + X[3 * r + 1] * Y[3 * k + 1] + X[3 * r + 2] * Y[3 * k + 2]);
+                        gP[4 * r + 3] = gm[r];
+                    }
+                }
+            }
+        }
+    }
+    // the selected groups' poses: per slot present in the wave a butterfly over its lanes, the four waves in order, one row per
+    // (workgroup, slot); k_grad_poses adds the rows in workgroup order.  Dead lanes and lanes of other groups hold zeros.
+    if constexpr (POSES) {
+        __shared__ float s_pose[4][SAS_MAX_POSE_GRAD_GROUPS][12];
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        for (int q = 0; q < S.n_sel; ++q) {
+            const bool mine = slot == q;
+            const bool present = __any(mine);   // (wave-uniform)
+#pragma unroll
+            for (int k = 0; k < 12; ++k) {
+                float v = mine ? gP[k] : 0.0f;
+                if (present)
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
+                if (lane == 0) s_pose[wv][q][k] = v;
+            }
+        }
+        __syncthreads();
+        for (int t = (int)threadIdx.x; t < 12 * S.n_sel; t += 256) {   // (n_sel x 12 values, up to 384)
+            const int q = t / 12, k = t - 12 * q;
+            if (SAS_IN(12 * ((int64_t)blockIdx.x * S.n_sel) + t, 12 * (int64_t)gridDim.x * S.n_sel, 813))
+                S.partial[12 * ((int64_t)blockIdx.x * S.n_sel) + t] = ((s_pose[0][q][k] + s_pose[1][q][k]) + s_pose[2][q][k]) + s_pose[3][q][k];
         }
     }
     // the view matrix: wave butterflies, then the four waves in order
@@ -521,6 +588,27 @@ __global__ __launch_bounds__(256) void k_grad_project(SasScene s, SasCam c, cons
         B.partial[12 * (int64_t)blockIdx.x + threadIdx.x] = ((s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + s_part[2][threadIdx.x]) + s_part[3][threadIdx.x];
 }
 
+// d_group_poses[slot][k] += the workgroups' rows of that slot in workgroup order
+__global__ __launch_bounds__(12 * SAS_MAX_POSE_GRAD_GROUPS) void k_grad_poses(const float *partial, int n_wg, int n_sel, float *d_group_poses)
+{
+    const int t = threadIdx.x;
+    if (t >= 12 * n_sel) return;
+    // the additions in workgroup order, one after the other; sixteen rows' loads are in flight at a time (a load per addition leaves
+    // the one workgroup waiting on memory for every row: 3 907 rows at a million Gaussians)
+    const int64_t stride = 12 * (int64_t)n_sel;
+    float v = 0.0f;
+    int w = 0;
+    for (; w + 16 <= n_wg; w += 16) {
+        float x[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) x[i] = partial[stride * (w + i) + t];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v += x[i];
+    }
+    for (; w < n_wg; ++w) v += partial[stride * w + t];
+    d_group_poses[t] += v;
+}
+
 // d_viewmat[k] += the workgroups' rows in workgroup order
 __global__ __launch_bounds__(64) void k_grad_viewmat(const float *partial, int n_wg, float *d_viewmat)
 {
@@ -535,12 +623,17 @@ __global__ __launch_bounds__(64) void k_grad_viewmat(const float *partial, int n
 
 SAS_BOUNDS_ACCESSOR(sas_debug_bounds_grad)
 
-void sas_launch_grad_project(hipStream_t st, const SasScene &s, const SasParams &P, const SasFrame &f, const SasGradProj &B)
+void sas_launch_grad_project(hipStream_t st, const SasScene &s, const SasParams &P, const SasFrame &f, const SasGradProj &B,
+                             const SasPoseSel &S)
 {
     if (s.n <= 0) return;
     const int n_wg = (int)((s.n + 255) / 256);
-    hipLaunchKernelGGL(k_grad_project, dim3((unsigned)n_wg), dim3(256), 0, st, s, P.cam, (const uint4 *)f.info, f.group_Rt, B);
+    const bool with_poses = S.n_sel > 0 && S.n_sel <= SAS_MAX_POSE_GRAD_GROUPS && S.partial && S.d_group_poses;
+    if (with_poses) hipLaunchKernelGGL(k_grad_project<true>, dim3((unsigned)n_wg), dim3(256), 0, st, s, P.cam, (const uint4 *)f.info, f.group_Rt, B, S);
+    else hipLaunchKernelGGL(k_grad_project<false>, dim3((unsigned)n_wg), dim3(256), 0, st, s, P.cam, (const uint4 *)f.info, f.group_Rt, B, S);
     if (B.partial && B.d_viewmat) hipLaunchKernelGGL(k_grad_viewmat, dim3(1), dim3(64), 0, st, (const float *)B.partial, n_wg, B.d_viewmat);
+    if (with_poses)
+        hipLaunchKernelGGL(k_grad_poses, dim3(1), dim3(12 * SAS_MAX_POSE_GRAD_GROUPS), 0, st, (const float *)S.partial, n_wg, S.n_sel, S.d_group_poses);
 }
 
 void sas_launch_grad_tiles(hipStream_t st, const SasScene &s, int tiles, const SasParams &P, const SasFrame &f, const SasGrad &B,

@@ -271,8 +271,20 @@ struct SasGradProj {
     float *d_viewmat;        // [3,4] rows [R | t] (with partial)
     long long n;
 };
+// ... and to the poses of up to SAS_MAX_POSE_GRAD_GROUPS selected groups (sas_render_backward_poses): slot q of the selection is group
+// (ids[q / 4] >> 8 (q % 4)) & 255.  n_sel == 0: no pose gradient, the other fields are not read.
+#ifndef SAS_MAX_POSE_GRAD_GROUPS
+#define SAS_MAX_POSE_GRAD_GROUPS 32   // (include/sim_a_splat_amd.h)
+#endif
+struct SasPoseSel {
+    int n_sel;
+    unsigned ids[SAS_MAX_POSE_GRAD_GROUPS / 4];
+    float *partial;          // [ceil(n / 256)][n_sel][12] scratch: one row per (workgroup, slot)
+    float *d_group_poses;    // [n_sel,12] rows [R | t], in the selection's order
+};
 // behind sas_launch_grad_tiles on the same frame, which keeps its info records and has its group poses on the device
-void sas_launch_grad_project(hipStream_t st, const SasScene &s, const SasParams &P, const SasFrame &f, const SasGradProj &B);
+void sas_launch_grad_project(hipStream_t st, const SasScene &s, const SasParams &P, const SasFrame &f, const SasGradProj &B,
+                             const SasPoseSel &S);
 // store <- features [nt,C] (device; nullptr: one-hot of the triangles' pose groups), through finite_colour
 void sas_launch_mesh_feature_store(hipStream_t st, int64_t nt, const int4 *tri, const float *src, int C, float *store);
 

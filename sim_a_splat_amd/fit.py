@@ -12,7 +12,8 @@ whose kernels deliver the gradients ``render_backward`` takes ("Pho
 PSNR of the scene as it stands.
 
 Out of scope, and why: multi-scale SSIM, LPIPS, depth and alpha loss terms (pass one through ``loss_and_grad``); screen-size splits and
-prunes and ``revised_opacity`` of gsplat's strategy; gradients for K, the group poses and meshes (the limits of the backward pass).
+prunes and ``revised_opacity`` of gsplat's strategy; gradients for K and meshes (the limits of the backward pass).  The group poses are
+not variables of this loop: ``register.refine_group_poses`` fits them.
 """
 from __future__ import annotations
 

@@ -1006,7 +1006,8 @@ class Rasterizer:
     @_locked
     def render_backward(self, viewmat: ArrayLike, K: ArrayLike, width: int, height: int, g_rgb=None, g_alpha=None, g_depth=None, *,
                         screen_space: bool = False, out: Optional[Dict[str, torch.Tensor]] = None,
-                        want: Optional[Iterable[str]] = None, fast_exp: bool = False) -> Dict[str, torch.Tensor]:
+                        want: Optional[Iterable[str]] = None, fast_exp: bool = False,
+                        pose_groups: Optional[Sequence[int]] = None) -> Dict[str, torch.Tensor]:
         """The backward pass of one view (sas_render_backward; DESIGN.md 3, "Backward pass").  ``g_rgb [H,W,3]``, ``g_alpha [H,W]``,
         ``g_depth [H,W]`` (tensors or arrays, each may be None, not all) are the gradients of a loss with respect to the frame's RAW
         accumulators: ``sum c alpha T`` (rgb before background and clamp), ``1 - T_final`` and ``sum z alpha T`` (depth before the
@@ -1018,7 +1019,11 @@ class Rasterizer:
         ``out``: a dict of such tensors to ACCUMULATE into (several views sum); missing keys are allocated zeroed.  ``want``: only
         these keys are computed and returned (the others are NULL to the C call, whose kernels then neither read nor write them):
         a pose optimiser asks for ``("viewmat",)`` alone.
-        Decisions (culls, clamps, the compositing thresholds) are constants; K, the group poses and meshes are not differentiated (a
+        ``pose_groups``: up to 32 distinct group ids (sas_render_backward_poses); the result gains ``group_poses [n_sel,3,4]``, the
+        gradient with respect to the rows ``[R | t]`` of those groups' current poses (twelve independent entries each, as ``viewmat``), in
+        the order of ``pose_groups``; ``want`` may name it only then, and ``("group_poses",)`` alone computes nothing else.  More groups:
+        call again with the next 32.
+        Decisions (culls, clamps, the compositing thresholds) are constants; K, meshes and joint angles are not differentiated (a
         scene with meshes is refused).  The sums over pixels are float atomics: last bits vary from run to run.  Blocking."""
         V, pV = self._host_arg(viewmat, 16)
         Kc, pK = self._host_arg(K, 9)
@@ -1035,6 +1040,15 @@ class Rasterizer:
             scene = self._scene_shapes()
             shapes = {k: scene.pop(k) for k in ("means", "opacities", "colors")}
             shapes.update(viewmat=(3, 4), **scene)   # (the keys keep the order they always had: it shows in results and messages)
+        sel = None
+        if pose_groups is not None:
+            if screen_space:
+                raise ValueError("render_backward: pose_groups needs the projection's backward: not with screen_space=True")
+            ids = [int(g) for g in pose_groups]
+            if not ids or any(g < 0 or g > 255 for g in ids):
+                raise ValueError(f"render_backward: pose_groups must name group ids in 0..255, got {tuple(pose_groups)}")
+            sel = np.ascontiguousarray(ids, dtype=np.uint8)
+            shapes["group_poses"] = (len(ids), 3, 4)
         if want is not None:
             want = tuple(want)
             unknown = [k for k in want if k not in shapes]
@@ -1054,12 +1068,18 @@ class Rasterizer:
         if screen_space:
             rc = self._L.sas_render_backward_screen(self._ctx, pV, pK, W, H, flags, ptr(gr), ptr(ga), ptr(gd), ptr(res.get("means2d")),
                                                     ptr(res.get("conics")), ptr(res.get("opacities")), ptr(res.get("colors")), ptr(res.get("depths")), stream)
+        elif sel is not None:
+            with_poses = "group_poses" in res   # (left out through ``want``: the plain call)
+            rc = self._L.sas_render_backward_poses(self._ctx, pV, pK, W, H, flags, ptr(gr), ptr(ga), ptr(gd), ptr(res.get("means")),
+                                                   ptr(res.get("opacities")), ptr(res.get("colors")), ptr(res.get("quats")), ptr(res.get("scales")),
+                                                   ptr(res.get("covariances")), ptr(res.get("viewmat")), len(sel) if with_poses else 0,
+                                                   sel.ctypes.data if with_poses else None, ptr(res.get("group_poses")), stream)
         else:
             rc = self._L.sas_render_backward(self._ctx, pV, pK, W, H, flags, ptr(gr), ptr(ga), ptr(gd), ptr(res.get("means")), ptr(res.get("opacities")),
                                              ptr(res.get("colors")), ptr(res.get("quats")), ptr(res.get("scales")), ptr(res.get("covariances")),
                                              ptr(res.get("viewmat")), stream)
         if rc != 0:
-            self._check(rc, "sas_render_backward_screen" if screen_space else "sas_render_backward")
+            self._check(rc, "sas_render_backward_screen" if screen_space else "sas_render_backward_poses" if sel is not None else "sas_render_backward")
         self._in_flight(True)
         return res
 

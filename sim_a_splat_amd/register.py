@@ -283,6 +283,104 @@ def refine_camera_pose(r, image, V0, K, W: int, H: int, iters: int = 300, mask=N
     return res
 
 
+# ---- group poses from pictures: where is the T-block, where are the links ("Backward pass") -------------------------------------
+@dataclass
+class GroupPoseRefinement:
+    poses: np.ndarray                   # [G,3,4] float64, rows [R | t] of every group (the groups that were not refined as they were)
+    loss: float                         # mean squared colour difference of the last evaluation, at full size, averaged over the views
+    history: List[Tuple[int, float]] = field(default_factory=list)   # (downsampling factor, loss) of every evaluation
+
+
+def refine_group_poses(r, images, viewmats, Ks, W: int, H: int, groups: Sequence[int], iters: int = 200, masks=None, pivots=None,
+                       step: Tuple[float, float] = (0.01, 0.01), factors: Sequence[int] = (2, 1), background=(0.0, 0.0, 0.0),
+                       loss_and_grad: Optional[Callable] = None) -> GroupPoseRefinement:
+    """Refine the poses of the splat groups ``groups`` (up to 32 ids) of rasterizer ``r`` so that its frames look like ``images
+    [C,H,W,3]`` (float, 0..1) seen from ``viewmats [C,4,4]`` (world -> camera) with ``Ks [C,3,3]``: all views observe ONE set of poses.
+    ``refine_camera_pose``'s scheme per group: Adam on an se(3) twist that left-multiplies the group's pose about its pivot
+    (``pivots [n_sel,3]``, world coordinates; None: the pose's translation, where the canonical origin lands), minimising the mean
+    squared colour difference over ``masks [C,H,W]`` averaged over the views, coarse to fine over ``factors`` with the step falling to
+    a twentieth over each level.  Every step renders every view and accumulates the pose gradient of ``Rasterizer.render_backward``
+    through ``out=``.  The start is ``r.get_group_poses()``; the poses are written to ``r`` with ``set_group_poses`` every step and are
+    left at the result.  ``loss_and_grad(poses [G,3,4], V, K, w, h, target, mask) -> (loss, d_poses [n_sel,3,4])`` replaces the
+    renderer for one view (tests run the same optimiser on a CPU reference)."""
+    import torch
+    import torch.nn.functional as Fn
+    dev = getattr(r, "device", "cpu")
+    sel = [int(g) for g in groups]
+    n_sel = len(sel)
+    Vs = np.asarray(_host(viewmats), np.float64).reshape(-1, 4, 4)
+    C = Vs.shape[0]
+    K0s = np.asarray(_host(Ks), np.float64).reshape(-1, 3, 3)
+    if K0s.shape[0] == 1 and C > 1:
+        K0s = np.repeat(K0s, C, axis=0)
+    imgs = torch.as_tensor(np.asarray(_host(images), np.float32)).reshape(C, H, W, 3)
+    ms = torch.ones((C, H, W), dtype=torch.float32) if masks is None else (torch.as_tensor(np.asarray(_host(masks))) != 0).to(torch.float32).reshape(C, H, W)
+    poses = np.asarray(r.get_group_poses(), np.float64).reshape(-1, 3, 4).copy()
+    if n_sel < 1 or len(set(sel)) != n_sel or min(sel) < 0 or max(sel) >= poses.shape[0]:
+        raise ValueError(f"refine_group_poses: groups must name distinct ids below {poses.shape[0]}, got {tuple(groups)}")
+    piv = poses[sel, :, 3].copy() if pivots is None else np.asarray(_host(pivots), np.float64).reshape(n_sel, 3).copy()
+
+    def evaluate(G, Kcs, w, h, targets, tms):
+        """(loss, d_poses [n_sel,3,4]) averaged over the views."""
+        if loss_and_grad is not None:
+            parts = [loss_and_grad(G, Vs[v], Kcs[v], w, h, targets[v], tms[v]) for v in range(C)]
+            return sum(p[0] for p in parts) / C, sum(np.asarray(p[1], np.float64).reshape(n_sel, 3, 4) for p in parts) / C
+        from .autograd import prechain
+        acc, total = None, 0.0
+        for v in range(C):
+            V32, K32 = Vs[v].astype(np.float32), Kcs[v].astype(np.float32)
+            out = r.render(V32, K32, w, h, background)
+            rgb, alpha, depth = out["rgb"].clone(), out["alpha"].clone(), out["depth"].clone()
+            t, k = targets[v].to(rgb.device), tms[v].to(rgb.device)
+            scale = 1.0 / (3.0 * float(torch.clamp(k.sum(), min=1.0)) * C)
+            diff = k[..., None] * (rgb - t)
+            total += float((diff * (rgb - t)).sum()) * scale
+            g_acc, g_a, g_z = prechain(rgb, alpha, depth, background, 2.0 * scale * diff, None, None)
+            acc = r.render_backward(V32, K32, w, h, g_acc, g_a, g_z, want=("group_poses",), pose_groups=sel, out=acc)
+        return total, acc["group_poses"].double().cpu().numpy()
+
+    res = GroupPoseRefinement(poses, float("nan"))
+    per = max(1, int(iters) // max(1, len(factors)))
+    for f in factors:
+        w, h = max(1, W // f), max(1, H // f)
+        if f == 1:
+            targets, tms = imgs, ms
+        else:
+            # area average of the masked images, renormalised by the mask's coverage
+            cover = Fn.interpolate(ms[:, None], size=(h, w), mode="area")[:, 0]
+            targets = Fn.interpolate((imgs * ms[..., None]).permute(0, 3, 1, 2), size=(h, w), mode="area").permute(0, 2, 3, 1) / torch.clamp(cover, min=1e-6)[..., None]
+            tms = (cover > 0.5).to(torch.float32)
+        Kcs = K0s.copy()
+        Kcs[:, 0] *= w / W
+        Kcs[:, 1] *= h / H
+        m1, m2 = np.zeros((n_sel, 6)), np.zeros((n_sel, 6))
+        for it in range(per):
+            r.set_group_poses(poses.reshape(-1, 12).astype(np.float32))
+            loss, dG = evaluate(poses, Kcs, w, h, targets, tms)
+            res.history.append((int(f), loss))
+            decay = 0.05 ** (it / max(1, per - 1))
+            for q, g in enumerate(sel):
+                G4 = np.eye(4)
+                G4[:3] = poses[g]
+                tw = twist_gradient(dG[q], G4)
+                tw[:3] += np.cross(tw[3:], piv[q])   # the same twist about the pivot
+                m1[q] = 0.9 * m1[q] + 0.1 * tw
+                m2[q] = 0.999 * m2[q] + 0.001 * tw * tw
+                hat = (m1[q] / (1 - 0.9 ** (it + 1))) / (np.sqrt(m2[q] / (1 - 0.999 ** (it + 1))) + 1e-12)
+                Tp = np.eye(4)
+                Tp[:3, 3] = piv[q]
+                Tpi = np.eye(4)
+                Tpi[:3, 3] = -piv[q]
+                M = Tp @ se3_exp(-np.concatenate([step[0] * decay * hat[:3], step[1] * decay * hat[3:]])) @ Tpi
+                poses[g] = (M @ G4)[:3]
+                piv[q] = (M @ np.append(piv[q], 1.0))[:3]   # the pivot is a point of the group: it moves with it
+    r.set_group_poses(poses.reshape(-1, 12).astype(np.float32))
+    res.poses = poses
+    res.loss = evaluate(poses, K0s, W, H, imgs, ms)[0]
+    res.history.append((1, res.loss))
+    return res
+
+
 def main(argv: Optional[Sequence[str]] = None, matcher=None) -> int:
     import argparse
     from . import io, poses, segment

@@ -454,6 +454,37 @@ class SplatScene:
         camera c sees the scene under ``pose_sets[pose_set[c]]`` (vectorised envs); the scene's own poses are not touched."""
         return self.get_observations(height, width, cam_poses, fov, pose_sets, pose_set, min_alpha)["labels"]
 
+    def refine_handle_poses(self, handles, images, height: int, width: int, cam_poses, fov: Optional[float] = None, iters: int = 200,
+                            masks=None):
+        """Where are these groups, given these pictures: refine the poses of ``handles`` (up to 32 splat-group handles) so that the
+        scene's frames from ``cam_poses [(wxyz, position), ...]`` look like ``images [C,H,W,3]`` (uint8, or float 0..1) over ``masks
+        [C,H,W]`` -- ``register.refine_group_poses`` on the handles' pose rows, each turning about the posed centroid of its centres,
+        with the views of ``get_renders``.  On return the handles' ``wxyz`` (a unit quaternion) and ``position`` hold the refined poses,
+        and the result (``GroupPoseRefinement``) the whole block.  The lock is held throughout; a scene with meshes is refused (the
+        backward pass does not take occlusion by meshes)."""
+        from .register import refine_group_poses
+        hs = list(handles)
+        V, K = self._views_and_Ks(int(height), int(width), *_camera_arrays(cam_poses), self._camera_or(fov=fov)[2])
+        img = np.asarray(images.detach().cpu().numpy() if isinstance(images, torch.Tensor) else images)
+        img = img.astype(np.float32) / 255.0 if img.dtype == np.uint8 else img.astype(np.float32)
+        with self.lock:
+            by_row = {g["row"]: g for g in self._groups}
+            for h in hs:
+                if h._scene is not self or h.index not in by_row:
+                    raise ValueError(f"refine_handle_poses: {getattr(h, 'name', h)!r} is not a splat group of this scene")
+            self._sync()
+            pivots = np.stack([mv3(self._Rt[h.index, :, :3].astype(np.float64), by_row[h.index]["centers"].astype(np.float64)).mean(axis=0)
+                               + self._Rt[h.index, :, 3] for h in hs])
+            res = refine_group_poses(self._raster, img, V, K, int(width), int(height), [h.index for h in hs], iters=iters, masks=masks,
+                                     pivots=pivots, background=self.background)
+            for h in hs:   # through a unit quaternion, as the setters do; the block is rewritten from the handles
+                h._refresh()
+                h._wxyz = np.asarray(matrix_to_quat_wxyz(res.poses[h.index, :, :3]), np.float64)
+                h._wxyz = h._wxyz / np.linalg.norm(h._wxyz)
+                h._position = res.poses[h.index, :, 3].copy()
+                h._write_row()
+            return res
+
     def close(self) -> None:
         with self.lock:
             self._raster.close()

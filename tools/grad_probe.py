@@ -3,6 +3,11 @@ same run, the calls alternating, medians over the rounds (profiles/render_backwa
 
     python tools/grad_probe.py [--out FILE]     one 240x320 Gym-camera frame of the 292 247-Gaussian stand-in and one 1920x1080 view of
                                                 config 3
+    python tools/grad_probe.py --poses N [--out FILE]   the same two settings with N posed splat groups: render_backward for
+                                                ("viewmat",), for ("group_poses",), and the full call with and without pose_groups
+                                                (appended to FILE: profiles/group_pose_grad.txt).  Copied into the tools/ of a
+                                                checkout of an earlier commit it times the rows that build has, for a comparison
+                                                within one session.
 
 Every row is a whole blocking call (projection, binning, sort, k_blend and what the call adds behind it).  The calls differ in what they
 write besides: the two render rows write rgb, alpha and depth, the lift and backward rows write none of them.
@@ -93,11 +98,65 @@ def case(name, n, seed, ls, G, W, H, f, rounds):
     r.close()
 
 
+def poses_case(name, n, seed, ls, W, H, f, rounds, n_poses):
+    """The --poses leg: the scene with n_poses splat groups under random poses; the pose optimisers' calls and the full call with and
+    without the pose gradient, alternating.  A library without sas_render_backward_poses (this file run from a checkout of an earlier
+    commit) runs the rows it has: the unposed ones, for the comparison in one session."""
+    from sim_a_splat_amd import _capi
+    from sim_a_splat_amd.synthetic import random_group_poses
+    sc = make_scene(n, seed=seed, log_scale_mean=float(np.log(ls)), n_groups=n_poses)
+    c = ring_camera(W, H, f)
+    V, K = c.viewmat, c.K
+    r = Rasterizer(0)
+    r.upload(sc.means, sc.opacities, sc.sh, quats=sc.quats, scales=sc.scales, sh_degree=sc.sh_degree, group_id=sc.group_id, n_groups=n_poses)
+    r.set_group_poses(random_group_poses(n_poses, seed + 1))
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    g_rgb = torch.randn((H, W, 3), device="cuda", generator=gen)
+    g_a = torch.randn((H, W), device="cuda", generator=gen)
+    g_d = torch.randn((H, W), device="cuda", generator=gen)
+    posed = hasattr(_capi.lib(), "sas_render_backward_poses")
+    groups = tuple(range(n_poses))
+    full = r.render_backward(V, K, W, H, g_rgb, g_a, g_d)
+    say(f"== {name}, {n_poses} posed groups: {n} Gaussians, one view of {W}x{H}; package {Path(_capi.__file__).resolve().parent.parent.name}, "
+        f"{'with' if posed else 'WITHOUT'} sas_render_backward_poses")
+    calls = {
+        "render_backward want=viewmat": lambda: r.render_backward(V, K, W, H, g_rgb, g_a, g_d, out=full, want=("viewmat",)),
+        "render_backward (no pose_groups)": lambda: r.render_backward(V, K, W, H, g_rgb, g_a, g_d, out=full),
+    }
+    if posed:
+        fullp = r.render_backward(V, K, W, H, g_rgb, g_a, g_d, pose_groups=groups)
+        calls[f"render_backward want=group_poses ({n_poses} groups)"] = lambda: r.render_backward(V, K, W, H, g_rgb, g_a, g_d, out=fullp, want=("group_poses",), pose_groups=groups)
+        calls[f"render_backward pose_groups ({n_poses} groups)"] = lambda: r.render_backward(V, K, W, H, g_rgb, g_a, g_d, out=fullp, pose_groups=groups)
+    for _ in range(3):   # warm-up: allocations, the clock ramp
+        for fn in calls.values():
+            fn()
+    res = {k: [] for k in calls}
+    for _ in range(rounds):
+        for k, fn in calls.items():
+            res[k].append(timed(fn))
+    say(f"{'ms, median of ' + str(rounds) + ' rounds [min..max]':52s} {'device events':>28s} {'call wall':>10s}")
+    for k, rows in res.items():
+        a = np.array(rows)
+        m = np.median(a, axis=0)
+        say(f"{k:52s} {m[0]:8.3f} [{a[:, 0].min():.3f}..{a[:, 0].max():.3f}] {m[1]:10.3f}")
+    say()
+    r.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default="")
+    ap.add_argument("--poses", type=int, default=0, help="N: time the pose-gradient calls with N posed groups instead (profiles/group_pose_grad.txt)")
     a = ap.parse_args()
     say(f"device: {torch.cuda.get_device_name(0)}")
+    if a.poses:
+        poses_case("Gym camera", 292_247, 2, 0.01, 320, 240, 262.5, 15, a.poses)
+        poses_case("config 3", 1_000_000, 3, 0.006, 1920, 1080, 1000.0, 11, a.poses)
+        if a.out:
+            Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+            with open(a.out, "a") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     case("Gym camera", 292_247, 2, 0.01, 7, 320, 240, 262.5, 9)
     case("config 3", 1_000_000, 3, 0.006, 0, 1920, 1080, 1000.0, 7)
     if a.out:
