@@ -390,6 +390,25 @@ int ensure(sas_ctx *c, DevBuf &b, size_t bytes)
     return SAS_OK;
 }
 
+// ... and several buffers in the order given: the first failure is the call's.
+struct Want { DevBuf &buf; size_t bytes; };
+int ensure(sas_ctx *c, std::initializer_list<Want> wants)
+{
+    for (const Want &w : wants)
+        if (const int rc = ensure(c, w.buf, w.bytes)) return rc;
+    return SAS_OK;
+}
+
+// Behind the launches of a blocking call on `st`: what launching left behind, `ev` (optional) recorded behind them, the wait.
+int finish_launches(sas_ctx *c, hipStream_t st, const char *what, hipEvent_t ev = nullptr)
+{
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && ev) e = hipEventRecord(ev, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    return SAS_OK;
+}
+
 // The optimiser state goes (a new scene, sas_scene_adam_reset): hipFree waits for the step that may still be using it.
 int Adam::drop(sas_ctx *c)
 {
@@ -413,11 +432,7 @@ int Planes::alloc(sas_ctx *c, int64_t count, int colour_planes)
     n = count;
     n_pad = (count + 63) & ~63ll;
     const size_t np = (size_t)(n_pad > 0 ? n_pad : 64), plane = sizeof(float4) * np;
-    int rc;
-    if ((rc = ensure(c, g0, plane)) || (rc = ensure(c, g1, plane)) || (rc = ensure(c, g2, plane)) || (rc = ensure(c, col, plane * colour_planes)) ||
-        (rc = ensure(c, gid8, np)) || (rc = ensure(c, perm, sizeof(int) * np)))
-        return rc;
-    return SAS_OK;
+    return ensure(c, {{g0, plane}, {g1, plane}, {g2, plane}, {col, plane * colour_planes}, {gid8, np}, {perm, sizeof(int) * np}});
 }
 
 // What of the resident scene a call has changed: the values in the planes; the count and the storage order too; or everything.
@@ -1179,10 +1194,7 @@ int fill_feature_store(sas_ctx *c, DevBuf &store, size_t stride, int channels, c
     if (rows && n_rows > 0 && (rc = device_floats(c, rows, n_rows * (size_t)channels, stage, &src))) return rc;
     hipStream_t st = c->slots[0].fs;
     launch(st, src, (float *)store.p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-    return SAS_OK;
+    return finish_launches(c, st, what);
 }
 
 }  // namespace
@@ -1697,10 +1709,8 @@ int sas_scene_meshes(sas_ctx *c, int64_t n_vertices, const float *vertices, int6
     // validated: only now are the previous meshes replaced (a rejected call leaves them in place; a failed device copy
     // below leaves none)
     forget(c, HAVE_MESH);
-    int rc;
-    if ((rc = ensure(c, c->mesh_vert, sizeof(float4) * std::max<size_t>(nv, 1)))) return rc;
-    if ((rc = ensure(c, c->mesh_tri, sizeof(int4) * nt))) return rc;
-    if ((rc = ensure(c, c->mesh_col, sizeof(float4) * nt))) return rc;
+    if (const int rc = ensure(c, {{c->mesh_vert, sizeof(float4) * std::max<size_t>(nv, 1)}, {c->mesh_tri, sizeof(int4) * nt}, {c->mesh_col, sizeof(float4) * nt}}))
+        return rc;
     if (nv) HIP_TRY(c, hipMemcpy(c->mesh_vert.p, v4.data(), sizeof(float4) * nv, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->mesh_tri.p, t4.data(), sizeof(int4) * nt, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->mesh_col.p, c4.data(), sizeof(float4) * nt, hipMemcpyHostToDevice));
@@ -1761,6 +1771,52 @@ int sas_scene_mesh_vertex_attributes(sas_ctx *c, int64_t n_vertices, const float
     return SAS_OK;
 }
 
+// ---- what the calls that need no scene share: sas_query_meshes, sas_match_points, sas_sample_points, sas_fuse_depth ----------------------
+
+static int check_max_distance(sas_ctx *c, float max_distance)
+{
+    if (!(max_distance >= 0.0f)) return fail(c, SAS_ERR_INVALID, "max_distance must be >= 0 (INFINITY allowed), got %g", (double)max_distance);
+    return SAS_OK;
+}
+
+// rows: a row-major 3x4 block A|t, or nullptr: the identity
+static SasAffine pack_affine(const float *rows)
+{
+    SasAffine m;
+    for (int k = 0; k < 3; ++k) {
+        for (int j = 0; j < 3; ++j) m.A[3 * k + j] = rows ? rows[4 * k + j] : (k == j ? 1.0f : 0.0f);
+        m.t[k] = rows ? rows[4 * k + 3] : 0.0f;
+    }
+    return m;
+}
+
+static SasDepthView pack_depth_view(const float *K, const float *rows) { return SasDepthView{K[0], K[4], K[2], K[5], pack_affine(rows)}; }
+
+// What a call that takes depth views checks of them: C views of W x H pixels, `depth`, Ks [C,9], transform [C,12] or nullptr, flags.
+// sized_without_views: W and H must be positive, and a view within the pixel limit, even when C is 0 (sas_fuse_depth; sas_sample_points
+// accepts any size with no view).  C itself is the caller's to check, first.
+static int check_depth_views(sas_ctx *c, const char *who, int C, int W, int H, const float *depth, const float *Ks, const float *transform,
+                             unsigned flags, bool sized_without_views)
+{
+    if (flags & ~SAS_TIMING) return fail(c, SAS_ERR_INVALID, "%s: flags 0x%x not accepted (SAS_TIMING; blocking only)", who, flags);
+    if (C > 0 || sized_without_views) {
+        if (W <= 0 || H <= 0) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, W, H);
+        const long long px_max = 0x7fffffffll - 256, px_view = (long long)H * W;   // (no product beyond 2^62)
+        if (px_view > px_max || (long long)C * px_view > px_max)
+            return fail(c, SAS_ERR_INVALID, "%s: %d views of %dx%d are more than 2^31 - 256 pixels", who, C, W, H);
+    }
+    if (C > 0 && (!depth || !Ks)) return fail(c, SAS_ERR_INVALID, "%s: depth and Ks are required", who);
+    for (int v = 0; v < C; ++v) {
+        const float *Kv = Ks + 9 * (size_t)v, *Tv = transform ? transform + 12 * (size_t)v : nullptr;
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(Kv[k])) return fail(c, SAS_ERR_INVALID, "%s: Ks[%d][%d] = %g is not finite", who, v, k, (double)Kv[k]);
+        if (!(Kv[0] > 0.0f) || !(Kv[4] > 0.0f)) return fail(c, SAS_ERR_INVALID, "%s: view %d: fx = %g, fy = %g must be > 0", who, v, (double)Kv[0], (double)Kv[4]);
+        for (int k = 0; Tv && k < 12; ++k)
+            if (!std::isfinite(Tv[k])) return fail(c, SAS_ERR_INVALID, "%s: transform[%d][%d] = %g is not finite", who, v, k, (double)Tv[k]);
+    }
+    return SAS_OK;
+}
+
 int sas_query_meshes(sas_ctx *c, int64_t n_points, const float *points, int64_t n_vertices, const float *vertices, int64_t n_triangles,
                      const int32_t *triangles, int n_meshes, const int64_t *mesh_offsets, float max_distance, float *distance,
                      float *winding, void *stream)
@@ -1770,7 +1826,7 @@ int sas_query_meshes(sas_ctx *c, int64_t n_points, const float *points, int64_t 
         return fail(c, SAS_ERR_INVALID, "bad query sizes: %lld points, %lld vertices, %lld triangles", (long long)n_points,
                     (long long)n_vertices, (long long)n_triangles);
     if (n_meshes < 1 || n_meshes > 256) return fail(c, SAS_ERR_INVALID, "n_meshes %d out of [1,256]", n_meshes);
-    if (!(max_distance >= 0.0f)) return fail(c, SAS_ERR_INVALID, "max_distance must be >= 0 (INFINITY allowed), got %g", (double)max_distance);
+    if (const int rc = check_max_distance(c, max_distance)) return rc;
     if (!distance && !winding) return fail(c, SAS_ERR_INVALID, "distance and winding are both NULL");
     if (!mesh_offsets || (n_points > 0 && !points) || (n_triangles > 0 && (!vertices || !triangles)))
         return fail(c, SAS_ERR_INVALID, "points, vertices, triangles and mesh_offsets are required");
@@ -1814,12 +1870,12 @@ int sas_query_meshes(sas_ctx *c, int64_t n_points, const float *points, int64_t 
     }
     if (n_points == 0) return SAS_OK;
     if (const int rc = complete_all(c)) return rc;
-    int rc;
-    if ((rc = ensure(c, c->query_pts, sizeof(float) * 3 * np))) return rc;
-    if ((rc = ensure(c, c->query_tri, sizeof(float4) * std::max<size_t>(rec.size(), 1)))) return rc;
-    if ((rc = ensure(c, c->query_mesh, sizeof(SasQueryMesh) * table.size()))) return rc;
-    if ((rc = ensure(c, c->query_list, sizeof(int) * np * table.size()))) return rc;
-    if ((rc = ensure(c, c->query_count, sizeof(int) * table.size()))) return rc;
+    if (const int rc = ensure(c, {{c->query_pts, sizeof(float) * 3 * np},
+                                  {c->query_tri, sizeof(float4) * std::max<size_t>(rec.size(), 1)},
+                                  {c->query_mesh, sizeof(SasQueryMesh) * table.size()},
+                                  {c->query_list, sizeof(int) * np * table.size()},
+                                  {c->query_count, sizeof(int) * table.size()}}))
+        return rc;
     HIP_TRY(c, hipMemcpy(c->query_pts.p, points, sizeof(float) * 3 * np, hipMemcpyDefault));
     if (!rec.empty()) HIP_TRY(c, hipMemcpy(c->query_tri.p, rec.data(), sizeof(float4) * rec.size(), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->query_mesh.p, table.data(), sizeof(SasQueryMesh) * table.size(), hipMemcpyHostToDevice));
@@ -1837,10 +1893,7 @@ int sas_query_meshes(sas_ctx *c, int64_t n_points, const float *points, int64_t 
     q.max_distance = max_distance;
     hipStream_t st = (hipStream_t)stream;
     sas_launch_query(st, q);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "mesh query: %s", hipGetErrorString(e));
-    return SAS_OK;
+    return finish_launches(c, st, "mesh query");
 }
 
 // The slice count of a sas_match_points call: `asked`, or (0) as many as bring the grid of k_match_slice to four workgroups per compute
@@ -1859,16 +1912,13 @@ int sas_match_points(sas_ctx *c, int64_t n_source, const float *source, int64_t 
     if (n_source < 0 || n_source > 0x7fffff00ll || n_target < 0 || n_target > 0x7fffff00ll)
         return fail(c, SAS_ERR_INVALID, "bad match sizes: %lld source points, %lld target points", (long long)n_source, (long long)n_target);
     if ((n_source > 0 && !source) || (n_target > 0 && !target)) return fail(c, SAS_ERR_INVALID, "source and target are required");
-    if (!(max_distance >= 0.0f)) return fail(c, SAS_ERR_INVALID, "max_distance must be >= 0 (INFINITY allowed), got %g", (double)max_distance);
+    if (const int rc = check_max_distance(c, max_distance)) return rc;
     if (slices < 0) return fail(c, SAS_ERR_INVALID, "slices must be >= 0 (0: the library's choice), got %d", slices);
     if (!index && !dist2 && !moments) return fail(c, SAS_ERR_INVALID, "index, dist2 and moments are all NULL");
-    SasMatch m{};
-    for (int k = 0; k < 3; ++k) {
-        for (int j = 0; j < 3; ++j) m.A[3 * k + j] = transform ? transform[4 * k + j] : (k == j ? 1.0f : 0.0f);
-        m.t[k] = transform ? transform[4 * k + 3] : 0.0f;
-    }
     for (int k = 0; transform && k < 12; ++k)
         if (!std::isfinite(transform[k])) return fail(c, SAS_ERR_INVALID, "transform[%d] = %g is not finite", k, (double)transform[k]);
+    SasMatch m{};
+    m.m = pack_affine(transform);
     if (moments) std::fill(moments, moments + SAS_MATCH_MOMENTS, 0.0);
     if (n_source == 0) return SAS_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1886,13 +1936,13 @@ int sas_match_points(sas_ctx *c, int64_t n_source, const float *source, int64_t 
     m.slice_targets = std::max(1ll, (n_chunks + m.slices - 1) / m.slices) * SAS_MATCH_CHUNK;
     m.slices = (int)std::max(1ll, (n_target + m.slice_targets - 1) / m.slice_targets);   // (no slice is empty)
     m.md2 = max_distance * max_distance;
-    int rc;
-    if ((rc = ensure(c, c->match_src, sizeof(float) * 3 * ns))) return rc;
-    if ((rc = ensure(c, c->match_tgt, sizeof(float) * 3 * std::max<size_t>(nt, 1)))) return rc;
-    if ((rc = ensure(c, c->match_keys, sizeof(unsigned long long) * ns * (size_t)m.slices))) return rc;
-    if ((rc = ensure(c, c->match_index, sizeof(int32_t) * ns))) return rc;
-    if ((rc = ensure(c, c->match_dist2, sizeof(float) * ns))) return rc;
-    if ((rc = ensure(c, c->match_partial, sizeof(double) * SAS_MATCH_MOMENTS * ((size_t)m.n_blocks + 1)))) return rc;
+    if (const int rc = ensure(c, {{c->match_src, sizeof(float) * 3 * ns},
+                                  {c->match_tgt, sizeof(float) * 3 * std::max<size_t>(nt, 1)},
+                                  {c->match_keys, sizeof(unsigned long long) * ns * (size_t)m.slices},
+                                  {c->match_index, sizeof(int32_t) * ns},
+                                  {c->match_dist2, sizeof(float) * ns},
+                                  {c->match_partial, sizeof(double) * SAS_MATCH_MOMENTS * ((size_t)m.n_blocks + 1)}}))
+        return rc;
     HIP_TRY(c, hipMemcpy(c->match_src.p, source, sizeof(float) * 3 * ns, hipMemcpyDefault));
     if (nt) HIP_TRY(c, hipMemcpy(c->match_tgt.p, target, sizeof(float) * 3 * nt, hipMemcpyDefault));
     m.source = (const float *)c->match_src.p;
@@ -1904,9 +1954,7 @@ int sas_match_points(sas_ctx *c, int64_t n_source, const float *source, int64_t 
     m.moments = moments ? (double *)c->match_partial.p + SAS_MATCH_MOMENTS * (size_t)m.n_blocks : nullptr;   // the row behind them
     hipStream_t st = (hipStream_t)stream;
     sas_launch_match(st, m);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "point matching: %s", hipGetErrorString(e));
+    if (const int rc = finish_launches(c, st, "point matching")) return rc;
     if (index) HIP_TRY(c, hipMemcpy(index, c->match_index.p, sizeof(int32_t) * ns, hipMemcpyDefault));
     if (dist2) HIP_TRY(c, hipMemcpy(dist2, c->match_dist2.p, sizeof(float) * ns, hipMemcpyDefault));
     if (moments) HIP_TRY(c, hipMemcpy(moments, m.moments, sizeof(double) * SAS_MATCH_MOMENTS, hipMemcpyDeviceToHost));
@@ -1921,16 +1969,12 @@ int sas_sample_points(sas_ctx *c, int n_views, int width, int height, const floa
     if (!c) return SAS_ERR_INVALID;
     const char *who = "sas_sample_points";
     const int C = n_views, E = n_clouds, K = n_points;
-    if (flags & ~SAS_TIMING) return fail(c, SAS_ERR_INVALID, "%s: flags 0x%x not accepted (SAS_TIMING; blocking only)", who, flags);
     if (C < 0 || C > 65535) return fail(c, SAS_ERR_INVALID, "%s: n_views %d out of [0,65535]", who, C);
     if (E < 1) return fail(c, SAS_ERR_INVALID, "%s: n_clouds %d, at least one is needed", who, E);
     if (K < 0) return fail(c, SAS_ERR_INVALID, "%s: n_points %d is negative", who, K);
     if (stride < 1) return fail(c, SAS_ERR_INVALID, "%s: stride %d, must be >= 1", who, stride);
     if ((long long)E * std::max(K, 1) > 0x7fffff00ll) return fail(c, SAS_ERR_INVALID, "%s: %d clouds of %d points are too many", who, E, K);
-    if (C > 0 && (width <= 0 || height <= 0)) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
-    if (C > 0 && (long long)C * height * width > 0x7fffffffll - 256)
-        return fail(c, SAS_ERR_INVALID, "%s: %d views of %dx%d are more than 2^31 - 256 pixels", who, C, width, height);
-    if (C > 0 && (!depth || !Ks)) return fail(c, SAS_ERR_INVALID, "%s: depth and Ks are required", who);
+    if (const int rc = check_depth_views(c, who, C, width, height, depth, Ks, transform, flags, false)) return rc;
     if (K > 0 && !index) return fail(c, SAS_ERR_INVALID, "%s: the index output is required", who);
     if (colors && !rgb8) return fail(c, SAS_ERR_INVALID, "%s: colors without rgb8", who);
     if (labels_out && !labels) return fail(c, SAS_ERR_INVALID, "%s: labels_out without labels", who);
@@ -1956,16 +2000,8 @@ int sas_sample_points(sas_ctx *c, int n_views, int width, int height, const floa
                 return fail(c, SAS_ERR_INVALID, "%s: a voxel grid of more than 2^24 cells (%d x %d x ...)", who, q.n[0], q.n[1]);
         }
     }
-    for (int v = 0; v < C; ++v) {
-        const float *Kv = Ks + 9 * v;
-        for (int k = 0; k < 9; ++k)
-            if (!std::isfinite(Kv[k])) return fail(c, SAS_ERR_INVALID, "%s: Ks[%d][%d] = %g is not finite", who, v, k, (double)Kv[k]);
-        if (!(Kv[0] > 0.0f) || !(Kv[4] > 0.0f)) return fail(c, SAS_ERR_INVALID, "%s: view %d: fx = %g, fy = %g must be > 0", who, v, (double)Kv[0], (double)Kv[4]);
-        for (int k = 0; transform && k < 12; ++k)
-            if (!std::isfinite(transform[12 * v + k]))
-                return fail(c, SAS_ERR_INVALID, "%s: transform[%d][%d] = %g is not finite", who, v, k, (double)transform[12 * v + k]);
-        if (cloud && (cloud[v] < 0 || cloud[v] >= E)) return fail(c, SAS_ERR_INVALID, "%s: cloud[%d] = %d out of [0,%d)", who, v, cloud[v], E);
-    }
+    for (int v = 0; cloud && v < C; ++v)
+        if (cloud[v] < 0 || cloud[v] >= E) return fail(c, SAS_ERR_INVALID, "%s: cloud[%d] = %d out of [0,%d)", who, v, cloud[v], E);
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;
     q.C = C; q.E = E; q.W = width; q.H = height; q.stride = stride; q.K = K;
@@ -1987,27 +2023,22 @@ int sas_sample_points(sas_ctx *c, int n_views, int width, int height, const floa
     for (int e = 0; e < E; ++e) { base[e] = first; first += views_of[e] * q.S; }
     for (int v = 0; v < C; ++v) {
         SasCloudView &V = view[v];
-        const float *Kv = Ks + 9 * v;
-        V.fx = Kv[0]; V.fy = Kv[4]; V.cx = Kv[2]; V.cy = Kv[5];
-        for (int k = 0; k < 3; ++k) {
-            for (int j = 0; j < 3; ++j) V.A[3 * k + j] = transform ? transform[12 * v + 4 * k + j] : (k == j ? 1.0f : 0.0f);
-            V.t[k] = transform ? transform[12 * v + 4 * k + 3] : 0.0f;
-        }
+        V.cam = pack_depth_view(Ks + 9 * (size_t)v, transform ? transform + 12 * (size_t)v : nullptr);
         V.cloud = cloud ? cloud[v] : 0;
         V.pad = 0;
         V.base = base[V.cloud];
     }
     const bool use_keep = keep && labels;
     if (use_keep) std::copy(keep, keep + 256, par.data() + off_keep);
-    int rc;
     const size_t rows = (size_t)std::max(q.n_rows, 1ll), blocks = (size_t)std::max(q.n_blocks, 1ll);
-    if ((rc = ensure(c, c->cloud_par, par.size()))) return rc;
-    if ((rc = ensure(c, c->cloud_grid, sizeof(unsigned) * (size_t)std::max(q.n_grid, 1ll)))) return rc;
-    if ((rc = ensure(c, c->cloud_cand, sizeof(float4) * rows))) return rc;
-    if ((rc = ensure(c, c->cloud_blk, sizeof(unsigned) * 2 * blocks))) return rc;
-    if ((rc = ensure(c, c->cloud_rows, sizeof(float4) * rows))) return rc;
-    if ((rc = ensure(c, c->cloud_dist, sizeof(float) * rows))) return rc;
-    if ((rc = ensure(c, c->cloud_count, sizeof(int) * (size_t)E))) return rc;
+    if (const int rc = ensure(c, {{c->cloud_par, par.size()},
+                                  {c->cloud_grid, sizeof(unsigned) * (size_t)std::max(q.n_grid, 1ll)},
+                                  {c->cloud_cand, sizeof(float4) * rows},
+                                  {c->cloud_blk, sizeof(unsigned) * 2 * blocks},
+                                  {c->cloud_rows, sizeof(float4) * rows},
+                                  {c->cloud_dist, sizeof(float) * rows},
+                                  {c->cloud_count, sizeof(int) * (size_t)E}}))
+        return rc;
     HIP_TRY(c, hipMemcpy(c->cloud_par.p, par.data(), par.size(), hipMemcpyHostToDevice));
     unsigned char *dpar = (unsigned char *)c->cloud_par.p;
     q.depth = depth; q.rgb8 = rgb8; q.labels = labels;
@@ -2032,9 +2063,7 @@ int sas_sample_points(sas_ctx *c, int n_views, int width, int height, const floa
             evh[k] = ev[k];
         }
     sas_launch_cloud(st, q, (flags & SAS_TIMING) ? evh : nullptr);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "point cloud: %s", hipGetErrorString(e));
+    if (const int rc = finish_launches(c, st, "point cloud")) return rc;
     if (flags & SAS_TIMING) {
         std::fill(c->stage_ms, c->stage_ms + SAS_T_COUNT, 0.0f);
         (void)hipEventElapsedTime(&c->stage_ms[SAS_T_PROJECT], evh[0], evh[1]);
@@ -2053,12 +2082,8 @@ int sas_fuse_depth(sas_ctx *c, int n_views, int width, int height, const float *
     if (!c) return SAS_ERR_INVALID;
     const char *who = "sas_fuse_depth";
     const int C = n_views;
-    if (flags & ~SAS_TIMING) return fail(c, SAS_ERR_INVALID, "%s: flags 0x%x not accepted (SAS_TIMING; blocking only)", who, flags);
     if (C < 0) return fail(c, SAS_ERR_INVALID, "%s: n_views %d is negative", who, C);
-    if (width <= 0 || height <= 0) return fail(c, SAS_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
-    const long long px_max = 0x7fffffffll - 256, px_view = (long long)height * width;   // (no product beyond 2^62)
-    if (px_view > px_max || (long long)C * px_view > px_max)
-        return fail(c, SAS_ERR_INVALID, "%s: %d views of %dx%d are more than 2^31 - 256 pixels", who, C, width, height);
+    if (const int rc = check_depth_views(c, who, C, width, height, depth, Ks, transform, flags, true)) return rc;
     if (!lo || !dims) return fail(c, SAS_ERR_INVALID, "%s: lo and dims are required", who);
     SasFuse q{};
     q.n_vox = 1;
@@ -2077,16 +2102,6 @@ int sas_fuse_depth(sas_ctx *c, int n_views, int width, int height, const float *
     if (keep && !labels) return fail(c, SAS_ERR_INVALID, "%s: keep without labels", who);
     if (color && !rgb8) return fail(c, SAS_ERR_INVALID, "%s: color without rgb8", who);
     if (!tsdf || !weight) return fail(c, SAS_ERR_INVALID, "%s: tsdf and weight are required", who);
-    if (C > 0 && (!depth || !Ks)) return fail(c, SAS_ERR_INVALID, "%s: depth and Ks are required", who);
-    for (int v = 0; v < C; ++v) {
-        const float *Kv = Ks + 9 * (size_t)v;
-        for (int k = 0; k < 9; ++k)
-            if (!std::isfinite(Kv[k])) return fail(c, SAS_ERR_INVALID, "%s: Ks[%d][%d] = %g is not finite", who, v, k, (double)Kv[k]);
-        if (!(Kv[0] > 0.0f) || !(Kv[4] > 0.0f)) return fail(c, SAS_ERR_INVALID, "%s: view %d: fx = %g, fy = %g must be > 0", who, v, (double)Kv[0], (double)Kv[4]);
-        for (int k = 0; transform && k < 12; ++k)
-            if (!std::isfinite(transform[12 * (size_t)v + k]))
-                return fail(c, SAS_ERR_INVALID, "%s: transform[%d][%d] = %g is not finite", who, v, k, (double)transform[12 * (size_t)v + k]);
-    }
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;
     if (C == 0) return SAS_OK;
@@ -2097,12 +2112,12 @@ int sas_fuse_depth(sas_ctx *c, int n_views, int width, int height, const float *
     // the per-view rows and the keep table: one host block, one copy per launch (one launch unless the call has more than
     // SAS_FUSE_MAX_ROWS views: then launches in view order, which is what the contract's view order asks for)
     const int rows_max = std::min(C, SAS_FUSE_MAX_ROWS);
-    const size_t off_keep = sizeof(SasFuseView) * (size_t)rows_max;
+    const size_t off_keep = sizeof(SasDepthView) * (size_t)rows_max;
     std::vector<unsigned char> par(off_keep + 256);
     if (keep) std::copy(keep, keep + 256, par.data() + off_keep);
     if (const int rc = ensure(c, c->fuse_par, par.size())) return rc;
     unsigned char *dpar = (unsigned char *)c->fuse_par.p;
-    q.view = reinterpret_cast<const SasFuseView *>(dpar);
+    q.view = reinterpret_cast<const SasDepthView *>(dpar);
     q.keep = keep ? dpar + off_keep : nullptr;
     hipStream_t st = (hipStream_t)stream;
     Event ev[2];
@@ -2113,17 +2128,9 @@ int sas_fuse_depth(sas_ctx *c, int n_views, int width, int height, const float *
     const size_t px = (size_t)width * (size_t)height;
     for (int v0 = 0; v0 < C; v0 += rows_max) {
         const int n = std::min(rows_max, C - v0);
-        SasFuseView *view = reinterpret_cast<SasFuseView *>(par.data());
-        for (int r = 0; r < n; ++r) {
-            const int v = v0 + r;
-            SasFuseView &V = view[r];
-            const float *Kv = Ks + 9 * (size_t)v;
-            V.fx = Kv[0]; V.cx = Kv[2]; V.fy = Kv[4]; V.cy = Kv[5];
-            for (int k = 0; k < 3; ++k) {
-                for (int j = 0; j < 3; ++j) V.A[3 * k + j] = transform ? transform[12 * (size_t)v + 4 * k + j] : (k == j ? 1.0f : 0.0f);
-                V.t[k] = transform ? transform[12 * (size_t)v + 4 * k + 3] : 0.0f;
-            }
-        }
+        SasDepthView *view = reinterpret_cast<SasDepthView *>(par.data());
+        for (int r = 0; r < n; ++r)
+            view[r] = pack_depth_view(Ks + 9 * (size_t)(v0 + r), transform ? transform + 12 * (size_t)(v0 + r) : nullptr);
         // (the block is the call's own: the launch before this one, if any, has been waited for)
         HIP_TRY(c, hipMemcpy(dpar, par.data(), par.size(), hipMemcpyHostToDevice));
         q.C = q.n_rows = n;
@@ -2132,10 +2139,8 @@ int sas_fuse_depth(sas_ctx *c, int n_views, int width, int height, const float *
         q.rgb8 = rgb8 ? rgb8 + 3 * (size_t)v0 * px : nullptr;
         q.labels = labels ? labels + (size_t)v0 * px : nullptr;
         sas_launch_fuse(st, q);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess && v0 + n == C && (flags & SAS_TIMING)) e = hipEventRecord(ev[1], st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(c, SAS_ERR_HIP, "depth fusion: %s", hipGetErrorString(e));
+        // (SAS_TIMING: the closing stamp goes behind the last launch, in front of its wait)
+        if (const int rc = finish_launches(c, st, "depth fusion", v0 + n == C && (flags & SAS_TIMING) ? (hipEvent_t)ev[1] : nullptr)) return rc;
     }
     if (flags & SAS_TIMING) {
         std::fill(c->stage_ms, c->stage_ms + SAS_T_COUNT, 0.0f);
@@ -2638,9 +2643,7 @@ int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *gr
     const int coeff_floats = sas_coeff_floats(sc.sh_degree), planes = sas_colour_planes(sc.sh_degree);
     const size_t n = (size_t)sc.n, nb = (n + 255) / 256;
     int rc;
-    if ((rc = ensure(c, c->density_inv, sizeof(int) * n)) || (rc = ensure(c, c->density_cls, n)) ||
-        (rc = ensure(c, c->density_blk, sizeof(unsigned) * (6 * nb + 4))))
-        return rc;
+    if ((rc = ensure(c, {{c->density_inv, sizeof(int) * n}, {c->density_cls, n}, {c->density_blk, sizeof(unsigned) * (6 * nb + 4)}}))) return rc;
     SasDensity q{};
     q.g0 = sc.g0; q.g1 = sc.g1; q.g2 = sc.g2; q.col = sc.col; q.gid8 = sc.gid8; q.perm = sc.perm;
     q.inv = (int *)c->density_inv.p;
@@ -2679,9 +2682,7 @@ int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *gr
     // the new scene in the caller's order
     const size_t m = (size_t)pl.n_new;
     DevBuf a_means, a_q, a_s, a_cov, a_op, a_col, a_gid, a_par;
-    if ((rc = ensure(c, a_means, sizeof(float) * 3 * m)) || (rc = ensure(c, a_op, sizeof(float) * m)) ||
-        (rc = ensure(c, a_col, sizeof(float) * (size_t)coeff_floats * m)))
-        return rc;
+    if ((rc = ensure(c, {{a_means, sizeof(float) * 3 * m}, {a_op, sizeof(float) * m}, {a_col, sizeof(float) * (size_t)coeff_floats * m}}))) return rc;
     if (sc.cov_mode ? (rc = ensure(c, a_cov, sizeof(float) * 6 * m)) : ((rc = ensure(c, a_q, sizeof(float) * 4 * m)) || (rc = ensure(c, a_s, sizeof(float) * 3 * m)))) return rc;
     if (sc.n_groups > 0 && (rc = ensure(c, a_gid, m))) return rc;
     if (!parents_out && (rc = ensure(c, a_par, sizeof(int) * m))) return rc;
@@ -2861,29 +2862,26 @@ int sas_frames_completed(sas_ctx *c, int64_t *submitted, int64_t *completed)
 }
 
 #ifdef SAS_DEBUG_BOUNDS
-extern "C" int sas_debug_bounds_kernels(unsigned long long *out, int reset);
-extern "C" int sas_debug_bounds_tiles(unsigned long long *out, int reset);
-extern "C" int sas_debug_bounds_mesh(unsigned long long *out, int reset);
-extern "C" int sas_debug_bounds_query(unsigned long long *out, int reset);
-extern "C" int sas_debug_bounds_match(unsigned long long *out, int reset);
-extern "C" int sas_debug_bounds_cloud(unsigned long long *out, int reset);
-extern "C" int sas_debug_bounds_fuse(unsigned long long *out, int reset);
-extern "C" int sas_debug_bounds_grad(unsigned long long *out, int reset);
-extern "C" int sas_debug_bounds_fit(unsigned long long *out, int reset);
-extern "C" int sas_debug_bounds_loss(unsigned long long *out, int reset);
-extern "C" int sas_debug_bounds_density(unsigned long long *out, int reset);
+// every kernel file's counter (SAS_BOUNDS_ACCESSOR in sas_device.h): one line per file, in the order their reports are looked at
+#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density)
+#define SAS_BOUNDS_DECLARE(name) extern "C" int sas_debug_bounds_##name(unsigned long long *out, int reset);
+#define SAS_BOUNDS_ENTRY(name) sas_debug_bounds_##name,
+SAS_BOUNDS_FILES(SAS_BOUNDS_DECLARE)
 /* Bounds-checked build only: out[0] = guarded accesses found out of range since the last reset (they were
- * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none). */
+ * skipped, not executed), out[1..3] = code, index and limit of the first one (0 if none): the first file's that has a report. */
 int sas_debug_bounds(unsigned long long *out, int reset)
 {
-    unsigned long long a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, p[4] = {0, 0, 0, 0}, s[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0}, l[4] = {0, 0, 0, 0}, d[4] = {0, 0, 0, 0};
-    if (hipDeviceSynchronize() != hipSuccess || sas_debug_bounds_kernels(a, reset) || sas_debug_bounds_tiles(b, reset) ||
-        sas_debug_bounds_mesh(m, reset) || sas_debug_bounds_query(q, reset) || sas_debug_bounds_match(p, reset) ||
-        sas_debug_bounds_cloud(s, reset) || sas_debug_bounds_fuse(f, reset) || sas_debug_bounds_grad(g, reset) || sas_debug_bounds_fit(t, reset) || sas_debug_bounds_loss(l, reset) || sas_debug_bounds_density(d, reset))
-        return SAS_ERR_HIP;
-    const unsigned long long *first = a[0] ? a : (b[0] ? b : (m[0] ? m : (q[0] ? q : (p[0] ? p : (s[0] ? s : (f[0] ? f : (g[0] ? g : (t[0] ? t : (l[0] ? l : d)))))))));
-    out[0] = a[0] + b[0] + m[0] + q[0] + p[0] + s[0] + f[0] + g[0] + t[0] + l[0] + d[0];
-    out[1] = first[1]; out[2] = first[2]; out[3] = first[3];
+    int (*const files[])(unsigned long long *, int) = {SAS_BOUNDS_FILES(SAS_BOUNDS_ENTRY)};
+    if (hipDeviceSynchronize() != hipSuccess) return SAS_ERR_HIP;
+    unsigned long long sum = 0, first[4] = {0, 0, 0, 0};
+    for (const auto file : files) {
+        unsigned long long w[4] = {0, 0, 0, 0};
+        if (file(w, reset)) return SAS_ERR_HIP;
+        if (w[0] && !first[0]) std::copy(w, w + 4, first);
+        sum += w[0];
+    }
+    out[0] = sum;
+    std::copy(first + 1, first + 4, out + 1);
     return SAS_OK;
 }
 #endif

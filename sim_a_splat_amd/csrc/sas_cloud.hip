@@ -55,10 +55,10 @@ __global__ __launch_bounds__(kCloudThreads) void k_cloud_mark(SasCloud q)
     const float d = q.depth[p];
     bool ok = d > 0.0f && d < INFINITY;
     if (ok && q.labels && q.keep) ok = q.keep[q.labels[p]] != 0;
-    const float x = ((float)u - V.cx) * d / V.fx, y = ((float)v - V.cy) * d / V.fy, z = d;
-    const float w0 = ((V.A[0] * x + V.A[1] * y) + V.A[2] * z) + V.t[0];
-    const float w1 = ((V.A[3] * x + V.A[4] * y) + V.A[5] * z) + V.t[1];
-    const float w2 = ((V.A[6] * x + V.A[7] * y) + V.A[8] * z) + V.t[2];
+    const float x = ((float)u - V.cam.cx) * d / V.cam.fx, y = ((float)v - V.cam.cy) * d / V.cam.fy, z = d;
+    const float w0 = sas_affine_row<0>(V.cam, x, y, z);
+    const float w1 = sas_affine_row<1>(V.cam, x, y, z);
+    const float w2 = sas_affine_row<2>(V.cam, x, y, z);
     ok = ok && finite_f(w0) && finite_f(w1) && finite_f(w2);
     if (q.has_bounds)
         ok = ok && q.lo[0] <= w0 && w0 <= q.hi[0] && q.lo[1] <= w1 && w1 <= q.hi[1] && q.lo[2] <= w2 && w2 <= q.hi[2];

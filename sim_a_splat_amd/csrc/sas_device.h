@@ -140,6 +140,16 @@ DEV float dot3(float a0, float a1, float a2, float b0, float b1, float b2)
 {
     return fma_(a2, b2, fma_(a1, b1, a0 * b0));
 }
+// Row R of A p + t, p = (x, y, z), for the calls that need no scene; nothing fused: the association order is part of their contract.
+// v: the record that holds the map as its member `m` (SasDepthView, SasMatch).  It takes the record and not the SasAffine because
+// k_fuse, handed a pointer into the middle of its view row, keeps a second base register in its view loop: two more scalar instructions
+// per view (tools/isa_gate.py).
+template <int R, class V>
+DEV float sas_affine_row(const V &v, float x, float y, float z)
+{
+    const SasAffine &m = v.m;
+    return ((m.A[3 * R] * x + m.A[3 * R + 1] * y) + m.A[3 * R + 2] * z) + m.t[R];
+}
 // p moved by the 3x4 row block G = [R | t] (a group pose), in place
 DEV void pose_point(const float *G, float *p)
 {

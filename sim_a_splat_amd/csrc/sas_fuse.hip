@@ -5,7 +5,7 @@
 //   k_fuse   one lane per voxel, flat index g = (k ny + j) nx + i along x: a wave reads and writes 256 contiguous bytes of tsdf and of
 //            weight, and neighbouring lanes gather neighbouring pixels.  The lane reads its voxel once, walks the views in ascending
 //            order with the voxel in registers, and writes it once -- only if some view updated it: a volume outside every frustum
-//            costs one read.  The view's row {fx, cx, fy, cy, A|t} is indexed by the loop counter alone: wave-uniform loads.
+//            costs one read.  The view's row {fx, fy, cx, cy, A|t} is indexed by the loop counter alone: wave-uniform loads.
 // No LDS, no atomics, no wait between workgroups: a voxel's result depends on its own pixels only.
 // Arithmetic: IEEE binary32, nothing fused (-ffp-contract=off, no fma_).
 #include "sas_device.h"
@@ -34,11 +34,11 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse(SasFuse q)
     bool updated = false, coloured = false;
     for (int c = 0; c < q.C; ++c) {
         if (!SAS_IN(c, q.n_rows, 703)) break;   // (uniform)
-        const SasFuseView &V = q.view[c];
-        const float qz = ((V.A[6] * px + V.A[7] * py) + V.A[8] * pz) + V.t[2];
+        const SasDepthView &V = q.view[c];
+        const float qz = sas_affine_row<2>(V, px, py, pz);
         if (!(qz >= q.near_z)) continue;
-        const float qx = ((V.A[0] * px + V.A[1] * py) + V.A[2] * pz) + V.t[0];
-        const float qy = ((V.A[3] * px + V.A[4] * py) + V.A[5] * pz) + V.t[1];
+        const float qx = sas_affine_row<0>(V, px, py, pz);
+        const float qy = sas_affine_row<1>(V, px, py, pz);
         float uf = ((V.fx * (qx / qz)) + V.cx) - q.pixel_centre;
         float vf = ((V.fy * (qy / qz)) + V.cy) - q.pixel_centre;
         uf = uf + 0.5f;

@@ -1,6 +1,7 @@
 // Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #define SAS_TILE 16
@@ -401,6 +402,17 @@ struct SasQuery {
 // count <- 0, the box pass (culled pairs read +inf / 0), the evaluation of the candidates
 void sas_launch_query(hipStream_t st, const SasQuery &q);
 
+// The 3x4 map A|t of the calls that need no scene, and a depth frame's view: its intrinsics and the map between the camera and the
+// call's frame.  sas_affine_row (sas_device.h) is the one spelling of A p + t; it finds the map as the member `m` of its record.
+struct SasAffine {
+    float A[9], t[3];
+};
+struct SasDepthView {
+    float fx, fy, cx, cy;
+    SasAffine m;
+};
+static_assert(sizeof(SasDepthView) == 64, "a view's row is one 64-byte line");
+
 // Point matching (sas_match_points; DESIGN.md 3, "Point matching").  All three kernels take the whole call by value.
 #define SAS_MATCH_CHUNK 256     // targets k_match_slice stages in LDS at a time (4 KiB)
 #define SAS_MATCH_MOMENTS 18    // n, sum p' (3), sum q (3), sum q p'^T (9, row-major), sum |p'|^2, sum d2
@@ -416,7 +428,7 @@ struct SasMatch {
     long long n_blocks;         // ceil(n_source / 256)
     long long slice_targets;    // targets per slice, a multiple of SAS_MATCH_CHUNK
     int slices;                 // slices * slice_targets >= n_target
-    float A[9], t[3];           // p' = A p + t
+    SasAffine m;                // p' = A p + t
     float md2;                  // max_distance^2 in float32 (INFINITY: every match holds)
 };
 // keys <- slice minima, index / dist2 / partial <- the merge, moments <- the partial rows in workgroup order
@@ -426,11 +438,11 @@ void sas_launch_match(hipStream_t st, const SasMatch &m);
 // rows live in one device block beside the keep table.
 #define SAS_CLOUD_RESIDENT 16384   // survivors k_cloud_fps keeps in registers: 16 per lane of its 1024 (4 registers each; 128 are a lane's share)
 struct SasCloudView {
-    float fx, fy, cx, cy;
-    float A[9], t[3];      // camera -> output frame
+    SasDepthView cam;      // cam.m: camera -> output frame
     int cloud, pad;
     long long base;        // first row of its cloud in rows / dist (SasCloud::cloud_base[cloud])
 };
+static_assert(sizeof(SasCloudView) == 80 && offsetof(SasCloudView, cloud) == 64, "the view's row, then its cloud");
 struct SasCloud {
     const float *depth;         // [C,H,W]
     const uint8_t *rgb8;        // [C,H,W,3] or nullptr
@@ -467,15 +479,11 @@ void sas_launch_cloud(hipStream_t st, const SasCloud &q, hipEvent_t *ev);
 // device block beside the keep table.
 #define SAS_FUSE_THREADS 256      // voxels per workgroup of k_fuse
 #define SAS_FUSE_MAX_ROWS 4096    // per-view rows of one launch: a call of more views is served by launches in view order
-struct SasFuseView {
-    float fx, cx, fy, cy;
-    float A[9], t[3];           // volume frame -> camera
-};
 struct SasFuse {
     const float *depth;         // [C,H,W], the first view of this launch
     const uint8_t *rgb8;        // [C,H,W,3] or nullptr
     const uint8_t *labels;      // [C,H,W] or nullptr
-    const SasFuseView *view;    // [C] device
+    const SasDepthView *view;   // [C] device; m: volume frame -> camera
     const uint8_t *keep;        // [256] device, or nullptr (non-null only with labels)
     float *tsdf, *weight;       // [nz,ny,nx]
     float *color;               // [nz,ny,nx,3] or nullptr (non-null only with rgb8)

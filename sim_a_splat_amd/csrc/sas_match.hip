@@ -23,13 +23,13 @@ constexpr int kMatchThreads = 256;
 static_assert(SAS_MATCH_CHUNK == kMatchThreads, "every thread of k_match_slice stages one target of a chunk");
 constexpr unsigned long long kNoMatch = (0x7f800000ull << 32) | 0xffffffffull;   // d2 = +inf: above the key of every match
 
-// p' = A p + t, each component ((A_k0 x + A_k1 y) + A_k2 z) + t_k
+// p' = A p + t (sas_affine_row)
 DEV void move_source(const SasMatch &m, long long i, float &px, float &py, float &pz)
 {
     const float x = m.source[3 * i], y = m.source[3 * i + 1], z = m.source[3 * i + 2];
-    px = ((m.A[0] * x + m.A[1] * y) + m.A[2] * z) + m.t[0];
-    py = ((m.A[3] * x + m.A[4] * y) + m.A[5] * z) + m.t[1];
-    pz = ((m.A[6] * x + m.A[7] * y) + m.A[8] * z) + m.t[2];
+    px = sas_affine_row<0>(m, x, y, z);
+    py = sas_affine_row<1>(m, x, y, z);
+    pz = sas_affine_row<2>(m, x, y, z);
 }
 
 __global__ __launch_bounds__(kMatchThreads) void k_match_slice(SasMatch m)

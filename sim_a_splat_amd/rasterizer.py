@@ -31,6 +31,13 @@ def _wait_for(*inputs) -> None:
             torch.cuda.synchronize(a.device)
 
 
+def _addr(a):
+    """The address of a device tensor or a NumPy array for the C ABI; None for None and for an empty one."""
+    if isinstance(a, torch.Tensor):
+        return a.data_ptr() if a.numel() else None
+    return a.ctypes.data if a is not None and a.size else None
+
+
 def _as_f32(a: ArrayLike, shape: Tuple[int, ...], name: str):
     """Return (keepalive, pointer) of a contiguous float32 array with the given shape."""
     if isinstance(a, torch.Tensor):
@@ -62,22 +69,28 @@ LIFT_ONE = _capi.SAS_LIFT_ONE   # 2**32: the fixed-point unit of lift_labels' vo
 LIFT_FEATURE_ONE = _capi.SAS_LIFT_FEATURE_ONE   # 2**24: the fixed-point unit of lift_features' weights
 
 
+def _views_and_frame(viewmats, frame):
+    """``viewmats [C,4,4]`` and ``frame`` (4x4, or None) as float64 arrays; ValueError on a wrong shape."""
+    V = np.asarray(_host(viewmats), dtype=np.float64)
+    if V.ndim != 3 or V.shape[1:] != (4, 4):
+        raise ValueError(f"viewmats must be [C,4,4], got {list(V.shape)}")
+    F = None if frame is None else np.asarray(_host(frame), dtype=np.float64)
+    if F is not None and F.shape != (4, 4):
+        raise ValueError(f"frame must be 4x4, got {list(F.shape)}")
+    return V, F
+
+
 def cloud_transforms(viewmats, frame=None) -> np.ndarray:
     """Camera-to-output-frame maps of ``sample_point_cloud``: ``[C,12]`` float32 rows ``A|t``, the rigid inverse of every world-to-camera
     ``viewmats [C,4,4]`` (``R^T | -R^T t``, in float64) with ``frame`` (4x4, world to output frame; any affine map) multiplied on from
     the left, rounded to float32 once.  ValueError on a wrong shape."""
-    V = np.asarray(_host(viewmats), dtype=np.float64)
-    if V.ndim != 3 or V.shape[1:] != (4, 4):
-        raise ValueError(f"viewmats must be [C,4,4], got {list(V.shape)}")
+    V, F = _views_and_frame(viewmats, frame)
     inv = np.zeros_like(V)
     Rt = np.transpose(V[:, :3, :3], (0, 2, 1))
     inv[:, :3, :3] = Rt
     inv[:, :3, 3] = -np.einsum("cij,cj->ci", Rt, V[:, :3, 3])
     inv[:, 3, 3] = 1.0
-    if frame is not None:
-        F = np.asarray(_host(frame), dtype=np.float64)
-        if F.shape != (4, 4):
-            raise ValueError(f"frame must be 4x4, got {list(F.shape)}")
+    if F is not None:
         inv = F[None] @ inv
     return np.ascontiguousarray(inv[:, :3, :].reshape(-1, 12).astype(np.float32))
 
@@ -86,13 +99,8 @@ def fuse_transforms(viewmats, frame=None) -> np.ndarray:
     """Volume-frame-to-camera maps of ``fuse_depth``: ``[C,12]`` float32 rows ``A|t``, every world-to-camera ``viewmats [C,4,4]`` with
     the inverse of ``frame`` (4x4, world to volume frame; any invertible affine map -- ``cloud_transforms``' argument) multiplied on
     from the right, ``viewmat @ inv(frame)`` in float64, rounded to float32 once.  ValueError on a wrong shape."""
-    V = np.asarray(_host(viewmats), dtype=np.float64)
-    if V.ndim != 3 or V.shape[1:] != (4, 4):
-        raise ValueError(f"viewmats must be [C,4,4], got {list(V.shape)}")
-    if frame is not None:
-        F = np.asarray(_host(frame), dtype=np.float64)
-        if F.shape != (4, 4):
-            raise ValueError(f"frame must be 4x4, got {list(F.shape)}")
+    V, F = _views_and_frame(viewmats, frame)
+    if F is not None:
         V = V @ np.linalg.inv(F)[None]
     return np.ascontiguousarray(V[:, :3, :].reshape(-1, 12).astype(np.float32))
 
@@ -472,6 +480,27 @@ class Rasterizer:
             raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
         return t
 
+    def _depth_views(self, C: int, W: int, H: int, depth, Ks, rgb8, labels, keep_labels):
+        """What ``sample_point_cloud`` and ``fuse_depth`` make of their views' inputs: ``Ks [C,3,3]`` as 9 C float32 on the host, the keep
+        table of ``keep_labels`` (which need ``labels``), and ``depth``, ``rgb8``, ``labels`` on the device (None stays None)."""
+        Kc = np.ascontiguousarray(np.asarray(_host(Ks), dtype=np.float32)).reshape(-1)
+        if Kc.size != 9 * C:
+            raise ValueError(f"Ks must be [{C},3,3], got {Kc.size} values")
+        if keep_labels is not None and labels is None:
+            raise ValueError("keep_labels needs labels")
+        keep = cloud_keep_table(keep_labels)
+        d = self._device_image(depth, torch.float32, C * H * W, "depth", (C, H, W))
+        c8 = None if rgb8 is None else self._device_image(rgb8, torch.uint8, 3 * C * H * W, "rgb8", (C, H, W, 3))
+        lab = None if labels is None else self._device_image(labels, torch.uint8, C * H * W, "labels", (C, H, W))
+        return Kc, keep, d, c8, lab
+
+    def _blocking_call(self, entry: str, *args) -> None:
+        """C-ABI ``entry(ctx, *args, stream)``, blocking, on the caller's stream: it runs behind what the stream holds (``_device_image``'s copies)."""
+        rc = getattr(self._L, entry)(self._ctx, *args, self._stream())
+        if rc != 0:
+            self._check(rc, entry)
+        self._in_flight(True)
+
     @_locked
     def sample_point_cloud(self, depth: ArrayLike, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int, n_points: int, *,
                            rgb8: Optional[ArrayLike] = None, labels: Optional[ArrayLike] = None, keep_labels=None, bounds=None,
@@ -492,23 +521,15 @@ class Rasterizer:
         (project: marking, scatter: compaction, blend: sampling)."""
         T = cloud_transforms(viewmats, frame)
         C, W, H, K, E = T.shape[0], int(width), int(height), int(n_points), int(n_clouds)
-        Kc = np.ascontiguousarray(np.asarray(_host(Ks), dtype=np.float32)).reshape(-1)
-        if Kc.size != 9 * C:
-            raise ValueError(f"Ks must be [{C},3,3], got {Kc.size} values")
         if K < 0 or E < 1 or W < 0 or H < 0:
             raise ValueError(f"sample_point_cloud: n_points {K}, n_clouds {E}, size {W}x{H}")
-        if keep_labels is not None and labels is None:
-            raise ValueError("keep_labels needs labels")
-        keep = cloud_keep_table(keep_labels)
+        Kc, keep, d, c8, lab = self._depth_views(C, W, H, depth, Ks, rgb8, labels, keep_labels)
         b = cloud_bounds(bounds)
         cl = None
         if clouds is not None:
             cl = np.ascontiguousarray(np.asarray(clouds, dtype=np.int32).reshape(-1))
             if cl.shape[0] != C:
                 raise ValueError(f"clouds must name one cloud per view ({C}), got {cl.shape[0]}")
-        d = self._device_image(depth, torch.float32, C * H * W, "depth", (C, H, W))
-        c8 = None if rgb8 is None else self._device_image(rgb8, torch.uint8, 3 * C * H * W, "rgb8", (C, H, W, 3))
-        lab = None if labels is None else self._device_image(labels, torch.uint8, C * H * W, "labels", (C, H, W))
         dev = self.device
         res = {"points": torch.empty((E, K, 3), dtype=torch.float32, device=dev), "index": torch.empty((E, K), dtype=torch.int32, device=dev),
                "count": torch.empty((E,), dtype=torch.int32, device=dev)}
@@ -516,15 +537,9 @@ class Rasterizer:
             res["colors"] = torch.empty((E, K, 3), dtype=torch.uint8, device=dev)
         if lab is not None:
             res["labels"] = torch.empty((E, K), dtype=torch.uint8, device=dev)
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
-        host = lambda a: a.ctypes.data if a is not None and a.size else None
-        stream = self._stream()   # (the call runs behind what this stream holds: the copies above)
-        rc = self._L.sas_sample_points(self._ctx, C, W, H, ptr(d), ptr(c8), ptr(lab), host(Kc), host(T), host(cl), E, host(keep), host(b),
-                                       float(voxel_size), int(stride), K, _capi.SAS_TIMING if timing else 0, ptr(res["points"]),
-                                       ptr(res["index"]), ptr(res.get("colors")), ptr(res.get("labels")), res["count"].data_ptr(), stream)
-        if rc != 0:
-            self._check(rc, "sas_sample_points")
-        self._in_flight(True)
+        self._blocking_call("sas_sample_points", C, W, H, _addr(d), _addr(c8), _addr(lab), _addr(Kc), _addr(T), _addr(cl), E, _addr(keep), _addr(b),
+                            float(voxel_size), int(stride), K, _capi.SAS_TIMING if timing else 0, _addr(res["points"]), _addr(res["index"]),
+                            _addr(res.get("colors")), _addr(res.get("labels")), res["count"].data_ptr())
         return res
 
     @_locked
@@ -545,14 +560,9 @@ class Rasterizer:
         ``timing``: ``stage_times()`` then holds the call's kernel (blend, total)."""
         T = fuse_transforms(viewmats, frame)
         C, W, H = T.shape[0], int(width), int(height)
-        Kc = np.ascontiguousarray(np.asarray(_host(Ks), dtype=np.float32)).reshape(-1)
-        if Kc.size != 9 * C:
-            raise ValueError(f"Ks must be [{C},3,3], got {Kc.size} values")
         if W < 0 or H < 0:
             raise ValueError(f"fuse_depth: size {W}x{H}")
-        if keep_labels is not None and labels is None:
-            raise ValueError("keep_labels needs labels")
-        keep = cloud_keep_table(keep_labels)
+        Kc, keep, d, c8, lab = self._depth_views(C, W, H, depth, Ks, rgb8, labels, keep_labels)
         nx, ny, nz = (int(n) for n in volume.dims)
         for name, t, shape in (("tsdf", volume.tsdf, (nz, ny, nx)), ("weight", volume.weight, (nz, ny, nx)), ("color", volume.color, (nz, ny, nx, 3))):
             if t is None and name == "color":
@@ -569,21 +579,11 @@ class Rasterizer:
                 A = A @ np.linalg.inv(np.asarray(_host(frame), dtype=np.float64))[:3, :3]
             scale = float(np.cbrt(abs(np.linalg.det(A))))
         tr = (4.0 * voxel if trunc is None else float(trunc)) * scale
-        d = self._device_image(depth, torch.float32, C * H * W, "depth", (C, H, W))
-        c8 = None if rgb8 is None else self._device_image(rgb8, torch.uint8, 3 * C * H * W, "rgb8", (C, H, W, 3))
-        lab = None if labels is None else self._device_image(labels, torch.uint8, C * H * W, "labels", (C, H, W))
         lo = np.ascontiguousarray(np.asarray(_host(volume.lo), dtype=np.float32).reshape(3))
         dims = np.array([nx, ny, nz], np.int32)
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
-        host = lambda a: a.ctypes.data if a is not None and a.size else None
-        stream = self._stream()   # (the call runs behind what this stream holds: the copies above)
-        rc = self._L.sas_fuse_depth(self._ctx, C, W, H, ptr(d), ptr(c8), ptr(lab), host(Kc), host(T), host(keep), lo.ctypes.data, voxel,
-                                    dims.ctypes.data, tr, float(near), float(pixel_centre), float(max_weight),
-                                    _capi.SAS_TIMING if timing else 0, ptr(volume.tsdf), ptr(volume.weight),
-                                    ptr(volume.color) if c8 is not None else None, stream)
-        if rc != 0:
-            self._check(rc, "sas_fuse_depth")
-        self._in_flight(True)
+        self._blocking_call("sas_fuse_depth", C, W, H, _addr(d), _addr(c8), _addr(lab), _addr(Kc), _addr(T), _addr(keep), lo.ctypes.data, voxel,
+                            dims.ctypes.data, tr, float(near), float(pixel_centre), float(max_weight), _capi.SAS_TIMING if timing else 0,
+                            _addr(volume.tsdf), _addr(volume.weight), _addr(volume.color) if c8 is not None else None)
 
     @_locked
     def set_group_poses(self, Rt: ArrayLike) -> None:
@@ -1063,21 +1063,20 @@ class Rasterizer:
             elif not self._is_mine(t, torch.float32, shape):
                 raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor {shape} on {self.device}")
             res[name] = t
-        ptr = lambda t: t.data_ptr() if t is not None else None
         flags, stream = _flags(True, fast_exp=fast_exp), self._stream()
         if screen_space:
-            rc = self._L.sas_render_backward_screen(self._ctx, pV, pK, W, H, flags, ptr(gr), ptr(ga), ptr(gd), ptr(res.get("means2d")),
-                                                    ptr(res.get("conics")), ptr(res.get("opacities")), ptr(res.get("colors")), ptr(res.get("depths")), stream)
+            rc = self._L.sas_render_backward_screen(self._ctx, pV, pK, W, H, flags, _addr(gr), _addr(ga), _addr(gd), _addr(res.get("means2d")),
+                                                    _addr(res.get("conics")), _addr(res.get("opacities")), _addr(res.get("colors")), _addr(res.get("depths")), stream)
         elif sel is not None:
             with_poses = "group_poses" in res   # (left out through ``want``: the plain call)
-            rc = self._L.sas_render_backward_poses(self._ctx, pV, pK, W, H, flags, ptr(gr), ptr(ga), ptr(gd), ptr(res.get("means")),
-                                                   ptr(res.get("opacities")), ptr(res.get("colors")), ptr(res.get("quats")), ptr(res.get("scales")),
-                                                   ptr(res.get("covariances")), ptr(res.get("viewmat")), len(sel) if with_poses else 0,
-                                                   sel.ctypes.data if with_poses else None, ptr(res.get("group_poses")), stream)
+            rc = self._L.sas_render_backward_poses(self._ctx, pV, pK, W, H, flags, _addr(gr), _addr(ga), _addr(gd), _addr(res.get("means")),
+                                                   _addr(res.get("opacities")), _addr(res.get("colors")), _addr(res.get("quats")), _addr(res.get("scales")),
+                                                   _addr(res.get("covariances")), _addr(res.get("viewmat")), len(sel) if with_poses else 0,
+                                                   sel.ctypes.data if with_poses else None, _addr(res.get("group_poses")), stream)
         else:
-            rc = self._L.sas_render_backward(self._ctx, pV, pK, W, H, flags, ptr(gr), ptr(ga), ptr(gd), ptr(res.get("means")), ptr(res.get("opacities")),
-                                             ptr(res.get("colors")), ptr(res.get("quats")), ptr(res.get("scales")), ptr(res.get("covariances")),
-                                             ptr(res.get("viewmat")), stream)
+            rc = self._L.sas_render_backward(self._ctx, pV, pK, W, H, flags, _addr(gr), _addr(ga), _addr(gd), _addr(res.get("means")), _addr(res.get("opacities")),
+                                             _addr(res.get("colors")), _addr(res.get("quats")), _addr(res.get("scales")), _addr(res.get("covariances")),
+                                             _addr(res.get("viewmat")), stream)
         if rc != 0:
             self._check(rc, "sas_render_backward_screen" if screen_space else "sas_render_backward_poses" if sel is not None else "sas_render_backward")
         self._in_flight(True)
@@ -1246,9 +1245,8 @@ class Rasterizer:
             raise ValueError("g_alpha belongs to the prechained form: pass the frame's alpha")
         for k in grads:
             res[k] = torch.empty((H, W, 3) if k == "g_rgb" else (H, W), dtype=torch.float32, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        rc = self._L.sas_photometric_loss(self._ctx, W, H, x.data_ptr(), y.data_ptr(), ptr(m), ptr(a), pbg, lam, terms.data_ptr(),
-                                          ptr(res.get("g_rgb")), ptr(res.get("g_alpha")), self._stream())
+        rc = self._L.sas_photometric_loss(self._ctx, W, H, x.data_ptr(), y.data_ptr(), _addr(m), _addr(a), pbg, lam, terms.data_ptr(),
+                                          _addr(res.get("g_rgb")), _addr(res.get("g_alpha")), self._stream())
         if rc != 0:
             self._check(rc, "sas_photometric_loss")
         return res

@@ -124,7 +124,14 @@ def test_extractors_read_the_committed_outputs():
         == {"render_us": 19.81, "bare_us": 18.33, "py_us": pytest.approx(1.48)}
     assert extract["host_overhead"](stray + "n=1000: host enqueue 23.2 us/frame, end-to-end 141.0 us/frame\n") \
         == {"enqueue_us": 23.2, "end_to_end_us": 141.0}
-    for probe in ("stage3", "bench", "config_fps", "door_b", "vec_env", "demo_env", "py_overhead", "host_overhead"):
+    # the calls that need no scene: every call median the probe prints, and nothing but what the row declares
+    for probe, name, want in (("cloud", "point_cloud.txt", {"cloud1_512": 3.650, "cloud1_1024": 7.187, "cloud1_4096": 28.642, "cloud16_512": 3.879,
+                                                            "cloud16_1024": 7.475, "cloud16_4096": 29.118}),
+                              ("fuse", "tsdf_fuse.txt", {"fuse2_128": 0.078, "fuse2_256": 0.202, "fuse32_128": 0.319, "fuse32_256": 1.807}),
+                              ("match", "match_points.txt", {"match113831": 0.764, "match292247": 1.871})):
+        assert extract[probe](stray + (PROFILES / name).read_text()) == want
+        assert set(ab.PROBES[probe][3]) == set(want) and not any(ab.PROBES[probe][3].values())   # (all lower-is-better)
+    for probe in ("stage3", "bench", "config_fps", "door_b", "vec_env", "demo_env", "py_overhead", "host_overhead", "cloud", "fuse", "match"):
         with pytest.raises(Exception):   # a probe that died: the libdrm line and a traceback
             ab.declared(probe)(stray + "Traceback (most recent call last):\n")
 

@@ -8,6 +8,7 @@ measured.  Every test fails without the feature: the entry point and the methods
 bounds-checked build, and its last test reads that build's counter.
 """
 import ctypes
+import re
 import sys
 from pathlib import Path
 
@@ -26,6 +27,8 @@ import fuse_ref as fr  # noqa: E402
 pytestmark = pytest.mark.gpu
 NAMES = ("tsdf", "weight", "color")
 WG = _capi.SAS_FUSE_THREADS
+# per-view rows of one launch (the C ABI does not export it: read where the library defines it)
+MAX_ROWS = int(re.search(r"#define SAS_FUSE_MAX_ROWS\s+(\d+)", (Path(__file__).resolve().parent.parent / "sim_a_splat_amd" / "csrc" / "sas_internal.h").read_text()).group(1))
 
 
 def _equal(what, got, want):
@@ -260,6 +263,22 @@ def test_determinism(rasterizer):
         init = (o["tsdf"], o["weight"], o["color"])
     assert all(a[k].tobytes() == x.tobytes() for k, x in zip(NAMES, init))
     print(f"  7 views at once, again from device inputs, and as 7 single-view calls: {sum(a[k].nbytes for k in NAMES)} bytes equal")
+
+
+def test_more_views_than_one_launch(rasterizer):
+    """SAS_FUSE_MAX_ROWS + 1 views: the call is served by two launches in view order, the second with the last view alone in rows packed
+    afresh.  From the reference alone: the last view changes tsdf and colour, so the bytes cannot be equal without the second launch."""
+    assert MAX_ROWS == 4096
+    C = MAX_ROWS + 1
+    c = fc.drawn(C, 4, 6, seed=77, dims=(5, 3, 3), voxel=0.02)
+    got, want, _ = _method(rasterizer, c)
+    n = _equal(f"{C} views", got, want)
+    V = c["viewmats"]
+    first = fr.fuse32(*fr.empty_volume(c["dims"]), c["depth"][:MAX_ROWS], c["Ks"][:MAX_ROWS], fuse_transforms(V[:MAX_ROWS]), c["lo"], c["voxel"],
+                      _camera_trunc(V, None, c["trunc"]), rgb8=c["rgb8"][:MAX_ROWS])
+    differ = {k: int((want[k].view(np.uint8).reshape(-1) != first[k].view(np.uint8).reshape(-1)).sum()) for k in NAMES}
+    print(f"  {C} views of 4x6 into 5x3x3 voxels: {int((want['weight'] > 0).sum())} touched, {n} bytes equal; view {C} alone changes {differ} bytes of fuse32")
+    assert differ["tsdf"] > 0 and differ["color"] > 0
 
 
 # ---- 5: errors -----------------------------------------------------------------------------------------------------------------------

@@ -47,13 +47,28 @@ def door_b(m):
     return {"door_b_steps": float(steps), **{f"door_b_{k}_ms": v for k, v in ast.literal_eval(stages).items()}}
 
 
+def sectioned(name):
+    """read() of a probe that prints a heading per configuration and a line per size under it.  Its expression matches either, as
+    (the heading's number, '', '') or ('', size, ms): {name.format(heading's number, size): ms} in the order printed."""
+    def read(m):
+        got, head = {}, None
+        for h, size, ms in m:
+            if h:
+                head = h
+            else:
+                got[name.format(head, size)] = float(ms)
+        return got
+    return read
+
+
 def stage(cfg):
     return ([PY, "tools/stage_probe.py", "--cfg", str(cfg)], 200, stage_ms, {"project_ms": LO, "tile_ms": LO, "total_ms": LO})
 
 
 # name -> argv, time limit (s), extractor (stdout -> {metric: float}), {metric: larger is better}.  200 / 300 s as the shell scripts
 # had them; chosen here where they had none: stage1, stage2 and stage3_plain 200 like stage3, bench_driver 300 like bench,
-# config_fps / door_b / vec_env / demo_env as tools/refresh_profiles.sh limits them, py_overhead and host_overhead 200.
+# config_fps / door_b / vec_env / demo_env as tools/refresh_profiles.sh limits them, py_overhead and host_overhead 200, cloud / fuse /
+# match 300 like bench (their torch baselines run once: --torch-repeats 1).
 PROBES = {
     "stage1": stage(1), "stage2": stage(2), "stage3": stage(3), "stage5": stage(5),
     "stage3_plain": ([PY, "tools/stage_probe.py", "--cfg", "3", "--frames", "300", "--plain"], 200,
@@ -81,6 +96,16 @@ PROBES = {
                       prose(r"^n=\d+: host enqueue ([\d.]+) us/frame, end-to-end ([\d.]+) us/frame",
                             lambda m: {"enqueue_us": float(m[0][0]), "end_to_end_us": float(m[0][1])}),
                       {"enqueue_us": LO, "end_to_end_us": LO}),
+    # the calls that need no scene: the medians of the blocking calls (ms); the probes exit 1 when their torch baselines disagree
+    "cloud": ([PY, "tools/cloud_probe.py", "--torch-repeats", "1"], 300,
+              prose(r"^(?:E = (\d+) \(|  K = (\d+): sample call ([\d.]+) ms)", sectioned("cloud{}_{}")),
+              {f"cloud{e}_{k}": LO for e in (1, 16) for k in (512, 1024, 4096)}),
+    "fuse": ([PY, "tools/fuse_probe.py", "--torch-repeats", "1"], 300,
+             prose(r"^(?:C = (\d+) views:|  (\d+)\^3 voxels: fuse call ([\d.]+) ms)", sectioned("fuse{}_{}")),
+             {f"fuse{c}_{n}": LO for c in (2, 32) for n in (128, 256)}),
+    "match": ([PY, "tools/match_probe.py"], 300,
+              prose(r"^\d+ x (\d+) = \S+ pairs: +([\d.]+) ms per call", lambda m: {f"match{t}": float(ms) for t, ms in m}),
+              {"match113831": LO, "match292247": LO}),
 }
 
 
