@@ -44,6 +44,14 @@ F32_ERR = {
         full=dict(means=1.16e-06, opacities=5.82e-07, colors=4.64e-07, viewmat=1.45e-06, quats=6.66e-07, scales=7.25e-07)),
     "special:all": dict(screen=dict(means2d=1.27e-06, conics=7.40e-07, opacities=4.19e-07, colors=7.07e-07, depths=3.95e-07),
         full=dict(means=1.14e-06, opacities=4.19e-07, colors=7.07e-07, viewmat=1.12e-06, quats=7.45e-07, scales=8.21e-07)),
+    "offaxis:all": dict(screen=dict(means2d=2.39e-06, conics=1.97e-06, opacities=8.42e-07, colors=1.35e-06, depths=2.78e-07),
+        full=dict(means=1.64e-06, opacities=8.42e-07, colors=1.35e-06, viewmat=2.05e-06, quats=9.27e-07, scales=1.48e-06)),
+    "clamp:all": dict(screen=dict(means2d=1.96e-06, conics=2.33e-07, opacities=7.60e-07, colors=9.40e-07, depths=6.27e-07),
+        full=dict(means=2.28e-06, opacities=7.60e-07, colors=9.40e-07, viewmat=1.13e-06, quats=1.01e-06, scales=8.90e-07)),
+    "clamp_cov6:all": dict(screen=dict(means2d=1.57e-06, conics=6.78e-07, opacities=6.65e-07, colors=1.20e-06, depths=8.37e-07),
+        full=dict(means=1.60e-06, opacities=6.65e-07, colors=1.20e-06, viewmat=1.32e-06, covariances=2.18e-06)),
+    "clamp_groups:all": dict(screen=dict(means2d=1.05e-06, conics=2.04e-07, opacities=4.42e-07, colors=5.69e-07, depths=6.09e-07),
+        full=dict(means=6.56e-07, opacities=4.42e-07, colors=5.69e-07, viewmat=9.46e-07, quats=4.38e-07, scales=5.70e-07)),
     "blob_32x32:rgb": dict(screen=dict(means2d=5.91e-07, conics=7.05e-07, opacities=9.71e-07, colors=5.54e-07, depths=0.00e+00),
         full=dict(means=6.51e-07, opacities=9.71e-07, colors=5.54e-07, viewmat=8.56e-07, quats=9.15e-07, scales=8.36e-07)),
     "blob_32x32:alpha": dict(screen=dict(means2d=9.26e-07, conics=7.54e-07, opacities=4.60e-07, colors=0.00e+00, depths=0.00e+00),
@@ -52,6 +60,8 @@ F32_ERR = {
         full=dict(means=8.81e-07, opacities=4.97e-07, colors=0.00e+00, viewmat=1.01e-06, quats=1.44e-06, scales=8.73e-07)),
     "two_views": dict(means=1.15e-06, opacities=6.57e-07, colors=1.13e-06, quats=1.16e-06, scales=7.79e-07),
     "l2": dict(means=6.79e-06, opacities=1.80e-06, colors=2.18e-07, viewmat=1.39e-06, quats=7.43e-06, scales=9.99e-06),
+    "l2:clamp": dict(means=1.09e-06, opacities=1.75e-06, colors=8.65e-07, viewmat=5.84e-07, quats=1.88e-06, scales=5.02e-06),
+    "clamp:extras": dict(means=6.73e-07, quats=1.01e-06, scales=8.90e-07),
 }
 FACTOR = 4.0
 
@@ -120,6 +130,19 @@ def test_clamped_alpha_passes_nothing_to_opacity_or_sigma(rasterizer):
     assert len(behind) > 0 and i not in behind   # others at that pixel do receive through their (unclamped) alphas
 
 
+def test_clamped_gaussians_alone(rasterizer):
+    """The five Gaussians of "clamp" beyond the limits of the Jacobian's clamp, held apart from the blob: upstream gradients only inside
+    their rectangles, and the measure taken over THEIR rows of means, quats and scales alone, against four times the float32 reference's
+    figure on those rows -- the blob's larger gradients cannot hide a wrong branch."""
+    r = rasterizer
+    sc, (V, K, W, H), _ = gc.case("clamp")
+    g, _ = gc.extras_upstream()
+    sc_kit.upload(r, sc)
+    full = r.render_backward(V, K, W, H, *g, want=gc.EXTRA_ROWS)
+    rows = list(gc.CLAMP.values())
+    _hold("clamp:extras", {k: full[k].double().cpu().numpy()[rows] for k in gc.EXTRA_ROWS}, gc.extras_reference(), F32_ERR["clamp:extras"])
+
+
 def test_want_selects_the_outputs(rasterizer):
     """``want`` leaves the other outputs NULL to the C call: only the named keys come back, held to the reference as in the full call."""
     r = rasterizer
@@ -154,9 +177,10 @@ def test_two_views_sum(rasterizer):
     _hold("two_views", got, ref, F32_ERR["two_views"])
 
 
-def test_autograd_l2_loss(rasterizer):
+@pytest.mark.parametrize("key", list(gc.L2_KEYS), ids=list(gc.L2_KEYS.values()))
+def test_autograd_l2_loss(rasterizer, key):
     r = rasterizer
-    name = "blob_40x24"
+    name = gc.L2_KEYS[key]
     sc, cam, _ = gc.case(name)
     V, K, W, H = cam
     ref, keep = gc.l2_reference(name)
@@ -173,7 +197,7 @@ def test_autograd_l2_loss(rasterizer):
     keys = list(params)
     grads = torch.autograd.grad(loss, [vm] + [params[k] for k in keys])
     got = dict(viewmat=grads[0][:3].double().cpu().numpy(), **{k: g.double().cpu().numpy() for k, g in zip(keys, grads[1:])})
-    _hold("l2", got, ref, F32_ERR["l2"])
+    _hold(key, got, ref, F32_ERR[key])
 
 
 def test_refine_camera_pose_recovers(rasterizer):
@@ -189,6 +213,24 @@ def test_refine_camera_pose_recovers(rasterizer):
     res = refine_camera_pose(r, target, V0, K, W, H, iters=300)
     a1, d1 = gc.pose_error(res.viewmat, V)
     print(f"BACKWARD refine_camera_pose: {a0:.3f} deg, {d0 * 1e3:.2f} mm -> {a1:.4f} deg, {d1 * 1e3:.3f} mm; loss {res.history[0][1]:.3e} -> {res.loss:.3e}")
+    assert a0 > 2.9 and d0 > 0.02
+    assert a1 < 0.1 * gc.POSE_ANGLE_DEG and d1 < 0.1 * gc.POSE_SHIFT
+
+
+def test_refine_camera_pose_recovers_off_axis(rasterizer):
+    """The same scene, perturbation, iterations and acceptance under a camera with fx != fy, its principal point a fifth of the image off
+    the centre and roll (grad_cases.pose_case_offaxis): the pyramid's rescaled K and the pose gradient hold off-axis.  (The CPU reference's
+    loss falls monotonically along the twist at all three levels: test_grad_cpu.py.)"""
+    from sim_a_splat_amd.register import refine_camera_pose, se3_exp
+    r = rasterizer
+    sc, (V, K, W, H), xi = gc.pose_case_offaxis()
+    sc_kit.upload(r, sc)
+    target = r.render(V, K, W, H)["rgb"].clone()
+    V0 = se3_exp(xi) @ np.asarray(V, np.float64)
+    a0, d0 = gc.pose_error(V0, V)
+    res = refine_camera_pose(r, target, V0, K, W, H, iters=300)
+    a1, d1 = gc.pose_error(res.viewmat, V)
+    print(f"BACKWARD refine_camera_pose off-axis: {a0:.3f} deg, {d0 * 1e3:.2f} mm -> {a1:.4f} deg, {d1 * 1e3:.3f} mm; loss {res.history[0][1]:.3e} -> {res.loss:.3e}")
     assert a0 > 2.9 and d0 > 0.02
     assert a1 < 0.1 * gc.POSE_ANGLE_DEG and d1 < 0.1 * gc.POSE_SHIFT
 

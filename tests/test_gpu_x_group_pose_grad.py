@@ -29,6 +29,7 @@ F32_ERR = {
     "gp_sh2": dict(means=1.86e-06, opacities=3.15e-07, colors=4.90e-07, viewmat=6.03e-07, quats=1.41e-06, scales=4.19e-07, group_poses=5.51e-07),
     "gp_rare": dict(means=1.87e-06, opacities=9.26e-07, colors=5.51e-07, viewmat=1.49e-06, quats=1.63e-06, scales=1.15e-06, group_poses=1.20e-06),
     "gp_behind": dict(means=1.27e-06, opacities=1.54e-06, colors=1.29e-06, viewmat=1.49e-06, quats=9.32e-07, scales=1.18e-06, group_poses=8.65e-07),
+    "gp_clamp": dict(means=1.50e-06, opacities=7.00e-07, colors=4.41e-07, viewmat=2.74e-06, quats=4.22e-07, scales=7.02e-07, group_poses=9.50e-07),
     "gp_rare_row": dict(group_poses=2.36e-06),
     "two_views": dict(group_poses=8.65e-07),
     "l2": dict(group_poses=1.81e-06, viewmat=1.04e-06),

@@ -1,8 +1,11 @@
 """CPU: the yardstick of the backward pass (tests/tools/grad_ref.py) and what the GPU tests assume of their cases (tests/tools/grad_cases.py).
 
 - the reference's forward is oracle/np_twin.py's to 1e-10,
-- its gradients are central finite differences of itself in float64 (every output, the view matrix included),
+- its gradients are central finite differences of itself in float64 (every output, the view matrix included), also under a camera with
+  fx != fy, an off-centre principal point and roll, and with Gaussians beyond the limits of the Jacobian's clamp,
 - every GPU case keeps the masking and margin conditions of DESIGN.md 3, "Backward pass",
+- the off-axis and clamp cases exercise what they are there for: the clamp binds (or does not), the clamped Gaussians carry weight, and a
+  reference that is wrong in the clamp's gradient, in fx against fy or in the principal point is far outside the GPU bound,
 - autograd.prechain is torch autograd of the frame's pointwise tail,
 - the new entry points are declared, bound and built."""
 import sys
@@ -78,14 +81,38 @@ def _fd_case():
     return sc, sc_kit.ring(16, 16, f=40.0, yaw=25.0, elev=0.3)
 
 
+FD_CAMERA = dict(W=16, H=16, fx=40.0, fy=32.0, cx=6.5, cy=9.5, eye=(3.0 * np.sin(np.deg2rad(25.0)), 0.3, 3.0 * np.cos(np.deg2rad(25.0))),
+                 target=(-0.04, -0.17, 0.05), roll_deg=20.0)   # _fd_case's place; aimed so that the six Gaussians stay in the middle of the image
+FD_CLAMP_Z, FD_CLAMP_OVER, FD_CLAMP_SCALE = 1.2, 1.06, 0.08
+
+
+def _fd_clamped(sc, cam):
+    """``sc`` plus two Gaussians close to the lens: one beyond the positive x limit of the Jacobian's clamp, one beyond the negative y
+    limit (chosen on the CPU so that the test's precondition holds: no near pixel, no marginal Gaussian)."""
+    V = np.asarray(cam[0], np.float64).reshape(4, 4)
+    xp, _, _, yn = gc.clamp_limits(cam)
+    z, s = FD_CLAMP_Z, FD_CLAMP_SCALE
+    world = np.array([V[:3, :3].T @ (np.array([ux * z, uy * z, z]) - V[:3, 3]) for ux, uy in ((FD_CLAMP_OVER * xp, 0.05), (-0.03, -FD_CLAMP_OVER * yn))])
+    cat = lambda a, b: np.concatenate([np.asarray(a), np.asarray(b, np.asarray(a).dtype)], 0)
+    rng = np.random.default_rng(17)
+    return dict(sc, means=cat(sc["means"], world), op=cat(sc["op"], [0.8, 0.7]),
+                colors=cat(sc["colors"], 0.3 * rng.normal(size=(2,) + np.asarray(sc["colors"]).shape[1:])),
+                quats=cat(sc["quats"], [[1, 0.1, -0.2, 0.1], [0.9, -0.2, 0.1, 0.3]]),
+                scales=cat(sc["scales"], [[s, 0.9 * s, 1.1 * s], [1.1 * s, s, 0.9 * s]]))
+
+
 def _loss(sc, cam, P, vm, g):
     _, _, I, F = grad_ref.forward(sc, cam, torch.float64, viewmat=vm, P=P)
     return (g[0] * F["acc_rgb"]).sum() + (g[1] * F["alpha"]).sum() + (g[2] * F["acc_z"]).sum(), F, I
 
 
-@pytest.mark.parametrize("form", ["quats", "cov6", "groups"])
+@pytest.mark.parametrize("form", ["quats", "cov6", "groups", "general", "general_clamp"])
 def test_gradients_are_finite_differences(form):
     sc, cam = _fd_case()
+    if form.startswith("general"):
+        cam = sc_kit.general(**FD_CAMERA)
+    if form == "general_clamp":
+        sc = _fd_clamped(sc, cam)
     if form == "cov6":
         sc = gc._cov6(sc)
     if form == "groups":
@@ -97,6 +124,10 @@ def test_gradients_are_finite_differences(form):
     loss, F, I = _loss(sc, cam, P, vm, g)
     assert not F["near"].any() and not I["margin"].any() and I["valid"].all()
     assert (F["alpha"] > 0.05).sum() > 50   # the Gaussians show
+    if form == "general_clamp":             # the two extras bind the clamp, and nothing else does
+        (xp, xn, yp, yn), u = I["limits"], I["ratios"].numpy()
+        assert u[-2, 0] > xp * (1 + grad_ref.MARGIN) and u[-1, 1] < -yn * (1 + grad_ref.MARGIN)
+        assert np.all((u[:-2, 0] < xp) & (u[:-2, 0] > -xn) & (u[:-2, 1] < yp) & (u[:-2, 1] > -yn))
     loss.backward()
     leaves = dict(P, viewmat=vm)
     for name, t in leaves.items():
@@ -163,6 +194,107 @@ def test_pose_case_has_no_nearer_minimum():
     assert all(a > b for a, b in zip(losses, losses[1:])) and losses[-1] == 0.0, losses
 
 
+@pytest.mark.parametrize("factor", [4, 2, 1])
+def test_offaxis_pose_case_has_no_nearer_minimum(factor):
+    """test_pose_case_has_no_nearer_minimum for grad_cases.pose_case_offaxis (fx != fy, the principal point a fifth of the image off the
+    centre, roll), at each of the three levels of register.refine_camera_pose with K's two rows rescaled as it rescales them."""
+    from sim_a_splat_amd.register import se3_exp
+    sc, (V, K, W, H), xi = gc.pose_case_offaxis()
+    assert K[0, 0] != K[1, 1] and abs(K[0, 2] - W / 2) > 0.1999 * W and abs(K[1, 2] - H / 2) > 0.1999 * H   # (K is float32)
+    w, h = W // factor, H // factor
+    Kc = np.asarray(K, np.float64).copy()
+    Kc[0] *= w / W
+    Kc[1] *= h / H
+    P = {k: (None if v is None else v.detach()) for k, v in grad_ref.leaves(sc).items()}
+
+    def rgb(Vc):
+        with torch.no_grad():
+            F = grad_ref.forward(sc, (Vc, Kc, w, h), viewmat=torch.tensor(np.asarray(Vc, np.float64)[:3]), P=P)[3]
+            return grad_ref.finish(F)["rgb"]
+    target = rgb(np.asarray(V, np.float64))
+    losses = [float(((rgb(se3_exp((1.0 - t) * xi) @ np.asarray(V, np.float64)) - target) ** 2).mean()) for t in np.linspace(0.0, 1.0, 6)]
+    assert all(a > b for a, b in zip(losses, losses[1:])) and losses[-1] == 0.0, losses
+
+
+NEW_CASES = ("offaxis",) + gc.CLAMP_NAMES
+GPU_FACTOR = 4.0   # tests/test_gpu_t_backward.py's FACTOR: the GPU bound is this times the float32 reference's figure
+
+
+@pytest.mark.parametrize("name", NEW_CASES)
+def test_offaxis_and_clamp_case_conditions(name):
+    """From the reference alone.  The camera is off-axis; in the "clamp*" cases each of the four limits of the Jacobian's clamp is
+    exceeded by a VALID Gaussian by more than the margin, the published ones among them, and in "offaxis" none is; each published clamp
+    Gaussian carries at least 5 % of the case's largest gradient of the means and of the scales (of the covariances in the cov6 form);
+    and every figure of the float32 reference is at most 1e-5, as in the cases before these."""
+    sc, cam, _ = gc.case(name)
+    V, K, W, H = cam
+    assert K[0, 0] != K[1, 1] and K[0, 2] != W / 2 and K[1, 2] != H / 2
+    assert not np.allclose(np.asarray(V)[0, :3] @ [0.0, 1.0, 0.0], 0.0, atol=0.1)   # roll: the camera's x axis is not level
+    ref = gc.reference(name)
+    with torch.no_grad():
+        I = grad_ref.forward(sc, cam)[2]
+    (xp, xn, yp, yn), u, valid = I["limits"], I["ratios"].numpy(), ref["valid"]
+    assert np.allclose((xp, xn, yp, yn), gc.clamp_limits(cam), rtol=1e-12) and len({xp, xn, yp, yn}) == 4   # four limits, all apart
+    m = 1 + grad_ref.MARGIN
+    over = [valid & (u[:, 0] > xp * m), valid & (u[:, 0] < -xn * m), valid & (u[:, 1] > yp * m), valid & (u[:, 1] < -yn * m)]
+    inside = (u[:, 0] < xp) & (u[:, 0] > -xn) & (u[:, 1] < yp) & (u[:, 1] > -yn)
+    if name == "offaxis":
+        assert valid.all() and inside.all()
+    else:
+        n = len(valid)
+        idx = {k: n + i for k, i in gc.CLAMP.items()}
+        assert valid[list(idx.values())].all()
+        assert over[0][idx["x_pos"]] and over[1][idx["x_neg"]] and over[2][idx["y_pos"]] and over[3][idx["y_neg"]]
+        assert over[0][idx["corner"]] and over[3][idx["corner"]]
+        assert inside[:n - 5].all()   # the blob is as in "offaxis"
+        if name == "clamp_groups":
+            gid = np.asarray(sc["gid"])
+            G = np.asarray(sc["Rt"], np.float64).reshape(-1, 3, 4)[gc.CLAMP_GROUP]
+            assert np.all(gid[-5:] == gc.CLAMP_GROUP) and not np.allclose(G[:, :3], np.eye(3), atol=1e-2) and np.abs(G[:, 3]).max() > 1e-2
+        for k in ("means", "covariances" if name == "clamp_cov6" else "scales"):
+            a = np.abs(ref["full"][k])
+            share = a[list(idx.values())].max(axis=1) / a.max()
+            assert share.min() >= 0.05, (k, share)
+    e = gc.float32_errors(name)
+    worst = max(max(e["screen"].values()), max(e["full"].values()))
+    assert worst <= 1e-5, e
+
+
+@pytest.mark.parametrize("name,kind", [("offaxis", "swap_f"), ("offaxis", "centred")] + [(n, "straight_through") for n in gc.CLAMP_NAMES])
+def test_offaxis_and_clamp_cases_are_sensitive(name, kind):
+    """A reference that is wrong in one way -- fx and fy exchanged, the principal point centred, the clamp's gradient passed straight
+    through to x and y (grad_ref.project's mutant; its forward is the reference's) -- misses the GPU test's bound on ``means`` and on
+    ``viewmat`` by more than a factor of 100: an implementation with that error cannot pass."""
+    ref, e = gc.reference(name)["full"], gc.float32_errors(name)["full"]
+    mut = gc.mutant_reference(name, kind)
+    for k in ("means", "viewmat"):
+        d = grad_ref.rel_err(mut[k], ref[k])
+        print(f"BACKWARD mutant {kind} on {name}: {k} off by {d:.3e}, GPU bound {GPU_FACTOR * e[k]:.3e}")
+        assert d > 100 * GPU_FACTOR * e[k], (k, d, e[k])
+    if kind == "straight_through":
+        sc, cam, _ = gc.case(name)
+        with torch.no_grad():
+            a, b = grad_ref.forward(sc, cam)[3], grad_ref.forward(sc, cam, straight_through=True)[3]
+        assert all(torch.equal(a[k], b[k]) for k in a)   # the same frame: only the derivative differs
+
+
+def test_extras_upstream_covers_the_clamped_gaussians():
+    """The GPU test that holds the five extras' rows of "clamp" alone: its upstream gradients are zero outside their rectangles and at the
+    masked pixels, every extra's rows of means, quats and scales receive, and on EACH extra's row of ``means`` the straight-through mutant
+    is off by more than 100 times that test's bound, four times the float32 figure, in that test's measure (over the five rows)."""
+    g, inside = gc.extras_upstream()
+    near = gc.reference("clamp")["near"]
+    assert 0 < inside.sum() and all(np.all(gi[~inside | near] == 0) for gi in g)
+    rows, r32 = gc.extras_reference(), gc.extras_reference("float32")
+    for k in gc.EXTRA_ROWS:
+        assert rows[k].shape[0] == 5 and np.all(np.abs(rows[k]).max(axis=1) > 0), k
+        assert grad_ref.rel_err(r32[k], rows[k]) <= 1e-5
+    sc, cam, _ = gc.case("clamp")
+    mut = grad_ref.gradients(sc, cam, *g, mask_near=False, straight_through=True)["full"]["means"][list(gc.CLAMP.values())]
+    off = np.abs(mut - rows["means"]).max(axis=1) / np.abs(rows["means"]).max()
+    assert off.min() > 100 * GPU_FACTOR * grad_ref.rel_err(r32["means"], rows["means"]), off
+
+
 def test_special_case_clamps_alpha_at_its_pixel():
     """From the reference alone: the opacity-1 Gaussian of "special" has o e^-sigma beyond 0.999 by more than the margin at
     grad_cases.CLAMP_PIXEL, that pixel is not masked, the Gaussian is the frontmost entry there, and the reference passes nothing through
@@ -225,7 +357,7 @@ def test_float32_error_table_of_the_gpu_test_is_current():
     spec = importlib.util.spec_from_file_location("gpu_t_backward", Path(__file__).resolve().parent / "test_gpu_t_backward.py")
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    assert set(mod.F32_ERR) == {f"{n}:{m}" for n, m in gc.RUNS} | {"two_views", "l2"}
+    assert set(mod.F32_ERR) == {f"{n}:{m}" for n, m in gc.RUNS} | {"two_views", "clamp:extras"} | set(gc.L2_KEYS)
     for name, mode in gc.RUNS:
         now = gc.float32_errors(name, mode)
         for part in ("screen", "full"):
@@ -234,8 +366,10 @@ def test_float32_error_table_of_the_gpu_test_is_current():
             for k, v in now[part].items():
                 assert abs(table[k] - v) <= 0.25 * v + 1e-12, (name, mode, part, k, table[k], v)
     a, b = gc.two_view_reference()[0], gc.two_view_reference("float32")[0]
-    l64, l32 = gc.l2_reference("blob_40x24")[0], gc.l2_reference("blob_40x24", "float32")[0]
-    for key, x64, x32 in (("two_views", a, b), ("l2", l64, l32)):
+    rows = [("two_views", a, b), ("clamp:extras", gc.extras_reference(), gc.extras_reference("float32"))]
+    rows += [(key, gc.l2_reference(name)[0], gc.l2_reference(name, "float32")[0]) for key, name in gc.L2_KEYS.items()]
+    for key, x64, x32 in rows:
+        assert set(mod.F32_ERR[key]) == set(x64)
         for k in x64:
             v = grad_ref.rel_err(x32[k], x64[k])
             assert abs(mod.F32_ERR[key][k] - v) <= 0.25 * v + 1e-12, (key, k, mod.F32_ERR[key][k], v)

@@ -10,6 +10,7 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tests" / "tools"))
+import grad_cases as gc  # noqa: E402
 import grad_ref  # noqa: E402
 import group_pose_cases as gpc  # noqa: E402
 import group_pose_ref as gpr  # noqa: E402
@@ -41,6 +42,30 @@ def test_case_conditions(name):
         assert mine.sum() > 100 and not ref["valid"][mine].any() and ref["valid"][~mine].all()
         assert np.all(ref["full"]["group_poses"][gpc.BEHIND_GROUP] == 0)
         assert np.all(ref["full"]["means"][mine] == 0)
+    if name == "gp_clamp":
+        import torch
+        n, extras = len(gid), [len(gid) + i for i in gc.CLAMP.values()]
+        assert np.all(gid[extras] == gc.CLAMP_GROUP) and ref["valid"][extras].all()
+        G = np.asarray(sc["Rt"], np.float64).reshape(-1, 3, 4)[gc.CLAMP_GROUP]
+        assert not np.allclose(G[:, :3], np.eye(3), atol=1e-2) and np.abs(G[:, 3]).max() > 1e-2   # a pose that is not the identity
+        with torch.no_grad():
+            I = gpr.forward(sc, cam)[3]
+        (xp, xn, yp, yn), u, m = I["limits"], I["ratios"].numpy(), 1 + grad_ref.MARGIN
+        k = {key: n + i for key, i in gc.CLAMP.items()}   # placed through the pose: beyond the limits AFTER posing
+        assert u[k["x_pos"], 0] > xp * m and u[k["x_neg"], 0] < -xn * m and u[k["y_pos"], 1] > yp * m and u[k["y_neg"], 1] < -yn * m
+        assert u[k["corner"], 0] > xp * m and u[k["corner"], 1] < -yn * m
+
+
+def test_clamp_case_is_sensitive_in_its_group_pose():
+    """grad_ref.project's straight-through mutant (the clamp's gradient passed to x and y, the same forward) moves dL/dG of the group
+    that holds the clamped Gaussians of "gp_clamp" by more than 100 times the GPU bound, four times the float32 reference's figure: the
+    clamp's z route flows into that group's pose, and the case would show an implementation that lost it."""
+    ref, mut = gpc.reference("gp_clamp")["full"]["group_poses"], gpc.mutant_reference("gp_clamp")["group_poses"]
+    f32 = gpc.float32_errors("gp_clamp")["group_poses"]
+    assert f32 <= 1e-5
+    d = np.abs(mut[gc.CLAMP_GROUP] - ref[gc.CLAMP_GROUP]).max() / np.abs(ref).max()   # in the measure of the GPU test: over the whole array
+    print(f"GROUP POSE straight-through mutant on gp_clamp: group {gc.CLAMP_GROUP} off by {d:.3e}, GPU bound {4.0 * f32:.3e}")
+    assert d > 100 * 4.0 * f32
 
 
 def test_posing_in_front_changes_nothing_else():
@@ -58,7 +83,7 @@ def test_posing_in_front_changes_nothing_else():
 ENTRIES = ((0, 0), (1, 2), (2, 1), (0, 3), (2, 3), (1, 3))   # rotation and translation entries of a pose [3,4]
 
 
-@pytest.mark.parametrize("name", ["gp600", "gp600_cov6", "gp_sh2", "gp_rare"])
+@pytest.mark.parametrize("name", ["gp600", "gp600_cov6", "gp_sh2", "gp_rare", "gp_clamp"])
 def test_reference_against_central_differences(name):
     """dL/dG of the yardstick against central differences of the float64 loss with the mask held fixed.  The step is fixed; the
     tolerance per entry is derived here: the central difference at h errs by h^2 f'''/6, which the difference at 2h shows fourfold, so
@@ -78,7 +103,7 @@ def test_reference_against_central_differences(name):
         return (gpr.loss_at(sc, cam, Gp, g, keep) - gpr.loss_at(sc, cam, Gm, g, keep)) / (2.0 * step)
 
     # every group of the two cases that are cheap or new in kind; of the same scene's other forms the groups that differ
-    groups = {"gp600": range(G0.shape[0]), "gp_sh2": range(G0.shape[0]), "gp600_cov6": (0, 3), "gp_rare": (gpc.RARE_GROUP,)}[name]
+    groups = {"gp600": range(G0.shape[0]), "gp_sh2": range(G0.shape[0]), "gp600_cov6": (0, 3), "gp_rare": (gpc.RARE_GROUP,), "gp_clamp": (gc.CLAMP_GROUP,)}[name]
     for grp in groups:
         for rc in (ENTRIES[grp % 2::2] if name == "gp_sh2" else ENTRIES[grp % 3::3]):   # a few entries of each group: rotation and translation
             d1, d2 = diff(grp, rc, h), diff(grp, rc, 2.0 * h)

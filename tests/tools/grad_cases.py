@@ -2,7 +2,8 @@
 name.  Seeds and scene parameters were chosen on the CPU (tests/tools/grad_ref.py) so that at most 2 % of a case's pixels are masked, and a
 drawn Gaussian whose projection-level decision (near / far and opacity culls, the radius' ceil, the rectangle against the image, the
 Jacobian's clamp) lies within grad_ref.MARGIN of its threshold is rejected from the draw (``_clean``: such a decision depends on the
-Gaussian and the camera alone); test_grad_cpu.py asserts both conditions for every case as the tests use it."""
+Gaussian and the camera alone); test_grad_cpu.py asserts both conditions for every case as the tests use it.  Most cases stand under
+scene_cases.ring (fx = fy, centred principal point, no roll); "offaxis" and the "clamp*" cases stand under scene_cases.general."""
 import functools
 
 import numpy as np
@@ -78,6 +79,51 @@ def _dense(seed=8):
     return _clean(lr.blob_scene(2000, seed, 0.08, spread=1.0, z_spread=0.5, op=(0.7, 0.99)), sc_kit.ring(48, 48, f=54.0, yaw=0.0, elev=0.0))
 
 
+# ---- an off-axis camera, and Gaussians beyond the limits of the Jacobian's clamp -----------------------------------------------------------
+OFFAXIS = dict(W=40, H=28, fx=20.0, fy=15.0, cx=14.0, cy=17.0, eye=(0.6, 0.5, 2.6), target=(0.1, -0.1, 0.0), roll_deg=25.0)
+CLAMP_Z, CLAMP_OVER, CLAMP_OPACITY = 0.9, 1.04, 0.8   # the extras: camera depth, x/z or y/z over the limit, opacity ...
+CLAMP_SCALE = (0.16, 0.13, 0.17)                     # ... and scales: not quite round, so that their quaternions receive too (chosen on the
+#                                                      CPU among a few triples: no marginal Gaussian in any of the three cases)
+CLAMP = dict(x_pos=-5, x_neg=-4, y_pos=-3, y_neg=-2, corner=-1)         # indices of the extra Gaussians of the "clamp*" cases
+CLAMP_NAMES = ("clamp", "clamp_cov6", "clamp_groups")
+CLAMP_GROUP = 1                                                          # the (posed) group the extras of "clamp_groups" belong to
+
+
+def clamp_limits(cam):
+    """(x_pos, x_neg, y_pos, y_neg): the bounds on x/z and y/z beyond which the Jacobian's tx / ty are clamped (oracle/np_twin.py)."""
+    _, K, W, H = cam
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    return ((W - cx) / fx + 0.15 * W / fx, cx / fx + 0.15 * W / fx, (H - cy) / fy + 0.15 * H / fy, cy / fy + 0.15 * H / fy)
+
+
+def _offaxis(n_groups=0):
+    """The blob under a camera with fx != fy, an off-centre principal point and roll; no Gaussian reaches a clamp limit."""
+    return _clean(lr.blob_scene(64, 11, 0.12, n_groups=n_groups), sc_kit.general(**OFFAXIS))
+
+
+def _clamp(n_groups=0):
+    """"offaxis" plus five Gaussians close to the lens, each at a camera-frame point (u_x z, u_y z, z) unprojected through the inverse of
+    the case's own view matrix: one beyond each of the four limits by the factor CLAMP_OVER, the fifth beyond two at once (CLAMP names
+    them).  With groups the five belong to group CLAMP_GROUP and are placed through the inverse of its pose as well: they land there
+    AFTER posing."""
+    sc, cam = _offaxis(n_groups)
+    V = np.asarray(cam[0], np.float64).reshape(4, 4)
+    xp, xn, yp, yn = clamp_limits(cam)
+    f, z = CLAMP_OVER, CLAMP_Z
+    ratios = [(f * xp, 0.15), (-f * xn, -0.1), (0.2, f * yp), (-0.15, -f * yn), (f * xp, -f * yn)]
+    world = np.array([V[:3, :3].T @ (np.array([ux * z, uy * z, z]) - V[:3, 3]) for ux, uy in ratios])
+    cat = lambda a, b: np.concatenate([np.asarray(a), np.asarray(b, np.asarray(a).dtype)], 0)
+    if n_groups:
+        G = np.asarray(sc["Rt"], np.float64).reshape(-1, 3, 4)[CLAMP_GROUP]
+        world = (world - G[:, 3]) @ G[:, :3]   # the canonical point m with Rg m + t = world
+        sc = dict(sc, gid=cat(sc["gid"], [CLAMP_GROUP] * 5))
+    sc = dict(sc, means=cat(sc["means"], world), op=cat(sc["op"], [CLAMP_OPACITY] * 5),
+              colors=cat(sc["colors"], [[0.9, 0.3, 0.2], [0.2, 0.8, 0.3], [0.3, 0.4, 0.9], [0.8, 0.8, 0.2], [0.6, 0.2, 0.7]]),
+              quats=cat(sc["quats"], [[1, 0, 0, 0]] * 5), scales=cat(sc["scales"], [CLAMP_SCALE] * 5))
+    return sc, cam
+
+
 BUILDERS = {
     "blob_32x32": lambda: _blob(32, 32),
     "blob_40x24": lambda: _blob(40, 24),
@@ -90,8 +136,14 @@ BUILDERS = {
     "groups3": lambda: _blob(40, 24, n_groups=3),
     "special": _special,
 }
-NAMES = tuple(BUILDERS)
 BUILDERS["two_views"] = lambda: _two_views()   # (not a case of its own: the scene of two_view_reference)
+BUILDERS.update({                              # (behind it: a case's upstream gradients are drawn from its place in this table)
+    "offaxis": _offaxis,
+    "clamp": _clamp,
+    "clamp_cov6": lambda: (_cov6(_clamp()[0]), _clamp()[1]),
+    "clamp_groups": lambda: _clamp(n_groups=3),
+})
+NAMES = tuple(n for n in BUILDERS if n != "two_views")
 SPECIAL = dict(behind=-3, transparent=-2, clamped=-1)   # indices of the extra Gaussians of "special"
 
 
@@ -122,6 +174,53 @@ def masked_upstream(name, which=(True, True, True)):
     return [None if not w else (gi * (keep[..., None] if gi.ndim == 3 else keep)).astype(np.float32) for gi, w in zip(g, which)]
 
 
+# ---- what the new cases are measured with: mutants of the reference, and the clamped Gaussians held alone ----------------------------------
+MUTANTS = ("straight_through", "swap_f", "centred")
+
+
+@functools.lru_cache(maxsize=None)
+def mutant_reference(name, kind):
+    """The full gradients of the case, same masked upstream gradients, from a reference that is wrong in one way: ``straight_through``
+    (grad_ref.project's mutant: the clamp's gradient goes to x and y), ``swap_f`` (fx and fy exchanged in K), ``centred`` (the principal
+    point at the image's centre).  A case counts only if these are far from the reference (test_grad_cpu.py)."""
+    sc, (V, K, W, H), _ = case(name)
+    K = np.array(K, np.float64).reshape(3, 3)
+    if kind == "swap_f":
+        K[0, 0], K[1, 1] = K[1, 1], K[0, 0]
+    if kind == "centred":
+        K[0, 2], K[1, 2] = W / 2.0, H / 2.0
+    return grad_ref.gradients(sc, (V, K, W, H), *masked_upstream(name), mask_near=False, straight_through=kind == "straight_through")["full"]
+
+
+EXTRA_ROWS = ("means", "quats", "scales")
+
+
+@functools.lru_cache(maxsize=None)
+def extras_upstream():
+    """The masked upstream gradients of "clamp", zeroed outside the five extras' rectangles (means2d +- radii of the reference): what the
+    extras' rows receive is then no smaller than anything else in the arrays."""
+    import torch
+    sc, cam, _ = case("clamp")
+    W, H = cam[2], cam[3]
+    with torch.no_grad():
+        I = grad_ref.forward(sc, cam)[2]
+    m2, rad = I["means2d"].numpy(), I["radii"].numpy()
+    px, py = np.meshgrid(np.arange(W) + 0.5, np.arange(H) + 0.5)
+    inside = np.zeros((H, W), bool)
+    for i in CLAMP.values():
+        inside |= (np.abs(px - m2[i, 0]) <= rad[i, 0]) & (np.abs(py - m2[i, 1]) <= rad[i, 1])
+    return tuple((gi * (inside[..., None] if gi.ndim == 3 else inside)).astype(np.float32) for gi in masked_upstream("clamp")), inside
+
+
+@functools.lru_cache(maxsize=None)
+def extras_reference(dtype_name="float64"):
+    """The extras' rows (in CLAMP's order) of EXTRA_ROWS of the full gradients of "clamp" under extras_upstream."""
+    import torch
+    sc, cam, _ = case("clamp")
+    full = grad_ref.gradients(sc, cam, *extras_upstream()[0], dtype=getattr(torch, dtype_name), mask_near=False)["full"]
+    return {k: full[k][list(CLAMP.values())] for k in EXTRA_ROWS}
+
+
 # ---- two views of one scene, and a plain L2 loss on the delivered frame ---------------------------------------------------------------
 def second_camera():
     return sc_kit.ring(32, 32, f=0.45 * 32, yaw=70.0, elev=0.4)
@@ -145,6 +244,7 @@ def two_view_reference(dtype_name="float64"):
 
 
 L2_BACKGROUND = (0.1, 0.3, 0.2)
+L2_KEYS = {"l2": "blob_40x24", "l2:clamp": "clamp"}   # the rows of the float32 table and their cases
 
 
 @functools.lru_cache(maxsize=None)
@@ -196,6 +296,16 @@ def pose_case():
     return sc, cam, xi
 
 
+def pose_case_offaxis():
+    """pose_case's scene and twist under a camera at the same place with fx != fy, its principal point a fifth of the image off the
+    centre in x and in y (12.8 of 64 pixels each) and 15 degrees of roll, aimed so that the scene's centre still falls on the image's
+    centre.  Chosen on the CPU: the loss falls monotonically along the twist at all three pyramid levels (test_grad_cpu.py)."""
+    sc, _, xi = pose_case()
+    yaw = np.deg2rad(10.0)
+    cam = sc_kit.general(64, 64, 72.0, 60.0, 44.8, 19.2, (3.0 * np.sin(yaw), 0.2, 3.0 * np.cos(yaw)), (0.34, 0.75, -0.1), 15.0)
+    return sc, cam, xi
+
+
 def pose_error(V_est, V_true):
     """(angle in degrees, distance between the camera centres) between two world -> camera matrices."""
     A, B = np.asarray(V_est, np.float64).reshape(4, 4), np.asarray(V_true, np.float64).reshape(4, 4)
@@ -211,5 +321,8 @@ if __name__ == "__main__":   # the table of profiles/render_backward.txt and of 
         print("        full=dict(" + ", ".join(f"{k}={v:.2e}" for k, v in e["full"].items()) + ")),")
     a, b = two_view_reference()[0], two_view_reference("float32")[0]
     print('    "two_views": dict(' + ", ".join(f"{k}={grad_ref.rel_err(b[k], a[k]):.2e}" for k in a) + "),")
-    a, b = l2_reference("blob_40x24")[0], l2_reference("blob_40x24", "float32")[0]
-    print('    "l2": dict(' + ", ".join(f"{k}={grad_ref.rel_err(b[k], a[k]):.2e}" for k in a) + "),")
+    for key, name in L2_KEYS.items():
+        a, b = l2_reference(name)[0], l2_reference(name, "float32")[0]
+        print(f'    "{key}": dict(' + ", ".join(f"{k}={grad_ref.rel_err(b[k], a[k]):.2e}" for k in a) + "),")
+    a, b = extras_reference(), extras_reference("float32")
+    print('    "clamp:extras": dict(' + ", ".join(f"{k}={grad_ref.rel_err(b[k], a[k]):.2e}" for k in a) + "),")

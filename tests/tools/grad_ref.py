@@ -62,9 +62,12 @@ def _near(v, thr):
     return (v - thr).abs() <= MARGIN * abs(thr)
 
 
-def project(P, viewmat, K, W, H, sh_degree, group_id=None, group_Rt=None):
+def project(P, viewmat, K, W, H, sh_degree, group_id=None, group_Rt=None, straight_through=False):
     """np_twin.project on tensors: ``P`` holds means, op, colors and quats + scales or cov6; ``viewmat [3,4]``.  Returns the
-    intermediates, ``valid`` / ``radii`` (detached) and ``margin``: per Gaussian, whether a projection-level decision is within MARGIN."""
+    intermediates, ``valid`` / ``radii`` (detached), ``margin``: per Gaussian, whether a projection-level decision is within MARGIN,
+    and what the Jacobian's clamp saw: ``ratios [N,2]`` (x/z, y/z, detached) and ``limits`` (x_pos, x_neg, y_pos, y_neg).
+    ``straight_through`` is a MUTANT the tests measure their cases' sensitivity with: the same forward, but the clamp's gradient
+    passes to x and y as if it never bound."""
     means, op = P["means"], P["op"]
     dt = means.dtype
     n = means.shape[0]
@@ -105,6 +108,8 @@ def project(P, viewmat, K, W, H, sh_degree, group_id=None, group_Rt=None):
         margin = margin | (valid & (_near(u, float(lo)) | _near(u, float(hi))))
     tx = zs * torch.minimum(lim_x_pos, torch.maximum(-lim_x_neg, ux))
     ty = zs * torch.minimum(lim_y_pos, torch.maximum(-lim_y_neg, uy))
+    if straight_through:
+        tx, ty = x + (tx - x).detach(), y + (ty - y).detach()
     zero = torch.zeros_like(rz)
     J = torch.stack([fx * rz, zero, -fx * tx * rz * rz, zero, fy * rz, -fy * ty * rz * rz], dim=1).reshape(-1, 2, 3)
     c2 = J @ covc @ J.transpose(1, 2)
@@ -147,7 +152,8 @@ def project(P, viewmat, K, W, H, sh_degree, group_id=None, group_Rt=None):
     else:
         rgb = P["colors"].reshape(n, 3) * 1.0
     return dict(valid=valid, radii=radii, margin=margin, means2d=torch.stack([mx, my], dim=1), depths=z * 1.0, conics=conic,
-                colors=rgb, opacities=op * 1.0)
+                colors=rgb, opacities=op * 1.0, ratios=torch.stack([ux, uy], dim=1).detach(),
+                limits=tuple(float(v) for v in (lim_x_pos, lim_x_neg, lim_y_pos, lim_y_neg)))
 
 
 def render(I, valid, radii, W, H):
@@ -212,7 +218,7 @@ def leaves(sc, dtype=torch.float64):
     return P
 
 
-def forward(sc, cam, dtype=torch.float64, Rt=None, viewmat=None, P=None):
+def forward(sc, cam, dtype=torch.float64, Rt=None, viewmat=None, P=None, straight_through=False):
     """(leaves P, viewmat leaf [3,4], intermediates, raw frame) of scene ``sc`` seen by ``cam = (V, K, W, H)``."""
     V, K, W, H = cam
     P = leaves(sc, dtype) if P is None else P
@@ -220,7 +226,7 @@ def forward(sc, cam, dtype=torch.float64, Rt=None, viewmat=None, P=None):
         viewmat = torch.tensor(np.asarray(V, np.float64).reshape(4, 4)[:3], dtype=dtype, requires_grad=True)
     gid = sc.get("gid")
     rt = (sc.get("Rt") if Rt is None else Rt) if gid is not None else None
-    I = project(P, viewmat, K, W, H, sc["sh"], gid, rt)
+    I = project(P, viewmat, K, W, H, sc["sh"], gid, rt, straight_through)
     for k in SCREEN:
         if I[k].requires_grad:
             I[k].retain_grad()
@@ -235,11 +241,11 @@ def finish(F, background=(0.0, 0.0, 0.0)):
     return dict(rgb=torch.clamp(F["acc_rgb"] + (1 - a)[..., None] * bg, 0, 1), alpha=a, depth=F["acc_z"] / torch.clamp(a, min=1e-10))
 
 
-def gradients(sc, cam, g_rgb=None, g_alpha=None, g_depth=None, dtype=torch.float64, Rt=None, mask_near=True):
+def gradients(sc, cam, g_rgb=None, g_alpha=None, g_depth=None, dtype=torch.float64, Rt=None, mask_near=True, straight_through=False):
     """Gradients of ``sum g_rgb acc_rgb + sum g_alpha alpha + sum g_depth acc_z``: {"screen": means2d, conics, opacities, colors, depths;
     "full": means, opacities, colors, quats + scales | covariances, viewmat; "near": the masked pixels [H,W]; "valid"; "margin"}.
     ``mask_near``: the upstream gradients are zeroed at the ``near`` pixels first (the caller zeroes the same pixels for the GPU)."""
-    P, vm, I, F = forward(sc, cam, dtype, Rt)
+    P, vm, I, F = forward(sc, cam, dtype, Rt, straight_through=straight_through)
     keep = (~F["near"]).to(dtype) if mask_near else torch.ones_like(F["alpha"])
     loss = torch.zeros((), dtype=dtype)
     for g, f in ((g_rgb, F["acc_rgb"]), (g_alpha, F["alpha"]), (g_depth, F["acc_z"])):

@@ -1,7 +1,8 @@
 """The cases of the group-pose gradient tests (tests/test_group_pose_cpu.py, tests/test_gpu_x_group_pose_grad.py): grouped scenes, their
 cameras and upstream gradients, the float64 reference of tests/tools/group_pose_ref.py per case (computed once and shared), and the
 float32 reference's own error, which sets the GPU bound.  The shapes are the smallest at which the kernel can go wrong: several
-workgroups, several groups per wave, a group absent from most waves, a group that is culled whole.  As in grad_cases.py a case masks at most
+workgroups, several groups per wave, a group absent from most waves, a group that is culled whole, a group whose Gaussians lie beyond
+the limits of the Jacobian's clamp under an off-axis camera.  As in grad_cases.py a case masks at most
 MAX_MASKED of its pixels and holds no Gaussian with a marginal projection decision; test_group_pose_cpu.py asserts both.
 
     python tests/tools/group_pose_cases.py      prints the F32_ERR table of tests/test_gpu_x_group_pose_grad.py"""
@@ -59,6 +60,7 @@ BUILDERS = {
     "gp_sh2": _gp_sh2,
     "gp_rare": _gp_rare,
     "gp_behind": _gp_behind,
+    "gp_clamp": lambda: gc.BUILDERS["clamp_groups"](),   # five Gaussians of group gc.CLAMP_GROUP beyond the limits of the Jacobian's clamp
 }
 NAMES = tuple(BUILDERS)
 
@@ -87,6 +89,13 @@ def masked_upstream(name):
     sc, cam, g = case(name)
     keep = ~reference(name)["near"]
     return [(gi * (keep[..., None] if gi.ndim == 3 else keep)).astype(np.float32) for gi in g]
+
+
+@functools.lru_cache(maxsize=None)
+def mutant_reference(name):
+    """The full gradients from grad_ref.project's straight-through mutant (the clamp's gradient passed to x and y), same upstream gradients."""
+    sc, cam, _ = case(name)
+    return gpr.gradients(sc, cam, *masked_upstream(name), mask_near=False, straight_through=True)["full"]
 
 
 def float32_errors(name):

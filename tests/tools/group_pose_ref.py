@@ -25,14 +25,14 @@ def pose(P, G, gid):
     return dict(means=means, op=P["op"], colors=P["colors"], cov6=cov6)
 
 
-def forward(sc, cam, dtype=torch.float64, Rt=None, G=None):
+def forward(sc, cam, dtype=torch.float64, Rt=None, G=None, straight_through=False):
     """(leaves P, pose leaf G [n_groups,3,4], viewmat leaf [3,4], intermediates, raw frame)."""
     V, K, W, H = cam
     P = grad_ref.leaves(sc, dtype)
     if G is None:
         G = torch.tensor(np.asarray(sc["Rt"] if Rt is None else Rt, np.float64).reshape(-1, 3, 4), dtype=dtype, requires_grad=True)
     vm = torch.tensor(np.asarray(V, np.float64).reshape(4, 4)[:3], dtype=dtype, requires_grad=True)
-    I = grad_ref.project(pose(P, G, sc["gid"]), vm, K, W, H, sc["sh"], None, None)
+    I = grad_ref.project(pose(P, G, sc["gid"]), vm, K, W, H, sc["sh"], None, None, straight_through)
     F = grad_ref.render(I, I["valid"], I["radii"], W, H)
     return P, G, vm, I, F
 
@@ -48,10 +48,10 @@ def _full(P, G, vm):
     return full
 
 
-def gradients(sc, cam, g_rgb=None, g_alpha=None, g_depth=None, dtype=torch.float64, Rt=None, mask_near=True):
+def gradients(sc, cam, g_rgb=None, g_alpha=None, g_depth=None, dtype=torch.float64, Rt=None, mask_near=True, straight_through=False):
     """grad_ref.gradients with the poses as a variable: {"full": means, opacities, colors, viewmat, quats + scales | covariances,
-    group_poses [n_groups,3,4]; "near"; "valid"; "margin"; "loss"}."""
-    P, G, vm, I, F = forward(sc, cam, dtype, Rt)
+    group_poses [n_groups,3,4]; "near"; "valid"; "margin"; "loss"}.  ``straight_through``: grad_ref.project's mutant."""
+    P, G, vm, I, F = forward(sc, cam, dtype, Rt, straight_through=straight_through)
     keep = (~F["near"]).to(dtype) if mask_near else torch.ones_like(F["alpha"])
     loss = torch.zeros((), dtype=dtype)
     for g, f in ((g_rgb, F["acc_rgb"]), (g_alpha, F["alpha"]), (g_depth, F["acc_z"])):

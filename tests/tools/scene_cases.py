@@ -11,7 +11,8 @@ ROOT = Path(__file__).resolve().parent.parent.parent
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 import oracle  # noqa: E402
-from sim_a_splat_amd.synthetic import config_scene_and_cameras, make_scene, random_group_poses, ring_camera  # noqa: E402
+from sim_a_splat_amd.synthetic import (config_scene_and_cameras, intrinsics, look_at_viewmat, make_scene, random_group_poses,  # noqa: E402
+                                       ring_camera)
 
 GOLDEN = ROOT / "tests" / "golden"
 OUTS = ("rgb", "alpha", "depth", "rgb8")
@@ -52,6 +53,16 @@ def config3_window():
 def ring(W=96, H=64, f=90.0, yaw=15.0, elev=0.2):
     c = ring_camera(W, H, f, yaw_deg=yaw, elev=elev)
     return np.asarray(c.viewmat, np.float32), np.asarray(c.K, np.float32), W, H
+
+
+def general(W, H, fx, fy, cx, cy, eye, target=(0.0, 0.0, 0.0), roll_deg=0.0):
+    """A pinhole camera with its own fx, fy and principal point, at ``eye`` looking at ``target``, rolled by ``roll_deg`` about its
+    optical axis: V = Rz(roll) look_at(eye, target)."""
+    a = np.deg2rad(roll_deg)
+    Rz = np.eye(4)
+    Rz[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+    V = Rz @ np.asarray(look_at_viewmat(eye, target), np.float64)
+    return V.astype(np.float32), np.asarray(intrinsics(fx, fy, cx, cy), np.float32), W, H
 
 
 def oracle_frame(sc, cam, bg, keep=None, Rt=None, **kw):
