@@ -692,6 +692,58 @@ int sas_scene_densify_times(sas_ctx *ctx, float *ms, int n);
 int sas_scene_reset_opacity(sas_ctx *ctx, float max_opacity, void *stream);
 
 /*
+ * MCMC density control on the resident scene ("MCMC density control"): the strategy of "3D Gaussian Splatting as Markov
+ * Chain Monte Carlo" (Kheradmand et al. 2024) in the form of gsplat's MCMCStrategy -- the number of Gaussians is a budget.  It needs no
+ * gradient statistics.
+ *
+ * sas_scene_mcmc_noise moves every mean by noise shaped by the Gaussian's own covariance and switched off by its opacity.  For the
+ * Gaussian with CALLER's index i, all in float32, nothing fused:
+ *   g = 1 / (1 + expf(-100 ((1 - o) - 0.995)))        (an overflow of expf makes g exactly 0: the mean keeps its bits)
+ *   n_k = (xi_k g) scale,   xi three standard normals of the counter-based generator keyed by (seed, step, i, axis)
+ *   mean_k += (C_k0 n_0 + C_k1 n_1) + C_k2 n_2,   C = M M^T, M = R(q / |q|) diag(s); for a scene uploaded as cov6, C is the stored one.
+ * The key holds the caller's index, never the slot: the result does not depend on the storage order.  Only the means change; the
+ * optimiser state is not touched.  The call only enqueues on `stream`, behind the frames in flight; it invalidates the last frame as
+ * sas_scene_adam_step does.  scale == 0 changes nothing.  SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID for a negative or
+ * non-finite scale and for step < 1.
+ */
+int sas_scene_mcmc_noise(sas_ctx *ctx, float scale, int step, unsigned seed, void *stream);
+
+/*
+ * sas_scene_mcmc_refine replaces the resident scene of N Gaussians by one of N_new = N + n_grow: dead Gaussians are re-born on alive
+ * ones, and the set grows towards cap_max.  Every decision is made on the OLD set, in ONE pass (gsplat relocates, then samples again
+ * for the growth; here both draw from the same old opacities).
+ *   DEAD     o <= min_opacity, or NaN; alive otherwise.   n_grow = max(0, min(cap_max, (int64)floor(grow_factor N)) - N), in binary64.
+ *   DRAWS    D = n_dead + n_grow, proportional to opacity, exactly: w_i = alive ? (uint32)(o_i 2^24) : 0; P_i the inclusive prefix of w
+ *            in the caller's order (uint64); draw d takes the 64-bit u_d of the generator keyed by (seed, d), t = mulhi64(u_d, total),
+ *            and selects the i with P_(i-1) <= t < P_i.  copies_i = the draws that selected i.
+ *            (An opacity above 1 is outside the contract; it weighs as 1.)
+ *   SOURCES  copies_i > 0 (gsplat's compute_relocation): n = min(copies_i + 1, 51), o' = 1 - (1 - o)^(1/n),
+ *            denom = sum_{i=1..n} sum_{k=0..i-1} C(i-1, k) (-1)^k o'^(k+1) / sqrt(k+1), both in binary64 in that order; o' and o / denom
+ *            rounded once to float32; o' <- min(max(o', min_opacity), 1 - FLT_EPSILON); scale' = (o / denom) scale per axis in float32.
+ *   NEW SCENE, in the new caller's order: the alive Gaussians in their old order (a source carries o' and scale', everything else bit
+ *            for bit), then D children in draw order, each a bit-identical copy of its modified source, mean included (the noise
+ *            separates them afterwards).  Group ids are inherited.
+ *   OPTIMISER STATE  an alive Gaussian that is no source keeps moments and raw values bit for bit; sources and children get zero moments
+ *            in every group (gsplat leaves a relocated Gaussian's moments in place) and fresh raw values from their new resident values.
+ *   parents_out_or_null  int32 DEVICE with room for max(N, min(cap_max, floor(grow_factor N))) entries; [0, N_new) <- each new Gaussian's
+ *            old index.   counts_out  HOST: (N_new, relocated = n_dead, added = n_grow).
+ * D == 0 leaves the scene untouched: parents = 0 .. N-1, counts (N, 0, 0).  Otherwise storage order, feature store, last frame, group
+ * poses, link constants, meshes and sh_degree are treated as sas_scene_densify treats them.  Blocking; completes the frames in flight.
+ * SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID -- the scene stays as it was -- for cfg / counts_out NULL, min_opacity outside
+ * [0, 1) (NaN included), cap_max < 1 or > 2^31 - 256, grow_factor < 1 or not finite, a cov6 scene (it has no scales to relocate), an
+ * empty scene, and no alive Gaussian.
+ */
+typedef struct sas_mcmc_config {
+    int64_t cap_max;       /* the budget, >= 1 */
+    double grow_factor;    /* 1.05 */
+    float min_opacity;     /* 0.005 */
+    unsigned seed;
+} sas_mcmc_config;
+/* (sas_scene_densify_times then reports this call's laps: the weights and their totals' read-back; the draws, the rows and the read-back
+ * of the new means and group ids; the storage order; allocation, relayout, state and commit.) */
+int sas_scene_mcmc_refine(sas_ctx *ctx, const sas_mcmc_config *cfg, int32_t *parents_out_or_null, int64_t counts_out[3], void *stream);
+
+/*
  * Photometric loss of 3DGS training and its gradient ("Photometric loss"): for a delivered frame x = rgb [H,W,3] and a
  * target y [H,W,3] (float32 DEVICE, 0..1) and an optional mask w [H,W] (uint8 DEVICE, non-zero counts; NULL: every pixel counts),
  *   loss = (1 - lambda) l1 + lambda (1 - ssim),   l1 = sum w |x - y| / D,   ssim = sum w ssim_p / D,   mse = sum w (x - y)^2 / D,

@@ -35,7 +35,7 @@ STAT_NAMES = ("n_visible", "n_isect", "max_tile_len", "capacity", "regrows", "wi
 
 # every symbol include/sim_a_splat_amd.h declares
 EXPORTS = (
-    "sas_create", "sas_destroy", "sas_scene_upload", "sas_set_group_poses", "sas_set_link_constants", "sas_set_link_poses", "sas_get_group_poses", "sas_link_attached_frame", "sas_link_group_poses", "sas_attached_frame", "sas_camera_matrices", "sas_render_cameras_host", "sas_render", "sas_render_rgbd", "sas_scene_features", "sas_render_features", "sas_scene_meshes", "sas_scene_mesh_features", "sas_scene_mesh_vertex_attributes", "sas_query_meshes", "sas_match_points", "sas_sample_points", "sas_fuse_depth", "sas_render_batch", "sas_render_batch_host", "sas_render_batch_posed", "sas_render_batch_host_posed", "sas_render_batch_labels", "sas_render_batch_labels_posed", "sas_lift_labels", "sas_lift_features", "sas_render_backward_screen", "sas_render_backward", "sas_render_backward_poses", "sas_scene_adam_step", "sas_scene_adam_reset", "sas_density_accumulate", "sas_scene_densify", "sas_scene_densify_times", "sas_scene_reset_opacity", "sas_photometric_loss", "sas_scene_read", "sas_wait", "sas_frames_completed",
+    "sas_create", "sas_destroy", "sas_scene_upload", "sas_set_group_poses", "sas_set_link_constants", "sas_set_link_poses", "sas_get_group_poses", "sas_link_attached_frame", "sas_link_group_poses", "sas_attached_frame", "sas_camera_matrices", "sas_render_cameras_host", "sas_render", "sas_render_rgbd", "sas_scene_features", "sas_render_features", "sas_scene_meshes", "sas_scene_mesh_features", "sas_scene_mesh_vertex_attributes", "sas_query_meshes", "sas_match_points", "sas_sample_points", "sas_fuse_depth", "sas_render_batch", "sas_render_batch_host", "sas_render_batch_posed", "sas_render_batch_host_posed", "sas_render_batch_labels", "sas_render_batch_labels_posed", "sas_lift_labels", "sas_lift_features", "sas_render_backward_screen", "sas_render_backward", "sas_render_backward_poses", "sas_scene_adam_step", "sas_scene_adam_reset", "sas_density_accumulate", "sas_scene_densify", "sas_scene_densify_times", "sas_scene_reset_opacity", "sas_scene_mcmc_noise", "sas_scene_mcmc_refine", "sas_photometric_loss", "sas_scene_read", "sas_wait", "sas_frames_completed",
     "sas_last_error", "sas_stage_times", "sas_stage_time_means", "sas_frame_stats", "sas_read_projection", "sas_read_tile_lists",
     "sas_version",
 )
@@ -60,6 +60,11 @@ class DensifyConfig(ctypes.Structure):
     """sas_densify_config of include/sim_a_splat_amd.h."""
     _fields_ = [(k, ctypes.c_float) for k in ("grow_grad2d", "grow_scale3d", "prune_opacity", "prune_scale3d", "scene_extent", "split_factor")] + \
                [("max_gaussians", ctypes.c_int64), ("seed", ctypes.c_uint), ("flags", ctypes.c_uint)]
+
+
+class McmcConfig(ctypes.Structure):
+    """sas_mcmc_config of include/sim_a_splat_amd.h."""
+    _fields_ = [("cap_max", ctypes.c_int64), ("grow_factor", ctypes.c_double), ("min_opacity", ctypes.c_float), ("seed", ctypes.c_uint)]
 
 
 class SasError(RuntimeError):
@@ -126,6 +131,8 @@ def lib() -> ctypes.CDLL:
     L.sas_scene_densify.argtypes = [vp, ctypes.POINTER(DensifyConfig), vp, vp, vp, vp, vp]
     L.sas_scene_densify_times.argtypes = [vp, vp, ci]
     L.sas_scene_reset_opacity.argtypes = [vp, cf, vp]
+    L.sas_scene_mcmc_noise.argtypes = [vp, cf, ci, cu, vp]
+    L.sas_scene_mcmc_refine.argtypes = [vp, ctypes.POINTER(McmcConfig), vp, vp, vp]
     L.sas_photometric_loss.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp]
     L.sas_scene_read.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.sas_wait.argtypes = [vp]

@@ -301,9 +301,10 @@ struct sas_ctx : Settings {
     Event adam_done;      // recorded behind a step on the caller's stream: the slots' streams wait for it
     DevBuf grad_screen;   // sas_render_backward: [10 n] screen-space sums + [ceil(n / 256)][12] view-matrix rows (SasGradProj)
     int grad_frame = 0;   // the last frame is a backward frame: 1 of sas_render_backward_screen, 2 of sas_render_backward (grad_screen holds its sums); 0: none
-    Event density_done;   // recorded behind sas_density_accumulate / sas_scene_reset_opacity on the caller's stream: the slots' streams wait for it
-    DevBuf density_inv, density_cls, density_blk;   // scratch of sas_scene_densify (SasDensity)
-    float densify_ms[4] = {0, 0, 0, 0};   // host clock of the last sas_scene_densify: classes, scatter, storage_order, relayout + state + commit
+    Event density_done;   // recorded behind sas_density_accumulate / sas_scene_reset_opacity / sas_scene_mcmc_noise on the caller's stream: the slots' streams wait for it
+    DevBuf density_inv, density_cls, density_blk;   // scratch of sas_scene_densify (SasDensity); sas_scene_mcmc_refine shares inv and blk
+    DevBuf mcmc_u32, mcmc_u64, mcmc_reloc;          // scratch of sas_scene_mcmc_refine (SasMcmc): weight | copies, prefix, reloc
+    float densify_ms[4] = {0, 0, 0, 0};   // host clock of the last sas_scene_densify / sas_scene_mcmc_refine: classes, scatter, storage_order, relayout + state + commit
     DevBuf loss_scratch;  // sas_photometric_loss: [9 H W] partial planes + [tiles][4] workgroup sums + D (SasLoss)
     int match_cus = 0;   // compute units of the device, asked once (the slice count of sas_match_points)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
@@ -2617,6 +2618,72 @@ int sas_density_accumulate(sas_ctx *c, int width, int height, const float *d_mea
     return slots_wait_for(c, c->density_done, st);   // (the next frame of that slot writes its info records anew)
 }
 
+// The host clock of a densify or refine call, lap by lap (sas_scene_densify_times).
+struct Laps {
+    using clock = std::chrono::steady_clock;
+    float *ms;
+    clock::time_point t0 = clock::now();
+    void operator()(int k)
+    {
+        const auto t1 = clock::now();
+        ms[k] = std::chrono::duration<float, std::milli>(t1 - t0).count();
+        t0 = t1;
+    }
+};
+
+// The rows of a new scene in the caller's order (device, as sas_scene_upload takes them), each new Gaussian's old index, and which rows
+// start their optimiser state anew: the ones `fresh` marks, or (nullptr) the ones from n_survivors on.
+struct NewRows {
+    int64_t n;
+    const float *means, *quats, *scales, *cov6, *opac, *colors;
+    const uint8_t *gid;       // or nullptr: no groups
+    const int *parents;
+    const uint8_t *fresh;
+    int64_t n_survivors;
+};
+
+// The tail sas_scene_densify and sas_scene_mcmc_refine share: the storage order of the new rows (on the host, as for an upload), new planes
+// and new optimiser state beside the old ones, relayout, the carried state, and the swap.  inv_old: caller's index -> old slot.  Laps 1 to 3
+// are taken here.  Nothing changes the context before the last wait: a failure leaves the scene as it was.
+static int commit_rows(sas_ctx *c, const NewRows &r, const int *inv_old, hipStream_t st, Laps &lap)
+{
+    const SasScene sc = c->scene;
+    const int coeff_floats = sas_coeff_floats(sc.sh_degree), planes = sas_colour_planes(sc.sh_degree);
+    int rc;
+    OrderInput in;
+    if ((rc = in.fetch(c, r.n, r.means, r.gid, true, st))) return rc;
+    lap(1);
+    Planes np;
+    Adam na;
+    in.order(np.perm_host);
+    lap(2);
+    if ((rc = np.alloc(c, r.n, planes))) return rc;
+    std::copy(c->adam.on, c->adam.on + Adam::GROUPS, na.on);
+    for (int k = 0; k < Adam::kRows; ++k)   // (every buffer zeroed: the lanes n .. n_pad)
+        if (na.on[Adam::rows[k].group] && (rc = na.alloc(c, k, np.n_pad, planes, st, true))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(np.perm.p, np.perm_host.data(), sizeof(int) * (size_t)r.n, hipMemcpyHostToDevice, st));
+    sas_launch_relayout(st, r.n, np.n_pad, (const int *)np.perm.p, r.means, r.quats, r.scales, r.cov6, r.opac, r.colors, coeff_floats, planes,
+                        r.gid, (float4 *)np.g0.p, (float4 *)np.g1.p, (float4 *)np.g2.p, (float4 *)np.col.p, (uint8_t *)np.gid8.p);
+    SasDensityState s{};
+    s.perm_new = (const int *)np.perm.p; s.parents = r.parents; s.inv_old = inv_old;
+    s.g0_new = (const float4 *)np.g0.p; s.g2_new = (const float4 *)np.g2.p;
+    s.n_new = r.n; s.n_survivors = r.n_survivors; s.n_old = sc.n; s.n_pad_old = sc.n_pad; s.n_pad_new = np.n_pad;
+    s.planes = planes;
+    s.old_ = c->adam.view();
+    s.new_ = na.view();
+    sas_launch_density_state(st, s, r.fresh);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+
+    // the context takes the new scene (the old buffers go with this scope)
+    std::swap(c->planes, np);
+    std::swap(c->adam, na);
+    c->planes.bind(c->scene);
+    scene_changed(c, Changed::CountAndOrder);
+    lap(3);
+    return SAS_OK;
+}
+
 // Densify, prune and re-order (sas_density.hip).  Host work: validation, two read-backs (the class totals; the new means and group ids
 // for storage_order), the allocations.  Everything the new scene needs is allocated before the context changes.
 int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *grad_sum, const int32_t *count, int32_t *parents_out,
@@ -2662,13 +2729,7 @@ int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *gr
     q.blk_off = q.blk_count + 3 * nb;
     q.totals = q.blk_off + 3 * nb;
     q.nb = (long long)nb;
-    using clock = std::chrono::steady_clock;
-    auto t0 = clock::now();
-    auto lap = [&](int k) {
-        const auto t1 = clock::now();
-        c->densify_ms[k] = std::chrono::duration<float, std::milli>(t1 - t0).count();
-        t0 = t1;
-    };
+    Laps lap{c->densify_ms};
     sas_launch_density_classes(st, q);
     HIP_TRY(c, hipGetLastError());
     unsigned totals[3] = {0, 0, 0};
@@ -2693,42 +2754,115 @@ int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *gr
     q.n_new = pl.n_new;
     sas_launch_density_scatter(st, q);
     HIP_TRY(c, hipGetLastError());
-    // its storage order, on the host as for an upload
-    OrderInput in;
-    if ((rc = in.fetch(c, pl.n_new, q.means, q.gid, true, st))) return rc;
-    lap(1);
-    Planes np;   // new planes and new state, beside the old ones
-    Adam na;
-    in.order(np.perm_host);
-    lap(2);
-    if ((rc = np.alloc(c, pl.n_new, planes))) return rc;
-    std::copy(c->adam.on, c->adam.on + Adam::GROUPS, na.on);
-    for (int k = 0; k < Adam::kRows; ++k)   // (every buffer zeroed: the lanes n .. n_pad)
-        if (na.on[Adam::rows[k].group] && (rc = na.alloc(c, k, np.n_pad, planes, st, true))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(np.perm.p, np.perm_host.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
-    sas_launch_relayout(st, pl.n_new, np.n_pad, (const int *)np.perm.p, q.means, q.quats, q.scales, q.cov6, q.opac, q.colors, coeff_floats, planes,
-                        q.gid, (float4 *)np.g0.p, (float4 *)np.g1.p, (float4 *)np.g2.p, (float4 *)np.col.p, (uint8_t *)np.gid8.p);
-    SasDensityState s{};
-    s.perm_new = (const int *)np.perm.p; s.parents = q.parents; s.inv_old = q.inv;
-    s.g0_new = (const float4 *)np.g0.p; s.g2_new = (const float4 *)np.g2.p;
-    s.n_new = pl.n_new; s.n_survivors = pl.survivors; s.n_old = sc.n; s.n_pad_old = sc.n_pad; s.n_pad_new = np.n_pad;
-    s.planes = planes;
-    s.old_ = c->adam.view();
-    s.new_ = na.view();
-    sas_launch_density_state(st, s);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(st));   // (nothing above has changed the context: a failure so far leaves the scene as it was)
-
-    // the context takes the new scene (the old buffers go with this scope)
-    std::swap(c->planes, np);
-    std::swap(c->adam, na);
-    c->planes.bind(c->scene);
-    scene_changed(c, Changed::CountAndOrder);
+    NewRows rows{pl.n_new, q.means, q.quats, q.scales, q.cov6, q.opac, q.colors, q.gid, q.parents, nullptr, pl.survivors};
+    if ((rc = commit_rows(c, rows, q.inv, st, lap))) return rc;
     counts_out[0] = pl.n_new;
     counts_out[1] = pl.clones;
     counts_out[2] = pl.splits;
     counts_out[3] = sc.n - (long long)totals[0];
-    lap(3);
+    return SAS_OK;
+}
+
+// Noise on the means (k_mcmc_noise).  Host work: validation, one launch, one event.
+int sas_scene_mcmc_noise(sas_ctx *c, float scale, int step, unsigned seed, void *stream)
+{
+    const char *who = "sas_scene_mcmc_noise";
+    if (const int rc = need_scene(c, who)) return rc;
+    if (const int rc = check_rate(c, who, "scale", scale)) return rc;
+    if (step < 1) return fail(c, SAS_ERR_INVALID, "%s: step %d < 1 (the count is 1-based)", who, step);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;   // (no frame reads the planes while they change)
+    if (c->scene.n <= 0 || scale == 0.0f) return SAS_OK;   // nothing moves: the last frame stays valid
+    SasMcmcNoise q{};
+    q.g0 = (float4 *)c->planes.g0.p; q.g1 = c->scene.g1; q.g2 = c->scene.g2;
+    q.perm = c->scene.perm;
+    q.n = c->scene.n;
+    q.cov_mode = c->scene.cov_mode;
+    q.scale = scale; q.seed = seed; q.step = (unsigned)step;
+    hipStream_t st = (hipStream_t)stream;
+    sas_launch_mcmc_noise(st, q);
+    HIP_TRY(c, hipGetLastError());
+    if (const int rc = slots_wait_for(c, c->density_done, st)) return rc;
+    scene_changed(c, Changed::Values);
+    return SAS_OK;
+}
+
+// Relocate and grow (sas_mcmc.hip).  Host work: validation, two read-backs (the totals; the new means and group ids for storage_order),
+// the allocations, and the tail it shares with sas_scene_densify.
+int sas_scene_mcmc_refine(sas_ctx *c, const sas_mcmc_config *cfg, int32_t *parents_out, int64_t counts_out[3], void *stream)
+{
+    const char *who = "sas_scene_mcmc_refine";
+    if (const int rc = need_scene(c, who)) return rc;
+    if (!cfg || !counts_out) return fail(c, SAS_ERR_INVALID, "%s: cfg and counts_out are required", who);
+    if (!(cfg->min_opacity >= 0.0f && cfg->min_opacity < 1.0f)) return fail(c, SAS_ERR_INVALID, "%s: min_opacity %g outside [0, 1)", who, (double)cfg->min_opacity);
+    if (cfg->cap_max < 1 || cfg->cap_max > 0x7fffffffll - 256) return fail(c, SAS_ERR_INVALID, "%s: cap_max %lld out of range", who, (long long)cfg->cap_max);
+    if (!(cfg->grow_factor >= 1.0 && cfg->grow_factor < (double)INFINITY)) return fail(c, SAS_ERR_INVALID, "%s: grow_factor %g < 1 or not finite", who, cfg->grow_factor);
+    if (c->scene.cov_mode) return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as covariances, which have no scales to relocate", who);
+    const SasScene sc = c->scene;
+    if (sc.n <= 0) return fail(c, SAS_ERR_INVALID, "%s: the scene is empty", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int coeff_floats = sas_coeff_floats(sc.sh_degree), planes = sas_colour_planes(sc.sh_degree);
+    const size_t n = (size_t)sc.n, nb = (n + 255) / 256;
+    int rc;
+    // scratch: inv | weight, copies (4 n each) | prefix (8 n) | reloc (16 n) | the workgroup sums, their offsets and the totals
+    if ((rc = ensure(c, {{c->density_inv, sizeof(int) * n}, {c->mcmc_u32, sizeof(unsigned) * 2 * n}, {c->mcmc_u64, sizeof(unsigned long long) * n},
+                         {c->mcmc_reloc, sizeof(float4) * n}, {c->density_blk, sizeof(unsigned long long) * (3 * nb + 2)}}))) return rc;
+    SasMcmc q{};
+    q.g0 = sc.g0; q.g1 = sc.g1; q.g2 = sc.g2; q.col = sc.col; q.gid8 = sc.gid8;
+    q.inv = (const int *)c->density_inv.p;
+    q.n = sc.n; q.n_pad = sc.n_pad;
+    q.coeff_floats = coeff_floats; q.planes = planes;
+    q.min_opacity = cfg->min_opacity; q.seed = cfg->seed;
+    q.weight = (unsigned *)c->mcmc_u32.p; q.copies = q.weight + n;
+    q.prefix = (unsigned long long *)c->mcmc_u64.p;
+    q.reloc = (float4 *)c->mcmc_reloc.p;
+    q.blk_weight = (unsigned long long *)c->density_blk.p; q.blk_weight_off = q.blk_weight + nb; q.totals = q.blk_weight_off + nb;
+    q.blk_alive = (unsigned *)(q.totals + 2); q.blk_alive_off = q.blk_alive + nb;
+    q.nb = (long long)nb;
+    Laps lap{c->densify_ms};
+    sas_launch_density_inverse(st, sc.n, sc.perm, (int *)c->density_inv.p);
+    sas_launch_mcmc_weights(st, q);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long totals[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(totals, q.totals, sizeof(totals), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (totals[0] == 0 || totals[1] == 0) return fail(c, SAS_ERR_INVALID, "%s: no alive Gaussian (opacity > %g): refused, the scene stays", who, (double)cfg->min_opacity);
+    const SasMcmcPlan pl = sas_mcmc_plan(sc.n, (long long)totals[0], cfg->cap_max, cfg->grow_factor);
+    lap(0);
+    if (pl.draws == 0) {   // nothing to do: the scene, its order and its state stay
+        if (parents_out) {
+            sas_launch_mcmc_identity(st, sc.n, parents_out);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipStreamSynchronize(st));
+        }
+        for (int k = 1; k < 4; ++k) c->densify_ms[k] = 0.0f;
+        counts_out[0] = sc.n; counts_out[1] = 0; counts_out[2] = 0;
+        return SAS_OK;
+    }
+    // the new scene in the caller's order
+    const size_t m = (size_t)pl.n_new;
+    DevBuf a_means, a_q, a_s, a_op, a_col, a_gid, a_par, a_fresh, a_src;
+    if ((rc = ensure(c, {{a_means, sizeof(float) * 3 * m}, {a_q, sizeof(float) * 4 * m}, {a_s, sizeof(float) * 3 * m}, {a_op, sizeof(float) * m},
+                         {a_col, sizeof(float) * (size_t)coeff_floats * m}, {a_fresh, m}, {a_src, sizeof(int) * (size_t)pl.draws}}))) return rc;
+    if (sc.n_groups > 0 && (rc = ensure(c, a_gid, m))) return rc;
+    if (!parents_out && (rc = ensure(c, a_par, sizeof(int) * m))) return rc;
+    q.n_alive = (long long)totals[0]; q.draws = pl.draws; q.n_new = pl.n_new;
+    q.total_weight = totals[1];
+    q.source = (int *)a_src.p;
+    q.means = (float *)a_means.p; q.quats = (float *)a_q.p; q.scales = (float *)a_s.p; q.opac = (float *)a_op.p; q.colors = (float *)a_col.p;
+    q.gid = (uint8_t *)a_gid.p;
+    q.parents = parents_out ? parents_out : (int *)a_par.p;
+    q.fresh = (uint8_t *)a_fresh.p;
+    HIP_TRY(c, hipMemsetAsync(q.copies, 0, sizeof(unsigned) * n, st));
+    sas_launch_mcmc_rows(st, q);
+    HIP_TRY(c, hipGetLastError());
+    NewRows rows{pl.n_new, q.means, q.quats, q.scales, nullptr, q.opac, q.colors, q.gid, q.parents, q.fresh, 0};
+    if ((rc = commit_rows(c, rows, q.inv, st, lap))) return rc;
+    counts_out[0] = pl.n_new;
+    counts_out[1] = pl.n_dead;
+    counts_out[2] = pl.n_grow;
     return SAS_OK;
 }
 
@@ -2863,7 +2997,7 @@ int sas_frames_completed(sas_ctx *c, int64_t *submitted, int64_t *completed)
 
 #ifdef SAS_DEBUG_BOUNDS
 // every kernel file's counter (SAS_BOUNDS_ACCESSOR in sas_device.h): one line per file, in the order their reports are looked at
-#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density)
+#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density) X(mcmc)
 #define SAS_BOUNDS_DECLARE(name) extern "C" int sas_debug_bounds_##name(unsigned long long *out, int reset);
 #define SAS_BOUNDS_ENTRY(name) sas_debug_bounds_##name,
 SAS_BOUNDS_FILES(SAS_BOUNDS_DECLARE)

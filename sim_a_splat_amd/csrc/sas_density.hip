@@ -10,6 +10,7 @@
 //   k_density_scatter     the grid of k_density_flag again: rank in class = offset + rank in workgroup (ballots), then the new scene's
 //                         rows in the caller's order (AoS, what sas_scene_upload takes) and `parents`: survivors, clones, pairs of children.
 //   k_density_state       one lane per NEW storage slot: the optimiser state of its parent's old slot, or a fresh one.
+//   k_density_state_fresh   behind it, the rows a mask marks started anew (sas_scene_mcmc_refine).
 //   k_opacity_reset       one lane per storage slot: min(opacity, cap), and the opacity state of the lanes it changed.
 // The planes of the new scene are laid out by k_relayout, as an upload lays them out.  The split between kernels is the one of
 // sas_cloud.hip's compaction: no kernel waits for another workgroup, no look-back, no atomics.
@@ -112,22 +113,11 @@ __global__ __launch_bounds__(kThreads) void k_density_scan(const SasDensity q)
 }
 
 // ---- the children of a split ------------------------------------------------------------------------------------------------------
-// A stateless generator: a 32-bit integer hash (two xorshift-multiply rounds) of (seed, parent, counter), two hashes per normal, Box-Muller.
-DEV unsigned mix32(unsigned x)
-{
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
+// The generator of sas_device.h keyed by (seed, parent, counter).
 DEV float density_normal(unsigned seed, unsigned parent, int child, int axis)
 {
     const unsigned base = mix32(mix32(seed ^ 0x9e3779b9u) + parent);
-    const unsigned c = 2u * (unsigned)(3 * child + axis);
-    const unsigned h1 = mix32(base ^ ((c + 1u) * 0x9e3779b9u)), h2 = mix32(base ^ ((c + 2u) * 0x9e3779b9u));
-    const float u1 = (float)((h1 >> 8) + 1u) * 5.9604644775390625e-8f;   // (0, 1], a multiple of 2^-24
-    const float u2 = (float)(h2 >> 8) * 5.9604644775390625e-8f;          // [0, 1)
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
+    return hashed_normal(base, 2u * (unsigned)(3 * child + axis));
 }
 
 // row `pos` of the new scene: Gaussian `i` (old slot j) with the mean and the scale given
@@ -239,6 +229,33 @@ __global__ __launch_bounds__(kThreads) void k_density_state(const SasDensityStat
         }
 }
 
+// Behind k_density_state run with n_survivors = n_new (every row takes its parent's state): the rows `mask` marks start anew -- zero
+// moments, raw values from the new planes (sas_scene_mcmc_refine: its fresh rows lie among the others).
+__global__ __launch_bounds__(kThreads) void k_density_state_fresh(const SasDensityState q, const uint8_t *mask)
+{
+    const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;   // new slot
+    if (j >= q.n_new) return;
+    const long long i = q.perm_new[j];                                    // new caller's index
+    if (!SAS_IN(i, q.n_new, 1015) || !SAS_IN(j, q.n_pad_new, 1016) || !mask[i]) return;
+    const SasAdamState &s = q.new_;
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (s.means_m) { s.means_m[j] = zero; s.means_v[j] = zero; }
+    if (s.quats_m) { s.quats_m[j] = zero; s.quats_v[j] = zero; }
+    if (s.opac) s.opac[j] = make_float4(0.0f, 0.0f, raw_opacity(q.g0_new[j].w), 0.0f);
+    if (s.scales_m) {
+        const float4 G = q.g2_new[j];
+        s.scales_m[j] = zero;
+        s.scales_v[j] = zero;
+        s.scales_raw[j] = make_float4(raw_scale(G.x), raw_scale(G.y), raw_scale(G.z), 0.0f);
+    }
+    if (s.sh_m)
+        for (int pl = 0; pl < q.planes; ++pl) {
+            const long long on = (long long)pl * q.n_pad_new + j;
+            s.sh_m[on] = zero;
+            s.sh_v[on] = zero;
+        }
+}
+
 __global__ __launch_bounds__(kThreads) void k_opacity_reset(long long n, float cap, float4 *g0, float4 *opac)
 {
     const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -261,6 +278,12 @@ void sas_launch_density_accumulate(hipStream_t st, const SasDensityStats &q)
     hipLaunchKernelGGL(k_density_accumulate, dim3(grid_of(q.n)), dim3(kThreads), 0, st, q);
 }
 
+void sas_launch_density_inverse(hipStream_t st, int64_t n, const int *perm, int *inv)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_density_inverse, dim3(grid_of(n)), dim3(kThreads), 0, st, (long long)n, perm, inv);
+}
+
 void sas_launch_density_classes(hipStream_t st, const SasDensity &q)
 {
     if (q.n <= 0) return;
@@ -275,10 +298,13 @@ void sas_launch_density_scatter(hipStream_t st, const SasDensity &q)
     hipLaunchKernelGGL(k_density_scatter, dim3((unsigned)q.nb), dim3(kThreads), 0, st, q);
 }
 
-void sas_launch_density_state(hipStream_t st, const SasDensityState &q)
+void sas_launch_density_state(hipStream_t st, const SasDensityState &q, const uint8_t *fresh)
 {
     if (q.n_new <= 0) return;
-    hipLaunchKernelGGL(k_density_state, dim3(grid_of(q.n_new)), dim3(kThreads), 0, st, q);
+    SasDensityState all = q;
+    if (fresh) all.n_survivors = q.n_new;
+    hipLaunchKernelGGL(k_density_state, dim3(grid_of(q.n_new)), dim3(kThreads), 0, st, all);
+    if (fresh) hipLaunchKernelGGL(k_density_state_fresh, dim3(grid_of(q.n_new)), dim3(kThreads), 0, st, q, fresh);
 }
 
 void sas_launch_opacity_reset(hipStream_t st, int64_t n, float cap, float4 *g0, float4 *opac)

@@ -1,4 +1,4 @@
-// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip and sas_density.hip.
+// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip and sas_mcmc.hip.
 // Everything here follows the arithmetic contract of DESIGN.md: IEEE binary32 operations, fused
 // only where fma_() is written (translation units are built with -ffp-contract=off).
 #pragma once
@@ -63,6 +63,24 @@ DEV float4 nt_load(const float4 *p)
 // value outside the domain -- an opacity outside (0, 1), a scale that is no positive finite number: that variable stays fixed.
 DEV float raw_opacity(float o) { return (o > 0.0f && o < 1.0f) ? logf(o / (1.0f - o)) : NAN; }
 DEV float raw_scale(float s) { return (s > 0.0f && s < INFINITY) ? logf(s) : NAN; }
+
+// ---- the counter-based generator (sas_density.hip, sas_mcmc.hip) ------------------------------------------------------------
+// Stateless: a 32-bit integer hash (two xorshift-multiply rounds) of the key, two hashes per normal, Box-Muller.  `base` is the hash of
+// everything in the key but the counter `c` (even: the normal uses c + 1 and c + 2).
+DEV unsigned mix32(unsigned x)
+{
+    x ^= x >> 16; x *= 0x7feb352du;
+    x ^= x >> 15; x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+DEV float hashed_normal(unsigned base, unsigned c)
+{
+    const unsigned h1 = mix32(base ^ ((c + 1u) * 0x9e3779b9u)), h2 = mix32(base ^ ((c + 2u) * 0x9e3779b9u));
+    const float u1 = (float)((h1 >> 8) + 1u) * 5.9604644775390625e-8f;   // (0, 1], a multiple of 2^-24
+    const float u2 = (float)(h2 >> 8) * 5.9604644775390625e-8f;          // [0, 1)
+    return sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
+}
 
 // ---- wave64 reductions and scan on the DPP network --------------------------------------------------------------------------------
 // hipcc lowers __shfl_xor / __shfl_up to ds_bpermute_b32: a trip through the LDS crossbar per step, six DEPENDENT trips per reduction

@@ -1,6 +1,7 @@
-// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip, sas_mcmc.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -632,6 +633,71 @@ struct SasDensityState {
     int planes;
     SasAdamState old_, new_;   // (old_ is only read)
 };
-void sas_launch_density_state(hipStream_t st, const SasDensityState &q);
+// fresh: [n_new] in the new caller's order, non-zero marks the fresh rows (sas_scene_mcmc_refine); nullptr: the rows from n_survivors on
+void sas_launch_density_state(hipStream_t st, const SasDensityState &q, const uint8_t *fresh = nullptr);
+// inv[perm[slot]] = slot
+void sas_launch_density_inverse(hipStream_t st, int64_t n, const int *perm, int *inv);
 // opacity <- min(opacity, cap) in g0; opac (nullptr: no state) <- (0, 0, logit(cap), -) where it changed
 void sas_launch_opacity_reset(hipStream_t st, int64_t n, float cap, float4 *g0, float4 *opac);
+
+// MCMC density control (sas_scene_mcmc_noise, sas_scene_mcmc_refine; DESIGN.md 3, "MCMC density control").  Every kernel takes its call
+// by value.
+struct SasMcmcNoise {
+    float4 *g0;                 // the means are written in place
+    const float4 *g1, *g2;
+    const int *perm;            // [n] slot -> caller's index
+    long long n;
+    int cov_mode;
+    float scale;
+    unsigned seed, step;
+};
+void sas_launch_mcmc_noise(hipStream_t st, const SasMcmcNoise &q);
+
+#define SAS_MCMC_MAX_N 51   /* gsplat's binomial table: a source is relocated as min(copies + 1, 51) Gaussians */
+// What a refine call makes of the alive count (the product in binary64, as gsplat's int(grow_factor * N)).
+struct SasMcmcPlan {
+    long long n_dead, n_grow, draws, n_new;
+};
+static inline SasMcmcPlan sas_mcmc_plan(long long n, long long n_alive, long long cap_max, double grow_factor)
+{
+    SasMcmcPlan p;
+    const double want = floor(grow_factor * (double)n);
+    const long long target = want < (double)cap_max ? (long long)want : cap_max;
+    p.n_dead = n - n_alive;
+    p.n_grow = target > n ? target - n : 0;
+    p.draws = p.n_dead + p.n_grow;
+    p.n_new = n_alive + p.draws;
+    return p;
+}
+struct SasMcmc {
+    const float4 *g0, *g1, *g2, *col;   // the old scene's planes (quaternions and scales)
+    const uint8_t *gid8;
+    const int *inv;             // [n] caller's index -> old slot (sas_launch_density_inverse)
+    long long n, n_pad;
+    int coeff_floats, planes;
+    float min_opacity;
+    unsigned seed;
+    // scratch, in the caller's order
+    unsigned *weight;           // [n] alive ? (uint32)(o 2^24) : 0
+    unsigned long long *prefix; // [n] inclusive sums of weight
+    unsigned *copies;           // [n] draws that selected i (zeroed by the caller)
+    float4 *reloc;              // [n] (o', scale'), written for the sources
+    unsigned *blk_alive, *blk_alive_off;          // [nb] alive per workgroup, and the exclusive offsets
+    unsigned long long *blk_weight, *blk_weight_off;   // [nb] weight per workgroup, and the exclusive offsets
+    unsigned long long *totals; // [2] (alive, weight)
+    long long nb;               // ceil(n / 256)
+    // once the host has sized the new scene from the totals: the draws and the new rows in the caller's order
+    long long n_alive, draws, n_new;
+    unsigned long long total_weight;
+    int *source;                // [draws] the old index draw d selected
+    float *means, *quats, *scales, *opac, *colors;
+    uint8_t *gid;               // or nullptr: no groups
+    int *parents;               // [n_new]
+    uint8_t *fresh;             // [n_new] 1: a source or a child (its optimiser state starts anew)
+};
+// weight, blk_*, totals <- the alive set and its weights
+void sas_launch_mcmc_weights(hipStream_t st, const SasMcmc &q);
+// ... and, once the host has read the totals: prefix, copies, source, reloc, and the rows of the new scene
+void sas_launch_mcmc_rows(hipStream_t st, const SasMcmc &q);
+// parents[i] = i (a call with nothing to do)
+void sas_launch_mcmc_identity(hipStream_t st, int64_t n, int *parents);

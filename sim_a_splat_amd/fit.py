@@ -4,7 +4,10 @@
 accumulate through ``out=``), ``adam_step`` the scene where it lives.  Nothing is uploaded between steps, so the storage order, the
 groups, the features and the meshes of the context stay as they are.  With ``densify=DensifyConfig(...)`` the loop also keeps the density
 statistics (``density_accumulate`` after every backward pass) and, on the config's schedule, calls ``densify`` and ``reset_opacity``: N changes
-where the scene lives, the optimiser state follows the survivors ("Density control").
+where the scene lives, the optimiser state follows the survivors ("Density control").  With ``densify=McmcConfig(cap_max, ...)``
+the number of Gaussians is a budget instead: opacity and scale regularisers let Gaussians die, ``mcmc_refine`` re-births the dead on live
+ones and grows the set by 5 % a time up to ``cap_max``, and ``mcmc_noise`` after every step does the exploring ("MCMC
+density control").  That path keeps no statistics; ``mcmc_refine`` pays the same host sort of the storage order ``densify`` pays.
 
 The loss: ``loss=None`` descends a mean absolute difference (or the caller's ``loss_and_grad``) with the chain to the raw accumulators in
 torch; ``loss="dssim"`` descends the 3DGS photometric loss ``(1 - lambda) L1 + lambda (1 - SSIM)`` through ``Rasterizer.photometric_loss``,
@@ -18,7 +21,7 @@ not variables of this loop: ``register.refine_group_poses`` fits them.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -40,6 +43,7 @@ class FitResult:
     history: List[float] = field(default_factory=list)
     steps: int = 0
     n_history: List[int] = field(default_factory=list)   # with ``densify``: the scene's N after step ``t + 1`` (empty without)
+    refines: List[Tuple[int, int, int, int]] = field(default_factory=list)   # with a ``McmcConfig``: (step, N, relocated, added) of every ``mcmc_refine``
 
     @property
     def loss(self) -> float:
@@ -80,6 +84,41 @@ class DensifyConfig:
         if not float(self.split_factor) > 1.0 or self.max_gaussians < 0 or not 0.0 < float(self.reset_opacity) < 1.0:
             raise ValueError(f"DensifyConfig: split_factor {self.split_factor} <= 1, max_gaussians {self.max_gaussians} < 0 or reset_opacity "
                              f"{self.reset_opacity} outside (0, 1)")
+
+
+@dataclass
+class McmcConfig:
+    """The budget and schedule of MCMC density control in ``fit_scene``, gsplat's ``MCMCStrategy``'s: after step ``t`` (1-based) with
+    ``start < t < stop`` and ``t % every == 0`` the dead Gaussians (opacity at most ``min_opacity``) are relocated onto alive ones and the
+    set grows by ``grow_factor`` up to ``cap_max`` (``Rasterizer.mcmc_refine``); after EVERY step the means get noise of scale
+    ``noise_lr`` times the means' current rate (``Rasterizer.mcmc_noise``).  ``opacity_reg`` and ``scale_reg`` weigh the regularisers
+    ``mean(opacity)`` and ``mean(scale)`` that let Gaussians die."""
+    cap_max: int
+    start: int = 500
+    stop: int = 25000
+    every: int = 100
+    min_opacity: float = 0.005
+    grow_factor: float = 1.05
+    noise_lr: float = 5e5
+    opacity_reg: float = 0.01
+    scale_reg: float = 0.01
+    seed: int = 0
+
+    def refine_at(self, t: int) -> bool:
+        return self.start < t < self.stop and self.every > 0 and t % self.every == 0
+
+    def check(self) -> None:
+        if int(self.cap_max) < 1 or self.every < 1 or self.start < 0:
+            raise ValueError(f"McmcConfig: cap_max {self.cap_max} < 1, every {self.every} < 1 or a negative start {self.start}")
+        if not 0.0 <= float(self.min_opacity) < 1.0 or not 1.0 <= float(self.grow_factor) < float("inf"):
+            raise ValueError(f"McmcConfig: min_opacity {self.min_opacity} outside [0, 1) or grow_factor {self.grow_factor} < 1 or not finite")
+        for k in ("noise_lr", "opacity_reg", "scale_reg"):
+            if not (0.0 <= float(getattr(self, k)) < float("inf")):
+                raise ValueError(f"McmcConfig: {k} {getattr(self, k)} is negative or not finite")
+
+
+def _scene_count(R) -> int:
+    return int(R.n) if hasattr(R, "n") else int(R.read_scene()["means"].shape[0])
 
 
 def _new_density_stats(R) -> Dict[str, torch.Tensor]:
@@ -156,7 +195,7 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
               lrs: Optional[Dict[str, float]] = None, masks=None, views_per_step: int = 1,
               background: Sequence[float] = (0.0, 0.0, 0.0), loss_and_grad: Optional[Callable] = None, renderer=None, seed: int = 0,
               extent: Optional[float] = None, visible_only: bool = True, loss: Optional[str] = None, lambda_dssim: float = 0.2,
-              densify: Optional[DensifyConfig] = None) -> FitResult:
+              densify: Union[DensifyConfig, McmcConfig, None] = None) -> FitResult:
     """``iters`` Adam steps of the scene resident in ``r`` towards ``images [C,H,W,3]`` (float, 0..1) seen from ``viewmats [C,4,4]``,
     ``Ks [C,3,3]``.  Each step draws ``views_per_step`` views (without replacement, ``seed``), renders each, takes the loss gradient
     with respect to the delivered frame in torch on the frame's device, runs it through ``autograd.prechain``, accumulates
@@ -178,7 +217,16 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
     ``densify``: a ``DensifyConfig`` turns adaptive density control on: ``density_accumulate`` follows every ``render_backward``, and after
     the steps of the config's schedule ``densify`` (then new statistics; the gradient buffers are made anew every step anyway) and
     ``reset_opacity`` are called, with the scene extent the means' rate uses.  ``n_history`` then holds N after every step.  A stand-in
-    ``renderer`` needs those three methods too.  ``None``: the loop above, unchanged."""
+    ``renderer`` needs those three methods too.  ``None``: the loop above, unchanged.
+
+    ``densify=McmcConfig(cap_max, ...)``: MCMC density control instead ("MCMC density control"); no statistics are kept.
+    Before ``adam_step``, ``opacity_reg / N`` is added to the accumulated ``opacities`` gradient and ``scale_reg / (3 N)`` to the ``scales``
+    gradient, where those groups are in ``what``: the derivatives of ``opacity_reg mean(o)`` and ``scale_reg mean(s)`` with respect to the
+    activated arrays, at the current N.  After ``adam_step``, on the config's schedule, ``mcmc_refine(seed=cfg.seed + t)``; then, every
+    step, ``mcmc_noise(noise_lr * the means' rate of step t, t, cfg.seed)``.  ``n_history`` holds N after every step; it never exceeds
+    ``max(cap_max, the initial N)``; ``refines`` holds ``(step, N, relocated, added)`` of every ``mcmc_refine``.  The regularisers make every gradient non-zero, so ``visible_only`` then skips nothing.
+    ``noise_lr > 0`` without ``"means"`` in ``what`` is refused.  The regularisers are not part of ``history``, which stays the image
+    loss.  Not provided: gsplat's two-pass order (relocate, then sample again for the growth) and its screen-size rules."""
     R = r if renderer is None else renderer
     _check_loss("fit_scene", loss, loss_and_grad, lambda_dssim)
     what = tuple(what)
@@ -203,7 +251,17 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
     rng = np.random.default_rng(seed)
     targets: Dict[int, Tuple[torch.Tensor, Optional[torch.Tensor]]] = {}
     losses = []
-    stats, n_history, was_reset = None, [], False
+    stats, n_history, refines, was_reset = None, [], [], False
+    mcmc, densify = (densify, None) if isinstance(densify, McmcConfig) else (None, densify)
+    n_now = 0
+    if mcmc is not None:
+        mcmc.check()
+        missing = [k for k in ("mcmc_refine", "mcmc_noise") if not hasattr(R, k)]
+        if missing:
+            raise ValueError(f"fit_scene: densify=McmcConfig needs a renderer with {missing}")
+        if mcmc.noise_lr > 0 and "means" not in what:
+            raise ValueError("fit_scene: McmcConfig.noise_lr > 0 scales the means' learning rate: put 'means' into what, or set noise_lr=0")
+        n_now = _scene_count(R)
     if densify is not None:
         densify.check()
         missing = [k for k in ("density_accumulate", "densify", "reset_opacity") if not hasattr(R, k)]
@@ -231,8 +289,21 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
                 R.density_accumulate(W, H, stats)
             value = torch.as_tensor(value).detach().reshape(())
             total = value if total is None else total + value
+        if mcmc is not None:   # d/do of opacity_reg mean(o), d/ds of scale_reg mean(s): constants, at the current N
+            if "opacities" in what and mcmc.opacity_reg:
+                acc["opacities"].add_(float(mcmc.opacity_reg) / n_now)
+            if "scales" in what and mcmc.scale_reg:
+                acc["scales"].add_(float(mcmc.scale_reg) / (3 * n_now))
         R.adam_step(acc, step_rates(rates, what, extent, t, int(iters)), t, visible_only=visible_only)
         losses.append(total / per)
+        if mcmc is not None:
+            if mcmc.refine_at(t):
+                done = R.mcmc_refine(min_opacity=mcmc.min_opacity, cap_max=int(mcmc.cap_max), grow_factor=mcmc.grow_factor, seed=mcmc.seed + t)
+                n_now = int(done["n"])
+                refines.append((t, n_now, int(done["relocated"]), int(done["added"])))
+            if mcmc.noise_lr > 0:
+                R.mcmc_noise(float(mcmc.noise_lr) * step_rates(rates, what, extent, t, int(iters))["means"], t, mcmc.seed)
+            n_history.append(n_now)
         if stats is not None:
             if densify.densify_at(t):
                 R.densify(stats, grow_grad2d=densify.grow_grad2d, grow_scale3d=densify.grow_scale3d, prune_opacity=densify.prune_opacity,
@@ -244,7 +315,7 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
                 was_reset = True
             n_history.append(int(stats["count"].shape[0]))
     history = [float(x) for x in torch.stack(losses).cpu()] if losses else []   # (one read-back for the run: no step waits for its loss)
-    return FitResult(history=history, steps=len(history), n_history=n_history)
+    return FitResult(history=history, steps=len(history), n_history=n_history, refines=refines)
 
 
 def image_metrics(r, viewmats, Ks, W: int, H: int, images, masks=None, background: Sequence[float] = (0.0, 0.0, 0.0)) -> Dict[str, torch.Tensor]:

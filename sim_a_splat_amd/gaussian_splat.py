@@ -378,7 +378,7 @@ class GaussianSplat:
         """Fit the model's Gaussians to ``images [C,H,W,3]`` (float, 0..1, camera 0's size) taken from ``poses [C,>=3,4]`` (camera-to-world,
         OpenGL axes, as ``render(pose)`` takes one): ``fit.fit_scene`` on the model's rasterizer, over the model's background colour, with
         camera 0's intrinsics.  ``what``: the variable groups (``means``, ``opacities``, ``colors``, ``quats``, ``scales``); N stays fixed unless
-        ``densify`` (a ``fit.DensifyConfig``) turns density control on -- every per-Gaussian parameter of the model is then replaced at the
+        ``densify`` (a ``fit.DensifyConfig``, or a ``fit.McmcConfig`` for a fixed budget of Gaussians) turns density control on -- every per-Gaussian parameter of the model is then replaced at the
         new N (SH bands beyond the uploaded degree start at zero).
         ``loss="dssim"`` descends the 3DGS photometric loss with weight ``lambda_dssim`` on its SSIM term (``fit.fit_scene``).
         The fitted arrays are written back into the model's raw parameters, so a later save holds them.  Returns the ``FitResult``."""

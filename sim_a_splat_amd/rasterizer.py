@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import math
 import threading
 from typing import Dict, Iterable, Optional, Sequence, Tuple, Union
 
@@ -1204,6 +1205,50 @@ class Rasterizer:
         if rc != 0:
             self._check(rc, "sas_scene_reset_opacity")
         self._in_flight(True)
+
+    # -- MCMC density control -------------------------------------------------------------------
+    _MCMC_CONFIG = dict(min_opacity=0.005, cap_max=1_000_000, grow_factor=1.05, seed=0)
+
+    @_locked
+    def mcmc_noise(self, scale: float, step: int, seed: int = 0) -> None:
+        """Noise on the RESIDENT means (sas_scene_mcmc_noise; DESIGN.md 3, "MCMC density control"): every mean moves by
+        ``C (xi g scale)`` -- ``C`` the Gaussian's own covariance, ``g = sigmoid(-100 (o - 0.005))`` the gate that leaves opaque
+        Gaussians where they are, ``xi`` three standard normals keyed by ``(seed, step, the Gaussian's index in the caller's order,
+        axis)``: the same key gives the same bits whatever the storage order.  ``scale``: gsplat's ``noise_lr`` times the means' current
+        learning rate; 0 changes nothing.  ``step``: 1-based.  The optimiser state is not touched; the last frame's ``read_projection`` /
+        ``read_tile_lists`` are gone.  Works on scenes uploaded as covariances too.  Only enqueues, on the current stream."""
+        rc = self._L.sas_scene_mcmc_noise(self._ctx, float(scale), int(step), int(seed) & 0xffffffff, self._stream())
+        if rc != 0:
+            self._check(rc, "sas_scene_mcmc_noise")
+        self._in_flight(True)
+
+    @_locked
+    def mcmc_refine(self, **config) -> Dict[str, object]:
+        """Relocate the dead Gaussians of the RESIDENT scene onto alive ones and grow the set towards a cap (sas_scene_mcmc_refine;
+        DESIGN.md 3, "MCMC density control").  ``config``: ``min_opacity`` (0.005: at or below it a Gaussian is dead), ``cap_max``
+        (1 000 000), ``grow_factor`` (1.05) and ``seed`` (0).  ``n_dead + n_grow`` alive Gaussians are drawn in proportion to their
+        opacity; a drawn one and its children share its opacity and shrink (gsplat's ``compute_relocation``).  Returns ``n`` (the new
+        count, also ``self.n``; never above ``max(cap_max, the old n)``), ``relocated``, ``added`` and ``parents`` (int32 ``[n]`` device:
+        each new Gaussian's old index).  Gaussians that were neither drawn nor born keep their optimiser state, the others start anew;
+        features are dropped (``upload_features(f[parents])``).  Refused for a scene uploaded as covariances.  Blocking."""
+        unknown = [k for k in config if k not in self._MCMC_CONFIG]
+        if unknown:
+            raise ValueError(f"mcmc_refine: unknown settings {unknown}; expected some of {tuple(self._MCMC_CONFIG)}")
+        cf = dict(self._MCMC_CONFIG, **config)
+        cfg = _capi.McmcConfig(int(cf["cap_max"]), float(cf["grow_factor"]), float(cf["min_opacity"]), int(cf["seed"]) & 0xffffffff)
+        room = self.n
+        if math.isfinite(cfg.grow_factor) and cfg.grow_factor >= 1.0:   # (anything else is refused below)
+            room = max(room, int(min(float(cfg.cap_max), cfg.grow_factor * self.n)))   # (clamped as a float, then floored: the product may be inf)
+        parents = torch.empty(max(room, 1), dtype=torch.int32, device=self.device)
+        counts = (ctypes.c_int64 * 3)()
+        rc = self._L.sas_scene_mcmc_refine(self._ctx, ctypes.byref(cfg), parents.data_ptr(), counts, self._stream())
+        if rc != 0:
+            self._check(rc, "sas_scene_mcmc_refine")
+        self._in_flight(True)
+        if int(counts[1]) or int(counts[2]):
+            self._forget("features")
+        self.n = int(counts[0])
+        return dict(n=self.n, relocated=int(counts[1]), added=int(counts[2]), parents=parents[:self.n])
 
     @_locked
     def photometric_loss(self, rgb, target, *, mask=None, alpha=None, background: Sequence[float] = (0.0, 0.0, 0.0),
