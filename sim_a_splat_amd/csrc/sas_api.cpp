@@ -58,26 +58,20 @@ struct ViewOut {
     uint8_t *rgb8_host = nullptr;   // sas_render_batch_host: host copy of rgb8, made on the frame's stream
     float *features = nullptr;      // sas_render_features: [H,W,feat_c] (device), composited behind the frame's k_blend
     uint8_t *labels = nullptr;      // sas_render_batch_labels: [H,W] (device), the argmax of the one-hot stores' channels
-    // sas_lift_labels: the view's label image [H,W] (device) and the per-Gaussian sums the frame ADDS to (either may be nullptr)
-    const uint8_t *lift_labels = nullptr;
-    int64_t *lift_votes = nullptr, *lift_seen = nullptr;
-    int lift_n = 0;                 // n_labels
-    // sas_lift_features: the view's feature image [H,W,lift_c] and mask [H,W] (device; the mask may be nullptr) and the sums likewise
-    const float *lift_images = nullptr;
-    const uint8_t *lift_mask = nullptr;
-    int64_t *lift_sums = nullptr, *lift_weight = nullptr;
-    int lift_c = 0;
-    float lift_scale = 0.0f;
-    // sas_render_backward_screen: the view's pixel gradients (device, each may be nullptr) and the per-Gaussian gradients the frame ADDS to
-    bool grad = false;
-    const float *grad_rgb = nullptr, *grad_alpha = nullptr, *grad_depth = nullptr;
-    float *grad_means2d = nullptr, *grad_conics = nullptr, *grad_opacities = nullptr, *grad_colors = nullptr, *grad_depths = nullptr;
-    // sas_render_backward: the chain through the projection behind it (the five sums above are then all set), what it ADDS to
-    bool grad_chain = false;
-    float *chain_means = nullptr, *chain_opacities = nullptr, *chain_sh = nullptr, *chain_quats = nullptr, *chain_scales = nullptr,
-          *chain_cov6 = nullptr, *chain_viewmat = nullptr, *chain_partial = nullptr;
-    SasPoseSel chain_poses{};       // sas_render_backward_poses: the selected groups, their scratch rows and what they ADD to (n_sel 0: none)
+    // The frame's list reader: what walks its complete lists once more behind k_blend and ADDS to buffers of the caller's, with its
+    // arguments as the record its kernel takes.  At most one per frame, so the records share their bytes.
+    enum Reader : uint8_t { NO_READER, LIFT_LABELS, LIFT_FEATURES, BACKWARD } reader = NO_READER;
+    // sas_render_backward_screen: k_grad_tiles' record; sas_render_backward: k_grad_project's behind it (proj.s_means2d nullptr: no
+    // chain), whose s_* are tiles' d_*; sas_render_backward_poses: the selected groups as well (poses.n_sel 0: none)
+    struct Backward { SasGrad tiles; SasGradProj proj; SasPoseSel poses; };
+    union {
+        SasLift lift;                    // sas_lift_labels
+        SasLiftFeatures lift_features;   // sas_lift_features
+        Backward back{};
+    };
+    bool chained() const { return reader == BACKWARD && back.proj.s_means2d; }   // (k_grad_project reads the group poses on the device)
 };
+static_assert(sizeof(ViewOut) <= 344, "ViewOut is copied per view into RenderArgs on the render path: it was 344 bytes with the readers' arguments field by field");
 
 struct RenderArgs {
     float viewmat[16], K[9], bg[3];
@@ -944,7 +938,7 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
     } else {
         // (a pair shares its poses: the leader's block serves both views; the triangle setup of a mesh frame reads the
         // slot's poses on the device)
-        enqueue_poses(c, sl, nv, st, ld.mesh || a.out.grad_chain);   // (k_grad_project reads the poses on the device)
+        enqueue_poses(c, sl, nv, st, ld.mesh || a.out.chained());   // (k_grad_project reads the poses on the device)
         if (timing) HIP_TRY(c, hipEventRecord(ld.ev[0], st));
         if (follower) {
             sas_launch_project2(st, c->scene, P, f, follower->params, frame_of(c, *follower));
@@ -987,25 +981,18 @@ int enqueue_chain(sas_ctx *c, Slot *const *sl, int nv, Slot *follower = nullptr,
         // a feature frame (sas_render_features): the same lists and records once more, per chunk of channels
         if (a.out.features) sas_launch_blend_features(st, c->scene, tiles, P, f, features_of(c, a), fast_exp, nullptr);
         if (a.out.labels) sas_launch_blend_labels(st, c->scene, tiles, P, f, labels_of(c, a), fast_exp, nullptr);   // a label frame: likewise
-        if (a.out.lift_labels) {   // a lift frame: the same lists, the weights handed back to their Gaussians
-            const SasLift B{a.out.lift_labels, (unsigned long long *)a.out.lift_votes, (unsigned long long *)a.out.lift_seen, c->scene.n, a.out.lift_n};
-            sas_launch_lift_labels(st, c->scene, tiles, P, f, B, fast_exp);
-        }
-        if (a.out.lift_images) {   // ... or, channel by channel, the pixels' features weighted by them
-            const SasLiftFeatures B{a.out.lift_images, a.out.lift_mask, (unsigned long long *)a.out.lift_sums,
-                                    (unsigned long long *)a.out.lift_weight, c->scene.n, a.out.lift_c, a.out.lift_scale};
-            sas_launch_lift_features(st, c->scene, tiles, P, f, B, fast_exp);
-        }
-        if (a.out.grad) {   // a backward frame: the same lists walked there and back (sas_grad.hip)
-            const SasGrad B{a.out.grad_rgb, a.out.grad_alpha, a.out.grad_depth, a.out.grad_means2d, a.out.grad_conics,
-                            a.out.grad_opacities, a.out.grad_colors, a.out.grad_depths, c->scene.n};
-            sas_launch_grad_tiles(st, c->scene, tiles, P, f, B, fast_exp);
-            if (a.out.grad_chain) {
-                const SasGradProj Q{a.out.grad_means2d, a.out.grad_conics, a.out.grad_opacities, a.out.grad_colors, a.out.grad_depths,
-                                    a.out.chain_means, a.out.chain_opacities, a.out.chain_sh, a.out.chain_quats, a.out.chain_scales,
-                                    a.out.chain_cov6, a.out.chain_viewmat ? a.out.chain_partial : nullptr, a.out.chain_viewmat, c->scene.n};
-                sas_launch_grad_project(st, c->scene, P, f, Q, a.out.chain_poses);
-            }
+        switch (a.out.reader) {
+        case ViewOut::NO_READER: break;
+        case ViewOut::LIFT_LABELS:   // a lift frame: the same lists, the weights handed back to their Gaussians
+            sas_launch_lift_labels(st, c->scene, tiles, P, f, a.out.lift, fast_exp);
+            break;
+        case ViewOut::LIFT_FEATURES:   // ... or, channel by channel, the pixels' features weighted by them
+            sas_launch_lift_features(st, c->scene, tiles, P, f, a.out.lift_features, fast_exp);
+            break;
+        case ViewOut::BACKWARD:   // a backward frame: the same lists walked there and back (sas_grad.hip)
+            sas_launch_grad_tiles(st, c->scene, tiles, P, f, a.out.back.tiles, fast_exp);
+            if (a.out.chained()) sas_launch_grad_project(st, c->scene, P, f, a.out.back.proj, a.out.back.poses);
+            break;
         }
     } else if (nv > 1) {
         // (quad: by the size of one view (prepare_frame): groups of four 300-tile views still gain (vec_env_probe))
@@ -1543,7 +1530,7 @@ static void fill_args(RenderArgs &a, const ViewCall &v, int width, int height, c
     const ViewOut &o = v.out;
     a.solo = solo;
     // rgb8 beside rgb8_host is the context's own staging frame (sas_render_batch_host): nothing of the caller's on the device
-    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || o.labels || o.lift_labels || o.lift_images || o.grad || (o.rgb8 && !o.rgb8_host);
+    a.order_caller = o.rgb || o.alpha || o.depth || o.points || o.mask || o.features || o.labels || o.reader != ViewOut::NO_READER || (o.rgb8 && !o.rgb8_host);
     memcpy(a.viewmat, v.viewmat, sizeof(a.viewmat));
     memcpy(a.K, v.K, sizeof(a.K));
     for (int k = 0; k < 3; ++k) a.bg[k] = background ? background[k] : 0.0f;
@@ -2319,10 +2306,8 @@ int sas_lift_labels(sas_ctx *c, int n_views, const float *viewmats, const float 
     const size_t px = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
     return lift_views(c, "sas_lift_labels", n_views, viewmats, Ks, width, height, flags, stream, [&](int v) {
         ViewOut o;
-        o.lift_labels = labels + px * v;
-        o.lift_votes = votes;
-        o.lift_seen = seen;
-        o.lift_n = n_labels;
+        o.reader = ViewOut::LIFT_LABELS;
+        o.lift = SasLift{labels + px * v, (unsigned long long *)votes, (unsigned long long *)seen, c->scene.n, n_labels};
         return o;
     });
 }
@@ -2341,12 +2326,9 @@ int sas_lift_features(sas_ctx *c, int n_views, const float *viewmats, const floa
     const size_t px = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
     return lift_views(c, "sas_lift_features", n_views, viewmats, Ks, width, height, flags, stream, [&](int v) {
         ViewOut o;
-        o.lift_images = images + px * (size_t)channels * v;
-        o.lift_mask = mask ? mask + px * v : nullptr;
-        o.lift_sums = sums;
-        o.lift_weight = weight;
-        o.lift_c = channels;
-        o.lift_scale = feature_scale;
+        o.reader = ViewOut::LIFT_FEATURES;
+        o.lift_features = SasLiftFeatures{images + px * (size_t)channels * v, mask ? mask + px * v : nullptr, (unsigned long long *)sums,
+                                          (unsigned long long *)weight, c->scene.n, channels, feature_scale};
         return o;
     });
 }
@@ -2378,13 +2360,11 @@ static int slots_wait_for(sas_ctx *c, Event &ev, hipStream_t st)
 }
 
 // A backward frame's ViewOut: the view's pixel gradients and the five screen-space sums it adds to.
-static ViewOut grad_view(const float *g_rgb, const float *g_alpha, const float *g_depth, float *d_means2d, float *d_conics, float *d_opacities,
-                         float *d_colors, float *d_depths)
+static ViewOut grad_view(const SasGrad &tiles)
 {
     ViewOut o;
-    o.grad = true;
-    o.grad_rgb = g_rgb; o.grad_alpha = g_alpha; o.grad_depth = g_depth;
-    o.grad_means2d = d_means2d; o.grad_conics = d_conics; o.grad_opacities = d_opacities; o.grad_colors = d_colors; o.grad_depths = d_depths;
+    o.reader = ViewOut::BACKWARD;
+    o.back.tiles = tiles;
     return o;
 }
 
@@ -2398,7 +2378,7 @@ int sas_render_backward_screen(sas_ctx *c, const float *viewmat, const float *K,
     if (!d_means2d && !d_conics && !d_opacities && !d_colors && !d_depths)
         return fail(c, SAS_ERR_INVALID, "sas_render_backward_screen: every output is NULL");
     const int rc = lift_views(c, "sas_render_backward_screen", 1, viewmat, K, width, height, flags, stream,
-                              [&](int) { return grad_view(g_rgb, g_alpha, g_depth, d_means2d, d_conics, d_opacities, d_colors, d_depths); });
+                              [&](int) { return grad_view({g_rgb, g_alpha, g_depth, d_means2d, d_conics, d_opacities, d_colors, d_depths, c->scene.n}); });
     if (!rc) c->grad_frame = 1;
     return rc;
 }
@@ -2441,12 +2421,11 @@ static int render_backward(sas_ctx *c, const char *who, const float *viewmat, co
     HIP_TRY(c, hipMemsetAsync(s, 0, floats * sizeof(float), (hipStream_t)stream));
     S.partial = n_sel > 0 ? s + floats : nullptr;
     const int rc = lift_views(c, who, 1, viewmat, K, width, height, flags, stream, [&](int) {
-        ViewOut o = grad_view(g_rgb, g_alpha, g_depth, s, s + 2 * n, s + 5 * n, s + 6 * n, s + 9 * n);
-        o.grad_chain = true;
-        o.chain_partial = s + 10 * n;
-        o.chain_means = d_means; o.chain_opacities = d_opacities; o.chain_sh = d_sh; o.chain_quats = d_quats; o.chain_scales = d_scales;
-        o.chain_cov6 = d_cov6; o.chain_viewmat = d_viewmat;
-        o.chain_poses = S;
+        ViewOut o = grad_view({g_rgb, g_alpha, g_depth, s, s + 2 * n, s + 5 * n, s + 6 * n, s + 9 * n, c->scene.n});
+        const SasGrad &g = o.back.tiles;
+        o.back.proj = SasGradProj{g.d_means2d, g.d_conics, g.d_opacities, g.d_colors, g.d_depths, d_means, d_opacities, d_sh, d_quats, d_scales,
+                                  d_cov6, d_viewmat ? s + 10 * n : nullptr, d_viewmat, c->scene.n};
+        o.back.poses = S;
         return o;
     });
     if (!rc) c->grad_frame = 2;   // (sas_density_accumulate may read the sums in grad_screen)

@@ -1,4 +1,4 @@
-// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip and sas_mcmc.hip.
+// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip and sas_mcmc.hip: arithmetic, the bounds-checked build, DPP reductions and row sums, contract T6 per pair, and the start of a workgroup on one tile of a frame (pixel layout, pixel state, the tile's list, the truncated-list rule).
 // Everything here follows the arithmetic contract of DESIGN.md: IEEE binary32 operations, fused
 // only where fma_() is written (translation units are built with -ffp-contract=off).
 #pragma once
@@ -127,6 +127,22 @@ DEV unsigned wave_inclusive_sum_u32(unsigned x)
     return (unsigned)v;
 }
 
+// sum over the 16 lanes of this lane's DPP row: the first four butterflies of wave_reduce_i32 on v_mov_dpp, for a value of 32 bits.  A row
+// IS a 4x4 block of the tile's pixels (pixel_of): neighbours in a quad, the quad's other pair, then -- every lane of a quad holding the
+// quad's sum -- the row's half mirror swaps the quads of a half and the row mirror the halves.  Every lane of the row then holds the
+// sum; unsigned sums are modular (two's complement values add as well).  Every lane of the wave is active at the call sites.
+template <int CTRL, typename T>
+DEV T mov_dpp(T v) { return __builtin_bit_cast(T, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true)); }
+template <typename T>   // unsigned, float
+DEV T row_sum(T v)
+{
+    v += mov_dpp<0xB1>(v);    // quad_perm:[1,0,3,2]
+    v += mov_dpp<0x4E>(v);    // quad_perm:[2,3,0,1]
+    v += mov_dpp<0x141>(v);   // row_half_mirror
+    v += mov_dpp<0x140>(v);   // row_mirror
+    return v;
+}
+
 // lane `src` (uniform) of a register: v_readlane_b32 (hipcc's __shfl(v, src) is a ds_bpermute_b32 round trip even when src is uniform)
 DEV int lane_get(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 DEV unsigned lane_get(unsigned v, int src) { return (unsigned)__builtin_amdgcn_readlane((int)v, src); }
@@ -226,3 +242,80 @@ DEV float splat_sigma(const float4 K, const float2 H, float dx, float dy) { retu
 template <bool FAST_EXP>
 DEV float splat_exp(float sigma, float sE5) { return FAST_EXP ? __expf(fmaxf(-sigma, -86.0f)) : c_expf_neg(fmaxf(-sigma, -86.0f), sE5); }
 DEV float splat_alpha(const float2 H, float E) { return fminf(kMaxAlpha, H.y * E); }
+
+// ---- a workgroup on one tile of a frame: the pixel layout, the pixel's start, the tile's list (sas_tile.hip, sas_grad.hip) ---------------
+// Pixel of (wave, lane) inside the tile: wave w owns the 8x8 quadrant (w & 1, w >> 1); its four
+// 16-lane groups own the quadrant's 4x4 blocks, so that each group can walk its own splat queue.
+DEV void pixel_of(int wv, int lane, int &ox, int &oy)
+{
+    const int g = lane >> 4, q = lane & 15;
+    ox = (wv & 1) * 8 + (g & 1) * 4 + (q & 3);
+    oy = (wv >> 1) * 8 + (g >> 1) * 4 + (q >> 2);
+}
+
+// Per-pixel compositing state.  x is the pixel centre relative to the tile's centre.  A terminated
+// pixel (transmittance test fired, or outside the image) is parked at x = NaN: every later sigma is
+// then NaN and fails `sigma <= thr` by itself, so the inner loop carries no "done" flag.
+struct PixState {
+    float T, r, g, b, d;
+    float x;
+};
+// Contract T6: the tile-local frame (u, v, x, y) has its origin at the CENTRE of the 16-pixel tile (x, y in -7.5 .. 7.5)
+constexpr float kTileCentre = 8.0f;
+DEV PixState pix_init(bool inside, int ox) { return PixState{1.0f, 0.f, 0.f, 0.f, 0.f, inside ? ((float)ox + 0.5f) - kTileCentre : __builtin_nanf("")}; }
+// Pixel (ox, oy) of tile (tx, ty) starts: its image coordinates, whether it lies inside the image, its state; wdone: the wave has
+// no pixel inside.
+DEV PixState pixel_begin(const SasCam &c, int tx, int ty, int ox, int oy, int &ix, int &iy, bool &inside, bool &wdone)
+{
+    ix = tx * SAS_TILE + ox;
+    iy = ty * SAS_TILE + oy;
+    inside = ix < c.W && iy < c.H;
+    const PixState p = pix_init(inside, ox);
+    wdone = __all(!inside);
+    return p;
+}
+// A tile's segment [beg, end) of the frame's key / id arrays.  (The clamp to the arrays' capacity is a safety check: the
+// projection never hands out more.)
+DEV void tile_segment(const SasFrame &f, int tile, long long &beg, long long &end)
+{
+    beg = f.tile_offset[tile];
+    end = f.tile_offset[tile + 1];
+    if (end > f.cap) end = f.cap;
+}
+
+// One lane of a workgroup on tile `tile`: its pixel and the tile's depth-ordered list -- what a kernel that composites a tile's list
+// starts from, behind its own tile lookup and range checks (blend_tile inside its persistent loop; label_tile, k_lift_labels,
+// k_lift_features).  tile_lane fills in the pixel, tile_list the list: entries ids[0, count) of f.sorted_ids.  Two steps, because each
+// kernel reads what it needs at its pixel in between and hipcc schedules the loads in the order they are written; the range checks
+// stay in the kernels, because returns that come out of a shared function compile to other code (profiles/list_readers_ab.txt).
+// k_blend_features[_mesh] and k_grad_tiles keep their own text (see there).
+struct TileLane {
+    int tile, tx, ty, ox, oy, ix, iy;   // the tile; the pixel inside it (pixel_of) and in the image
+    bool inside, wdone;                 // the pixel lies inside the image; the wave has no pixel inside
+    PixState p;
+    const int *ids;                     // (blend_range's slot lambda goes over a local copy: capturing this record changes k_blend*'s code)
+    int count;
+};
+DEV TileLane tile_lane(const SasCam &c, int tile, int wv, int lane)
+{
+    TileLane w;
+    w.tile = tile;
+    w.tx = tile % c.tw;
+    w.ty = tile / c.tw;
+    pixel_of(wv, lane, w.ox, w.oy);
+    w.p = pixel_begin(c, w.tx, w.ty, w.ox, w.oy, w.ix, w.iy, w.inside, w.wdone);
+    return w;
+}
+template <bool CLAMP = true>   // (false: k_blend*'s text, which hands blend_range the difference as it is: a negative count is an empty list)
+DEV void tile_list(const SasFrame &f, TileLane &w)
+{
+    long long beg, end;
+    tile_segment(f, w.tile, beg, end);
+    w.ids = f.sorted_ids + beg;
+    w.count = (!CLAMP || end > beg) ? (int)(end - beg) : 0;
+}
+// The truncated-list rule of every kernel that walks a FINISHED frame's complete lists and ADDS into buffers of the caller's
+// (k_lift_labels, k_lift_features, k_grad_tiles): a frame whose lists outgrew the key buffer is rendered again (complete_oldest), so
+// its first rendering adds NOTHING -- the truncated lists would be counted on top of the second rendering's complete ones.  Uniform;
+// such a kernel returns on it before it reads a list.
+DEV bool lists_truncated(const SasFrame &f) { return (long long)f.tile_offset[f.n_tiles] > f.cap; }

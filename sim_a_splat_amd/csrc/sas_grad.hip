@@ -22,20 +22,7 @@
 namespace {
 
 constexpr int kGradVals = 10;   // mean2d (2), conic (3), opacity, colour (3), depth
-constexpr float kGradTileCentre = 8.0f;   // contract T6: the tile-local frame has its origin at the tile's centre
 constexpr int kGradAccStride = kGradVals;   // an entry's ten accumulators lie side by side: a row's ten adds fall in ten banks, the handover reads linearly
-
-// sum over the 16 lanes of this lane's DPP row (a 4x4 block of pixels); every lane of the wave is active at the call sites
-template <int CTRL>
-DEV float row_move_f(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true)); }
-DEV float row_sum_f(float v)
-{
-    v += row_move_f<0xB1>(v);    // quad_perm:[1,0,3,2]
-    v += row_move_f<0x4E>(v);    // quad_perm:[2,3,0,1]
-    v += row_move_f<0x141>(v);   // row_half_mirror
-    v += row_move_f<0x140>(v);   // row_mirror
-    return v;
-}
 
 struct GradLds {
     float4 k[256];    // (u, v, A/2, B): mean2d relative to the tile's centre, conic
@@ -68,26 +55,28 @@ __global__ __launch_bounds__(256) void k_grad_tiles(SasParams P, SasFrame f, lon
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int oi = (int)blockIdx.x;
     if (!SAS_IN(oi, f.n_tiles, 801) || oi >= f.n_tiles) return;
-    if ((long long)f.tile_offset[f.n_tiles] > f.cap) return;   // (uniform) truncated lists: the frame's second rendering adds
+    if (lists_truncated(f)) return;   // (uniform) the frame's second rendering adds
     const int tile = f.tile_order[oi];
     if (!SAS_IN(tile, f.n_tiles, 802) || tile < 0 || tile >= f.n_tiles) return;   // (uniform)
     const int tx = tile % c.tw, ty = tile / c.tw;
-    // the tile kernel's pixel layout: wave w owns the 8x8 quadrant w, its 16-lane rows the quadrant's 4x4 blocks
+    // the tile kernel's pixel layout (pixel_of: wave w owns the 8x8 quadrant w, its 16-lane rows the quadrant's 4x4 blocks), written out:
+    // through pixel_of / tile_lane hipcc forms the coordinates with other bit operations, and the config-3 backward frame measured
+    // 0.5 .. 1.6 % over the parent's range (profiles/list_readers_ab.txt)
     const int g4 = lane >> 4, q4 = lane & 15;
     const int ox = (wv & 1) * 8 + (g4 & 1) * 4 + (q4 & 3), oy = (wv >> 1) * 8 + (g4 >> 1) * 4 + (q4 >> 2);
     const int ix = tx * SAS_TILE + ox, iy = ty * SAS_TILE + oy;
     const bool inside = ix < c.W && iy < c.H;
     const long long pix = (long long)iy * c.W + ix;
-    const float x = ((float)ox + 0.5f) - kGradTileCentre, y = ((float)oy + 0.5f) - kGradTileCentre;
-    const float X0 = (float)(tx * SAS_TILE) + kGradTileCentre, Y0 = (float)(ty * SAS_TILE) + kGradTileCentre;
+    const float x = ((float)ox + 0.5f) - kTileCentre, y = ((float)oy + 0.5f) - kTileCentre;
+    const float X0 = (float)(tx * SAS_TILE) + kTileCentre, Y0 = (float)(ty * SAS_TILE) + kTileCentre;
     float gr = 0.0f, gg = 0.0f, gb = 0.0f, ga = 0.0f, gd = 0.0f;
     if (inside && SAS_IN(pix, P.out.n_pixels, 803)) {
         if (B.g_rgb) { gr = B.g_rgb[3 * pix + 0]; gg = B.g_rgb[3 * pix + 1]; gb = B.g_rgb[3 * pix + 2]; }
         if (B.g_alpha) ga = B.g_alpha[pix];
         if (B.g_depth) gd = B.g_depth[pix];
     }
-    long long beg = f.tile_offset[tile], end = f.tile_offset[tile + 1];
-    if (end > f.cap) end = f.cap;
+    long long beg, end;
+    tile_segment(f, tile, beg, end);
     const int count = end > beg ? (int)(end - beg) : 0;
     const int *ids = f.sorted_ids + beg;
 
@@ -182,7 +171,7 @@ __global__ __launch_bounds__(256) void k_grad_tiles(SasParams P, SasFrame f, lon
                 float mine = 0.0f;
 #pragma unroll
                 for (int k = 0; k < kGradVals; ++k) {
-                    const float s = row_sum_f(d[k]);
+                    const float s = row_sum(d[k]);
                     if (q4 == k) mine = s;
                 }
                 if (q4 < kGradVals && mine != 0.0f && SAS_IN(e * kGradAccStride + q4, 256 * kGradAccStride, 805)) atomicAdd(&L.acc[e * kGradAccStride + q4], mine);

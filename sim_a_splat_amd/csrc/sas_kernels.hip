@@ -590,7 +590,7 @@ DEV void bin_outside_window(const SasFrame &f, int seg, bool outside, int tw, co
         });
     } else {
         for_each_tile(outside, l.x0, l.x1, l.y0, l.y1, tw, 0u, 0u,
-                      [&](int tile, unsigned, unsigned) { if (SAS_IN(tile, f.n_tiles, 103)) atomicAdd(&f.tile_big[tile], 1); });
+                      [&](int tile, unsigned, unsigned) { if (SAS_IN(tile, f.n_tiles, 106)) atomicAdd(&f.tile_big[tile], 1); });
     }
 }
 

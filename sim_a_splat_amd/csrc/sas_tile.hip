@@ -37,15 +37,6 @@ DEV bool key_greater(unsigned long long a, unsigned long long b, const int *perm
     return perm[lo32(a)] > perm[lo32(b)];
 }
 
-// A tile's segment [beg, end) of the frame's key / id arrays.  (The clamp to the arrays' capacity is a safety check: the
-// projection never hands out more.)
-DEV void tile_segment(const SasFrame &f, int tile, long long &beg, long long &end)
-{
-    beg = f.tile_offset[tile];
-    end = f.tile_offset[tile + 1];
-    if (end > f.cap) end = f.cap;
-}
-
 // ================================================================================================
 // LDS radix sort building blocks
 // ================================================================================================
@@ -457,15 +448,6 @@ DEV unsigned block_mask16(int tx, int ty, float mx, float my, float A, float B, 
     return m;
 }
 
-// Pixel of (wave, lane) inside the tile: wave w owns the 8x8 quadrant (w & 1, w >> 1); its four
-// 16-lane groups own the quadrant's 4x4 blocks, so that each group can walk its own splat queue.
-DEV void pixel_of(int wv, int lane, int &ox, int &oy)
-{
-    const int g = lane >> 4, q = lane & 15;
-    ox = (wv & 1) * 8 + (g & 1) * 4 + (q & 3);
-    oy = (wv >> 1) * 8 + (g >> 1) * 4 + (q >> 2);
-}
-
 // ---- quad layout (k_tile_lazy<..., QUAD>: frames of a few hundred tiles, binned in 8-pixel tiles) ----
 // One workgroup per 8x8 quadrant qd = (qx, qy) of a 16-pixel tile, with the quadrant's own list; wave w of a workgroup owns the quadrant's
 // 4x4 block w; a lane is (pixel q = lane >> 2 of the block, entry slot e = lane & 3): the four lanes of a
@@ -498,36 +480,15 @@ DEV unsigned block_mask4(int tx, int ty, int qd, float mx, float my, float A, fl
     return m;
 }
 
-// Per-pixel compositing state.  x is the pixel centre relative to the tile's centre.  A terminated
-// pixel (transmittance test fired, or outside the image) is parked at x = NaN: every later sigma is
-// then NaN and fails `sigma <= thr` by itself, so the inner loop carries no "done" flag.
-struct PixState {
-    float T, r, g, b, d;
-    float x;
-};
 // the pixel's tile-local row (its column is PixState::x, which doubles as the parking flag)
 struct PixConst {
     float y;
 };
 DEV bool pix_dead(const PixState &p) { return p.x != p.x; }
-// Contract T6: the tile-local frame (u, v, x, y) has its origin at the CENTRE of the 16-pixel tile (x, y in -7.5 .. 7.5)
-constexpr float kTileCentre = 8.0f;
-DEV PixState pix_init(bool inside, int ox) { return PixState{1.0f, 0.f, 0.f, 0.f, 0.f, inside ? ((float)ox + 0.5f) - kTileCentre : __builtin_nanf("")}; }
 DEV PixConst pix_const(int ox, int oy)
 {
     (void)ox;
     return PixConst{((float)oy + 0.5f) - kTileCentre};
-}
-// Pixel (ox, oy) of tile (tx, ty) starts: its image coordinates, whether it lies inside the image, its state; wdone: the wave has
-// no pixel inside.
-DEV PixState pixel_begin(const SasCam &c, int tx, int ty, int ox, int oy, int &ix, int &iy, bool &inside, bool &wdone)
-{
-    ix = tx * SAS_TILE + ox;
-    iy = ty * SAS_TILE + oy;
-    inside = ix < c.W && iy < c.H;
-    const PixState p = pix_init(inside, ox);
-    wdone = __all(!inside);
-    return p;
 }
 typedef float f32x3 __attribute__((ext_vector_type(3)));
 
@@ -1307,11 +1268,10 @@ DEV void blend_tile(const SasParams &P, const SasFrame &f, long long n_gauss, in
     const SasCam &c = P.cam;
     const BlendLds L = blend_lds(s_raw);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int tx = tile % c.tw, ty = tile / c.tw;
-    int ox, oy, ix, iy;
-    bool inside, wdone;
-    pixel_of(wv, lane, ox, oy);
-    PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
+    TileLane w = tile_lane(c, tile, wv, lane);
+    const int tx = w.tx, ty = w.ty, ox = w.ox, oy = w.oy, ix = w.ix, iy = w.iy;
+    const bool inside = w.inside;
+    PixState p = w.p;
     SasOutputs o = P.out;
     float zlim = 0.0f;
     if constexpr (MESH) {
@@ -1323,13 +1283,12 @@ DEV void blend_tile(const SasParams &P, const SasFrame &f, long long n_gauss, in
         if constexpr (SCENE)
             if (X->win && inside && SAS_IN((long long)iy * c.W + ix, o.n_pixels, 322)) X->win[(long long)iy * c.W + ix] = win;
     }
-    long long beg, end;
-    tile_segment(f, tile, beg, end);
-    const int *ids = f.sorted_ids + beg;
+    tile_list<false>(f, w);
+    const int *ids = w.ids;
     unsigned long long ph_lap_ = 0ull;
     RgbdPayload pay;
-    blend_range<FAST_EXP, MESH>(f, n_gauss, tx, ty, pix_const(ox, oy), (int)(end - beg),
-                                [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay, zlim);
+    blend_range<FAST_EXP, MESH>(f, n_gauss, tx, ty, pix_const(ox, oy), w.count,
+                                [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, w.wdone, ph_lap_, sync_phase, pay, zlim);
     unsigned packed;
     float ED = write_pixel(o, p, inside, ix, iy, c.W, packed);
     if constexpr (SCENE) {
@@ -1609,7 +1568,7 @@ DEV DepthBuckets bucket_long_list(const unsigned long long *g, int n, const Lazy
             if (SAS_IN(B.bucket_of_depth(dd), 256, 208)) atomicAdd(&S.hist[B.bucket_of_depth(dd)], 1u);
         }
     } else {
-        for_each_key<U>(n, 0u, [&](int i) { return hi32(g[i]); }, [&](int, unsigned d) { if (SAS_IN(B.bucket_of_depth(d), 256, 208)) atomicAdd(&S.hist[B.bucket_of_depth(d)], 1u); });
+        for_each_key<U>(n, 0u, [&](int i) { return hi32(g[i]); }, [&](int, unsigned d) { if (SAS_IN(B.bucket_of_depth(d), 256, 207)) atomicAdd(&S.hist[B.bucket_of_depth(d)], 1u); });
     }
     __syncthreads();
     PH_LAP(2);
@@ -2135,8 +2094,8 @@ __global__ __launch_bounds__(256) void k_feature_store(long long n, long long n_
     const int q = (int)(t / n_pad);
     const long long j = t - (long long)q * n_pad;
     long long i = -1;
-    if (j < n && SAS_IN(j, n, 301)) i = perm[j];
-    if (j < n && !(SAS_IN(i, n, 302) && i < n)) i = -1;
+    if (j < n && SAS_IN(j, n, 306)) i = perm[j];
+    if (j < n && !(SAS_IN(i, n, 307) && i < n)) i = -1;
     const int id = (!src && i >= 0 && SAS_IN(j, n_pad, 304)) ? (int)gid8[j] : -1;
     feature_store_row<303, 305>(t, total, q, i, n, id, src, C, store);
 }
@@ -2153,9 +2112,34 @@ __global__ __launch_bounds__(256) void k_mesh_feature_store(long long nt, const 
     feature_store_row<325, 326>(i, total, q, t, nt, grp, src, C, store);
 }
 
+// m = triangle t's row of chunk q in the triangles' feature store (k_mesh_feature_store): what a covered pixel shows behind its splats
+DEV void mesh_feature_row(const SasMeshFeatures &MF, int q, long long t, float *m)
+{
+    const float4 *row = reinterpret_cast<const float4 *>(MF.store) + ((long long)q * MF.nt + t) * kFeatQ;
+#pragma unroll
+    for (int r = 0; r < kFeatQ; ++r) {
+        const float4 v = row[r];
+        m[4 * r] = v.x; m[4 * r + 1] = v.y; m[4 * r + 2] = v.z; m[4 * r + 3] = v.w;
+    }
+}
+
+// The pixel's image coordinates again after blend_range, from a thread index opaque to hipcc: kept alive across the loop they cost the
+// register that decides the feature kernels' sixth wave per SIMD.  Returns whether the pixel lies inside the image.
+DEV bool pixel_again(const SasCam &c, int tx, int ty, int &ix, int &iy)
+{
+    int t2 = threadIdx.x, ox, oy;
+    asm volatile("" : "+v"(t2));
+    pixel_of(t2 >> 6, t2 & 63, ox, oy);
+    bool inside, w2;
+    pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, w2);
+    return inside;
+}
+
 // One workgroup per (tile, chunk of SAS_FEAT_K channels), one lane per pixel (pixel_of), on the complete depth-ordered list the
 // full path's k_blend has just composited: the same blend_range, with the chunk's channels in the colours' place.  Every chunk
-// recomputes alpha and T.
+// recomputes alpha and T.  (The prologue is this kernel's own text, and k_blend_features_mesh's likewise: started from tile_lane /
+// tile_list as the label and lift kernels are, both come out 'equal' and not 'same' -- the list's length is formed at another place in
+// the scalar code -- and these two are the kernels whose register count decides a wave per SIMD.)
 template <bool FAST_EXP>
 // Six waves per SIMD as before (80 VGPRs, 25 KiB of LDS): hipcc settles for five (92 VGPRs) unless told.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_blend_features(SasParams P, SasFrame f, long long n_gauss,
@@ -2168,7 +2152,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     const int oi = (int)blockIdx.x, q = (int)blockIdx.y;
     if (!SAS_IN(oi, f.n_tiles, 310)) return;
     const int tile = f.tile_order[oi];
-    if (!SAS_IN(tile, f.n_tiles, 311)) return;   // (uniform)
+    if (!SAS_IN(tile, f.n_tiles, 312)) return;   // (uniform)
     const int tx = tile % c.tw, ty = tile / c.tw;
     int ox, oy, ix, iy;
     bool inside, wdone;
@@ -2183,15 +2167,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     blend_range<FAST_EXP>(f, n_gauss, tx, ty, pix_const(ox, oy), end > beg ? (int)(end - beg) : 0,
                           [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay);
     // write_pixel's epilogue on the chunk's channels: a = 1 - T, w = 1 - a, v = acc + w bg (no clamp)
-    {   // (the pixel's coordinates again, from a thread index opaque to hipcc: kept alive across blend_range they cost the register
-        // that decides the kernel's sixth wave per SIMD)
-        int t2 = tid;
-        asm volatile("" : "+v"(t2));
-        pixel_of(t2 >> 6, t2 & 63, ox, oy);
-        bool w2;
-        pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, w2);
-    }
-    if (!inside) return;
+    if (!pixel_again(c, tx, ty, ix, iy)) return;
     const long long pix = (long long)iy * c.W + ix;
     if (!SAS_IN(pix, P.out.n_pixels, 316)) return;
     const float a = 1.0f - p.T;
@@ -2242,16 +2218,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     unsigned sync_phase = 0u;
     blend_range<FAST_EXP, true>(f, n_gauss, tx, ty, pix_const(ox, oy), end > beg ? (int)(end - beg) : 0,
                                 [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay, zlim);
-    {   // (the pixel's coordinates again, as in k_blend_features)
-        int t2 = tid;
-        asm volatile("" : "+v"(t2));
-        pixel_of(t2 >> 6, t2 & 63, ox, oy);
-        bool w2;
-        pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, w2);
-    }
-    if (!inside) return;
+    if (!pixel_again(c, tx, ty, ix, iy)) return;
     const long long pix = (long long)iy * c.W + ix;
-    if (!SAS_IN(pix, P.out.n_pixels, 331)) return;
+    if (!SAS_IN(pix, P.out.n_pixels, 334)) return;
     const float a = 1.0f - p.T;
     const float wb = 1.0f - a;
     const int c0 = q * SAS_FEAT_K;
@@ -2261,14 +2230,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     const long long t = (long long)((unsigned)win >> 1);
     const bool covered = win != ~0ull && t < MF.nt && SAS_IN(t, MF.nt, 328);
     float m[SAS_FEAT_K];
-    if (covered) {
-        const float4 *row = reinterpret_cast<const float4 *>(MF.store) + ((long long)q * MF.nt + t) * kFeatQ;
-#pragma unroll
-        for (int r = 0; r < kFeatQ; ++r) {
-            const float4 v = row[r];
-            m[4 * r] = v.x; m[4 * r + 1] = v.y; m[4 * r + 2] = v.z; m[4 * r + 3] = v.w;
-        }
-    }
+    if (covered) mesh_feature_row(MF, q, t, m);
 #pragma unroll
     for (int k = 0; k < SAS_FEAT_K; ++k) {
         const int ch = c0 + k;
@@ -2294,12 +2256,9 @@ DEV void label_tile(const SasParams &P, const SasFrame &f, long long n_gauss, co
     if (!SAS_IN(oi, f.n_tiles, 340)) return;
     const int tile = f.tile_order[oi];
     if (!SAS_IN(tile, f.n_tiles, 341)) return;   // (uniform)
-    const int tx = tile % c.tw, ty = tile / c.tw;
-    int ox, oy, ix, iy;
-    bool inside, wdone0;
-    pixel_of(wv, lane, ox, oy);
-    pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone0);
-    const long long pix = (long long)iy * c.W + ix;
+    TileLane w = tile_lane(c, tile, wv, lane);
+    const bool inside = w.inside;
+    const long long pix = (long long)w.iy * c.W + w.ix;
     // the pixel's triangle as the frame's k_blend_mesh_scene resolved it (MF->win): its depth stops the splats, its row closes the sum
     unsigned long long win = ~0ull;
     float zlim = __builtin_inff();
@@ -2310,20 +2269,18 @@ DEV void label_tile(const SasParams &P, const SasFrame &f, long long n_gauss, co
     const long long t = (long long)((unsigned)win >> 1);   // (records 2 t, 2 t + 1 belong to triangle t)
     bool covered = false;
     if constexpr (MESH) covered = win != ~0ull && t < MF->nt && SAS_IN(t, MF->nt, 343);
-    long long beg, end;
-    tile_segment(f, tile, beg, end);
-    const int *ids = f.sorted_ids + beg;
-    const int count = end > beg ? (int)(end - beg) : 0;
+    tile_list(f, w);
+    const int *ids = w.ids;
     unsigned long long ph_lap_ = 0ull;
     unsigned sync_phase = 0u;
     float best = -__builtin_inff(), T = 1.0f;
     int arg = 255;
 #pragma unroll 1
     for (int q = 0; q < B.chunks; ++q) {
-        PixState p = pix_init(inside, ox);
-        bool wdone = wdone0;
+        PixState p = w.p;   // (the pixel starts afresh)
+        bool wdone = w.wdone;
         FeaturePayloadT<MESH> pay{reinterpret_cast<const float4 *>(B.store) + (long long)q * B.n_pad * kFeatQ, B.n_pad, {}};
-        blend_range<FAST_EXP, MESH>(f, n_gauss, tx, ty, pix_const(ox, oy), count,
+        blend_range<FAST_EXP, MESH>(f, n_gauss, w.tx, w.ty, pix_const(w.ox, w.oy), w.count,
                                     [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay, zlim);
         T = p.T;   // (the same in every pass)
         const float a = 1.0f - p.T;
@@ -2332,14 +2289,7 @@ DEV void label_tile(const SasParams &P, const SasFrame &f, long long n_gauss, co
 #pragma unroll
         for (int k = 0; k < SAS_FEAT_K; ++k) m[k] = 0.0f;
         if constexpr (MESH) {
-            if (covered && SAS_IN((long long)q * MF->nt + t, (long long)B.chunks * MF->nt, 344)) {
-                const float4 *row = reinterpret_cast<const float4 *>(MF->store) + ((long long)q * MF->nt + t) * kFeatQ;
-#pragma unroll
-                for (int r = 0; r < kFeatQ; ++r) {
-                    const float4 v = row[r];
-                    m[4 * r] = v.x; m[4 * r + 1] = v.y; m[4 * r + 2] = v.z; m[4 * r + 3] = v.w;
-                }
-            }
+            if (covered && SAS_IN((long long)q * MF->nt + t, (long long)B.chunks * MF->nt, 344)) mesh_feature_row(*MF, q, t, m);
         }
 #pragma unroll
         for (int k = 0; k < SAS_FEAT_K; ++k) {
@@ -2375,41 +2325,39 @@ __global__ __launch_bounds__(256) void k_blend_labels_mesh(SasParams P, SasFrame
 // first -- over the block for `seen`, over the block's lanes of one label for `votes` -- and one lane issues one 64-bit integer
 // atomic per (entry, block[, label]).  The four waves are not combined through LDS: they own different quadrants of the tile and
 // walk a batch at their own pace, and an entry reaches few blocks ("Label lifting").
-struct LiftPayload {
+// The plumbing of such a payload (blend_range's PAY; Self supplies give(idx, vis): one entry, whose Gaussian the lanes of a block share
+// because they read the same queue slot).
+template <typename Self, int CHK_ID, int CHK_SLOT, int CHK_OFF>
+struct IndexPayload {
     typedef int Rec;
     typedef int V;
     const int *perm;               // slot j holds the caller's Gaussian perm[j]
-    unsigned long long *votes;     // [n][n_labels], or nullptr
-    unsigned long long *seen;      // [n], or nullptr
     long long n;
-    int n_labels;
-    int label;                     // of this lane's pixel; >= n_labels: unlabelled (255, and pixels outside the image)
     DEV Rec none() const { return 0; }
-    DEV Rec fetch(const SasFrame &, long long id) const { return (SAS_IN(id, n, 350) && id < n) ? perm[id] : 0; }
+    DEV Rec fetch(const SasFrame &, long long id) const { return (SAS_IN(id, n, CHK_ID) && id < n) ? perm[id] : 0; }
     DEV void stage(const BlendLds &L, int slot, const Rec &c, float) const
     {
-        if (SAS_IN(slot, kStage, 351)) *reinterpret_cast<int *>(L.q2 + slot) = c;
+        if (SAS_IN(slot, kStage, CHK_SLOT)) *reinterpret_cast<int *>(L.q2 + slot) = c;
     }
     DEV void stage_sentinel(const BlendLds &L, float z0) const { L.q2[256] = make_float4(z0, z0, z0, z0); }   // Gaussian 0, weight 0
     DEV V load(const char *q2b, unsigned off) const
     {
-        if (!SAS_IN(off >> 4, kStage, 352)) off = 256u << 4;
+        if (!SAS_IN(off >> 4, kStage, CHK_OFF)) off = 256u << 4;
         return *reinterpret_cast<const int *>(q2b + off);
     }
     DEV float depth(const V &) const { return 0.0f; }
-    // sum over the 16 lanes of this lane's 4x4 block (lanes 16 g .. 16 g + 15 of the wave); q < 2^32 each, so the halves cannot overflow
-    // (a DPP row IS a block's 16 lanes: neighbours in a quad, the quad's other pair, then -- every lane of a quad holding the quad's
-    // sum -- the row's half mirror swaps the quads of a half and the row mirror the halves.  Every lane of the wave is active here.)
-    template <int CTRL>
-    static DEV unsigned row_move(unsigned v) { return (unsigned)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true); }
-    static DEV unsigned row_sum(unsigned v)
+    DEV void add(PixState &, const V &c0, float vis0, const V &c1, float vis1) const
     {
-        v += row_move<0xB1>(v);    // quad_perm:[1,0,3,2]
-        v += row_move<0x4E>(v);    // quad_perm:[2,3,0,1]
-        v += row_move<0x141>(v);   // row_half_mirror
-        v += row_move<0x140>(v);   // row_mirror
-        return v;
+        static_cast<const Self *>(this)->give(c0, vis0);
+        static_cast<const Self *>(this)->give(c1, vis1);
     }
+};
+struct LiftPayload : IndexPayload<LiftPayload, 350, 351, 352> {
+    unsigned long long *votes;     // [n][n_labels], or nullptr
+    unsigned long long *seen;      // [n], or nullptr
+    int n_labels;
+    int label;                     // of this lane's pixel; >= n_labels: unlabelled (255, and pixels outside the image)
+    // sum over the 16 lanes of this lane's 4x4 block (a DPP row: row_sum); q < 2^32 each, so the halves cannot overflow
     static DEV unsigned long long block_sum(unsigned q)
     {
         const unsigned lo = row_sum(q & 0xffffu), hi = row_sum(q >> 16);
@@ -2444,11 +2392,6 @@ struct LiftPayload {
             }
         }
     }
-    DEV void add(PixState &, const V &c0, float vis0, const V &c1, float vis1) const
-    {
-        give(c0, vis0);
-        give(c1, vis1);
-    }
 };
 
 // One workgroup per tile, one lane per pixel (pixel_of), on the complete depth-ordered lists the frame's k_blend has just composited.
@@ -2462,56 +2405,34 @@ __global__ __launch_bounds__(256) void k_lift_labels(SasParams P, SasFrame f, lo
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int oi = (int)blockIdx.x;
     if (!SAS_IN(oi, f.n_tiles, 355) || oi >= f.n_tiles) return;
-    if ((long long)f.tile_offset[f.n_tiles] > f.cap) return;   // (uniform) truncated lists: the frame's second rendering votes
+    if (lists_truncated(f)) return;   // (uniform) the frame's second rendering votes
     const int tile = f.tile_order[oi];
     if (!SAS_IN(tile, f.n_tiles, 356) || tile < 0 || tile >= f.n_tiles) return;   // (uniform)
-    const int tx = tile % c.tw, ty = tile / c.tw;
-    int ox, oy, ix, iy;
-    bool inside, wdone;
-    pixel_of(wv, lane, ox, oy);
-    PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
-    const long long pix = (long long)iy * c.W + ix;
+    TileLane w = tile_lane(c, tile, wv, lane);
+    const long long pix = (long long)w.iy * c.W + w.ix;
     int label = 256;
-    if (inside && SAS_IN(pix, P.out.n_pixels, 357)) label = (int)B.labels[pix];
-    long long beg, end;
-    tile_segment(f, tile, beg, end);
-    const int *ids = f.sorted_ids + beg;
-    LiftPayload pay{perm, B.votes, B.seen, B.n, B.n_labels, label};
+    if (w.inside && SAS_IN(pix, P.out.n_pixels, 357)) label = (int)B.labels[pix];
+    tile_list(f, w);
+    const int *ids = w.ids;
+    LiftPayload pay{{perm, B.n}, B.votes, B.seen, B.n_labels, label};
     unsigned long long ph_lap_ = 0ull;
     unsigned sync_phase = 0u;
-    blend_range<FAST_EXP>(f, n_gauss, tx, ty, pix_const(ox, oy), end > beg ? (int)(end - beg) : 0,
-                          [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay);
+    blend_range<FAST_EXP>(f, n_gauss, w.tx, w.ty, pix_const(w.ox, w.oy), w.count,
+                          [&](int i) { return (long long)(unsigned)ids[i]; }, L, w.p, w.wdone, ph_lap_, sync_phase, pay);
 }
 
 // Feature lifting (sas_lift_features): LiftPayload with the pixel's SAS_FEAT_K quantised channels of one chunk in the label's place.
 // q = floor(weight 2^24) < 2^24 and |fq| <= 32767, so q fq is a signed 40-bit product: q is split into two 12-bit halves, whose
-// products with fq stay below 2^27 and whose sums over the 16 lanes of a 4x4 block (a DPP row: LiftPayload::row_sum, which is
+// products with fq stay below 2^27 and whose sums over the 16 lanes of a 4x4 block (a DPP row: row_sum, which is
 // modular and therefore sums two's complement values as well) stay below 2^31.  Every lane of the row then holds the block's eight
 // channel sums; lane k < 8 issues channel k's 64-bit atomic, so one atomic wave-instruction writes one contiguous 64-byte segment
 // sums[i, 8c .. 8c + 7] per block.  Chunk 0 alone adds `weight`.  No float atomics, no combining across waves.
-struct LiftFeaturePayload {
-    typedef int Rec;
-    typedef int V;
-    const int *perm;               // slot j holds the caller's Gaussian perm[j]
+struct LiftFeaturePayload : IndexPayload<LiftFeaturePayload, 360, 361, 362> {
     unsigned long long *sums;      // [n][C], or nullptr
     unsigned long long *weight;    // [n], or nullptr (and in every chunk but the first)
-    long long n;
     int C, c0;                     // channels of the image; first channel of this workgroup's chunk
     bool live;                     // this lane's pixel is inside the image and not masked out
     int fq[SAS_FEAT_K];            // the pixel's quantised channels c0 .. c0 + 7 (0 beyond C)
-    DEV Rec none() const { return 0; }
-    DEV Rec fetch(const SasFrame &, long long id) const { return (SAS_IN(id, n, 360) && id < n) ? perm[id] : 0; }
-    DEV void stage(const BlendLds &L, int slot, const Rec &c, float) const
-    {
-        if (SAS_IN(slot, kStage, 361)) *reinterpret_cast<int *>(L.q2 + slot) = c;
-    }
-    DEV void stage_sentinel(const BlendLds &L, float z0) const { L.q2[256] = make_float4(z0, z0, z0, z0); }   // Gaussian 0, weight 0
-    DEV V load(const char *q2b, unsigned off) const
-    {
-        if (!SAS_IN(off >> 4, kStage, 362)) off = 256u << 4;
-        return *reinterpret_cast<const int *>(q2b + off);
-    }
-    DEV float depth(const V &) const { return 0.0f; }
     // (int32) rintf(min(max(x scale, -32767), 32767)), NaN -> 0: fminf / fmaxf return the operand that is a number, so NaN is tested
     static DEV int quantise(float x, float scale)
     {
@@ -2527,26 +2448,21 @@ struct LiftFeaturePayload {
         if (!__ballot(q != 0u)) return;   // (uniform) nobody in the wave composited this entry
         const int l16 = (int)(threadIdx.x & 15u);
         const bool ok = idx >= 0 && (long long)idx < n && SAS_IN(idx, n, 363);
-        const unsigned qs = LiftPayload::row_sum(q);   // 16 q < 2^28
+        const unsigned qs = row_sum(q);   // 16 q < 2^28
         if (weight && l16 == 0 && qs != 0u && ok) atomicAdd(weight + idx, (unsigned long long)qs);
         if (!sums) return;   // (uniform)
         const int ql = (int)(q & 0xfffu), qh = (int)(q >> 12);
         int lo = 0, hi = 0;   // of this lane's channel, l16
 #pragma unroll
         for (int k = 0; k < SAS_FEAT_K; ++k) {
-            const int sl = (int)LiftPayload::row_sum((unsigned)__mul24(ql, fq[k]));   // (both factors fit 24 bits: full-rate multiplies)
-            const int sh = (int)LiftPayload::row_sum((unsigned)__mul24(qh, fq[k]));
+            const int sl = (int)row_sum((unsigned)__mul24(ql, fq[k]));   // (both factors fit 24 bits: full-rate multiplies)
+            const int sh = (int)row_sum((unsigned)__mul24(qh, fq[k]));
             if (l16 == k) { lo = sl; hi = sh; }
         }
         const long long s = (long long)hi * 4096 + (long long)lo;
         const int ch = c0 + l16;
         const long long at = (long long)idx * C + ch;
         if (l16 < SAS_FEAT_K && ch < C && qs != 0u && s != 0 && ok && SAS_IN(at, n * C, 364)) atomicAdd(sums + at, (unsigned long long)s);
-    }
-    DEV void add(PixState &, const V &c0_, float vis0, const V &c1_, float vis1) const
-    {
-        give(c0_, vis0);
-        give(c1_, vis1);
     }
 };
 
@@ -2562,19 +2478,15 @@ __global__ __launch_bounds__(256) void k_lift_features(SasParams P, SasFrame f, 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int oi = (int)blockIdx.x, chunk = (int)blockIdx.y;
     if (!SAS_IN(oi, f.n_tiles, 365) || oi >= f.n_tiles) return;
-    if ((long long)f.tile_offset[f.n_tiles] > f.cap) return;   // (uniform) truncated lists: the frame's second rendering adds
+    if (lists_truncated(f)) return;   // (uniform) the frame's second rendering adds
     const int tile = f.tile_order[oi];
     if (!SAS_IN(tile, f.n_tiles, 366) || tile < 0 || tile >= f.n_tiles) return;   // (uniform)
     const int c0 = chunk * SAS_FEAT_K;
     if (c0 >= B.C) return;   // (uniform)
-    const int tx = tile % c.tw, ty = tile / c.tw;
-    int ox, oy, ix, iy;
-    bool inside, wdone;
-    pixel_of(wv, lane, ox, oy);
-    PixState p = pixel_begin(c, tx, ty, ox, oy, ix, iy, inside, wdone);
-    const long long pix = (long long)iy * c.W + ix;
-    LiftFeaturePayload pay{perm, B.sums, chunk == 0 ? B.weight : nullptr, B.n, B.C, c0, false, {}};
-    bool live = inside && SAS_IN(pix, P.out.n_pixels, 367);
+    TileLane w = tile_lane(c, tile, wv, lane);
+    const long long pix = (long long)w.iy * c.W + w.ix;
+    LiftFeaturePayload pay{{perm, B.n}, B.sums, chunk == 0 ? B.weight : nullptr, B.C, c0, false, {}};
+    bool live = w.inside && SAS_IN(pix, P.out.n_pixels, 367);
     if (live && B.mask) live = B.mask[pix] != 0;
 #pragma unroll
     for (int k = 0; k < SAS_FEAT_K; ++k) {
@@ -2584,13 +2496,12 @@ __global__ __launch_bounds__(256) void k_lift_features(SasParams P, SasFrame f, 
         pay.fq[k] = LiftFeaturePayload::quantise(x, B.scale);
     }
     pay.live = live;
-    long long beg, end;
-    tile_segment(f, tile, beg, end);
-    const int *ids = f.sorted_ids + beg;
+    tile_list(f, w);
+    const int *ids = w.ids;
     unsigned long long ph_lap_ = 0ull;
     unsigned sync_phase = 0u;
-    blend_range<FAST_EXP>(f, n_gauss, tx, ty, pix_const(ox, oy), end > beg ? (int)(end - beg) : 0,
-                          [&](int i) { return (long long)(unsigned)ids[i]; }, L, p, wdone, ph_lap_, sync_phase, pay);
+    blend_range<FAST_EXP>(f, n_gauss, w.tx, w.ty, pix_const(w.ox, w.oy), w.count,
+                          [&](int i) { return (long long)(unsigned)ids[i]; }, L, w.p, w.wdone, ph_lap_, sync_phase, pay);
 }
 
 }  // namespace

@@ -24,6 +24,55 @@ def test_header_symbols_are_exported(built_lib):
         assert hasattr(L, name), name
 
 
+def _last_argument(text, at):
+    """The last argument of the call whose opening parenthesis is at text[at]."""
+    depth, start = 0, at + 1
+    for i in range(at, len(text)):
+        ch = text[i]
+        if ch == "(":
+            depth += 1
+        elif ch == ")":
+            depth -= 1
+            if depth == 0:
+                return text[start:i].strip()
+        elif ch == "," and depth == 1:
+            start = i + 1
+    raise AssertionError("unbalanced SAS_IN(")
+
+
+def test_every_bounds_code_names_one_site():
+    """sas_debug_bounds reports the first violation BY CODE, so a code names one site: every literal code of a SAS_IN(.., code) in
+    csrc/ occurs once, and the codes a template takes as int parameters (CHK_*) are distinct literals over all its instantiations."""
+    text = ""
+    for src in sorted((ROOT / "sim_a_splat_amd" / "csrc").iterdir()):
+        if src.suffix in (".hip", ".h"):
+            body = re.sub(r"//[^\n]*", "", src.read_text())
+            text += "\n".join(ln for ln in body.split("\n") if not ln.lstrip().startswith("#define SAS_IN")) + "\n"
+    codes, names = [], set()
+    for m in re.finditer(r"\bSAS_IN\(", text):
+        arg = _last_argument(text, m.end() - 1)
+        (codes.append(int(arg)) if arg.isdigit() else names.add(arg))
+    assert len(codes) > 100, len(codes)   # (the scan found the guards)
+    # templates with code parameters: name -> positions of its CHK_* parameters; every use names literals there
+    templated = set()
+    for m in re.finditer(r"template\s*<([^<>]*\bint\s+CHK_[^<>]*)>\s*(?:struct\s+(\w+)|DEV\s+[\w\s]+?[\s*&](\w+)\s*\()", text):
+        params = [p.split()[-1] for p in m.group(1).split(",")]
+        where = [i for i, p in enumerate(params) if p.startswith("CHK_")]
+        templated |= {params[i] for i in where}
+        name = m.group(2) or m.group(3)
+        uses = re.findall(r"\b%s<([^<>;(){}]*)>" % name, text)
+        assert uses, name
+        for use in uses:
+            args = [a.strip() for a in use.split(",")]
+            assert len(args) == len(params) and all(args[i].isdigit() for i in where), (name, use)
+            codes += [int(args[i]) for i in where]
+    assert templated >= {"CHK_SRC", "CHK_DST", "CHK_ID", "CHK_SLOT", "CHK_OFF"}, templated
+    # what is neither a literal nor a template's parameter is a code handed on as a function's argument
+    assert names - templated <= {"code"}, names - templated
+    again = sorted({c for c in codes if codes.count(c) > 1})
+    assert not again, f"bounds codes used at more than one site: {again}"
+
+
 def test_stat_and_stage_names_follow_the_header_enums():
     """The Python names of sas_frame_stats / sas_stage_times slots are the header's enums, in order."""
     from sim_a_splat_amd import _capi

@@ -61,6 +61,18 @@ def sectioned(name):
     return read
 
 
+def rows(names):
+    """read() of a probe that prints, per scene, one line per call with its device time first: the expression matches
+    (the call's words, ms); names maps those words to a metric's stem, and the scenes are numbered in the order printed."""
+    def read(m):
+        got = {}
+        for words, ms in m:
+            k = 1 + sum(1 for g in got if g.rsplit("_", 1)[0] == names[words])
+            got[f"{names[words]}_{k}"] = float(ms)
+        return got
+    return read
+
+
 def stage(cfg):
     return ([PY, "tools/stage_probe.py", "--cfg", str(cfg)], 200, stage_ms, {"project_ms": LO, "tile_ms": LO, "total_ms": LO})
 
@@ -106,6 +118,19 @@ PROBES = {
     "match": ([PY, "tools/match_probe.py"], 300,
               prose(r"^\d+ x (\d+) = \S+ pairs: +([\d.]+) ms per call", lambda m: {f"match{t}": float(ms) for t, ms in m}),
               {"match113831": LO, "match292247": LO}),
+    # the list readers behind a full-sort frame, per scene (1: the Gym cameras, 2: the 1920x1080 view of config 3): ms per view of the tile
+    # stage (k_blend + the reader) for the lift probes, of the call's device events for the backward probe
+    "lift": ([PY, "tools/lift_probe.py"], 300,
+             prose(r"^lift_labels \((votes \+ seen|seen only)\) +([\d.]+) \[", rows({"votes + seen": "lift", "seen only": "lift_seen"})),
+             {f"{k}_{s}": LO for k in ("lift", "lift_seen") for s in (1, 2)}),
+    "lift_features": ([PY, "tools/lift_features_probe.py"], 300,
+                      prose(r"^lift_features (C=\d+ \((?:sums \+ weight|weight only)\)) +([\d.]+) \[",
+                            rows({f"C={c} ({w})": f"liftf{c}{s}" for c in (3, 8, 32, 256) for w, s in (("sums + weight", ""), ("weight only", "w"))})),
+                      {f"liftf{c}{s}_{k}": LO for c in (3, 8, 32, 256) for s in ("", "w") for k in (1, 2)}),
+    "grad": ([PY, "tools/grad_probe.py"], 300,
+             prose(r"^render_backward (screen_space \(k_grad_tiles\)|\(k_grad_tiles \+ k_grad_project\)) +([\d.]+) \[",
+                   rows({"screen_space (k_grad_tiles)": "grad_tiles", "(k_grad_tiles + k_grad_project)": "grad_full"})),
+             {f"{k}_{s}": LO for k in ("grad_tiles", "grad_full") for s in (1, 2)}),
 }
 
 
