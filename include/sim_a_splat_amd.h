@@ -680,8 +680,10 @@ typedef struct sas_densify_config {
 } sas_densify_config;
 int sas_scene_densify(sas_ctx *ctx, const sas_densify_config *cfg, const float *grad_sum, const int32_t *count,
                       int32_t *parents_out_or_null, int64_t counts_out[4], void *stream);
-/* Host clock of the last successful sas_scene_densify, ms[0..n) of: the classes and their totals' read-back; the scatter and the read-back
- * of the new means and group ids; the storage order (the host sort); allocation, relayout, state and commit (tools/densify_probe.py). */
+/* Host clock of the last successful sas_scene_densify, ms[0..n) of: the classes and their totals' read-back; the scatter's enqueue; the
+ * storage order's enqueue; allocation, relayout, state and commit, whose wait is the first behind the scatter's and the order's kernels
+ * (tools/densify_probe.py).  Under SAS_ORDER=0 (the storage order on the host) ms[1] ends behind the read-back of the new means and group
+ * ids and ms[2] is the host sort. */
 int sas_scene_densify_times(sas_ctx *ctx, float *ms, int n);
 
 /*
@@ -739,8 +741,8 @@ typedef struct sas_mcmc_config {
     float min_opacity;     /* 0.005 */
     unsigned seed;
 } sas_mcmc_config;
-/* (sas_scene_densify_times then reports this call's laps: the weights and their totals' read-back; the draws, the rows and the read-back
- * of the new means and group ids; the storage order; allocation, relayout, state and commit.) */
+/* (sas_scene_densify_times then reports this call's laps: the weights and their totals' read-back; the draws' and the rows' enqueue; the
+ * storage order's enqueue; allocation, relayout, state and commit -- see there, also for SAS_ORDER=0.) */
 int sas_scene_mcmc_refine(sas_ctx *ctx, const sas_mcmc_config *cfg, int32_t *parents_out_or_null, int64_t counts_out[3], void *stream);
 
 /*
@@ -772,6 +774,24 @@ int sas_photometric_loss(sas_ctx *ctx, int width, int height, const float *rgb, 
  * scene was not uploaded in is SAS_ERR_INVALID; SAS_ERR_NO_SCENE before an upload.  Blocking; frames in flight are completed.
  */
 int sas_scene_read(sas_ctx *ctx, float *means, float *quats, float *scales, float *cov6, float *opacities, float *colors);
+
+/*
+ * The storage order ("Storage order"): the permutation slot -> caller's index in which a scene's Gaussians are stored,
+ * ordered by (group id, Hilbert index of the mean at 10 bits per axis over the finite coordinates' box, caller's index).  Computed on the
+ * device; the same bits as the host function the library keeps as its reference (SAS_ORDER=0 selects that one for uploads, densify and
+ * refine calls of a context).
+ *
+ * sas_storage_order needs no scene: means [n,3] float32, group_id [n] uint8 or NULL, perm_out [n] int32, all DEVICE.  Non-finite
+ * coordinates quantise to 0.  It only ENQUEUES, on `stream`: perm_out is complete when the stream reaches it.  n == 0 does nothing.  The
+ * scratch is the context's: a call on another stream runs behind the one before, and a call with a larger n than any before it grows
+ * the scratch first -- hipFree and hipMalloc, which wait for the device (so no earlier call loses its buffers) and are not allowed
+ * inside a stream capture: call once at the largest n before capturing.  SAS_ERR_INVALID for n < 0 or > 2^31 - 1, means or perm_out NULL.
+ *
+ * sas_scene_order copies the resident scene's permutation to perm_out [N] int32, HOST or DEVICE.  Blocking; frames in flight are
+ * completed.  SAS_ERR_NO_SCENE before an upload; an empty scene writes nothing.
+ */
+int sas_storage_order(sas_ctx *ctx, int64_t n, const float *means, const uint8_t *group_id_or_null, int32_t *perm_out, void *stream);
+int sas_scene_order(sas_ctx *ctx, int32_t *perm_out);
 
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical

@@ -92,9 +92,12 @@ struct RenderArgs {
 // The resident scene's planes (k_relayout's layout) and its storage order; sas_scene_densify builds a second record and swaps it in.
 struct Planes {
     DevBuf g0, g1, g2, col, gid8, perm;
-    std::vector<int> perm_host;   // perm's host copy: slot -> caller's index
+    std::vector<int> perm_host;   // perm's host copy (slot -> caller's index), made on demand: host_perm() fills it, forget_host_perm() drops it
+    bool perm_host_valid = false;
     int64_t n = 0, n_pad = 0;
-    int alloc(sas_ctx *c, int64_t count, int colour_planes);   // (the device buffers alone: perm_host is the caller's to fill)
+    int alloc(sas_ctx *c, int64_t count, int colour_planes);   // (the device buffers alone)
+    int host_perm(sas_ctx *c, const int **out);   // the host copy, read back from `perm` when it is not there (blocking)
+    void forget_host_perm() { perm_host.clear(); perm_host_valid = false; }   // wherever the device `perm` changes
     void bind(SasScene &s) const
     {
         s.g0 = (const float4 *)g0.p; s.g1 = (const float4 *)g1.p; s.g2 = (const float4 *)g2.p; s.col = (const float4 *)col.p;
@@ -250,6 +253,10 @@ struct Settings {
     // nothing in flight: the ring restarts at slot 0, so that a sequence of frames always meets the slots in the same order
     // (SAS_RING_RESTART=0: the ring goes on where it stood -- bench passes of 25 steps then start on alternating slot pairs)
     bool ring_restart = true;
+    // the storage order of a scene (upload, densify, mcmc_refine) is computed on the device (sas_order.hip); SAS_ORDER=0: by storage_order()
+    // on the host, from read-back means and group ids -- the reference the device path equals bit for bit, kept for A/B runs
+    // (tools/order_probe.py, profiles/storage_order.txt)
+    bool order_on_device = true;
     static Settings from_env()
     {
         Settings s;
@@ -265,6 +272,7 @@ struct Settings {
         if (num("SAS_DIRECT_BUDGET_MB", v)) s.direct_budget = std::max(1ll, v) << 20;
         if (num("SAS_QUAD_TILES", v) && v >= 0) s.quad_max_tiles = s.quad_max_tiles_solo = (int)v;
         if (num("SAS_RING_RESTART", v)) s.ring_restart = v != 0;
+        if (num("SAS_ORDER", v)) s.order_on_device = v != 0;
         return s;
     }
 };
@@ -298,7 +306,12 @@ struct sas_ctx : Settings {
     Event density_done;   // recorded behind sas_density_accumulate / sas_scene_reset_opacity / sas_scene_mcmc_noise on the caller's stream: the slots' streams wait for it
     DevBuf density_inv, density_cls, density_blk;   // scratch of sas_scene_densify (SasDensity); sas_scene_mcmc_refine shares inv and blk
     DevBuf mcmc_u32, mcmc_u64, mcmc_reloc;          // scratch of sas_scene_mcmc_refine (SasMcmc): weight | copies, prefix, reloc
-    float densify_ms[4] = {0, 0, 0, 0};   // host clock of the last sas_scene_densify / sas_scene_mcmc_refine: classes, scatter, storage_order, relayout + state + commit
+    DevBuf order_key, order_idx, order_table, order_rec;   // scratch of device_order (SasOrder): keys x 2, indices x 2, histogram table, partials + record
+    Event order_done;     // recorded behind device_order's launches: the next call's stream waits for it before it reuses the scratch
+    // host clock of the last sas_scene_densify / sas_scene_mcmc_refine: classes, scatter, storage order, relayout + state + commit.  With the
+    // order on the device (the default) laps 1 and 2 clock the ENQUEUE of the scatter and of the order; the kernels' time falls into lap 3,
+    // whose wait is the first behind them.  SAS_ORDER=0: lap 1 ends behind the read-back, lap 2 is the host sort.
+    float densify_ms[4] = {0, 0, 0, 0};
     DevBuf loss_scratch;  // sas_photometric_loss: [9 H W] partial planes + [tiles][4] workgroup sums + D (SasLoss)
     int match_cus = 0;   // compute units of the device, asked once (the slice count of sas_match_points)
     DevBuf host_stage;   // device staging of sas_render_batch_host's uint8 frames
@@ -525,6 +538,52 @@ struct OrderInput {
     }
     void order(std::vector<int> &perm) const { storage_order(n, means.data(), gid.empty() ? nullptr : gid.data(), perm); }
 };
+
+// The same permutation on the device (sas_order.hip), from device arrays into d_perm_out: enqueued on `stream`, nothing is waited for.  The
+// scratch is the context's and grows with the largest n; a call on another stream than the one before runs behind it (order_done).
+// n_groups: ids at or above it are reported in the record order_record() reads (256: a byte cannot be).
+int device_order(sas_ctx *c, int64_t n, const float *d_means, const uint8_t *d_gid_or_null, int *d_perm_out, hipStream_t stream, int n_groups = 256)
+{
+    if (n <= 0) return SAS_OK;
+    SasOrder q{};
+    q.means = d_means; q.gid = d_gid_or_null; q.perm = d_perm_out;
+    q.n = n; q.n_tiles = (n + SAS_ORDER_TILE - 1) / SAS_ORDER_TILE;
+    q.n_groups = n_groups;
+    const size_t m = (size_t)n, tiles = (size_t)q.n_tiles;
+    if (const int rc = ensure(c, {{c->order_key, sizeof(unsigned long long) * 2 * m}, {c->order_idx, sizeof(int) * 2 * m},
+                                  {c->order_table, sizeof(unsigned) * 256 * tiles},
+                                  {c->order_rec, sizeof(SasOrderRecord) + sizeof(int) * SAS_ORDER_PARTIAL * tiles}}))
+        return rc;
+    q.key[0] = (unsigned long long *)c->order_key.p; q.key[1] = q.key[0] + m;
+    q.idx[0] = (int *)c->order_idx.p; q.idx[1] = q.idx[0] + m;
+    q.table = (unsigned *)c->order_table.p;
+    q.rec = (SasOrderRecord *)c->order_rec.p;
+    q.partial = (int *)(q.rec + 1);
+    if (!c->order_done.h) HIP_TRY(c, hipEventCreateWithFlags(c->order_done.put(), hipEventDisableTiming));
+    else HIP_TRY(c, hipStreamWaitEvent(stream, c->order_done, 0));
+    sas_launch_order(stream, q);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->order_done, stream));
+    return SAS_OK;
+}
+
+// What the last device_order found of the group ids, once its stream has been waited for.
+int order_record(sas_ctx *c, SasOrderRecord &rec)
+{
+    HIP_TRY(c, hipMemcpy(&rec, c->order_rec.p, sizeof(rec), hipMemcpyDeviceToHost));
+    return SAS_OK;
+}
+
+int Planes::host_perm(sas_ctx *c, const int **out)
+{
+    if (!perm_host_valid) {
+        perm_host.resize((size_t)n);
+        if (n > 0) HIP_TRY(c, hipMemcpy(perm_host.data(), perm.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+        perm_host_valid = true;
+    }
+    *out = perm_host.data();
+    return SAS_OK;
+}
 
 // Camera constants in the oracle's operation order (oracle/sas_oracle.c cam_from, project_one).
 void make_cam(const float *V, const float *K, int W, int H, int tile_px, SasCam &c)
@@ -1247,15 +1306,18 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
     Planes &pl = c->planes;
     int rc;
     if ((rc = pl.alloc(c, n, planes))) return rc;
-    pl.perm_host.clear();
+    pl.forget_host_perm();
     if (n > 0) {
-        // storage order from host copies of the means / group ids
-        OrderInput in;
-        if ((rc = in.fetch(c, n, means, group_id, false, nullptr))) return rc;
-        for (int64_t i = 0; i < n && group_id; ++i)
-            if (in.gid[(size_t)i] >= n_groups) return fail(c, SAS_ERR_INVALID, "group_id[%lld]=%d >= n_groups=%d", (long long)i, (int)in.gid[(size_t)i], n_groups);
-        in.order(pl.perm_host);
-        HIP_TRY(c, hipMemcpy(pl.perm.p, pl.perm_host.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        if (!c->order_on_device) {
+            // SAS_ORDER=0: storage order from host copies of the means / group ids
+            OrderInput in;
+            if ((rc = in.fetch(c, n, means, group_id, false, nullptr))) return rc;
+            for (int64_t i = 0; i < n && group_id; ++i)
+                if (in.gid[(size_t)i] >= n_groups) return fail(c, SAS_ERR_INVALID, "group_id[%lld]=%d >= n_groups=%d", (long long)i, (int)in.gid[(size_t)i], n_groups);
+            in.order(pl.perm_host);
+            pl.perm_host_valid = true;
+            HIP_TRY(c, hipMemcpy(pl.perm.p, pl.perm_host.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        }
 
         // stage the caller's arrays (host or device) and re-lay them out on the device
         DevBuf s_means, s_q, s_s, s_cov, s_op, s_col, s_gid;
@@ -1271,6 +1333,17 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
         if (!rc) rc = stage(s_op, opacities, sizeof(float) * n);
         if (!rc) rc = stage(s_col, colors, sizeof(float) * (size_t)coeff_floats * n);
         if (!rc && group_id) rc = stage(s_gid, group_id, (size_t)n);
+        if (!rc && c->order_on_device) {
+            // storage order from the staged means / group ids, where they are; only the record of the group ids' check comes back
+            SasOrderRecord rec{};
+            rc = device_order(c, n, (const float *)s_means.p, group_id ? (const uint8_t *)s_gid.p : nullptr, (int *)pl.perm.p, nullptr, n_groups);
+            if (!rc && group_id) {
+                hipError_t e = hipStreamSynchronize(nullptr);
+                if (e != hipSuccess) rc = fail(c, SAS_ERR_HIP, "storage order: %s", hipGetErrorString(e));
+                if (!rc) rc = order_record(c, rec);
+                if (!rc && rec.bad_index >= 0) rc = fail(c, SAS_ERR_INVALID, "group_id[%lld]=%d >= n_groups=%d", (long long)rec.bad_index, rec.bad_id, n_groups);
+            }
+        }
         if (!rc) {
             sas_launch_relayout(nullptr, n, pl.n_pad, (const int *)pl.perm.p, (const float *)s_means.p,
                                 (const float *)s_q.p, (const float *)s_s.p, (const float *)s_cov.p,
@@ -2621,7 +2694,7 @@ struct NewRows {
     int64_t n_survivors;
 };
 
-// The tail sas_scene_densify and sas_scene_mcmc_refine share: the storage order of the new rows (on the host, as for an upload), new planes
+// The tail sas_scene_densify and sas_scene_mcmc_refine share: the storage order of the new rows (device_order, where they lie; SAS_ORDER=0: on the host, from read-back copies), new planes
 // and new optimiser state beside the old ones, relayout, the carried state, and the swap.  inv_old: caller's index -> old slot.  Laps 1 to 3
 // are taken here.  Nothing changes the context before the last wait: a failure leaves the scene as it was.
 static int commit_rows(sas_ctx *c, const NewRows &r, const int *inv_old, hipStream_t st, Laps &lap)
@@ -2629,18 +2702,28 @@ static int commit_rows(sas_ctx *c, const NewRows &r, const int *inv_old, hipStre
     const SasScene sc = c->scene;
     const int coeff_floats = sas_coeff_floats(sc.sh_degree), planes = sas_colour_planes(sc.sh_degree);
     int rc;
-    OrderInput in;
-    if ((rc = in.fetch(c, r.n, r.means, r.gid, true, st))) return rc;
-    lap(1);
     Planes np;
     Adam na;
-    in.order(np.perm_host);
-    lap(2);
-    if ((rc = np.alloc(c, r.n, planes))) return rc;
+    if (c->order_on_device) {
+        // the new `perm` alone, in front of lap 1: lap 2 is the order's enqueue and nothing else (np.alloc below finds it in place)
+        if ((rc = ensure(c, np.perm, sizeof(int) * (size_t)std::max<int64_t>((r.n + 63) & ~63ll, 64)))) return rc;
+        lap(1);   // (the scatter's enqueue: nothing is read back for the order)
+        if ((rc = device_order(c, r.n, r.means, r.gid, (int *)np.perm.p, st))) return rc;
+        lap(2);
+        if ((rc = np.alloc(c, r.n, planes))) return rc;   // (in lap 3, as on the host path)
+    } else {   // SAS_ORDER=0
+        OrderInput in;
+        if ((rc = in.fetch(c, r.n, r.means, r.gid, true, st))) return rc;
+        lap(1);
+        in.order(np.perm_host);
+        np.perm_host_valid = true;
+        lap(2);
+        if ((rc = np.alloc(c, r.n, planes))) return rc;
+    }
     std::copy(c->adam.on, c->adam.on + Adam::GROUPS, na.on);
     for (int k = 0; k < Adam::kRows; ++k)   // (every buffer zeroed: the lanes n .. n_pad)
         if (na.on[Adam::rows[k].group] && (rc = na.alloc(c, k, np.n_pad, planes, st, true))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(np.perm.p, np.perm_host.data(), sizeof(int) * (size_t)r.n, hipMemcpyHostToDevice, st));
+    if (!c->order_on_device) HIP_TRY(c, hipMemcpyAsync(np.perm.p, np.perm_host.data(), sizeof(int) * (size_t)r.n, hipMemcpyHostToDevice, st));
     sas_launch_relayout(st, r.n, np.n_pad, (const int *)np.perm.p, r.means, r.quats, r.scales, r.cov6, r.opac, r.colors, coeff_floats, planes,
                         r.gid, (float4 *)np.g0.p, (float4 *)np.g1.p, (float4 *)np.g2.p, (float4 *)np.col.p, (uint8_t *)np.gid8.p);
     SasDensityState s{};
@@ -2663,8 +2746,8 @@ static int commit_rows(sas_ctx *c, const NewRows &r, const int *inv_old, hipStre
     return SAS_OK;
 }
 
-// Densify, prune and re-order (sas_density.hip).  Host work: validation, two read-backs (the class totals; the new means and group ids
-// for storage_order), the allocations.  Everything the new scene needs is allocated before the context changes.
+// Densify, prune and re-order (sas_density.hip, sas_order.hip).  Host work: validation, one read-back (the class totals; SAS_ORDER=0: the new
+// means and group ids too, for storage_order), the allocations.  Everything the new scene needs is allocated before the context changes.
 int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *grad_sum, const int32_t *count, int32_t *parents_out,
                       int64_t counts_out[4], void *stream)
 {
@@ -2766,7 +2849,7 @@ int sas_scene_mcmc_noise(sas_ctx *c, float scale, int step, unsigned seed, void 
     return SAS_OK;
 }
 
-// Relocate and grow (sas_mcmc.hip).  Host work: validation, two read-backs (the totals; the new means and group ids for storage_order),
+// Relocate and grow (sas_mcmc.hip).  Host work: validation, one read-back (the totals; SAS_ORDER=0: the new means and group ids too),
 // the allocations, and the tail it shares with sas_scene_densify.
 int sas_scene_mcmc_refine(sas_ctx *c, const sas_mcmc_config *cfg, int32_t *parents_out, int64_t counts_out[3], void *stream)
 {
@@ -2865,6 +2948,31 @@ int sas_scene_reset_opacity(sas_ctx *c, float max_opacity, void *stream)
     HIP_TRY(c, hipGetLastError());
     if (const int rc = slots_wait_for(c, c->density_done, st)) return rc;
     scene_changed(c, Changed::Values);
+    return SAS_OK;
+}
+
+// The storage order of any means and group ids (device arrays), scene-free: device_order on the caller's stream.  Nothing is waited for.
+int sas_storage_order(sas_ctx *c, int64_t n, const float *means, const uint8_t *group_id_or_null, int32_t *perm_out, void *stream)
+{
+    if (!c) return SAS_ERR_INVALID;
+    if (n < 0 || n > 0x7fffffffll) return fail(c, SAS_ERR_INVALID, "sas_storage_order: n=%lld out of range", (long long)n);
+    if (n == 0) return SAS_OK;
+    if (!means || !perm_out) return fail(c, SAS_ERR_INVALID, "sas_storage_order: means and perm_out are required");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return device_order(c, n, means, group_id_or_null, perm_out, (hipStream_t)stream);
+}
+
+// The resident scene's permutation (slot -> caller's index), behind everything in flight; host or device destination.
+int sas_scene_order(sas_ctx *c, int32_t *perm_out)
+{
+    const char *who = "sas_scene_order";
+    if (const int rc = need_scene(c, who)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;
+    if (c->scene.n == 0) return SAS_OK;
+    if (!perm_out) return fail(c, SAS_ERR_INVALID, "%s: perm_out is NULL", who);
+    HIP_TRY(c, hipDeviceSynchronize());   // (optimiser steps and density calls run on the caller's streams)
+    HIP_TRY(c, hipMemcpy(perm_out, c->planes.perm.p, sizeof(int32_t) * (size_t)c->scene.n, hipMemcpyDefault));
     return SAS_OK;
 }
 
@@ -2976,7 +3084,7 @@ int sas_frames_completed(sas_ctx *c, int64_t *submitted, int64_t *completed)
 
 #ifdef SAS_DEBUG_BOUNDS
 // every kernel file's counter (SAS_BOUNDS_ACCESSOR in sas_device.h): one line per file, in the order their reports are looked at
-#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density) X(mcmc)
+#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density) X(mcmc) X(order)
 #define SAS_BOUNDS_DECLARE(name) extern "C" int sas_debug_bounds_##name(unsigned long long *out, int reset);
 #define SAS_BOUNDS_ENTRY(name) sas_debug_bounds_##name,
 SAS_BOUNDS_FILES(SAS_BOUNDS_DECLARE)
@@ -3052,8 +3160,10 @@ int sas_read_projection(sas_ctx *c, int32_t *radii, float *means2d, float *depth
         HIP_TRY(c, hipMemcpy(col.data(), q.col.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
         HIP_TRY(c, hipMemcpy(info.data(), q.info.p, sizeof(uint32_t) * 4 * n, hipMemcpyDeviceToHost));
     }
+    const int *perm = nullptr;
+    if (const int rc = c->planes.host_perm(c, &perm)) return rc;
     for (int64_t j = 0; j < n; ++j) {
-        const int64_t i = c->planes.perm_host[(size_t)j];   // slot j holds the caller's Gaussian i
+        const int64_t i = perm[(size_t)j];   // slot j holds the caller's Gaussian i
         const uint32_t rx = info[4 * j + 2], ry = info[4 * j + 3];   // radii: 32 bits each
         const bool vis = rx != 0;
         const float *r = &rec[8 * j], *cl = &col[4 * j];
@@ -3085,9 +3195,11 @@ int sas_read_tile_lists(sas_ctx *c, int32_t *tile_offsets, int32_t *sorted_ids, 
         if (m > cap) m = cap;
         if (m > q.cap) m = q.cap;
         if (m > 0) HIP_TRY(c, hipMemcpy(sorted_ids, q.ids.p, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost));
+        const int *perm = nullptr;
+        if (const int rc = c->planes.host_perm(c, &perm)) return rc;
         for (int64_t k = 0; k < m; ++k) {   // storage slots -> caller indices
             const int j = sorted_ids[k];
-            sorted_ids[k] = (j >= 0 && j < c->scene.n) ? c->planes.perm_host[(size_t)j] : -1;
+            sorted_ids[k] = (j >= 0 && j < c->scene.n) ? perm[(size_t)j] : -1;
         }
     }
     return SAS_OK;

@@ -701,3 +701,28 @@ void sas_launch_mcmc_weights(hipStream_t st, const SasMcmc &q);
 void sas_launch_mcmc_rows(hipStream_t st, const SasMcmc &q);
 // parents[i] = i (a call with nothing to do)
 void sas_launch_mcmc_identity(hipStream_t st, int64_t n, int *parents);
+
+// Storage order on the device (sas_storage_order, and behind sas_scene_upload, sas_scene_densify and sas_scene_mcmc_refine; DESIGN.md 3,
+// "Storage order"): the permutation storage_order() of sas_api.cpp gives on the host.  Every kernel takes its call by value.
+#define SAS_ORDER_TILE 2048         // keys a workgroup of a sort pass ranks (eight per lane); Gaussians per workgroup of the bounds pass
+#define SAS_ORDER_SCAN_ROUND 1024   // entries of the [256][tiles] histogram table the one-workgroup scan takes per round (four per lane)
+#define SAS_ORDER_PARTIAL 8         // ints of a workgroup's partial bounds: lo[3], hi[3] (as ordered ints), the first bad index, one unused
+struct SasOrderRecord {
+    float lo[3], hi[3], inv[3];   // per axis over the finite coordinates; inv = hi > lo ? 1023 / (hi - lo) : 0
+    int bad_index, bad_id;        // the smallest i with gid[i] >= n_groups and that id; -1, 0: none
+};
+struct SasOrder {
+    const float *means;           // [n,3] caller's order
+    const uint8_t *gid;           // [n] or nullptr: no groups (and no fifth pass)
+    long long n, n_tiles;         // n_tiles = ceil(n / SAS_ORDER_TILE)
+    int n_groups;                 // ids at or above it are reported in rec (256: none can be)
+    int *perm;                    // [n] out: slot -> caller's index
+    // scratch
+    unsigned long long *key[2];   // [n] each: group << 32 | Hilbert index, ping and pong
+    int *idx[2];                  // [n] each: the caller's indices that travel with the keys
+    unsigned *table;              // [256][n_tiles] digit-major histogram of a pass, then its exclusive offsets (16-byte aligned)
+    int *partial;                 // [n_tiles][SAS_ORDER_PARTIAL]
+    SasOrderRecord *rec;
+};
+// bounds, keys and the sort: 3 + 3 x (4 or 5) launches on st, nothing else
+void sas_launch_order(hipStream_t st, const SasOrder &q);

@@ -7,7 +7,7 @@ statistics (``density_accumulate`` after every backward pass) and, on the config
 where the scene lives, the optimiser state follows the survivors ("Density control").  With ``densify=McmcConfig(cap_max, ...)``
 the number of Gaussians is a budget instead: opacity and scale regularisers let Gaussians die, ``mcmc_refine`` re-births the dead on live
 ones and grows the set by 5 % a time up to ``cap_max``, and ``mcmc_noise`` after every step does the exploring ("MCMC
-density control").  That path keeps no statistics; ``mcmc_refine`` pays the same host sort of the storage order ``densify`` pays.
+density control").  That path keeps no statistics; ``mcmc_refine`` renews the storage order as ``densify`` does, on the device ("Storage order").
 
 The loss: ``loss=None`` descends a mean absolute difference (or the caller's ``loss_and_grad``) with the chain to the raw accumulators in
 torch; ``loss="dssim"`` descends the 3DGS photometric loss ``(1 - lambda) L1 + lambda (1 - SSIM)`` through ``Rasterizer.photometric_loss``,

@@ -1310,6 +1310,39 @@ class Rasterizer:
         return res
 
     @_locked
+    def storage_order(self, means: ArrayLike, group_id: Optional[ArrayLike] = None) -> torch.Tensor:
+        """The storage order ``upload`` would give these ``means [N,3]`` and ``group_id [N]`` (uint8; None: no groups), computed on the
+        device (sas_storage_order; DESIGN.md 3, "Storage order"): int32 ``[N]`` on the device, slot -> the caller's index, ordered by
+        (group, Hilbert index of the mean, index).  Device tensors are read where they are.  Needs no scene.  Only enqueues, on the
+        current stream (a call at a larger N than any before first grows the context's scratch, which waits for the device)."""
+        m = (means.detach() if isinstance(means, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(means, dtype=np.float32))))
+        m = m.to(device=self.device, dtype=torch.float32).contiguous()
+        if m.dim() != 2 or m.shape[1] != 3:
+            raise ValueError(f"means must be [N,3], got {list(m.shape)}")
+        n = int(m.shape[0])
+        g = None
+        if group_id is not None:
+            g = group_id.detach() if isinstance(group_id, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(group_id, dtype=np.uint8)))
+            g = g.to(device=self.device, dtype=torch.uint8).contiguous()
+            if g.numel() != n:
+                raise ValueError(f"group_id must be [{n}], got {list(g.shape)}")
+        perm = torch.empty(n, dtype=torch.int32, device=self.device)
+        rc = self._L.sas_storage_order(self._ctx, n, _addr(m), _addr(g), _addr(perm), self._stream())
+        if rc != 0:
+            self._check(rc, "sas_storage_order")
+        return perm   # (m and g were made on this stream or are the caller's: the allocator hands their memory on behind the kernels)
+
+    @_locked
+    def read_order(self) -> torch.Tensor:
+        """The resident scene's storage order (sas_scene_order): int32 ``[N]`` on the device, slot -> the caller's index, as
+        ``storage_order(read_scene()["means"], group_id)`` gives it straight after an ``upload``, a ``densify`` or an ``mcmc_refine``.
+        Blocking."""
+        perm = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        torch.cuda.synchronize(self.device)   # (the allocator may hand out memory that work in flight still uses)
+        self._check(self._L.sas_scene_order(self._ctx, _addr(perm)), "sas_scene_order")
+        return perm
+
+    @_locked
     def render_batch_host(self, viewmats: ArrayLike, Ks: ArrayLike, width: int, height: int,
                           background: Sequence[float] = (0.0, 0.0, 0.0), *, out: Optional[torch.Tensor] = None,
                           pose_sets: Optional[ArrayLike] = None, pose_set: Optional[Sequence[int]] = None) -> torch.Tensor:

@@ -10,7 +10,8 @@ rounds after a warm-up, the scene uploaded and stepped anew (untimed) in front o
 
   density_accumulate     device events around the call, after a render_backward
   densify                wall time of the blocking call, and its parts as the library clocks them on the host (sas_scene_densify_times):
-                         classes + totals read-back | scatter + means read-back | storage_order (host sort) | relayout + state
+                         classes + totals read-back | scatter (enqueue) | storage order (enqueue) | relayout + state + the wait for all three
+                           (under SAS_ORDER=0: rows + means read-back | storage_order, the host sort | relayout + state; tools/order_probe.py compares the two)
   reset_opacity          device events around the call
   torch alternative      read_scene -> masks, cat, randn children in torch on the device -> upload; it LOSES the optimiser moments (an
                          upload drops them), which densify carries"""
@@ -130,8 +131,8 @@ def case(name, n, seed, ls, G, W, H, f, rounds):
     say(f"  reset_opacity (device events)                 {med(rst):9.3f} ms  [{min(rst):.3f}..{max(rst):.3f}]")
     say(f"  densify, blocking call (wall)                 {med(dens):9.3f} ms  [{min(dens):.3f}..{max(dens):.3f}]")
     say(f"    classes + totals read-back                  {p[0]:9.3f} ms")
-    say(f"    scatter + means / group ids read-back       {p[1]:9.3f} ms")
-    say(f"    storage_order on the host (the sort)        {p[2]:9.3f} ms   = {100 * p[2] / max(sum(p), 1e-9):.0f} % of the call's clocked parts")
+    say(f"    scatter: enqueue (SAS_ORDER=0: + read-back) {p[1]:9.3f} ms")
+    say(f"    storage order: enqueue (SAS_ORDER=0: sort)  {p[2]:9.3f} ms   = {100 * p[2] / max(sum(p), 1e-9):.0f} % of the call's clocked parts")
     say(f"    allocation, relayout + state, commit        {p[3]:9.3f} ms")
     say(f"  read_scene -> torch rules -> upload (wall)    {med(alt):9.3f} ms  [{min(alt):.3f}..{max(alt):.3f}]   (loses the moments)")
     say(f"  alternative / densify = {med(alt) / med(dens):.2f}x")

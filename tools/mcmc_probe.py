@@ -12,7 +12,8 @@ relocates 10 % and adds 5 %.  Per scene, in one process on one box, medians over
                            the planes, the gradients and the moments, 1 740 B)
   iteration                render + photometric_loss + render_backward + adam_step, with and without mcmc_noise behind it (wall, synchronised)
   mcmc_refine              wall time of the blocking call, and its parts as the library clocks them on the host (sas_scene_densify_times):
-                           weights + totals read-back | draws, rows + means read-back | storage_order (host sort) | relayout + state
+                           weights + totals read-back | draws, rows (enqueue) | storage order (enqueue) | relayout + state + the wait for all three
+                           (under SAS_ORDER=0: rows + means read-back | storage_order, the host sort | relayout + state; tools/order_probe.py compares the two)
   densify                  the same scene and state through the default strategy's call (about 10 % cloned, 10 % split, 5 % pruned), for scale"""
 import argparse
 import ctypes
@@ -126,8 +127,8 @@ def case(name, n, seed, ls, G, W, H, f, rounds):
     say(f"  mcmc_refine: N {n} -> {out['n']}: relocated {out['relocated']} ({100 * out['relocated'] / n:.1f} %), added {out['added']} ({100 * out['added'] / n:.1f} %); medians of {rounds} rounds")
     say(f"  mcmc_refine, blocking call (wall)             {med(ref):9.3f} ms  [{min(ref):.3f}..{max(ref):.3f}]")
     say(f"    weights + totals read-back                  {p[0]:9.3f} ms")
-    say(f"    draws, rows + means / group ids read-back   {p[1]:9.3f} ms")
-    say(f"    storage_order on the host (the sort)        {p[2]:9.3f} ms   = {100 * p[2] / max(sum(p), 1e-9):.0f} % of the call's clocked parts")
+    say(f"    draws, rows: enqueue (SAS_ORDER=0: + r.-b.) {p[1]:9.3f} ms")
+    say(f"    storage order: enqueue (SAS_ORDER=0: sort)  {p[2]:9.3f} ms   = {100 * p[2] / max(sum(p), 1e-9):.0f} % of the call's clocked parts")
     say(f"    allocation, relayout + state, commit        {p[3]:9.3f} ms")
     say(f"  densify: N {n} -> {dout['n']} (cloned {dout['cloned']}, split {dout['split']}, pruned {dout['pruned']})")
     say(f"  densify, blocking call (wall)                 {med(dens):9.3f} ms  [{min(dens):.3f}..{max(dens):.3f}]   parts {dp[0]:.3f} | {dp[1]:.3f} | {dp[2]:.3f} | {dp[3]:.3f} ms")
