@@ -793,6 +793,27 @@ int sas_scene_read(sas_ctx *ctx, float *means, float *quats, float *scales, floa
 int sas_storage_order(sas_ctx *ctx, int64_t n, const float *means, const uint8_t *group_id_or_null, int32_t *perm_out, void *stream);
 int sas_scene_order(sas_ctx *ctx, int32_t *perm_out);
 
+/*
+ * Nearest neighbours within one cloud ("Scene from points"): for every point of points [n,3] its k nearest OTHER points of the
+ * same cloud, exactly.  d2 = (dx dx + dy dy) + dz dz in IEEE binary32, nothing fused, d = candidate - point; candidates are compared by the
+ * key bits(d2) << 32 | index: the k smallest keys win, in ascending order, so equal distances go to the lower index.  The point itself is
+ * left out by INDEX: a duplicate is a neighbour at d2 = 0.  A candidate whose d2 is NaN or +inf never counts, so a point with a non-finite
+ * coordinate neither is a neighbour nor has one.  Missing neighbours read dist2 = +inf, index = -1.  No result depends on the grid the
+ * library searches with, on the launch shape or on the order in which its workgroups run.
+ *
+ * points, dist2_out [n,k] float32 and index_out_or_null [n,k] int32 are DEVICE arrays.  Needs no scene.  It only ENQUEUES, on `stream`, and
+ * shares sas_storage_order's rules for the context's scratch (a larger n grows it first, which waits for the device).  n == 0 does nothing.
+ * SAS_ERR_INVALID for k outside 1..8, n < 0 or > 2^31 - 1, points or dist2_out NULL with n > 0.
+ * The environment variable SAS_KNN_GRID=g (read when the context is created) forces g cells per axis in the place of the library's choice;
+ * g = 1 is pure brute force.
+ *
+ * sas_knn_last_counts (blocking) reports what the last call decided on the device, up to n of: [0] points the grid search handed to the
+ * brute-force kernel, [1..3] the grid's cells per axis, [4] 1 when there was no grid (the whole cloud went through the brute-force kernel),
+ * [5], [6] the occupied cells of the 32^3 and 16^3 occupancy grids the choice was made from.  Zeros before the first call.
+ */
+int sas_knn_points(sas_ctx *ctx, int64_t n, const float *points, int k, float *dist2_out, int32_t *index_out_or_null, void *stream);
+int sas_knn_last_counts(sas_ctx *ctx, int64_t *out, int n);
+
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical
  * field of view; the view matrices and intrinsics are those of sas_camera_matrices. */

@@ -257,6 +257,9 @@ struct Settings {
     // on the host, from read-back means and group ids -- the reference the device path equals bit for bit, kept for A/B runs
     // (tools/order_probe.py, profiles/storage_order.txt)
     bool order_on_device = true;
+    // sas_knn_points chooses its grid on the device (sas_knn.hip: the grid rule); SAS_KNN_GRID=g forces g cells per axis, 1: no grid, every
+    // point through the brute-force kernel.  No result depends on it: the knob is there so that tests and tools/knn_probe.py compare the paths
+    int knn_grid = 0;
     static Settings from_env()
     {
         Settings s;
@@ -273,6 +276,7 @@ struct Settings {
         if (num("SAS_QUAD_TILES", v) && v >= 0) s.quad_max_tiles = s.quad_max_tiles_solo = (int)v;
         if (num("SAS_RING_RESTART", v)) s.ring_restart = v != 0;
         if (num("SAS_ORDER", v)) s.order_on_device = v != 0;
+        if (num("SAS_KNN_GRID", v) && v >= 1 && v <= SAS_KNN_MAX_AXIS) s.knn_grid = (int)v;
         return s;
     }
 };
@@ -308,6 +312,8 @@ struct sas_ctx : Settings {
     DevBuf mcmc_u32, mcmc_u64, mcmc_reloc;          // scratch of sas_scene_mcmc_refine (SasMcmc): weight | copies, prefix, reloc
     DevBuf order_key, order_idx, order_table, order_rec;   // scratch of device_order (SasOrder): keys x 2, indices x 2, histogram table, partials + record
     Event order_done;     // recorded behind device_order's launches: the next call's stream waits for it before it reuses the scratch
+    DevBuf knn_pts, knn_table, knn_left, knn_keys, knn_rec;   // scratch of sas_knn_points (SasKnn): cell-ordered points, cell table + block sums, leftover list, slice keys, records
+    Event knn_done;       // recorded behind sas_knn_points' launches, as order_done
     // host clock of the last sas_scene_densify / sas_scene_mcmc_refine: classes, scatter, storage order, relayout + state + commit.  With the
     // order on the device (the default) laps 1 and 2 clock the ENQUEUE of the scatter and of the order; the kernels' time falls into lap 3,
     // whose wait is the first behind them.  SAS_ORDER=0: lap 1 ends behind the read-back, lap 2 is the host sort.
@@ -2962,6 +2968,81 @@ int sas_storage_order(sas_ctx *c, int64_t n, const float *means, const uint8_t *
     return device_order(c, n, means, group_id_or_null, perm_out, (hipStream_t)stream);
 }
 
+// The k nearest other points of every point of one cloud (sas_knn.hip), scene-free, device arrays: enqueued on the caller's stream, nothing is
+// waited for.  The scratch is the context's and grows with the largest call; a call on another stream than the one before runs behind it.
+//   knn_rec:   [SasOrderRecord | SasKnnGrid | pad to 256 | occupancy words | partial bounds of sas_launch_order_bounds]
+//   knn_table: [4 zero words | table_len cell entries | table_len / SAS_KNN_SCAN_BLOCK block sums]
+int sas_knn_points(sas_ctx *c, int64_t n, const float *points, int k, float *dist2_out, int32_t *index_out_or_null, void *stream)
+{
+    const char *who = "sas_knn_points";
+    if (!c) return SAS_ERR_INVALID;
+    if (k < 1 || k > SAS_KNN_MAX_K) return fail(c, SAS_ERR_INVALID, "%s: k=%d out of [1,%d]", who, k, SAS_KNN_MAX_K);
+    if (n < 0 || n > 0x7fffffffll) return fail(c, SAS_ERR_INVALID, "%s: n=%lld out of range", who, (long long)n);
+    if (n == 0) return SAS_OK;
+    if (!points || !dist2_out) return fail(c, SAS_ERR_INVALID, "%s: points and dist2_out are required", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t m = (size_t)n;
+    const int K = k <= 3 ? 3 : SAS_KNN_MAX_K;
+    SasKnn q{};
+    q.points = points; q.n = n; q.k = k; q.forced_g = c->knn_grid;
+    q.dist2 = dist2_out; q.index = index_out_or_null;
+    q.cells_cap = std::min<long long>(SAS_KNN_MAX_CELLS, std::max<long long>(4096, 2 * (long long)n));
+    q.table_len = (q.cells_cap + 1 + SAS_KNN_SCAN_BLOCK - 1) / SAS_KNN_SCAN_BLOCK * SAS_KNN_SCAN_BLOCK;
+    // slices of k_knn_brute: as many as keep the slice keys within 256 MiB, 32 at most; never more than the cloud has chunks
+    const long long n_chunks = (n + SAS_KNN_CHUNK - 1) / SAS_KNN_CHUNK;
+    long long slices = std::min<long long>(32, std::max<long long>(1, (256ll << 20) / (long long)(sizeof(unsigned long long) * m * K)));
+    slices = std::min(slices, n_chunks);
+    q.slice_points = (n_chunks + slices - 1) / slices * SAS_KNN_CHUNK;
+    q.slices = (int)((n + q.slice_points - 1) / q.slice_points);   // (no slice is empty)
+    SasOrder b{};
+    b.means = points; b.n = n; b.n_tiles = (n + SAS_ORDER_TILE - 1) / SAS_ORDER_TILE; b.n_groups = 256;
+    const size_t rec_bytes = 256, occ_bytes = sizeof(unsigned) * SAS_KNN_COARSE * SAS_KNN_COARSE;
+    static_assert(sizeof(SasOrderRecord) + sizeof(SasKnnGrid) <= 256, "the two records share the block's first 256 bytes");
+    const size_t table_words = 4 + (size_t)q.table_len + (size_t)(q.table_len / SAS_KNN_SCAN_BLOCK);
+    if (const int rc = ensure(c, {{c->knn_pts, sizeof(float4) * m}, {c->knn_table, sizeof(unsigned) * table_words}, {c->knn_left, sizeof(int) * m},
+                                  {c->knn_keys, sizeof(unsigned long long) * m * (size_t)K * (size_t)q.slices},
+                                  {c->knn_rec, rec_bytes + occ_bytes + sizeof(int) * SAS_ORDER_PARTIAL * (size_t)b.n_tiles}}))
+        return rc;
+    char *rec = (char *)c->knn_rec.p;
+    b.rec = (SasOrderRecord *)rec;
+    b.partial = (int *)(rec + rec_bytes + occ_bytes);
+    q.bounds = b.rec;
+    q.grid = (SasKnnGrid *)(rec + sizeof(SasOrderRecord));
+    q.occ = (unsigned *)(rec + rec_bytes);
+    q.table = (unsigned *)c->knn_table.p + 4;
+    q.blk = q.table + q.table_len;
+    q.pts = (float4 *)c->knn_pts.p;
+    q.left = (int *)c->knn_left.p;
+    q.keys = (unsigned long long *)c->knn_keys.p;
+    if (!c->knn_done.h) HIP_TRY(c, hipEventCreateWithFlags(c->knn_done.put(), hipEventDisableTiming));
+    else HIP_TRY(c, hipStreamWaitEvent(st, c->knn_done, 0));
+    HIP_TRY(c, hipMemsetAsync(rec, 0, rec_bytes + occ_bytes, st));
+    HIP_TRY(c, hipMemsetAsync(c->knn_table.p, 0, sizeof(unsigned) * table_words, st));
+    sas_launch_order_bounds(st, b);
+    sas_launch_knn(st, q);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->knn_done, st));
+    return SAS_OK;
+}
+
+// What the last sas_knn_points decided on the device, once its work is done (blocking): out[0] points the ring search handed to the brute-force
+// kernel (the whole cloud without a grid: out[4] = 1), out[1..3] the grid's cells per axis, out[5], out[6] the occupied 32^3 / 16^3 coarse cells.
+int sas_knn_last_counts(sas_ctx *c, int64_t *out, int n)
+{
+    if (!c || !out) return SAS_ERR_INVALID;
+    SasKnnGrid G{};
+    G.n[0] = G.n[1] = G.n[2] = 0;
+    if (c->knn_rec.p) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipDeviceSynchronize());
+        HIP_TRY(c, hipMemcpy(&G, (const char *)c->knn_rec.p + sizeof(SasOrderRecord), sizeof(G), hipMemcpyDeviceToHost));
+    }
+    const int64_t v[7] = {(int64_t)G.left_count, G.n[0], G.n[1], G.n[2], G.brute, G.occupied[0], G.occupied[1]};
+    for (int k = 0; k < n && k < 7; ++k) out[k] = v[k];
+    return SAS_OK;
+}
+
 // The resident scene's permutation (slot -> caller's index), behind everything in flight; host or device destination.
 int sas_scene_order(sas_ctx *c, int32_t *perm_out)
 {
@@ -3084,7 +3165,7 @@ int sas_frames_completed(sas_ctx *c, int64_t *submitted, int64_t *completed)
 
 #ifdef SAS_DEBUG_BOUNDS
 // every kernel file's counter (SAS_BOUNDS_ACCESSOR in sas_device.h): one line per file, in the order their reports are looked at
-#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density) X(mcmc) X(order)
+#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density) X(mcmc) X(order) X(knn)
 #define SAS_BOUNDS_DECLARE(name) extern "C" int sas_debug_bounds_##name(unsigned long long *out, int reset);
 #define SAS_BOUNDS_ENTRY(name) sas_debug_bounds_##name,
 SAS_BOUNDS_FILES(SAS_BOUNDS_DECLARE)

@@ -1,4 +1,4 @@
-// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip, sas_mcmc.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip, sas_mcmc.hip, sas_order.hip, sas_knn.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -726,3 +726,45 @@ struct SasOrder {
 };
 // bounds, keys and the sort: 3 + 3 x (4 or 5) launches on st, nothing else
 void sas_launch_order(hipStream_t st, const SasOrder &q);
+// the first two launches of sas_launch_order alone: q.rec <- lo, hi, inv (and the group record) of q.means; reads means, gid, n, n_tiles, n_groups,
+// writes partial and rec (sas_knn.hip takes its grid's bounds from it)
+void sas_launch_order_bounds(hipStream_t st, const SasOrder &q);
+
+// k nearest neighbours within one cloud (sas_knn_points; DESIGN.md 3, "Scene from points").  Every kernel takes its call by value; what the
+// device decides (the grid, the leftover count) lives in one record the kernels read.
+#define SAS_KNN_MAX_K 8
+#define SAS_KNN_MAX_AXIS 1024           // cells per axis at most: the stop bound's rounding margin is derived for it (sas_knn.hip)
+#define SAS_KNN_MAX_CELLS (1 << 21)     // the table budget: cells of a grid at most (8 MiB of starts)
+#define SAS_KNN_SCAN_BLOCK 2048         // table entries per workgroup of the scan kernels (eight per lane)
+#define SAS_KNN_RING_LIMIT 4            // a lane still searching after this Chebyshev ring goes to the leftover list
+#define SAS_KNN_CHUNK 256               // candidates k_knn_brute stages in LDS at a time (4 KiB)
+#define SAS_KNN_COARSE 32               // cells per axis of the occupancy bitmask the grid rule reads
+struct SasKnnGrid {
+    float lo[3];          // the finite bounds' lower corner
+    float inv, h_lo;      // cell(v) = min((int)((v - lo) * inv), n - 1); h_lo: a float below the real 1 / inv
+    int n[3], n_cells;    // cells per axis (x fastest) and their product
+    int brute;            // 1: no grid (forced, or no extent to divide): every point goes through k_knn_brute, in the caller's order
+    unsigned left_count;  // points the ring search handed to k_knn_brute
+    int occupied[2];      // occupied cells of the 32^3 and the 16^3 coarse grid (what the rule saw)
+};
+struct SasKnn {
+    const float *points;          // [n,3] caller's order
+    long long n;
+    int k, forced_g;              // forced_g > 0: SAS_KNN_GRID
+    float *dist2;                 // [n,k] out
+    int *index;                   // [n,k] out or nullptr
+    // scratch
+    const SasOrderRecord *bounds; // of sas_launch_order_bounds
+    unsigned *occ;                // [32 * 32] words: bit x of word z * 32 + y is coarse cell (x, y, z)
+    SasKnnGrid *grid;
+    unsigned *table;              // [table_len] counts, then starts, then ends per cell; table[-1] == 0; cell n_cells holds the non-finite points
+    unsigned *blk;                // [table_len / SAS_KNN_SCAN_BLOCK] block sums, then their exclusive offsets
+    float4 *pts;                  // [n] (x, y, z, bits(index)) in cell order
+    int *left;                    // [n] positions in pts of the leftover points, in no particular order
+    unsigned long long *keys;     // [slices][n][K] slice results of k_knn_brute
+    long long cells_cap;          // cells the grid may have: table_len >= cells_cap + 1
+    long long table_len;          // a multiple of SAS_KNN_SCAN_BLOCK
+    long long slice_points;       // candidates per slice, a multiple of SAS_KNN_CHUNK
+    int slices;
+};
+void sas_launch_knn(hipStream_t st, const SasKnn &q);

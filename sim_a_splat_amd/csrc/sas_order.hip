@@ -264,12 +264,20 @@ __global__ __launch_bounds__(kThreads) void k_order_scatter(const SasOrder q, co
 
 SAS_BOUNDS_ACCESSOR(sas_debug_bounds_order)
 
-void sas_launch_order(hipStream_t st, const SasOrder &q)
+// the bounds alone: q.rec <- lo, hi, inv and the first bad group id (sas_knn.hip lays its grid over them)
+void sas_launch_order_bounds(hipStream_t st, const SasOrder &q)
 {
     if (q.n <= 0) return;
     const dim3 tiles((unsigned)q.n_tiles), wg(kThreads);
     hipLaunchKernelGGL(k_order_bounds, tiles, wg, 0, st, q);
     hipLaunchKernelGGL(k_order_bounds_tail, dim3(1), wg, 0, st, q);
+}
+
+void sas_launch_order(hipStream_t st, const SasOrder &q)
+{
+    if (q.n <= 0) return;
+    const dim3 tiles((unsigned)q.n_tiles), wg(kThreads);
+    sas_launch_order_bounds(st, q);
     hipLaunchKernelGGL(k_order_keys, dim3((unsigned)((q.n + kThreads - 1) / kThreads)), wg, 0, st, q);
     const int passes = q.gid ? 5 : 4;   // bytes 0 .. 3 hold the 30 Hilbert bits, byte 4 the group
     for (int p = 0; p < passes; ++p) {

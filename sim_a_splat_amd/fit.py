@@ -12,7 +12,7 @@ density control").  That path keeps no statistics; ``mcmc_refine`` renews the st
 The loss: ``loss=None`` descends a mean absolute difference (or the caller's ``loss_and_grad``) with the chain to the raw accumulators in
 torch; ``loss="dssim"`` descends the 3DGS photometric loss ``(1 - lambda) L1 + lambda (1 - SSIM)`` through ``Rasterizer.photometric_loss``,
 whose kernels deliver the gradients ``render_backward`` takes ("Photometric loss").  ``image_metrics`` reports L1, SSIM and
-PSNR of the scene as it stands.
+PSNR of the scene as it stands.  ``init_scene`` makes the first scene from a point cloud ("Scene from points").
 
 Out of scope, and why: multi-scale SSIM, LPIPS, depth and alpha loss terms (pass one through ``loss_and_grad``); screen-size splits and
 prunes and ``revised_opacity`` of gsplat's strategy; gradients for K and meshes (the limits of the backward pass).  The group poses are
@@ -331,3 +331,75 @@ def image_metrics(r, viewmats, Ks, W: int, H: int, images, masks=None, backgroun
                                        want_grad=False)["terms"])
     t = torch.stack(rows).cpu() if rows else torch.zeros((0, 4))
     return dict(l1=t[:, 1], ssim=t[:, 2], mse=t[:, 3], psnr=-10.0 * torch.log10(t[:, 3]))
+
+
+SH_C0 = 0.28209479177387814   # the DC basis function: colour = 0.5 + SH_C0 * coefficient
+
+
+def init_scene(r, points, colors=None, *, sh_degree: int = 3, init_opacity: float = 0.1, init_scale: float = 1.0, min_dist2: float = 1e-7,
+               group_id=None, n_groups: int = 0, knn: Optional[Callable] = None) -> Dict[str, torch.Tensor]:
+    """The first scene from a point cloud, the published initialisation (Kerbl et al. 2023; gsplat's trainer), ending in ``r.upload`` of the
+    activated arrays, which are returned (float32 tensors on the device the distances live on):
+
+    - ``means`` = ``points [N,3]``;
+    - ``scales [N,3]`` = ``init_scale * sqrt(max(m, min_dist2))`` on all three axes, ``m = ((d0 + d1) + d2) / 3`` in float32 the mean squared
+      distance to the three nearest other points (gsplat's rule with 3DGS's clamp), from ``r.knn_points(points, 3)`` (a HIP kernel;
+      DESIGN.md 3, "Scene from points");
+    - ``opacities`` = ``init_opacity``; ``quats`` = the identity ``(1, 0, 0, 0)``;
+    - ``colors [N,(sh_degree+1)^2,3]``: the DC row ``(rgb - 0.5) / SH_C0``, the other rows zero.  ``colors [N,3]`` is float in 0..1 or uint8
+      (divided by 255 in float32); ``None`` is grey 0.5.
+
+    ``group_id`` / ``n_groups`` go to ``upload`` as they are.  ``knn``: a callable ``(points, k) -> dist2 [N,k]`` used in ``r.knn_points``' place
+    (the CPU tests pass the numpy restatement).  ``ValueError`` for fewer than 4 points, a non-finite point, ``colors`` of another length
+    or outside 0..1, ``sh_degree < 0``.  Not provided: readers for COLMAP or PLY clouds, random initial rotations."""
+    who = "init_scene"
+    if int(sh_degree) < 0:
+        raise ValueError(f"{who}: sh_degree {sh_degree} must be >= 0")
+    if isinstance(points, torch.Tensor):
+        p = points.detach().to(torch.float32)
+    else:
+        p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float32)))
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError(f"{who}: points must be [N,3], got {list(p.shape)}")
+    n = int(p.shape[0])
+    if n < 4:
+        raise ValueError(f"{who}: {n} points, at least 4 are needed (three neighbours each)")
+    if knn is None:
+        p = p.to(r.device).contiguous()
+        if not bool(torch.isfinite(p).all()):
+            raise ValueError(f"{who}: points hold a non-finite coordinate")
+        d = r.knn_points(p, 3, indices=False)["dist2"]
+    else:
+        if not bool(torch.isfinite(p).all()):
+            raise ValueError(f"{who}: points hold a non-finite coordinate")
+        d = knn(p.cpu().numpy(), 3)
+        d = d.detach() if isinstance(d, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(d, dtype=np.float32)))
+        d = d.to(device=p.device, dtype=torch.float32)
+    if tuple(d.shape) != (n, 3):
+        raise ValueError(f"{who}: knn returned {list(d.shape)}, expected [{n}, 3]")
+    dev = p.device
+    # a divisor as a one-element tensor: torch turns a division by a Python number into a product with its reciprocal, which is not the
+    # correctly rounded quotient the formulas (and tests/tools/knn_ref.py) name
+    const = lambda v: torch.full((1,), v, dtype=torch.float32, device=dev)
+    if colors is None:
+        rgb = torch.full((n, 3), 0.5, dtype=torch.float32, device=dev)
+    else:
+        c = colors.detach() if isinstance(colors, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(colors)))
+        if tuple(c.shape) != (n, 3):
+            raise ValueError(f"{who}: colors must be [{n}, 3], got {list(c.shape)}")
+        c = c.to(dev)
+        rgb = c.to(torch.float32) / const(255.0) if c.dtype == torch.uint8 else c.to(torch.float32)
+        if not bool(((rgb >= 0.0) & (rgb <= 1.0)).all()):
+            raise ValueError(f"{who}: colors outside 0..1 (float) / not uint8")
+    m = ((d[:, 0] + d[:, 1]) + d[:, 2]) / const(3.0)
+    s = float(init_scale) * torch.sqrt(torch.clamp(m, min=float(min_dist2)))
+    kk = (int(sh_degree) + 1) ** 2
+    sh = torch.zeros((n, kk, 3), dtype=torch.float32, device=dev)
+    sh[:, 0, :] = (rgb - 0.5) / const(SH_C0)
+    quats = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+    quats[:, 0] = 1.0
+    scene = dict(means=p.contiguous(), opacities=torch.full((n,), float(init_opacity), dtype=torch.float32, device=dev), colors=sh,
+                 quats=quats, scales=s.to(torch.float32)[:, None].expand(n, 3).contiguous())
+    r.upload(scene["means"], scene["opacities"], scene["colors"], quats=scene["quats"], scales=scene["scales"], sh_degree=int(sh_degree),
+             group_id=group_id, n_groups=n_groups)
+    return scene

@@ -1333,6 +1333,36 @@ class Rasterizer:
         return perm   # (m and g were made on this stream or are the caller's: the allocator hands their memory on behind the kernels)
 
     @_locked
+    def knn_points(self, points: ArrayLike, k: int = 3, indices: bool = True) -> Dict[str, torch.Tensor]:
+        """For every point of ``points [N,3]`` its ``k`` (1..8) nearest OTHER points of the same cloud, exactly (sas_knn_points; DESIGN.md
+        3, "Scene from points"): ``dist2`` float32 ``[N,k]`` ascending and, with ``indices``, ``index`` int32 ``[N,k]``, device tensors.
+        ``d2 = (dx*dx + dy*dy) + dz*dz`` in float32; equal distances go to the lower index; the point itself is left out by index, so a
+        duplicate is a neighbour at 0; a point with a non-finite coordinate neither is a neighbour nor has one; a missing neighbour reads
+        ``+inf`` / ``-1``.  Device tensors are read where they are.  Needs no scene.  Only enqueues, on the current stream (a call at a
+        larger N than any before first grows the context's scratch, which waits for the device)."""
+        p = (points.detach() if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float32))))
+        p = p.to(device=self.device, dtype=torch.float32).contiguous()
+        if p.dim() != 2 or p.shape[1] != 3:
+            raise ValueError(f"points must be [N,3], got {list(p.shape)}")
+        n, k = int(p.shape[0]), int(k)
+        res = {"dist2": torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device)}
+        if indices:
+            res["index"] = torch.empty((n, max(k, 0)), dtype=torch.int32, device=self.device)
+        rc = self._L.sas_knn_points(self._ctx, n, _addr(p), k, _addr(res["dist2"]), _addr(res.get("index")), self._stream())
+        if rc != 0:
+            self._check(rc, "sas_knn_points")
+        return res   # (p was made on this stream or is the caller's: the allocator hands its memory on behind the kernels)
+
+    @_locked
+    def knn_stats(self) -> Dict[str, object]:
+        """What the last ``knn_points`` decided on the device (sas_knn_last_counts; blocking): ``leftover`` points its grid search handed
+        to the brute-force kernel, the ``grid``'s cells per axis, ``brute`` (no grid: the whole cloud went through the brute-force
+        kernel) and the ``occupied`` cells of the 32^3 and 16^3 occupancy grids the grid was chosen from."""
+        out = np.zeros(7, np.int64)
+        self._check(self._L.sas_knn_last_counts(self._ctx, out.ctypes.data, 7), "sas_knn_last_counts")
+        return {"leftover": int(out[0]), "grid": tuple(int(v) for v in out[1:4]), "brute": bool(out[4]), "occupied": (int(out[5]), int(out[6]))}
+
+    @_locked
     def read_order(self) -> torch.Tensor:
         """The resident scene's storage order (sas_scene_order): int32 ``[N]`` on the device, slot -> the caller's index, as
         ``storage_order(read_scene()["means"], group_id)`` gives it straight after an ``upload``, a ``densify`` or an ``mcmc_refine``.
