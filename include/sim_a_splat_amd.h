@@ -814,6 +814,45 @@ int sas_scene_order(sas_ctx *ctx, int32_t *perm_out);
 int sas_knn_points(sas_ctx *ctx, int64_t n, const float *points, int k, float *dist2_out, int32_t *index_out_or_null, void *stream);
 int sas_knn_last_counts(sas_ctx *ctx, int64_t *out, int n);
 
+/*
+ * Deformable splats ("Deformation"): an embedded deformation graph over the resident scene.  Every Gaussian is bound to up
+ * to 8 of M control nodes with weights; the nodes move rigidly, the means follow by linear blend skinning and the orientations by a
+ * blended quaternion.  Node transforms are expected to be RIGID: stretch and shear are not represented.
+ *
+ * sas_knn_cross -- for every point of points [n,3] its k (1..8) nearest NODES of nodes [m,3], 1 <= m <= 65536, exactly: sas_knn_points'
+ * contract (d2 = (dx dx + dy dy) + dz dz in binary32 with d = node - point, keys bits(d2) << 32 | node index, the k smallest ascending, a
+ * NaN or +inf d2 never counts, missing neighbours read +inf / -1) with two differences: nothing is left out by index, and a node with
+ * d2 > max_distance^2 (binary32, the square formed once on the host; INFINITY: no cut) never counts.  m < k is allowed.  points, nodes,
+ * dist2_out [n,k] float32 and index_out_or_null [n,k] int32 are DEVICE arrays.  Needs no scene and no scratch; it only ENQUEUES, on `stream`.
+ * SAS_ERR_INVALID for k outside 1..8, n < 0 or > 2^31 - 1, m outside 1..65536, a negative or NaN max_distance, a missing array with n > 0.
+ *
+ * sas_scene_skin -- bind a skin to the resident scene: indices [N,k] int32 and weights [N,k] float32, 1 <= k <= 8, DEVICE arrays in the
+ * caller's order.  The first bind snapshots the means, orientations and scales (or covariances) as the REST pose; a bind over a skin
+ * replaces the entries and keeps the rest pose.  k == 0 (indices and weights ignored) clears the skin: the rest pose returns bit for
+ * bit.  While a skin is bound sas_scene_adam_step, sas_scene_densify, sas_scene_mcmc_refine, sas_scene_mcmc_noise and
+ * sas_scene_reset_opacity are SAS_ERR_INVALID ("scene is skinned") and change nothing; everything that reads the scene sees the deformed
+ * Gaussians; sas_scene_upload drops the skin.  Enqueued on `stream`; frames in flight are completed first.
+ * sas_scene_skin_read -- the entries back in the caller's order, [N,k] each with the k of the bind, HOST or DEVICE.  Blocking.
+ * SAS_ERR_INVALID without a skin.
+ *
+ * sas_scene_deform -- node_Rt [m,3,4] float32 DEVICE, rows [R | t] that map REST to CURRENT in the frame the scene was uploaded in (in
+ * front of the group poses), 1 <= m <= 65536.  An entry is LIVE when 0 <= index < m and weight > 0; every other entry is ignored.  Per
+ * Gaussian with live entries j, in entry order and binary32, nothing fused:
+ *   mean'  = mean + (sum_j w_j ((R_j mean + t_j) - mean)) / sum_j w_j
+ *   q_b    = normalize(sum_j s_j w_j q_j), q_j the unit quaternion of R_j, s_j = -1 where dot(q_j, q_first) < 0
+ *   quat'  = q_b (x) quat (scales untouched), or Sigma' = R(q_b) Sigma R(q_b)^T for a scene uploaded as covariances
+ * A Gaussian without a live entry keeps the rest pose's bits.  Opacities, colours, groups, the storage order and N are never written.
+ * The state is always rest -> current, never accumulated.  Two launches on `stream`, nothing is waited for but frames in flight; the last
+ * frame is invalidated as sas_scene_adam_step does.  SAS_ERR_INVALID without a skin, for m out of range or node_Rt NULL.
+ * The environment variable SAS_SKIN_LDS=bytes (read when the context is created; 0..16384, the default) is the size up to which the node
+ * records (64 B each) are staged in LDS; no result depends on it.
+ */
+int sas_knn_cross(sas_ctx *ctx, int64_t n, const float *points, int64_t m, const float *nodes, int k, float max_distance,
+                  float *dist2_out, int32_t *index_out_or_null, void *stream);
+int sas_scene_skin(sas_ctx *ctx, int k, const int32_t *indices, const float *weights, void *stream);
+int sas_scene_skin_read(sas_ctx *ctx, int32_t *indices_out, float *weights_out);
+int sas_scene_deform(sas_ctx *ctx, int m, const float *node_Rt, void *stream);
+
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical
  * field of view; the view matrices and intrinsics are those of sas_camera_matrices. */

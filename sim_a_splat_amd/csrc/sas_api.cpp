@@ -132,6 +132,18 @@ struct Adam {
     }
 };
 
+// The skin of the resident scene (sas_scene_skin; DESIGN.md 3, "Deformation"), slot order: the rest snapshot of g0 / g1 / g2 taken at the
+// first bind, the entries' planes, and the node records of the last sas_scene_deform.  k == 0: no skin is bound.  Clearing a skin gives no
+// memory back (hipFree would wait for the whole device in front of frames in flight): the buffers serve the next bind, and go where the
+// optimiser state goes, at the next upload or with the context.
+struct Skin {
+    DevBuf rest0, rest1, rest2, idx, w, nodes;
+    int k = 0;
+    bool bound() const { return k > 0; }
+    int kp() const { return k <= 4 ? 4 : SAS_SKIN_MAX_K; }
+    int drop(sas_ctx *c);
+};
+
 }  // namespace
 
 // Per-frame scratch.  Every slot owns one, so several frames can be on the GPU at the same time.
@@ -260,6 +272,9 @@ struct Settings {
     // sas_knn_points chooses its grid on the device (sas_knn.hip: the grid rule); SAS_KNN_GRID=g forces g cells per axis, 1: no grid, every
     // point through the brute-force kernel.  No result depends on it: the knob is there so that tests and tools/knn_probe.py compare the paths
     int knn_grid = 0;
+    // sas_scene_deform stages the node records in LDS while m * 64 B fits this budget (SAS_SKIN_LDS=bytes, 0: never; SAS_SKIN_LDS_BYTES at
+    // most, which is what the kernel reserves).  No result depends on it: the knob is there so that tests and tools/deform_probe.py compare the paths
+    int skin_lds = SAS_SKIN_LDS_BYTES;
     static Settings from_env()
     {
         Settings s;
@@ -277,6 +292,7 @@ struct Settings {
         if (num("SAS_RING_RESTART", v)) s.ring_restart = v != 0;
         if (num("SAS_ORDER", v)) s.order_on_device = v != 0;
         if (num("SAS_KNN_GRID", v) && v >= 1 && v <= SAS_KNN_MAX_AXIS) s.knn_grid = (int)v;
+        if (num("SAS_SKIN_LDS", v) && v >= 0) s.skin_lds = (int)std::min<long long>(v, SAS_SKIN_LDS_BYTES);
         return s;
     }
 };
@@ -305,6 +321,8 @@ struct sas_ctx : Settings {
     DevBuf fuse_par;   // per-view rows and keep table of sas_fuse_depth (SasFuse)
     Adam adam;            // optimiser state of the resident scene
     Event adam_done;      // recorded behind a step on the caller's stream: the slots' streams wait for it
+    Skin skin;            // skin of the resident scene
+    Event skin_done;      // recorded behind sas_scene_skin / sas_scene_deform on the caller's stream, as adam_done
     DevBuf grad_screen;   // sas_render_backward: [10 n] screen-space sums + [ceil(n / 256)][12] view-matrix rows (SasGradProj)
     int grad_frame = 0;   // the last frame is a backward frame: 1 of sas_render_backward_screen, 2 of sas_render_backward (grad_screen holds its sums); 0: none
     Event density_done;   // recorded behind sas_density_accumulate / sas_scene_reset_opacity / sas_scene_mcmc_noise on the caller's stream: the slots' streams wait for it
@@ -438,6 +456,21 @@ int Adam::alloc(sas_ctx *c, int row, int64_t n_pad, int colour_planes, hipStream
     if (const int rc = ensure(c, buf[row], bytes)) return rc;
     if (zero) HIP_TRY(c, hipMemsetAsync(buf[row].p, 0, bytes, st));
     return SAS_OK;
+}
+
+// The skin goes with its scene (sas_scene_upload): hipFree waits for the deformation that may still be using it.
+int Skin::drop(sas_ctx *c)
+{
+    for (DevBuf *b : {&rest0, &rest1, &rest2, &idx, &w, &nodes})
+        if (const int rc = b->release(c)) return rc;
+    k = 0;
+    return SAS_OK;
+}
+
+// The prologue of the calls that change the scene's raw values or its count: neither has a meaning over deformed planes.
+int need_unskinned(sas_ctx *c, const char *who)
+{
+    return c->skin.bound() ? fail(c, SAS_ERR_INVALID, "%s: scene is skinned: clear_skin() first", who) : SAS_OK;
 }
 
 // Room for `count` Gaussians: whole waves of 64 slots, and 64 slots for an empty scene.
@@ -1306,6 +1339,7 @@ int sas_scene_upload(sas_ctx *c, int64_t n, const float *means, const float *qua
     if (const int rc = complete_all(c)) return rc;
     forget(c, HAVE_SCENE);
     if (const int rc = c->adam.drop(c)) return rc;   // (hipFree waits for the step that may still be using the state)
+    if (const int rc = c->skin.drop(c)) return rc;   // (the scene is new)
 
     const int deg = sh_degree < 0 ? -1 : sh_degree;
     const int coeff_floats = sas_coeff_floats(deg), planes = sas_colour_planes(deg);
@@ -2538,6 +2572,7 @@ int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_m
     if (!c) return SAS_ERR_INVALID;
     if (!cfg) return fail(c, SAS_ERR_INVALID, "%s: cfg is NULL", who);
     if (const int rc = need_scene(c, who)) return rc;
+    if (const int rc = need_unskinned(c, who)) return rc;
     if (!d_means && !d_opacities && !d_sh && !d_quats && !d_scales) return fail(c, SAS_ERR_INVALID, "%s: every gradient is NULL", who);
     if (cfg->step < 1) return fail(c, SAS_ERR_INVALID, "%s: step %d < 1 (the count is 1-based)", who, cfg->step);
     for (const float lr : {cfg->lr_means, cfg->lr_opacities, cfg->lr_sh_dc, cfg->lr_sh_rest, cfg->lr_quats, cfg->lr_scales})
@@ -2759,6 +2794,7 @@ int sas_scene_densify(sas_ctx *c, const sas_densify_config *cfg, const float *gr
 {
     const char *who = "sas_scene_densify";
     if (const int rc = need_scene(c, who)) return rc;
+    if (const int rc = need_unskinned(c, who)) return rc;
     if (!cfg) return fail(c, SAS_ERR_INVALID, "%s: cfg is NULL", who);
     if (!grad_sum || !count || !counts_out) return fail(c, SAS_ERR_INVALID, "%s: grad_sum, count and counts_out are required", who);
     if (cfg->flags & ~(SAS_DENSIFY_GROW | SAS_DENSIFY_PRUNE_OPACITY | SAS_DENSIFY_PRUNE_SCALE))
@@ -2836,6 +2872,7 @@ int sas_scene_mcmc_noise(sas_ctx *c, float scale, int step, unsigned seed, void 
 {
     const char *who = "sas_scene_mcmc_noise";
     if (const int rc = need_scene(c, who)) return rc;
+    if (const int rc = need_unskinned(c, who)) return rc;
     if (const int rc = check_rate(c, who, "scale", scale)) return rc;
     if (step < 1) return fail(c, SAS_ERR_INVALID, "%s: step %d < 1 (the count is 1-based)", who, step);
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2861,6 +2898,7 @@ int sas_scene_mcmc_refine(sas_ctx *c, const sas_mcmc_config *cfg, int32_t *paren
 {
     const char *who = "sas_scene_mcmc_refine";
     if (const int rc = need_scene(c, who)) return rc;
+    if (const int rc = need_unskinned(c, who)) return rc;
     if (!cfg || !counts_out) return fail(c, SAS_ERR_INVALID, "%s: cfg and counts_out are required", who);
     if (!(cfg->min_opacity >= 0.0f && cfg->min_opacity < 1.0f)) return fail(c, SAS_ERR_INVALID, "%s: min_opacity %g outside [0, 1)", who, (double)cfg->min_opacity);
     if (cfg->cap_max < 1 || cfg->cap_max > 0x7fffffffll - 256) return fail(c, SAS_ERR_INVALID, "%s: cap_max %lld out of range", who, (long long)cfg->cap_max);
@@ -2945,6 +2983,7 @@ int sas_scene_reset_opacity(sas_ctx *c, float max_opacity, void *stream)
 {
     const char *who = "sas_scene_reset_opacity";
     if (const int rc = need_scene(c, who)) return rc;
+    if (const int rc = need_unskinned(c, who)) return rc;
     if (!(max_opacity > 0.0f && max_opacity < 1.0f)) return fail(c, SAS_ERR_INVALID, "%s: max_opacity %g outside (0, 1)", who, (double)max_opacity);
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = complete_all(c)) return rc;   // (no frame reads the planes while they change)
@@ -3023,6 +3062,121 @@ int sas_knn_points(sas_ctx *c, int64_t n, const float *points, int k, float *dis
     sas_launch_knn(st, q);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->knn_done, st));
+    return SAS_OK;
+}
+
+// The k nearest nodes of a second cloud for every point (k_knn_cross), scene-free, device arrays: one launch on the caller's stream, no
+// scratch, nothing is waited for.
+int sas_knn_cross(sas_ctx *c, int64_t n, const float *points, int64_t m, const float *nodes, int k, float max_distance, float *dist2_out,
+                  int32_t *index_out_or_null, void *stream)
+{
+    const char *who = "sas_knn_cross";
+    if (!c) return SAS_ERR_INVALID;
+    if (k < 1 || k > SAS_KNN_MAX_K) return fail(c, SAS_ERR_INVALID, "%s: k=%d out of [1,%d]", who, k, SAS_KNN_MAX_K);
+    if (n < 0 || n > 0x7fffffffll) return fail(c, SAS_ERR_INVALID, "%s: n=%lld out of range", who, (long long)n);
+    if (m < 1 || m > SAS_KNN_CROSS_MAX_NODES) return fail(c, SAS_ERR_INVALID, "%s: m=%lld out of [1,%d]", who, (long long)m, SAS_KNN_CROSS_MAX_NODES);
+    if (const int rc = check_max_distance(c, max_distance)) return rc;
+    if (n == 0) return SAS_OK;
+    if (!points || !nodes || !dist2_out) return fail(c, SAS_ERR_INVALID, "%s: points, nodes and dist2_out are required", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const SasKnnCross q{points, nodes, n, (int)m, k, max_distance * max_distance, dist2_out, index_out_or_null};
+    sas_launch_knn_cross((hipStream_t)stream, q);
+    HIP_TRY(c, hipGetLastError());
+    return SAS_OK;
+}
+
+// Bind, replace or clear the skin (k_skin_bind).  Host work: validation, the planes' allocations, the rest snapshot as device copies on the
+// caller's stream, one launch, one event.
+int sas_scene_skin(sas_ctx *c, int k, const int32_t *indices, const float *weights, void *stream)
+{
+    const char *who = "sas_scene_skin";
+    if (const int rc = need_scene(c, who)) return rc;
+    if (k < 0 || k > SAS_SKIN_MAX_K) return fail(c, SAS_ERR_INVALID, "%s: k=%d out of [0,%d]", who, k, SAS_SKIN_MAX_K);
+    const SasScene &sc = c->scene;
+    if (k > 0 && sc.n > 0 && (!indices || !weights)) return fail(c, SAS_ERR_INVALID, "%s: indices and weights are required", who);
+    Skin &sk = c->skin;
+    if (k == 0 && !sk.bound()) return SAS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;   // (no frame reads the planes while they change)
+    hipStream_t st = (hipStream_t)stream;
+    Planes &pl = c->planes;
+    const size_t np = (size_t)(pl.n_pad > 0 ? pl.n_pad : 64), plane = sizeof(float4) * np;
+    DevBuf *rest[3] = {&sk.rest0, &sk.rest1, &sk.rest2}, *live[3] = {&pl.g0, &pl.g1, &pl.g2};
+    if (k == 0) {   // the rest planes back, bit for bit
+        for (int p = 0; p < 3; ++p) HIP_TRY(c, hipMemcpyAsync(live[p]->p, rest[p]->p, plane, hipMemcpyDeviceToDevice, st));
+        sk.k = 0;
+        if (const int rc = slots_wait_for(c, c->skin_done, st)) return rc;
+        scene_changed(c, Changed::Values);
+        return SAS_OK;
+    }
+    const int kp = k <= 4 ? 4 : SAS_SKIN_MAX_K;
+    if (const int rc = ensure(c, {{sk.idx, plane * (kp / 4)}, {sk.w, plane * (kp / 4)}})) return rc;
+    if (!sk.bound()) {   // the first bind: what the planes hold now is the rest pose
+        if (const int rc = ensure(c, {{sk.rest0, plane}, {sk.rest1, plane}, {sk.rest2, plane}})) return rc;
+        for (int p = 0; p < 3; ++p) HIP_TRY(c, hipMemcpyAsync(rest[p]->p, live[p]->p, plane, hipMemcpyDeviceToDevice, st));
+    }
+    const SasSkinBind q{sc.perm, indices, weights, sc.n, pl.n_pad, k, kp, (int4 *)sk.idx.p, (float4 *)sk.w.p};
+    sas_launch_skin_bind(st, q);
+    HIP_TRY(c, hipGetLastError());
+    sk.k = k;
+    return slots_wait_for(c, c->skin_done, st);   // (the planes' values stay: the last frame does too)
+}
+
+// The binding in the caller's order (k_skin_read), on the context's own stream; host or device destinations.  Blocking.
+int sas_scene_skin_read(sas_ctx *c, int32_t *indices_out, float *weights_out)
+{
+    const char *who = "sas_scene_skin_read";
+    if (const int rc = need_scene(c, who)) return rc;
+    const Skin &sk = c->skin;
+    if (!sk.bound()) return fail(c, SAS_ERR_INVALID, "%s: no skin is bound", who);
+    if (!indices_out || !weights_out) return fail(c, SAS_ERR_INVALID, "%s: indices_out and weights_out are required", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;
+    const SasScene &sc = c->scene;
+    const size_t count = (size_t)sc.n * (size_t)sk.k;
+    if (count == 0) return SAS_OK;
+    DevBuf s_idx, s_w;
+    if (const int rc = ensure(c, {{s_idx, sizeof(int) * count}, {s_w, sizeof(float) * count}})) return rc;
+    HIP_TRY(c, hipDeviceSynchronize());   // (the bind ran on the caller's stream)
+    const SasSkinRead q{sc.perm, (const int4 *)sk.idx.p, (const float4 *)sk.w.p, sc.n, sc.n_pad, sk.k, (int *)s_idx.p, (float *)s_w.p};
+    hipStream_t st = c->slots[0].fs;
+    sas_launch_skin_read(st, q);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipMemcpy(indices_out, s_idx.p, sizeof(int) * count, hipMemcpyDefault));
+    HIP_TRY(c, hipMemcpy(weights_out, s_w.p, sizeof(float) * count, hipMemcpyDefault));
+    return SAS_OK;
+}
+
+// Move the skinned scene to the nodes' transforms (k_skin_nodes, k_deform): always rest -> current.  Host work: validation, the node
+// records' buffer (grown by the first call at a larger m), two launches, one event.
+int sas_scene_deform(sas_ctx *c, int m, const float *node_Rt, void *stream)
+{
+    const char *who = "sas_scene_deform";
+    if (const int rc = need_scene(c, who)) return rc;
+    Skin &sk = c->skin;
+    if (!sk.bound()) return fail(c, SAS_ERR_INVALID, "%s: no skin is bound: sas_scene_skin first", who);
+    if (m < 1 || m > SAS_KNN_CROSS_MAX_NODES) return fail(c, SAS_ERR_INVALID, "%s: m=%d out of [1,%d]", who, m, SAS_KNN_CROSS_MAX_NODES);
+    if (!node_Rt) return fail(c, SAS_ERR_INVALID, "%s: node_Rt is NULL", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = complete_all(c)) return rc;   // (no frame reads the planes while they change)
+    const SasScene &sc = c->scene;
+    if (sc.n <= 0) return SAS_OK;
+    if (const int rc = ensure(c, sk.nodes, sizeof(SasSkinNode) * (size_t)m)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    SasDeform q{};
+    q.node_Rt = node_Rt;
+    q.nodes = (SasSkinNode *)sk.nodes.p;
+    q.r0 = (const float4 *)sk.rest0.p; q.r1 = (const float4 *)sk.rest1.p; q.r2 = (const float4 *)sk.rest2.p;
+    q.g0 = (float4 *)c->planes.g0.p; q.g1 = (float4 *)c->planes.g1.p; q.g2 = (float4 *)c->planes.g2.p;
+    q.idx = (const int4 *)sk.idx.p; q.w = (const float4 *)sk.w.p;
+    q.n = sc.n; q.n_pad = sc.n_pad;
+    q.m = m; q.kp = sk.kp(); q.cov_mode = sc.cov_mode;
+    q.lds = sizeof(SasSkinNode) * (size_t)m <= (size_t)c->skin_lds;
+    sas_launch_deform(st, q);
+    HIP_TRY(c, hipGetLastError());
+    if (const int rc = slots_wait_for(c, c->skin_done, st)) return rc;
+    scene_changed(c, Changed::Values);   // the last frame showed the scene before the deformation
     return SAS_OK;
 }
 
@@ -3165,7 +3319,7 @@ int sas_frames_completed(sas_ctx *c, int64_t *submitted, int64_t *completed)
 
 #ifdef SAS_DEBUG_BOUNDS
 // every kernel file's counter (SAS_BOUNDS_ACCESSOR in sas_device.h): one line per file, in the order their reports are looked at
-#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density) X(mcmc) X(order) X(knn)
+#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density) X(mcmc) X(order) X(knn) X(skin)
 #define SAS_BOUNDS_DECLARE(name) extern "C" int sas_debug_bounds_##name(unsigned long long *out, int reset);
 #define SAS_BOUNDS_ENTRY(name) sas_debug_bounds_##name,
 SAS_BOUNDS_FILES(SAS_BOUNDS_DECLARE)

@@ -1,4 +1,4 @@
-// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip, sas_mcmc.hip, sas_order.hip and sas_knn.hip: arithmetic, the bounds-checked build, DPP reductions and row sums, contract T6 per pair, and the start of a workgroup on one tile of a frame (pixel layout, pixel state, the tile's list, the truncated-list rule).
+// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip, sas_mcmc.hip, sas_order.hip, sas_knn.hip and sas_skin.hip: arithmetic, the bounds-checked build, DPP reductions and row sums, contract T6 per pair, and the start of a workgroup on one tile of a frame (pixel layout, pixel state, the tile's list, the truncated-list rule).
 // Everything here follows the arithmetic contract of DESIGN.md: IEEE binary32 operations, fused
 // only where fma_() is written (translation units are built with -ffp-contract=off).
 #pragma once
@@ -80,6 +80,23 @@ DEV float hashed_normal(unsigned base, unsigned c)
     const float u1 = (float)((h1 >> 8) + 1u) * 5.9604644775390625e-8f;   // (0, 1], a multiple of 2^-24
     const float u2 = (float)(h2 >> 8) * 5.9604644775390625e-8f;          // [0, 1)
     return sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
+}
+
+// ---- nearest-neighbour keys (sas_knn.hip, sas_skin.hip; DESIGN.md 3, "Scene from points") -----------------------------------------------
+// A candidate j at squared distance d2 is the key bits(d2) << 32 | j: smaller is nearer, ties go to the lower index.
+constexpr unsigned long long kKnnNone = (0x7f800000ull << 32) | 0xffffffffull;   // d2 = +inf: above the key of every neighbour
+DEV bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+DEV bool finite3(float x, float y, float z) { return finite_f32(x) && finite_f32(y) && finite_f32(z); }
+// the K smallest keys, ascending; x is no key of the set already (every candidate is met once)
+template <int K>
+DEV void keep_key(unsigned long long (&best)[K], unsigned long long x)
+{
+#pragma unroll
+    for (int j = K - 1; j > 0; --j) {
+        const unsigned long long below = best[j - 1];
+        best[j] = x < below ? below : (x < best[j] ? x : best[j]);
+    }
+    best[0] = x < best[0] ? x : best[0];
 }
 
 // ---- wave64 reductions and scan on the DPP network --------------------------------------------------------------------------------

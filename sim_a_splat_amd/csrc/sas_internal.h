@@ -1,4 +1,4 @@
-// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip, sas_mcmc.hip, sas_order.hip, sas_knn.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
+// Shared between sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip, sas_mcmc.hip, sas_order.hip, sas_knn.hip, sas_skin.hip (device code + launchers: through sas_device.h) and sas_api.cpp (context, C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -768,3 +768,59 @@ struct SasKnn {
     int slices;
 };
 void sas_launch_knn(hipStream_t st, const SasKnn &q);
+
+// Deformable splats (sas_knn_cross, sas_scene_skin, sas_scene_deform; DESIGN.md 3, "Deformation"; sas_skin.hip).  Every kernel takes its call
+// by value.
+#define SAS_KNN_CROSS_MAX_NODES 65536   // nodes of the second cloud at most: every lane walks them all
+#define SAS_SKIN_MAX_K 8                // entries per Gaussian at most; the planes hold 4 (k <= 4) or 8
+#define SAS_SKIN_LDS_BYTES 16384        // node records k_deform stages in LDS at most (256 records): the SAS_SKIN_LDS budget's default and ceiling
+// k nearest nodes of another cloud for every point: sas_knn.hip's contract, nothing left out by index, and a cut at md2
+struct SasKnnCross {
+    const float *points;   // [n,3]
+    const float *nodes;    // [m,3]
+    long long n;
+    int m, k;
+    float md2;             // max_distance^2 in float32 (INFINITY: no cut)
+    float *dist2;          // [n,k] out
+    int *index;            // [n,k] out or nullptr
+};
+void sas_launch_knn_cross(hipStream_t st, const SasKnnCross &q);
+// A node's record: the rows [R | t] as given and the unit quaternion wxyz of R
+struct SasSkinNode {
+    float Rt[12], q[4];
+};
+static_assert(sizeof(SasSkinNode) == 64, "a node's record is one 64-byte line");
+// The skin planes, slot order: plane p of idx / w holds entries 4p .. 4p + 3 of every slot, stride n_pad
+struct SasSkinBind {
+    const int *perm;        // [n] slot -> caller's index
+    const int *indices;     // [n,k] caller's order
+    const float *weights;   // [n,k]
+    long long n, n_pad;
+    int k, kp;              // kp = 4 or 8: entries k .. kp - 1 read (-1, 0)
+    int4 *idx;              // [kp / 4][n_pad]
+    float4 *w;              // [kp / 4][n_pad]
+};
+void sas_launch_skin_bind(hipStream_t st, const SasSkinBind &q);
+// ... and back in the caller's order (sas_scene_skin_read)
+struct SasSkinRead {
+    const int *perm;
+    const int4 *idx;
+    const float4 *w;
+    long long n, n_pad;
+    int k;
+    int *indices;           // [n,k] out
+    float *weights;         // [n,k] out
+};
+void sas_launch_skin_read(hipStream_t st, const SasSkinRead &q);
+struct SasDeform {
+    const float *node_Rt;        // [m,12] the caller's rows
+    SasSkinNode *nodes;          // [m] scratch: written by k_skin_nodes, read by k_deform
+    const float4 *r0, *r1, *r2;  // the rest planes
+    float4 *g0, *g1, *g2;        // the scene's planes, written
+    const int4 *idx;
+    const float4 *w;
+    long long n, n_pad;
+    int m, kp, cov_mode;
+    int lds;                     // 1: the node records pass through LDS (m * 64 B within the budget)
+};
+void sas_launch_deform(hipStream_t st, const SasDeform &q);

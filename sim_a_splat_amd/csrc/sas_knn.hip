@@ -46,6 +46,7 @@
 // clamped to [1, 1024]; while the cells outnumber the table budget (min(2^21, max(4096, 2 N))) h grows by 1.26.  None of this is exact
 // arithmetic and none of it has to be: no result depends on the grid.
 // Arithmetic of the results: IEEE binary32, nothing fused (-ffp-contract=off, no fma_).
+// The keys' helpers (kKnnNone, keep_key, finite3) live in sas_device.h: sas_skin.hip's k_knn_cross extends this contract to a second cloud.
 #include "sas_device.h"
 
 #pragma clang fp contract(off)
@@ -57,12 +58,8 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kBlock = SAS_KNN_SCAN_BLOCK;
 constexpr int kCoarse = SAS_KNN_COARSE;
 constexpr float kTargetPerCell = 3.0f;
-constexpr unsigned long long kNone = (0x7f800000ull << 32) | 0xffffffffull;   // d2 = +inf: above the key of every neighbour
 static_assert(kBlock == 8 * kThreads && SAS_KNN_CHUNK == kThreads && kCoarse == 32, "eight table entries per lane, one candidate per thread of a chunk, one word per coarse row");
 static_assert(SAS_KNN_RING_LIMIT <= 64 && SAS_KNN_MAX_AXIS <= 1024, "the stop bound's margin is derived for these");
-
-DEV bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-DEV bool finite3(float x, float y, float z) { return finite_f32(x) && finite_f32(y) && finite_f32(z); }
 
 // the cell of a finite coordinate on an axis of n cells (monotone in v: the stop rule rests on it)
 DEV int cell_axis(float v, float lo, float inv, int n)
@@ -254,18 +251,6 @@ __global__ __launch_bounds__(kThreads) void k_knn_scatter(const SasKnn q)
     if (SAS_IN(pos, q.n, 1407) && pos < q.n) q.pts[pos] = make_float4(x, y, z, __uint_as_float((unsigned)i));
 }
 
-// the K smallest keys, ascending; x is no key of the set already (every candidate is met once)
-template <int K>
-DEV void keep_key(unsigned long long (&best)[K], unsigned long long x)
-{
-#pragma unroll
-    for (int j = K - 1; j > 0; --j) {
-        const unsigned long long below = best[j - 1];
-        best[j] = x < below ? below : (x < best[j] ? x : best[j]);
-    }
-    best[0] = x < best[0] ? x : best[0];
-}
-
 // candidate c against the point (px, py, pz) of index i: the contract's d2 and key
 template <int K>
 DEV void meet(unsigned long long (&best)[K], const float4 c, float px, float py, float pz, unsigned i)
@@ -302,7 +287,7 @@ __global__ __launch_bounds__(kThreads) void k_knn_search(const SasKnn q)
     const long long n_finite = min((long long)q.table[G.n_cells - 1], q.n);   // the end of the last cell
     unsigned long long best[K];
 #pragma unroll
-    for (int j = 0; j < K; ++j) best[j] = kNone;
+    for (int j = 0; j < K; ++j) best[j] = kKnnNone;
     bool left = false;
     if (s < q.n) {
         const float4 p = q.pts[s];
@@ -362,7 +347,7 @@ __global__ __launch_bounds__(kThreads) void k_knn_brute(const SasKnn q)
     const unsigned i = __float_as_uint(p.w);
     unsigned long long best[K];
 #pragma unroll
-    for (int j = 0; j < K; ++j) best[j] = kNone;
+    for (int j = 0; j < K; ++j) best[j] = kKnnNone;
     const long long first = (long long)slice * q.slice_points, last = min(first + q.slice_points, q.n);
     for (long long base = first; base < last; base += SAS_KNN_CHUNK) {
         const int nload = (int)min((long long)SAS_KNN_CHUNK, last - base);
@@ -391,7 +376,7 @@ __global__ __launch_bounds__(kThreads) void k_knn_merge(const SasKnn q)
     const unsigned i = __float_as_uint(q.pts[s].w);
     unsigned long long best[K];
 #pragma unroll
-    for (int j = 0; j < K; ++j) best[j] = kNone;
+    for (int j = 0; j < K; ++j) best[j] = kKnnNone;
     for (int sl = 0; sl < q.slices; ++sl)
 #pragma unroll
         for (int j = 0; j < K; ++j) {

@@ -255,6 +255,7 @@ class Rasterizer:
         self.n = 0
         self.n_groups = 0
         self.sh_degree, self.covariance_form = 3, "quats"   # of the scene last uploaded (render_backward shapes its outputs by them)
+        self._group_ids = None
         self._forget("scene")
         self._keep = []  # outputs of in-flight async frames (the C ABI keeps up to four)
         self._argcache = {}  # id(argument) -> (argument, float32 array, address): _host_arg
@@ -281,6 +282,7 @@ class Rasterizer:
         s = set(stores)
         if "scene" in s:
             s |= {"features", "meshes"}
+            self._skin_k = 0       # entries per Gaussian of the bound skin (set_skin; 0: none): a new scene has none
         if s & {"features", "meshes"}:
             s.add("mesh_features")
         if "meshes" in s:          # vertex attributes sit beside the meshes (upload_mesh_vertex_attributes)
@@ -342,6 +344,7 @@ class Rasterizer:
         self.n = n
         self.n_groups = int(n_groups) if group_id is not None else 0
         self.sh_degree, self.covariance_form = int(sh_degree), "quats" if pq is not None else "cov6"
+        self._group_ids = g if group_id is not None else None   # (bind_skin(group=...) selects by them)
         self._forget("scene")
 
     @_locked
@@ -1195,7 +1198,14 @@ class Rasterizer:
         self._in_flight(True)
         self.n = int(counts[0])
         self._forget("features")
+        self._regroup(parents[:self.n])
         return dict(n=self.n, parents=parents[:self.n], cloned=int(counts[1]), split=int(counts[2]), pruned=int(counts[3]))
+
+    def _regroup(self, parents: torch.Tensor) -> None:
+        """The splat-group ids this object remembers (``bind_skin(group=...)`` selects by them) follow a new set of Gaussians: each takes
+        its parent's, as the library's do."""
+        if self._group_ids is not None:
+            self._group_ids = torch.as_tensor(self._group_ids).to(self.device).reshape(-1)[parents.long()]
 
     @_locked
     def reset_opacity(self, max_opacity: float = 0.01) -> None:
@@ -1248,6 +1258,7 @@ class Rasterizer:
         if int(counts[1]) or int(counts[2]):
             self._forget("features")
         self.n = int(counts[0])
+        self._regroup(parents[:self.n])
         return dict(n=self.n, relocated=int(counts[1]), added=int(counts[2]), parents=parents[:self.n])
 
     @_locked
@@ -1361,6 +1372,145 @@ class Rasterizer:
         out = np.zeros(7, np.int64)
         self._check(self._L.sas_knn_last_counts(self._ctx, out.ctypes.data, 7), "sas_knn_last_counts")
         return {"leftover": int(out[0]), "grid": tuple(int(v) for v in out[1:4]), "brute": bool(out[4]), "occupied": (int(out[5]), int(out[6]))}
+
+    # -- deformable splats ----------------------------------------------------------------------
+    def _cloud(self, a: ArrayLike, name: str) -> torch.Tensor:
+        """``a [N,3]`` as a contiguous float32 tensor on this context's device (a device tensor that is one already: itself)."""
+        t = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32)))
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{name} must be [N,3], got {list(t.shape)}")
+        return t
+
+    @_locked
+    def knn_nodes(self, points: ArrayLike, nodes: ArrayLike, k: int = 4, max_distance: float = math.inf,
+                  indices: bool = True) -> Dict[str, torch.Tensor]:
+        """For every point of ``points [N,3]`` its ``k`` (1..8) nearest of ``nodes [M,3]`` (1 <= M <= 65536), exactly (sas_knn_cross;
+        DESIGN.md 3, "Deformation"): ``dist2`` float32 ``[N,k]`` ascending and, with ``indices``, ``index`` int32 ``[N,k]``, device
+        tensors.  ``knn_points``' contract -- ``d2 = (dx*dx + dy*dy) + dz*dz`` in float32, equal distances to the lower index, a
+        non-finite ``d2`` never counts, a missing neighbour reads ``+inf`` / ``-1`` -- but nothing is left out by index, and a node
+        farther than ``max_distance`` never counts.  ``M < k`` leaves the last columns missing.  Device tensors are read where they
+        are.  Needs no scene.  Only enqueues, on the current stream."""
+        p, q = self._cloud(points, "points"), self._cloud(nodes, "nodes")
+        n, m, k = int(p.shape[0]), int(q.shape[0]), int(k)
+        res = {"dist2": torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device)}
+        if indices:
+            res["index"] = torch.empty((n, max(k, 0)), dtype=torch.int32, device=self.device)
+        rc = self._L.sas_knn_cross(self._ctx, n, _addr(p), m, _addr(q), k, float(max_distance), _addr(res["dist2"]), _addr(res.get("index")),
+                                   self._stream())
+        if rc != 0:
+            self._check(rc, "sas_knn_cross")
+        return res   # (p and q were made on this stream or are the caller's: the allocator hands their memory on behind the kernel)
+
+    @property
+    def has_skin(self) -> bool:
+        """A skin is bound to the resident scene (``set_skin`` / ``bind_skin``; ``clear_skin`` and ``upload`` end it)."""
+        return self._skin_k > 0
+
+    @_locked
+    def set_skin(self, indices: ArrayLike, weights: ArrayLike) -> None:
+        """Bind the resident scene to control nodes (sas_scene_skin; DESIGN.md 3, "Deformation"): ``indices [N,k]`` (integers; int32
+        device tensors are read where they are) and ``weights [N,k]`` (float32), ``1 <= k <= 8``, in ``upload``'s order.  An entry counts
+        in ``deform`` when ``0 <= index < m`` and ``weight > 0``; anything else is ignored.  The first bind keeps the scene as it stands
+        as the REST pose; a bind over a skin replaces the entries and keeps the rest pose.  While a skin is bound ``adam_step``,
+        ``densify``, ``mcmc_refine``, ``mcmc_noise`` and ``reset_opacity`` raise.  Only enqueues, on the current stream."""
+        def dev(a, dt, name):
+            t = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+            if t.dim() != 2 or t.shape[0] != self.n or not 1 <= t.shape[1] <= _capi.SAS_SKIN_MAX_K:
+                raise ValueError(f"{name} must be [{self.n}, k] with 1 <= k <= {_capi.SAS_SKIN_MAX_K}, got {list(t.shape)}")
+            if dt == torch.int32 and (t.dtype.is_floating_point or t.dtype == torch.bool):
+                raise ValueError(f"{name} must hold integers, got {t.dtype}")
+            return t.to(device=self.device, dtype=dt).contiguous()
+        i, w = dev(indices, torch.int32, "indices"), dev(weights, torch.float32, "weights")
+        if i.shape != w.shape:
+            raise ValueError(f"indices {list(i.shape)} and weights {list(w.shape)} differ in shape")
+        rc = self._L.sas_scene_skin(self._ctx, int(i.shape[1]), _addr(i), _addr(w), self._stream())
+        if rc != 0:
+            self._check(rc, "sas_scene_skin")
+        self._skin_k = int(i.shape[1])
+        self._in_flight(True)
+
+    @_locked
+    def read_skin(self) -> Dict[str, torch.Tensor]:
+        """The bound skin in ``upload``'s order (sas_scene_skin_read): ``indices`` int32 and ``weights`` float32, ``[N,k]`` device
+        tensors, the bits ``set_skin`` was given.  Blocking."""
+        if not self.has_skin:
+            raise SasError("read_skin: no skin is bound")
+        res = {"indices": torch.empty((self.n, self._skin_k), dtype=torch.int32, device=self.device),
+               "weights": torch.empty((self.n, self._skin_k), dtype=torch.float32, device=self.device)}
+        torch.cuda.synchronize(self.device)   # (the allocator may hand out memory that work in flight still uses)
+        if self.n:
+            self._check(self._L.sas_scene_skin_read(self._ctx, _addr(res["indices"]), _addr(res["weights"])), "sas_scene_skin_read")
+        return res
+
+    @_locked
+    def clear_skin(self) -> None:
+        """Unbind the skin: the rest pose returns bit for bit, and the calls a skin refuses work again.  Without a skin: nothing.  Only
+        enqueues, on the current stream."""
+        rc = self._L.sas_scene_skin(self._ctx, 0, None, None, self._stream())
+        if rc != 0:
+            self._check(rc, "sas_scene_skin")
+        self._skin_k = 0
+        self._in_flight(True)
+
+    @_locked
+    def deform(self, node_transforms: ArrayLike) -> None:
+        """Move the skinned scene (sas_scene_deform; DESIGN.md 3, "Deformation"): ``node_transforms [m,3,4]``, rows ``[R | t]`` that map
+        the REST pose to the current one in the frame of ``upload`` (in front of the group poses).  Means follow by linear blend
+        skinning over each Gaussian's live entries, orientations by the blended quaternion; the transforms are expected to be rigid
+        (stretch and shear are dropped).  Always rest -> current: two calls do not accumulate.  A float32 device tensor is read where
+        it is, unchecked; NumPy arrays and lists are copied and checked (``deform.check_node_transforms``: shape, finite, ``R^T R``
+        within 1e-4 of identity).  The next frame shows the deformed scene; ``read_scene`` returns it.  Only enqueues, on the current
+        stream."""
+        if isinstance(node_transforms, torch.Tensor) and node_transforms.is_cuda:
+            t = node_transforms.detach()
+            if not (t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and t.dim() == 3 and tuple(t.shape[1:]) == (3, 4)):
+                raise ValueError(f"node_transforms on the device must be a contiguous float32 tensor [m,3,4] on {self.device}, got {t.dtype} {list(t.shape)}")
+        else:
+            from .deform import check_node_transforms
+            t = torch.from_numpy(check_node_transforms(_host(node_transforms))).to(self.device)
+        m = int(t.shape[0])
+        if not 1 <= m <= _capi.SAS_KNN_CROSS_MAX_NODES:
+            raise ValueError(f"node_transforms: m={m} out of [1, {_capi.SAS_KNN_CROSS_MAX_NODES}]")
+        rc = self._L.sas_scene_deform(self._ctx, m, _addr(t), self._stream())
+        if rc != 0:
+            self._check(rc, "sas_scene_deform")
+        self._in_flight(True)
+
+    @_locked
+    def bind_skin(self, nodes: ArrayLike, k: int = 4, sigma: Optional[float] = None, max_distance: float = math.inf,
+                  group: Optional[int] = None) -> Dict[str, object]:
+        """Bind every Gaussian to its ``k`` nearest of ``nodes [M,3]`` (the scene's frame, rest pose) with radial weights, and
+        ``set_skin`` the result: the rest means come from ``read_scene()``, the neighbours from ``knn_nodes``, and
+        ``w_j = exp(-(d2_j - d2_0) / (2 sigma^2))`` -- the nearest node's weight is exactly 1, so no row underflows to a zero sum.
+        Missing neighbours (beyond ``max_distance``, or ``M < k``) and Gaussians outside ``group`` (a splat group id of ``upload``; None:
+        all) get index -1 and weight 0: they stay at rest.  ``sigma`` None: the mean distance of a node to its nearest other node
+        (``knn_points(nodes, 1)``; 1 for a single node).  A skin bound already is cleared first: the nodes are matched against the rest
+        pose.  Returns ``indices``, ``weights`` (device tensors) and ``sigma``.  Blocking."""
+        q = self._cloud(nodes, "nodes")
+        if sigma is None:
+            d2 = self.knn_points(q, 1)["dist2"].cpu().numpy().astype(np.float64).reshape(-1)
+            d2 = d2[np.isfinite(d2)]
+            sigma = float(np.mean(np.sqrt(d2))) if d2.size else 1.0
+        sigma = float(sigma)
+        if not (sigma > 0.0 and math.isfinite(sigma)):
+            raise ValueError(f"sigma must be positive and finite, got {sigma} (coincident nodes? pass sigma)")
+        keep = None
+        if group is not None:
+            if self._group_ids is None or not 0 <= int(group) < self.n_groups:
+                raise ValueError(f"group {group}: the scene has {self.n_groups} splat groups")
+            keep = torch.as_tensor(self._group_ids).to(self.device).reshape(-1) == int(group)
+        self.clear_skin()   # (a skin bound already: back to the rest pose, which is what the nodes are matched against)
+        nn = self.knn_nodes(self.read_scene()["means"], q, k, max_distance)
+        d2, idx = nn["dist2"], nn["index"]
+        w = torch.exp(-(d2 - d2[:, :1]) / (2.0 * sigma * sigma))
+        off = idx < 0
+        if keep is not None:
+            off = off | ~keep[:, None]
+        w = torch.where(off, torch.zeros_like(w), w)
+        idx = torch.where(off, torch.full_like(idx, -1), idx)
+        self.set_skin(idx, w)
+        return {"indices": idx, "weights": w, "sigma": sigma}
 
     @_locked
     def read_order(self) -> torch.Tensor:

@@ -118,6 +118,7 @@ class SplatScene:
         self.background = tuple(background)
         self.mesh_ambient, self.mesh_diffuse = 0.4, 0.6   # mesh shading ("Meshes"); set before the first render
         self.camera = _Camera()
+        self._deformable = None   # (handle, nodes, bind_kw) of bind_deformable: bound again whenever the scene is uploaded again
 
     def _register(self, handle_class, name: str, wxyz, position):
         """(lock held)  A new handle on a pose row of its own, written into the block; the scene is uploaded again before the next frame."""
@@ -230,6 +231,30 @@ class SplatScene:
             self._raster.set_link_poses(q_msg, p_msg, out=self._Rt.reshape(-1))
             self._links_gen += 1
 
+    # -- deformable groups ("Deformation") ------------------------------------------
+    def bind_deformable(self, handle: GaussianSplatHandle, nodes, **bind_kw) -> Dict[str, object]:
+        """Make ``handle``'s splat group deformable: its Gaussians are bound to ``nodes [M,3]`` (the handle's LOCAL frame, the frame of
+        ``add_gaussian_splats``' centers) as ``Rasterizer.bind_skin`` binds them (``k``, ``sigma``, ``max_distance``); every other group
+        stays rigid.  The handle's ``.wxyz`` / ``.position`` still pose the deformed group.  One deformable group per scene.  Returns
+        ``bind_skin``'s result."""
+        with self.lock:
+            if not isinstance(handle, GaussianSplatHandle) or isinstance(handle, MeshHandle) or handle._scene is not self:
+                raise ValueError("bind_deformable: a splat-group handle of this scene is required")
+            self._deformable = None
+            self._sync()
+            res = self._raster.bind_skin(nodes, group=handle.index, **bind_kw)
+            self._deformable = (handle, np.array(nodes, np.float32, copy=True), dict(bind_kw))
+            return res
+
+    def deform(self, node_transforms) -> None:
+        """``Rasterizer.deform`` for the group of ``bind_deformable``: ``node_transforms [M,3,4]``, rest -> current in the handle's
+        local frame.  The next ``get_render*`` shows it."""
+        with self.lock:
+            if self._deformable is None:
+                raise RuntimeError("bind_deformable first")
+            self._sync()
+            self._raster.deform(node_transforms)
+
     # -- internals ---------------------------------------------------------------------------
     def _sync(self) -> None:
         if not self._uploaded:
@@ -264,6 +289,9 @@ class SplatScene:
             self._uploaded = True
             self._poses_dirty = True
             self._link_owner_applied = _NO_OWNER_APPLIED    # a fresh upload: the context holds nobody's link constants
+            if self._deformable is not None:                # ... and no skin
+                h, nodes, kw = self._deformable
+                self._raster.bind_skin(nodes, group=h.index, **kw)
         if self._poses_dirty and self._handles:
             self._raster.set_group_poses(self._Rt.reshape(-1, 12))
         self._poses_dirty = False
