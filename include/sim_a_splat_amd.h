@@ -846,12 +846,29 @@ int sas_knn_last_counts(sas_ctx *ctx, int64_t *out, int n);
  * frame is invalidated as sas_scene_adam_step does.  SAS_ERR_INVALID without a skin, for m out of range or node_Rt NULL.
  * The environment variable SAS_SKIN_LDS=bytes (read when the context is created; 0..16384, the default) is the size up to which the node
  * records (64 B each) are staged in LDS; no result depends on it.
+ *
+ * sas_scene_deform_backward -- the adjoint of the LAST sas_scene_deform on the bound skin: from the gradients of the deformed arrays, as
+ * sas_render_backward writes them on a skinned scene (d_means [N,3], and d_quats [N,4] for a quaternion scene or d_cov6 [N,6] for a
+ * covariance scene; float32 DEVICE, the caller's order), to d_node_Rt [m,3,4] float32 DEVICE, WRITTEN: the gradient with respect to the
+ * twelve entries of every node's [R | t], each an independent variable, exactly as d_viewmat and d_group_poses treat theirs.  m is the
+ * last deform's.  The orientation gradient that does not match the scene's form must be NULL; d_means or the orientation gradient may be
+ * NULL, not both; with the orientation gradient NULL the rotation path is skipped entirely.  The function differentiated is the one
+ * sas_scene_deform evaluates with every decision a constant: which entries are live, the branch of the matrix-to-quaternion conversion,
+ * the signs s_j, and the fallback to q_first.  The node records the deform left on the device are the saved state: node_Rt may have
+ * changed since.  A node no live entry names gets an exact zero row; zero upstream gives exact zeros.  Otherwise the sums are float
+ * atomics and vary in their last bits from run to run.  The adjoint is linear in its inputs: sum the views' gradients, call once.
+ * It only ENQUEUES on `stream` (behind the deform, and behind its own previous call, whose accumulator it shares); no host
+ * synchronisation.  SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID without a skin, without a sas_scene_deform since the skin was
+ * bound (a rebind or a clear resets that), for all three gradients NULL, an orientation gradient of the wrong form, d_node_Rt NULL.
+ * SAS_SKIN_GRAD_LDS=bytes (0..131072, the default) is the size up to which the per-node sums (64 B each) are kept in LDS by every
+ * workgroup; SAS_SKIN_GRAD_STAGED=0/1 forces the form of the adds.  Both change the order of the sums only.
  */
 int sas_knn_cross(sas_ctx *ctx, int64_t n, const float *points, int64_t m, const float *nodes, int k, float max_distance,
                   float *dist2_out, int32_t *index_out_or_null, void *stream);
 int sas_scene_skin(sas_ctx *ctx, int k, const int32_t *indices, const float *weights, void *stream);
 int sas_scene_skin_read(sas_ctx *ctx, int32_t *indices_out, float *weights_out);
 int sas_scene_deform(sas_ctx *ctx, int m, const float *node_Rt, void *stream);
+int sas_scene_deform_backward(sas_ctx *ctx, const float *d_means, const float *d_quats, const float *d_cov6, float *d_node_Rt, void *stream);
 
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical

@@ -8,7 +8,8 @@ their gradients have somewhere to go -- after an optimiser step of the caller's 
 ``Rasterizer.adam_step``: a fused Adam step on the resident scene from the gradients ``Rasterizer.render_backward`` returns
 (``fit.fit_scene`` is the loop).  The view matrix is an argument of every call and needs no upload.
 
-The poses of the splat groups are a variable too (``group_poses=``, up to 32 groups per frame).  Not differentiated: K, meshes (a
+The poses of the splat groups are a variable too (``group_poses=``, up to 32 groups per frame), and so are the node transforms of a
+deformable scene (``node_transforms=``).  Not differentiated: K, meshes (a
 scene with meshes is refused), joint angles, and every decision of the renderer (culls, clamps, the alpha and transmittance
 thresholds), which are constants of the derivative.  The per-Gaussian sums are float atomics: gradients
 vary in their last bits from run to run.
@@ -47,31 +48,37 @@ def prechain(rgb: torch.Tensor, alpha: torch.Tensor, depth: torch.Tensor, backgr
 
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, r, viewmat, K, W, H, background, keys, pose_groups, group_poses, *tensors):
+    def forward(ctx, r, viewmat, K, W, H, background, keys, pose_groups, group_poses, node_transforms, *tensors):
         V = np.eye(4, dtype=np.float32)
         V[:viewmat.shape[0]] = viewmat.detach().cpu().numpy().astype(np.float32)
         if group_poses is not None:   # the frame is rendered under these poses, and they stay set
             r.set_group_poses(group_poses.detach().to(torch.float32).cpu().numpy().reshape(-1, 12))
+        if node_transforms is not None:   # ... and under this deformation, which stays too
+            r.deform(node_transforms.detach().to(device=r.device, dtype=torch.float32).contiguous())
         out = r.render(V, K, W, H, background)
         rgb, alpha, depth = out["rgb"].clone(), out["alpha"].clone(), out["depth"].clone()
         ctx.save_for_backward(rgb, alpha, depth)
         pmeta = None if group_poses is None else (group_poses.device, group_poses.dtype, tuple(group_poses.shape))
+        nmeta = None if node_transforms is None else (node_transforms.device, node_transforms.dtype, tuple(node_transforms.shape))
         ctx.call = (r, V, K, W, H, background, keys, tuple(viewmat.shape), viewmat.device, viewmat.dtype,
-                    [(t.device, t.dtype, tuple(t.shape)) for t in tensors], pose_groups, pmeta)
+                    [(t.device, t.dtype, tuple(t.shape)) for t in tensors], pose_groups, pmeta, nmeta)
         return rgb, alpha, depth
 
     @staticmethod
     def backward(ctx, g_rgb, g_alpha, g_depth):
         rgb, alpha, depth = ctx.saved_tensors
-        r, V, K, W, H, background, keys, vshape, vdev, vdt, metas, pose_groups, pmeta = ctx.call
+        r, V, K, W, H, background, keys, vshape, vdev, vdt, metas, pose_groups, pmeta, nmeta = ctx.call
         g_acc, g_a, g_z = prechain(rgb, alpha, depth, background, g_rgb, g_alpha, g_depth)
         # only what some input needs: the projection's backward neither reads nor writes the rest
-        needs = ctx.needs_input_grad[9:]
+        needs = ctx.needs_input_grad[10:]
         need_poses = pmeta is not None and ctx.needs_input_grad[8]
+        need_nodes = nmeta is not None and ctx.needs_input_grad[9]
         want = (("viewmat",) if ctx.needs_input_grad[1] else ()) + tuple(k for k, need in zip(keys, needs) if need) + \
             (("group_poses",) if need_poses else ())
+        if need_nodes:   # the deformed means and orientations are what the nodes move
+            want += tuple(k for k in ("means", "quats" if r.covariance_form == "quats" else "covariances") if k not in want)
         if not want:
-            return (None,) * (9 + len(keys))
+            return (None,) * (10 + len(keys))
         res = r.render_backward(V, K, W, H, g_acc, g_a, g_z, want=want, pose_groups=pose_groups if need_poses else None)
         grads = [None]
         if ctx.needs_input_grad[1]:
@@ -84,9 +91,13 @@ class _Render(torch.autograd.Function):
             full = torch.zeros((pshape[0], 12), dtype=torch.float32, device=res["group_poses"].device)
             full[torch.as_tensor(list(pose_groups), dtype=torch.long, device=full.device)] = res["group_poses"].reshape(-1, 12)
             gp = full.reshape(pshape).to(device=pdev, dtype=pdt)
+        gn = None
+        if need_nodes:
+            ndev, ndt, nshape = nmeta
+            gn = r.deform_backward(res).reshape(nshape).to(device=ndev, dtype=ndt)
         for k, (dev, dt, shape), need in zip(keys, metas, needs):
             grads.append(res[k].reshape(shape).to(device=dev, dtype=dt) if need else None)
-        return (None, grads[0], None, None, None, None, None, None, gp, *grads[1:])
+        return (None, grads[0], None, None, None, None, None, None, gp, gn, *grads[1:])
 
 
 class _PhotometricLoss(torch.autograd.Function):
@@ -115,7 +126,7 @@ def photometric_loss(r, rgb: torch.Tensor, target, mask=None, lambda_dssim: floa
 
 def render_differentiable(r, viewmat: torch.Tensor, K, width: int, height: int, params: Optional[Dict[str, torch.Tensor]] = None,
                           background: Optional[Sequence[float]] = None, group_poses: Optional[torch.Tensor] = None,
-                          pose_groups: Optional[Sequence[int]] = None) -> Dict[str, torch.Tensor]:
+                          pose_groups: Optional[Sequence[int]] = None, node_transforms: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """One frame of rasterizer ``r`` -- ``rgb [H,W,3]``, ``alpha [H,W,1]``, ``depth [H,W,1]`` on its device -- through which gradients
     flow to ``viewmat`` (``[4,4]`` or ``[3,4]``, world to camera; its twelve upper entries are independent variables) and to those
     tensors of ``params`` that require grad.  ``params`` maps ``means``, ``opacities``, ``colors``, ``quats``, ``scales`` or
@@ -125,7 +136,12 @@ def render_differentiable(r, viewmat: torch.Tensor, K, width: int, height: int, 
     ``group_poses``: ``[G,3,4]`` or ``[G,12]``, rows ``[R | t]`` of ALL the scene's splat groups.  Unlike ``params`` it is a value: its
     detached float32 copy is set with ``set_group_poses`` before the frame (and stays set), and its gradient comes back in its shape,
     device and dtype, twelve independent entries per group, the rows of ``pose_groups`` filled and the rest zero.  ``pose_groups``
-    defaults to all groups when there are at most 32 of them; with more it is required (32 ids at the most per frame)."""
+    defaults to all groups when there are at most 32 of them; with more it is required (32 ids at the most per frame).
+
+    ``node_transforms``: ``[m,3,4]``, rows ``[R | t]`` of the nodes of the skin bound to ``r`` (``Rasterizer.bind_skin``).  A value like
+    ``group_poses``: its detached float32 copy goes through ``r.deform`` before the frame (and stays set), and its gradient comes back
+    in its shape, device and dtype, twelve independent entries per node (``Rasterizer.deform_backward``).  It combines with
+    ``viewmat``, ``group_poses`` and ``params`` in one call; under a skin the gradients of ``params`` are those of the DEFORMED arrays."""
     bg = (0.0, 0.0, 0.0) if background is None else tuple(float(v) for v in background)
     params = params or {}
     unknown = [k for k in params if k not in PARAM_KEYS]
@@ -145,5 +161,8 @@ def render_differentiable(r, viewmat: torch.Tensor, K, width: int, height: int, 
         sel = tuple(int(g) for g in pose_groups)
     elif pose_groups is not None:
         raise ValueError("render_differentiable: pose_groups without group_poses")
-    rgb, alpha, depth = _Render.apply(r, viewmat, Kc, int(width), int(height), bg, keys, sel, group_poses, *[params[k] for k in keys])
+    if node_transforms is not None and (node_transforms.dim() != 3 or tuple(node_transforms.shape[1:]) != (3, 4)):
+        raise ValueError(f"render_differentiable: node_transforms must be [m,3,4], got {tuple(node_transforms.shape)}")
+    rgb, alpha, depth = _Render.apply(r, viewmat, Kc, int(width), int(height), bg, keys, sel, group_poses, node_transforms,
+                                      *[params[k] for k in keys])
     return dict(rgb=rgb, alpha=alpha, depth=depth)

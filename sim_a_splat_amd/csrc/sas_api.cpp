@@ -135,10 +135,12 @@ struct Adam {
 // The skin of the resident scene (sas_scene_skin; DESIGN.md 3, "Deformation"), slot order: the rest snapshot of g0 / g1 / g2 taken at the
 // first bind, the entries' planes, and the node records of the last sas_scene_deform.  k == 0: no skin is bound.  Clearing a skin gives no
 // memory back (hipFree would wait for the whole device in front of frames in flight): the buffers serve the next bind, and go where the
-// optimiser state goes, at the next upload or with the context.
+// optimiser state goes, at the next upload or with the context.  m: the node count of the last sas_scene_deform since the bind, whose records
+// `nodes` holds (0: none -- sas_scene_deform_backward has nothing to differentiate); grad_acc: that call's accumulator [m,16].
 struct Skin {
-    DevBuf rest0, rest1, rest2, idx, w, nodes;
+    DevBuf rest0, rest1, rest2, idx, w, nodes, grad_acc;
     int k = 0;
+    int m = 0;
     bool bound() const { return k > 0; }
     int kp() const { return k <= 4 ? 4 : SAS_SKIN_MAX_K; }
     int drop(sas_ctx *c);
@@ -275,6 +277,13 @@ struct Settings {
     // sas_scene_deform stages the node records in LDS while m * 64 B fits this budget (SAS_SKIN_LDS=bytes, 0: never; SAS_SKIN_LDS_BYTES at
     // most, which is what the kernel reserves).  No result depends on it: the knob is there so that tests and tools/deform_probe.py compare the paths
     int skin_lds = SAS_SKIN_LDS_BYTES;
+    // sas_scene_deform_backward sums its accumulator rows in LDS while m * 64 B fits this budget (SAS_SKIN_GRAD_LDS=bytes, 0: never;
+    // SAS_SKIN_GRAD_LDS_MAX at most), and above it adds to global memory.  skin_grad_staged: rows pass through LDS and are added 16 lanes per row
+    // (1) or every lane adds its own row (0); -1: the faster form (profiles/deform_grad.txt): staged on the global path, and on the LDS path while the
+    // accumulator is within SAS_SKIN_GRAD_STAGED_LDS_BYTES (beyond it the stage costs workgroups per CU).  SAS_SKIN_GRAD_STAGED=0/1 forces one.
+    // Results differ in their last bits only (the order of a float sum): the knobs are there so that tests and tools/deform_grad_probe.py compare
+    int skin_grad_lds = SAS_SKIN_GRAD_LDS_BYTES;
+    int skin_grad_staged = -1;
     static Settings from_env()
     {
         Settings s;
@@ -293,6 +302,8 @@ struct Settings {
         if (num("SAS_ORDER", v)) s.order_on_device = v != 0;
         if (num("SAS_KNN_GRID", v) && v >= 1 && v <= SAS_KNN_MAX_AXIS) s.knn_grid = (int)v;
         if (num("SAS_SKIN_LDS", v) && v >= 0) s.skin_lds = (int)std::min<long long>(v, SAS_SKIN_LDS_BYTES);
+        if (num("SAS_SKIN_GRAD_LDS", v) && v >= 0) s.skin_grad_lds = (int)std::min<long long>(v, SAS_SKIN_GRAD_LDS_MAX);
+        if (num("SAS_SKIN_GRAD_STAGED", v)) s.skin_grad_staged = v != 0 ? 1 : 0;
         return s;
     }
 };
@@ -323,6 +334,7 @@ struct sas_ctx : Settings {
     Event adam_done;      // recorded behind a step on the caller's stream: the slots' streams wait for it
     Skin skin;            // skin of the resident scene
     Event skin_done;      // recorded behind sas_scene_skin / sas_scene_deform on the caller's stream, as adam_done
+    Event skin_grad_done; // recorded behind sas_scene_deform_backward's launches: the next call's stream waits for it before it zeroes the accumulator
     DevBuf grad_screen;   // sas_render_backward: [10 n] screen-space sums + [ceil(n / 256)][12] view-matrix rows (SasGradProj)
     int grad_frame = 0;   // the last frame is a backward frame: 1 of sas_render_backward_screen, 2 of sas_render_backward (grad_screen holds its sums); 0: none
     Event density_done;   // recorded behind sas_density_accumulate / sas_scene_reset_opacity / sas_scene_mcmc_noise on the caller's stream: the slots' streams wait for it
@@ -461,9 +473,9 @@ int Adam::alloc(sas_ctx *c, int row, int64_t n_pad, int colour_planes, hipStream
 // The skin goes with its scene (sas_scene_upload): hipFree waits for the deformation that may still be using it.
 int Skin::drop(sas_ctx *c)
 {
-    for (DevBuf *b : {&rest0, &rest1, &rest2, &idx, &w, &nodes})
+    for (DevBuf *b : {&rest0, &rest1, &rest2, &idx, &w, &nodes, &grad_acc})
         if (const int rc = b->release(c)) return rc;
-    k = 0;
+    k = m = 0;
     return SAS_OK;
 }
 
@@ -3104,7 +3116,7 @@ int sas_scene_skin(sas_ctx *c, int k, const int32_t *indices, const float *weigh
     DevBuf *rest[3] = {&sk.rest0, &sk.rest1, &sk.rest2}, *live[3] = {&pl.g0, &pl.g1, &pl.g2};
     if (k == 0) {   // the rest planes back, bit for bit
         for (int p = 0; p < 3; ++p) HIP_TRY(c, hipMemcpyAsync(live[p]->p, rest[p]->p, plane, hipMemcpyDeviceToDevice, st));
-        sk.k = 0;
+        sk.k = sk.m = 0;
         if (const int rc = slots_wait_for(c, c->skin_done, st)) return rc;
         scene_changed(c, Changed::Values);
         return SAS_OK;
@@ -3119,6 +3131,7 @@ int sas_scene_skin(sas_ctx *c, int k, const int32_t *indices, const float *weigh
     sas_launch_skin_bind(st, q);
     HIP_TRY(c, hipGetLastError());
     sk.k = k;
+    sk.m = 0;   // (the records belong to the entries before)
     return slots_wait_for(c, c->skin_done, st);   // (the planes' values stay: the last frame does too)
 }
 
@@ -3175,8 +3188,60 @@ int sas_scene_deform(sas_ctx *c, int m, const float *node_Rt, void *stream)
     q.lds = sizeof(SasSkinNode) * (size_t)m <= (size_t)c->skin_lds;
     sas_launch_deform(st, q);
     HIP_TRY(c, hipGetLastError());
+    sk.m = m;
     if (const int rc = slots_wait_for(c, c->skin_done, st)) return rc;
     scene_changed(c, Changed::Values);   // the last frame showed the scene before the deformation
+    return SAS_OK;
+}
+
+// The adjoint of the last sas_scene_deform (k_deform_grad, k_skin_nodes_grad).  Host work: validation, the accumulator (grown by the first call at
+// a larger m), two stream waits, one memset, two launches, one event.  No host synchronisation.
+int sas_scene_deform_backward(sas_ctx *c, const float *d_means, const float *d_quats, const float *d_cov6, float *d_node_Rt, void *stream)
+{
+    const char *who = "sas_scene_deform_backward";
+    if (const int rc = need_scene(c, who)) return rc;
+    Skin &sk = c->skin;
+    if (!sk.bound()) return fail(c, SAS_ERR_INVALID, "%s: no skin is bound: sas_scene_skin first", who);
+    if (sk.m <= 0) return fail(c, SAS_ERR_INVALID, "%s: no sas_scene_deform since the skin was bound", who);
+    if (!d_means && !d_quats && !d_cov6) return fail(c, SAS_ERR_INVALID, "%s: d_means, d_quats and d_cov6 are all NULL", who);
+    const SasScene &sc = c->scene;
+    if (sc.cov_mode ? d_quats != nullptr : d_cov6 != nullptr)
+        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as %s: %s must be NULL", who, sc.cov_mode ? "covariances" : "quaternions",
+                    sc.cov_mode ? "d_quats" : "d_cov6");
+    if (!d_node_Rt) return fail(c, SAS_ERR_INVALID, "%s: d_node_Rt is NULL", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int m = sk.m;
+    const size_t acc_bytes = sizeof(float) * SAS_SKIN_GRAD_ROW * (size_t)m;
+    if (const int rc = ensure(c, sk.grad_acc, acc_bytes)) return rc;
+    if (c->match_cus <= 0) {
+        HIP_TRY(c, hipDeviceGetAttribute(&c->match_cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        if (c->match_cus <= 0) c->match_cus = 1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    SasDeformGrad q{};
+    q.perm = sc.perm;
+    q.d_means = d_means; q.d_quats = d_quats; q.d_cov6 = d_cov6;
+    q.nodes = (const SasSkinNode *)sk.nodes.p;
+    q.r0 = (const float4 *)sk.rest0.p; q.r1 = (const float4 *)sk.rest1.p; q.r2 = (const float4 *)sk.rest2.p;
+    q.idx = (const int4 *)sk.idx.p; q.w = (const float4 *)sk.w.p;
+    q.n = sc.n; q.n_pad = sc.n_pad;
+    q.m = m; q.kp = sk.kp(); q.cov_mode = sc.cov_mode;
+    q.lds = acc_bytes <= (size_t)c->skin_grad_lds;
+    q.staged = c->skin_grad_staged >= 0 ? c->skin_grad_staged : (!q.lds || acc_bytes <= SAS_SKIN_GRAD_STAGED_LDS_BYTES);
+    // a persistent grid: as many workgroups per CU as their LDS allows, 4 at the most
+    const size_t lds_bytes = sas_deform_grad_lds_bytes(m, q.lds != 0, q.staged != 0);
+    const long long per_cu = std::max<long long>(1, std::min<long long>(4, lds_bytes ? (160 * 1024) / (long long)lds_bytes : 4));
+    q.blocks = (int)std::max<long long>(1, std::min<long long>((sc.n + 255) / 256, per_cu * c->match_cus));
+    q.acc = (float *)sk.grad_acc.p;
+    q.out = d_node_Rt;
+    // behind the deformation whose records are read, and behind the call before, whose accumulator this is
+    if (c->skin_done.h) HIP_TRY(c, hipStreamWaitEvent(st, c->skin_done, 0));
+    if (!c->skin_grad_done.h) HIP_TRY(c, hipEventCreateWithFlags(c->skin_grad_done.put(), hipEventDisableTiming));
+    else HIP_TRY(c, hipStreamWaitEvent(st, c->skin_grad_done, 0));
+    HIP_TRY(c, hipMemsetAsync(q.acc, 0, acc_bytes, st));
+    sas_launch_deform_grad(st, q);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->skin_grad_done, st));
     return SAS_OK;
 }
 

@@ -824,3 +824,27 @@ struct SasDeform {
     int lds;                     // 1: the node records pass through LDS (m * 64 B within the budget)
 };
 void sas_launch_deform(hipStream_t st, const SasDeform &q);
+// The adjoint of the two (sas_scene_deform_backward): per-Gaussian gradients -> per-node [R | t] gradients
+#define SAS_SKIN_GRAD_ROW 16              // floats a live entry adds to its node's accumulator row: dt 3, the mean path's dR 9, dq 4
+#define SAS_SKIN_GRAD_LDS_MAX 131072      // accumulator bytes k_deform_grad keeps in LDS at most (2048 nodes): the SAS_SKIN_GRAD_LDS budget's ceiling
+#define SAS_SKIN_GRAD_LDS_BYTES 131072    // ... and its default: at 2048 nodes the LDS path is still 2.4x the global one (profiles/deform_grad.txt)
+#define SAS_SKIN_GRAD_STAGED_LDS_BYTES 16384   // LDS path: accumulator bytes up to which the rows are staged (256 nodes: staged 0.39 ms, own rows 0.47; at 1024 0.50 and 0.46)
+struct SasDeformGrad {
+    const int *perm;             // [n] slot -> caller's index
+    const float *d_means;        // [n,3] caller's order, or nullptr
+    const float *d_quats;        // [n,4] or nullptr (quaternion scenes)
+    const float *d_cov6;         // [n,6] or nullptr (covariance scenes)
+    const SasSkinNode *nodes;    // [m] the last sas_scene_deform's records
+    const float4 *r0, *r1, *r2;  // the rest planes
+    const int4 *idx;
+    const float4 *w;
+    long long n, n_pad;
+    int m, kp, cov_mode;
+    int lds;                     // 1: the accumulator rows are summed in LDS and flushed once per workgroup
+    int staged;                  // 1: a workgroup's rows pass through LDS and are added 16 lanes per row
+    int blocks;                  // workgroups of the persistent grid
+    float *acc;                  // [m,16] zeroed by the caller on the stream
+    float *out;                  // [m,12] written
+};
+size_t sas_deform_grad_lds_bytes(int m, bool lds, bool staged);   // dynamic LDS of one workgroup
+void sas_launch_deform_grad(hipStream_t st, const SasDeformGrad &q);

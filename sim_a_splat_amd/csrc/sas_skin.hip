@@ -23,6 +23,36 @@
 //                   in LDS by every workgroup (m * 64 B within SAS_SKIN_LDS_BYTES); else each lane reads its records from global memory.  The
 //                   arithmetic is the same text on the same values: both paths give the same bits.
 // Arithmetic: IEEE binary32, nothing fused (-ffp-contract=off, no fma_); tests/tools/skin_ref.py restates it.
+//
+// The adjoint (sas_scene_deform_backward): from per-Gaussian gradients of the deformed means and orientations to the gradient of every node's
+// twelve entries [R | t], each an independent variable.  Every decision of the forward is a constant: which entries are live, the branch of
+// k_skin_nodes, the signs s_j, the fallback to q_first.  Nothing is saved by the forward but the node records.
+//   k_deform_grad<LDS,STAGED,KP>  one lane per slot, a persistent grid walking the slots with a stride.  The lane recomputes W, a, n2, q_b, q_first
+//                   and the signs, and forms one 16-float ROW per live entry: dt (3) = (w_j / W) g, the mean path's dR (9) = (w_j / W) g m_rest^T,
+//                   dq_j (4) = s_j w_j da with da = (dq_b - q_b (q_b . dq_b)) / |a| (fallback: dq_b to the first live entry, nothing to the others).
+//                   dq_b: quaternion scenes, the product of h with q_rest that transposes q_b (x) q_rest; covariance scenes, dR_b = 2 G R_b Sigma
+//                   (G the symmetric matrix of the six, off-diagonals halved) through the matrix of q_b.  The rows are summed per node into
+//                   acc [m,16], zeroed on the stream by every call.
+//   k_skin_nodes_grad  one lane per node: acc row -> the 12 outputs.  dt and dR as summed, plus du = (dq - q (q . dq)) / |u| through the transpose of
+//                   the branch's linear map R -> u.  A node no live entry names reads a zero row and writes exact zeros.
+// Sizing.  At a million Gaussians and k = 4 there are 4 M rows of 64 B: 256 MB of adds.  Straight to memory that is 0.2 ms at best at the chip-wide
+// float-atomic rate of about 1.3 TB/s, and the shape is against it: one lane per row is the 64-rows-per-instruction shape (about 17x slower), and
+// with M = 64 every add lands in 4 KB, the contended case.  So the rows are summed on chip first: while m * 64 B fits the budget (SAS_SKIN_GRAD_LDS
+// bytes, SAS_SKIN_GRAD_LDS_BYTES by default; 0: never) every workgroup keeps acc in LDS, adds there with LDS float atomics and flushes ONCE with global float
+// atomics over contiguous floats -- a wave-instruction covers 256 contiguous bytes, 4 node rows, the full-rate shape; zeros are not sent.  The grid
+// is persistent, as many workgroups per CU as their LDS allows and 4 at most, so the flush costs blocks * m * 64 B and not N k * 64 B.  Above the
+// budget the rows go to global memory.  STAGED: a workgroup's 256 rows of one entry pass through 16 KB of LDS and come out transposed, 16 lanes per
+// row, so that an atomic instruction covers 4 whole 64-B rows; not STAGED: every lane adds its own 16 floats, 64 rows per instruction.  Both forms
+// exist for both paths (SAS_SKIN_GRAD_STAGED=0/1 forces one).  Measured (profiles/deform_grad.txt; a million Gaussians, k = 4): on the global path
+// the staged form is 5 to 7 times the other (m = 16384: 0.63 against 4.6 ms; 64-B segments reach 0.3 to 0.45 of the 1.3 TB/s), so it is what that
+// path takes.  The LDS path beats it at every m that fits (m = 2048: 0.46 against 1.10 ms; m = 64: 0.39 against 8.6), so the budget's default is its
+// ceiling, SAS_SKIN_GRAD_LDS_MAX.  Within the LDS path the staged form wins while the accumulator is small (m = 256: 0.39 against 0.47 ms: the LDS
+// adds of a wave then land in 4 rows and not in 64) and loses once the 17 KB of stage cost workgroups per CU (m = 1024: 0.50 against 0.46): staged up
+// to SAS_SKIN_GRAD_STAGED_LDS_BYTES.  Combining equal nodes within a wave in front of the LDS add was not built: at m = 64 the LDS path runs in the
+// time it runs in at m = 2048, so the adds' conflicts do not bind.
+// Residency: 60 to 70 VGPRs (7 or 8 waves per SIMD by registers, no spills); what bounds it is the LDS, all of it dynamic: 17 408 B of stage and
+// m * 64 B of sums -- 4 workgroups per CU up to m = 368 staged, 2 at m = 1024 and 1 at m = 2048 with every lane adding its own row.
+// Float atomics: the sums depend on arrival order and vary in their last bits from run to run; zero rows and zero upstream give exact zeros.
 #include "sas_device.h"
 
 #pragma clang fp contract(off)
@@ -237,6 +267,258 @@ __global__ __launch_bounds__(kThreads) void k_deform(const SasDeform q)
     q.g2[j] = o2;
 }
 
+// ---- the adjoint ---------------------------------------------------------------------------------------------------------------------------
+constexpr int kRow = SAS_SKIN_GRAD_ROW;                  // floats of a row: dt 3, dR 9, dq 4
+constexpr int kStageFloats = kThreads * kRow;            // a workgroup's rows of one entry
+static_assert(kRow == 16 && kThreads % kRow == 0, "16 lanes per row in the staged flush");
+
+// one float into a row of acc: LDS or global, both no-return float atomics
+DEV void add_to(float *acc, long long at, float v) { atomicAdd(acc + at, v); }
+
+template <bool LDS, bool STAGED, int KP>
+__global__ __launch_bounds__(kThreads) void k_deform_grad(const SasDeformGrad q)
+{
+    extern __shared__ float s_mem[];
+    float *s_stage = s_mem;                                            // [256][16] (STAGED)
+    int *s_node = reinterpret_cast<int *>(s_mem + kStageFloats);       // [256]     (STAGED)
+    float *s_acc = s_mem + (STAGED ? kStageFloats + kThreads : 0);     // [m][16]   (LDS)
+    const int tid = threadIdx.x;
+    const int n_acc = q.m * kRow;
+    if constexpr (LDS) {
+        for (int t = tid; t < n_acc; t += kThreads) s_acc[t] = 0.0f;
+        __syncthreads();
+    }
+    float *acc = LDS ? s_acc : q.acc;
+    const float4 *g_nodes = reinterpret_cast<const float4 *>(q.nodes);
+    const bool rot = q.d_quats != nullptr || q.d_cov6 != nullptr;
+    const int n_col = rot ? kRow : 12;                                 // without an orientation gradient the dq columns are never touched
+    // the walk is the same for every lane of the workgroup: the barriers of the staged form are met by all
+    for (long long base = (long long)blockIdx.x * kThreads; base < q.n; base += (long long)gridDim.x * kThreads) {
+        const long long j = base + tid;   // slot
+        const bool active = j < q.n && SAS_IN(j, q.n_pad, 1510);
+        int id[KP];
+        float wt[KP];
+#pragma unroll
+        for (int e = 0; e < KP; ++e) { id[e] = -1; wt[e] = 0.0f; }
+        float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0, r2 = r0;
+        float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+        float h[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (active) {
+            r0 = q.r0[j]; r1 = q.r1[j]; r2 = q.r2[j];
+#pragma unroll
+            for (int p = 0; p < KP / 4; ++p) {
+                const int4 v = q.idx[(long long)p * q.n_pad + j];
+                const float4 u = q.w[(long long)p * q.n_pad + j];
+                id[4 * p] = v.x; id[4 * p + 1] = v.y; id[4 * p + 2] = v.z; id[4 * p + 3] = v.w;
+                wt[4 * p] = u.x; wt[4 * p + 1] = u.y; wt[4 * p + 2] = u.z; wt[4 * p + 3] = u.w;
+            }
+            const long long i = q.perm[j];   // the caller's index
+            if (SAS_IN(i, q.n, 1511)) {
+                if (q.d_means) { gx = q.d_means[3 * i]; gy = q.d_means[3 * i + 1]; gz = q.d_means[3 * i + 2]; }
+                if (q.d_quats) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) h[c] = q.d_quats[4 * i + c];
+                }
+                if (q.d_cov6) {
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) h[c] = q.d_cov6[6 * i + c];
+                }
+            }
+        }
+        // the forward's sums again: W, a, q_first
+        float W = 0.0f;
+        float4 f = make_float4(1.0f, 0.0f, 0.0f, 0.0f), aq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        bool any = false;
+        int first = -1;
+#pragma unroll
+        for (int e = 0; e < KP; ++e) {
+            const float we = wt[e];
+            if (!(id[e] >= 0 && id[e] < q.m && we > 0.0f)) continue;   // not live
+            W = W + we;
+            if (!rot) { any = true; continue; }
+            const float4 qn = g_nodes[4 * (long long)id[e] + 3];
+            if (!any) { f = qn; first = e; }
+            any = true;
+            const float dot = ((qn.x * f.x + qn.y * f.y) + qn.z * f.z) + qn.w * f.w;
+            const float sw = dot < 0.0f ? -we : we;
+            aq.x = aq.x + sw * qn.x;
+            aq.y = aq.y + sw * qn.y;
+            aq.z = aq.z + sw * qn.z;
+            aq.w = aq.w + sw * qn.w;
+        }
+        // dq_b, then da (or, in the fallback, dq_first)
+        float4 da = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        bool fallback = false;
+        if (any && rot) {
+            const float n2 = ((aq.x * aq.x + aq.y * aq.y) + aq.z * aq.z) + aq.w * aq.w;
+            float bw = f.x, bx = f.y, by = f.z, bz = f.w, inv = 1.0f;
+            fallback = !(n2 > 0.0f && n2 < INFINITY);
+            if (!fallback) {
+                inv = 1.0f / sqrtf(n2);
+                bw = aq.x * inv; bx = aq.y * inv; by = aq.z * inv; bz = aq.w * inv;
+            }
+            float dw, dx, dy, dz;
+            if (!q.cov_mode) {   // q' = q_b (x) q_rest, bilinear: h times the conjugate of q_rest
+                dw = ((h[0] * r1.x + h[1] * r1.y) + h[2] * r1.z) + h[3] * r1.w;
+                dx = ((h[1] * r1.x - h[0] * r1.y) - h[2] * r1.w) + h[3] * r1.z;
+                dy = ((h[2] * r1.x - h[0] * r1.z) + h[1] * r1.w) - h[3] * r1.y;
+                dz = ((h[3] * r1.x - h[0] * r1.w) - h[1] * r1.z) + h[2] * r1.y;
+            } else {             // Sigma' = R_b Sigma R_b^T: D = dR_b = 2 G (R_b Sigma), then the matrix of q_b
+                const float R[3][3] = {{1.0f - 2.0f * (by * by + bz * bz), 2.0f * (bx * by - bw * bz), 2.0f * (bx * bz + bw * by)},
+                                       {2.0f * (bx * by + bw * bz), 1.0f - 2.0f * (bx * bx + bz * bz), 2.0f * (by * bz - bw * bx)},
+                                       {2.0f * (bx * bz - bw * by), 2.0f * (by * bz + bw * bx), 1.0f - 2.0f * (bx * bx + by * by)}};
+                const float S[3][3] = {{r1.x, r1.y, r1.z}, {r1.y, r1.w, r2.x}, {r1.z, r2.x, r2.y}};
+                const float G[3][3] = {{2.0f * h[0], h[1], h[2]}, {h[1], 2.0f * h[3], h[4]}, {h[2], h[4], 2.0f * h[5]}};   // 2 G
+                float T[3][3], D[3][3];
+#pragma unroll
+                for (int a = 0; a < 3; ++a)
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) T[a][k] = (R[a][0] * S[0][k] + R[a][1] * S[1][k]) + R[a][2] * S[2][k];
+#pragma unroll
+                for (int a = 0; a < 3; ++a)
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) D[a][k] = (G[a][0] * T[0][k] + G[a][1] * T[1][k]) + G[a][2] * T[2][k];
+                dw = 2.0f * (((bz * (D[1][0] - D[0][1]) + by * (D[0][2] - D[2][0])) + bx * (D[2][1] - D[1][2])));
+                dx = 2.0f * ((((by * (D[0][1] + D[1][0]) + bz * (D[0][2] + D[2][0])) + bw * (D[2][1] - D[1][2])) - 2.0f * bx * (D[1][1] + D[2][2])));
+                dy = 2.0f * ((((bx * (D[0][1] + D[1][0]) + bz * (D[1][2] + D[2][1])) + bw * (D[0][2] - D[2][0])) - 2.0f * by * (D[0][0] + D[2][2])));
+                dz = 2.0f * ((((bx * (D[0][2] + D[2][0]) + by * (D[1][2] + D[2][1])) + bw * (D[1][0] - D[0][1])) - 2.0f * bz * (D[0][0] + D[1][1])));
+            }
+            if (fallback) {
+                da = make_float4(dw, dx, dy, dz);
+            } else {
+                const float dot = ((bw * dw + bx * dx) + by * dy) + bz * dz;
+                da = make_float4((dw - bw * dot) * inv, (dx - bx * dot) * inv, (dy - by * dot) * inv, (dz - bz * dot) * inv);
+            }
+        }
+        // one row per live entry
+#pragma unroll
+        for (int e = 0; e < KP; ++e) {
+            const float we = wt[e];
+            const bool live = id[e] >= 0 && id[e] < q.m && we > 0.0f;
+            float row[kRow];
+#pragma unroll
+            for (int c = 0; c < kRow; ++c) row[c] = 0.0f;
+            if (live) {
+                const float cw = we / W;
+                const float cg[3] = {cw * gx, cw * gy, cw * gz};
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    row[a] = cg[a];
+                    row[3 + 3 * a] = cg[a] * r0.x;
+                    row[4 + 3 * a] = cg[a] * r0.y;
+                    row[5 + 3 * a] = cg[a] * r0.z;
+                }
+                if (rot) {
+                    float sw = e == first ? 1.0f : 0.0f;   // the fallback: q_b is q_first as it stands
+                    if (!fallback) {
+                        const float4 qn = g_nodes[4 * (long long)id[e] + 3];
+                        const float dot = ((qn.x * f.x + qn.y * f.y) + qn.z * f.z) + qn.w * f.w;
+                        sw = dot < 0.0f ? -we : we;
+                    }
+                    row[12] = sw * da.x; row[13] = sw * da.y; row[14] = sw * da.z; row[15] = sw * da.w;
+                }
+            }
+            if constexpr (STAGED) {
+                if (SAS_IN(tid, kThreads, 1512)) {
+                    float4 *dst = reinterpret_cast<float4 *>(s_stage + tid * kRow);
+#pragma unroll
+                    for (int c = 0; c < kRow / 4; ++c) dst[c] = make_float4(row[4 * c], row[4 * c + 1], row[4 * c + 2], row[4 * c + 3]);
+                    s_node[tid] = live ? id[e] : -1;
+                }
+                __syncthreads();
+                const int col = tid % kRow;
+#pragma unroll 4
+                for (int r = tid / kRow; r < kThreads; r += kThreads / kRow) {   // a wave: 4 rows of 16 lanes
+                    const int node = s_node[r];
+                    if (node < 0 || col >= n_col) continue;
+                    const float v = s_stage[r * kRow + col];
+                    if (SAS_IN(node, q.m, 1513)) add_to(acc, (long long)node * kRow + col, v);
+                }
+                __syncthreads();   // the stage is free for the next entry
+            } else {
+                if (live && SAS_IN(id[e], q.m, 1514)) {
+#pragma unroll
+                    for (int c = 0; c < kRow; ++c)
+                        if (c < n_col) add_to(acc, (long long)id[e] * kRow + c, row[c]);
+                }
+            }
+        }
+    }
+    if constexpr (LDS) {   // one flush: contiguous floats, 4 node rows per wave-instruction; zeros stay at home
+        __syncthreads();
+        for (int t = tid; t < n_acc; t += kThreads) {
+            const float v = s_acc[t];
+            if (v != 0.0f && SAS_IN(t, n_acc, 1515)) atomicAdd(q.acc + t, v);
+        }
+    }
+}
+
+// acc row -> the node's 12 outputs: rows [dR | dt]
+__global__ __launch_bounds__(kThreads) void k_skin_nodes_grad(const SasDeformGrad q)
+{
+    const int a = blockIdx.x * kThreads + threadIdx.x;
+    if (a >= q.m || !SAS_IN(a, q.m, 1516)) return;
+    const float4 *A = reinterpret_cast<const float4 *>(q.acc + (long long)a * kRow);
+    const float4 a0 = A[0], a1 = A[1], a2 = A[2], dq = A[3];
+    const float dt[3] = {a0.x, a0.y, a0.z};
+    float dR[3][3] = {{a0.w, a1.x, a1.y}, {a1.z, a1.w, a2.x}, {a2.y, a2.z, a2.w}};
+    if (q.d_quats != nullptr || q.d_cov6 != nullptr) {
+        const float4 *rec = reinterpret_cast<const float4 *>(q.nodes + a);
+        const float4 G0 = rec[0], G1 = rec[1], G2 = rec[2], qn = rec[3];
+        const float r00 = G0.x, r01 = G0.y, r02 = G0.z, r10 = G1.x, r11 = G1.y, r12 = G1.z, r20 = G2.x, r21 = G2.y, r22 = G2.z;
+        const float tr = (r00 + r11) + r22;
+        int branch;
+        float w, x, y, z;
+        if (tr >= r00 && tr >= r11 && tr >= r22) {
+            branch = 0; w = 1.0f + tr; x = r21 - r12; y = r02 - r20; z = r10 - r01;
+        } else if (r00 >= r11 && r00 >= r22) {
+            branch = 1; w = r21 - r12; x = ((1.0f + r00) - r11) - r22; y = r01 + r10; z = r02 + r20;
+        } else if (r11 >= r22) {
+            branch = 2; w = r02 - r20; x = r01 + r10; y = ((1.0f + r11) - r00) - r22; z = r12 + r21;
+        } else {
+            branch = 3; w = r10 - r01; x = r02 + r20; y = r12 + r21; z = ((1.0f + r22) - r00) - r11;
+        }
+        const float inv = 1.0f / sqrtf(((w * w + x * x) + y * y) + z * z);
+        const float dot = ((qn.x * dq.x + qn.y * dq.y) + qn.z * dq.z) + qn.w * dq.w;
+        const float uw = (dq.x - qn.x * dot) * inv, ux = (dq.y - qn.y * dot) * inv, uy = (dq.z - qn.z * dot) * inv, uz = (dq.w - qn.w * dot) * inv;
+        // the transpose of the branch's map R -> u
+        if (branch == 0) {
+            dR[0][0] += uw; dR[1][1] += uw; dR[2][2] += uw;
+            dR[2][1] += ux; dR[1][2] -= ux; dR[0][2] += uy; dR[2][0] -= uy; dR[1][0] += uz; dR[0][1] -= uz;
+        } else if (branch == 1) {
+            dR[2][1] += uw; dR[1][2] -= uw;
+            dR[0][0] += ux; dR[1][1] -= ux; dR[2][2] -= ux;
+            dR[0][1] += uy; dR[1][0] += uy; dR[0][2] += uz; dR[2][0] += uz;
+        } else if (branch == 2) {
+            dR[0][2] += uw; dR[2][0] -= uw;
+            dR[0][1] += ux; dR[1][0] += ux;
+            dR[1][1] += uy; dR[0][0] -= uy; dR[2][2] -= uy;
+            dR[1][2] += uz; dR[2][1] += uz;
+        } else {
+            dR[1][0] += uw; dR[0][1] -= uw;
+            dR[0][2] += ux; dR[2][0] += ux; dR[1][2] += uy; dR[2][1] += uy;
+            dR[2][2] += uz; dR[0][0] -= uz; dR[1][1] -= uz;
+        }
+    }
+    float *o = q.out + 12 * (long long)a;   // (the caller's array: no alignment beyond a float's is asked of it)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        o[4 * i] = dR[i][0]; o[4 * i + 1] = dR[i][1]; o[4 * i + 2] = dR[i][2]; o[4 * i + 3] = dt[i];
+    }
+}
+
+template <bool LDS, bool STAGED>
+void launch_deform_grad(hipStream_t st, const SasDeformGrad &q, size_t lds_bytes)
+{
+    auto go = [&](auto kernel) {
+        // above 64 KiB a kernel has to ask for its dynamic LDS
+        if (lds_bytes > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)q.blocks), dim3(kThreads), lds_bytes, st, q);
+    };
+    if (q.kp <= 4) go(k_deform_grad<LDS, STAGED, 4>);
+    else go(k_deform_grad<LDS, STAGED, 8>);
+}
+
 template <bool LDS>
 void launch_deform(hipStream_t st, const SasDeform &q, unsigned blocks)
 {
@@ -276,4 +558,22 @@ void sas_launch_deform(hipStream_t st, const SasDeform &q)
     const unsigned blocks = (unsigned)((q.n + kThreads - 1) / kThreads);
     if (q.lds && (size_t)q.m * sizeof(SasSkinNode) <= SAS_SKIN_LDS_BYTES) launch_deform<true>(st, q, blocks);
     else launch_deform<false>(st, q, blocks);
+}
+
+size_t sas_deform_grad_lds_bytes(int m, bool lds, bool staged)
+{
+    return (staged ? sizeof(float) * (size_t)(kStageFloats + kThreads) : 0) + (lds ? sizeof(float) * kRow * (size_t)m : 0);
+}
+
+// the rows into acc (zeroed by the caller on st), then the nodes: two launches on st
+void sas_launch_deform_grad(hipStream_t st, const SasDeformGrad &q)
+{
+    if (q.n <= 0 || q.m <= 0 || q.blocks <= 0) return;
+    const bool lds = q.lds && sizeof(float) * kRow * (size_t)q.m <= SAS_SKIN_GRAD_LDS_MAX;
+    const size_t bytes = sas_deform_grad_lds_bytes(q.m, lds, q.staged != 0);
+    if (lds && q.staged) launch_deform_grad<true, true>(st, q, bytes);
+    else if (lds) launch_deform_grad<true, false>(st, q, bytes);
+    else if (q.staged) launch_deform_grad<false, true>(st, q, bytes);
+    else launch_deform_grad<false, false>(st, q, bytes);
+    hipLaunchKernelGGL(k_skin_nodes_grad, dim3((unsigned)((q.m + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, q);
 }

@@ -1,12 +1,18 @@
 """Host-side conveniences around the deformable splats ("Deformation"): where to put control nodes, and how to turn the
 moving vertices a physics engine publishes into the rigid per-node transforms ``Rasterizer.deform`` takes.  Plain numpy, float64 inside;
-nothing here touches the GPU.
+nothing here touches the GPU but ``fit_node_transforms``, through the rasterizer it is given.
 
     nodes = grid_nodes(bounds, spacing)                  # or farthest_nodes(points, m)
     r.bind_skin(nodes, k=4)
     r.deform(transforms_from_positions(nodes, moved_nodes))
+
+The other way round -- the node transforms from pictures -- is ``fit_node_transforms``: an optimiser on the host around
+``Rasterizer.render_backward`` and ``Rasterizer.deform_backward``, with ``rigidity`` as its regulariser.
 """
 from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -105,3 +111,200 @@ def check_node_transforms(node_transforms) -> np.ndarray:
     if mirrored.size:
         raise ValueError(f"node_transforms[{int(mirrored[0])}]: det R < 0 (a reflection is no rotation)")
     return a
+
+
+# ---- node transforms from pictures: how is the cloth bent ("Deformation": the adjoint) -----------------------------------------
+def _neighbour_table(nodes, neighbours: int) -> np.ndarray:
+    """``[M,k]`` indices of every node's ``k = min(neighbours, M - 1)`` nearest OTHER rest nodes, taken as ``transforms_from_positions`` takes
+    them (squared distances in float64, a stable sort: ties to the lower index)."""
+    a = np.asarray(nodes, np.float64).reshape(-1, 3)
+    M = a.shape[0]
+    k = int(min(max(neighbours, 0), M - 1))
+    if k <= 0:
+        return np.zeros((M, 0), np.int64)
+    d2 = ((a[:, None, :] - a[None, :, :]) ** 2).sum(axis=2)
+    order = np.argsort(d2, axis=1, kind="stable")[:, :k + 1]
+    out = np.zeros((M, k), np.int64)
+    for i in range(M):
+        out[i] = [j for j in order[i] if j != i][:k]
+    return out
+
+
+def rigidity(nodes, transforms, neighbours: int = 6):
+    """The embedded-deformation consistency term and its gradient: ``sum_i sum_{j in N(i)} |T_i(g_j) - T_j(g_j)|^2 / (M k)`` with ``g`` the
+    rest ``nodes [M,3]``, ``T_i(x) = R_i x + t_i`` the rows of ``transforms [M,3,4]`` and ``N(i)`` node i's ``k = min(neighbours, M - 1)``
+    nearest other nodes, taken as ``transforms_from_positions`` takes them: neighbouring nodes should agree on where each other goes.  Zero
+    for one rigid motion of all nodes.  Returns ``(value, d_transforms [M,3,4])``, float64, the gradient analytic, the twelve entries of
+    every node independent."""
+    g = np.asarray(nodes, np.float64).reshape(-1, 3)
+    T = np.asarray(transforms, np.float64).reshape(-1, 3, 4)
+    if T.shape[0] != g.shape[0]:
+        raise ValueError(f"rigidity: {g.shape[0]} nodes but {T.shape[0]} transforms")
+    M = g.shape[0]
+    nb = _neighbour_table(g, neighbours)
+    d = np.zeros_like(T)
+    k = nb.shape[1]
+    if k == 0:
+        return 0.0, d
+    R, t = T[:, :, :3], T[:, :, 3]
+    gj = g[nb]                                                                      # [M,k,3]
+    res = (np.einsum("mab,mkb->mka", R, gj) + t[:, None, :]) - (np.einsum("mkab,mkb->mka", R[nb], gj) + t[nb])
+    scale = 1.0 / (M * k)
+    value = float((res * res).sum() * scale)
+    dres = 2.0 * scale * res
+    d[:, :, :3] = np.einsum("mka,mkb->mab", dres, gj)
+    d[:, :, 3] = dres.sum(axis=1)
+    np.subtract.at(d[:, :, :3], nb.reshape(-1), np.einsum("mka,mkb->mkab", dres, gj).reshape(-1, 3, 3))
+    np.subtract.at(d[:, :, 3], nb.reshape(-1), dres.reshape(-1, 3))
+    return value, d
+
+
+def se3_exp_batch(xi) -> np.ndarray:
+    """``register.se3_exp`` of ``xi [M,6]`` twists ``(omega, v)`` at once: ``[M,4,4]`` float64."""
+    xi = np.asarray(xi, np.float64).reshape(-1, 6)
+    w, v = xi[:, :3], xi[:, 3:]
+    th = np.linalg.norm(w, axis=1)
+    small = th < 1e-8
+    ths = np.where(small, 1.0, th)
+    A = np.where(small, 1.0 - th * th / 6.0, np.sin(ths) / ths)
+    B = np.where(small, 0.5 - th * th / 24.0, (1.0 - np.cos(ths)) / (ths * ths))
+    C = np.where(small, 1.0 / 6.0 - th * th / 120.0, (ths - np.sin(ths)) / ths ** 3)
+    Wx = np.zeros((xi.shape[0], 3, 3))
+    Wx[:, 0, 1], Wx[:, 0, 2], Wx[:, 1, 0], Wx[:, 1, 2], Wx[:, 2, 0], Wx[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
+    W2 = Wx @ Wx
+    T = np.tile(np.eye(4), (xi.shape[0], 1, 1))
+    T[:, :3, :3] = np.eye(3) + A[:, None, None] * Wx + B[:, None, None] * W2
+    T[:, :3, 3] = np.einsum("mab,mb->ma", np.eye(3) + B[:, None, None] * Wx + C[:, None, None] * W2, v)
+    return T
+
+
+def twist_gradient_batch(d_transforms, transforms, pivots=None) -> np.ndarray:
+    """``register.twist_gradient`` of ``[M,3,4]`` gradients and transforms at once: the gradient ``[M,6]`` with respect to a twist at 0 that
+    left-multiplies each transform; with ``pivots [M,3]`` the twist turns about that point instead of the origin."""
+    G = np.asarray(d_transforms, np.float64).reshape(-1, 3, 4)
+    A = np.asarray(transforms, np.float64).reshape(-1, 3, 4)
+    out = np.zeros((G.shape[0], 6))
+    out[:, :3] = np.cross(A.transpose(0, 2, 1), G.transpose(0, 2, 1)).sum(axis=1)   # e_k . sum_c A[:, c] x G[:, c]
+    out[:, 3:] = G[:, :, 3]
+    if pivots is not None:
+        out[:, :3] += np.cross(out[:, 3:], np.asarray(pivots, np.float64).reshape(-1, 3))
+    return out
+
+
+@dataclass
+class NodeFit:
+    transforms: np.ndarray              # [M,3,4] float64, rows [R | t] of every node, rest -> current
+    loss: float                         # the last evaluation at full size: mean squared colour difference over the views + rigidity_weight * rigidity
+    history: List[Tuple[int, float]] = field(default_factory=list)   # (downsampling factor, loss) of every evaluation
+
+
+# Chosen on the CPU recovery case of tests/tools/skin_grad_ref.py (a 3x3 node grid under a bent sheet, two 64x48 views, 60 iterations): the run's
+# end error over the weights 0, 0.003, 0.01, 0.03 and 0.1 is tabulated there (RECOVER_TABLE); this is the weight with the smallest.
+RIGIDITY_WEIGHT = 0.01
+
+
+def fit_node_transforms(r, images, viewmats, Ks, W: int, H: int, nodes, iters: int = 200, masks=None, start=None,
+                        step: Tuple[float, float] = (0.01, 0.01), factors: Sequence[int] = (2, 1), rigidity_weight: float = RIGIDITY_WEIGHT,
+                        background=(0.0, 0.0, 0.0), loss_and_grad: Optional[Callable] = None) -> NodeFit:
+    """Fit the node transforms of the skin bound to rasterizer ``r`` so that its frames look like ``images [C,H,W,3]`` (float, 0..1) seen
+    from ``viewmats [C,4,4]`` (world -> camera) with ``Ks [C,3,3]``: given pictures of the cloth as it lies now, how is it bent.  ``nodes
+    [M,3]``: the rest positions the skin was bound with.  ``register.refine_group_poses``' scheme per node: Adam on an se(3) twist that
+    left-multiplies the node's transform about the node's CURRENT position ``R_i g_i + t_i``, coarse to fine over ``factors`` with the step
+    (``step``: radians, scene units) falling to a twentieth over each level.  The loss is the mean squared colour difference over ``masks
+    [C,H,W]`` averaged over the views, plus ``rigidity_weight * rigidity(nodes, T)``.  Every step is ``r.deform(T)``, one ``render`` +
+    ``prechain`` + ``render_backward(out=acc)`` per view, ONE ``deform_backward(acc)``, one ``[M,12]`` read-back and the twist update in
+    float64 numpy, vectorised over the nodes -- a host update meant for node counts in the hundreds, not for tens of thousands.  ``start
+    [M,3,4]``: where to begin (None: the identity, the rest pose).  ``r`` is left deformed at the result.  ``loss_and_grad(T [M,3,4], V, K,
+    w, h, target, mask) -> (loss, d_T [M,3,4])`` replaces the renderer for one view (tests run the same optimiser on a CPU reference;
+    ``r`` may then be None).
+
+    ``rigidity_weight``: the default was chosen on the CPU recovery case of the tests (a bent sheet under a 3x3 node grid, two views): of
+    the weights 0, 0.003, 0.01, 0.03 and 0.1 tried there it ends closest to the true deformed means (0.29 of the start after 60 iterations,
+    against 0.34 without the term and 0.39 at 0.1).  The colour loss starts at 2e-3 there: scale the weight with the loss of your scene.
+
+    Not fitted: skin weights, rest parameters, node positions; stretch and shear (the twist keeps every transform rigid)."""
+    import torch
+    import torch.nn.functional as Fn
+    from .rasterizer import _host
+    g = np.asarray(_host(nodes), np.float64).reshape(-1, 3)
+    M = g.shape[0]
+    Vs = np.asarray(_host(viewmats), np.float64).reshape(-1, 4, 4)
+    C = Vs.shape[0]
+    K0s = np.asarray(_host(Ks), np.float64).reshape(-1, 3, 3)
+    if K0s.shape[0] == 1 and C > 1:
+        K0s = np.repeat(K0s, C, axis=0)
+    if M < 1 or C < 1 or K0s.shape[0] != C:
+        raise ValueError(f"fit_node_transforms: need nodes [M,3], viewmats [C,4,4] and Ks [C,3,3], got {M} nodes, {C} views, {K0s.shape[0]} Ks")
+    imgs = torch.as_tensor(np.asarray(_host(images), np.float32)).reshape(C, H, W, 3)
+    ms = torch.ones((C, H, W), dtype=torch.float32) if masks is None else (torch.as_tensor(np.asarray(_host(masks))) != 0).to(torch.float32).reshape(C, H, W)
+    if start is None:
+        T = np.zeros((M, 3, 4))
+        T[:, 0, 0] = T[:, 1, 1] = T[:, 2, 2] = 1.0
+    else:
+        T = np.asarray(_host(start), np.float64).copy()
+        if T.shape != (M, 3, 4):
+            raise ValueError(f"fit_node_transforms: start must be [{M},3,4], got {list(T.shape)}")
+    if not float(rigidity_weight) >= 0.0:
+        raise ValueError(f"fit_node_transforms: rigidity_weight must be >= 0, got {rigidity_weight}")
+    if loss_and_grad is None and not getattr(r, "has_skin", False):
+        raise ValueError("fit_node_transforms: no skin is bound to the rasterizer: bind_skin(nodes) first")
+    key = None if loss_and_grad is not None else ("quats" if r.covariance_form == "quats" else "covariances")
+
+    def evaluate(T, Kcs, w, h, targets, tms):
+        """(loss, d_T [M,3,4]): the colour term averaged over the views plus the rigidity term."""
+        if loss_and_grad is not None:
+            parts = [loss_and_grad(T, Vs[v], Kcs[v], w, h, targets[v], tms[v]) for v in range(C)]
+            total, dT = sum(p[0] for p in parts) / C, sum(np.asarray(p[1], np.float64).reshape(M, 3, 4) for p in parts) / C
+        else:
+            from .autograd import prechain
+            r.deform(np.ascontiguousarray(T.astype(np.float32)))
+            acc, total = None, 0.0
+            for v in range(C):
+                V32, K32 = Vs[v].astype(np.float32), Kcs[v].astype(np.float32)
+                out = r.render(V32, K32, w, h, background)
+                rgb, alpha, depth = out["rgb"].clone(), out["alpha"].clone(), out["depth"].clone()
+                t, k = targets[v].to(rgb.device), tms[v].to(rgb.device)
+                scale = 1.0 / (3.0 * float(torch.clamp(k.sum(), min=1.0)) * C)
+                diff = k[..., None] * (rgb - t)
+                total += float((diff * (rgb - t)).sum()) * scale
+                g_acc, g_a, g_z = prechain(rgb, alpha, depth, background, 2.0 * scale * diff, None, None)
+                acc = r.render_backward(V32, K32, w, h, g_acc, g_a, g_z, want=("means", key), out=acc)
+            dT = r.deform_backward(acc).double().cpu().numpy()
+        if rigidity_weight > 0.0:
+            val, dreg = rigidity(g, T)
+            total, dT = total + rigidity_weight * val, dT + rigidity_weight * dreg
+        return total, dT
+
+    res = NodeFit(T, float("nan"))
+    per = max(1, int(iters) // max(1, len(factors)))
+    for f in factors:
+        w, h = max(1, W // f), max(1, H // f)
+        if f == 1:
+            targets, tms = imgs, ms
+        else:
+            # area average of the masked images, renormalised by the mask's coverage
+            cover = Fn.interpolate(ms[:, None], size=(h, w), mode="area")[:, 0]
+            targets = Fn.interpolate((imgs * ms[..., None]).permute(0, 3, 1, 2), size=(h, w), mode="area").permute(0, 2, 3, 1) / torch.clamp(cover, min=1e-6)[..., None]
+            tms = (cover > 0.5).to(torch.float32)
+        Kcs = K0s.copy()
+        Kcs[:, 0] *= w / W
+        Kcs[:, 1] *= h / H
+        m1, m2 = np.zeros((M, 6)), np.zeros((M, 6))
+        for it in range(per):
+            loss, dT = evaluate(T, Kcs, w, h, targets, tms)
+            res.history.append((int(f), loss))
+            piv = np.einsum("mab,mb->ma", T[:, :, :3], g) + T[:, :, 3]   # where every node is now
+            tw = twist_gradient_batch(dT, T, piv)
+            m1 = 0.9 * m1 + 0.1 * tw
+            m2 = 0.999 * m2 + 0.001 * tw * tw
+            hat = (m1 / (1 - 0.9 ** (it + 1))) / (np.sqrt(m2 / (1 - 0.999 ** (it + 1))) + 1e-12)
+            decay = 0.05 ** (it / max(1, per - 1))
+            E = se3_exp_batch(-np.concatenate([step[0] * decay * hat[:, :3], step[1] * decay * hat[:, 3:]], axis=1))
+            # about the pivot: x -> E (x - p) + p
+            Rn = E[:, :3, :3] @ T[:, :, :3]
+            tn = np.einsum("mab,mb->ma", E[:, :3, :3], T[:, :, 3] - piv) + E[:, :3, 3] + piv
+            T = np.concatenate([Rn, tn[:, :, None]], axis=2)
+    res.transforms = T
+    res.loss = evaluate(T, K0s, W, H, imgs, ms)[0]   # (leaves r deformed at the result)
+    res.history.append((1, res.loss))
+    return res

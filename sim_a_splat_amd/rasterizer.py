@@ -283,6 +283,7 @@ class Rasterizer:
         if "scene" in s:
             s |= {"features", "meshes"}
             self._skin_k = 0       # entries per Gaussian of the bound skin (set_skin; 0: none): a new scene has none
+            self._deform_m = 0     # nodes of the last deform since the bind (0: none): deform_backward's row count
         if s & {"features", "meshes"}:
             s.add("mesh_features")
         if "meshes" in s:          # vertex attributes sit beside the meshes (upload_mesh_vertex_attributes)
@@ -1428,6 +1429,7 @@ class Rasterizer:
         if rc != 0:
             self._check(rc, "sas_scene_skin")
         self._skin_k = int(i.shape[1])
+        self._deform_m = 0
         self._in_flight(True)
 
     @_locked
@@ -1450,7 +1452,7 @@ class Rasterizer:
         rc = self._L.sas_scene_skin(self._ctx, 0, None, None, self._stream())
         if rc != 0:
             self._check(rc, "sas_scene_skin")
-        self._skin_k = 0
+        self._skin_k = self._deform_m = 0
         self._in_flight(True)
 
     @_locked
@@ -1475,7 +1477,47 @@ class Rasterizer:
         rc = self._L.sas_scene_deform(self._ctx, m, _addr(t), self._stream())
         if rc != 0:
             self._check(rc, "sas_scene_deform")
+        if self.n:
+            self._deform_m = m
         self._in_flight(True)
+
+    @_locked
+    def deform_backward(self, grads: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """The adjoint of the last ``deform`` (sas_scene_deform_backward; DESIGN.md 3, "Deformation"): from the gradients of the DEFORMED
+        arrays to the gradient of the node transforms, ``[m,3,4]`` float32 on the device, rows ``[dR | dt]``, the twelve entries of every
+        node independent variables as ``viewmat``'s and ``group_poses``' are.  ``grads``: the dict ``render_backward`` returns or
+        accumulates through ``out=`` on the skinned scene; ``means`` and ``quats`` (or ``covariances``, as the scene was uploaded) are
+        read, contiguous float32 device tensors of the scene's shapes; a missing key is left out (not both: without an orientation
+        gradient the rotation path is skipped), other keys are ignored.  The adjoint is linear, so several views need no ``out=`` here:
+        accumulate ``render_backward(..., out=acc, want=("means", "quats"))`` over the views and call ``deform_backward(acc)`` once.
+        What is differentiated is ``deform`` as evaluated, with the live entries, the quaternion branch of every node, the signs and
+        the fallback as constants; the state is the node records ``deform`` left on the device, not the caller's tensor.  A node no live
+        entry names gets an exact zero row, zero gradients give exact zeros; otherwise the sums are float atomics and vary in their
+        last bits from run to run.  ``SasError`` without a skin or without a ``deform`` since the bind.  Only enqueues, on the current
+        stream."""
+        if not isinstance(grads, dict):
+            raise ValueError("deform_backward: grads must be a dict as render_backward returns it")
+        if not self.has_skin:
+            raise SasError("deform_backward: no skin is bound")
+        if self._deform_m <= 0:
+            raise SasError("deform_backward: no deform since the skin was bound")
+        shapes = self._scene_shapes()
+        other = "covariances" if self.covariance_form == "quats" else "quats"
+        if grads.get(other) is not None:
+            raise ValueError(f"deform_backward: the scene was uploaded as {'quats' if other == 'covariances' else 'covariances'}: drop grads[{other!r}]")
+        ptrs = {}
+        for k in ("means", "quats", "covariances"):
+            t = grads.get(k)
+            if t is not None and not self._is_mine(t, torch.float32, shapes[k]):
+                raise ValueError(f"grads[{k!r}] must be a contiguous float32 tensor {shapes[k]} on {self.device}")
+            ptrs[k] = None if t is None else t.data_ptr()
+        if all(p is None for p in ptrs.values()):
+            raise ValueError("deform_backward: grads holds neither means nor the orientation gradient")
+        out = torch.empty((self._deform_m, 3, 4), dtype=torch.float32, device=self.device)
+        rc = self._L.sas_scene_deform_backward(self._ctx, ptrs["means"], ptrs["quats"], ptrs["covariances"], _addr(out), self._stream())
+        if rc != 0:
+            self._check(rc, "sas_scene_deform_backward")
+        return out
 
     @_locked
     def bind_skin(self, nodes: ArrayLike, k: int = 4, sigma: Optional[float] = None, max_distance: float = math.inf,

@@ -255,6 +255,26 @@ class SplatScene:
             self._sync()
             self._raster.deform(node_transforms)
 
+    def fit_deformation(self, images, height: int, width: int, cam_poses, fov: Optional[float] = None, iters: int = 200, masks=None, **kw):
+        """How is the deformable group bent, given these pictures: ``deform.fit_node_transforms`` on the nodes of ``bind_deformable``, in the
+        handle's local frame, so that the scene's frames from ``cam_poses [(wxyz, position), ...]`` look like ``images [C,H,W,3]`` (uint8,
+        or float 0..1) over ``masks [C,H,W]``, with the views of ``get_renders``.  ``kw`` goes to ``fit_node_transforms`` (``start``,
+        ``step``, ``factors``, ``rigidity_weight``).  The scene is left deformed at the result, which the next ``get_render*`` shows; returns
+        the ``NodeFit``.  The lock is held throughout; a scene with meshes is refused (the backward pass does not take occlusion by
+        meshes)."""
+        from .deform import fit_node_transforms
+        V, K = self._views_and_Ks(int(height), int(width), *_camera_arrays(cam_poses), self._camera_or(fov=fov)[2])
+        img = np.asarray(images.detach().cpu().numpy() if isinstance(images, torch.Tensor) else images)
+        img = img.astype(np.float32) / 255.0 if img.dtype == np.uint8 else img.astype(np.float32)
+        with self.lock:
+            if self._deformable is None:
+                raise RuntimeError("bind_deformable first")
+            if self._meshes:
+                raise RuntimeError("fit_deformation: the scene holds meshes, which the backward pass does not take")
+            self._sync()
+            return fit_node_transforms(self._raster, img, V, K, int(width), int(height), self._deformable[1], iters=iters, masks=masks,
+                                       background=self.background, **kw)
+
     # -- internals ---------------------------------------------------------------------------
     def _sync(self) -> None:
         if not self._uploaded:
