@@ -829,7 +829,7 @@ int sas_knn_last_counts(sas_ctx *ctx, int64_t *out, int n);
  * sas_scene_skin -- bind a skin to the resident scene: indices [N,k] int32 and weights [N,k] float32, 1 <= k <= 8, DEVICE arrays in the
  * caller's order.  The first bind snapshots the means, orientations and scales (or covariances) as the REST pose; a bind over a skin
  * replaces the entries and keeps the rest pose.  k == 0 (indices and weights ignored) clears the skin: the rest pose returns bit for
- * bit.  While a skin is bound sas_scene_adam_step, sas_scene_densify, sas_scene_mcmc_refine, sas_scene_mcmc_noise and
+ * bit (as sas_scene_adam_step_rest has stepped it, if it has).  While a skin is bound sas_scene_adam_step, sas_scene_densify, sas_scene_mcmc_refine, sas_scene_mcmc_noise and
  * sas_scene_reset_opacity are SAS_ERR_INVALID ("scene is skinned") and change nothing; everything that reads the scene sees the deformed
  * Gaussians; sas_scene_upload drops the skin.  Enqueued on `stream`; frames in flight are completed first.
  * sas_scene_skin_read -- the entries back in the caller's order, [N,k] each with the k of the bind, HOST or DEVICE.  Blocking.
@@ -862,13 +862,43 @@ int sas_knn_last_counts(sas_ctx *ctx, int64_t *out, int n);
  * bound (a rebind or a clear resets that), for all three gradients NULL, an orientation gradient of the wrong form, d_node_Rt NULL.
  * SAS_SKIN_GRAD_LDS=bytes (0..131072, the default) is the size up to which the per-node sums (64 B each) are kept in LDS by every
  * workgroup; SAS_SKIN_GRAD_STAGED=0/1 forces the form of the adds.  Both change the order of the sums only.
+ *
+ * sas_scene_deform_backward_rest -- the adjoint of the LAST sas_scene_deform to the REST arrays, the Gaussians that are stored: the same
+ * inputs as sas_scene_deform_backward, under the same form rule, to d_rest_means [N,3] and d_rest_quats [N,4] or d_rest_cov6 [N,6], float32
+ * DEVICE arrays in the caller's order.  The call ACCUMULATES: out[i] += the gradient, so that the sum over time steps, each with its own
+ * deformation, is taken here; zero the arrays before the first.  An output is given exactly where its input is (d_rest_means with
+ * d_means, and so on); no output may overlap an input or another output.  With the forward's decisions as constants:
+ *   d_mean   = g + (sum_j w_j ((R_j^T g) - g)) / sum_j w_j, over the live entries in entry order
+ *   d_quat   = conj(q_b) (x) h (the transpose of the left product by q_b), or dSigma = R(q_b)^T G R(q_b) for a covariance scene, G the
+ *              symmetric matrix of d_cov6 in sas_render_backward's convention, written back in that convention
+ * A Gaussian without a live entry has its gradient passed through bit for bit; with flags & SAS_DEFORM_REST_BOUND_ONLY it adds nothing
+ * (for skins bound to one group: the static rest of the scene then gets no step from a fit of the deformable group).  Every output depends
+ * on its own input alone, and an all-zero gradient adds exact zeros: SAS_ADAM_VISIBLE_ONLY keeps its meaning.  No atomics: the same inputs
+ * give the same bits on every run and under every SAS_SKIN_LDS.  Opacity, colour and scale gradients are untouched by a deformation: they
+ * are the rest scene's as sas_render_backward wrote them.  It only ENQUEUES on `stream`, behind the deform; no host synchronisation.
+ * SAS_ERR_NO_SCENE before an upload; SAS_ERR_INVALID without a skin, without a sas_scene_deform since the skin was bound, for unknown
+ * flags, all three gradients NULL, an orientation gradient of the wrong form, an output without its input or an input without its
+ * output, or overlapping arrays.
+ *
+ * sas_scene_adam_step_rest -- sas_scene_adam_step on the REST scene of a bound skin: the same arguments, kernel, variables and optimiser
+ * state (a group stepped here for the first time starts as it would there; the moments survive clearing the skin), with gradients with
+ * respect to the rest arrays (sas_scene_deform_backward_rest's sums, and sas_render_backward's opacity, colour and scale gradients as
+ * they are).  The rest planes are stepped; colours are no part of the rest snapshot and step where they live.  Then the last deformation is
+ * applied again from the node records on the device -- without a sas_scene_deform since the bind the rest planes are copied -- so every
+ * reader sees the stepped scene in its current bend, and clearing the skin returns the STEPPED rest scene.  The last frame is invalidated
+ * as sas_scene_deform does.  SAS_ERR_INVALID without a skin; sas_scene_adam_step itself stays refused under one.
  */
+#define SAS_DEFORM_REST_BOUND_ONLY 1u
 int sas_knn_cross(sas_ctx *ctx, int64_t n, const float *points, int64_t m, const float *nodes, int k, float max_distance,
                   float *dist2_out, int32_t *index_out_or_null, void *stream);
 int sas_scene_skin(sas_ctx *ctx, int k, const int32_t *indices, const float *weights, void *stream);
 int sas_scene_skin_read(sas_ctx *ctx, int32_t *indices_out, float *weights_out);
 int sas_scene_deform(sas_ctx *ctx, int m, const float *node_Rt, void *stream);
 int sas_scene_deform_backward(sas_ctx *ctx, const float *d_means, const float *d_quats, const float *d_cov6, float *d_node_Rt, void *stream);
+int sas_scene_deform_backward_rest(sas_ctx *ctx, const float *d_means, const float *d_quats, const float *d_cov6, float *d_rest_means,
+                                   float *d_rest_quats, float *d_rest_cov6, unsigned flags, void *stream);
+int sas_scene_adam_step_rest(sas_ctx *ctx, const sas_adam_config *cfg, const float *d_means, const float *d_opacities, const float *d_sh,
+                             const float *d_quats, const float *d_scales, void *stream);
 
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical

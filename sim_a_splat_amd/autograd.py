@@ -9,7 +9,7 @@ their gradients have somewhere to go -- after an optimiser step of the caller's 
 (``fit.fit_scene`` is the loop).  The view matrix is an argument of every call and needs no upload.
 
 The poses of the splat groups are a variable too (``group_poses=``, up to 32 groups per frame), and so are the node transforms of a
-deformable scene (``node_transforms=``).  Not differentiated: K, meshes (a
+deformable scene (``node_transforms=``), whose REST arrays ``params`` names with ``rest_params=True``.  Not differentiated: K, meshes (a
 scene with meshes is refused), joint angles, and every decision of the renderer (culls, clamps, the alpha and transmittance
 thresholds), which are constants of the derivative.  The per-Gaussian sums are float atomics: gradients
 vary in their last bits from run to run.
@@ -48,7 +48,7 @@ def prechain(rgb: torch.Tensor, alpha: torch.Tensor, depth: torch.Tensor, backgr
 
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, r, viewmat, K, W, H, background, keys, pose_groups, group_poses, node_transforms, *tensors):
+    def forward(ctx, r, viewmat, K, W, H, background, keys, pose_groups, group_poses, node_transforms, rest_params, *tensors):
         V = np.eye(4, dtype=np.float32)
         V[:viewmat.shape[0]] = viewmat.detach().cpu().numpy().astype(np.float32)
         if group_poses is not None:   # the frame is rendered under these poses, and they stay set
@@ -61,16 +61,16 @@ class _Render(torch.autograd.Function):
         pmeta = None if group_poses is None else (group_poses.device, group_poses.dtype, tuple(group_poses.shape))
         nmeta = None if node_transforms is None else (node_transforms.device, node_transforms.dtype, tuple(node_transforms.shape))
         ctx.call = (r, V, K, W, H, background, keys, tuple(viewmat.shape), viewmat.device, viewmat.dtype,
-                    [(t.device, t.dtype, tuple(t.shape)) for t in tensors], pose_groups, pmeta, nmeta)
+                    [(t.device, t.dtype, tuple(t.shape)) for t in tensors], pose_groups, pmeta, nmeta, rest_params)
         return rgb, alpha, depth
 
     @staticmethod
     def backward(ctx, g_rgb, g_alpha, g_depth):
         rgb, alpha, depth = ctx.saved_tensors
-        r, V, K, W, H, background, keys, vshape, vdev, vdt, metas, pose_groups, pmeta, nmeta = ctx.call
+        r, V, K, W, H, background, keys, vshape, vdev, vdt, metas, pose_groups, pmeta, nmeta, rest_params = ctx.call
         g_acc, g_a, g_z = prechain(rgb, alpha, depth, background, g_rgb, g_alpha, g_depth)
         # only what some input needs: the projection's backward neither reads nor writes the rest
-        needs = ctx.needs_input_grad[10:]
+        needs = ctx.needs_input_grad[11:]
         need_poses = pmeta is not None and ctx.needs_input_grad[8]
         need_nodes = nmeta is not None and ctx.needs_input_grad[9]
         want = (("viewmat",) if ctx.needs_input_grad[1] else ()) + tuple(k for k, need in zip(keys, needs) if need) + \
@@ -78,7 +78,7 @@ class _Render(torch.autograd.Function):
         if need_nodes:   # the deformed means and orientations are what the nodes move
             want += tuple(k for k in ("means", "quats" if r.covariance_form == "quats" else "covariances") if k not in want)
         if not want:
-            return (None,) * (10 + len(keys))
+            return (None,) * (11 + len(keys))
         res = r.render_backward(V, K, W, H, g_acc, g_a, g_z, want=want, pose_groups=pose_groups if need_poses else None)
         grads = [None]
         if ctx.needs_input_grad[1]:
@@ -95,9 +95,13 @@ class _Render(torch.autograd.Function):
         if need_nodes:
             ndev, ndt, nshape = nmeta
             gn = r.deform_backward(res).reshape(nshape).to(device=ndev, dtype=ndt)
+        if rest_params:   # params names the REST arrays: what the deformation moved goes through its adjoint, the others are theirs as they are
+            moved = {k: res[k] for k, need in zip(keys, needs) if need and k in ("means", "quats", "covariances")}
+            if moved:
+                res = dict(res, **r.deform_backward_rest(moved))
         for k, (dev, dt, shape), need in zip(keys, metas, needs):
             grads.append(res[k].reshape(shape).to(device=dev, dtype=dt) if need else None)
-        return (None, grads[0], None, None, None, None, None, None, gp, gn, *grads[1:])
+        return (None, grads[0], None, None, None, None, None, None, gp, gn, None, *grads[1:])
 
 
 class _PhotometricLoss(torch.autograd.Function):
@@ -126,7 +130,8 @@ def photometric_loss(r, rgb: torch.Tensor, target, mask=None, lambda_dssim: floa
 
 def render_differentiable(r, viewmat: torch.Tensor, K, width: int, height: int, params: Optional[Dict[str, torch.Tensor]] = None,
                           background: Optional[Sequence[float]] = None, group_poses: Optional[torch.Tensor] = None,
-                          pose_groups: Optional[Sequence[int]] = None, node_transforms: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                          pose_groups: Optional[Sequence[int]] = None, node_transforms: Optional[torch.Tensor] = None,
+                          rest_params: bool = False) -> Dict[str, torch.Tensor]:
     """One frame of rasterizer ``r`` -- ``rgb [H,W,3]``, ``alpha [H,W,1]``, ``depth [H,W,1]`` on its device -- through which gradients
     flow to ``viewmat`` (``[4,4]`` or ``[3,4]``, world to camera; its twelve upper entries are independent variables) and to those
     tensors of ``params`` that require grad.  ``params`` maps ``means``, ``opacities``, ``colors``, ``quats``, ``scales`` or
@@ -141,7 +146,12 @@ def render_differentiable(r, viewmat: torch.Tensor, K, width: int, height: int, 
     ``node_transforms``: ``[m,3,4]``, rows ``[R | t]`` of the nodes of the skin bound to ``r`` (``Rasterizer.bind_skin``).  A value like
     ``group_poses``: its detached float32 copy goes through ``r.deform`` before the frame (and stays set), and its gradient comes back
     in its shape, device and dtype, twelve independent entries per node (``Rasterizer.deform_backward``).  It combines with
-    ``viewmat``, ``group_poses`` and ``params`` in one call; under a skin the gradients of ``params`` are those of the DEFORMED arrays."""
+    ``viewmat``, ``group_poses`` and ``params`` in one call; under a skin the gradients of ``params`` are those of the DEFORMED arrays.
+
+    ``rest_params=True``: ``params`` names the REST arrays of the skinned scene, and the ``means`` / ``quats`` / ``covariances``
+    gradients go through the deformation's adjoint (``Rasterizer.deform_backward_rest``) -- the frame is a function of the Gaussians
+    that are stored; ``opacities``, ``colors`` and ``scales`` are untouched by a deformation.  It needs a skin and a deformation
+    (``node_transforms=``, or ``r.deform`` before the call)."""
     bg = (0.0, 0.0, 0.0) if background is None else tuple(float(v) for v in background)
     params = params or {}
     unknown = [k for k in params if k not in PARAM_KEYS]
@@ -163,6 +173,8 @@ def render_differentiable(r, viewmat: torch.Tensor, K, width: int, height: int, 
         raise ValueError("render_differentiable: pose_groups without group_poses")
     if node_transforms is not None and (node_transforms.dim() != 3 or tuple(node_transforms.shape[1:]) != (3, 4)):
         raise ValueError(f"render_differentiable: node_transforms must be [m,3,4], got {tuple(node_transforms.shape)}")
-    rgb, alpha, depth = _Render.apply(r, viewmat, Kc, int(width), int(height), bg, keys, sel, group_poses, node_transforms,
+    if rest_params and not r.has_skin:
+        raise ValueError("render_differentiable: rest_params=True needs a skin bound to the rasterizer (bind_skin / set_skin)")
+    rgb, alpha, depth = _Render.apply(r, viewmat, Kc, int(width), int(height), bg, keys, sel, group_poses, node_transforms, bool(rest_params),
                                       *[params[k] for k in keys])
     return dict(rgb=rgb, alpha=alpha, depth=depth)

@@ -2576,15 +2576,22 @@ int sas_render_backward_poses(sas_ctx *c, const float *viewmat, const float *K, 
                            d_sh, d_quats, d_scales, d_cov6, d_viewmat, n_sel, sel, d_group_poses, stream);
 }
 
-// The fused Adam step on the resident planes (k_adam_scene).  Host work: validation, the first-step allocations, one launch, one event.
-int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_means, const float *d_opacities, const float *d_sh,
-                        const float *d_quats, const float *d_scales, void *stream)
+static int redeform(sas_ctx *c, hipStream_t st);
+
+// The fused Adam step (k_adam_scene) behind sas_scene_adam_step and sas_scene_adam_step_rest.  Host work: validation, the first-step
+// allocations, one launch, one event.  rest: the planes stepped are the skin's rest planes (colours step where they live: they are no part of
+// the snapshot), and the last deformation is applied to the stepped rest planes again.
+static int adam_step(sas_ctx *c, const char *who, bool rest, const sas_adam_config *cfg, const float *d_means, const float *d_opacities,
+                     const float *d_sh, const float *d_quats, const float *d_scales, void *stream)
 {
-    const char *who = "sas_scene_adam_step";
     if (!c) return SAS_ERR_INVALID;
     if (!cfg) return fail(c, SAS_ERR_INVALID, "%s: cfg is NULL", who);
     if (const int rc = need_scene(c, who)) return rc;
-    if (const int rc = need_unskinned(c, who)) return rc;
+    if (!rest) {
+        if (const int rc = need_unskinned(c, who)) return rc;
+    } else if (!c->skin.bound()) {
+        return fail(c, SAS_ERR_INVALID, "%s: no skin is bound: the unskinned scene steps through sas_scene_adam_step", who);
+    }
     if (!d_means && !d_opacities && !d_sh && !d_quats && !d_scales) return fail(c, SAS_ERR_INVALID, "%s: every gradient is NULL", who);
     if (cfg->step < 1) return fail(c, SAS_ERR_INVALID, "%s: step %d < 1 (the count is 1-based)", who, cfg->step);
     for (const float lr : {cfg->lr_means, cfg->lr_opacities, cfg->lr_sh_dc, cfg->lr_sh_rest, cfg->lr_quats, cfg->lr_scales})
@@ -2616,12 +2623,15 @@ int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_m
                 if (const int rc = a.alloc(c, k, sc.n_pad, planes, st, Adam::rows[k].zeroed)) return rc;
     }
     if (fresh[Adam::OPACITIES] || fresh[Adam::SCALES]) {
-        sas_launch_adam_init(st, sc.n, sc.g0, sc.g2, a.view(fresh));
+        sas_launch_adam_init(st, sc.n, rest ? (const float4 *)c->skin.rest0.p : sc.g0, rest ? (const float4 *)c->skin.rest2.p : sc.g2, a.view(fresh));
         HIP_TRY(c, hipGetLastError());
     }
     for (int g = 0; g < Adam::GROUPS; ++g) a.on[g] = a.on[g] || fresh[g];
     SasAdam k{};
-    k.g0 = (float4 *)c->planes.g0.p; k.g1 = (float4 *)c->planes.g1.p; k.g2 = (float4 *)c->planes.g2.p; k.col = (float4 *)c->planes.col.p;
+    k.g0 = (float4 *)(rest ? c->skin.rest0.p : c->planes.g0.p);
+    k.g1 = (float4 *)(rest ? c->skin.rest1.p : c->planes.g1.p);
+    k.g2 = (float4 *)(rest ? c->skin.rest2.p : c->planes.g2.p);
+    k.col = (float4 *)c->planes.col.p;
     k.perm = sc.perm;
     k.n = sc.n; k.n_pad = sc.n_pad;
     k.coeff_floats = coeff_floats; k.planes = planes;
@@ -2640,11 +2650,27 @@ int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_m
     k.eps = cfg->eps;
     k.visible_only = (cfg->flags & SAS_ADAM_VISIBLE_ONLY) != 0;
     k.sh_aligned = coeff_floats % 4 == 0 && ((uintptr_t)d_sh & 15u) == 0;
+    if (rest && c->skin_done.h) HIP_TRY(c, hipStreamWaitEvent(st, c->skin_done, 0));   // (the snapshot and the records were made on a caller's stream)
     sas_launch_adam_scene(st, k);
     HIP_TRY(c, hipGetLastError());
-    if (const int rc = slots_wait_for(c, c->adam_done, st)) return rc;
+    if (rest)
+        if (const int rc = redeform(c, st)) return rc;   // the live planes: the stepped rest scene in its current bend
+    if (const int rc = slots_wait_for(c, rest ? c->skin_done : c->adam_done, st)) return rc;
     scene_changed(c, Changed::Values);   // the last frame showed the scene before the step
     return SAS_OK;
+}
+
+int sas_scene_adam_step(sas_ctx *c, const sas_adam_config *cfg, const float *d_means, const float *d_opacities, const float *d_sh,
+                        const float *d_quats, const float *d_scales, void *stream)
+{
+    return adam_step(c, "sas_scene_adam_step", false, cfg, d_means, d_opacities, d_sh, d_quats, d_scales, stream);
+}
+
+// ... on the REST planes of a skinned scene: the same kernel, the same optimiser state.
+int sas_scene_adam_step_rest(sas_ctx *c, const sas_adam_config *cfg, const float *d_means, const float *d_opacities, const float *d_sh,
+                             const float *d_quats, const float *d_scales, void *stream)
+{
+    return adam_step(c, "sas_scene_adam_step_rest", true, cfg, d_means, d_opacities, d_sh, d_quats, d_scales, stream);
 }
 
 // The photometric loss and its gradient (k_loss_stats, k_loss_tail, k_loss_grad).  Host work: validation, the scratch, the window, the launches.
@@ -3161,6 +3187,39 @@ int sas_scene_skin_read(sas_ctx *c, int32_t *indices_out, float *weights_out)
     return SAS_OK;
 }
 
+// k_deform's call on the bound skin with m node records: rest planes -> live planes.
+static SasDeform deform_call(sas_ctx *c, int m)
+{
+    const Skin &sk = c->skin;
+    const SasScene &sc = c->scene;
+    SasDeform q{};
+    q.nodes = (SasSkinNode *)sk.nodes.p;
+    q.r0 = (const float4 *)sk.rest0.p; q.r1 = (const float4 *)sk.rest1.p; q.r2 = (const float4 *)sk.rest2.p;
+    q.g0 = (float4 *)c->planes.g0.p; q.g1 = (float4 *)c->planes.g1.p; q.g2 = (float4 *)c->planes.g2.p;
+    q.idx = (const int4 *)sk.idx.p; q.w = (const float4 *)sk.w.p;
+    q.n = sc.n; q.n_pad = sc.n_pad;
+    q.m = m; q.kp = sk.kp(); q.cov_mode = sc.cov_mode;
+    q.lds = sizeof(SasSkinNode) * (size_t)m <= (size_t)c->skin_lds;
+    return q;
+}
+
+// The live planes again from rest planes that have changed (sas_scene_adam_step_rest): the last deformation from the node records it left on
+// the device (k_deform alone), or, without a sas_scene_deform since the bind, the rest planes as they are.
+static int redeform(sas_ctx *c, hipStream_t st)
+{
+    const Skin &sk = c->skin;
+    if (sk.m > 0) {
+        sas_launch_deform_planes(st, deform_call(c, sk.m));
+        HIP_TRY(c, hipGetLastError());
+        return SAS_OK;
+    }
+    const Planes &pl = c->planes;
+    const size_t plane = sizeof(float4) * (size_t)(pl.n_pad > 0 ? pl.n_pad : 64);
+    const DevBuf *rest[3] = {&sk.rest0, &sk.rest1, &sk.rest2}, *live[3] = {&pl.g0, &pl.g1, &pl.g2};
+    for (int p = 0; p < 3; ++p) HIP_TRY(c, hipMemcpyAsync(live[p]->p, rest[p]->p, plane, hipMemcpyDeviceToDevice, st));
+    return SAS_OK;
+}
+
 // Move the skinned scene to the nodes' transforms (k_skin_nodes, k_deform): always rest -> current.  Host work: validation, the node
 // records' buffer (grown by the first call at a larger m), two launches, one event.
 int sas_scene_deform(sas_ctx *c, int m, const float *node_Rt, void *stream)
@@ -3177,15 +3236,8 @@ int sas_scene_deform(sas_ctx *c, int m, const float *node_Rt, void *stream)
     if (sc.n <= 0) return SAS_OK;
     if (const int rc = ensure(c, sk.nodes, sizeof(SasSkinNode) * (size_t)m)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    SasDeform q{};
+    SasDeform q = deform_call(c, m);
     q.node_Rt = node_Rt;
-    q.nodes = (SasSkinNode *)sk.nodes.p;
-    q.r0 = (const float4 *)sk.rest0.p; q.r1 = (const float4 *)sk.rest1.p; q.r2 = (const float4 *)sk.rest2.p;
-    q.g0 = (float4 *)c->planes.g0.p; q.g1 = (float4 *)c->planes.g1.p; q.g2 = (float4 *)c->planes.g2.p;
-    q.idx = (const int4 *)sk.idx.p; q.w = (const float4 *)sk.w.p;
-    q.n = sc.n; q.n_pad = sc.n_pad;
-    q.m = m; q.kp = sk.kp(); q.cov_mode = sc.cov_mode;
-    q.lds = sizeof(SasSkinNode) * (size_t)m <= (size_t)c->skin_lds;
     sas_launch_deform(st, q);
     HIP_TRY(c, hipGetLastError());
     sk.m = m;
@@ -3242,6 +3294,56 @@ int sas_scene_deform_backward(sas_ctx *c, const float *d_means, const float *d_q
     sas_launch_deform_grad(st, q);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->skin_grad_done, st));
+    return SAS_OK;
+}
+
+// The adjoint of the last sas_scene_deform to the REST arrays (k_deform_rest_grad), added to the caller's arrays.  Host work: validation, one
+// stream wait, one launch.  No host synchronisation.
+int sas_scene_deform_backward_rest(sas_ctx *c, const float *d_means, const float *d_quats, const float *d_cov6, float *d_rest_means,
+                                   float *d_rest_quats, float *d_rest_cov6, unsigned flags, void *stream)
+{
+    const char *who = "sas_scene_deform_backward_rest";
+    if (const int rc = need_scene(c, who)) return rc;
+    const Skin &sk = c->skin;
+    if (!sk.bound()) return fail(c, SAS_ERR_INVALID, "%s: no skin is bound: sas_scene_skin first", who);
+    if (sk.m <= 0) return fail(c, SAS_ERR_INVALID, "%s: no sas_scene_deform since the skin was bound", who);
+    if (flags & ~SAS_DEFORM_REST_BOUND_ONLY) return fail(c, SAS_ERR_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (!d_means && !d_quats && !d_cov6) return fail(c, SAS_ERR_INVALID, "%s: d_means, d_quats and d_cov6 are all NULL", who);
+    const SasScene &sc = c->scene;
+    if (sc.cov_mode ? d_quats != nullptr : d_cov6 != nullptr)
+        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as %s: %s must be NULL", who, sc.cov_mode ? "covariances" : "quaternions",
+                    sc.cov_mode ? "d_quats" : "d_cov6");
+    struct Pair { const char *name; const float *in; float *out; int width; };
+    const Pair pairs[3] = {{"means", d_means, d_rest_means, 3}, {"quats", d_quats, d_rest_quats, 4}, {"cov6", d_cov6, d_rest_cov6, 6}};
+    for (const Pair &p : pairs)
+        if ((p.in != nullptr) != (p.out != nullptr))
+            return fail(c, SAS_ERR_INVALID, "%s: d_%s and d_rest_%s go together: one is NULL and the other is not", who, p.name, p.name);
+    // every lane reads its inputs and adds to its outputs while other lanes do the same: no output may overlap an input or another output
+    auto overlap = [&](const float *a, int wa, const float *b, int wb) {
+        const uintptr_t a0 = (uintptr_t)a, a1 = a0 + sizeof(float) * (size_t)wa * (size_t)sc.n, b0 = (uintptr_t)b, b1 = b0 + sizeof(float) * (size_t)wb * (size_t)sc.n;
+        return a && b && a0 < b1 && b0 < a1;
+    };
+    for (int o = 0; o < 3; ++o)
+        for (int k = 0; k < 3; ++k)
+            if (overlap(pairs[o].out, pairs[o].width, pairs[k].in, pairs[k].width) ||
+                (k != o && overlap(pairs[o].out, pairs[o].width, pairs[k].out, pairs[k].width)))
+                return fail(c, SAS_ERR_INVALID, "%s: d_rest_%s overlaps d_%s%s: the call adds to its outputs, in place it has no meaning", who,
+                            pairs[o].name, overlap(pairs[o].out, pairs[o].width, pairs[k].in, pairs[k].width) ? "" : "rest_", pairs[k].name);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    SasDeformRestGrad q{};
+    q.perm = sc.perm;
+    q.d_means = d_means; q.d_quats = d_quats; q.d_cov6 = d_cov6;
+    q.nodes = (const SasSkinNode *)sk.nodes.p;
+    q.idx = (const int4 *)sk.idx.p; q.w = (const float4 *)sk.w.p;
+    q.n = sc.n; q.n_pad = sc.n_pad;
+    q.m = sk.m; q.kp = sk.kp();
+    q.lds = sizeof(SasSkinNode) * (size_t)sk.m <= (size_t)c->skin_lds;
+    q.bound_only = (flags & SAS_DEFORM_REST_BOUND_ONLY) != 0;
+    q.o_means = d_rest_means; q.o_quats = d_rest_quats; q.o_cov6 = d_rest_cov6;
+    if (c->skin_done.h) HIP_TRY(c, hipStreamWaitEvent(st, c->skin_done, 0));   // behind the deformation whose records are read
+    sas_launch_deform_rest_grad(st, q);
+    HIP_TRY(c, hipGetLastError());
     return SAS_OK;
 }
 

@@ -824,6 +824,25 @@ struct SasDeform {
     int lds;                     // 1: the node records pass through LDS (m * 64 B within the budget)
 };
 void sas_launch_deform(hipStream_t st, const SasDeform &q);
+void sas_launch_deform_planes(hipStream_t st, const SasDeform &q);   // k_deform alone, on the records q.nodes holds already (node_Rt unused)
+// The adjoint to the REST arrays (sas_scene_deform_backward_rest): per-Gaussian gradients of the deformed arrays -> of the rest arrays, added
+struct SasDeformRestGrad {
+    const int *perm;             // [n] slot -> caller's index
+    const float *d_means;        // [n,3] caller's order, or nullptr
+    const float *d_quats;        // [n,4] or nullptr (quaternion scenes)
+    const float *d_cov6;         // [n,6] or nullptr (covariance scenes)
+    const SasSkinNode *nodes;    // [m] the last sas_scene_deform's records
+    const int4 *idx;
+    const float4 *w;
+    long long n, n_pad;
+    int m, kp;
+    int lds;                     // 1: the node records pass through LDS (m * 64 B within the budget)
+    int bound_only;              // 1: a Gaussian without a live entry adds nothing (0: its gradient passes through)
+    float *o_means;              // [n,3] added to; given exactly where d_means is
+    float *o_quats;              // [n,4]
+    float *o_cov6;               // [n,6]
+};
+void sas_launch_deform_rest_grad(hipStream_t st, const SasDeformRestGrad &q);
 // The adjoint of the two (sas_scene_deform_backward): per-Gaussian gradients -> per-node [R | t] gradients
 #define SAS_SKIN_GRAD_ROW 16              // floats a live entry adds to its node's accumulator row: dt 3, the mean path's dR 9, dq 4
 #define SAS_SKIN_GRAD_LDS_MAX 131072      // accumulator bytes k_deform_grad keeps in LDS at most (2048 nodes): the SAS_SKIN_GRAD_LDS budget's ceiling

@@ -53,6 +53,20 @@
 // Residency: 60 to 70 VGPRs (7 or 8 waves per SIMD by registers, no spills); what bounds it is the LDS, all of it dynamic: 17 408 B of stage and
 // m * 64 B of sums -- 4 workgroups per CU up to m = 368 staged, 2 at m = 1024 and 1 at m = 2048 with every lane adding its own row.
 // Float atomics: the sums depend on arrival order and vary in their last bits from run to run; zero rows and zero upstream give exact zeros.
+//
+// The adjoint to the REST arrays (sas_scene_deform_backward_rest): the same gradients of the deformed arrays -> gradients of the Gaussians that are
+// stored, ADDED to the caller's arrays (the deformation differs per time step: the sum over time steps is taken here).
+//   k_deform_rest_grad<LDS,KP>  one lane per slot, k_deform's shape: the gradients are gathered at perm[slot] as k_adam_scene gathers them and the
+//                   results are added at the same caller's index; the skin planes and the node records as k_deform reads them (LDS up to
+//                   SAS_SKIN_LDS_BYTES, else global: the same text on the same values, the same bits).  The forward is linear in each rest array,
+//                   so no rest plane is read.  With the forward's decisions as constants (live entries, signs, normalisation, fallback):
+//                     mean:       d_m = g + (sum_j w_j ((R_j^T g) - g)) / W, in entry order; R^T g = (r0 gx + r1 gy) + r2 gz by columns
+//                     quaternion: d_q_rest = conj(q_b) (x) h, the transpose of the left product by q_b; q_b recomputed as k_deform does
+//                     covariance: dSigma = R_b^T G R_b, G the symmetric matrix of the six with the off-diagonals halved; an off-diagonal of
+//                                 the result's six is the sum of its two entries (render_backward's convention for `covariances`)
+//                     no live entry: the gradient is added as it is (SAS_DEFORM_REST_BOUND_ONLY: nothing is added)
+//                   Each output depends on its own input alone, and a zero input adds zeros.  No atomics: a Gaussian has one lane, the same inputs
+//                   give the same bits on every run and on both paths.
 #include "sas_device.h"
 
 #pragma clang fp contract(off)
@@ -507,6 +521,127 @@ __global__ __launch_bounds__(kThreads) void k_skin_nodes_grad(const SasDeformGra
     }
 }
 
+// ---- the adjoint to the rest arrays ---------------------------------------------------------------------------------------------------------
+// one caller's row added to: out[at + c] += v[c] (the caller's arrays: no alignment beyond a float's is asked of them)
+template <int C>
+DEV void add_row(float *out, long long at, const float (&v)[C])
+{
+#pragma unroll
+    for (int c = 0; c < C; ++c) out[at + c] = out[at + c] + v[c];
+}
+
+template <bool LDS, int KP>
+__global__ __launch_bounds__(kThreads) void k_deform_rest_grad(const SasDeformRestGrad q)
+{
+    __shared__ float4 s_nodes[LDS ? SAS_SKIN_LDS_BYTES / 16 : 1];
+    const float4 *g_nodes = reinterpret_cast<const float4 *>(q.nodes);
+    if constexpr (LDS) {
+        for (int t = threadIdx.x; t < 4 * q.m; t += kThreads)
+            if (SAS_IN(t, SAS_SKIN_LDS_BYTES / 16, 1517)) s_nodes[t] = g_nodes[t];
+        __syncthreads();
+    }
+    const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;   // slot
+    if (j >= q.n || !SAS_IN(j, q.n_pad, 1518)) return;
+    const long long i = q.perm[j];                                        // the caller's index
+    if (!SAS_IN(i, q.n, 1519)) return;
+    auto rec = [&](int node, int part) -> float4 {
+        if constexpr (LDS) return s_nodes[4 * node + part];
+        else return g_nodes[4 * (long long)node + part];
+    };
+    int id[KP];
+    float wt[KP];
+#pragma unroll
+    for (int p = 0; p < KP / 4; ++p) {
+        const int4 v = q.idx[(long long)p * q.n_pad + j];
+        const float4 u = q.w[(long long)p * q.n_pad + j];
+        id[4 * p] = v.x; id[4 * p + 1] = v.y; id[4 * p + 2] = v.z; id[4 * p + 3] = v.w;
+        wt[4 * p] = u.x; wt[4 * p + 1] = u.y; wt[4 * p + 2] = u.z; wt[4 * p + 3] = u.w;
+    }
+    const bool rot = q.d_quats != nullptr || q.d_cov6 != nullptr;
+    float g[3] = {0.0f, 0.0f, 0.0f};
+    float h[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (q.d_means) { g[0] = q.d_means[3 * i]; g[1] = q.d_means[3 * i + 1]; g[2] = q.d_means[3 * i + 2]; }
+    if (q.d_quats) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) h[c] = q.d_quats[4 * i + c];
+    }
+    if (q.d_cov6) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) h[c] = q.d_cov6[6 * i + c];
+    }
+    // the forward's walk over the live entries: W and a again, and the mean path's sum_j w_j ((R_j^T g) - g)
+    float ax = 0.0f, ay = 0.0f, az = 0.0f, W = 0.0f;
+    float4 f = make_float4(1.0f, 0.0f, 0.0f, 0.0f), aq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    bool any = false;
+#pragma unroll
+    for (int e = 0; e < KP; ++e) {
+        const float we = wt[e];
+        if (!(id[e] >= 0 && id[e] < q.m && we > 0.0f)) continue;   // not live
+        W = W + we;
+        if (q.d_means) {
+            const float4 a = rec(id[e], 0), b = rec(id[e], 1), c = rec(id[e], 2);
+            const float u0 = (a.x * g[0] + b.x * g[1]) + c.x * g[2];
+            const float u1 = (a.y * g[0] + b.y * g[1]) + c.y * g[2];
+            const float u2 = (a.z * g[0] + b.z * g[1]) + c.z * g[2];
+            ax = ax + we * (u0 - g[0]);
+            ay = ay + we * (u1 - g[1]);
+            az = az + we * (u2 - g[2]);
+        }
+        if (rot) {
+            const float4 qn = rec(id[e], 3);
+            if (!any) f = qn;
+            const float dot = ((qn.x * f.x + qn.y * f.y) + qn.z * f.z) + qn.w * f.w;
+            const float sw = dot < 0.0f ? -we : we;
+            aq.x = aq.x + sw * qn.x;
+            aq.y = aq.y + sw * qn.y;
+            aq.z = aq.z + sw * qn.z;
+            aq.w = aq.w + sw * qn.w;
+        }
+        any = true;
+    }
+    if (!any) {   // the forward copied the rest bits: the gradient passes through as it is
+        if (q.bound_only) return;
+        if (q.d_means) add_row<3>(q.o_means, 3 * i, g);
+        if (q.d_quats) add_row<4>(q.o_quats, 4 * i, {h[0], h[1], h[2], h[3]});
+        if (q.d_cov6) add_row<6>(q.o_cov6, 6 * i, h);
+        return;
+    }
+    if (q.d_means) add_row<3>(q.o_means, 3 * i, {g[0] + ax / W, g[1] + ay / W, g[2] + az / W});
+    if (!rot) return;
+    const float n2 = ((aq.x * aq.x + aq.y * aq.y) + aq.z * aq.z) + aq.w * aq.w;
+    float bw = f.x, bx = f.y, by = f.z, bz = f.w;
+    if (n2 > 0.0f && n2 < INFINITY) {
+        const float inv = 1.0f / sqrtf(n2);
+        bw = aq.x * inv; bx = aq.y * inv; by = aq.z * inv; bz = aq.w * inv;
+    }
+    if (q.d_quats) {   // q' = q_b (x) q_rest: the transpose of the left product, the conjugate of q_b times h
+        add_row<4>(q.o_quats, 4 * i, {((bw * h[0] + bx * h[1]) + by * h[2]) + bz * h[3],
+                                      ((bw * h[1] - bx * h[0]) + bz * h[2]) - by * h[3],
+                                      ((bw * h[2] - by * h[0]) - bz * h[1]) + bx * h[3],
+                                      ((bw * h[3] - bz * h[0]) + by * h[1]) - bx * h[2]});
+    } else {           // Sigma' = R_b Sigma R_b^T: dSigma = R_b^T G R_b, G the symmetric matrix of the six with its off-diagonals halved
+        const float R[3][3] = {{1.0f - 2.0f * (by * by + bz * bz), 2.0f * (bx * by - bw * bz), 2.0f * (bx * bz + bw * by)},
+                               {2.0f * (bx * by + bw * bz), 1.0f - 2.0f * (bx * bx + bz * bz), 2.0f * (by * bz - bw * bx)},
+                               {2.0f * (bx * bz - bw * by), 2.0f * (by * bz + bw * bx), 1.0f - 2.0f * (bx * bx + by * by)}};
+        const float G[3][3] = {{h[0], 0.5f * h[1], 0.5f * h[2]}, {0.5f * h[1], h[3], 0.5f * h[4]}, {0.5f * h[2], 0.5f * h[4], h[5]}};
+        float T[3][3];   // R_b^T G
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) T[a][k] = (R[0][a] * G[0][k] + R[1][a] * G[1][k]) + R[2][a] * G[2][k];
+        auto out = [&](int a, int k) { return (T[a][0] * R[0][k] + T[a][1] * R[1][k]) + T[a][2] * R[2][k]; };
+        // an off-diagonal of the six stands for two entries of Sigma: both halves' gradients add
+        add_row<6>(q.o_cov6, 6 * i, {out(0, 0), out(0, 1) + out(1, 0), out(0, 2) + out(2, 0), out(1, 1), out(1, 2) + out(2, 1), out(2, 2)});
+    }
+}
+
+template <bool LDS>
+void launch_deform_rest_grad(hipStream_t st, const SasDeformRestGrad &q, unsigned blocks)
+{
+    if (q.kp <= 4) hipLaunchKernelGGL((k_deform_rest_grad<LDS, 4>), dim3(blocks), dim3(kThreads), 0, st, q);
+    else hipLaunchKernelGGL((k_deform_rest_grad<LDS, 8>), dim3(blocks), dim3(kThreads), 0, st, q);
+}
+
 template <bool LDS, bool STAGED>
 void launch_deform_grad(hipStream_t st, const SasDeformGrad &q, size_t lds_bytes)
 {
@@ -555,9 +690,25 @@ void sas_launch_deform(hipStream_t st, const SasDeform &q)
 {
     if (q.n <= 0 || q.m <= 0) return;
     hipLaunchKernelGGL(k_skin_nodes, dim3((unsigned)((q.m + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, q);
+    sas_launch_deform_planes(st, q);
+}
+
+// the planes alone, from the records q.nodes holds: one launch on st
+void sas_launch_deform_planes(hipStream_t st, const SasDeform &q)
+{
+    if (q.n <= 0 || q.m <= 0) return;
     const unsigned blocks = (unsigned)((q.n + kThreads - 1) / kThreads);
     if (q.lds && (size_t)q.m * sizeof(SasSkinNode) <= SAS_SKIN_LDS_BYTES) launch_deform<true>(st, q, blocks);
     else launch_deform<false>(st, q, blocks);
+}
+
+// the rest arrays' gradients, added to: one launch on st
+void sas_launch_deform_rest_grad(hipStream_t st, const SasDeformRestGrad &q)
+{
+    if (q.n <= 0 || q.m <= 0) return;
+    const unsigned blocks = (unsigned)((q.n + kThreads - 1) / kThreads);
+    if (q.lds && (size_t)q.m * sizeof(SasSkinNode) <= SAS_SKIN_LDS_BYTES) launch_deform_rest_grad<true>(st, q, blocks);
+    else launch_deform_rest_grad<false>(st, q, blocks);
 }
 
 size_t sas_deform_grad_lds_bytes(int m, bool lds, bool staged)

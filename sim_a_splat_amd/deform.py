@@ -1,13 +1,15 @@
 """Host-side conveniences around the deformable splats ("Deformation"): where to put control nodes, and how to turn the
 moving vertices a physics engine publishes into the rigid per-node transforms ``Rasterizer.deform`` takes.  Plain numpy, float64 inside;
-nothing here touches the GPU but ``fit_node_transforms``, through the rasterizer it is given.
+nothing here touches the GPU but ``fit_node_transforms`` and ``fit_dynamic_scene``, through the rasterizer they are given.
 
     nodes = grid_nodes(bounds, spacing)                  # or farthest_nodes(points, m)
     r.bind_skin(nodes, k=4)
     r.deform(transforms_from_positions(nodes, moved_nodes))
 
 The other way round -- the node transforms from pictures -- is ``fit_node_transforms``: an optimiser on the host around
-``Rasterizer.render_backward`` and ``Rasterizer.deform_backward``, with ``rigidity`` as its regulariser.
+``Rasterizer.render_backward`` and ``Rasterizer.deform_backward``, with ``rigidity`` as its regulariser.  ``fit_dynamic_scene`` fits the
+REST scene (and, if asked, the transforms too) from pictures of the object in several bends: ``Rasterizer.deform_backward_rest`` sums the
+time steps' gradients, ``Rasterizer.adam_step(rest=True)`` applies them.
 """
 from __future__ import annotations
 
@@ -191,6 +193,22 @@ def twist_gradient_batch(d_transforms, transforms, pivots=None) -> np.ndarray:
     return out
 
 
+def _twist_step(T, dT, g, m1, m2, it: int, per: int, step):
+    """One Adam step (0-based ``it`` of ``per``) of every node's se(3) twist about the node's current position, the step falling to a
+    twentieth over ``per`` steps: ``(T, m1, m2)`` after it.  ``T``, ``dT [M,3,4]``, ``g [M,3]`` the rest nodes, ``m1``, ``m2 [M,6]``."""
+    piv = np.einsum("mab,mb->ma", T[:, :, :3], g) + T[:, :, 3]   # where every node is now
+    tw = twist_gradient_batch(dT, T, piv)
+    m1 = 0.9 * m1 + 0.1 * tw
+    m2 = 0.999 * m2 + 0.001 * tw * tw
+    hat = (m1 / (1 - 0.9 ** (it + 1))) / (np.sqrt(m2 / (1 - 0.999 ** (it + 1))) + 1e-12)
+    decay = 0.05 ** (it / max(1, per - 1))
+    E = se3_exp_batch(-np.concatenate([step[0] * decay * hat[:, :3], step[1] * decay * hat[:, 3:]], axis=1))
+    # about the pivot: x -> E (x - p) + p
+    Rn = E[:, :3, :3] @ T[:, :, :3]
+    tn = np.einsum("mab,mb->ma", E[:, :3, :3], T[:, :, 3] - piv) + E[:, :3, 3] + piv
+    return np.concatenate([Rn, tn[:, :, None]], axis=2), m1, m2
+
+
 @dataclass
 class NodeFit:
     transforms: np.ndarray              # [M,3,4] float64, rows [R | t] of every node, rest -> current
@@ -222,7 +240,8 @@ def fit_node_transforms(r, images, viewmats, Ks, W: int, H: int, nodes, iters: i
     the weights 0, 0.003, 0.01, 0.03 and 0.1 tried there it ends closest to the true deformed means (0.29 of the start after 60 iterations,
     against 0.34 without the term and 0.39 at 0.1).  The colour loss starts at 2e-3 there: scale the weight with the loss of your scene.
 
-    Not fitted: skin weights, rest parameters, node positions; stretch and shear (the twist keeps every transform rigid)."""
+    Not fitted: skin weights, node positions; stretch and shear (the twist keeps every transform rigid).  The rest parameters are
+    ``fit_dynamic_scene``'s."""
     import torch
     import torch.nn.functional as Fn
     from .rasterizer import _host
@@ -293,18 +312,138 @@ def fit_node_transforms(r, images, viewmats, Ks, W: int, H: int, nodes, iters: i
         for it in range(per):
             loss, dT = evaluate(T, Kcs, w, h, targets, tms)
             res.history.append((int(f), loss))
-            piv = np.einsum("mab,mb->ma", T[:, :, :3], g) + T[:, :, 3]   # where every node is now
-            tw = twist_gradient_batch(dT, T, piv)
-            m1 = 0.9 * m1 + 0.1 * tw
-            m2 = 0.999 * m2 + 0.001 * tw * tw
-            hat = (m1 / (1 - 0.9 ** (it + 1))) / (np.sqrt(m2 / (1 - 0.999 ** (it + 1))) + 1e-12)
-            decay = 0.05 ** (it / max(1, per - 1))
-            E = se3_exp_batch(-np.concatenate([step[0] * decay * hat[:, :3], step[1] * decay * hat[:, 3:]], axis=1))
-            # about the pivot: x -> E (x - p) + p
-            Rn = E[:, :3, :3] @ T[:, :, :3]
-            tn = np.einsum("mab,mb->ma", E[:, :3, :3], T[:, :, 3] - piv) + E[:, :3, 3] + piv
-            T = np.concatenate([Rn, tn[:, :, None]], axis=2)
+            T, m1, m2 = _twist_step(T, dT, g, m1, m2, it, per, step)
     res.transforms = T
     res.loss = evaluate(T, K0s, W, H, imgs, ms)[0]   # (leaves r deformed at the result)
     res.history.append((1, res.loss))
     return res
+
+
+# ---- the rest scene from pictures of its motion ("Deformation": the adjoint to the rest arrays) -------------------------------
+@dataclass
+class DynamicFit:
+    history: List[float]                # the loss of every iteration: the views' mean per time step, averaged over the time steps (+ the rigidity terms)
+    transforms: np.ndarray              # [S,M,3,4] float64: the node transforms of every time step, as given or as fitted
+    steps: int = 0
+
+
+def fit_dynamic_scene(r, frames, nodes, what: Sequence[str] = ("means", "colors"), transforms=None, fit_transforms: bool = False,
+                      iters: int = 100, lrs=None, loss: Optional[str] = None, lambda_dssim: float = 0.2, loss_and_grad: Optional[Callable] = None,
+                      rigidity_weight: float = RIGIDITY_WEIGHT, step: Tuple[float, float] = (0.01, 0.01), background=(0.0, 0.0, 0.0),
+                      extent: Optional[float] = None, visible_only: bool = True, bound_only: bool = False, renderer=None) -> DynamicFit:
+    """Fit the REST scene of the skin bound to rasterizer ``r`` from pictures of the object in several bends.  ``frames``: one dict per
+    time step with ``images [C,H,W,3]`` (float, 0..1), ``viewmats [C,4,4]``, ``Ks [C,3,3]`` and optionally ``masks [C,H,W]``; all images
+    have one size.  ``transforms [S,M,3,4]``: the node transforms of every time step, known (from a simulator) or a start value; None:
+    the identity.  ``nodes [M,3]``: the rest positions the skin was bound with.  ``what``, ``lrs``, ``extent``, ``loss`` / ``lambda_dssim``
+    / ``loss_and_grad`` and ``visible_only`` are ``fit.fit_scene``'s (``what`` names variable groups of the REST scene).
+
+    Per iteration and time step t: ``deform(T_t)``; per view a frame, the loss (a view counts ``1 / C_t``) and
+    ``render_backward(out=acc_t)``; then ``deform_backward_rest(acc_t, out=rest_acc)`` for the ``means`` / ``quats`` gradients -- the
+    ``opacities``, ``colors`` and ``scales`` gradients are the rest scene's as they are and sum over the time steps by themselves -- and,
+    with ``fit_transforms``, ``deform_backward(acc_t)``.  After all time steps ONE ``adam_step(..., rest=True)``, then
+    ``fit_node_transforms``' twist update per time step (``step``, ``rigidity_weight``; the step falls to a twentieth over the run).
+    With ``fit_transforms`` time step 0 is the anchor: its transforms stay as given, which takes the freedom between rest pose and
+    transforms away.  ``bound_only``: only the Gaussians the skin binds (a live entry under ``M`` nodes) are fitted -- ``deform_backward_rest``
+    adds nothing for the others, and their ``opacities``, ``colors`` and ``scales`` gradients are zeroed before the step, which with
+    ``visible_only`` skips them whole: the static rest of a scene keeps its bits.
+
+    ``r`` is left deformed at the last time step; ``r.clear_skin()`` then ``r.read_scene()`` is the fitted rest scene.  ``renderer``: an
+    object with the rasterizer's methods used here, in ``r``'s place (tests run the loop on a CPU reference).  Moments left by an earlier
+    fit are dropped first.  Not fitted: skin weights, node positions, stretch and shear."""
+    import torch
+    from . import fit as _fit
+    from .autograd import prechain
+    from .rasterizer import _host
+    R = r if renderer is None else renderer
+    who = "fit_dynamic_scene"
+    _fit._check_loss(who, loss, loss_and_grad, lambda_dssim)
+    what = tuple(what)
+    if not what or any(k not in _fit._WHAT for k in what):
+        raise ValueError(f"{who}: what must name some of {_fit._WHAT}, got {what}")
+    if not getattr(R, "has_skin", False):
+        raise ValueError(f"{who}: no skin is bound to the rasterizer: bind_skin(nodes) first")
+    frames = list(frames)
+    S = len(frames)
+    if S < 1:
+        raise ValueError(f"{who}: frames is empty")
+    g = np.asarray(_host(nodes), np.float64).reshape(-1, 3)
+    M = g.shape[0]
+    if transforms is None:
+        T = np.zeros((S, M, 3, 4))
+        T[:, :, 0, 0] = T[:, :, 1, 1] = T[:, :, 2, 2] = 1.0
+    else:
+        T = np.asarray(_host(transforms), np.float64).copy()
+        if T.shape != (S, M, 3, 4):
+            raise ValueError(f"{who}: transforms must be [{S},{M},3,4] (time steps, nodes), got {list(T.shape)}")
+    if not float(rigidity_weight) >= 0.0:
+        raise ValueError(f"{who}: rigidity_weight must be >= 0, got {rigidity_weight}")
+    views, H, W = [], None, None
+    for t, f in enumerate(frames):
+        img = np.asarray(_host(f["images"]), np.float32)
+        if img.ndim != 4 or img.shape[3] != 3 or (H is not None and img.shape[1:3] != (H, W)):
+            raise ValueError(f"{who}: frames[{t}]['images'] must be [C,H,W,3], one size for all time steps, got {list(img.shape)}")
+        H, W = int(img.shape[1]), int(img.shape[2])
+        V, K = _fit._pack_views(f"{who}: frames[{t}]", f["viewmats"], f["Ks"], img, f.get("masks"))
+        views.append([V, K, img, f.get("masks"), {}])
+    quat_scene = getattr(R, "covariance_form", "quats") == "quats"
+    orient = "quats" if quat_scene else "covariances"
+    moved = tuple(k for k in ("means", "quats") if k in what)                    # what the deformation moves, of the variables
+    passed = tuple(k for k in what if k not in moved)
+    want = what + tuple(k for k in ("means", orient) if fit_transforms and k not in what)
+    rates = dict(_fit.DEFAULT_LRS, **(lrs or {}))
+    bg = tuple(float(v) for v in background)
+    lg = _fit.l1_loss_and_grad if loss_and_grad is None else loss_and_grad
+    if hasattr(R, "adam_reset"):
+        R.adam_reset()
+    if extent is None:
+        extent = 1.0
+        if "means" in what:   # (of the scene as it stands: a bend does not change the scale of things)
+            m = R.read_scene()["means"]
+            extent = float((m - m.mean(dim=0)).norm(dim=1).max()) if m.shape[0] else 1.0
+    n_iters = int(iters)
+    bound = None
+    if bound_only and passed:
+        sk = R.read_skin()
+        bound = ((sk["indices"] >= 0) & (sk["indices"] < M) & (sk["weights"] > 0)).any(dim=1)
+    m1, m2 = np.zeros((S, M, 6)), np.zeros((S, M, 6))
+    losses = []
+    for it in range(1, n_iters + 1):
+        rest_acc, shared, total, dTs = {}, {}, None, {}
+        for t, (V, K, img, masks, cache) in enumerate(views):
+            R.deform(np.ascontiguousarray(T[t].astype(np.float32)))
+            acc_t = dict(shared)
+            C = V.shape[0]
+            for v in range(C):
+                out = R.render(V[v], K[v], W, H, bg)
+                rgb = out["rgb"]
+                if v not in cache:   # a view's target and mask move to the frames' device once
+                    tm = None if masks is None else torch.as_tensor(masks[v]).to(rgb.device)
+                    cache[v] = (torch.as_tensor(img[v]).to(device=rgb.device, dtype=rgb.dtype).reshape(rgb.shape), tm)
+                if loss is None:
+                    value, g_rgb = lg(rgb, *cache[v])
+                    g_acc, g_a, _ = prechain(rgb, out["alpha"], out["depth"], bg, g_rgb / C, None, None)
+                else:
+                    pl = R.photometric_loss(rgb, cache[v][0], mask=cache[v][1], alpha=out["alpha"], background=bg, lambda_dssim=lambda_dssim)
+                    value, g_acc, g_a = pl["loss"], pl["g_rgb"] / C, pl["g_alpha"] / C
+                acc_t = R.render_backward(V[v], K[v], W, H, g_acc, g_a, None, out=acc_t, want=want)
+                value = torch.as_tensor(value).detach().reshape(()) / (C * S)
+                total = value if total is None else total + value
+            shared = {k: acc_t[k] for k in passed}
+            if moved:
+                rest_acc = R.deform_backward_rest({k: acc_t[k] for k in moved}, out=rest_acc, bound_only=bound_only)
+            if fit_transforms and t > 0:
+                dTs[t] = R.deform_backward({k: acc_t[k] for k in ("means", orient)})
+        if bound is not None:
+            for k, a in shared.items():
+                a.mul_(bound.reshape((-1,) + (1,) * (a.dim() - 1)).to(a.dtype))
+        R.adam_step(dict(shared, **rest_acc), _fit.step_rates(rates, what, extent, it, n_iters), it, visible_only=visible_only, rest=True)
+        for t, d in dTs.items():   # (the read-backs wait for the step's work once, here)
+            dT = torch.as_tensor(d).double().cpu().numpy().reshape(M, 3, 4)
+            if rigidity_weight > 0.0:
+                val, dreg = rigidity(g, T[t])
+                total, dT = total + rigidity_weight * val / S, dT + rigidity_weight * dreg
+            T[t], m1[t], m2[t] = _twist_step(T[t], dT, g, m1[t], m2[t], it - 1, n_iters, step)
+        losses.append(total)
+    R.deform(np.ascontiguousarray(T[S - 1].astype(np.float32)))
+    history = [float(x) for x in torch.stack([torch.as_tensor(x, dtype=torch.float64).cpu() for x in losses])] if losses else []
+    return DynamicFit(history=history, transforms=T, steps=len(history))

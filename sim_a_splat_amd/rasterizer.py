@@ -1100,7 +1100,7 @@ class Rasterizer:
 
     @_locked
     def adam_step(self, grads: Dict[str, torch.Tensor], lrs: Dict[str, float], step: int, betas: Tuple[float, float] = (0.9, 0.999),
-                  eps: float = 1e-15, visible_only: bool = False) -> None:
+                  eps: float = 1e-15, visible_only: bool = False, rest: bool = False) -> None:
         """One fused Adam step on the RESIDENT scene (sas_scene_adam_step; DESIGN.md 3, "Optimiser step"): the next frame shows the
         stepped scene, with no upload.  ``grads``: what ``render_backward`` returns or accumulates into through ``out=`` -- float32
         device tensors under ``means``, ``opacities``, ``colors``, ``quats``, ``scales``, with respect to the activated arrays; other
@@ -1110,7 +1110,12 @@ class Rasterizer:
         covariances are fixed.  ``step``: 1-based, the caller's count.  ``visible_only``: Gaussians whose gradient is exactly zero
         in every stepped array (culled in every view of the batch) are skipped, moments included.  The moments live in the context
         until ``adam_reset`` or the next ``upload``.  ``n``, ``sh_degree``, groups, group poses, features and meshes stay; the last
-        frame's ``read_projection`` / ``read_tile_lists`` do not.  The call only enqueues, on the current stream."""
+        frame's ``read_projection`` / ``read_tile_lists`` do not.  The call only enqueues, on the current stream.
+        ``rest=True`` (sas_scene_adam_step_rest): the step on the REST scene of a bound skin -- ``grads`` are then gradients with
+        respect to the rest arrays: ``deform_backward_rest``'s ``means`` and ``quats``, and ``render_backward``'s ``opacities``,
+        ``colors`` and ``scales`` as they are (a deformation does not touch them).  The same kernel on the same optimiser state; the
+        last ``deform`` is applied again to the stepped rest scene, so the next frame and ``read_scene`` show it in its current bend,
+        and ``clear_skin`` returns the stepped rest scene.  ``SasError`` without a skin; ``rest=False`` under a skin raises as ever."""
         unknown = [k for k in lrs if k not in self._ADAM_LRS]
         if unknown:
             raise ValueError(f"adam_step: unknown learning rates {unknown}; expected some of {self._ADAM_LRS}")
@@ -1128,10 +1133,11 @@ class Rasterizer:
             ptrs[k] = t.data_ptr()
         cfg = _capi.AdamConfig(*[float(lrs.get(k, 0.0)) for k in self._ADAM_LRS], float(betas[0]), float(betas[1]), float(eps), int(step),
                                _capi.SAS_ADAM_VISIBLE_ONLY if visible_only else 0)
-        rc = self._L.sas_scene_adam_step(self._ctx, ctypes.byref(cfg), ptrs["means"], ptrs["opacities"], ptrs["colors"], ptrs["quats"],
-                                         ptrs["scales"], self._stream())
+        entry = "sas_scene_adam_step_rest" if rest else "sas_scene_adam_step"
+        rc = getattr(self._L, entry)(self._ctx, ctypes.byref(cfg), ptrs["means"], ptrs["opacities"], ptrs["colors"], ptrs["quats"],
+                                     ptrs["scales"], self._stream())
         if rc != 0:
-            self._check(rc, "sas_scene_adam_step")
+            self._check(rc, entry)
         self._in_flight(True)
 
     @_locked
@@ -1413,7 +1419,7 @@ class Rasterizer:
         """Bind the resident scene to control nodes (sas_scene_skin; DESIGN.md 3, "Deformation"): ``indices [N,k]`` (integers; int32
         device tensors are read where they are) and ``weights [N,k]`` (float32), ``1 <= k <= 8``, in ``upload``'s order.  An entry counts
         in ``deform`` when ``0 <= index < m`` and ``weight > 0``; anything else is ignored.  The first bind keeps the scene as it stands
-        as the REST pose; a bind over a skin replaces the entries and keeps the rest pose.  While a skin is bound ``adam_step``,
+        as the REST pose; a bind over a skin replaces the entries and keeps the rest pose.  While a skin is bound ``adam_step`` (but for ``rest=True``),
         ``densify``, ``mcmc_refine``, ``mcmc_noise`` and ``reset_opacity`` raise.  Only enqueues, on the current stream."""
         def dev(a, dt, name):
             t = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
@@ -1447,8 +1453,8 @@ class Rasterizer:
 
     @_locked
     def clear_skin(self) -> None:
-        """Unbind the skin: the rest pose returns bit for bit, and the calls a skin refuses work again.  Without a skin: nothing.  Only
-        enqueues, on the current stream."""
+        """Unbind the skin: the rest pose returns bit for bit (as ``adam_step(rest=True)`` has stepped it, if it has), and the calls a
+        skin refuses work again.  Without a skin: nothing.  Only enqueues, on the current stream."""
         rc = self._L.sas_scene_skin(self._ctx, 0, None, None, self._stream())
         if rc != 0:
             self._check(rc, "sas_scene_skin")
@@ -1518,6 +1524,58 @@ class Rasterizer:
         if rc != 0:
             self._check(rc, "sas_scene_deform_backward")
         return out
+
+    @_locked
+    def deform_backward_rest(self, grads: Dict[str, torch.Tensor], out: Optional[Dict[str, torch.Tensor]] = None,
+                             bound_only: bool = False) -> Dict[str, torch.Tensor]:
+        """The adjoint of the last ``deform`` to the REST scene (sas_scene_deform_backward_rest; DESIGN.md 3, "Deformation"): from the
+        gradients of the DEFORMED arrays, the dict ``render_backward`` returns or accumulates on the skinned scene, to the gradients of
+        the Gaussians that are stored.  Returns a dict with ``means`` and ``quats`` (or ``covariances``, as the scene was uploaded) for
+        the keys ``grads`` holds, float32 device tensors of the scene's shapes; a missing key is left out (not both), other keys are
+        ignored: the ``opacities``, ``colors`` and ``scales`` gradients are untouched by a deformation and are the rest scene's as they
+        stand.  ``out``: a dict of such tensors to ACCUMULATE into -- every time step has its own deformation, so the sum over time
+        steps is taken here: ``deform(T_t)``, the views' ``render_backward(out=acc_t)``, ``deform_backward_rest(acc_t, out=rest_acc)``
+        per step, then one ``adam_step(rest_acc, ..., rest=True)``.  Missing keys are allocated zeroed; a tensor of ``out`` must not be
+        one of ``grads``.  A Gaussian without a live entry has its gradient passed through bit for bit; ``bound_only=True``: it adds
+        nothing (skins bound with ``group=``: the static rest of the scene is then not stepped).  An all-zero gradient adds exact zeros.
+        No atomics: the same inputs give the same bits on every run.  ``SasError`` without a skin or without a ``deform`` since the
+        bind.  Only enqueues, on the current stream."""
+        if not isinstance(grads, dict):
+            raise ValueError("deform_backward_rest: grads must be a dict as render_backward returns it")
+        if out is not None and not isinstance(out, dict):
+            raise ValueError("deform_backward_rest: out must be a dict of tensors to accumulate into")
+        if not self.has_skin:
+            raise SasError("deform_backward_rest: no skin is bound")
+        if self._deform_m <= 0:
+            raise SasError("deform_backward_rest: no deform since the skin was bound")
+        shapes = self._scene_shapes()
+        other = "covariances" if self.covariance_form == "quats" else "quats"
+        if grads.get(other) is not None:
+            raise ValueError(f"deform_backward_rest: the scene was uploaded as {'quats' if other == 'covariances' else 'covariances'}: drop grads[{other!r}]")
+        ptrs, res = {}, {}
+        for k in ("means", "quats", "covariances"):
+            t = grads.get(k)
+            ptrs[k] = ptrs["o_" + k] = None
+            if t is None:
+                continue
+            if not self._is_mine(t, torch.float32, shapes[k]):
+                raise ValueError(f"grads[{k!r}] must be a contiguous float32 tensor {shapes[k]} on {self.device}")
+            o = out.get(k) if out else None
+            if o is None:
+                o = torch.zeros(shapes[k], dtype=torch.float32, device=self.device)
+            elif not self._is_mine(o, torch.float32, shapes[k]):
+                raise ValueError(f"out[{k!r}] must be a contiguous float32 tensor {shapes[k]} on {self.device}")
+            res[k] = o
+            ptrs[k], ptrs["o_" + k] = t.data_ptr(), o.data_ptr()
+        if not res:
+            raise ValueError("deform_backward_rest: grads holds neither means nor the orientation gradient")
+        if self.n == 0:
+            return res
+        rc = self._L.sas_scene_deform_backward_rest(self._ctx, ptrs["means"], ptrs["quats"], ptrs["covariances"], ptrs["o_means"], ptrs["o_quats"],
+                                                    ptrs["o_covariances"], _capi.SAS_DEFORM_REST_BOUND_ONLY if bound_only else 0, self._stream())
+        if rc != 0:
+            self._check(rc, "sas_scene_deform_backward_rest")
+        return res
 
     @_locked
     def bind_skin(self, nodes: ArrayLike, k: int = 4, sigma: Optional[float] = None, max_distance: float = math.inf,

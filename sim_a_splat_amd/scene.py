@@ -275,6 +275,48 @@ class SplatScene:
             return fit_node_transforms(self._raster, img, V, K, int(width), int(height), self._deformable[1], iters=iters, masks=masks,
                                        background=self.background, **kw)
 
+    def fit_dynamic(self, frames, height: int, width: int, fov: Optional[float] = None, what=("means", "colors"), transforms=None,
+                    iters: int = 100, **kw):
+        """The deformable group's REST Gaussians from pictures of it in several bends: ``deform.fit_dynamic_scene`` on the nodes of
+        ``bind_deformable``, in the handle's local frame.  ``frames``: one dict per time step with ``images [C,H,W,3]`` (uint8, or float
+        0..1), ``cam_poses [(wxyz, position), ...]`` and optionally ``masks [C,H,W]``, with the views of ``get_renders``; ``transforms
+        [S,M,3,4]``: the nodes' transforms of every time step.  ``what``: of ``means``, ``colors``, ``opacities`` (the covariances of a
+        scene are fixed).  ``kw`` goes to ``fit_dynamic_scene`` (``fit_transforms``, ``lrs``, ``loss``, ``rigidity_weight``, ...).  Only
+        the bound group is fitted (``bound_only=True``): every other group keeps its bits.  The fitted arrays replace the ones ``add_gaussian_splats`` was given, so
+        a later upload keeps them; the scene is left deformed at the last time step.  Returns the ``DynamicFit``.  The lock is held
+        throughout; a scene with meshes is refused."""
+        from .deform import fit_dynamic_scene
+        fov_ = self._camera_or(fov=fov)[2]
+        packed = []
+        for f in frames:
+            V, K = self._views_and_Ks(int(height), int(width), *_camera_arrays(f["cam_poses"]), fov_)
+            img = np.asarray(f["images"].detach().cpu().numpy() if isinstance(f["images"], torch.Tensor) else f["images"])
+            img = img.astype(np.float32) / 255.0 if img.dtype == np.uint8 else img.astype(np.float32)
+            packed.append(dict(images=img, viewmats=V, Ks=K, masks=f.get("masks")))
+        with self.lock:
+            if self._deformable is None:
+                raise RuntimeError("bind_deformable first")
+            if self._meshes:
+                raise RuntimeError("fit_dynamic: the scene holds meshes, which the backward pass does not take")
+            self._sync()
+            r = self._raster
+            res = fit_dynamic_scene(r, packed, self._deformable[1], what=what, transforms=transforms, iters=iters, background=self.background,
+                                    bound_only=True, **kw)
+            # the rest scene back into the groups' arrays: the skin is lifted for the read and bound again with the same entries
+            skin = r.read_skin()
+            r.clear_skin()
+            rest = {k: v.cpu().numpy() for k, v in r.read_scene().items()}
+            r.set_skin(skin["indices"], skin["weights"])
+            r.deform(np.ascontiguousarray(res.transforms[-1].astype(np.float32)))
+            at = 0
+            for grp in self._groups:
+                n = grp["centers"].shape[0]
+                grp["centers"] = rest["means"][at:at + n].copy()
+                grp["rgbs"] = rest["colors"][at:at + n].reshape(n, 3).copy()
+                grp["opacities"] = rest["opacities"][at:at + n].copy()
+                at += n
+            return res
+
     # -- internals ---------------------------------------------------------------------------
     def _sync(self) -> None:
         if not self._uploaded:
