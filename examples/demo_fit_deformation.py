@@ -2,13 +2,15 @@
 """How is the sheet bent, given pictures of it: the node transforms of a deformable splat group fitted to camera frames (DESIGN.md 3,
 "Deformation": the adjoint).
 
-    python examples/demo_fit_deformation.py [--iters 200] [--sheet 20000] [--views 4] [--step 60]
+    python examples/demo_fit_deformation.py [--iters 200] [--sheet 20000] [--views 4] [--step 60] [--optimizer host|device]
 
 demo_deform_cloth.py's sheet (a 1 x 1 square of flat Gaussians bound to an 8 x 8 node grid) is put into ONE pose of its travelling wave and
 rendered from a few cameras: those frames are the targets.  The sheet goes back to rest, and ``SplatScene.fit_deformation`` recovers the node
 transforms from the pictures alone -- every step is a ``deform``, a ``render`` + ``render_backward`` per view, one ``deform_backward`` and a
 twist update of the 64 nodes on the host.  Printed: the mean distance of the deformed means to the TRUE deformed means before and after,
-and the time per step -- a measurement of THIS scene, not a guarantee: how far a fit gets depends on the texture, the views and the bend."""
+and the time per step -- a measurement of THIS scene, not a guarantee: how far a fit gets depends on the texture, the views and the bend.
+``--optimizer device`` keeps the twist update on the GPU (``deform.NodeOptimizer``): the rigidity term and the update are two kernels, and
+nothing is read back between the first step and the last."""
 from __future__ import annotations
 
 import argparse
@@ -45,6 +47,7 @@ def main():
     ap.add_argument("--step", type=int, default=60, help="the wave's step whose pose is the truth")
     ap.add_argument("--width", type=int, default=256)
     ap.add_argument("--height", type=int, default=256)
+    ap.add_argument("--optimizer", choices=("host", "device"), default="host", help="where the nodes' twist update runs")
     a = ap.parse_args()
 
     scene = SplatScene(0, background=(0.05, 0.05, 0.08))
@@ -60,14 +63,15 @@ def main():
     scene.deform(deform.transforms_from_positions(nodes, nodes))
     rest = scene._raster.read_scene()["means"].cpu().numpy()
     t0 = time.perf_counter()
-    res = scene.fit_deformation(images, a.height, a.width, cams, iters=a.iters)
+    res = scene.fit_deformation(images, a.height, a.width, cams, iters=a.iters, **({} if a.optimizer == "host" else {"optimizer": a.optimizer}))
     ms = (time.perf_counter() - t0) * 1e3 / max(1, len(res.history))
     after = scene._raster.read_scene()["means"].cpu().numpy()
     e0, e1 = np.linalg.norm(rest - truth, axis=1).mean(), np.linalg.norm(after - truth, axis=1).mean()
     print(f"{a.sheet} Gaussians, {nodes.shape[0]} nodes, {a.views} views of {a.width} x {a.height}, {a.iters} iterations")
     print(f"mean distance of the deformed means to the true ones: {e0:.5f} at rest -> {e1:.5f} fitted ({e1 / e0:.3f} of the start); "
           f"loss {res.history[0][1]:.3e} -> {res.loss:.3e}")
-    print(f"time per step (deform, {a.views} x (frame + backward), deform_backward, host update): {ms:.2f} ms")
+    update = "host update" if a.optimizer == "host" else "rigidity + twist step on the device"
+    print(f"time per step (deform, {a.views} x (frame + backward), deform_backward, {update}): {ms:.2f} ms")
     scene.close()
 
 

@@ -900,6 +900,52 @@ int sas_scene_deform_backward_rest(sas_ctx *ctx, const float *d_means, const flo
 int sas_scene_adam_step_rest(sas_ctx *ctx, const sas_adam_config *cfg, const float *d_means, const float *d_opacities, const float *d_sh,
                              const float *d_quats, const float *d_scales, void *stream);
 
+/*
+ * The node optimiser on the device ("Deformation": the node optimiser): what fits the node transforms of a skin from the
+ * gradients sas_scene_deform_backward writes, without the host in the loop.  Both calls are scene-free, take DEVICE arrays, only ENQUEUE on
+ * `stream`, require 1 <= m <= 65536 and use no atomics: the same inputs give the same bits on every run.  The STATE -- the rows [R | t], the
+ * Adam moments, the rigidity gradient -- is BINARY64 (double): a rotation left-multiplied hundreds of times in binary32 drifts away from
+ * R^T R = I, and sas_scene_deform does not check device arrays.  The float32 rows sas_scene_deform takes are the state rounded once.
+ *
+ * sas_nodes_rigidity -- the embedded-deformation consistency term and its gradient:
+ *   value = sum_i sum_{j in N(i)} |T_i(g_j) - T_j(g_j)|^2 / (m kn),   T(x) = R x + t the rows Rt64 [m,3,4], g = nodes [m,3] float32,
+ * N(i) the kn (0..8) entries nb [m,kn] int32 of node i; an entry outside [0, m) is ignored.  d_Rt64_out [m,3,4] double, WRITTEN: the
+ * gradient with respect to the twelve entries of every node, each an independent variable.  value_out [1] double, written.
+ * rev_start [m + 1] / rev_edge is the REVERSE table: rev_edge[rev_start[j] .. rev_start[j + 1]) lists the edge numbers i kn + slot with
+ * nb[i][slot] == j in ascending order; rev_start[m] <= m kn entries are read (ranges are clipped to that, edge numbers out of range are
+ * ignored).  One lane per node: lane i sums its own kn edges in slot order, then its incoming edges in table order, every residual
+ * recomputed from the two transforms -- the order of every sum is fixed, and a node with in-degree m - 1 is correct (and slow).  The value
+ * is one partial sum per workgroup, then one fixed-order reduction; the partials (2 KiB) belong to the context and are allocated by its
+ * first call: no later call allocates.  kn == 0 writes exact zeros and a value of 0 (nb and the reverse table may then be NULL).
+ * SAS_ERR_INVALID for m or kn out of range, or a missing array.
+ *
+ * sas_nodes_twist_step -- one Adam step of every node's se(3) twist, left-multiplied about the node's CURRENT position p = R g + t.  The
+ * gradient is G = double(d_Rt32) + weight64 * d_Rt64 ([m,3,4] each; either may be NULL, not both).  Per node, in binary64:
+ *   tw   = (sum_c A[:,c] x G[:,c] over the four columns of A = [R | t], + G[:,3] x p;  G[:,3])          (the twist gradient about p)
+ *   m1   = beta1 m1 + gain1 tw,   m2 = beta2 m2 + gain2 tw tw                                            ([m,6] each, in place)
+ *   hat  = (m1 / c1) / (sqrt(m2 / c2) + eps)
+ *   E    = exp(-(lr_rot hat[0:3], lr_trans hat[3:6]))      (Rodrigues; below |omega| = 1e-8 the series 1 - th^2/6, 1/2 - th^2/24, 1/6 - th^2/120)
+ *   R   <- E_R R,   t <- (E_R (t - p) + E_t) + p                                                         (Rt64, in place)
+ * and Rt32_out [m,3,4] float32 = Rt64 rounded once (its bits are float(Rt64)).  gain1 / gain2 are the weights of the new gradient in the
+ * moments, 1 - beta in exact arithmetic; they are given beside the betas because 1 - 0.999 in binary64 is not the binary64 0.001 a host
+ * optimiser writes (they are 4 units in the last place apart).  The bias corrections c1 = 1 - beta1^step, c2 = 1 - beta2^step and the
+ * decayed rates are formed on the host.  One launch, no scratch.
+ * SAS_ERR_INVALID for m out of range, non-finite or negative rates, eps or weight64, betas outside [0,1), gains outside (0,1], c1 or
+ * c2 <= 0, both gradients NULL, or a missing array.
+ */
+typedef struct sas_node_step_config {
+    double lr_rot, lr_trans;   /* radians, scene units */
+    double beta1, beta2;       /* 0.9, 0.999 */
+    double c1, c2;             /* 1 - beta1^(it + 1), 1 - beta2^(it + 1) */
+    double eps;                /* 1e-12 */
+    double gain1, gain2;       /* 0.1, 0.001 */
+} sas_node_step_config;
+int sas_nodes_rigidity(sas_ctx *ctx, int64_t m, const float *nodes, const double *Rt64, int kn, const int32_t *nb, const int32_t *rev_start,
+                       const int32_t *rev_edge, double *d_Rt64_out, double *value_out, void *stream);
+int sas_nodes_twist_step(sas_ctx *ctx, int64_t m, const float *nodes, const float *d_Rt32_or_null, const double *d_Rt64_or_null,
+                         double weight64, double *Rt64, double *m1, double *m2, float *Rt32_out, const sas_node_step_config *cfg,
+                         void *stream);
+
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical
  * field of view; the view matrices and intrinsics are those of sas_camera_matrices. */

@@ -16,7 +16,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libsas_hip.so"
-SOURCES = [CSRC / "sas_kernels.hip", CSRC / "sas_tile.hip", CSRC / "sas_mesh.hip", CSRC / "sas_query.hip", CSRC / "sas_match.hip", CSRC / "sas_cloud.hip", CSRC / "sas_fuse.hip", CSRC / "sas_grad.hip", CSRC / "sas_fit.hip", CSRC / "sas_loss.hip", CSRC / "sas_density.hip", CSRC / "sas_mcmc.hip", CSRC / "sas_order.hip", CSRC / "sas_knn.hip", CSRC / "sas_skin.hip",
+SOURCES = [CSRC / "sas_kernels.hip", CSRC / "sas_tile.hip", CSRC / "sas_mesh.hip", CSRC / "sas_query.hip", CSRC / "sas_match.hip", CSRC / "sas_cloud.hip", CSRC / "sas_fuse.hip", CSRC / "sas_grad.hip", CSRC / "sas_fit.hip", CSRC / "sas_loss.hip", CSRC / "sas_density.hip", CSRC / "sas_mcmc.hip", CSRC / "sas_order.hip", CSRC / "sas_knn.hip", CSRC / "sas_skin.hip", CSRC / "sas_nodes.hip",
            CSRC / "sas_api.cpp"]
 DEPS = SOURCES + [CSRC / "sas_internal.h", CSRC / "sas_device.h", PKG.parent / "include" / "sim_a_splat_amd.h"]
 ARCH = "gfx950"

@@ -344,6 +344,8 @@ struct sas_ctx : Settings {
     Event order_done;     // recorded behind device_order's launches: the next call's stream waits for it before it reuses the scratch
     DevBuf knn_pts, knn_table, knn_left, knn_keys, knn_rec;   // scratch of sas_knn_points (SasKnn): cell-ordered points, cell table + block sums, leftover list, slice keys, records
     Event knn_done;       // recorded behind sas_knn_points' launches, as order_done
+    DevBuf nodes_partial; // scratch of sas_nodes_rigidity: SAS_NODES_MAX_PARTIALS doubles, allocated by a context's first call
+    Event nodes_done;     // recorded behind sas_nodes_rigidity's launches, as knn_done
     // host clock of the last sas_scene_densify / sas_scene_mcmc_refine: classes, scatter, storage order, relayout + state + commit.  With the
     // order on the device (the default) laps 1 and 2 clock the ENQUEUE of the scatter and of the order; the kernels' time falls into lap 3,
     // whose wait is the first behind them.  SAS_ORDER=0: lap 1 ends behind the read-back, lap 2 is the host sort.
@@ -3123,6 +3125,58 @@ int sas_knn_cross(sas_ctx *c, int64_t n, const float *points, int64_t m, const f
     return SAS_OK;
 }
 
+// The rigidity term of a deformation graph and its gradient (k_nodes_rigidity, k_nodes_value), scene-free, device arrays, binary64: two launches
+// on the caller's stream, nothing is waited for.  The partial sums of the value are the context's (2 KiB, allocated by the first call); a call
+// on another stream than the one before runs behind it.
+int sas_nodes_rigidity(sas_ctx *c, int64_t m, const float *nodes, const double *Rt64, int kn, const int32_t *nb, const int32_t *rev_start,
+                       const int32_t *rev_edge, double *d_Rt64_out, double *value_out, void *stream)
+{
+    const char *who = "sas_nodes_rigidity";
+    if (!c) return SAS_ERR_INVALID;
+    if (m < 1 || m > SAS_KNN_CROSS_MAX_NODES) return fail(c, SAS_ERR_INVALID, "%s: m=%lld out of [1,%d]", who, (long long)m, SAS_KNN_CROSS_MAX_NODES);
+    if (kn < 0 || kn > SAS_NODES_MAX_K) return fail(c, SAS_ERR_INVALID, "%s: kn=%d out of [0,%d]", who, kn, SAS_NODES_MAX_K);
+    if (!nodes || !Rt64 || !d_Rt64_out || !value_out) return fail(c, SAS_ERR_INVALID, "%s: nodes, Rt64, d_Rt64_out and value_out are required", who);
+    if (kn > 0 && (!nb || !rev_start || !rev_edge)) return fail(c, SAS_ERR_INVALID, "%s: nb, rev_start and rev_edge are required with kn > 0", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (const int rc = ensure(c, c->nodes_partial, sizeof(double) * SAS_NODES_MAX_PARTIALS)) return rc;
+    if (!c->nodes_done.h) HIP_TRY(c, hipEventCreateWithFlags(c->nodes_done.put(), hipEventDisableTiming));
+    else HIP_TRY(c, hipStreamWaitEvent(st, c->nodes_done, 0));
+    const SasNodesRigidity q{nodes, Rt64, nb, rev_start, rev_edge, (int)m, kn, d_Rt64_out, (double *)c->nodes_partial.p, value_out};
+    sas_launch_nodes_rigidity(st, q);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->nodes_done, st));
+    return SAS_OK;
+}
+
+// One Adam step of every node's se(3) twist about the node's current position (k_nodes_twist_step), scene-free, device arrays, binary64: one
+// launch on the caller's stream, no scratch, nothing is waited for.
+int sas_nodes_twist_step(sas_ctx *c, int64_t m, const float *nodes, const float *d_Rt32_or_null, const double *d_Rt64_or_null, double weight64,
+                         double *Rt64, double *m1, double *m2, float *Rt32_out, const sas_node_step_config *cfg, void *stream)
+{
+    const char *who = "sas_nodes_twist_step";
+    if (!c) return SAS_ERR_INVALID;
+    if (m < 1 || m > SAS_KNN_CROSS_MAX_NODES) return fail(c, SAS_ERR_INVALID, "%s: m=%lld out of [1,%d]", who, (long long)m, SAS_KNN_CROSS_MAX_NODES);
+    if (!cfg || !nodes || !Rt64 || !m1 || !m2 || !Rt32_out) return fail(c, SAS_ERR_INVALID, "%s: cfg, nodes, Rt64, m1, m2 and Rt32_out are required", who);
+    if (!d_Rt32_or_null && !d_Rt64_or_null) return fail(c, SAS_ERR_INVALID, "%s: one of d_Rt32 and d_Rt64 is required", who);
+    if (!std::isfinite(weight64)) return fail(c, SAS_ERR_INVALID, "%s: weight64 = %g is not finite", who, weight64);
+    for (const double lr : {cfg->lr_rot, cfg->lr_trans})
+        if (!(lr >= 0.0) || !std::isfinite(lr)) return fail(c, SAS_ERR_INVALID, "%s: rates (%g, %g) must be finite and >= 0", who, cfg->lr_rot, cfg->lr_trans);
+    for (const double b : {cfg->beta1, cfg->beta2})
+        if (!(b >= 0.0 && b < 1.0)) return fail(c, SAS_ERR_INVALID, "%s: betas (%g, %g) must lie in [0,1)", who, cfg->beta1, cfg->beta2);
+    for (const double g : {cfg->gain1, cfg->gain2})
+        if (!(g > 0.0 && g <= 1.0)) return fail(c, SAS_ERR_INVALID, "%s: gains (%g, %g) must lie in (0,1]", who, cfg->gain1, cfg->gain2);
+    for (const double v : {cfg->c1, cfg->c2})
+        if (!(v > 0.0) || !std::isfinite(v)) return fail(c, SAS_ERR_INVALID, "%s: c1 = %g, c2 = %g must be finite and > 0", who, cfg->c1, cfg->c2);
+    if (!(cfg->eps >= 0.0) || !std::isfinite(cfg->eps)) return fail(c, SAS_ERR_INVALID, "%s: eps = %g must be finite and >= 0", who, cfg->eps);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const SasNodesStep q{nodes, d_Rt32_or_null, d_Rt64_or_null, weight64, Rt64, m1, m2, Rt32_out, (int)m,
+                         cfg->lr_rot, cfg->lr_trans, cfg->beta1, cfg->beta2, cfg->gain1, cfg->gain2, cfg->c1, cfg->c2, cfg->eps};
+    sas_launch_nodes_step((hipStream_t)stream, q);
+    HIP_TRY(c, hipGetLastError());
+    return SAS_OK;
+}
+
 // Bind, replace or clear the skin (k_skin_bind).  Host work: validation, the planes' allocations, the rest snapshot as device copies on the
 // caller's stream, one launch, one event.
 int sas_scene_skin(sas_ctx *c, int k, const int32_t *indices, const float *weights, void *stream)
@@ -3486,7 +3540,7 @@ int sas_frames_completed(sas_ctx *c, int64_t *submitted, int64_t *completed)
 
 #ifdef SAS_DEBUG_BOUNDS
 // every kernel file's counter (SAS_BOUNDS_ACCESSOR in sas_device.h): one line per file, in the order their reports are looked at
-#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density) X(mcmc) X(order) X(knn) X(skin)
+#define SAS_BOUNDS_FILES(X) X(kernels) X(tiles) X(mesh) X(query) X(match) X(cloud) X(fuse) X(grad) X(fit) X(loss) X(density) X(mcmc) X(order) X(knn) X(skin) X(nodes)
 #define SAS_BOUNDS_DECLARE(name) extern "C" int sas_debug_bounds_##name(unsigned long long *out, int reset);
 #define SAS_BOUNDS_ENTRY(name) sas_debug_bounds_##name,
 SAS_BOUNDS_FILES(SAS_BOUNDS_DECLARE)

@@ -1,4 +1,4 @@
-// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip, sas_mcmc.hip, sas_order.hip, sas_knn.hip and sas_skin.hip: arithmetic, the bounds-checked build, DPP reductions and row sums, contract T6 per pair, and the start of a workgroup on one tile of a frame (pixel layout, pixel state, the tile's list, the truncated-list rule).
+// sas_device.h -- device-side helpers shared by sas_kernels.hip, sas_tile.hip, sas_mesh.hip, sas_query.hip, sas_match.hip, sas_cloud.hip, sas_fuse.hip, sas_grad.hip, sas_fit.hip, sas_loss.hip, sas_density.hip, sas_mcmc.hip, sas_order.hip, sas_knn.hip, sas_skin.hip and sas_nodes.hip: arithmetic, the bounds-checked build, DPP reductions and row sums, contract T6 per pair, and the start of a workgroup on one tile of a frame (pixel layout, pixel state, the tile's list, the truncated-list rule).
 // Everything here follows the arithmetic contract of DESIGN.md: IEEE binary32 operations, fused
 // only where fma_() is written (translation units are built with -ffp-contract=off).
 #pragma once

@@ -867,3 +867,30 @@ struct SasDeformGrad {
 };
 size_t sas_deform_grad_lds_bytes(int m, bool lds, bool staged);   // dynamic LDS of one workgroup
 void sas_launch_deform_grad(hipStream_t st, const SasDeformGrad &q);
+
+// The node optimiser on the device (sas_nodes_rigidity, sas_nodes_twist_step; DESIGN.md 3, "Deformation"; sas_nodes.hip).  The state is binary64.
+#define SAS_NODES_MAX_K 8                 // neighbours per node of the rigidity term at most
+#define SAS_NODES_MAX_PARTIALS 256        // workgroups of k_nodes_rigidity at most: one partial sum of the value each (the context's 2 KiB)
+struct SasNodesRigidity {
+    const float *nodes;      // [m,3] rest positions
+    const double *Rt;        // [m,12] rows [R | t]
+    const int *nb;           // [m,kn] neighbour table; an entry outside [0, m) is ignored
+    const int *rev_start;    // [m + 1] node -> its range of rev_edge
+    const int *rev_edge;     // edge numbers i * kn + slot with nb[i][slot] == node, ascending per node; the first rev_start[m] <= m kn are read
+    int m, kn;
+    double *d_Rt;            // [m,12] written
+    double *partial;         // [SAS_NODES_MAX_PARTIALS] scratch: a workgroup's sum of |r|^2
+    double *value;           // [1] written
+};
+void sas_launch_nodes_rigidity(hipStream_t st, const SasNodesRigidity &q);   // two launches
+struct SasNodesStep {
+    const float *nodes;      // [m,3]
+    const float *d32;        // [m,12] or nullptr
+    const double *d64;       // [m,12] or nullptr: the gradient is double(d32) + weight * d64
+    double weight;
+    double *Rt, *m1, *m2;    // [m,12], [m,6], [m,6] in place
+    float *Rt32;             // [m,12] written: float(Rt)
+    int m;
+    double lr_rot, lr_trans, beta1, beta2, gain1, gain2, c1, c2, eps;   // sas_node_step_config
+};
+void sas_launch_nodes_step(hipStream_t st, const SasNodesStep &q);

@@ -6,8 +6,9 @@ nothing here touches the GPU but ``fit_node_transforms`` and ``fit_dynamic_scene
     r.bind_skin(nodes, k=4)
     r.deform(transforms_from_positions(nodes, moved_nodes))
 
-The other way round -- the node transforms from pictures -- is ``fit_node_transforms``: an optimiser on the host around
-``Rasterizer.render_backward`` and ``Rasterizer.deform_backward``, with ``rigidity`` as its regulariser.  ``fit_dynamic_scene`` fits the
+The other way round -- the node transforms from pictures -- is ``fit_node_transforms``: an optimiser around
+``Rasterizer.render_backward`` and ``Rasterizer.deform_backward``, with ``rigidity`` as its regulariser; its twist update runs on the host
+in float64 numpy, or (``optimizer="device"``) on the GPU through ``NodeOptimizer``, two HIP kernels on float64 state.  ``fit_dynamic_scene`` fits the
 REST scene (and, if asked, the transforms too) from pictures of the object in several bends: ``Rasterizer.deform_backward_rest`` sums the
 time steps' gradients, ``Rasterizer.adam_step(rest=True)`` applies them.
 """
@@ -132,18 +133,53 @@ def _neighbour_table(nodes, neighbours: int) -> np.ndarray:
     return out
 
 
-def rigidity(nodes, transforms, neighbours: int = 6):
+def reverse_table(table) -> Tuple[np.ndarray, np.ndarray]:
+    """The reverse of a neighbour table ``[M,k]``: ``(rev_start [M+1], rev_edge [M*k])`` int32.  ``rev_edge[rev_start[j] : rev_start[j+1]]``
+    lists the edge numbers ``i * k + slot`` with ``table[i, slot] == j`` in ascending order (a stable sort of the edges by their target);
+    entries outside ``[0, M)`` name no node and are left out, and ``rev_edge`` is padded with -1 behind its ``rev_start[M]`` edges.  What
+    ``Rasterizer.node_rigidity`` takes beside the table."""
+    nb = np.asarray(table)
+    if nb.ndim != 2 or nb.dtype.kind not in "iu":
+        raise ValueError(f"reverse_table: table must be an integer array [M,k], got {nb.dtype} {list(nb.shape)}")
+    M = nb.shape[0]
+    flat = nb.reshape(-1).astype(np.int64)
+    edges = np.nonzero((flat >= 0) & (flat < M))[0]
+    order = np.argsort(flat[edges], kind="stable")
+    rev_edge = np.full(flat.size, -1, np.int32)
+    rev_edge[:edges.size] = edges[order]
+    rev_start = np.zeros(M + 1, np.int32)
+    rev_start[1:] = np.cumsum(np.bincount(flat[edges], minlength=M))
+    return rev_start, rev_edge
+
+
+def rigidity(nodes, transforms, neighbours: int = 6, table=None):
     """The embedded-deformation consistency term and its gradient: ``sum_i sum_{j in N(i)} |T_i(g_j) - T_j(g_j)|^2 / (M k)`` with ``g`` the
     rest ``nodes [M,3]``, ``T_i(x) = R_i x + t_i`` the rows of ``transforms [M,3,4]`` and ``N(i)`` node i's ``k = min(neighbours, M - 1)``
     nearest other nodes, taken as ``transforms_from_positions`` takes them: neighbouring nodes should agree on where each other goes.  Zero
     for one rigid motion of all nodes.  Returns ``(value, d_transforms [M,3,4])``, float64, the gradient analytic, the twelve entries of
-    every node independent."""
+    every node independent.
+
+    ``table [M,k]`` (integers; an entry outside ``[0, M)`` names no neighbour) takes the place of that neighbour search, ``neighbours``
+    is then ignored: ``NodeOptimizer`` regularises over ``Rasterizer.knn_points``' table.  The two searches differ in one respect: the
+    search here orders by squared distances in float64, ``knn_points`` by squared distances in float32.  On a grid whose spacing is not
+    representable in binary32 (1/7, say) neighbours at EQUAL distance can therefore be chosen differently, and the host and the device
+    optimiser then regularise over slightly different edge sets; each is held to its own table.  On a grid with a representable spacing
+    (0.5) the two tables are identical."""
     g = np.asarray(nodes, np.float64).reshape(-1, 3)
     T = np.asarray(transforms, np.float64).reshape(-1, 3, 4)
     if T.shape[0] != g.shape[0]:
         raise ValueError(f"rigidity: {g.shape[0]} nodes but {T.shape[0]} transforms")
     M = g.shape[0]
-    nb = _neighbour_table(g, neighbours)
+    live = None
+    if table is None:
+        nb = _neighbour_table(g, neighbours)
+    else:
+        nb = np.asarray(table)
+        if nb.ndim != 2 or nb.shape[0] != M or nb.dtype.kind not in "iu":
+            raise ValueError(f"rigidity: table must be an integer array [{M},k], got {nb.dtype} {list(nb.shape)}")
+        nb = nb.astype(np.int64)
+        live = (nb >= 0) & (nb < M)
+        nb = np.where(live, nb, 0)
     d = np.zeros_like(T)
     k = nb.shape[1]
     if k == 0:
@@ -151,6 +187,8 @@ def rigidity(nodes, transforms, neighbours: int = 6):
     R, t = T[:, :, :3], T[:, :, 3]
     gj = g[nb]                                                                      # [M,k,3]
     res = (np.einsum("mab,mkb->mka", R, gj) + t[:, None, :]) - (np.einsum("mkab,mkb->mka", R[nb], gj) + t[nb])
+    if live is not None and not live.all():
+        res = np.where(live[:, :, None], res, 0.0)
     scale = 1.0 / (M * k)
     value = float((res * res).sum() * scale)
     dres = 2.0 * scale * res
@@ -209,6 +247,111 @@ def _twist_step(T, dT, g, m1, m2, it: int, per: int, step):
     return np.concatenate([Rn, tn[:, :, None]], axis=2), m1, m2
 
 
+class NodeOptimizer:
+    """``rigidity`` + ``_twist_step`` on the device (sas_nodes_rigidity, sas_nodes_twist_step; DESIGN.md 3, "Deformation"): the node
+    transforms of a skin bound to rasterizer ``r``, their Adam moments and the neighbour graph live there, and a step only enqueues.
+    Device tensors it owns: ``nodes [M,3]`` float32, ``table [M,k]`` int32 with its reverse ``rev_start [M+1]`` / ``rev_edge [M*k]``,
+    ``transforms64 [M,3,4]``, ``m1``, ``m2 [M,6]`` float64 and ``transforms [M,3,4]`` float32 -- ``transforms64`` rounded once, the
+    tensor ``r.deform`` reads where it is.
+
+    The table is ``r.knn_points(nodes, k=min(neighbours, M - 1))``: squared distances in float32, ties to the lower index, the node
+    itself left out by index (see ``rigidity`` on how that differs from the host's search); ``neighbours`` is 0..8.  The reverse table
+    is built once, on the host, from one read-back of it.  ``transforms [M,3,4]``: where to begin (None: the identity).  ``graph``:
+    another NodeOptimizer over the same nodes whose nodes and tables are shared (one graph for the time steps of a dynamic fit).
+    Only the constructor and ``read()`` wait for the device."""
+
+    def __init__(self, r, nodes, neighbours: int = 6, transforms=None, graph: Optional["NodeOptimizer"] = None):
+        import torch
+        from . import _capi
+        from .rasterizer import _host
+        self.r = r
+        if graph is not None:
+            self.nodes, self.table, self.rev_start, self.rev_edge = graph.nodes, graph.table, graph.rev_start, graph.rev_edge
+        else:
+            g = np.ascontiguousarray(np.asarray(_host(nodes), np.float32))
+            if g.ndim != 2 or g.shape[1] != 3 or not 1 <= g.shape[0] <= _capi.SAS_KNN_CROSS_MAX_NODES:
+                raise ValueError(f"NodeOptimizer: nodes must be [M,3] with 1 <= M <= {_capi.SAS_KNN_CROSS_MAX_NODES}, got {list(g.shape)}")
+            if not np.isfinite(g).all():
+                raise ValueError("NodeOptimizer: nodes holds non-finite entries")
+            if not 0 <= int(neighbours) <= _capi.SAS_NODES_MAX_K:
+                raise ValueError(f"NodeOptimizer: neighbours={neighbours} out of [0, {_capi.SAS_NODES_MAX_K}]")
+            self.nodes = torch.from_numpy(g).to(r.device)
+            k = int(min(int(neighbours), g.shape[0] - 1))
+            self.table = self.rev_start = self.rev_edge = None
+            if k > 0:
+                self.table = r.knn_points(self.nodes, k)["index"]
+                rs, re = reverse_table(self.table.cpu().numpy())   # (the one read-back of the set-up)
+                self.rev_start, self.rev_edge = torch.from_numpy(rs).to(r.device), torch.from_numpy(re).to(r.device)
+        M = int(self.nodes.shape[0])
+        dev = r.device
+        self.transforms64 = torch.zeros((M, 3, 4), dtype=torch.float64, device=dev)
+        self.transforms = torch.zeros((M, 3, 4), dtype=torch.float32, device=dev)
+        self.m1 = torch.zeros((M, 6), dtype=torch.float64, device=dev)
+        self.m2 = torch.zeros((M, 6), dtype=torch.float64, device=dev)
+        self._d_reg = torch.empty((M, 3, 4), dtype=torch.float64, device=dev)
+        self._zero = torch.zeros((), dtype=torch.float64, device=dev)
+        if transforms is None:
+            transforms = np.tile(np.eye(3, 4), (M, 1, 1))
+        self.set_transforms(transforms)
+
+    @property
+    def m(self) -> int:
+        return int(self.nodes.shape[0])
+
+    @property
+    def k(self) -> int:
+        return 0 if self.table is None else int(self.table.shape[1])
+
+    def set_transforms(self, T) -> None:
+        """Replace the transforms (the moments stay: ``reset_moments``).  ``T [M,3,4]``: a device tensor is converted where it is,
+        unchecked, as ``Rasterizer.deform`` takes it; anything else is checked for shape and finite entries and copied."""
+        import torch
+        M = self.m
+        if isinstance(T, torch.Tensor) and T.is_cuda:
+            if tuple(T.shape) != (M, 3, 4):
+                raise ValueError(f"NodeOptimizer: transforms must be [{M},3,4], got {list(T.shape)}")
+            self.transforms64.copy_(T.detach())
+        else:
+            a = np.ascontiguousarray(np.asarray(T.detach().numpy() if isinstance(T, torch.Tensor) else T, np.float64))
+            if a.shape != (M, 3, 4) or not np.isfinite(a).all():
+                raise ValueError(f"NodeOptimizer: transforms must be finite and [{M},3,4], got {list(a.shape)}")
+            self.transforms64.copy_(torch.from_numpy(a))
+        self.transforms.copy_(self.transforms64)   # (rounded once)
+
+    def reset_moments(self) -> None:
+        self.m1.zero_()
+        self.m2.zero_()
+
+    def rigidity(self):
+        """``(value, d_transforms [M,3,4])`` of the rigidity term at the current transforms: float64 device tensors, fresh ones."""
+        res = self.r.node_rigidity(self.nodes, self.transforms64, self.table, self.rev_start, self.rev_edge)
+        return res["value"], res["d_transforms"]
+
+    def step(self, d_transforms, it: int, per: int, step: Tuple[float, float] = (0.01, 0.01), rigidity_weight: Optional[float] = None):
+        """One step of ``fit_node_transforms``' update (0-based ``it`` of ``per``) from ``d_transforms [M,3,4]``, the float32 device
+        tensor ``Rasterizer.deform_backward`` returns (None: the rigidity term alone), plus ``rigidity_weight`` (None:
+        ``RIGIDITY_WEIGHT``) times the rigidity gradient.  Returns the rigidity VALUE at the transforms the step started from, a
+        float64 device scalar (exact 0 with a weight of 0 or without neighbours).  Two kernels, enqueued on the current stream."""
+        w = RIGIDITY_WEIGHT if rigidity_weight is None else float(rigidity_weight)
+        if not w >= 0.0:
+            raise ValueError(f"NodeOptimizer.step: rigidity_weight must be >= 0, got {rigidity_weight}")
+        it, per = int(it), int(per)
+        value, d_reg = self._zero, None
+        if w > 0.0 and self.k > 0:
+            value = self.r.node_rigidity(self.nodes, self.transforms64, self.table, self.rev_start, self.rev_edge, out=self._d_reg)["value"]
+            d_reg = self._d_reg
+        if d_transforms is None and d_reg is None:
+            raise ValueError("NodeOptimizer.step: no gradient: d_transforms is None and the rigidity term is off")
+        decay = 0.05 ** (it / max(1, per - 1))   # (the expressions of _twist_step: the same doubles)
+        self.r.node_twist_step(self.nodes, self.transforms64, self.m1, self.m2, self.transforms, d_transforms, d_reg, w,
+                               lr=(step[0] * decay, step[1] * decay), c1=1 - 0.9 ** (it + 1), c2=1 - 0.999 ** (it + 1))
+        return value
+
+    def read(self) -> np.ndarray:
+        """The transforms as float64 numpy ``[M,3,4]``.  Blocking."""
+        return self.transforms64.cpu().numpy()
+
+
 @dataclass
 class NodeFit:
     transforms: np.ndarray              # [M,3,4] float64, rows [R | t] of every node, rest -> current
@@ -223,7 +366,7 @@ RIGIDITY_WEIGHT = 0.01
 
 def fit_node_transforms(r, images, viewmats, Ks, W: int, H: int, nodes, iters: int = 200, masks=None, start=None,
                         step: Tuple[float, float] = (0.01, 0.01), factors: Sequence[int] = (2, 1), rigidity_weight: float = RIGIDITY_WEIGHT,
-                        background=(0.0, 0.0, 0.0), loss_and_grad: Optional[Callable] = None) -> NodeFit:
+                        background=(0.0, 0.0, 0.0), loss_and_grad: Optional[Callable] = None, optimizer: str = "host") -> NodeFit:
     """Fit the node transforms of the skin bound to rasterizer ``r`` so that its frames look like ``images [C,H,W,3]`` (float, 0..1) seen
     from ``viewmats [C,4,4]`` (world -> camera) with ``Ks [C,3,3]``: given pictures of the cloth as it lies now, how is it bent.  ``nodes
     [M,3]``: the rest positions the skin was bound with.  ``register.refine_group_poses``' scheme per node: Adam on an se(3) twist that
@@ -240,11 +383,22 @@ def fit_node_transforms(r, images, viewmats, Ks, W: int, H: int, nodes, iters: i
     the weights 0, 0.003, 0.01, 0.03 and 0.1 tried there it ends closest to the true deformed means (0.29 of the start after 60 iterations,
     against 0.34 without the term and 0.39 at 0.1).  The colour loss starts at 2e-3 there: scale the weight with the loss of your scene.
 
+    ``optimizer``: ``"host"`` is the loop above.  ``"device"`` runs the same schedule -- the same ``factors`` and steps per level, moments
+    reset per level, the same loss -- through a ``NodeOptimizer``: the rigidity term and the twist update are two HIP kernels on float64
+    state, ``deform`` reads the transforms where they are, the mask sums and intrinsics are formed once per level, the per-view losses
+    stay device scalars and the gradient accumulator is reused, so nothing is read back between the first iteration and the last; the
+    history comes back as one stack at the end.  Its rigidity term runs over ``Rasterizer.knn_points``' neighbour table (see
+    ``rigidity``).  ``"device"`` with ``loss_and_grad`` is refused: that is the CPU reference's door.
+
     Not fitted: skin weights, node positions; stretch and shear (the twist keeps every transform rigid).  The rest parameters are
     ``fit_dynamic_scene``'s."""
     import torch
     import torch.nn.functional as Fn
     from .rasterizer import _host
+    if optimizer not in ("host", "device"):
+        raise ValueError(f"fit_node_transforms: optimizer must be 'host' or 'device', got {optimizer!r}")
+    if optimizer == "device" and loss_and_grad is not None:
+        raise ValueError("fit_node_transforms: optimizer='device' runs the rasterizer's kernels: not with loss_and_grad")
     g = np.asarray(_host(nodes), np.float64).reshape(-1, 3)
     M = g.shape[0]
     Vs = np.asarray(_host(viewmats), np.float64).reshape(-1, 4, 4)
@@ -296,7 +450,37 @@ def fit_node_transforms(r, images, viewmats, Ks, W: int, H: int, nodes, iters: i
 
     res = NodeFit(T, float("nan"))
     per = max(1, int(iters) // max(1, len(factors)))
-    for f in factors:
+    opt = NodeOptimizer(r, g, transforms=T) if optimizer == "device" else None
+    acc, losses, levels = {}, [], []   # (device mode: the reused accumulator, the losses as device scalars, their levels)
+
+    def enqueue(cams, w, h, targets, tms, scales):
+        """The device form of ``evaluate``, one ``level``'s arguments: ``deform`` and the views' frames and backward passes, summed into
+        ``acc``; returns the colour loss as a float64 device scalar."""
+        from .autograd import prechain
+        r.deform(opt.transforms)
+        for a in acc.values():
+            a.zero_()
+        total = None
+        for v in range(C):
+            out = r.render(cams[v][0], cams[v][1], w, h, background)
+            rgb, alpha, depth = out["rgb"].clone(), out["alpha"].clone(), out["depth"].clone()
+            err = rgb - targets[v]
+            diff = tms[v][..., None] * err
+            value = (diff * err).sum().to(torch.float64) * scales[v]
+            total = value if total is None else total + value
+            g_acc, g_a, g_z = prechain(rgb, alpha, depth, background, 2.0 * scales[v] * diff, None, None)
+            acc.update(r.render_backward(cams[v][0], cams[v][1], w, h, g_acc, g_a, g_z, want=("means", key), out=acc))
+        return total
+
+    def level(f):
+        """One level, formed once: the cameras, the size, the targets and masks on the device, and the views' ``1 / (3 sum(mask) C)``."""
+        w, h, targets, tms, Kcs = at_factor(f)
+        scales = [1.0 / (3.0 * float(torch.clamp(tms[v].sum(), min=1.0)) * C) for v in range(C)]   # (host tensors: nothing waits)
+        cams = [(Vs[v].astype(np.float32), Kcs[v].astype(np.float32)) for v in range(C)]
+        return cams, w, h, targets.to(r.device), tms.to(r.device), scales
+
+    def at_factor(f):
+        """One level of the pyramid: its size, the targets and masks at it (host tensors) and the cameras' intrinsics."""
         w, h = max(1, W // f), max(1, H // f)
         if f == 1:
             targets, tms = imgs, ms
@@ -308,6 +492,25 @@ def fit_node_transforms(r, images, viewmats, Ks, W: int, H: int, nodes, iters: i
         Kcs = K0s.copy()
         Kcs[:, 0] *= w / W
         Kcs[:, 1] *= h / H
+        return w, h, targets, tms, Kcs
+
+    if opt is not None:
+        for f in factors:
+            lv = level(f)
+            opt.reset_moments()
+            for it in range(per):
+                colour = enqueue(*lv)
+                reg = opt.step(r.deform_backward(acc), it, per, step, rigidity_weight)
+                losses.append(colour + rigidity_weight * reg)
+                levels.append(int(f))
+        colour = enqueue(*level(1))   # (leaves r deformed at the result)
+        losses.append(colour + rigidity_weight * opt.rigidity()[0] if rigidity_weight > 0.0 else colour)
+        levels.append(1)
+        res.history = list(zip(levels, torch.stack(losses).cpu().tolist()))   # (the one read-back of the run, beside the transforms)
+        res.transforms, res.loss = opt.read(), res.history[-1][1]
+        return res
+    for f in factors:
+        w, h, targets, tms, Kcs = at_factor(f)
         m1, m2 = np.zeros((M, 6)), np.zeros((M, 6))
         for it in range(per):
             loss, dT = evaluate(T, Kcs, w, h, targets, tms)
@@ -330,7 +533,7 @@ class DynamicFit:
 def fit_dynamic_scene(r, frames, nodes, what: Sequence[str] = ("means", "colors"), transforms=None, fit_transforms: bool = False,
                       iters: int = 100, lrs=None, loss: Optional[str] = None, lambda_dssim: float = 0.2, loss_and_grad: Optional[Callable] = None,
                       rigidity_weight: float = RIGIDITY_WEIGHT, step: Tuple[float, float] = (0.01, 0.01), background=(0.0, 0.0, 0.0),
-                      extent: Optional[float] = None, visible_only: bool = True, bound_only: bool = False, renderer=None) -> DynamicFit:
+                      extent: Optional[float] = None, visible_only: bool = True, bound_only: bool = False, renderer=None, optimizer: str = "host") -> DynamicFit:
     """Fit the REST scene of the skin bound to rasterizer ``r`` from pictures of the object in several bends.  ``frames``: one dict per
     time step with ``images [C,H,W,3]`` (float, 0..1), ``viewmats [C,4,4]``, ``Ks [C,3,3]`` and optionally ``masks [C,H,W]``; all images
     have one size.  ``transforms [S,M,3,4]``: the node transforms of every time step, known (from a simulator) or a start value; None:
@@ -349,13 +552,22 @@ def fit_dynamic_scene(r, frames, nodes, what: Sequence[str] = ("means", "colors"
 
     ``r`` is left deformed at the last time step; ``r.clear_skin()`` then ``r.read_scene()`` is the fitted rest scene.  ``renderer``: an
     object with the rasterizer's methods used here, in ``r``'s place (tests run the loop on a CPU reference).  Moments left by an earlier
-    fit are dropped first.  Not fitted: skin weights, node positions, stretch and shear."""
+    fit are dropped first.  Not fitted: skin weights, node positions, stretch and shear.
+
+    ``optimizer`` (with ``fit_transforms``): ``"host"`` reads every time step's ``deform_backward`` back and steps it in float64 numpy.
+    ``"device"`` holds one ``NodeOptimizer`` per time step t > 0, all over one neighbour graph: the rigidity term and the twist update
+    are kernels, ``deform`` reads their transforms where they are, and nothing is read back before the run ends.  It needs the
+    rasterizer's own kernels: refused with ``renderer=``."""
     import torch
     from . import fit as _fit
     from .autograd import prechain
     from .rasterizer import _host
     R = r if renderer is None else renderer
     who = "fit_dynamic_scene"
+    if optimizer not in ("host", "device"):
+        raise ValueError(f"{who}: optimizer must be 'host' or 'device', got {optimizer!r}")
+    if optimizer == "device" and renderer is not None:
+        raise ValueError(f"{who}: optimizer='device' runs the rasterizer's kernels: not with renderer=")
     _fit._check_loss(who, loss, loss_and_grad, lambda_dssim)
     what = tuple(what)
     if not what or any(k not in _fit._WHAT for k in what):
@@ -406,11 +618,18 @@ def fit_dynamic_scene(r, frames, nodes, what: Sequence[str] = ("means", "colors"
         sk = R.read_skin()
         bound = ((sk["indices"] >= 0) & (sk["indices"] < M) & (sk["weights"] > 0)).any(dim=1)
     m1, m2 = np.zeros((S, M, 6)), np.zeros((S, M, 6))
+    opts, held = {}, {}   # the device optimisers of the time steps that move, and the device transforms of those that do not
+    if optimizer == "device":
+        for t in range(S):
+            if fit_transforms and t > 0:
+                opts[t] = NodeOptimizer(R, g, transforms=T[t], graph=opts.get(1))
+            else:
+                held[t] = torch.from_numpy(check_node_transforms(T[t])).to(R.device)
     losses = []
     for it in range(1, n_iters + 1):
         rest_acc, shared, total, dTs = {}, {}, None, {}
         for t, (V, K, img, masks, cache) in enumerate(views):
-            R.deform(np.ascontiguousarray(T[t].astype(np.float32)))
+            R.deform(opts[t].transforms if t in opts else held[t] if t in held else np.ascontiguousarray(T[t].astype(np.float32)))
             acc_t = dict(shared)
             C = V.shape[0]
             for v in range(C):
@@ -437,13 +656,19 @@ def fit_dynamic_scene(r, frames, nodes, what: Sequence[str] = ("means", "colors"
             for k, a in shared.items():
                 a.mul_(bound.reshape((-1,) + (1,) * (a.dim() - 1)).to(a.dtype))
         R.adam_step(dict(shared, **rest_acc), _fit.step_rates(rates, what, extent, it, n_iters), it, visible_only=visible_only, rest=True)
-        for t, d in dTs.items():   # (the read-backs wait for the step's work once, here)
+        for t, d in dTs.items():   # (the host's read-backs wait for the step's work once, here)
+            if t in opts:
+                val = opts[t].step(d, it - 1, n_iters, step, rigidity_weight)
+                total = total + rigidity_weight * val / S
+                continue
             dT = torch.as_tensor(d).double().cpu().numpy().reshape(M, 3, 4)
             if rigidity_weight > 0.0:
                 val, dreg = rigidity(g, T[t])
                 total, dT = total + rigidity_weight * val / S, dT + rigidity_weight * dreg
             T[t], m1[t], m2[t] = _twist_step(T[t], dT, g, m1[t], m2[t], it - 1, n_iters, step)
         losses.append(total)
+    for t, opt in opts.items():
+        T[t] = opt.read()
     R.deform(np.ascontiguousarray(T[S - 1].astype(np.float32)))
     history = [float(x) for x in torch.stack([torch.as_tensor(x, dtype=torch.float64).cpu() for x in losses])] if losses else []
     return DynamicFit(history=history, transforms=T, steps=len(history))

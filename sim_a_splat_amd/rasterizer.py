@@ -1612,6 +1612,76 @@ class Rasterizer:
         self.set_skin(idx, w)
         return {"indices": idx, "weights": w, "sigma": sigma}
 
+    def _node_array(self, t, dtype: torch.dtype, shape: Tuple[int, ...], name: str) -> torch.Tensor:
+        """``t`` as it is, if it is a contiguous device tensor of ``dtype`` and ``shape`` on this context's device; ValueError otherwise."""
+        if not self._is_mine(t, dtype, shape):
+            raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} tensor {list(shape)} on {self.device}")
+        return t
+
+    @_locked
+    def node_rigidity(self, nodes: torch.Tensor, transforms64: torch.Tensor, neighbours: Optional[torch.Tensor] = None,
+                      rev_start: Optional[torch.Tensor] = None, rev_edge: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The rigidity term of a deformation graph and its gradient on the device (sas_nodes_rigidity; DESIGN.md 3, "Deformation"):
+        what ``deform.rigidity(nodes, T, table=neighbours)`` evaluates, in float64.  Device tensors, read where they are: ``nodes [M,3]``
+        float32, ``transforms64 [M,3,4]`` float64, ``neighbours [M,kn]`` int32 (``0 <= kn <= 8``; an entry outside ``[0, M)`` is ignored;
+        None: no edges) and its reverse table as ``deform.reverse_table`` builds it: ``rev_start [M+1]`` int32 and ``rev_edge [M*kn]``
+        int32, of which the first ``rev_start[M]`` entries are read.  Returns ``value`` (a float64 device scalar) and ``d_transforms
+        [M,3,4]`` float64 (``out``: the tensor to write it to).  No atomics: the same inputs give the same bits.  Needs no
+        scene.  Only enqueues, on the current stream."""
+        if not isinstance(nodes, torch.Tensor) or nodes.dim() != 2:
+            raise ValueError("nodes must be a float32 device tensor [M,3]")
+        m = int(nodes.shape[0])
+        kn = 0 if neighbours is None else int(neighbours.shape[1]) if isinstance(neighbours, torch.Tensor) and neighbours.dim() == 2 else -1
+        if not 1 <= m <= _capi.SAS_KNN_CROSS_MAX_NODES:
+            raise ValueError(f"node_rigidity: m={m} out of [1, {_capi.SAS_KNN_CROSS_MAX_NODES}]")
+        if not 0 <= kn <= _capi.SAS_NODES_MAX_K:
+            raise ValueError(f"node_rigidity: neighbours must be [M,kn] with 0 <= kn <= {_capi.SAS_NODES_MAX_K}")
+        g = self._node_array(nodes, torch.float32, (m, 3), "nodes")
+        T = self._node_array(transforms64, torch.float64, (m, 3, 4), "transforms64")
+        nb = rs = re = None
+        if kn > 0:
+            nb = self._node_array(neighbours, torch.int32, (m, kn), "neighbours")
+            rs = self._node_array(rev_start, torch.int32, (m + 1,), "rev_start")
+            re = self._node_array(rev_edge, torch.int32, (m * kn,), "rev_edge")
+        d = torch.empty((m, 3, 4), dtype=torch.float64, device=self.device) if out is None else self._node_array(out, torch.float64, (m, 3, 4), "out")
+        v = torch.empty(1, dtype=torch.float64, device=self.device)
+        rc = self._L.sas_nodes_rigidity(self._ctx, m, _addr(g), _addr(T), kn, _addr(nb), _addr(rs), _addr(re), _addr(d), _addr(v), self._stream())
+        if rc != 0:
+            self._check(rc, "sas_nodes_rigidity")
+        return {"value": v[0], "d_transforms": d}
+
+    @_locked
+    def node_twist_step(self, nodes: torch.Tensor, transforms64: torch.Tensor, m1: torch.Tensor, m2: torch.Tensor, transforms32: torch.Tensor,
+                        d_transforms: Optional[torch.Tensor] = None, d_transforms64: Optional[torch.Tensor] = None, weight64: float = 1.0, *,
+                        lr: Tuple[float, float], c1: float, c2: float, beta1: float = 0.9, beta2: float = 0.999, gain1: float = 0.1,
+                        gain2: float = 0.001, eps: float = 1e-12) -> None:
+        """One Adam step of every node's se(3) twist about the node's current position, on the device (sas_nodes_twist_step; DESIGN.md
+        3, "Deformation"): ``deform._twist_step``'s operations per node, in float64.  Device tensors: ``nodes [M,3]`` float32; the
+        state ``transforms64 [M,3,4]``, ``m1``, ``m2 [M,6]`` float64, stepped IN PLACE; ``transforms32 [M,3,4]`` float32, written: the
+        stepped transforms rounded once, what ``deform`` takes.  The gradient is ``double(d_transforms) + weight64 * d_transforms64``
+        (float32 / float64 ``[M,3,4]``; either may be None, not both).  ``lr``: the (rotation, translation) rates of this step, decay
+        included; ``c1``, ``c2``: Adam's bias corrections ``1 - beta ** (it + 1)``; ``gain``: the weight of the new gradient in a
+        moment.  Needs no scene.  Only enqueues, on the current stream."""
+        if not isinstance(nodes, torch.Tensor) or nodes.dim() != 2:
+            raise ValueError("nodes must be a float32 device tensor [M,3]")
+        m = int(nodes.shape[0])
+        if not 1 <= m <= _capi.SAS_KNN_CROSS_MAX_NODES:
+            raise ValueError(f"node_twist_step: m={m} out of [1, {_capi.SAS_KNN_CROSS_MAX_NODES}]")
+        g = self._node_array(nodes, torch.float32, (m, 3), "nodes")
+        T = self._node_array(transforms64, torch.float64, (m, 3, 4), "transforms64")
+        a1, a2 = self._node_array(m1, torch.float64, (m, 6), "m1"), self._node_array(m2, torch.float64, (m, 6), "m2")
+        T32 = self._node_array(transforms32, torch.float32, (m, 3, 4), "transforms32")
+        d32 = None if d_transforms is None else self._node_array(d_transforms, torch.float32, (m, 3, 4), "d_transforms")
+        d64 = None if d_transforms64 is None else self._node_array(d_transforms64, torch.float64, (m, 3, 4), "d_transforms64")
+        if d32 is None and d64 is None:
+            raise ValueError("node_twist_step: one of d_transforms and d_transforms64 is required")
+        cfg = _capi.NodeStepConfig(float(lr[0]), float(lr[1]), float(beta1), float(beta2), float(c1), float(c2), float(eps), float(gain1), float(gain2))
+        rc = self._L.sas_nodes_twist_step(self._ctx, m, _addr(g), _addr(d32), _addr(d64), float(weight64), _addr(T), _addr(a1), _addr(a2), _addr(T32),
+                                          ctypes.byref(cfg), self._stream())
+        if rc != 0:
+            self._check(rc, "sas_nodes_twist_step")
+
     @_locked
     def read_order(self) -> torch.Tensor:
         """The resident scene's storage order (sas_scene_order): int32 ``[N]`` on the device, slot -> the caller's index, as

@@ -259,7 +259,7 @@ class SplatScene:
         """How is the deformable group bent, given these pictures: ``deform.fit_node_transforms`` on the nodes of ``bind_deformable``, in the
         handle's local frame, so that the scene's frames from ``cam_poses [(wxyz, position), ...]`` look like ``images [C,H,W,3]`` (uint8,
         or float 0..1) over ``masks [C,H,W]``, with the views of ``get_renders``.  ``kw`` goes to ``fit_node_transforms`` (``start``,
-        ``step``, ``factors``, ``rigidity_weight``).  The scene is left deformed at the result, which the next ``get_render*`` shows; returns
+        ``step``, ``factors``, ``rigidity_weight``; ``optimizer="device"`` keeps the nodes' twist update on the GPU, ``deform.NodeOptimizer``).  The scene is left deformed at the result, which the next ``get_render*`` shows; returns
         the ``NodeFit``.  The lock is held throughout; a scene with meshes is refused (the backward pass does not take occlusion by
         meshes)."""
         from .deform import fit_node_transforms
@@ -281,7 +281,8 @@ class SplatScene:
         ``bind_deformable``, in the handle's local frame.  ``frames``: one dict per time step with ``images [C,H,W,3]`` (uint8, or float
         0..1), ``cam_poses [(wxyz, position), ...]`` and optionally ``masks [C,H,W]``, with the views of ``get_renders``; ``transforms
         [S,M,3,4]``: the nodes' transforms of every time step.  ``what``: of ``means``, ``colors``, ``opacities`` (the covariances of a
-        scene are fixed).  ``kw`` goes to ``fit_dynamic_scene`` (``fit_transforms``, ``lrs``, ``loss``, ``rigidity_weight``, ...).  Only
+        scene are fixed).  ``kw`` goes to ``fit_dynamic_scene`` (``fit_transforms``, ``lrs``, ``loss``, ``rigidity_weight``, ...; with ``fit_transforms``, ``optimizer="device"`` keeps the nodes' twist
+        updates on the GPU).  Only
         the bound group is fitted (``bound_only=True``): every other group keeps its bits.  The fitted arrays replace the ones ``add_gaussian_splats`` was given, so
         a later upload keeps them; the scene is left deformed at the last time step.  Returns the ``DynamicFit``.  The lock is held
         throughout; a scene with meshes is refused."""
