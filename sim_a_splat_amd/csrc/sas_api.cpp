@@ -3241,20 +3241,49 @@ int sas_scene_skin_read(sas_ctx *c, int32_t *indices_out, float *weights_out)
     return SAS_OK;
 }
 
+// What the deformation and its adjoints read of the bound skin, with m node records: the fields the three calls share.  (They are fields of
+// each call and not one embedded record: the kernels take their arguments where the calls had them.)
+static const auto skin_view = [](auto &q, const sas_ctx *c, int m) {   // (a generic lambda: no template may stand in this extern "C" block)
+    const Skin &sk = c->skin;
+    q.nodes = (SasSkinNode *)sk.nodes.p;
+    q.idx = (const int4 *)sk.idx.p; q.w = (const float4 *)sk.w.p;
+    q.n = c->scene.n; q.n_pad = c->scene.n_pad;
+    q.m = m; q.kp = sk.kp();
+};
+// ... and the upstream gradients of the two adjoints, in the caller's order
+static const auto skin_grads = [](auto &q, const sas_ctx *c, const float *d_means, const float *d_quats, const float *d_cov6) {
+    q.perm = c->scene.perm;
+    q.d_means = d_means; q.d_quats = d_quats; q.d_cov6 = d_cov6;
+};
+
 // k_deform's call on the bound skin with m node records: rest planes -> live planes.
 static SasDeform deform_call(sas_ctx *c, int m)
 {
     const Skin &sk = c->skin;
-    const SasScene &sc = c->scene;
     SasDeform q{};
-    q.nodes = (SasSkinNode *)sk.nodes.p;
+    skin_view(q, c, m);
     q.r0 = (const float4 *)sk.rest0.p; q.r1 = (const float4 *)sk.rest1.p; q.r2 = (const float4 *)sk.rest2.p;
     q.g0 = (float4 *)c->planes.g0.p; q.g1 = (float4 *)c->planes.g1.p; q.g2 = (float4 *)c->planes.g2.p;
-    q.idx = (const int4 *)sk.idx.p; q.w = (const float4 *)sk.w.p;
-    q.n = sc.n; q.n_pad = sc.n_pad;
-    q.m = m; q.kp = sk.kp(); q.cov_mode = sc.cov_mode;
+    q.cov_mode = c->scene.cov_mode;
     q.lds = sizeof(SasSkinNode) * (size_t)m <= (size_t)c->skin_lds;
     return q;
+}
+
+// What both adjoints of the last sas_scene_deform refuse alike, in this order; flags: the caller's, of which it knows the bits `known`.
+static int deform_backward_checks(sas_ctx *c, const char *who, const float *d_means, const float *d_quats, const float *d_cov6, unsigned flags = 0,
+                                  unsigned known = 0)
+{
+    if (const int rc = need_scene(c, who)) return rc;
+    const Skin &sk = c->skin;
+    if (!sk.bound()) return fail(c, SAS_ERR_INVALID, "%s: no skin is bound: sas_scene_skin first", who);
+    if (sk.m <= 0) return fail(c, SAS_ERR_INVALID, "%s: no sas_scene_deform since the skin was bound", who);
+    if (flags & ~known) return fail(c, SAS_ERR_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (!d_means && !d_quats && !d_cov6) return fail(c, SAS_ERR_INVALID, "%s: d_means, d_quats and d_cov6 are all NULL", who);
+    const SasScene &sc = c->scene;
+    if (sc.cov_mode ? d_quats != nullptr : d_cov6 != nullptr)
+        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as %s: %s must be NULL", who, sc.cov_mode ? "covariances" : "quaternions",
+                    sc.cov_mode ? "d_quats" : "d_cov6");
+    return SAS_OK;
 }
 
 // The live planes again from rest planes that have changed (sas_scene_adam_step_rest): the last deformation from the node records it left on
@@ -3305,15 +3334,9 @@ int sas_scene_deform(sas_ctx *c, int m, const float *node_Rt, void *stream)
 int sas_scene_deform_backward(sas_ctx *c, const float *d_means, const float *d_quats, const float *d_cov6, float *d_node_Rt, void *stream)
 {
     const char *who = "sas_scene_deform_backward";
-    if (const int rc = need_scene(c, who)) return rc;
+    if (const int rc = deform_backward_checks(c, who, d_means, d_quats, d_cov6)) return rc;
     Skin &sk = c->skin;
-    if (!sk.bound()) return fail(c, SAS_ERR_INVALID, "%s: no skin is bound: sas_scene_skin first", who);
-    if (sk.m <= 0) return fail(c, SAS_ERR_INVALID, "%s: no sas_scene_deform since the skin was bound", who);
-    if (!d_means && !d_quats && !d_cov6) return fail(c, SAS_ERR_INVALID, "%s: d_means, d_quats and d_cov6 are all NULL", who);
     const SasScene &sc = c->scene;
-    if (sc.cov_mode ? d_quats != nullptr : d_cov6 != nullptr)
-        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as %s: %s must be NULL", who, sc.cov_mode ? "covariances" : "quaternions",
-                    sc.cov_mode ? "d_quats" : "d_cov6");
     if (!d_node_Rt) return fail(c, SAS_ERR_INVALID, "%s: d_node_Rt is NULL", who);
     HIP_TRY(c, hipSetDevice(c->device));
     const int m = sk.m;
@@ -3325,13 +3348,10 @@ int sas_scene_deform_backward(sas_ctx *c, const float *d_means, const float *d_q
     }
     hipStream_t st = (hipStream_t)stream;
     SasDeformGrad q{};
-    q.perm = sc.perm;
-    q.d_means = d_means; q.d_quats = d_quats; q.d_cov6 = d_cov6;
-    q.nodes = (const SasSkinNode *)sk.nodes.p;
+    skin_grads(q, c, d_means, d_quats, d_cov6);
+    skin_view(q, c, m);
     q.r0 = (const float4 *)sk.rest0.p; q.r1 = (const float4 *)sk.rest1.p; q.r2 = (const float4 *)sk.rest2.p;
-    q.idx = (const int4 *)sk.idx.p; q.w = (const float4 *)sk.w.p;
-    q.n = sc.n; q.n_pad = sc.n_pad;
-    q.m = m; q.kp = sk.kp(); q.cov_mode = sc.cov_mode;
+    q.cov_mode = sc.cov_mode;
     q.lds = acc_bytes <= (size_t)c->skin_grad_lds;
     q.staged = c->skin_grad_staged >= 0 ? c->skin_grad_staged : (!q.lds || acc_bytes <= SAS_SKIN_GRAD_STAGED_LDS_BYTES);
     // a persistent grid: as many workgroups per CU as their LDS allows, 4 at the most
@@ -3357,16 +3377,9 @@ int sas_scene_deform_backward_rest(sas_ctx *c, const float *d_means, const float
                                    float *d_rest_quats, float *d_rest_cov6, unsigned flags, void *stream)
 {
     const char *who = "sas_scene_deform_backward_rest";
-    if (const int rc = need_scene(c, who)) return rc;
+    if (const int rc = deform_backward_checks(c, who, d_means, d_quats, d_cov6, flags, SAS_DEFORM_REST_BOUND_ONLY)) return rc;
     const Skin &sk = c->skin;
-    if (!sk.bound()) return fail(c, SAS_ERR_INVALID, "%s: no skin is bound: sas_scene_skin first", who);
-    if (sk.m <= 0) return fail(c, SAS_ERR_INVALID, "%s: no sas_scene_deform since the skin was bound", who);
-    if (flags & ~SAS_DEFORM_REST_BOUND_ONLY) return fail(c, SAS_ERR_INVALID, "%s: unknown flags 0x%x", who, flags);
-    if (!d_means && !d_quats && !d_cov6) return fail(c, SAS_ERR_INVALID, "%s: d_means, d_quats and d_cov6 are all NULL", who);
     const SasScene &sc = c->scene;
-    if (sc.cov_mode ? d_quats != nullptr : d_cov6 != nullptr)
-        return fail(c, SAS_ERR_INVALID, "%s: the scene was uploaded as %s: %s must be NULL", who, sc.cov_mode ? "covariances" : "quaternions",
-                    sc.cov_mode ? "d_quats" : "d_cov6");
     struct Pair { const char *name; const float *in; float *out; int width; };
     const Pair pairs[3] = {{"means", d_means, d_rest_means, 3}, {"quats", d_quats, d_rest_quats, 4}, {"cov6", d_cov6, d_rest_cov6, 6}};
     for (const Pair &p : pairs)
@@ -3386,12 +3399,8 @@ int sas_scene_deform_backward_rest(sas_ctx *c, const float *d_means, const float
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     SasDeformRestGrad q{};
-    q.perm = sc.perm;
-    q.d_means = d_means; q.d_quats = d_quats; q.d_cov6 = d_cov6;
-    q.nodes = (const SasSkinNode *)sk.nodes.p;
-    q.idx = (const int4 *)sk.idx.p; q.w = (const float4 *)sk.w.p;
-    q.n = sc.n; q.n_pad = sc.n_pad;
-    q.m = sk.m; q.kp = sk.kp();
+    skin_grads(q, c, d_means, d_quats, d_cov6);
+    skin_view(q, c, sk.m);
     q.lds = sizeof(SasSkinNode) * (size_t)sk.m <= (size_t)c->skin_lds;
     q.bound_only = (flags & SAS_DEFORM_REST_BOUND_ONLY) != 0;
     q.o_means = d_rest_means; q.o_quats = d_rest_quats; q.o_cov6 = d_rest_cov6;

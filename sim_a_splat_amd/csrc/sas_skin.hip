@@ -9,30 +9,38 @@
 //   k_skin_bind     one lane per slot: the caller's [N,k] indices and weights through perm into planes of int4 / float4 per slot, stride
 //                   n_pad, padded to 4 or 8 entries with (-1, 0).
 //   k_skin_read     the inverse: the planes back in the caller's order.
-//   k_skin_nodes    one lane per node: R -> the unit quaternion wxyz, by the branch of the largest of (trace, R00, R11, R22); the node's
-//                   64-byte record (SasSkinNode).
-//   k_deform<LDS,KP> one lane per slot: the rest planes and the slot's skin planes -> g0, g1, g2.  The LIVE entries are those with
-//                   0 <= index < m and weight > 0; every other entry is ignored, so no index reaches memory unchecked.
-//                     no live entry: the three planes are the rest planes' bits
-//                     mean:     m' = m + (sum_j w_j ((R_j m + t_j) - m)) / W,  W = sum_j w_j, in entry order; R m + t = ((r0 x + r1 y) + r2 z) + t
-//                     rotation: q_b = normalize(sum_j s_j w_j q_j), s_j = -1 where dot(q_j, q_first) < 0 (q_first: the first live entry's); a sum
-//                               of norm zero or not finite gives q_first
-//                     quaternion scenes: g1 = q_b (x) q_rest (Hamilton, not renormalised: the projection normalises), scales untouched
-//                     covariance scenes: Sigma' = R_b Sigma_rest R_b^T, R_b the matrix of q_b
-//                   Opacity, the group-id bits and g2.z of a covariance scene are the rest planes' bits.  LDS: the node records are staged
-//                   in LDS by every workgroup (m * 64 B within SAS_SKIN_LDS_BYTES); else each lane reads its records from global memory.  The
-//                   arithmetic is the same text on the same values: both paths give the same bits.
+//
+// The skin walk: what the forward (k_deform) and both adjoints (k_deform_grad, k_deform_rest_grad) decide alike.  Each rule stands ONCE, as a
+// helper or the macro below, and the three kernels use it: an adjoint differentiates the forward as evaluated, every decision a constant, and
+// it is the forward's decision because it is the same text.  Nothing is saved by the forward but the node records.  What stays in each
+// kernel is the walk's control flow: the loop over the entries, `first live entry sets q_first`, and what the kernel adds.
+//   node records    k_skin_nodes, one lane per node: the rows [R | t] as given and R -> the unit quaternion wxyz, by the branch of the largest
+//                   of (trace, R00, R11, R22) (quat_branch); the 64-byte record (SasSkinNode).  NodeRecords<LDS> reads them: staged in LDS by
+//                   every workgroup (m * 64 B within SAS_SKIN_LDS_BYTES), else from global memory -- the same values, so the same bits.
+//   live entries    SkinEntries<KP>: a slot's KP = 4 or 8 entries from its skin planes.  LIVE (SKIN_LIVE) are those with 0 <= index < m and weight > 0;
+//                   every other entry is ignored, so no index reaches memory unchecked.  W = sum_j w_j over the live entries, in entry order.
+//   blend           QuatBlend: q_b = normalize(sum_j s_j w_j q_j) over the live entries in entry order, s_j = -1 where dot(q_j, q_first) < 0
+//                   (q_first: the first live entry's).
+//   fallback        a sum of norm zero or not finite gives q_b = q_first (QuatBlend::unit).
+//   R_b             quat_matrix: the matrix of q_b.
 // Arithmetic: IEEE binary32, nothing fused (-ffp-contract=off, no fma_); tests/tools/skin_ref.py restates it.
 //
+//   k_deform<LDS,KP> one lane per slot: the rest planes and the slot's skin planes -> g0, g1, g2.
+//                     no live entry: the three planes are the rest planes' bits
+//                     mean:     m' = m + (sum_j w_j ((R_j m + t_j) - m)) / W, in entry order; R m + t = ((r0 x + r1 y) + r2 z) + t
+//                     quaternion scenes: g1 = q_b (x) q_rest (Hamilton, not renormalised: the projection normalises), scales untouched
+//                     covariance scenes: Sigma' = R_b Sigma_rest R_b^T
+//                   Opacity, the group-id bits and g2.z of a covariance scene are the rest planes' bits.
+//
 // The adjoint (sas_scene_deform_backward): from per-Gaussian gradients of the deformed means and orientations to the gradient of every node's
-// twelve entries [R | t], each an independent variable.  Every decision of the forward is a constant: which entries are live, the branch of
-// k_skin_nodes, the signs s_j, the fallback to q_first.  Nothing is saved by the forward but the node records.
-//   k_deform_grad<LDS,STAGED,KP>  one lane per slot, a persistent grid walking the slots with a stride.  The lane recomputes W, a, n2, q_b, q_first
-//                   and the signs, and forms one 16-float ROW per live entry: dt (3) = (w_j / W) g, the mean path's dR (9) = (w_j / W) g m_rest^T,
-//                   dq_j (4) = s_j w_j da with da = (dq_b - q_b (q_b . dq_b)) / |a| (fallback: dq_b to the first live entry, nothing to the others).
-//                   dq_b: quaternion scenes, the product of h with q_rest that transposes q_b (x) q_rest; covariance scenes, dR_b = 2 G R_b Sigma
-//                   (G the symmetric matrix of the six, off-diagonals halved) through the matrix of q_b.  The rows are summed per node into
-//                   acc [m,16], zeroed on the stream by every call.
+// twelve entries [R | t], each an independent variable.
+//   k_deform_grad<LDS,STAGED,KP>  one lane per slot, a persistent grid walking the slots with a stride; its LDS is the accumulator's, so the
+//                   quaternions come from global memory, and without an orientation gradient they are not read at all.  On top of the walk
+//                   (with the index of the first live entry) it forms one 16-float ROW per live entry: dt (3) = (w_j / W) g, the mean path's
+//                   dR (9) = (w_j / W) g m_rest^T, dq_j (4) = s_j w_j da with da = (dq_b - q_b (q_b . dq_b)) / |a| (fallback: dq_b to the first
+//                   live entry, nothing to the others).  dq_b: quaternion scenes, the product of h with q_rest that transposes q_b (x) q_rest;
+//                   covariance scenes, dR_b = 2 G R_b Sigma (G the symmetric matrix of the six, off-diagonals halved) through the matrix of
+//                   q_b.  The rows are summed per node into acc [m,16], zeroed on the stream by every call.
 //   k_skin_nodes_grad  one lane per node: acc row -> the 12 outputs.  dt and dR as summed, plus du = (dq - q (q . dq)) / |u| through the transpose of
 //                   the branch's linear map R -> u.  A node no live entry names reads a zero row and writes exact zeros.
 // Sizing.  At a million Gaussians and k = 4 there are 4 M rows of 64 B: 256 MB of adds.  Straight to memory that is 0.2 ms at best at the chip-wide
@@ -56,18 +64,19 @@
 //
 // The adjoint to the REST arrays (sas_scene_deform_backward_rest): the same gradients of the deformed arrays -> gradients of the Gaussians that are
 // stored, ADDED to the caller's arrays (the deformation differs per time step: the sum over time steps is taken here).
-//   k_deform_rest_grad<LDS,KP>  one lane per slot, k_deform's shape: the gradients are gathered at perm[slot] as k_adam_scene gathers them and the
-//                   results are added at the same caller's index; the skin planes and the node records as k_deform reads them (LDS up to
-//                   SAS_SKIN_LDS_BYTES, else global: the same text on the same values, the same bits).  The forward is linear in each rest array,
-//                   so no rest plane is read.  With the forward's decisions as constants (live entries, signs, normalisation, fallback):
+//   k_deform_rest_grad<LDS,KP>  one lane per slot, k_deform's shape: the gradients are gathered at perm[slot] as k_adam_scene gathers them
+//                   (load_row, as k_deform_grad gathers them) and the results are added at the same caller's index.  The forward is linear
+//                   in each rest array, so no rest plane is read, and the mean path is computed only where d_means is given:
 //                     mean:       d_m = g + (sum_j w_j ((R_j^T g) - g)) / W, in entry order; R^T g = (r0 gx + r1 gy) + r2 gz by columns
-//                     quaternion: d_q_rest = conj(q_b) (x) h, the transpose of the left product by q_b; q_b recomputed as k_deform does
+//                     quaternion: d_q_rest = conj(q_b) (x) h, the transpose of the left product by q_b
 //                     covariance: dSigma = R_b^T G R_b, G the symmetric matrix of the six with the off-diagonals halved; an off-diagonal of
 //                                 the result's six is the sum of its two entries (render_backward's convention for `covariances`)
 //                     no live entry: the gradient is added as it is (SAS_DEFORM_REST_BOUND_ONLY: nothing is added)
 //                   Each output depends on its own input alone, and a zero input adds zeros.  No atomics: a Gaussian has one lane, the same inputs
 //                   give the same bits on every run and on both paths.
 #include "sas_device.h"
+
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -167,67 +176,168 @@ __global__ __launch_bounds__(kThreads) void k_skin_read(const SasSkinRead q)
     }
 }
 
-// R -> wxyz.  Each branch's four terms are 4 c times the quaternion, c its largest component: no cancellation in the term that is squared.
+// ---- the skin walk's shared pieces (the header: each rule once) ---------------------------------------------------------------------------------
+// R -> u = 4 c times the quaternion wxyz, c its largest component: no cancellation in the term that is squared.
+// Returns the branch; inv = 1 / |u|.
+DEV int quat_branch(const float (&R)[3][3], float4 &u, float &inv)
+{
+    const float r00 = R[0][0], r01 = R[0][1], r02 = R[0][2], r10 = R[1][0], r11 = R[1][1], r12 = R[1][2], r20 = R[2][0], r21 = R[2][1], r22 = R[2][2];
+    const float tr = (r00 + r11) + r22;
+    int branch;
+    float w, x, y, z;
+    if (tr >= r00 && tr >= r11 && tr >= r22) {
+        branch = 0; w = 1.0f + tr; x = r21 - r12; y = r02 - r20; z = r10 - r01;
+    } else if (r00 >= r11 && r00 >= r22) {
+        branch = 1; w = r21 - r12; x = ((1.0f + r00) - r11) - r22; y = r01 + r10; z = r02 + r20;
+    } else if (r11 >= r22) {
+        branch = 2; w = r02 - r20; x = r01 + r10; y = ((1.0f + r11) - r00) - r22; z = r12 + r21;
+    } else {
+        branch = 3; w = r10 - r01; x = r02 + r20; y = r12 + r21; z = ((1.0f + r22) - r00) - r11;
+    }
+    inv = 1.0f / sqrtf(((w * w + x * x) + y * y) + z * z);
+    u = make_float4(w, x, y, z);
+    return branch;
+}
+
+// The ONE live test: entry (id, w) under m nodes.  A macro, not a function: a function is optimised on its own before it is inlined and hands
+// the kernel one flag, and the kernels then branch once per entry where this text branches on the index first -- other kernels
+// (profiles/skin_refactor_isa_gate.txt), measured slower.  For the same reason the helpers below hold no decision of the walk, only its
+// straight-line pieces, and the loops over planes and entries stay in the kernels.
+#define SKIN_LIVE(id, w, m) ((id) >= 0 && (id) < (m) && (w) > 0.0f)
+
+// a slot's entries; a lane that loads nothing holds none that is live
+template <int KP>
+struct SkinEntries {
+    int id[KP];
+    float wt[KP];
+    DEV SkinEntries()
+    {
+#pragma unroll
+        for (int e = 0; e < KP; ++e) { id[e] = -1; wt[e] = 0.0f; }
+    }
+    // plane p of the skin planes: entries 4p .. 4p + 3 of slot j
+    DEV void load(int p, const int4 *idx, const float4 *w, long long n_pad, long long j)
+    {
+        const int4 v = idx[(long long)p * n_pad + j];
+        const float4 u = w[(long long)p * n_pad + j];
+        id[4 * p] = v.x; id[4 * p + 1] = v.y; id[4 * p + 2] = v.z; id[4 * p + 3] = v.w;
+        wt[4 * p] = u.x; wt[4 * p + 1] = u.y; wt[4 * p + 2] = u.z; wt[4 * p + 3] = u.w;
+    }
+};
+
+// the node records as float4 parts (0..2: the rows [R | t], 3: the quaternion); LDS: staged by the whole workgroup in lds, SAS_IN under `code`
+template <bool LDS>
+struct NodeRecords {
+    const float4 *g_nodes;
+    float4 *s_nodes;
+    DEV NodeRecords(const SasSkinNode *nodes, int m, float4 *lds = nullptr, int code = 0) : g_nodes(reinterpret_cast<const float4 *>(nodes)), s_nodes(lds)
+    {
+        if constexpr (LDS) {
+            for (int t = threadIdx.x; t < 4 * m; t += kThreads)
+                if (SAS_IN(t, SAS_SKIN_LDS_BYTES / 16, code)) s_nodes[t] = g_nodes[t];
+            __syncthreads();
+        }
+    }
+    DEV float4 rec(int node, int part) const
+    {
+        if constexpr (LDS) return s_nodes[4 * node + part];
+        else return g_nodes[4 * (long long)node + part];
+    }
+};
+
+// the sign-aligned quaternion sum over the live entries, in entry order
+struct QuatBlend {
+    float4 f = make_float4(1.0f, 0.0f, 0.0f, 0.0f), aq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // q_first, the sum
+    // s_j w_j
+    DEV float sign(const float4 qn, float we) const
+    {
+        const float dot = ((qn.x * f.x + qn.y * f.y) + qn.z * f.z) + qn.w * f.w;
+        return dot < 0.0f ? -we : we;
+    }
+    DEV void add(const float4 qn, float we)
+    {
+        const float sw = sign(qn, we);
+        aq.x = aq.x + sw * qn.x;
+        aq.y = aq.y + sw * qn.y;
+        aq.z = aq.z + sw * qn.z;
+        aq.w = aq.w + sw * qn.w;
+    }
+    // q_b wxyz, normalised: true; or (the sum's norm zero or not finite) q_first as it stands: false.  inv = 1 / |sum|, or 1
+    DEV bool unit(float4 &qb, float &inv) const
+    {
+        const float n2 = ((aq.x * aq.x + aq.y * aq.y) + aq.z * aq.z) + aq.w * aq.w;
+        qb = f;
+        inv = 1.0f;
+        if (n2 > 0.0f && n2 < INFINITY) {
+            inv = 1.0f / sqrtf(n2);
+            qb = make_float4(aq.x * inv, aq.y * inv, aq.z * inv, aq.w * inv);
+            return true;
+        }
+        return false;
+    }
+};
+
+// the matrix of the unit quaternion (bw, bx, by, bz)
+DEV void quat_matrix(float (&R)[3][3], float bw, float bx, float by, float bz)
+{
+    R[0][0] = 1.0f - 2.0f * (by * by + bz * bz); R[0][1] = 2.0f * (bx * by - bw * bz); R[0][2] = 2.0f * (bx * bz + bw * by);
+    R[1][0] = 2.0f * (bx * by + bw * bz); R[1][1] = 1.0f - 2.0f * (bx * bx + bz * bz); R[1][2] = 2.0f * (by * bz - bw * bx);
+    R[2][0] = 2.0f * (bx * bz - bw * by); R[2][1] = 2.0f * (by * bz + bw * bx); R[2][2] = 1.0f - 2.0f * (bx * bx + by * by);
+}
+
+// one caller's row read: v[c] = in[at + c] (the adjoints' gather of an upstream gradient at the caller's index)
+template <int C>
+DEV void load_row(const float *in, long long at, float *v)
+{
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = in[at + c];
+}
+
+// launch(KP as an integral constant): the instantiation for kp entries per slot
+template <typename F>
+void with_kp(int kp, F &&launch)
+{
+    if (kp <= 4) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, 8>{});
+}
+
+// ---- the forward ----------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_skin_nodes(const SasDeform q)
 {
     const int a = blockIdx.x * kThreads + threadIdx.x;
     if (a >= q.m) return;
     const float *G = q.node_Rt + 12 * (long long)a;
-    const float r00 = G[0], r01 = G[1], r02 = G[2], r10 = G[4], r11 = G[5], r12 = G[6], r20 = G[8], r21 = G[9], r22 = G[10];
-    const float tr = (r00 + r11) + r22;
-    float w, x, y, z;
-    if (tr >= r00 && tr >= r11 && tr >= r22) {
-        w = 1.0f + tr; x = r21 - r12; y = r02 - r20; z = r10 - r01;
-    } else if (r00 >= r11 && r00 >= r22) {
-        w = r21 - r12; x = ((1.0f + r00) - r11) - r22; y = r01 + r10; z = r02 + r20;
-    } else if (r11 >= r22) {
-        w = r02 - r20; x = r01 + r10; y = ((1.0f + r11) - r00) - r22; z = r12 + r21;
-    } else {
-        w = r10 - r01; x = r02 + r20; y = r12 + r21; z = ((1.0f + r22) - r00) - r11;
-    }
-    const float inv = 1.0f / sqrtf(((w * w + x * x) + y * y) + z * z);
+    const float R[3][3] = {{G[0], G[1], G[2]}, {G[4], G[5], G[6]}, {G[8], G[9], G[10]}};
+    float4 u;
+    float inv;
+    quat_branch(R, u, inv);
     if (!SAS_IN(a, q.m, 1507)) return;
     float4 *rec = reinterpret_cast<float4 *>(q.nodes + a);
     rec[0] = make_float4(G[0], G[1], G[2], G[3]);
     rec[1] = make_float4(G[4], G[5], G[6], G[7]);
     rec[2] = make_float4(G[8], G[9], G[10], G[11]);
-    rec[3] = make_float4(w * inv, x * inv, y * inv, z * inv);
+    rec[3] = make_float4(u.x * inv, u.y * inv, u.z * inv, u.w * inv);
 }
 
 template <bool LDS, int KP>
 __global__ __launch_bounds__(kThreads) void k_deform(const SasDeform q)
 {
     __shared__ float4 s_nodes[LDS ? SAS_SKIN_LDS_BYTES / 16 : 1];
-    const float4 *g_nodes = reinterpret_cast<const float4 *>(q.nodes);
-    if constexpr (LDS) {
-        for (int t = threadIdx.x; t < 4 * q.m; t += kThreads)
-            if (SAS_IN(t, SAS_SKIN_LDS_BYTES / 16, 1508)) s_nodes[t] = g_nodes[t];
-        __syncthreads();
-    }
+    const NodeRecords<LDS> nodes(q.nodes, q.m, s_nodes, 1508);
     const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;   // slot
     if (j >= q.n || !SAS_IN(j, q.n_pad, 1509)) return;
-    auto rec = [&](int node, int part) -> float4 {
-        if constexpr (LDS) return s_nodes[4 * node + part];
-        else return g_nodes[4 * (long long)node + part];
-    };
     const float4 r0 = q.r0[j], r1 = q.r1[j], r2 = q.r2[j];
-    int id[KP];
-    float wt[KP];
+    SkinEntries<KP> en;
 #pragma unroll
-    for (int p = 0; p < KP / 4; ++p) {
-        const int4 v = q.idx[(long long)p * q.n_pad + j];
-        const float4 u = q.w[(long long)p * q.n_pad + j];
-        id[4 * p] = v.x; id[4 * p + 1] = v.y; id[4 * p + 2] = v.z; id[4 * p + 3] = v.w;
-        wt[4 * p] = u.x; wt[4 * p + 1] = u.y; wt[4 * p + 2] = u.z; wt[4 * p + 3] = u.w;
-    }
+    for (int p = 0; p < KP / 4; ++p) en.load(p, q.idx, q.w, q.n_pad, j);
     float ax = 0.0f, ay = 0.0f, az = 0.0f, W = 0.0f;
-    float4 f = make_float4(1.0f, 0.0f, 0.0f, 0.0f), aq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    QuatBlend blend;
     bool any = false;
 #pragma unroll
     for (int e = 0; e < KP; ++e) {
-        const float we = wt[e];
-        if (!(id[e] >= 0 && id[e] < q.m && we > 0.0f)) continue;   // not live
-        const float4 a = rec(id[e], 0), b = rec(id[e], 1), c = rec(id[e], 2), qn = rec(id[e], 3);
+        const float we = en.wt[e];
+        if (!SKIN_LIVE(en.id[e], we, q.m)) continue;
+        const float4 a = nodes.rec(en.id[e], 0), b = nodes.rec(en.id[e], 1), c = nodes.rec(en.id[e], 2), qn = nodes.rec(en.id[e], 3);
         const float y0 = ((a.x * r0.x + a.y * r0.y) + a.z * r0.z) + a.w;
         const float y1 = ((b.x * r0.x + b.y * r0.y) + b.z * r0.z) + b.w;
         const float y2 = ((c.x * r0.x + c.y * r0.y) + c.z * r0.z) + c.w;
@@ -235,35 +345,27 @@ __global__ __launch_bounds__(kThreads) void k_deform(const SasDeform q)
         ay = ay + we * (y1 - r0.y);
         az = az + we * (y2 - r0.z);
         W = W + we;
-        if (!any) f = qn;
+        if (!any) blend.f = qn;
         any = true;
-        const float dot = ((qn.x * f.x + qn.y * f.y) + qn.z * f.z) + qn.w * f.w;
-        const float sw = dot < 0.0f ? -we : we;
-        aq.x = aq.x + sw * qn.x;
-        aq.y = aq.y + sw * qn.y;
-        aq.z = aq.z + sw * qn.z;
-        aq.w = aq.w + sw * qn.w;
+        blend.add(qn, we);
     }
     float4 o0 = r0, o1 = r1, o2 = r2;
     if (any) {
         o0.x = r0.x + ax / W;
         o0.y = r0.y + ay / W;
         o0.z = r0.z + az / W;
-        const float n2 = ((aq.x * aq.x + aq.y * aq.y) + aq.z * aq.z) + aq.w * aq.w;
-        float bw = f.x, bx = f.y, by = f.z, bz = f.w;
-        if (n2 > 0.0f && n2 < INFINITY) {
-            const float inv = 1.0f / sqrtf(n2);
-            bw = aq.x * inv; bx = aq.y * inv; by = aq.z * inv; bz = aq.w * inv;
-        }
+        float4 qb;
+        float inv;
+        blend.unit(qb, inv);
+        const float bw = qb.x, bx = qb.y, by = qb.z, bz = qb.w;
         if (!q.cov_mode) {   // q_b (x) q_rest
             o1.x = ((bw * r1.x - bx * r1.y) - by * r1.z) - bz * r1.w;
             o1.y = ((bw * r1.y + bx * r1.x) + by * r1.w) - bz * r1.z;
             o1.z = ((bw * r1.z - bx * r1.w) + by * r1.x) + bz * r1.y;
             o1.w = ((bw * r1.w + bx * r1.z) - by * r1.y) + bz * r1.x;
         } else {             // R_b Sigma R_b^T
-            const float R[3][3] = {{1.0f - 2.0f * (by * by + bz * bz), 2.0f * (bx * by - bw * bz), 2.0f * (bx * bz + bw * by)},
-                                   {2.0f * (bx * by + bw * bz), 1.0f - 2.0f * (bx * bx + bz * bz), 2.0f * (by * bz - bw * bx)},
-                                   {2.0f * (bx * bz - bw * by), 2.0f * (by * bz + bw * bx), 1.0f - 2.0f * (bx * bx + by * by)}};
+            float R[3][3];
+            quat_matrix(R, bw, bx, by, bz);
             const float S[3][3] = {{r1.x, r1.y, r1.z}, {r1.y, r1.w, r2.x}, {r1.z, r2.x, r2.y}};
             float T[3][3];
 #pragma unroll
@@ -303,74 +405,52 @@ __global__ __launch_bounds__(kThreads) void k_deform_grad(const SasDeformGrad q)
         __syncthreads();
     }
     float *acc = LDS ? s_acc : q.acc;
-    const float4 *g_nodes = reinterpret_cast<const float4 *>(q.nodes);
+    const NodeRecords<false> nodes(q.nodes, q.m);            // (the LDS is the accumulator's)
     const bool rot = q.d_quats != nullptr || q.d_cov6 != nullptr;
     const int n_col = rot ? kRow : 12;                                 // without an orientation gradient the dq columns are never touched
     // the walk is the same for every lane of the workgroup: the barriers of the staged form are met by all
     for (long long base = (long long)blockIdx.x * kThreads; base < q.n; base += (long long)gridDim.x * kThreads) {
         const long long j = base + tid;   // slot
         const bool active = j < q.n && SAS_IN(j, q.n_pad, 1510);
-        int id[KP];
-        float wt[KP];
-#pragma unroll
-        for (int e = 0; e < KP; ++e) { id[e] = -1; wt[e] = 0.0f; }
+        SkinEntries<KP> en;
         float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0, r2 = r0;
-        float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+        float g[3] = {0.0f, 0.0f, 0.0f};
         float h[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         if (active) {
             r0 = q.r0[j]; r1 = q.r1[j]; r2 = q.r2[j];
-#pragma unroll
-            for (int p = 0; p < KP / 4; ++p) {
-                const int4 v = q.idx[(long long)p * q.n_pad + j];
-                const float4 u = q.w[(long long)p * q.n_pad + j];
-                id[4 * p] = v.x; id[4 * p + 1] = v.y; id[4 * p + 2] = v.z; id[4 * p + 3] = v.w;
-                wt[4 * p] = u.x; wt[4 * p + 1] = u.y; wt[4 * p + 2] = u.z; wt[4 * p + 3] = u.w;
-            }
+        #pragma unroll
+    for (int p = 0; p < KP / 4; ++p) en.load(p, q.idx, q.w, q.n_pad, j);
             const long long i = q.perm[j];   // the caller's index
             if (SAS_IN(i, q.n, 1511)) {
-                if (q.d_means) { gx = q.d_means[3 * i]; gy = q.d_means[3 * i + 1]; gz = q.d_means[3 * i + 2]; }
-                if (q.d_quats) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) h[c] = q.d_quats[4 * i + c];
-                }
-                if (q.d_cov6) {
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) h[c] = q.d_cov6[6 * i + c];
-                }
+                if (q.d_means) load_row<3>(q.d_means, 3 * i, g);
+                if (q.d_quats) load_row<4>(q.d_quats, 4 * i, h);
+                if (q.d_cov6) load_row<6>(q.d_cov6, 6 * i, h);
             }
         }
         // the forward's sums again: W, a, q_first
         float W = 0.0f;
-        float4 f = make_float4(1.0f, 0.0f, 0.0f, 0.0f), aq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        QuatBlend blend;
         bool any = false;
         int first = -1;
 #pragma unroll
         for (int e = 0; e < KP; ++e) {
-            const float we = wt[e];
-            if (!(id[e] >= 0 && id[e] < q.m && we > 0.0f)) continue;   // not live
+            const float we = en.wt[e];
+            if (!SKIN_LIVE(en.id[e], we, q.m)) continue;
             W = W + we;
             if (!rot) { any = true; continue; }
-            const float4 qn = g_nodes[4 * (long long)id[e] + 3];
-            if (!any) { f = qn; first = e; }
+            const float4 qn = nodes.rec(en.id[e], 3);
+            if (!any) { blend.f = qn; first = e; }
             any = true;
-            const float dot = ((qn.x * f.x + qn.y * f.y) + qn.z * f.z) + qn.w * f.w;
-            const float sw = dot < 0.0f ? -we : we;
-            aq.x = aq.x + sw * qn.x;
-            aq.y = aq.y + sw * qn.y;
-            aq.z = aq.z + sw * qn.z;
-            aq.w = aq.w + sw * qn.w;
+            blend.add(qn, we);
         }
         // dq_b, then da (or, in the fallback, dq_first)
         float4 da = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         bool fallback = false;
         if (any && rot) {
-            const float n2 = ((aq.x * aq.x + aq.y * aq.y) + aq.z * aq.z) + aq.w * aq.w;
-            float bw = f.x, bx = f.y, by = f.z, bz = f.w, inv = 1.0f;
-            fallback = !(n2 > 0.0f && n2 < INFINITY);
-            if (!fallback) {
-                inv = 1.0f / sqrtf(n2);
-                bw = aq.x * inv; bx = aq.y * inv; by = aq.z * inv; bz = aq.w * inv;
-            }
+            float4 qb;
+            float inv;
+            fallback = !blend.unit(qb, inv);
+            const float bw = qb.x, bx = qb.y, by = qb.z, bz = qb.w;
             float dw, dx, dy, dz;
             if (!q.cov_mode) {   // q' = q_b (x) q_rest, bilinear: h times the conjugate of q_rest
                 dw = ((h[0] * r1.x + h[1] * r1.y) + h[2] * r1.z) + h[3] * r1.w;
@@ -378,9 +458,8 @@ __global__ __launch_bounds__(kThreads) void k_deform_grad(const SasDeformGrad q)
                 dy = ((h[2] * r1.x - h[0] * r1.z) + h[1] * r1.w) - h[3] * r1.y;
                 dz = ((h[3] * r1.x - h[0] * r1.w) - h[1] * r1.z) + h[2] * r1.y;
             } else {             // Sigma' = R_b Sigma R_b^T: D = dR_b = 2 G (R_b Sigma), then the matrix of q_b
-                const float R[3][3] = {{1.0f - 2.0f * (by * by + bz * bz), 2.0f * (bx * by - bw * bz), 2.0f * (bx * bz + bw * by)},
-                                       {2.0f * (bx * by + bw * bz), 1.0f - 2.0f * (bx * bx + bz * bz), 2.0f * (by * bz - bw * bx)},
-                                       {2.0f * (bx * bz - bw * by), 2.0f * (by * bz + bw * bx), 1.0f - 2.0f * (bx * bx + by * by)}};
+                float R[3][3];
+                quat_matrix(R, bw, bx, by, bz);
                 const float S[3][3] = {{r1.x, r1.y, r1.z}, {r1.y, r1.w, r2.x}, {r1.z, r2.x, r2.y}};
                 const float G[3][3] = {{2.0f * h[0], h[1], h[2]}, {h[1], 2.0f * h[3], h[4]}, {h[2], h[4], 2.0f * h[5]}};   // 2 G
                 float T[3][3], D[3][3];
@@ -407,14 +486,14 @@ __global__ __launch_bounds__(kThreads) void k_deform_grad(const SasDeformGrad q)
         // one row per live entry
 #pragma unroll
         for (int e = 0; e < KP; ++e) {
-            const float we = wt[e];
-            const bool live = id[e] >= 0 && id[e] < q.m && we > 0.0f;
+            const float we = en.wt[e];
+            const bool live = SKIN_LIVE(en.id[e], we, q.m);
             float row[kRow];
 #pragma unroll
             for (int c = 0; c < kRow; ++c) row[c] = 0.0f;
             if (live) {
                 const float cw = we / W;
-                const float cg[3] = {cw * gx, cw * gy, cw * gz};
+                const float cg[3] = {cw * g[0], cw * g[1], cw * g[2]};
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
                     row[a] = cg[a];
@@ -424,11 +503,7 @@ __global__ __launch_bounds__(kThreads) void k_deform_grad(const SasDeformGrad q)
                 }
                 if (rot) {
                     float sw = e == first ? 1.0f : 0.0f;   // the fallback: q_b is q_first as it stands
-                    if (!fallback) {
-                        const float4 qn = g_nodes[4 * (long long)id[e] + 3];
-                        const float dot = ((qn.x * f.x + qn.y * f.y) + qn.z * f.z) + qn.w * f.w;
-                        sw = dot < 0.0f ? -we : we;
-                    }
+                    if (!fallback) sw = blend.sign(nodes.rec(en.id[e], 3), we);
                     row[12] = sw * da.x; row[13] = sw * da.y; row[14] = sw * da.z; row[15] = sw * da.w;
                 }
             }
@@ -437,7 +512,7 @@ __global__ __launch_bounds__(kThreads) void k_deform_grad(const SasDeformGrad q)
                     float4 *dst = reinterpret_cast<float4 *>(s_stage + tid * kRow);
 #pragma unroll
                     for (int c = 0; c < kRow / 4; ++c) dst[c] = make_float4(row[4 * c], row[4 * c + 1], row[4 * c + 2], row[4 * c + 3]);
-                    s_node[tid] = live ? id[e] : -1;
+                    s_node[tid] = live ? en.id[e] : -1;
                 }
                 __syncthreads();
                 const int col = tid % kRow;
@@ -450,10 +525,10 @@ __global__ __launch_bounds__(kThreads) void k_deform_grad(const SasDeformGrad q)
                 }
                 __syncthreads();   // the stage is free for the next entry
             } else {
-                if (live && SAS_IN(id[e], q.m, 1514)) {
+                if (live && SAS_IN(en.id[e], q.m, 1514)) {
 #pragma unroll
                     for (int c = 0; c < kRow; ++c)
-                        if (c < n_col) add_to(acc, (long long)id[e] * kRow + c, row[c]);
+                        if (c < n_col) add_to(acc, (long long)en.id[e] * kRow + c, row[c]);
                 }
             }
         }
@@ -479,20 +554,10 @@ __global__ __launch_bounds__(kThreads) void k_skin_nodes_grad(const SasDeformGra
     if (q.d_quats != nullptr || q.d_cov6 != nullptr) {
         const float4 *rec = reinterpret_cast<const float4 *>(q.nodes + a);
         const float4 G0 = rec[0], G1 = rec[1], G2 = rec[2], qn = rec[3];
-        const float r00 = G0.x, r01 = G0.y, r02 = G0.z, r10 = G1.x, r11 = G1.y, r12 = G1.z, r20 = G2.x, r21 = G2.y, r22 = G2.z;
-        const float tr = (r00 + r11) + r22;
-        int branch;
-        float w, x, y, z;
-        if (tr >= r00 && tr >= r11 && tr >= r22) {
-            branch = 0; w = 1.0f + tr; x = r21 - r12; y = r02 - r20; z = r10 - r01;
-        } else if (r00 >= r11 && r00 >= r22) {
-            branch = 1; w = r21 - r12; x = ((1.0f + r00) - r11) - r22; y = r01 + r10; z = r02 + r20;
-        } else if (r11 >= r22) {
-            branch = 2; w = r02 - r20; x = r01 + r10; y = ((1.0f + r11) - r00) - r22; z = r12 + r21;
-        } else {
-            branch = 3; w = r10 - r01; x = r02 + r20; y = r12 + r21; z = ((1.0f + r22) - r00) - r11;
-        }
-        const float inv = 1.0f / sqrtf(((w * w + x * x) + y * y) + z * z);
+        const float R[3][3] = {{G0.x, G0.y, G0.z}, {G1.x, G1.y, G1.z}, {G2.x, G2.y, G2.z}};
+        float4 u;
+        float inv;
+        const int branch = quat_branch(R, u, inv);
         const float dot = ((qn.x * dq.x + qn.y * dq.y) + qn.z * dq.z) + qn.w * dq.w;
         const float uw = (dq.x - qn.x * dot) * inv, ux = (dq.y - qn.y * dot) * inv, uy = (dq.z - qn.z * dot) * inv, uz = (dq.w - qn.w * dot) * inv;
         // the transpose of the branch's map R -> u
@@ -534,52 +599,31 @@ template <bool LDS, int KP>
 __global__ __launch_bounds__(kThreads) void k_deform_rest_grad(const SasDeformRestGrad q)
 {
     __shared__ float4 s_nodes[LDS ? SAS_SKIN_LDS_BYTES / 16 : 1];
-    const float4 *g_nodes = reinterpret_cast<const float4 *>(q.nodes);
-    if constexpr (LDS) {
-        for (int t = threadIdx.x; t < 4 * q.m; t += kThreads)
-            if (SAS_IN(t, SAS_SKIN_LDS_BYTES / 16, 1517)) s_nodes[t] = g_nodes[t];
-        __syncthreads();
-    }
+    const NodeRecords<LDS> nodes(q.nodes, q.m, s_nodes, 1517);
     const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;   // slot
     if (j >= q.n || !SAS_IN(j, q.n_pad, 1518)) return;
-    const long long i = q.perm[j];                                        // the caller's index
+    const long long i = q.perm[j];                                     // the caller's index
     if (!SAS_IN(i, q.n, 1519)) return;
-    auto rec = [&](int node, int part) -> float4 {
-        if constexpr (LDS) return s_nodes[4 * node + part];
-        else return g_nodes[4 * (long long)node + part];
-    };
-    int id[KP];
-    float wt[KP];
+    SkinEntries<KP> en;
 #pragma unroll
-    for (int p = 0; p < KP / 4; ++p) {
-        const int4 v = q.idx[(long long)p * q.n_pad + j];
-        const float4 u = q.w[(long long)p * q.n_pad + j];
-        id[4 * p] = v.x; id[4 * p + 1] = v.y; id[4 * p + 2] = v.z; id[4 * p + 3] = v.w;
-        wt[4 * p] = u.x; wt[4 * p + 1] = u.y; wt[4 * p + 2] = u.z; wt[4 * p + 3] = u.w;
-    }
+    for (int p = 0; p < KP / 4; ++p) en.load(p, q.idx, q.w, q.n_pad, j);
     const bool rot = q.d_quats != nullptr || q.d_cov6 != nullptr;
     float g[3] = {0.0f, 0.0f, 0.0f};
     float h[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (q.d_means) { g[0] = q.d_means[3 * i]; g[1] = q.d_means[3 * i + 1]; g[2] = q.d_means[3 * i + 2]; }
-    if (q.d_quats) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) h[c] = q.d_quats[4 * i + c];
-    }
-    if (q.d_cov6) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) h[c] = q.d_cov6[6 * i + c];
-    }
+    if (q.d_means) load_row<3>(q.d_means, 3 * i, g);
+    if (q.d_quats) load_row<4>(q.d_quats, 4 * i, h);
+    if (q.d_cov6) load_row<6>(q.d_cov6, 6 * i, h);
     // the forward's walk over the live entries: W and a again, and the mean path's sum_j w_j ((R_j^T g) - g)
     float ax = 0.0f, ay = 0.0f, az = 0.0f, W = 0.0f;
-    float4 f = make_float4(1.0f, 0.0f, 0.0f, 0.0f), aq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    QuatBlend blend;
     bool any = false;
 #pragma unroll
     for (int e = 0; e < KP; ++e) {
-        const float we = wt[e];
-        if (!(id[e] >= 0 && id[e] < q.m && we > 0.0f)) continue;   // not live
+        const float we = en.wt[e];
+        if (!SKIN_LIVE(en.id[e], we, q.m)) continue;
         W = W + we;
         if (q.d_means) {
-            const float4 a = rec(id[e], 0), b = rec(id[e], 1), c = rec(id[e], 2);
+            const float4 a = nodes.rec(en.id[e], 0), b = nodes.rec(en.id[e], 1), c = nodes.rec(en.id[e], 2);
             const float u0 = (a.x * g[0] + b.x * g[1]) + c.x * g[2];
             const float u1 = (a.y * g[0] + b.y * g[1]) + c.y * g[2];
             const float u2 = (a.z * g[0] + b.z * g[1]) + c.z * g[2];
@@ -588,14 +632,9 @@ __global__ __launch_bounds__(kThreads) void k_deform_rest_grad(const SasDeformRe
             az = az + we * (u2 - g[2]);
         }
         if (rot) {
-            const float4 qn = rec(id[e], 3);
-            if (!any) f = qn;
-            const float dot = ((qn.x * f.x + qn.y * f.y) + qn.z * f.z) + qn.w * f.w;
-            const float sw = dot < 0.0f ? -we : we;
-            aq.x = aq.x + sw * qn.x;
-            aq.y = aq.y + sw * qn.y;
-            aq.z = aq.z + sw * qn.z;
-            aq.w = aq.w + sw * qn.w;
+            const float4 qn = nodes.rec(en.id[e], 3);
+            if (!any) blend.f = qn;
+            blend.add(qn, we);
         }
         any = true;
     }
@@ -608,21 +647,18 @@ __global__ __launch_bounds__(kThreads) void k_deform_rest_grad(const SasDeformRe
     }
     if (q.d_means) add_row<3>(q.o_means, 3 * i, {g[0] + ax / W, g[1] + ay / W, g[2] + az / W});
     if (!rot) return;
-    const float n2 = ((aq.x * aq.x + aq.y * aq.y) + aq.z * aq.z) + aq.w * aq.w;
-    float bw = f.x, bx = f.y, by = f.z, bz = f.w;
-    if (n2 > 0.0f && n2 < INFINITY) {
-        const float inv = 1.0f / sqrtf(n2);
-        bw = aq.x * inv; bx = aq.y * inv; by = aq.z * inv; bz = aq.w * inv;
-    }
+    float4 qb;
+    float inv;
+    blend.unit(qb, inv);
+    const float bw = qb.x, bx = qb.y, by = qb.z, bz = qb.w;
     if (q.d_quats) {   // q' = q_b (x) q_rest: the transpose of the left product, the conjugate of q_b times h
         add_row<4>(q.o_quats, 4 * i, {((bw * h[0] + bx * h[1]) + by * h[2]) + bz * h[3],
                                       ((bw * h[1] - bx * h[0]) + bz * h[2]) - by * h[3],
                                       ((bw * h[2] - by * h[0]) - bz * h[1]) + bx * h[3],
                                       ((bw * h[3] - bz * h[0]) + by * h[1]) - bx * h[2]});
-    } else {           // Sigma' = R_b Sigma R_b^T: dSigma = R_b^T G R_b, G the symmetric matrix of the six with its off-diagonals halved
-        const float R[3][3] = {{1.0f - 2.0f * (by * by + bz * bz), 2.0f * (bx * by - bw * bz), 2.0f * (bx * bz + bw * by)},
-                               {2.0f * (bx * by + bw * bz), 1.0f - 2.0f * (bx * bx + bz * bz), 2.0f * (by * bz - bw * bx)},
-                               {2.0f * (bx * bz - bw * by), 2.0f * (by * bz + bw * bx), 1.0f - 2.0f * (bx * bx + by * by)}};
+    } else {              // Sigma' = R_b Sigma R_b^T: dSigma = R_b^T G R_b, G the symmetric matrix of the six with its off-diagonals halved
+        float R[3][3];
+        quat_matrix(R, bw, bx, by, bz);
         const float G[3][3] = {{h[0], 0.5f * h[1], 0.5f * h[2]}, {0.5f * h[1], h[3], 0.5f * h[4]}, {0.5f * h[2], 0.5f * h[4], h[5]}};
         float T[3][3];   // R_b^T G
 #pragma unroll
@@ -633,32 +669,6 @@ __global__ __launch_bounds__(kThreads) void k_deform_rest_grad(const SasDeformRe
         // an off-diagonal of the six stands for two entries of Sigma: both halves' gradients add
         add_row<6>(q.o_cov6, 6 * i, {out(0, 0), out(0, 1) + out(1, 0), out(0, 2) + out(2, 0), out(1, 1), out(1, 2) + out(2, 1), out(2, 2)});
     }
-}
-
-template <bool LDS>
-void launch_deform_rest_grad(hipStream_t st, const SasDeformRestGrad &q, unsigned blocks)
-{
-    if (q.kp <= 4) hipLaunchKernelGGL((k_deform_rest_grad<LDS, 4>), dim3(blocks), dim3(kThreads), 0, st, q);
-    else hipLaunchKernelGGL((k_deform_rest_grad<LDS, 8>), dim3(blocks), dim3(kThreads), 0, st, q);
-}
-
-template <bool LDS, bool STAGED>
-void launch_deform_grad(hipStream_t st, const SasDeformGrad &q, size_t lds_bytes)
-{
-    auto go = [&](auto kernel) {
-        // above 64 KiB a kernel has to ask for its dynamic LDS
-        if (lds_bytes > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)q.blocks), dim3(kThreads), lds_bytes, st, q);
-    };
-    if (q.kp <= 4) go(k_deform_grad<LDS, STAGED, 4>);
-    else go(k_deform_grad<LDS, STAGED, 8>);
-}
-
-template <bool LDS>
-void launch_deform(hipStream_t st, const SasDeform &q, unsigned blocks)
-{
-    if (q.kp <= 4) hipLaunchKernelGGL((k_deform<LDS, 4>), dim3(blocks), dim3(kThreads), 0, st, q);
-    else hipLaunchKernelGGL((k_deform<LDS, 8>), dim3(blocks), dim3(kThreads), 0, st, q);
 }
 
 }  // namespace
@@ -697,18 +707,24 @@ void sas_launch_deform(hipStream_t st, const SasDeform &q)
 void sas_launch_deform_planes(hipStream_t st, const SasDeform &q)
 {
     if (q.n <= 0 || q.m <= 0) return;
-    const unsigned blocks = (unsigned)((q.n + kThreads - 1) / kThreads);
-    if (q.lds && (size_t)q.m * sizeof(SasSkinNode) <= SAS_SKIN_LDS_BYTES) launch_deform<true>(st, q, blocks);
-    else launch_deform<false>(st, q, blocks);
+    const dim3 blocks((unsigned)((q.n + kThreads - 1) / kThreads));
+    const bool lds = q.lds && (size_t)q.m * sizeof(SasSkinNode) <= SAS_SKIN_LDS_BYTES;
+    with_kp(q.kp, [&](auto KP) {
+        if (lds) hipLaunchKernelGGL((k_deform<true, decltype(KP)::value>), blocks, dim3(kThreads), 0, st, q);
+        else hipLaunchKernelGGL((k_deform<false, decltype(KP)::value>), blocks, dim3(kThreads), 0, st, q);
+    });
 }
 
 // the rest arrays' gradients, added to: one launch on st
 void sas_launch_deform_rest_grad(hipStream_t st, const SasDeformRestGrad &q)
 {
     if (q.n <= 0 || q.m <= 0) return;
-    const unsigned blocks = (unsigned)((q.n + kThreads - 1) / kThreads);
-    if (q.lds && (size_t)q.m * sizeof(SasSkinNode) <= SAS_SKIN_LDS_BYTES) launch_deform_rest_grad<true>(st, q, blocks);
-    else launch_deform_rest_grad<false>(st, q, blocks);
+    const dim3 blocks((unsigned)((q.n + kThreads - 1) / kThreads));
+    const bool lds = q.lds && (size_t)q.m * sizeof(SasSkinNode) <= SAS_SKIN_LDS_BYTES;
+    with_kp(q.kp, [&](auto KP) {
+        if (lds) hipLaunchKernelGGL((k_deform_rest_grad<true, decltype(KP)::value>), blocks, dim3(kThreads), 0, st, q);
+        else hipLaunchKernelGGL((k_deform_rest_grad<false, decltype(KP)::value>), blocks, dim3(kThreads), 0, st, q);
+    });
 }
 
 size_t sas_deform_grad_lds_bytes(int m, bool lds, bool staged)
@@ -722,9 +738,17 @@ void sas_launch_deform_grad(hipStream_t st, const SasDeformGrad &q)
     if (q.n <= 0 || q.m <= 0 || q.blocks <= 0) return;
     const bool lds = q.lds && sizeof(float) * kRow * (size_t)q.m <= SAS_SKIN_GRAD_LDS_MAX;
     const size_t bytes = sas_deform_grad_lds_bytes(q.m, lds, q.staged != 0);
-    if (lds && q.staged) launch_deform_grad<true, true>(st, q, bytes);
-    else if (lds) launch_deform_grad<true, false>(st, q, bytes);
-    else if (q.staged) launch_deform_grad<false, true>(st, q, bytes);
-    else launch_deform_grad<false, false>(st, q, bytes);
+    auto go = [&](auto kernel) {
+        // above 64 KiB a kernel has to ask for its dynamic LDS
+        if (bytes > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)q.blocks), dim3(kThreads), bytes, st, q);
+    };
+    with_kp(q.kp, [&](auto KP) {
+        constexpr int kp = decltype(KP)::value;
+        if (lds && q.staged) go(k_deform_grad<true, true, kp>);
+        else if (lds) go(k_deform_grad<true, false, kp>);
+        else if (q.staged) go(k_deform_grad<false, true, kp>);
+        else go(k_deform_grad<false, false, kp>);
+    });
     hipLaunchKernelGGL(k_skin_nodes_grad, dim3((unsigned)((q.m + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, q);
 }

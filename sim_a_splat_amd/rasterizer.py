@@ -1487,6 +1487,32 @@ class Rasterizer:
             self._deform_m = m
         self._in_flight(True)
 
+    def _deform_grads(self, who: str, grads, out=None) -> Dict[str, Optional[torch.Tensor]]:
+        """What ``deform_backward`` and ``deform_backward_rest`` check alike: ``grads`` (and ``out``, where given) a dict, a skin and a
+        ``deform`` since the bind, no gradient of the other orientation form.  Returns ``grads``' checked tensor, or None, under each of
+        ``means``, ``quats`` and ``covariances``: not all are None."""
+        if not isinstance(grads, dict):
+            raise ValueError(f"{who}: grads must be a dict as render_backward returns it")
+        if out is not None and not isinstance(out, dict):
+            raise ValueError(f"{who}: out must be a dict of tensors to accumulate into")
+        if not self.has_skin:
+            raise SasError(f"{who}: no skin is bound")
+        if self._deform_m <= 0:
+            raise SasError(f"{who}: no deform since the skin was bound")
+        shapes = self._scene_shapes()
+        other = "covariances" if self.covariance_form == "quats" else "quats"
+        if grads.get(other) is not None:
+            raise ValueError(f"{who}: the scene was uploaded as {'quats' if other == 'covariances' else 'covariances'}: drop grads[{other!r}]")
+        given = {}
+        for k in ("means", "quats", "covariances"):
+            t = grads.get(k)
+            if t is not None and not self._is_mine(t, torch.float32, shapes[k]):
+                raise ValueError(f"grads[{k!r}] must be a contiguous float32 tensor {shapes[k]} on {self.device}")
+            given[k] = t
+        if all(t is None for t in given.values()):
+            raise ValueError(f"{who}: grads holds neither means nor the orientation gradient")
+        return given
+
     @_locked
     def deform_backward(self, grads: Dict[str, torch.Tensor]) -> torch.Tensor:
         """The adjoint of the last ``deform`` (sas_scene_deform_backward; DESIGN.md 3, "Deformation"): from the gradients of the DEFORMED
@@ -1501,24 +1527,7 @@ class Rasterizer:
         entry names gets an exact zero row, zero gradients give exact zeros; otherwise the sums are float atomics and vary in their
         last bits from run to run.  ``SasError`` without a skin or without a ``deform`` since the bind.  Only enqueues, on the current
         stream."""
-        if not isinstance(grads, dict):
-            raise ValueError("deform_backward: grads must be a dict as render_backward returns it")
-        if not self.has_skin:
-            raise SasError("deform_backward: no skin is bound")
-        if self._deform_m <= 0:
-            raise SasError("deform_backward: no deform since the skin was bound")
-        shapes = self._scene_shapes()
-        other = "covariances" if self.covariance_form == "quats" else "quats"
-        if grads.get(other) is not None:
-            raise ValueError(f"deform_backward: the scene was uploaded as {'quats' if other == 'covariances' else 'covariances'}: drop grads[{other!r}]")
-        ptrs = {}
-        for k in ("means", "quats", "covariances"):
-            t = grads.get(k)
-            if t is not None and not self._is_mine(t, torch.float32, shapes[k]):
-                raise ValueError(f"grads[{k!r}] must be a contiguous float32 tensor {shapes[k]} on {self.device}")
-            ptrs[k] = None if t is None else t.data_ptr()
-        if all(p is None for p in ptrs.values()):
-            raise ValueError("deform_backward: grads holds neither means nor the orientation gradient")
+        ptrs = {k: None if t is None else t.data_ptr() for k, t in self._deform_grads("deform_backward", grads).items()}
         out = torch.empty((self._deform_m, 3, 4), dtype=torch.float32, device=self.device)
         rc = self._L.sas_scene_deform_backward(self._ctx, ptrs["means"], ptrs["quats"], ptrs["covariances"], _addr(out), self._stream())
         if rc != 0:
@@ -1540,26 +1549,12 @@ class Rasterizer:
         nothing (skins bound with ``group=``: the static rest of the scene is then not stepped).  An all-zero gradient adds exact zeros.
         No atomics: the same inputs give the same bits on every run.  ``SasError`` without a skin or without a ``deform`` since the
         bind.  Only enqueues, on the current stream."""
-        if not isinstance(grads, dict):
-            raise ValueError("deform_backward_rest: grads must be a dict as render_backward returns it")
-        if out is not None and not isinstance(out, dict):
-            raise ValueError("deform_backward_rest: out must be a dict of tensors to accumulate into")
-        if not self.has_skin:
-            raise SasError("deform_backward_rest: no skin is bound")
-        if self._deform_m <= 0:
-            raise SasError("deform_backward_rest: no deform since the skin was bound")
         shapes = self._scene_shapes()
-        other = "covariances" if self.covariance_form == "quats" else "quats"
-        if grads.get(other) is not None:
-            raise ValueError(f"deform_backward_rest: the scene was uploaded as {'quats' if other == 'covariances' else 'covariances'}: drop grads[{other!r}]")
         ptrs, res = {}, {}
-        for k in ("means", "quats", "covariances"):
-            t = grads.get(k)
+        for k, t in self._deform_grads("deform_backward_rest", grads, out).items():
             ptrs[k] = ptrs["o_" + k] = None
             if t is None:
                 continue
-            if not self._is_mine(t, torch.float32, shapes[k]):
-                raise ValueError(f"grads[{k!r}] must be a contiguous float32 tensor {shapes[k]} on {self.device}")
             o = out.get(k) if out else None
             if o is None:
                 o = torch.zeros(shapes[k], dtype=torch.float32, device=self.device)
@@ -1567,8 +1562,6 @@ class Rasterizer:
                 raise ValueError(f"out[{k!r}] must be a contiguous float32 tensor {shapes[k]} on {self.device}")
             res[k] = o
             ptrs[k], ptrs["o_" + k] = t.data_ptr(), o.data_ptr()
-        if not res:
-            raise ValueError("deform_backward_rest: grads holds neither means nor the orientation gradient")
         if self.n == 0:
             return res
         rc = self._L.sas_scene_deform_backward_rest(self._ctx, ptrs["means"], ptrs["quats"], ptrs["covariances"], ptrs["o_means"], ptrs["o_quats"],

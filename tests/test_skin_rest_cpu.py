@@ -1,6 +1,6 @@
 """CPU: the yardstick of the deformation's adjoint to the REST arrays (tests/tools/skin_rest_ref.py) and the host side of the fit across
-time steps (deform.fit_dynamic_scene; DESIGN.md 3, "Deformation").  The kit's tensor form of the restatement is held to
-skin_grad_ref.deform_torch bit for bit; its float64 gradient is held to central differences; every case keeps its decisions 1e-4 from their
+time steps (deform.fit_dynamic_scene; DESIGN.md 3, "Deformation").  The restatement (skin_grad_ref.deform_torch) called with rest tensors
+is held to itself called with rest arrays bit for bit; its float64 gradient is held to central differences; every case keeps its decisions 1e-4 from their
 thresholds in every entry order of the yardstick; the header, the exports and the Python front end carry the two new entry points;
 fit_dynamic_scene runs on the float64 reference and its rest means approach the truth.  No GPU."""
 import inspect
@@ -27,10 +27,11 @@ ALL = [(name, form) for name in rr.CASES for form in rr.FORMS]
 
 @pytest.mark.parametrize("name,form", ALL)
 def test_tensor_form_is_deform_torch_bit_for_bit(name, form):
+    """The one restatement called with rest TENSORS (the form gradients flow through) against itself called with rest arrays."""
     c = rr.case(name, form)
     for dt in (torch.float64, torch.float32):
         theirs = sg.deform_torch(c["rest"], c["indices"], c["weights"], torch.from_numpy(c["transforms"]).to(dt), dt)
-        mine = rr.deform_torch_rest({k: torch.from_numpy(v) for k, v in c["rest"].items()}, c["indices"], c["weights"], torch.from_numpy(c["transforms"]), dt)
+        mine = sg.deform_torch({k: torch.from_numpy(v) for k, v in c["rest"].items()}, c["indices"], c["weights"], torch.from_numpy(c["transforms"]), dt)
         assert set(mine) == set(theirs)
         for k in theirs:
             assert mine[k].dtype == dt and torch.equal(mine[k], theirs[k]), (name, form, dt, k)
@@ -48,7 +49,7 @@ def test_reference_against_central_differences(form):
 
         def loss(rest):
             with torch.no_grad():
-                o = rr.deform_torch_rest({k: torch.from_numpy(v) for k, v in rest.items()}, c["indices"], c["weights"], torch.from_numpy(c["transforms"]))
+                o = sg.deform_torch({k: torch.from_numpy(v) for k, v in rest.items()}, c["indices"], c["weights"], torch.from_numpy(c["transforms"]))
             return float((o["means"].numpy() * dm).sum() + (o[key].numpy() * do).sum())
 
         got = rr.grad64(name, form)
@@ -102,10 +103,14 @@ def test_kit_sizes_and_entry_points_follow_the_library():
     assert inspect.signature(Rasterizer.adam_step).parameters["rest"].default is False
     assert inspect.signature(autograd.render_differentiable).parameters["rest_params"].default is False
     assert callable(SplatScene.fit_dynamic)
-    # a new bounds code per site of the new kernel
+    # one bounds code per checked site of the file, each a literal written once; the rest adjoint's three stand in its kernel, as arguments
+    # of SAS_IN or of the helper that checks under the caller's code
     text = (ROOT / "sim_a_splat_amd" / "csrc" / "sas_skin.hip").read_text()
-    body = text[text.index("void k_deform_rest_grad"):text.index("void launch_deform_rest_grad")]
-    assert sorted(int(v) for v in re.findall(r"SAS_IN\([^;]*?, (\d+)\)", body)) == [1517, 1518, 1519]
+    code = "\n".join(line.split("//")[0] for line in text.split("\n"))
+    assert sorted(int(v) for v in re.findall(r"\b15\d\d\b", code)) == list(range(1501, 1520))
+    body = code[code.index("void k_deform_rest_grad"):]
+    body = body[:body.index("\n}\n")]
+    assert sorted(int(v) for v in re.findall(r"\([^;]*?, (15\d\d)\)", body)) == [1517, 1518, 1519]
 
 
 def test_fit_dynamic_scene_on_the_reference():

@@ -48,11 +48,12 @@ def node_quats_torch(R: torch.Tensor) -> torch.Tensor:
     return q * inv[:, None]
 
 
-def deform_torch(rest, indices, weights, node_Rt: torch.Tensor, dtype=torch.float64):
-    """``skin_ref.deform_ref`` in torch: ``node_Rt [m,3,4]`` a tensor of ``dtype`` (the float32 values, converted), through which gradients
-    flow.  Returns the deformed ``means`` and ``quats`` or ``covariances`` as tensors of ``dtype``."""
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32))).to(dtype)
-    G = node_Rt.reshape(-1, 3, 4)
+def deform_torch(rest, indices, weights, node_Rt, dtype=torch.float64):
+    """``skin_ref.deform_ref`` in torch: ``node_Rt [m,3,4]`` a tensor (of ``dtype``: the float32 values, converted) through which gradients
+    flow.  ``rest``: arrays, taken as their float32 values, or TENSORS, used as they are, so that gradients flow to them too; both are
+    converted to ``dtype``.  Returns the deformed ``means`` and ``quats`` or ``covariances`` as tensors of ``dtype``."""
+    T = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32)))).to(dtype)
+    G = torch.as_tensor(node_Rt).to(dtype).reshape(-1, 3, 4)
     m = G.shape[0]
     R, t = G[:, :, :3], G[:, :, 3]
     Q = node_quats_torch(R)

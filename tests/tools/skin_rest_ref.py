@@ -2,9 +2,8 @@
 csrc/sas_skin.hip, k_deform_rest_grad), the cases the CPU and GPU tests of ``Rasterizer.deform_backward_rest`` share, and the recovery case
 of ``deform.fit_dynamic_scene`` with its float64 stand-in renderer.  Every case is from a fixed seed.
 
-``skin_grad_ref.deform_torch`` reads its rest arrays through numpy (``np.asarray`` of a tensor that requires grad raises), so a gradient
-cannot flow to them through it as it stands.  ``deform_torch_rest`` is therefore the same expressions in the same order on rest TENSORS, taken
-as they are; tests/test_skin_rest_cpu.py holds it to ``deform_torch`` bit for bit, in float64 and in float32, on every case.
+``skin_grad_ref.deform_torch`` takes its rest arrays as arrays or as TENSORS, which it uses as they are: a gradient flows to them;
+tests/test_skin_rest_cpu.py holds the two call forms to each other bit for bit, in float64 and in float32, on every case.
 ``rest_grad_ref`` is its vector-Jacobian product with respect to the rest tensors: float64 is the reference; float32 restates the device's
 arithmetic up to the order of the sums over a Gaussian's entries, which autograd chooses: ``f32_err`` is the largest error, per array, of
 the float32 evaluation against the float64 one over ORDERS shuffled orders of the entries (each order against the float64 evaluation in
@@ -33,63 +32,6 @@ MARGIN = sg.MARGIN
 ORDERS = 4              # shuffled entry orders of f32_err
 
 
-def deform_torch_rest(rest, indices, weights, node_Rt, dtype=torch.float64):
-    """``deform_torch`` with ``rest`` a dict of TENSORS (``means`` and ``quats`` or ``covariances``), used as they are and converted to
-    ``dtype``: gradients flow to them.  The same expressions in the same order."""
-    G = torch.as_tensor(node_Rt).to(dtype).reshape(-1, 3, 4)
-    m = G.shape[0]
-    R, t = G[:, :, :3], G[:, :, 3]
-    Q = node_quats_torch(R)
-    mean = rest["means"].to(dtype)
-    idx = torch.from_numpy(np.asarray(indices).astype(np.int64))
-    wts = torch.from_numpy(np.ascontiguousarray(np.asarray(weights, np.float32))).to(dtype)
-    n, k = idx.shape
-    acc = torch.zeros((n, 3), dtype=dtype)
-    W = torch.zeros(n, dtype=dtype)
-    aq = torch.zeros((n, 4), dtype=dtype)
-    f = torch.zeros((n, 4), dtype=dtype)
-    any_ = torch.zeros(n, dtype=torch.bool)
-    for e in range(k):
-        live = (idx[:, e] >= 0) & (idx[:, e] < m) & (wts[:, e] > 0)
-        ic = torch.where(live, idx[:, e], torch.zeros_like(idx[:, e]))
-        we = wts[:, e]
-        Rj, tj, qj = R[ic], t[ic], Q[ic]
-        y = ((Rj[:, :, 0] * mean[:, None, 0] + Rj[:, :, 1] * mean[:, None, 1]) + Rj[:, :, 2] * mean[:, None, 2]) + tj
-        acc = torch.where(live[:, None], acc + we[:, None] * (y - mean), acc)
-        W = torch.where(live, W + we, W)
-        f = torch.where((live & ~any_)[:, None], qj, f)
-        any_ = any_ | live
-        dot = ((qj[:, 0] * f[:, 0] + qj[:, 1] * f[:, 1]) + qj[:, 2] * f[:, 2]) + qj[:, 3] * f[:, 3]
-        sw = torch.where(dot < 0, -we, we)
-        aq = torch.where(live[:, None], aq + sw[:, None] * qj, aq)
-    Ws = torch.where(any_, W, torch.ones_like(W))
-    out = {"means": torch.where(any_[:, None], mean + acc / Ws[:, None], mean)}
-    n2 = ((aq[:, 0] * aq[:, 0] + aq[:, 1] * aq[:, 1]) + aq[:, 2] * aq[:, 2]) + aq[:, 3] * aq[:, 3]
-    ok = (n2 > 0) & torch.isfinite(n2)
-    n2s = torch.where(ok, n2, torch.ones_like(n2))
-    qb = torch.where(ok[:, None], aq * (1.0 / torch.sqrt(n2s))[:, None], f)
-    bw, bx, by, bz = qb[:, 0], qb[:, 1], qb[:, 2], qb[:, 3]
-    if rest.get("quats") is not None:
-        r = rest["quats"].to(dtype)
-        rw, rx, ry, rz = r[:, 0], r[:, 1], r[:, 2], r[:, 3]
-        q = torch.stack([((bw * rw - bx * rx) - by * ry) - bz * rz, ((bw * rx + bx * rw) + by * rz) - bz * ry,
-                         ((bw * ry - bx * rz) + by * rw) + bz * rx, ((bw * rz + bx * ry) - by * rx) + bz * rw], dim=1)
-        out["quats"] = torch.where(any_[:, None], q, r)
-    else:
-        c = rest["covariances"].to(dtype)
-        Rb = torch.stack([torch.stack([1.0 - 2.0 * (by * by + bz * bz), 2.0 * (bx * by - bw * bz), 2.0 * (bx * bz + bw * by)], dim=1),
-                          torch.stack([2.0 * (bx * by + bw * bz), 1.0 - 2.0 * (bx * bx + bz * bz), 2.0 * (by * bz - bw * bx)], dim=1),
-                          torch.stack([2.0 * (bx * bz - bw * by), 2.0 * (by * bz + bw * bx), 1.0 - 2.0 * (bx * bx + by * by)], dim=1)], dim=1)
-        S = torch.stack([torch.stack([c[:, 0], c[:, 1], c[:, 2]], dim=1), torch.stack([c[:, 1], c[:, 3], c[:, 4]], dim=1),
-                         torch.stack([c[:, 2], c[:, 4], c[:, 5]], dim=1)], dim=1)
-        Tm = torch.stack([torch.stack([(Rb[:, i, 0] * S[:, 0, j] + Rb[:, i, 1] * S[:, 1, j]) + Rb[:, i, 2] * S[:, 2, j] for j in range(3)], dim=1)
-                          for i in range(3)], dim=1)
-        o = lambda i, j: (Tm[:, i, 0] * Rb[:, j, 0] + Tm[:, i, 1] * Rb[:, j, 1]) + Tm[:, i, 2] * Rb[:, j, 2]
-        cov = torch.stack([o(0, 0), o(0, 1), o(0, 2), o(1, 1), o(1, 2), o(2, 2)], dim=1)
-        out["covariances"] = torch.where(any_[:, None], cov, c)
-    return out
-
-
 def live_rows(indices, weights, m: int) -> np.ndarray:
     """[N] bool: the Gaussian has a live entry under ``m`` nodes."""
     idx, w = np.asarray(indices), np.asarray(weights)
@@ -108,7 +50,7 @@ def rest_grad_ref(rest, indices, weights, node_Rt, d_means=None, d_orient=None, 
     leaf = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32))).to(dtype).requires_grad_(True)
     P = {"means": leaf(rest["means"]), key: leaf(rest[key])}
     m = np.asarray(node_Rt).reshape(-1, 3, 4).shape[0]
-    out = deform_torch_rest(P, idx, w, torch.from_numpy(np.ascontiguousarray(np.asarray(node_Rt, np.float32).reshape(-1, 3, 4))), dtype)
+    out = deform_torch(P, idx, w, torch.from_numpy(np.ascontiguousarray(np.asarray(node_Rt, np.float32).reshape(-1, 3, 4))), dtype)
     loss = torch.zeros((), dtype=dtype)
     given = []
     for k, d in (("means", d_means), (key, d_orient)):
@@ -267,7 +209,7 @@ def dynamic_case() -> dict:
 
 
 class DynRefRenderer:
-    """The rasterizer's methods ``fit_dynamic_scene`` uses, on the float64 references: ``deform_torch_rest`` bends, grad_ref renders and
+    """The rasterizer's methods ``fit_dynamic_scene`` uses, on the float64 references: ``deform_torch`` bends, grad_ref renders and
     differentiates, ``rest_grad_ref``'s function and ``skin_grad_ref``'s are the adjoints, fit_ref steps.  The state is the REST scene."""
     covariance_form = "quats"
     has_skin = True
@@ -294,7 +236,7 @@ class DynRefRenderer:
         """The deformed means and quats (tensors) of rest tensors ``P`` under the current transforms."""
         if self.T is None:
             return dict(means=P["means"], quats=P["quats"])
-        return deform_torch_rest(P, self.c["indices"], self.c["weights"], torch.from_numpy(self.T.astype(np.float64)), torch.float64)
+        return deform_torch(P, self.c["indices"], self.c["weights"], torch.from_numpy(self.T.astype(np.float64)), torch.float64)
 
     def read_scene(self):
         x = self.S["x"]
@@ -344,7 +286,7 @@ class DynRefRenderer:
         x = self.S["x"]
         rest = dict(means=torch.from_numpy(x["means"]), quats=torch.from_numpy(x["quats"]))
         G = torch.from_numpy(self.T.astype(np.float64)).requires_grad_(True)
-        bent = deform_torch_rest(rest, self.c["indices"], self.c["weights"], G, torch.float64)
+        bent = deform_torch(rest, self.c["indices"], self.c["weights"], G, torch.float64)
         sum((bent[k] * grads[k].double()).sum() for k in ("means", "quats") if grads.get(k) is not None).backward()
         return G.grad
 
