@@ -19,6 +19,8 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._picture_fit import adam_scalars, device_level, pyramid_level, squared_colour_pass, twist_adam
+
 ORTHONORMAL_TOL = 1e-4   # |R^T R - I| a checked node transform may have, per entry
 
 
@@ -235,12 +237,8 @@ def _twist_step(T, dT, g, m1, m2, it: int, per: int, step):
     """One Adam step (0-based ``it`` of ``per``) of every node's se(3) twist about the node's current position, the step falling to a
     twentieth over ``per`` steps: ``(T, m1, m2)`` after it.  ``T``, ``dT [M,3,4]``, ``g [M,3]`` the rest nodes, ``m1``, ``m2 [M,6]``."""
     piv = np.einsum("mab,mb->ma", T[:, :, :3], g) + T[:, :, 3]   # where every node is now
-    tw = twist_gradient_batch(dT, T, piv)
-    m1 = 0.9 * m1 + 0.1 * tw
-    m2 = 0.999 * m2 + 0.001 * tw * tw
-    hat = (m1 / (1 - 0.9 ** (it + 1))) / (np.sqrt(m2 / (1 - 0.999 ** (it + 1))) + 1e-12)
-    decay = 0.05 ** (it / max(1, per - 1))
-    E = se3_exp_batch(-np.concatenate([step[0] * decay * hat[:, :3], step[1] * decay * hat[:, 3:]], axis=1))
+    xi, m1, m2 = twist_adam(twist_gradient_batch(dT, T, piv), m1, m2, it, per, step)
+    E = se3_exp_batch(xi)
     # about the pivot: x -> E (x - p) + p
     Rn = E[:, :3, :3] @ T[:, :, :3]
     tn = np.einsum("mab,mb->ma", E[:, :3, :3], T[:, :, 3] - piv) + E[:, :3, 3] + piv
@@ -342,14 +340,51 @@ class NodeOptimizer:
             d_reg = self._d_reg
         if d_transforms is None and d_reg is None:
             raise ValueError("NodeOptimizer.step: no gradient: d_transforms is None and the rigidity term is off")
-        decay = 0.05 ** (it / max(1, per - 1))   # (the expressions of _twist_step: the same doubles)
+        decay, c1, c2 = adam_scalars(it, per)   # (the doubles of _twist_step's rule)
         self.r.node_twist_step(self.nodes, self.transforms64, self.m1, self.m2, self.transforms, d_transforms, d_reg, w,
-                               lr=(step[0] * decay, step[1] * decay), c1=1 - 0.9 ** (it + 1), c2=1 - 0.999 ** (it + 1))
+                               lr=(step[0] * decay, step[1] * decay), c1=c1, c2=c2)
         return value
 
     def read(self) -> np.ndarray:
         """The transforms as float64 numpy ``[M,3,4]``.  Blocking."""
         return self.transforms64.cpu().numpy()
+
+
+class _HostNodes:
+    """``NodeOptimizer``'s members on the host, for the fitting loops: the node transforms ``transforms64 [M,3,4]`` and their Adam moments
+    as float64 numpy, a step ``rigidity`` + ``_twist_step``.  The rigidity term runs over the host's own neighbour search, made once."""
+
+    def __init__(self, nodes, transforms):
+        self.nodes = np.asarray(nodes, np.float64).reshape(-1, 3)
+        self.table = _neighbour_table(self.nodes, 6)
+        self.transforms64 = np.asarray(transforms, np.float64)
+        self.reset_moments()
+
+    @property
+    def transforms(self) -> np.ndarray:
+        """What ``Rasterizer.deform`` takes: contiguous float32, checked there."""
+        return np.ascontiguousarray(self.transforms64.astype(np.float32))
+
+    def reset_moments(self) -> None:
+        self.m1, self.m2 = np.zeros((self.nodes.shape[0], 6)), np.zeros((self.nodes.shape[0], 6))
+
+    def rigidity(self):
+        return rigidity(self.nodes, self.transforms64, table=self.table)
+
+    def step(self, d_transforms, it: int, per: int, step, rigidity_weight: float):
+        """``NodeOptimizer.step`` from ``d_transforms [M,3,4]``, read back where it is a device tensor: returns the rigidity value at the
+        transforms the step started from, a float (exact 0 with a weight of 0)."""
+        import torch
+        dT = torch.as_tensor(d_transforms).double().cpu().numpy().reshape(self.transforms64.shape)
+        value = 0.0
+        if rigidity_weight > 0.0:
+            value, d_reg = self.rigidity()
+            dT = dT + rigidity_weight * d_reg
+        self.transforms64, self.m1, self.m2 = _twist_step(self.transforms64, dT, self.nodes, self.m1, self.m2, it, per, step)
+        return value
+
+    def read(self) -> np.ndarray:
+        return self.transforms64
 
 
 @dataclass
@@ -373,27 +408,24 @@ def fit_node_transforms(r, images, viewmats, Ks, W: int, H: int, nodes, iters: i
     left-multiplies the node's transform about the node's CURRENT position ``R_i g_i + t_i``, coarse to fine over ``factors`` with the step
     (``step``: radians, scene units) falling to a twentieth over each level.  The loss is the mean squared colour difference over ``masks
     [C,H,W]`` averaged over the views, plus ``rigidity_weight * rigidity(nodes, T)``.  Every step is ``r.deform(T)``, one ``render`` +
-    ``prechain`` + ``render_backward(out=acc)`` per view, ONE ``deform_backward(acc)``, one ``[M,12]`` read-back and the twist update in
-    float64 numpy, vectorised over the nodes -- a host update meant for node counts in the hundreds, not for tens of thousands.  ``start
-    [M,3,4]``: where to begin (None: the identity, the rest pose).  ``r`` is left deformed at the result.  ``loss_and_grad(T [M,3,4], V, K,
-    w, h, target, mask) -> (loss, d_T [M,3,4])`` replaces the renderer for one view (tests run the same optimiser on a CPU reference;
-    ``r`` may then be None).
+    ``prechain`` + ``render_backward(out=acc)`` per view into one reused accumulator, ONE ``deform_backward(acc)`` and the stepper's
+    ``step``; the losses stay device scalars and come back as one stack at the end.  ``start [M,3,4]``: where to begin (None: the
+    identity, the rest pose).  ``r`` is left deformed at the result.  ``loss_and_grad(T [M,3,4], V, K, w, h, target, mask) -> (loss, d_T
+    [M,3,4])`` replaces the renderer for one view (tests run the same optimiser on a CPU reference; ``r`` may then be None).
 
     ``rigidity_weight``: the default was chosen on the CPU recovery case of the tests (a bent sheet under a 3x3 node grid, two views): of
     the weights 0, 0.003, 0.01, 0.03 and 0.1 tried there it ends closest to the true deformed means (0.29 of the start after 60 iterations,
     against 0.34 without the term and 0.39 at 0.1).  The colour loss starts at 2e-3 there: scale the weight with the loss of your scene.
 
-    ``optimizer``: ``"host"`` is the loop above.  ``"device"`` runs the same schedule -- the same ``factors`` and steps per level, moments
-    reset per level, the same loss -- through a ``NodeOptimizer``: the rigidity term and the twist update are two HIP kernels on float64
-    state, ``deform`` reads the transforms where they are, the mask sums and intrinsics are formed once per level, the per-view losses
-    stay device scalars and the gradient accumulator is reused, so nothing is read back between the first iteration and the last; the
-    history comes back as one stack at the end.  Its rigidity term runs over ``Rasterizer.knn_points``' neighbour table (see
+    ``optimizer`` chooses the stepper of that one loop.  ``"host"``: one ``[M,12]`` read-back per step, then ``rigidity`` and the twist
+    update in float64 numpy, vectorised over the nodes -- meant for node counts in the hundreds, not for tens of thousands.  ``"device"``:
+    a ``NodeOptimizer`` -- the two are HIP kernels on float64 state and ``deform`` reads the transforms where they are, so nothing is read
+    back between the first iteration and the last.  Its rigidity term runs over ``Rasterizer.knn_points``' neighbour table (see
     ``rigidity``).  ``"device"`` with ``loss_and_grad`` is refused: that is the CPU reference's door.
 
     Not fitted: skin weights, node positions; stretch and shear (the twist keeps every transform rigid).  The rest parameters are
     ``fit_dynamic_scene``'s."""
     import torch
-    import torch.nn.functional as Fn
     from .rasterizer import _host
     if optimizer not in ("host", "device"):
         raise ValueError(f"fit_node_transforms: optimizer must be 'host' or 'device', got {optimizer!r}")
@@ -422,104 +454,34 @@ def fit_node_transforms(r, images, viewmats, Ks, W: int, H: int, nodes, iters: i
     if loss_and_grad is None and not getattr(r, "has_skin", False):
         raise ValueError("fit_node_transforms: no skin is bound to the rasterizer: bind_skin(nodes) first")
     key = None if loss_and_grad is not None else ("quats" if r.covariance_form == "quats" else "covariances")
-
-    def evaluate(T, Kcs, w, h, targets, tms):
-        """(loss, d_T [M,3,4]): the colour term averaged over the views plus the rigidity term."""
-        if loss_and_grad is not None:
-            parts = [loss_and_grad(T, Vs[v], Kcs[v], w, h, targets[v], tms[v]) for v in range(C)]
-            total, dT = sum(p[0] for p in parts) / C, sum(np.asarray(p[1], np.float64).reshape(M, 3, 4) for p in parts) / C
-        else:
-            from .autograd import prechain
-            r.deform(np.ascontiguousarray(T.astype(np.float32)))
-            acc, total = None, 0.0
-            for v in range(C):
-                V32, K32 = Vs[v].astype(np.float32), Kcs[v].astype(np.float32)
-                out = r.render(V32, K32, w, h, background)
-                rgb, alpha, depth = out["rgb"].clone(), out["alpha"].clone(), out["depth"].clone()
-                t, k = targets[v].to(rgb.device), tms[v].to(rgb.device)
-                scale = 1.0 / (3.0 * float(torch.clamp(k.sum(), min=1.0)) * C)
-                diff = k[..., None] * (rgb - t)
-                total += float((diff * (rgb - t)).sum()) * scale
-                g_acc, g_a, g_z = prechain(rgb, alpha, depth, background, 2.0 * scale * diff, None, None)
-                acc = r.render_backward(V32, K32, w, h, g_acc, g_a, g_z, want=("means", key), out=acc)
-            dT = r.deform_backward(acc).double().cpu().numpy()
-        if rigidity_weight > 0.0:
-            val, dreg = rigidity(g, T)
-            total, dT = total + rigidity_weight * val, dT + rigidity_weight * dreg
-        return total, dT
-
-    res = NodeFit(T, float("nan"))
     per = max(1, int(iters) // max(1, len(factors)))
-    opt = NodeOptimizer(r, g, transforms=T) if optimizer == "device" else None
-    acc, losses, levels = {}, [], []   # (device mode: the reused accumulator, the losses as device scalars, their levels)
+    opt = NodeOptimizer(r, g, transforms=T) if optimizer == "device" else _HostNodes(g, T)
+    acc, losses, levels = {}, [], []   # the views' summed gradients (made by the first pass, reused), the losses as they come, their levels
+    level = (lambda f: pyramid_level(imgs, ms, K0s, W, H, f)) if loss_and_grad is not None else (lambda f: device_level(imgs, ms, Vs, K0s, W, H, f, r.device))
 
-    def enqueue(cams, w, h, targets, tms, scales):
-        """The device form of ``evaluate``, one ``level``'s arguments: ``deform`` and the views' frames and backward passes, summed into
-        ``acc``; returns the colour loss as a float64 device scalar."""
-        from .autograd import prechain
+    def evaluate(lv, grad=True):
+        """(colour loss averaged over the views, d_T [M,3,4]) at the stepper's transforms and one ``level``; with the renderer both stay on the device."""
+        if loss_and_grad is not None:
+            w, h, targets, tms, Kcs = lv
+            parts = [loss_and_grad(opt.transforms64, Vs[v], Kcs[v], w, h, targets[v], tms[v]) for v in range(C)]
+            return sum(p[0] for p in parts) / C, sum(np.asarray(p[1], np.float64).reshape(M, 3, 4) for p in parts) / C
         r.deform(opt.transforms)
-        for a in acc.values():
-            a.zero_()
-        total = None
-        for v in range(C):
-            out = r.render(cams[v][0], cams[v][1], w, h, background)
-            rgb, alpha, depth = out["rgb"].clone(), out["alpha"].clone(), out["depth"].clone()
-            err = rgb - targets[v]
-            diff = tms[v][..., None] * err
-            value = (diff * err).sum().to(torch.float64) * scales[v]
-            total = value if total is None else total + value
-            g_acc, g_a, g_z = prechain(rgb, alpha, depth, background, 2.0 * scales[v] * diff, None, None)
-            acc.update(r.render_backward(cams[v][0], cams[v][1], w, h, g_acc, g_a, g_z, want=("means", key), out=acc))
-        return total
+        colour = squared_colour_pass(r, *lv, background, acc, want=("means", key))
+        return colour, r.deform_backward(acc) if grad else None
 
-    def level(f):
-        """One level, formed once: the cameras, the size, the targets and masks on the device, and the views' ``1 / (3 sum(mask) C)``."""
-        w, h, targets, tms, Kcs = at_factor(f)
-        scales = [1.0 / (3.0 * float(torch.clamp(tms[v].sum(), min=1.0)) * C) for v in range(C)]   # (host tensors: nothing waits)
-        cams = [(Vs[v].astype(np.float32), Kcs[v].astype(np.float32)) for v in range(C)]
-        return cams, w, h, targets.to(r.device), tms.to(r.device), scales
-
-    def at_factor(f):
-        """One level of the pyramid: its size, the targets and masks at it (host tensors) and the cameras' intrinsics."""
-        w, h = max(1, W // f), max(1, H // f)
-        if f == 1:
-            targets, tms = imgs, ms
-        else:
-            # area average of the masked images, renormalised by the mask's coverage
-            cover = Fn.interpolate(ms[:, None], size=(h, w), mode="area")[:, 0]
-            targets = Fn.interpolate((imgs * ms[..., None]).permute(0, 3, 1, 2), size=(h, w), mode="area").permute(0, 2, 3, 1) / torch.clamp(cover, min=1e-6)[..., None]
-            tms = (cover > 0.5).to(torch.float32)
-        Kcs = K0s.copy()
-        Kcs[:, 0] *= w / W
-        Kcs[:, 1] *= h / H
-        return w, h, targets, tms, Kcs
-
-    if opt is not None:
-        for f in factors:
-            lv = level(f)
-            opt.reset_moments()
-            for it in range(per):
-                colour = enqueue(*lv)
-                reg = opt.step(r.deform_backward(acc), it, per, step, rigidity_weight)
-                losses.append(colour + rigidity_weight * reg)
-                levels.append(int(f))
-        colour = enqueue(*level(1))   # (leaves r deformed at the result)
-        losses.append(colour + rigidity_weight * opt.rigidity()[0] if rigidity_weight > 0.0 else colour)
-        levels.append(1)
-        res.history = list(zip(levels, torch.stack(losses).cpu().tolist()))   # (the one read-back of the run, beside the transforms)
-        res.transforms, res.loss = opt.read(), res.history[-1][1]
-        return res
     for f in factors:
-        w, h, targets, tms, Kcs = at_factor(f)
-        m1, m2 = np.zeros((M, 6)), np.zeros((M, 6))
+        lv = level(f)
+        opt.reset_moments()
         for it in range(per):
-            loss, dT = evaluate(T, Kcs, w, h, targets, tms)
-            res.history.append((int(f), loss))
-            T, m1, m2 = _twist_step(T, dT, g, m1, m2, it, per, step)
-    res.transforms = T
-    res.loss = evaluate(T, K0s, W, H, imgs, ms)[0]   # (leaves r deformed at the result)
-    res.history.append((1, res.loss))
-    return res
+            colour, dT = evaluate(lv)
+            reg = opt.step(dT, it, per, step, rigidity_weight)
+            losses.append(colour + rigidity_weight * reg)
+            levels.append(int(f))
+    colour = evaluate(level(1), grad=False)[0]   # (leaves r deformed at the result)
+    losses.append(colour + rigidity_weight * opt.rigidity()[0] if rigidity_weight > 0.0 else colour)
+    levels.append(1)
+    history = torch.stack([torch.as_tensor(x, dtype=torch.float64) for x in losses]).cpu().tolist()   # (the one read-back of the losses)
+    return NodeFit(opt.read(), history[-1], list(zip(levels, history)))
 
 
 # ---- the rest scene from pictures of its motion (DESIGN.md 3, "Deformation": the adjoint to the rest arrays) -------------------------------
@@ -560,7 +522,6 @@ def fit_dynamic_scene(r, frames, nodes, what: Sequence[str] = ("means", "colors"
     rasterizer's own kernels: refused with ``renderer=``."""
     import torch
     from . import fit as _fit
-    from .autograd import prechain
     from .rasterizer import _host
     R = r if renderer is None else renderer
     who = "fit_dynamic_scene"
@@ -617,58 +578,39 @@ def fit_dynamic_scene(r, frames, nodes, what: Sequence[str] = ("means", "colors"
     if bound_only and passed:
         sk = R.read_skin()
         bound = ((sk["indices"] >= 0) & (sk["indices"] < M) & (sk["weights"] > 0)).any(dim=1)
-    m1, m2 = np.zeros((S, M, 6)), np.zeros((S, M, 6))
-    opts, held = {}, {}   # the device optimisers of the time steps that move, and the device transforms of those that do not
-    if optimizer == "device":
-        for t in range(S):
-            if fit_transforms and t > 0:
-                opts[t] = NodeOptimizer(R, g, transforms=T[t], graph=opts.get(1))
-            else:
-                held[t] = torch.from_numpy(check_node_transforms(T[t])).to(R.device)
+    opts, held = {}, {}   # the steppers of the time steps that move, and the float32 transforms of those that do not
+    for t in range(S):
+        if fit_transforms and t > 0:
+            opts[t] = NodeOptimizer(R, g, transforms=T[t], graph=opts.get(1)) if optimizer == "device" else _HostNodes(g, T[t])
+        else:
+            held[t] = np.ascontiguousarray(T[t].astype(np.float32))
+            if optimizer == "device":
+                held[t] = torch.from_numpy(check_node_transforms(held[t])).to(R.device)
     losses = []
     for it in range(1, n_iters + 1):
         rest_acc, shared, total, dTs = {}, {}, None, {}
         for t, (V, K, img, masks, cache) in enumerate(views):
-            R.deform(opts[t].transforms if t in opts else held[t] if t in held else np.ascontiguousarray(T[t].astype(np.float32)))
+            R.deform(opts[t].transforms if t in opts else held[t])
             acc_t = dict(shared)
             C = V.shape[0]
             for v in range(C):
-                out = R.render(V[v], K[v], W, H, bg)
-                rgb = out["rgb"]
-                if v not in cache:   # a view's target and mask move to the frames' device once
-                    tm = None if masks is None else torch.as_tensor(masks[v]).to(rgb.device)
-                    cache[v] = (torch.as_tensor(img[v]).to(device=rgb.device, dtype=rgb.dtype).reshape(rgb.shape), tm)
-                if loss is None:
-                    value, g_rgb = lg(rgb, *cache[v])
-                    g_acc, g_a, _ = prechain(rgb, out["alpha"], out["depth"], bg, g_rgb / C, None, None)
-                else:
-                    pl = R.photometric_loss(rgb, cache[v][0], mask=cache[v][1], alpha=out["alpha"], background=bg, lambda_dssim=lambda_dssim)
-                    value, g_acc, g_a = pl["loss"], pl["g_rgb"] / C, pl["g_alpha"] / C
-                acc_t = R.render_backward(V[v], K[v], W, H, g_acc, g_a, None, out=acc_t, want=want)
+                value, acc_t, _ = _fit._view_pass(R, V[v], K[v], W, H, bg, cache, v, img, masks, loss, lg, lambda_dssim, C, out=acc_t, want=want)
                 value = torch.as_tensor(value).detach().reshape(()) / (C * S)
                 total = value if total is None else total + value
             shared = {k: acc_t[k] for k in passed}
             if moved:
                 rest_acc = R.deform_backward_rest({k: acc_t[k] for k in moved}, out=rest_acc, bound_only=bound_only)
-            if fit_transforms and t > 0:
+            if t in opts:
                 dTs[t] = R.deform_backward({k: acc_t[k] for k in ("means", orient)})
         if bound is not None:
             for k, a in shared.items():
                 a.mul_(bound.reshape((-1,) + (1,) * (a.dim() - 1)).to(a.dtype))
         R.adam_step(dict(shared, **rest_acc), _fit.step_rates(rates, what, extent, it, n_iters), it, visible_only=visible_only, rest=True)
         for t, d in dTs.items():   # (the host's read-backs wait for the step's work once, here)
-            if t in opts:
-                val = opts[t].step(d, it - 1, n_iters, step, rigidity_weight)
-                total = total + rigidity_weight * val / S
-                continue
-            dT = torch.as_tensor(d).double().cpu().numpy().reshape(M, 3, 4)
-            if rigidity_weight > 0.0:
-                val, dreg = rigidity(g, T[t])
-                total, dT = total + rigidity_weight * val / S, dT + rigidity_weight * dreg
-            T[t], m1[t], m2[t] = _twist_step(T[t], dT, g, m1[t], m2[t], it - 1, n_iters, step)
+            total = total + rigidity_weight * opts[t].step(d, it - 1, n_iters, step, rigidity_weight) / S
         losses.append(total)
     for t, opt in opts.items():
         T[t] = opt.read()
     R.deform(np.ascontiguousarray(T[S - 1].astype(np.float32)))
-    history = [float(x) for x in torch.stack([torch.as_tensor(x, dtype=torch.float64).cpu() for x in losses])] if losses else []
+    history = torch.stack([torch.as_tensor(x, dtype=torch.float64) for x in losses]).cpu().tolist() if losses else []   # (the one read-back of the losses)
     return DynamicFit(history=history, transforms=T, steps=len(history))

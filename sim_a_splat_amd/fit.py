@@ -170,6 +170,27 @@ def _pack_views(who: str, viewmats, Ks, images, masks) -> Tuple[np.ndarray, np.n
     return V, K
 
 
+def _view_pass(R, V, K, W: int, H: int, bg, cache: Dict[int, tuple], v: int, images, masks, loss: Optional[str], lg: Callable,
+               lambda_dssim: float, share: int, out, want):
+    """One view of a step, for ``fit_scene`` and ``deform.fit_dynamic_scene``: the frame, the loss against view ``v``'s target and mask
+    (moved to the frame's device once, kept in ``cache``) -- ``lg`` and the chain to the raw accumulators in torch, or with ``loss`` the
+    renderer's ``photometric_loss`` -- and ``render_backward(out=out, want=want)`` of its gradient divided by ``share`` (the views that share
+    a step's weight; 1: as it is).  Returns ``(the loss, the accumulated gradients, the frame)``."""
+    frame = R.render(V, K, W, H, bg)
+    rgb = frame["rgb"]
+    if v not in cache:
+        tm = None if masks is None else torch.as_tensor(masks[v]).to(rgb.device)
+        cache[v] = (torch.as_tensor(images[v]).to(device=rgb.device, dtype=rgb.dtype).reshape(rgb.shape), tm)
+    weigh = (lambda g: g) if share == 1 else (lambda g: g / share)
+    if loss is None:
+        value, g_rgb = lg(rgb, *cache[v])
+        g_acc, g_a, _ = prechain(rgb, frame["alpha"], frame["depth"], bg, weigh(g_rgb), None, None)
+    else:
+        pl = R.photometric_loss(rgb, cache[v][0], mask=cache[v][1], alpha=frame["alpha"], background=bg, lambda_dssim=lambda_dssim)
+        value, g_acc, g_a = pl["loss"], weigh(pl["g_rgb"]), weigh(pl["g_alpha"])
+    return value, R.render_backward(V, K, W, H, g_acc, g_a, None, out=out, want=want), frame
+
+
 def mean_loss(r, viewmats, Ks, W: int, H: int, images, masks=None, background: Sequence[float] = (0.0, 0.0, 0.0),
               loss_and_grad: Optional[Callable] = None, loss: Optional[str] = None, lambda_dssim: float = 0.2) -> float:
     """The loss ``fit_scene`` descends, averaged over ALL the views, for the scene as it stands in ``r`` (or a stand-in)."""
@@ -273,18 +294,7 @@ def fit_scene(r, viewmats, Ks, W: int, H: int, images, iters: int, what: Sequenc
         total = None
         for v in rng.choice(C, size=per, replace=False):
             v = int(v)
-            out = R.render(V[v], K[v], W, H, bg)
-            rgb = out["rgb"]
-            if v not in targets:   # a view's target and mask move to the frames' device once
-                tm = None if masks is None else torch.as_tensor(masks[v]).to(rgb.device)
-                targets[v] = (torch.as_tensor(images[v]).to(device=rgb.device, dtype=rgb.dtype).reshape(rgb.shape), tm)
-            if loss is None:
-                value, g_rgb = lg(rgb, *targets[v])
-                g_acc, g_a, _ = prechain(rgb, out["alpha"], out["depth"], bg, g_rgb, None, None)
-            else:
-                pl = R.photometric_loss(rgb, targets[v][0], mask=targets[v][1], alpha=out["alpha"], background=bg, lambda_dssim=lambda_dssim)
-                value, g_acc, g_a = pl["loss"], pl["g_rgb"], pl["g_alpha"]
-            acc = R.render_backward(V[v], K[v], W, H, g_acc, g_a, None, out=acc, want=what)
+            value, acc, _ = _view_pass(R, V[v], K[v], W, H, bg, targets, v, images, masks, loss, lg, lambda_dssim, 1, out=acc, want=what)
             if stats is not None:
                 R.density_accumulate(W, H, stats)
             value = torch.as_tensor(value).detach().reshape(())

@@ -227,7 +227,7 @@ def refine_camera_pose(r, image, V0, K, W: int, H: int, iters: int = 300, mask=N
     ``autograd.render_differentiable``; ``loss_and_grad(V, K, W, H, target, mask) -> (loss, d_viewmat [3,4])`` replaces the renderer
     (tests run the same optimiser on a CPU reference).  What the renderer does not differentiate -- K, decisions -- stays fixed."""
     import torch
-    import torch.nn.functional as Fn
+    from ._picture_fit import pyramid_level, twist_adam
     dev = getattr(r, "device", "cpu")
     img = torch.as_tensor(np.asarray(_host(image), np.float32)).reshape(H, W, 3)
     m = torch.ones((H, W), dtype=torch.float32) if mask is None else (torch.as_tensor(np.asarray(_host(mask))) != 0).to(torch.float32).reshape(H, W)
@@ -255,28 +255,15 @@ def refine_camera_pose(r, image, V0, K, W: int, H: int, iters: int = 300, mask=N
     res = PoseRefinement(V, float("nan"))
     per = max(1, int(iters) // max(1, len(factors)))
     for f in factors:
-        w, h = max(1, W // f), max(1, H // f)
-        if f == 1:
-            target, tm = img, m
-        else:
-            # area average of the masked image, renormalised by the mask's coverage
-            cover = Fn.interpolate(m[None, None], size=(h, w), mode="area")[0, 0]
-            target = Fn.interpolate((img * m[..., None]).permute(2, 0, 1)[None], size=(h, w), mode="area")[0].permute(1, 2, 0) / torch.clamp(cover, min=1e-6)[..., None]
-            tm = (cover > 0.5).to(torch.float32)
-        Kc = K0.copy()
-        Kc[0] *= w / W
-        Kc[1] *= h / H
-        m1, m2 = np.zeros(6), np.zeros(6)
+        w, h, targets, tms, Kcs = pyramid_level(img[None], m[None], K0[None], W, H, f)
+        m1, m2 = np.zeros((1, 6)), np.zeros((1, 6))
         for it in range(per):
-            loss, dV = evaluate(V, Kc, w, h, target, tm)
+            loss, dV = evaluate(V, Kcs[0], w, h, targets[0], tms[0])
             res.history.append((int(f), loss))
             g = twist_gradient(dV, V)
             g[:3] += np.cross(g[3:], Tp[:3, 3])   # the same twist about the pivot
-            m1 = 0.9 * m1 + 0.1 * g
-            m2 = 0.999 * m2 + 0.001 * g * g
-            hat = (m1 / (1 - 0.9 ** (it + 1))) / (np.sqrt(m2 / (1 - 0.999 ** (it + 1))) + 1e-12)
-            decay = 0.05 ** (it / max(1, per - 1))
-            V = Tp @ se3_exp(-np.concatenate([step[0] * decay * hat[:3], step[1] * decay * hat[3:]])) @ Tpi @ V
+            xi, m1, m2 = twist_adam(g[None], m1, m2, it, per, step)
+            V = Tp @ se3_exp(xi[0]) @ Tpi @ V
     res.viewmat = V
     res.loss = evaluate(V, K0, W, H, img, m)[0]
     res.history.append((1, res.loss))
@@ -304,8 +291,7 @@ def refine_group_poses(r, images, viewmats, Ks, W: int, H: int, groups: Sequence
     left at the result.  ``loss_and_grad(poses [G,3,4], V, K, w, h, target, mask) -> (loss, d_poses [n_sel,3,4])`` replaces the
     renderer for one view (tests run the same optimiser on a CPU reference)."""
     import torch
-    import torch.nn.functional as Fn
-    dev = getattr(r, "device", "cpu")
+    from ._picture_fit import device_level, pyramid_level, squared_colour_pass, twist_adam
     sel = [int(g) for g in groups]
     n_sel = len(sel)
     Vs = np.asarray(_host(viewmats), np.float64).reshape(-1, 4, 4)
@@ -319,64 +305,43 @@ def refine_group_poses(r, images, viewmats, Ks, W: int, H: int, groups: Sequence
     if n_sel < 1 or len(set(sel)) != n_sel or min(sel) < 0 or max(sel) >= poses.shape[0]:
         raise ValueError(f"refine_group_poses: groups must name distinct ids below {poses.shape[0]}, got {tuple(groups)}")
     piv = poses[sel, :, 3].copy() if pivots is None else np.asarray(_host(pivots), np.float64).reshape(n_sel, 3).copy()
+    acc = {}   # the pose gradients of the views, summed: made by the first pass, reused by the others
+    level = (lambda f: pyramid_level(imgs, ms, K0s, W, H, f)) if loss_and_grad is not None else (lambda f: device_level(imgs, ms, Vs, K0s, W, H, f, r.device))
 
-    def evaluate(G, Kcs, w, h, targets, tms):
-        """(loss, d_poses [n_sel,3,4]) averaged over the views."""
+    def evaluate(G, lv):
+        """(loss, d_poses [n_sel,3,4]) averaged over the views, at one ``level``."""
         if loss_and_grad is not None:
+            w, h, targets, tms, Kcs = lv
             parts = [loss_and_grad(G, Vs[v], Kcs[v], w, h, targets[v], tms[v]) for v in range(C)]
             return sum(p[0] for p in parts) / C, sum(np.asarray(p[1], np.float64).reshape(n_sel, 3, 4) for p in parts) / C
-        from .autograd import prechain
-        acc, total = None, 0.0
-        for v in range(C):
-            V32, K32 = Vs[v].astype(np.float32), Kcs[v].astype(np.float32)
-            out = r.render(V32, K32, w, h, background)
-            rgb, alpha, depth = out["rgb"].clone(), out["alpha"].clone(), out["depth"].clone()
-            t, k = targets[v].to(rgb.device), tms[v].to(rgb.device)
-            scale = 1.0 / (3.0 * float(torch.clamp(k.sum(), min=1.0)) * C)
-            diff = k[..., None] * (rgb - t)
-            total += float((diff * (rgb - t)).sum()) * scale
-            g_acc, g_a, g_z = prechain(rgb, alpha, depth, background, 2.0 * scale * diff, None, None)
-            acc = r.render_backward(V32, K32, w, h, g_acc, g_a, g_z, want=("group_poses",), pose_groups=sel, out=acc)
-        return total, acc["group_poses"].double().cpu().numpy()
+        total = squared_colour_pass(r, *lv, background, acc, want=("group_poses",), pose_groups=sel)
+        return float(total), acc["group_poses"].double().cpu().numpy()   # (the evaluation waits here, once)
 
     res = GroupPoseRefinement(poses, float("nan"))
     per = max(1, int(iters) // max(1, len(factors)))
     for f in factors:
-        w, h = max(1, W // f), max(1, H // f)
-        if f == 1:
-            targets, tms = imgs, ms
-        else:
-            # area average of the masked images, renormalised by the mask's coverage
-            cover = Fn.interpolate(ms[:, None], size=(h, w), mode="area")[:, 0]
-            targets = Fn.interpolate((imgs * ms[..., None]).permute(0, 3, 1, 2), size=(h, w), mode="area").permute(0, 2, 3, 1) / torch.clamp(cover, min=1e-6)[..., None]
-            tms = (cover > 0.5).to(torch.float32)
-        Kcs = K0s.copy()
-        Kcs[:, 0] *= w / W
-        Kcs[:, 1] *= h / H
+        lv = level(f)
         m1, m2 = np.zeros((n_sel, 6)), np.zeros((n_sel, 6))
         for it in range(per):
             r.set_group_poses(poses.reshape(-1, 12).astype(np.float32))
-            loss, dG = evaluate(poses, Kcs, w, h, targets, tms)
+            loss, dG = evaluate(poses, lv)
             res.history.append((int(f), loss))
-            decay = 0.05 ** (it / max(1, per - 1))
+            G4 = np.tile(np.eye(4), (n_sel, 1, 1))
+            G4[:, :3] = poses[sel]
+            tw = np.stack([twist_gradient(dG[q], G4[q]) for q in range(n_sel)])
+            tw[:, :3] += np.cross(tw[:, 3:], piv)   # the same twists about the pivots
+            xi, m1, m2 = twist_adam(tw, m1, m2, it, per, step)
             for q, g in enumerate(sel):
-                G4 = np.eye(4)
-                G4[:3] = poses[g]
-                tw = twist_gradient(dG[q], G4)
-                tw[:3] += np.cross(tw[3:], piv[q])   # the same twist about the pivot
-                m1[q] = 0.9 * m1[q] + 0.1 * tw
-                m2[q] = 0.999 * m2[q] + 0.001 * tw * tw
-                hat = (m1[q] / (1 - 0.9 ** (it + 1))) / (np.sqrt(m2[q] / (1 - 0.999 ** (it + 1))) + 1e-12)
                 Tp = np.eye(4)
                 Tp[:3, 3] = piv[q]
                 Tpi = np.eye(4)
                 Tpi[:3, 3] = -piv[q]
-                M = Tp @ se3_exp(-np.concatenate([step[0] * decay * hat[:3], step[1] * decay * hat[3:]])) @ Tpi
-                poses[g] = (M @ G4)[:3]
+                M = Tp @ se3_exp(xi[q]) @ Tpi
+                poses[g] = (M @ G4[q])[:3]
                 piv[q] = (M @ np.append(piv[q], 1.0))[:3]   # the pivot is a point of the group: it moves with it
     r.set_group_poses(poses.reshape(-1, 12).astype(np.float32))
     res.poses = poses
-    res.loss = evaluate(poses, K0s, W, H, imgs, ms)[0]
+    res.loss = evaluate(poses, level(1))[0]
     res.history.append((1, res.loss))
     return res
 
