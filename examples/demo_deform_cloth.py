@@ -2,13 +2,16 @@
 """A sheet of Gaussians that bends: a deformable splat group beside a static scene, driven as a physics engine would drive it -- by the
 moving positions of a few control nodes ("Deformation").
 
-    python examples/demo_deform_cloth.py [--steps 200] [--sheet 40000] [--scene 100000] [--save frame.png]
+    python examples/demo_deform_cloth.py [--steps 200] [--sheet 40000] [--scene 100000] [--driver host|device] [--save frame.png]
 
 The sheet (a 1 x 1 square of flat Gaussians in its own group) is bound to an 8 x 8 node grid; every step a travelling wave moves the nodes,
 ``deform.transforms_from_positions`` turns the positions into rigid per-node transforms, ``SplatScene.deform`` moves the resident Gaussians
 in place, and a frame comes through the Door-B path (``get_render``).  Printed: the step time (transforms on the host + deform + frame),
 and the largest distance between the deformed means and the analytic wave surface -- a measurement of THIS scene: 64 nodes and a blend of
-four of them follow a wave of this length that closely, no more."""
+four of them follow a wave of this length that closely, no more.
+
+``--driver device``: the node positions are formed on the GPU (as a simulator that keeps its state there would hand them over) and
+``SplatScene.deform_positions`` -- ``deform.NodeDriver``, one HIP kernel -- takes the place of the host's fits: nothing is read back."""
 from __future__ import annotations
 
 import argparse
@@ -63,6 +66,7 @@ def main():
     ap.add_argument("--scene", type=int, default=100_000)
     ap.add_argument("--width", type=int, default=256)
     ap.add_argument("--height", type=int, default=256)
+    ap.add_argument("--driver", choices=("host", "device"), default="host", help="where the node positions become transforms")
     ap.add_argument("--save", default="", help="write the last frame as a PNG (needs PIL)")
     a = ap.parse_args()
 
@@ -77,11 +81,19 @@ def main():
     rest = scene._raster.read_scene()["means"].cpu().numpy()[a.scene:]
     times, worst = [], 0.0
     frame = None
+    if a.driver == "device":
+        import torch
+        nodes_dev = torch.from_numpy(nodes).to(scene._raster.device)
     for step in range(a.steps):
         t0 = time.perf_counter()
-        moved = nodes.astype(np.float64)
-        moved[:, 2] = wave(moved[:, 0], step)
-        scene.deform(deform.transforms_from_positions(nodes, moved, neighbours=6))
+        if a.driver == "device":
+            moved = nodes_dev.clone()
+            moved[:, 2] = AMPLITUDE * torch.sin(2.0 * np.pi * (nodes_dev[:, 0] / WAVELENGTH - SPEED * step))
+            scene.deform_positions(moved)
+        else:
+            moved = nodes.astype(np.float64)
+            moved[:, 2] = wave(moved[:, 0], step)
+            scene.deform(deform.transforms_from_positions(nodes, moved, neighbours=6))
         frame = scene.get_render(a.height, a.width, **cam)
         times.append((time.perf_counter() - t0) * 1e3)
         if step % 25 == 0 or step == a.steps - 1:   # the measurement reads the scene back: outside the timed part
@@ -89,7 +101,7 @@ def main():
             # distance to the wave surface z = wave(x), along z at the deformed x (the surface's slope is at most 0.42)
             worst = max(worst, float(np.abs(now[:, 2] - wave(now[:, 0], step)).max()))
     t = np.array(times[min(10, len(times) - 1):])
-    print(f"step (transforms on the host + deform + {a.width} x {a.height} frame): median {np.median(t):.3f} ms, [{t.min():.3f}..{t.max():.3f}] over {t.size} steps")
+    print(f"step (transforms on the {a.driver} + deform + {a.width} x {a.height} frame): median {np.median(t):.3f} ms, [{t.min():.3f}..{t.max():.3f}] over {t.size} steps")
     print(f"largest |z - wave(x)| of a deformed mean over the sampled steps: {worst:.4f} (amplitude {AMPLITUDE}, wavelength {WAVELENGTH}, node spacing {1 / 7:.3f}; "
           f"the sheet's means at rest spread {float(np.abs(rest[:, 2]).max()):.4f} from their plane)")
     if a.save:

@@ -946,6 +946,31 @@ int sas_nodes_twist_step(sas_ctx *ctx, int64_t m, const float *nodes, const floa
                          double weight64, double *Rt64, double *m1, double *m2, float *Rt32_out, const sas_node_step_config *cfg,
                          void *stream);
 
+/*
+ * The node driver on the device ("Deformation": the node driver): the rigid rows [R | t] of every node from the node POSITIONS a
+ * physics engine publishes -- what deform.transforms_from_positions computes on the host -- so that positions -> transforms -> sas_scene_deform
+ * -> frame stays on the device.  Scene-free, DEVICE arrays, only ENQUEUES on `stream`, no atomics, no scratch: the same inputs give the same bits.
+ *
+ * sas_nodes_fit_rigid -- nodes [m,3] float32 the rest positions, moved [steps,m,3] float32 their positions in `steps` >= 1 time steps (a
+ * recorded trajectory is one launch), nb [m,kn] int32 (kn 0..8) sas_knn_points' table of the rest nodes.  One lane per (step, node), binary64,
+ * only + - * / and sqrt, every loop of a fixed length (a poisoned input costs what a clean one costs):
+ *   members  node i itself, then nb[i] in slot order; an entry outside [0, m) is ignored, and so is a member whose moved position has a
+ *            non-finite coordinate.  If node i's OWN moved position is not finite the lane writes [I | 0].
+ *   S        = sum (a - ca)(b - cb)^T over the members in that order, ca / cb the centroids of their rest / moved positions
+ *   N        Horn's symmetric 4x4 matrix of S; all four eigenpairs by 14 cyclic Jacobi sweeps (a fixed count: csrc/sas_internal.h)
+ *   q        (1,0,0,0) projected onto the span of the eigenvectors whose eigenvalue is within 1e-9 (times the largest |eigenvalue|) of the
+ *            top one, normalised.  One rule for every case: the top eigenvector with q_w >= 0 for a neighbourhood of full rank; of all
+ *            optimal rotations the one of LEAST angle for a collinear one (two nodes, a rope); the identity for S = 0 (kn = 0, one node, all
+ *            members coincident).  A projection with a squared norm below 1e-12 is an exact half turn: the top eigenvector as it is.
+ *   R, t     R of the unit quaternion -- always a proper rotation, there is no determinant to correct -- and t = moved_i - R rest_i: the
+ *            node lands on its moved position.
+ * Rt64_out_or_null [steps,m,3,4] double and Rt32_out [steps,m,3,4] float32 = the double rounded once, both WRITTEN.  Not represented: member
+ * weights, pinned nodes, stretch and shear.
+ * SAS_ERR_INVALID for m outside 1..65536, steps < 1 or steps * m > 2^30, kn out of range, or a missing array (nb may be NULL with kn == 0).
+ */
+int sas_nodes_fit_rigid(sas_ctx *ctx, int steps, int64_t m, const float *nodes, const float *moved, int kn, const int32_t *nb,
+                        double *Rt64_out_or_null, float *Rt32_out, void *stream);
+
 /* sas_render_batch_host from camera POSES: n_views camera-to-world poses (wxyz [n,4], position [n,3], float64, OpenCV
  * axes: what client.get_render(height, width, wxyz, position) takes, splat_env_wrapper.py:148-157) and one vertical
  * field of view; the view matrices and intrinsics are those of sas_camera_matrices. */

@@ -37,6 +37,7 @@ SAS_SKIN_LDS_BYTES = 16384   # node records the deformation kernel stages in LDS
 SAS_SKIN_GRAD_LDS_BYTES = 131072   # per-node sums the deformation's adjoint keeps in LDS at most: the SAS_SKIN_GRAD_LDS budget's default (csrc/sas_internal.h)
 SAS_KNN_RING_LIMIT = 4  # rings of cells its grid search visits before a point goes to the brute-force kernel (csrc/sas_internal.h)
 SAS_NODES_MAX_K = 8   # neighbours per node sas_nodes_rigidity takes at most (csrc/sas_internal.h)
+SAS_NODES_FIT_MAX_LANES = 1 << 30   # (step, node) pairs sas_nodes_fit_rigid takes at most (csrc/sas_internal.h)
 SAS_MAX_POSE_GRAD_GROUPS = 32   # groups whose pose gradient one sas_render_backward_poses call forms
 
 STAGE_NAMES = ("project", "scan", "scatter", "sort", "blend", "tail", "total")
@@ -44,7 +45,7 @@ STAT_NAMES = ("n_visible", "n_isect", "max_tile_len", "capacity", "regrows", "wi
 
 # every symbol include/sim_a_splat_amd.h declares
 EXPORTS = (
-    "sas_create", "sas_destroy", "sas_scene_upload", "sas_set_group_poses", "sas_set_link_constants", "sas_set_link_poses", "sas_get_group_poses", "sas_link_attached_frame", "sas_link_group_poses", "sas_attached_frame", "sas_camera_matrices", "sas_render_cameras_host", "sas_render", "sas_render_rgbd", "sas_scene_features", "sas_render_features", "sas_scene_meshes", "sas_scene_mesh_features", "sas_scene_mesh_vertex_attributes", "sas_query_meshes", "sas_match_points", "sas_sample_points", "sas_fuse_depth", "sas_render_batch", "sas_render_batch_host", "sas_render_batch_posed", "sas_render_batch_host_posed", "sas_render_batch_labels", "sas_render_batch_labels_posed", "sas_lift_labels", "sas_lift_features", "sas_render_backward_screen", "sas_render_backward", "sas_render_backward_poses", "sas_scene_adam_step", "sas_scene_adam_reset", "sas_density_accumulate", "sas_scene_densify", "sas_scene_densify_times", "sas_scene_reset_opacity", "sas_scene_mcmc_noise", "sas_scene_mcmc_refine", "sas_photometric_loss", "sas_scene_read", "sas_storage_order", "sas_scene_order", "sas_knn_points", "sas_knn_last_counts", "sas_knn_cross", "sas_scene_skin", "sas_scene_skin_read", "sas_scene_deform", "sas_scene_deform_backward", "sas_scene_deform_backward_rest", "sas_scene_adam_step_rest", "sas_nodes_rigidity", "sas_nodes_twist_step", "sas_wait", "sas_frames_completed",
+    "sas_create", "sas_destroy", "sas_scene_upload", "sas_set_group_poses", "sas_set_link_constants", "sas_set_link_poses", "sas_get_group_poses", "sas_link_attached_frame", "sas_link_group_poses", "sas_attached_frame", "sas_camera_matrices", "sas_render_cameras_host", "sas_render", "sas_render_rgbd", "sas_scene_features", "sas_render_features", "sas_scene_meshes", "sas_scene_mesh_features", "sas_scene_mesh_vertex_attributes", "sas_query_meshes", "sas_match_points", "sas_sample_points", "sas_fuse_depth", "sas_render_batch", "sas_render_batch_host", "sas_render_batch_posed", "sas_render_batch_host_posed", "sas_render_batch_labels", "sas_render_batch_labels_posed", "sas_lift_labels", "sas_lift_features", "sas_render_backward_screen", "sas_render_backward", "sas_render_backward_poses", "sas_scene_adam_step", "sas_scene_adam_reset", "sas_density_accumulate", "sas_scene_densify", "sas_scene_densify_times", "sas_scene_reset_opacity", "sas_scene_mcmc_noise", "sas_scene_mcmc_refine", "sas_photometric_loss", "sas_scene_read", "sas_storage_order", "sas_scene_order", "sas_knn_points", "sas_knn_last_counts", "sas_knn_cross", "sas_scene_skin", "sas_scene_skin_read", "sas_scene_deform", "sas_scene_deform_backward", "sas_scene_deform_backward_rest", "sas_scene_adam_step_rest", "sas_nodes_rigidity", "sas_nodes_twist_step", "sas_nodes_fit_rigid", "sas_wait", "sas_frames_completed",
     "sas_last_error", "sas_stage_times", "sas_stage_time_means", "sas_frame_stats", "sas_read_projection", "sas_read_tile_lists",
     "sas_version",
 )
@@ -163,6 +164,7 @@ def lib() -> ctypes.CDLL:
     L.sas_scene_adam_step_rest.argtypes = L.sas_scene_adam_step.argtypes
     L.sas_nodes_rigidity.argtypes = [vp, i64, vp, vp, ci, vp, vp, vp, vp, vp, vp]
     L.sas_nodes_twist_step.argtypes = [vp, i64, vp, vp, vp, cd, vp, vp, vp, vp, ctypes.POINTER(NodeStepConfig), vp]
+    L.sas_nodes_fit_rigid.argtypes = [vp, ci, i64, vp, vp, ci, vp, vp, vp, vp]
     L.sas_wait.argtypes = [vp]
     L.sas_frames_completed.argtypes = [vp, vp, vp]
     L.sas_last_error.argtypes = [vp]

@@ -7,6 +7,7 @@ hipcc cross-compiles without a GPU.  -ffp-contract=off is part of the arithmetic
 """
 from __future__ import annotations
 
+import hashlib
 import os
 import shutil
 import subprocess
@@ -32,6 +33,30 @@ def hipcc_path() -> str:
 
 def up_to_date() -> bool:
     return LIB.exists() and all(LIB.stat().st_mtime >= d.stat().st_mtime for d in DEPS)
+
+
+BOUNDS_LIB = PKG.parent / "variants" / "lib_bounds.so"
+BOUNDS_FLAGS = ("-DSAS_DEBUG_BOUNDS",)
+
+
+def source_stamp(extra_flags=()) -> str:
+    """What a variant was built from: a digest of every source and header, the flags and the compiler options."""
+    h = hashlib.sha256(" ".join([OPT_LEVEL, ARCH, os.environ.get("SAS_HIPCC_FLAGS", ""), *extra_flags]).encode())
+    for d in DEPS:
+        h.update(d.read_bytes())
+    return h.hexdigest()
+
+
+def bounds_variant() -> Path:
+    """``variants/lib_bounds.so``, the bounds-checked build (-DSAS_DEBUG_BOUNDS) of THESE sources: built unless the stamp beside it says
+    that it was built from them already (the sources' contents, not their times: a copied tree keeps no times)."""
+    stamp = BOUNDS_LIB.with_suffix(".stamp")
+    want = source_stamp(BOUNDS_FLAGS)
+    if not (BOUNDS_LIB.exists() and stamp.exists() and stamp.read_text().strip() == want):
+        BOUNDS_LIB.parent.mkdir(exist_ok=True)
+        build(force=True, out=BOUNDS_LIB, extra_flags=BOUNDS_FLAGS)
+        stamp.write_text(want + "\n")
+    return BOUNDS_LIB
 
 
 def build(force: bool = False, verbose: bool = False, out: Path = None, extra_flags=()) -> Path:

@@ -3177,6 +3177,26 @@ int sas_nodes_twist_step(sas_ctx *c, int64_t m, const float *nodes, const float 
     return SAS_OK;
 }
 
+// Every node's rigid [R | t] from moved node positions (k_nodes_fit_rigid), scene-free, device arrays, binary64: one launch on the caller's
+// stream, no scratch, nothing is waited for.
+int sas_nodes_fit_rigid(sas_ctx *c, int steps, int64_t m, const float *nodes, const float *moved, int kn, const int32_t *nb, double *Rt64_out_or_null,
+                        float *Rt32_out, void *stream)
+{
+    const char *who = "sas_nodes_fit_rigid";
+    if (!c) return SAS_ERR_INVALID;
+    if (m < 1 || m > SAS_KNN_CROSS_MAX_NODES) return fail(c, SAS_ERR_INVALID, "%s: m=%lld out of [1,%d]", who, (long long)m, SAS_KNN_CROSS_MAX_NODES);
+    if (steps < 1 || (int64_t)steps * m > SAS_NODES_FIT_MAX_LANES)
+        return fail(c, SAS_ERR_INVALID, "%s: steps=%d out of range (steps >= 1, steps * m <= %d)", who, steps, SAS_NODES_FIT_MAX_LANES);
+    if (kn < 0 || kn > SAS_NODES_MAX_K) return fail(c, SAS_ERR_INVALID, "%s: kn=%d out of [0,%d]", who, kn, SAS_NODES_MAX_K);
+    if (!nodes || !moved || !Rt32_out) return fail(c, SAS_ERR_INVALID, "%s: nodes, moved and Rt32_out are required", who);
+    if (kn > 0 && !nb) return fail(c, SAS_ERR_INVALID, "%s: nb is required with kn > 0", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const SasNodesFit q{nodes, moved, nb, steps, (int)m, kn, Rt64_out_or_null, Rt32_out};
+    sas_launch_nodes_fit((hipStream_t)stream, q);
+    HIP_TRY(c, hipGetLastError());
+    return SAS_OK;
+}
+
 // Bind, replace or clear the skin (k_skin_bind).  Host work: validation, the planes' allocations, the rest snapshot as device copies on the
 // caller's stream, one launch, one event.
 int sas_scene_skin(sas_ctx *c, int k, const int32_t *indices, const float *weights, void *stream)

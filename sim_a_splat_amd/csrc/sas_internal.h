@@ -894,3 +894,23 @@ struct SasNodesStep {
     double lr_rot, lr_trans, beta1, beta2, gain1, gain2, c1, c2, eps;   // sas_node_step_config
 };
 void sas_launch_nodes_step(hipStream_t st, const SasNodesStep &q);
+// The node driver (sas_nodes_fit_rigid): every node's rigid [R | t] from moved node positions.
+#define SAS_NODES_FIT_GAP 1e-9            // eigenvalues of Horn's matrix within this times the largest |eigenvalue| of the top one span the quaternion's space
+#define SAS_NODES_FIT_HALF_TURN 1e-12     // a projection of (1,0,0,0) onto that space with a squared norm below this is an exact half turn
+// Cyclic Jacobi sweeps, FIXED.  Counted on the CPU by tests/tools/node_fit_ref.py (sweeps_needed): the smallest count after which the largest
+// off-diagonal entry stays within four roundings (4 * 2^-53) of the largest |eigenvalue| is 12 over the kit's 22 668 matrices and 11 over 100 000
+// drawn ones (full rank, rank two, rank one, a repeated singular value, scales 1e-20 .. 1e20).  Both counts belong to rank-one matrices (two
+// members, a rope): the double top eigenvalue's pair converges linearly there, halving per sweep from up to 2.5e-13 of the scale -- an entry
+// between two eigenvectors that are both in the quaternion's span, so it never reaches the result.  Every matrix of another kind is at 1e-14
+// after five sweeps and at an exact zero after eight.  Plus two: 14.
+#define SAS_NODES_FIT_SWEEPS 14
+#define SAS_NODES_FIT_MAX_LANES (1 << 30)  // steps * m at most: one lane each, in 256-lane workgroups of one grid
+struct SasNodesFit {
+    const float *nodes;      // [m,3] rest positions
+    const float *moved;      // [steps,m,3]
+    const int *nb;           // [m,kn] neighbour table; an entry outside [0, m) is ignored
+    int steps, m, kn;
+    double *Rt64;            // [steps,m,12] written, or nullptr
+    float *Rt32;             // [steps,m,12] written: float(Rt64)
+};
+void sas_launch_nodes_fit(hipStream_t st, const SasNodesFit &q);

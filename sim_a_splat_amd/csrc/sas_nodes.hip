@@ -1,5 +1,5 @@
-// sas_nodes.hip -- the node optimiser of the deformable splats on the device (sas_nodes_rigidity, sas_nodes_twist_step; DESIGN.md 3,
-// "Deformation": the node optimiser), hand-written for gfx950 (CDNA4, wave64).  The state -- every node's rows [R | t], the two Adam moments of its
+// sas_nodes.hip -- the node optimiser and the node driver of the deformable splats on the device (sas_nodes_rigidity, sas_nodes_twist_step,
+// sas_nodes_fit_rigid; DESIGN.md 3, "Deformation": the node optimiser, the node driver), hand-written for gfx950 (CDNA4, wave64).  The state -- every node's rows [R | t], the two Adam moments of its
 // twist, the rigidity gradient -- is BINARY64: a rotation that is left-multiplied hundreds of times in binary32 drifts away from R^T R = I, and
 // sas_scene_deform does not check device arrays.  The float32 rows sas_scene_deform reads are the state rounded ONCE (sas_mcmc.hip's precedent).
 // One lane per node, 256-lane workgroups, plain vector loads and stores, no atomics: the same inputs give the same bits.  M <= 65 536 lanes of
@@ -17,8 +17,17 @@
 //                      the twist gradient about p (sum_c A[:,c] x G[:,c] over the four columns, + G[:,3] x p); the two moments; hat = (m1 / c1) /
 //                      (sqrt(m2 / c2) + eps); xi = -(lr_rot hat_w, lr_trans hat_v); E = exp(xi) with the series branch below |w| = 1e-8;
 //                      R <- E_R R, t <- (E_R (t - p) + E_t) + p; Rt32 = float(Rt64).
-// Arithmetic: IEEE binary64, nothing fused, correctly rounded / and sqrt; sin and cos are the device library's.  tests/tools/node_opt_ref.py
-// restates both kernels.
+//   k_nodes_fit_rigid  deform.transforms_from_positions per (step, node), without an SVD: the members (the node, then its table entries in slot
+//                      order; an entry outside [0, m) or with a non-finite moved position is left out), their centroids, the cross-covariance
+//                      S = sum (a - ca)(b - cb)^T in member order, Horn's symmetric 4x4 matrix of S, SAS_NODES_FIT_SWEEPS cyclic Jacobi sweeps
+//                      for all four eigenpairs, and the quaternion = (1,0,0,0) projected onto the span of the eigenvectors whose eigenvalue
+//                      is within SAS_NODES_FIT_GAP of the top one, normalised: the top eigenvector with q_w >= 0 for a neighbourhood of full
+//                      rank, the LEAST rotation of all optimal ones for a collinear one, the identity for S = 0; a projection that vanishes
+//                      (an exact half turn) takes the top eigenvector as it is.  Always a proper rotation: there is no determinant to correct.
+//                      t = moved_i - R rest_i.  Every loop has a compile-time trip count and no branch depends on the data but the first
+//                      (the node's own moved position is not finite: [I | 0]), so a poisoned input costs what a clean one costs.
+// Arithmetic: IEEE binary64, nothing fused, correctly rounded / and sqrt; sin and cos are the device library's (k_nodes_fit_rigid uses
+// neither).  tests/tools/node_opt_ref.py restates the optimiser's kernels, tests/tools/node_fit_ref.py the driver's.
 #include "sas_device.h"
 
 #pragma clang fp contract(off)
@@ -220,6 +229,171 @@ __global__ __launch_bounds__(kThreads) void k_nodes_twist_step(const SasNodesSte
     }
 }
 
+DEV bool finite3(float x, float y, float z)
+{
+    const float big = 3.402823466e38f;
+    return fabsf(x) <= big && fabsf(y) <= big && fabsf(z) <= big;   // (false for NaN and for either infinity)
+}
+
+// One Jacobi rotation of the symmetric A about the pivot (P, Q), accumulated into the columns of V; node_fit_ref.jacobi's operations.
+template <int P, int Q>
+DEV void jacobi_turn(double (&A)[4][4], double (&V)[4][4])
+{
+    const double apq = A[P][Q], app = A[P][P], aqq = A[Q][Q];
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double sgn = theta >= 0.0 ? 1.0 : -1.0;
+    double t = sgn / (fabs(theta) + sqrt(theta * theta + 1.0));   // (a theta that overflowed: t = 0 by itself)
+    t = apq == 0.0 ? 0.0 : t;                                      // (an exactly zero pivot turns nothing)
+    const double c = 1.0 / sqrt(t * t + 1.0);
+    const double s = t * c;
+    A[P][P] = app - t * apq;
+    A[Q][Q] = aqq + t * apq;
+    A[P][Q] = A[Q][P] = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (r == P || r == Q) continue;
+        const double arp = A[r][P], arq = A[r][Q];
+        A[r][P] = A[P][r] = c * arp - s * arq;
+        A[r][Q] = A[Q][r] = s * arp + c * arq;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const double vrp = V[r][P], vrq = V[r][Q];
+        V[r][P] = c * vrp - s * vrq;
+        V[r][Q] = s * vrp + c * vrq;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_nodes_fit_rigid(const SasNodesFit q)
+{
+    const long long lanes = (long long)q.steps * q.m;
+    const long long lane = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (lane >= lanes || !SAS_IN(lane, lanes, 1607)) return;
+    const long long i = lane % q.m, base = lane - i;   // base: the step's first row of `moved`
+    const float *mv = q.moved + 3 * base;
+    const float px = mv[3 * i], py = mv[3 * i + 1], pz = mv[3 * i + 2];
+    double out[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    if (finite3(px, py, pz)) {
+        const double gx = (double)q.nodes[3 * i], gy = (double)q.nodes[3 * i + 1], gz = (double)q.nodes[3 * i + 2];
+        // the members: the node itself, then its table entries in slot order
+        int member[SAS_NODES_MAX_K];
+        double cnt = 1.0, ca[3] = {0.0 + gx, 0.0 + gy, 0.0 + gz}, cb[3] = {0.0 + (double)px, 0.0 + (double)py, 0.0 + (double)pz};   // (sums that begin at +0)
+#pragma unroll
+        for (int slot = 0; slot < SAS_NODES_MAX_K; ++slot) {
+            int j = -1;
+            if (slot < q.kn && SAS_IN(i * q.kn + slot, (long long)q.m * q.kn, 1608)) j = q.nb[i * q.kn + slot];
+            bool on = j >= 0 && j < q.m && SAS_IN(base + j, lanes, 1609);
+            const long long jj = on ? j : i;
+            const float bx = mv[3 * jj], by = mv[3 * jj + 1], bz = mv[3 * jj + 2];
+            on = on && finite3(bx, by, bz);
+            member[slot] = on ? j : -1;
+            cnt = cnt + (on ? 1.0 : 0.0);
+            ca[0] = ca[0] + (on ? (double)q.nodes[3 * jj] : 0.0);
+            ca[1] = ca[1] + (on ? (double)q.nodes[3 * jj + 1] : 0.0);
+            ca[2] = ca[2] + (on ? (double)q.nodes[3 * jj + 2] : 0.0);
+            cb[0] = cb[0] + (on ? (double)bx : 0.0);
+            cb[1] = cb[1] + (on ? (double)by : 0.0);
+            cb[2] = cb[2] + (on ? (double)bz : 0.0);
+        }
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            ca[u] = ca[u] / cnt;
+            cb[u] = cb[u] / cnt;
+        }
+        // S[u][v] = sum (a - ca)_u (b - cb)_v, in member order
+        double S[3][3];
+        {
+            const double da[3] = {gx - ca[0], gy - ca[1], gz - ca[2]}, db[3] = {(double)px - cb[0], (double)py - cb[1], (double)pz - cb[2]};
+#pragma unroll
+            for (int u = 0; u < 3; ++u)
+#pragma unroll
+                for (int v = 0; v < 3; ++v) S[u][v] = 0.0 + da[u] * db[v];
+        }
+#pragma unroll
+        for (int slot = 0; slot < SAS_NODES_MAX_K; ++slot) {
+            const bool on = member[slot] >= 0;
+            const long long jj = on ? member[slot] : i;
+            const double da[3] = {(double)q.nodes[3 * jj] - ca[0], (double)q.nodes[3 * jj + 1] - ca[1], (double)q.nodes[3 * jj + 2] - ca[2]};
+            const double db[3] = {(double)mv[3 * jj] - cb[0], (double)mv[3 * jj + 1] - cb[1], (double)mv[3 * jj + 2] - cb[2]};
+#pragma unroll
+            for (int u = 0; u < 3; ++u)
+#pragma unroll
+                for (int v = 0; v < 3; ++v) S[u][v] = S[u][v] + (on ? da[u] * db[v] : 0.0);
+        }
+        // Horn's matrix: its top eigenvector is the quaternion (w, x, y, z) of the best rotation
+        double A[4][4], V[4][4];
+        A[0][0] = (S[0][0] + S[1][1]) + S[2][2];
+        A[0][1] = S[1][2] - S[2][1];
+        A[0][2] = S[2][0] - S[0][2];
+        A[0][3] = S[0][1] - S[1][0];
+        A[1][1] = (S[0][0] - S[1][1]) - S[2][2];
+        A[1][2] = S[0][1] + S[1][0];
+        A[1][3] = S[2][0] + S[0][2];
+        A[2][2] = (S[1][1] - S[0][0]) - S[2][2];
+        A[2][3] = S[1][2] + S[2][1];
+        A[3][3] = (S[2][2] - S[0][0]) - S[1][1];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                if (b < a) A[a][b] = A[b][a];
+                V[a][b] = a == b ? 1.0 : 0.0;
+            }
+#pragma unroll 1
+        for (int sweep = 0; sweep < SAS_NODES_FIT_SWEEPS; ++sweep) {
+            jacobi_turn<0, 1>(A, V);
+            jacobi_turn<0, 2>(A, V);
+            jacobi_turn<0, 3>(A, V);
+            jacobi_turn<1, 2>(A, V);
+            jacobi_turn<1, 3>(A, V);
+            jacobi_turn<2, 3>(A, V);
+        }
+        // (1,0,0,0) projected onto the span of the top eigenvectors
+        const double l[4] = {A[0][0], A[1][1], A[2][2], A[3][3]};
+        const double t01 = l[0] > l[1] ? l[0] : l[1], t23 = l[2] > l[3] ? l[2] : l[3];
+        const double top = t01 > t23 ? t01 : t23;
+        const double s01 = fabs(l[0]) > fabs(l[1]) ? fabs(l[0]) : fabs(l[1]), s23 = fabs(l[2]) > fabs(l[3]) ? fabs(l[2]) : fabs(l[3]);
+        const double reach = SAS_NODES_FIT_GAP * (s01 > s23 ? s01 : s23);
+        double qt[4] = {0.0, 0.0, 0.0, 0.0}, first[4] = {0.0, 0.0, 0.0, 0.0};
+        bool taken = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double w = (top - l[k]) <= reach ? V[0][k] : 0.0;
+            const bool pick = l[k] == top && !taken;
+            taken = taken || pick;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                qt[r] = qt[r] + w * V[r][k];
+                first[r] = pick ? V[r][k] : first[r];
+            }
+        }
+        double n2 = ((qt[0] * qt[0] + qt[1] * qt[1]) + qt[2] * qt[2]) + qt[3] * qt[3];
+        const bool half = n2 < SAS_NODES_FIT_HALF_TURN;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) qt[r] = half ? first[r] : qt[r];
+        n2 = ((qt[0] * qt[0] + qt[1] * qt[1]) + qt[2] * qt[2]) + qt[3] * qt[3];
+        const double norm = sqrt(n2);
+        const double w = qt[0] / norm, x = qt[1] / norm, y = qt[2] / norm, z = qt[3] / norm;
+        out[0] = 1.0 - 2.0 * (y * y + z * z);
+        out[1] = 2.0 * (x * y - w * z);
+        out[2] = 2.0 * (x * z + w * y);
+        out[4] = 2.0 * (x * y + w * z);
+        out[5] = 1.0 - 2.0 * (x * x + z * z);
+        out[6] = 2.0 * (y * z - w * x);
+        out[8] = 2.0 * (x * z - w * y);
+        out[9] = 2.0 * (y * z + w * x);
+        out[10] = 1.0 - 2.0 * (x * x + y * y);
+        const double p[3] = {(double)px, (double)py, (double)pz};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) out[4 * a + 3] = p[a] - ((out[4 * a] * gx + out[4 * a + 1] * gy) + out[4 * a + 2] * gz);
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        if (q.Rt64) q.Rt64[12 * lane + k] = out[k];
+        q.Rt32[12 * lane + k] = (float)out[k];
+    }
+}
+
 }  // namespace
 
 SAS_BOUNDS_ACCESSOR(sas_debug_bounds_nodes)
@@ -235,4 +409,10 @@ void sas_launch_nodes_step(hipStream_t st, const SasNodesStep &q)
 {
     const int blocks = (q.m + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(k_nodes_twist_step, dim3(blocks), dim3(kThreads), 0, st, q);
+}
+
+void sas_launch_nodes_fit(hipStream_t st, const SasNodesFit &q)
+{
+    const long long lanes = (long long)q.steps * q.m;
+    hipLaunchKernelGGL(k_nodes_fit_rigid, dim3((unsigned)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, q);
 }

@@ -1,10 +1,12 @@
 """Host-side conveniences around the deformable splats ("Deformation"): where to put control nodes, and how to turn the
 moving vertices a physics engine publishes into the rigid per-node transforms ``Rasterizer.deform`` takes.  Plain numpy, float64 inside;
-nothing here touches the GPU but ``fit_node_transforms`` and ``fit_dynamic_scene``, through the rasterizer they are given.
+nothing here touches the GPU but ``NodeDriver``, ``NodeOptimizer``, ``fit_node_transforms`` and ``fit_dynamic_scene``, through the
+rasterizer they are given.
 
     nodes = grid_nodes(bounds, spacing)                  # or farthest_nodes(points, m)
     r.bind_skin(nodes, k=4)
-    r.deform(transforms_from_positions(nodes, moved_nodes))
+    r.deform(transforms_from_positions(nodes, moved_nodes))       # on the host; or, with the positions on the device:
+    driver = NodeDriver(r, nodes); driver.drive(moved_nodes)      # one HIP kernel in front of deform, nothing read back
 
 The other way round -- the node transforms from pictures -- is ``fit_node_transforms``: an optimiser around
 ``Rasterizer.render_backward`` and ``Rasterizer.deform_backward``, with ``rigidity`` as its regulariser; its twist update runs on the host
@@ -69,18 +71,25 @@ def kabsch(src, dst):
     return R, cb - R @ ca
 
 
-def transforms_from_positions(rest_nodes, moved_nodes, neighbours: int = 6) -> np.ndarray:
-    """Per-node rigid transforms ``[M,3,4]`` float32, rest -> current, from node POSITIONS alone: node i's ``[R | t]`` is the Kabsch fit
-    (float64) of itself and its ``neighbours`` nearest rest nodes onto their moved positions, re-centred so that it carries the node
-    exactly onto its moved position (``t = moved_i - R rest_i``).  A neighbourhood that does not span a plane and a line off it -- fewer
-    than three nodes, or all collinear -- leaves the rotation about its axis undetermined: the fit then returns the least rotation.
-    This is the bridge from a physics engine's moving vertices to ``Rasterizer.deform``."""
+def _fit_positions64(rest_nodes, moved_nodes, neighbours: int = 6, table=None) -> np.ndarray:
+    """``transforms_from_positions`` before its rounding to float32: ``[M,3,4]`` float64."""
     a = np.asarray(rest_nodes, np.float64).reshape(-1, 3)
     b = np.asarray(moved_nodes, np.float64).reshape(-1, 3)
     if a.shape != b.shape:
         raise ValueError(f"rest_nodes {a.shape} and moved_nodes {b.shape} differ in shape")
     M = a.shape[0]
     out = np.zeros((M, 3, 4), np.float64)
+    if table is not None:
+        nbs = np.asarray(table)
+        if nbs.ndim != 2 or nbs.shape[0] != M or nbs.dtype.kind not in "iu":
+            raise ValueError(f"transforms_from_positions: table must be an integer array [{M},k], got {nbs.dtype} {list(nbs.shape)}")
+        nbs = nbs.astype(np.int64)
+        for i in range(M):
+            nb = np.concatenate([[i], nbs[i][(nbs[i] >= 0) & (nbs[i] < M)]])
+            R = kabsch(a[nb], b[nb])[0] if nb.size >= 2 else np.eye(3)
+            out[i, :, :3] = R
+            out[i, :, 3] = b[i] - R @ a[i]
+        return out
     k = int(min(max(neighbours, 0), M - 1))
     d2 = ((a[:, None, :] - a[None, :, :]) ** 2).sum(axis=2) if M else np.zeros((0, 0))
     order = np.argsort(d2, axis=1, kind="stable")[:, :k + 1]   # (the node itself first: distance 0; ties to the lower index)
@@ -91,7 +100,23 @@ def transforms_from_positions(rest_nodes, moved_nodes, neighbours: int = 6) -> n
         R = kabsch(a[nb], b[nb])[0] if k >= 1 else np.eye(3)
         out[i, :, :3] = R
         out[i, :, 3] = b[i] - R @ a[i]
-    return np.ascontiguousarray(out.astype(np.float32))
+    return out
+
+
+def transforms_from_positions(rest_nodes, moved_nodes, neighbours: int = 6, table=None) -> np.ndarray:
+    """Per-node rigid transforms ``[M,3,4]`` float32, rest -> current, from node POSITIONS alone: node i's ``[R | t]`` is the Kabsch fit
+    (float64) of itself and its ``neighbours`` nearest rest nodes onto their moved positions, re-centred so that it carries the node
+    exactly onto its moved position (``t = moved_i - R rest_i``).  A neighbourhood that does not span a plane and a line off it -- fewer
+    than three nodes, or all collinear -- leaves the rotation about its axis undetermined: the fit here then maps the rest line onto the
+    moved one, but its twist about that line is whatever the SVD chose, not the least rotation (on drawn collinear neighbourhoods its angle
+    exceeds the least one by a median of 42 degrees); ``NodeDriver`` returns the least one.
+    This is the bridge from a physics engine's moving vertices to ``Rasterizer.deform``, on the host: an ``[M,M,3]`` table and ``M`` SVDs
+    per call.  ``NodeDriver`` is the same bridge on the device.
+
+    ``table [M,k]`` (integers; an entry outside ``[0, M)`` names no neighbour) takes the place of the neighbour search, ``neighbours`` is
+    then ignored: node i's members are itself and its live entries in slot order, as ``rigidity(table=)`` takes them (see there on how
+    ``Rasterizer.knn_points``' table can differ from the search here at equal distances)."""
+    return np.ascontiguousarray(_fit_positions64(rest_nodes, moved_nodes, neighbours, table).astype(np.float32))
 
 
 def check_node_transforms(node_transforms) -> np.ndarray:
@@ -348,6 +373,82 @@ class NodeOptimizer:
     def read(self) -> np.ndarray:
         """The transforms as float64 numpy ``[M,3,4]``.  Blocking."""
         return self.transforms64.cpu().numpy()
+
+
+class NodeDriver:
+    """``transforms_from_positions`` on the device, in front of ``Rasterizer.deform`` (sas_nodes_fit_rigid; DESIGN.md 3, "Deformation"): the
+    bridge from the node positions a simulator holds on the GPU to the deformed scene, without the host in between.  Device tensors it
+    owns: ``nodes [M,3]`` float32, ``table [M,k]`` int32 (None without neighbours) and ``transforms [M,3,4]`` float32, written by every
+    ``drive`` and read by ``r.deform`` where it is.
+
+    The table is ``r.knn_points(nodes, k=min(neighbours, M - 1))``, as ``NodeOptimizer``'s (``neighbours`` is 0..8).  ``graph``: a
+    ``NodeOptimizer`` or ``NodeDriver`` over the same nodes of the same rasterizer whose ``nodes`` and ``table`` are shared: ``knn_points``
+    runs once for both; ``neighbours`` is then the graph's, and ``nodes`` is only checked for its shape (None: not at all).
+    Every node's rotation is the best rigid fit of itself and its neighbours; a collinear neighbourhood (two nodes, a rope) gets the
+    LEAST rotation of all best ones, coincident members the identity.  A node whose moved position is not finite keeps ``[I | 0]`` and is
+    left out of its neighbours' fits.
+
+    Not provided: per-member weights; a simulator mesh with more vertices than nodes (index it before the call); a batch of environments
+    with different deformations; pinned nodes; stretch and shear."""
+
+    def __init__(self, r, nodes, neighbours: int = 6, graph=None):
+        import torch
+        from . import _capi
+        from .rasterizer import _host
+        self.r = r
+        if graph is not None:   # (``neighbours`` is the graph's then)
+            if graph.r is not r:
+                raise ValueError("NodeDriver: graph belongs to another rasterizer")
+            if nodes is not None and tuple(np.shape(_host(nodes))) != tuple(graph.nodes.shape):
+                raise ValueError(f"NodeDriver: graph is over {list(graph.nodes.shape)} nodes, nodes is {list(np.shape(_host(nodes)))}")
+            self.nodes, self.table = graph.nodes, graph.table
+        else:
+            g = np.ascontiguousarray(np.asarray(_host(nodes), np.float32))
+            if g.ndim != 2 or g.shape[1] != 3 or not 1 <= g.shape[0] <= _capi.SAS_KNN_CROSS_MAX_NODES:
+                raise ValueError(f"NodeDriver: nodes must be [M,3] with 1 <= M <= {_capi.SAS_KNN_CROSS_MAX_NODES}, got {list(g.shape)}")
+            if not np.isfinite(g).all():
+                raise ValueError("NodeDriver: nodes holds non-finite entries")
+            if not 0 <= int(neighbours) <= _capi.SAS_NODES_MAX_K:
+                raise ValueError(f"NodeDriver: neighbours={neighbours} out of [0, {_capi.SAS_NODES_MAX_K}]")
+            self.nodes = torch.from_numpy(g).to(r.device)
+            k = int(min(int(neighbours), g.shape[0] - 1))
+            self.table = r.knn_points(self.nodes, k)["index"] if k > 0 else None
+        M = int(self.nodes.shape[0])
+        self.transforms = torch.zeros((M, 3, 4), dtype=torch.float32, device=r.device)
+        self.transforms[:, 0, 0] = self.transforms[:, 1, 1] = self.transforms[:, 2, 2] = 1.0
+
+    @property
+    def m(self) -> int:
+        return int(self.nodes.shape[0])
+
+    @property
+    def k(self) -> int:
+        return 0 if self.table is None else int(self.table.shape[1])
+
+    def _moved(self, moved, steps_allowed: bool):
+        """``moved`` as a float32 device tensor: one on the device as it is, anything else checked for its shape and copied."""
+        import torch
+        M = self.m
+        if isinstance(moved, torch.Tensor) and moved.is_cuda:
+            return moved.detach()
+        a = np.ascontiguousarray(np.asarray(moved.detach().numpy() if isinstance(moved, torch.Tensor) else moved, np.float32))
+        if not (a.shape == (M, 3) or (steps_allowed and a.ndim == 3 and a.shape[0] >= 1 and a.shape[1:] == (M, 3))):
+            raise ValueError(f"NodeDriver: moved must be [{M},3]" + (f" or [S,{M},3]" if steps_allowed else "") + f", got {list(a.shape)}")
+        return torch.from_numpy(a).to(self.r.device)
+
+    def fit(self, moved):
+        """The transforms of ``moved [M,3]`` or ``[S,M,3]`` (``S`` time steps, one launch) without deforming anything: ``{"transforms",
+        "transforms64"}``, fresh float32 / float64 device tensors ``[M,3,4]`` or ``[S,M,3,4]``.  Only enqueues."""
+        return self.r.node_fit_rigid(self.nodes, self._moved(moved, True), self.table)
+
+    def drive(self, moved):
+        """Deform the skin bound to the rasterizer by the node positions ``moved [M,3]``: a float32 device tensor is read where it is,
+        unchecked; anything else is checked for its shape and copied (non-finite rows are allowed: the kernel's rule).  The fit goes into
+        ``self.transforms`` (reused, returned), then ``r.deform(self.transforms)``.  Two kernels enqueued on the current stream; nothing
+        blocks."""
+        self.r.node_fit_rigid(self.nodes, self._moved(moved, False), self.table, out=self.transforms, want64=False)
+        self.r.deform(self.transforms)
+        return self.transforms
 
 
 class _HostNodes:

@@ -1676,6 +1676,46 @@ class Rasterizer:
             self._check(rc, "sas_nodes_twist_step")
 
     @_locked
+    def node_fit_rigid(self, nodes: torch.Tensor, moved: torch.Tensor, table: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                       out64: Optional[torch.Tensor] = None, want64: bool = True) -> Dict[str, Optional[torch.Tensor]]:
+        """Every node's rigid ``[R | t]``, rest -> moved, from node POSITIONS on the device (sas_nodes_fit_rigid; DESIGN.md 3,
+        "Deformation"): what ``deform.transforms_from_positions(nodes, moved, table=table)`` computes, without the host.  Device tensors, read
+        where they are: ``nodes [M,3]`` float32, ``moved [M,3]`` or ``[S,M,3]`` float32 (``S`` time steps in one launch), ``table [M,kn]``
+        int32 (``0 <= kn <= 8``, ``knn_points``' table; an entry outside ``[0, M)`` is ignored; None: no neighbours, every rotation the
+        identity).  A member whose moved position is not finite is left out of its neighbours' fits; a node whose OWN moved position is not
+        finite gets ``[I | 0]``.  A collinear neighbourhood (two nodes, a rope) gets the LEAST rotation of all optimal ones.  Returns
+        ``transforms64`` (float64) and ``transforms`` (float32, the float64 rounded once: what ``deform`` takes), ``[M,3,4]`` or
+        ``[S,M,3,4]`` as ``moved`` is shaped; ``out`` / ``out64`` are the tensors to write them to.  ``want64=False``: the float64 rows are
+        not written (``transforms64`` is None).  No atomics: the same
+        inputs give the same bits.  Needs no scene.  Only enqueues, on the current stream."""
+        if not isinstance(nodes, torch.Tensor) or nodes.dim() != 2:
+            raise ValueError("nodes must be a float32 device tensor [M,3]")
+        m = int(nodes.shape[0])
+        if not 1 <= m <= _capi.SAS_KNN_CROSS_MAX_NODES:
+            raise ValueError(f"node_fit_rigid: m={m} out of [1, {_capi.SAS_KNN_CROSS_MAX_NODES}]")
+        if not isinstance(moved, torch.Tensor) or moved.dim() not in (2, 3):
+            raise ValueError(f"moved must be a float32 device tensor [{m},3] or [S,{m},3]")
+        lead = tuple(moved.shape[:-2])
+        steps = int(lead[0]) if lead else 1
+        if steps < 1 or steps * m > _capi.SAS_NODES_FIT_MAX_LANES:
+            raise ValueError(f"node_fit_rigid: {steps} time steps of {m} nodes: need 1 <= S and S * M <= {_capi.SAS_NODES_FIT_MAX_LANES}")
+        kn = 0 if table is None else int(table.shape[1]) if isinstance(table, torch.Tensor) and table.dim() == 2 else -1
+        if not 0 <= kn <= _capi.SAS_NODES_MAX_K:
+            raise ValueError(f"node_fit_rigid: table must be [M,kn] with 0 <= kn <= {_capi.SAS_NODES_MAX_K}")
+        g = self._node_array(nodes, torch.float32, (m, 3), "nodes")
+        b = self._node_array(moved, torch.float32, lead + (m, 3), "moved")
+        nb = self._node_array(table, torch.int32, (m, kn), "table") if kn > 0 else None
+        shape = lead + (m, 3, 4)
+        T32 = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else self._node_array(out, torch.float32, shape, "out")
+        T64 = None
+        if want64 or out64 is not None:
+            T64 = torch.empty(shape, dtype=torch.float64, device=self.device) if out64 is None else self._node_array(out64, torch.float64, shape, "out64")
+        rc = self._L.sas_nodes_fit_rigid(self._ctx, steps, m, _addr(g), _addr(b), kn, _addr(nb), _addr(T64), _addr(T32), self._stream())
+        if rc != 0:
+            self._check(rc, "sas_nodes_fit_rigid")
+        return {"transforms": T32, "transforms64": T64}
+
+    @_locked
     def read_order(self) -> torch.Tensor:
         """The resident scene's storage order (sas_scene_order): int32 ``[N]`` on the device, slot -> the caller's index, as
         ``storage_order(read_scene()["means"], group_id)`` gives it straight after an ``upload``, a ``densify`` or an ``mcmc_refine``.

@@ -119,6 +119,7 @@ class SplatScene:
         self.mesh_ambient, self.mesh_diffuse = 0.4, 0.6   # mesh shading ("Meshes"); set before the first render
         self.camera = _Camera()
         self._deformable = None   # (handle, nodes, bind_kw) of bind_deformable: bound again whenever the scene is uploaded again
+        self._driver = None       # the deform.NodeDriver of deform_positions, made on its first call; dropped by bind_deformable
 
     def _register(self, handle_class, name: str, wxyz, position):
         """(lock held)  A new handle on a pose row of its own, written into the block; the scene is uploaded again before the next frame."""
@@ -240,7 +241,7 @@ class SplatScene:
         with self.lock:
             if not isinstance(handle, GaussianSplatHandle) or isinstance(handle, MeshHandle) or handle._scene is not self:
                 raise ValueError("bind_deformable: a splat-group handle of this scene is required")
-            self._deformable = None
+            self._deformable = self._driver = None
             self._sync()
             res = self._raster.bind_skin(nodes, group=handle.index, **bind_kw)
             self._deformable = (handle, np.array(nodes, np.float32, copy=True), dict(bind_kw))
@@ -254,6 +255,21 @@ class SplatScene:
                 raise RuntimeError("bind_deformable first")
             self._sync()
             self._raster.deform(node_transforms)
+
+    def deform_positions(self, moved_nodes):
+        """``deform`` from node POSITIONS: ``moved_nodes [M,3]`` (the handle's local frame; a float32 device tensor is read where it is),
+        where the nodes of ``bind_deformable`` are now -- what a physics engine publishes.  A ``deform.NodeDriver`` over the stored nodes,
+        made by the first call and kept until the next ``bind_deformable``, fits every node's rigid transform on the device and deforms
+        the group; nothing is read back.  The handle's pose is applied on top, as for ``deform``.  Returns the transforms, the driver's
+        float32 device tensor ``[M,3,4]``."""
+        with self.lock:
+            if self._deformable is None:
+                raise RuntimeError("bind_deformable first")
+            self._sync()
+            if self._driver is None:
+                from .deform import NodeDriver
+                self._driver = NodeDriver(self._raster, self._deformable[1])
+            return self._driver.drive(moved_nodes)
 
     def fit_deformation(self, images, height: int, width: int, cam_poses, fov: Optional[float] = None, iters: int = 200, masks=None, **kw):
         """How is the deformable group bent, given these pictures: ``deform.fit_node_transforms`` on the nodes of ``bind_deformable``, in the
